@@ -3,10 +3,14 @@
 hot path on BASELINE.json configs[3]: 1920x1080, 1024 spp, the reference's 38-sphere
 Cornell-box-style room, depth 16.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either under a launcher -- python -m torch.distributed.run --nproc-per-node N ...
      bench.py --gpus N ... -- or plain `python bench.py --gpus N`, which starts its own ranks
      in a child torch.distributed.run, see launch_ranks)
+
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes the last timed
+frame (dump_outputs).  Everything that takes work of its own -- the CPU baseline and the parity blocks, the other
+configurations, the integrators, host_path / cli_host, assembly_check -- runs with --full only.
 
 One "step" = one full frame.  With N ranks the frame's 8x8 tiles are interleaved over the
 ranks (rank r renders tiles r, r+N, ...: no data-path collective), then the compact tile
@@ -15,7 +19,7 @@ work is fixed as N grows ("scaling": "strong").  Inputs (scene, camera) are resi
 before the timed region; the timed region is K x (render [+ gather] + untile), bracketed by
 barrier + synchronize, MAX over ranks.
 
-The JSON line also carries
+The JSON line also carries (every key from cpu_baseline on, phase_ms / ranks_seen / rank_kernel_ms excepted: --full only)
   roofline      fp64-VALU roofline of the render kernel (the binding roof of this branchy
                 fp64 path) from HIP-event kernel times measured here.
                 `achieved` counts SURVEY section 8d's ALGORITHMIC flops (what the reference's
@@ -832,6 +836,37 @@ def launch_ranks(n):
     return proc.returncode
 
 
+# ---- --dump-outputs: what the timed path computed, for comparing two builds output for output -----------------
+
+DUMP_BUDGET = 64_000_000   # bytes per dump, all files together
+
+
+def dump_outputs(out_dir, frame, frame8, counters, budget=DUMP_BUDGET):
+    """Write the last timed step's results as out_dir/<name>.npy: `frame` (H x W x 3 float32, the linear framebuffer),
+    `frame_u8` (the tonemapped bytes as float32) and `counters` (float64: rays, ray-bounces, intersection tests, samples of
+    one step).  A frame whose two arrays exceed `budget` is written as a fixed sample instead: the same pixels (seeded by
+    SEED and the frame size) every run, `frame` / `frame_u8` as n x 3 and their linear indices in `pixel_index` (float64).
+    -> the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    f = np.asarray(frame, dtype=np.float32)
+    f8 = np.asarray(frame8).astype(np.float32)
+    arrays = {"counters": np.asarray(counters, dtype=np.float64)}
+    n = f.size // 3
+    per_pixel = 2 * 3 * 4
+    room = budget - 4096                                      # .npy headers and the counters
+    if n * per_pixel <= room:
+        arrays["frame"], arrays["frame_u8"] = f, f8
+    else:
+        k = room // (per_pixel + 8)                           # + the float64 index of each sampled pixel
+        idx = np.sort(np.random.default_rng([SEED, n]).choice(n, size=k, replace=False))
+        arrays["pixel_index"] = idx.astype(np.float64)
+        arrays["frame"], arrays["frame_u8"] = f.reshape(-1, 3)[idx], f8.reshape(-1, 3)[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 # ---- main ------------------------------------------------------------------------------
 
 def main():
@@ -845,19 +880,24 @@ def main():
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--chunks", type=int, default=0, help="sample chunks per tile (0 = rt_hip_suggest_chunks)")
     ap.add_argument("--shard", type=str, default="", help="dev: render only rank R of a W-way partition, 'R/W', on this one GPU")
-    ap.add_argument("--cpu-tiles", type=int, default=2048, help="8x8 tiles of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--cpu-workers", type=int, default=0, help="processes of the CPU baseline (0 = the CPUs this process may use)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the per-configuration array")
+    ap.add_argument("--cpu-tiles", type=int, default=2048, help="--full: 8x8 tiles of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-workers", type=int, default=0, help="--full: processes of the CPU baseline (0 = the CPUs this process may use)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the per-configuration array")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the same-run parity blocks (the CPU baseline is still timed; its pixels are thrown away)")
+                    help="--full: skip the same-run parity blocks (the CPU baseline is still timed; its pixels are thrown away)")
     ap.add_argument("--c5-spp", type=int, default=0,
-                    help="spp of config 5 in the per-configuration array (0 = its own 4096: ~4 s a frame on one GPU)")
+                    help="--full: spp of config 5 in the per-configuration array (0 = its own 4096: ~4 s a frame on one GPU)")
     ap.add_argument("--integrators-only", action="store_true",
                     help="dev: only the `integrators` entries (glass scene, cast_ray), one JSON line, no CPU legs")
     ap.add_argument("--logical-devices", action="store_true",
                     help="with --host-path: --gpus N LOGICAL devices mapped onto GPU 0 (rt_hip_set_device_map)")
     ap.add_argument("--host-path", action="store_true",
                     help="single process: time rt_hip_render_image() over --gpus devices (the C host's path) and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baseline + same-run parity, the per-configuration array, the "
+                         "integrators, host_path / host_path_logical8 / cli_host (N = 1), assembly_check (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.host_path:
         return host_path_main(args)
@@ -1029,26 +1069,30 @@ def main():
                              "algorithmic_bytes_per_launch": alg_bytes},
         }
         out["roofline"].update(executed_work(committed_diag(args.config), launch_casts, kern_s, sc.n_objects, sc.n_triangles))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, image.cpu().numpy(), image8.cpu().numpy(),
+                         [rays / steps, casts / steps, tests / steps, samples / steps])
         if world > 1:
-            # the frame assembled from N ranks' tiles must hold the bits one GPU renders: rank 0 renders a strided sample of
-            # the frame's tiles alone (outside the timed region) and compares them with the gathered image, bit for bit
-            try:
-                import numpy as np
-                a_first, a_stride, a_count = sample_tiles(W, H, 2048)
-                a_px, a_slot, a_pit = tile_pixel_indices(W, H, a_first, a_stride, a_count)
-                a_t, a_t8, _ = gs.render_tiles(SEED, a_first, a_stride, a_count)
-                torch.cuda.synchronize(dev)
-                idx = torch.from_numpy(a_px.astype(np.int64)).to(dev)
-                same = bool((image.reshape(-1, 3)[idx].cpu().numpy().view(np.uint32) == a_t.cpu().numpy()[a_slot, a_pit].view(np.uint32)).all() and
-                            (image8.reshape(-1, 3)[idx].cpu().numpy() == a_t8.cpu().numpy()[a_slot, a_pit]).all())
-                out["assembly_check"] = {"tiles": int(a_count), "pixels": int(len(a_px)), "bit_identical_to_one_gpu": same,
-                                         "what": f"the frame gathered from {world} ranks against rank 0's own render of tiles "
-                                                 f"{a_first} + {a_stride} k"}
-                if not same:
-                    out["error"] = "the frame assembled from the ranks' tiles differs from a one-GPU render of the same tiles"
-                    rc = 6
-            except Exception as exc:
-                out["assembly_check"] = {"error": repr(exc)}
+            # (--full) the frame assembled from N ranks' tiles must hold the bits one GPU renders: rank 0 renders a strided
+            # sample of the frame's tiles alone (outside the timed region) and compares them with the gathered image, bit for bit
+            if args.full:
+                try:
+                    import numpy as np
+                    a_first, a_stride, a_count = sample_tiles(W, H, 2048)
+                    a_px, a_slot, a_pit = tile_pixel_indices(W, H, a_first, a_stride, a_count)
+                    a_t, a_t8, _ = gs.render_tiles(SEED, a_first, a_stride, a_count)
+                    torch.cuda.synchronize(dev)
+                    idx = torch.from_numpy(a_px.astype(np.int64)).to(dev)
+                    same = bool((image.reshape(-1, 3)[idx].cpu().numpy().view(np.uint32) == a_t.cpu().numpy()[a_slot, a_pit].view(np.uint32)).all() and
+                                (image8.reshape(-1, 3)[idx].cpu().numpy() == a_t8.cpu().numpy()[a_slot, a_pit]).all())
+                    out["assembly_check"] = {"tiles": int(a_count), "pixels": int(len(a_px)), "bit_identical_to_one_gpu": same,
+                                             "what": f"the frame gathered from {world} ranks against rank 0's own render of tiles "
+                                                     f"{a_first} + {a_stride} k"}
+                    if not same:
+                        out["error"] = "the frame assembled from the ranks' tiles differs from a one-GPU render of the same tiles"
+                        rc = 6
+                except Exception as exc:
+                    out["assembly_check"] = {"error": repr(exc)}
             out["ranks_seen"] = ranks_seen
             out["phase_ms"] = {"render": max(p[0] for p in rank_phase), "gather": max(p[1] for p in rank_phase),
                                "untile": rank_phase[0][2],
@@ -1060,7 +1104,7 @@ def main():
             if ranks_seen != args.gpus:
                 out["error"] = f"the backend connected {ranks_seen} ranks, --gpus asked for {args.gpus}" + ("; " + out["error"] if "error" in out else "")
                 rc = 3
-        if world == 1 and not args.no_configs and not args.shard:
+        if world == 1 and args.full and not args.no_configs and not args.shard:
             lines = []
             for cfg, cspp in ((1, 0), (2, 0), (3, 0), (5, args.c5_spp)):
                 if cfg == args.config:
@@ -1083,7 +1127,7 @@ def main():
                 except Exception as exc:
                     ints.append({"integrator": kind, "error": repr(exc)})
             out["integrators"] = ints
-        if world == 1 and args.cpu_tiles > 0:
+        if world == 1 and args.full and args.cpu_tiles > 0:
             sample = None
             try:
                 if args.config == 4:
@@ -1118,8 +1162,9 @@ def main():
     # whole-call time (PCIe-inclusive; never `value`), then the same frame on 8 LOGICAL devices mapped onto this GPU -- the
     # multi-device path executed and compared bit for bit on the one GPU there is -- and the C command-line host's process
     # wall time by phase.  A failure or time-out is reported, never fatal.
-    # (N = 1: with the other extras of the default line only -- `--no-configs` runs, i.e. profiling passes and A/Bs, skip them)
-    if not rehearse and not args.shard and os.environ.get("RT_BENCH_HOST_PATH", "1") != "0" and (world > 1 or not args.no_configs):
+    # (--full only; N = 1: with the other extras of the --full line only -- `--no-configs` runs skip them)
+    if args.full and not rehearse and not args.shard and os.environ.get("RT_BENCH_HOST_PATH", "1") != "0" and \
+            (world > 1 or not args.no_configs):
         if rank == 0:
             out["host_path"] = run_host_path_child(args, world)
             if world == 1:

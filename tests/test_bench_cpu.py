@@ -166,3 +166,32 @@ def test_isa_and_diag_records_follow_the_sources_too():
         fresh = bench.executed_work(d, 1e9, 0.1, 8, 0, source_sha=d["source_sha256"])
         assert 0 < fresh["frac_executed"] < 1
     assert sha  # (whether the committed records are fresh TODAY is the profile session's business; bench.py says so in its line)
+
+
+def test_dump_outputs_whole_frame_and_fixed_sample(tmp_path):
+    """--dump-outputs: the whole frame while it fits the budget; beyond it, the same seeded pixel sample every time, within
+    the budget, with the indices it took"""
+    rng = np.random.default_rng(5)
+    frame = rng.random((36, 64, 3)).astype(np.float32)
+    frame8 = (frame * 255).astype(np.uint8)
+    names = bench.dump_outputs(str(tmp_path / "whole"), frame, frame8, [10, 9, 8, 7])
+    assert names == ["counters", "frame", "frame_u8"]
+    f = np.load(tmp_path / "whole" / "frame.npy")
+    assert f.dtype == np.float32 and np.array_equal(f, frame)
+    f8 = np.load(tmp_path / "whole" / "frame_u8.npy")
+    assert f8.dtype == np.float32 and np.array_equal(f8, frame8.astype(np.float32))
+    c = np.load(tmp_path / "whole" / "counters.npy")
+    assert c.dtype == np.float64 and c.tolist() == [10, 9, 8, 7]
+    budget = 4096 + 32 * 1024
+    for k in range(2):
+        names = bench.dump_outputs(str(tmp_path / f"s{k}"), frame, frame8, [1, 2, 3, 4], budget=budget)
+        assert names == ["counters", "frame", "frame_u8", "pixel_index"]
+    files = {n: np.load(tmp_path / "s0" / f"{n}.npy") for n in names}
+    assert sum(os.path.getsize(tmp_path / "s0" / f"{n}.npy") for n in names) <= budget
+    idx = files["pixel_index"]
+    assert idx.dtype == np.float64 and 0 < len(idx) < 36 * 64 and (np.diff(idx) > 0).all()
+    i = idx.astype(np.int64)
+    assert np.array_equal(files["frame"], frame.reshape(-1, 3)[i])
+    assert np.array_equal(files["frame_u8"], frame8.reshape(-1, 3)[i].astype(np.float32))
+    for n in names:
+        assert np.array_equal(files[n], np.load(tmp_path / "s1" / f"{n}.npy")), n

@@ -55,7 +55,8 @@ def test_bench_four_ranks_rehearsal_assembles_the_one_gpu_frame():
     test process is one of them; the eight-rank assembly runs on the CPU over gloo in tests/test_dist_cpu.py, and eight
     LOGICAL devices run through the C host's path in tests/test_gpu_devmap.py.)"""
     d = _child([os.path.join(ROOT, "bench.py"), "--gpus", "4", "--config", "1", "--width", "250", "--height", "250", "--spp", "4",
-                "--steps", "1", "--warmup", "1", "--cpu-tiles", "0", "--no-configs"], env={"RT_BENCH_REHEARSE": "1"}, timeout=400)
+                "--steps", "1", "--warmup", "1", "--cpu-tiles", "0", "--no-configs", "--full"], env={"RT_BENCH_REHEARSE": "1"},
+               timeout=400)
     assert d["n_gpus"] == 4 and d["ranks_seen"] == 4 and "REHEARSAL" in d["config"]["parallelism"]
     assert d["assembly_check"]["bit_identical_to_one_gpu"] is True and d["assembly_check"]["tiles"] == 1024
     assert len(d["rank_kernel_ms"]["per_rank"]) == 4

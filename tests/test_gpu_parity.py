@@ -767,7 +767,7 @@ def test_bench_two_ranks_rehearsal(gpu):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--config", "2", "--spp", "4", "--steps", "1", "--warmup", "1", "--cpu-tiles", "0", "--no-configs"]
+    common = ["--config", "2", "--spp", "4", "--steps", "1", "--warmup", "1", "--cpu-tiles", "0", "--no-configs", "--full"]
     env = dict(os.environ, RT_BENCH_REHEARSE="1", MASTER_ADDR="127.0.0.1")
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29671", os.path.join(root, "bench.py"),
@@ -812,7 +812,7 @@ def test_bench_host_path_and_config_array(gpu):
     d = json.loads([ln for ln in hp.stdout.splitlines() if ln.startswith("{")][0])["host_path"]
     assert d["n_devices"] == 1 and len(d["call_ms"]) == 2 and d["ray_bounces_per_s"] > 0
     run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "1", "--steps", "1", "--warmup", "1",
-                          "--cpu-tiles", "0", "--c5-spp", "1"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--cpu-tiles", "0", "--c5-spp", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert run.returncode == 0, run.stderr[-2000:]
     d = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][0])
     got = {c["config"]: c for c in d["configs"]}
@@ -845,7 +845,8 @@ def test_bench_parity_block_against_the_compiled_reference(gpu):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "4", "--width", "480", "--height", "270",
-                          "--spp", "16", "--steps", "2", "--warmup", "1", "--cpu-tiles", "256", "--cpu-workers", "4", "--no-configs"],
+                          "--spp", "16", "--steps", "2", "--warmup", "1", "--cpu-tiles", "256", "--cpu-workers", "4", "--no-configs",
+                          "--full"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert run.returncode == 0, (run.stdout[-1500:], run.stderr[-1500:])
     d = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
@@ -856,11 +857,51 @@ def test_bench_parity_block_against_the_compiled_reference(gpu):
     assert d["cpu_baseline"]["value"] > 0 and "error" not in d
     # a mesh configuration goes through the reference's revived mesh scan (RefMeshOracle)
     run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "3", "--width", "240", "--height", "136",
-                          "--spp", "8", "--steps", "1", "--warmup", "1", "--cpu-tiles", "64", "--cpu-workers", "4", "--no-configs"],
+                          "--spp", "8", "--steps", "1", "--warmup", "1", "--cpu-tiles", "64", "--cpu-workers", "4", "--no-configs",
+                          "--full"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert run.returncode == 0, (run.stdout[-1500:], run.stderr[-1500:])
     d = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["parity"]["ok"] and "mesh" in d["parity"]["oracle"], d["parity"]
+
+
+def test_bench_plain_run_and_dump_outputs(gpu, tmp_path):
+    """a plain bench.py run (no --full) times exactly --steps steps and carries none of the --full extras; --dump-outputs
+    writes the last timed frame, bit-equal to a render of the same scene here and the same from run to run"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    from rt_amd import scene as S
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "2", "--width", "200", "--height", "150",
+              "--spp", "8", "--warmup", "1"]
+    lines = []
+    for k, steps in enumerate((3, 1)):
+        run = subprocess.run(common + ["--steps", str(steps), "--dump-outputs", str(tmp_path / f"d{k}")],
+                             capture_output=True, text=True, timeout=300, cwd=root)
+        assert run.returncode == 0, (run.stdout[-1500:], run.stderr[-1500:])
+        lines.append(json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1]))
+    d = lines[0]
+    assert d["metric"] == "ray-bounces/sec" and d["unit"] == "ray-bounces/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert not set(d) & {"configs", "integrators", "cpu_baseline", "cpu_as_shipped", "parity", "host_path", "host_path_logical8",
+                         "cli_host", "assembly_check"}, sorted(d)
+    got = [{n: np.load(tmp_path / f"d{k}" / f"{n}.npy") for n in ("frame", "frame_u8", "counters")} for k in range(2)]
+    a = got[0]
+    assert a["frame"].dtype == np.float32 and a["frame"].shape == (150, 200, 3)
+    assert a["frame_u8"].dtype == np.float32 and a["frame_u8"].shape == (150, 200, 3)
+    assert a["counters"].dtype == np.float64 and a["counters"].tolist()[:2] == [d["ray_count_per_step"], d["ray_bounces_per_step"]]
+    for n in a:
+        assert np.array_equal(a[n], got[1][n]), n
+    gs = gpu.GpuScene(S.build_scene(2, 200, 150, 8))
+    img, img8, st = gs.render_image(SEED)
+    gs.close()
+    torch.cuda.synchronize()
+    assert np.array_equal(a["frame"].view(np.uint32), img.cpu().numpy().view(np.uint32))
+    assert np.array_equal(a["frame_u8"], img8.cpu().numpy().astype(np.float32))
+    assert a["counters"].tolist() == [st["rays"], st["casts"], st["tests"], st["samples"]]
 
 
 def test_mesh_hierarchy_partitions_and_chunks_are_bit_invariant(gpu):
