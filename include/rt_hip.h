@@ -175,6 +175,9 @@ typedef struct
   int32_t samples_per_chunk, max_depth;
   uint32_t have_park_ws;            /* the parked-walk workspace could be allocated */
   uint32_t wide_pend_ok;            /* the pending-ray pool could be had at 4 x 512 stacks per slot */
+  double max_emission;              /* max |emission component| over all materials: with samples_per_chunk (taken as the
+                                     * launch's samples) and max_depth, whether the fixed-point pixel sums resolve the launch;
+                                     * where they do not, trace_path takes the M_REFRACTION forms' unbounded sums */
 } RtHipSceneClass;
 const char *rt_hip_kernel_for_class(const RtHipSceneClass *scene_class);
 
@@ -205,7 +208,9 @@ int rt_hip_render_tiles(const RtHipScene *scene, const RtHipCamera *camera, cons
  * sample_chunks == 1); it is cleared, filled and resolved on `stream`.
  * rt_hip_suggest_chunks() returns a good value for the scene's device. */
 size_t rt_hip_chunk_workspace_bytes(uint32_t tile_count);   /* enough for any scene */
-/* ... for this scene: scenes without M_REFRACTION need a sixth of it (plain fixed-point sums; the others keep windowed sums) */
+/* ... for this scene: scenes without M_REFRACTION need a sixth of it (plain fixed-point sums; the others keep windowed sums).
+ * A launch of such a scene whose fixed-point sums would be too coarse (an emitter bright for its samples and depth) takes the
+ * M_REFRACTION forms' unbounded sums and renders in one chunk, whatever sample_chunks asks: the image is the same. */
 size_t rt_hip_scene_chunk_workspace_bytes(const RtHipScene *scene, uint32_t tile_count);
 uint32_t rt_hip_suggest_chunks(const RtHipScene *scene, uint32_t tile_count, int32_t samples);
 /* ... knowing the launch's max_depth: scenes with M_REFRACTION need samples_per_chunk x 2^(max_depth + 1) <= 2^30 for the pooled
@@ -229,7 +234,10 @@ int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t
  * each) so that tests can compare it bit for bit with IEEE results computed on the host:
  * op 0 sqrt without range scaling (valid for 0 or >= 2^-767), 1 quotient by a small integer
  * through its reciprocal, 2 library sqrt, 3 IEEE division, 4 the fused r*2^-30 - 1 mapping,
- * 5 reciprocal without range scaling (valid for 2^-500 <= a <= 2^500). */
+ * 5 reciprocal without range scaling (valid for 2^-500 <= a <= 2^500), 6 the tabulated atan2 (a, b), 7 frac1 = fmod(a, 1.0),
+ * 8 win_add of every a[i] into the windowed accumulator out[0..6) as h_out holds it on entry (n >= 8; out[6] counts refused
+ * terms), 9 win_normalize + win_value of groups of six words (bit patterns in h_a[8g..8g+6); n a multiple of 8) -> h_out[8g..8g+6)
+ * the normalised words, h_out[8g+6] the value. */
 int rt_hip_selftest_math(int op, const double *h_a, const double *h_b, double *h_out, size_t n, int device);
 
 /* Runs the render kernels' own exact primitive tests (intersect_sphere raytracer.c:77-118,

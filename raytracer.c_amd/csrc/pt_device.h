@@ -49,6 +49,7 @@
 #ifndef PT_DEVICE_H
 #define PT_DEVICE_H
 
+#include <math.h>
 #include <stdint.h>
 
 #define PT_TILE 8
@@ -107,10 +108,12 @@
 __host__ __device__
 #endif
 static inline bool pt_refr_pool_fits(int32_t samples, int32_t max_depth)
-{ /* pt_scene_ctx.h, win_add: a window word holds 2^31 pieces.  A path adds one piece per word when it ends, and a sample has at
-   * most 2^max_depth paths (every one of its refractive hits starts one more: a full binary tree's leaves) -- the rule keeps
-   * samples x 2^(max_depth + 1) <= 2^30, a factor four inside the capacity.  (`samples`: of one sample chunk; until round 5 the
-   * rule was 2^(max_depth + 2) on a launch's whole sample count.) */
+{ /* pt_scene_ctx.h, win_add: a window word holds 2^31 pieces (each below 2^32: |sum| < 2^63).  Every event of a path can add one
+   * term, i.e. one piece per word, and every refractive hit of a sample starts one more path: a sample is at most a full binary
+   * tree of max_depth + 2 levels, 2^(max_depth + 2) - 1 terms.  The rule keeps samples x 2^(max_depth + 1) <= 2^30, so a chunk
+   * adds at most 2^31 pieces to a word: exactly the capacity, no margin beyond it (tests/test_gpu_parity.py checks the
+   * capacity itself through rt_hip_selftest_math op 8).  (`samples`: of one sample chunk; until round 5 the rule was
+   * 2^(max_depth + 2) on a launch's whole sample count.) */
   return max_depth + 1 <= 30 && ((int64_t)samples << (max_depth + 1)) <= ((int64_t)1 << 30);
 }
 /* the fewest sample chunks with which a launch of `samples` per pixel fits the rule; 0: none does (max_depth > 29) */
@@ -123,6 +126,38 @@ static inline uint32_t pt_refr_pool_chunks_needed(int32_t samples, int32_t max_d
     return 0u;
   const int64_t per_chunk = ((int64_t)1 << 30) >> (max_depth + 1); /* >= 1 */
   return (uint32_t)(((int64_t)samples + per_chunk - 1) / per_chunk);
+}
+
+/* ---- the pixel sums a trace_path launch can use (host side: pt_classify and the launch read the same functions) ----------
+ * Fixed point (fixed_term, pt_math.h): every term of a sample is bounded by per_sample = (max_depth + 2) x max(BACKGROUND,
+ * max |emission|) x 1.01 (throughput <= 1 without M_REFRACTION; at most max_depth + 2 events).  The scale is 2^s, the largest
+ * power of two with samples x per_sample x 2^s < 2^62 (the sum) and per_sample x 2^s < 2^51 (a term read off an fp64
+ * mantissa).  -> s; INT32_MIN when the bound is not a finite positive number. */
+static inline int pt_acc_scale_exp(double max_emission, int32_t samples, int32_t max_depth)
+{
+  const double per_sample = ((double)max_depth + 2.0) * fmax(10.0 / 255.0, max_emission) * 1.01;
+  const double bound = per_sample * (double)samples;
+  if (!(bound > 0) || !(bound < 1e300))
+    return INT32_MIN;
+  int e = 0, e1 = 0;
+  (void)frexp(4611686018427387904.0 / bound, &e);    /* 2^62 / bound = m * 2^e, m in [0.5, 1) */
+  (void)frexp(2251799813685248.0 / per_sample, &e1); /* 2^51 / per_sample */
+  return (e1 < e ? e1 : e) - 1;
+}
+/* A term is rounded to a multiple of 2^-s, so a pixel mean is off by up to (max_depth + 2) x 2^-s / 2.  The brightest emitter
+ * sets s whether or not a ray can reach it: at 1e15 a pixel of BACKGROUND rounds to 0.  The fixed-point sums are kept while that
+ * error is <= 2^-30 (float32's half ulp at 1/64; the baseline launches sit at 2^-31.8, config 4 at 1024 spp and depth 16, and
+ * 2^-30.8, config 5 at 4096 spp); beyond it the launch takes the windowed or fp64 sums of the M_REFRACTION forms, exact
+ * above 2^-64 (pt_classify). */
+static inline bool pt_fixed_sums_fit(double max_emission, int32_t samples, int32_t max_depth)
+{
+  const int s = pt_acc_scale_exp(max_emission, samples, max_depth);
+  return s != INT32_MIN && ldexp((double)max_depth + 2.0, -s - 1) <= ldexp(1.0, -30);
+}
+/* win_add refuses a term of 2^128 or more (it flags the pixel): scenes whose bound reaches that keep fp64 sums (the static kernels) */
+static inline bool pt_window_terms_fit(double max_emission, int32_t max_depth)
+{
+  return ((double)max_depth + 2.0) * fmax(10.0 / 255.0, max_emission) * 1.01 < 3.402823669209385e38; /* 2^128 */
 }
 
 #define PT_FLAG_DIFFUSE 2u
@@ -313,9 +348,19 @@ struct PtPickFacts
   int32_t samples, max_depth; /* samples: per sample chunk */
   bool have_park_ws;          /* the parked-walk kernels' ring workspace exists on the device */
   bool wide_pend_ok;          /* the pending-ray pool can be had at 4 x 512 stacks per slot */
+  int32_t launch_samples;     /* samples per pixel of the whole launch (all chunks): with max_emission, the fixed-point scale */
+  double max_emission;        /* max |emission component| over all materials (pt_acc_scale_exp) */
 };
 int pt_pick_kernel(const PtSceneView &scene, const PtPickFacts &facts);          /* -> index into the family */
 hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int which);
+/* entries per pending-ray stack a launch needs: max_depth + 2 where a material has two children (M_REFRACTION under trace_path,
+ * M_REFLECTION | M_REFRACTION under cast_ray); one where none has -- nothing is ever pushed (a scene on the M_REFRACTION forms for
+ * their unbounded sums, pt_classify), at any depth */
+static inline uint32_t pt_pend_entries(const PtSceneView &scene, uint32_t integrator, int32_t max_depth)
+{
+  const bool two_children = integrator == 1u ? scene.any_mirror_glass != 0u : scene.any_refract != 0u;
+  return two_children ? (uint32_t)max_depth + 2u : 1u;
+}
 const char *pt_kernel_name_of(int which);
 int pt_kernel_count(void);
 bool pt_kernel_uses_pend_pool(int which);

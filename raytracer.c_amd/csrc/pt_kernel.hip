@@ -288,7 +288,8 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
  * on caller data so a test can compare them bit for bit with the host's IEEE results.
  * op 0: sqrt_unscaled(a[i]);  op 1: div_small_int(a[i], b[i], 1/b[i]);  op 2: the library
  * sqrt(a[i]);  op 3: a[i] / b[i];  op 4: rnd_pm1-style fused r * 2^-30 - 1 with r = a[i];  op 5: rcp_unscaled(a[i]);
- * op 6: atan2_tab(a[i], b[i]);  op 7: frac1(a[i]) (= fmod(a[i], 1.0));  op 8: win_add of every a[i] into one accumulator (out[0..6]). */
+ * op 6: atan2_tab(a[i], b[i]);  op 7: frac1(a[i]) (= fmod(a[i], 1.0));  op 8: win_add of every a[i] into one accumulator (out[0..6]);
+ * op 9: win_normalize, then win_value, of the PT_WIN_N words a[8 g .. 8 g + 6) (bit patterns) -> out[8 g ..]: the words, the value. */
 extern "C" __global__ __launch_bounds__(256) void pt_selftest_math(int op, const double *a, const double *b,
                                                                   double *out, size_t n)
 {
@@ -315,10 +316,26 @@ extern "C" __global__ __launch_bounds__(256) void pt_selftest_math(int op, const
     else if (op == 7)
       r = frac1(a[i]);
     else if (op == 8)
-    { /* the windowed pixel sums of pt_render_tiles_refr_pool: every a[i] into ONE accumulator, out[0 .. PT_WIN_N) (zeroed by the
-       * caller); out[PT_WIN_N] counts the values win_add refused (non-finite, or at least 2^128) */
+    { /* the windowed pixel sums of pt_render_tiles_refr_pool: every a[i] into ONE accumulator, out[0 .. PT_WIN_N) (as the caller
+       * initialised it: zeros, or words that start near the capacity); out[PT_WIN_N] counts the values win_add refused
+       * (non-finite, or at least 2^128) */
       if (!win_add(reinterpret_cast<unsigned long long *>(out), a[i]))
         atomicAdd(reinterpret_cast<unsigned long long *>(out) + PT_WIN_N, 1ull);
+      continue;
+    }
+    else if (op == 9)
+    { /* how a chunk's window is merged and read (pt_resolve_tiles): one group of eight doubles per lane */
+      if ((i & 7u) == 0u && i + 8u <= n)
+      {
+        unsigned long long w[PT_WIN_N];
+        for (int k = 0; k < PT_WIN_N; k++)
+          w[k] = (unsigned long long)__double_as_longlong(a[i + k]);
+        win_normalize(w);
+        for (int k = 0; k < PT_WIN_N; k++)
+          out[i + k] = __longlong_as_double((long long)w[k]);
+        out[i + PT_WIN_N] = win_value(w);
+        out[i + PT_WIN_N + 1] = 0.0;
+      }
       continue;
     }
     out[i] = r;
@@ -812,12 +829,18 @@ PtPickKey pt_classify(const PtSceneView &scene, const PtPickFacts &f)
     k.mat = scene.any_mirror_glass ? GLASS2 : PLAIN;
   else
     k.mat = scene.any_refract ? REFR : (scene.any_checker ? CHK : PLAIN);
+  /* sums: the fixed-point pixel sums resolve this launch's terms finely enough (pt_fixed_sums_fit), or the scene takes the
+   * unbounded sums of the REFR rows -- their bodies carry the plain and checker code -- like a scene with M_REFRACTION */
+  if (!cast && !pt_fixed_sums_fit(f.max_emission, f.launch_samples, f.max_depth))
+    k.mat = REFR;
   /* the parked-walk body's conditions: a ring workspace, references that fit the walk's 24-bit stack entries (range: the rows) */
   k.park = (f.have_park_ws && scene.n_bvh_nodes < (1u << 23) && scene.n_triangles < (1u << (23 - PT_BVH_COUNT_BITS))) ? YES : NO;
   k.round = scene.mesh_round ? YES : NO;
   /* the pooled refraction kernels' windowed sums hold 2^31 pieces per word: a sample of a refractive scene has at most
-   * 2^(max_depth + 2) terms (a full binary tree of children), so a launch needs samples x 2^(max_depth + 2) <= 2^30 */
-  k.fit = (pt_refr_pool_fits(f.samples, f.max_depth) && (k.mesh < HIER || f.wide_pend_ok)) ? YES : NO;
+   * 2^(max_depth + 2) - 1 terms (a full binary tree of children), so a chunk needs samples x 2^(max_depth + 1) <= 2^30
+   * (pt_refr_pool_fits); and no term may reach 2^128 (pt_window_terms_fit) */
+  k.fit = (pt_refr_pool_fits(f.samples, f.max_depth) && pt_window_terms_fit(f.max_emission, f.max_depth) &&
+           (k.mesh < HIER || f.wide_pend_ok)) ? YES : NO;
   return k;
 }
 
@@ -969,7 +992,7 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
   const PtKernelFn kernel = k.fn;
   if (k.stages_none)
     lds_bytes = extra_lds; /* the in-memory pooled kernels stage nothing, whatever the scene's size */
-  if (k.pend_pool && (launch.pend_ws == nullptr || launch.pend_entries < (uint32_t)launch.max_depth + 2u ||
+  if (k.pend_pool && (launch.pend_ws == nullptr || launch.pend_entries < pt_pend_entries(launch.scene, launch.integrator, launch.max_depth) ||
                       launch.pend_slot_doubles < (uint64_t)launch.pend_entries * PT_PEND_FIELDS_HOST * pt_kernel_pend_columns_of(which)))
     return hipErrorInvalidValue; /* a kernel with a pending-ray stack needs its pool, wide enough (rt_hip_shim.hip: pend_pool_for) */
   const bool queued = k.queued;

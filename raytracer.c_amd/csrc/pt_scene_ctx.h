@@ -194,7 +194,7 @@ struct PendStack
  * (at most three) 32-bit pieces that fall into consecutive words, and each piece is added with an integer LDS atomic.
  * Integer addition commutes and associates, so the sums do not depend on the order or grouping of terms (any lane / wave /
  * tile / GPU assignment gives the same words), there is no rounding at all above 2^PT_WIN_E0, and a word overflows only
- * after 2^31 pieces (pt_refr_pool_fits keeps a sample chunk's samples x 2^(max_depth + 1) below 2^30; chunks are merged in
+ * after 2^31 pieces (pt_refr_pool_fits keeps a sample chunk's samples x 2^(max_depth + 1) below 2^30: at most 2^31 terms, the capacity itself; chunks are merged in
  * carry-normalised form, win_normalize, whose words are below 2^32 each).  Range: 2^-64 (bits below are dropped: 5e-20
  * absolute per term) to 2^128, all a float32 pixel can hold; a term at or above that flags the pixel like a NaN.  (Six words: a
  * seventh would cost the kernel its fourth workgroup per CU.) */
@@ -239,9 +239,12 @@ __device__ __forceinline__ void win_normalize(unsigned long long *w)
     w[k + 1] += (unsigned long long)c;
   }
 }
-/* the sum: words (normalised by the caller: win_normalize) combined from the top (each conversion and product is exact up to 2^-53
- * relative of its own word: the result is within a few ulps of the exact sum, which is more than the reference's own
- * left-to-right fp64 summation guarantees) */
+/* the sum: words (normalised by the caller: win_normalize) combined from the top.  Words 0..4 are below 2^32, so their products
+ * with 2^(E0 + 32 k) are exact; only the top word's conversion and the five adds round.  The partial sums are exact integers
+ * times 2^(E0 + 32 k) until the first one that needs more than 53 bits (at word k, weight 2^m: it is then >= 2^(m + 53)); that
+ * rounding costs half an ulp, and what the lower words still add is below 2^m, under half an ulp of the partial -- each later add
+ * moves it by at most one ulp of a neighbouring binade.  |win_value - exact sum| <= 2 ulp of the result (rt_hip_selftest_math
+ * op 9 checks it against the exact rational sum), more than the reference's own left-to-right fp64 summation guarantees */
 __device__ __forceinline__ double win_value(const unsigned long long *w)
 {
   double v = 0.0;

@@ -1101,7 +1101,7 @@ const char *rt_hip_kernel_name(const RtHipScene *scene, uint32_t integrator)
     /* (a scene that has met its workspace keeps it, whatever is injected later; one that has not yet would not get it now) */
     no_ws = scene->park_tried ? scene->park_ws == nullptr : (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_PARK_WS) != 0;
   }
-  const PtPickFacts facts = {integrator, 1, 0, !no_ws, !(g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_WIDE_PEND)};
+  const PtPickFacts facts = {integrator, 1, 0, !no_ws, !(g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_WIDE_PEND), 1, scene->max_emission};
   return pt_kernel_name_of(pt_pick_kernel(scene->view, facts));
 }
 
@@ -1133,7 +1133,8 @@ const char *rt_hip_kernel_for_class(const RtHipSceneClass *c)
   v.any_mirror_glass = c->any_mirror_glass ? 1u : 0u;
   v.wide_range = c->wide_range ? 1u : 0u;
   v.mesh_round = c->mesh_round ? 1u : 0u;
-  const PtPickFacts facts = {c->integrator, c->samples_per_chunk, c->max_depth, c->have_park_ws != 0, c->wide_pend_ok != 0};
+  const PtPickFacts facts = {c->integrator, c->samples_per_chunk, c->max_depth, c->have_park_ws != 0, c->wide_pend_ok != 0,
+                             c->samples_per_chunk, c->max_emission};
   return pt_kernel_name_of(pt_pick_kernel(v, facts));
 }
 
@@ -1227,7 +1228,8 @@ uint32_t rt_hip_suggest_chunks_depth(const RtHipScene *scene, uint32_t tile_coun
   {
     std::lock_guard<std::mutex> lock(scene->table_mutex);
     const bool have_ws = scene->park_tried ? scene->park_ws != nullptr : (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_PARK_WS) == 0;
-    const PtPickFacts facts = {RT_HIP_TRACE_PATH, (int32_t)(((uint64_t)samples + need - 1) / need), max_depth, have_ws, true};
+    const PtPickFacts facts = {RT_HIP_TRACE_PATH, (int32_t)(((uint64_t)samples + need - 1) / need), max_depth, have_ws, true,
+                               samples, scene->max_emission};
     const int which = pt_pick_kernel(scene->view, facts);
     queued = pt_kernel_is_queued(which);
     windowed = pt_kernel_is_windowed(which);
@@ -1433,21 +1435,13 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
   {
     /* Fixed-point scale of the per-pixel sums (pt_render_tiles): a sample's radiance is
      * sum_k T_k (.) e_k with throughput T <= 1 (albedo/prob <= 1, cos <= 1) over at most
-     * max_depth + 2 events, so every term and every sample is bounded by
-     * (max_depth + 2) * max(BACKGROUND, max emission).  Two conditions on the power-of-two scale: the sum
-     * of `samples` samples stays below 2^62, and a single term stays below 2^51 -- the kernels read a
-     * term's integer off an fp64 mantissa (fixed_term in pt_math.h). */
-    const double per_sample = ((double)params->max_depth + 2.0) * std::fmax(10.0 / 255.0, scene->max_emission) * 1.01;
-    const double bound = per_sample * (double)params->samples;
-    if (!(bound > 0) || !(bound < 1e300))
-      return fail(RT_HIP_EINVAL, "emission magnitudes give no finite radiance bound (%g)", bound);
-    int e = 0, e1 = 0;
-    (void)std::frexp(4611686018427387904.0 / bound, &e);      /* 2^62 / bound = m * 2^e, m in [0.5, 1) */
-    (void)std::frexp(2251799813685248.0 / per_sample, &e1);   /* 2^51 / per_sample */
-    if (e1 < e)
-      e = e1;
-    L.acc_scale = std::ldexp(1.0, e - 1);
-    L.acc_inv_scale = std::ldexp(1.0, 1 - e);
+     * max_depth + 2 events -- pt_acc_scale_exp (pt_device.h), which pt_classify reads too: whether these sums are
+     * fine enough for the launch (pt_fixed_sums_fit) picks the kernel. */
+    const int s = pt_acc_scale_exp(scene->max_emission, params->samples, params->max_depth);
+    if (s == INT32_MIN)
+      return fail(RT_HIP_EINVAL, "emission magnitudes give no finite radiance bound (%g)", scene->max_emission);
+    L.acc_scale = std::ldexp(1.0, s);
+    L.acc_inv_scale = std::ldexp(1.0, -s);
   }
   L.tile_first = params->tile_first;
   L.tile_stride = params->tile_stride;
@@ -1492,8 +1486,14 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
     if (need > sample_chunks && need <= (uint64_t)params->samples && need * params->tile_count <= 0x7FFFFFFFull)
       sample_chunks = (uint32_t)need;
   }
+  /* a scene without M_REFRACTION whose launch needs the unbounded sums (pt_fixed_sums_fit) would take the windowed chunk
+   * record, six times the plain one its caller may have sized the workspace for (rt_hip_scene_chunk_workspace_bytes): it
+   * renders its samples in one chunk -- the image does not depend on the chunk count */
+  if (!cast_ray && !scene->view.any_refract && !pt_fixed_sums_fit(scene->max_emission, params->samples, params->max_depth))
+    sample_chunks = 1;
   const int32_t samples_per_chunk = (int32_t)(((int64_t)params->samples + sample_chunks - 1) / sample_chunks);
-  PtPickFacts facts = {L.integrator, samples_per_chunk, params->max_depth, L.park_ws != nullptr, true};
+  PtPickFacts facts = {L.integrator, samples_per_chunk, params->max_depth, L.park_ws != nullptr, true, params->samples,
+                       scene->max_emission};
   int which = pt_pick_kernel(L.scene, facts);
   auto chunks_of = [&](int k) {
     if (pt_kernel_takes_chunks(k))
@@ -1513,7 +1513,7 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
   if (pt_kernel_uses_pend_pool(which))
   {
     std::lock_guard<std::mutex> pend_lock(g_pend_mutex);
-    rc = pend_pool_for(scene->device, (uint32_t)params->max_depth + 2u, pt_kernel_pend_columns_of(which), L);
+    rc = pend_pool_for(scene->device, pt_pend_entries(L.scene, L.integrator, params->max_depth), pt_kernel_pend_columns_of(which), L);
     /* the parked-walk refraction kernels want four times the stacks per slot (1.2 GB at depth 5, 5.7 GB at 32): where that
      * cannot be had, the pool of the other kernels will do -- the table's fit = NO row names the static kernel of the family */
     if (rc == RT_HIP_ENOMEM && pt_kernel_pend_columns_of(which) > PT_PEND_COLUMNS)
@@ -1522,7 +1522,8 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
       which = pt_pick_kernel(L.scene, facts);
       L.sample_chunks = chunks_of(which);
       L.acc_windows = pt_kernel_is_windowed(which) ? 1u : 0u;
-      rc = pt_kernel_uses_pend_pool(which) ? pend_pool_for(scene->device, (uint32_t)params->max_depth + 2u, pt_kernel_pend_columns_of(which), L)
+      rc = pt_kernel_uses_pend_pool(which) ? pend_pool_for(scene->device, pt_pend_entries(L.scene, L.integrator, params->max_depth),
+                                                           pt_kernel_pend_columns_of(which), L)
                                            : RT_HIP_OK;
     }
     if (rc)
@@ -1543,7 +1544,7 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
 
 int rt_hip_selftest_math(int op, const double *h_a, const double *h_b, double *h_out, size_t n, int device)
 {
-  if (!h_a || !h_b || !h_out || op < 0 || op > 8 || (op == 8 && n < 8))
+  if (!h_a || !h_b || !h_out || op < 0 || op > 9 || (op == 8 && n < 8) || (op == 9 && n % 8 != 0))
     return fail(RT_HIP_EINVAL, "bad self-test arguments");
   if (device < 0 || device >= usable_devices())
     return fail(RT_HIP_ENODEV, "no HIP device %d", device);
@@ -1555,7 +1556,9 @@ int rt_hip_selftest_math(int op, const double *h_a, const double *h_b, double *h
   hipError_t e = hipMalloc(&d, 3 * n * sizeof(double));
   if (e == hipSuccess) e = hipMemcpy(d, h_a, n * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d + n, h_b, n * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d + 2 * n, 0, n * sizeof(double)); /* (op 8 accumulates into out) */
+  /* op 8 accumulates into out, starting from what the caller put there */
+  if (e == hipSuccess) e = op == 8 ? hipMemcpy(d + 2 * n, h_out, n * sizeof(double), hipMemcpyHostToDevice)
+                                   : hipMemset(d + 2 * n, 0, n * sizeof(double));
   if (e == hipSuccess) e = pt_launch_selftest(op, d, d + n, d + 2 * n, n, nullptr);
   if (e == hipSuccess) e = hipMemcpy(h_out, d + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost);
   (void)hipFree(d);

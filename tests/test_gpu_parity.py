@@ -456,6 +456,107 @@ def test_device_math_shortcuts_are_bit_exact(gpu):
     assert got == want, "the windowed sum is not the exact sum of the truncated terms"
 
 
+def _selftest(op, a, out):
+    from rt_amd import abi
+    shim = abi.load_shim()
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    out = np.ascontiguousarray(out, dtype=np.float64)
+    rc = shim.rt_hip_selftest_math(op, a.ctypes.data, a.ctypes.data, out.ctypes.data, a.size, 0)
+    assert rc == 0, shim.rt_hip_last_error().decode()
+    return out
+
+
+_M64 = (1 << 64) - 1
+
+
+def _s64(x):
+    x &= _M64
+    return x - (1 << 64) if x >> 63 else x
+
+
+def _win_total(words):
+    """the integer a window's six words stand for (word k: weight 2^(32 k), every word a signed 64-bit integer)"""
+    return sum(_s64(int(w)) << (32 * k) for k, w in enumerate(words))
+
+
+def _win_canonical(total):
+    """the carry-normalised form of that integer, as win_normalize states it: words 0..4 in [0, 2^32), the top word the rest"""
+    assert -(1 << 223) <= total < (1 << 223)
+    return [(total >> (32 * k)) & 0xFFFFFFFF for k in range(5)] + [(total >> 160) & _M64]
+
+
+def _win_op9(groups):
+    a = np.array([w for g in groups for w in list(g) + [0, 0]], dtype=np.uint64).view(np.float64)
+    out = _selftest(9, a, np.zeros(a.size)).reshape(-1, 8)
+    return out[:, :6].view(np.uint64), out[:, 6]
+
+
+def test_window_normalize_is_canonical_and_win_value_within_2_ulp(gpu):
+    """win_normalize then win_value (pt_scene_ctx.h) on words the caller supplies: random words of both signs, carries that run
+    through all six words, and the extremes the capacity rule allows (2^31 pieces below 2^32 in a word: |word| < 2^63).  The
+    normalised words must be the canonical form of the words' integer exactly, and the value within 2 ulp of that integer x 2^-64
+    (the bound derived at win_value)"""
+    from fractions import Fraction
+    import math
+    rng = np.random.default_rng(91)
+    cap = (1 << 31) * ((1 << 32) - 1)   # the largest |word| the capacity rule lets a word reach
+    groups = []
+    for k in range(4000):
+        mode = k % 5
+        if mode == 0:
+            g = [int(x) for x in rng.integers(-(1 << 62), 1 << 62, 6)]
+        elif mode == 1:
+            g = [int(x) for x in rng.integers(-(1 << 34), 1 << 34, 6)]
+        elif mode == 2:   # a large low word over a small top: the value needs all 192 bits, and cancels
+            g = [int(rng.integers(-(1 << 62), 1 << 62))] + [int(x) for x in rng.integers(0, 1 << 32, 4)] + [int(rng.integers(-3, 3))]
+        elif mode == 3:
+            g = [int(x) for x in rng.integers(0, 1 << 32, 6)]
+            g[int(rng.integers(0, 6))] *= -1
+        else:
+            g = [int(rng.choice([-cap, cap, 0, 1, -1])) for _ in range(6)]
+        groups.append(g)
+    groups += [[-1, 0, 0, 0, 0, 0],                  # a borrow through all six words: -2^-64
+               [1 << 32, (1 << 32) - 1, (1 << 32) - 1, (1 << 32) - 1, (1 << 32) - 1, 0],   # a carry through all six: 2^96
+               [cap] * 6, [-cap] * 6, [cap, -cap, cap, -cap, cap, -cap], [0] * 6,
+               [0, 0, 0, 0, 0, (1 << 62)], [0, 0, 0, 0, 0, -(1 << 62)], [-1, -1, -1, -1, -1, 1]]
+    words, values = _win_op9([[w & _M64 for w in g] for g in groups])
+    for g, w, v in zip(groups, words, values.tolist()):
+        total = _win_total([x & _M64 for x in g])
+        assert [int(x) for x in w] == _win_canonical(total), g
+        exact = Fraction(total, 1 << 64)
+        if total == 0:
+            assert v == 0.0, g
+            continue
+        assert abs(Fraction(v) - exact) <= 2 * Fraction(math.ulp(v)), (g, v, float(exact))
+
+
+def test_window_grouping_gives_identical_normalised_words(gpu):
+    """the same pieces added up in two groupings -- all at once, or in three parts normalised apiece and then added word by word
+    (how sample chunks are merged) -- normalise to the same words"""
+    rng = np.random.default_rng(92)
+    vals = np.concatenate([rng.normal(size=60000) * 10.0 ** rng.uniform(-20, 30, 60000), rng.uniform(-3, 3, 30000)])
+    whole = _selftest(8, vals, np.zeros(vals.size))[:6].view(np.uint64)
+    parts = [_selftest(8, p, np.zeros(p.size))[:6].view(np.uint64) for p in np.array_split(vals, 3)]
+    normed = _win_op9([p.tolist() for p in parts])[0]
+    merged = [sum(int(normed[j][k]) for j in range(3)) & _M64 for k in range(6)]
+    a, _ = _win_op9([whole.tolist(), merged])
+    assert [int(x) for x in a[0]] == [int(x) for x in a[1]]
+    assert [int(x) for x in a[0]] == _win_canonical(_win_total(whole.tolist()))
+
+
+@pytest.mark.parametrize("sign", [1, -1])
+def test_window_word_holds_its_capacity(gpu, sign):
+    """a window word holds 2^31 pieces below 2^32 (pt_refr_pool_fits: the most a sample chunk adds): start word 2 at 2^31 - 64
+    pieces of 2^32 - 1 and add the last 64 through win_add -- the sum is exact, no wrap"""
+    piece = float((1 << 32) - 1)   # x 2^0: word 2 (weight 2^(-64 + 64)) alone
+    start = ((1 << 31) - 64) * ((1 << 32) - 1) * sign
+    out = np.zeros(64)
+    out.view(np.int64)[2] = start
+    got = _selftest(8, np.full(64, sign * piece), out)[:7].view(np.int64)
+    assert got[6] == 0
+    assert [int(x) for x in got[:6]] == [0, 0, sign * (1 << 31) * ((1 << 32) - 1), 0, 0, 0]
+
+
 def _random_scene(seed, with_mesh, n_tris, extra_flags=(), materials="all"):
     """a deliberately nasty random scene: overlapping / nested / touching spheres, radii from
     1e-3 to 1e4, every material flag, HDR emission, camera possibly inside a sphere, optional

@@ -17,7 +17,7 @@ class SceneClass(C.Structure):
     _fields_ = [("integrator", C.c_uint32), ("n_spheres", C.c_uint32), ("n_meshes", C.c_uint32), ("n_triangles", C.c_uint32),
                 ("any_checker", C.c_uint32), ("any_refract", C.c_uint32), ("any_mirror_glass", C.c_uint32),
                 ("wide_range", C.c_uint32), ("mesh_round", C.c_uint32), ("samples_per_chunk", C.c_int32),
-                ("max_depth", C.c_int32), ("have_park_ws", C.c_uint32), ("wide_pend_ok", C.c_uint32)]
+                ("max_depth", C.c_int32), ("have_park_ws", C.c_uint32), ("wide_pend_ok", C.c_uint32), ("max_emission", C.c_double)]
 
 
 @pytest.fixture(scope="module")
@@ -26,8 +26,8 @@ def pick():
     shim = abi.load_shim()
 
     def f(integrator=PATH, spheres=0, meshes=0, tris=0, chk=0, refr=0, glass2=0, wide=0, round_=0, spp=64, depth=5,
-          park_ws=1, wide_pend=1):
-        c = SceneClass(integrator, spheres, meshes, tris, chk, refr, glass2, wide, round_, spp, depth, park_ws, wide_pend)
+          park_ws=1, wide_pend=1, emission=0.0):
+        c = SceneClass(integrator, spheres, meshes, tris, chk, refr, glass2, wide, round_, spp, depth, park_ws, wide_pend, emission)
         return shim.rt_hip_kernel_for_class(C.byref(c)).decode()
     return f
 
@@ -150,3 +150,81 @@ def test_the_table_is_total_and_every_shipped_kernel_is_some_class_s_row(pick):
         seen.add(name)
     assert seen == family, f"rows no class reaches: {sorted(family - seen)}"
     assert len(family) == 35
+
+
+# Where the fixed-point pixel sums hand over (pt_device.h: pt_fixed_sums_fit).  A term is rounded to 2^-s, the launch's scale
+# set by its brightest emitter, so a pixel mean is off by up to (max_depth + 2) x 2^-s / 2; beyond 2^-30 the launch takes the
+# unbounded sums of the M_REFRACTION rows (windowed, or fp64 in the static kernels where the windows do not fit).  At 64 spp
+# and depth 5 that is between a brightest emitter of 5e4 (2^-30.7) and 1e5 (2^-29.7).  Every fixed-point member:
+# (class, its kernel, the kernel of the same class with an emitter of 1e5, ... of 1e38: terms past win_add's 2^128)
+SUMS_HANDOVER = [
+    (dict(spheres=10), "pt_render_tiles", "pt_render_tiles_refr_pool", "pt_render_tiles_refr"),
+    (dict(spheres=10, chk=1), "pt_render_tiles_chk", "pt_render_tiles_refr_pool", "pt_render_tiles_refr"),
+    (dict(spheres=10, wide=1), "pt_render_tiles_big", "pt_render_tiles_big_refr", "pt_render_tiles_big_refr"),
+    (dict(spheres=10, wide=1, chk=1), "pt_render_tiles_big_chk", "pt_render_tiles_big_refr", "pt_render_tiles_big_refr"),
+    (dict(spheres=5, meshes=1, tris=12), "pt_render_tiles_tri", "pt_render_tiles_tri_refr_pool", "pt_render_tiles_tri_refr"),
+    (dict(spheres=5, meshes=1, tris=12, chk=1), "pt_render_tiles_tri_chk", "pt_render_tiles_tri_refr_pool", "pt_render_tiles_tri_refr"),
+    (dict(spheres=8, meshes=1, tris=10240, round_=1), "pt_render_tiles_tri_queued_sph", "pt_render_tiles_tri_queued_refr_sph",
+     "pt_render_tiles_tri_big_refr"),
+    (dict(spheres=8, meshes=1, tris=10240), "pt_render_tiles_tri_queued", "pt_render_tiles_tri_queued_refr", "pt_render_tiles_tri_big_refr"),
+    (dict(spheres=8, meshes=1, tris=10240, round_=1, chk=1), "pt_render_tiles_tri_queued_chk_sph", "pt_render_tiles_tri_queued_refr_sph",
+     "pt_render_tiles_tri_big_refr"),
+    (dict(spheres=8, meshes=1, tris=10240, chk=1), "pt_render_tiles_tri_queued_chk", "pt_render_tiles_tri_queued_refr",
+     "pt_render_tiles_tri_big_refr"),
+    (dict(spheres=8, meshes=1, tris=10240, park_ws=0), "pt_render_tiles_tri_big", "pt_render_tiles_tri_big_refr", "pt_render_tiles_tri_big_refr"),
+    (dict(spheres=8, meshes=1, tris=10240, chk=1, park_ws=0), "pt_render_tiles_tri_big_chk", "pt_render_tiles_tri_big_refr",
+     "pt_render_tiles_tri_big_refr"),
+    (dict(spheres=126), "pt_render_tiles_pool_mem_s", "pt_render_tiles_refr_pool_mem", "pt_render_tiles_refr"),
+    (dict(spheres=126, chk=1), "pt_render_tiles_pool_mem_s_chk", "pt_render_tiles_refr_pool_mem", "pt_render_tiles_refr"),
+    (dict(spheres=306), "pt_render_tiles_pool_mem_s", "pt_render_tiles_refr_pool_mem", "pt_render_tiles_mem"),
+    (dict(spheres=306, chk=1), "pt_render_tiles_pool_mem_s_chk", "pt_render_tiles_refr_pool_mem", "pt_render_tiles_mem"),
+    (dict(spheres=306, wide=1), "pt_render_tiles_pool_mem", "pt_render_tiles_mem", "pt_render_tiles_mem"),
+    (dict(spheres=306, wide=1, chk=1), "pt_render_tiles_pool_mem_chk", "pt_render_tiles_mem", "pt_render_tiles_mem"),
+    (dict(spheres=306, meshes=1, tris=100), "pt_render_tiles_pool_mem_tri", "pt_render_tiles_mem", "pt_render_tiles_mem"),
+    (dict(spheres=306, meshes=1, tris=100, chk=1), "pt_render_tiles_pool_mem_tri_chk", "pt_render_tiles_mem", "pt_render_tiles_mem"),
+    (dict(spheres=306, meshes=1, tris=600), "pt_render_tiles_tri_queued_mem", "pt_render_tiles_mem", "pt_render_tiles_mem"),
+    (dict(spheres=306, meshes=1, tris=600, chk=1), "pt_render_tiles_tri_queued_mem_chk", "pt_render_tiles_mem", "pt_render_tiles_mem"),
+]
+
+
+@pytest.mark.parametrize("cls,fixed,unbounded,static", SUMS_HANDOVER, ids=[r[1] + ":" + "+".join(f"{a}={b}" for a, b in r[0].items())
+                                                                          for r in SUMS_HANDOVER])
+def test_fixed_point_members_hand_over_to_unbounded_sums(pick, cls, fixed, unbounded, static):
+    assert pick(PATH, emission=5e4, **cls) == fixed
+    assert pick(PATH, emission=1e5, **cls) == unbounded
+    assert pick(PATH, emission=1e37, **cls) == unbounded          # 7 x 1e37 x 1.01 < 2^128
+    assert pick(PATH, emission=1e38, **cls) == static
+    assert pick(PATH, emission=-1e5, **cls) == fixed                # (the class states a magnitude: the shim passes max |e|)
+    # cast_ray sums in fp64 whatever the emitters: its rows do not move
+    assert pick(CAST, emission=1e38, **cls) == pick(CAST, **cls)
+
+
+# the scale's other inputs: samples (the 2^62 bound on a pixel's sum) and depth (terms per sample, and their bound)
+SCALE_ROWS = [
+    # the baseline's launches keep their kernels: config 4 at 1024 spp and depth 16 with a light of 2.4e3 (2^-31.8), config 5 at
+    # 4096 spp (2^-30.8) -- and both with the 9.4 their host scenes actually carry
+    (dict(spheres=38, spp=1024, depth=16, emission=2.4e3), "pt_render_tiles"),
+    (dict(spheres=8, meshes=1, tris=10240, round_=1, spp=4096, depth=16, emission=2.4e3), "pt_render_tiles_tri_queued_sph"),
+    (dict(spheres=38, spp=1024, depth=16, emission=9.412), "pt_render_tiles"),
+    (dict(spheres=8, meshes=1, tris=10240, round_=1, spp=4096, depth=16, emission=9.412), "pt_render_tiles_tri_queued_sph"),
+    # ... one step of samples further, the light of 2.4e3 is past the limit (2^-29.8)
+    (dict(spheres=8, meshes=1, tris=10240, round_=1, spp=8192, depth=16, emission=2.4e3), "pt_render_tiles_tri_queued_refr_sph"),
+    (dict(spheres=38, spp=8192, depth=16, emission=2.4e3), "pt_render_tiles_refr_pool"),
+    # the most samples a launch takes decide through the 2^62 bound, not the 2^51 one: 2^26 spp of a dim room at depth 16
+    (dict(spheres=38, spp=1 << 26, depth=16, emission=9.412), "pt_render_tiles_refr"),
+    (dict(spheres=38, spp=1 << 20, depth=16, emission=9.412), "pt_render_tiles"),
+    # depth: 200 bounces with config 4's 9.4 are still fine; with a light of 2.4e3 they take the static kernel (fp64 sums:
+    # the windowed forms carry a depth of six bits and fit up to depth 29)
+    (dict(spheres=38, spp=16, depth=200, emission=9.412), "pt_render_tiles"),
+    (dict(spheres=38, spp=16, depth=200, emission=2.4e3), "pt_render_tiles_refr"),
+    (dict(spheres=38, spp=1, depth=29, emission=1e9), "pt_render_tiles_refr_pool"),   # one sample per chunk at the deepest depth that fits
+    (dict(spheres=38, spp=1, depth=30, emission=1e9), "pt_render_tiles_refr"),
+    # scenes with M_REFRACTION already sum without a bound; terms that reach 2^128 move them to the static kernel too
+    (dict(spheres=5, refr=1, emission=1e37), "pt_render_tiles_refr_pool"),
+    (dict(spheres=5, refr=1, emission=1e38), "pt_render_tiles_refr"),
+]
+
+
+@pytest.mark.parametrize("cls,kernel", SCALE_ROWS, ids=[f"{k}:{'+'.join(f'{a}={b}' for a, b in c.items())}" for c, k in SCALE_ROWS])
+def test_the_fixed_point_scale_s_other_inputs(pick, cls, kernel):
+    assert pick(PATH, **cls) == kernel
