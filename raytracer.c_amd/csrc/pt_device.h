@@ -341,17 +341,39 @@ struct PtLaunch
 #include <hip/hip_runtime.h>
 /* host-side launchers, defined next to the kernels in pt_kernel.hip */
 size_t pt_render_lds_bytes(const PtSceneView &scene);
-/* what a launch adds to the scene's content when the kernel is picked (pt_kernel.hip: pt_pick_table) */
-struct PtPickFacts
+/* the chunks a trace_path launch of a scene with M_REFRACTION takes at least when it has a chunk workspace (pt_plan_launch;
+ * rt_hip_suggest_chunks_depth suggests as many): pt_refr_pool_chunks_needed where that is a usable chunk count -- at most one
+ * chunk per sample, tile_count x chunks within the grid limit -- else 1 (max_depth > 29: the static kernels render it) */
+static inline uint32_t pt_refr_chunk_floor(const PtSceneView &scene, int32_t samples, int32_t max_depth, uint32_t tile_count)
 {
-  uint32_t integrator;
-  int32_t samples, max_depth; /* samples: per sample chunk */
+  if (!scene.any_refract)
+    return 1u;
+  const uint64_t need = pt_refr_pool_chunks_needed(samples, max_depth);
+  return (need >= 1u && need <= (uint64_t)samples && need * tile_count <= 0x7FFFFFFFull) ? (uint32_t)need : 1u;
+}
+/* The launch plan (pt_kernel.hip: pt_plan_launch): which member of the family runs a launch, with how many sample chunks, and
+ * which pools it needs -- the one place these are decided.  What the launch asks ... */
+struct PtPlanAsk
+{
+  uint32_t integrator;        /* 0 trace_path, 1 cast_ray */
+  int32_t samples, max_depth; /* samples per pixel of the whole launch */
+  double max_emission;        /* max |emission component| over all materials (pt_acc_scale_exp) */
+  uint32_t sample_chunks;     /* as requested by the caller */
+  bool have_chunk_ws;         /* the caller gave a chunk workspace */
+  uint32_t tile_count;
   bool have_park_ws;          /* the parked-walk kernels' ring workspace exists on the device */
   bool wide_pend_ok;          /* the pending-ray pool can be had at 4 x 512 stacks per slot */
-  int32_t launch_samples;     /* samples per pixel of the whole launch (all chunks): with max_emission, the fixed-point scale */
-  double max_emission;        /* max |emission component| over all materials (pt_acc_scale_exp) */
 };
-int pt_pick_kernel(const PtSceneView &scene, const PtPickFacts &facts);          /* -> index into the family */
+/* ... and what it gets */
+struct PtPlan
+{
+  int kernel;                          /* index into the family */
+  uint32_t sample_chunks;              /* what the kernel runs */
+  bool windowed;                       /* pixel sums are windowed (win_add): the chunk workspace has PT_ACC_WS_WORDS_WIN words per tile */
+  bool queued;                         /* parked walks: a tile per wave */
+  uint32_t pend_entries, pend_columns; /* the pending-ray pool it needs (pend_pool_for); 0 entries: none */
+};
+PtPlan pt_plan_launch(const PtSceneView &scene, const PtPlanAsk &ask);
 hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int which);
 /* entries per pending-ray stack a launch needs: max_depth + 2 where a material has two children (M_REFRACTION under trace_path,
  * M_REFLECTION | M_REFRACTION under cast_ray); one where none has -- nothing is ever pushed (a scene on the M_REFRACTION forms for
@@ -363,11 +385,6 @@ static inline uint32_t pt_pend_entries(const PtSceneView &scene, uint32_t integr
 }
 const char *pt_kernel_name_of(int which);
 int pt_kernel_count(void);
-bool pt_kernel_uses_pend_pool(int which);
-bool pt_kernel_is_queued(int which);
-bool pt_kernel_takes_chunks(int which);
-bool pt_kernel_is_windowed(int which); /* pixel sums are windowed (win_add): the chunk workspace has PT_ACC_WS_WORDS_WIN words per tile */
-uint32_t pt_kernel_pend_columns_of(int which);
 unsigned long long pt_kernel_launches(int which);
 uint32_t pt_pool_slots_per_xcd(bool park_pool); /* on the current device */
 #ifdef PT_DEV_KERNELS

@@ -35,7 +35,7 @@
  * pt_render_tiles_refr_pool (the same body for small sphere scenes with M_REFRACTION: windowed pixel sums, pending rays that
  * travel with a path), pt_render_tiles_tri_queued* (hierarchy scenes: parked walks; _refr: with M_REFRACTION), pt_render_tiles[..]_refr and
  * pt_whitted_tiles[..] (static body: refraction's two-child tree where the pooled kernel does not apply, and cast_ray,
- * raytracer.c:556-641), see pt_pick_kernel.
+ * raytracer.c:556-641): one list, PT_FAMILY below; which member a launch takes: pt_pick_kernel, inside pt_plan_launch.
  *
  * pt_render_tiles_v0 (development builds only, -DPT_DEV_KERNELS: kept for A/B and as the plainest statement of the algorithm): static
  * assignment lane = (pixel, sample slice), literal scan, fp64 partial sums combined by
@@ -62,8 +62,9 @@
  *   pt_body_pooled.h  render_tiles_pooled   (pt_render_tiles[_tri][_big][_chk], _pool_mem*, _refr_pool*)
  *   pt_body_queued.h  render_tiles_queued   (pt_render_tiles_tri_queued*: parked walks, also with M_REFRACTION)
  *   pt_body_static.h  render_tiles_static   (pt_render_tiles_v0, *_refr, pt_whitted_tiles*, *_mem)
- * This file keeps the kernel entry points (the family, by scene content), the table-building and self-test kernels, pt_untile,
- * and the host-side launchers (pt_pick_kernel, pt_launch_render) declared in pt_device.h.
+ * This file keeps the kernel family (PT_FAMILY: the entry points, their ids and properties), the table-building and self-test
+ * kernels, pt_untile, and the host side declared in pt_device.h: the launch plan (pt_plan_launch, around the pick table
+ * pt_pick_kernel) and the launchers (pt_launch_render).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -82,171 +83,155 @@
 #include "pt_body_queued.h"
 #include "pt_body_static.h"
 
-/* Kernel family pt_render_tiles[_tri][_big][_chk|_refr], picked by scene content
- * (pt_pick_kernel): "_tri" = scene has triangles; "_big" = the filter table is not in LDS
- * (more than PT_FILT_LDS_MAX primitives, or centres / radii beyond fp32's comfortable range):
- * table by scalar loads, NaN-safe compares, triangles through the hierarchy; "_chk" = scene
- * has M_CHECKERED materials (atan2_tab / frac1); "_refr" = scene has M_REFRACTION materials
- * (static body + pending second children in the pool; also covers M_CHECKERED) -- small staged sphere scenes take
- * pt_render_tiles_refr_pool, the pooled body, instead.
- * pt_render_tiles itself is the headline configuration: diffuse / mirror / emissive spheres,
- * small scene. */
-#define PT_KERNEL_G(name, bounds, CHECKER, TRIS, FILT_LDS, GEOM_LDS)                         \
-  extern "C" __global__ bounds void name(const PtLaunch L)                                  \
-  {                                                                                         \
-    render_tiles_pooled<CHECKER, TRIS, FILT_LDS, GEOM_LDS>(L);                              \
-  }
-#define PT_KERNEL(name, bounds, CHECKER, TRIS, FILT_LDS) PT_KERNEL_G(name, bounds, CHECKER, TRIS, FILT_LDS, true)
-PT_KERNEL(pt_render_tiles, __launch_bounds__(PT_BLOCK, PT_MIN_WAVES), false, false, true)
-PT_KERNEL(pt_render_tiles_big, __launch_bounds__(PT_BLOCK, PT_MIN_WAVES), false, false, false)
-PT_KERNEL(pt_render_tiles_tri, __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_TRI), false, true, true)
-PT_KERNEL(pt_render_tiles_tri_big, __launch_bounds__(PT_BLOCK, 4), false, true, false) /* 24 KB of traversal stacks: 4 workgroups per CU */
-/* the hierarchy kernels with parked walks; the pooled ones above are the table's park = NO rows (no ring workspace, or a scene beyond
- * fp32's comfortable range), and RT_HIP_KERNEL_VARIANT=2 of the development build for A/B */
+/* ---- the kernel family: ONE list, one line per member ----------------------------------------------------------------------
+ * Each line gives the member's id (what pt_pick_table names), its entry point, its __launch_bounds__, its properties and the
+ * body it instantiates.  The entry points, the ids (enum PtKernelId) and the rows of pt_kernels[] are all generated from it, in
+ * this order: rt_hip_kernel_launches(index) and the coverage table list the members in it.
+ *
+ * Names, by scene content (pt_pick_kernel): pt_render_tiles[_tri][_big][_chk|_refr]: "_tri" = scene has triangles; "_big" = the
+ * filter table is not in LDS (more than PT_FILT_LDS_MAX primitives, or centres / radii beyond fp32's comfortable range): table by
+ * scalar loads, NaN-safe compares, triangles through the hierarchy; "_chk" = scene has M_CHECKERED materials (atan2_tab / frac1);
+ * "_refr" = scene has M_REFRACTION materials (static body + pending second children in the pool; also covers M_CHECKERED).
+ * pt_render_tiles itself is the headline configuration: diffuse / mirror / emissive spheres, small scene.
+ *   pt_render_tiles_tri_queued*   hierarchy scenes with parked walks (_sph: round meshes, the probe is the triangles' bounding
+ *                                 sphere alone; _refr: with M_REFRACTION -- windowed sums in the workspace, pending second children
+ *                                 that travel with a path, also through the ring; _mem: spheres beyond the LDS staging budget next
+ *                                 to such a mesh, sphere geometry, materials and filter pairs from memory, the general probe).  The
+ *                                 pooled _tri / _tri_big kernels are the table's park = NO rows (no ring workspace, or a scene beyond
+ *                                 fp32's comfortable range) and RT_HIP_KERNEL_VARIANT=2 of the development build for A/B.  (No
+ *                                 _mem refraction form: at three waves it spills two doubles inside the trip loop, and scenes with
+ *                                 M_REFRACTION, more spheres than the staging holds AND a large mesh are the rarest class there is
+ *                                 -- they keep pt_render_tiles_mem.)
+ *   pt_render_tiles_*refr_pool*   M_REFRACTION on the pooled body: small sphere scenes, streamed sphere scenes (_mem: the
+ *                                 reference's own generator gives a fifth of its spheres M_REFRACTION, main.c:107-115, so a large
+ *                                 packed room is exactly this class), small scenes with a mesh (_tri).
+ *   pt_render_tiles_pool_mem*     scenes whose sphere geometry + materials exceed the LDS staging budget (pt_geom_in_lds: more than
+ *                                 256 spheres): the SAME pooled body -- job pool, swap, fixed-point sums, four rejection rounds per
+ *                                 trip, sample chunks -- with geometry and materials gathered from memory (PtSceneView.geom4 /
+ *                                 material: 32 + 64 bytes per sphere, L2-resident up to tens of thousands of spheres) and the filter
+ *                                 table streamed through scalar loads as in the _big kernels.  _s: sphere-only scenes within fp32's
+ *                                 comfortable range, with the small scenes' FORM of the filter -- sign tests, per-tile culling of
+ *                                 the primary trips, the walls pruned among themselves -- read from memory (stage_scene,
+ *                                 FILT_FROM_MEMORY); measured on rooms packed as main.c:65-138 would (tools/many_spheres.py,
+ *                                 profiles/r04_many_spheres.txt).  Until round 4 the 257th sphere dropped a scene onto
+ *                                 pt_render_tiles_mem, the static body with every material's code and a 2.7 KB private stack per lane.
+ *   pt_whitted_tiles[..]          cast_ray (raytracer.c:556-641): the static body with whitted_step, without a pending-ray stack
+ *                                 (scenes with a material that has both M_REFLECTION and M_REFRACTION take pt_whitted_tiles_mem).
+ *   pt_render_tiles_mem, pt_whitted_tiles_mem   beyond the staging budget (more than ~256 spheres, or thousands of meshes): the most
+ *                                 general static body -- every material, triangles through the hierarchy -- reading geometry and
+ *                                 materials from memory.  The O(n) sphere scan dominates such scenes whatever the kernel around it does.
+ *
+ * Properties (PtKernelProps), by name:
+ *   PEND_POOL    pushes pending second children: needs a slot of the pending-ray pool (rt_hip_shim.hip, pend_pool_for)
+ *   QUEUED       parked walks: a tile per WAVE (four work units per workgroup), filter pairs + traversal stacks in dynamic LDS
+ *   STAGES_NONE  geometry and tables from memory: no staged scene in LDS, whatever the scene's size
+ *   WIDE_PEND    4 x 512 stacks per pool slot (path ids that travel through the ring)
+ *   CHUNKS       takes sample_chunks > 1 (integer partial sums merged by pt_resolve_tiles)
+ *   WINDOWED     ... as windowed sums (win_add): PT_ACC_WS_WORDS_WIN words per tile of the chunk workspace */
+enum PtKernelProps : uint32_t
+{
+  PEND_POOL = 1u, QUEUED = 2u, STAGES_NONE = 4u, WIDE_PEND = 8u, CHUNKS = 16u, WINDOWED = 32u
+};
+
+/* launch bounds (waves per SIMD; PT_MIN_WAVES, _TRI, _CHK: pt_body_pooled.h).  `make variant DEFS=-DPT_MIN_WAVES_...` and
+ * tools/gpu_ab.py override them.  _tri_big: 24 KB of traversal stacks, 4 workgroups per CU. */
 #ifndef PT_MIN_WAVES_QUEUED
 #define PT_MIN_WAVES_QUEUED 4
 #endif
-extern "C" __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_QUEUED) void pt_render_tiles_tri_queued(const PtLaunch L)
-{
-  render_tiles_queued<false>(L);
-}
-extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_render_tiles_tri_queued_chk(const PtLaunch L)
-{
-  render_tiles_queued<true>(L);
-}
-/* round meshes: the probe is the triangles' bounding sphere alone (bvh_probe) */
-extern "C" __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_QUEUED) void pt_render_tiles_tri_queued_sph(const PtLaunch L)
-{
-  render_tiles_queued<false, true>(L);
-}
-extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_render_tiles_tri_queued_chk_sph(const PtLaunch L)
-{
-  render_tiles_queued<true, true>(L);
-}
-/* hierarchy scenes with M_REFRACTION: parked walks + windowed sums + pending second children that travel with a path, also
- * through the ring (render_tiles_queued, REFR); windowed sums in the workspace (global atomics): LDS as the other forms */
 #ifndef PT_MIN_WAVES_QUEUED_REFR
 #define PT_MIN_WAVES_QUEUED_REFR 3
 #endif
-extern "C" __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_QUEUED_REFR) void pt_render_tiles_tri_queued_refr(const PtLaunch L)
-{
-  render_tiles_queued<true, false, true>(L);
-}
-extern "C" __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_QUEUED_REFR) void pt_render_tiles_tri_queued_refr_sph(const PtLaunch L)
-{
-  render_tiles_queued<true, true, true>(L);
-}
-/* ... and the two forms for scenes whose SPHERES exceed the LDS staging budget next to such a mesh (render_tiles_queued,
- * GEOM_LDS = false: sphere geometry, materials and the spheres' filter pairs from memory); the probe is the general one */
-extern "C" __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_QUEUED) void pt_render_tiles_tri_queued_mem(const PtLaunch L)
-{
-  render_tiles_queued<false, false, false, false>(L);
-}
-extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_render_tiles_tri_queued_mem_chk(const PtLaunch L)
-{
-  render_tiles_queued<true, false, false, false>(L);
-}
-/* (no refraction form here: at three waves it spills two doubles inside the trip loop, and scenes with M_REFRACTION, more
- * spheres than the staging holds AND a large mesh are the rarest class there is -- they keep pt_render_tiles_mem) */
-/* small sphere scenes with M_REFRACTION on the pooled body (render_tiles_pooled, REFR) */
 #ifndef PT_MIN_WAVES_REFR_POOL
 #define PT_MIN_WAVES_REFR_POOL 4
 #endif
-extern "C" __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_REFR_POOL) void pt_render_tiles_refr_pool(const PtLaunch L)
-{
-  render_tiles_pooled<true, false, true, true, true>(L);
-}
-/* ... and the same for sphere scenes that are streamed (beyond the staging budget, or beyond ~85 spheres by preference): geometry and
- * materials from memory, the sign-form table by scalar loads, as pt_render_tiles_pool_mem_s -- the reference's own generator gives a
- * fifth of its spheres M_REFRACTION (main.c:107-115), so a large packed room is exactly this scene class */
-extern "C" __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_REFR_POOL) void pt_render_tiles_refr_pool_mem(const PtLaunch L)
-{
-  render_tiles_pooled<true, false, true, false, true>(L);
-}
-/* ... and for small scenes with a mesh (the flat filter + fp32 pre-test kernels' scene class) */
-extern "C" __global__ __launch_bounds__(PT_BLOCK, 3) void pt_render_tiles_tri_refr_pool(const PtLaunch L)
-{
-  render_tiles_pooled<true, true, true, true, true>(L);
-}
-PT_KERNEL(pt_render_tiles_chk, __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_CHK), true, false, true)
-PT_KERNEL(pt_render_tiles_big_chk, __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_CHK), true, false, false)
-PT_KERNEL(pt_render_tiles_tri_chk, __launch_bounds__(PT_BLOCK), true, true, true)
-PT_KERNEL(pt_render_tiles_tri_big_chk, __launch_bounds__(PT_BLOCK), true, true, false)
-/* Scenes whose sphere geometry + materials exceed the LDS staging budget (pt_geom_in_lds: more than 256 spheres): the SAME
- * pooled body -- job pool, swap, fixed-point sums, four rejection rounds per trip, sample chunks -- with geometry and
- * materials gathered from memory (PtSceneView.geom4 / material: 32 + 64 bytes per sphere, L2-resident up to tens of
- * thousands of spheres) and the filter table streamed through scalar loads as in the _big kernels.  Until round 4 the
- * 257th sphere dropped a scene onto pt_render_tiles_mem, the static body with every material's code and a 2.7 KB
- * private stack per lane (still the kernel of such scenes WITH M_REFRACTION, whose throughput is unbounded). */
-PT_KERNEL_G(pt_render_tiles_pool_mem, __launch_bounds__(PT_BLOCK, PT_MIN_WAVES), false, false, false, false)
-PT_KERNEL_G(pt_render_tiles_pool_mem_chk, __launch_bounds__(PT_BLOCK), true, false, false, false)
-PT_KERNEL_G(pt_render_tiles_pool_mem_tri, __launch_bounds__(PT_BLOCK, 4), false, true, false, false)
-PT_KERNEL_G(pt_render_tiles_pool_mem_tri_chk, __launch_bounds__(PT_BLOCK), true, true, false, false)
-/* ... and, for sphere-only scenes within fp32's comfortable range (no centre or radius beyond 1e17), with the small scenes' FORM
- * of the filter -- sign tests, per-tile culling of the primary trips, the walls pruned among themselves -- read from memory
- * (stage_scene, FILT_FROM_MEMORY).  Measured on rooms packed as main.c:65-138 would (tools/many_spheres.py, profiles/r04_many_spheres.txt). */
-PT_KERNEL_G(pt_render_tiles_pool_mem_s, __launch_bounds__(PT_BLOCK, PT_MIN_WAVES), false, false, true, false)
-PT_KERNEL_G(pt_render_tiles_pool_mem_s_chk, __launch_bounds__(PT_BLOCK), true, false, true, false)
-#undef PT_KERNEL
-#undef PT_KERNEL_G
-
-/* launch bounds of the M_REFRACTION kernels (waves per SIMD).  Until round 4 they had none: 203-232 VGPRs and a 2.7 KB private
- * stack, two waves per SIMD.  With the pending rays in the pool (PendStack) and the material code's library calls gone
- * (atan2_tab, cube, frac1) the sphere kernels need 127 VGPRs and the mesh kernels ~150, without scratch */
+/* the static M_REFRACTION kernels.  Until round 4 they had none: 203-232 VGPRs and a 2.7 KB private stack, two waves per SIMD.
+ * With the pending rays in the pool (PendStack) and the material code's library calls gone (atan2_tab, cube, frac1) the sphere
+ * kernels need 127 VGPRs and the mesh kernels ~150, without scratch */
 #ifndef PT_MIN_WAVES_REFR
 #define PT_MIN_WAVES_REFR 4
 #endif
 #ifndef PT_MIN_WAVES_REFR_TRI
 #define PT_MIN_WAVES_REFR_TRI 3
 #endif
-#define PT_KERNEL_STATIC(name, WAVES, VARIANT, REFRACT, CHECKER, TRIS, FILT_LDS)             \
-  extern "C" __global__ __launch_bounds__(PT_BLOCK, WAVES) void name(const PtLaunch L)      \
-  {                                                                                         \
-    render_tiles_static<VARIANT, REFRACT, CHECKER, TRIS, FILT_LDS, 0, true>(L);             \
-  }
-#ifdef PT_DEV_KERNELS
-PT_KERNEL_STATIC(pt_render_tiles_v0, 1, 0, false, true, true, false)
-#endif
-PT_KERNEL_STATIC(pt_render_tiles_refr, PT_MIN_WAVES_REFR, 1, true, true, false, true)
-PT_KERNEL_STATIC(pt_render_tiles_big_refr, PT_MIN_WAVES_REFR, 1, true, true, false, false)
-PT_KERNEL_STATIC(pt_render_tiles_tri_refr, PT_MIN_WAVES_REFR_TRI, 1, true, true, true, true)
-PT_KERNEL_STATIC(pt_render_tiles_tri_big_refr, PT_MIN_WAVES_REFR_TRI, 1, true, true, true, false)
-#undef PT_KERNEL_STATIC
-
-/* cast_ray kernels: the static body with whitted_step, without a pending-ray stack (scenes with
- * a material that has both M_REFLECTION and M_REFRACTION take pt_whitted_tiles_mem) */
-/* Launch bounds measured on the MI355X (1920x1080 x 64 spp, ms at 4 / 3 / 2 waves per SIMD): spheres
- * (config 4) 8.2 / 8.4 / 9.4; small mesh (config 3) 6.2 / 5.2 / 6.5; hierarchy (config 5, 4K x 8 spp)
- * 8.6 / 8.1 / 8.9.  None of the three is free of scratch below 2 waves (228-308 B at 4, 44-156 B at 3). */
+/* cast_ray, measured on the MI355X (1920x1080 x 64 spp, ms at 4 / 3 / 2 waves per SIMD): spheres (config 4) 8.2 / 8.4 / 9.4;
+ * small mesh (config 3) 6.2 / 5.2 / 6.5; hierarchy (config 5, 4K x 8 spp) 8.6 / 8.1 / 8.9.  None of the three is free of
+ * scratch below 2 waves (228-308 B at 4, 44-156 B at 3). */
 #ifndef PT_MIN_WAVES_WHITTED
 #define PT_MIN_WAVES_WHITTED 4
 #endif
 #ifndef PT_MIN_WAVES_WHITTED_TRI
 #define PT_MIN_WAVES_WHITTED_TRI 3
 #endif
-#define PT_KERNEL_WHITTED(name, WAVES, TRIS, FILT_LDS)                                       \
-  extern "C" __global__ __launch_bounds__(PT_BLOCK, WAVES) void name(const PtLaunch L)      \
-  {                                                                                         \
-    render_tiles_static<1, false, true, TRIS, FILT_LDS, 1, true>(L);                        \
-  }
-PT_KERNEL_WHITTED(pt_whitted_tiles, PT_MIN_WAVES_WHITTED, false, true)
-PT_KERNEL_WHITTED(pt_whitted_tiles_big, PT_MIN_WAVES_WHITTED, false, false)
-PT_KERNEL_WHITTED(pt_whitted_tiles_tri, PT_MIN_WAVES_WHITTED_TRI, true, true)
-PT_KERNEL_WHITTED(pt_whitted_tiles_tri_big, PT_MIN_WAVES_WHITTED_TRI, true, false)
-#undef PT_KERNEL_WHITTED
 
-/* Scenes whose sphere geometry + materials exceed the LDS staging budget (pt_geom_in_lds: more
- * than ~256 spheres, or thousands of meshes): the most general static body -- every material,
- * triangles through the hierarchy -- reading geometry and materials from memory.  The O(n)
- * sphere scan dominates such scenes whatever the kernel around it does. */
-extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_render_tiles_mem(const PtLaunch L)
+/* bodies: render_tiles_pooled<CHECKER, TRIS, FILT_LDS, GEOM_LDS[, REFR]>, render_tiles_queued<CHECKER[, SPHERE_PROBE, REFR,
+ * GEOM_LDS]>, render_tiles_static<VARIANT, REFRACT, CHECKER, TRIS, FILT_LDS, WHITTED, GEOM_LDS> */
+#define PT_FAMILY(X) \
+  X(K_TILES,               pt_render_tiles,                     (PT_BLOCK, PT_MIN_WAVES),             CHUNKS,                                             render_tiles_pooled<false, false, true, true>) \
+  X(K_BIG,                 pt_render_tiles_big,                 (PT_BLOCK, PT_MIN_WAVES),             CHUNKS,                                             render_tiles_pooled<false, false, false, true>) \
+  X(K_TRI,                 pt_render_tiles_tri,                 (PT_BLOCK, PT_MIN_WAVES_TRI),         CHUNKS,                                             render_tiles_pooled<false, true, true, true>) \
+  X(K_TRI_BIG,             pt_render_tiles_tri_big,             (PT_BLOCK, 4),                        CHUNKS,                                             render_tiles_pooled<false, true, false, true>) \
+  X(K_CHK,                 pt_render_tiles_chk,                 (PT_BLOCK, PT_MIN_WAVES_CHK),         CHUNKS,                                             render_tiles_pooled<true, false, true, true>) \
+  X(K_BIG_CHK,             pt_render_tiles_big_chk,             (PT_BLOCK, PT_MIN_WAVES_CHK),         CHUNKS,                                             render_tiles_pooled<true, false, false, true>) \
+  X(K_TRI_CHK,             pt_render_tiles_tri_chk,             (PT_BLOCK),                           CHUNKS,                                             render_tiles_pooled<true, true, true, true>) \
+  X(K_TRI_BIG_CHK,         pt_render_tiles_tri_big_chk,         (PT_BLOCK),                           CHUNKS,                                             render_tiles_pooled<true, true, false, true>) \
+  X(K_REFR,                pt_render_tiles_refr,                (PT_BLOCK, PT_MIN_WAVES_REFR),        PEND_POOL,                                          render_tiles_static<1, true, true, false, true, 0, true>) \
+  X(K_BIG_REFR,            pt_render_tiles_big_refr,            (PT_BLOCK, PT_MIN_WAVES_REFR),        PEND_POOL,                                          render_tiles_static<1, true, true, false, false, 0, true>) \
+  X(K_TRI_REFR,            pt_render_tiles_tri_refr,            (PT_BLOCK, PT_MIN_WAVES_REFR_TRI),    PEND_POOL,                                          render_tiles_static<1, true, true, true, true, 0, true>) \
+  X(K_TRI_BIG_REFR,        pt_render_tiles_tri_big_refr,        (PT_BLOCK, PT_MIN_WAVES_REFR_TRI),    PEND_POOL,                                          render_tiles_static<1, true, true, true, false, 0, true>) \
+  X(K_WHITTED,             pt_whitted_tiles,                    (PT_BLOCK, PT_MIN_WAVES_WHITTED),     0,                                                  render_tiles_static<1, false, true, false, true, 1, true>) \
+  X(K_WHITTED_BIG,         pt_whitted_tiles_big,                (PT_BLOCK, PT_MIN_WAVES_WHITTED),     0,                                                  render_tiles_static<1, false, true, false, false, 1, true>) \
+  X(K_WHITTED_TRI,         pt_whitted_tiles_tri,                (PT_BLOCK, PT_MIN_WAVES_WHITTED_TRI), 0,                                                  render_tiles_static<1, false, true, true, true, 1, true>) \
+  X(K_WHITTED_TRI_BIG,     pt_whitted_tiles_tri_big,            (PT_BLOCK, PT_MIN_WAVES_WHITTED_TRI), 0,                                                  render_tiles_static<1, false, true, true, false, 1, true>) \
+  X(K_MEM,                 pt_render_tiles_mem,                 (PT_BLOCK),                           PEND_POOL,                                          render_tiles_static<1, true, true, true, false, 0, false>) \
+  X(K_WHITTED_MEM,         pt_whitted_tiles_mem,                (PT_BLOCK),                           PEND_POOL,                                          render_tiles_static<1, false, true, true, false, 2, false>) \
+  X(K_TRI_QUEUED,          pt_render_tiles_tri_queued,          (PT_BLOCK, PT_MIN_WAVES_QUEUED),      QUEUED | CHUNKS,                                    render_tiles_queued<false>) \
+  X(K_TRI_QUEUED_CHK,      pt_render_tiles_tri_queued_chk,      (PT_BLOCK),                           QUEUED | CHUNKS,                                    render_tiles_queued<true>) \
+  X(K_TRI_QUEUED_SPH,      pt_render_tiles_tri_queued_sph,      (PT_BLOCK, PT_MIN_WAVES_QUEUED),      QUEUED | CHUNKS,                                    render_tiles_queued<false, true>) \
+  X(K_POOL_MEM,            pt_render_tiles_pool_mem,            (PT_BLOCK, PT_MIN_WAVES),             STAGES_NONE | CHUNKS,                               render_tiles_pooled<false, false, false, false>) \
+  X(K_POOL_MEM_CHK,        pt_render_tiles_pool_mem_chk,        (PT_BLOCK),                           STAGES_NONE | CHUNKS,                               render_tiles_pooled<true, false, false, false>) \
+  X(K_POOL_MEM_TRI,        pt_render_tiles_pool_mem_tri,        (PT_BLOCK, 4),                        STAGES_NONE | CHUNKS,                               render_tiles_pooled<false, true, false, false>) \
+  X(K_POOL_MEM_TRI_CHK,    pt_render_tiles_pool_mem_tri_chk,    (PT_BLOCK),                           STAGES_NONE | CHUNKS,                               render_tiles_pooled<true, true, false, false>) \
+  X(K_POOL_MEM_S,          pt_render_tiles_pool_mem_s,          (PT_BLOCK, PT_MIN_WAVES),             STAGES_NONE | CHUNKS,                               render_tiles_pooled<false, false, true, false>) \
+  X(K_POOL_MEM_S_CHK,      pt_render_tiles_pool_mem_s_chk,      (PT_BLOCK),                           STAGES_NONE | CHUNKS,                               render_tiles_pooled<true, false, true, false>) \
+  X(K_REFR_POOL,           pt_render_tiles_refr_pool,           (PT_BLOCK, PT_MIN_WAVES_REFR_POOL),   PEND_POOL | CHUNKS | WINDOWED,                      render_tiles_pooled<true, false, true, true, true>) \
+  X(K_REFR_POOL_MEM,       pt_render_tiles_refr_pool_mem,       (PT_BLOCK, PT_MIN_WAVES_REFR_POOL),   PEND_POOL | STAGES_NONE | CHUNKS | WINDOWED,        render_tiles_pooled<true, false, true, false, true>) \
+  X(K_TRI_REFR_POOL,       pt_render_tiles_tri_refr_pool,       (PT_BLOCK, 3),                        PEND_POOL | CHUNKS | WINDOWED,                      render_tiles_pooled<true, true, true, true, true>) \
+  X(K_TRI_QUEUED_REFR,     pt_render_tiles_tri_queued_refr,     (PT_BLOCK, PT_MIN_WAVES_QUEUED_REFR), PEND_POOL | QUEUED | WIDE_PEND | CHUNKS | WINDOWED, render_tiles_queued<true, false, true>) \
+  X(K_TRI_QUEUED_REFR_SPH, pt_render_tiles_tri_queued_refr_sph, (PT_BLOCK, PT_MIN_WAVES_QUEUED_REFR), PEND_POOL | QUEUED | WIDE_PEND | CHUNKS | WINDOWED, render_tiles_queued<true, true, true>) \
+  X(K_TRI_QUEUED_CHK_SPH,  pt_render_tiles_tri_queued_chk_sph,  (PT_BLOCK),                           QUEUED | CHUNKS,                                    render_tiles_queued<true, true>) \
+  X(K_TRI_QUEUED_MEM,      pt_render_tiles_tri_queued_mem,      (PT_BLOCK, PT_MIN_WAVES_QUEUED),      QUEUED | STAGES_NONE | CHUNKS,                      render_tiles_queued<false, false, false, false>) \
+  X(K_TRI_QUEUED_MEM_CHK,  pt_render_tiles_tri_queued_mem_chk,  (PT_BLOCK),                           QUEUED | STAGES_NONE | CHUNKS,                      render_tiles_queued<true, false, false, false>)
+/* the literal single-phase scan: development builds only (RT_HIP_KERNEL_VARIANT=0), the last member */
+#ifdef PT_DEV_KERNELS
+#define PT_FAMILY_DEV(X) X(K_V0, pt_render_tiles_v0, (PT_BLOCK), 0, render_tiles_static<0, false, true, true, false, 0, true>)
+#else
+#define PT_FAMILY_DEV(X)
+#endif
+
+#define PT_ENTRY(id, name, bounds, props, ...) \
+  extern "C" __global__ __launch_bounds__ bounds void name(const PtLaunch L) { __VA_ARGS__(L); }
+PT_FAMILY(PT_ENTRY)
+PT_FAMILY_DEV(PT_ENTRY)
+#undef PT_ENTRY
+
+#define PT_ID(id, ...) id,
+enum PtKernelId
 {
-  render_tiles_static<1, true, true, true, false, 0, false>(L);
-}
-extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_whitted_tiles_mem(const PtLaunch L)
+  PT_FAMILY(PT_ID) PT_FAMILY_DEV(PT_ID) K_COUNT
+};
+#undef PT_ID
+typedef void (*PtKernelFn)(const PtLaunch);
+struct PtKernelInfo
 {
-  render_tiles_static<1, false, true, true, false, 2, false>(L);
-}
+  const char *name;
+  PtKernelFn fn;
+  uint32_t props; /* PtKernelProps */
+  bool has(uint32_t p) const { return (props & p) != 0u; }
+  uint32_t pend_columns() const { return has(WIDE_PEND) ? 4u * 512u : PT_PEND_COLUMNS; }
+};
+#define PT_INFO(id, name, bounds, props, ...) {#name, name, props},
+static const PtKernelInfo pt_kernels[K_COUNT] = {PT_FAMILY(PT_INFO) PT_FAMILY_DEV(PT_INFO)};
+#undef PT_INFO
 
 /* Second pass of a chunked render: per-tile fixed-point sums -> float3 + tonemapped bytes. */
 extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const PtLaunch L)
@@ -658,65 +643,6 @@ size_t pt_render_lds_bytes(const PtSceneView &sc)
   return doubles * sizeof(double);
 }
 
-/* The kernel family: one row per member. */
-enum PtKernelId
-{
-  K_TILES = 0, K_BIG, K_TRI, K_TRI_BIG,
-  K_CHK, K_BIG_CHK, K_TRI_CHK, K_TRI_BIG_CHK,
-  K_REFR, K_BIG_REFR, K_TRI_REFR, K_TRI_BIG_REFR,
-  K_WHITTED, K_WHITTED_BIG, K_WHITTED_TRI, K_WHITTED_TRI_BIG,
-  K_MEM, K_WHITTED_MEM,
-  K_TRI_QUEUED, K_TRI_QUEUED_CHK, K_TRI_QUEUED_SPH,
-  K_POOL_MEM, K_POOL_MEM_CHK, K_POOL_MEM_TRI, K_POOL_MEM_TRI_CHK, K_POOL_MEM_S, K_POOL_MEM_S_CHK,
-  K_REFR_POOL, K_REFR_POOL_MEM, K_TRI_REFR_POOL,
-  K_TRI_QUEUED_REFR, K_TRI_QUEUED_REFR_SPH, K_TRI_QUEUED_CHK_SPH,
-  K_TRI_QUEUED_MEM, K_TRI_QUEUED_MEM_CHK,
-#ifdef PT_DEV_KERNELS
-  K_V0, /* the literal single-phase scan: development builds only (RT_HIP_KERNEL_VARIANT=0) */
-#endif
-  K_COUNT
-};
-typedef void (*PtKernelFn)(const PtLaunch);
-struct PtKernelInfo
-{
-  const char *name;
-  PtKernelFn fn;
-  bool pend_pool;    /* pushes pending second children: needs a slot of the pending-ray pool (rt_hip_shim.hip, pend_pool_for) */
-  bool queued;       /* parked walks: a tile per WAVE (four work units per workgroup), filter pairs + traversal stacks in dynamic LDS */
-  bool stages_none;  /* geometry and tables from memory: no staged scene in LDS, whatever the scene's size */
-  bool wide_pend;    /* 4 x 512 stacks per pool slot (path ids that travel through the ring) */
-  bool chunks;       /* takes sample_chunks > 1 (integer partial sums merged by pt_resolve_tiles) */
-  bool windowed;     /* ... as windowed sums (win_add): PT_ACC_WS_WORDS_WIN words per tile of the chunk workspace */
-};
-#define PT_K(fn, pend, queued, none, wide, chunks) {#fn, fn, pend, queued, none, wide, chunks, false}
-#define PT_KW(fn, pend, queued, none, wide) {#fn, fn, pend, queued, none, wide, true, true}
-static const PtKernelInfo pt_kernels[K_COUNT] = {
-    PT_K(pt_render_tiles, false, false, false, false, true),          PT_K(pt_render_tiles_big, false, false, false, false, true),
-    PT_K(pt_render_tiles_tri, false, false, false, false, true),      PT_K(pt_render_tiles_tri_big, false, false, false, false, true),
-    PT_K(pt_render_tiles_chk, false, false, false, false, true),      PT_K(pt_render_tiles_big_chk, false, false, false, false, true),
-    PT_K(pt_render_tiles_tri_chk, false, false, false, false, true),  PT_K(pt_render_tiles_tri_big_chk, false, false, false, false, true),
-    PT_K(pt_render_tiles_refr, true, false, false, false, false),     PT_K(pt_render_tiles_big_refr, true, false, false, false, false),
-    PT_K(pt_render_tiles_tri_refr, true, false, false, false, false), PT_K(pt_render_tiles_tri_big_refr, true, false, false, false, false),
-    PT_K(pt_whitted_tiles, false, false, false, false, false),        PT_K(pt_whitted_tiles_big, false, false, false, false, false),
-    PT_K(pt_whitted_tiles_tri, false, false, false, false, false),    PT_K(pt_whitted_tiles_tri_big, false, false, false, false, false),
-    PT_K(pt_render_tiles_mem, true, false, false, false, false),      PT_K(pt_whitted_tiles_mem, true, false, false, false, false),
-    PT_K(pt_render_tiles_tri_queued, false, true, false, false, true), PT_K(pt_render_tiles_tri_queued_chk, false, true, false, false, true),
-    PT_K(pt_render_tiles_tri_queued_sph, false, true, false, false, true),
-    PT_K(pt_render_tiles_pool_mem, false, false, true, false, true),  PT_K(pt_render_tiles_pool_mem_chk, false, false, true, false, true),
-    PT_K(pt_render_tiles_pool_mem_tri, false, false, true, false, true), PT_K(pt_render_tiles_pool_mem_tri_chk, false, false, true, false, true),
-    PT_K(pt_render_tiles_pool_mem_s, false, false, true, false, true), PT_K(pt_render_tiles_pool_mem_s_chk, false, false, true, false, true),
-    PT_KW(pt_render_tiles_refr_pool, true, false, false, false), PT_KW(pt_render_tiles_refr_pool_mem, true, false, true, false),
-    PT_KW(pt_render_tiles_tri_refr_pool, true, false, false, false),
-    PT_KW(pt_render_tiles_tri_queued_refr, true, true, false, true), PT_KW(pt_render_tiles_tri_queued_refr_sph, true, true, false, true),
-    PT_K(pt_render_tiles_tri_queued_chk_sph, false, true, false, false, true),
-    PT_K(pt_render_tiles_tri_queued_mem, false, true, true, false, true), PT_K(pt_render_tiles_tri_queued_mem_chk, false, true, true, false, true),
-#ifdef PT_DEV_KERNELS
-    PT_K(pt_render_tiles_v0, false, false, false, false, false),
-#endif
-};
-#undef PT_K
-#undef PT_KW
-
 /* ---- which member a launch takes: ONE table ------------------------------------------------------------------------------
  * A launch is classified by the six things the family is split by, and the first row of pt_pick_table that matches names the
  * kernel.  The fallbacks (no ring workspace, windowed sums that do not fit, a pending-ray pool that could not be had at
@@ -812,6 +738,17 @@ static bool pt_row_matches(const PtPickRow &r, const PtPickKey &k)
          ok(r.round, k.round) && ok(r.fit, k.fit);
 }
 
+/* what a launch adds to the scene's content when the kernel is picked (pt_plan_launch fills it in) */
+struct PtPickFacts
+{
+  uint32_t integrator;
+  int32_t samples, max_depth; /* samples: per sample chunk */
+  bool have_park_ws;          /* the parked-walk kernels' ring workspace exists on the device */
+  bool wide_pend_ok;          /* the pending-ray pool can be had at 4 x 512 stacks per slot */
+  int32_t launch_samples;     /* samples per pixel of the whole launch (all chunks): with max_emission, the fixed-point scale */
+  double max_emission;        /* max |emission component| over all materials (pt_acc_scale_exp) */
+};
+
 PtPickKey pt_classify(const PtSceneView &scene, const PtPickFacts &f)
 {
   PtPickKey k;
@@ -877,7 +814,7 @@ static int pt_dev_pick(PtPickKey &k)
 }
 #endif
 
-int pt_pick_kernel(const PtSceneView &scene, const PtPickFacts &f)
+static int pt_pick_kernel(const PtSceneView &scene, const PtPickFacts &f)
 {
   PtPickKey k = pt_classify(scene, f);
 #ifdef PT_DEV_KERNELS
@@ -893,13 +830,52 @@ int pt_pick_kernel(const PtSceneView &scene, const PtPickFacts &f)
   return -1; /* unreachable: the table's last rows of every (integ, stage, mesh) block match ANY of the rest -- pinned by tests/test_pick_table.py */
 }
 
+/* ---- how a launch runs: its kernel, the sample chunks that kernel runs and the pools it needs, decided HERE ----------------------
+ * rt_hip_render_tiles_chunked, rt_hip_suggest_chunks_depth, rt_hip_kernel_name and rt_hip_kernel_for_class ask pt_plan_launch and
+ * re-decide nothing.  In this order:
+ *   1. a trace_path launch of a scene with M_REFRACTION that was given a chunk workspace gets at least as many chunks as the
+ *      windowed sums of the pooled / parked-walk forms need (pt_refr_chunk_floor) -- the image does not depend on the chunk
+ *      count, and the workspace's size does not either; without a workspace it keeps its one chunk, and where that does not fit
+ *      the table's fit = NO row (the static kernel of the family) renders it;
+ *   2. a trace_path launch of a scene without M_REFRACTION whose fixed-point sums do not fit (pt_fixed_sums_fit) would take the
+ *      windowed chunk record, six times the plain one its caller may have sized the workspace for
+ *      (rt_hip_scene_chunk_workspace_bytes): it renders its samples in one chunk;
+ *   3. the kernel: pt_pick_kernel for the samples of one chunk;
+ *   4. a kernel that does not take chunks (the static bodies: cast_ray, the fit = NO rows of M_REFRACTION) runs one -- the pick
+ *      of step 3 stays the one made for the chunks asked for.
+ * Host arithmetic only, no HIP call: it runs on every launch, and without a device. */
+PtPlan pt_plan_launch(const PtSceneView &scene, const PtPlanAsk &a)
+{
+  const bool trace_path = a.integrator != 1u;
+  uint32_t chunks = a.sample_chunks > 1u ? a.sample_chunks : 1u;
+  if (trace_path && a.have_chunk_ws)
+  {
+    const uint32_t need = pt_refr_chunk_floor(scene, a.samples, a.max_depth, a.tile_count);
+    if (need > chunks)
+      chunks = need;
+  }
+  if (trace_path && !scene.any_refract && !pt_fixed_sums_fit(a.max_emission, a.samples, a.max_depth))
+    chunks = 1u;
+  const int32_t samples_per_chunk = (int32_t)(((int64_t)a.samples + chunks - 1) / chunks);
+  const PtPickFacts facts = {a.integrator, samples_per_chunk, a.max_depth, a.have_park_ws, a.wide_pend_ok, a.samples, a.max_emission};
+  PtPlan p = {};
+  p.kernel = pt_pick_kernel(scene, facts);
+  if (p.kernel < 0)
+    return p; /* unreachable (pt_pick_kernel); pt_launch_render refuses it */
+  const PtKernelInfo &k = pt_kernels[p.kernel];
+  p.sample_chunks = k.has(CHUNKS) ? chunks : 1u;
+  p.windowed = k.has(WINDOWED);
+  p.queued = k.has(QUEUED);
+  if (k.has(PEND_POOL))
+  {
+    p.pend_entries = pt_pend_entries(scene, a.integrator, a.max_depth);
+    p.pend_columns = k.pend_columns();
+  }
+  return p;
+}
+
 const char *pt_kernel_name_of(int which) { return which >= 0 && which < K_COUNT ? pt_kernels[which].name : ""; }
 int pt_kernel_count(void) { return K_COUNT; }
-bool pt_kernel_uses_pend_pool(int which) { return pt_kernels[which].pend_pool; }
-bool pt_kernel_is_queued(int which) { return pt_kernels[which].queued; }
-bool pt_kernel_takes_chunks(int which) { return pt_kernels[which].chunks; }
-bool pt_kernel_is_windowed(int which) { return pt_kernels[which].windowed; }
-uint32_t pt_kernel_pend_columns_of(int which) { return pt_kernels[which].wide_pend ? 4u * 512u : PT_PEND_COLUMNS; }
 
 /* launches per family member in this process (rt_hip_kernel_launches): what a test run actually exercised */
 static std::atomic<unsigned long long> pt_launch_counts[K_COUNT];
@@ -924,7 +900,7 @@ uint32_t pt_pool_slots_per_xcd(bool park_pool)
   int most = 1;
   for (int k = 0; k < K_COUNT; k++)
   {
-    if (!(park_pool ? pt_kernels[k].queued : pt_kernels[k].pend_pool))
+    if (!pt_kernels[k].has(park_pool ? QUEUED : PEND_POOL))
       continue;
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(pt_kernels[k].fn), PT_BLOCK, 0) == hipSuccess)
@@ -990,18 +966,18 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
   size_t lds_bytes = pt_render_lds_bytes(launch.scene) + extra_lds;
   const PtKernelInfo &k = pt_kernels[which];
   const PtKernelFn kernel = k.fn;
-  if (k.stages_none)
+  if (k.has(STAGES_NONE))
     lds_bytes = extra_lds; /* the in-memory pooled kernels stage nothing, whatever the scene's size */
-  if (k.pend_pool && (launch.pend_ws == nullptr || launch.pend_entries < pt_pend_entries(launch.scene, launch.integrator, launch.max_depth) ||
-                      launch.pend_slot_doubles < (uint64_t)launch.pend_entries * PT_PEND_FIELDS_HOST * pt_kernel_pend_columns_of(which)))
+  if (k.has(PEND_POOL) && (launch.pend_ws == nullptr || launch.pend_entries < pt_pend_entries(launch.scene, launch.integrator, launch.max_depth) ||
+                      launch.pend_slot_doubles < (uint64_t)launch.pend_entries * PT_PEND_FIELDS_HOST * k.pend_columns()))
     return hipErrorInvalidValue; /* a kernel with a pending-ray stack needs its pool, wide enough (rt_hip_shim.hip: pend_pool_for) */
-  const bool queued = k.queued;
+  const bool queued = k.has(QUEUED);
   if (queued && (launch.park_ws == nullptr || launch.park_slots_per_xcd == 0u))
     return hipErrorInvalidValue; /* the parked-walk kernels never run without their workspace (pt_pick_kernel: park) */
-  if (launch.sample_chunks > 1 && !k.chunks)
+  if (launch.sample_chunks > 1 && !k.has(CHUNKS))
     return hipErrorInvalidValue;
   if (queued) /* the spheres' filter pairs (staged forms), then per-lane traversal stacks (24-bit entries) sized by the tree, after the staged scene */
-    lds_bytes += (k.stages_none ? (size_t)0 : (size_t)pt_filt_pair_slots(launch.scene.n_spheres) * 8u) +
+    lds_bytes += (k.has(STAGES_NONE) ? (size_t)0 : (size_t)pt_filt_pair_slots(launch.scene.n_spheres) * 8u) +
                  (((size_t)max(launch.scene.bvh_depth, 1u) * PT_BLOCK * 3u + 15u) & ~(size_t)15u);
   if (lds_bytes > 64 * 1024)
   { /* the attribute belongs to the (kernel, current device) pair: set whenever it is needed -- a process-wide
@@ -1013,9 +989,9 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
   }
   if (launch.sample_chunks > 1)
   {
-    if ((launch.acc_windows != 0u) != k.windowed || launch.acc_ws == nullptr)
+    if ((launch.acc_windows != 0u) != k.has(WINDOWED) || launch.acc_ws == nullptr)
       return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(launch.acc_ws, 0, (size_t)launch.tile_count * (k.windowed ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long), stream);
+    hipError_t e = hipMemsetAsync(launch.acc_ws, 0, (size_t)launch.tile_count * (k.has(WINDOWED) ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long), stream);
     if (e != hipSuccess)
       return e;
   }

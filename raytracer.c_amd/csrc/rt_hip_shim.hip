@@ -1088,21 +1088,25 @@ int rt_hip_scene_hull_facets(const RtHipScene *scene, uint32_t *n_plus, uint32_t
   return 0;
 }
 
+/* the scene has the parked-walk workspace, or would get it at its first launch (rt_hip_render_tiles_chunked acquires it) */
+static bool park_ws_expected(const RtHipScene *scene)
+{
+  std::lock_guard<std::mutex> lock(scene->table_mutex);
+  /* (a scene that has met its workspace keeps it, whatever is injected later; one that has not yet would not get it now) */
+  return scene->park_tried ? scene->park_ws != nullptr : (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_PARK_WS) == 0;
+}
+
 const char *rt_hip_kernel_name(const RtHipScene *scene, uint32_t integrator)
 {
   if (!scene)
     return "";
   /* a scene whose parked-walk workspace could not be allocated runs on the lane-waiting kernels: report what a launch
    * takes, so that an out-of-memory fallback cannot pass as a measurement of the parked-walk kernels.  What is assumed of
-   * the launch itself: sums that fit, a pending-ray pool of full width -- rt_hip_last_launch_kernel() has the fact. */
-  bool no_ws;
-  {
-    std::lock_guard<std::mutex> lock(scene->table_mutex);
-    /* (a scene that has met its workspace keeps it, whatever is injected later; one that has not yet would not get it now) */
-    no_ws = scene->park_tried ? scene->park_ws == nullptr : (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_PARK_WS) != 0;
-  }
-  const PtPickFacts facts = {integrator, 1, 0, !no_ws, !(g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_WIDE_PEND), 1, scene->max_emission};
-  return pt_kernel_name_of(pt_pick_kernel(scene->view, facts));
+   * the launch itself: sums that fit (one sample at depth 0, one chunk), a pending-ray pool of full width --
+   * rt_hip_last_launch_kernel() has the fact. */
+  const PtPlanAsk ask = {.integrator = integrator, .samples = 1, .max_depth = 0, .max_emission = scene->max_emission, .sample_chunks = 1,
+                         .have_park_ws = park_ws_expected(scene), .wide_pend_ok = !(g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_WIDE_PEND)};
+  return pt_kernel_name_of(pt_plan_launch(scene->view, ask).kernel);
 }
 
 const char *rt_hip_last_launch_kernel(void) { return pt_kernel_name_of(g_last_kernel); }
@@ -1133,9 +1137,10 @@ const char *rt_hip_kernel_for_class(const RtHipSceneClass *c)
   v.any_mirror_glass = c->any_mirror_glass ? 1u : 0u;
   v.wide_range = c->wide_range ? 1u : 0u;
   v.mesh_round = c->mesh_round ? 1u : 0u;
-  const PtPickFacts facts = {c->integrator, c->samples_per_chunk, c->max_depth, c->have_park_ws != 0, c->wide_pend_ok != 0,
-                             c->samples_per_chunk, c->max_emission};
-  return pt_kernel_name_of(pt_pick_kernel(v, facts));
+  /* one chunk of samples_per_chunk samples, without a chunk workspace: the class's facts go to the pick unchanged */
+  const PtPlanAsk ask = {.integrator = c->integrator, .samples = c->samples_per_chunk, .max_depth = c->max_depth, .max_emission = c->max_emission,
+                         .sample_chunks = 1, .have_park_ws = c->have_park_ws != 0, .wide_pend_ok = c->wide_pend_ok != 0};
+  return pt_kernel_name_of(pt_plan_launch(v, ask).kernel);
 }
 
 void rt_hip_selftest_fail_alloc(uint32_t mask) { g_fail_alloc.store(mask); }
@@ -1210,32 +1215,21 @@ uint32_t rt_hip_suggest_chunks_depth(const RtHipScene *scene, uint32_t tile_coun
   if (!scene || tile_count == 0 || samples < 1)
     return 1;
   /* scenes with M_REFRACTION: at least as many chunks as the windowed sums need (pt_refr_pool_fits per chunk) */
-  uint64_t need = 1;
-  if (scene->view.any_refract)
-  {
-    need = pt_refr_pool_chunks_needed(samples, max_depth);
-    if (need == 0 || need > (uint64_t)samples || need * tile_count > 0x7FFFFFFFull)
-      need = 1; /* no chunking fits (max_depth > 29): the static kernels, which do not split samples */
-  }
+  const uint64_t need = pt_refr_chunk_floor(scene->view, samples, max_depth, tile_count);
   if (samples < 128)
     return (uint32_t)need;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, scene->device) != hipSuccess)
     return (uint32_t)need;
-  /* which body the scene takes: the parked-walk kernels render a tile per WAVE (four per workgroup, four workgroups per CU),
-   * and a chunk of theirs must be longer -- a wave amortises its walk batches and its final, partly filled walk over its pool */
-  bool queued, windowed;
-  {
-    std::lock_guard<std::mutex> lock(scene->table_mutex);
-    const bool have_ws = scene->park_tried ? scene->park_ws != nullptr : (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_PARK_WS) == 0;
-    const PtPickFacts facts = {RT_HIP_TRACE_PATH, (int32_t)(((uint64_t)samples + need - 1) / need), max_depth, have_ws, true,
-                               samples, scene->max_emission};
-    const int which = pt_pick_kernel(scene->view, facts);
-    queued = pt_kernel_is_queued(which);
-    windowed = pt_kernel_is_windowed(which);
-  }
+  /* which body the scene takes (the plan of a launch with a chunk workspace): the parked-walk kernels render a tile per WAVE
+   * (four per workgroup, four workgroups per CU), and a chunk of theirs must be longer -- a wave amortises its walk batches and
+   * its final, partly filled walk over its pool */
+  const PtPlanAsk ask = {.integrator = RT_HIP_TRACE_PATH, .samples = samples, .max_depth = max_depth, .max_emission = scene->max_emission,
+                         .sample_chunks = 1, .have_chunk_ws = true, .tile_count = tile_count, .have_park_ws = park_ws_expected(scene),
+                         .wide_pend_ok = true};
+  const PtPlan plan = pt_plan_launch(scene->view, ask);
   uint64_t want, min_chunk_samples;
-  if (queued)
+  if (plan.queued)
   {
     /* >= 30 rounds of workgroups (the expensive tiles -- those on the mesh -- are few and long: one workgroup of four of them at
      * 4096 spp outlasts a rank's whole ideal share at N = 8), >= 128 samples per chunk.  One rank's share of config 5 at N = 8,
@@ -1254,7 +1248,7 @@ uint32_t rt_hip_suggest_chunks_depth(const RtHipScene *scene, uint32_t tile_coun
   /* a chunk keeps >= 128 samples (a workgroup's fixed costs -- staging, keys, culling, the resolve pass -- against its pool: config 3's
    * share at N = 8, 256 spp, ms by chunks 1: 2.63, 2: 2.61, 4: 2.70, 8: 3.01); the M_REFRACTION forms >= 64 (a refractive sample
    * is two to three times the rays: the glass mesh's share at N = 8, 256 spp 2: 48.8, 4: 45.9, 8: 46.9) */
-  min_chunk_samples = windowed ? 64 : 128;
+  min_chunk_samples = plan.windowed ? 64 : 128;
   uint64_t chunks = (want + tile_count - 1) / tile_count;
   const uint64_t cap = (uint64_t)samples / min_chunk_samples;
   if (chunks > cap) chunks = cap;
@@ -1475,34 +1469,13 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
       L.park_slots_per_xcd = scene->park_slots_per_xcd;
     }
   }
-  /* ---- which kernel (pt_kernel.hip: pt_pick_table), and how many sample chunks it takes ---- */
-  /* scenes with M_REFRACTION: the windowed sums of the pooled / parked-walk forms hold a bounded number of samples per chunk
-   * (pt_refr_pool_fits).  A caller that handed over a workspace gets at least as many chunks as that needs -- the image does
-   * not depend on the chunk count, and the workspace's size does not either; without a workspace the launch keeps its one
-   * chunk, and where that does not fit the table's fit = NO row (the static kernel of the family) renders it. */
-  if (!cast_ray && scene->view.any_refract && d_workspace)
-  {
-    const uint64_t need = pt_refr_pool_chunks_needed(params->samples, params->max_depth);
-    if (need > sample_chunks && need <= (uint64_t)params->samples && need * params->tile_count <= 0x7FFFFFFFull)
-      sample_chunks = (uint32_t)need;
-  }
-  /* a scene without M_REFRACTION whose launch needs the unbounded sums (pt_fixed_sums_fit) would take the windowed chunk
-   * record, six times the plain one its caller may have sized the workspace for (rt_hip_scene_chunk_workspace_bytes): it
-   * renders its samples in one chunk -- the image does not depend on the chunk count */
-  if (!cast_ray && !scene->view.any_refract && !pt_fixed_sums_fit(scene->max_emission, params->samples, params->max_depth))
-    sample_chunks = 1;
-  const int32_t samples_per_chunk = (int32_t)(((int64_t)params->samples + sample_chunks - 1) / sample_chunks);
-  PtPickFacts facts = {L.integrator, samples_per_chunk, params->max_depth, L.park_ws != nullptr, true, params->samples,
-                       scene->max_emission};
-  int which = pt_pick_kernel(L.scene, facts);
-  auto chunks_of = [&](int k) {
-    if (pt_kernel_takes_chunks(k))
-      return sample_chunks;
-    /* the static bodies (cast_ray, the fit = NO rows of M_REFRACTION) do not split samples */
-    return 1u;
-  };
-  L.sample_chunks = chunks_of(which);
-  L.acc_windows = pt_kernel_is_windowed(which) ? 1u : 0u;
+  /* ---- which kernel, how many sample chunks it runs, which pools it needs: the plan (pt_kernel.hip, pt_plan_launch) ---- */
+  PtPlanAsk ask = {.integrator = L.integrator, .samples = params->samples, .max_depth = params->max_depth, .max_emission = scene->max_emission,
+                   .sample_chunks = sample_chunks, .have_chunk_ws = d_workspace != nullptr, .tile_count = params->tile_count,
+                   .have_park_ws = L.park_ws != nullptr, .wide_pend_ok = true};
+  PtPlan plan = pt_plan_launch(L.scene, ask);
+  L.sample_chunks = plan.sample_chunks;
+  L.acc_windows = plan.windowed ? 1u : 0u;
   if ((uint64_t)L.tile_count * L.sample_chunks > 0x7FFFFFFFull)
     return fail(RT_HIP_EINVAL, "tile_count x sample_chunks exceeds the grid limit");
   size_t slot = 0;
@@ -1510,35 +1483,34 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
   if (rc)
     return rc;
   hipError_t e;
-  if (pt_kernel_uses_pend_pool(which))
+  if (plan.pend_entries)
   {
     std::lock_guard<std::mutex> pend_lock(g_pend_mutex);
-    rc = pend_pool_for(scene->device, pt_pend_entries(L.scene, L.integrator, params->max_depth), pt_kernel_pend_columns_of(which), L);
+    rc = pend_pool_for(scene->device, plan.pend_entries, plan.pend_columns, L);
     /* the parked-walk refraction kernels want four times the stacks per slot (1.2 GB at depth 5, 5.7 GB at 32): where that
-     * cannot be had, the pool of the other kernels will do -- the table's fit = NO row names the static kernel of the family */
-    if (rc == RT_HIP_ENOMEM && pt_kernel_pend_columns_of(which) > PT_PEND_COLUMNS)
+     * cannot be had, the pool of the other kernels will do -- planned again, the table's fit = NO row names the static kernel
+     * of the family */
+    if (rc == RT_HIP_ENOMEM && plan.pend_columns > PT_PEND_COLUMNS)
     {
-      facts.wide_pend_ok = false;
-      which = pt_pick_kernel(L.scene, facts);
-      L.sample_chunks = chunks_of(which);
-      L.acc_windows = pt_kernel_is_windowed(which) ? 1u : 0u;
-      rc = pt_kernel_uses_pend_pool(which) ? pend_pool_for(scene->device, pt_pend_entries(L.scene, L.integrator, params->max_depth),
-                                                           pt_kernel_pend_columns_of(which), L)
-                                           : RT_HIP_OK;
+      ask.wide_pend_ok = false;
+      plan = pt_plan_launch(L.scene, ask);
+      L.sample_chunks = plan.sample_chunks;
+      L.acc_windows = plan.windowed ? 1u : 0u;
+      rc = plan.pend_entries ? pend_pool_for(scene->device, plan.pend_entries, plan.pend_columns, L) : RT_HIP_OK;
     }
     if (rc)
     {
       release_tables(scene, slot, static_cast<hipStream_t>(stream));
       return rc;
     }
-    e = pt_launch_render(L, static_cast<hipStream_t>(stream), which);
+    e = pt_launch_render(L, static_cast<hipStream_t>(stream), plan.kernel);
   }
   else
-    e = pt_launch_render(L, static_cast<hipStream_t>(stream), which);
+    e = pt_launch_render(L, static_cast<hipStream_t>(stream), plan.kernel);
   release_tables(scene, slot, static_cast<hipStream_t>(stream));
   if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_kernel_name_of(which), hipGetErrorString(e));
-  g_last_kernel = which;
+    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_kernel_name_of(plan.kernel), hipGetErrorString(e));
+  g_last_kernel = plan.kernel;
   return RT_HIP_OK;
 }
 
