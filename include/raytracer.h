@@ -247,6 +247,17 @@ int rt_get_integrator(void);
 void rt_set_cancel_flag(const volatile int *flag);
 int rt_last_render_cancelled(void);
 
+/* Progressive rendering: render_ex's frame (options->samples per pixel, the budget) in passes of pass_samples (the last one may
+ * be shorter), on ONE device.  After every pass on_pass (may be NULL) gets the samples done, the budget, the pass's kernel seconds
+ * and `user`.  The cancel flag (rt_set_cancel_flag) is polled between passes; at least one pass always runs.  framebuffer and
+ * linear_rgb (either may be NULL) receive the whole image of the samples done: after the budget it is the one-shot frame bit for
+ * bit (include/rt_hip.h, rt_hip_accum_*); when cancelled, a complete image of fewer samples, and rt_last_render_cancelled()
+ * reports 1.  Returns the samples per pixel the image holds, or a negative RT_HIP_E* code with the reason on stderr: more than one
+ * device (rt_set_devices), pass_samples < 1, or a failure of the GPU path.  The counters and timings below are those of all passes. */
+typedef void RtPassFn(int done, int total, double kernel_seconds, void *user);
+int render_progressive(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects, MeshObject *meshes,
+                       size_t n_meshes, Camera *camera, Options *options, int pass_samples, RtPassFn *on_pass, void *user);
+
 /* Kernel-only wall time of the last render()/render_ex(), seconds, and the
  * count of scene casts (rays that ran the intersection scan). */
 double rt_last_render_seconds(void);

@@ -222,6 +222,40 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
                                 uint32_t sample_chunks, void *d_workspace, float *d_tiles_rgb,
                                 uint8_t *d_tiles_rgb8, uint64_t *d_stats, void *stream);
 
+/* ---- progressive rendering: one frame accumulated over passes ------------------------------------------------------------
+ * An accumulation renders the frame of params->samples samples per pixel (the BUDGET) in passes of any sizes, and can be resolved
+ * after any pass into the mean of the samples done so far.  The frame after the whole budget is BIT-IDENTICAL to the one-shot
+ * frame, whatever the passes were: what rt_hip_render_tiles_chunked gives for the same parameters at
+ * rt_hip_suggest_chunks_depth(budget) chunks (tiles, bytes and the summed counters); and two accumulations of the same frame agree
+ * bit for bit at every sample count both have reached.  A sample's value depends only on its (seed, pixel, sample) stream
+ * (rt_rng.h), and the pixel sums are exact integers (fixed point, or windowed words) or fp64 slice sums added in the one-shot order.
+ *   - The plan is made ONCE, at create: pt_plan_launch for the whole budget with a chunk workspace and the suggested chunks, with
+ *     the fallback rows of a one-shot launch (no parked-walk workspace, no wide pending-ray pool) and the budget's fixed-point
+ *     scale.  Every pass runs that member with those sums; rt_hip_accum_kernel names it.
+ *   - Create allocates the frame's sums -- tile_count x 9,240 bytes for windowed sums (the M_REFRACTION forms), x 1,560 for
+ *     fixed-point ones, x 6,144 (3 x 256 fp64 slice sums) for the static body; at 1080p about 300 / 50 / 200 MB -- and, where the
+ *     member needs one, a pending-ray pool of its own, and holds them until destroy.  The scene (and with it the parked-walk
+ *     workspace) must outlive the accumulation.
+ *   - rt_hip_accum_add renders the next `samples` samples of every pixel (asynchronous on `stream`; d_stats: RT_HIP_NSTATS
+ *     accumulators, += per pass, may be NULL -- over all passes they sum to the one-shot counters).  samples <= 0 or more than the
+ *     budget has left: RT_HIP_EINVAL, nothing changes.  The passes of one accumulation must run in order (one stream, or
+ *     synchronised between them).
+ *   - rt_hip_accum_resolve writes the mean of the samples done so far into a compact tile buffer (as rt_hip_render_tiles);
+ *     asynchronous on `stream`, which must be ordered after the passes.  rt_hip_accum_read_image is the synchronous row-major form
+ *     for C hosts (waits for the device, either output may be NULL; pixels of tiles outside the accumulation's tile set are 0)
+ *     and checks the device's status word (rt_hip_launch_status). */
+typedef struct RtHipAccum RtHipAccum; /* opaque */
+int rt_hip_accum_create(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, RtHipAccum **out_accum);
+int rt_hip_accum_add(RtHipAccum *accum, int32_t samples, uint64_t *d_stats, void *stream);
+int rt_hip_accum_resolve(const RtHipAccum *accum, float *d_tiles_rgb, uint8_t *d_tiles_rgb8, void *stream); /* mean of samples done */
+int rt_hip_accum_read_image(const RtHipAccum *accum, float *h_rgb, uint8_t *h_rgb8);
+/* rt_hip_accum_add for C hosts: on the null stream, synchronous; h_stats (RT_HIP_NSTATS, may be NULL) += the pass's counters,
+ * kernel_seconds (may be NULL) = the pass's device time */
+int rt_hip_accum_add_host(RtHipAccum *accum, int32_t samples, uint64_t *h_stats, double *kernel_seconds);
+int32_t rt_hip_accum_samples(const RtHipAccum *accum); /* samples per pixel done */
+const char *rt_hip_accum_kernel(const RtHipAccum *accum);
+void rt_hip_accum_destroy(RtHipAccum *accum);
+
 /* Scatter a compact tile buffer into row-major images (either output may be
  * NULL together with its input). */
 int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t width, int32_t height,

@@ -157,9 +157,10 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L)
   const uint32_t vrows = ty0 >= (uint32_t)L.height ? 0u : min(SWAP ? (uint32_t)PT_TILE : 2u, (uint32_t)L.height - ty0);
   const uint32_t n_valid = vcols * vrows;
   const uint32_t spp = (uint32_t)L.samples;
-  /* this workgroup's share of the samples: [s_begin, s_end) of every pixel */
-  const uint32_t s_begin = (uint32_t)(((uint64_t)chunk * spp) / L.sample_chunks);
-  const uint32_t s_end = (uint32_t)(((uint64_t)(chunk + 1u) * spp) / L.sample_chunks);
+  /* this workgroup's share of the samples: [s_begin, s_end) of every pixel (absolute indices: a pass of an accumulation starts at
+   * sample_first, 0 otherwise) */
+  const uint32_t s_begin = L.sample_first + (uint32_t)(((uint64_t)chunk * spp) / L.sample_chunks);
+  const uint32_t s_end = L.sample_first + (uint32_t)(((uint64_t)(chunk + 1u) * spp) / L.sample_chunks);
   const uint32_t pool_jobs = n_valid * (s_end - s_begin); /* jobs: j -> pixel j % n_valid, sample s_begin + j / n_valid */
 
   Path P;
@@ -572,7 +573,7 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L)
     if (!pend_ok && threadIdx.x < 3)
       pix_nan[threadIdx.x] = ~0ull;
     __syncthreads();
-    if (L.sample_chunks == 1)
+    if (L.sample_chunks == 1 && !L.acc_keep)
     {
       /* thread = (pixel, channel), as finish_pixels: the windowed sum -> mean -> float + tonemapped byte */
       if (threadIdx.x < PT_TILE_PIXELS * 3)
@@ -590,7 +591,7 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L)
     }
     else
     {
-      /* one of several sample chunks of this tile: its windows, carry-normalised (words below 2^32: the tile's record takes one
+      /* one of several sample chunks of this tile (or a pass of an accumulation): its windows, carry-normalised (words below 2^32: the tile's record takes one
        * piece per chunk and word), are added to the tile's record in HBM -- integer atomics: exact, order-free;
        * pt_resolve_tiles normalises the total and finishes the pixels */
       if (threadIdx.x < PT_TILE_PIXELS * 3)
@@ -610,7 +611,7 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L)
     if (pend_ok && threadIdx.x == 0)
       atomicExch(&L.pend_flags[pend_slot], 0u); /* every lane is past its last pop (the barriers above) */
   }
-  else if (L.sample_chunks == 1)
+  else if (L.sample_chunks == 1 && !L.acc_keep)
   {
     finish_pixels(L, pix_sum, pix_nan, tile, out_f, out_b);
     __syncthreads();
@@ -626,7 +627,7 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L)
   }
   else
   {
-    /* one of several sample chunks of this tile: add the partial sums to the tile's record in
+    /* one of several sample chunks of this tile (or a pass of an accumulation): add the partial sums to the tile's record in
      * HBM (integer atomics: exact, order-independent); pt_resolve_tiles finishes the pixels */
     if (threadIdx.x < PT_TILE_PIXELS * 3 && pix_sum[threadIdx.x] != 0)
       atomicAdd(&L.acc_ws[(size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x], pix_sum[threadIdx.x]);

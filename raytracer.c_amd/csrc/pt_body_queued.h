@@ -430,8 +430,8 @@ __device__ __forceinline__ void render_tiles_queued(const PtLaunch &L)
   const uint32_t vrows = min((uint32_t)PT_TILE, (uint32_t)L.height - ty0);
   const uint32_t n_valid = vcols * vrows;
   const uint32_t spp = (uint32_t)L.samples;
-  const uint32_t s_begin = (uint32_t)(((uint64_t)chunk * spp) / L.sample_chunks);
-  const uint32_t s_end = (uint32_t)(((uint64_t)(chunk + 1u) * spp) / L.sample_chunks);
+  const uint32_t s_begin = L.sample_first + (uint32_t)(((uint64_t)chunk * spp) / L.sample_chunks); /* absolute, as render_tiles_pooled */
+  const uint32_t s_end = L.sample_first + (uint32_t)(((uint64_t)(chunk + 1u) * spp) / L.sample_chunks);
   const uint32_t park_slot = park_slot_lds;
   const uint32_t pend_slot = REFR ? pend_slot_lds : 0u;
   /* (REFR: without its slot of the pending-ray pool -- a sizing bug of the pool, never seen -- a workgroup renders nothing either) */
@@ -984,7 +984,7 @@ __device__ __forceinline__ void render_tiles_queued(const PtLaunch &L)
     if (REFR)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); /* ... and its global ones have reached the L2 */
     __builtin_amdgcn_wave_barrier();
-    if (L.sample_chunks == 1)
+    if (L.sample_chunks == 1 && !L.acc_keep)
     {
       const uint32_t t = lane;
       const bool inside = (t & 7u) < vcols && (t >> 3) < vrows;
@@ -1028,7 +1028,7 @@ __device__ __forceinline__ void render_tiles_queued(const PtLaunch &L)
     }
     else if (REFR)
     {
-      /* one of several sample chunks of this tile, windowed form: the wave's windows (in its workspace region; its atomics have
+      /* one of several sample chunks of this tile (or a pass of an accumulation), windowed form: the wave's windows (in its workspace region; its atomics have
        * reached the L2, the loads bypass the L1), carry-normalised per pixel channel, added to the tile's record */
       for (uint32_t pc = lane; ring_ok && pc < PT_TILE_PIXELS * 3; pc += 64) /* (no slot: no windows of its own; the NaN masks below say so) */
       {
@@ -1048,7 +1048,7 @@ __device__ __forceinline__ void render_tiles_queued(const PtLaunch &L)
     }
     else
     {
-      /* one of several sample chunks of this tile: exact integer partial sums to the tile's record */
+      /* one of several sample chunks of this tile (or a pass of an accumulation): exact integer partial sums to the tile's record */
       for (uint32_t k = lane; k < PT_TILE_PIXELS * 3; k += 64)
         if (pix_sum[k] != 0)
           atomicAdd(&L.acc_ws[(size_t)slot * (PT_TILE_PIXELS * 3) + k], pix_sum[k]);

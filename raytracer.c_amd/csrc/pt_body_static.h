@@ -52,8 +52,22 @@ __device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
   const uint32_t pixel = py * (uint32_t)L.width + px;
   const uint32_t spp = (uint32_t)L.samples;
   const CameraRegs cam = load_camera(L);
+  /* this launch's samples: [sample_first, s_end), absolute; the lane's are those of its slice, s == slice (mod 4) */
+  const uint32_t s_end = L.sample_first + spp;
+  const bool keep = L.acc_keep != 0u;
+  double *const keep_sum = keep ? L.slice_ws + (size_t)blockIdx.x * (3u * PT_BLOCK) + threadIdx.x : nullptr;
 
   V3 acc = {0, 0, 0}; /* sum of finished samples of this lane's slice */
+  /* Accumulation (acc_keep): the slice sum goes on from where the previous pass left it, and below it is stored back unreduced.
+   * A lane adds the same samples in the same ascending order, one fp64 addition each, whether they come in one launch or in
+   * passes: the store and reload between passes keep the double exactly, so every addition has the same operands as in a
+   * one-shot launch and pt_resolve_slices, reducing the four slices by the same shuffles, gives the same pixel bit for bit. */
+  if (keep)
+  {
+    acc.x = keep_sum[0];
+    acc.y = keep_sum[PT_BLOCK];
+    acc.z = keep_sum[2 * PT_BLOCK];
+  }
   Path P;
   P.o = {0, 0, 0};
   P.d = {0, 0, 1};
@@ -62,7 +76,7 @@ __device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
   P.rng = 1;
   P.depth = 0;
   uint32_t n_rays = 0, n_casts = 0;
-  uint32_t s = inside ? slice : spp;
+  uint32_t s = inside ? L.sample_first + ((slice - L.sample_first) & (PT_SLICES - 1)) : s_end;
   bool fresh = true;
   /* kernels with two-child materials: the workgroup's slot of the pending-ray pool (PendStack) */
   constexpr bool STACKED = REFRACT || WHITTED == 2;
@@ -80,12 +94,12 @@ __device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
   const PendStack stack = {STACKED && pend_ok ? L.pend_ws + (size_t)pend_slot * L.pend_slot_doubles + threadIdx.x : nullptr,
                            STACKED && pend_ok ? (int)L.pend_entries : 0, PT_BLOCK, PT_PEND_FIELDS * PT_BLOCK};
   if (!pend_ok)
-    s = spp;
+    s = s_end;
   int stack_n = 0;
   unsigned long long *diag_ptr = L.stats;
   (void)diag_ptr;
 
-  while (s < spp)
+  while (s < s_end)
   {
     DIAG(0, 1);
     DIAG_LANES(1);
@@ -108,7 +122,24 @@ __device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
     }
   }
 
-  /* per-pixel mean: fixed-order reduction over the 4 slice lanes */
+  if (keep)
+  { /* a pass of an accumulation: the slice sums stay unreduced (a workgroup without its pool slot makes them NaN for good) */
+    const double quiet_nan = __longlong_as_double(0x7FF8000000000000ll);
+    keep_sum[0] = pend_ok ? acc.x : quiet_nan;
+    keep_sum[PT_BLOCK] = pend_ok ? acc.y : quiet_nan;
+    keep_sum[2 * PT_BLOCK] = pend_ok ? acc.z : quiet_nan;
+    if (n_rays)
+    {
+      atomicAdd(&wg_stats[0], (unsigned long long)n_rays);
+      atomicAdd(&wg_stats[1], (unsigned long long)n_casts);
+    }
+    __syncthreads();
+    store_tile(L, out_f, out_b, wg_stats, tile, blockIdx.x, S.n_sph + S.n_tri, false, true);
+    if (STACKED && pend_ok && threadIdx.x == 0)
+      atomicExch(&L.pend_flags[pend_slot], 0u);
+    return;
+  }
+  /* per-pixel mean: fixed-order reduction over the 4 slice lanes (pt_resolve_slices repeats it) */
   acc.x += __shfl_xor(acc.x, 1);
   acc.y += __shfl_xor(acc.y, 1);
   acc.z += __shfl_xor(acc.z, 1);

@@ -310,6 +310,12 @@ struct PtLaunch
   uint32_t sample_chunks; /* workgroups per tile: each renders 1/sample_chunks of the samples */
   uint32_t acc_windows;   /* sample_chunks > 1: acc_ws holds WINDOWED sums (tile_count x 192 x PT_WIN_N words, then the NaN masks): the M_REFRACTION forms */
   uint32_t integrator;    /* 0 trace_path (raytracer.c:482-554), 1 cast_ray (:556-641) */
+  /* accumulation mode (rt_hip_accum_*, rt_hip_shim.hip): a PASS renders the absolute samples [sample_first, sample_first + samples)
+   * of every pixel, and with acc_keep set it adds them to the frame's sums and finishes no pixel -- the CHUNKS members into acc_ws
+   * (even with one chunk), the static body into slice_ws.  Both zero: a one-shot launch, as before */
+  uint32_t sample_first;
+  uint32_t acc_keep;
+  double *slice_ws; /* static body, acc_keep: tile_count x 3 x PT_BLOCK fp64 slice sums (lane l of tile k, channel c at (3 k + c) x 256 + l), unreduced */
   /* sign-test kernels: the scene's leading pairs of wall-sized spheres (radius >= 1000) are pruned among themselves before
    * the exact tests (pt_filter.h, BigPrune): how many pairs (0: off), the distance margin, the least distance and per sphere the least q32 of a wall that may prune */
   uint32_t big_pairs;
@@ -375,6 +381,10 @@ struct PtPlan
 };
 PtPlan pt_plan_launch(const PtSceneView &scene, const PtPlanAsk &ask);
 hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int which);
+/* accumulation (rt_hip_accum_*): whether member `which` keeps its sums in acc_ws (CHUNKS) rather than as slice sums (the static
+ * body), and the resolve of the sums its passes left: pt_resolve_tiles or pt_resolve_slices over launch.samples samples */
+bool pt_kernel_takes_chunks(int which);
+hipError_t pt_launch_resolve(const PtLaunch &launch, hipStream_t stream, int which);
 /* entries per pending-ray stack a launch needs: max_depth + 2 where a material has two children (M_REFRACTION under trace_path,
  * M_REFLECTION | M_REFRACTION under cast_ray); one where none has -- nothing is ever pushed (a scene on the M_REFRACTION forms for
  * their unbounded sums, pt_classify), at any depth */

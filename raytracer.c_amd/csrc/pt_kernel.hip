@@ -269,6 +269,48 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
         reinterpret_cast<const uint32_t *>(out_b)[threadIdx.x];
 }
 
+/* Resolve of an accumulation on the static body (rt_hip_accum_resolve): the slice sums its passes left in L.slice_ws -> pixel
+ * means over L.samples (the samples done so far).  Not a member of the family: no scene, no samples.  The lane mapping, the
+ * shuffles, the scale and the stores are render_tiles_static's own, so after the whole budget the tile is the one-shot tile bit
+ * for bit (the reason is given there). */
+extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_slices(const PtLaunch L)
+{
+  __shared__ float out_f[PT_TILE_PIXELS * 3];
+  __shared__ uint8_t out_b[PT_TILE_PIXELS * 3 + 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t pix_in_tile = wave * 16u + (lane >> 2);
+  const uint32_t slice = lane & (PT_SLICES - 1);
+  const uint32_t slot = blockIdx.x;
+  const uint32_t tile = L.tile_first + slot * L.tile_stride;
+  const uint32_t px = (tile % L.tiles_x) * PT_TILE + (pix_in_tile & 7u);
+  const uint32_t py = (tile / L.tiles_x) * PT_TILE + (pix_in_tile >> 3);
+  const bool inside = px < (uint32_t)L.width && py < (uint32_t)L.height;
+  const double *const sum = L.slice_ws + (size_t)slot * (3u * PT_BLOCK) + threadIdx.x;
+  V3 acc = {sum[0], sum[PT_BLOCK], sum[2 * PT_BLOCK]};
+  acc.x += __shfl_xor(acc.x, 1);
+  acc.y += __shfl_xor(acc.y, 1);
+  acc.z += __shfl_xor(acc.z, 1);
+  acc.x += __shfl_xor(acc.x, 2);
+  acc.y += __shfl_xor(acc.y, 2);
+  acc.z += __shfl_xor(acc.z, 2);
+  const V3 mean = v_scale(acc, 1.0 / (double)(uint32_t)L.samples);
+  if (slice == 0)
+  {
+    out_f[3 * pix_in_tile + 0] = inside ? (float)mean.x : 0.f;
+    out_f[3 * pix_in_tile + 1] = inside ? (float)mean.y : 0.f;
+    out_f[3 * pix_in_tile + 2] = inside ? (float)mean.z : 0.f;
+    out_b[3 * pix_in_tile + 0] = inside ? tonemap(mean.x) : 0;
+    out_b[3 * pix_in_tile + 1] = inside ? tonemap(mean.y) : 0;
+    out_b[3 * pix_in_tile + 2] = inside ? tonemap(mean.z) : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x < PT_TILE_PIXELS * 3)
+    L.tiles_rgb[(size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x] = out_f[threadIdx.x];
+  if (L.tiles_rgb8 && threadIdx.x < PT_TILE_PIXELS * 3 / 4)
+    reinterpret_cast<uint32_t *>(L.tiles_rgb8)[(size_t)slot * (PT_TILE_PIXELS * 3 / 4) + threadIdx.x] =
+        reinterpret_cast<const uint32_t *>(out_b)[threadIdx.x];
+}
+
 /* Self-test hook (rt_hip_selftest_math): evaluates the kernel's exact-arithmetic shortcuts
  * on caller data so a test can compare them bit for bit with the host's IEEE results.
  * op 0: sqrt_unscaled(a[i]);  op 1: div_small_int(a[i], b[i], 1/b[i]);  op 2: the library
@@ -987,7 +1029,9 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
     if (e != hipSuccess)
       return e;
   }
-  if (launch.sample_chunks > 1)
+  if (launch.acc_keep && (k.has(CHUNKS) ? launch.acc_ws == nullptr || (launch.acc_windows != 0u) != k.has(WINDOWED) : launch.slice_ws == nullptr))
+    return hipErrorInvalidValue; /* a pass of an accumulation adds to the sums its caller holds: they are neither cleared nor resolved here */
+  if (launch.sample_chunks > 1 && !launch.acc_keep)
   {
     if ((launch.acc_windows != 0u) != k.has(WINDOWED) || launch.acc_ws == nullptr)
       return hipErrorInvalidValue;
@@ -999,12 +1043,33 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
   const uint32_t n_units = launch.tile_count * launch.sample_chunks;
   hipLaunchKernelGGL(kernel, dim3(queued ? (n_units + PT_BLOCK / 64 - 1) / (PT_BLOCK / 64) : n_units), dim3(PT_BLOCK), lds_bytes,
                      stream, launch);
-  if (launch.sample_chunks > 1)
+  if (launch.sample_chunks > 1 && !launch.acc_keep)
     hipLaunchKernelGGL(pt_resolve_tiles, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch);
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess)
     pt_launch_counts[which].fetch_add(1ull);
   return e;
+}
+
+bool pt_kernel_takes_chunks(int which) { return which >= 0 && which < K_COUNT && pt_kernels[which].has(CHUNKS); }
+
+hipError_t pt_launch_resolve(const PtLaunch &launch, hipStream_t stream, int which)
+{
+  if (which < 0 || which >= K_COUNT || launch.tile_count == 0u || launch.samples < 1)
+    return hipErrorInvalidValue;
+  if (pt_kernels[which].has(CHUNKS))
+  {
+    if (launch.acc_ws == nullptr || (launch.acc_windows != 0u) != pt_kernels[which].has(WINDOWED))
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_resolve_tiles, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch);
+  }
+  else
+  {
+    if (launch.slice_ws == nullptr)
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_resolve_slices, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch);
+  }
+  return hipGetLastError();
 }
 
 hipError_t pt_launch_selftest_intersect(int kind, const double *rays, const double *prims, const double *entry_src,

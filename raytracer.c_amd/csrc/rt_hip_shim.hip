@@ -518,6 +518,42 @@ int pend_pool_for(int device, uint32_t entries, uint32_t columns, PtLaunch &L)
   return RT_HIP_OK;
 }
 
+/* A pending-ray pool of an accumulation's own (rt_hip_accum_create): laid out as the device's pool (flags, then slots), allocated
+ * once for the plan and held until rt_hip_accum_destroy, so that no other launch can grow, shrink or free it mid-frame.  The
+ * injected failure of the wide pool applies as in pend_pool_for.  The current device is the scene's. */
+int pend_pool_own(uint32_t entries, uint32_t columns, PtLaunch &L, char **out)
+{
+  *out = nullptr;
+  const uint32_t per = pt_pool_slots_per_xcd(false);
+  const size_t slot_bytes = (size_t)entries * PT_PEND_FIELDS_HOST * columns * sizeof(double);
+  const size_t bytes = pend_flag_bytes(per) + (size_t)PT_PARK_XCDS * per * slot_bytes;
+  if (columns > PT_PEND_COLUMNS && (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_WIDE_PEND))
+    return fail(RT_HIP_ENOMEM, "pending-ray pool for max_depth %u (%zu MB): allocation failure injected", entries - 2u, bytes >> 20);
+  char *ws = nullptr;
+  hipError_t e = hipMalloc(&ws, bytes);
+  if (e != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(RT_HIP_ENOMEM, "pending-ray pool for max_depth %u (%zu MB): %s", entries - 2u, bytes >> 20, hipGetErrorString(e));
+  }
+  e = hipMemset(ws, 0, pend_flag_bytes(per));
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess)
+  {
+    (void)hipGetLastError();
+    (void)hipFree(ws);
+    return fail(RT_HIP_ERUNTIME, "pending-ray pool: %s", hipGetErrorString(e));
+  }
+  L.pend_flags = reinterpret_cast<uint32_t *>(ws);
+  L.pend_ws = reinterpret_cast<double *>(ws + pend_flag_bytes(per));
+  L.pend_slots_per_xcd = per;
+  L.pend_entries = entries;
+  L.pend_slot_doubles = (uint64_t)entries * PT_PEND_FIELDS_HOST * columns;
+  *out = ws;
+  return RT_HIP_OK;
+}
+
 /* the per-device status word of render launches (PtLaunch.status, rt_hip_launch_status) */
 std::mutex g_status_mutex;
 uint32_t *g_status[64] = {nullptr};
@@ -1353,17 +1389,11 @@ int rt_hip_render_tiles(const RtHipScene *scene, const RtHipCamera *camera, cons
   return rt_hip_render_tiles_chunked(scene, camera, params, 1, nullptr, d_tiles_rgb, d_tiles_rgb8, d_stats, stream);
 }
 
-int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params,
-                                uint32_t sample_chunks, void *d_workspace, float *d_tiles_rgb,
-                                uint8_t *d_tiles_rgb8, uint64_t *d_stats, void *stream)
+/* What a launch of rt_hip_render_tiles_chunked and an accumulation (rt_hip_accum_create) have in common before the plan: the
+ * parameters checked, and the launch's scene- and camera-dependent fields.  *empty: no tile to render (not an error). */
+static int launch_prepare(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, PtLaunch &L, bool *empty)
 {
-  if (!scene || !camera || !d_tiles_rgb)
-    return fail(RT_HIP_EINVAL, "scene, camera and d_tiles_rgb are required");
-  if (sample_chunks < 1 || (params && (int64_t)sample_chunks > params->samples))
-    return fail(RT_HIP_EINVAL, "sample_chunks must be in [1, samples]");
-  if (sample_chunks > 1 && !d_workspace)
-    return fail(RT_HIP_EINVAL, "sample_chunks > 1 needs a workspace of rt_hip_chunk_workspace_bytes(tile_count)");
-  int rc = check_params(params);
+  const int rc = check_params(params);
   if (rc)
     return rc;
   const bool cast_ray = params->integrator == RT_HIP_CAST_RAY;
@@ -1377,7 +1407,8 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
                 PT_REFRACT_MAX_DEPTH);
   const uint32_t tx = tiles_x_of(params->width), ty = tiles_y_of(params->height);
   const uint64_t n_tiles = (uint64_t)tx * ty;
-  if (params->tile_count == 0)
+  *empty = params->tile_count == 0;
+  if (*empty)
     return RT_HIP_OK;
   if (params->tile_stride == 0 && params->tile_count > 1)
     return fail(RT_HIP_EINVAL, "tile_stride must be >= 1");
@@ -1386,7 +1417,6 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
     return fail(RT_HIP_EINVAL, "tile range [%u + k*%u, k < %u] exceeds the image's %llu tiles", params->tile_first,
                 params->tile_stride, params->tile_count, (unsigned long long)n_tiles);
 
-  PtLaunch L;
   memset(&L, 0, sizeof L);
   L.scene = scene->view;
   memcpy(L.cam.pos, camera->position, sizeof L.cam.pos);
@@ -1442,14 +1472,14 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
   L.tile_count = params->tile_count;
   L.tiles_x = tx;
   L.integrator = cast_ray ? 1u : 0u;
-  L.acc_ws = static_cast<unsigned long long *>(d_workspace);
-  L.tiles_rgb = d_tiles_rgb;
-  L.tiles_rgb8 = d_tiles_rgb8;
-  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
+  return RT_HIP_OK;
+}
 
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  rc = status_word_for(scene->device, &L.status);
+/* ... and, with the scene's device current: the device's status word and the parked-walk workspace */
+static int launch_device_state(const RtHipScene *scene, PtLaunch &L)
+{
+  const bool cast_ray = L.integrator == 1u;
+  const int rc = status_word_for(scene->device, &L.status);
   if (rc)
     return rc;
   if (scene->view.n_bvh_nodes != 0 && !cast_ray)
@@ -1469,6 +1499,33 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
       L.park_slots_per_xcd = scene->park_slots_per_xcd;
     }
   }
+  return RT_HIP_OK;
+}
+
+int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params,
+                                uint32_t sample_chunks, void *d_workspace, float *d_tiles_rgb,
+                                uint8_t *d_tiles_rgb8, uint64_t *d_stats, void *stream)
+{
+  if (!scene || !camera || !d_tiles_rgb)
+    return fail(RT_HIP_EINVAL, "scene, camera and d_tiles_rgb are required");
+  if (sample_chunks < 1 || (params && (int64_t)sample_chunks > params->samples))
+    return fail(RT_HIP_EINVAL, "sample_chunks must be in [1, samples]");
+  if (sample_chunks > 1 && !d_workspace)
+    return fail(RT_HIP_EINVAL, "sample_chunks > 1 needs a workspace of rt_hip_chunk_workspace_bytes(tile_count)");
+  PtLaunch L;
+  bool empty = false;
+  int rc = launch_prepare(scene, camera, params, L, &empty);
+  if (rc || empty)
+    return rc;
+  L.acc_ws = static_cast<unsigned long long *>(d_workspace);
+  L.tiles_rgb = d_tiles_rgb;
+  L.tiles_rgb8 = d_tiles_rgb8;
+  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  rc = launch_device_state(scene, L);
+  if (rc)
+    return rc;
   /* ---- which kernel, how many sample chunks it runs, which pools it needs: the plan (pt_kernel.hip, pt_plan_launch) ---- */
   PtPlanAsk ask = {.integrator = L.integrator, .samples = params->samples, .max_depth = params->max_depth, .max_emission = scene->max_emission,
                    .sample_chunks = sample_chunks, .have_chunk_ws = d_workspace != nullptr, .tile_count = params->tile_count,
@@ -1513,6 +1570,266 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
   g_last_kernel = plan.kernel;
   return RT_HIP_OK;
 }
+
+/* ---- progressive rendering: one frame accumulated over passes (rt_hip.h, RtHipAccum) ----------------------------------------
+ * The plan is made once, for the whole budget, and every pass launches its member in accumulation mode (PtLaunch.sample_first,
+ * acc_keep): the CHUNKS members add exact integer sums (fixed point, or windowed words) to the tile records in `sums`, the static
+ * body continues its lanes' fp64 slice sums there.  A pass never re-plans, and the pools the plan needs are held here. */
+struct RtHipAccum
+{
+  const RtHipScene *scene = nullptr;
+  PtLaunch L;                  /* the launch as planned at create; a pass sets samples, sample_first, sample_chunks, stats */
+  int kernel = -1;
+  bool takes_chunks = false;   /* CHUNKS member: sums are tile records (pt_resolve_tiles); else slice sums (pt_resolve_slices) */
+  int32_t budget = 0, done = 0;
+  int32_t plan_spc = 0;        /* the plan's samples per chunk: no workgroup of a pass gets more */
+  void *sums = nullptr;
+  char *pend = nullptr;        /* the accumulation's own pending-ray pool (pend_pool_own), or nullptr */
+};
+
+static void accum_free(RtHipAccum *a)
+{
+  if (!a)
+    return;
+  if (a->sums || a->pend)
+  {
+    DeviceScope scope(a->scene->device);
+    (void)hipDeviceSynchronize(); /* no pass may still be using them */
+    if (a->sums)
+      (void)hipFree(a->sums);
+    if (a->pend)
+      (void)hipFree(a->pend);
+  }
+  delete a;
+}
+
+int rt_hip_accum_create(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, RtHipAccum **out)
+{
+  if (out)
+    *out = nullptr;
+  if (!scene || !camera || !params || !out)
+    return fail(RT_HIP_EINVAL, "scene, camera, params and out are required");
+  if (params->samples < 1)
+    return fail(RT_HIP_EINVAL, "the sample budget (params->samples) must be >= 1");
+  PtLaunch L;
+  bool empty = false;
+  int rc = launch_prepare(scene, camera, params, L, &empty);
+  if (rc)
+    return rc;
+  if (empty)
+    return fail(RT_HIP_EINVAL, "an accumulation needs tile_count >= 1");
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  rc = launch_device_state(scene, L);
+  if (rc)
+    return rc;
+  /* the plan of a one-shot launch of the whole budget with a chunk workspace and the suggested chunks: the same member, the same
+   * sum form, the same fallback rows; the fixed-point scale is the budget's (launch_prepare) */
+  const uint32_t chunks = rt_hip_suggest_chunks_depth(scene, params->tile_count, params->samples, params->max_depth);
+  PtPlanAsk ask = {.integrator = L.integrator, .samples = params->samples, .max_depth = params->max_depth, .max_emission = scene->max_emission,
+                   .sample_chunks = chunks, .have_chunk_ws = true, .tile_count = params->tile_count,
+                   .have_park_ws = L.park_ws != nullptr, .wide_pend_ok = true};
+  PtPlan plan = pt_plan_launch(L.scene, ask);
+  if (plan.kernel < 0)
+    return fail(RT_HIP_ERUNTIME, "no kernel for this scene"); /* unreachable (pt_pick_kernel) */
+  RtHipAccum *a = new (std::nothrow) RtHipAccum();
+  if (!a)
+    return fail(RT_HIP_ENOMEM, "accumulation: out of host memory");
+  a->scene = scene;
+  if (plan.pend_entries)
+  {
+    rc = pend_pool_own(plan.pend_entries, plan.pend_columns, L, &a->pend);
+    if (rc == RT_HIP_ENOMEM && plan.pend_columns > PT_PEND_COLUMNS)
+    { /* as rt_hip_render_tiles_chunked: without the wide pool, planned again (the fit = NO row) */
+      ask.wide_pend_ok = false;
+      plan = pt_plan_launch(L.scene, ask);
+      rc = plan.pend_entries ? pend_pool_own(plan.pend_entries, plan.pend_columns, L, &a->pend) : RT_HIP_OK;
+    }
+    if (rc)
+    {
+      accum_free(a);
+      return rc;
+    }
+  }
+  a->kernel = plan.kernel;
+  a->takes_chunks = pt_kernel_takes_chunks(plan.kernel);
+  a->budget = params->samples;
+  a->plan_spc = (int32_t)(((int64_t)params->samples + plan.sample_chunks - 1) / plan.sample_chunks);
+  L.acc_windows = plan.windowed ? 1u : 0u;
+  L.acc_keep = 1u;
+  const size_t bytes = a->takes_chunks ? (size_t)L.tile_count * (plan.windowed ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long)
+                                       : (size_t)L.tile_count * 3u * PT_BLOCK * sizeof(double);
+  hipError_t e = hipMalloc(&a->sums, bytes);
+  if (e != hipSuccess)
+  {
+    (void)hipGetLastError();
+    a->sums = nullptr;
+    accum_free(a);
+    return fail(RT_HIP_ENOMEM, "accumulation sums (%zu MB): %s", bytes >> 20, hipGetErrorString(e));
+  }
+  e = hipMemset(a->sums, 0, bytes);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(nullptr); /* zero before a pass on any stream adds to them */
+  if (e != hipSuccess)
+  {
+    (void)hipGetLastError();
+    accum_free(a);
+    return fail(RT_HIP_ERUNTIME, "accumulation sums: %s", hipGetErrorString(e));
+  }
+  if (a->takes_chunks)
+    L.acc_ws = static_cast<unsigned long long *>(a->sums);
+  else
+    L.slice_ws = static_cast<double *>(a->sums);
+  a->L = L;
+  *out = a;
+  return RT_HIP_OK;
+}
+
+int rt_hip_accum_add(RtHipAccum *a, int32_t samples, uint64_t *d_stats, void *stream)
+{
+  if (!a)
+    return fail(RT_HIP_EINVAL, "accumulation is NULL");
+  if (samples <= 0 || samples > a->budget - a->done)
+    return fail(RT_HIP_EINVAL, "a pass takes 1 .. %d samples (budget %d, %d done), not %d", a->budget - a->done, a->budget, a->done, samples);
+  const RtHipScene *scene = a->scene;
+  PtLaunch L = a->L;
+  L.samples = samples;
+  L.sample_first = (uint32_t)a->done;
+  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
+  L.sample_chunks = 1u;
+  if (a->takes_chunks)
+  { /* no workgroup gets more samples than the plan's chunks have (that is what the windowed words are sized by), and a small
+     * tile count gets the chunks the suggestion asks for.  Capacity: every chunk adds at most one piece below 2^32 to a word of
+     * the tile records, and every chunk has at least one sample, so over all passes a word takes at most budget < 2^31 pieces */
+    uint64_t chunks = ((uint64_t)samples + (uint64_t)a->plan_spc - 1u) / (uint64_t)a->plan_spc;
+    chunks = std::max<uint64_t>(chunks, rt_hip_suggest_chunks_depth(scene, L.tile_count, samples, L.max_depth));
+    chunks = std::min<uint64_t>(chunks, (uint64_t)samples);
+    if ((uint64_t)L.tile_count * chunks > 0x7FFFFFFFull)
+      return fail(RT_HIP_EINVAL, "tile_count x sample_chunks exceeds the grid limit");
+    L.sample_chunks = (uint32_t)chunks;
+  }
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  size_t slot = 0;
+  int rc = acquire_tables(scene, L.near_R, static_cast<hipStream_t>(stream), &L.scene.filt, &L.scene.bvh_nodes, &slot);
+  if (rc)
+    return rc;
+  const hipError_t e = pt_launch_render(L, static_cast<hipStream_t>(stream), a->kernel);
+  release_tables(scene, slot, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "%s pass: %s", pt_kernel_name_of(a->kernel), hipGetErrorString(e));
+  a->done += samples;
+  return RT_HIP_OK;
+}
+
+int rt_hip_accum_add_host(RtHipAccum *a, int32_t samples, uint64_t *h_stats, double *kernel_seconds)
+{
+  if (kernel_seconds)
+    *kernel_seconds = 0;
+  if (!a)
+    return fail(RT_HIP_EINVAL, "accumulation is NULL");
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  unsigned long long *d_stats = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(hipMalloc(&d_stats, RT_HIP_NSTATS * sizeof *d_stats));
+  hipError_t e = hipMemset(d_stats, 0, RT_HIP_NSTATS * sizeof *d_stats);
+  if (e == hipSuccess)
+    e = hipEventCreate(&ev[0]);
+  if (e == hipSuccess)
+    e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess)
+    e = hipEventRecord(ev[0], nullptr);
+  int rc = RT_HIP_OK;
+  if (e == hipSuccess)
+  {
+    rc = rt_hip_accum_add(a, samples, reinterpret_cast<uint64_t *>(d_stats), nullptr);
+    if (!rc)
+      e = hipEventRecord(ev[1], nullptr);
+    if (!rc && e == hipSuccess)
+      e = hipEventSynchronize(ev[1]);
+  }
+  unsigned long long st[RT_HIP_NSTATS] = {0, 0, 0, 0};
+  if (!rc && e == hipSuccess)
+    e = hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost);
+  float ms = 0.f;
+  if (!rc && e == hipSuccess)
+    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  for (hipEvent_t x : ev)
+    if (x)
+      (void)hipEventDestroy(x);
+  (void)hipFree(d_stats);
+  if (rc)
+    return rc;
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "accumulation pass: %s", hipGetErrorString(e));
+  if (h_stats)
+    for (int k = 0; k < RT_HIP_NSTATS; k++)
+      h_stats[k] += st[k];
+  if (kernel_seconds)
+    *kernel_seconds = 1e-3 * (double)ms;
+  return RT_HIP_OK;
+}
+
+int rt_hip_accum_resolve(const RtHipAccum *a, float *d_tiles_rgb, uint8_t *d_tiles_rgb8, void *stream)
+{
+  if (!a || !d_tiles_rgb)
+    return fail(RT_HIP_EINVAL, "accumulation and d_tiles_rgb are required");
+  if (a->done < 1)
+    return fail(RT_HIP_EINVAL, "the accumulation holds no sample yet");
+  PtLaunch L = a->L;
+  L.samples = a->done;
+  L.tiles_rgb = d_tiles_rgb;
+  L.tiles_rgb8 = d_tiles_rgb8;
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  const hipError_t e = pt_launch_resolve(L, static_cast<hipStream_t>(stream), a->kernel);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "accumulation resolve: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int rt_hip_accum_read_image(const RtHipAccum *a, float *h_rgb, uint8_t *h_rgb8)
+{
+  if (!a || (!h_rgb && !h_rgb8))
+    return fail(RT_HIP_EINVAL, "accumulation and an output are required");
+  const PtLaunch &L = a->L;
+  const size_t tile_vals = (size_t)L.tile_count * PT_TILE_PIXELS * 3, img_vals = (size_t)L.width * L.height * 3;
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  HIP_TRY(hipDeviceSynchronize()); /* the passes, on whatever stream they ran */
+  char *buf = nullptr;
+  const size_t bytes = tile_vals * 5 + img_vals * 5; /* tiles f32 + u8, image f32 + u8 */
+  HIP_TRY(hipMalloc(&buf, bytes));
+  float *tiles = reinterpret_cast<float *>(buf), *img = reinterpret_cast<float *>(buf + tile_vals * 5);
+  uint8_t *tiles8 = reinterpret_cast<uint8_t *>(buf + tile_vals * 4), *img8 = reinterpret_cast<uint8_t *>(buf + tile_vals * 5 + img_vals * 4);
+  int rc = rt_hip_accum_resolve(a, tiles, tiles8, nullptr);
+  hipError_t e = hipSuccess;
+  if (!rc)
+  {
+    e = hipMemset(img, 0, img_vals * 5);
+    if (e == hipSuccess)
+      e = pt_launch_untile(tiles, tiles8, L.width, L.height, L.tile_first, L.tile_stride, L.tile_count, img, img8, nullptr);
+    if (e == hipSuccess && h_rgb)
+      e = hipMemcpy(h_rgb, img, img_vals * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && h_rgb8)
+      e = hipMemcpy(h_rgb8, img8, img_vals, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(buf);
+  if (rc)
+    return rc;
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "accumulation read: %s", hipGetErrorString(e));
+  uint32_t flags = 0;
+  rc = status_take(a->scene->device, &flags);
+  return rc ? rc : status_to_error(flags);
+}
+
+int32_t rt_hip_accum_samples(const RtHipAccum *a) { return a ? a->done : 0; }
+
+const char *rt_hip_accum_kernel(const RtHipAccum *a) { return a ? pt_kernel_name_of(a->kernel) : ""; }
+
+void rt_hip_accum_destroy(RtHipAccum *a) { accum_free(a); }
 
 int rt_hip_selftest_math(int op, const double *h_a, const double *h_b, double *h_out, size_t n, int device)
 {

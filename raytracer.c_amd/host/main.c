@@ -11,11 +11,14 @@
  *   -r <seed>    RNG seed (default 1666943821)
  *   -i <0|1>     integrator: 0 trace_path (default), 1 cast_ray -- the `#if 1` of
  *                raytracer.c:207-211
+ *   -p <samples> progressive: add the samples in passes of this many (render_progressive, one GPU), a
+ *                line per pass; the PNG is the one-shot image bit for bit
  * Timing is wall-clock (the reference's clock()/integer division, main.c:427-433,
  * reports summed CPU time truncated to seconds -- deliberately not reproduced).
  * SIGINT: the reference's handler writes and frees the live framebuffer from
  * signal context (main.c:37-48); here it only sets a flag that the renderer
  * polls between slabs of tiles, and the partial image is written normally.
+ * With -p it is polled between passes, and the image is whole, of fewer samples.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <signal.h>
@@ -34,6 +37,14 @@ static void on_sigint(int sig)
   interrupted = 1;
 }
 
+/* -p: one line per pass */
+static void on_pass(int done, int total, double kernel_seconds, void *user)
+{
+  (void)user;
+  printf("pass: %d / %d samples per pixel (GPU kernels %f s)\n", done, total, kernel_seconds);
+  fflush(stdout);
+}
+
 static double now_seconds(void)
 {
   struct timespec ts;
@@ -45,6 +56,7 @@ typedef struct
 {
   Options options;
   int depth, config, gpus, integrator;
+  int pass; /* -p: samples per pass; 0: not given (one-shot) */
   uint64_t seed;
 } Args;
 
@@ -53,7 +65,7 @@ static void usage(const char *prog)
   fprintf(stderr,
           "Usage: %s -w <width> -h <height> -s <samples per pixel> -o <filename>\n"
           "          [-d <max depth>] [-c <scene config 1..5>] [-g <gpus>] [-r <seed>]\n"
-          "          [-i <integrator: 0 trace_path, 1 cast_ray>]\n",
+          "          [-i <integrator: 0 trace_path, 1 cast_ray>] [-p <samples per pass, one GPU>]\n",
           prog);
 }
 
@@ -75,6 +87,11 @@ static int parse_args(int argc, char **argv, Args *a)
     case 'g': a->gpus = atoi(val); break;
     case 'r': a->seed = strtoull(val, NULL, 10); break;
     case 'i': a->integrator = atoi(val); break;
+    case 'p':
+      a->pass = atoi(val);
+      if (a->pass < 1)
+        return -1; /* -p 0 (or not a number) */
+      break;
     default: return -1;
     }
   }
@@ -102,7 +119,8 @@ int main(int argc, char **argv)
   }
   RtSceneInfo info;
   if (rt_scene_info(a.config, &info) != 0 || a.options.width < 2 || a.options.height < 2 || a.options.samples < 1 ||
-      (a.integrator != RT_TRACE_PATH && a.integrator != RT_CAST_RAY))
+      (a.integrator != RT_TRACE_PATH && a.integrator != RT_CAST_RAY) ||
+      (a.pass > 0 && (a.pass > a.options.samples || a.gpus > 1)))
   {
     usage(argv[0]);
     return EXIT_FAILURE;
@@ -139,7 +157,16 @@ int main(int argc, char **argv)
   const double t_hip = now_seconds();
 
   double tic = now_seconds();
-  render_ex(framebuffer, NULL, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options);
+  int held = a.options.samples;
+  if (a.pass > 0)
+  {
+    held = render_progressive(framebuffer, NULL, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options, a.pass,
+                              on_pass, NULL);
+    if (held < 0)
+      return EXIT_FAILURE; /* render_progressive said why */
+  }
+  else
+    render_ex(framebuffer, NULL, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options);
   double toc = now_seconds();
   double phase[3] = {0, 0, 0};
   rt_hip_last_image_phases(phase);
@@ -152,9 +179,11 @@ int main(int argc, char **argv)
          a.gpus == 1 ? "" : "s");
   if (kernel_s > 0)
     printf("%.3e ray-bounces/s, %.2f Mpixel-samples/s\n", (double)rt_last_ray_bounces() / kernel_s,
-           (double)a.options.width * a.options.height * a.options.samples / kernel_s * 1e-6);
+           (double)a.options.width * a.options.height * held / kernel_s * 1e-6);
   int status = EXIT_SUCCESS;
-  if (rt_last_render_cancelled())
+  if (rt_last_render_cancelled() && a.pass > 0)
+    printf("interrupted: the image holds %d of %d samples per pixel\n", held, a.options.samples);
+  else if (rt_last_render_cancelled())
     printf("interrupted: the image holds the tiles finished so far\n");
   printf("writing result to '%s'...\n", a.options.result);
 #ifndef VALGRIND

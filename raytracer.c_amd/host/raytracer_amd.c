@@ -57,7 +57,12 @@ void rt_set_integrator(int integrator)
 }
 int rt_get_integrator(void) { return g_integrator; }
 double rt_last_render_seconds(void) { return g_last_seconds; }
-void rt_set_cancel_flag(const volatile int *flag) { rt_hip_set_cancel_flag(flag); }
+static const volatile int *g_cancel_flag = NULL; /* render_progressive polls it between passes */
+void rt_set_cancel_flag(const volatile int *flag)
+{
+  g_cancel_flag = flag;
+  rt_hip_set_cancel_flag(flag);
+}
 int rt_last_render_cancelled(void) { return g_last_cancelled; }
 long long rt_last_ray_bounces(void) { return g_last_bounces; }
 
@@ -205,8 +210,8 @@ static int devices_to_use(void)
   return n >= 1 ? n : 1;
 }
 
-void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects,
-               MeshObject *meshes, size_t n_meshes, Camera *camera, Options *options)
+/* the shim's mesh records for the caller's MeshObjects (NULL for none; exits when out of memory, as render does) */
+static RtHipMesh *hip_meshes(MeshObject *meshes, size_t n_meshes)
 {
   RtHipMesh *hm = NULL;
   if (n_meshes)
@@ -226,7 +231,12 @@ void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t 
       hm[m].vertices = (const RtHipVertex *)meshes[m].mesh.vertices;
     }
   }
+  return hm;
+}
 
+/* the whole image, with the run-time settings */
+static RtHipParams image_params(const Options *options)
+{
   RtHipParams p;
   memset(&p, 0, sizeof p);
   p.width = options->width;
@@ -235,6 +245,14 @@ void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t 
   p.max_depth = g_max_depth;
   p.seed = g_seed;
   p.integrator = g_integrator == RT_CAST_RAY ? RT_HIP_CAST_RAY : RT_HIP_TRACE_PATH;
+  return p;
+}
+
+void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects,
+               MeshObject *meshes, size_t n_meshes, Camera *camera, Options *options)
+{
+  RtHipMesh *hm = hip_meshes(meshes, n_meshes);
+  RtHipParams p = image_params(options);
 
   uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
   double seconds = 0;
@@ -257,4 +275,61 @@ void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t 
 void render(uint8_t *framebuffer, Object *objects, size_t n_objects, Camera *camera, Options *options)
 {
   render_ex(framebuffer, NULL, objects, n_objects, NULL, 0, camera, options);
+}
+
+int render_progressive(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects, MeshObject *meshes,
+                       size_t n_meshes, Camera *camera, Options *options, int pass_samples, RtPassFn *on_pass, void *user)
+{
+  if (devices_to_use() > 1)
+  {
+    fprintf(stderr, "render_progressive: renders on one device (%d set)\n", devices_to_use());
+    return RT_HIP_EINVAL;
+  }
+  if (pass_samples < 1)
+  {
+    fprintf(stderr, "render_progressive: pass_samples must be >= 1\n");
+    return RT_HIP_EINVAL;
+  }
+  RtHipMesh *hm = hip_meshes(meshes, n_meshes);
+  RtHipParams p = image_params(options);
+  p.tile_first = 0;
+  p.tile_stride = 1;
+  p.tile_count = (uint32_t)(((options->width + RT_HIP_TILE - 1) / RT_HIP_TILE) * ((options->height + RT_HIP_TILE - 1) / RT_HIP_TILE));
+  RtHipScene *scene = NULL;
+  RtHipAccum *acc = NULL;
+  uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
+  double seconds = 0;
+  int done = 0;
+  int rc = rt_hip_scene_create((const RtHipSphere *)objects, n_objects, hm, n_meshes, 0, &scene);
+  if (!rc)
+    rc = rt_hip_accum_create(scene, (const RtHipCamera *)camera, &p, &acc);
+  while (!rc)
+  {
+    const int n = pass_samples < p.samples - done ? pass_samples : p.samples - done;
+    double pass_s = 0;
+    rc = rt_hip_accum_add_host(acc, n, stats, &pass_s);
+    if (rc)
+      break;
+    done += n;
+    seconds += pass_s;
+    if (on_pass)
+      on_pass(done, p.samples, pass_s, user);
+    if (done >= p.samples || (g_cancel_flag && *g_cancel_flag))
+      break;
+  }
+  if (!rc)
+    rc = rt_hip_accum_read_image(acc, linear_rgb, framebuffer);
+  if (rc)
+    fprintf(stderr, "render_progressive: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+  rt_hip_accum_destroy(acc);
+  rt_hip_scene_destroy(scene);
+  free(hm);
+  if (rc)
+    return rc;
+  g_last_cancelled = done < p.samples;
+  ray_count += (long long)stats[RT_HIP_STAT_RAYS];
+  intersection_test_count += (long long)stats[RT_HIP_STAT_TESTS];
+  g_last_seconds = seconds;
+  g_last_bounces = (long long)stats[RT_HIP_STAT_CASTS];
+  return done;
 }

@@ -15,6 +15,9 @@ TILE, TILE_PIXELS, TILE_FLOATS = 8, 64, 192
 STAT_RAYS, STAT_CASTS, STAT_TESTS, STAT_SAMPLES, NSTATS = 0, 1, 2, 3, 4
 FAIL_ALLOC_PARK_WS, FAIL_ALLOC_WIDE_PEND = 1, 2   # rt_hip_selftest_fail_alloc
 FAIL_PEND_SLOT, FAIL_PARK_SLOT = 1, 2             # rt_hip_launch_status
+EINVAL = -2                                       # RT_HIP_EINVAL
+# render_progressive's per-pass callback: (samples done, budget, kernel seconds of the pass, user)
+PASS_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_double, C.c_void_p)
 
 
 class Vec2(C.Structure):
@@ -108,6 +111,14 @@ SHIM_SYMBOLS = {
     "rt_hip_selftest_xcc": (C.c_int, [C.c_uint32, C.c_void_p, C.c_int]),
     "rt_hip_selftest_intersect": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_int]),
+    "rt_hip_accum_create": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipParams), C.POINTER(C.c_void_p)]),
+    "rt_hip_accum_add": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rt_hip_accum_add_host": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "rt_hip_accum_resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_accum_read_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_accum_samples": (C.c_int32, [C.c_void_p]),
+    "rt_hip_accum_kernel": (C.c_char_p, [C.c_void_p]),
+    "rt_hip_accum_destroy": (None, [C.c_void_p]),
     "rt_hip_untile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_set_cancel_flag": (None, [C.c_void_p]),
@@ -152,6 +163,8 @@ HOST_SYMBOLS = {
     "rt_get_max_depth": (C.c_int, []),
     "rt_get_seed": (C.c_uint64, []),
     "rt_set_cancel_flag": (None, [C.c_void_p]),
+    "render_progressive": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
+                                     C.POINTER(Camera), C.POINTER(Options), C.c_int, C.c_void_p, C.c_void_p]),
     "rt_last_render_cancelled": (C.c_int, []),
     "rt_last_render_seconds": (C.c_double, []),
     "rt_last_ray_bounces": (C.c_longlong, []),

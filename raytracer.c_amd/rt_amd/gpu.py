@@ -107,6 +107,18 @@ class GpuScene:
                "rt_hip_render_tiles_chunked")
         return tiles, tiles8, stats
 
+    def accumulate(self, seed, samples, max_depth=None, integrator="path", first=0, stride=1, count=None, camera=None):
+        """A progressive render of `samples` per pixel (the budget) over tiles first + k * stride, k < count (default: the whole
+        image), added in passes: Accumulation.add(n).  After the whole budget its resolve() is render_tiles()' frame for the same
+        budget at suggest_chunks() chunks, bit for bit, whatever the passes were (rt_hip.h, rt_hip_accum_*)."""
+        if count is None:
+            count = n_tiles(self.scene.width, self.scene.height)
+        p = self.params(seed, first, stride, count, samples, max_depth, integrator)
+        handle = C.c_void_p()
+        _check(self.shim.rt_hip_accum_create(self.handle, C.byref(camera if camera is not None else self.scene.camera),
+                                             C.byref(p), C.byref(handle)), "rt_hip_accum_create")
+        return Accumulation(self, handle, count)
+
     def untile(self, tiles, tiles8, first, stride, count, image=None, image8=None):
         """Scatter a compact tile buffer into row-major images on torch's current stream."""
         dev = tiles.device
@@ -134,6 +146,55 @@ class GpuScene:
         st = stats.cpu().tolist()
         return image, image8, dict(rays=st[abi.STAT_RAYS], casts=st[abi.STAT_CASTS], tests=st[abi.STAT_TESTS],
                                    samples=st[abi.STAT_SAMPLES])
+
+
+class Accumulation:
+    """An accumulation (rt_hip_accum_*) made by GpuScene.accumulate.  Passes and resolves run asynchronously on torch's current
+    stream; the scene must stay open until close()."""
+
+    def __init__(self, gs, handle, count):
+        self.gs, self.shim, self.handle, self.count = gs, gs.shim, handle, count
+
+    @property
+    def samples(self):
+        """samples per pixel done so far"""
+        return int(self.shim.rt_hip_accum_samples(self.handle))
+
+    @property
+    def kernel(self):
+        """the member every pass runs (the plan made at creation)"""
+        return self.shim.rt_hip_accum_kernel(self.handle).decode()
+
+    def add(self, n, stats=None):
+        """render the next n samples of every pixel; stats: an i64 [4] device tensor the pass's counters are added to"""
+        dev = torch.device("cuda", self.gs.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.shim.rt_hip_accum_add(self.handle, n, stats.data_ptr() if stats is not None else None, C.c_void_p(stream)),
+               "rt_hip_accum_add")
+        return stats
+
+    def resolve(self, tiles=None, tiles8=None):
+        """the mean of the samples done -> (tiles f32 [count,64,3], tiles8 u8 [count,64,3]); pass buffers to reuse them"""
+        dev = torch.device("cuda", self.gs.device)
+        if tiles is None:
+            tiles = torch.empty((self.count, abi.TILE_PIXELS, 3), dtype=torch.float32, device=dev)
+        if tiles8 is None:
+            tiles8 = torch.empty((self.count, abi.TILE_PIXELS, 3), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.shim.rt_hip_accum_resolve(self.handle, tiles.data_ptr(), tiles8.data_ptr(), C.c_void_p(stream)),
+               "rt_hip_accum_resolve")
+        return tiles, tiles8
+
+    def close(self):
+        if self.handle:
+            self.shim.rt_hip_accum_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def render_image_host(scene, seed, n_devices=1, samples=None, max_depth=None, integrator="path"):
