@@ -35,9 +35,17 @@ class GpuScene:
         _check(self.shim.rt_hip_scene_create(scene.objects, scene.n_objects, self._meshes, scene.n_meshes, device,
                                              C.byref(handle)), "rt_hip_scene_create")
         self.handle = handle
+        self._accums = []  # handles of the accumulations made here: closed before the scene (rt_hip.h: the scene outlives them)
 
     def close(self):
         if self.handle:
+            # first whatever accumulation is still open: the garbage collector finalises a scene and its accumulations in any
+            # order when they die together, and rt_hip_accum_destroy reads the scene
+            for h in self._accums:
+                if h:
+                    self.shim.rt_hip_accum_destroy(h)
+                    h.value = None
+            self._accums = []
             self.shim.rt_hip_scene_destroy(self.handle)
             self.handle = None
 
@@ -117,6 +125,7 @@ class GpuScene:
         handle = C.c_void_p()
         _check(self.shim.rt_hip_accum_create(self.handle, C.byref(camera if camera is not None else self.scene.camera),
                                              C.byref(p), C.byref(handle)), "rt_hip_accum_create")
+        self._accums = [h for h in self._accums if h] + [handle]
         return Accumulation(self, handle, count)
 
     def untile(self, tiles, tiles8, first, stride, count, image=None, image8=None):
@@ -188,7 +197,7 @@ class Accumulation:
     def close(self):
         if self.handle:
             self.shim.rt_hip_accum_destroy(self.handle)
-            self.handle = None
+            self.handle.value = None   # the object GpuScene.close() holds too
 
     def __del__(self):
         try:

@@ -2,7 +2,6 @@
 to in passes of any sizes is, after the whole budget, the one-shot frame BIT FOR BIT -- on every row of the pick table --
 and in between it is the oracle's frame of the samples done."""
 import ctypes as C
-import math
 import os
 import subprocess
 
@@ -11,7 +10,7 @@ import pytest
 
 from conftest import SEED
 from test_gpu_parity import PICK_ROWS, _WP
-from util import assert_parity, fixed_point_floor
+from util import acc_scale_exp, assert_parity, fixed_point_floor
 
 pytestmark = pytest.mark.gpu
 
@@ -44,16 +43,6 @@ def _accumulate(gs, seed, passes, integrator="path", budget=None):
     t, t8 = acc.resolve()
     torch.cuda.synchronize()
     return acc, t, t8, stats
-
-
-def _acc_scale_exp(sc, samples):
-    """pt_acc_scale_exp of pt_device.h: the fixed-point scale 2^s of a launch of `samples`"""
-    emax = max([abs(c) for i in range(sc.n_objects) for c in sc.objects[i].emission.tuple()] +
-               [abs(c) for i in range(sc.n_meshes) for c in sc.meshes[i].emission.tuple()] + [0.0])
-    per_sample = (sc.max_depth + 2.0) * max(10.0 / 255.0, emax) * 1.01
-    _, e = math.frexp(4611686018427387904.0 / (per_sample * samples))
-    _, e1 = math.frexp(2251799813685248.0 / per_sample)
-    return min(e, e1) - 1
 
 
 @pytest.mark.parametrize("cls,integrator,faults,kernel", PICK_ROWS,
@@ -104,7 +93,7 @@ def test_intermediate_frames_are_the_oracle_s_frames_of_the_samples_done(gpu, pt
     import torch
     acc = gs.accumulate(SEED, budget, integrator=integrator)
     stats = torch.zeros(4, dtype=torch.int64, device=torch.device("cuda", 0))
-    floor = max(fixed_point_floor(sc), (sc.max_depth + 2) * 2.0 ** -_acc_scale_exp(sc, budget) / 2)
+    floor = max(fixed_point_floor(sc), (sc.max_depth + 2) * 2.0 ** -acc_scale_exp(sc, budget) / 2)
     for n in (3, 4):
         acc.add(n, stats)
         k = acc.samples
@@ -212,6 +201,28 @@ def test_create_holds_the_pools_it_planned_with(gpu):
     assert stats.tolist() == st.tolist()
     gs.launch_status()
     acc.close()
+    gs.close()
+    sc.free()
+
+
+def test_closing_the_scene_first_closes_its_accumulations(gpu):
+    """GpuScene.close() destroys the accumulations still open on it before the scene (rt_hip.h: the scene outlives them): the
+    garbage collector finalises a scene and its accumulations in any order when they die together, as after a failed test.
+    The accumulation's own close() is then a no-op, and the device stays usable"""
+    import torch
+    from util import glass_scene
+    sc = glass_scene(48, 32, 4)
+    gs = gpu.GpuScene(sc)
+    acc = gs.accumulate(SEED, 4)
+    acc.add(2)
+    torch.cuda.synchronize()
+    gs.close()
+    assert not acc.handle and acc.samples == 0
+    acc.close()
+    assert float(torch.ones(4, device="cuda").sum()) == 4.0   # no HIP error left behind for the next call to find
+    gs = gpu.GpuScene(sc)
+    _one_shot(gs, SEED, gpu.n_tiles(sc.width, sc.height))
+    gs.launch_status()
     gs.close()
     sc.free()
 

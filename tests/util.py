@@ -70,6 +70,17 @@ def fixed_point_floor(sc):
     return (sc.max_depth + 2) ** 2 * emax * 2.0 ** -51
 
 
+def acc_scale_exp(sc, samples):
+    """pt_acc_scale_exp of pt_device.h: the fixed-point scale 2^s of a launch of `samples`"""
+    import math
+    emax = max([abs(c) for i in range(sc.n_objects) for c in sc.objects[i].emission.tuple()] +
+               [abs(c) for i in range(sc.n_meshes) for c in sc.meshes[i].emission.tuple()] + [0.0])
+    per_sample = (sc.max_depth + 2.0) * max(10.0 / 255.0, emax) * 1.01
+    _, e = math.frexp(4611686018427387904.0 / (per_sample * samples))
+    _, e1 = math.frexp(2251799813685248.0 / per_sample)
+    return min(e, e1) - 1
+
+
 def untile_numpy(tiles, width, height, first, stride, count, image):
     """numpy statement of rt_hip_untile(): tiles [>=count, 64, 3] -> image [H, W, 3] in place"""
     tx = (width + 7) // 8
