@@ -12,7 +12,10 @@ shim (RT_HIP_SHIM_PATH=.../librt_hip_diag.so, RT_HIP_DIAG_WALK_REJECTED=1) and p
   parked rays, parked rays the probe alone would have let through, rays that left a hull facet, leaf pre-tests.
 
 The PT_DIAG build is a checker's build of the product kernels, not the product: it never runs outside these tests.
-usage: diag_child.py SET   with SET in {configs, fullsize, fuzz, convex, rooms, wide}"""
+usage: diag_child.py SET   with SET in {configs, fullsize, fuzz, convex, rooms, wide, views}
+
+The set `views` is every row of the kernel pick table (tests/test_gpu_parity.py: PICK_ROWS) under every variant of
+util.VARIANTS, each with the row's integrator and allocation faults; its records also name the kernel the launch took."""
 import json
 import os
 import sys
@@ -66,6 +69,20 @@ def scene_sets(which):
     raise SystemExit(f"unknown scene set {which!r}")
 
 
+def view_rows():
+    """the `views` set: -> (name, scene, integrator, faults, row kernel) for every pick-table row under every variant"""
+    from test_gpu_parity import PICK_ROWS
+    from util import VARIANTS, class_scene, pick_moves, view_variant
+    out = []
+    for cls, integrator, faults, kernel in PICK_ROWS:
+        base = class_scene(**cls)
+        for v in VARIANTS:
+            if not pick_moves(cls, kernel, v):
+                out.append((f"{kernel}:{'+'.join(f'{a}={b}' for a, b in cls.items())}:{v}", view_variant(base, v), integrator, faults,
+                            kernel))
+    return out
+
+
 def main():
     shim_path = os.environ.get("RT_HIP_SHIM_PATH", "")
     if "diag" not in os.path.basename(shim_path):
@@ -73,22 +90,38 @@ def main():
     os.environ["RT_HIP_DIAG_WALK_REJECTED"] = "1"   # read by the shim at every launch
     import torch
     from rt_amd import gpu as G
-    for name, sc in scene_sets(sys.argv[1] if len(sys.argv) > 1 else "configs"):
-        for integrator in ("path", "whitted"):
+    from rt_amd import abi
+    which = sys.argv[1] if len(sys.argv) > 1 else "configs"
+    if which == "views":
+        runs = [(name, sc, [integrator], faults, kernel) for name, sc, integrator, faults, kernel in view_rows()]
+    else:
+        runs = [(name, sc, ["path", "whitted"], 0, None) for name, sc in scene_sets(which)]
+    shim = abi.load_shim()
+    for name, sc, integrators, faults, row_kernel in runs:
+        for integrator in integrators:
             if integrator == "whitted" and sc.max_depth > 32:
                 continue
+            if faults & abi.FAIL_ALLOC_WIDE_PEND:
+                shim.rt_hip_release_cache()   # no pending-ray pool yet: the launch has to ask for the wide one
+            shim.rt_hip_selftest_fail_alloc(faults)
             gs = G.GpuScene(sc)
-            stats = torch.zeros(48, dtype=torch.int64, device="cuda")
             try:
-                gs.render_tiles(1666943821, 0, 1, G.n_tiles(sc.width, sc.height), stats=stats, integrator=integrator)
+                stats = torch.zeros(48, dtype=torch.int64, device="cuda")
+                total = G.n_tiles(sc.width, sc.height)
+                # (the views set launches as the row tests do, at the suggested chunks: the row's kernel is that launch's)
+                chunks = gs.suggest_chunks(total) if row_kernel and integrator == "path" else 1
+                gs.render_tiles(1666943821, 0, 1, total, stats=stats, integrator=integrator, chunks=chunks)
             except G.ShimError as e:
                 print(json.dumps({"scene": name, "integrator": integrator, "skipped": str(e)}), flush=True)
                 gs.close()
                 continue
+            finally:
+                shim.rt_hip_selftest_fail_alloc(0)
             torch.cuda.synchronize()
             st = stats.cpu().tolist()
             d = st[4:]
             print(json.dumps({"scene": name, "integrator": integrator, "kernel": gs.kernel_name(integrator),
+                              "last_launch_kernel": gs.last_launch_kernel(), "row_kernel": row_kernel,
                               "n_primitives": sc.n_primitives, "casts": st[1], "violations": d[12],
                               "candidates": d[3], "parked": d[17], "parked_probe_would_park": d[23],
                               "left_hull_facet": d[28], "tile_cannot_see_mesh": d[38], "leaf_pretests": d[16], "small_mesh_pretests": d[35],

@@ -114,3 +114,37 @@ def test_diag_rooms_beyond_the_staging_budget_zero_violations():
     # rays were parked and walked (also those the probe rejects), leaves were pre-tested: 0 violations above
     assert len(mesh) == 1 and mesh[0]["kernel"] == "pt_render_tiles_tri_queued_mem", mesh
     assert 0 < mesh[0]["candidates"] < mesh[0]["casts"] * 308 and mesh[0]["parked"] > mesh[0]["parked_probe_would_park"] > 0 and mesh[0]["leaf_pretests"] > 0
+
+
+def test_diag_pick_rows_under_views_zero_violations():
+    """every row of the kernel pick table (tests/test_gpu_parity.py: PICK_ROWS) under every camera and placement variant of
+    util.VARIANTS, with the row's allocation faults: no conservative rule dropped anything, every member ran, and where a
+    variant is built to bring a rule into play, the rule was applied"""
+    from test_gpu_parity import PICK_ROWS
+    recs = _run("views", timeout=300)
+    _no_violations(recs)
+    assert not [r for r in recs if "skipped" in r], [r for r in recs if "skipped" in r]
+    bad = [r for r in recs if r["last_launch_kernel"] != r["row_kernel"]]
+    assert not bad, f"launches that left their row: {bad[:5]}"
+    assert {r["last_launch_kernel"] for r in recs} == {k for _, _, _, k in PICK_ROWS}
+    by = {}
+    for r in recs:
+        by.setdefault(r["row_kernel"], []).append(r)
+    for k, rs in by.items():   # the filter dropped primitives (else the re-check had nothing to check)
+        assert any(0 < r["candidates"] < r["casts"] * r["n_primitives"] for r in rs), (k, rs[:3])
+    for r in recs:
+        v = r["scene"].rsplit(":", 1)[1]
+        queued = "_queued" in r["row_kernel"]
+        if v == "telephoto" and queued:      # aimed past the triangles' ball: tiles that cannot see the mesh
+            assert r["tile_cannot_see_mesh"] > 0, r
+        if r["row_kernel"].endswith("_sph"):  # the sphere probe: rays it alone would park
+            assert r["parked_probe_would_park"] > 0 or v == "telephoto", r
+    # the hull-facet rule and BigPrune under every variant whose scale leaves them in play: at far (near_R ~ 6e7) and huge the
+    # hull margin exceeds 1 (hull_margin_for: no walk is skipped), at far the walls' bounds are too loose for BigPrune
+    # (big_prune_for switches it off), and at tiny the walls are no longer wall-sized (radius 10 < 1000)
+    rnd = [r for r in recs if "round_mesh=True" in r["scene"] and "_queued" in r["row_kernel"]]
+    for v in ("inside", "steep", "telephoto", "wide", "sheared", "near_plane", "tiny"):
+        assert sum(x["left_hull_facet"] for x in rnd if x["scene"].endswith(":" + v)) > 0, v
+    rooms = [r for r in recs if r["row_kernel"] in ("pt_render_tiles", "pt_render_tiles_pool_mem_s")]
+    for v in ("inside", "steep", "telephoto", "wide", "sheared", "near_plane", "huge"):
+        assert sum(r["walls_pruned"] for r in rooms if r["scene"].endswith(":" + v)) > 0, v

@@ -449,3 +449,187 @@ def class_scene(n_packed=4, tris=0, chk=False, refr=False, glass2=False, wide=Fa
         flags = abi.M_REFRACTION if mesh_refr else abi.M_DEFAULT
         meshes = [dict(flags=flags | (abi.M_CHECKERED if mesh_chk else 0), color=(0.9, 0.85, 0.8), triangles=tl)]
     return S.custom_scene(objs, width, height, samples, depth, (0, 0, 50), (0, 0, 0), meshes=meshes)
+
+
+# ---- the same scene through other cameras, and placed far out or scaled (tests/test_views_cpu.py, test_gpu_views.py) -------
+# Camera variants keep the geometry; placement variants move geometry and camera together.  Every hand-built camera keeps
+# its eye off the plane of its frame, so that get_camera_ray's pos - (llc + H u + V v) is never zero for any u, v a jittered
+# sample can take (the reference asserts m > 0 in vec3_normalize).
+VIEWS = ("inside", "steep", "telephoto", "wide", "sheared", "near_plane")
+PLACEMENTS = ("far", "tiny", "huge")
+VARIANTS = VIEWS + PLACEMENTS
+# far: |FAR_OFFSET| = 2.02e7 lies in [2^24, 2^25), so every centre and vertex of a row's room (extent < 100) is spaced 2 apart
+# in fp32: more than a quarter of the smallest packed sphere's radius (0.93 in a room of 300) and of the median triangle edge
+# (~3 on the sheet, ~2.2 on the round mesh) -- the margins that widen by e |c| are then as large as the primitives they guard.
+# near_R = 1.5 (|camera| + reach) + 1 ~ 6.1e7 stays far below RT_NEAR_R_LIMIT (1e15).  Mixed signs: no axis is special.
+FAR_OFFSET = (-1.5e7, 1.1e7, -0.8e7)
+SCALES = {"tiny": 1e-3, "huge": 1e3}
+# (row kernel, variant) pairs whose scene class changes with the variant, and why
+PICK_MOVES = {
+    # the wide rows' floor sphere of radius 1e19 is what makes them wide_range (a centre or radius beyond 1e17); scaled by
+    # 1e-3 it is 1e16, and the scene is an ordinary one: the plain filter kernels take it
+    ("pt_render_tiles_big", "tiny"), ("pt_render_tiles_big_chk", "tiny"), ("pt_render_tiles_big_refr", "tiny"),
+    ("pt_render_tiles_tri_big", "tiny:wide"), ("pt_render_tiles_pool_mem", "tiny"), ("pt_render_tiles_pool_mem_chk", "tiny"),
+    ("pt_whitted_tiles_big", "tiny"),
+}
+
+
+def pick_moves(cls, kernel, variant):
+    """the row (cls, kernel) leaves the pick table's row under `variant` (PICK_MOVES)"""
+    return (kernel, variant) in PICK_MOVES or (cls.get("wide") and (kernel, variant + ":wide") in PICK_MOVES)
+
+
+def scene_parts(sc):
+    """-> (object dicts, mesh dicts) of a Scene, as custom_scene takes them (vertex positions and texture coordinates)"""
+    import ctypes as C
+    objs = [dict(flags=int(o.flags), radius=float(o.radius), center=o.center.tuple(), color=o.color.tuple(),
+                 emission=o.emission.tuple()) for o in (sc.objects[i] for i in range(sc.n_objects))]
+    meshes = []
+    for m in range(sc.n_meshes):
+        mo = sc.meshes[m]
+        n = 3 * mo.mesh.num_triangles
+        v = np.ctypeslib.as_array(C.cast(mo.mesh.vertices, C.POINTER(C.c_double)), shape=(n, 5)).copy()
+        meshes.append(dict(flags=int(mo.flags), color=mo.color.tuple(), emission=mo.emission.tuple(), vertices=v))
+    return objs, meshes
+
+
+def camera_arrays(cam):
+    """-> pos, H, V, llc as fp64 numpy vectors"""
+    return tuple(np.array(getattr(cam, f).tuple()) for f in ("position", "horizontal", "vertical", "lower_left_corner"))
+
+
+def hand_camera(pos, H, V, llc):
+    from rt_amd import abi
+    cam = abi.Camera()
+    cam.position, cam.horizontal = abi.Vec3(*map(float, pos)), abi.Vec3(*map(float, H))
+    cam.vertical, cam.lower_left_corner = abi.Vec3(*map(float, V)), abi.Vec3(*map(float, llc))
+    return cam
+
+
+def _rebuild(sc, objs, meshes, camera):
+    from rt_amd import scene as S
+    tm = [dict(flags=m["flags"], color=m["color"], emission=m["emission"],
+               triangles=[[tuple(r) for r in m["vertices"][3 * t:3 * t + 3]] for t in range(len(m["vertices"]) // 3)])
+          for m in meshes]
+    out = S.custom_scene(objs, sc.width, sc.height, sc.samples, sc.max_depth, (0, 0, 1), (0, 0, 0), meshes=tm)
+    out.camera = camera
+    return out
+
+
+def mesh_ball(meshes):
+    """the triangles' bounding ball as the shim forms it: centre = middle of the bounds, radius = the farthest vertex"""
+    v = np.concatenate([m["vertices"][:, :3] for m in meshes])
+    c = 0.5 * v.min(axis=0) + 0.5 * v.max(axis=0)
+    return c, float(np.sqrt(((v - c) ** 2).sum(axis=1).max()))
+
+
+def free_point(objs, near, clearance=1.0):
+    """a point near `near` at least `clearance` outside every sphere (walls included: the room is the space outside them)"""
+    rng = np.random.default_rng(3)
+    objs = [o for o in objs if o["radius"] < 1e15]   # (the wide rows' floor of radius 1e19: fp64 cannot tell its surface here)
+    c = np.array([o["center"] for o in objs])
+    r = np.array([o["radius"] for o in objs])
+    for k in range(10000):
+        p = np.asarray(near, float) + (rng.uniform(-1, 1, 3) * min(12.0, 0.5 + 0.01 * k) if k else 0.0)
+        if (np.sqrt(((c - p) ** 2).sum(axis=1)) > r + clearance).all():
+            return p
+    raise AssertionError("no free point")
+
+
+def _frame(pos, forward, right, up, width, height, half_w, centre_uv=(0.5, 0.5)):
+    """a frame at distance |forward| from the eye, of half-width half_w x |forward| and the image's aspect: -> H, V, llc with
+    pos - (llc + H u + V v) = forward + H (cu - u) + V (cv - v)"""
+    f = np.asarray(forward, float)
+    right = np.asarray(right, float) / np.linalg.norm(right)
+    up = np.asarray(up, float) / np.linalg.norm(up)
+    H = right * (2.0 * half_w * np.linalg.norm(f))
+    V = up * (2.0 * half_w * np.linalg.norm(f) * height / width)
+    llc = np.asarray(pos, float) - f - H * centre_uv[0] - V * centre_uv[1]
+    return H, V, llc
+
+
+def _basis(forward):
+    f = np.asarray(forward, float) / np.linalg.norm(forward)
+    right = np.cross([0.0, 1.0, 0.0], f)
+    right /= np.linalg.norm(right)
+    return f, right, np.cross(f, right)
+
+
+def view_variant(sc, name):
+    """the scene `sc` (a util.class_scene row: config 4's room, camera (0, 0, 50) -> origin) under variant `name` of VARIANTS:
+    a new Scene with the same geometry, materials, size, spp and depth and another camera, or the whole scene and its camera
+    moved (far) or scaled about the origin (tiny, huge).  See tests/test_views_cpu.py for what each one is shown to reach."""
+    from rt_amd import scene as S
+    objs, meshes = scene_parts(sc)
+    pos0, H0, V0, llc0 = camera_arrays(sc.camera)
+    w, h = sc.width, sc.height
+    small = [o for o in objs if o["radius"] < 1000]
+    if name in PLACEMENTS:
+        off = np.array(FAR_OFFSET) if name == "far" else np.zeros(3)
+        s = SCALES.get(name, 1.0)
+        for o in objs:
+            o["center"] = tuple(np.array(o["center"]) * s + off)
+            o["radius"] = o["radius"] * s
+        for m in meshes:
+            m["vertices"][:, :3] = m["vertices"][:, :3] * s + off
+        return _rebuild(sc, objs, meshes, hand_camera(pos0 * s + off, H0 * s, V0 * s, llc0 * s + off))
+    if name == "inside":
+        if meshes:
+            c, R = mesh_ball(meshes)
+            # inside the triangles' ball; for the tessellated ball (radius 7) also inside the ball itself, off its centre
+            near = c + (np.array([1.0, 0.5, -2.0]) if R < 10 else np.array([3.0, 2.0, 10.0]))
+            pos = free_point(objs, near, clearance=0.3)
+        elif objs[8]["flags"] & 8 and sc.max_depth <= 8:
+            # the first packed sphere is glass (refr rows): the camera inside it, off its centre (not at depth 30, where every
+            # camera ray would grow a tree of up to 2^30 rays inside the glass)
+            pos = np.array(objs[8]["center"]) + 0.4 * objs[8]["radius"] * np.array([0.6, -0.48, 0.64])
+        else:
+            pos = free_point(objs, (4.0, 3.0, 10.0))
+        cam = S.make_camera(w, h, tuple(pos), tuple(pos + np.array([0.35, -0.25, -1.0])))
+        return _rebuild(sc, objs, meshes, cam)
+    if name == "steep":
+        # straight down from under the ceiling, 1e-3 off the vertical: right = normalize(y x forward) of a near-zero cross product
+        return _rebuild(sc, objs, meshes, S.make_camera(w, h, (0.0, 15.0, 1e-3), (0.0, 0.0, 0.0)))
+    if name == "telephoto":
+        # a frame 6e-5 across at distance 1 (tiles of ~1e-5 rad): aimed past the silhouette of a ball -- the triangles' bounding
+        # ball in mesh scenes, by 0.02 rad (tile_cone_reaches_ball's 1e-5 off cos(theta) alone widens a cone by sqrt(2e-5) =
+        # 4.5e-3 rad: no tile sees the mesh), else the first packed sphere (its edge in view)
+        if meshes:
+            c, R = mesh_ball(meshes)
+            past = 0.02
+        else:
+            c, R = np.array(objs[8]["center"]), objs[8]["radius"]
+            past = 0.0
+        pos = pos0
+        L = c - pos
+        D = np.linalg.norm(L)
+        f0, right, up = _basis(L)
+        ang = np.arcsin(min(R / D, 1.0)) + past
+        f = np.cos(ang) * f0 + np.sin(ang) * right
+        _, right, up = _basis(f)
+        H, V, llc = _frame(pos, f, right, up, w, h, 3e-5)
+        return _rebuild(sc, objs, meshes, hand_camera(pos, H, V, llc))
+    if name == "wide":
+        # a 176 degree horizontal field of view (half-width tan 88 deg) from inside the room: the central tiles' cones pass 90 deg
+        pos = np.array([0.0, 0.0, 45.0])
+        f, right, up = _basis((0.1, -0.05, -1.0))
+        H, V, llc = _frame(pos, f, right, up, w, h, np.tan(np.radians(88.0)))
+        return _rebuild(sc, objs, meshes, hand_camera(pos, H, V, llc))
+    if name == "sheared":
+        # rolled 30 deg, mirrored (H negated), V sheared towards H, and the principal ray (the frame point nearest the eye)
+        # outside the frame: u = -0.3 of it
+        f, right, up = _basis(-pos0)
+        a = np.radians(30.0)
+        r2, u2 = np.cos(a) * right + np.sin(a) * up, -np.sin(a) * right + np.cos(a) * up
+        H = -r2 * 2.0 * np.tan(np.radians(25.0))
+        V = (u2 + 0.4 * r2) * 2.0 * np.tan(np.radians(25.0)) * h / w
+        llc = pos0 - f - H * (-0.3) - V * 0.55
+        return _rebuild(sc, objs, meshes, hand_camera(pos0, H, V, llc))
+    if name == "near_plane":
+        # the eye 1e-3 in front of its frame, over the frame point u = 0.4, v = 0.6: tiles around it see nearly a half-space
+        pos = np.array([0.0, 2.0, 45.0])
+        f, right, up = _basis((0.05, -0.1, -1.0))
+        H, V = right * 3.0, up * 3.0 * h / w
+        llc = pos - f * 1e-3 - H * 0.4 - V * 0.6
+        return _rebuild(sc, objs, meshes, hand_camera(pos, H, V, llc))
+    raise KeyError(name)
