@@ -258,6 +258,21 @@ typedef void RtPassFn(int done, int total, double kernel_seconds, void *user);
 int render_progressive(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects, MeshObject *meshes,
                        size_t n_meshes, Camera *camera, Options *options, int pass_samples, RtPassFn *on_pass, void *user);
 
+/* First-hit feature buffers of the frame's own samples (include/rt_hip.h, rt_hip_render_aov_*): options->samples camera samples
+ * per pixel with the seed of rt_get_seed(), i.e. the samples render_ex draws its camera rays with.  Row-major arrays of
+ * width x height pixels, each may be NULL (not all): albedo and normal 3 floats per pixel (the mean over the samples of the
+ * first hit's colour -- checkered where M_CHECKERED -- and unit normal; BACKGROUND and 0 for a sample that misses), depth the
+ * least t of the samples that hit (+inf: none), object_id the object that gave it (spheres 0..n_objects-1, then meshes;
+ * 0xFFFFFFFF: none), hits how many samples hit.  Runs on one device, the first of the device map.  Returns the samples per
+ * pixel, or a negative RT_HIP_E* code with the reason on stderr. */
+typedef struct
+{
+  float *albedo, *normal, *depth;
+  uint32_t *object_id, *hits;
+} RtAovImage;
+int render_aov(RtAovImage *out, Object *objects, size_t n_objects, MeshObject *meshes, size_t n_meshes, Camera *camera,
+               Options *options);
+
 /* Kernel-only wall time of the last render()/render_ex(), seconds, and the
  * count of scene casts (rays that ran the intersection scan). */
 double rt_last_render_seconds(void);

@@ -256,6 +256,47 @@ int32_t rt_hip_accum_samples(const RtHipAccum *accum); /* samples per pixel done
 const char *rt_hip_accum_kernel(const RtHipAccum *accum);
 void rt_hip_accum_destroy(RtHipAccum *accum);
 
+/* ---- first-hit feature buffers (AOVs): albedo, normal, depth, object id ---------------------------------------------------
+ * What a denoiser wants next to the noisy colour (albedo and normal of the first hit, averaged over the same camera samples), and
+ * what viewers and compositors want for picking and masks (depth, object id).  A launch uses params->width, height, seed and the
+ * tile_* fields; params->samples is S (>= 1); max_depth and integrator are ignored.  For each pixel (x, y) of the launch's tiles and
+ * each sample s = 0 .. S-1:
+ *   1. the camera ray of beauty sample s: the first two draws r0, r1 of the (seed, y*w + x, s) stream (rt_rng.h),
+ *      u = (x + r0) / (w - 1), v = (y + r1) / (h - 1), get_camera_ray -- so S = the frame's spp describes the frame's own samples;
+ *   2. the closest hit of intersect() (spheres first, then meshes in array order; strict <, the first index wins a tie): its t;
+ *      its OBJECT ID (sphere i: i; a mesh: n_spheres + its index -- rt_hip_scene_create's numbering); its UNIT NORMAL as
+ *      trace_path uses it (spheres vec3_normalize(point - centre), triangles calculate_surface_normal; never flipped toward the
+ *      viewer); its ALBEDO, the object's color -- on M_CHECKERED objects checkered_texture(color, hit.u, hit.v, 100000) with the
+ *      (u, v) trace_path textures with (on meshes: the last passing triangle's) -- not divided by the roulette probability;
+ *   3. a sample that hits nothing: albedo = BACKGROUND (10/255 per channel), normal = 0.
+ * Per pixel: albedo, normal = the fp64 vec3_add of the samples in ascending order from 0, times 1.0 / S (fp64), rounded to float;
+ * hits = how many samples hit; depth = the smallest t of those that hit, as float (+inf: none); object = the id of the sample that
+ * gave depth, the lowest s on equal t (0xFFFFFFFF: none).  All of it is fp64 arithmetic in a fixed order: the buffers equal a CPU
+ * evaluation of the reference's own code bit for bit.
+ *   - rt_hip_render_aov_tiles: asynchronous on `stream`.  d_tiles holds device pointers, each may be NULL but not all; the
+ *     buffers are compact tile-major as rt_hip_render_tiles': tile k of the launch owns albedo / normal [k*192, +192) floats and
+ *     depth / object / hits [k*64, +64) words; pixels of a tile outside the image read 0 (object 0xFFFFFFFF).  An AOV launch
+ *     takes no pending-ray pool, parked-walk workspace, chunk workspace or status word: it has nothing to run out of.
+ *   - rt_hip_untile_aov scatters such buffers (those non-NULL in both structs) into row-major images (w*h*3 / w*h words).
+ *   - rt_hip_render_aov_image: the whole image, synchronous, on one device -- logical device `device` of rt_hip_render_image's
+ *     device map (the HIP device itself without a map) -- into host arrays (h_image: row-major, each may be NULL, not all).
+ *   - rt_hip_aov_kernel_name names the form a scene's launches take; rt_hip_aov_kernel_count / _launches list the forms and how
+ *     many launches of each this process has made (the AOV kernels are not members of the family of rt_hip_kernel_count). */
+typedef struct
+{
+  float *albedo, *normal, *depth; /* 3, 3, 1 floats per pixel */
+  uint32_t *object, *hits;        /* 1 word per pixel */
+} RtHipAov;
+int rt_hip_render_aov_tiles(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *d_tiles,
+                            void *stream);
+int rt_hip_untile_aov(const RtHipAov *d_tiles, int32_t width, int32_t height, uint32_t tile_first, uint32_t tile_stride,
+                      uint32_t tile_count, const RtHipAov *d_image, void *stream);
+int rt_hip_render_aov_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                            const RtHipCamera *camera, const RtHipParams *params, int device, const RtHipAov *h_image);
+const char *rt_hip_aov_kernel_name(const RtHipScene *scene);
+int rt_hip_aov_kernel_count(void);
+const char *rt_hip_aov_kernel_launches(int index, uint64_t *launches);
+
 /* Scatter a compact tile buffer into row-major images (either output may be
  * NULL together with its input). */
 int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t width, int32_t height,

@@ -343,6 +343,14 @@ struct PtLaunch
   unsigned long long *stats;
 };
 
+/* The compact tile-major outputs of an AOV launch (rt_hip.h, RtHipAov; render_aov in pt_kernel.hip): tile slot k owns albedo / normal
+ * [k*192, +192) and depth / object / hits [k*64, +64).  Any pointer may be null (not all: the launcher refuses that). */
+struct PtAovOut
+{
+  float *albedo, *normal, *depth;
+  uint32_t *object, *hits;
+};
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 /* host-side launchers, defined next to the kernels in pt_kernel.hip */
@@ -408,6 +416,15 @@ hipError_t pt_launch_selftest(int op, const double *a, const double *b, double *
 hipError_t pt_launch_selftest_intersect(int kind, const double *rays, const double *prims, const double *entry_src,
                                         float *filt, float *tri32, uint32_t n, double near_R, double filt_shift,
                                         uint8_t *hit, double *tuv, unsigned long long *keep, hipStream_t stream);
+/* the AOV kernels (pt_kernel.hip: render_aov, PT_AOV_FAMILY): which form a scene takes, the launch (a tile per wave; the outputs: PtAovOut),
+ * names and launch counters; and the scatter of their compact 1- or 3-channel 32-bit buffers to row-major images */
+int pt_aov_pick(const PtSceneView &scene);
+hipError_t pt_launch_aov(const PtLaunch &launch, const PtAovOut &out, hipStream_t stream, int which);
+const char *pt_aov_kernel_name_of(int which);
+int pt_aov_kernel_count(void);
+unsigned long long pt_aov_kernel_launches(int which);
+hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int width, int height, uint32_t tile_first,
+                                uint32_t tile_stride, uint32_t tile_count, uint32_t *image, hipStream_t stream);
 hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,
                             uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *image_rgb,
                             uint8_t *image_rgb8, hipStream_t stream);

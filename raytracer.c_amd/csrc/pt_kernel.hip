@@ -62,9 +62,10 @@
  *   pt_body_pooled.h  render_tiles_pooled   (pt_render_tiles[_tri][_big][_chk], _pool_mem*, _refr_pool*)
  *   pt_body_queued.h  render_tiles_queued   (pt_render_tiles_tri_queued*: parked walks, also with M_REFRACTION)
  *   pt_body_static.h  render_tiles_static   (pt_render_tiles_v0, *_refr, pt_whitted_tiles*, *_mem)
- * This file keeps the kernel family (PT_FAMILY: the entry points, their ids and properties), the table-building and self-test
- * kernels, pt_untile, and the host side declared in pt_device.h: the launch plan (pt_plan_launch, around the pick table
- * pt_pick_kernel) and the launchers (pt_launch_render).
+ * This file keeps the kernel family (PT_FAMILY: the entry points, their ids and properties), the AOV kernels (render_aov,
+ * PT_AOV_FAMILY: first-hit feature buffers, not members of the family), the table-building and self-test kernels, pt_untile,
+ * and the host side declared in pt_device.h: the launch plan (pt_plan_launch, around the pick table pt_pick_kernel) and the
+ * launchers (pt_launch_render, pt_launch_aov).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -232,6 +233,182 @@ struct PtKernelInfo
 #define PT_INFO(id, name, bounds, props, ...) {#name, name, props},
 static const PtKernelInfo pt_kernels[K_COUNT] = {PT_FAMILY(PT_INFO) PT_FAMILY_DEV(PT_INFO)};
 #undef PT_INFO
+
+/* ---- AOV body: a workgroup = four tiles, a wave = one tile, a lane = one pixel ----------------------------------------------
+ * A lane runs the pixel's samples s = 0 .. samples - 1 in ascending order.  Per sample: the camera ray of beauty sample s
+ * (start_sample: the first two draws of the (seed, pixel, s) stream, get_camera_ray), then ONE intersect() -- scan_filtered,
+ * the exact-test path of the beauty kernels with the same filter, pre-tests, hierarchy and TriLast rule, so the first hit is
+ * theirs by construction -- and from the winner what trace_path's first call forms: the unit normal (never flipped), the
+ * object's colour as given (not divided by the roulette probability) or its checkered_texture, and t.  A miss counts as
+ * BACKGROUND albedo and a zero normal.  The sums are fp64 vec3_add in sample order from zero, scaled by 1.0 / samples and
+ * rounded to float32 (render(), raytracer.c:199-215): the lane holds its pixel's sums alone, so there is no cross-lane
+ * reduction and the order is the contract's.  No path state, no pool, no ring, no status word: nothing can run out.
+ * CHECKER: the scene has M_CHECKERED materials (u, v tracked); TRIS: triangles (flat scan with FILT_LDS, else the hierarchy);
+ * FILT_LDS: the filter table is staged (pt_filter_in_lds); GEOM_LDS: sphere geometry + materials are staged (pt_geom_in_lds). */
+template <bool CHECKER, bool TRIS, bool FILT_LDS, bool GEOM_LDS>
+__device__ __forceinline__ void render_aov(const PtLaunch &L, const PtAovOut &O)
+{
+  static_assert(GEOM_LDS || !FILT_LDS, "a staged filter table comes with staged geometry");
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  SceneCtx S_init = stage_scene<GEOM_LDS, FILT_LDS>(L, lds);
+  __shared__ double atan_tab[CHECKER ? PT_ATAN_TAB : 1];
+  if (CHECKER)
+  {
+    atan_table_to_lds(atan_tab);
+    S_init.atan_tab = atan_tab;
+  }
+  const SceneCtx S = S_init;
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t slot = blockIdx.x * (PT_BLOCK / 64u) + wave;
+  if (slot >= L.tile_count)
+    return; /* the last workgroup's spare waves (no barrier follows) */
+  const uint32_t tile = L.tile_first + slot * L.tile_stride;
+  const uint32_t px = (tile % L.tiles_x) * PT_TILE + (lane & 7u);
+  const uint32_t py = (tile / L.tiles_x) * PT_TILE + (lane >> 3);
+  const bool inside = px < (uint32_t)L.width && py < (uint32_t)L.height;
+  const uint32_t pixel = py * (uint32_t)L.width + px;
+  const uint64_t pixel_key = rt_rng_pixel_key(L.seed, pixel);
+  const CameraRegs cam = load_camera(L);
+  constexpr bool BVH = TRIS && !FILT_LDS;
+  constexpr bool LAST = CHECKER && TRIS;
+
+  V3 alb_sum = {0, 0, 0}, nrm_sum = {0, 0, 0};
+  double t_min = __longlong_as_double(0x7FF0000000000000ll); /* +inf: no sample hit yet */
+  uint32_t object = 0xFFFFFFFFu, hits = 0u;
+  const uint32_t spp = inside ? (uint32_t)L.samples : 0u;
+  for (uint32_t s = 0; s < spp; s++)
+  {
+    Path P;
+    start_sample(P, cam, pixel_key, px, py, sample_term(s));
+    const V3 o = P.o, d = P.d;
+    double min_t = S.t_start, bary_u = 0, bary_v = 0;
+    int best = -1;
+    TriLast last = {-1, 0, 0};
+    /* trace_step's intersect() call, argument for argument (VARIANT 1, MODE 0) */
+    scan_filtered<TRIS, BVH, FILT_LDS, true, LAST>(
+        S.geom, S.tri, FILT_LDS ? S.filt_lds : S.filt, S.near_R2, S.n_sph, S.n_sph + S.n_tri, o, d, min_t, best, bary_u, bary_v,
+        nullptr, S.bvh_nodes, S.n_bvh_nodes, S.bvh_tri, S.filt_shift, &last, S.stale_uv, S.tri32, nullptr, S.big,
+        (TRIS && FILT_LDS && !LAST) ? &S.mesh_bound : nullptr);
+    V3 albedo = {S.bg, S.bg, S.bg}, n = {0, 0, 0};
+    if (best >= 0)
+    {
+      uint32_t id;
+      const bool is_tri = TRIS && (uint32_t)best >= S.n_sph;
+      if (!is_tri)
+      { /* the winner's normal as trace_step forms it (pt_trace.h: vec3_normalize(point - centre), point_at :257) */
+        const V3 p = v_add(o, v_scale(d, min_t));
+        const V3 pc = v_sub(p, ld3(S.geom + PT_GEOM_STRIDE * best));
+        n = v_scale(pc, rcp_unscaled(sqrt_unscaled(v_dot(pc, pc))));
+        id = (uint32_t)best;
+      }
+      else
+      {
+        const uint32_t ti = (uint32_t)best - S.n_sph;
+        n = ld3(S.tri_normal + 3 * (size_t)ti); /* calculate_surface_normal */
+        id = S.tri_object[ti] & ~(PT_HULL_PLUS | PT_HULL_MINUS);
+      }
+      albedo = ld3(S.color_raw + 3 * (size_t)id);
+      const uint32_t flags = (uint32_t)__double_as_longlong(S.mat[PT_MAT_STRIDE * id + 7]);
+      if (CHECKER && (flags & PT_FLAG_CHECKER))
+      {
+        /* restated from trace_step (pt_trace.h, the M_CHECKERED block): hit.u / hit.v as the scan leaves them -- the LAST
+         * passing triangle's if the ray passes any (TriLast), else the closest sphere's (:410-411) -- then checkered_texture
+         * :386-391 with M = 100000 (:508), here on the colour itself */
+        double tex_u, tex_v;
+        if (!(TRIS && last.idx >= 0))
+        {
+          tex_u = atan2_tab(n.x, n.z, S.atan_tab) / (2 * kPi) + 0.5;
+          tex_v = n.y * 0.5 + 0.5;
+        }
+        else
+        {
+          const double *tx = S.tri_tex + 6 * (size_t)((uint32_t)last.idx - S.n_sph);
+          const double lu = last.u, lv = last.v;
+          double w0 = 1 - lu - lv;
+          tex_u = (tx[0] * w0 + tx[2] * lu) + tx[4] * lv;
+          tex_v = (tx[1] * w0 + tx[3] * lu) + tx[5] * lv;
+        }
+        double on = (double)((frac1(tex_u * 100000.0) > 0.5) ^ (frac1(tex_v * 100000.0) < 0.5));
+        double c = 0.3 * (1 - on) + 0.7 * on;
+        albedo = v_scale(albedo, c);
+      }
+      hits++;
+      if (min_t < t_min) /* ascending s, strict <: the lowest sample wins a tie */
+      {
+        t_min = min_t;
+        object = id;
+      }
+    }
+    alb_sum = v_add(alb_sum, albedo);
+    nrm_sum = v_add(nrm_sum, n);
+  }
+
+  const double inv = 1.0 / (double)(uint32_t)L.samples;
+  const V3 alb = v_scale(alb_sum, inv), nrm = v_scale(nrm_sum, inv);
+  const size_t px3 = (size_t)slot * (PT_TILE_PIXELS * 3) + 3u * lane, px1 = (size_t)slot * PT_TILE_PIXELS + lane;
+  if (O.albedo)
+  {
+    O.albedo[px3 + 0] = inside ? (float)alb.x : 0.f;
+    O.albedo[px3 + 1] = inside ? (float)alb.y : 0.f;
+    O.albedo[px3 + 2] = inside ? (float)alb.z : 0.f;
+  }
+  if (O.normal)
+  {
+    O.normal[px3 + 0] = inside ? (float)nrm.x : 0.f;
+    O.normal[px3 + 1] = inside ? (float)nrm.y : 0.f;
+    O.normal[px3 + 2] = inside ? (float)nrm.z : 0.f;
+  }
+  if (O.depth)
+    O.depth[px1] = inside ? (float)t_min : 0.f;
+  if (O.object)
+    O.object[px1] = object;
+  if (O.hits)
+    O.hits[px1] = hits;
+}
+
+/* ---- the AOV kernels (rt_hip_render_aov_tiles): first-hit feature buffers, one list of their own ---------------------------
+ * Not members of PT_FAMILY: they trace no path, take no pool, ring, chunk workspace or status word, and no row of the pick table
+ * names them.  Which one a launch takes is decided by the scene alone (pt_aov_pick): the forms the scene classes need --
+ *   pt_aov_tiles[_chk]          spheres staged, filter staged (sign-test form)
+ *   pt_aov_tiles_tri[_chk]      + triangles through the flat filter and the fp32 pre-test
+ *   pt_aov_tiles_big[_chk]      spheres staged, filter by scalar loads (more than PT_FILT_LDS_MAX primitives, or a wide range)
+ *   pt_aov_tiles_tri_big[_chk]  + triangles through the hierarchy
+ *   pt_aov_tiles_mem[_chk]      geometry and materials from memory (pt_geom_in_lds false), triangles (if any) through the hierarchy
+ * _chk: the scene has M_CHECKERED materials (u, v tracked).  Body: render_aov<CHECKER, TRIS, FILT_LDS, GEOM_LDS>. */
+#define PT_AOV_FAMILY(X) \
+  X(A_TILES,           pt_aov_tiles,           render_aov<false, false, true, true>) \
+  X(A_TILES_CHK,       pt_aov_tiles_chk,       render_aov<true, false, true, true>) \
+  X(A_TRI,             pt_aov_tiles_tri,       render_aov<false, true, true, true>) \
+  X(A_TRI_CHK,         pt_aov_tiles_tri_chk,   render_aov<true, true, true, true>) \
+  X(A_BIG,             pt_aov_tiles_big,       render_aov<false, false, false, true>) \
+  X(A_BIG_CHK,         pt_aov_tiles_big_chk,   render_aov<true, false, false, true>) \
+  X(A_TRI_BIG,         pt_aov_tiles_tri_big,   render_aov<false, true, false, true>) \
+  X(A_TRI_BIG_CHK,     pt_aov_tiles_tri_big_chk, render_aov<true, true, false, true>) \
+  X(A_MEM,             pt_aov_tiles_mem,       render_aov<false, true, false, false>) \
+  X(A_MEM_CHK,         pt_aov_tiles_mem_chk,   render_aov<true, true, false, false>)
+
+#define PT_AOV_ENTRY(id, name, ...) \
+  extern "C" __global__ __launch_bounds__(PT_BLOCK) void name(const PtLaunch L, const PtAovOut O) { __VA_ARGS__(L, O); }
+PT_AOV_FAMILY(PT_AOV_ENTRY)
+#undef PT_AOV_ENTRY
+
+#define PT_AOV_ID(id, ...) id,
+enum PtAovKernelId
+{
+  PT_AOV_FAMILY(PT_AOV_ID) A_COUNT
+};
+#undef PT_AOV_ID
+typedef void (*PtAovKernelFn)(const PtLaunch, const PtAovOut);
+struct PtAovKernelInfo
+{
+  const char *name;
+  PtAovKernelFn fn;
+};
+#define PT_AOV_INFO(id, name, ...) {#name, name},
+static const PtAovKernelInfo pt_aov_kernels[A_COUNT] = {PT_AOV_FAMILY(PT_AOV_INFO)};
+#undef PT_AOV_INFO
 
 /* Second pass of a chunked render: per-tile fixed-point sums -> float3 + tonemapped bytes. */
 extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const PtLaunch L)
@@ -672,6 +849,26 @@ extern "C" __global__ __launch_bounds__(256) void pt_untile(const float *tiles_r
   }
 }
 
+/* The same for the AOV buffers: 1- or 3-channel 32-bit words (float or uint32 alike), one thread per (pixel-in-tile, tile, word) */
+extern "C" __global__ __launch_bounds__(256) void pt_untile_aov(const uint32_t *tiles, int width, int height, uint32_t tiles_x,
+                                                              uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count,
+                                                              uint32_t channels, uint32_t *image)
+{
+  const size_t total = (size_t)tile_count * PT_TILE_PIXELS * channels;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x)
+  {
+    const size_t px = idx / channels;
+    const uint32_t c = (uint32_t)(idx - px * channels);
+    const uint32_t k = (uint32_t)(px / PT_TILE_PIXELS), pit = (uint32_t)(px % PT_TILE_PIXELS);
+    const uint32_t tile = tile_first + k * tile_stride;
+    const uint32_t x = (tile % tiles_x) * PT_TILE + (pit & 7u);
+    const uint32_t y = (tile / tiles_x) * PT_TILE + (pit >> 3);
+    if (x >= (uint32_t)width || y >= (uint32_t)height)
+      continue;
+    image[((size_t)y * width + x) * channels + c] = tiles[idx];
+  }
+}
+
 /* ---- launch wrappers (host side), declared in pt_device.h ---------------------- */
 
 size_t pt_render_lds_bytes(const PtSceneView &sc)
@@ -1098,5 +1295,57 @@ hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, i
     blocks = 8192;
   hipLaunchKernelGGL(pt_untile, dim3(blocks), dim3(256), 0, stream, tiles_rgb, tiles_rgb8, width, height, tiles_x,
                      tile_first, tile_stride, tile_count, image_rgb, image_rgb8);
+  return hipGetLastError();
+}
+
+/* ---- the AOV kernels: which form a scene takes, and the launch ------------------------------------------------------------ */
+int pt_aov_pick(const PtSceneView &scene)
+{
+  const bool chk = scene.any_checker != 0u;
+  if (!pt_geom_in_lds(scene))
+    return chk ? A_MEM_CHK : A_MEM;
+  const bool tris = scene.n_triangles != 0u;
+  if (pt_filter_in_lds(scene))
+    return tris ? (chk ? A_TRI_CHK : A_TRI) : (chk ? A_TILES_CHK : A_TILES);
+  return tris ? (chk ? A_TRI_BIG_CHK : A_TRI_BIG) : (chk ? A_BIG_CHK : A_BIG);
+}
+
+const char *pt_aov_kernel_name_of(int which) { return which >= 0 && which < A_COUNT ? pt_aov_kernels[which].name : ""; }
+int pt_aov_kernel_count(void) { return A_COUNT; }
+
+static std::atomic<unsigned long long> pt_aov_launch_counts[A_COUNT];
+unsigned long long pt_aov_kernel_launches(int which) { return which >= 0 && which < A_COUNT ? pt_aov_launch_counts[which].load() : 0ull; }
+
+hipError_t pt_launch_aov(const PtLaunch &launch, const PtAovOut &out, hipStream_t stream, int which)
+{
+  if (which < 0 || which >= A_COUNT || launch.tile_count == 0u)
+    return hipErrorInvalidValue;
+  /* the staged scene as the beauty kernels stage it (nothing for the in-memory forms) */
+  const size_t lds_bytes = which == A_MEM || which == A_MEM_CHK ? 0 : pt_render_lds_bytes(launch.scene);
+  const PtAovKernelFn kernel = pt_aov_kernels[which].fn;
+  if (lds_bytes > 64 * 1024)
+  {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess)
+      return e;
+  }
+  const uint32_t waves = PT_BLOCK / 64u; /* a tile per wave */
+  hipLaunchKernelGGL(kernel, dim3((launch.tile_count + waves - 1u) / waves), dim3(PT_BLOCK), lds_bytes, stream, launch, out);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess)
+    pt_aov_launch_counts[which].fetch_add(1ull);
+  return e;
+}
+
+hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int width, int height, uint32_t tile_first,
+                                uint32_t tile_stride, uint32_t tile_count, uint32_t *image, hipStream_t stream)
+{
+  const uint32_t tiles_x = ((uint32_t)width + PT_TILE - 1) / PT_TILE;
+  const size_t total = (size_t)tile_count * PT_TILE_PIXELS * channels;
+  uint32_t blocks = (uint32_t)((total + 255) / 256);
+  if (blocks > 8192)
+    blocks = 8192;
+  hipLaunchKernelGGL(pt_untile_aov, dim3(blocks), dim3(256), 0, stream, tiles, width, height, tiles_x, tile_first, tile_stride,
+                     tile_count, channels, image);
   return hipGetLastError();
 }

@@ -1968,6 +1968,82 @@ int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t
   return RT_HIP_OK;
 }
 
+/* ---- first-hit feature buffers (rt_hip.h, RtHipAov) ----------------------------------------------------------------------
+ * The launch takes launch_prepare's camera-dependent fields and acquire_tables' filter, hierarchy and fp32 triangle table -- what
+ * the beauty kernels' intersect() reads -- and nothing else: not pt_plan_launch (the AOV forms are no rows of the pick table, the
+ * scene alone picks one: pt_aov_pick), nor launch_device_state (the body needs neither the status word nor the parked-walk
+ * workspace: it cannot fail on the device and walks the hierarchy per lane). */
+static bool aov_any(const RtHipAov *a) { return a && (a->albedo || a->normal || a->depth || a->object || a->hits); }
+
+const char *rt_hip_aov_kernel_name(const RtHipScene *scene) { return scene ? pt_aov_kernel_name_of(pt_aov_pick(scene->view)) : ""; }
+
+int rt_hip_aov_kernel_count(void) { return pt_aov_kernel_count(); }
+
+const char *rt_hip_aov_kernel_launches(int index, uint64_t *launches)
+{
+  if (index < 0 || index >= pt_aov_kernel_count())
+    return nullptr;
+  if (launches)
+    *launches = pt_aov_kernel_launches(index);
+  return pt_aov_kernel_name_of(index);
+}
+
+int rt_hip_render_aov_tiles(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *d_tiles,
+                            void *stream)
+{
+  if (!scene || !camera || !params)
+    return fail(RT_HIP_EINVAL, "scene, camera and params are required");
+  if (!aov_any(d_tiles))
+    return fail(RT_HIP_EINVAL, "d_tiles: at least one output buffer is required");
+  RtHipParams p = *params;
+  p.max_depth = 0; /* ignored: one intersect() per sample */
+  p.integrator = RT_HIP_TRACE_PATH;
+  PtLaunch L;
+  bool empty = false;
+  int rc = launch_prepare(scene, camera, &p, L, &empty);
+  if (rc || empty)
+    return rc;
+  const PtAovOut out = {d_tiles->albedo, d_tiles->normal, d_tiles->depth, d_tiles->object, d_tiles->hits};
+  const int which = pt_aov_pick(scene->view);
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  size_t slot = 0;
+  rc = acquire_tables(scene, L.near_R, static_cast<hipStream_t>(stream), &L.scene.filt, &L.scene.bvh_nodes, &slot);
+  if (rc)
+    return rc;
+  const hipError_t e = pt_launch_aov(L, out, static_cast<hipStream_t>(stream), which);
+  release_tables(scene, slot, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_aov_kernel_name_of(which), hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int rt_hip_untile_aov(const RtHipAov *d_tiles, int32_t width, int32_t height, uint32_t tile_first, uint32_t tile_stride,
+                      uint32_t tile_count, const RtHipAov *d_image, void *stream)
+{
+  if (!d_tiles || !d_image || width < 1 || height < 1)
+    return fail(RT_HIP_EINVAL, "tile and image buffers and the image size are required");
+  if (tile_count == 0)
+    return RT_HIP_OK;
+  if (tile_stride == 0 && tile_count > 1)
+    return fail(RT_HIP_EINVAL, "tile_stride must be >= 1");
+  const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
+  if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
+    return fail(RT_HIP_EINVAL, "tile range exceeds the image");
+  const void *src[5] = {d_tiles->albedo, d_tiles->normal, d_tiles->depth, d_tiles->object, d_tiles->hits};
+  void *dst[5] = {d_image->albedo, d_image->normal, d_image->depth, d_image->object, d_image->hits};
+  for (int k = 0; k < 5; k++)
+  {
+    if (!src[k] || !dst[k])
+      continue;
+    const hipError_t e = pt_launch_untile_aov(static_cast<const uint32_t *>(src[k]), k < 2 ? 3u : 1u, width, height, tile_first,
+                                              tile_stride, tile_count, static_cast<uint32_t *>(dst[k]), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "pt_untile_aov launch: %s", hipGetErrorString(e));
+  }
+  return RT_HIP_OK;
+}
+
 /* Whole image on n_devices GPUs of this process.  Device g renders tiles
  * g, g+G, g+2G, ... into its own compact buffer; the buffers are gathered on
  * device 0 with grouped ncclSend/ncclRecv (point-to-point over xGMI: a gather
@@ -2542,3 +2618,106 @@ uint64_t cache_builds_impl()
 }
 
 } // namespace
+
+namespace
+{
+/* rt_hip_render_aov_image: a scene of its own on the device, compact buffers for the requested outputs, one launch over every
+ * tile, the scatter, the copies.  Synchronous on the null stream. */
+int render_aov_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                          const RtHipCamera *camera, const RtHipParams *params, int device, const RtHipAov *h_image)
+{
+  if (!camera || !params)
+    return fail(RT_HIP_EINVAL, "camera and params are required");
+  if (!aov_any(h_image))
+    return fail(RT_HIP_EINVAL, "h_image: at least one output array is required");
+  int rc = check_params(params);
+  if (rc)
+    return rc;
+  const int have = usable_devices();
+  if (have < 1)
+    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
+  int phys = device;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    device_map_from_env();
+    if (!g_device_map.empty())
+    {
+      if (device < 0 || device >= (int)g_device_map.size())
+        return fail(RT_HIP_ENODEV, "logical device %d: the device map has %d entries", device, (int)g_device_map.size());
+      phys = g_device_map[device];
+    }
+  }
+  if (phys < 0 || phys >= have)
+    return fail(RT_HIP_ENODEV, "no HIP device %d", phys);
+  RtHipScene *scene = nullptr;
+  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &scene);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  if (scope.status != hipSuccess)
+  {
+    rt_hip_scene_destroy(scene);
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", phys, hipGetErrorString(scope.status));
+  }
+  RtHipParams p = *params;
+  p.tile_first = 0;
+  p.tile_stride = 1;
+  p.tile_count = tiles_x_of(p.width) * tiles_y_of(p.height);
+  const size_t tile_px = (size_t)p.tile_count * PT_TILE_PIXELS, img_px = (size_t)p.width * p.height;
+  /* one allocation: per requested output its tile buffer and its image, words of 4 bytes */
+  void *host[5] = {h_image->albedo, h_image->normal, h_image->depth, h_image->object, h_image->hits};
+  size_t off[5] = {0, 0, 0, 0, 0}, words = 0;
+  for (int k = 0; k < 5; k++)
+    if (host[k])
+    {
+      off[k] = words;
+      words += (k < 2 ? 3u : 1u) * (tile_px + img_px);
+    }
+  uint32_t *buf = nullptr;
+  hipError_t e = hipMalloc(&buf, words * 4u);
+  RtHipAov tiles = {}, image = {};
+  void **tp[5] = {(void **)&tiles.albedo, (void **)&tiles.normal, (void **)&tiles.depth, (void **)&tiles.object, (void **)&tiles.hits};
+  void **ip[5] = {(void **)&image.albedo, (void **)&image.normal, (void **)&image.depth, (void **)&image.object, (void **)&image.hits};
+  if (e == hipSuccess)
+    for (int k = 0; k < 5; k++)
+      if (host[k])
+      {
+        *tp[k] = buf + off[k];
+        *ip[k] = buf + off[k] + (k < 2 ? 3u : 1u) * tile_px;
+      }
+  if (e == hipSuccess)
+  {
+    rc = rt_hip_render_aov_tiles(scene, camera, &p, &tiles, nullptr);
+    if (!rc)
+      rc = rt_hip_untile_aov(&tiles, p.width, p.height, 0, 1, p.tile_count, &image, nullptr);
+    for (int k = 0; !rc && e == hipSuccess && k < 5; k++)
+      if (host[k])
+        e = hipMemcpy(host[k], *ip[k], (k < 2 ? 3u : 1u) * img_px * 4u, hipMemcpyDeviceToHost);
+  }
+  if (buf)
+    (void)hipFree(buf);
+  rt_hip_scene_destroy(scene);
+  if (rc)
+    return rc;
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? RT_HIP_ENOMEM : RT_HIP_ERUNTIME, "AOV image: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+} // namespace
+
+extern "C" int rt_hip_render_aov_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                                       const RtHipCamera *camera, const RtHipParams *params, int device, const RtHipAov *h_image)
+{
+  try
+  {
+    return render_aov_image_impl(spheres, n_spheres, meshes, n_meshes, camera, params, device, h_image);
+  }
+  catch (const std::bad_alloc &)
+  {
+    return fail(RT_HIP_ENOMEM, "host allocation failed in rt_hip_render_aov_image");
+  }
+  catch (...)
+  {
+    return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in rt_hip_render_aov_image");
+  }
+}

@@ -13,6 +13,9 @@
  *                raytracer.c:207-211
  *   -p <samples> progressive: add the samples in passes of this many (render_progressive, one GPU), a
  *                line per pass; the PNG is the one-shot image bit for bit
+ *   -a <prefix>  after the frame, its first-hit feature buffers (render_aov: the frame's own camera samples, same -s
+ *                and seed, one GPU): <prefix>_albedo.pfm and <prefix>_normal.pfm (PF, 3 channels), <prefix>_depth.pfm
+ *                (Pf) -- little-endian, rows stored bottom to top as PFM has them, so they show the PNG's picture
  * Timing is wall-clock (the reference's clock()/integer division, main.c:427-433,
  * reports summed CPU time truncated to seconds -- deliberately not reproduced).
  * SIGINT: the reference's handler writes and frees the live framebuffer from
@@ -45,6 +48,39 @@ static void on_pass(int done, int total, double kernel_seconds, void *user)
   fflush(stdout);
 }
 
+/* -a: one PFM file, little-endian (scale -1.0), rows bottom to top; `rows` is row-major with row 0 at the top (as the PNG) */
+static int write_pfm(const char *prefix, const char *name, const float *rows, int w, int h, int channels)
+{
+  char path[4096];
+  if (snprintf(path, sizeof path, "%s_%s.pfm", prefix, name) >= (int)sizeof path)
+    return -1;
+  FILE *f = fopen(path, "wb");
+  if (!f)
+    return -1;
+  int ok = fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", w, h) > 0;
+  const size_t row_vals = (size_t)w * channels;
+  uint8_t *buf = (uint8_t *)malloc(row_vals * 4);
+  ok = ok && buf;
+  for (int y = h - 1; ok && y >= 0; y--)
+  {
+    for (size_t k = 0; k < row_vals; k++)
+    {
+      uint32_t u;
+      memcpy(&u, &rows[(size_t)y * row_vals + k], 4);
+      buf[4 * k + 0] = (uint8_t)u;
+      buf[4 * k + 1] = (uint8_t)(u >> 8);
+      buf[4 * k + 2] = (uint8_t)(u >> 16);
+      buf[4 * k + 3] = (uint8_t)(u >> 24);
+    }
+    ok = fwrite(buf, 4, row_vals, f) == row_vals;
+  }
+  free(buf);
+  ok = (fclose(f) == 0) && ok;
+  if (ok)
+    printf("wrote '%s'\n", path);
+  return ok ? 0 : -1;
+}
+
 static double now_seconds(void)
 {
   struct timespec ts;
@@ -57,6 +93,7 @@ typedef struct
   Options options;
   int depth, config, gpus, integrator;
   int pass; /* -p: samples per pass; 0: not given (one-shot) */
+  const char *aov; /* -a: prefix of the feature-buffer files; NULL: none */
   uint64_t seed;
 } Args;
 
@@ -65,7 +102,8 @@ static void usage(const char *prog)
   fprintf(stderr,
           "Usage: %s -w <width> -h <height> -s <samples per pixel> -o <filename>\n"
           "          [-d <max depth>] [-c <scene config 1..5>] [-g <gpus>] [-r <seed>]\n"
-          "          [-i <integrator: 0 trace_path, 1 cast_ray>] [-p <samples per pass, one GPU>]\n",
+          "          [-i <integrator: 0 trace_path, 1 cast_ray>] [-p <samples per pass, one GPU>]\n"
+          "          [-a <prefix of the albedo / normal / depth .pfm files>]\n",
           prog);
 }
 
@@ -87,6 +125,7 @@ static int parse_args(int argc, char **argv, Args *a)
     case 'g': a->gpus = atoi(val); break;
     case 'r': a->seed = strtoull(val, NULL, 10); break;
     case 'i': a->integrator = atoi(val); break;
+    case 'a': a->aov = val; break;
     case 'p':
       a->pass = atoi(val);
       if (a->pass < 1)
@@ -192,6 +231,25 @@ int main(int argc, char **argv)
   else
     printf("done.\n");
 #endif
+  if (a.aov && status == EXIT_SUCCESS)
+  { /* the frame's own samples: as many as the image holds, the same seed */
+    const size_t n_px = (size_t)a.options.width * (size_t)a.options.height;
+    float *albedo = (float *)malloc(n_px * 3 * sizeof(float)), *normal = (float *)malloc(n_px * 3 * sizeof(float));
+    float *depth = (float *)malloc(n_px * sizeof(float));
+    RtAovImage aov = {albedo, normal, depth, NULL, NULL};
+    Options o = a.options;
+    o.samples = held;
+    if (!albedo || !normal || !depth || render_aov(&aov, scene, info.n_objects, meshes, info.n_meshes, &camera, &o) < 0 ||
+        write_pfm(a.aov, "albedo", albedo, o.width, o.height, 3) || write_pfm(a.aov, "normal", normal, o.width, o.height, 3) ||
+        write_pfm(a.aov, "depth", depth, o.width, o.height, 1))
+    {
+      fprintf(stderr, "could not write the feature buffers (-a %s)\n", a.aov);
+      status = EXIT_FAILURE;
+    }
+    free(albedo);
+    free(normal);
+    free(depth);
+  }
   printf("phases: HIP runtime start %.6f s, context %.6f s, render %.6f s, copy out %.6f s, PNG %.6f s\n", t_hip - t_start, phase[0],
          phase[1], phase[2], now_seconds() - toc);
   rt_scene_free_meshes(meshes, info.n_meshes);

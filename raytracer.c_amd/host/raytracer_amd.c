@@ -333,3 +333,24 @@ int render_progressive(uint8_t *framebuffer, float *linear_rgb, Object *objects,
   g_last_bounces = (long long)stats[RT_HIP_STAT_CASTS];
   return done;
 }
+
+int render_aov(RtAovImage *out, Object *objects, size_t n_objects, MeshObject *meshes, size_t n_meshes, Camera *camera,
+               Options *options)
+{
+  if (!out || !camera || !options)
+  {
+    fprintf(stderr, "render_aov: out, camera and options are required\n");
+    return RT_HIP_EINVAL;
+  }
+  RtHipMesh *hm = hip_meshes(meshes, n_meshes);
+  RtHipParams p = image_params(options);
+  const RtHipAov h = {out->albedo, out->normal, out->depth, out->object_id, out->hits};
+  const int rc = rt_hip_render_aov_image((const RtHipSphere *)objects, n_objects, hm, n_meshes, (const RtHipCamera *)camera, &p, 0, &h);
+  free(hm);
+  if (rc)
+  {
+    fprintf(stderr, "render_aov: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+    return rc;
+  }
+  return p.samples;
+}

@@ -77,6 +77,20 @@ class RtHipParams(C.Structure):
                 ("tile_count", C.c_uint32), ("integrator", C.c_uint32)]
 
 
+class RtHipAov(C.Structure):  # rt_hip.h: device (tiles) or host (image) pointers of the first-hit feature buffers; NULL: not wanted
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("object", C.c_void_p), ("hits", C.c_void_p)]
+
+
+class RtAovImage(C.Structure):  # include/raytracer.h: render_aov's row-major host arrays
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("object_id", C.c_void_p),
+                ("hits", C.c_void_p)]
+
+
+AOV_FIELDS = ("albedo", "normal", "depth", "object", "hits")   # RtHipAov order
+AOV_CHANNELS = {"albedo": 3, "normal": 3, "depth": 1, "object": 1, "hits": 1}
+ENODEV = -1                                                     # RT_HIP_ENODEV
+
+
 TRACE_PATH, CAST_RAY = 0, 1  # RtHipParams.integrator / rt_set_integrator()
 INTEGRATORS = {"path": TRACE_PATH, "whitted": CAST_RAY}
 
@@ -134,6 +148,14 @@ SHIM_SYMBOLS = {
     "rt_hip_launch_status": (C.c_int, [C.c_int, C.POINTER(C.c_uint32)]),
     "rt_hip_selftest_fail_alloc": (None, [C.c_uint32]),
     "rt_hip_selftest_pool_slots": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rt_hip_render_aov_tiles": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipParams), C.POINTER(RtHipAov), C.c_void_p]),
+    "rt_hip_untile_aov": (C.c_int, [C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                    C.POINTER(RtHipAov), C.c_void_p]),
+    "rt_hip_render_aov_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.POINTER(Camera),
+                                          C.POINTER(RtHipParams), C.c_int, C.POINTER(RtHipAov)]),
+    "rt_hip_aov_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "rt_hip_aov_kernel_count": (C.c_int, []),
+    "rt_hip_aov_kernel_launches": (C.c_char_p, [C.c_int, C.POINTER(C.c_uint64)]),
     "rt_hip_render_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t,
                                       C.POINTER(Camera), C.POINTER(RtHipParams), C.c_int, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
@@ -165,6 +187,8 @@ HOST_SYMBOLS = {
     "rt_set_cancel_flag": (None, [C.c_void_p]),
     "render_progressive": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
                                      C.POINTER(Camera), C.POINTER(Options), C.c_int, C.c_void_p, C.c_void_p]),
+    "render_aov": (C.c_int, [C.POINTER(RtAovImage), C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
+                             C.POINTER(Camera), C.POINTER(Options)]),
     "rt_last_render_cancelled": (C.c_int, []),
     "rt_last_render_seconds": (C.c_double, []),
     "rt_last_ray_bounces": (C.c_longlong, []),

@@ -143,6 +143,54 @@ class GpuScene:
                "rt_hip_untile")
         return image, image8
 
+    def aov_kernel_name(self):
+        """the AOV form this scene's render_aov launches take"""
+        return self.shim.rt_hip_aov_kernel_name(self.handle).decode()
+
+    def render_aov(self, seed, samples, first=0, stride=1, count=None, camera=None, want=abi.AOV_FIELDS):
+        """First-hit feature buffers of `samples` camera samples per pixel (rt_hip.h, rt_hip_render_aov_tiles) over tiles
+        first + k * stride, k < count (default: the whole image), asynchronous on torch's current stream -> dict of compact
+        tile-major tensors: albedo / normal f32 [count,64,3], depth f32 [count,64], object / hits int32 [count,64] (the uint32
+        words of the C-ABI, bit for bit: .view(torch.uint32) or numpy's .view(np.uint32) reads them as such).  want: which."""
+        if count is None:
+            count = n_tiles(self.scene.width, self.scene.height)
+        dev = torch.device("cuda", self.device)
+        out, aov = {}, abi.RtHipAov()
+        for f in want:
+            shape = (max(count, 1), abi.TILE_PIXELS) + ((3,) if abi.AOV_CHANNELS[f] == 3 else ())
+            out[f] = torch.empty(shape, dtype=torch.float32 if f in ("albedo", "normal", "depth") else torch.int32, device=dev)
+            setattr(aov, f, out[f].data_ptr())
+        p = self.params(seed, first, stride, count, samples)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.shim.rt_hip_render_aov_tiles(self.handle, C.byref(camera if camera is not None else self.scene.camera),
+                                                 C.byref(p), C.byref(aov), C.c_void_p(stream)), "rt_hip_render_aov_tiles")
+        return out
+
+    def untile_aov(self, tiles, first, stride, count):
+        """Scatter render_aov's compact buffers into row-major tensors ([H,W,3] / [H,W], zeros where no tile of the set lies)
+        on torch's current stream"""
+        w, h = self.scene.width, self.scene.height
+        src, dst, out = abi.RtHipAov(), abi.RtHipAov(), {}
+        for f, t in tiles.items():
+            out[f] = torch.zeros((h, w) + ((3,) if abi.AOV_CHANNELS[f] == 3 else ()), dtype=t.dtype, device=t.device)
+            setattr(src, f, t.data_ptr())
+            setattr(dst, f, out[f].data_ptr())
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        _check(self.shim.rt_hip_untile_aov(C.byref(src), w, h, first, stride, count, C.byref(dst), C.c_void_p(stream)),
+               "rt_hip_untile_aov")
+        return out
+
+    def aov_image(self, seed, samples):
+        """The whole image's feature buffers on this GPU, synchronised -> dict of row-major numpy arrays: albedo / normal
+        float32 [H,W,3], depth float32 [H,W], object / hits uint32 [H,W]"""
+        total = n_tiles(self.scene.width, self.scene.height)
+        img = self.untile_aov(self.render_aov(seed, samples, 0, 1, total), 0, 1, total)
+        torch.cuda.synchronize(torch.device("cuda", self.device))
+        out = {f: t.cpu().numpy() for f, t in img.items()}
+        for f in ("object", "hits"):
+            out[f] = out[f].view("uint32")
+        return out
+
     def render_image(self, seed, samples=None, max_depth=None, integrator="path"):
         """Whole image on this one GPU -> (image f32 [H,W,3], image8 u8 [H,W,3], stats dict), synchronised."""
         total = n_tiles(self.scene.width, self.scene.height)
@@ -225,3 +273,21 @@ def render_image_host(scene, seed, n_devices=1, samples=None, max_depth=None, in
                                     C.byref(p), n_devices, img.ctypes.data, img8.ctypes.data, stats, C.byref(secs)),
            "rt_hip_render_image")
     return img, img8, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3]), secs.value
+
+
+def aov_image_host(scene, seed, samples, device=0):
+    """rt_hip_render_aov_image(): the C hosts' entry point (its own scene on logical device `device`, synchronous) -> dict of
+    row-major numpy arrays as GpuScene.aov_image"""
+    import numpy as np
+    shim = abi.load_shim()
+    p = abi.RtHipParams()
+    p.width, p.height, p.samples, p.seed = scene.width, scene.height, samples, seed
+    h, w = scene.height, scene.width
+    out, aov = {}, abi.RtHipAov()
+    for f in abi.AOV_FIELDS:
+        out[f] = np.zeros((h, w, 3) if abi.AOV_CHANNELS[f] == 3 else (h, w), dtype=np.float32 if f in ("albedo", "normal", "depth") else np.uint32)
+        setattr(aov, f, out[f].ctypes.data)
+    meshes = scene.hip_meshes()
+    _check(shim.rt_hip_render_aov_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera), C.byref(p),
+                                        device, C.byref(aov)), "rt_hip_render_aov_image")
+    return out
