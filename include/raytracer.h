@@ -35,6 +35,7 @@
 #include <time.h>
 
 #include "vector.h"
+#include "rt_hip.h" /* RtHipDenoiseParams (denoise_frame) */
 
 #ifdef __cplusplus
 extern "C" {
@@ -272,6 +273,15 @@ typedef struct
 } RtAovImage;
 int render_aov(RtAovImage *out, Object *objects, size_t n_objects, MeshObject *meshes, size_t n_meshes, Camera *camera,
                Options *options);
+
+/* Edge-avoiding a-trous denoise of a frame (include/rt_hip.h, rt_hip_denoise: the contract in full) guided by the first-hit
+ * buffers of its own samples: linear_in is the frame's linear mean (render_ex's linear_rgb, width x height x 3 floats), aov its
+ * render_aov buffers (normal, depth and hits always; albedo with RT_HIP_DENOISE_DEMODULATE, object_id with _OBJECT_EDGES).
+ * Writes the denoised linear image to linear_out and its tonemapped bytes to framebuffer (either may be NULL, not both; linear_out
+ * may be linear_in).  params NULL: rt_hip_denoise_defaults.  Runs on one device, the first of the device map.  Returns 0, or a
+ * negative RT_HIP_E* code with the reason on stderr. */
+int denoise_frame(uint8_t *framebuffer, float *linear_out, const float *linear_in, const RtAovImage *aov, int width, int height,
+                  const RtHipDenoiseParams *params);
 
 /* Kernel-only wall time of the last render()/render_ex(), seconds, and the
  * count of scene casts (rays that ran the intersection scan). */

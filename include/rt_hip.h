@@ -297,6 +297,54 @@ const char *rt_hip_aov_kernel_name(const RtHipScene *scene);
 int rt_hip_aov_kernel_count(void);
 const char *rt_hip_aov_kernel_launches(int index, uint64_t *launches);
 
+/* ---- edge-avoiding a-trous denoiser guided by the first-hit buffers ---------------------------------------------------------
+ * Inputs: row-major images of w x h pixels (1 <= w, h <= 2^20, w*h < 2^32) on one device -- colour c (3 floats per pixel: the
+ * linear mean of rt_hip_render_tiles or rt_hip_accum_resolve after rt_hip_untile) and the RtHipAov buffers of the same frame
+ * after rt_hip_untile_aov: albedo a (needed with DEMODULATE only), normal n, depth z, hits h, object o (with OBJECT_EDGES only).
+ * All arithmetic is fp64 +, -, *, / in the order written; values read from float buffers are widened exactly; every stored
+ * intermediate is rounded to float32 (RNE).  eps = 2^-10, h5 = [1/16, 1/4, 3/8, 1/4, 1/16] (index dx + 2).
+ *   1. A pixel is INVALID if any channel of c is not finite: its output is its input colour, and no pixel uses it as a neighbour.
+ *   2. e0 = float(c / (a + eps)) per channel with DEMODULATE, else e0 = c.
+ *   3. For i = 0 .. L-1: step s = 2^i, sigma_i = sigma_color * 2^-i, S2 = sigma_i * sigma_i.  For each valid p, W = A = 0 (fp64);
+ *      taps q = p + s*(dx, dy), dy = -2..2 (outer), dx = -2..2 (inner).  A tap outside the image or invalid is SKIPPED (not added:
+ *      adding +0.0 would turn a -0.0 sum positive).  The centre tap has w = 9/64 and no edge terms.  Any other tap:
+ *        - OBJECT_EDGES: skip q if o_q != o_p;
+ *        - h_p == h_q == 0 (both background): wn = Zn = Zd = 1; exactly one of h_p, h_q is 0: skip q;
+ *        - otherwise g = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z, g = (g > 0) ? g : 0, wn = g squared k times;
+ *          D = (sigma_depth * z_p) * (s * max(|dx|, |dy|)), Zn = D*D, dz = z_q - z_p, Zd = Zn + dz*dz; if Zd == 0: Zn = Zd = 1;
+ *        - dc = ((de.x*de.x + de.y*de.y) + de.z*de.z) with de = e_q - e_p;
+ *        - w = (((h5[dx]*h5[dy]) * wn) * (S2 * Zn)) / ((S2 + dc) * Zd);  W += w, then A += w * e_q per channel.
+ *      e_{i+1}(p) = float(A / W) per channel (W >= 9/64).
+ *   4. out = float(e_L * (a + eps)) with DEMODULATE, else e_L; invalid pixels pass c through.  out8 = the render epilogue's
+ *      tonemap of the widened float.  L = 0 is allowed (without DEMODULATE it is the identity).
+ * The contract is total: any buffer contents (NaN normals, a finite depth with 0 hits, ...) have a defined result.
+ *   - rt_hip_denoise_defaults: L = 5, sigma_color = 0.5, k = 3, sigma_depth = 1.0, DEMODULATE.
+ *   - rt_hip_denoise_workspace_bytes: the d_workspace rt_hip_denoise needs for w x h (0 for a size out of range).
+ *   - rt_hip_denoise: asynchronous on `stream`, on the device that holds d_rgb.  d_aov: device image pointers (the ones the flags
+ *     need); either output may be NULL, not both; d_out_rgb == d_rgb is allowed (in place).  Arguments are checked before the
+ *     device is looked for: RT_HIP_EINVAL, then RT_HIP_ENODEV.
+ *   - rt_hip_denoise_image: the same from host arrays, synchronous, with its own device buffers, on logical device `device` of
+ *     rt_hip_render_image's device map (the HIP device itself without a map). */
+typedef struct
+{
+  int32_t iterations;         /* L, 0 .. 10 */
+  uint32_t flags;             /* RT_HIP_DENOISE_* */
+  uint32_t normal_power_log2; /* k, 0 .. 10: the normal weight is max(0, n_p.n_q)^(2^k) */
+  double sigma_color;        /* > 0, finite */
+  double sigma_depth;         /* > 0, finite */
+} RtHipDenoiseParams;
+enum
+{
+  RT_HIP_DENOISE_DEMODULATE = 1u,   /* filter c / (albedo + eps), multiply the albedo back after */
+  RT_HIP_DENOISE_OBJECT_EDGES = 2u, /* never mix pixels of different object ids */
+};
+void rt_hip_denoise_defaults(RtHipDenoiseParams *params);
+size_t rt_hip_denoise_workspace_bytes(int32_t width, int32_t height);
+int rt_hip_denoise(const float *d_rgb, const RtHipAov *d_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
+                   void *d_workspace, float *d_out_rgb, uint8_t *d_out_rgb8, void *stream);
+int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
+                         int device, float *h_out_rgb, uint8_t *h_out_rgb8);
+
 /* Scatter a compact tile buffer into row-major images (either output may be
  * NULL together with its input). */
 int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t width, int32_t height,

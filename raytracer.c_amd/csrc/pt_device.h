@@ -351,6 +351,22 @@ struct PtAovOut
   uint32_t *object, *hits;
 };
 
+/* One launch of the denoiser (rt_hip.h, rt_hip_denoise; pt_denoise_* in pt_kernel.hip).  The workspace holds, per pixel of the
+ * row-major w x h image: two ping-pong float4 colour buffers e[0], e[1] (the filtered signal, .w = 1 valid / 0 invalid), the
+ * guidance float4 (normal, depth) and uint2 (hits, object) the prepare pass packs so that a tap is three loads. */
+struct PtDenoise
+{
+  const float *rgb, *albedo, *normal, *depth; /* inputs: albedo only with DEMODULATE */
+  const uint32_t *hits, *object;              /* object only with OBJECT_EDGES */
+  float *e[2], *guide;                        /* workspace: 4 floats per pixel each */
+  uint32_t *hit_obj;                          /* workspace: 2 words per pixel */
+  float *out_rgb;                             /* each may be null, not both */
+  uint8_t *out_rgb8;
+  int32_t width, height;
+  uint32_t demodulate, object_edges, k; /* rt_hip.h: RT_HIP_DENOISE_DEMODULATE, _OBJECT_EDGES (0 / 1), normal_power_log2 */
+  double sigma_z;
+};
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 /* host-side launchers, defined next to the kernels in pt_kernel.hip */
@@ -425,6 +441,8 @@ int pt_aov_kernel_count(void);
 unsigned long long pt_aov_kernel_launches(int which);
 hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int width, int height, uint32_t tile_first,
                                 uint32_t tile_stride, uint32_t tile_count, uint32_t *image, hipStream_t stream);
+/* the denoiser: the prepare pass and `iterations` filter passes (the last one remodulates and tonemaps) on `stream` */
+hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma_color, hipStream_t stream);
 hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,
                             uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *image_rgb,
                             uint8_t *image_rgb8, hipStream_t stream);

@@ -869,6 +869,164 @@ extern "C" __global__ __launch_bounds__(256) void pt_untile_aov(const uint32_t *
   }
 }
 
+/* ---- the denoiser (rt_hip_denoise): edge-avoiding a-trous wavelet filter guided by the first-hit buffers --------------------
+ * rt_hip.h states the arithmetic; this is it, operation for operation, in fp64 (-ffp-contract=off: no fused multiply-add).  A lane
+ * is a pixel.  pt_denoise_prepare demodulates and packs the guidance (normal + depth: one 16-B load, hits + object: one 8-B load)
+ * and the validity flag (e.w); each pt_denoise_filter launch is one iteration, ping-ponging e[0] / e[1]; the _final forms of both
+ * remodulate and tonemap instead of storing the signal (L = 0: prepare_final alone).  The tap loop is unrolled and the same for
+ * every lane of a wave: out-of-image taps load a clamped pixel and every skip is a predicate on the accumulation, not a branch. */
+__device__ __forceinline__ void denoise_store(const PtDenoise &D, size_t p, float ox, float oy, float oz)
+{
+  if (D.out_rgb)
+  {
+    D.out_rgb[3 * p + 0] = ox;
+    D.out_rgb[3 * p + 1] = oy;
+    D.out_rgb[3 * p + 2] = oz;
+  }
+  if (D.out_rgb8)
+  {
+    D.out_rgb8[3 * p + 0] = tonemap((double)ox);
+    D.out_rgb8[3 * p + 1] = tonemap((double)oy);
+    D.out_rgb8[3 * p + 2] = tonemap((double)oz);
+  }
+}
+
+/* step 4: out = float(e * (a + eps)) (DEMODULATE) or e; an invalid pixel passes its input colour through */
+__device__ __forceinline__ void denoise_finish(const PtDenoise &D, size_t p, bool valid, float ex, float ey, float ez)
+{
+  constexpr double eps = 1.0 / 1024.0;
+  if (!valid)
+    denoise_store(D, p, D.rgb[3 * p + 0], D.rgb[3 * p + 1], D.rgb[3 * p + 2]);
+  else if (D.demodulate)
+    denoise_store(D, p, (float)((double)ex * ((double)D.albedo[3 * p + 0] + eps)), (float)((double)ey * ((double)D.albedo[3 * p + 1] + eps)),
+                  (float)((double)ez * ((double)D.albedo[3 * p + 2] + eps)));
+  else
+    denoise_store(D, p, ex, ey, ez);
+}
+
+template <bool FINAL>
+__device__ __forceinline__ void denoise_prepare(const PtDenoise &D)
+{
+  constexpr double eps = 1.0 / 1024.0;
+  const size_t n = (size_t)D.width * (size_t)D.height;
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n)
+    return;
+  const float cx = D.rgb[3 * p + 0], cy = D.rgb[3 * p + 1], cz = D.rgb[3 * p + 2];
+  const bool valid = isfinite(cx) && isfinite(cy) && isfinite(cz);
+  float ex = cx, ey = cy, ez = cz;
+  if (D.demodulate)
+  {
+    ex = (float)((double)cx / ((double)D.albedo[3 * p + 0] + eps));
+    ey = (float)((double)cy / ((double)D.albedo[3 * p + 1] + eps));
+    ez = (float)((double)cz / ((double)D.albedo[3 * p + 2] + eps));
+  }
+  if (FINAL)
+  {
+    denoise_finish(D, p, valid, ex, ey, ez);
+    return;
+  }
+  reinterpret_cast<float4 *>(D.e[0])[p] = make_float4(ex, ey, ez, valid ? 1.f : 0.f);
+  reinterpret_cast<float4 *>(D.guide)[p] = make_float4(D.normal[3 * p + 0], D.normal[3 * p + 1], D.normal[3 * p + 2], D.depth[p]);
+  reinterpret_cast<uint2 *>(D.hit_obj)[p] = make_uint2(D.hits[p], D.object_edges ? D.object[p] : 0u);
+}
+
+/* one iteration: e[src] -> e[src ^ 1] at step s (a workgroup = a 16 x 16 block of pixels, a wave = 16 x 4) */
+template <bool FINAL>
+__device__ __forceinline__ void denoise_filter(const PtDenoise &D, uint32_t src, int32_t step, double S2)
+{
+  const uint32_t bx = ((uint32_t)D.width + 15u) / 16u;
+  const int32_t x = (int32_t)((blockIdx.x % bx) * 16u + (threadIdx.x & 15u));
+  const int32_t y = (int32_t)((blockIdx.x / bx) * 16u + (threadIdx.x >> 4));
+  if (x >= D.width || y >= D.height)
+    return; /* no barrier follows */
+  const size_t p = (size_t)y * (size_t)D.width + (size_t)x;
+  const float4 *ein = reinterpret_cast<const float4 *>(D.e[src]);
+  const float4 *guide = reinterpret_cast<const float4 *>(D.guide);
+  const uint2 *hit_obj = reinterpret_cast<const uint2 *>(D.hit_obj);
+  const float4 ep = ein[p];
+  if (ep.w == 0.f)
+  { /* invalid: never filtered, never a neighbour */
+    if (FINAL)
+      denoise_finish(D, p, false, 0.f, 0.f, 0.f);
+    else
+      reinterpret_cast<float4 *>(D.e[src ^ 1u])[p] = ep;
+    return;
+  }
+  const float4 gp = guide[p];
+  const uint2 hop = hit_obj[p];
+  const bool edges = D.object_edges != 0u;
+  const double epx = ep.x, epy = ep.y, epz = ep.z;
+  const double npx = gp.x, npy = gp.y, npz = gp.z, zp = gp.w;
+  const double Dp = D.sigma_z * zp;
+  constexpr double h5[5] = {1.0 / 16, 1.0 / 4, 3.0 / 8, 1.0 / 4, 1.0 / 16};
+  double W = 0, Ax = 0, Ay = 0, Az = 0;
+  /* a row of five taps at a time: unrolling all 25 would hoist every tap's loads (240 VGPRs, one wave per SIMD) */
+#pragma unroll 1
+  for (int dy = -2; dy <= 2; dy++)
+  {
+    const int ady = dy < 0 ? -dy : dy;
+    const double hy = ady == 0 ? h5[2] : ady == 1 ? h5[1] : h5[0];
+#pragma unroll
+    for (int dx = -2; dx <= 2; dx++)
+    {
+      if (dx == 0 && dy == 0)
+      { /* the centre: 9/64, no edge terms */
+        const double w = 9.0 / 64.0;
+        W += w;
+        Ax += w * epx;
+        Ay += w * epy;
+        Az += w * epz;
+        continue;
+      }
+      const int64_t qx = (int64_t)x + (int64_t)step * dx, qy = (int64_t)y + (int64_t)step * dy;
+      const bool inside = qx >= 0 && qx < D.width && qy >= 0 && qy < D.height;
+      const size_t q = (size_t)(inside ? qy : y) * (size_t)D.width + (size_t)(inside ? qx : x);
+      const float4 eq = ein[q], gq = guide[q];
+      const uint2 hoq = hit_obj[q];
+      const bool bg_p = hop.x == 0u, bg_q = hoq.x == 0u;
+      const bool take = inside && eq.w != 0.f && (!edges || hoq.y == hop.y) && bg_p == bg_q;
+      double g = (npx * (double)gq.x + npy * (double)gq.y) + npz * (double)gq.z;
+      g = (g > 0) ? g : 0.0;
+      double wn = g;
+      for (uint32_t i = 0; i < D.k; i++)
+        wn = wn * wn;
+      const int adx = dx < 0 ? -dx : dx, m = adx > ady ? adx : ady;
+      const double Dd = Dp * (double)(step * m);
+      double Zn = Dd * Dd;
+      const double dz = (double)gq.w - zp;
+      double Zd = Zn + dz * dz;
+      if (Zd == 0)
+        Zn = Zd = 1.0;
+      if (bg_p && bg_q)
+        wn = Zn = Zd = 1.0;
+      const double dex = (double)eq.x - epx, dey = (double)eq.y - epy, dez = (double)eq.z - epz;
+      const double dc = (dex * dex + dey * dey) + dez * dez;
+      const double w = (((h5[dx + 2] * hy) * wn) * (S2 * Zn)) / ((S2 + dc) * Zd);
+      W = take ? W + w : W;
+      Ax = take ? Ax + w * (double)eq.x : Ax;
+      Ay = take ? Ay + w * (double)eq.y : Ay;
+      Az = take ? Az + w * (double)eq.z : Az;
+    }
+  }
+  const float ox = (float)(Ax / W), oy = (float)(Ay / W), oz = (float)(Az / W);
+  if (FINAL)
+    denoise_finish(D, p, true, ox, oy, oz);
+  else
+    reinterpret_cast<float4 *>(D.e[src ^ 1u])[p] = make_float4(ox, oy, oz, 1.f);
+}
+
+extern "C" __global__ __launch_bounds__(256) void pt_denoise_prepare(const PtDenoise D) { denoise_prepare<false>(D); }
+extern "C" __global__ __launch_bounds__(256) void pt_denoise_prepare_final(const PtDenoise D) { denoise_prepare<true>(D); }
+extern "C" __global__ __launch_bounds__(256) void pt_denoise_filter(const PtDenoise D, uint32_t src, int32_t step, double S2)
+{
+  denoise_filter<false>(D, src, step, S2);
+}
+extern "C" __global__ __launch_bounds__(256) void pt_denoise_filter_final(const PtDenoise D, uint32_t src, int32_t step, double S2)
+{
+  denoise_filter<true>(D, src, step, S2);
+}
+
 /* ---- launch wrappers (host side), declared in pt_device.h ---------------------- */
 
 size_t pt_render_lds_bytes(const PtSceneView &sc)
@@ -1348,4 +1506,30 @@ hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int wi
   hipLaunchKernelGGL(pt_untile_aov, dim3(blocks), dim3(256), 0, stream, tiles, width, height, tiles_x, tile_first, tile_stride,
                      tile_count, channels, image);
   return hipGetLastError();
+}
+
+/* ---- the denoiser's launches (rt_hip_denoise) ------------------------------------------------------------------------------ */
+hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma_color, hipStream_t stream)
+{
+  const size_t n = (size_t)args.width * (size_t)args.height;
+  const uint32_t blocks_1d = (uint32_t)((n + 255u) / 256u);
+  const uint32_t blocks_2d = (((uint32_t)args.width + 15u) / 16u) * (((uint32_t)args.height + 15u) / 16u);
+  if (iterations == 0)
+  {
+    hipLaunchKernelGGL(pt_denoise_prepare_final, dim3(blocks_1d), dim3(256), 0, stream, args);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(pt_denoise_prepare, dim3(blocks_1d), dim3(256), 0, stream, args);
+  hipError_t e = hipGetLastError();
+  double sigma = sigma_color;
+  for (int i = 0; i < iterations && e == hipSuccess; i++, sigma *= 0.5)
+  {
+    const double S2 = sigma * sigma;
+    if (i + 1 == iterations)
+      hipLaunchKernelGGL(pt_denoise_filter_final, dim3(blocks_2d), dim3(256), 0, stream, args, (uint32_t)(i & 1), (int32_t)1 << i, S2);
+    else
+      hipLaunchKernelGGL(pt_denoise_filter, dim3(blocks_2d), dim3(256), 0, stream, args, (uint32_t)(i & 1), (int32_t)1 << i, S2);
+    e = hipGetLastError();
+  }
+  return e;
 }

@@ -19,6 +19,7 @@
 #include <limits>
 #include <mutex>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "pt_device.h"
@@ -2621,6 +2622,28 @@ uint64_t cache_builds_impl()
 
 namespace
 {
+/* logical device `device` of the device map (the HIP device itself without a map) -> the HIP device, or RT_HIP_ENODEV */
+int physical_device(int device, int *phys)
+{
+  const int have = usable_devices();
+  if (have < 1)
+    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
+  *phys = device;
+  {
+    std::lock_guard<std::mutex> lock(g_ctx_mutex);
+    device_map_from_env();
+    if (!g_device_map.empty())
+    {
+      if (device < 0 || device >= (int)g_device_map.size())
+        return fail(RT_HIP_ENODEV, "logical device %d: the device map has %d entries", device, (int)g_device_map.size());
+      *phys = g_device_map[device];
+    }
+  }
+  if (*phys < 0 || *phys >= have)
+    return fail(RT_HIP_ENODEV, "no HIP device %d", *phys);
+  return RT_HIP_OK;
+}
+
 /* rt_hip_render_aov_image: a scene of its own on the device, compact buffers for the requested outputs, one launch over every
  * tile, the scatter, the copies.  Synchronous on the null stream. */
 int render_aov_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
@@ -2633,22 +2656,10 @@ int render_aov_image_impl(const RtHipSphere *spheres, size_t n_spheres, const Rt
   int rc = check_params(params);
   if (rc)
     return rc;
-  const int have = usable_devices();
-  if (have < 1)
-    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
-  int phys = device;
-  {
-    std::lock_guard<std::mutex> lock(g_ctx_mutex);
-    device_map_from_env();
-    if (!g_device_map.empty())
-    {
-      if (device < 0 || device >= (int)g_device_map.size())
-        return fail(RT_HIP_ENODEV, "logical device %d: the device map has %d entries", device, (int)g_device_map.size());
-      phys = g_device_map[device];
-    }
-  }
-  if (phys < 0 || phys >= have)
-    return fail(RT_HIP_ENODEV, "no HIP device %d", phys);
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
   RtHipScene *scene = nullptr;
   rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &scene);
   if (rc)
@@ -2721,3 +2732,199 @@ extern "C" int rt_hip_render_aov_image(const RtHipSphere *spheres, size_t n_sphe
     return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in rt_hip_render_aov_image");
   }
 }
+
+namespace
+{
+/* ---- the denoiser (rt_hip.h, rt_hip_denoise_*) ------------------------------------------------------------------------------
+ * Workspace layout for n = w*h pixels, each part 256-B aligned: e[0], e[1] and the guidance (16 B per pixel each), then hits +
+ * object (8 B per pixel).  The kernels and their arithmetic are pt_denoise_* in pt_kernel.hip. */
+size_t align256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+
+bool denoise_size_ok(int32_t width, int32_t height)
+{
+  return width >= 1 && height >= 1 && width <= (1 << 20) && height <= (1 << 20) && (uint64_t)width * (uint64_t)height <= 0xFFFFFFFFull;
+}
+
+size_t denoise_ws_bytes(size_t n) { return 3u * align256(16u * n) + align256(8u * n); }
+
+int check_denoise(const float *rgb, const RtHipAov *aov, int32_t width, int32_t height, const RtHipDenoiseParams *p, const void *out_rgb,
+                  const void *out_rgb8)
+{
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is NULL");
+  if (!denoise_size_ok(width, height))
+    return fail(RT_HIP_EINVAL, "width and height must be in [1, 2^20] with fewer than 2^32 pixels");
+  if (p->iterations < 0 || p->iterations > 10)
+    return fail(RT_HIP_EINVAL, "iterations must be in [0, 10]");
+  if (p->normal_power_log2 > 10)
+    return fail(RT_HIP_EINVAL, "normal_power_log2 must be in [0, 10]");
+  if (p->flags & ~(uint32_t)(RT_HIP_DENOISE_DEMODULATE | RT_HIP_DENOISE_OBJECT_EDGES))
+    return fail(RT_HIP_EINVAL, "unknown denoise flags 0x%x", p->flags);
+  if (!(std::isfinite(p->sigma_color) && p->sigma_color > 0) || !(std::isfinite(p->sigma_depth) && p->sigma_depth > 0))
+    return fail(RT_HIP_EINVAL, "sigma_color and sigma_depth must be finite and > 0");
+  if (!rgb)
+    return fail(RT_HIP_EINVAL, "the colour image is required");
+  if (!aov || !aov->normal || !aov->depth || !aov->hits)
+    return fail(RT_HIP_EINVAL, "the normal, depth and hits buffers are required");
+  if ((p->flags & RT_HIP_DENOISE_DEMODULATE) && !aov->albedo)
+    return fail(RT_HIP_EINVAL, "RT_HIP_DENOISE_DEMODULATE needs the albedo buffer");
+  if ((p->flags & RT_HIP_DENOISE_OBJECT_EDGES) && !aov->object)
+    return fail(RT_HIP_EINVAL, "RT_HIP_DENOISE_OBJECT_EDGES needs the object buffer");
+  if (!out_rgb && !out_rgb8)
+    return fail(RT_HIP_EINVAL, "at least one output is required");
+  return RT_HIP_OK;
+}
+
+/* the launches of a checked call, on the current device */
+int denoise_launch(const float *rgb, const RtHipAov *aov, int32_t width, int32_t height, const RtHipDenoiseParams *p, void *ws,
+                   float *out_rgb, uint8_t *out_rgb8, hipStream_t stream)
+{
+  const size_t n = (size_t)width * (size_t)height, part = align256(16u * n);
+  char *w = static_cast<char *>(ws);
+  PtDenoise D = {};
+  D.rgb = rgb;
+  D.albedo = aov->albedo;
+  D.normal = aov->normal;
+  D.depth = aov->depth;
+  D.hits = aov->hits;
+  D.object = aov->object;
+  D.e[0] = reinterpret_cast<float *>(w);
+  D.e[1] = reinterpret_cast<float *>(w + part);
+  D.guide = reinterpret_cast<float *>(w + 2u * part);
+  D.hit_obj = reinterpret_cast<uint32_t *>(w + 3u * part);
+  D.out_rgb = out_rgb;
+  D.out_rgb8 = out_rgb8;
+  D.width = width;
+  D.height = height;
+  D.demodulate = (p->flags & RT_HIP_DENOISE_DEMODULATE) ? 1u : 0u;
+  D.object_edges = (p->flags & RT_HIP_DENOISE_OBJECT_EDGES) ? 1u : 0u;
+  D.k = p->normal_power_log2;
+  D.sigma_z = p->sigma_depth;
+  const hipError_t e = pt_launch_denoise(D, p->iterations, p->sigma_color, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "pt_denoise launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int denoise_image_impl(const float *h_rgb, const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
+                       int device, float *h_out, uint8_t *h_out8)
+{
+  int rc = check_denoise(h_rgb, h_aov, width, height, params, h_out, h_out8);
+  if (rc)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", phys, hipGetErrorString(scope.status));
+  const size_t n = (size_t)width * (size_t)height;
+  const bool demod = (params->flags & RT_HIP_DENOISE_DEMODULATE) != 0, edges = (params->flags & RT_HIP_DENOISE_OBJECT_EDGES) != 0;
+  /* one allocation: the workspace, then colour (in and out: in place), albedo, normal, depth, hits, object, bytes */
+  const size_t ws = denoise_ws_bytes(n), b3 = align256(12u * n), b1 = align256(4u * n);
+  const size_t total = ws + b3 * (demod ? 3u : 2u) + b1 * (edges ? 3u : 2u) + align256(3u * n);
+  char *buf = nullptr;
+  hipError_t e = hipMalloc(&buf, total);
+  if (e == hipSuccess)
+  {
+    char *at = buf + ws;
+    float *rgb = reinterpret_cast<float *>(at);
+    at += b3;
+    RtHipAov d = {};
+    if (demod)
+    {
+      d.albedo = reinterpret_cast<float *>(at);
+      at += b3;
+    }
+    d.normal = reinterpret_cast<float *>(at);
+    at += b3;
+    d.depth = reinterpret_cast<float *>(at);
+    at += b1;
+    d.hits = reinterpret_cast<uint32_t *>(at);
+    at += b1;
+    if (edges)
+    {
+      d.object = reinterpret_cast<uint32_t *>(at);
+      at += b1;
+    }
+    uint8_t *rgb8 = reinterpret_cast<uint8_t *>(at);
+    const std::pair<void *, const void *> in[6] = {{rgb, h_rgb}, {d.albedo, h_aov->albedo}, {d.normal, h_aov->normal},
+                                                   {d.depth, h_aov->depth}, {d.hits, h_aov->hits}, {d.object, h_aov->object}};
+    const size_t bytes[6] = {12u * n, 12u * n, 12u * n, 4u * n, 4u * n, 4u * n};
+    for (int k = 0; k < 6 && e == hipSuccess; k++)
+      if (in[k].first)
+        e = hipMemcpy(in[k].first, in[k].second, bytes[k], hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+      rc = denoise_launch(rgb, &d, width, height, params, buf, h_out ? rgb : nullptr, h_out8 ? rgb8 : nullptr, nullptr);
+    if (e == hipSuccess && !rc && h_out)
+      e = hipMemcpy(h_out, rgb, 12u * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !rc && h_out8)
+      e = hipMemcpy(h_out8, rgb8, 3u * n, hipMemcpyDeviceToHost);
+  }
+  if (buf)
+    (void)hipFree(buf);
+  if (rc)
+    return rc;
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? RT_HIP_ENOMEM : RT_HIP_ERUNTIME, "denoise image: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+} // namespace
+
+extern "C" {
+
+void rt_hip_denoise_defaults(RtHipDenoiseParams *params)
+{
+  if (!params)
+    return;
+  *params = RtHipDenoiseParams{};
+  params->iterations = 5;
+  params->flags = RT_HIP_DENOISE_DEMODULATE;
+  params->normal_power_log2 = 3;
+  params->sigma_color = 0.5;
+  params->sigma_depth = 1.0;
+}
+
+size_t rt_hip_denoise_workspace_bytes(int32_t width, int32_t height)
+{
+  return denoise_size_ok(width, height) ? denoise_ws_bytes((size_t)width * (size_t)height) : 0u;
+}
+
+int rt_hip_denoise(const float *d_rgb, const RtHipAov *d_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
+                   void *d_workspace, float *d_out_rgb, uint8_t *d_out_rgb8, void *stream)
+{
+  int rc = check_denoise(d_rgb, d_aov, width, height, params, d_out_rgb, d_out_rgb8);
+  if (rc)
+    return rc;
+  if (!d_workspace)
+    return fail(RT_HIP_EINVAL, "d_workspace is required (rt_hip_denoise_workspace_bytes)");
+  if (usable_devices() < 1)
+    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
+  /* the device that holds the colour: a host pointer here would fault the kernel, so it is refused */
+  hipPointerAttribute_t attr = {};
+  if (hipPointerGetAttributes(&attr, d_rgb) != hipSuccess || attr.type != hipMemoryTypeDevice)
+  {
+    (void)hipGetLastError();
+    return fail(RT_HIP_EINVAL, "d_rgb is not device memory");
+  }
+  DeviceScope scope(attr.device);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  return denoise_launch(d_rgb, d_aov, width, height, params, d_workspace, d_out_rgb, d_out_rgb8, static_cast<hipStream_t>(stream));
+}
+
+int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
+                         int device, float *h_out_rgb, uint8_t *h_out_rgb8)
+{
+  try
+  {
+    return denoise_image_impl(h_rgb, h_aov, width, height, params, device, h_out_rgb, h_out_rgb8);
+  }
+  catch (...)
+  {
+    return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in rt_hip_denoise_image");
+  }
+}
+
+} // extern "C"

@@ -16,6 +16,9 @@
  *   -a <prefix>  after the frame, its first-hit feature buffers (render_aov: the frame's own camera samples, same -s
  *                and seed, one GPU): <prefix>_albedo.pfm and <prefix>_normal.pfm (PF, 3 channels), <prefix>_depth.pfm
  *                (Pf) -- little-endian, rows stored bottom to top as PFM has them, so they show the PNG's picture
+ *   -n <iters>   denoise (denoise_frame, rt_hip_denoise's defaults with this many iterations, 0..10, one GPU): after the
+ *                frame, the first-hit buffers of its own samples (as -a; with -p the samples done), then the denoised PNG to
+ *                -o and the frame as rendered to <name>.noisy.png (-o's name without .png)
  * Timing is wall-clock (the reference's clock()/integer division, main.c:427-433,
  * reports summed CPU time truncated to seconds -- deliberately not reproduced).
  * SIGINT: the reference's handler writes and frees the live framebuffer from
@@ -94,6 +97,7 @@ typedef struct
   int depth, config, gpus, integrator;
   int pass; /* -p: samples per pass; 0: not given (one-shot) */
   const char *aov; /* -a: prefix of the feature-buffer files; NULL: none */
+  int denoise;     /* -n: iterations + 1; 0: not given */
   uint64_t seed;
 } Args;
 
@@ -103,7 +107,8 @@ static void usage(const char *prog)
           "Usage: %s -w <width> -h <height> -s <samples per pixel> -o <filename>\n"
           "          [-d <max depth>] [-c <scene config 1..5>] [-g <gpus>] [-r <seed>]\n"
           "          [-i <integrator: 0 trace_path, 1 cast_ray>] [-p <samples per pass, one GPU>]\n"
-          "          [-a <prefix of the albedo / normal / depth .pfm files>]\n",
+          "          [-a <prefix of the albedo / normal / depth .pfm files>]\n"
+          "          [-n <denoise iterations 0..10: -o denoised, <name>.noisy.png as rendered>]\n",
           prog);
 }
 
@@ -126,6 +131,11 @@ static int parse_args(int argc, char **argv, Args *a)
     case 'r': a->seed = strtoull(val, NULL, 10); break;
     case 'i': a->integrator = atoi(val); break;
     case 'a': a->aov = val; break;
+    case 'n':
+      a->denoise = atoi(val) + 1;
+      if (a->denoise < 1 || a->denoise > 11 || val[0] < '0' || val[0] > '9')
+        return -1;
+      break;
     case 'p':
       a->pass = atoi(val);
       if (a->pass < 1)
@@ -195,17 +205,34 @@ int main(int argc, char **argv)
   (void)rt_hip_device_count();
   const double t_hip = now_seconds();
 
+  /* -n: the frame's linear mean is the denoiser's input; the PNG of the frame as rendered goes to <name>.noisy.png */
+  const size_t n_px = (size_t)a.options.width * (size_t)a.options.height;
+  float *linear = a.denoise ? (float *)malloc(n_px * 3 * sizeof(float)) : NULL;
+  char noisy_path[4096];
+  const char *frame_path = a.options.result;
+  if (a.denoise)
+  {
+    const size_t len = strlen(a.options.result);
+    const size_t stem = len >= 4 && strcmp(a.options.result + len - 4, ".png") == 0 ? len - 4 : len;
+    if (!linear || snprintf(noisy_path, sizeof noisy_path, "%.*s.noisy.png", (int)stem, a.options.result) >= (int)sizeof noisy_path)
+    {
+      fprintf(stderr, "could not allocate the linear frame or name the noisy PNG (-n)\n");
+      return EXIT_FAILURE;
+    }
+    frame_path = noisy_path;
+  }
+
   double tic = now_seconds();
   int held = a.options.samples;
   if (a.pass > 0)
   {
-    held = render_progressive(framebuffer, NULL, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options, a.pass,
+    held = render_progressive(framebuffer, linear, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options, a.pass,
                               on_pass, NULL);
     if (held < 0)
       return EXIT_FAILURE; /* render_progressive said why */
   }
   else
-    render_ex(framebuffer, NULL, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options);
+    render_ex(framebuffer, linear, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options);
   double toc = now_seconds();
   double phase[3] = {0, 0, 0};
   rt_hip_last_image_phases(phase);
@@ -224,16 +251,15 @@ int main(int argc, char **argv)
     printf("interrupted: the image holds %d of %d samples per pixel\n", held, a.options.samples);
   else if (rt_last_render_cancelled())
     printf("interrupted: the image holds the tiles finished so far\n");
-  printf("writing result to '%s'...\n", a.options.result);
+  printf("writing result to '%s'...\n", frame_path);
 #ifndef VALGRIND
-  if (stbi_write_png(a.options.result, a.options.width, a.options.height, 3, framebuffer, a.options.width * 3) == 0)
+  if (stbi_write_png(frame_path, a.options.width, a.options.height, 3, framebuffer, a.options.width * 3) == 0)
     status = EXIT_FAILURE;
   else
     printf("done.\n");
 #endif
   if (a.aov && status == EXIT_SUCCESS)
   { /* the frame's own samples: as many as the image holds, the same seed */
-    const size_t n_px = (size_t)a.options.width * (size_t)a.options.height;
     float *albedo = (float *)malloc(n_px * 3 * sizeof(float)), *normal = (float *)malloc(n_px * 3 * sizeof(float));
     float *depth = (float *)malloc(n_px * sizeof(float));
     RtAovImage aov = {albedo, normal, depth, NULL, NULL};
@@ -250,11 +276,50 @@ int main(int argc, char **argv)
     free(normal);
     free(depth);
   }
+  if (a.denoise && status == EXIT_SUCCESS)
+  {
+    if (held < 1 || (rt_last_render_cancelled() && a.pass == 0))
+    { /* a one-shot frame cut short holds finished tiles only: nothing to denoise */
+      fprintf(stderr, "not denoised: the frame is incomplete\n");
+      status = EXIT_FAILURE;
+    }
+    else
+    {
+      float *albedo = (float *)malloc(n_px * 3 * sizeof(float)), *normal = (float *)malloc(n_px * 3 * sizeof(float));
+      float *depth = (float *)malloc(n_px * sizeof(float));
+      uint32_t *hits = (uint32_t *)malloc(n_px * sizeof(uint32_t));
+      RtAovImage aov = {albedo, normal, depth, NULL, hits};
+      Options o = a.options;
+      o.samples = held;
+      RtHipDenoiseParams dp;
+      rt_hip_denoise_defaults(&dp);
+      dp.iterations = a.denoise - 1;
+      const double t0 = now_seconds();
+      if (!albedo || !normal || !depth || !hits || render_aov(&aov, scene, info.n_objects, meshes, info.n_meshes, &camera, &o) < 0 ||
+          denoise_frame(framebuffer, NULL, linear, &aov, o.width, o.height, &dp) != 0)
+      {
+        fprintf(stderr, "could not denoise the frame (-n %d)\n", a.denoise - 1);
+        status = EXIT_FAILURE;
+      }
+      else
+      {
+        printf("denoised (%d iterations, first-hit buffers of %d samples) in %f s; writing '%s'...\n", dp.iterations, held,
+               now_seconds() - t0, a.options.result);
+        if (stbi_write_png(a.options.result, o.width, o.height, 3, framebuffer, o.width * 3) == 0)
+          status = EXIT_FAILURE;
+      }
+      free(albedo);
+      free(normal);
+      free(depth);
+      free(hits);
+    }
+  }
   printf("phases: HIP runtime start %.6f s, context %.6f s, render %.6f s, copy out %.6f s, PNG %.6f s\n", t_hip - t_start, phase[0],
          phase[1], phase[2], now_seconds() - toc);
   rt_scene_free_meshes(meshes, info.n_meshes);
   free(meshes);
   free(scene);
   free(framebuffer);
+  free(linear);
   return status;
 }

@@ -354,3 +354,20 @@ int render_aov(RtAovImage *out, Object *objects, size_t n_objects, MeshObject *m
   }
   return p.samples;
 }
+
+int denoise_frame(uint8_t *framebuffer, float *linear_out, const float *linear_in, const RtAovImage *aov, int width, int height,
+                  const RtHipDenoiseParams *params)
+{
+  RtHipDenoiseParams defaults;
+  rt_hip_denoise_defaults(&defaults);
+  if (!aov)
+  {
+    fprintf(stderr, "denoise_frame: the feature buffers are required\n");
+    return RT_HIP_EINVAL;
+  }
+  const RtHipAov h = {aov->albedo, aov->normal, aov->depth, aov->object_id, aov->hits};
+  const int rc = rt_hip_denoise_image(linear_in, &h, width, height, params ? params : &defaults, 0, linear_out, framebuffer);
+  if (rc)
+    fprintf(stderr, "denoise_frame: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+  return rc;
+}

@@ -86,6 +86,13 @@ class RtAovImage(C.Structure):  # include/raytracer.h: render_aov's row-major ho
                 ("hits", C.c_void_p)]
 
 
+class RtHipDenoiseParams(C.Structure):  # rt_hip.h: the denoiser's parameters (rt_hip_denoise_defaults)
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("normal_power_log2", C.c_uint32),
+                ("sigma_color", C.c_double), ("sigma_depth", C.c_double)]
+
+
+DENOISE_DEMODULATE, DENOISE_OBJECT_EDGES = 1, 2   # RT_HIP_DENOISE_*
+
 AOV_FIELDS = ("albedo", "normal", "depth", "object", "hits")   # RtHipAov order
 AOV_CHANNELS = {"albedo": 3, "normal": 3, "depth": 1, "object": 1, "hits": 1}
 ENODEV = -1                                                     # RT_HIP_ENODEV
@@ -156,6 +163,12 @@ SHIM_SYMBOLS = {
     "rt_hip_aov_kernel_name": (C.c_char_p, [C.c_void_p]),
     "rt_hip_aov_kernel_count": (C.c_int, []),
     "rt_hip_aov_kernel_launches": (C.c_char_p, [C.c_int, C.POINTER(C.c_uint64)]),
+    "rt_hip_denoise_defaults": (None, [C.POINTER(RtHipDenoiseParams)]),
+    "rt_hip_denoise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rt_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_denoise_image": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_int,
+                                       C.c_void_p, C.c_void_p]),
     "rt_hip_render_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t,
                                       C.POINTER(Camera), C.POINTER(RtHipParams), C.c_int, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
@@ -189,6 +202,8 @@ HOST_SYMBOLS = {
                                      C.POINTER(Camera), C.POINTER(Options), C.c_int, C.c_void_p, C.c_void_p]),
     "render_aov": (C.c_int, [C.POINTER(RtAovImage), C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
                              C.POINTER(Camera), C.POINTER(Options)]),
+    "denoise_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.c_int, C.c_int,
+                                C.POINTER(RtHipDenoiseParams)]),
     "rt_last_render_cancelled": (C.c_int, []),
     "rt_last_render_seconds": (C.c_double, []),
     "rt_last_ray_bounces": (C.c_longlong, []),
@@ -239,3 +254,18 @@ def load_host():
             raise RuntimeError(f"{HOST_PATH} is missing: build it with `make host`")
         _host = _bind(C.CDLL(HOST_PATH), HOST_SYMBOLS)
     return _host
+
+
+def denoise_params(iterations=None, sigma_color=None, sigma_depth=None, normal_power_log2=None, demodulate=None,
+                   object_edges=None):
+    """rt_hip_denoise_defaults() with the given fields replaced (None: the default)"""
+    p = RtHipDenoiseParams()
+    load_shim().rt_hip_denoise_defaults(C.byref(p))
+    for f, v in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_depth", sigma_depth),
+                 ("normal_power_log2", normal_power_log2)):
+        if v is not None:
+            setattr(p, f, v)
+    for bit, v in ((DENOISE_DEMODULATE, demodulate), (DENOISE_OBJECT_EDGES, object_edges)):
+        if v is not None:
+            p.flags = (p.flags | bit) if v else (p.flags & ~bit)
+    return p

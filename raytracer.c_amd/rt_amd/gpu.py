@@ -126,7 +126,7 @@ class GpuScene:
         _check(self.shim.rt_hip_accum_create(self.handle, C.byref(camera if camera is not None else self.scene.camera),
                                              C.byref(p), C.byref(handle)), "rt_hip_accum_create")
         self._accums = [h for h in self._accums if h] + [handle]
-        return Accumulation(self, handle, count)
+        return Accumulation(self, handle, count, seed, first, stride, camera)
 
     def untile(self, tiles, tiles8, first, stride, count, image=None, image8=None):
         """Scatter a compact tile buffer into row-major images on torch's current stream."""
@@ -191,6 +191,16 @@ class GpuScene:
             out[f] = out[f].view("uint32")
         return out
 
+    def denoised_image(self, seed, samples, **params):
+        """The whole frame of `samples` per pixel (render_image), its first-hit buffers of the same samples, and the denoise
+        (rt_hip_denoise; params: abi.denoise_params' keywords) -> numpy (noisy f32 [H,W,3], denoised f32 [H,W,3], denoised u8 [H,W,3])"""
+        image, _, _ = self.render_image(seed, samples)
+        total = n_tiles(self.scene.width, self.scene.height)
+        aov = self.untile_aov(self.render_aov(seed, samples, 0, 1, total, want=DENOISE_AOV), 0, 1, total)
+        rgb, rgb8 = denoise(image, aov, self.scene.width, self.scene.height, **params)
+        torch.cuda.synchronize(image.device)
+        return image.cpu().numpy(), rgb.cpu().numpy(), rgb8.cpu().numpy()
+
     def render_image(self, seed, samples=None, max_depth=None, integrator="path"):
         """Whole image on this one GPU -> (image f32 [H,W,3], image8 u8 [H,W,3], stats dict), synchronised."""
         total = n_tiles(self.scene.width, self.scene.height)
@@ -209,8 +219,9 @@ class Accumulation:
     """An accumulation (rt_hip_accum_*) made by GpuScene.accumulate.  Passes and resolves run asynchronously on torch's current
     stream; the scene must stay open until close()."""
 
-    def __init__(self, gs, handle, count):
+    def __init__(self, gs, handle, count, seed=None, first=0, stride=1, camera=None):
         self.gs, self.shim, self.handle, self.count = gs, gs.shim, handle, count
+        self.seed, self.first, self.stride, self.camera = seed, first, stride, camera
 
     @property
     def samples(self):
@@ -242,6 +253,22 @@ class Accumulation:
                "rt_hip_accum_resolve")
         return tiles, tiles8
 
+    def denoised(self, **params):
+        """The progressive preview: the mean of the samples done (resolve), the first-hit buffers of those samples, and the
+        denoise (rt_hip_denoise; params: abi.denoise_params' keywords) -> (rgb f32 [H,W,3], rgb8 u8 [H,W,3]) on torch's current
+        stream.  The accumulation must cover the whole image."""
+        w, h = self.gs.scene.width, self.gs.scene.height
+        total = n_tiles(w, h)
+        if (self.first, self.stride, self.count) != (0, 1, total):
+            raise ValueError("denoised(): the accumulation must cover the whole image (first 0, stride 1, every tile)")
+        done = self.samples
+        if done < 1:
+            raise ValueError("denoised(): no samples done yet")
+        tiles, tiles8 = self.resolve()
+        image, _ = self.gs.untile(tiles, tiles8, 0, 1, total)
+        aov = self.gs.untile_aov(self.gs.render_aov(self.seed, done, 0, 1, total, camera=self.camera, want=DENOISE_AOV), 0, 1, total)
+        return denoise(image, aov, w, h, **params)
+
     def close(self):
         if self.handle:
             self.shim.rt_hip_accum_destroy(self.handle)
@@ -252,6 +279,40 @@ class Accumulation:
             self.close()
         except Exception:
             pass
+
+
+DENOISE_AOV = ("albedo", "normal", "depth", "object", "hits")   # what the denoiser may read (object: OBJECT_EDGES only)
+
+
+def denoise(rgb, aov, width, height, out=None, **params):
+    """rt_hip_denoise on torch device tensors, asynchronous on torch's current stream: rgb f32 [H,W,3] (row-major, contiguous),
+    aov a dict of row-major buffers as GpuScene.untile_aov gives them (normal, depth, hits; albedo with demodulate, object with
+    object_edges), params abi.denoise_params' keywords.  out: an f32 [H,W,3] tensor for the result (it may be rgb itself).
+    -> (rgb f32 [H,W,3], rgb8 u8 [H,W,3])"""
+    dev = rgb.device
+    shim = abi.load_shim()
+    p = abi.denoise_params(**params)
+    for t in [rgb] + list(aov.values()):
+        if t.device != dev or not t.is_contiguous():
+            raise ValueError("denoise(): every buffer must be a contiguous tensor on the colour's device")
+    if rgb.dtype != torch.float32 or rgb.numel() != width * height * 3:
+        raise ValueError("denoise(): rgb must be float32 of width * height * 3 values")
+    a = abi.RtHipAov()
+    for f, t in aov.items():
+        if f in abi.AOV_FIELDS:
+            if t.numel() != width * height * abi.AOV_CHANNELS[f]:
+                raise ValueError(f"denoise(): {f} must hold width * height * {abi.AOV_CHANNELS[f]} values")
+            setattr(a, f, t.data_ptr())
+    if out is None:
+        out = torch.empty((height, width, 3), dtype=torch.float32, device=dev)
+    elif out.device != dev or out.dtype != torch.float32 or out.numel() != width * height * 3 or not out.is_contiguous():
+        raise ValueError("denoise(): out must be a contiguous float32 tensor of width * height * 3 values on the colour's device")
+    out8 = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(shim.rt_hip_denoise_workspace_bytes(width, height), 1), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_denoise(C.c_void_p(rgb.data_ptr()), C.byref(a), width, height, C.byref(p), C.c_void_p(ws.data_ptr()),
+                               C.c_void_p(out.data_ptr()), C.c_void_p(out8.data_ptr()), C.c_void_p(stream)), "rt_hip_denoise")
+    return out, out8
 
 
 def render_image_host(scene, seed, n_devices=1, samples=None, max_depth=None, integrator="path"):
