@@ -19,9 +19,11 @@ def _materials(sc):
     return out
 
 
-def expected_pixels(ref, sc, seed, samples, pixels, camera=None):
+def expected_pixels(ref, sc, seed, samples, pixels, camera=None, extra=None):
     """ref: an oracle_py.RefMeshOracle.  pixels: row-major pixel indices y * w + x.  -> dict of arrays over the pixels, as the
-    device buffers hold them: albedo / normal float32 [n,3], depth float32 [n], object / hits uint32 [n]"""
+    device buffers hold them: albedo / normal float32 [n,3], depth float32 [n], object / hits uint32 [n].
+    extra: a dict that receives what the buffers do not show -- t_min float64 [n] (the depth before its rounding to float32)
+    and checker uint32 [n,2]: how many of the pixel's samples hit an M_CHECKERED object and took its 0.3x / its 0.7x albedo"""
     cam = camera if camera is not None else sc.camera
     w, h = sc.width, sc.height
     mats = _materials(sc)
@@ -30,6 +32,7 @@ def expected_pixels(ref, sc, seed, samples, pixels, camera=None):
     out = dict(albedo=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float32), depth=np.zeros(n, np.float32),
                object=np.zeros(n, np.uint32), hits=np.zeros(n, np.uint32))
     inv = 1.0 / float(samples)
+    t64, checker = np.full(n, np.inf), np.zeros((n, 2), np.uint32)
     for k, p in enumerate(pixels):
         x, y = int(p % w), int(p // w)
         alb, nrm = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
@@ -42,6 +45,9 @@ def expected_pixels(ref, sc, seed, samples, pixels, camera=None):
             if hit["hit"]:
                 color, flags = mats[hit["id"]]
                 a = ref.checkered(color, hit["u"], hit["v"], 100000.0) if flags & M_CHECKERED else color
+                if flags & M_CHECKERED:
+                    c = int(np.argmax(color))
+                    checker[k, int(float(a[c]) > 0.5 * float(color[c]))] += 1
                 nn = hit["normal"]
                 hits += 1
                 if hit["min_t"] < t_min:
@@ -55,13 +61,16 @@ def expected_pixels(ref, sc, seed, samples, pixels, camera=None):
         out["depth"][k] = t_min
         out["object"][k] = obj
         out["hits"][k] = hits
+        t64[k] = t_min
+    if extra is not None:
+        extra["t_min"], extra["checker"] = t64, checker
     return out
 
 
-def expected_image(ref, sc, seed, samples, camera=None):
-    """expected_pixels over the whole image, shaped as GpuScene.aov_image returns it"""
+def expected_image(ref, sc, seed, samples, camera=None, extra=None):
+    """expected_pixels over the whole image, shaped as GpuScene.aov_image returns it (extra: flat over the pixels)"""
     w, h = sc.width, sc.height
-    e = expected_pixels(ref, sc, seed, samples, np.arange(w * h), camera)
+    e = expected_pixels(ref, sc, seed, samples, np.arange(w * h), camera, extra)
     return {f: (a.reshape(h, w, 3) if a.ndim == 2 else a.reshape(h, w)) for f, a in e.items()}
 
 

@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from denoise_expected import DEMODULATE, OBJECT_EDGES, denoise, same_floats
+from denoise_expected import COLD, DEMODULATE, HOT, OBJECT_EDGES, _edge_inputs, denoise, same_floats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "raytracer.c_amd", "host", "raytracer")
@@ -117,6 +117,177 @@ def test_total_on_inconsistent_inputs():
     for s in (1e-6, 1e6):
         a = _run(b, iterations=4, sigma_color=s, sigma_depth=s, flags=DEMODULATE | OBJECT_EDGES)
         assert same_floats(a, _run(b, iterations=4, sigma_color=s, sigma_depth=s, flags=DEMODULATE | OBJECT_EDGES))
+
+
+# ---- the vectorised restatement against a scalar one, at the edges of the accepted range -------------------------------------
+# denoise() is the expectation of the GPU tests; its np.where / clamped-index forms are pinned above on ordinary values only.
+# scalar_denoise follows include/rt_hip.h steps 1-4 line by line: Python floats are IEEE doubles (+, -, * never raise and never
+# fuse; / goes through _div, Python's own raising on a zero divisor), f32() is each stored rounding.
+
+def f32(x):
+    """a double rounded to float32 (RNE; overflow to inf, denormals kept), widened back exactly"""
+    with np.errstate(all="ignore"):
+        return float(np.float32(x))
+
+
+def _div(a, b):
+    """IEEE 754 a / b"""
+    if b != 0.0:
+        return a / b
+    if a == 0.0 or math.isnan(a):
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+def scalar_denoise(rgb, albedo, normal, depth, hits, obj, iterations=5, sigma_color=0.5, normal_power_log2=3, sigma_depth=1.0,
+                   flags=DEMODULATE):
+    h, w = depth.shape
+    eps = 2.0 ** -10
+    h5 = [1.0 / 16, 1.0 / 4, 3.0 / 8, 1.0 / 4, 1.0 / 16]
+    c = [[[float(rgb[y, x, k]) for k in range(3)] for x in range(w)] for y in range(h)]
+    # 1. a pixel is invalid if any channel of c is not finite
+    valid = [[all(math.isfinite(v) for v in c[y][x]) for x in range(w)] for y in range(h)]
+    # 2. e0 = float(c / (a + eps)) with DEMODULATE, else c
+    if flags & DEMODULATE:
+        a = [[[float(albedo[y, x, k]) + eps for k in range(3)] for x in range(w)] for y in range(h)]
+        e = [[[f32(_div(c[y][x][k], a[y][x][k])) for k in range(3)] for x in range(w)] for y in range(h)]
+    else:
+        e = [[list(c[y][x]) for x in range(w)] for y in range(h)]
+    n = [[[float(normal[y, x, k]) for k in range(3)] for x in range(w)] for y in range(h)]
+    z = [[float(depth[y, x]) for x in range(w)] for y in range(h)]
+    # 3. the iterations
+    for i in range(iterations):
+        s = 2 ** i
+        sigma_i = sigma_color * 2.0 ** -i
+        S2 = sigma_i * sigma_i
+        nxt = [[list(e[y][x]) for x in range(w)] for y in range(h)]
+        for y in range(h):
+            for x in range(w):
+                if not valid[y][x]:
+                    continue
+                W, A = 0.0, [0.0, 0.0, 0.0]
+                ep = e[y][x]
+                for dy in range(-2, 3):
+                    for dx in range(-2, 3):
+                        qx, qy = x + s * dx, y + s * dy
+                        if dx == 0 and dy == 0:
+                            wt = 9.0 / 64.0
+                        else:
+                            if qx < 0 or qx >= w or qy < 0 or qy >= h or not valid[qy][qx]:
+                                continue
+                            if flags & OBJECT_EDGES and int(obj[qy, qx]) != int(obj[y, x]):
+                                continue
+                            hp, hq = int(hits[y, x]), int(hits[qy, qx])
+                            if hp == 0 and hq == 0:
+                                wn = Zn = Zd = 1.0
+                            elif hp == 0 or hq == 0:
+                                continue
+                            else:
+                                g = (n[y][x][0] * n[qy][qx][0] + n[y][x][1] * n[qy][qx][1]) + n[y][x][2] * n[qy][qx][2]
+                                g = g if g > 0 else 0.0
+                                wn = g
+                                for _ in range(normal_power_log2):
+                                    wn = wn * wn
+                                D = (sigma_depth * z[y][x]) * float(s * max(abs(dx), abs(dy)))
+                                Zn = D * D
+                                dz = z[qy][qx] - z[y][x]
+                                Zd = Zn + dz * dz
+                                if Zd == 0:
+                                    Zn = Zd = 1.0
+                            de = [e[qy][qx][k] - ep[k] for k in range(3)]
+                            dc = (de[0] * de[0] + de[1] * de[1]) + de[2] * de[2]
+                            wt = _div(((h5[dx + 2] * h5[dy + 2]) * wn) * (S2 * Zn), (S2 + dc) * Zd)
+                        W += wt
+                        for k in range(3):
+                            A[k] += wt * e[qy][qx][k]
+                nxt[y][x] = [f32(_div(A[k], W)) for k in range(3)]
+        e = nxt
+    # 4. out = float(e_L * (a + eps)) with DEMODULATE, else e_L; invalid pixels pass c through
+    out = np.zeros((h, w, 3), np.float32)
+    for y in range(h):
+        for x in range(w):
+            for k in range(3):
+                if not valid[y][x]:
+                    out[y, x, k] = rgb[y, x, k]
+                else:
+                    out[y, x, k] = np.float32(f32(e[y][x][k] * a[y][x][k]) if flags & DEMODULATE else e[y][x][k])
+    return out
+
+
+def _both(rgb, aov, **p):
+    vec = denoise(rgb, aov["albedo"], aov["normal"], aov["depth"], aov["hits"], aov["object"], **p)
+    with np.errstate(all="ignore"):
+        sca = scalar_denoise(rgb, aov["albedo"], aov["normal"], aov["depth"], aov["hits"], aov["object"], **p)
+    return vec, sca
+
+
+def test_scalar_restatement_gives_the_hand_computed_values():
+    c = np.zeros((3, 3, 3), np.float32)
+    c[1, 1] = 1.0
+    b = _flat(3, 3, c)
+    out = scalar_denoise(b["rgb"], b["albedo"], b["normal"], b["depth"], b["hits"], b["obj"], iterations=1, sigma_color=1.0,
+                         normal_power_log2=0, flags=0)
+    assert np.all(out[1, 1] == np.float32(9 / 19)) and np.all(out[0, 0] == np.float32(4 / 109)) and np.all(out[0, 1] == np.float32(3 / 68))
+    assert f32(1e39) == math.inf and f32(2.0 ** -149) == 2.0 ** -149 and f32(2.0 ** -150) == 0.0 and f32(3 * 2.0 ** -150) == 2.0 ** -148
+    assert math.copysign(1.0, f32(-1e-60)) == -1.0 and math.isnan(_div(0.0, 0.0)) and _div(-1.0, 0.0) == -math.inf == _div(1.0, -0.0)
+
+
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+@pytest.mark.parametrize("size", [(12, 9), (7, 5), (1, 11), (11, 1), (1, 1), (2, 40), (40, 2)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_vectorised_restatement_equals_the_scalar_one_at_the_edges(size, flags):
+    """_edge_inputs with every hot value (hot_band = 1) and with none, L 0 .. 10, k 0 .. 10, sigmas up to the ends of the accepted
+    range.  Without hot values and at k <= 3 most valid pixels stay finite, so that equality is not NaN == NaN alone"""
+    w, h = size
+    sig = ((0.5, 1.0), (1e-6, 1e6), (1e6, 1e-6), (float.fromhex("0x1.6a09e667f3bcdp-529"), 1.7976931348623157e308), (math.nextafter(2.0 ** 512, 0.0), 5e-324))
+    for hot_band in (0.0, 1.0):
+        rgb, aov, planted = _edge_inputs(w, h, np.random.default_rng(w * 100 + h + 7 * flags), hot_band=hot_band)
+        if hot_band and w * h >= 100:
+            assert all(len(planted[c]) for c in COLD + HOT)
+        valid = np.isfinite(rgb).all(axis=2)
+        for n, (L, k) in enumerate(((0, 3), (1, 0), (2, 3), (5, 3), (3, 10), (10, 2), (10, 10), (7, 8), (4, 1))):
+            sc, sz = sig[n % len(sig)] if n >= 4 else (0.5, 1.0)
+            vec, sca = _both(rgb, aov, iterations=L, normal_power_log2=k, sigma_color=sc, sigma_depth=sz, flags=flags)
+            assert same_floats(vec, sca), f"{w}x{h} flags {flags} hot {hot_band} L {L} k {k} sigma {sc} {sz}: " \
+                f"{int((vec.view(np.uint32) != sca.view(np.uint32)).sum())} words differ"
+            assert np.array_equal(vec[~valid].view(np.uint32), rgb[~valid].view(np.uint32))
+            if not hot_band and n < 4 and valid.sum() >= 20:
+                assert np.isfinite(vec[valid]).all(axis=1).mean() > 0.5, f"{w}x{h} flags {flags} L {L}: mostly non-finite"
+
+
+def test_edge_inputs_plant_what_they_say_and_the_nan_cap_holds():
+    """every category in its share of the pixels, next to ordinary ones; and the condition the GPU test relies on: at 320 x 200
+    with the hot values in the left eighth, at most half of the valid pixels are non-finite after five iterations, per flags"""
+    w, h = 320, 200
+    rgb, aov, planted = _edge_inputs(w, h, np.random.default_rng(99))
+    n_cat = len(COLD) + len(HOT)
+    for cat in COLD:
+        assert abs(len(planted[cat]) - 0.4 * w * h / n_cat) <= 2, cat
+    for cat in HOT:
+        assert 0.06 * 0.4 * w * h / n_cat < len(planted[cat]) < 0.2 * 0.4 * w * h / n_cat, cat
+        assert (planted[cat] % w < 40).all()
+    every = np.concatenate(list(planted.values()))
+    assert len(np.unique(every)) == len(every) and 0.3 < len(every) / (w * h) < 0.4
+    flat = lambda a: a.reshape(w * h, -1)
+    fmax = np.float32(np.finfo(np.float32).max)
+    assert (flat(rgb)[planted["flt_max"]] == fmax).all() and (flat(rgb)[planted["neg_flt_max"]] == -fmax).any(axis=1).all()
+    d = flat(rgb)[planted["denormal"]]
+    assert (d > 0).all() and (d < np.finfo(np.float32).tiny).all()
+    assert np.signbit(flat(rgb)[planted["neg_zero"]]).all() and (flat(rgb)[planted["neg_zero"]] == 0).all()
+    assert (flat(rgb)[planted["negative"]] < 0).all()
+    assert (flat(aov["albedo"])[planted["albedo_minus_eps"]][:, :2] == np.float32(-2.0 ** -10)).all()
+    assert (flat(aov["albedo"])[planted["albedo_zero"]] == 0).all() and (flat(aov["albedo"])[planted["albedo_flt_max"]] == fmax).all()
+    assert (flat(aov["depth"])[planted["depth_minus_inf"]] == -np.inf).all() and (flat(aov["depth"])[planted["depth_flt_max"]] == fmax).all()
+    assert (flat(aov["depth"])[planted["hit_with_inf_depth"]] == np.inf).all() and (flat(aov["hits"])[planted["hit_with_inf_depth"]] > 0).all()
+    assert (flat(aov["hits"])[planted["miss_with_depth"]] == 0).all() and np.isfinite(flat(aov["depth"])[planted["miss_with_depth"]]).all()
+    assert (flat(aov["object"])[planted["no_object_id"]] == 0xFFFFFFFF).all() and (flat(aov["hits"])[planted["no_object_id"]] > 0).all()
+    ln = lambda cat: np.linalg.norm(flat(aov["normal"])[planted[cat]].astype(np.float64), axis=1)
+    assert (ln("normal_zero") == 0).all() and (ln("normal_1e19") > 0.9e19).all() and (ln("normal_1e-19") < 1.1e-19).all()
+    valid = np.isfinite(rgb).all(axis=2)
+    assert not valid.reshape(-1)[planted["invalid"]].any()
+    for flags in range(4):
+        out = denoise(rgb, aov["albedo"], aov["normal"], aov["depth"], aov["hits"], aov["object"], iterations=5, flags=flags)
+        bad = float((~np.isfinite(out).all(axis=2) & valid).sum()) / float(valid.sum())
+        assert 0.01 < bad <= 0.5, f"flags {flags}: {bad:.3f} of the valid pixels non-finite"
 
 
 # ---- the entry points without a device -------------------------------------------------------------------------------------

@@ -246,14 +246,7 @@ def test_host_library_and_cli_equal_the_python_buffers(gpu, tmp_path):
     sc.free()
 
 
-# one scene class per AOV form (pt_aov_pick)
-FORM_CLASSES = [
-    ("pt_aov_tiles", dict(n_packed=4)), ("pt_aov_tiles_chk", dict(n_packed=4, chk=True)),
-    ("pt_aov_tiles_tri", dict(n_packed=4, tris=40)), ("pt_aov_tiles_tri_chk", dict(n_packed=4, tris=40, mesh_chk=True)),
-    ("pt_aov_tiles_big", dict(n_packed=4, wide=True)), ("pt_aov_tiles_big_chk", dict(n_packed=4, wide=True, chk=True)),
-    ("pt_aov_tiles_tri_big", dict(n_packed=4, tris=400)), ("pt_aov_tiles_tri_big_chk", dict(n_packed=4, tris=400, chk=True)),
-    ("pt_aov_tiles_mem", dict(n_packed=300, tris=60)), ("pt_aov_tiles_mem_chk", dict(n_packed=300, wide=True, chk=True)),
-]
+from util import AOV_FORM_CLASSES as FORM_CLASSES   # one scene class per AOV form (pt_aov_pick)
 
 
 def test_zz_every_aov_form_was_compared(gpu, ref_mesh):

@@ -404,12 +404,13 @@ def lopsided_mesh_scene(seed):
 
 
 def class_scene(n_packed=4, tris=0, chk=False, refr=False, glass2=False, wide=False, mesh_refr=False, mesh_chk=False,
-                round_mesh=False, depth=5, width=48, height=32, samples=3, seed=1):
+                round_mesh=False, depth=5, width=48, height=32, samples=3, seed=1, open_back=False):
     """a small scene of a chosen CLASS of the kernel pick table (pt_kernel.hip, pt_pick_table): config 4's room with `n_packed`
     packed spheres (8 + n_packed spheres: <= 85 staged, 86..256 streamed by preference, beyond that too large to stage),
     optionally a mesh of `tris` triangles (a bumpy sheet; round_mesh: a tessellated ball instead, whose bounding sphere is the
     better probe), material flags on chosen objects, and -- wide -- a floor sphere of radius 1e19 through the room (a centre
-    or radius beyond 1e17 is what `wide_range` means)"""
+    or radius beyond 1e17 is what `wide_range` means); open_back leaves out the back wall (object 1, the one the class's own
+    camera faces -- the objects after it move up by one): camera rays that pass everything else hit nothing"""
     from rt_amd import abi, scene as S
     room = packed_room(n_packed, seed, width, height, samples, depth)
     objs = [dict(flags=int(room.objects[i].flags), radius=float(room.objects[i].radius), center=room.objects[i].center.tuple(),
@@ -426,6 +427,9 @@ def class_scene(n_packed=4, tris=0, chk=False, refr=False, glass2=False, wide=Fa
         objs[9]["emission"] = (0.0, 0.0, 0.0)
     if wide:
         objs.append(dict(flags=abi.M_DEFAULT, radius=1e19, center=(0.0, -1e19 - 12.0, 0.0), color=(0.6, 0.7, 0.5)))
+    if open_back:
+        assert objs[1]["center"][2] < -1000 and objs[1]["radius"] >= 1000
+        del objs[1]
     meshes = []
     if tris:
         rng = np.random.default_rng(500 + seed)
@@ -472,6 +476,45 @@ PICK_MOVES = {
     ("pt_render_tiles_tri_big", "tiny:wide"), ("pt_render_tiles_pool_mem", "tiny"), ("pt_render_tiles_pool_mem_chk", "tiny"),
     ("pt_whitted_tiles_big", "tiny"),
 }
+
+
+# one scene class per AOV form (pt_aov_pick of pt_kernel.hip: _mem when the sphere geometry and materials are beyond the staging
+# budget, pt_geom_in_lds; else _tri / plain when the filter table is staged, pt_filter_in_lds: at most 256 spheres + triangles
+# and no wide range; else _tri_big / _big; _chk with any M_CHECKERED material).  tests/test_gpu_aov.py compares each from the
+# class's own camera, tests/test_gpu_aov_views.py under every variant at AOV_VIEW_SIZE, and tests/test_aov_views_cpu.py shows
+# what those frames hold.  Two classes have no back wall (open_back): their frames hold misses and silhouettes inside pixels,
+# which a closed room never shows (every camera ray of the other classes hits something).
+AOV_FORM_CLASSES = [
+    ("pt_aov_tiles", dict(n_packed=4)), ("pt_aov_tiles_chk", dict(n_packed=4, chk=True, open_back=True)),
+    ("pt_aov_tiles_tri", dict(n_packed=4, tris=40)), ("pt_aov_tiles_tri_chk", dict(n_packed=4, tris=40, mesh_chk=True)),
+    ("pt_aov_tiles_big", dict(n_packed=4, wide=True)), ("pt_aov_tiles_big_chk", dict(n_packed=4, wide=True, chk=True)),
+    ("pt_aov_tiles_tri_big", dict(n_packed=4, tris=400, open_back=True)), ("pt_aov_tiles_tri_big_chk", dict(n_packed=4, tris=400, chk=True)),
+    ("pt_aov_tiles_mem", dict(n_packed=300, tris=60)), ("pt_aov_tiles_mem_chk", dict(n_packed=300, wide=True, chk=True)),
+]
+AOV_VIEW_SIZE = dict(width=64, height=40, samples=2)
+# (class's form, variant) -> the form the launch takes instead, and why
+AOV_MOVES = {
+    # the floor of radius 1e19 is the only thing that makes these two classes wide_range; scaled by 1e-3 it is 1e16 <= 1e17, and
+    # with 13 spheres and no triangles pt_filter_in_lds holds: the staged-filter forms take the scene
+    ("pt_aov_tiles_big", "tiny"): "pt_aov_tiles", ("pt_aov_tiles_big_chk", "tiny"): "pt_aov_tiles_chk",
+    # not listed, for these reasons: pt_aov_tiles_mem_chk (309 spheres, wide) under tiny stops being wide_range too, but
+    # pt_geom_in_lds is false whatever the range, and pt_aov_pick asks that first; pt_aov_tiles_tri_big[_chk] are _big through
+    # their 400 triangles (> 256 filter entries), not through a range; huge and far make nothing wide (walls of 1e4 x 1e3 = 1e7,
+    # centres 2e7 out), and the floor of 1e19 x 1e3 = 1e22 stays wide; a camera changes no scene class
+}
+
+
+def aov_form_under(form, variant):
+    """the AOV form a launch of `form`'s class of AOV_FORM_CLASSES takes under `variant` (AOV_MOVES)"""
+    return AOV_MOVES.get((form, variant), form)
+
+
+def aov_view_scene(cls, variant, **size):
+    """the scene of class `cls` at AOV_VIEW_SIZE (or `size`) under `variant`"""
+    base = class_scene(**cls, **(size or AOV_VIEW_SIZE))
+    sc = view_variant(base, variant)
+    base.free()
+    return sc
 
 
 def pick_moves(cls, kernel, variant):
