@@ -259,6 +259,20 @@ typedef void RtPassFn(int done, int total, double kernel_seconds, void *user);
 int render_progressive(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects, MeshObject *meshes,
                        size_t n_meshes, Camera *camera, Options *options, int pass_samples, RtPassFn *on_pass, void *user);
 
+/* Adaptive sampling: render_ex's frame with options->samples as the BUDGET per pixel, on ONE device.  8x8 tiles whose error
+ * estimate has settled stop early (include/rt_hip.h, rt_hip_accum_run_adaptive; params == NULL: rt_hip_adapt_defaults); every
+ * tile of the frame is, bit for bit, the tile of a uniform frame of that tile's own sample count.  framebuffer and linear_rgb
+ * (either may be NULL, not both) receive the image; tile_samples (may be NULL) the count map, ceil(w/8) x ceil(h/8) words,
+ * row-major.  After every estimate on_checkpoint (may be NULL) gets the samples done, the budget, the tiles still live and `user`;
+ * the cancel flag (rt_set_cancel_flag) is polled there: when cancelled the image holds the samples done and
+ * rt_last_render_cancelled() reports 1.  Returns the LARGEST per-tile count, or a negative RT_HIP_E* code with the reason on
+ * stderr.  The counters and timings below are those of all passes. */
+long long rt_last_pixel_samples(void); /* pixel samples the last render_adaptive rendered (its mean per pixel: / (w * h)) */
+typedef void RtCheckpointFn(int done, int total, unsigned live_tiles, void *user);
+int render_adaptive(uint8_t *framebuffer, float *linear_rgb, uint32_t *tile_samples, Object *objects, size_t n_objects,
+                    MeshObject *meshes, size_t n_meshes, Camera *camera, Options *options, const RtHipAdaptParams *params,
+                    RtCheckpointFn *on_checkpoint, void *user);
+
 /* First-hit feature buffers of the frame's own samples (include/rt_hip.h, rt_hip_render_aov_*): options->samples camera samples
  * per pixel with the seed of rt_get_seed(), i.e. the samples render_ex draws its camera rays with.  Row-major arrays of
  * width x height pixels, each may be NULL (not all): albedo and normal 3 floats per pixel (the mean over the samples of the

@@ -256,6 +256,74 @@ int32_t rt_hip_accum_samples(const RtHipAccum *accum); /* samples per pixel done
 const char *rt_hip_accum_kernel(const RtHipAccum *accum);
 void rt_hip_accum_destroy(RtHipAccum *accum);
 
+/* ---- adaptive sampling: converged tiles stop early, the frame stays bit-exact ------------------------------------------------
+ * An accumulation can FREEZE tiles between passes: a frozen tile takes no further samples, the passes that follow render the live
+ * tiles only, and a resolve divides every tile by its own sample count.  Freezing is monotone -- a frozen tile never comes back --
+ * so every live tile has had every sample [0, done) and a pass keeps one first sample.
+ * THE CONTRACT: after any sequence of passes and freezes, slot k holds exactly the samples [0, n_k) of its pixels, and its resolved
+ * floats and bytes equal, bit for bit, what a UNIFORM accumulation of the same parameters and budget resolves for that tile after
+ * n_k samples; the counters summed over all passes equal the sum over slots of the counters of that slot's samples [0, n_k).  With
+ * nothing frozen the frame after the budget is the one-shot frame, as before.
+ *   - rt_hip_tile_error: the error estimate of every tile from two compact tile-major float buffers as rt_hip_accum_resolve writes
+ *     them, d_cur (means of the first n samples) and d_prev (of the first h < n); asynchronous on `stream`, on the device that holds
+ *     d_cur; a pure function of its buffers.  fp64 + - * / sqrt in the order written, floats widened exactly, eps = 2^-10:
+ *       pixel p of a tile, inside the image and all six channel values finite:
+ *         d = (|cur.r - prev.r| + |cur.g - prev.g|) + |cur.b - prev.b|,  l = (cur.r + cur.g) + cur.b,  l = (l > 0) ? l : 0,
+ *         e_p = d / sqrt(l + eps);  any other pixel: e_p = +0.0 (outside the image; or NaN / inf, which more samples cannot cure);
+ *       tile: v = e[0..64); for m = 32, 16, 8, 4, 2, 1: v[i] = v[i] + v[i + m] for i < m;  E = float(v[0] / valid), valid = the
+ *         number of the tile's pixels inside the image.
+ *     Half the distance between the means of the two halves of the samples, relative to the pixel's brightness: the measure of
+ *     Dammertz et al.'s hierarchical stopping condition, per 8x8 tile.  d_error: one float per slot.
+ *   - rt_hip_accum_freeze: slot k stays live iff it is live AND some slot u of the accumulation whose tile lies within Chebyshev
+ *     distance `dilate` (0 .. 2 tiles, in the image's tile grid) of slot k's tile has !(E[u] <= threshold) -- a NaN error keeps;
+ *     with tile_stride > 1 the tiles that are not in the accumulation do not vote.  Every other live slot freezes at the samples
+ *     done so far.  threshold <= 0 freezes nothing.  Runs on `stream` and WAITS on it for *live_count (the next pass's grid needs it).
+ *     rt_hip_accum_freeze_mask imposes a host mask instead (h_keep: one byte per slot, 0 = freeze; a frozen slot stays frozen).
+ *   - rt_hip_accum_add / _add_host with frozen tiles render the live slots only (the chunks are planned for that many tiles) and
+ *     count what they rendered; with no live tile they return RT_HIP_OK, render nothing and the samples done do NOT advance.
+ *   - rt_hip_accum_resolve / _read_image divide every slot by its own count once a tile is frozen.
+ *   - rt_hip_accum_tile_samples: the sample-count map, one word per slot (a live slot: the samples done); a copy on the null stream.
+ *   - rt_hip_accum_run_adaptive: the driver for C hosts, synchronous, on the null stream, from an empty accumulation.  Passes end
+ *     at the targets of rt_hip_adapt_schedule: h = max(1, min_samples / 2), then 2h, 4h, ... and the budget.  The first target is
+ *     resolved into `prev`; after every later target below the budget: resolve into `cur`, rt_hip_tile_error, rt_hip_accum_freeze,
+ *     on_checkpoint(user, samples done, live tiles) (may be NULL; nonzero return: RT_HIP_ECANCELLED), swap; it ends when the budget is
+ *     spent or no tile is live.  The last pass is followed by no estimate.  threshold = +inf freezes every tile at the first
+ *     checkpoint (2h samples).  h_stats (RT_HIP_NSTATS, may be NULL) += what was rendered; kernel_seconds (may be NULL) = device time
+ *     of the passes, resolves, estimates and freezes.
+ *     kernel_seconds sums two timers: the passes' own (rt_hip_accum_add_host) and one around every checkpoint's resolve,
+ *     estimate and freeze.  With threshold <= 0 no resolve and no estimate is made at all: the passes alone.
+ *   - rt_hip_render_adaptive_image: the whole image for C hosts, synchronous: a scene and an accumulation of its own on logical
+ *     device `device` of rt_hip_render_image's device map (the HIP device itself without a map), the driver (adapt == NULL: the
+ *     defaults), then the row-major frame (h_rgb, h_rgb8: either may be NULL, not both), the count map (h_tile_samples, may be
+ *     NULL: ceil(w/8) x ceil(h/8) words, row-major) and the counters (h_stats, overwritten, may be NULL).  params->tile_* are
+ *     ignored.  When on_checkpoint cancels, the outputs hold the frame of the samples done and the call returns RT_HIP_ECANCELLED.
+ *   - Streams: a freeze rewrites the slot list on ITS stream and a pass reads it on the pass's; like the passes themselves, the
+ *     freezes, passes and resolves of one accumulation must be ordered by the caller when their streams differ.  A freeze that
+ *     fails on the device after the list was rewritten leaves the accumulation unusable (RT_HIP_ERUNTIME from then on).
+ *   - rt_hip_adapt_schedule: the pass targets for a budget (ascending, the last is the budget) into targets[0 .. cap); returns how
+ *     many there are (0 for a budget or min_samples below 1).  No device.
+ *   - rt_hip_adapt_defaults: min_samples 16, threshold 0.02, dilate 1. */
+typedef struct
+{
+  int32_t min_samples; /* >= 1: the first estimate compares min_samples / 2 with min_samples samples */
+  uint32_t dilate;     /* 0 .. 2 tiles */
+  double threshold;    /* a tile whose error (and whose neighbours') is <= threshold stops */
+} RtHipAdaptParams;
+void rt_hip_adapt_defaults(RtHipAdaptParams *params);
+int rt_hip_adapt_schedule(int32_t budget, int32_t min_samples, int32_t *targets, int32_t cap);
+int rt_hip_tile_error(const float *d_cur, const float *d_prev, int32_t width, int32_t height, uint32_t tile_first, uint32_t tile_stride,
+                      uint32_t tile_count, float *d_error, void *stream);
+int rt_hip_accum_freeze(RtHipAccum *accum, const float *d_error, double threshold, uint32_t dilate, uint32_t *live_count, void *stream);
+int rt_hip_accum_freeze_mask(RtHipAccum *accum, const uint8_t *h_keep, uint32_t *live_count, void *stream);
+int rt_hip_accum_tile_samples(const RtHipAccum *accum, uint32_t *h_counts);
+uint32_t rt_hip_accum_live_tiles(const RtHipAccum *accum);
+int rt_hip_accum_run_adaptive(RtHipAccum *accum, const RtHipAdaptParams *params, uint64_t *h_stats, double *kernel_seconds,
+                              int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles), void *user);
+int rt_hip_render_adaptive_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                                 const RtHipCamera *camera, const RtHipParams *params, const RtHipAdaptParams *adapt, int device,
+                                 float *h_rgb, uint8_t *h_rgb8, uint32_t *h_tile_samples, uint64_t *h_stats, double *kernel_seconds,
+                                 int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles), void *user);
+
 /* ---- first-hit feature buffers (AOVs): albedo, normal, depth, object id ---------------------------------------------------
  * What a denoiser wants next to the noisy colour (albedo and normal of the first hit, averaged over the same camera samples), and
  * what viewers and compositors want for picking and masks (depth, object id).  A launch uses params->width, height, seed and the

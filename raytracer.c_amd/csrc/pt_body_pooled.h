@@ -50,7 +50,7 @@
  * waits on a per-lane stack while paths of this body move between lanes (here: the stack is addressed by a path ID that
  * travels with the path -- PendStack, pend_id_take). */
 template <bool CHECKER, bool TRIS, bool FILT_LDS, bool GEOM_LDS, bool REFR = false>
-__device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L)
+__device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const bool LIST)
 {
   static_assert(!REFR || (CHECKER && FILT_LDS && (GEOM_LDS || !TRIS)), "the pooled refraction kernels: sphere scenes (staged, or streamed from memory) and small staged mesh scenes, every material");
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -126,7 +126,7 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L)
   }
   if (threadIdx.x < PT_TILE_PIXELS)
   {
-    const uint32_t t0 = L.tile_first + (blockIdx.x % L.tile_count) * L.tile_stride;
+    const uint32_t t0 = L.tile_first + launch_slot(L, blockIdx.x % launch_slots(L, LIST), LIST) * L.tile_stride;
     const uint32_t kx = (t0 % L.tiles_x) * PT_TILE + (threadIdx.x & 7u), ky = (t0 / L.tiles_x) * PT_TILE + (threadIdx.x >> 3);
     pix_key[threadIdx.x] = rt_rng_pixel_key(L.seed, ky * (uint32_t)L.width + kx);
   }
@@ -139,7 +139,7 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L)
   const uint32_t wave = threadIdx.x >> 6;
   /* grid = tile_count x sample_chunks, chunk-major: consecutive workgroups are different
    * tiles, so the chunks of an expensive tile are spread over the launch */
-  const uint32_t slot = blockIdx.x % L.tile_count, chunk = blockIdx.x / L.tile_count;
+  const uint32_t slot = launch_slot(L, blockIdx.x % launch_slots(L, LIST), LIST), chunk = blockIdx.x / launch_slots(L, LIST);
   const uint32_t tile = L.tile_first + slot * L.tile_stride;
   const bool cull_ok = S.n_sph + S.n_tri <= 64u * CULL_WORDS;
   if (SWAP && FILT_LDS && cull_ok)

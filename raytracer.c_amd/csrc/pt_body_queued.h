@@ -322,7 +322,7 @@ typedef PoolStackT<512u, 511u> RingStack;
  * more than 256 triangles -- sphere geometry and materials gathered from memory, the spheres' sign-form filter pairs read from
  * memory by scalar loads (as pt_render_tiles_pool_mem_s does for sphere-only scenes); everything else as the staged form. */
 template <bool CHECKER, bool SPHERE_PROBE = false, bool REFR = false, bool GEOM_LDS = true>
-__device__ __forceinline__ void render_tiles_queued(const PtLaunch &L)
+__device__ __forceinline__ void render_tiles_queued(const PtLaunch &L, const bool LIST)
 {
   static_assert(!REFR || CHECKER, "the refraction form carries every material's code");
   constexpr bool TRIS = true, FILT_LDS = false;
@@ -417,13 +417,13 @@ __device__ __forceinline__ void render_tiles_queued(const PtLaunch &L)
   /* work units = tile_count x sample_chunks, chunk-major (consecutive units are different tiles; REFR: tile-major, below); wave w of
    * workgroup b takes unit 4 b + w; the last workgroup may have waves without a unit (pool = 0) */
   const uint32_t unit = blockIdx.x * (PT_BLOCK / 64) + wave;
-  const bool has_unit = unit < L.tile_count * L.sample_chunks;
+  const bool has_unit = unit < launch_slots(L, LIST) * L.sample_chunks;
   /* (the refraction form: TILE-major -- a workgroup's four waves render four chunks of ONE tile: they walk the same part of the
    * hierarchy, and their windowed sums and pending-ray stacks touch the same lines; one rank's share of the glass mesh at N = 8,
    * 256 spp, four chunks: 45.9 -> 40.6 ms of an ideal 37.8.  The plain forms lose 3.5 % that way: profiles/r05_shard_order_experiments.txt) */
   constexpr bool TILE_MAJOR = REFR;
-  const uint32_t slot = !has_unit ? 0u : (TILE_MAJOR ? unit / L.sample_chunks : unit % L.tile_count);
-  const uint32_t chunk = !has_unit ? 0u : (TILE_MAJOR ? unit % L.sample_chunks : unit / L.tile_count);
+  const uint32_t slot = launch_slot_wave(L, !has_unit ? 0u : (TILE_MAJOR ? unit / L.sample_chunks : unit % launch_slots(L, LIST)), LIST);
+  const uint32_t chunk = !has_unit ? 0u : (TILE_MAJOR ? unit % L.sample_chunks : unit / launch_slots(L, LIST));
   const uint32_t tile = L.tile_first + slot * L.tile_stride;
   const uint32_t tx0 = (tile % L.tiles_x) * PT_TILE, ty0 = (tile / L.tiles_x) * PT_TILE;
   const uint32_t vcols = min((uint32_t)PT_TILE, (uint32_t)L.width - tx0);
@@ -958,11 +958,16 @@ __device__ __forceinline__ void render_tiles_queued(const PtLaunch &L)
   {
     /* the tile's numbers once more (see wave_now) */
     const uint32_t unit_e = blockIdx.x * (PT_BLOCK / 64) + wave_now();
-    const uint32_t slot = TILE_MAJOR ? unit_e / L.sample_chunks : unit_e % L.tile_count;
-    const uint32_t chunk = TILE_MAJOR ? unit_e % L.sample_chunks : unit_e / L.tile_count;
+    const uint32_t slot = launch_slot_wave(L, TILE_MAJOR ? unit_e / L.sample_chunks : unit_e % launch_slots(L, LIST), LIST);
+    const uint32_t chunk = TILE_MAJOR ? unit_e % L.sample_chunks : unit_e / launch_slots(L, LIST);
     const uint32_t tile_e = L.tile_first + slot * L.tile_stride;
-    const uint32_t vcols = min((uint32_t)PT_TILE, (uint32_t)L.width - (tile_e % L.tiles_x) * PT_TILE);
-    const uint32_t vrows = min((uint32_t)PT_TILE, (uint32_t)L.height - (tile_e / L.tiles_x) * PT_TILE);
+    /* (the list entries' tile row length likewise: seen as the prologue's, the reciprocal of its division is kept in a register across
+     * the trip loop, and with the slot a loaded value that register was spilled) */
+    uint32_t tiles_x_e = L.tiles_x;
+    if (LIST)
+      asm volatile("" : "+s"(tiles_x_e));
+    const uint32_t vcols = min((uint32_t)PT_TILE, (uint32_t)L.width - (tile_e % tiles_x_e) * PT_TILE);
+    const uint32_t vrows = min((uint32_t)PT_TILE, (uint32_t)L.height - (tile_e / tiles_x_e) * PT_TILE);
     const uint32_t n_valid = vcols * vrows;
     unsigned long long *const pix_sum = pix_sum_all[REFR ? 0u : wave_now()];
     unsigned long long *const pix_nan = pix_nan_all[wave_now()];

@@ -14,7 +14,7 @@
 /* WHITTED: 0 = trace_path, 1 = cast_ray for scenes where no material has both M_REFLECTION and
  * M_REFRACTION (one child per hit at most: no pending-ray stack), 2 = cast_ray with the stack */
 template <int VARIANT, bool REFRACT, bool CHECKER, bool TRIS, bool FILT_LDS, int WHITTED, bool GEOM_LDS>
-__device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
+__device__ __forceinline__ void render_tiles_static(const PtLaunch &L, const bool LIST)
 {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ float out_f[PT_TILE_PIXELS * 3];
@@ -45,7 +45,8 @@ __device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t pix_in_tile = wave * 16u + (lane >> 2);
   const uint32_t slice = lane & (PT_SLICES - 1);
-  const uint32_t tile = L.tile_first + blockIdx.x * L.tile_stride;
+  const uint32_t slot = launch_slot(L, blockIdx.x, LIST);
+  const uint32_t tile = L.tile_first + slot * L.tile_stride;
   const uint32_t px = (tile % L.tiles_x) * PT_TILE + (pix_in_tile & 7u);
   const uint32_t py = (tile / L.tiles_x) * PT_TILE + (pix_in_tile >> 3);
   const bool inside = px < (uint32_t)L.width && py < (uint32_t)L.height;
@@ -55,7 +56,7 @@ __device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
   /* this launch's samples: [sample_first, s_end), absolute; the lane's are those of its slice, s == slice (mod 4) */
   const uint32_t s_end = L.sample_first + spp;
   const bool keep = L.acc_keep != 0u;
-  double *const keep_sum = keep ? L.slice_ws + (size_t)blockIdx.x * (3u * PT_BLOCK) + threadIdx.x : nullptr;
+  double *const keep_sum = keep ? L.slice_ws + (size_t)slot * (3u * PT_BLOCK) + threadIdx.x : nullptr;
 
   V3 acc = {0, 0, 0}; /* sum of finished samples of this lane's slice */
   /* Accumulation (acc_keep): the slice sum goes on from where the previous pass left it, and below it is stored back unreduced.
@@ -134,7 +135,7 @@ __device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
       atomicAdd(&wg_stats[1], (unsigned long long)n_casts);
     }
     __syncthreads();
-    store_tile(L, out_f, out_b, wg_stats, tile, blockIdx.x, S.n_sph + S.n_tri, false, true);
+    store_tile(L, out_f, out_b, wg_stats, tile, slot, S.n_sph + S.n_tri, false, true);
     if (STACKED && pend_ok && threadIdx.x == 0)
       atomicExch(&L.pend_flags[pend_slot], 0u);
     return;
@@ -164,7 +165,7 @@ __device__ __forceinline__ void render_tiles_static(const PtLaunch &L)
     atomicAdd(&wg_stats[1], (unsigned long long)n_casts);
   }
   __syncthreads();
-  store_tile(L, out_f, out_b, wg_stats, tile, blockIdx.x, S.n_sph + S.n_tri, true, true);
+  store_tile(L, out_f, out_b, wg_stats, tile, slot, S.n_sph + S.n_tri, true, true);
   if (STACKED && pend_ok && threadIdx.x == 0)
     atomicExch(&L.pend_flags[pend_slot], 0u); /* every lane is past its last pop (the barrier above) */
 }

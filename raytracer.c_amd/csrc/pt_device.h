@@ -341,6 +341,12 @@ struct PtLaunch
   float *tiles_rgb;
   uint8_t *tiles_rgb8;
   unsigned long long *stats;
+  /* adaptive sampling (rt_hip_accum_freeze): a pass that renders a SET of the frame's slots.  With a list the launch's work units run
+   * over slot_count entries instead of tile_count and entry j renders slot slot_list[j] (ascending, each < tile_count); the tile, the
+   * pixel keys and every workspace address follow from the slot as before, the NaN masks stay behind tile_count records.  Null / 0 in
+   * every launch without frozen tiles; a list needs acc_keep (pt_launch_render) */
+  const uint32_t *slot_list;
+  uint32_t slot_count;
 };
 
 /* The compact tile-major outputs of an AOV launch (rt_hip.h, RtHipAov; render_aov in pt_kernel.hip): tile slot k owns albedo / normal
@@ -406,9 +412,18 @@ struct PtPlan
 PtPlan pt_plan_launch(const PtSceneView &scene, const PtPlanAsk &ask);
 hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int which);
 /* accumulation (rt_hip_accum_*): whether member `which` keeps its sums in acc_ws (CHUNKS) rather than as slice sums (the static
- * body), and the resolve of the sums its passes left: pt_resolve_tiles or pt_resolve_slices over launch.samples samples */
+ * body), and the resolve of the sums its passes left: pt_resolve_tiles or pt_resolve_slices over launch.samples samples
+ * (tile_samples: null, or a count per slot that replaces it where nonzero) */
 bool pt_kernel_takes_chunks(int which);
-hipError_t pt_launch_resolve(const PtLaunch &launch, hipStream_t stream, int which);
+hipError_t pt_launch_resolve(const PtLaunch &launch, const uint32_t *tile_samples, hipStream_t stream, int which);
+/* adaptive sampling: the per-tile error estimate of two resolves (pt_tile_error), and the freeze -- the keep mask from the errors
+ * (error == nullptr: `keep` holds the caller's mask), then the live slots frozen or compacted into slot_list (pt_tile_compact).
+ * tile_samples: per slot, 0 = live, else the count it froze at (device, tile_count words) */
+hipError_t pt_launch_tile_error(const float *cur, const float *prev, int width, int height, uint32_t tile_first, uint32_t tile_stride,
+                                uint32_t tile_count, float *error, hipStream_t stream);
+hipError_t pt_launch_tile_freeze(const float *error, double threshold, int dilate, uint8_t *keep, uint32_t *tile_samples, int width,
+                                 int height, uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, uint32_t done,
+                                 uint32_t *slot_list, uint32_t *live_count, hipStream_t stream);
 /* entries per pending-ray stack a launch needs: max_depth + 2 where a material has two children (M_REFRACTION under trace_path,
  * M_REFLECTION | M_REFRACTION under cast_ray); one where none has -- nothing is ever pushed (a scene on the M_REFRACTION forms for
  * their unbounded sums, pt_classify), at any depth */

@@ -210,7 +210,8 @@ enum PtKernelProps : uint32_t
 #endif
 
 #define PT_ENTRY(id, name, bounds, props, ...) \
-  extern "C" __global__ __launch_bounds__ bounds void name(const PtLaunch L) { __VA_ARGS__(L); }
+  extern "C" __global__ __launch_bounds__ bounds void name(const PtLaunch L) { __VA_ARGS__(L, false); } \
+  extern "C" __global__ __launch_bounds__ bounds void name##_list(const PtLaunch L) { __VA_ARGS__(L, true); }
 PT_FAMILY(PT_ENTRY)
 PT_FAMILY_DEV(PT_ENTRY)
 #undef PT_ENTRY
@@ -226,11 +227,12 @@ struct PtKernelInfo
 {
   const char *name;
   PtKernelFn fn;
+  PtKernelFn fn_list; /* the same member over a slot list (PtLaunch.slot_list): the passes of an accumulation with frozen tiles */
   uint32_t props; /* PtKernelProps */
   bool has(uint32_t p) const { return (props & p) != 0u; }
   uint32_t pend_columns() const { return has(WIDE_PEND) ? 4u * 512u : PT_PEND_COLUMNS; }
 };
-#define PT_INFO(id, name, bounds, props, ...) {#name, name, props},
+#define PT_INFO(id, name, bounds, props, ...) {#name, name, name##_list, props},
 static const PtKernelInfo pt_kernels[K_COUNT] = {PT_FAMILY(PT_INFO) PT_FAMILY_DEV(PT_INFO)};
 #undef PT_INFO
 
@@ -410,12 +412,41 @@ struct PtAovKernelInfo
 static const PtAovKernelInfo pt_aov_kernels[A_COUNT] = {PT_AOV_FAMILY(PT_AOV_INFO)};
 #undef PT_AOV_INFO
 
-/* Second pass of a chunked render: per-tile fixed-point sums -> float3 + tonemapped bytes. */
-extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const PtLaunch L)
+/* The sample count a resolve divides slot `slot` by: the launch's, or -- an accumulation with frozen tiles (rt_hip_accum_freeze) --
+ * the slot's own where it has one (0: the slot is live and holds the launch's count). */
+__device__ __forceinline__ int32_t resolve_samples(const PtLaunch &L, const uint32_t *tile_samples, uint32_t slot)
+{
+  const uint32_t own = tile_samples ? tile_samples[slot] : 0u;
+  return own ? (int32_t)own : L.samples;
+}
+
+/* finish_pixels (pt_trace.h) with the sample count as an argument: the resolve's own copy, statement for statement, so that the
+ * members of the family, which finish their one-chunk tiles with finish_pixels, keep the code they had */
+__device__ __forceinline__ void resolve_finish_pixels(const PtLaunch &L, int32_t samples, const unsigned long long *sums,
+                                                      const unsigned long long *nan_mask, uint32_t tile, float *out_f, uint8_t *out_b)
+{
+  if (threadIdx.x < PT_TILE_PIXELS * 3)
+  {
+    const uint32_t t = threadIdx.x / 3u, c = threadIdx.x - 3u * t;
+    const bool inside = (tile % L.tiles_x) * PT_TILE + (t & 7u) < (uint32_t)L.width &&
+                        (tile / L.tiles_x) * PT_TILE + (t >> 3) < (uint32_t)L.height;
+    const double inv_s = 1.0 / (double)samples;
+    double mean = ((double)(long long)sums[threadIdx.x] * L.acc_inv_scale) * inv_s;
+    const double quiet_nan = __longlong_as_double(0x7FF8000000000000ll);
+    mean = ((nan_mask[c] >> t) & 1ull) ? quiet_nan : mean;
+    out_f[threadIdx.x] = inside ? (float)mean : 0.f;
+    out_b[threadIdx.x] = inside ? tonemap(mean) : 0;
+  }
+}
+
+/* Second pass of a chunked render: per-tile fixed-point sums -> float3 + tonemapped bytes.  tile_samples: null, or a count per
+ * slot (resolve_samples): the slot is finished exactly as a launch of that many samples finishes it. */
+extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const PtLaunch L, const uint32_t *tile_samples)
 {
   __shared__ float out_f[PT_TILE_PIXELS * 3];
   __shared__ uint8_t out_b[PT_TILE_PIXELS * 3 + 64];
   const uint32_t slot = blockIdx.x;
+  const int32_t samples = resolve_samples(L, tile_samples, slot);
   const uint32_t tile = L.tile_first + slot * L.tile_stride;
   if (L.acc_windows)
   { /* the M_REFRACTION forms: windowed sums (win_add), merged chunk by chunk in carry-normalised form */
@@ -428,7 +459,7 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
       for (int k = 0; k < PT_WIN_N; k++)
         w[k] = L.acc_ws[((size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x) * PT_WIN_N + k];
       win_normalize(w);
-      double mean = win_value(w) * (1.0 / (double)L.samples);
+      double mean = win_value(w) * (1.0 / (double)samples);
       const unsigned long long nan_mask = L.acc_ws[(size_t)L.tile_count * (PT_TILE_PIXELS * 3 * PT_WIN_N) + (size_t)slot * 3 + c];
       mean = ((nan_mask >> t) & 1ull) ? __longlong_as_double(0x7FF8000000000000ll) : mean;
       out_f[threadIdx.x] = inside ? (float)mean : 0.f;
@@ -436,8 +467,8 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
     }
   }
   else
-    finish_pixels(L, L.acc_ws + (size_t)slot * (PT_TILE_PIXELS * 3),
-                  L.acc_ws + (size_t)L.tile_count * (PT_TILE_PIXELS * 3) + (size_t)slot * 3, tile, out_f, out_b);
+    resolve_finish_pixels(L, samples, L.acc_ws + (size_t)slot * (PT_TILE_PIXELS * 3),
+                          L.acc_ws + (size_t)L.tile_count * (PT_TILE_PIXELS * 3) + (size_t)slot * 3, tile, out_f, out_b);
   __syncthreads();
   if (threadIdx.x < PT_TILE_PIXELS * 3)
     L.tiles_rgb[(size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x] = out_f[threadIdx.x];
@@ -450,7 +481,7 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
  * means over L.samples (the samples done so far).  Not a member of the family: no scene, no samples.  The lane mapping, the
  * shuffles, the scale and the stores are render_tiles_static's own, so after the whole budget the tile is the one-shot tile bit
  * for bit (the reason is given there). */
-extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_slices(const PtLaunch L)
+extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_slices(const PtLaunch L, const uint32_t *tile_samples)
 {
   __shared__ float out_f[PT_TILE_PIXELS * 3];
   __shared__ uint8_t out_b[PT_TILE_PIXELS * 3 + 64];
@@ -470,7 +501,7 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_slices(const P
   acc.x += __shfl_xor(acc.x, 2);
   acc.y += __shfl_xor(acc.y, 2);
   acc.z += __shfl_xor(acc.z, 2);
-  const V3 mean = v_scale(acc, 1.0 / (double)(uint32_t)L.samples);
+  const V3 mean = v_scale(acc, 1.0 / (double)(uint32_t)resolve_samples(L, tile_samples, slot));
   if (slice == 0)
   {
     out_f[3 * pix_in_tile + 0] = inside ? (float)mean.x : 0.f;
@@ -486,6 +517,107 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_slices(const P
   if (L.tiles_rgb8 && threadIdx.x < PT_TILE_PIXELS * 3 / 4)
     reinterpret_cast<uint32_t *>(L.tiles_rgb8)[(size_t)slot * (PT_TILE_PIXELS * 3 / 4) + threadIdx.x] =
         reinterpret_cast<const uint32_t *>(out_b)[threadIdx.x];
+}
+
+/* ---- adaptive sampling (rt_hip.h: rt_hip_tile_error, rt_hip_accum_freeze) ---------------------------------------------------
+ * pt_tile_error: the error estimate of a tile from two resolves of one accumulation, `cur` (means of the first n samples) and
+ * `prev` (of the first h < n), compact tile-major.  A wave per tile, a lane per pixel; fp64 in the order rt_hip.h writes, floats
+ * widened exactly.  The tile's sum is a butterfly over the lanes: fp64 addition commutes, so lane 0 holds the bits of the tree
+ * v[i] += v[i + m], m = 32 .. 1.  No scene, no LDS. */
+extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_tile_error(const float *__restrict__ cur, const float *__restrict__ prev, int width,
+                                                                     int height, uint32_t tiles_x, uint32_t tile_first,
+                                                                     uint32_t tile_stride, uint32_t tile_count, float *__restrict__ error)
+{
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t slot = blockIdx.x * (PT_BLOCK / 64u) + wave;
+  if (slot >= tile_count)
+    return;
+  const uint32_t tile = tile_first + slot * tile_stride;
+  const uint32_t tx0 = (tile % tiles_x) * PT_TILE, ty0 = (tile / tiles_x) * PT_TILE;
+  const bool inside = tx0 + (lane & 7u) < (uint32_t)width && ty0 + (lane >> 3) < (uint32_t)height;
+  const uint32_t valid = min((uint32_t)PT_TILE, (uint32_t)width - tx0) * min((uint32_t)PT_TILE, (uint32_t)height - ty0);
+  const size_t at = (size_t)slot * (PT_TILE_PIXELS * 3) + 3u * lane;
+  const float c0 = cur[at], c1 = cur[at + 1], c2 = cur[at + 2], p0 = prev[at], p1 = prev[at + 1], p2 = prev[at + 2];
+  const bool finite = isfinite(c0) && isfinite(c1) && isfinite(c2) && isfinite(p0) && isfinite(p1) && isfinite(p2);
+  double e = 0.0;
+  if (inside && finite)
+  {
+    const double d = (fabs((double)c0 - (double)p0) + fabs((double)c1 - (double)p1)) + fabs((double)c2 - (double)p2);
+    double l = ((double)c0 + (double)c1) + (double)c2;
+    l = (l > 0.0) ? l : 0.0;
+    e = d / sqrt(l + 0x1p-10);
+  }
+  for (int m = 32; m > 0; m >>= 1)
+    e = e + __shfl_xor(e, m);
+  if (lane == 0)
+    error[slot] = (float)(e / (double)valid);
+}
+
+/* pt_tile_keep: keep[k] = 1 iff slot k is live (tile_samples[k] == 0) and some slot u of the launch whose tile lies within
+ * Chebyshev distance `dilate` of slot k's tile, in the image's tile grid, has !(error[u] <= threshold); tiles that are not in
+ * the launch (tile_stride > 1) do not vote.  A thread per slot. */
+extern "C" __global__ __launch_bounds__(256) void pt_tile_keep(const float *__restrict__ error, const uint32_t *__restrict__ tile_samples,
+                                                               uint32_t tiles_x, uint32_t tiles_y, uint32_t tile_first, uint32_t tile_stride,
+                                                               uint32_t tile_count, double threshold, int dilate, uint8_t *__restrict__ keep)
+{
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= tile_count)
+    return;
+  const uint32_t tile = tile_first + k * tile_stride;
+  const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
+  bool vote = false;
+  for (int dy = -dilate; dy <= dilate; dy++)
+    for (int dx = -dilate; dx <= dilate; dx++)
+    {
+      const int x = tx + dx, y = ty + dy;
+      if (x < 0 || y < 0 || x >= (int)tiles_x || y >= (int)tiles_y)
+        continue;
+      const uint32_t t = (uint32_t)y * tiles_x + (uint32_t)x;
+      if (t < tile_first)
+        continue;
+      const uint32_t off = t - tile_first;
+      const uint32_t u = tile_stride ? off / tile_stride : 0u;
+      if (u >= tile_count || u * tile_stride != off)
+        continue;
+      vote = vote || !((double)error[u] <= threshold);
+    }
+  keep[k] = (vote && tile_samples[k] == 0u) ? 1 : 0;
+}
+
+/* pt_tile_compact: the freeze itself.  A live slot (tile_samples[k] == 0) that keep[k] does not keep is frozen at `done` samples;
+ * the slots still live go to slot_list in ascending order -- the list is a function of the mask alone -- and their number to
+ * *live_count.  One workgroup: thread i owns the slots [i * per, (i + 1) * per), counts, scans the counts, then writes. */
+#define PT_COMPACT_THREADS 1024
+extern "C" __global__ __launch_bounds__(PT_COMPACT_THREADS) void pt_tile_compact(const uint8_t *__restrict__ keep, uint32_t *__restrict__ tile_samples,
+                                                                               uint32_t tile_count, uint32_t done, uint32_t *__restrict__ slot_list,
+                                                                               uint32_t *__restrict__ live_count)
+{
+  __shared__ uint32_t part[PT_COMPACT_THREADS];
+  const uint32_t per = (tile_count + PT_COMPACT_THREADS - 1u) / PT_COMPACT_THREADS;
+  const uint32_t k0 = min(tile_count, threadIdx.x * per), k1 = min(tile_count, k0 + per);
+  uint32_t n = 0;
+  for (uint32_t k = k0; k < k1; k++)
+  {
+    const bool live = tile_samples[k] == 0u;
+    if (live && !keep[k])
+      tile_samples[k] = done;
+    n += (live && keep[k]) ? 1u : 0u;
+  }
+  part[threadIdx.x] = n;
+  __syncthreads();
+  for (uint32_t step = 1; step < PT_COMPACT_THREADS; step <<= 1)
+  { /* inclusive scan (Hillis-Steele) */
+    const uint32_t add = threadIdx.x >= step ? part[threadIdx.x - step] : 0u;
+    __syncthreads();
+    part[threadIdx.x] += add;
+    __syncthreads();
+  }
+  uint32_t at = part[threadIdx.x] - n;
+  for (uint32_t k = k0; k < k1; k++)
+    if (tile_samples[k] == 0u)
+      slot_list[at++] = k;
+  if (threadIdx.x == PT_COMPACT_THREADS - 1)
+    *live_count = part[threadIdx.x];
 }
 
 /* Self-test hook (rt_hip_selftest_math): evaluates the kernel's exact-arithmetic shortcuts
@@ -1362,7 +1494,7 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
 #endif
   size_t lds_bytes = pt_render_lds_bytes(launch.scene) + extra_lds;
   const PtKernelInfo &k = pt_kernels[which];
-  const PtKernelFn kernel = k.fn;
+  const PtKernelFn kernel = launch.slot_list ? k.fn_list : k.fn;
   if (k.has(STAGES_NONE))
     lds_bytes = extra_lds; /* the in-memory pooled kernels stage nothing, whatever the scene's size */
   if (k.has(PEND_POOL) && (launch.pend_ws == nullptr || launch.pend_entries < pt_pend_entries(launch.scene, launch.integrator, launch.max_depth) ||
@@ -1394,12 +1526,15 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
     if (e != hipSuccess)
       return e;
   }
+  /* a pass over a set of the frame's slots (PtLaunch.slot_list): only an accumulation has sums that outlive the launch */
+  if ((launch.slot_list != nullptr) != (launch.slot_count != 0u) || (launch.slot_list && !launch.acc_keep) || launch.slot_count > launch.tile_count)
+    return hipErrorInvalidValue;
   /* the parked-walk kernels render a tile per wave, four work units per workgroup */
-  const uint32_t n_units = launch.tile_count * launch.sample_chunks;
+  const uint32_t n_units = (launch.slot_list ? launch.slot_count : launch.tile_count) * launch.sample_chunks;
   hipLaunchKernelGGL(kernel, dim3(queued ? (n_units + PT_BLOCK / 64 - 1) / (PT_BLOCK / 64) : n_units), dim3(PT_BLOCK), lds_bytes,
                      stream, launch);
   if (launch.sample_chunks > 1 && !launch.acc_keep)
-    hipLaunchKernelGGL(pt_resolve_tiles, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch);
+    hipLaunchKernelGGL(pt_resolve_tiles, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch, static_cast<const uint32_t *>(nullptr));
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess)
     pt_launch_counts[which].fetch_add(1ull);
@@ -1408,7 +1543,7 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
 
 bool pt_kernel_takes_chunks(int which) { return which >= 0 && which < K_COUNT && pt_kernels[which].has(CHUNKS); }
 
-hipError_t pt_launch_resolve(const PtLaunch &launch, hipStream_t stream, int which)
+hipError_t pt_launch_resolve(const PtLaunch &launch, const uint32_t *tile_samples, hipStream_t stream, int which)
 {
   if (which < 0 || which >= K_COUNT || launch.tile_count == 0u || launch.samples < 1)
     return hipErrorInvalidValue;
@@ -1416,14 +1551,35 @@ hipError_t pt_launch_resolve(const PtLaunch &launch, hipStream_t stream, int whi
   {
     if (launch.acc_ws == nullptr || (launch.acc_windows != 0u) != pt_kernels[which].has(WINDOWED))
       return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pt_resolve_tiles, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch);
+    hipLaunchKernelGGL(pt_resolve_tiles, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch, tile_samples);
   }
   else
   {
     if (launch.slice_ws == nullptr)
       return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pt_resolve_slices, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch);
+    hipLaunchKernelGGL(pt_resolve_slices, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch, tile_samples);
   }
+  return hipGetLastError();
+}
+
+hipError_t pt_launch_tile_error(const float *cur, const float *prev, int width, int height, uint32_t tile_first, uint32_t tile_stride,
+                                uint32_t tile_count, float *error, hipStream_t stream)
+{
+  const uint32_t tiles_x = ((uint32_t)width + PT_TILE - 1) / PT_TILE, waves = PT_BLOCK / 64u;
+  hipLaunchKernelGGL(pt_tile_error, dim3((tile_count + waves - 1u) / waves), dim3(PT_BLOCK), 0, stream, cur, prev, width, height, tiles_x,
+                     tile_first, tile_stride, tile_count, error);
+  return hipGetLastError();
+}
+
+hipError_t pt_launch_tile_freeze(const float *error, double threshold, int dilate, uint8_t *keep, uint32_t *tile_samples, int width,
+                                 int height, uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, uint32_t done,
+                                 uint32_t *slot_list, uint32_t *live_count, hipStream_t stream)
+{
+  const uint32_t tiles_x = ((uint32_t)width + PT_TILE - 1) / PT_TILE, tiles_y = ((uint32_t)height + PT_TILE - 1) / PT_TILE;
+  if (error) /* else the caller has put its own mask into keep */
+    hipLaunchKernelGGL(pt_tile_keep, dim3((tile_count + 255u) / 256u), dim3(256), 0, stream, error, tile_samples, tiles_x, tiles_y, tile_first,
+                       tile_stride, tile_count, threshold, dilate, keep);
+  hipLaunchKernelGGL(pt_tile_compact, dim3(1), dim3(PT_COMPACT_THREADS), 0, stream, keep, tile_samples, tile_count, done, slot_list, live_count);
   return hipGetLastError();
 }
 

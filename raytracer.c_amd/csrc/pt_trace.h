@@ -476,6 +476,19 @@ __device__ __forceinline__ bool whitted_step(const SceneCtx &S, Path &P, uint32_
  * integer sum cannot, so the pooled kernels flag such samples apart and the pixel becomes NaN
  * here.  (Samples are otherwise finite and within the scale's bound: emission is finite and the
  * throughput at most 1, rt_hip_render_tiles_chunked.) */
+/* A launch's slots: how many its work units run over, and the slot of entry j -- the frame's own numbering without a list
+ * (PtLaunch.slot_list), the list's entry with one.  LIST is a constant of the kernel's entry (pt_kernel.hip, PT_ENTRY: every
+ * member has a second entry, name_list, for the passes over a slot list): the members themselves read no new field and compile
+ * to the code they had.  Wave-uniform, read once in the prologue. */
+__device__ __forceinline__ uint32_t launch_slots(const PtLaunch &L, const bool LIST) { return LIST ? L.slot_count : L.tile_count; }
+__device__ __forceinline__ uint32_t launch_slot(const PtLaunch &L, uint32_t j, const bool LIST) { return LIST ? L.slot_list[j] : j; }
+/* ... where j comes from the wave's index (the parked-walk body: a tile per wave): uniform in the wave, which the compiler cannot
+ * see -- told so, the entry is a scalar load and takes no address registers from the lanes */
+__device__ __forceinline__ uint32_t launch_slot_wave(const PtLaunch &L, uint32_t j, const bool LIST)
+{
+  return LIST ? L.slot_list[__builtin_amdgcn_readfirstlane(j)] : j;
+}
+
 __device__ __forceinline__ void finish_pixels(const PtLaunch &L, const unsigned long long *sums,
                                               const unsigned long long *nan_mask, uint32_t tile, float *out_f,
                                               uint8_t *out_b)

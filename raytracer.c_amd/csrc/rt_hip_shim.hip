@@ -1586,6 +1586,14 @@ struct RtHipAccum
   int32_t plan_spc = 0;        /* the plan's samples per chunk: no workgroup of a pass gets more */
   void *sums = nullptr;
   char *pend = nullptr;        /* the accumulation's own pending-ray pool (pend_pool_own), or nullptr */
+  /* adaptive sampling, allocated at the first freeze (accum_adapt_state) in one block: per slot the count it froze at (0: live),
+   * the live slots in ascending order, their number, the keep mask of a freeze */
+  uint32_t *tile_samples = nullptr, *slot_list = nullptr, *d_live_count = nullptr;
+  uint8_t *keep = nullptr;
+  uint32_t live_count = 0;     /* host copy; meaningful once tile_samples exists */
+  bool any_frozen = false;
+  bool broken = false;         /* a freeze failed after the device had rewritten the list: the host's count is stale, nothing may launch */
+  float *adapt_buf = nullptr;  /* rt_hip_accum_run_adaptive: two compact resolves and the error per slot */
 };
 
 static void accum_free(RtHipAccum *a)
@@ -1600,6 +1608,10 @@ static void accum_free(RtHipAccum *a)
       (void)hipFree(a->sums);
     if (a->pend)
       (void)hipFree(a->pend);
+    if (a->tile_samples)
+      (void)hipFree(a->tile_samples);
+    if (a->adapt_buf)
+      (void)hipFree(a->adapt_buf);
   }
   delete a;
 }
@@ -1692,20 +1704,31 @@ int rt_hip_accum_add(RtHipAccum *a, int32_t samples, uint64_t *d_stats, void *st
     return fail(RT_HIP_EINVAL, "accumulation is NULL");
   if (samples <= 0 || samples > a->budget - a->done)
     return fail(RT_HIP_EINVAL, "a pass takes 1 .. %d samples (budget %d, %d done), not %d", a->budget - a->done, a->budget, a->done, samples);
+  if (a->broken)
+    return fail(RT_HIP_ERUNTIME, "the accumulation is unusable: an earlier freeze failed on the device");
   const RtHipScene *scene = a->scene;
   PtLaunch L = a->L;
   L.samples = samples;
   L.sample_first = (uint32_t)a->done;
   L.stats = reinterpret_cast<unsigned long long *>(d_stats);
   L.sample_chunks = 1u;
+  /* with frozen tiles the pass renders the live slots only, and the chunks are planned for that many tiles */
+  const uint32_t pass_tiles = a->any_frozen ? a->live_count : L.tile_count;
+  if (pass_tiles == 0u)
+    return RT_HIP_OK; /* every tile is frozen: nothing is rendered and `done` stays */
+  if (a->any_frozen)
+  {
+    L.slot_list = a->slot_list;
+    L.slot_count = a->live_count;
+  }
   if (a->takes_chunks)
   { /* no workgroup gets more samples than the plan's chunks have (that is what the windowed words are sized by), and a small
      * tile count gets the chunks the suggestion asks for.  Capacity: every chunk adds at most one piece below 2^32 to a word of
      * the tile records, and every chunk has at least one sample, so over all passes a word takes at most budget < 2^31 pieces */
     uint64_t chunks = ((uint64_t)samples + (uint64_t)a->plan_spc - 1u) / (uint64_t)a->plan_spc;
-    chunks = std::max<uint64_t>(chunks, rt_hip_suggest_chunks_depth(scene, L.tile_count, samples, L.max_depth));
+    chunks = std::max<uint64_t>(chunks, rt_hip_suggest_chunks_depth(scene, pass_tiles, samples, L.max_depth));
     chunks = std::min<uint64_t>(chunks, (uint64_t)samples);
-    if ((uint64_t)L.tile_count * chunks > 0x7FFFFFFFull)
+    if ((uint64_t)pass_tiles * chunks > 0x7FFFFFFFull)
       return fail(RT_HIP_EINVAL, "tile_count x sample_chunks exceeds the grid limit");
     L.sample_chunks = (uint32_t)chunks;
   }
@@ -1778,13 +1801,15 @@ int rt_hip_accum_resolve(const RtHipAccum *a, float *d_tiles_rgb, uint8_t *d_til
     return fail(RT_HIP_EINVAL, "accumulation and d_tiles_rgb are required");
   if (a->done < 1)
     return fail(RT_HIP_EINVAL, "the accumulation holds no sample yet");
+  if (a->broken)
+    return fail(RT_HIP_ERUNTIME, "the accumulation is unusable: an earlier freeze failed on the device");
   PtLaunch L = a->L;
   L.samples = a->done;
   L.tiles_rgb = d_tiles_rgb;
   L.tiles_rgb8 = d_tiles_rgb8;
   DeviceScope scope(a->scene->device);
   HIP_TRY(scope.status);
-  const hipError_t e = pt_launch_resolve(L, static_cast<hipStream_t>(stream), a->kernel);
+  const hipError_t e = pt_launch_resolve(L, a->any_frozen ? a->tile_samples : nullptr, static_cast<hipStream_t>(stream), a->kernel);
   if (e != hipSuccess)
     return fail(RT_HIP_ERUNTIME, "accumulation resolve: %s", hipGetErrorString(e));
   return RT_HIP_OK;
@@ -1831,6 +1856,273 @@ int32_t rt_hip_accum_samples(const RtHipAccum *a) { return a ? a->done : 0; }
 const char *rt_hip_accum_kernel(const RtHipAccum *a) { return a ? pt_kernel_name_of(a->kernel) : ""; }
 
 void rt_hip_accum_destroy(RtHipAccum *a) { accum_free(a); }
+
+/* ---- adaptive sampling: the error estimate, the freeze, the driver (rt_hip.h) ------------------------------------------------ */
+
+int rt_hip_tile_error(const float *d_cur, const float *d_prev, int32_t width, int32_t height, uint32_t tile_first, uint32_t tile_stride,
+                      uint32_t tile_count, float *d_error, void *stream)
+{
+  if (!d_cur || !d_prev || !d_error)
+    return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error are required");
+  if (width < 1 || height < 1)
+    return fail(RT_HIP_EINVAL, "width and height must be >= 1");
+  if (tile_count == 0)
+    return RT_HIP_OK;
+  if (tile_stride == 0 && tile_count > 1)
+    return fail(RT_HIP_EINVAL, "tile_stride must be >= 1");
+  const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
+  if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
+    return fail(RT_HIP_EINVAL, "tile range outside the image");
+  if (usable_devices() < 1)
+    return fail(RT_HIP_ENODEV, "no usable HIP device");
+  hipPointerAttribute_t attr = {};
+  int on = -1;
+  for (const void *ptr : {static_cast<const void *>(d_cur), static_cast<const void *>(d_prev), static_cast<const void *>(d_error)})
+  {
+    if (hipPointerGetAttributes(&attr, ptr) != hipSuccess || attr.type != hipMemoryTypeDevice)
+    {
+      (void)hipGetLastError();
+      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be device memory");
+    }
+    if (on >= 0 && attr.device != on)
+      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be on one device (%d, %d)", on, attr.device);
+    on = attr.device;
+  }
+  DeviceScope scope(attr.device);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  const hipError_t e = pt_launch_tile_error(d_cur, d_prev, width, height, tile_first, tile_stride, tile_count, d_error, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "tile error: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+/* the freeze state of an accumulation, made at its first freeze: every slot live */
+static int accum_adapt_state(RtHipAccum *a)
+{
+  if (a->tile_samples)
+    return RT_HIP_OK;
+  const size_t n = a->L.tile_count;
+  const size_t bytes = (2 * n + 1) * sizeof(uint32_t) + n;
+  uint32_t *buf = nullptr;
+  hipError_t e = hipMalloc(&buf, bytes);
+  if (e != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(RT_HIP_ENOMEM, "freeze state (%zu KB): %s", bytes >> 10, hipGetErrorString(e));
+  }
+  e = hipMemset(buf, 0, bytes);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess)
+  {
+    (void)hipGetLastError();
+    (void)hipFree(buf);
+    return fail(RT_HIP_ERUNTIME, "freeze state: %s", hipGetErrorString(e));
+  }
+  a->tile_samples = buf;
+  a->slot_list = buf + n;
+  a->d_live_count = buf + 2 * n;
+  a->keep = reinterpret_cast<uint8_t *>(buf + 2 * n + 1);
+  a->live_count = (uint32_t)n;
+  return RT_HIP_OK;
+}
+
+static int accum_freeze(RtHipAccum *a, const float *d_error, const uint8_t *h_keep, double threshold, uint32_t dilate, uint32_t *live_count,
+                        void *stream)
+{
+  if (live_count)
+    *live_count = 0;
+  if (!a)
+    return fail(RT_HIP_EINVAL, "accumulation is NULL");
+  if (!d_error && !h_keep)
+    return fail(RT_HIP_EINVAL, "a freeze needs the tile errors or a keep mask");
+  if (dilate > 2u)
+    return fail(RT_HIP_EINVAL, "dilate is 0 .. 2 tiles, not %u", dilate);
+  if (a->done < 1)
+    return fail(RT_HIP_EINVAL, "the accumulation holds no sample yet");
+  if (a->broken)
+    return fail(RT_HIP_ERUNTIME, "the accumulation is unusable: an earlier freeze failed on the device");
+  const PtLaunch &L = a->L;
+  if (d_error && !(threshold > 0.0))
+  { /* a threshold <= 0 (or NaN) freezes nothing: the frame stays the uniform one */
+    if (live_count)
+      *live_count = a->tile_samples ? a->live_count : L.tile_count;
+    return RT_HIP_OK;
+  }
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  int rc = accum_adapt_state(a);
+  if (rc)
+    return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipError_t e = hipSuccess;
+  if (!d_error)
+    e = hipMemcpyAsync(a->keep, h_keep, L.tile_count, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = pt_launch_tile_freeze(d_error, threshold, (int)dilate, a->keep, a->tile_samples, L.width, L.height, L.tile_first, L.tile_stride,
+                              L.tile_count, (uint32_t)a->done, a->slot_list, a->d_live_count, st);
+  uint32_t n = 0;
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(&n, a->d_live_count, sizeof n, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st); /* the next pass's grid needs the count on the host */
+  if (e != hipSuccess)
+  { /* the device may have rewritten the counts and the list: the host's copy of the live count cannot be trusted any more */
+    a->broken = true;
+    return fail(RT_HIP_ERUNTIME, "freeze: %s", hipGetErrorString(e));
+  }
+  a->live_count = n;
+  a->any_frozen = a->any_frozen || n < L.tile_count;
+  if (live_count)
+    *live_count = n;
+  return RT_HIP_OK;
+}
+
+int rt_hip_accum_freeze(RtHipAccum *a, const float *d_error, double threshold, uint32_t dilate, uint32_t *live_count, void *stream)
+{
+  if (a && !d_error)
+    return fail(RT_HIP_EINVAL, "d_error is required (rt_hip_accum_freeze_mask takes a host mask)");
+  return accum_freeze(a, d_error, nullptr, threshold, dilate, live_count, stream);
+}
+
+int rt_hip_accum_freeze_mask(RtHipAccum *a, const uint8_t *h_keep, uint32_t *live_count, void *stream)
+{
+  if (a && !h_keep)
+    return fail(RT_HIP_EINVAL, "h_keep is required");
+  return accum_freeze(a, nullptr, h_keep, 0.0, 0u, live_count, stream);
+}
+
+int rt_hip_accum_tile_samples(const RtHipAccum *a, uint32_t *h_counts)
+{
+  if (!a || !h_counts)
+    return fail(RT_HIP_EINVAL, "accumulation and h_counts are required");
+  const uint32_t n = a->L.tile_count;
+  if (a->tile_samples)
+  {
+    DeviceScope scope(a->scene->device);
+    HIP_TRY(scope.status);
+    /* a freeze has waited for its stream before it returned: the counts are at rest, and a copy on the null stream is enough */
+    HIP_TRY(hipMemcpy(h_counts, a->tile_samples, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  for (uint32_t k = 0; k < n; k++)
+    if (!a->tile_samples || h_counts[k] == 0u)
+      h_counts[k] = (uint32_t)a->done; /* a live slot holds every sample done so far */
+  return RT_HIP_OK;
+}
+
+uint32_t rt_hip_accum_live_tiles(const RtHipAccum *a) { return !a ? 0u : (a->tile_samples ? a->live_count : a->L.tile_count); }
+
+void rt_hip_adapt_defaults(RtHipAdaptParams *p)
+{
+  if (!p)
+    return;
+  p->min_samples = 16;
+  p->dilate = 1u;
+  p->threshold = 0.02;
+}
+
+int rt_hip_adapt_schedule(int32_t budget, int32_t min_samples, int32_t *targets, int32_t cap)
+{
+  if (budget < 1 || min_samples < 1)
+    return 0;
+  int n = 0;
+  const int64_t h = std::max<int64_t>(1, min_samples / 2);
+  for (int64_t t = h;; t *= 2)
+  {
+    const int32_t target = (int32_t)std::min<int64_t>(t, budget);
+    if (targets && n < cap)
+      targets[n] = target;
+    n++;
+    if (target == budget)
+      break;
+  }
+  return n;
+}
+
+int rt_hip_accum_run_adaptive(RtHipAccum *a, const RtHipAdaptParams *p, uint64_t *h_stats, double *kernel_seconds,
+                              int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles), void *user)
+{
+  if (kernel_seconds)
+    *kernel_seconds = 0;
+  if (!a || !p)
+    return fail(RT_HIP_EINVAL, "accumulation and params are required");
+  if (p->min_samples < 1 || p->dilate > 2u || p->threshold != p->threshold)
+    return fail(RT_HIP_EINVAL, "adaptive parameters: min_samples >= 1, dilate 0 .. 2, threshold not NaN");
+  if (a->done != 0)
+    return fail(RT_HIP_EINVAL, "the driver starts from an empty accumulation (%d samples done)", a->done);
+  const PtLaunch &L = a->L;
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  const size_t tile_vals = (size_t)L.tile_count * PT_TILE_PIXELS * 3;
+  const bool estimate = p->threshold > 0.0;
+  if (estimate && !a->adapt_buf)
+  {
+    const hipError_t e = hipMalloc(&a->adapt_buf, (2 * tile_vals + L.tile_count) * sizeof(float));
+    if (e != hipSuccess)
+    {
+      (void)hipGetLastError();
+      a->adapt_buf = nullptr;
+      return fail(RT_HIP_ENOMEM, "adaptive buffers: %s", hipGetErrorString(e));
+    }
+  }
+  float *prev = a->adapt_buf, *cur = a->adapt_buf + tile_vals, *err = a->adapt_buf + 2 * tile_vals;
+  int32_t targets[32];
+  const int n_targets = rt_hip_adapt_schedule(a->budget, p->min_samples, targets, 32);
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipEventCreate(&ev[0]);
+  if (e == hipSuccess)
+    e = hipEventCreate(&ev[1]); /* (a failure leaves through the common exit below: nothing has been rendered) */
+  int rc = RT_HIP_OK;
+  double seconds = 0;
+  for (int i = 0; i < n_targets && !rc && e == hipSuccess; i++)
+  {
+    double pass_seconds = 0;
+    if (targets[i] > a->done)
+      rc = rt_hip_accum_add_host(a, targets[i] - a->done, h_stats, &pass_seconds);
+    seconds += pass_seconds;
+    if (rc || targets[i] == a->budget)
+      break; /* the last pass is followed by no estimate */
+    uint32_t live = rt_hip_accum_live_tiles(a);
+    if (estimate)
+    { /* (a threshold <= 0 freezes nothing: no resolve, no estimate, the passes alone) */
+      e = hipEventRecord(ev[0], nullptr);
+      if (e == hipSuccess)
+        rc = rt_hip_accum_resolve(a, i == 0 ? prev : cur, nullptr, nullptr);
+      if (i > 0 && !rc && e == hipSuccess)
+      {
+        /* (every slot is estimated, the frozen ones too: both resolves divide a frozen slot's unchanged sums by its own count, so
+         * cur == prev there, its error is +0.0 and it never votes in the dilation) */
+        rc = rt_hip_tile_error(cur, prev, L.width, L.height, L.tile_first, L.tile_stride, L.tile_count, err, nullptr);
+        if (!rc)
+          rc = rt_hip_accum_freeze(a, err, p->threshold, p->dilate, &live, nullptr);
+        std::swap(prev, cur);
+      }
+      if (!rc && e == hipSuccess)
+        e = hipEventRecord(ev[1], nullptr);
+      if (!rc && e == hipSuccess)
+        e = hipEventSynchronize(ev[1]);
+      float ms = 0.f;
+      if (!rc && e == hipSuccess)
+        e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+      seconds += 1e-3 * (double)ms; /* the checkpoint's own timer, added to the passes' (rt_hip_accum_add_host) */
+    }
+    if (!rc && e == hipSuccess && i > 0 && on_checkpoint && on_checkpoint(user, a->done, live))
+      rc = fail(RT_HIP_ECANCELLED, "adaptive render cancelled at %d samples", a->done);
+    if (!rc && i > 0 && live == 0u)
+      break;
+  }
+  for (hipEvent_t x : ev)
+    if (x)
+      (void)hipEventDestroy(x);
+  if (kernel_seconds)
+    *kernel_seconds = seconds;
+  if (rc)
+    return rc;
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "adaptive render: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
 
 int rt_hip_selftest_math(int op, const double *h_a, const double *h_b, double *h_out, size_t n, int device)
 {
@@ -2731,6 +3023,62 @@ extern "C" int rt_hip_render_aov_image(const RtHipSphere *spheres, size_t n_sphe
   {
     return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in rt_hip_render_aov_image");
   }
+}
+
+/* rt_hip_render_adaptive_image: a scene and an accumulation of their own on the logical device, the driver, the frame and the count
+ * map to host arrays.  Synchronous on the null stream. */
+extern "C" int rt_hip_render_adaptive_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                                            const RtHipCamera *camera, const RtHipParams *params, const RtHipAdaptParams *adapt, int device,
+                                            float *h_rgb, uint8_t *h_rgb8, uint32_t *h_tile_samples, uint64_t *h_stats,
+                                            double *kernel_seconds, int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles),
+                                            void *user)
+{
+  if (kernel_seconds)
+    *kernel_seconds = 0;
+  if (!camera || !params || (!h_rgb && !h_rgb8))
+    return fail(RT_HIP_EINVAL, "camera, params and an output image are required");
+  RtHipAdaptParams defaults;
+  rt_hip_adapt_defaults(&defaults);
+  if (!adapt)
+    adapt = &defaults;
+  if (adapt->min_samples < 1 || adapt->dilate > 2u || adapt->threshold != adapt->threshold)
+    return fail(RT_HIP_EINVAL, "adaptive parameters: min_samples >= 1, dilate 0 .. 2, threshold not NaN");
+  int rc = check_params(params);
+  if (rc)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  RtHipParams p = *params;
+  p.tile_first = 0;
+  p.tile_stride = 1;
+  p.tile_count = tiles_x_of(p.width) * tiles_y_of(p.height);
+  RtHipScene *scene = nullptr;
+  RtHipAccum *acc = nullptr;
+  uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
+  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &scene);
+  if (!rc)
+    rc = rt_hip_accum_create(scene, camera, &p, &acc);
+  if (!rc)
+    rc = rt_hip_accum_run_adaptive(acc, adapt, stats, kernel_seconds, on_checkpoint, user);
+  const bool cancelled = rc == RT_HIP_ECANCELLED; /* the frame of the samples done is still a whole image */
+  if (!rc || cancelled)
+  {
+    int rc2 = rt_hip_accum_read_image(acc, h_rgb, h_rgb8);
+    if (!rc2 && h_tile_samples)
+      rc2 = rt_hip_accum_tile_samples(acc, h_tile_samples);
+    if (rc2)
+      rc = rc2;
+    else if (cancelled)
+      (void)fail(RT_HIP_ECANCELLED, "adaptive render cancelled: the image holds the samples done so far");
+  }
+  if (h_stats)
+    for (int k = 0; k < RT_HIP_NSTATS; k++)
+      h_stats[k] = stats[k];
+  rt_hip_accum_destroy(acc);
+  rt_hip_scene_destroy(scene);
+  return rc;
 }
 
 namespace

@@ -44,6 +44,13 @@ static void on_sigint(int sig)
 }
 
 /* -p: one line per pass */
+static void on_checkpoint(int done, int total, unsigned live_tiles, void *user)
+{
+  (void)user;
+  printf("checkpoint: %d of %d samples, %u tiles live\n", done, total, live_tiles);
+  fflush(stdout);
+}
+
 static void on_pass(int done, int total, double kernel_seconds, void *user)
 {
   (void)user;
@@ -98,6 +105,8 @@ typedef struct
   int pass; /* -p: samples per pass; 0: not given (one-shot) */
   const char *aov; /* -a: prefix of the feature-buffer files; NULL: none */
   int denoise;     /* -n: iterations + 1; 0: not given */
+  int adaptive;    /* -e given */
+  double threshold; /* -e: the error at or below which a tile stops */
   uint64_t seed;
 } Args;
 
@@ -108,7 +117,8 @@ static void usage(const char *prog)
           "          [-d <max depth>] [-c <scene config 1..5>] [-g <gpus>] [-r <seed>]\n"
           "          [-i <integrator: 0 trace_path, 1 cast_ray>] [-p <samples per pass, one GPU>]\n"
           "          [-a <prefix of the albedo / normal / depth .pfm files>]\n"
-          "          [-n <denoise iterations 0..10: -o denoised, <name>.noisy.png as rendered>]\n",
+          "          [-n <denoise iterations 0..10: -o denoised, <name>.noisy.png as rendered>]\n"
+          "          [-e <adaptive sampling: tiles whose error estimate is <= this stop early; -s is the budget; one GPU>]\n",
           prog);
 }
 
@@ -134,6 +144,12 @@ static int parse_args(int argc, char **argv, Args *a)
     case 'n':
       a->denoise = atoi(val) + 1;
       if (a->denoise < 1 || a->denoise > 11 || val[0] < '0' || val[0] > '9')
+        return -1;
+      break;
+    case 'e':
+      a->adaptive = 1;
+      a->threshold = strtod(val, NULL);
+      if (!(a->threshold >= 0.0) || (val[0] != '.' && (val[0] < '0' || val[0] > '9')))
         return -1;
       break;
     case 'p':
@@ -169,7 +185,7 @@ int main(int argc, char **argv)
   RtSceneInfo info;
   if (rt_scene_info(a.config, &info) != 0 || a.options.width < 2 || a.options.height < 2 || a.options.samples < 1 ||
       (a.integrator != RT_TRACE_PATH && a.integrator != RT_CAST_RAY) ||
-      (a.pass > 0 && (a.pass > a.options.samples || a.gpus > 1)))
+      (a.pass > 0 && (a.pass > a.options.samples || a.gpus > 1)) || (a.adaptive && (a.pass > 0 || a.gpus > 1)))
   {
     usage(argv[0]);
     return EXIT_FAILURE;
@@ -224,7 +240,27 @@ int main(int argc, char **argv)
 
   double tic = now_seconds();
   int held = a.options.samples;
-  if (a.pass > 0)
+  if (a.adaptive)
+  {
+    const size_t n_tiles = (size_t)((a.options.width + 7) / 8) * (size_t)((a.options.height + 7) / 8);
+    uint32_t *counts = (uint32_t *)calloc(n_tiles, sizeof(uint32_t));
+    RtHipAdaptParams ap;
+    rt_hip_adapt_defaults(&ap);
+    ap.threshold = a.threshold;
+    held = counts ? render_adaptive(framebuffer, linear, counts, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options, &ap,
+                                    on_checkpoint, NULL)
+                  : -1;
+    if (held < 0)
+      return EXIT_FAILURE; /* render_adaptive said why */
+    size_t full = 0;
+    for (size_t k = 0; k < n_tiles; k++)
+      full += counts[k] >= (uint32_t)a.options.samples;
+    printf("adaptive: threshold %g, mean %.2f samples per pixel of %d, %.1f %% of the tiles ran the whole budget\n", a.threshold,
+           (double)rt_last_pixel_samples() / ((double)a.options.width * a.options.height), a.options.samples,
+           100.0 * (double)full / (double)n_tiles);
+    free(counts);
+  }
+  else if (a.pass > 0)
   {
     held = render_progressive(framebuffer, linear, scene, info.n_objects, meshes, info.n_meshes, &camera, &a.options, a.pass,
                               on_pass, NULL);
@@ -245,9 +281,9 @@ int main(int argc, char **argv)
          a.gpus == 1 ? "" : "s");
   if (kernel_s > 0)
     printf("%.3e ray-bounces/s, %.2f Mpixel-samples/s\n", (double)rt_last_ray_bounces() / kernel_s,
-           (double)a.options.width * a.options.height * held / kernel_s * 1e-6);
+           (a.adaptive ? (double)rt_last_pixel_samples() : (double)a.options.width * a.options.height * held) / kernel_s * 1e-6);
   int status = EXIT_SUCCESS;
-  if (rt_last_render_cancelled() && a.pass > 0)
+  if (rt_last_render_cancelled() && (a.pass > 0 || a.adaptive))
     printf("interrupted: the image holds %d of %d samples per pixel\n", held, a.options.samples);
   else if (rt_last_render_cancelled())
     printf("interrupted: the image holds the tiles finished so far\n");
@@ -258,13 +294,16 @@ int main(int argc, char **argv)
   else
     printf("done.\n");
 #endif
+  /* the first-hit buffers of -a and -n hold the frame's own samples: as many as the image holds -- of an adaptive frame the
+   * BUDGET's (its tiles hold prefixes of them), unless it was interrupted: then the samples done */
+  const int aov_samples = a.adaptive && !rt_last_render_cancelled() ? a.options.samples : held;
   if (a.aov && status == EXIT_SUCCESS)
   { /* the frame's own samples: as many as the image holds, the same seed */
     float *albedo = (float *)malloc(n_px * 3 * sizeof(float)), *normal = (float *)malloc(n_px * 3 * sizeof(float));
     float *depth = (float *)malloc(n_px * sizeof(float));
     RtAovImage aov = {albedo, normal, depth, NULL, NULL};
     Options o = a.options;
-    o.samples = held;
+    o.samples = aov_samples;
     if (!albedo || !normal || !depth || render_aov(&aov, scene, info.n_objects, meshes, info.n_meshes, &camera, &o) < 0 ||
         write_pfm(a.aov, "albedo", albedo, o.width, o.height, 3) || write_pfm(a.aov, "normal", normal, o.width, o.height, 3) ||
         write_pfm(a.aov, "depth", depth, o.width, o.height, 1))
@@ -278,7 +317,7 @@ int main(int argc, char **argv)
   }
   if (a.denoise && status == EXIT_SUCCESS)
   {
-    if (held < 1 || (rt_last_render_cancelled() && a.pass == 0))
+    if (held < 1 || (rt_last_render_cancelled() && a.pass == 0 && !a.adaptive))
     { /* a one-shot frame cut short holds finished tiles only: nothing to denoise */
       fprintf(stderr, "not denoised: the frame is incomplete\n");
       status = EXIT_FAILURE;
@@ -290,7 +329,7 @@ int main(int argc, char **argv)
       uint32_t *hits = (uint32_t *)malloc(n_px * sizeof(uint32_t));
       RtAovImage aov = {albedo, normal, depth, NULL, hits};
       Options o = a.options;
-      o.samples = held;
+      o.samples = aov_samples;
       RtHipDenoiseParams dp;
       rt_hip_denoise_defaults(&dp);
       dp.iterations = a.denoise - 1;
@@ -303,7 +342,7 @@ int main(int argc, char **argv)
       }
       else
       {
-        printf("denoised (%d iterations, first-hit buffers of %d samples) in %f s; writing '%s'...\n", dp.iterations, held,
+        printf("denoised (%d iterations, first-hit buffers of %d samples) in %f s; writing '%s'...\n", dp.iterations, aov_samples,
                now_seconds() - t0, a.options.result);
         if (stbi_write_png(a.options.result, o.width, o.height, 3, framebuffer, o.width * 3) == 0)
           status = EXIT_FAILURE;

@@ -57,6 +57,7 @@ void rt_set_integrator(int integrator)
 }
 int rt_get_integrator(void) { return g_integrator; }
 double rt_last_render_seconds(void) { return g_last_seconds; }
+static long long g_last_samples = 0; /* render_adaptive: pixel samples rendered */
 static const volatile int *g_cancel_flag = NULL; /* render_progressive polls it between passes */
 void rt_set_cancel_flag(const volatile int *flag)
 {
@@ -333,6 +334,70 @@ int render_progressive(uint8_t *framebuffer, float *linear_rgb, Object *objects,
   g_last_bounces = (long long)stats[RT_HIP_STAT_CASTS];
   return done;
 }
+
+typedef struct
+{
+  RtCheckpointFn *fn;
+  void *user;
+  int total, done;
+} AdaptHook;
+
+static int adapt_checkpoint(void *user, int32_t done, uint32_t live)
+{
+  AdaptHook *h = (AdaptHook *)user;
+  h->done = done;
+  if (h->fn)
+    h->fn(done, h->total, live, h->user);
+  return g_cancel_flag && *g_cancel_flag;
+}
+
+int render_adaptive(uint8_t *framebuffer, float *linear_rgb, uint32_t *tile_samples, Object *objects, size_t n_objects,
+                    MeshObject *meshes, size_t n_meshes, Camera *camera, Options *options, const RtHipAdaptParams *params,
+                    RtCheckpointFn *on_checkpoint, void *user)
+{
+  if (devices_to_use() > 1)
+  {
+    fprintf(stderr, "render_adaptive: renders on one device (%d set)\n", devices_to_use());
+    return RT_HIP_EINVAL;
+  }
+  if (!camera || !options || (!framebuffer && !linear_rgb))
+  {
+    fprintf(stderr, "render_adaptive: camera, options and an output are required\n");
+    return RT_HIP_EINVAL;
+  }
+  RtHipMesh *hm = hip_meshes(meshes, n_meshes);
+  RtHipParams p = image_params(options);
+  const size_t n_tiles = (size_t)((options->width + RT_HIP_TILE - 1) / RT_HIP_TILE) * (size_t)((options->height + RT_HIP_TILE - 1) / RT_HIP_TILE);
+  uint32_t *counts = tile_samples ? tile_samples : (uint32_t *)calloc(n_tiles ? n_tiles : 1, sizeof(uint32_t));
+  uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
+  double seconds = 0;
+  AdaptHook hook = {on_checkpoint, user, p.samples, 0};
+  int rc = counts ? rt_hip_render_adaptive_image((const RtHipSphere *)objects, n_objects, hm, n_meshes, (const RtHipCamera *)camera, &p, params,
+                                                 0, linear_rgb, framebuffer, counts, stats, &seconds, adapt_checkpoint, &hook)
+                  : RT_HIP_ENOMEM;
+  free(hm);
+  const int cancelled = rc == RT_HIP_ECANCELLED;
+  int most = 0;
+  if (!rc || cancelled)
+    for (size_t k = 0; k < n_tiles; k++)
+      most = (int)counts[k] > most ? (int)counts[k] : most;
+  if (counts != tile_samples)
+    free(counts);
+  if (rc && !cancelled)
+  {
+    fprintf(stderr, "render_adaptive: GPU path failed (%d): %s\n", rc, rc == RT_HIP_ENOMEM && !counts ? "out of host memory" : rt_hip_last_error());
+    return rc;
+  }
+  g_last_cancelled = cancelled;
+  ray_count += (long long)stats[RT_HIP_STAT_RAYS];
+  intersection_test_count += (long long)stats[RT_HIP_STAT_TESTS];
+  g_last_seconds = seconds;
+  g_last_bounces = (long long)stats[RT_HIP_STAT_CASTS];
+  g_last_samples = (long long)stats[RT_HIP_STAT_SAMPLES];
+  return most;
+}
+
+long long rt_last_pixel_samples(void) { return g_last_samples; }
 
 int render_aov(RtAovImage *out, Object *objects, size_t n_objects, MeshObject *meshes, size_t n_meshes, Camera *camera,
                Options *options)

@@ -91,6 +91,12 @@ class RtHipDenoiseParams(C.Structure):  # rt_hip.h: the denoiser's parameters (r
                 ("sigma_color", C.c_double), ("sigma_depth", C.c_double)]
 
 
+class RtHipAdaptParams(C.Structure):  # rt_hip.h: adaptive sampling (rt_hip_adapt_defaults)
+    _fields_ = [("min_samples", C.c_int32), ("dilate", C.c_uint32), ("threshold", C.c_double)]
+
+
+ADAPT_CHECKPOINT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_uint32)  # on_checkpoint(user, samples done, live tiles)
+
 DENOISE_DEMODULATE, DENOISE_OBJECT_EDGES = 1, 2   # RT_HIP_DENOISE_*
 
 AOV_FIELDS = ("albedo", "normal", "depth", "object", "hits")   # RtHipAov order
@@ -140,6 +146,19 @@ SHIM_SYMBOLS = {
     "rt_hip_accum_samples": (C.c_int32, [C.c_void_p]),
     "rt_hip_accum_kernel": (C.c_char_p, [C.c_void_p]),
     "rt_hip_accum_destroy": (None, [C.c_void_p]),
+    "rt_hip_adapt_defaults": (None, [C.POINTER(RtHipAdaptParams)]),
+    "rt_hip_adapt_schedule": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "rt_hip_tile_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                    C.c_void_p]),
+    "rt_hip_accum_freeze": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),
+    "rt_hip_accum_freeze_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+    "rt_hip_accum_tile_samples": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_hip_accum_live_tiles": (C.c_uint32, [C.c_void_p]),
+    "rt_hip_accum_run_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RtHipAdaptParams), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+                                            C.c_void_p, C.c_void_p]),
+    "rt_hip_render_adaptive_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.POINTER(Camera),
+                                               C.POINTER(RtHipParams), C.POINTER(RtHipAdaptParams), C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "rt_hip_untile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_set_cancel_flag": (None, [C.c_void_p]),
@@ -200,6 +219,9 @@ HOST_SYMBOLS = {
     "rt_set_cancel_flag": (None, [C.c_void_p]),
     "render_progressive": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
                                      C.POINTER(Camera), C.POINTER(Options), C.c_int, C.c_void_p, C.c_void_p]),
+    "render_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
+                                  C.POINTER(Camera), C.POINTER(Options), C.POINTER(RtHipAdaptParams), C.c_void_p, C.c_void_p]),
+    "rt_last_pixel_samples": (C.c_longlong, []),
     "render_aov": (C.c_int, [C.POINTER(RtAovImage), C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
                              C.POINTER(Camera), C.POINTER(Options)]),
     "denoise_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.c_int, C.c_int,
@@ -269,3 +291,20 @@ def denoise_params(iterations=None, sigma_color=None, sigma_depth=None, normal_p
         if v is not None:
             p.flags = (p.flags | bit) if v else (p.flags & ~bit)
     return p
+
+
+def adapt_params(min_samples=None, threshold=None, dilate=None):
+    """rt_hip_adapt_defaults() with the given fields replaced (None: the default)"""
+    p = RtHipAdaptParams()
+    load_shim().rt_hip_adapt_defaults(C.byref(p))
+    for f, v in (("min_samples", min_samples), ("threshold", threshold), ("dilate", dilate)):
+        if v is not None:
+            setattr(p, f, v)
+    return p
+
+
+def adapt_schedule(budget, min_samples):
+    """rt_hip_adapt_schedule(): the sample counts the passes of an adaptive render end at (no device needed)"""
+    buf = (C.c_int32 * 32)()
+    n = load_shim().rt_hip_adapt_schedule(budget, min_samples, buf, 32)
+    return [int(buf[k]) for k in range(n)]

@@ -201,6 +201,24 @@ class GpuScene:
         torch.cuda.synchronize(image.device)
         return image.cpu().numpy(), rgb.cpu().numpy(), rgb8.cpu().numpy()
 
+    def render_adaptive(self, seed, samples, max_depth=None, integrator="path", **params):
+        """An adaptive frame of at most `samples` per pixel on this GPU (Accumulation.run_adaptive; params: abi.adapt_params'
+        keywords) -> (image f32 [H,W,3], image8 u8 [H,W,3], tile sample counts uint32 [tiles_y, tiles_x], stats dict, device
+        seconds), synchronised."""
+        w, h = self.scene.width, self.scene.height
+        total = n_tiles(w, h)
+        acc = self.accumulate(seed, samples, max_depth=max_depth, integrator=integrator)
+        try:
+            st, secs = acc.run_adaptive(**params)
+            tiles, tiles8 = acc.resolve()
+            image, image8 = self.untile(tiles, tiles8, 0, 1, total)
+            counts = acc.tile_samples().reshape((h + abi.TILE - 1) // abi.TILE, (w + abi.TILE - 1) // abi.TILE)
+            torch.cuda.synchronize(tiles.device)
+            self.launch_status()
+        finally:
+            acc.close()
+        return image, image8, counts, st, secs
+
     def render_image(self, seed, samples=None, max_depth=None, integrator="path"):
         """Whole image on this one GPU -> (image f32 [H,W,3], image8 u8 [H,W,3], stats dict), synchronised."""
         total = n_tiles(self.scene.width, self.scene.height)
@@ -269,6 +287,54 @@ class Accumulation:
         aov = self.gs.untile_aov(self.gs.render_aov(self.seed, done, 0, 1, total, camera=self.camera, want=DENOISE_AOV), 0, 1, total)
         return denoise(image, aov, w, h, **params)
 
+    @property
+    def live_tiles(self):
+        """how many slots still take samples (all of them until a freeze)"""
+        return int(self.shim.rt_hip_accum_live_tiles(self.handle))
+
+    def freeze(self, error=None, mask=None, threshold=None, dilate=None):
+        """Stop tiles (rt_hip_accum_freeze): with `error` (an f32 [count] device tensor, tile_error's) every live slot whose own
+        error and whose neighbours' within `dilate` tiles are <= threshold; with `mask` (one byte per slot, host or device, 0 =
+        freeze) the slots the caller names.  Runs on torch's current stream and waits for the count -> live slots left."""
+        if (error is None) == (mask is None):
+            raise ValueError("freeze(): give the tile errors or a mask")
+        dev = torch.device("cuda", self.gs.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        live = C.c_uint32(0)
+        if error is not None:
+            p = abi.adapt_params(threshold=threshold, dilate=dilate)
+            if error.device != dev or error.dtype != torch.float32 or error.numel() != self.count or not error.is_contiguous():
+                raise ValueError("freeze(): error must be a contiguous float32 tensor of one value per slot on the scene's device")
+            _check(self.shim.rt_hip_accum_freeze(self.handle, C.c_void_p(error.data_ptr()), p.threshold, p.dilate, C.byref(live),
+                                                 C.c_void_p(stream)), "rt_hip_accum_freeze")
+        else:
+            import numpy as np
+            m = np.ascontiguousarray((mask.cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)) != 0, dtype=np.uint8)
+            if m.size != self.count:
+                raise ValueError("freeze(): mask must hold one value per slot")
+            _check(self.shim.rt_hip_accum_freeze_mask(self.handle, C.c_void_p(m.ctypes.data), C.byref(live), C.c_void_p(stream)),
+                   "rt_hip_accum_freeze_mask")
+        return int(live.value)
+
+    def tile_samples(self):
+        """the sample-count map: numpy uint32 [count], how many samples each slot holds (synchronises)"""
+        import numpy as np
+        out = np.zeros(self.count, dtype=np.uint32)
+        _check(self.shim.rt_hip_accum_tile_samples(self.handle, C.c_void_p(out.ctypes.data)), "rt_hip_accum_tile_samples")
+        return out
+
+    def run_adaptive(self, on_checkpoint=None, **params):
+        """The adaptive driver (rt_hip_accum_run_adaptive; params: abi.adapt_params' keywords), synchronous on the null stream,
+        from an empty accumulation.  on_checkpoint(samples_done, live_tiles) -> truthy to cancel.
+        -> (stats dict of what was rendered, device seconds)"""
+        p = abi.adapt_params(**params)
+        stats = (C.c_uint64 * abi.NSTATS)()
+        secs = C.c_double(0)
+        cb = abi.ADAPT_CHECKPOINT(lambda user, done, live: 1 if on_checkpoint(done, live) else 0) if on_checkpoint else None
+        _check(self.shim.rt_hip_accum_run_adaptive(self.handle, C.byref(p), stats, C.byref(secs),
+                                                   C.cast(cb, C.c_void_p) if cb else None, None), "rt_hip_accum_run_adaptive")
+        return dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3]), secs.value
+
     def close(self):
         if self.handle:
             self.shim.rt_hip_accum_destroy(self.handle)
@@ -279,6 +345,24 @@ class Accumulation:
             self.close()
         except Exception:
             pass
+
+
+def tile_error(cur, prev, width, height, first=0, stride=1, count=None, out=None):
+    """rt_hip_tile_error on torch device tensors, asynchronous on torch's current stream: cur, prev f32 [count,64,3] compact tile
+    buffers as Accumulation.resolve gives them (the means of the first n and of the first h < n samples) -> f32 [count], the
+    error estimate of every slot"""
+    dev = cur.device
+    if count is None:
+        count = n_tiles(width, height)
+    for t in (cur, prev):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count * abi.TILE_PIXELS * 3:
+            raise ValueError("tile_error(): cur and prev must be contiguous float32 tile buffers of count x 64 x 3 on one device")
+    if out is None:
+        out = torch.empty(count, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(abi.load_shim().rt_hip_tile_error(C.c_void_p(cur.data_ptr()), C.c_void_p(prev.data_ptr()), width, height, first, stride,
+                                             count, C.c_void_p(out.data_ptr()), C.c_void_p(stream)), "rt_hip_tile_error")
+    return out
 
 
 DENOISE_AOV = ("albedo", "normal", "depth", "object", "hits")   # what the denoiser may read (object: OBJECT_EDGES only)
@@ -352,3 +436,26 @@ def aov_image_host(scene, seed, samples, device=0):
     _check(shim.rt_hip_render_aov_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera), C.byref(p),
                                         device, C.byref(aov)), "rt_hip_render_aov_image")
     return out
+
+
+def adaptive_image_host(scene, seed, samples, device=0, max_depth=None, integrator="path", **params):
+    """rt_hip_render_adaptive_image(): the C hosts' entry point (its own scene and accumulation on logical device `device`,
+    synchronous; params: abi.adapt_params' keywords) -> (image f32 [H,W,3], image8 u8 [H,W,3], tile sample counts uint32
+    [tiles_y, tiles_x], stats dict, device seconds)"""
+    import numpy as np
+    shim = abi.load_shim()
+    p = abi.RtHipParams()
+    p.width, p.height, p.samples, p.seed = scene.width, scene.height, samples, seed
+    p.max_depth = scene.max_depth if max_depth is None else max_depth
+    p.integrator = abi.INTEGRATORS[integrator]
+    ap = abi.adapt_params(**params)
+    h, w = scene.height, scene.width
+    img, img8 = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.uint8)
+    counts = np.zeros(((h + abi.TILE - 1) // abi.TILE, (w + abi.TILE - 1) // abi.TILE), np.uint32)
+    stats = (C.c_uint64 * abi.NSTATS)()
+    secs = C.c_double(0)
+    meshes = scene.hip_meshes()
+    _check(shim.rt_hip_render_adaptive_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera), C.byref(p),
+                                             C.byref(ap), device, img.ctypes.data, img8.ctypes.data, counts.ctypes.data, stats,
+                                             C.byref(secs), None, None), "rt_hip_render_adaptive_image")
+    return img, img8, counts, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3]), secs.value
