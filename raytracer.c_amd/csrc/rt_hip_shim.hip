@@ -36,6 +36,147 @@ static_assert(RT_HIP_TILE == PT_TILE && RT_HIP_TILE_PIXELS == PT_TILE_PIXELS, "t
 static_assert((2.0 * RT_NEAR_R_LIMIT / 1.5) * (2.0 * RT_NEAR_R_LIMIT / 1.5) * 1.0001 < 3.2e150 /* < 2^500 */,
               "the near_R limit keeps |e1||e2||d| inside rcp_unscaled's range");
 
+namespace
+{
+
+thread_local char g_err[512] = "";
+const volatile int *g_cancel = nullptr; /* rt_hip_set_cancel_flag */
+
+int fail(int code, const char *fmt, ...)
+{
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+#define HIP_TRY(expr)                                                                               \
+  do                                                                                                \
+  {                                                                                                 \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess)                                                                           \
+    {                                                                                               \
+      (void)hipGetLastError(); /* reported here: no later call may find it again */                 \
+      return fail(e_ == hipErrorOutOfMemory ? RT_HIP_ENOMEM : RT_HIP_ERUNTIME, "%s: %s", #expr,     \
+                  hipGetErrorString(e_));                                                           \
+    }                                                                                               \
+  } while (0)
+
+#define NCCL_TRY(expr)                                                                              \
+  do                                                                                                \
+  {                                                                                                 \
+    ncclResult_t r_ = (expr);                                                                       \
+    if (r_ != ncclSuccess)                                                                          \
+      return fail(RT_HIP_ERUNTIME, "%s: %s", #expr, ncclGetErrorString(r_));                        \
+  } while (0)
+
+/* selects a device for the current scope and puts the previous one back */
+struct DeviceScope
+{
+  int prev = -1;
+  hipError_t status;
+  explicit DeviceScope(int device)
+  {
+    status = hipGetDevice(&prev);
+    if (status == hipSuccess && prev != device)
+      status = hipSetDevice(device);
+  }
+  ~DeviceScope()
+  {
+    if (prev >= 0)
+      (void)hipSetDevice(prev);
+  }
+};
+
+/* A device allocation that is freed when its owner -- a scope, or a longer-lived object that has it as a member -- goes away.
+ * alloc() reports as hipMalloc does and leaves no sticky error behind a failure (the caller may go on with less: a later
+ * hipGetLastError() must not see it).  at<T>(byte offset) is the typed view of a part.  Movable, not copyable. */
+struct DeviceBuffer
+{
+  void *ptr = nullptr;
+  DeviceBuffer() = default;
+  DeviceBuffer(DeviceBuffer &&o) noexcept { std::swap(ptr, o.ptr); }
+  DeviceBuffer &operator=(DeviceBuffer &&o) noexcept
+  {
+    std::swap(ptr, o.ptr); /* what this one held goes with `o` */
+    return *this;
+  }
+  ~DeviceBuffer() { release(); }
+  hipError_t alloc(size_t bytes)
+  {
+    release();
+    const hipError_t e = hipMalloc(&ptr, bytes);
+    if (e != hipSuccess)
+    {
+      ptr = nullptr;
+      (void)hipGetLastError();
+    }
+    return e;
+  }
+  void release()
+  {
+    if (ptr)
+      (void)hipFree(ptr);
+    ptr = nullptr;
+  }
+  explicit operator bool() const { return ptr != nullptr; }
+  template <class T>
+  T *at(size_t byte_offset = 0) const
+  {
+    return reinterpret_cast<T *>(static_cast<char *>(ptr) + byte_offset);
+  }
+};
+
+/* Two timing events around a piece of work on one stream.  Movable, not copyable. */
+struct EventPair
+{
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  EventPair() = default;
+  EventPair(EventPair &&o) noexcept { std::swap(ev, o.ev); }
+  EventPair &operator=(EventPair &&o) noexcept
+  {
+    std::swap(ev, o.ev);
+    return *this;
+  }
+  ~EventPair()
+  {
+    for (hipEvent_t x : ev)
+      if (x)
+        (void)hipEventDestroy(x);
+  }
+  hipError_t create()
+  {
+    const hipError_t e = hipEventCreate(&ev[0]);
+    return e == hipSuccess ? hipEventCreate(&ev[1]) : e;
+  }
+  hipError_t start(hipStream_t stream) { return hipEventRecord(ev[0], stream); }
+  hipError_t stop(hipStream_t stream) { return hipEventRecord(ev[1], stream); }
+  hipError_t wait() { return hipEventSynchronize(ev[1]); } /* for the stop */
+  hipError_t elapsed_ms(float *ms) { return hipEventElapsedTime(ms, ev[0], ev[1]); }
+};
+
+/* C++ exceptions (std::bad_alloc from a std::vector, above all) must not cross the C boundary: every entry point whose body can
+ * throw runs it in here */
+template <class F>
+int guarded(const char *name, F &&body)
+{
+  try
+  {
+    return body();
+  }
+  catch (const std::bad_alloc &)
+  {
+    return fail(RT_HIP_ENOMEM, "host allocation failed in %s", name);
+  }
+  catch (...)
+  {
+    return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in %s", name);
+  }
+}
+
+} // namespace
+
 /* The camera-dependent tables of a scene (packed-fp32 filter table, fp32 hierarchy nodes; both
  * depend on near_R, i.e. on the camera's distance) for one near_R.  Built once on the stream of
  * the first launch that needs them and immutable afterwards, so launches of one scene with
@@ -87,55 +228,32 @@ struct RtHipScene
   bool hull_flags = false; /* tri_object carries PT_HULL_PLUS / PT_HULL_MINUS (pt_build_hull_flags ran) */
 };
 
+/* ---- progressive rendering: one frame accumulated over passes (rt_hip.h, RtHipAccum) ----------------------------------------
+ * The plan is made once, for the whole budget, and every pass launches its member in accumulation mode (PtLaunch.sample_first,
+ * acc_keep): the CHUNKS members add exact integer sums (fixed point, or windowed words) to the tile records in `sums`, the static
+ * body continues its lanes' fp64 slice sums there.  A pass never re-plans, and the pools the plan needs are held here. */
+struct RtHipAccum
+{
+  const RtHipScene *scene = nullptr;
+  PtLaunch L;                  /* the launch as planned at create; a pass sets samples, sample_first, sample_chunks, stats */
+  int kernel = -1;
+  bool takes_chunks = false;   /* CHUNKS member: sums are tile records (pt_resolve_tiles); else slice sums (pt_resolve_slices) */
+  int32_t budget = 0, done = 0;
+  int32_t plan_spc = 0;        /* the plan's samples per chunk: no workgroup of a pass gets more */
+  /* the sums, the accumulation's own pending-ray pool (pend_pool_own; empty where the plan needs none), and for adaptive sampling
+   * the freeze state, allocated at the first freeze (accum_adapt_state) in one block -- per slot the count it froze at (0: live),
+   * the live slots in ascending order, their number, the keep mask of a freeze -- and rt_hip_accum_run_adaptive's two compact
+   * resolves and the error per slot.  accum_free waits for the device before they go. */
+  DeviceBuffer sums, pend, tile_samples, adapt_buf;
+  uint32_t *slot_list = nullptr, *d_live_count = nullptr; /* inside tile_samples */
+  uint8_t *keep = nullptr;
+  uint32_t live_count = 0;     /* host copy; meaningful once tile_samples exists */
+  bool any_frozen = false;
+  bool broken = false;         /* a freeze failed after the device had rewritten the list: the host's count is stale, nothing may launch */
+};
+
 namespace
 {
-
-thread_local char g_err[512] = "";
-const volatile int *g_cancel = nullptr; /* rt_hip_set_cancel_flag */
-
-int fail(int code, const char *fmt, ...)
-{
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                               \
-  do                                                                                                \
-  {                                                                                                 \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess)                                                                           \
-      return fail(e_ == hipErrorOutOfMemory ? RT_HIP_ENOMEM : RT_HIP_ERUNTIME, "%s: %s", #expr,     \
-                  hipGetErrorString(e_));                                                           \
-  } while (0)
-
-#define NCCL_TRY(expr)                                                                              \
-  do                                                                                                \
-  {                                                                                                 \
-    ncclResult_t r_ = (expr);                                                                       \
-    if (r_ != ncclSuccess)                                                                          \
-      return fail(RT_HIP_ERUNTIME, "%s: %s", #expr, ncclGetErrorString(r_));                        \
-  } while (0)
-
-/* selects a device for the current scope and puts the previous one back */
-struct DeviceScope
-{
-  int prev = -1;
-  hipError_t status;
-  explicit DeviceScope(int device)
-  {
-    status = hipGetDevice(&prev);
-    if (status == hipSuccess && prev != device)
-      status = hipSetDevice(device);
-  }
-  ~DeviceScope()
-  {
-    if (prev >= 0)
-      (void)hipSetDevice(prev);
-  }
-};
 
 int usable_devices()
 {
@@ -147,6 +265,8 @@ int usable_devices()
   }
   return n;
 }
+
+bool have_device(int device) { return device >= 0 && device < usable_devices(); }
 
 /* host mirrors of the reference's vector.h operations (order matters) */
 struct H3
@@ -522,36 +642,31 @@ int pend_pool_for(int device, uint32_t entries, uint32_t columns, PtLaunch &L)
 /* A pending-ray pool of an accumulation's own (rt_hip_accum_create): laid out as the device's pool (flags, then slots), allocated
  * once for the plan and held until rt_hip_accum_destroy, so that no other launch can grow, shrink or free it mid-frame.  The
  * injected failure of the wide pool applies as in pend_pool_for.  The current device is the scene's. */
-int pend_pool_own(uint32_t entries, uint32_t columns, PtLaunch &L, char **out)
+int pend_pool_own(uint32_t entries, uint32_t columns, PtLaunch &L, DeviceBuffer &out)
 {
-  *out = nullptr;
   const uint32_t per = pt_pool_slots_per_xcd(false);
   const size_t slot_bytes = (size_t)entries * PT_PEND_FIELDS_HOST * columns * sizeof(double);
   const size_t bytes = pend_flag_bytes(per) + (size_t)PT_PARK_XCDS * per * slot_bytes;
   if (columns > PT_PEND_COLUMNS && (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_WIDE_PEND))
     return fail(RT_HIP_ENOMEM, "pending-ray pool for max_depth %u (%zu MB): allocation failure injected", entries - 2u, bytes >> 20);
-  char *ws = nullptr;
-  hipError_t e = hipMalloc(&ws, bytes);
+  DeviceBuffer ws;
+  hipError_t e = ws.alloc(bytes);
   if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
     return fail(RT_HIP_ENOMEM, "pending-ray pool for max_depth %u (%zu MB): %s", entries - 2u, bytes >> 20, hipGetErrorString(e));
-  }
-  e = hipMemset(ws, 0, pend_flag_bytes(per));
+  e = hipMemset(ws.ptr, 0, pend_flag_bytes(per));
   if (e == hipSuccess)
     e = hipStreamSynchronize(nullptr);
   if (e != hipSuccess)
   {
     (void)hipGetLastError();
-    (void)hipFree(ws);
     return fail(RT_HIP_ERUNTIME, "pending-ray pool: %s", hipGetErrorString(e));
   }
-  L.pend_flags = reinterpret_cast<uint32_t *>(ws);
-  L.pend_ws = reinterpret_cast<double *>(ws + pend_flag_bytes(per));
+  L.pend_flags = ws.at<uint32_t>();
+  L.pend_ws = ws.at<double>(pend_flag_bytes(per));
   L.pend_slots_per_xcd = per;
   L.pend_entries = entries;
   L.pend_slot_doubles = (uint64_t)entries * PT_PEND_FIELDS_HOST * columns;
-  *out = ws;
+  out = std::move(ws);
   return RT_HIP_OK;
 }
 
@@ -658,110 +773,20 @@ int check_params(const RtHipParams *p)
   return RT_HIP_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-const char *rt_hip_last_error(void) { return g_err; }
-
-void rt_hip_set_cancel_flag(const volatile int *flag) { g_cancel = flag; }
-
-int rt_hip_device_count(void) { return usable_devices(); }
-
-int rt_hip_device_info(int device, char *name, size_t name_cap, int *compute_units)
+/* every tile of the image, in order */
+void whole_image(RtHipParams &p)
 {
-  if (device < 0 || device >= usable_devices())
-    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (name && name_cap)
-    snprintf(name, name_cap, "%s (%s)", prop.name, prop.gcnArchName);
-  if (compute_units)
-    *compute_units = prop.multiProcessorCount;
+  p.tile_first = 0;
+  p.tile_stride = 1;
+  p.tile_count = tiles_x_of(p.width) * tiles_y_of(p.height);
+}
+
+int check_adapt(const RtHipAdaptParams *p)
+{
+  if (p->min_samples < 1 || p->dilate > 2u || p->threshold != p->threshold)
+    return fail(RT_HIP_EINVAL, "adaptive parameters: min_samples >= 1, dilate 0 .. 2, threshold not NaN");
   return RT_HIP_OK;
 }
-
-} /* extern "C" */
-
-namespace
-{
-int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
-                      int device, RtHipScene **out_scene);
-int render_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
-                      const RtHipCamera *camera, const RtHipParams *params, int n_devices, float *h_image_rgb,
-                      uint8_t *h_image_rgb8, uint64_t *h_stats, double *kernel_seconds);
-void release_cache_impl();
-uint64_t cache_builds_impl();
-int set_device_map_impl(const int *map, int n);
-void last_phases_impl(double out[3]);
-} // namespace
-
-extern "C" {
-
-/* C++ exceptions (std::bad_alloc from the staging vectors) must not cross the C boundary */
-int rt_hip_scene_create(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
-                        size_t n_meshes, int device, RtHipScene **out_scene)
-{
-  try
-  {
-    return scene_create_impl(spheres, n_spheres, meshes, n_meshes, device, out_scene);
-  }
-  catch (const std::bad_alloc &)
-  {
-    return fail(RT_HIP_ENOMEM, "host allocation failed while staging the scene");
-  }
-  catch (...)
-  {
-    return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in rt_hip_scene_create");
-  }
-}
-
-void rt_hip_release_cache(void) { release_cache_impl(); }
-
-void rt_hip_last_image_phases(double seconds[3])
-{
-  if (seconds)
-    last_phases_impl(seconds);
-}
-
-int rt_hip_set_device_map(const int *map, int n)
-{
-  try
-  {
-    return set_device_map_impl(map, n);
-  }
-  catch (...)
-  {
-    return fail(RT_HIP_ENOMEM, "host allocation failed in rt_hip_set_device_map");
-  }
-}
-
-uint64_t rt_hip_cache_builds(void) { return cache_builds_impl(); }
-
-int rt_hip_render_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
-                        size_t n_meshes, const RtHipCamera *camera, const RtHipParams *params,
-                        int n_devices, float *h_image_rgb, uint8_t *h_image_rgb8, uint64_t *h_stats,
-                        double *kernel_seconds)
-{
-  try
-  {
-    return render_image_impl(spheres, n_spheres, meshes, n_meshes, camera, params, n_devices, h_image_rgb,
-                             h_image_rgb8, h_stats, kernel_seconds);
-  }
-  catch (const std::bad_alloc &)
-  {
-    return fail(RT_HIP_ENOMEM, "host allocation failed in rt_hip_render_image");
-  }
-  catch (...)
-  {
-    return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in rt_hip_render_image");
-  }
-}
-
-} /* extern "C" */
-
-namespace
-{
 
 int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
                       int device, RtHipScene **out_scene)
@@ -771,7 +796,7 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   *out_scene = nullptr;
   if ((n_spheres && !spheres) || (n_meshes && !meshes))
     return fail(RT_HIP_EINVAL, "NULL scene array with non-zero count");
-  if (device < 0 || device >= usable_devices())
+  if (!have_device(device))
     return fail(RT_HIP_ENODEV, "no HIP device %d (found %d)", device, usable_devices());
 
   size_t n_tri = 0;
@@ -1063,242 +1088,19 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   return RT_HIP_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-void rt_hip_scene_destroy(RtHipScene *scene)
-{
-  if (!scene)
-    return;
-  {
-    DeviceScope scope(scene->device);
-    for (TableSet &t : scene->tables)
-    {
-      if (t.built) (void)hipEventSynchronize(t.built);
-      for (auto &r : t.readers)
-      {
-        (void)hipEventSynchronize(r.second);
-        (void)hipEventDestroy(r.second);
-      }
-      if (t.built) (void)hipEventDestroy(t.built);
-      if (t.owned)
-      {
-        (void)hipFree(t.filt);
-        (void)hipFree(t.bvh_nodes);
-      }
-    }
-    if (scene->park_ws)
-    { /* every launch of this scene must be past its last ring access before the pool can go */
-      (void)hipDeviceSynchronize();
-      park_drop_ws(scene->device);
-    }
-    (void)hipFree(scene->blob);
-  }
-  delete scene;
-}
-
-int rt_hip_scene_device(const RtHipScene *scene) { return scene ? scene->device : -1; }
-
-size_t rt_hip_scene_primitives(const RtHipScene *scene)
-{
-  return scene ? (size_t)scene->view.n_spheres + scene->view.n_triangles : 0;
-}
-
-int rt_hip_scene_hull_facets(const RtHipScene *scene, uint32_t *n_plus, uint32_t *n_minus)
-{
-  if (!scene || !n_plus || !n_minus)
-    return fail(RT_HIP_EINVAL, "rt_hip_scene_hull_facets: null argument");
-  *n_plus = *n_minus = 0;
-  const size_t n = scene->view.n_triangles;
-  if (n == 0 || !scene->hull_flags)
-    return 0;
-  std::vector<uint32_t> obj(n);
-  DeviceScope on(scene->device);
-  HIP_TRY(on.status);
-  HIP_TRY(hipMemcpy(obj.data(), scene->view.tri_object, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n; i++)
-  {
-    *n_plus += (obj[i] & PT_HULL_PLUS) ? 1u : 0u;
-    *n_minus += (obj[i] & PT_HULL_MINUS) ? 1u : 0u;
-  }
-  return 0;
-}
-
 /* the scene has the parked-walk workspace, or would get it at its first launch (rt_hip_render_tiles_chunked acquires it) */
-static bool park_ws_expected(const RtHipScene *scene)
+bool park_ws_expected(const RtHipScene *scene)
 {
   std::lock_guard<std::mutex> lock(scene->table_mutex);
   /* (a scene that has met its workspace keeps it, whatever is injected later; one that has not yet would not get it now) */
   return scene->park_tried ? scene->park_ws != nullptr : (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_PARK_WS) == 0;
 }
 
-const char *rt_hip_kernel_name(const RtHipScene *scene, uint32_t integrator)
-{
-  if (!scene)
-    return "";
-  /* a scene whose parked-walk workspace could not be allocated runs on the lane-waiting kernels: report what a launch
-   * takes, so that an out-of-memory fallback cannot pass as a measurement of the parked-walk kernels.  What is assumed of
-   * the launch itself: sums that fit (one sample at depth 0, one chunk), a pending-ray pool of full width --
-   * rt_hip_last_launch_kernel() has the fact. */
-  const PtPlanAsk ask = {.integrator = integrator, .samples = 1, .max_depth = 0, .max_emission = scene->max_emission, .sample_chunks = 1,
-                         .have_park_ws = park_ws_expected(scene), .wide_pend_ok = !(g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_WIDE_PEND)};
-  return pt_kernel_name_of(pt_plan_launch(scene->view, ask).kernel);
-}
-
-const char *rt_hip_last_launch_kernel(void) { return pt_kernel_name_of(g_last_kernel); }
-
-int rt_hip_kernel_count(void) { return pt_kernel_count(); }
-
-const char *rt_hip_kernel_launches(int index, uint64_t *launches)
-{
-  if (index < 0 || index >= pt_kernel_count())
-    return nullptr;
-  if (launches)
-    *launches = pt_kernel_launches(index);
-  return pt_kernel_name_of(index);
-}
-
-const char *rt_hip_kernel_for_class(const RtHipSceneClass *c)
-{
-  if (!c)
-    return "";
-  PtSceneView v;
-  memset(&v, 0, sizeof v);
-  v.n_spheres = c->n_spheres;
-  v.n_meshes = c->n_meshes;
-  v.n_triangles = c->n_triangles;
-  v.n_bvh_nodes = c->n_triangles ? std::max(1u, c->n_triangles / 8u) : 0u;
-  v.any_checker = c->any_checker ? 1u : 0u;
-  v.any_refract = c->any_refract ? 1u : 0u;
-  v.any_mirror_glass = c->any_mirror_glass ? 1u : 0u;
-  v.wide_range = c->wide_range ? 1u : 0u;
-  v.mesh_round = c->mesh_round ? 1u : 0u;
-  /* one chunk of samples_per_chunk samples, without a chunk workspace: the class's facts go to the pick unchanged */
-  const PtPlanAsk ask = {.integrator = c->integrator, .samples = c->samples_per_chunk, .max_depth = c->max_depth, .max_emission = c->max_emission,
-                         .sample_chunks = 1, .have_park_ws = c->have_park_ws != 0, .wide_pend_ok = c->wide_pend_ok != 0};
-  return pt_kernel_name_of(pt_plan_launch(v, ask).kernel);
-}
-
-void rt_hip_selftest_fail_alloc(uint32_t mask) { g_fail_alloc.store(mask); }
-
-int rt_hip_selftest_pool_slots(int device, uint32_t *park_slots_per_xcd, uint32_t *pend_slots_per_xcd)
-{
-  if (device < 0 || device >= usable_devices())
-    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  if (park_slots_per_xcd)
-    *park_slots_per_xcd = pt_pool_slots_per_xcd(true);
-  if (pend_slots_per_xcd)
-    *pend_slots_per_xcd = pt_pool_slots_per_xcd(false);
-  return RT_HIP_OK;
-}
-
-int rt_hip_pool_bytes(int device, size_t *park_ws_bytes, size_t *pend_pool_bytes)
-{
-  if (device < 0 || device >= 64 || device >= usable_devices())
-    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
-  if (park_ws_bytes)
-  {
-    std::lock_guard<std::mutex> lock(g_park_mutex);
-    const ParkPool &p = g_park[device];
-    *park_ws_bytes = p.ws ? park_flag_bytes(p.slots_per_xcd) + (size_t)PT_PARK_XCDS * p.slots_per_xcd * (PT_BLOCK / 64) * (size_t)PT_PARK_WAVE_BYTES : 0;
-  }
-  if (pend_pool_bytes)
-  {
-    std::lock_guard<std::mutex> lock(g_pend_mutex);
-    const PendPool &p = g_pend[device];
-    *pend_pool_bytes = p.ws ? pend_flag_bytes(p.slots_per_xcd) + (size_t)PT_PARK_XCDS * p.slots_per_xcd * p.entries * PT_PEND_FIELDS_HOST * p.columns * sizeof(double) : 0;
-  }
-  return RT_HIP_OK;
-}
-
-int rt_hip_launch_status(int device, uint32_t *flags)
-{
-  uint32_t f = 0;
-  if (flags)
-    *flags = 0;
-  if (device < 0 || device >= usable_devices())
-    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  int rc = status_take(device, &f);
-  if (rc)
-    return rc;
-  if (flags)
-    *flags = f;
-  return status_to_error(f);
-}
-
-size_t rt_hip_chunk_workspace_bytes(uint32_t tile_count)
-{ /* enough for any scene: the windowed sums of the M_REFRACTION forms are the larger record */
-  return (size_t)tile_count * PT_ACC_WS_WORDS_WIN * sizeof(unsigned long long);
-}
-
-size_t rt_hip_scene_chunk_workspace_bytes(const RtHipScene *scene, uint32_t tile_count)
-{
-  const bool windowed = !scene || scene->view.any_refract;
-  return (size_t)tile_count * (windowed ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long);
-}
-
-uint32_t rt_hip_suggest_chunks(const RtHipScene *scene, uint32_t tile_count, int32_t samples)
-{
-  return rt_hip_suggest_chunks_depth(scene, tile_count, samples, 0);
-}
-
-uint32_t rt_hip_suggest_chunks_depth(const RtHipScene *scene, uint32_t tile_count, int32_t samples, int32_t max_depth)
-{
-  if (!scene || tile_count == 0 || samples < 1)
-    return 1;
-  /* scenes with M_REFRACTION: at least as many chunks as the windowed sums need (pt_refr_pool_fits per chunk) */
-  const uint64_t need = pt_refr_chunk_floor(scene->view, samples, max_depth, tile_count);
-  if (samples < 128)
-    return (uint32_t)need;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, scene->device) != hipSuccess)
-    return (uint32_t)need;
-  /* which body the scene takes (the plan of a launch with a chunk workspace): the parked-walk kernels render a tile per WAVE
-   * (four per workgroup, four workgroups per CU), and a chunk of theirs must be longer -- a wave amortises its walk batches and
-   * its final, partly filled walk over its pool */
-  const PtPlanAsk ask = {.integrator = RT_HIP_TRACE_PATH, .samples = samples, .max_depth = max_depth, .max_emission = scene->max_emission,
-                         .sample_chunks = 1, .have_chunk_ws = true, .tile_count = tile_count, .have_park_ws = park_ws_expected(scene),
-                         .wide_pend_ok = true};
-  const PtPlan plan = pt_plan_launch(scene->view, ask);
-  uint64_t want, min_chunk_samples;
-  if (plan.queued)
-  {
-    /* >= 30 rounds of workgroups (the expensive tiles -- those on the mesh -- are few and long: one workgroup of four of them at
-     * 4096 spp outlasts a rank's whole ideal share at N = 8), >= 128 samples per chunk.  One rank's share of config 5 at N = 8,
-     * ms by chunks (tools/shard_chunks.py, profiles/r05_shard_chunks.txt): 4096 spp 1: 608, 2: 505, 4: 465, 8: 447, 12: 443, 16: 443
-     * (ideal 418); 256 spp 1: 39.2, 2: 37.1, 4: 41.8, 8: 42.6 (ideal 27.0).  Round 4's rule (tiles, not workgroups; 64 samples)
-     * gave 2 and 4. */
-    want = 30ull * 4ull * 4ull * (uint64_t)prop.multiProcessorCount;
-  }
-  else
-  {
-    /* aim for >= 20 workgroups per resident slot (5 per CU), so the last, partly filled round
-     * of the launch is a small fraction of it.  (One rank's share of the headline frame at
-     * N = 8 / 4 / 2, ms by chunks: 2: 30.0, 4: 29.3, 6: 29.4, 8: 29.6, 16: 30.9 / 1: 59.1, 2: 57.7, 4: 57.5 / 1: 114.7, 2: 113.4.) */
-    want = 20ull * 5ull * (uint64_t)prop.multiProcessorCount;
-  }
-  /* a chunk keeps >= 128 samples (a workgroup's fixed costs -- staging, keys, culling, the resolve pass -- against its pool: config 3's
-   * share at N = 8, 256 spp, ms by chunks 1: 2.63, 2: 2.61, 4: 2.70, 8: 3.01); the M_REFRACTION forms >= 64 (a refractive sample
-   * is two to three times the rays: the glass mesh's share at N = 8, 256 spp 2: 48.8, 4: 45.9, 8: 46.9) */
-  min_chunk_samples = plan.windowed ? 64 : 128;
-  uint64_t chunks = (want + tile_count - 1) / tile_count;
-  const uint64_t cap = (uint64_t)samples / min_chunk_samples;
-  if (chunks > cap) chunks = cap;
-  if (chunks > 16) chunks = 16;
-  if (chunks < need) chunks = need;
-  return chunks < 1 ? 1u : (uint32_t)chunks;
-}
-
 /* bvh_probe's bounding sphere of the triangles for one near_R: the thresholds of a bounding entry of the flat
  * filter in its compare form, widened exactly as pt_build_filter widens them (e = 2^-24, A = |c| + near_R:
  * |tca32 - tca| <= 6.2 e A, |d2_32 - d2| <= 20.5 e A^2 for origins within near_R; the conversions to fp32 are
  * inside the (1 + k e) factors).  Non-finite or overflowing values give thresholds that keep every ray. */
-static void mesh_bound_for(const RtHipScene *scene, double near_R, float out[5])
+void mesh_bound_for(const RtHipScene *scene, double near_R, float out[5])
 {
   const float inf = std::numeric_limits<float>::infinity();
   out[0] = out[1] = out[2] = 0.f;
@@ -1318,7 +1120,7 @@ static void mesh_bound_for(const RtHipScene *scene, double near_R, float out[5])
  * tol, W >= r2_hi' - r^2 (pt_sign_widen_total of pt_device.h, the very function pt_build_filter widens by, x 1.001), E = 28 e A^2 + 6 e | |c|^2 -
  * r^2 |:  qmin = (r / 16)^2 + W + E,  tmin = 2 (tol + 11.2 e A),  delta = 1.5 max (22.4 e A + 8 (W + E) / r).
  * Anything non-finite or implausible switches the pruning off. */
-static void big_prune_for(const RtHipScene *scene, double near_R, double filt_shift, PtLaunch &L)
+void big_prune_for(const RtHipScene *scene, double near_R, double filt_shift, PtLaunch &L)
 {
   L.big_pairs = 0;
   L.big_delta = L.big_tmin = 0.f;
@@ -1375,7 +1177,7 @@ static void big_prune_for(const RtHipScene *scene, double near_R, double filt_sh
  * Never below 1e-3; scenes so large that mu reaches 1 simply never skip a walk.  D holds for rays whose hit
  * distance is at most 2 near_R: then |o - v0| <= 1.0001 x that + the facet's size as well; trace_step drops the
  * facet's mark for any other (a bounce that came in from a far point of a wall-sized sphere, say). */
-static double hull_margin_for(const RtHipScene *scene, double near_R)
+double hull_margin_for(const RtHipScene *scene, double near_R)
 {
   if (!scene->hull_flags || !(near_R < 1e150))
     return 2.0; /* no ray has m . d > 2 */
@@ -1384,15 +1186,9 @@ static double hull_margin_for(const RtHipScene *scene, double near_R)
   return std::fmax(1e-3, 4.0 * (tau + delta) / 1e-8);
 }
 
-int rt_hip_render_tiles(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params,
-                        float *d_tiles_rgb, uint8_t *d_tiles_rgb8, uint64_t *d_stats, void *stream)
-{
-  return rt_hip_render_tiles_chunked(scene, camera, params, 1, nullptr, d_tiles_rgb, d_tiles_rgb8, d_stats, stream);
-}
-
 /* What a launch of rt_hip_render_tiles_chunked and an accumulation (rt_hip_accum_create) have in common before the plan: the
  * parameters checked, and the launch's scene- and camera-dependent fields.  *empty: no tile to render (not an error). */
-static int launch_prepare(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, PtLaunch &L, bool *empty)
+int launch_prepare(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, PtLaunch &L, bool *empty)
 {
   const int rc = check_params(params);
   if (rc)
@@ -1477,7 +1273,7 @@ static int launch_prepare(const RtHipScene *scene, const RtHipCamera *camera, co
 }
 
 /* ... and, with the scene's device current: the device's status word and the parked-walk workspace */
-static int launch_device_state(const RtHipScene *scene, PtLaunch &L)
+int launch_device_state(const RtHipScene *scene, PtLaunch &L)
 {
   const bool cast_ray = L.integrator == 1u;
   const int rc = status_word_for(scene->device, &L.status);
@@ -1503,432 +1299,69 @@ static int launch_device_state(const RtHipScene *scene, PtLaunch &L)
   return RT_HIP_OK;
 }
 
-int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params,
-                                uint32_t sample_chunks, void *d_workspace, float *d_tiles_rgb,
-                                uint8_t *d_tiles_rgb8, uint64_t *d_stats, void *stream)
+/* What a launch of `scene` asks the plan (pt_kernel.hip, pt_plan_launch).  wide_pend_ok starts out true: who knows that the wide
+ * pending-ray pool cannot be had says so afterwards. */
+PtPlanAsk ask_for(const RtHipScene *scene, uint32_t integrator, int32_t samples, int32_t max_depth, uint32_t sample_chunks,
+                  bool have_chunk_ws, uint32_t tile_count, bool have_park_ws)
 {
-  if (!scene || !camera || !d_tiles_rgb)
-    return fail(RT_HIP_EINVAL, "scene, camera and d_tiles_rgb are required");
-  if (sample_chunks < 1 || (params && (int64_t)sample_chunks > params->samples))
-    return fail(RT_HIP_EINVAL, "sample_chunks must be in [1, samples]");
-  if (sample_chunks > 1 && !d_workspace)
-    return fail(RT_HIP_EINVAL, "sample_chunks > 1 needs a workspace of rt_hip_chunk_workspace_bytes(tile_count)");
-  PtLaunch L;
-  bool empty = false;
-  int rc = launch_prepare(scene, camera, params, L, &empty);
-  if (rc || empty)
-    return rc;
-  L.acc_ws = static_cast<unsigned long long *>(d_workspace);
-  L.tiles_rgb = d_tiles_rgb;
-  L.tiles_rgb8 = d_tiles_rgb8;
-  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  rc = launch_device_state(scene, L);
-  if (rc)
-    return rc;
-  /* ---- which kernel, how many sample chunks it runs, which pools it needs: the plan (pt_kernel.hip, pt_plan_launch) ---- */
-  PtPlanAsk ask = {.integrator = L.integrator, .samples = params->samples, .max_depth = params->max_depth, .max_emission = scene->max_emission,
-                   .sample_chunks = sample_chunks, .have_chunk_ws = d_workspace != nullptr, .tile_count = params->tile_count,
-                   .have_park_ws = L.park_ws != nullptr, .wide_pend_ok = true};
-  PtPlan plan = pt_plan_launch(L.scene, ask);
-  L.sample_chunks = plan.sample_chunks;
-  L.acc_windows = plan.windowed ? 1u : 0u;
-  if ((uint64_t)L.tile_count * L.sample_chunks > 0x7FFFFFFFull)
-    return fail(RT_HIP_EINVAL, "tile_count x sample_chunks exceeds the grid limit");
-  size_t slot = 0;
-  rc = acquire_tables(scene, L.near_R, static_cast<hipStream_t>(stream), &L.scene.filt, &L.scene.bvh_nodes, &slot);
-  if (rc)
-    return rc;
-  hipError_t e;
-  if (plan.pend_entries)
-  {
-    std::lock_guard<std::mutex> pend_lock(g_pend_mutex);
-    rc = pend_pool_for(scene->device, plan.pend_entries, plan.pend_columns, L);
-    /* the parked-walk refraction kernels want four times the stacks per slot (1.2 GB at depth 5, 5.7 GB at 32): where that
-     * cannot be had, the pool of the other kernels will do -- planned again, the table's fit = NO row names the static kernel
-     * of the family */
-    if (rc == RT_HIP_ENOMEM && plan.pend_columns > PT_PEND_COLUMNS)
-    {
-      ask.wide_pend_ok = false;
-      plan = pt_plan_launch(L.scene, ask);
-      L.sample_chunks = plan.sample_chunks;
-      L.acc_windows = plan.windowed ? 1u : 0u;
-      rc = plan.pend_entries ? pend_pool_for(scene->device, plan.pend_entries, plan.pend_columns, L) : RT_HIP_OK;
-    }
-    if (rc)
-    {
-      release_tables(scene, slot, static_cast<hipStream_t>(stream));
-      return rc;
-    }
-    e = pt_launch_render(L, static_cast<hipStream_t>(stream), plan.kernel);
-  }
-  else
-    e = pt_launch_render(L, static_cast<hipStream_t>(stream), plan.kernel);
-  release_tables(scene, slot, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_kernel_name_of(plan.kernel), hipGetErrorString(e));
-  g_last_kernel = plan.kernel;
-  return RT_HIP_OK;
+  return {.integrator = integrator, .samples = samples, .max_depth = max_depth, .max_emission = scene->max_emission,
+          .sample_chunks = sample_chunks, .have_chunk_ws = have_chunk_ws, .tile_count = tile_count, .have_park_ws = have_park_ws,
+          .wide_pend_ok = true};
 }
 
-/* ---- progressive rendering: one frame accumulated over passes (rt_hip.h, RtHipAccum) ----------------------------------------
- * The plan is made once, for the whole budget, and every pass launches its member in accumulation mode (PtLaunch.sample_first,
- * acc_keep): the CHUNKS members add exact integer sums (fixed point, or windowed words) to the tile records in `sums`, the static
- * body continues its lanes' fp64 slice sums there.  A pass never re-plans, and the pools the plan needs are held here. */
-struct RtHipAccum
+/* Which kernel, how many sample chunks it runs, which pools it needs: the plan of the prepared launch L, and the pending-ray pool
+ * it asks for, taken through take_pool(entries, columns, L).  The parked-walk refraction kernels want four times the stacks per
+ * slot (1.2 GB at depth 5, 5.7 GB at 32): where that cannot be had, the pool of the other kernels will do -- planned again, the
+ * table's fit = NO row names the static kernel of the family.  Sets L.sample_chunks and L.acc_windows. */
+template <class PoolFn>
+int plan_launch(const RtHipScene *scene, PtLaunch &L, uint32_t sample_chunks, bool have_chunk_ws, PoolFn take_pool, PtPlan *out)
 {
-  const RtHipScene *scene = nullptr;
-  PtLaunch L;                  /* the launch as planned at create; a pass sets samples, sample_first, sample_chunks, stats */
-  int kernel = -1;
-  bool takes_chunks = false;   /* CHUNKS member: sums are tile records (pt_resolve_tiles); else slice sums (pt_resolve_slices) */
-  int32_t budget = 0, done = 0;
-  int32_t plan_spc = 0;        /* the plan's samples per chunk: no workgroup of a pass gets more */
-  void *sums = nullptr;
-  char *pend = nullptr;        /* the accumulation's own pending-ray pool (pend_pool_own), or nullptr */
-  /* adaptive sampling, allocated at the first freeze (accum_adapt_state) in one block: per slot the count it froze at (0: live),
-   * the live slots in ascending order, their number, the keep mask of a freeze */
-  uint32_t *tile_samples = nullptr, *slot_list = nullptr, *d_live_count = nullptr;
-  uint8_t *keep = nullptr;
-  uint32_t live_count = 0;     /* host copy; meaningful once tile_samples exists */
-  bool any_frozen = false;
-  bool broken = false;         /* a freeze failed after the device had rewritten the list: the host's count is stale, nothing may launch */
-  float *adapt_buf = nullptr;  /* rt_hip_accum_run_adaptive: two compact resolves and the error per slot */
-};
+  PtPlanAsk ask = ask_for(scene, L.integrator, L.samples, L.max_depth, sample_chunks, have_chunk_ws, L.tile_count, L.park_ws != nullptr);
+  PtPlan plan = pt_plan_launch(L.scene, ask);
+  int rc = plan.pend_entries ? take_pool(plan.pend_entries, plan.pend_columns, L) : RT_HIP_OK;
+  if (rc == RT_HIP_ENOMEM && plan.pend_columns > PT_PEND_COLUMNS)
+  {
+    ask.wide_pend_ok = false;
+    plan = pt_plan_launch(L.scene, ask);
+    rc = plan.pend_entries ? take_pool(plan.pend_entries, plan.pend_columns, L) : RT_HIP_OK;
+  }
+  L.sample_chunks = plan.sample_chunks;
+  L.acc_windows = plan.windowed ? 1u : 0u;
+  *out = plan;
+  return rc;
+}
 
-static void accum_free(RtHipAccum *a)
+void accum_free(RtHipAccum *a)
 {
   if (!a)
     return;
-  if (a->sums || a->pend)
-  {
-    DeviceScope scope(a->scene->device);
-    (void)hipDeviceSynchronize(); /* no pass may still be using them */
-    if (a->sums)
-      (void)hipFree(a->sums);
-    if (a->pend)
-      (void)hipFree(a->pend);
-    if (a->tile_samples)
-      (void)hipFree(a->tile_samples);
-    if (a->adapt_buf)
-      (void)hipFree(a->adapt_buf);
-  }
+  DeviceScope scope(a->scene->device);
+  (void)hipDeviceSynchronize(); /* no pass may still be using what it owns */
   delete a;
 }
 
-int rt_hip_accum_create(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, RtHipAccum **out)
-{
-  if (out)
-    *out = nullptr;
-  if (!scene || !camera || !params || !out)
-    return fail(RT_HIP_EINVAL, "scene, camera, params and out are required");
-  if (params->samples < 1)
-    return fail(RT_HIP_EINVAL, "the sample budget (params->samples) must be >= 1");
-  PtLaunch L;
-  bool empty = false;
-  int rc = launch_prepare(scene, camera, params, L, &empty);
-  if (rc)
-    return rc;
-  if (empty)
-    return fail(RT_HIP_EINVAL, "an accumulation needs tile_count >= 1");
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  rc = launch_device_state(scene, L);
-  if (rc)
-    return rc;
-  /* the plan of a one-shot launch of the whole budget with a chunk workspace and the suggested chunks: the same member, the same
-   * sum form, the same fallback rows; the fixed-point scale is the budget's (launch_prepare) */
-  const uint32_t chunks = rt_hip_suggest_chunks_depth(scene, params->tile_count, params->samples, params->max_depth);
-  PtPlanAsk ask = {.integrator = L.integrator, .samples = params->samples, .max_depth = params->max_depth, .max_emission = scene->max_emission,
-                   .sample_chunks = chunks, .have_chunk_ws = true, .tile_count = params->tile_count,
-                   .have_park_ws = L.park_ws != nullptr, .wide_pend_ok = true};
-  PtPlan plan = pt_plan_launch(L.scene, ask);
-  if (plan.kernel < 0)
-    return fail(RT_HIP_ERUNTIME, "no kernel for this scene"); /* unreachable (pt_pick_kernel) */
-  RtHipAccum *a = new (std::nothrow) RtHipAccum();
-  if (!a)
-    return fail(RT_HIP_ENOMEM, "accumulation: out of host memory");
-  a->scene = scene;
-  if (plan.pend_entries)
-  {
-    rc = pend_pool_own(plan.pend_entries, plan.pend_columns, L, &a->pend);
-    if (rc == RT_HIP_ENOMEM && plan.pend_columns > PT_PEND_COLUMNS)
-    { /* as rt_hip_render_tiles_chunked: without the wide pool, planned again (the fit = NO row) */
-      ask.wide_pend_ok = false;
-      plan = pt_plan_launch(L.scene, ask);
-      rc = plan.pend_entries ? pend_pool_own(plan.pend_entries, plan.pend_columns, L, &a->pend) : RT_HIP_OK;
-    }
-    if (rc)
-    {
-      accum_free(a);
-      return rc;
-    }
-  }
-  a->kernel = plan.kernel;
-  a->takes_chunks = pt_kernel_takes_chunks(plan.kernel);
-  a->budget = params->samples;
-  a->plan_spc = (int32_t)(((int64_t)params->samples + plan.sample_chunks - 1) / plan.sample_chunks);
-  L.acc_windows = plan.windowed ? 1u : 0u;
-  L.acc_keep = 1u;
-  const size_t bytes = a->takes_chunks ? (size_t)L.tile_count * (plan.windowed ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long)
-                                       : (size_t)L.tile_count * 3u * PT_BLOCK * sizeof(double);
-  hipError_t e = hipMalloc(&a->sums, bytes);
-  if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
-    a->sums = nullptr;
-    accum_free(a);
-    return fail(RT_HIP_ENOMEM, "accumulation sums (%zu MB): %s", bytes >> 20, hipGetErrorString(e));
-  }
-  e = hipMemset(a->sums, 0, bytes);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(nullptr); /* zero before a pass on any stream adds to them */
-  if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
-    accum_free(a);
-    return fail(RT_HIP_ERUNTIME, "accumulation sums: %s", hipGetErrorString(e));
-  }
-  if (a->takes_chunks)
-    L.acc_ws = static_cast<unsigned long long *>(a->sums);
-  else
-    L.slice_ws = static_cast<double *>(a->sums);
-  a->L = L;
-  *out = a;
-  return RT_HIP_OK;
-}
-
-int rt_hip_accum_add(RtHipAccum *a, int32_t samples, uint64_t *d_stats, void *stream)
-{
-  if (!a)
-    return fail(RT_HIP_EINVAL, "accumulation is NULL");
-  if (samples <= 0 || samples > a->budget - a->done)
-    return fail(RT_HIP_EINVAL, "a pass takes 1 .. %d samples (budget %d, %d done), not %d", a->budget - a->done, a->budget, a->done, samples);
-  if (a->broken)
-    return fail(RT_HIP_ERUNTIME, "the accumulation is unusable: an earlier freeze failed on the device");
-  const RtHipScene *scene = a->scene;
-  PtLaunch L = a->L;
-  L.samples = samples;
-  L.sample_first = (uint32_t)a->done;
-  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
-  L.sample_chunks = 1u;
-  /* with frozen tiles the pass renders the live slots only, and the chunks are planned for that many tiles */
-  const uint32_t pass_tiles = a->any_frozen ? a->live_count : L.tile_count;
-  if (pass_tiles == 0u)
-    return RT_HIP_OK; /* every tile is frozen: nothing is rendered and `done` stays */
-  if (a->any_frozen)
-  {
-    L.slot_list = a->slot_list;
-    L.slot_count = a->live_count;
-  }
-  if (a->takes_chunks)
-  { /* no workgroup gets more samples than the plan's chunks have (that is what the windowed words are sized by), and a small
-     * tile count gets the chunks the suggestion asks for.  Capacity: every chunk adds at most one piece below 2^32 to a word of
-     * the tile records, and every chunk has at least one sample, so over all passes a word takes at most budget < 2^31 pieces */
-    uint64_t chunks = ((uint64_t)samples + (uint64_t)a->plan_spc - 1u) / (uint64_t)a->plan_spc;
-    chunks = std::max<uint64_t>(chunks, rt_hip_suggest_chunks_depth(scene, pass_tiles, samples, L.max_depth));
-    chunks = std::min<uint64_t>(chunks, (uint64_t)samples);
-    if ((uint64_t)pass_tiles * chunks > 0x7FFFFFFFull)
-      return fail(RT_HIP_EINVAL, "tile_count x sample_chunks exceeds the grid limit");
-    L.sample_chunks = (uint32_t)chunks;
-  }
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  size_t slot = 0;
-  int rc = acquire_tables(scene, L.near_R, static_cast<hipStream_t>(stream), &L.scene.filt, &L.scene.bvh_nodes, &slot);
-  if (rc)
-    return rc;
-  const hipError_t e = pt_launch_render(L, static_cast<hipStream_t>(stream), a->kernel);
-  release_tables(scene, slot, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s pass: %s", pt_kernel_name_of(a->kernel), hipGetErrorString(e));
-  a->done += samples;
-  return RT_HIP_OK;
-}
-
-int rt_hip_accum_add_host(RtHipAccum *a, int32_t samples, uint64_t *h_stats, double *kernel_seconds)
-{
-  if (kernel_seconds)
-    *kernel_seconds = 0;
-  if (!a)
-    return fail(RT_HIP_EINVAL, "accumulation is NULL");
-  DeviceScope scope(a->scene->device);
-  HIP_TRY(scope.status);
-  unsigned long long *d_stats = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(hipMalloc(&d_stats, RT_HIP_NSTATS * sizeof *d_stats));
-  hipError_t e = hipMemset(d_stats, 0, RT_HIP_NSTATS * sizeof *d_stats);
-  if (e == hipSuccess)
-    e = hipEventCreate(&ev[0]);
-  if (e == hipSuccess)
-    e = hipEventCreate(&ev[1]);
-  if (e == hipSuccess)
-    e = hipEventRecord(ev[0], nullptr);
-  int rc = RT_HIP_OK;
-  if (e == hipSuccess)
-  {
-    rc = rt_hip_accum_add(a, samples, reinterpret_cast<uint64_t *>(d_stats), nullptr);
-    if (!rc)
-      e = hipEventRecord(ev[1], nullptr);
-    if (!rc && e == hipSuccess)
-      e = hipEventSynchronize(ev[1]);
-  }
-  unsigned long long st[RT_HIP_NSTATS] = {0, 0, 0, 0};
-  if (!rc && e == hipSuccess)
-    e = hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost);
-  float ms = 0.f;
-  if (!rc && e == hipSuccess)
-    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  for (hipEvent_t x : ev)
-    if (x)
-      (void)hipEventDestroy(x);
-  (void)hipFree(d_stats);
-  if (rc)
-    return rc;
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "accumulation pass: %s", hipGetErrorString(e));
-  if (h_stats)
-    for (int k = 0; k < RT_HIP_NSTATS; k++)
-      h_stats[k] += st[k];
-  if (kernel_seconds)
-    *kernel_seconds = 1e-3 * (double)ms;
-  return RT_HIP_OK;
-}
-
-int rt_hip_accum_resolve(const RtHipAccum *a, float *d_tiles_rgb, uint8_t *d_tiles_rgb8, void *stream)
-{
-  if (!a || !d_tiles_rgb)
-    return fail(RT_HIP_EINVAL, "accumulation and d_tiles_rgb are required");
-  if (a->done < 1)
-    return fail(RT_HIP_EINVAL, "the accumulation holds no sample yet");
-  if (a->broken)
-    return fail(RT_HIP_ERUNTIME, "the accumulation is unusable: an earlier freeze failed on the device");
-  PtLaunch L = a->L;
-  L.samples = a->done;
-  L.tiles_rgb = d_tiles_rgb;
-  L.tiles_rgb8 = d_tiles_rgb8;
-  DeviceScope scope(a->scene->device);
-  HIP_TRY(scope.status);
-  const hipError_t e = pt_launch_resolve(L, a->any_frozen ? a->tile_samples : nullptr, static_cast<hipStream_t>(stream), a->kernel);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "accumulation resolve: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
-}
-
-int rt_hip_accum_read_image(const RtHipAccum *a, float *h_rgb, uint8_t *h_rgb8)
-{
-  if (!a || (!h_rgb && !h_rgb8))
-    return fail(RT_HIP_EINVAL, "accumulation and an output are required");
-  const PtLaunch &L = a->L;
-  const size_t tile_vals = (size_t)L.tile_count * PT_TILE_PIXELS * 3, img_vals = (size_t)L.width * L.height * 3;
-  DeviceScope scope(a->scene->device);
-  HIP_TRY(scope.status);
-  HIP_TRY(hipDeviceSynchronize()); /* the passes, on whatever stream they ran */
-  char *buf = nullptr;
-  const size_t bytes = tile_vals * 5 + img_vals * 5; /* tiles f32 + u8, image f32 + u8 */
-  HIP_TRY(hipMalloc(&buf, bytes));
-  float *tiles = reinterpret_cast<float *>(buf), *img = reinterpret_cast<float *>(buf + tile_vals * 5);
-  uint8_t *tiles8 = reinterpret_cast<uint8_t *>(buf + tile_vals * 4), *img8 = reinterpret_cast<uint8_t *>(buf + tile_vals * 5 + img_vals * 4);
-  int rc = rt_hip_accum_resolve(a, tiles, tiles8, nullptr);
-  hipError_t e = hipSuccess;
-  if (!rc)
-  {
-    e = hipMemset(img, 0, img_vals * 5);
-    if (e == hipSuccess)
-      e = pt_launch_untile(tiles, tiles8, L.width, L.height, L.tile_first, L.tile_stride, L.tile_count, img, img8, nullptr);
-    if (e == hipSuccess && h_rgb)
-      e = hipMemcpy(h_rgb, img, img_vals * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_rgb8)
-      e = hipMemcpy(h_rgb8, img8, img_vals, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(buf);
-  if (rc)
-    return rc;
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "accumulation read: %s", hipGetErrorString(e));
-  uint32_t flags = 0;
-  rc = status_take(a->scene->device, &flags);
-  return rc ? rc : status_to_error(flags);
-}
-
-int32_t rt_hip_accum_samples(const RtHipAccum *a) { return a ? a->done : 0; }
-
-const char *rt_hip_accum_kernel(const RtHipAccum *a) { return a ? pt_kernel_name_of(a->kernel) : ""; }
-
-void rt_hip_accum_destroy(RtHipAccum *a) { accum_free(a); }
-
-/* ---- adaptive sampling: the error estimate, the freeze, the driver (rt_hip.h) ------------------------------------------------ */
-
-int rt_hip_tile_error(const float *d_cur, const float *d_prev, int32_t width, int32_t height, uint32_t tile_first, uint32_t tile_stride,
-                      uint32_t tile_count, float *d_error, void *stream)
-{
-  if (!d_cur || !d_prev || !d_error)
-    return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error are required");
-  if (width < 1 || height < 1)
-    return fail(RT_HIP_EINVAL, "width and height must be >= 1");
-  if (tile_count == 0)
-    return RT_HIP_OK;
-  if (tile_stride == 0 && tile_count > 1)
-    return fail(RT_HIP_EINVAL, "tile_stride must be >= 1");
-  const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
-  if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
-    return fail(RT_HIP_EINVAL, "tile range outside the image");
-  if (usable_devices() < 1)
-    return fail(RT_HIP_ENODEV, "no usable HIP device");
-  hipPointerAttribute_t attr = {};
-  int on = -1;
-  for (const void *ptr : {static_cast<const void *>(d_cur), static_cast<const void *>(d_prev), static_cast<const void *>(d_error)})
-  {
-    if (hipPointerGetAttributes(&attr, ptr) != hipSuccess || attr.type != hipMemoryTypeDevice)
-    {
-      (void)hipGetLastError();
-      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be device memory");
-    }
-    if (on >= 0 && attr.device != on)
-      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be on one device (%d, %d)", on, attr.device);
-    on = attr.device;
-  }
-  DeviceScope scope(attr.device);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
-  const hipError_t e = pt_launch_tile_error(d_cur, d_prev, width, height, tile_first, tile_stride, tile_count, d_error, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "tile error: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
-}
-
 /* the freeze state of an accumulation, made at its first freeze: every slot live */
-static int accum_adapt_state(RtHipAccum *a)
+int accum_adapt_state(RtHipAccum *a)
 {
   if (a->tile_samples)
     return RT_HIP_OK;
   const size_t n = a->L.tile_count;
   const size_t bytes = (2 * n + 1) * sizeof(uint32_t) + n;
-  uint32_t *buf = nullptr;
-  hipError_t e = hipMalloc(&buf, bytes);
+  DeviceBuffer buf;
+  const hipError_t e = buf.alloc(bytes);
   if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
     return fail(RT_HIP_ENOMEM, "freeze state (%zu KB): %s", bytes >> 10, hipGetErrorString(e));
-  }
-  e = hipMemset(buf, 0, bytes);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
-    (void)hipFree(buf);
-    return fail(RT_HIP_ERUNTIME, "freeze state: %s", hipGetErrorString(e));
-  }
-  a->tile_samples = buf;
-  a->slot_list = buf + n;
-  a->d_live_count = buf + 2 * n;
-  a->keep = reinterpret_cast<uint8_t *>(buf + 2 * n + 1);
+  HIP_TRY(hipMemset(buf.ptr, 0, bytes));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  a->tile_samples = std::move(buf);
+  a->slot_list = a->tile_samples.at<uint32_t>() + n;
+  a->d_live_count = a->slot_list + n;
+  a->keep = reinterpret_cast<uint8_t *>(a->d_live_count + 1);
   a->live_count = (uint32_t)n;
   return RT_HIP_OK;
 }
 
-static int accum_freeze(RtHipAccum *a, const float *d_error, const uint8_t *h_keep, double threshold, uint32_t dilate, uint32_t *live_count,
+int accum_freeze(RtHipAccum *a, const float *d_error, const uint8_t *h_keep, double threshold, uint32_t dilate, uint32_t *live_count,
                         void *stream)
 {
   if (live_count)
@@ -1960,7 +1393,7 @@ static int accum_freeze(RtHipAccum *a, const float *d_error, const uint8_t *h_ke
   if (!d_error)
     e = hipMemcpyAsync(a->keep, h_keep, L.tile_count, hipMemcpyHostToDevice, st);
   if (e == hipSuccess)
-    e = pt_launch_tile_freeze(d_error, threshold, (int)dilate, a->keep, a->tile_samples, L.width, L.height, L.tile_first, L.tile_stride,
+    e = pt_launch_tile_freeze(d_error, threshold, (int)dilate, a->keep, a->tile_samples.at<uint32_t>(), L.width, L.height, L.tile_first, L.tile_stride,
                               L.tile_count, (uint32_t)a->done, a->slot_list, a->d_live_count, st);
   uint32_t n = 0;
   if (e == hipSuccess)
@@ -1979,117 +1412,43 @@ static int accum_freeze(RtHipAccum *a, const float *d_error, const uint8_t *h_ke
   return RT_HIP_OK;
 }
 
-int rt_hip_accum_freeze(RtHipAccum *a, const float *d_error, double threshold, uint32_t dilate, uint32_t *live_count, void *stream)
+/* the passes and checkpoints of rt_hip_accum_run_adaptive.  *seconds grows by every timed piece that ran, also when a later one
+ * fails or the caller cancels. */
+int adaptive_passes(RtHipAccum *a, const RtHipAdaptParams *p, uint64_t *h_stats,
+                    int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles), void *user, double *seconds)
 {
-  if (a && !d_error)
-    return fail(RT_HIP_EINVAL, "d_error is required (rt_hip_accum_freeze_mask takes a host mask)");
-  return accum_freeze(a, d_error, nullptr, threshold, dilate, live_count, stream);
-}
-
-int rt_hip_accum_freeze_mask(RtHipAccum *a, const uint8_t *h_keep, uint32_t *live_count, void *stream)
-{
-  if (a && !h_keep)
-    return fail(RT_HIP_EINVAL, "h_keep is required");
-  return accum_freeze(a, nullptr, h_keep, 0.0, 0u, live_count, stream);
-}
-
-int rt_hip_accum_tile_samples(const RtHipAccum *a, uint32_t *h_counts)
-{
-  if (!a || !h_counts)
-    return fail(RT_HIP_EINVAL, "accumulation and h_counts are required");
-  const uint32_t n = a->L.tile_count;
-  if (a->tile_samples)
-  {
-    DeviceScope scope(a->scene->device);
-    HIP_TRY(scope.status);
-    /* a freeze has waited for its stream before it returned: the counts are at rest, and a copy on the null stream is enough */
-    HIP_TRY(hipMemcpy(h_counts, a->tile_samples, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  }
-  for (uint32_t k = 0; k < n; k++)
-    if (!a->tile_samples || h_counts[k] == 0u)
-      h_counts[k] = (uint32_t)a->done; /* a live slot holds every sample done so far */
-  return RT_HIP_OK;
-}
-
-uint32_t rt_hip_accum_live_tiles(const RtHipAccum *a) { return !a ? 0u : (a->tile_samples ? a->live_count : a->L.tile_count); }
-
-void rt_hip_adapt_defaults(RtHipAdaptParams *p)
-{
-  if (!p)
-    return;
-  p->min_samples = 16;
-  p->dilate = 1u;
-  p->threshold = 0.02;
-}
-
-int rt_hip_adapt_schedule(int32_t budget, int32_t min_samples, int32_t *targets, int32_t cap)
-{
-  if (budget < 1 || min_samples < 1)
-    return 0;
-  int n = 0;
-  const int64_t h = std::max<int64_t>(1, min_samples / 2);
-  for (int64_t t = h;; t *= 2)
-  {
-    const int32_t target = (int32_t)std::min<int64_t>(t, budget);
-    if (targets && n < cap)
-      targets[n] = target;
-    n++;
-    if (target == budget)
-      break;
-  }
-  return n;
-}
-
-int rt_hip_accum_run_adaptive(RtHipAccum *a, const RtHipAdaptParams *p, uint64_t *h_stats, double *kernel_seconds,
-                              int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles), void *user)
-{
-  if (kernel_seconds)
-    *kernel_seconds = 0;
-  if (!a || !p)
-    return fail(RT_HIP_EINVAL, "accumulation and params are required");
-  if (p->min_samples < 1 || p->dilate > 2u || p->threshold != p->threshold)
-    return fail(RT_HIP_EINVAL, "adaptive parameters: min_samples >= 1, dilate 0 .. 2, threshold not NaN");
-  if (a->done != 0)
-    return fail(RT_HIP_EINVAL, "the driver starts from an empty accumulation (%d samples done)", a->done);
   const PtLaunch &L = a->L;
-  DeviceScope scope(a->scene->device);
-  HIP_TRY(scope.status);
   const size_t tile_vals = (size_t)L.tile_count * PT_TILE_PIXELS * 3;
   const bool estimate = p->threshold > 0.0;
   if (estimate && !a->adapt_buf)
   {
-    const hipError_t e = hipMalloc(&a->adapt_buf, (2 * tile_vals + L.tile_count) * sizeof(float));
+    const hipError_t e = a->adapt_buf.alloc((2 * tile_vals + L.tile_count) * sizeof(float));
     if (e != hipSuccess)
-    {
-      (void)hipGetLastError();
-      a->adapt_buf = nullptr;
       return fail(RT_HIP_ENOMEM, "adaptive buffers: %s", hipGetErrorString(e));
-    }
   }
-  float *prev = a->adapt_buf, *cur = a->adapt_buf + tile_vals, *err = a->adapt_buf + 2 * tile_vals;
+  float *prev = a->adapt_buf.at<float>(), *cur = prev + tile_vals, *err = prev + 2 * tile_vals;
   int32_t targets[32];
   const int n_targets = rt_hip_adapt_schedule(a->budget, p->min_samples, targets, 32);
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipError_t e = hipEventCreate(&ev[0]);
-  if (e == hipSuccess)
-    e = hipEventCreate(&ev[1]); /* (a failure leaves through the common exit below: nothing has been rendered) */
-  int rc = RT_HIP_OK;
-  double seconds = 0;
-  for (int i = 0; i < n_targets && !rc && e == hipSuccess; i++)
+  EventPair timer;
+  HIP_TRY(timer.create());
+  for (int i = 0; i < n_targets; i++)
   {
-    double pass_seconds = 0;
     if (targets[i] > a->done)
-      rc = rt_hip_accum_add_host(a, targets[i] - a->done, h_stats, &pass_seconds);
-    seconds += pass_seconds;
-    if (rc || targets[i] == a->budget)
+    {
+      double pass_seconds = 0;
+      const int rc = rt_hip_accum_add_host(a, targets[i] - a->done, h_stats, &pass_seconds);
+      *seconds += pass_seconds;
+      if (rc)
+        return rc;
+    }
+    if (targets[i] == a->budget)
       break; /* the last pass is followed by no estimate */
     uint32_t live = rt_hip_accum_live_tiles(a);
     if (estimate)
     { /* (a threshold <= 0 freezes nothing: no resolve, no estimate, the passes alone) */
-      e = hipEventRecord(ev[0], nullptr);
-      if (e == hipSuccess)
-        rc = rt_hip_accum_resolve(a, i == 0 ? prev : cur, nullptr, nullptr);
-      if (i > 0 && !rc && e == hipSuccess)
+      HIP_TRY(timer.start(nullptr));
+      int rc = rt_hip_accum_resolve(a, i == 0 ? prev : cur, nullptr, nullptr);
+      if (i > 0 && !rc)
       {
         /* (every slot is estimated, the frozen ones too: both resolves divide a frozen slot's unchanged sums by its own count, so
          * cur == prev there, its error is +0.0 and it never votes in the dilation) */
@@ -2098,273 +1457,49 @@ int rt_hip_accum_run_adaptive(RtHipAccum *a, const RtHipAdaptParams *p, uint64_t
           rc = rt_hip_accum_freeze(a, err, p->threshold, p->dilate, &live, nullptr);
         std::swap(prev, cur);
       }
-      if (!rc && e == hipSuccess)
-        e = hipEventRecord(ev[1], nullptr);
-      if (!rc && e == hipSuccess)
-        e = hipEventSynchronize(ev[1]);
+      if (rc)
+        return rc;
+      HIP_TRY(timer.stop(nullptr));
+      HIP_TRY(timer.wait());
       float ms = 0.f;
-      if (!rc && e == hipSuccess)
-        e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-      seconds += 1e-3 * (double)ms; /* the checkpoint's own timer, added to the passes' (rt_hip_accum_add_host) */
+      HIP_TRY(timer.elapsed_ms(&ms));
+      *seconds += 1e-3 * (double)ms; /* the checkpoint's own timer, added to the passes' (rt_hip_accum_add_host) */
     }
-    if (!rc && e == hipSuccess && i > 0 && on_checkpoint && on_checkpoint(user, a->done, live))
-      rc = fail(RT_HIP_ECANCELLED, "adaptive render cancelled at %d samples", a->done);
-    if (!rc && i > 0 && live == 0u)
+    if (i > 0 && on_checkpoint && on_checkpoint(user, a->done, live))
+      return fail(RT_HIP_ECANCELLED, "adaptive render cancelled at %d samples", a->done);
+    if (i > 0 && live == 0u)
       break;
   }
-  for (hipEvent_t x : ev)
-    if (x)
-      (void)hipEventDestroy(x);
-  if (kernel_seconds)
-    *kernel_seconds = seconds;
-  if (rc)
-    return rc;
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "adaptive render: %s", hipGetErrorString(e));
   return RT_HIP_OK;
 }
 
-int rt_hip_selftest_math(int op, const double *h_a, const double *h_b, double *h_out, size_t n, int device)
-{
-  if (!h_a || !h_b || !h_out || op < 0 || op > 9 || (op == 8 && n < 8) || (op == 9 && n % 8 != 0))
-    return fail(RT_HIP_EINVAL, "bad self-test arguments");
-  if (device < 0 || device >= usable_devices())
-    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
-  if (n == 0)
-    return RT_HIP_OK;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  double *d = nullptr;
-  hipError_t e = hipMalloc(&d, 3 * n * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(d, h_a, n * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + n, h_b, n * sizeof(double), hipMemcpyHostToDevice);
-  /* op 8 accumulates into out, starting from what the caller put there */
-  if (e == hipSuccess) e = op == 8 ? hipMemcpy(d + 2 * n, h_out, n * sizeof(double), hipMemcpyHostToDevice)
-                                   : hipMemset(d + 2 * n, 0, n * sizeof(double));
-  if (e == hipSuccess) e = pt_launch_selftest(op, d, d + n, d + 2 * n, n, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(h_out, d + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "self-test: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
-}
+bool aov_any(const RtHipAov *a) { return a && (a->albedo || a->normal || a->depth || a->object || a->hits); }
 
-int rt_hip_selftest_xcc(uint32_t n_workgroups, uint32_t h_counts[16], int device)
-{
-  if (!h_counts || n_workgroups == 0 || n_workgroups > (1u << 20))
-    return fail(RT_HIP_EINVAL, "bad self-test arguments");
-  if (device < 0 || device >= usable_devices())
-    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  unsigned int *d = nullptr;
-  hipError_t e = hipMalloc(&d, 16 * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMemset(d, 0, 16 * sizeof(unsigned int));
-  if (e == hipSuccess) e = pt_launch_selftest_xcc(d, n_workgroups, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(h_counts, d, 16 * sizeof(unsigned int), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "xcc self-test: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
-}
-
-int rt_hip_selftest_intersect(int kind, const double *h_rays, const double *h_prims, size_t n, double near_R,
-                              uint8_t *h_hit, double *h_tuv, uint64_t *h_keep, int device)
-{
-  if ((kind != 0 && kind != 1) || !h_rays || !h_prims || !h_hit || !h_tuv || !h_keep)
-    return fail(RT_HIP_EINVAL, "bad self-test arguments");
-  if (!(near_R > 0) || !(near_R < 1e15) || n > 0x7FFFFFFFu)
-    return fail(RT_HIP_EINVAL, "near_R must be a positive finite bound, n < 2^31");
-  if (device < 0 || device >= usable_devices())
-    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
-  if (n == 0)
-    return RT_HIP_OK;
-  try
-  {
-    /* the records exactly as rt_hip_scene_create lays them out (same helpers) */
-    const size_t rec = kind == 0 ? 4 : 9;
-    std::vector<double> prims(rec * n), entry(PT_ENTRY_SRC_STRIDE * n);
-    double max_center = 0;
-    for (size_t i = 0; i < n; i++)
-    {
-      double *e = &entry[PT_ENTRY_SRC_STRIDE * i];
-      if (kind == 0)
-      {
-        const double *p = h_prims + 4 * i;
-        if (!(std::fabs(p[3]) >= 1e-100) || !(std::fabs(p[3]) <= 1e17))
-          return fail(RT_HIP_ELIMIT, "sphere %zu: |radius| %g outside [1e-100, 1e17]", i, p[3]);
-        sphere_entry(p, p[3], e);
-        memcpy(&prims[4 * i], e, 4 * sizeof(double));
-      }
-      else
-        triangle_entry(h_prims + 9 * i, h_prims + 9 * i + 3, h_prims + 9 * i + 6, &prims[9 * i], e);
-      if (!(e[4] <= 1e17))
-        return fail(RT_HIP_ELIMIT, "primitive %zu: centre beyond 1e17", i);
-      max_center = std::fmax(max_center, e[4]);
-    }
-    const double filt_shift = 12.0 * 5.9604644775390625e-08 * (max_center + near_R) * (1.0 + 1e-9); /* as rt_hip_render_tiles */
-    const size_t n_blocks = (n + 63) / 64;
-    const size_t filt_bytes = (n_blocks * 32 + 1) * (size_t)PT_FILT_STRIDE * 2 * sizeof(float);
-    const size_t b_rays = 6 * n * 8, b_prims = rec * n * 8, b_entry = entry.size() * 8, b_tuv = 3 * n * 8, b_keep = 3 * n * 8;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_tri32 = kind == 1 ? n * PT_TRI32_STRIDE * sizeof(float) : 0;
-    const size_t o_rays = 0, o_prims = o_rays + pad(b_rays), o_entry = o_prims + pad(b_prims), o_filt = o_entry + pad(b_entry),
-                 o_tri32 = o_filt + pad(filt_bytes), o_tuv = o_tri32 + pad(b_tri32), o_keep = o_tuv + pad(b_tuv),
-                 o_hit = o_keep + pad(b_keep), total = o_hit + pad(n);
-    DeviceScope scope(device);
-    HIP_TRY(scope.status);
-    char *d = nullptr;
-    hipError_t e = hipMalloc(&d, total);
-    if (e != hipSuccess)
-      return fail(RT_HIP_ENOMEM, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
-    e = hipMemset(d + o_filt, 0, filt_bytes);
-    if (e == hipSuccess) e = hipMemcpy(d + o_rays, h_rays, b_rays, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + o_prims, prims.data(), b_prims, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + o_entry, entry.data(), b_entry, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = pt_launch_selftest_intersect(kind, reinterpret_cast<double *>(d + o_rays), reinterpret_cast<double *>(d + o_prims),
-                                       reinterpret_cast<double *>(d + o_entry), reinterpret_cast<float *>(d + o_filt),
-                                       reinterpret_cast<float *>(d + o_tri32), (uint32_t)n, near_R, filt_shift, reinterpret_cast<uint8_t *>(d + o_hit),
-                                       reinterpret_cast<double *>(d + o_tuv), reinterpret_cast<unsigned long long *>(d + o_keep),
-                                       nullptr);
-    if (e == hipSuccess) e = hipMemcpy(h_hit, d + o_hit, n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(h_tuv, d + o_tuv, b_tuv, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(h_keep, d + o_keep, b_keep, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "intersect self-test: %s", hipGetErrorString(e));
-    return RT_HIP_OK;
-  }
-  catch (const std::bad_alloc &)
-  {
-    return fail(RT_HIP_ENOMEM, "host allocation failed in rt_hip_selftest_intersect");
-  }
-}
-
-int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t width, int32_t height,
-                  uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *d_image_rgb,
-                  uint8_t *d_image_rgb8, void *stream)
-{
-  if (width < 1 || height < 1)
-    return fail(RT_HIP_EINVAL, "bad image size");
-  if ((d_image_rgb && !d_tiles_rgb) || (d_image_rgb8 && !d_tiles_rgb8))
-    return fail(RT_HIP_EINVAL, "an output image needs its tile buffer");
-  if (tile_count == 0 || (!d_image_rgb && !d_image_rgb8))
-    return RT_HIP_OK;
-  const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
-  if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
-    return fail(RT_HIP_EINVAL, "tile range exceeds the image");
-  hipError_t e = pt_launch_untile(d_tiles_rgb, d_tiles_rgb8, width, height, tile_first, tile_stride, tile_count,
-                                  d_image_rgb, d_image_rgb8, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_untile launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
-}
-
-/* ---- first-hit feature buffers (rt_hip.h, RtHipAov) ----------------------------------------------------------------------
- * The launch takes launch_prepare's camera-dependent fields and acquire_tables' filter, hierarchy and fp32 triangle table -- what
- * the beauty kernels' intersect() reads -- and nothing else: not pt_plan_launch (the AOV forms are no rows of the pick table, the
- * scene alone picks one: pt_aov_pick), nor launch_device_state (the body needs neither the status word nor the parked-walk
- * workspace: it cannot fail on the device and walks the hierarchy per lane). */
-static bool aov_any(const RtHipAov *a) { return a && (a->albedo || a->normal || a->depth || a->object || a->hits); }
-
-const char *rt_hip_aov_kernel_name(const RtHipScene *scene) { return scene ? pt_aov_kernel_name_of(pt_aov_pick(scene->view)) : ""; }
-
-int rt_hip_aov_kernel_count(void) { return pt_aov_kernel_count(); }
-
-const char *rt_hip_aov_kernel_launches(int index, uint64_t *launches)
-{
-  if (index < 0 || index >= pt_aov_kernel_count())
-    return nullptr;
-  if (launches)
-    *launches = pt_aov_kernel_launches(index);
-  return pt_aov_kernel_name_of(index);
-}
-
-int rt_hip_render_aov_tiles(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *d_tiles,
-                            void *stream)
-{
-  if (!scene || !camera || !params)
-    return fail(RT_HIP_EINVAL, "scene, camera and params are required");
-  if (!aov_any(d_tiles))
-    return fail(RT_HIP_EINVAL, "d_tiles: at least one output buffer is required");
-  RtHipParams p = *params;
-  p.max_depth = 0; /* ignored: one intersect() per sample */
-  p.integrator = RT_HIP_TRACE_PATH;
-  PtLaunch L;
-  bool empty = false;
-  int rc = launch_prepare(scene, camera, &p, L, &empty);
-  if (rc || empty)
-    return rc;
-  const PtAovOut out = {d_tiles->albedo, d_tiles->normal, d_tiles->depth, d_tiles->object, d_tiles->hits};
-  const int which = pt_aov_pick(scene->view);
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  size_t slot = 0;
-  rc = acquire_tables(scene, L.near_R, static_cast<hipStream_t>(stream), &L.scene.filt, &L.scene.bvh_nodes, &slot);
-  if (rc)
-    return rc;
-  const hipError_t e = pt_launch_aov(L, out, static_cast<hipStream_t>(stream), which);
-  release_tables(scene, slot, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_aov_kernel_name_of(which), hipGetErrorString(e));
-  return RT_HIP_OK;
-}
-
-int rt_hip_untile_aov(const RtHipAov *d_tiles, int32_t width, int32_t height, uint32_t tile_first, uint32_t tile_stride,
-                      uint32_t tile_count, const RtHipAov *d_image, void *stream)
-{
-  if (!d_tiles || !d_image || width < 1 || height < 1)
-    return fail(RT_HIP_EINVAL, "tile and image buffers and the image size are required");
-  if (tile_count == 0)
-    return RT_HIP_OK;
-  if (tile_stride == 0 && tile_count > 1)
-    return fail(RT_HIP_EINVAL, "tile_stride must be >= 1");
-  const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
-  if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
-    return fail(RT_HIP_EINVAL, "tile range exceeds the image");
-  const void *src[5] = {d_tiles->albedo, d_tiles->normal, d_tiles->depth, d_tiles->object, d_tiles->hits};
-  void *dst[5] = {d_image->albedo, d_image->normal, d_image->depth, d_image->object, d_image->hits};
-  for (int k = 0; k < 5; k++)
-  {
-    if (!src[k] || !dst[k])
-      continue;
-    const hipError_t e = pt_launch_untile_aov(static_cast<const uint32_t *>(src[k]), k < 2 ? 3u : 1u, width, height, tile_first,
-                                              tile_stride, tile_count, static_cast<uint32_t *>(dst[k]), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "pt_untile_aov launch: %s", hipGetErrorString(e));
-  }
-  return RT_HIP_OK;
-}
-
-/* Whole image on n_devices GPUs of this process.  Device g renders tiles
- * g, g+G, g+2G, ... into its own compact buffer; the buffers are gathered on
+/* ---- rt_hip_render_image: the whole image on n_devices GPUs of this process ------------------------------------------------
+ * Device g renders tiles g, g+G, g+2G, ... into its own compact buffer; the buffers are gathered on
  * device 0 with grouped ncclSend/ncclRecv (point-to-point over xGMI: a gather
  * to one root uses the root's 7 direct links concurrently, there is no ring),
- * scattered to the row-major image there, and copied to the host. */
-} /* extern "C" */
-
-namespace
-{
-
-/* Everything rt_hip_render_image() needs between calls -- per device: the uploaded scene, a
+ * scattered to the row-major image there, and copied to the host.
+ *
+ * Everything rt_hip_render_image() needs between calls -- per device: the uploaded scene, a
  * stream, timing events, the compact tile buffers, counters, the chunk workspace; on device 0 the
  * gathered tiles and the row-major images; and the RCCL communicators -- is kept in one cached
  * context and reused while the device count, the image size and the scene's bytes stay the same
  * (an animation loop calling render() per frame re-creates nothing; ncclCommInitAll alone costs
  * tens of milliseconds per call at 8 devices).  rt_hip_release_cache() drops it. */
+constexpr size_t TILE_VALS = (size_t)PT_TILE_PIXELS * 3; /* floats -- or bytes -- of a tile */
+
 struct ImageCtx
 {
   struct Dev
   {
     RtHipScene *scene = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    float *tiles = nullptr;
-    uint8_t *tiles8 = nullptr;
-    uint64_t *stats = nullptr;
-    void *ws = nullptr;
-    uint32_t count = 0;
+    EventPair timer;           /* around the device's share */
+    hipEvent_t done = nullptr; /* its tiles are complete (what a same-device copy or the lead's sends wait for) */
+    DeviceBuffer tiles, tiles8, stats, ws;
+    uint32_t count = 0;    /* tiles of its share */
+    size_t first_slot = 0; /* where its segment begins in the gathered tiles */
   };
   int G = 0, W = 0, H = 0;
   /* logical device g runs on physical device phys[g] (rt_hip_set_device_map; the identity without a map).  Logical devices
@@ -2377,12 +1512,11 @@ struct ImageCtx
   std::vector<unsigned char> scene_bytes; /* the scene this context was built for (scene_walk's runs): compared run by run */
   std::vector<Dev> dev;
   std::vector<ncclComm_t> comms; /* one per distinct physical device (comm_of) */
-  std::vector<hipEvent_t> done;  /* per logical device: its tiles are complete (what a same-device copy or the lead's sends wait for) */
-  float *all_tiles = nullptr, *image = nullptr;
-  uint8_t *all_tiles8 = nullptr, *image8 = nullptr;
+  DeviceBuffer all_tiles, all_tiles8, image, image8; /* on the root, phys[0] */
   uint64_t builds = 0; /* how many times a context was (re)built: exposed for tests */
 };
-ImageCtx g_ctx;
+/* (never destroyed: at process exit the members' destructors would call into a HIP runtime that may be gone already) */
+ImageCtx &g_ctx = *new ImageCtx;
 std::mutex g_ctx_mutex;
 double g_last_phases[3] = {0, 0, 0}; /* rt_hip_last_image_phases */
 
@@ -2416,16 +1550,18 @@ void device_map_from_env()
   g_device_map = m;
 }
 
+/* What needs an order: the streams drained, then the communicators, then each device's members with that device current.
+ * `builds` survives. */
 void ctx_release(ImageCtx &c)
 {
   int prev = 0;
   (void)hipGetDevice(&prev);
   for (int g = 0; g < (int)c.dev.size(); g++)
-  {
-    (void)hipSetDevice(g < (int)c.phys.size() ? c.phys[g] : g);
-    ImageCtx::Dev &d = c.dev[g];
-    if (d.stream) (void)hipStreamSynchronize(d.stream);
-  }
+    if (c.dev[g].stream)
+    {
+      (void)hipSetDevice(c.phys[g]);
+      (void)hipStreamSynchronize(c.dev[g].stream);
+    }
   for (int r = 0; r < (int)c.comms.size(); r++)
     if (c.comms[r])
     {
@@ -2439,31 +1575,37 @@ void ctx_release(ImageCtx &c)
     }
   for (int g = 0; g < (int)c.dev.size(); g++)
   {
-    (void)hipSetDevice(g < (int)c.phys.size() ? c.phys[g] : g);
+    (void)hipSetDevice(c.phys[g]);
     ImageCtx::Dev &d = c.dev[g];
-    if (d.t0) (void)hipEventDestroy(d.t0);
-    if (d.t1) (void)hipEventDestroy(d.t1);
-    if (g < (int)c.done.size() && c.done[g]) (void)hipEventDestroy(c.done[g]);
+    if (d.done) (void)hipEventDestroy(d.done);
     if (d.stream) (void)hipStreamDestroy(d.stream);
-    (void)hipFree(d.tiles);
-    (void)hipFree(d.tiles8);
-    (void)hipFree(d.stats);
-    (void)hipFree(d.ws);
     rt_hip_scene_destroy(d.scene);
+    d = ImageCtx::Dev(); /* its timer and buffers */
   }
-  if (!c.dev.empty())
-  {
-    (void)hipSetDevice(c.phys.empty() ? 0 : c.phys[0]);
-    (void)hipFree(c.all_tiles);
-    (void)hipFree(c.all_tiles8);
-    (void)hipFree(c.image);
-    (void)hipFree(c.image8);
-  }
-  (void)hipSetDevice(prev);
+  if (!c.phys.empty())
+    (void)hipSetDevice(c.phys[0]);
   const uint64_t builds = c.builds;
-  c = ImageCtx();
+  c = ImageCtx(); /* the root's gathered tiles and images */
   c.builds = builds;
+  (void)hipSetDevice(prev);
 }
+
+/* The error exit of the image context, made once g_ctx_mutex is held: unless keep() was called, leaving the scope drops the cached
+ * context -- a failure leaves it in an unknown state.  The caller's device is put back either way. */
+struct CtxGuard
+{
+  int prev = 0;
+  bool kept = false;
+  CtxGuard() { (void)hipGetDevice(&prev); }
+  CtxGuard(const CtxGuard &) = delete;
+  void keep() { kept = true; }
+  ~CtxGuard()
+  {
+    if (!kept)
+      ctx_release(g_ctx);
+    (void)hipSetDevice(prev);
+  }
+};
 
 /* Everything that defines the scene, field by field (struct padding is not part of the scene), as runs of bytes handed
  * to `f(ptr, n)` in a fixed order.  The cached context keeps the concatenation (ImageCtx::scene_bytes) and is reused only
@@ -2516,23 +1658,9 @@ void scene_serialise(std::vector<unsigned char> &bytes, const RtHipSphere *spher
   });
 }
 
-#define CTX_TRY(expr)                                                                               \
-  do                                                                                                \
-  {                                                                                                 \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess)                                                                           \
-    {                                                                                               \
-      int c_ = fail(e_ == hipErrorOutOfMemory ? RT_HIP_ENOMEM : RT_HIP_ERUNTIME, "%s: %s", #expr,   \
-                    hipGetErrorString(e_));                                                         \
-      ctx_release(g_ctx);                                                                           \
-      (void)hipSetDevice(prev);                                                                     \
-      return c_;                                                                                    \
-    }                                                                                               \
-  } while (0)
-
-/* makes g_ctx fit this call (device count and map, image size, scene); caller holds g_ctx_mutex */
+/* makes g_ctx fit this call (device count and map, image size, scene); caller holds g_ctx_mutex and a CtxGuard */
 int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, int G,
-                const std::vector<int> &phys, int W, int H, int prev)
+                const std::vector<int> &phys, int W, int H)
 {
   /* RT_HIP_FORCE_COMM=1: build the RCCL communicator(s) and run the gather's grouped send / recv block even where no
    * tile has to change devices (one device, or logical devices that all share one): every segment then travels through
@@ -2550,7 +1678,6 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
   c.phys = phys;
   c.comm_of.assign(G, 0);
   c.lead.assign(G, 0);
-  c.done.assign(G, nullptr);
   c.n_phys = 0;
   for (int g = 0; g < G; g++)
   {
@@ -2567,34 +1694,32 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
   c.comms.assign(c.n_phys, nullptr);
   const uint32_t n_tiles = tiles_x_of(W) * tiles_y_of(H);
   const size_t n_px = (size_t)W * H;
+  size_t first_slot = 0;
   for (int g = 0; g < G; g++)
   {
     ImageCtx::Dev &d = c.dev[g];
     d.count = (n_tiles > (uint32_t)g) ? (n_tiles - g + G - 1) / G : 0;
-    int rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys[g], &d.scene);
+    d.first_slot = first_slot;
+    first_slot += d.count;
+    const int rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys[g], &d.scene);
     if (rc)
-    {
-      ctx_release(c);
-      (void)hipSetDevice(prev);
       return rc;
-    }
-    CTX_TRY(hipSetDevice(phys[g]));
-    CTX_TRY(hipStreamCreate(&d.stream));
-    CTX_TRY(hipEventCreate(&d.t0));
-    CTX_TRY(hipEventCreate(&d.t1));
-    CTX_TRY(hipEventCreateWithFlags(&c.done[g], hipEventDisableTiming));
+    HIP_TRY(hipSetDevice(phys[g]));
+    HIP_TRY(hipStreamCreate(&d.stream));
+    HIP_TRY(d.timer.create());
+    HIP_TRY(hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
     const size_t slots = d.count ? d.count : 1;
-    CTX_TRY(hipMalloc(&d.tiles, slots * 192 * sizeof(float)));
-    CTX_TRY(hipMalloc(&d.tiles8, slots * 192));
-    CTX_TRY(hipMalloc(&d.stats, RT_HIP_NSTATS * sizeof(uint64_t)));
+    HIP_TRY(d.tiles.alloc(slots * TILE_VALS * sizeof(float)));
+    HIP_TRY(d.tiles8.alloc(slots * TILE_VALS));
+    HIP_TRY(d.stats.alloc(RT_HIP_NSTATS * sizeof(uint64_t)));
   }
-  CTX_TRY(hipSetDevice(phys[0]));
-  CTX_TRY(hipMalloc(&c.image, n_px * 3 * sizeof(float)));
-  CTX_TRY(hipMalloc(&c.image8, n_px * 3));
+  HIP_TRY(hipSetDevice(phys[0]));
+  HIP_TRY(c.image.alloc(n_px * 3 * sizeof(float)));
+  HIP_TRY(c.image8.alloc(n_px * 3));
   if (G > 1 || force_comm)
   {
-    CTX_TRY(hipMalloc(&c.all_tiles, (size_t)n_tiles * 192 * sizeof(float)));
-    CTX_TRY(hipMalloc(&c.all_tiles8, (size_t)n_tiles * 192));
+    HIP_TRY(c.all_tiles.alloc(n_tiles * TILE_VALS * sizeof(float)));
+    HIP_TRY(c.all_tiles8.alloc(n_tiles * TILE_VALS));
   }
   if (c.n_phys > 1 || force_comm)
   {
@@ -2602,20 +1727,203 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
     for (int g = 0; g < G; g++)
       if (c.lead[g] == g)
         ids[c.comm_of[g]] = phys[g];
-    ncclResult_t nr = ncclCommInitAll(c.comms.data(), c.n_phys, ids.data());
-    if (nr != ncclSuccess)
-    {
-      int code = fail(RT_HIP_ERUNTIME, "ncclCommInitAll: %s", ncclGetErrorString(nr));
-      ctx_release(c);
-      (void)hipSetDevice(prev);
-      return code;
-    }
+    NCCL_TRY(ncclCommInitAll(c.comms.data(), c.n_phys, ids.data()));
   }
   c.G = G;
   c.W = W;
   c.H = H;
   c.force_comm = force_comm;
   scene_serialise(c.scene_bytes, spheres, n_spheres, meshes, n_meshes);
+  return RT_HIP_OK;
+}
+
+/* ---- launch every device's share; -> *cancelled: the cancel flag was found set between two slabs ---- */
+int image_launch_shares(ImageCtx &c, const RtHipCamera *camera, const RtHipParams *params, bool *cancelled)
+{
+  const int G = c.G;
+  for (int g = 0; g < G; g++)
+  {
+    ImageCtx::Dev &d = c.dev[g];
+    HIP_TRY(hipSetDevice(c.phys[g]));
+    const size_t slots = d.count ? d.count : 1;
+    HIP_TRY(hipMemsetAsync(d.stats.ptr, 0, RT_HIP_NSTATS * sizeof(uint64_t), d.stream));
+    HIP_TRY(hipMemsetAsync(d.tiles.ptr, 0, slots * TILE_VALS * sizeof(float), d.stream)); /* unrendered tiles stay black, */
+    HIP_TRY(hipMemsetAsync(d.tiles8.ptr, 0, slots * TILE_VALS, d.stream));                /* like the reference's memset  */
+    HIP_TRY(d.timer.start(d.stream));
+  }
+  /* Long frames are rendered in slabs (contiguous runs of each device's tile list) so that a
+   * cancel request -- the CLI's SIGINT -- is honoured between slabs; what was finished is
+   * still gathered and returned (the reference dumps its partial framebuffer on SIGINT,
+   * main.c:37-48, from inside the signal handler; this does it from normal context). */
+  const double work = (double)c.W * c.H * (double)params->samples;
+  const uint32_t n_slabs = g_cancel ? (work > 4e9 ? 16u : (work > 2e8 ? 4u : 1u)) : 1u;
+  *cancelled = false;
+  for (uint32_t slab = 0; slab < n_slabs && !*cancelled; slab++)
+  {
+    for (int g = 0; g < G; g++)
+    {
+      ImageCtx::Dev &d = c.dev[g];
+      const uint32_t k0 = (uint32_t)(((uint64_t)d.count * slab) / n_slabs);
+      const uint32_t k1 = (uint32_t)(((uint64_t)d.count * (slab + 1)) / n_slabs);
+      if (k1 == k0)
+        continue;
+      HIP_TRY(hipSetDevice(c.phys[g]));
+      RtHipParams p = *params;
+      p.tile_first = (uint32_t)g + k0 * (uint32_t)G;
+      p.tile_stride = (uint32_t)G;
+      p.tile_count = k1 - k0;
+      const uint32_t chunks = p.integrator == RT_HIP_CAST_RAY ? 1u : rt_hip_suggest_chunks_depth(d.scene, p.tile_count, p.samples, p.max_depth);
+      if (chunks > 1 && !d.ws)
+        HIP_TRY(d.ws.alloc(rt_hip_scene_chunk_workspace_bytes(d.scene, d.count)));
+      const int rc = rt_hip_render_tiles_chunked(d.scene, camera, &p, chunks, d.ws.ptr, d.tiles.at<float>() + k0 * TILE_VALS,
+                                                 d.tiles8.at<uint8_t>() + k0 * TILE_VALS, d.stats.at<uint64_t>(), d.stream);
+      if (rc)
+        return rc;
+    }
+    if (n_slabs > 1)
+    {
+      for (int g = 0; g < G; g++)
+      {
+        HIP_TRY(hipSetDevice(c.phys[g]));
+        HIP_TRY(hipStreamSynchronize(c.dev[g].stream));
+      }
+      *cancelled = g_cancel && *g_cancel != 0;
+    }
+  }
+  for (int g = 0; g < G; g++)
+  {
+    HIP_TRY(hipSetDevice(c.phys[g]));
+    HIP_TRY(c.dev[g].timer.stop(c.dev[g].stream));
+    HIP_TRY(hipEventRecord(c.dev[g].done, c.dev[g].stream));
+  }
+  return RT_HIP_OK;
+}
+
+/* logical device g has a segment that must reach the gathered tiles (the root's own never travels, unless force_comm sends it
+ * through RCCL) ... and it goes by RCCL, not by a copy on the root's physical device */
+bool image_travels(const ImageCtx &c, int g) { return c.dev[g].count && (g != 0 || c.force_comm); }
+bool image_by_rccl(const ImageCtx &c, int g) { return c.force_comm || c.phys[g] != c.phys[0]; }
+
+ncclResult_t image_gather_rccl(ImageCtx &c)
+{
+  ncclResult_t nr = ncclGroupStart();
+  for (int g = 0; g < c.G && nr == ncclSuccess; g++)
+  {
+    if (!image_travels(c, g) || !image_by_rccl(c, g))
+      continue;
+    ImageCtx::Dev &d = c.dev[g];
+    const size_t nf = d.count * TILE_VALS, at = d.first_slot * TILE_VALS;
+    const int from = c.comm_of[g];
+    hipStream_t send_stream = c.dev[c.lead[g]].stream;
+    nr = ncclSend(d.tiles.ptr, nf, ncclFloat, 0, c.comms[from], send_stream);
+    if (nr == ncclSuccess) nr = ncclSend(d.tiles8.ptr, nf, ncclUint8, 0, c.comms[from], send_stream);
+    if (nr == ncclSuccess) nr = ncclRecv(c.all_tiles.at<float>() + at, nf, ncclFloat, from, c.comms[0], c.dev[0].stream);
+    if (nr == ncclSuccess) nr = ncclRecv(c.all_tiles8.at<uint8_t>() + at, nf, ncclUint8, from, c.comms[0], c.dev[0].stream);
+  }
+  const ncclResult_t ne = ncclGroupEnd();
+  return nr == ncclSuccess ? ne : nr;
+}
+
+/* ---- gather on logical device 0 (the root): every segment straight to it ----
+ * A segment whose sender shares the root's physical device is a device-to-device copy on the root's stream, ordered after
+ * the sender's `done` event; any other travels by grouped ncclSend / ncclRecv (point-to-point over xGMI: a gather to one
+ * root uses the root's direct links concurrently, there is no ring).  A physical device is ONE RCCL rank however many
+ * logical devices it carries: the rank's sends go on its lead's stream, which first waits for the other senders' `done`.
+ * force_comm: every segment, the root's own included, goes through RCCL. */
+int image_gather(ImageCtx &c)
+{
+  HIP_TRY(hipSetDevice(c.phys[0]));
+  bool any_rccl = false;
+  for (int g = 0; g < c.G; g++)
+  {
+    if (!image_travels(c, g))
+      continue;
+    ImageCtx::Dev &d = c.dev[g];
+    if (image_by_rccl(c, g))
+    {
+      any_rccl = true;
+      if (c.lead[g] != g)
+      {
+        HIP_TRY(hipSetDevice(c.phys[g]));
+        HIP_TRY(hipStreamWaitEvent(c.dev[c.lead[g]].stream, d.done, 0));
+      }
+    }
+    else
+    {
+      HIP_TRY(hipSetDevice(c.phys[0]));
+      HIP_TRY(hipStreamWaitEvent(c.dev[0].stream, d.done, 0));
+      const size_t nf = d.count * TILE_VALS, at = d.first_slot * TILE_VALS;
+      HIP_TRY(hipMemcpyAsync(c.all_tiles.at<float>() + at, d.tiles.ptr, nf * sizeof(float), hipMemcpyDeviceToDevice, c.dev[0].stream));
+      HIP_TRY(hipMemcpyAsync(c.all_tiles8.at<uint8_t>() + at, d.tiles8.ptr, nf, hipMemcpyDeviceToDevice, c.dev[0].stream));
+    }
+  }
+  if (any_rccl)
+    NCCL_TRY(image_gather_rccl(c));
+  return RT_HIP_OK;
+}
+
+/* scatter each device's segment into the row-major image (root), then wait until every stream is idle */
+int image_scatter(ImageCtx &c)
+{
+  HIP_TRY(hipSetDevice(c.phys[0]));
+  for (int g = 0; g < c.G; g++)
+  {
+    if (!c.dev[g].count)
+      continue;
+    const bool local = !image_travels(c, g); /* the root's own tiles, where they did not travel */
+    const float *src = local ? c.dev[0].tiles.at<float>() : c.all_tiles.at<float>() + c.dev[g].first_slot * TILE_VALS;
+    const uint8_t *src8 = local ? c.dev[0].tiles8.at<uint8_t>() : c.all_tiles8.at<uint8_t>() + c.dev[g].first_slot * TILE_VALS;
+    const int rc = rt_hip_untile(src, src8, c.W, c.H, (uint32_t)g, (uint32_t)c.G, c.dev[g].count, c.image.at<float>(),
+                                 c.image8.at<uint8_t>(), c.dev[0].stream);
+    if (rc)
+      return rc;
+  }
+  for (int g = 0; g < c.G; g++)
+  {
+    HIP_TRY(hipSetDevice(c.phys[g]));
+    HIP_TRY(hipStreamSynchronize(c.dev[g].stream));
+  }
+  return RT_HIP_OK;
+}
+
+/* the frame, bytes and counters to the host; -> *fail_flags: the status words (did every workgroup find its pool slots?) */
+int image_collect(ImageCtx &c, float *h_image_rgb, uint8_t *h_image_rgb8, uint64_t *h_stats, double *kernel_seconds, uint32_t *fail_flags)
+{
+  const size_t n_px = (size_t)c.W * c.H;
+  *fail_flags = 0;
+  for (int g = 0; g < c.G; g++)
+    if (c.lead[g] == g)
+    { /* the status word of each physical device */
+      HIP_TRY(hipSetDevice(c.phys[g]));
+      uint32_t f = 0;
+      const int rc = status_take(c.phys[g], &f);
+      if (rc)
+        return rc;
+      *fail_flags |= f;
+    }
+  HIP_TRY(hipSetDevice(c.phys[0]));
+  if (h_image_rgb)
+    HIP_TRY(hipMemcpy(h_image_rgb, c.image.ptr, n_px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (h_image_rgb8)
+    HIP_TRY(hipMemcpy(h_image_rgb8, c.image8.ptr, n_px * 3, hipMemcpyDeviceToHost));
+  double worst = 0;
+  uint64_t sums[RT_HIP_NSTATS] = {0, 0, 0, 0};
+  for (int g = 0; g < c.G; g++)
+  {
+    HIP_TRY(hipSetDevice(c.phys[g]));
+    float ms = 0;
+    HIP_TRY(c.dev[g].timer.elapsed_ms(&ms));
+    if (ms * 1e-3 > worst)
+      worst = ms * 1e-3;
+    uint64_t st[RT_HIP_NSTATS];
+    HIP_TRY(hipMemcpy(st, c.dev[g].stats.ptr, sizeof st, hipMemcpyDeviceToHost));
+    for (int k = 0; k < RT_HIP_NSTATS; k++)
+      sums[k] += st[k];
+  }
+  if (h_stats)
+    memcpy(h_stats, sums, sizeof sums);
+  if (kernel_seconds)
+    *kernel_seconds = worst;
   return RT_HIP_OK;
 }
 
@@ -2632,8 +1940,6 @@ int render_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   if (have < 1)
     return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
   const int W = params->width, H = params->height;
-  const size_t n_px = (size_t)W * H;
-
   std::lock_guard<std::mutex> lock(g_ctx_mutex); /* one frame at a time: the context is shared */
   device_map_from_env();
   const int limit = g_device_map.empty() ? have : (int)g_device_map.size();
@@ -2647,218 +1953,27 @@ int render_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     if (phys[g] < 0 || phys[g] >= have)
       return fail(RT_HIP_ENODEV, "device map entry %d -> %d: %d devices available", g, phys[g], have);
   }
-  int prev = 0;
-  (void)hipGetDevice(&prev);
   const auto tick0 = std::chrono::steady_clock::now();
-  rc = ctx_prepare(spheres, n_spheres, meshes, n_meshes, G, phys, W, H, prev);
+  CtxGuard guard; /* from here on a failure drops the cached context */
+  rc = ctx_prepare(spheres, n_spheres, meshes, n_meshes, G, phys, W, H);
   if (rc)
     return rc;
   const auto tick1 = std::chrono::steady_clock::now();
   ImageCtx &c = g_ctx;
-  std::vector<ImageCtx::Dev> &dev = c.dev;
-  /* a failure below leaves the cached context in an unknown state: drop it */
-#define IMG_TRY(expr)                                                                               \
-  do                                                                                                \
-  {                                                                                                 \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess)                                                                           \
-    {                                                                                               \
-      int c_ = fail(e_ == hipErrorOutOfMemory ? RT_HIP_ENOMEM : RT_HIP_ERUNTIME, "%s: %s", #expr,   \
-                    hipGetErrorString(e_));                                                         \
-      ctx_release(g_ctx);                                                                           \
-      (void)hipSetDevice(prev);                                                                     \
-      return c_;                                                                                    \
-    }                                                                                               \
-  } while (0)
-
-  /* ---- launch every device's share ---- */
-  for (int g = 0; g < G; g++)
-  {
-    ImageCtx::Dev &d = dev[g];
-    IMG_TRY(hipSetDevice(phys[g]));
-    const size_t slots = d.count ? d.count : 1;
-    IMG_TRY(hipMemsetAsync(d.stats, 0, RT_HIP_NSTATS * sizeof(uint64_t), d.stream));
-    IMG_TRY(hipMemsetAsync(d.tiles, 0, slots * 192 * sizeof(float), d.stream));  /* unrendered tiles stay black, */
-    IMG_TRY(hipMemsetAsync(d.tiles8, 0, slots * 192, d.stream));                 /* like the reference's memset  */
-    IMG_TRY(hipEventRecord(d.t0, d.stream));
-  }
-  /* Long frames are rendered in slabs (contiguous runs of each device's tile list) so that a
-   * cancel request -- the CLI's SIGINT -- is honoured between slabs; what was finished is
-   * still gathered and returned (the reference dumps its partial framebuffer on SIGINT,
-   * main.c:37-48, from inside the signal handler; this does it from normal context). */
-  const double work = (double)W * H * (double)params->samples;
-  const uint32_t n_slabs = g_cancel ? (work > 4e9 ? 16u : (work > 2e8 ? 4u : 1u)) : 1u;
   bool cancelled = false;
-  for (uint32_t slab = 0; slab < n_slabs && !cancelled; slab++)
-  {
-    for (int g = 0; g < G; g++)
-    {
-      ImageCtx::Dev &d = dev[g];
-      const uint32_t k0 = (uint32_t)(((uint64_t)d.count * slab) / n_slabs);
-      const uint32_t k1 = (uint32_t)(((uint64_t)d.count * (slab + 1)) / n_slabs);
-      if (k1 == k0)
-        continue;
-      IMG_TRY(hipSetDevice(phys[g]));
-      RtHipParams p = *params;
-      p.tile_first = (uint32_t)g + k0 * (uint32_t)G;
-      p.tile_stride = (uint32_t)G;
-      p.tile_count = k1 - k0;
-      const uint32_t chunks = p.integrator == RT_HIP_CAST_RAY ? 1u : rt_hip_suggest_chunks_depth(d.scene, p.tile_count, p.samples, p.max_depth);
-      if (chunks > 1 && !d.ws)
-        IMG_TRY(hipMalloc(&d.ws, rt_hip_scene_chunk_workspace_bytes(d.scene, d.count)));
-      rc = rt_hip_render_tiles_chunked(d.scene, camera, &p, chunks, d.ws, d.tiles + (size_t)k0 * 192,
-                                       d.tiles8 + (size_t)k0 * 192, d.stats, d.stream);
-      if (rc)
-      {
-        ctx_release(g_ctx);
-        (void)hipSetDevice(prev);
-        return rc;
-      }
-    }
-    if (n_slabs > 1)
-    {
-      for (int g = 0; g < G; g++)
-      {
-        IMG_TRY(hipSetDevice(phys[g]));
-        IMG_TRY(hipStreamSynchronize(dev[g].stream));
-      }
-      cancelled = g_cancel && *g_cancel != 0;
-    }
-  }
-  for (int g = 0; g < G; g++)
-  {
-    IMG_TRY(hipSetDevice(phys[g]));
-    IMG_TRY(hipEventRecord(dev[g].t1, dev[g].stream));
-    IMG_TRY(hipEventRecord(c.done[g], dev[g].stream));
-  }
-
-  /* ---- gather on logical device 0 (the root): every segment straight to it ----
-   * A segment whose sender shares the root's physical device is a device-to-device copy on the root's stream, ordered after
-   * the sender's `done` event; any other travels by grouped ncclSend / ncclRecv (point-to-point over xGMI: a gather to one
-   * root uses the root's direct links concurrently, there is no ring).  A physical device is ONE RCCL rank however many
-   * logical devices it carries: the rank's sends go on its lead's stream, which first waits for the other senders' `done`.
-   * force_comm: every segment, the root's own included, goes through RCCL. */
-  IMG_TRY(hipSetDevice(phys[0]));
-  std::vector<size_t> first_slot(G, 0);
-  for (int g = 1; g < G; g++)
-    first_slot[g] = first_slot[g - 1] + dev[g - 1].count;
-  auto by_rccl = [&](int g) { return c.force_comm || phys[g] != phys[0]; };
-  bool any_rccl = false;
-  for (int g = 0; g < G; g++)
-  {
-    if (!dev[g].count || (g == 0 && !c.force_comm))
-      continue;
-    if (by_rccl(g))
-    {
-      any_rccl = true;
-      if (c.lead[g] != g)
-      {
-        IMG_TRY(hipSetDevice(phys[g]));
-        IMG_TRY(hipStreamWaitEvent(dev[c.lead[g]].stream, c.done[g], 0));
-      }
-    }
-    else
-    {
-      IMG_TRY(hipSetDevice(phys[0]));
-      IMG_TRY(hipStreamWaitEvent(dev[0].stream, c.done[g], 0));
-      const size_t nf = (size_t)dev[g].count * 192;
-      IMG_TRY(hipMemcpyAsync(c.all_tiles + first_slot[g] * 192, dev[g].tiles, nf * sizeof(float), hipMemcpyDeviceToDevice, dev[0].stream));
-      IMG_TRY(hipMemcpyAsync(c.all_tiles8 + first_slot[g] * 192, dev[g].tiles8, nf, hipMemcpyDeviceToDevice, dev[0].stream));
-    }
-  }
-  if (any_rccl)
-  {
-    ncclResult_t nr = ncclGroupStart();
-    for (int g = 0; g < G && nr == ncclSuccess; g++)
-    {
-      if (!dev[g].count || (g == 0 && !c.force_comm) || !by_rccl(g))
-        continue;
-      const size_t nf = (size_t)dev[g].count * 192;
-      const int from = c.comm_of[g];
-      hipStream_t send_stream = dev[c.lead[g]].stream;
-      nr = ncclSend(dev[g].tiles, nf, ncclFloat, 0, c.comms[from], send_stream);
-      if (nr == ncclSuccess) nr = ncclSend(dev[g].tiles8, nf, ncclUint8, 0, c.comms[from], send_stream);
-      if (nr == ncclSuccess) nr = ncclRecv(c.all_tiles + first_slot[g] * 192, nf, ncclFloat, from, c.comms[0], dev[0].stream);
-      if (nr == ncclSuccess) nr = ncclRecv(c.all_tiles8 + first_slot[g] * 192, nf, ncclUint8, from, c.comms[0], dev[0].stream);
-    }
-    ncclResult_t ne = ncclGroupEnd();
-    if (nr == ncclSuccess)
-      nr = ne;
-    if (nr != ncclSuccess)
-    {
-      int code = fail(RT_HIP_ERUNTIME, "RCCL gather: %s", ncclGetErrorString(nr));
-      ctx_release(g_ctx);
-      (void)hipSetDevice(prev);
-      return code;
-    }
-  }
-  /* scatter each device's segment into the row-major image (root) */
-  IMG_TRY(hipSetDevice(phys[0]));
-  for (int g = 0; g < G; g++)
-  {
-    if (!dev[g].count)
-      continue;
-    const bool local = g == 0 && !c.force_comm; /* the root's own tiles never travel -- unless force_comm sent them through RCCL */
-    const float *src = local ? dev[0].tiles : c.all_tiles + first_slot[g] * 192;
-    const uint8_t *src8 = local ? dev[0].tiles8 : c.all_tiles8 + first_slot[g] * 192;
-    rc = rt_hip_untile(src, src8, W, H, (uint32_t)g, (uint32_t)G, dev[g].count, c.image, c.image8, dev[0].stream);
-    if (rc)
-    {
-      ctx_release(g_ctx);
-      (void)hipSetDevice(prev);
-      return rc;
-    }
-  }
-  for (int g = 0; g < G; g++)
-  {
-    IMG_TRY(hipSetDevice(phys[g]));
-    IMG_TRY(hipStreamSynchronize(dev[g].stream));
-  }
-
+  rc = image_launch_shares(c, camera, params, &cancelled);
+  if (!rc)
+    rc = image_gather(c);
+  if (!rc)
+    rc = image_scatter(c);
+  if (rc)
+    return rc;
   const auto tick2 = std::chrono::steady_clock::now();
-  /* ---- did every workgroup find its pool slots?  (the status word of each physical device) ---- */
   uint32_t fail_flags = 0;
-  for (int g = 0; g < G; g++)
-    if (c.lead[g] == g)
-    {
-      IMG_TRY(hipSetDevice(phys[g]));
-      uint32_t f = 0;
-      rc = status_take(phys[g], &f);
-      if (rc)
-      {
-        ctx_release(g_ctx);
-        (void)hipSetDevice(prev);
-        return rc;
-      }
-      fail_flags |= f;
-    }
-
-  /* ---- results ---- */
-  IMG_TRY(hipSetDevice(phys[0]));
-  if (h_image_rgb)
-    IMG_TRY(hipMemcpy(h_image_rgb, c.image, n_px * 3 * sizeof(float), hipMemcpyDeviceToHost));
-  if (h_image_rgb8)
-    IMG_TRY(hipMemcpy(h_image_rgb8, c.image8, n_px * 3, hipMemcpyDeviceToHost));
-  double worst = 0;
-  uint64_t sums[RT_HIP_NSTATS] = {0, 0, 0, 0};
-  for (int g = 0; g < G; g++)
-  {
-    IMG_TRY(hipSetDevice(phys[g]));
-    float ms = 0;
-    IMG_TRY(hipEventElapsedTime(&ms, dev[g].t0, dev[g].t1));
-    if (ms * 1e-3 > worst)
-      worst = ms * 1e-3;
-    uint64_t st[RT_HIP_NSTATS];
-    IMG_TRY(hipMemcpy(st, dev[g].stats, sizeof st, hipMemcpyDeviceToHost));
-    for (int k = 0; k < RT_HIP_NSTATS; k++)
-      sums[k] += st[k];
-  }
-  if (h_stats)
-    memcpy(h_stats, sums, sizeof sums);
-  if (kernel_seconds)
-    *kernel_seconds = worst;
-  (void)hipSetDevice(prev);
-#undef IMG_TRY
+  rc = image_collect(c, h_image_rgb, h_image_rgb8, h_stats, kernel_seconds, &fail_flags);
+  if (rc)
+    return rc;
+  guard.keep(); /* a status word or a cancel request is the frame's result: the context is sound */
   {
     const auto tick3 = std::chrono::steady_clock::now();
     auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -2910,10 +2025,6 @@ uint64_t cache_builds_impl()
   return g_ctx.builds;
 }
 
-} // namespace
-
-namespace
-{
 /* logical device `device` of the device map (the HIP device itself without a map) -> the HIP device, or RT_HIP_ENODEV */
 int physical_device(int device, int *phys)
 {
@@ -2936,8 +2047,48 @@ int physical_device(int device, int *phys)
   return RT_HIP_OK;
 }
 
-/* rt_hip_render_aov_image: a scene of its own on the device, compact buffers for the requested outputs, one launch over every
- * tile, the scatter, the copies.  Synchronous on the null stream. */
+/* rt_hip_render_aov_image on its scene: compact buffers for the requested outputs, one launch over every tile, the scatter, the
+ * copies.  Synchronous on the null stream. */
+int aov_image_of(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *h_image)
+{
+  DeviceScope scope(scene->device);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", scene->device, hipGetErrorString(scope.status));
+  RtHipParams p = *params;
+  whole_image(p);
+  const size_t tile_px = (size_t)p.tile_count * PT_TILE_PIXELS, img_px = (size_t)p.width * p.height;
+  /* one allocation: per requested output its tile buffer and its image, words of 4 bytes */
+  void *host[5] = {h_image->albedo, h_image->normal, h_image->depth, h_image->object, h_image->hits};
+  size_t off[5] = {0, 0, 0, 0, 0}, words = 0;
+  for (int k = 0; k < 5; k++)
+    if (host[k])
+    {
+      off[k] = words;
+      words += (k < 2 ? 3u : 1u) * (tile_px + img_px);
+    }
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc(words * 4u));
+  RtHipAov tiles = {}, image = {};
+  void **tp[5] = {(void **)&tiles.albedo, (void **)&tiles.normal, (void **)&tiles.depth, (void **)&tiles.object, (void **)&tiles.hits};
+  void **ip[5] = {(void **)&image.albedo, (void **)&image.normal, (void **)&image.depth, (void **)&image.object, (void **)&image.hits};
+  for (int k = 0; k < 5; k++)
+    if (host[k])
+    {
+      *tp[k] = buf.at<uint32_t>(4u * off[k]);
+      *ip[k] = buf.at<uint32_t>(4u * (off[k] + (k < 2 ? 3u : 1u) * tile_px));
+    }
+  int rc = rt_hip_render_aov_tiles(scene, camera, &p, &tiles, nullptr);
+  if (!rc)
+    rc = rt_hip_untile_aov(&tiles, p.width, p.height, 0, 1, p.tile_count, &image, nullptr);
+  if (rc)
+    return rc;
+  for (int k = 0; k < 5; k++)
+    if (host[k])
+      HIP_TRY(hipMemcpy(host[k], *ip[k], (k < 2 ? 3u : 1u) * img_px * 4u, hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
+/* ... with a scene of its own on the logical device */
 int render_aov_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
                           const RtHipCamera *camera, const RtHipParams *params, int device, const RtHipAov *h_image)
 {
@@ -2956,133 +2107,11 @@ int render_aov_image_impl(const RtHipSphere *spheres, size_t n_spheres, const Rt
   rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &scene);
   if (rc)
     return rc;
-  DeviceScope scope(phys);
-  if (scope.status != hipSuccess)
-  {
-    rt_hip_scene_destroy(scene);
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", phys, hipGetErrorString(scope.status));
-  }
-  RtHipParams p = *params;
-  p.tile_first = 0;
-  p.tile_stride = 1;
-  p.tile_count = tiles_x_of(p.width) * tiles_y_of(p.height);
-  const size_t tile_px = (size_t)p.tile_count * PT_TILE_PIXELS, img_px = (size_t)p.width * p.height;
-  /* one allocation: per requested output its tile buffer and its image, words of 4 bytes */
-  void *host[5] = {h_image->albedo, h_image->normal, h_image->depth, h_image->object, h_image->hits};
-  size_t off[5] = {0, 0, 0, 0, 0}, words = 0;
-  for (int k = 0; k < 5; k++)
-    if (host[k])
-    {
-      off[k] = words;
-      words += (k < 2 ? 3u : 1u) * (tile_px + img_px);
-    }
-  uint32_t *buf = nullptr;
-  hipError_t e = hipMalloc(&buf, words * 4u);
-  RtHipAov tiles = {}, image = {};
-  void **tp[5] = {(void **)&tiles.albedo, (void **)&tiles.normal, (void **)&tiles.depth, (void **)&tiles.object, (void **)&tiles.hits};
-  void **ip[5] = {(void **)&image.albedo, (void **)&image.normal, (void **)&image.depth, (void **)&image.object, (void **)&image.hits};
-  if (e == hipSuccess)
-    for (int k = 0; k < 5; k++)
-      if (host[k])
-      {
-        *tp[k] = buf + off[k];
-        *ip[k] = buf + off[k] + (k < 2 ? 3u : 1u) * tile_px;
-      }
-  if (e == hipSuccess)
-  {
-    rc = rt_hip_render_aov_tiles(scene, camera, &p, &tiles, nullptr);
-    if (!rc)
-      rc = rt_hip_untile_aov(&tiles, p.width, p.height, 0, 1, p.tile_count, &image, nullptr);
-    for (int k = 0; !rc && e == hipSuccess && k < 5; k++)
-      if (host[k])
-        e = hipMemcpy(host[k], *ip[k], (k < 2 ? 3u : 1u) * img_px * 4u, hipMemcpyDeviceToHost);
-  }
-  if (buf)
-    (void)hipFree(buf);
-  rt_hip_scene_destroy(scene);
-  if (rc)
-    return rc;
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? RT_HIP_ENOMEM : RT_HIP_ERUNTIME, "AOV image: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
-}
-} // namespace
-
-extern "C" int rt_hip_render_aov_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
-                                       const RtHipCamera *camera, const RtHipParams *params, int device, const RtHipAov *h_image)
-{
-  try
-  {
-    return render_aov_image_impl(spheres, n_spheres, meshes, n_meshes, camera, params, device, h_image);
-  }
-  catch (const std::bad_alloc &)
-  {
-    return fail(RT_HIP_ENOMEM, "host allocation failed in rt_hip_render_aov_image");
-  }
-  catch (...)
-  {
-    return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in rt_hip_render_aov_image");
-  }
-}
-
-/* rt_hip_render_adaptive_image: a scene and an accumulation of their own on the logical device, the driver, the frame and the count
- * map to host arrays.  Synchronous on the null stream. */
-extern "C" int rt_hip_render_adaptive_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
-                                            const RtHipCamera *camera, const RtHipParams *params, const RtHipAdaptParams *adapt, int device,
-                                            float *h_rgb, uint8_t *h_rgb8, uint32_t *h_tile_samples, uint64_t *h_stats,
-                                            double *kernel_seconds, int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles),
-                                            void *user)
-{
-  if (kernel_seconds)
-    *kernel_seconds = 0;
-  if (!camera || !params || (!h_rgb && !h_rgb8))
-    return fail(RT_HIP_EINVAL, "camera, params and an output image are required");
-  RtHipAdaptParams defaults;
-  rt_hip_adapt_defaults(&defaults);
-  if (!adapt)
-    adapt = &defaults;
-  if (adapt->min_samples < 1 || adapt->dilate > 2u || adapt->threshold != adapt->threshold)
-    return fail(RT_HIP_EINVAL, "adaptive parameters: min_samples >= 1, dilate 0 .. 2, threshold not NaN");
-  int rc = check_params(params);
-  if (rc)
-    return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  RtHipParams p = *params;
-  p.tile_first = 0;
-  p.tile_stride = 1;
-  p.tile_count = tiles_x_of(p.width) * tiles_y_of(p.height);
-  RtHipScene *scene = nullptr;
-  RtHipAccum *acc = nullptr;
-  uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
-  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &scene);
-  if (!rc)
-    rc = rt_hip_accum_create(scene, camera, &p, &acc);
-  if (!rc)
-    rc = rt_hip_accum_run_adaptive(acc, adapt, stats, kernel_seconds, on_checkpoint, user);
-  const bool cancelled = rc == RT_HIP_ECANCELLED; /* the frame of the samples done is still a whole image */
-  if (!rc || cancelled)
-  {
-    int rc2 = rt_hip_accum_read_image(acc, h_rgb, h_rgb8);
-    if (!rc2 && h_tile_samples)
-      rc2 = rt_hip_accum_tile_samples(acc, h_tile_samples);
-    if (rc2)
-      rc = rc2;
-    else if (cancelled)
-      (void)fail(RT_HIP_ECANCELLED, "adaptive render cancelled: the image holds the samples done so far");
-  }
-  if (h_stats)
-    for (int k = 0; k < RT_HIP_NSTATS; k++)
-      h_stats[k] = stats[k];
-  rt_hip_accum_destroy(acc);
+  rc = aov_image_of(scene, camera, params, h_image);
   rt_hip_scene_destroy(scene);
   return rc;
 }
 
-namespace
-{
 /* ---- the denoiser (rt_hip.h, rt_hip_denoise_*) ------------------------------------------------------------------------------
  * Workspace layout for n = w*h pixels, each part 256-B aligned: e[0], e[1] and the guidance (16 B per pixel each), then hits +
  * object (8 B per pixel).  The kernels and their arithmetic are pt_denoise_* in pt_kernel.hip. */
@@ -3171,56 +2200,959 @@ int denoise_image_impl(const float *h_rgb, const RtHipAov *h_aov, int32_t width,
   const bool demod = (params->flags & RT_HIP_DENOISE_DEMODULATE) != 0, edges = (params->flags & RT_HIP_DENOISE_OBJECT_EDGES) != 0;
   /* one allocation: the workspace, then colour (in and out: in place), albedo, normal, depth, hits, object, bytes */
   const size_t ws = denoise_ws_bytes(n), b3 = align256(12u * n), b1 = align256(4u * n);
-  const size_t total = ws + b3 * (demod ? 3u : 2u) + b1 * (edges ? 3u : 2u) + align256(3u * n);
-  char *buf = nullptr;
-  hipError_t e = hipMalloc(&buf, total);
-  if (e == hipSuccess)
-  {
-    char *at = buf + ws;
-    float *rgb = reinterpret_cast<float *>(at);
-    at += b3;
-    RtHipAov d = {};
-    if (demod)
-    {
-      d.albedo = reinterpret_cast<float *>(at);
-      at += b3;
-    }
-    d.normal = reinterpret_cast<float *>(at);
-    at += b3;
-    d.depth = reinterpret_cast<float *>(at);
-    at += b1;
-    d.hits = reinterpret_cast<uint32_t *>(at);
-    at += b1;
-    if (edges)
-    {
-      d.object = reinterpret_cast<uint32_t *>(at);
-      at += b1;
-    }
-    uint8_t *rgb8 = reinterpret_cast<uint8_t *>(at);
-    const std::pair<void *, const void *> in[6] = {{rgb, h_rgb}, {d.albedo, h_aov->albedo}, {d.normal, h_aov->normal},
-                                                   {d.depth, h_aov->depth}, {d.hits, h_aov->hits}, {d.object, h_aov->object}};
-    const size_t bytes[6] = {12u * n, 12u * n, 12u * n, 4u * n, 4u * n, 4u * n};
-    for (int k = 0; k < 6 && e == hipSuccess; k++)
-      if (in[k].first)
-        e = hipMemcpy(in[k].first, in[k].second, bytes[k], hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      rc = denoise_launch(rgb, &d, width, height, params, buf, h_out ? rgb : nullptr, h_out8 ? rgb8 : nullptr, nullptr);
-    if (e == hipSuccess && !rc && h_out)
-      e = hipMemcpy(h_out, rgb, 12u * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !rc && h_out8)
-      e = hipMemcpy(h_out8, rgb8, 3u * n, hipMemcpyDeviceToHost);
-  }
-  if (buf)
-    (void)hipFree(buf);
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc(ws + b3 * (demod ? 3u : 2u) + b1 * (edges ? 3u : 2u) + align256(3u * n)));
+  size_t at = ws;
+  auto part = [&](size_t bytes) { /* the next `bytes` of the allocation */
+    at += bytes;
+    return at - bytes;
+  };
+  float *rgb = buf.at<float>(part(b3));
+  RtHipAov d = {};
+  if (demod)
+    d.albedo = buf.at<float>(part(b3));
+  d.normal = buf.at<float>(part(b3));
+  d.depth = buf.at<float>(part(b1));
+  d.hits = buf.at<uint32_t>(part(b1));
+  if (edges)
+    d.object = buf.at<uint32_t>(part(b1));
+  uint8_t *rgb8 = buf.at<uint8_t>(at);
+  const std::pair<void *, const void *> in[6] = {{rgb, h_rgb}, {d.albedo, h_aov->albedo}, {d.normal, h_aov->normal},
+                                                 {d.depth, h_aov->depth}, {d.hits, h_aov->hits}, {d.object, h_aov->object}};
+  const size_t bytes[6] = {12u * n, 12u * n, 12u * n, 4u * n, 4u * n, 4u * n};
+  for (int k = 0; k < 6; k++)
+    if (in[k].first)
+      HIP_TRY(hipMemcpy(in[k].first, in[k].second, bytes[k], hipMemcpyHostToDevice));
+  rc = denoise_launch(rgb, &d, width, height, params, buf.ptr, h_out ? rgb : nullptr, h_out8 ? rgb8 : nullptr, nullptr);
   if (rc)
     return rc;
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? RT_HIP_ENOMEM : RT_HIP_ERUNTIME, "denoise image: %s", hipGetErrorString(e));
+  if (h_out)
+    HIP_TRY(hipMemcpy(h_out, rgb, 12u * n, hipMemcpyDeviceToHost));
+  if (h_out8)
+    HIP_TRY(hipMemcpy(h_out8, rgb8, 3u * n, hipMemcpyDeviceToHost));
   return RT_HIP_OK;
 }
+
 } // namespace
 
 extern "C" {
+
+const char *rt_hip_last_error(void) { return g_err; }
+
+void rt_hip_set_cancel_flag(const volatile int *flag) { g_cancel = flag; }
+
+int rt_hip_device_count(void) { return usable_devices(); }
+
+int rt_hip_device_info(int device, char *name, size_t name_cap, int *compute_units)
+{
+  if (!have_device(device))
+    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  if (name && name_cap)
+    snprintf(name, name_cap, "%s (%s)", prop.name, prop.gcnArchName);
+  if (compute_units)
+    *compute_units = prop.multiProcessorCount;
+  return RT_HIP_OK;
+}
+
+int rt_hip_scene_create(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
+                        size_t n_meshes, int device, RtHipScene **out_scene)
+{
+  return guarded("rt_hip_scene_create", [&] { return scene_create_impl(spheres, n_spheres, meshes, n_meshes, device, out_scene); });
+}
+
+void rt_hip_release_cache(void) { release_cache_impl(); }
+
+void rt_hip_last_image_phases(double seconds[3])
+{
+  if (seconds)
+    last_phases_impl(seconds);
+}
+
+int rt_hip_set_device_map(const int *map, int n)
+{
+  return guarded("rt_hip_set_device_map", [&] { return set_device_map_impl(map, n); });
+}
+
+uint64_t rt_hip_cache_builds(void) { return cache_builds_impl(); }
+
+int rt_hip_render_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
+                        size_t n_meshes, const RtHipCamera *camera, const RtHipParams *params,
+                        int n_devices, float *h_image_rgb, uint8_t *h_image_rgb8, uint64_t *h_stats,
+                        double *kernel_seconds)
+{
+  return guarded("rt_hip_render_image", [&] {
+    return render_image_impl(spheres, n_spheres, meshes, n_meshes, camera, params, n_devices, h_image_rgb, h_image_rgb8, h_stats,
+                             kernel_seconds);
+  });
+}
+
+void rt_hip_scene_destroy(RtHipScene *scene)
+{
+  if (!scene)
+    return;
+  {
+    DeviceScope scope(scene->device);
+    for (TableSet &t : scene->tables)
+    {
+      if (t.built) (void)hipEventSynchronize(t.built);
+      for (auto &r : t.readers)
+      {
+        (void)hipEventSynchronize(r.second);
+        (void)hipEventDestroy(r.second);
+      }
+      if (t.built) (void)hipEventDestroy(t.built);
+      if (t.owned)
+      {
+        (void)hipFree(t.filt);
+        (void)hipFree(t.bvh_nodes);
+      }
+    }
+    if (scene->park_ws)
+    { /* every launch of this scene must be past its last ring access before the pool can go */
+      (void)hipDeviceSynchronize();
+      park_drop_ws(scene->device);
+    }
+    (void)hipFree(scene->blob);
+  }
+  delete scene;
+}
+
+int rt_hip_scene_device(const RtHipScene *scene) { return scene ? scene->device : -1; }
+
+size_t rt_hip_scene_primitives(const RtHipScene *scene)
+{
+  return scene ? (size_t)scene->view.n_spheres + scene->view.n_triangles : 0;
+}
+
+int rt_hip_scene_hull_facets(const RtHipScene *scene, uint32_t *n_plus, uint32_t *n_minus)
+{
+  if (!scene || !n_plus || !n_minus)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_hull_facets: null argument");
+  *n_plus = *n_minus = 0;
+  const size_t n = scene->view.n_triangles;
+  if (n == 0 || !scene->hull_flags)
+    return 0;
+  return guarded("rt_hip_scene_hull_facets", [&]() -> int {
+    std::vector<uint32_t> obj(n);
+    DeviceScope on(scene->device);
+    HIP_TRY(on.status);
+    HIP_TRY(hipMemcpy(obj.data(), scene->view.tri_object, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++)
+    {
+      *n_plus += (obj[i] & PT_HULL_PLUS) ? 1u : 0u;
+      *n_minus += (obj[i] & PT_HULL_MINUS) ? 1u : 0u;
+    }
+    return 0;
+  });
+}
+
+const char *rt_hip_kernel_name(const RtHipScene *scene, uint32_t integrator)
+{
+  if (!scene)
+    return "";
+  /* a scene whose parked-walk workspace could not be allocated runs on the lane-waiting kernels: report what a launch
+   * takes, so that an out-of-memory fallback cannot pass as a measurement of the parked-walk kernels.  What is assumed of
+   * the launch itself: sums that fit (one sample at depth 0, one chunk), a pending-ray pool of full width --
+   * rt_hip_last_launch_kernel() has the fact. */
+  PtPlanAsk ask = ask_for(scene, integrator, 1, 0, 1, false, 0, park_ws_expected(scene));
+  ask.wide_pend_ok = !(g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_WIDE_PEND);
+  return pt_kernel_name_of(pt_plan_launch(scene->view, ask).kernel);
+}
+
+const char *rt_hip_last_launch_kernel(void) { return pt_kernel_name_of(g_last_kernel); }
+
+int rt_hip_kernel_count(void) { return pt_kernel_count(); }
+
+const char *rt_hip_kernel_launches(int index, uint64_t *launches)
+{
+  if (index < 0 || index >= pt_kernel_count())
+    return nullptr;
+  if (launches)
+    *launches = pt_kernel_launches(index);
+  return pt_kernel_name_of(index);
+}
+
+const char *rt_hip_kernel_for_class(const RtHipSceneClass *c)
+{
+  if (!c)
+    return "";
+  PtSceneView v;
+  memset(&v, 0, sizeof v);
+  v.n_spheres = c->n_spheres;
+  v.n_meshes = c->n_meshes;
+  v.n_triangles = c->n_triangles;
+  v.n_bvh_nodes = c->n_triangles ? std::max(1u, c->n_triangles / 8u) : 0u;
+  v.any_checker = c->any_checker ? 1u : 0u;
+  v.any_refract = c->any_refract ? 1u : 0u;
+  v.any_mirror_glass = c->any_mirror_glass ? 1u : 0u;
+  v.wide_range = c->wide_range ? 1u : 0u;
+  v.mesh_round = c->mesh_round ? 1u : 0u;
+  /* one chunk of samples_per_chunk samples, without a chunk workspace: the class's facts go to the pick unchanged */
+  const PtPlanAsk ask = {.integrator = c->integrator, .samples = c->samples_per_chunk, .max_depth = c->max_depth, .max_emission = c->max_emission,
+                         .sample_chunks = 1, .have_park_ws = c->have_park_ws != 0, .wide_pend_ok = c->wide_pend_ok != 0};
+  return pt_kernel_name_of(pt_plan_launch(v, ask).kernel);
+}
+
+void rt_hip_selftest_fail_alloc(uint32_t mask) { g_fail_alloc.store(mask); }
+
+int rt_hip_selftest_pool_slots(int device, uint32_t *park_slots_per_xcd, uint32_t *pend_slots_per_xcd)
+{
+  if (!have_device(device))
+    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  if (park_slots_per_xcd)
+    *park_slots_per_xcd = pt_pool_slots_per_xcd(true);
+  if (pend_slots_per_xcd)
+    *pend_slots_per_xcd = pt_pool_slots_per_xcd(false);
+  return RT_HIP_OK;
+}
+
+int rt_hip_pool_bytes(int device, size_t *park_ws_bytes, size_t *pend_pool_bytes)
+{
+  if (device < 0 || device >= 64 || device >= usable_devices())
+    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
+  if (park_ws_bytes)
+  {
+    std::lock_guard<std::mutex> lock(g_park_mutex);
+    const ParkPool &p = g_park[device];
+    *park_ws_bytes = p.ws ? park_flag_bytes(p.slots_per_xcd) + (size_t)PT_PARK_XCDS * p.slots_per_xcd * (PT_BLOCK / 64) * (size_t)PT_PARK_WAVE_BYTES : 0;
+  }
+  if (pend_pool_bytes)
+  {
+    std::lock_guard<std::mutex> lock(g_pend_mutex);
+    const PendPool &p = g_pend[device];
+    *pend_pool_bytes = p.ws ? pend_flag_bytes(p.slots_per_xcd) + (size_t)PT_PARK_XCDS * p.slots_per_xcd * p.entries * PT_PEND_FIELDS_HOST * p.columns * sizeof(double) : 0;
+  }
+  return RT_HIP_OK;
+}
+
+int rt_hip_launch_status(int device, uint32_t *flags)
+{
+  uint32_t f = 0;
+  if (flags)
+    *flags = 0;
+  if (!have_device(device))
+    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  int rc = status_take(device, &f);
+  if (rc)
+    return rc;
+  if (flags)
+    *flags = f;
+  return status_to_error(f);
+}
+
+size_t rt_hip_chunk_workspace_bytes(uint32_t tile_count)
+{ /* enough for any scene: the windowed sums of the M_REFRACTION forms are the larger record */
+  return (size_t)tile_count * PT_ACC_WS_WORDS_WIN * sizeof(unsigned long long);
+}
+
+size_t rt_hip_scene_chunk_workspace_bytes(const RtHipScene *scene, uint32_t tile_count)
+{
+  const bool windowed = !scene || scene->view.any_refract;
+  return (size_t)tile_count * (windowed ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long);
+}
+
+uint32_t rt_hip_suggest_chunks(const RtHipScene *scene, uint32_t tile_count, int32_t samples)
+{
+  return rt_hip_suggest_chunks_depth(scene, tile_count, samples, 0);
+}
+
+uint32_t rt_hip_suggest_chunks_depth(const RtHipScene *scene, uint32_t tile_count, int32_t samples, int32_t max_depth)
+{
+  if (!scene || tile_count == 0 || samples < 1)
+    return 1;
+  /* scenes with M_REFRACTION: at least as many chunks as the windowed sums need (pt_refr_pool_fits per chunk) */
+  const uint64_t need = pt_refr_chunk_floor(scene->view, samples, max_depth, tile_count);
+  if (samples < 128)
+    return (uint32_t)need;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, scene->device) != hipSuccess)
+    return (uint32_t)need;
+  /* which body the scene takes (the plan of a launch with a chunk workspace): the parked-walk kernels render a tile per WAVE
+   * (four per workgroup, four workgroups per CU), and a chunk of theirs must be longer -- a wave amortises its walk batches and
+   * its final, partly filled walk over its pool */
+  const PtPlan plan =
+      pt_plan_launch(scene->view, ask_for(scene, RT_HIP_TRACE_PATH, samples, max_depth, 1, true, tile_count, park_ws_expected(scene)));
+  uint64_t want, min_chunk_samples;
+  if (plan.queued)
+  {
+    /* >= 30 rounds of workgroups (the expensive tiles -- those on the mesh -- are few and long: one workgroup of four of them at
+     * 4096 spp outlasts a rank's whole ideal share at N = 8), >= 128 samples per chunk.  One rank's share of config 5 at N = 8,
+     * ms by chunks (tools/shard_chunks.py, profiles/r05_shard_chunks.txt): 4096 spp 1: 608, 2: 505, 4: 465, 8: 447, 12: 443, 16: 443
+     * (ideal 418); 256 spp 1: 39.2, 2: 37.1, 4: 41.8, 8: 42.6 (ideal 27.0).  Round 4's rule (tiles, not workgroups; 64 samples)
+     * gave 2 and 4. */
+    want = 30ull * 4ull * 4ull * (uint64_t)prop.multiProcessorCount;
+  }
+  else
+  {
+    /* aim for >= 20 workgroups per resident slot (5 per CU), so the last, partly filled round
+     * of the launch is a small fraction of it.  (One rank's share of the headline frame at
+     * N = 8 / 4 / 2, ms by chunks: 2: 30.0, 4: 29.3, 6: 29.4, 8: 29.6, 16: 30.9 / 1: 59.1, 2: 57.7, 4: 57.5 / 1: 114.7, 2: 113.4.) */
+    want = 20ull * 5ull * (uint64_t)prop.multiProcessorCount;
+  }
+  /* a chunk keeps >= 128 samples (a workgroup's fixed costs -- staging, keys, culling, the resolve pass -- against its pool: config 3's
+   * share at N = 8, 256 spp, ms by chunks 1: 2.63, 2: 2.61, 4: 2.70, 8: 3.01); the M_REFRACTION forms >= 64 (a refractive sample
+   * is two to three times the rays: the glass mesh's share at N = 8, 256 spp 2: 48.8, 4: 45.9, 8: 46.9) */
+  min_chunk_samples = plan.windowed ? 64 : 128;
+  uint64_t chunks = (want + tile_count - 1) / tile_count;
+  const uint64_t cap = (uint64_t)samples / min_chunk_samples;
+  if (chunks > cap) chunks = cap;
+  if (chunks > 16) chunks = 16;
+  if (chunks < need) chunks = need;
+  return chunks < 1 ? 1u : (uint32_t)chunks;
+}
+
+int rt_hip_render_tiles(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params,
+                        float *d_tiles_rgb, uint8_t *d_tiles_rgb8, uint64_t *d_stats, void *stream)
+{
+  return rt_hip_render_tiles_chunked(scene, camera, params, 1, nullptr, d_tiles_rgb, d_tiles_rgb8, d_stats, stream);
+}
+
+int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params,
+                                uint32_t sample_chunks, void *d_workspace, float *d_tiles_rgb,
+                                uint8_t *d_tiles_rgb8, uint64_t *d_stats, void *stream)
+{
+  if (!scene || !camera || !d_tiles_rgb)
+    return fail(RT_HIP_EINVAL, "scene, camera and d_tiles_rgb are required");
+  if (sample_chunks < 1 || (params && (int64_t)sample_chunks > params->samples))
+    return fail(RT_HIP_EINVAL, "sample_chunks must be in [1, samples]");
+  if (sample_chunks > 1 && !d_workspace)
+    return fail(RT_HIP_EINVAL, "sample_chunks > 1 needs a workspace of rt_hip_chunk_workspace_bytes(tile_count)");
+  return guarded("rt_hip_render_tiles_chunked", [&]() -> int {
+    PtLaunch L;
+    bool empty = false;
+    int rc = launch_prepare(scene, camera, params, L, &empty);
+    if (rc || empty)
+      return rc;
+    L.acc_ws = static_cast<unsigned long long *>(d_workspace);
+    L.tiles_rgb = d_tiles_rgb;
+    L.tiles_rgb8 = d_tiles_rgb8;
+    L.stats = reinterpret_cast<unsigned long long *>(d_stats);
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    rc = launch_device_state(scene, L);
+    if (rc)
+      return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    size_t slot = 0;
+    rc = acquire_tables(scene, L.near_R, st, &L.scene.filt, &L.scene.bvh_nodes, &slot);
+    if (rc)
+      return rc;
+    /* the device's pending-ray pool, where the plan needs one: g_pend_mutex from the lookup until the launch is enqueued */
+    std::unique_lock<std::mutex> pend_lock(g_pend_mutex, std::defer_lock);
+    PtPlan plan;
+    rc = plan_launch(scene, L, sample_chunks, d_workspace != nullptr,
+                     [&](uint32_t entries, uint32_t columns, PtLaunch &launch) {
+                       if (!pend_lock.owns_lock())
+                         pend_lock.lock();
+                       return pend_pool_for(scene->device, entries, columns, launch);
+                     },
+                     &plan);
+    if (!rc && (uint64_t)L.tile_count * L.sample_chunks > 0x7FFFFFFFull)
+      rc = fail(RT_HIP_EINVAL, "tile_count x sample_chunks exceeds the grid limit");
+    const hipError_t e = rc ? hipSuccess : pt_launch_render(L, st, plan.kernel);
+    if (pend_lock.owns_lock())
+      pend_lock.unlock();
+    release_tables(scene, slot, st);
+    if (rc)
+      return rc;
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_kernel_name_of(plan.kernel), hipGetErrorString(e));
+    g_last_kernel = plan.kernel;
+    return RT_HIP_OK;
+  });
+}
+
+/* ---- progressive rendering: one frame accumulated over passes (RtHipAccum, above) ---- */
+
+int rt_hip_accum_create(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, RtHipAccum **out)
+{
+  if (out)
+    *out = nullptr;
+  if (!scene || !camera || !params || !out)
+    return fail(RT_HIP_EINVAL, "scene, camera, params and out are required");
+  if (params->samples < 1)
+    return fail(RT_HIP_EINVAL, "the sample budget (params->samples) must be >= 1");
+  return guarded("rt_hip_accum_create", [&]() -> int {
+    PtLaunch L;
+    bool empty = false;
+    int rc = launch_prepare(scene, camera, params, L, &empty);
+    if (rc)
+      return rc;
+    if (empty)
+      return fail(RT_HIP_EINVAL, "an accumulation needs tile_count >= 1");
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    rc = launch_device_state(scene, L);
+    if (rc)
+      return rc;
+    RtHipAccum *a = new (std::nothrow) RtHipAccum();
+    if (!a)
+      return fail(RT_HIP_ENOMEM, "accumulation: out of host memory");
+    a->scene = scene;
+    /* the plan of a one-shot launch of the whole budget with a chunk workspace and the suggested chunks: the same member, the same
+     * sum form, the same fallback rows; the fixed-point scale is the budget's (launch_prepare) */
+    const uint32_t chunks = rt_hip_suggest_chunks_depth(scene, params->tile_count, params->samples, params->max_depth);
+    PtPlan plan;
+    rc = plan_launch(scene, L, chunks, true,
+                     [&](uint32_t entries, uint32_t columns, PtLaunch &launch) { return pend_pool_own(entries, columns, launch, a->pend); }, &plan);
+    if (!rc && plan.kernel < 0)
+      rc = fail(RT_HIP_ERUNTIME, "no kernel for this scene"); /* unreachable (pt_pick_kernel) */
+    if (rc)
+    {
+      accum_free(a);
+      return rc;
+    }
+    a->kernel = plan.kernel;
+    a->takes_chunks = pt_kernel_takes_chunks(plan.kernel);
+    a->budget = params->samples;
+    a->plan_spc = (int32_t)(((int64_t)params->samples + plan.sample_chunks - 1) / plan.sample_chunks);
+    L.acc_keep = 1u;
+    const size_t bytes = a->takes_chunks ? (size_t)L.tile_count * (plan.windowed ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long)
+                                         : (size_t)L.tile_count * 3u * PT_BLOCK * sizeof(double);
+    hipError_t e = a->sums.alloc(bytes);
+    if (e != hipSuccess)
+    {
+      accum_free(a);
+      return fail(RT_HIP_ENOMEM, "accumulation sums (%zu MB): %s", bytes >> 20, hipGetErrorString(e));
+    }
+    e = hipMemset(a->sums.ptr, 0, bytes);
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(nullptr); /* zero before a pass on any stream adds to them */
+    if (e != hipSuccess)
+    {
+      (void)hipGetLastError();
+      accum_free(a);
+      return fail(RT_HIP_ERUNTIME, "accumulation sums: %s", hipGetErrorString(e));
+    }
+    if (a->takes_chunks)
+      L.acc_ws = a->sums.at<unsigned long long>();
+    else
+      L.slice_ws = a->sums.at<double>();
+    a->L = L;
+    *out = a;
+    return RT_HIP_OK;
+  });
+}
+
+int rt_hip_accum_add(RtHipAccum *a, int32_t samples, uint64_t *d_stats, void *stream)
+{
+  if (!a)
+    return fail(RT_HIP_EINVAL, "accumulation is NULL");
+  if (samples <= 0 || samples > a->budget - a->done)
+    return fail(RT_HIP_EINVAL, "a pass takes 1 .. %d samples (budget %d, %d done), not %d", a->budget - a->done, a->budget, a->done, samples);
+  if (a->broken)
+    return fail(RT_HIP_ERUNTIME, "the accumulation is unusable: an earlier freeze failed on the device");
+  return guarded("rt_hip_accum_add", [&]() -> int {
+    const RtHipScene *scene = a->scene;
+    PtLaunch L = a->L;
+    L.samples = samples;
+    L.sample_first = (uint32_t)a->done;
+    L.stats = reinterpret_cast<unsigned long long *>(d_stats);
+    L.sample_chunks = 1u;
+    /* with frozen tiles the pass renders the live slots only, and the chunks are planned for that many tiles */
+    const uint32_t pass_tiles = a->any_frozen ? a->live_count : L.tile_count;
+    if (pass_tiles == 0u)
+      return RT_HIP_OK; /* every tile is frozen: nothing is rendered and `done` stays */
+    if (a->any_frozen)
+    {
+      L.slot_list = a->slot_list;
+      L.slot_count = a->live_count;
+    }
+    if (a->takes_chunks)
+    { /* no workgroup gets more samples than the plan's chunks have (that is what the windowed words are sized by), and a small
+       * tile count gets the chunks the suggestion asks for.  Capacity: every chunk adds at most one piece below 2^32 to a word of
+       * the tile records, and every chunk has at least one sample, so over all passes a word takes at most budget < 2^31 pieces */
+      uint64_t chunks = ((uint64_t)samples + (uint64_t)a->plan_spc - 1u) / (uint64_t)a->plan_spc;
+      chunks = std::max<uint64_t>(chunks, rt_hip_suggest_chunks_depth(scene, pass_tiles, samples, L.max_depth));
+      chunks = std::min<uint64_t>(chunks, (uint64_t)samples);
+      if ((uint64_t)pass_tiles * chunks > 0x7FFFFFFFull)
+        return fail(RT_HIP_EINVAL, "tile_count x sample_chunks exceeds the grid limit");
+      L.sample_chunks = (uint32_t)chunks;
+    }
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    size_t slot = 0;
+    int rc = acquire_tables(scene, L.near_R, static_cast<hipStream_t>(stream), &L.scene.filt, &L.scene.bvh_nodes, &slot);
+    if (rc)
+      return rc;
+    const hipError_t e = pt_launch_render(L, static_cast<hipStream_t>(stream), a->kernel);
+    release_tables(scene, slot, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "%s pass: %s", pt_kernel_name_of(a->kernel), hipGetErrorString(e));
+    a->done += samples;
+    return RT_HIP_OK;
+  });
+}
+
+int rt_hip_accum_add_host(RtHipAccum *a, int32_t samples, uint64_t *h_stats, double *kernel_seconds)
+{
+  if (kernel_seconds)
+    *kernel_seconds = 0;
+  if (!a)
+    return fail(RT_HIP_EINVAL, "accumulation is NULL");
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  DeviceBuffer d_stats;
+  EventPair timer;
+  HIP_TRY(d_stats.alloc(RT_HIP_NSTATS * sizeof(uint64_t)));
+  HIP_TRY(hipMemset(d_stats.ptr, 0, RT_HIP_NSTATS * sizeof(uint64_t)));
+  HIP_TRY(timer.create());
+  HIP_TRY(timer.start(nullptr));
+  const int rc = rt_hip_accum_add(a, samples, d_stats.at<uint64_t>(), nullptr);
+  if (rc)
+    return rc;
+  HIP_TRY(timer.stop(nullptr));
+  HIP_TRY(timer.wait());
+  uint64_t st[RT_HIP_NSTATS] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpy(st, d_stats.ptr, sizeof st, hipMemcpyDeviceToHost));
+  float ms = 0.f;
+  HIP_TRY(timer.elapsed_ms(&ms));
+  if (h_stats)
+    for (int k = 0; k < RT_HIP_NSTATS; k++)
+      h_stats[k] += st[k];
+  if (kernel_seconds)
+    *kernel_seconds = 1e-3 * (double)ms;
+  return RT_HIP_OK;
+}
+
+int rt_hip_accum_resolve(const RtHipAccum *a, float *d_tiles_rgb, uint8_t *d_tiles_rgb8, void *stream)
+{
+  if (!a || !d_tiles_rgb)
+    return fail(RT_HIP_EINVAL, "accumulation and d_tiles_rgb are required");
+  if (a->done < 1)
+    return fail(RT_HIP_EINVAL, "the accumulation holds no sample yet");
+  if (a->broken)
+    return fail(RT_HIP_ERUNTIME, "the accumulation is unusable: an earlier freeze failed on the device");
+  PtLaunch L = a->L;
+  L.samples = a->done;
+  L.tiles_rgb = d_tiles_rgb;
+  L.tiles_rgb8 = d_tiles_rgb8;
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  const hipError_t e = pt_launch_resolve(L, a->any_frozen ? a->tile_samples.at<uint32_t>() : nullptr, static_cast<hipStream_t>(stream), a->kernel);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "accumulation resolve: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int rt_hip_accum_read_image(const RtHipAccum *a, float *h_rgb, uint8_t *h_rgb8)
+{
+  if (!a || (!h_rgb && !h_rgb8))
+    return fail(RT_HIP_EINVAL, "accumulation and an output are required");
+  const PtLaunch &L = a->L;
+  const size_t tile_vals = (size_t)L.tile_count * PT_TILE_PIXELS * 3, img_vals = (size_t)L.width * L.height * 3;
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  HIP_TRY(hipDeviceSynchronize()); /* the passes, on whatever stream they ran */
+  DeviceBuffer buf;                /* tiles f32 + u8, image f32 + u8 */
+  HIP_TRY(buf.alloc(tile_vals * 5 + img_vals * 5));
+  float *tiles = buf.at<float>(0), *img = buf.at<float>(tile_vals * 5);
+  uint8_t *tiles8 = buf.at<uint8_t>(tile_vals * 4), *img8 = buf.at<uint8_t>(tile_vals * 5 + img_vals * 4);
+  int rc = rt_hip_accum_resolve(a, tiles, tiles8, nullptr);
+  if (rc)
+    return rc;
+  HIP_TRY(hipMemset(img, 0, img_vals * 5));
+  HIP_TRY(pt_launch_untile(tiles, tiles8, L.width, L.height, L.tile_first, L.tile_stride, L.tile_count, img, img8, nullptr));
+  if (h_rgb)
+    HIP_TRY(hipMemcpy(h_rgb, img, img_vals * sizeof(float), hipMemcpyDeviceToHost));
+  if (h_rgb8)
+    HIP_TRY(hipMemcpy(h_rgb8, img8, img_vals, hipMemcpyDeviceToHost));
+  uint32_t flags = 0;
+  rc = status_take(a->scene->device, &flags);
+  return rc ? rc : status_to_error(flags);
+}
+
+int32_t rt_hip_accum_samples(const RtHipAccum *a) { return a ? a->done : 0; }
+
+const char *rt_hip_accum_kernel(const RtHipAccum *a) { return a ? pt_kernel_name_of(a->kernel) : ""; }
+
+void rt_hip_accum_destroy(RtHipAccum *a) { accum_free(a); }
+
+/* ---- adaptive sampling: the error estimate, the freeze, the driver (rt_hip.h) ------------------------------------------------ */
+
+int rt_hip_tile_error(const float *d_cur, const float *d_prev, int32_t width, int32_t height, uint32_t tile_first, uint32_t tile_stride,
+                      uint32_t tile_count, float *d_error, void *stream)
+{
+  if (!d_cur || !d_prev || !d_error)
+    return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error are required");
+  if (width < 1 || height < 1)
+    return fail(RT_HIP_EINVAL, "width and height must be >= 1");
+  if (tile_count == 0)
+    return RT_HIP_OK;
+  if (tile_stride == 0 && tile_count > 1)
+    return fail(RT_HIP_EINVAL, "tile_stride must be >= 1");
+  const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
+  if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
+    return fail(RT_HIP_EINVAL, "tile range outside the image");
+  if (usable_devices() < 1)
+    return fail(RT_HIP_ENODEV, "no usable HIP device");
+  hipPointerAttribute_t attr = {};
+  int on = -1;
+  for (const void *ptr : {static_cast<const void *>(d_cur), static_cast<const void *>(d_prev), static_cast<const void *>(d_error)})
+  {
+    if (hipPointerGetAttributes(&attr, ptr) != hipSuccess || attr.type != hipMemoryTypeDevice)
+    {
+      (void)hipGetLastError();
+      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be device memory");
+    }
+    if (on >= 0 && attr.device != on)
+      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be on one device (%d, %d)", on, attr.device);
+    on = attr.device;
+  }
+  DeviceScope scope(attr.device);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  const hipError_t e = pt_launch_tile_error(d_cur, d_prev, width, height, tile_first, tile_stride, tile_count, d_error, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "tile error: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int rt_hip_accum_freeze(RtHipAccum *a, const float *d_error, double threshold, uint32_t dilate, uint32_t *live_count, void *stream)
+{
+  if (a && !d_error)
+    return fail(RT_HIP_EINVAL, "d_error is required (rt_hip_accum_freeze_mask takes a host mask)");
+  return accum_freeze(a, d_error, nullptr, threshold, dilate, live_count, stream);
+}
+
+int rt_hip_accum_freeze_mask(RtHipAccum *a, const uint8_t *h_keep, uint32_t *live_count, void *stream)
+{
+  if (a && !h_keep)
+    return fail(RT_HIP_EINVAL, "h_keep is required");
+  return accum_freeze(a, nullptr, h_keep, 0.0, 0u, live_count, stream);
+}
+
+int rt_hip_accum_tile_samples(const RtHipAccum *a, uint32_t *h_counts)
+{
+  if (!a || !h_counts)
+    return fail(RT_HIP_EINVAL, "accumulation and h_counts are required");
+  const uint32_t n = a->L.tile_count;
+  if (a->tile_samples)
+  {
+    DeviceScope scope(a->scene->device);
+    HIP_TRY(scope.status);
+    /* a freeze has waited for its stream before it returned: the counts are at rest, and a copy on the null stream is enough */
+    HIP_TRY(hipMemcpy(h_counts, a->tile_samples.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  for (uint32_t k = 0; k < n; k++)
+    if (!a->tile_samples || h_counts[k] == 0u)
+      h_counts[k] = (uint32_t)a->done; /* a live slot holds every sample done so far */
+  return RT_HIP_OK;
+}
+
+uint32_t rt_hip_accum_live_tiles(const RtHipAccum *a) { return !a ? 0u : (a->tile_samples ? a->live_count : a->L.tile_count); }
+
+void rt_hip_adapt_defaults(RtHipAdaptParams *p)
+{
+  if (!p)
+    return;
+  p->min_samples = 16;
+  p->dilate = 1u;
+  p->threshold = 0.02;
+}
+
+int rt_hip_adapt_schedule(int32_t budget, int32_t min_samples, int32_t *targets, int32_t cap)
+{
+  if (budget < 1 || min_samples < 1)
+    return 0;
+  int n = 0;
+  const int64_t h = std::max<int64_t>(1, min_samples / 2);
+  for (int64_t t = h;; t *= 2)
+  {
+    const int32_t target = (int32_t)std::min<int64_t>(t, budget);
+    if (targets && n < cap)
+      targets[n] = target;
+    n++;
+    if (target == budget)
+      break;
+  }
+  return n;
+}
+
+int rt_hip_accum_run_adaptive(RtHipAccum *a, const RtHipAdaptParams *p, uint64_t *h_stats, double *kernel_seconds,
+                              int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles), void *user)
+{
+  if (kernel_seconds)
+    *kernel_seconds = 0;
+  if (!a || !p)
+    return fail(RT_HIP_EINVAL, "accumulation and params are required");
+  int rc = check_adapt(p);
+  if (rc)
+    return rc;
+  if (a->done != 0)
+    return fail(RT_HIP_EINVAL, "the driver starts from an empty accumulation (%d samples done)", a->done);
+  DeviceScope scope(a->scene->device);
+  HIP_TRY(scope.status);
+  double seconds = 0;
+  rc = adaptive_passes(a, p, h_stats, on_checkpoint, user, &seconds);
+  if (kernel_seconds)
+    *kernel_seconds = seconds;
+  return rc;
+}
+
+int rt_hip_selftest_math(int op, const double *h_a, const double *h_b, double *h_out, size_t n, int device)
+{
+  if (!h_a || !h_b || !h_out || op < 0 || op > 9 || (op == 8 && n < 8) || (op == 9 && n % 8 != 0))
+    return fail(RT_HIP_EINVAL, "bad self-test arguments");
+  if (!have_device(device))
+    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
+  if (n == 0)
+    return RT_HIP_OK;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc(3 * n * sizeof(double)));
+  double *d = buf.at<double>();
+  HIP_TRY(hipMemcpy(d, h_a, n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d + n, h_b, n * sizeof(double), hipMemcpyHostToDevice));
+  /* op 8 accumulates into out, starting from what the caller put there */
+  HIP_TRY(op == 8 ? hipMemcpy(d + 2 * n, h_out, n * sizeof(double), hipMemcpyHostToDevice) : hipMemset(d + 2 * n, 0, n * sizeof(double)));
+  HIP_TRY(pt_launch_selftest(op, d, d + n, d + 2 * n, n, nullptr));
+  HIP_TRY(hipMemcpy(h_out, d + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
+int rt_hip_selftest_xcc(uint32_t n_workgroups, uint32_t h_counts[16], int device)
+{
+  if (!h_counts || n_workgroups == 0 || n_workgroups > (1u << 20))
+    return fail(RT_HIP_EINVAL, "bad self-test arguments");
+  if (!have_device(device))
+    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc(16 * sizeof(unsigned int)));
+  HIP_TRY(hipMemset(buf.ptr, 0, 16 * sizeof(unsigned int)));
+  HIP_TRY(pt_launch_selftest_xcc(buf.at<unsigned int>(), n_workgroups, nullptr));
+  HIP_TRY(hipMemcpy(h_counts, buf.ptr, 16 * sizeof(unsigned int), hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
+int rt_hip_selftest_intersect(int kind, const double *h_rays, const double *h_prims, size_t n, double near_R,
+                              uint8_t *h_hit, double *h_tuv, uint64_t *h_keep, int device)
+{
+  if ((kind != 0 && kind != 1) || !h_rays || !h_prims || !h_hit || !h_tuv || !h_keep)
+    return fail(RT_HIP_EINVAL, "bad self-test arguments");
+  if (!(near_R > 0) || !(near_R < 1e15) || n > 0x7FFFFFFFu)
+    return fail(RT_HIP_EINVAL, "near_R must be a positive finite bound, n < 2^31");
+  if (!have_device(device))
+    return fail(RT_HIP_ENODEV, "no HIP device %d", device);
+  if (n == 0)
+    return RT_HIP_OK;
+  return guarded("rt_hip_selftest_intersect", [&]() -> int {
+    /* the records exactly as rt_hip_scene_create lays them out (same helpers) */
+    const size_t rec = kind == 0 ? 4 : 9;
+    std::vector<double> prims(rec * n), entry(PT_ENTRY_SRC_STRIDE * n);
+    double max_center = 0;
+    for (size_t i = 0; i < n; i++)
+    {
+      double *e = &entry[PT_ENTRY_SRC_STRIDE * i];
+      if (kind == 0)
+      {
+        const double *p = h_prims + 4 * i;
+        if (!(std::fabs(p[3]) >= 1e-100) || !(std::fabs(p[3]) <= 1e17))
+          return fail(RT_HIP_ELIMIT, "sphere %zu: |radius| %g outside [1e-100, 1e17]", i, p[3]);
+        sphere_entry(p, p[3], e);
+        memcpy(&prims[4 * i], e, 4 * sizeof(double));
+      }
+      else
+        triangle_entry(h_prims + 9 * i, h_prims + 9 * i + 3, h_prims + 9 * i + 6, &prims[9 * i], e);
+      if (!(e[4] <= 1e17))
+        return fail(RT_HIP_ELIMIT, "primitive %zu: centre beyond 1e17", i);
+      max_center = std::fmax(max_center, e[4]);
+    }
+    const double filt_shift = 12.0 * 5.9604644775390625e-08 * (max_center + near_R) * (1.0 + 1e-9); /* as rt_hip_render_tiles */
+    const size_t n_blocks = (n + 63) / 64;
+    const size_t filt_bytes = (n_blocks * 32 + 1) * (size_t)PT_FILT_STRIDE * 2 * sizeof(float);
+    const size_t b_rays = 6 * n * 8, b_prims = rec * n * 8, b_entry = entry.size() * 8, b_tuv = 3 * n * 8, b_keep = 3 * n * 8;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_tri32 = kind == 1 ? n * PT_TRI32_STRIDE * sizeof(float) : 0;
+    const size_t o_rays = 0, o_prims = o_rays + pad(b_rays), o_entry = o_prims + pad(b_prims), o_filt = o_entry + pad(b_entry),
+                 o_tri32 = o_filt + pad(filt_bytes), o_tuv = o_tri32 + pad(b_tri32), o_keep = o_tuv + pad(b_tuv),
+                 o_hit = o_keep + pad(b_keep), total = o_hit + pad(n);
+    DeviceScope scope(device);
+    HIP_TRY(scope.status);
+    DeviceBuffer d;
+    const hipError_t e = d.alloc(total);
+    if (e != hipSuccess)
+      return fail(RT_HIP_ENOMEM, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
+    HIP_TRY(hipMemset(d.at<char>(o_filt), 0, filt_bytes));
+    HIP_TRY(hipMemcpy(d.at<char>(o_rays), h_rays, b_rays, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.at<char>(o_prims), prims.data(), b_prims, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.at<char>(o_entry), entry.data(), b_entry, hipMemcpyHostToDevice));
+    HIP_TRY(pt_launch_selftest_intersect(kind, d.at<double>(o_rays), d.at<double>(o_prims), d.at<double>(o_entry), d.at<float>(o_filt),
+                                         d.at<float>(o_tri32), (uint32_t)n, near_R, filt_shift, d.at<uint8_t>(o_hit), d.at<double>(o_tuv),
+                                         d.at<unsigned long long>(o_keep), nullptr));
+    HIP_TRY(hipMemcpy(h_hit, d.at<char>(o_hit), n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_tuv, d.at<char>(o_tuv), b_tuv, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_keep, d.at<char>(o_keep), b_keep, hipMemcpyDeviceToHost));
+    return RT_HIP_OK;
+  });
+}
+
+int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t width, int32_t height,
+                  uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *d_image_rgb,
+                  uint8_t *d_image_rgb8, void *stream)
+{
+  if (width < 1 || height < 1)
+    return fail(RT_HIP_EINVAL, "bad image size");
+  if ((d_image_rgb && !d_tiles_rgb) || (d_image_rgb8 && !d_tiles_rgb8))
+    return fail(RT_HIP_EINVAL, "an output image needs its tile buffer");
+  if (tile_count == 0 || (!d_image_rgb && !d_image_rgb8))
+    return RT_HIP_OK;
+  const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
+  if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
+    return fail(RT_HIP_EINVAL, "tile range exceeds the image");
+  hipError_t e = pt_launch_untile(d_tiles_rgb, d_tiles_rgb8, width, height, tile_first, tile_stride, tile_count,
+                                  d_image_rgb, d_image_rgb8, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "pt_untile launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+/* ---- first-hit feature buffers (rt_hip.h, RtHipAov) ----------------------------------------------------------------------
+ * The launch takes launch_prepare's camera-dependent fields and acquire_tables' filter, hierarchy and fp32 triangle table -- what
+ * the beauty kernels' intersect() reads -- and nothing else: not pt_plan_launch (the AOV forms are no rows of the pick table, the
+ * scene alone picks one: pt_aov_pick), nor launch_device_state (the body needs neither the status word nor the parked-walk
+ * workspace: it cannot fail on the device and walks the hierarchy per lane). */
+const char *rt_hip_aov_kernel_name(const RtHipScene *scene) { return scene ? pt_aov_kernel_name_of(pt_aov_pick(scene->view)) : ""; }
+
+int rt_hip_aov_kernel_count(void) { return pt_aov_kernel_count(); }
+
+const char *rt_hip_aov_kernel_launches(int index, uint64_t *launches)
+{
+  if (index < 0 || index >= pt_aov_kernel_count())
+    return nullptr;
+  if (launches)
+    *launches = pt_aov_kernel_launches(index);
+  return pt_aov_kernel_name_of(index);
+}
+
+int rt_hip_render_aov_tiles(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *d_tiles,
+                            void *stream)
+{
+  if (!scene || !camera || !params)
+    return fail(RT_HIP_EINVAL, "scene, camera and params are required");
+  if (!aov_any(d_tiles))
+    return fail(RT_HIP_EINVAL, "d_tiles: at least one output buffer is required");
+  return guarded("rt_hip_render_aov_tiles", [&]() -> int {
+    RtHipParams p = *params;
+    p.max_depth = 0; /* ignored: one intersect() per sample */
+    p.integrator = RT_HIP_TRACE_PATH;
+    PtLaunch L;
+    bool empty = false;
+    int rc = launch_prepare(scene, camera, &p, L, &empty);
+    if (rc || empty)
+      return rc;
+    const PtAovOut out = {d_tiles->albedo, d_tiles->normal, d_tiles->depth, d_tiles->object, d_tiles->hits};
+    const int which = pt_aov_pick(scene->view);
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    size_t slot = 0;
+    rc = acquire_tables(scene, L.near_R, static_cast<hipStream_t>(stream), &L.scene.filt, &L.scene.bvh_nodes, &slot);
+    if (rc)
+      return rc;
+    const hipError_t e = pt_launch_aov(L, out, static_cast<hipStream_t>(stream), which);
+    release_tables(scene, slot, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_aov_kernel_name_of(which), hipGetErrorString(e));
+    return RT_HIP_OK;
+  });
+}
+
+int rt_hip_untile_aov(const RtHipAov *d_tiles, int32_t width, int32_t height, uint32_t tile_first, uint32_t tile_stride,
+                      uint32_t tile_count, const RtHipAov *d_image, void *stream)
+{
+  if (!d_tiles || !d_image || width < 1 || height < 1)
+    return fail(RT_HIP_EINVAL, "tile and image buffers and the image size are required");
+  if (tile_count == 0)
+    return RT_HIP_OK;
+  if (tile_stride == 0 && tile_count > 1)
+    return fail(RT_HIP_EINVAL, "tile_stride must be >= 1");
+  const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
+  if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
+    return fail(RT_HIP_EINVAL, "tile range exceeds the image");
+  const void *src[5] = {d_tiles->albedo, d_tiles->normal, d_tiles->depth, d_tiles->object, d_tiles->hits};
+  void *dst[5] = {d_image->albedo, d_image->normal, d_image->depth, d_image->object, d_image->hits};
+  for (int k = 0; k < 5; k++)
+  {
+    if (!src[k] || !dst[k])
+      continue;
+    const hipError_t e = pt_launch_untile_aov(static_cast<const uint32_t *>(src[k]), k < 2 ? 3u : 1u, width, height, tile_first,
+                                              tile_stride, tile_count, static_cast<uint32_t *>(dst[k]), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "pt_untile_aov launch: %s", hipGetErrorString(e));
+  }
+  return RT_HIP_OK;
+}
+
+int rt_hip_render_aov_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                            const RtHipCamera *camera, const RtHipParams *params, int device, const RtHipAov *h_image)
+{
+  return guarded("rt_hip_render_aov_image",
+                 [&] { return render_aov_image_impl(spheres, n_spheres, meshes, n_meshes, camera, params, device, h_image); });
+}
+
+/* rt_hip_render_adaptive_image: a scene and an accumulation of their own on the logical device, the driver, the frame and the count
+ * map to host arrays.  Synchronous on the null stream. */
+int rt_hip_render_adaptive_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                                 const RtHipCamera *camera, const RtHipParams *params, const RtHipAdaptParams *adapt, int device,
+                                 float *h_rgb, uint8_t *h_rgb8, uint32_t *h_tile_samples, uint64_t *h_stats, double *kernel_seconds,
+                                 int (*on_checkpoint)(void *user, int32_t samples_done, uint32_t live_tiles), void *user)
+{
+  if (kernel_seconds)
+    *kernel_seconds = 0;
+  if (!camera || !params || (!h_rgb && !h_rgb8))
+    return fail(RT_HIP_EINVAL, "camera, params and an output image are required");
+  RtHipAdaptParams defaults;
+  rt_hip_adapt_defaults(&defaults);
+  if (!adapt)
+    adapt = &defaults;
+  int rc = check_adapt(adapt);
+  if (!rc)
+    rc = check_params(params);
+  if (rc)
+    return rc;
+  return guarded("rt_hip_render_adaptive_image", [&]() -> int {
+    int phys = -1;
+    rc = physical_device(device, &phys);
+    if (rc)
+      return rc;
+    RtHipParams p = *params;
+    whole_image(p);
+    RtHipScene *scene = nullptr;
+    RtHipAccum *acc = nullptr;
+    uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
+    rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &scene);
+    if (!rc)
+      rc = rt_hip_accum_create(scene, camera, &p, &acc);
+    if (!rc)
+      rc = rt_hip_accum_run_adaptive(acc, adapt, stats, kernel_seconds, on_checkpoint, user);
+    const bool cancelled = rc == RT_HIP_ECANCELLED; /* the frame of the samples done is still a whole image */
+    if (!rc || cancelled)
+    {
+      int rc2 = rt_hip_accum_read_image(acc, h_rgb, h_rgb8);
+      if (!rc2 && h_tile_samples)
+        rc2 = rt_hip_accum_tile_samples(acc, h_tile_samples);
+      if (rc2)
+        rc = rc2;
+      else if (cancelled)
+        (void)fail(RT_HIP_ECANCELLED, "adaptive render cancelled: the image holds the samples done so far");
+    }
+    if (h_stats)
+      for (int k = 0; k < RT_HIP_NSTATS; k++)
+        h_stats[k] = stats[k];
+    rt_hip_accum_destroy(acc);
+    rt_hip_scene_destroy(scene);
+    return rc;
+  });
+}
 
 void rt_hip_denoise_defaults(RtHipDenoiseParams *params)
 {
@@ -3265,14 +3197,8 @@ int rt_hip_denoise(const float *d_rgb, const RtHipAov *d_aov, int32_t width, int
 int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
                          int device, float *h_out_rgb, uint8_t *h_out_rgb8)
 {
-  try
-  {
-    return denoise_image_impl(h_rgb, h_aov, width, height, params, device, h_out_rgb, h_out_rgb8);
-  }
-  catch (...)
-  {
-    return fail(RT_HIP_ERUNTIME, "unexpected C++ exception in rt_hip_denoise_image");
-  }
+  return guarded("rt_hip_denoise_image",
+                 [&] { return denoise_image_impl(h_rgb, h_aov, width, height, params, device, h_out_rgb, h_out_rgb8); });
 }
 
 } // extern "C"
