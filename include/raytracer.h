@@ -288,6 +288,18 @@ typedef struct
 int render_aov(RtAovImage *out, Object *objects, size_t n_objects, MeshObject *meshes, size_t n_meshes, Camera *camera,
                Options *options);
 
+/* Closest hits of the caller's own rays (include/rt_hip.h, rt_hip_query_rays_host: the contract in full): for each of the n rays,
+ * used as given, what intersect() (raytracer.c:393-464; here: the spheres, then the meshes in array order) finds with hit->t =
+ * DBL_MAX on entry, as a hit iff its t < t_max[i] (t_max NULL: DBL_MAX for every ray).  status[i] (may be NULL): 1 hit, 0 miss,
+ * 2 invalid ray (a non-finite component, a direction whose squared length is farther than 2^-13 from 1, a NaN limit).  hits[i] of a
+ * hit holds t, point, normal and object_id (spheres 0 .. n_objects-1, then meshes) as the reference's arithmetic gives them, bit
+ * for bit, and u, v, the texture coordinates of the WINNER, computed on the host: spheres as raytracer.c:410-411 (libm's atan2),
+ * triangles the :154-167 interpolation of the vertices' tex with the winner's barycentrics.  (The literal scan leaves in u, v what
+ * the last passing triangle wrote, closest or not: a documented difference.)  Any other ray: t = DBL_MAX, object_id = 0xFFFFFFFF,
+ * the rest 0.  Runs on one device, the first of the device map.  Returns 0, or a negative RT_HIP_E* code with the reason on stderr. */
+int intersect_rays(const Ray *rays, size_t n, const double *t_max, Object *objects, size_t n_objects, MeshObject *meshes,
+                   size_t n_meshes, Hit *hits, uint8_t *status);
+
 /* Edge-avoiding a-trous denoise of a frame (include/rt_hip.h, rt_hip_denoise: the contract in full) guided by the first-hit
  * buffers of its own samples: linear_in is the frame's linear mean (render_ex's linear_rgb, width x height x 3 floats), aov its
  * render_aov buffers (normal, depth and hits always; albedo with RT_HIP_DENOISE_DEMODULATE, object_id with _OBJECT_EDGES).

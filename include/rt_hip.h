@@ -365,6 +365,78 @@ const char *rt_hip_aov_kernel_name(const RtHipScene *scene);
 int rt_hip_aov_kernel_count(void);
 const char *rt_hip_aov_kernel_launches(int index, uint64_t *launches);
 
+/* ---- ray queries: the closest hits of rays the caller chooses --------------------------------------------------------------
+ * What the scene scan of the render kernels answers for their own rays, for any rays: picking, line-of-sight and visibility tests,
+ * range sensors, collision probes.  A query takes n rays (0 <= n < 2^32).  Ray i comes from params->source:
+ *   RT_HIP_RAYS_GIVEN      d_rays holds n x 6 doubles (origin, direction), used as given;
+ *   RT_HIP_RAYS_CAMERA_UV  d_rays holds n x 2 doubles (u, v): the ray is get_camera_ray(params->camera, u, v) (raytracer.c:375-384),
+ *                          operation for operation, as the render kernels form it from a sample's two draws; u, v may lie outside [0, 1].
+ * With RT_HIP_RAYS_NORMALIZE in params->flags the direction is first replaced by vec3_normalize(d) (vector.h:53-58):
+ * m = sqrt((x*x + y*y) + z*z), then d * (1.0 / m), fp64, unfused, correctly rounded sqrt and reciprocal.
+ * d_t_max (n doubles; NULL: DBL_MAX for every ray) is a per-ray limit that makes the query a visibility test.
+ * A ray is INVALID (status 2) if any component of its origin is not finite; or any component of the direction the scan would use is
+ * not finite; or | ((dx*dx + dy*dy) + dz*dz) - 1 | > 2^-13 for that direction; or its t_max is NaN.  Every other ray is scanned.
+ * The result is that of intersect() (raytracer.c:393-464) with hit->t = DBL_MAX on entry: spheres 0 .. n_spheres-1, then meshes in
+ * array order, triangles in order, strict <, the first in scan order wins a tie.  The ray is a HIT (status 1) iff the winner's
+ * t < t_max (strict), otherwise a MISS (status 0).  Outputs are structure-of-arrays (RtHipHits; each pointer may be NULL, not all):
+ *   field   per ray    hit                                                                         miss / invalid
+ *   status  uint32     1                                                                           0 / 2
+ *   t       double     the winner's own t (the closest hit's, not what a later, farther primitive    +inf
+ *                      left in the reference's Hit.t)
+ *   object  uint32     rt_hip_scene_create's id (sphere i: i; a mesh: n_spheres + its index)       0xFFFFFFFF
+ *   prim    uint32     triangles: the global index in upload order (through the meshes in array    0xFFFFFFFF
+ *                      order), whatever order the hierarchy stores them in; spheres: 0xFFFFFFFF
+ *   point   3 double   point_at(ray, t) = o + d*t, unfused                                         0
+ *   normal  3 double   as the AOV contract: spheres vec3_normalize(point - centre), triangles       0
+ *                      calculate_surface_normal; never flipped
+ *   bary    2 double   triangles: the winner's own barycentric (u, v) as intersect_triangle leaves  0
+ *                      them (rt_hip_selftest_intersect's h_tuv[1..2]); spheres: 0
+ *   ray     6 double   the ray the scan used, after CAMERA_UV / NORMALIZE (also for misses; invalid rays: as computed)
+ * Everything is fp64 in the reference's order: for every valid ray the outputs equal the compiled reference bit for bit.
+ * params->origin_radius (>= 0, finite) is a hint for how far from the world origin the rays start.  It takes the place of the
+ * camera distance in near_R = 1.5 (origin_radius + reach) + 1 and in everything derived from it (the filter tables); it trades
+ * filter tightness against the fallback and does not change a single output bit: a ray that starts beyond near_R is scanned
+ * without the filter.  near_R >= 1e15: RT_HIP_EINVAL.
+ *   - rt_hip_query_defaults: source GIVEN, flags 0, camera NULL, origin_radius 0.
+ *   - rt_hip_query_rays: asynchronous on `stream`, on the scene's device.  d_rays must be 16-byte aligned.  Arguments are checked
+ *     before the device is looked for (RT_HIP_EINVAL, then RT_HIP_ENODEV).  n == 0 is RT_HIP_OK and launches nothing.  A query takes
+ *     no pool, workspace or status word: it has nothing to run out of.
+ *   - rt_hip_query_rays_host: the same from host arrays, synchronous, with a scene and buffers of its own, on logical device
+ *     `device` of rt_hip_render_image's device map (the HIP device itself without a map).
+ *   - rt_hip_query_kernel_name names the form a scene's queries take; rt_hip_query_kernel_count / _launches list the forms and how
+ *     many launches of each this process has made (the query kernels are not members of the family of rt_hip_kernel_count). */
+enum
+{
+  RT_HIP_RAYS_GIVEN = 0,
+  RT_HIP_RAYS_CAMERA_UV = 1
+};
+enum
+{
+  RT_HIP_RAYS_NORMALIZE = 1u
+};
+typedef struct
+{
+  uint32_t source;           /* RT_HIP_RAYS_GIVEN | RT_HIP_RAYS_CAMERA_UV */
+  uint32_t flags;            /* RT_HIP_RAYS_NORMALIZE */
+  const RtHipCamera *camera; /* host pointer; used with RT_HIP_RAYS_CAMERA_UV */
+  double origin_radius;      /* >= 0, finite */
+} RtHipQueryParams;
+typedef struct
+{
+  uint32_t *status;
+  double *t;
+  uint32_t *object, *prim;
+  double *point, *normal, *bary, *ray; /* 3, 3, 2, 6 doubles per ray */
+} RtHipHits;
+void rt_hip_query_defaults(RtHipQueryParams *params);
+int rt_hip_query_rays(const RtHipScene *scene, const double *d_rays, const double *d_t_max, uint64_t n, const RtHipQueryParams *params,
+                      const RtHipHits *d_hits, void *stream);
+int rt_hip_query_rays_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_rays,
+                           const double *h_t_max, uint64_t n, const RtHipQueryParams *params, int device, const RtHipHits *h_hits);
+const char *rt_hip_query_kernel_name(const RtHipScene *scene);
+int rt_hip_query_kernel_count(void);
+const char *rt_hip_query_kernel_launches(int index, uint64_t *launches);
+
 /* ---- edge-avoiding a-trous denoiser guided by the first-hit buffers ---------------------------------------------------------
  * Inputs: row-major images of w x h pixels (1 <= w, h <= 2^20, w*h < 2^32) on one device -- colour c (3 floats per pixel: the
  * linear mean of rt_hip_render_tiles or rt_hip_accum_resolve after rt_hip_untile) and the RtHipAov buffers of the same frame

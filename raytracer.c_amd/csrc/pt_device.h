@@ -357,6 +357,21 @@ struct PtAovOut
   uint32_t *object, *hits;
 };
 
+/* One ray query (rt_hip.h, rt_hip_query_rays; query_rays in pt_kernel.hip): n rays in, structure-of-arrays answers out.  rays:
+ * n x 6 doubles (origin, direction; 16-byte aligned: a ray is three 16-byte loads) or, with camera_uv, n x 2 doubles (u, v) for the
+ * launch's camera.  t_max: n doubles or null (DBL_MAX for every ray).  Any output may be null (not all: the shim refuses that). */
+struct PtQuery
+{
+  const double *rays;
+  const double *t_max;
+  uint64_t n; /* < 2^32 */
+  uint32_t camera_uv, normalize;
+  uint32_t *status;
+  double *t;
+  uint32_t *object, *prim;
+  double *point, *normal, *bary, *ray; /* 3, 3, 2, 6 doubles per ray */
+};
+
 /* One launch of the denoiser (rt_hip.h, rt_hip_denoise; pt_denoise_* in pt_kernel.hip).  The workspace holds, per pixel of the
  * row-major w x h image: two ping-pong float4 colour buffers e[0], e[1] (the filtered signal, .w = 1 valid / 0 invalid), the
  * guidance float4 (normal, depth) and uint2 (hits, object) the prepare pass packs so that a tap is three loads. */
@@ -456,6 +471,13 @@ int pt_aov_kernel_count(void);
 unsigned long long pt_aov_kernel_launches(int which);
 hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int width, int height, uint32_t tile_first,
                                 uint32_t tile_stride, uint32_t tile_count, uint32_t *image, hipStream_t stream);
+/* the ray-query kernels (pt_kernel.hip: query_rays, PT_QUERY_FAMILY): which form a scene takes, the launch (a ray per lane), names and
+ * launch counters */
+int pt_query_pick(const PtSceneView &scene);
+hipError_t pt_launch_query(const PtLaunch &launch, const PtQuery &query, hipStream_t stream, int which);
+const char *pt_query_kernel_name_of(int which);
+int pt_query_kernel_count(void);
+unsigned long long pt_query_kernel_launches(int which);
 /* the denoiser: the prepare pass and `iterations` filter passes (the last one remodulates and tonemaps) on `stream` */
 hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma_color, hipStream_t stream);
 hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,

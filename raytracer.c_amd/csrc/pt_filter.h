@@ -562,7 +562,18 @@ __device__ __forceinline__ void tri_may_hit32_x2(const float4 *__restrict__ ra, 
 
 /* SPH_LDS (hierarchy kernels with parked walks): the flat filter covers the spheres only, and their part of the pair
  * table is staged in LDS and used in the sign-test form, as in the sphere-only kernels. */
-template <bool TRIS, bool BVH, bool FILT_LDS, bool WALK = true, bool LAST = false, bool SPH_LDS = false, bool FILT_MEM = false>
+/* the per-lane "no rule" switch of scan_filtered: every conservative rule asks FiltRay.far_origin whether the ray is outside its
+ * error bounds; a lane that says so itself gets the same answer.  SWITCH = false (every render kernel): the ray as it is. */
+template <bool SWITCH>
+__device__ __forceinline__ FiltRay rules_switch(FiltRay r, bool no_rules)
+{
+  if (SWITCH && no_rules)
+    r.far_origin = 1u;
+  return r;
+}
+
+template <bool TRIS, bool BVH, bool FILT_LDS, bool WALK = true, bool LAST = false, bool SPH_LDS = false, bool FILT_MEM = false,
+          bool RULE_SWITCH = false>
 __device__ __forceinline__ void scan_filtered(const double *geom, const double *tri_geom,
                                               const f32x2 *__restrict__ filt, double near_R2, uint32_t n_sph,
                                               uint32_t n_entries, const V3 &o, const V3 &d, double &min_t,
@@ -571,8 +582,13 @@ __device__ __forceinline__ void scan_filtered(const double *geom, const double *
                                               uint32_t n_bvh_nodes = 0, const uint32_t *bvh_tri = nullptr,
                                               double filt_shift = 0.0, TriLast *last = nullptr, bool no_prune = false,
                                               const float4 *tri32 = nullptr, const uint32_t *prim_pairs = nullptr,
-                                              BigPrune big = BigPrune{nullptr, 0u}, const MeshBound *mesh_bound = nullptr)
+                                              BigPrune big = BigPrune{nullptr, 0u}, const MeshBound *mesh_bound = nullptr,
+                                              bool no_rules = false)
 {
+  /* no_rules (per lane, read with RULE_SWITCH only; the ray-query kernels, whose rays are the caller's): this ray is outside what the skipping rules are
+   * proven for, so none may drop anything for it -- the filter keeps every primitive, the fp32 pre-tests and the wall pruning
+   * are bypassed, the hierarchy walk enters every box and pre-tests no leaf.  The exact tests alone decide, in scan order.  It
+   * takes the route of a ray that starts beyond near_R, switched on explicitly: the ray itself is left as it is. */
   /* prim_pairs (wave-uniform; pooled kernels' primary trips, FILT_LDS only): per chunk the pairs that a camera ray of
    * this tile can reach (tile_cull); nullptr: every pair */
   /* with a hierarchy the flat filter covers the spheres only */
@@ -596,7 +612,7 @@ __device__ __forceinline__ void scan_filtered(const double *geom, const double *
    * outside fp32's comfortable range never use this form (pt_filter_in_lds). */
   static_assert(!SPH_LDS || (BVH && !FILT_LDS), "SPH_LDS is the sphere filter of the hierarchy kernels");
   constexpr bool SHIFT = (FILT_LDS && !TRIS) || SPH_LDS;
-  const FiltRay fr = filter_ray<SHIFT, SHIFT && !SPH_LDS>(o, d, filt_shift, near_R2);
+  const FiltRay fr = rules_switch<RULE_SWITCH>(filter_ray<SHIFT, SHIFT && !SPH_LDS>(o, d, filt_shift, near_R2), no_rules);
   const float ox = fr.ox, oy = fr.oy, oz = fr.oz;
   const f32x2 dx = fr.dx, dy = fr.dy, dz = fr.dz;
   const bool far_origin = fr.far_origin;

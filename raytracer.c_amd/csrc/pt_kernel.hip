@@ -63,9 +63,10 @@
  *   pt_body_queued.h  render_tiles_queued   (pt_render_tiles_tri_queued*: parked walks, also with M_REFRACTION)
  *   pt_body_static.h  render_tiles_static   (pt_render_tiles_v0, *_refr, pt_whitted_tiles*, *_mem)
  * This file keeps the kernel family (PT_FAMILY: the entry points, their ids and properties), the AOV kernels (render_aov,
- * PT_AOV_FAMILY: first-hit feature buffers, not members of the family), the table-building and self-test kernels, pt_untile,
+ * PT_AOV_FAMILY: first-hit feature buffers, not members of the family), the ray-query kernels (query_rays, PT_QUERY_FAMILY: closest
+ * hits of the caller's rays, a list of their own too), the table-building and self-test kernels, pt_untile,
  * and the host side declared in pt_device.h: the launch plan (pt_plan_launch, around the pick table pt_pick_kernel) and the
- * launchers (pt_launch_render, pt_launch_aov).
+ * launchers (pt_launch_render, pt_launch_aov, pt_launch_query).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -411,6 +412,151 @@ struct PtAovKernelInfo
 #define PT_AOV_INFO(id, name, ...) {#name, name},
 static const PtAovKernelInfo pt_aov_kernels[A_COUNT] = {PT_AOV_FAMILY(PT_AOV_INFO)};
 #undef PT_AOV_INFO
+
+/* ---- ray-query body: a lane = one ray of the caller's, a wave = 64 consecutive rays ---------------------------------------------
+ * rt_hip.h has the contract.  A lane forms its ray (as given, or get_camera_ray of its (u, v) as start_sample forms it; with
+ * `normalize` the direction goes through vec3_normalize first), decides whether it is valid, runs ONE intersect() -- scan_filtered
+ * with min_t = DBL_MAX on entry, as render_aov calls it -- and writes the winner's record, or a miss if the winner is not below
+ * the ray's t_max.  t_max never enters the scan: no rule sees it, the comparison after the scan is the whole visibility test.
+ * The skipping rules of scan_filtered are proven for the renderer's own rays: origins within near_R and directions that are
+ * vec3_normalize results.  A ray that starts beyond near_R takes the far_origin route as a bounce from a far wall does.  A ray
+ * whose direction is in the contract's band but not unit to rounding (| |d|^2 - 1 | > 2^-40; a vec3_normalize result is within
+ * 2^-50) is scanned with no_rules: the bounds at pt_build_filter, tri_may_hit32 and the sign-test form are written for |d| <=
+ * 1.0001 and |d|^2 >= 0.9998, which the band satisfies, but their budgets were evaluated at |d| = 1 (the drift of d2 under the
+ * pull-back, (1 - |d|^2) (2 tol tca + tol^2), is "1e-14" there and 1e-4 of that product at the band's edge), and a caller's ray
+ * is not worth re-deriving them for: the exact tests alone decide it.  The walls are not pruned among themselves (BigPrune is
+ * the pooled body's; render_aov does without it too), and the hull-facet rule and the bounding-sphere probe belong to trace_step
+ * and the parked walks: no query ray meets them.
+ * TRIS / FILT_LDS / GEOM_LDS as render_aov.  No texture is evaluated: no M_CHECKERED twin, no TriLast. */
+template <bool TRIS, bool FILT_LDS, bool GEOM_LDS>
+__device__ __forceinline__ void query_rays(const PtLaunch &L, const PtQuery &Q)
+{
+  static_assert(GEOM_LDS || !FILT_LDS, "a staged filter table comes with staged geometry");
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const SceneCtx S = stage_scene<GEOM_LDS, FILT_LDS>(L, lds);
+  __syncthreads();
+
+  const uint64_t i = (uint64_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+  if (i >= Q.n)
+    return; /* the last wave's spare lanes, the last workgroup's spare waves (no barrier follows) */
+  constexpr bool BVH = TRIS && !FILT_LDS;
+  V3 o, d;
+  if (Q.camera_uv)
+  { /* get_camera_ray (raytracer.c:375-384), as start_sample forms it from its two draws */
+    const double2 uv = reinterpret_cast<const double2 *>(Q.rays)[i];
+    const CameraRegs cam = load_camera(L);
+    const V3 on_plane = v_add(cam.llc, v_add(v_scale(cam.horizontal, uv.x), v_scale(cam.vertical, uv.y)));
+    o = cam.pos;
+    d = v_normalize_fast(v_sub(cam.pos, on_plane));
+  }
+  else
+  { /* a 48-byte record: three 16-byte loads */
+    const double2 *r = reinterpret_cast<const double2 *>(Q.rays) + 3u * i;
+    const double2 a = r[0], b = r[1], c = r[2];
+    o = {a.x, a.y, b.x};
+    d = {b.y, c.x, c.y};
+  }
+  if (Q.normalize)
+    d = v_normalize_fast(d); /* vec3_normalize (vector.h:53-58): zero gives NaN, an overflowing dot gives zero -- both invalid */
+  const double t_max = Q.t_max ? Q.t_max[i] : L.t_start;
+  const double dd = v_dot(d, d);
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);
+  auto finite = [&](double x) { return __builtin_fabs(x) < inf; }; /* false for NaN */
+  const bool valid = finite(o.x) && finite(o.y) && finite(o.z) && finite(d.x) && finite(d.y) && finite(d.z) &&
+                     __builtin_fabs(dd - 1.0) <= 0x1p-13 && t_max == t_max;
+  const bool no_rules = !(__builtin_fabs(dd - 1.0) <= 0x1p-40);
+
+  double min_t = S.t_start, bary_u = 0, bary_v = 0;
+  int best = -1;
+  if (valid)
+    scan_filtered<TRIS, BVH, FILT_LDS, true, false, false, false, true>(S.geom, S.tri, FILT_LDS ? S.filt_lds : S.filt, S.near_R2, S.n_sph, S.n_sph + S.n_tri,
+                                                    o, d, min_t, best, bary_u, bary_v, nullptr, S.bvh_nodes, S.n_bvh_nodes, S.bvh_tri,
+                                                    S.filt_shift, nullptr, false, S.tri32, nullptr, BigPrune{nullptr, 0u}, nullptr,
+                                                    no_rules);
+  const bool hit = valid && best >= 0 && min_t < t_max;
+  uint32_t object = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
+  V3 point = {0, 0, 0}, n = {0, 0, 0};
+  double bu = 0, bv = 0;
+  if (hit)
+  {
+    point = v_add(o, v_scale(d, min_t)); /* point_at */
+    if (!(TRIS && (uint32_t)best >= S.n_sph))
+    {
+      n = v_normalize_fast(v_sub(point, ld3(S.geom + PT_GEOM_STRIDE * best)));
+      object = (uint32_t)best;
+    }
+    else
+    {
+      const uint32_t ti = (uint32_t)best - S.n_sph; /* the scan index: upload order, whatever order the hierarchy visited in */
+      n = ld3(S.tri_normal + 3 * (size_t)ti);       /* calculate_surface_normal */
+      object = S.tri_object[ti] & ~(PT_HULL_PLUS | PT_HULL_MINUS);
+      prim = ti;
+      bu = bary_u;
+      bv = bary_v;
+    }
+  }
+  if (Q.status)
+    Q.status[i] = valid ? (hit ? 1u : 0u) : 2u;
+  if (Q.t)
+    Q.t[i] = hit ? min_t : inf;
+  if (Q.object)
+    Q.object[i] = object;
+  if (Q.prim)
+    Q.prim[i] = prim;
+  if (Q.point)
+  {
+    double *p = Q.point + 3u * i;
+    p[0] = point.x; p[1] = point.y; p[2] = point.z;
+  }
+  if (Q.normal)
+  {
+    double *p = Q.normal + 3u * i;
+    p[0] = n.x; p[1] = n.y; p[2] = n.z;
+  }
+  if (Q.bary)
+    reinterpret_cast<double2 *>(Q.bary)[i] = double2{bu, bv};
+  if (Q.ray)
+  {
+    double2 *p = reinterpret_cast<double2 *>(Q.ray) + 3u * i;
+    p[0] = double2{o.x, o.y}; p[1] = double2{o.z, d.x}; p[2] = double2{d.y, d.z};
+  }
+}
+
+/* ---- the ray-query kernels (rt_hip_query_rays): a list of their own, like the AOV kernels -- no rows of the pick table.  The
+ * scene alone picks the form (pt_query_pick), the five geometric forms of the AOV list:
+ *   pt_query_rays          spheres staged, filter staged (sign-test form)
+ *   pt_query_rays_tri      + triangles through the flat filter and the fp32 pre-test
+ *   pt_query_rays_big      spheres staged, filter by scalar loads
+ *   pt_query_rays_tri_big  + triangles through the hierarchy
+ *   pt_query_rays_mem      geometry from memory, triangles (if any) through the hierarchy
+ * Body: query_rays<TRIS, FILT_LDS, GEOM_LDS>. */
+#define PT_QUERY_FAMILY(X) \
+  X(Q_RAYS,    pt_query_rays,         query_rays<false, true, true>) \
+  X(Q_TRI,     pt_query_rays_tri,     query_rays<true, true, true>) \
+  X(Q_BIG,     pt_query_rays_big,     query_rays<false, false, true>) \
+  X(Q_TRI_BIG, pt_query_rays_tri_big, query_rays<true, false, true>) \
+  X(Q_MEM,     pt_query_rays_mem,     query_rays<true, false, false>)
+
+#define PT_QUERY_ENTRY(id, name, ...) \
+  extern "C" __global__ __launch_bounds__(PT_BLOCK) void name(const PtLaunch L, const PtQuery Q) { __VA_ARGS__(L, Q); }
+PT_QUERY_FAMILY(PT_QUERY_ENTRY)
+#undef PT_QUERY_ENTRY
+
+#define PT_QUERY_ID(id, ...) id,
+enum PtQueryKernelId
+{
+  PT_QUERY_FAMILY(PT_QUERY_ID) Q_COUNT
+};
+#undef PT_QUERY_ID
+typedef void (*PtQueryKernelFn)(const PtLaunch, const PtQuery);
+struct PtQueryKernelInfo
+{
+  const char *name;
+  PtQueryKernelFn fn;
+};
+#define PT_QUERY_INFO(id, name, ...) {#name, name},
+static const PtQueryKernelInfo pt_query_kernels[Q_COUNT] = {PT_QUERY_FAMILY(PT_QUERY_INFO)};
+#undef PT_QUERY_INFO
 
 /* The sample count a resolve divides slot `slot` by: the launch's, or -- an accumulation with frozen tiles (rt_hip_accum_freeze) --
  * the slot's own where it has one (0: the slot is live and holds the launch's count). */
@@ -1648,6 +1794,43 @@ hipError_t pt_launch_aov(const PtLaunch &launch, const PtAovOut &out, hipStream_
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess)
     pt_aov_launch_counts[which].fetch_add(1ull);
+  return e;
+}
+
+/* ---- the ray-query kernels: which form a scene takes, and the launch ------------------------------------------------------- */
+int pt_query_pick(const PtSceneView &scene)
+{
+  if (!pt_geom_in_lds(scene))
+    return Q_MEM;
+  const bool tris = scene.n_triangles != 0u;
+  if (pt_filter_in_lds(scene))
+    return tris ? Q_TRI : Q_RAYS;
+  return tris ? Q_TRI_BIG : Q_BIG;
+}
+
+const char *pt_query_kernel_name_of(int which) { return which >= 0 && which < Q_COUNT ? pt_query_kernels[which].name : ""; }
+int pt_query_kernel_count(void) { return Q_COUNT; }
+
+static std::atomic<unsigned long long> pt_query_launch_counts[Q_COUNT];
+unsigned long long pt_query_kernel_launches(int which) { return which >= 0 && which < Q_COUNT ? pt_query_launch_counts[which].load() : 0ull; }
+
+hipError_t pt_launch_query(const PtLaunch &launch, const PtQuery &query, hipStream_t stream, int which)
+{
+  if (which < 0 || which >= Q_COUNT || query.n == 0u || query.n > 0xFFFFFFFFull)
+    return hipErrorInvalidValue;
+  const size_t lds_bytes = which == Q_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the AOV launch */
+  const PtQueryKernelFn kernel = pt_query_kernels[which].fn;
+  if (lds_bytes > 64 * 1024)
+  {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess)
+      return e;
+  }
+  const uint32_t blocks = (uint32_t)((query.n + PT_BLOCK - 1u) / PT_BLOCK); /* at most 2^24 */
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_BLOCK), lds_bytes, stream, launch, query);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess)
+    pt_query_launch_counts[which].fetch_add(1ull);
   return e;
 }
 

@@ -2233,6 +2233,135 @@ int denoise_image_impl(const float *h_rgb, const RtHipAov *h_aov, int32_t width,
   return RT_HIP_OK;
 }
 
+/* ---- ray queries (rt_hip.h, rt_hip_query_*) ---------------------------------------------------------------------------------
+ * A query's launch takes the scene- and near_R-dependent fields of launch_prepare with origin_radius in the camera distance's
+ * place, and acquire_tables' filter, hierarchy and fp32 triangle table for that near_R -- what intersect() reads -- and nothing
+ * else: no plan, no pool, no status word (as an AOV launch).  The walls are not pruned among themselves (big_pairs stays 0). */
+bool hits_any(const RtHipHits *h)
+{
+  return h && (h->status || h->t || h->object || h->prim || h->point || h->normal || h->bary || h->ray);
+}
+
+/* the arguments of a query that need no device: RT_HIP_EINVAL, or RT_HIP_OK */
+int check_query(const void *rays, bool device_rays, uint64_t n, const RtHipQueryParams *p, const RtHipHits *hits)
+{
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is required");
+  if (!hits_any(hits))
+    return fail(RT_HIP_EINVAL, "hits: at least one output array is required");
+  if (n > 0xFFFFFFFFull)
+    return fail(RT_HIP_EINVAL, "n = %llu: a query takes fewer than 2^32 rays", (unsigned long long)n);
+  if (p->source != RT_HIP_RAYS_GIVEN && p->source != RT_HIP_RAYS_CAMERA_UV)
+    return fail(RT_HIP_EINVAL, "source %u is neither RT_HIP_RAYS_GIVEN nor RT_HIP_RAYS_CAMERA_UV", p->source);
+  if (p->flags & ~(uint32_t)RT_HIP_RAYS_NORMALIZE)
+    return fail(RT_HIP_EINVAL, "unknown flags %#x", p->flags);
+  if (!(p->origin_radius >= 0) || !std::isfinite(p->origin_radius))
+    return fail(RT_HIP_EINVAL, "origin_radius %g must be finite and >= 0", p->origin_radius);
+  if (p->source == RT_HIP_RAYS_CAMERA_UV && !p->camera)
+    return fail(RT_HIP_EINVAL, "RT_HIP_RAYS_CAMERA_UV needs params->camera");
+  if (n != 0 && !rays)
+    return fail(RT_HIP_EINVAL, "rays is required");
+  if (device_rays && (reinterpret_cast<uintptr_t>(rays) & 15u))
+    return fail(RT_HIP_EINVAL, "d_rays must be 16-byte aligned");
+  return RT_HIP_OK;
+}
+
+int query_launch(const RtHipScene *scene, const double *d_rays, const double *d_t_max, uint64_t n, const RtHipQueryParams *p,
+                 const RtHipHits *d_hits, hipStream_t stream)
+{
+  PtLaunch L;
+  memset(&L, 0, sizeof L);
+  L.scene = scene->view;
+  if (p->source == RT_HIP_RAYS_CAMERA_UV)
+  {
+    memcpy(L.cam.pos, p->camera->position, sizeof L.cam.pos);
+    memcpy(L.cam.horizontal, p->camera->horizontal, sizeof L.cam.horizontal);
+    memcpy(L.cam.vertical, p->camera->vertical, sizeof L.cam.vertical);
+    memcpy(L.cam.llc, p->camera->lower_left_corner, sizeof L.cam.llc);
+  }
+  L.near_R = 1.5 * (p->origin_radius + scene->reach) + 1.0;
+  if (!(L.near_R < RT_NEAR_R_LIMIT))
+    return fail(RT_HIP_EINVAL, "origin_radius and scene extent give near_R = %g: not a usable finite bound", L.near_R);
+  L.near_R2 = L.near_R * L.near_R;
+  L.filt_shift = 12.0 * 5.9604644775390625e-08 * (scene->max_center + L.near_R) * (1.0 + 1e-9);
+  mesh_bound_for(scene, L.near_R, L.mesh_bound);
+  L.hull_margin = 2.0; /* (no query ray leaves a facet: the rule is trace_step's) */
+  L.background = 10 / 255.0;
+  L.t_start = 1.7976931348623157e308; /* DBL_MAX */
+  const PtQuery Q = {.rays = d_rays, .t_max = d_t_max, .n = n, .camera_uv = p->source == RT_HIP_RAYS_CAMERA_UV ? 1u : 0u,
+                     .normalize = (p->flags & RT_HIP_RAYS_NORMALIZE) ? 1u : 0u, .status = d_hits->status, .t = d_hits->t,
+                     .object = d_hits->object, .prim = d_hits->prim, .point = d_hits->point, .normal = d_hits->normal,
+                     .bary = d_hits->bary, .ray = d_hits->ray};
+  const int which = pt_query_pick(scene->view);
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  size_t slot = 0;
+  const int rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
+  if (rc)
+    return rc;
+  const hipError_t e = pt_launch_query(L, Q, stream, which);
+  release_tables(scene, slot, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_query_kernel_name_of(which), hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+/* rt_hip_query_rays_host: a scene of its own on the logical device, one allocation for the rays, the limits and the requested
+ * outputs, the query on the null stream, the copies.  Everything is owned by this scope. */
+int query_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_rays,
+                         const double *h_t_max, uint64_t n, const RtHipQueryParams *params, int device, const RtHipHits *h_hits)
+{
+  int rc = check_query(h_rays, false, n, params, h_hits);
+  if (rc)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  if (n == 0)
+    return RT_HIP_OK;
+  struct SceneOwner
+  {
+    RtHipScene *scene = nullptr;
+    ~SceneOwner() { rt_hip_scene_destroy(scene); }
+  } own;
+  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &own.scene);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  const size_t ray_doubles = params->source == RT_HIP_RAYS_CAMERA_UV ? 2u : 6u;
+  void *host[8] = {h_hits->status, h_hits->t, h_hits->object, h_hits->prim, h_hits->point, h_hits->normal, h_hits->bary, h_hits->ray};
+  const size_t bytes_per_ray[8] = {4, 8, 4, 4, 24, 24, 16, 48};
+  size_t off[8], total = align256(ray_doubles * 8u * n);
+  const size_t off_tmax = total;
+  if (h_t_max)
+    total += align256(8u * n);
+  for (int k = 0; k < 8; k++)
+  {
+    off[k] = total;
+    if (host[k])
+      total += align256(bytes_per_ray[k] * n);
+  }
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc(total));
+  HIP_TRY(hipMemcpy(buf.ptr, h_rays, ray_doubles * 8u * n, hipMemcpyHostToDevice));
+  if (h_t_max)
+    HIP_TRY(hipMemcpy(buf.at<char>(off_tmax), h_t_max, 8u * n, hipMemcpyHostToDevice));
+  void *dev[8];
+  for (int k = 0; k < 8; k++)
+    dev[k] = host[k] ? buf.at<char>(off[k]) : nullptr;
+  const RtHipHits d_hits = {(uint32_t *)dev[0], (double *)dev[1], (uint32_t *)dev[2], (uint32_t *)dev[3],
+                            (double *)dev[4],   (double *)dev[5], (double *)dev[6],   (double *)dev[7]};
+  rc = query_launch(own.scene, buf.at<double>(), h_t_max ? buf.at<double>(off_tmax) : nullptr, n, params, &d_hits, nullptr);
+  if (rc)
+    return rc;
+  for (int k = 0; k < 8; k++)
+    if (host[k])
+      HIP_TRY(hipMemcpy(host[k], dev[k], bytes_per_ray[k] * n, hipMemcpyDeviceToHost)); /* (null stream: after the kernel) */
+  return RT_HIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -3063,6 +3192,48 @@ int rt_hip_render_aov_tiles(const RtHipScene *scene, const RtHipCamera *camera, 
     if (e != hipSuccess)
       return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_aov_kernel_name_of(which), hipGetErrorString(e));
     return RT_HIP_OK;
+  });
+}
+
+void rt_hip_query_defaults(RtHipQueryParams *params)
+{
+  if (!params)
+    return;
+  params->source = RT_HIP_RAYS_GIVEN;
+  params->flags = 0u;
+  params->camera = nullptr;
+  params->origin_radius = 0.0;
+}
+
+const char *rt_hip_query_kernel_name(const RtHipScene *scene) { return scene ? pt_query_kernel_name_of(pt_query_pick(scene->view)) : ""; }
+
+int rt_hip_query_kernel_count(void) { return pt_query_kernel_count(); }
+
+const char *rt_hip_query_kernel_launches(int index, uint64_t *launches)
+{
+  if (index < 0 || index >= pt_query_kernel_count())
+    return nullptr;
+  if (launches)
+    *launches = pt_query_kernel_launches(index);
+  return pt_query_kernel_name_of(index);
+}
+
+int rt_hip_query_rays(const RtHipScene *scene, const double *d_rays, const double *d_t_max, uint64_t n, const RtHipQueryParams *params,
+                      const RtHipHits *d_hits, void *stream)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "scene is required");
+  const int rc = check_query(d_rays, true, n, params, d_hits);
+  if (rc || n == 0)
+    return rc;
+  return guarded("rt_hip_query_rays", [&] { return query_launch(scene, d_rays, d_t_max, n, params, d_hits, static_cast<hipStream_t>(stream)); });
+}
+
+int rt_hip_query_rays_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_rays,
+                           const double *h_t_max, uint64_t n, const RtHipQueryParams *params, int device, const RtHipHits *h_hits)
+{
+  return guarded("rt_hip_query_rays_host", [&] {
+    return query_rays_host_impl(spheres, n_spheres, meshes, n_meshes, h_rays, h_t_max, n, params, device, h_hits);
   });
 }
 

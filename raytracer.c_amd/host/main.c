@@ -19,6 +19,9 @@
  *   -n <iters>   denoise (denoise_frame, rt_hip_denoise's defaults with this many iterations, 0..10, one GPU): after the
  *                frame, the first-hit buffers of its own samples (as -a; with -p the samples done), then the denoised PNG to
  *                -o and the frame as rendered to <name>.noisy.png (-o's name without .png)
+ *   -q <x,y>     query instead of rendering: what the ray through the centre of pixel (x, y) of the chosen scene and size hits
+ *                (rt_hip_query_rays_host with u = (x + 0.5) / (w - 1), v = (y + 0.5) / (h - 1)): status, object id,
+ *                primitive, t, point and normal, one line each.  Nothing is rendered or written.
  * Timing is wall-clock (the reference's clock()/integer division, main.c:427-433,
  * reports summed CPU time truncated to seconds -- deliberately not reproduced).
  * SIGINT: the reference's handler writes and frees the live framebuffer from
@@ -107,6 +110,8 @@ typedef struct
   int denoise;     /* -n: iterations + 1; 0: not given */
   int adaptive;    /* -e given */
   double threshold; /* -e: the error at or below which a tile stops */
+  int query;        /* -q given */
+  double qx, qy;    /* -q: the pixel */
   uint64_t seed;
 } Args;
 
@@ -118,7 +123,8 @@ static void usage(const char *prog)
           "          [-i <integrator: 0 trace_path, 1 cast_ray>] [-p <samples per pass, one GPU>]\n"
           "          [-a <prefix of the albedo / normal / depth .pfm files>]\n"
           "          [-n <denoise iterations 0..10: -o denoised, <name>.noisy.png as rendered>]\n"
-          "          [-e <adaptive sampling: tiles whose error estimate is <= this stop early; -s is the budget; one GPU>]\n",
+          "          [-e <adaptive sampling: tiles whose error estimate is <= this stop early; -s is the budget; one GPU>]\n"
+          "          [-q <x,y: print what the ray through the centre of that pixel hits; nothing is rendered>]\n",
           prog);
 }
 
@@ -152,6 +158,19 @@ static int parse_args(int argc, char **argv, Args *a)
       if (!(a->threshold >= 0.0) || (val[0] != '.' && (val[0] < '0' || val[0] > '9')))
         return -1;
       break;
+    case 'q':
+    {
+      char *end = NULL;
+      a->qx = strtod(val, &end);
+      if (end == val || *end != ',')
+        return -1;
+      const char *second = end + 1;
+      a->qy = strtod(second, &end);
+      if (end == second || *end != '\0' || !(a->qx >= 0) || !(a->qy >= 0) || a->qx != floor(a->qx) || a->qy != floor(a->qy))
+        return -1;
+      a->query = 1;
+      break;
+    }
     case 'p':
       a->pass = atoi(val);
       if (a->pass < 1)
@@ -161,6 +180,58 @@ static int parse_args(int argc, char **argv, Args *a)
     }
   }
   return 0;
+}
+
+/* -q: one camera ray through the shim's query entry point for C hosts */
+static int query_pixel(const Args *a, const RtSceneInfo *info, const Object *scene, const MeshObject *meshes, const Camera *camera)
+{
+  if (a->qx >= a->options.width || a->qy >= a->options.height)
+  {
+    fprintf(stderr, "-q %g,%g: outside the %d x %d image\n", a->qx, a->qy, a->options.width, a->options.height);
+    return EXIT_FAILURE;
+  }
+  RtHipMesh *hm = (RtHipMesh *)calloc(info->n_meshes ? info->n_meshes : 1, sizeof *hm);
+  if (!hm)
+    return EXIT_FAILURE;
+  for (size_t m = 0; m < info->n_meshes; m++)
+  {
+    hm[m].flags = meshes[m].flags;
+    memcpy(hm[m].color, &meshes[m].color, sizeof hm[m].color);
+    memcpy(hm[m].emission, &meshes[m].emission, sizeof hm[m].emission);
+    hm[m].num_triangles = meshes[m].mesh.num_triangles;
+    hm[m].vertices = (const RtHipVertex *)meshes[m].mesh.vertices;
+  }
+  const double uv[2] = {(a->qx + 0.5) / ((double)a->options.width - 1.0), (a->qy + 0.5) / ((double)a->options.height - 1.0)};
+  const double *c = &camera->position.x;
+  RtHipQueryParams p;
+  rt_hip_query_defaults(&p);
+  p.source = RT_HIP_RAYS_CAMERA_UV;
+  p.camera = (const RtHipCamera *)camera;
+  p.origin_radius = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+  uint32_t status = 0, object = 0, prim = 0;
+  double t = 0, point[3], normal[3];
+  const RtHipHits h = {&status, &t, &object, &prim, point, normal, NULL, NULL};
+  const int rc = rt_hip_query_rays_host((const RtHipSphere *)scene, info->n_objects, hm, info->n_meshes, uv, NULL, 1, &p, 0, &h);
+  free(hm);
+  if (rc)
+  {
+    fprintf(stderr, "query: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+    return EXIT_FAILURE;
+  }
+  printf("pixel = %.0f,%.0f\n", a->qx, a->qy);
+  printf("status = %u (%s)\n", status, status == 1 ? "hit" : (status == 0 ? "miss" : "invalid ray"));
+  if (status == 1)
+  {
+    printf("object = %u\n", object);
+    if (prim != 0xFFFFFFFFu)
+      printf("primitive = %u\n", prim);
+    else
+      printf("primitive = none (a sphere)\n");
+    printf("t = %.17g\n", t);
+    printf("point = %.17g %.17g %.17g\n", point[0], point[1], point[2]);
+    printf("normal = %.17g %.17g %.17g\n", normal[0], normal[1], normal[2]);
+  }
+  return EXIT_SUCCESS;
 }
 
 int main(int argc, char **argv)
@@ -209,6 +280,9 @@ int main(int argc, char **argv)
   vec3 pos = {info.cam_pos[0], info.cam_pos[1], info.cam_pos[2]};
   vec3 target = {info.cam_target[0], info.cam_target[1], info.cam_target[2]};
   init_camera(&camera, pos, target, &a.options);
+
+  if (a.query)
+    return query_pixel(&a, &info, scene, meshes, &camera);
 
   rt_set_max_depth(a.depth);
   rt_set_seed(a.seed);

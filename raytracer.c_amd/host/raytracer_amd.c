@@ -436,3 +436,75 @@ int denoise_frame(uint8_t *framebuffer, float *linear_out, const float *linear_i
     fprintf(stderr, "denoise_frame: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
   return rc;
 }
+
+int intersect_rays(const Ray *rays, size_t n, const double *t_max, Object *objects, size_t n_objects, MeshObject *meshes,
+                   size_t n_meshes, Hit *hits, uint8_t *status)
+{
+  if (!hits || (n && !rays))
+  {
+    fprintf(stderr, "intersect_rays: rays and hits are required\n");
+    return RT_HIP_EINVAL;
+  }
+  if (n == 0)
+    return 0;
+  /* one block: status, object, prim (words), then t, point, normal, bary (doubles) */
+  uint32_t *words = (uint32_t *)malloc(n * (3 * sizeof(uint32_t) + 9 * sizeof(double)) + sizeof(double));
+  if (!words)
+  {
+    fprintf(stderr, "intersect_rays: out of memory\n");
+    return RT_HIP_ENOMEM;
+  }
+  uint32_t *st = words, *object = words + n, *prim = words + 2 * n;
+  double *t = (double *)(((uintptr_t)(words + 3 * n) + 7u) & ~(uintptr_t)7u), *point = t + n, *normal = point + 3 * n, *bary = normal + 3 * n;
+  RtHipMesh *hm = hip_meshes(meshes, n_meshes);
+  RtHipQueryParams p;
+  rt_hip_query_defaults(&p);
+  const RtHipHits h = {st, t, object, prim, point, normal, bary, NULL};
+  const int rc = rt_hip_query_rays_host((const RtHipSphere *)objects, n_objects, hm, n_meshes, (const double *)rays, t_max, n, &p, 0, &h);
+  free(hm);
+  if (rc)
+  {
+    fprintf(stderr, "intersect_rays: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+    free(words);
+    return rc;
+  }
+  for (size_t i = 0; i < n; i++)
+  {
+    Hit out;
+    memset(&out, 0, sizeof out);
+    out.t = DBL_MAX;
+    out.object_id = 0xFFFFFFFFu;
+    if (st[i] == 1u)
+    {
+      out.t = t[i];
+      out.point = (vec3){point[3 * i], point[3 * i + 1], point[3 * i + 2]};
+      out.normal = (vec3){normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]};
+      out.object_id = object[i];
+      if (prim[i] == 0xFFFFFFFFu)
+      { /* raytracer.c:410-411 */
+        out.u = atan2(out.normal.x, out.normal.z) / (2 * PI) + 0.5;
+        out.v = out.normal.y * 0.5 + 0.5;
+      }
+      else
+      { /* the winner's triangle: prim counts through the meshes in array order; raytracer.c:154-167 */
+        size_t k = prim[i], m = 0;
+        while (m < n_meshes && k >= meshes[m].mesh.num_triangles)
+          k -= meshes[m++].mesh.num_triangles;
+        if (m < n_meshes)
+        {
+          const Vertex *v = meshes[m].mesh.vertices + 3 * k;
+          const double bu = bary[2 * i], bv = bary[2 * i + 1];
+          const vec2 tex = vec2_add(vec2_add(vec2_scalar_mult(v[0].tex, 1 - bu - bv), vec2_scalar_mult(v[1].tex, bu)),
+                                    vec2_scalar_mult(v[2].tex, bv));
+          out.u = tex.x;
+          out.v = tex.y;
+        }
+      }
+    }
+    hits[i] = out;
+    if (status)
+      status[i] = (uint8_t)st[i];
+  }
+  free(words);
+  return 0;
+}

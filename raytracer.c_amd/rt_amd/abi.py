@@ -95,6 +95,22 @@ class RtHipAdaptParams(C.Structure):  # rt_hip.h: adaptive sampling (rt_hip_adap
     _fields_ = [("min_samples", C.c_int32), ("dilate", C.c_uint32), ("threshold", C.c_double)]
 
 
+class RtHipQueryParams(C.Structure):  # rt_hip.h: a ray query (rt_hip_query_defaults), 24 B
+    _fields_ = [("source", C.c_uint32), ("flags", C.c_uint32), ("camera", C.POINTER(Camera)), ("origin_radius", C.c_double)]
+
+
+class RtHipHits(C.Structure):  # rt_hip.h: a query's structure-of-arrays outputs (device or host pointers; NULL: not wanted), 64 B
+    _fields_ = [("status", C.c_void_p), ("t", C.c_void_p), ("object", C.c_void_p), ("prim", C.c_void_p), ("point", C.c_void_p),
+                ("normal", C.c_void_p), ("bary", C.c_void_p), ("ray", C.c_void_p)]
+
+
+RAYS_GIVEN, RAYS_CAMERA_UV = 0, 1   # RtHipQueryParams.source
+RAYS_NORMALIZE = 1                  # RtHipQueryParams.flags
+HIT_FIELDS = ("status", "t", "object", "prim", "point", "normal", "bary", "ray")   # RtHipHits order
+HIT_SHAPES = {"status": ("uint32", 1), "t": ("float64", 1), "object": ("uint32", 1), "prim": ("uint32", 1), "point": ("float64", 3),
+              "normal": ("float64", 3), "bary": ("float64", 2), "ray": ("float64", 6)}   # dtype, values per ray
+NO_HIT = 0xFFFFFFFF                 # object / prim of a miss
+
 ADAPT_CHECKPOINT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_uint32)  # on_checkpoint(user, samples done, live tiles)
 
 DENOISE_DEMODULATE, DENOISE_OBJECT_EDGES = 1, 2   # RT_HIP_DENOISE_*
@@ -182,6 +198,14 @@ SHIM_SYMBOLS = {
     "rt_hip_aov_kernel_name": (C.c_char_p, [C.c_void_p]),
     "rt_hip_aov_kernel_count": (C.c_int, []),
     "rt_hip_aov_kernel_launches": (C.c_char_p, [C.c_int, C.POINTER(C.c_uint64)]),
+    "rt_hip_query_defaults": (None, [C.POINTER(RtHipQueryParams)]),
+    "rt_hip_query_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RtHipQueryParams), C.POINTER(RtHipHits),
+                                    C.c_void_p]),
+    "rt_hip_query_rays_host": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.POINTER(RtHipQueryParams), C.c_int, C.POINTER(RtHipHits)]),
+    "rt_hip_query_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "rt_hip_query_kernel_count": (C.c_int, []),
+    "rt_hip_query_kernel_launches": (C.c_char_p, [C.c_int, C.POINTER(C.c_uint64)]),
     "rt_hip_denoise_defaults": (None, [C.POINTER(RtHipDenoiseParams)]),
     "rt_hip_denoise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rt_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_void_p,
@@ -226,6 +250,8 @@ HOST_SYMBOLS = {
                              C.POINTER(Camera), C.POINTER(Options)]),
     "denoise_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.c_int, C.c_int,
                                 C.POINTER(RtHipDenoiseParams)]),
+    "intersect_rays": (C.c_int, [C.POINTER(Ray), C.c_size_t, C.c_void_p, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
+                                 C.POINTER(Hit), C.c_void_p]),
     "rt_last_render_cancelled": (C.c_int, []),
     "rt_last_render_seconds": (C.c_double, []),
     "rt_last_ray_bounces": (C.c_longlong, []),
@@ -290,6 +316,20 @@ def denoise_params(iterations=None, sigma_color=None, sigma_depth=None, normal_p
     for bit, v in ((DENOISE_DEMODULATE, demodulate), (DENOISE_OBJECT_EDGES, object_edges)):
         if v is not None:
             p.flags = (p.flags | bit) if v else (p.flags & ~bit)
+    return p
+
+
+def query_params(source=RAYS_GIVEN, normalize=False, camera=None, origin_radius=None):
+    """rt_hip_query_defaults() with the given fields replaced (origin_radius None: the default).  The camera is referenced, not
+    copied: keep it alive until the call that takes the params has returned."""
+    p = RtHipQueryParams()
+    load_shim().rt_hip_query_defaults(C.byref(p))
+    p.source = source
+    p.flags = RAYS_NORMALIZE if normalize else 0
+    if camera is not None:
+        p.camera = C.pointer(camera)
+    if origin_radius is not None:
+        p.origin_radius = origin_radius
     return p
 
 

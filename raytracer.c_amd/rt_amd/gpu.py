@@ -191,6 +191,59 @@ class GpuScene:
             out[f] = out[f].view("uint32")
         return out
 
+    def query_kernel_name(self):
+        """the ray-query form this scene's query_rays / query_uv launches take"""
+        return self.shim.rt_hip_query_kernel_name(self.handle).decode()
+
+    def _query(self, rays, per_ray, t_max, params, want):
+        dev = torch.device("cuda", self.device)
+        rays = torch.as_tensor(rays, dtype=torch.float64, device=dev).reshape(-1, per_ray).contiguous()
+        if rays.data_ptr() % 16:
+            rays = rays.clone()   # (a view into a larger tensor: the kernel loads 16 bytes at a time)
+        n = rays.shape[0]
+        if t_max is not None:
+            t_max = torch.as_tensor(t_max, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+            if t_max.numel() != n:
+                raise ValueError("query: t_max must hold one value per ray")
+        out, hits = {}, abi.RtHipHits()
+        for f in want:
+            dtype, k = abi.HIT_SHAPES[f]
+            out[f] = torch.empty((n, k) if k > 1 else (n,), dtype=torch.float64 if dtype == "float64" else torch.int32, device=dev)
+            setattr(hits, f, out[f].data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "wanted")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._query_inputs = (rays, t_max)   # keep alive until the stream has used them
+        _check(self.shim.rt_hip_query_rays(self.handle, C.c_void_p(rays.data_ptr() if n else None),
+                                           C.c_void_p(t_max.data_ptr()) if t_max is not None and n else None, n, C.byref(params),
+                                           C.byref(hits), C.c_void_p(stream)), "rt_hip_query_rays")
+        return out
+
+    def query_rays(self, rays, t_max=None, normalize=False, origin_radius=None, want=abi.HIT_FIELDS):
+        """Closest hits of the caller's rays (rt_hip.h, rt_hip_query_rays): rays [n, 6] float64 (origin, direction; a tensor on the
+        scene's device or anything torch.as_tensor takes), t_max [n] or None, asynchronous on torch's current stream -> dict of
+        device tensors: status / object / prim int32 [n] (the uint32 words of the C-ABI: numpy's .view(np.uint32) reads them as
+        such), t float64 [n], point / normal [n, 3], bary [n, 2], ray [n, 6].  want: which.  origin_radius: how far from the world
+        origin the rays start (a speed hint that changes no output bit; None: the default)."""
+        return self._query(rays, 6, t_max, abi.query_params(abi.RAYS_GIVEN, normalize, None, origin_radius), want)
+
+    def query_uv(self, uv, camera=None, t_max=None, normalize=False, origin_radius=None, want=abi.HIT_FIELDS):
+        """... of the camera rays get_camera_ray(camera, u, v) for uv [n, 2] float64 (camera None: the scene's own; origin_radius
+        None: the camera's distance from the world origin)"""
+        cam = camera if camera is not None else self.scene.camera
+        if origin_radius is None:
+            x, y, z = cam.position.tuple()
+            origin_radius = (x * x + y * y + z * z) ** 0.5
+        return self._query(uv, 2, t_max, abi.query_params(abi.RAYS_CAMERA_UV, normalize, cam, origin_radius), want)
+
+    def pick(self, x, y):
+        """What is under the centre of pixel (x, y) of the scene's own camera and size: u = (x + 0.5) / (w - 1), v = (y + 0.5) /
+        (h - 1) -> dict of Python values: status, object, prim, t, point, normal (synchronises)"""
+        uv = [[(x + 0.5) / (self.scene.width - 1), (y + 0.5) / (self.scene.height - 1)]]
+        out = self.query_uv(uv, want=("status", "object", "prim", "t", "point", "normal"))
+        torch.cuda.synchronize(torch.device("cuda", self.device))
+        res = {f: t.cpu().numpy() for f, t in out.items()}
+        return dict(status=int(res["status"][0]), object=int(res["object"].view("uint32")[0]), prim=int(res["prim"].view("uint32")[0]),
+                    t=float(res["t"][0]), point=tuple(res["point"][0].tolist()), normal=tuple(res["normal"][0].tolist()))
+
     def denoised_image(self, seed, samples, **params):
         """The whole frame of `samples` per pixel (render_image), its first-hit buffers of the same samples, and the denoise
         (rt_hip_denoise; params: abi.denoise_params' keywords) -> numpy (noisy f32 [H,W,3], denoised f32 [H,W,3], denoised u8 [H,W,3])"""
@@ -459,3 +512,29 @@ def adaptive_image_host(scene, seed, samples, device=0, max_depth=None, integrat
                                              C.byref(ap), device, img.ctypes.data, img8.ctypes.data, counts.ctypes.data, stats,
                                              C.byref(secs), None, None), "rt_hip_render_adaptive_image")
     return img, img8, counts, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3]), secs.value
+
+
+def query_rays_host(scene, rays, t_max=None, normalize=False, origin_radius=None, camera=None, device=0, want=abi.HIT_FIELDS):
+    """rt_hip_query_rays_host(): the C hosts' entry point (its own scene and buffers on logical device `device`, synchronous).
+    rays: [n, 6] float64 (origin, direction), or with `camera` (an abi.Camera) [n, 2] (u, v) -> dict of numpy arrays: status /
+    object / prim uint32 [n], t float64 [n], point / normal [n, 3], bary [n, 2], ray [n, 6]"""
+    import numpy as np
+    shim = abi.load_shim()
+    per_ray = 2 if camera is not None else 6
+    rays = np.ascontiguousarray(np.asarray(rays, dtype=np.float64).reshape(-1, per_ray))
+    n = rays.shape[0]
+    if t_max is not None:
+        t_max = np.ascontiguousarray(np.asarray(t_max, dtype=np.float64).reshape(-1))
+        if t_max.size != n:
+            raise ValueError("query_rays_host: t_max must hold one value per ray")
+    p = abi.query_params(abi.RAYS_CAMERA_UV if camera is not None else abi.RAYS_GIVEN, normalize, camera, origin_radius)
+    out, hits = {}, abi.RtHipHits()
+    for f in want:
+        dtype, k = abi.HIT_SHAPES[f]
+        out[f] = np.zeros((n, k) if k > 1 else (n,), dtype=dtype)
+        setattr(hits, f, out[f].ctypes.data)
+    meshes = scene.hip_meshes()
+    _check(shim.rt_hip_query_rays_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, rays.ctypes.data,
+                                       t_max.ctypes.data if t_max is not None else None, n, C.byref(p), device, C.byref(hits)),
+           "rt_hip_query_rays_host")
+    return out
