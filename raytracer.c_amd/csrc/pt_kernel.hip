@@ -57,8 +57,8 @@
  *   pt_math.h         vectors, RNG draws, fixed-point terms, tonemap, atan2_tab / cube / frac1, PT_DIAG / PT_PHASE macros
  *   pt_intersect.h    exact_sphere / exact_triangle (fp64, the reference's operation order), the hierarchy in packed fp32
  *   pt_filter.h       the phase-1 filter (three forms), BigPrune, tile_cull, the fp32 triangle pre-test, scan_filtered
- *   pt_scene_ctx.h    SceneCtx / stage_scene, Path, pending-ray stacks, windowed sums, camera, start_sample
- *   pt_trace.h        trace_step (trace_path), whitted_step (cast_ray), finish_pixels / store_tile
+ *   pt_scene_ctx.h    SceneCtx / stage_scene, intersect_scene (scan_filtered over a SceneCtx, callers without a TriLast), Path, pending-ray stacks, windowed sums, camera, start_sample
+ *   pt_trace.h        trace_step (trace_path), whitted_step (cast_ray), tile_pixel, finish_pixels / store_tile_pixels / store_tile
  *   pt_body_pooled.h  render_tiles_pooled   (pt_render_tiles[_tri][_big][_chk], _pool_mem*, _refr_pool*)
  *   pt_body_queued.h  render_tiles_queued   (pt_render_tiles_tri_queued*: parked walks, also with M_REFRACTION)
  *   pt_body_static.h  render_tiles_static   (pt_render_tiles_v0, *_refr, pt_whitted_tiles*, *_mem)
@@ -66,7 +66,8 @@
  * PT_AOV_FAMILY: first-hit feature buffers, not members of the family), the ray-query kernels (query_rays, PT_QUERY_FAMILY: closest
  * hits of the caller's rays, a list of their own too), the table-building and self-test kernels, pt_untile,
  * and the host side declared in pt_device.h: the launch plan (pt_plan_launch, around the pick table pt_pick_kernel) and the
- * launchers (pt_launch_render, pt_launch_aov, pt_launch_query).
+ * launchers (pt_launch_render, pt_launch_aov, pt_launch_query).  The three lists are a PtKernelList each (rows + launch
+ * counters) and the three launchers go through launch_staged (dynamic-LDS limit, launch, error).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -217,12 +218,36 @@ PT_FAMILY(PT_ENTRY)
 PT_FAMILY_DEV(PT_ENTRY)
 #undef PT_ENTRY
 
-#define PT_ID(id, ...) id,
+/* ---- a kernel list on the host: the rows an X-macro list generates, and how often each was launched in this process
+ * (what a test run actually exercised).  The three lists (PT_FAMILY, PT_AOV_FAMILY, PT_QUERY_FAMILY) are one of these each;
+ * pt_*_name_of / _count / _launches (pt_device.h) ask it.  The lists' ids come from PT_LIST_ID, the rows of the two plain
+ * lists from PT_LIST_INFO; the family's rows carry more (PT_INFO), and each list's entry points have their own signature, so
+ * the three ENTRY macros stay apart. */
+template <class Info, int N>
+struct PtKernelList
+{
+  Info info[N];
+  std::atomic<unsigned long long> counts[N];
+  bool valid(int i) const { return i >= 0 && i < N; }
+  const Info &operator[](int i) const { return info[i]; }
+  const char *name_of(int i) const { return valid(i) ? info[i].name : ""; }
+  unsigned long long launches(int i) const { return valid(i) ? counts[i].load() : 0ull; }
+  void launched(int i) { counts[i].fetch_add(1ull); }
+};
+/* a row of a list without properties (the AOV and the ray-query kernels) */
+template <class Fn>
+struct PtEntryInfo
+{
+  const char *name;
+  Fn fn;
+};
+#define PT_LIST_ID(id, ...) id,
+#define PT_LIST_INFO(id, name, ...) {#name, name},
+
 enum PtKernelId
 {
-  PT_FAMILY(PT_ID) PT_FAMILY_DEV(PT_ID) K_COUNT
+  PT_FAMILY(PT_LIST_ID) PT_FAMILY_DEV(PT_LIST_ID) K_COUNT
 };
-#undef PT_ID
 typedef void (*PtKernelFn)(const PtLaunch);
 struct PtKernelInfo
 {
@@ -234,7 +259,7 @@ struct PtKernelInfo
   uint32_t pend_columns() const { return has(WIDE_PEND) ? 4u * 512u : PT_PEND_COLUMNS; }
 };
 #define PT_INFO(id, name, bounds, props, ...) {#name, name, name##_list, props},
-static const PtKernelInfo pt_kernels[K_COUNT] = {PT_FAMILY(PT_INFO) PT_FAMILY_DEV(PT_INFO)};
+static PtKernelList<PtKernelInfo, K_COUNT> pt_kernels = {{PT_FAMILY(PT_INFO) PT_FAMILY_DEV(PT_INFO)}};
 #undef PT_INFO
 
 /* ---- AOV body: a workgroup = four tiles, a wave = one tile, a lane = one pixel ----------------------------------------------
@@ -268,9 +293,8 @@ __device__ __forceinline__ void render_aov(const PtLaunch &L, const PtAovOut &O)
   if (slot >= L.tile_count)
     return; /* the last workgroup's spare waves (no barrier follows) */
   const uint32_t tile = L.tile_first + slot * L.tile_stride;
-  const uint32_t px = (tile % L.tiles_x) * PT_TILE + (lane & 7u);
-  const uint32_t py = (tile / L.tiles_x) * PT_TILE + (lane >> 3);
-  const bool inside = px < (uint32_t)L.width && py < (uint32_t)L.height;
+  uint32_t px, py;
+  const bool inside = tile_pixel(L.tiles_x, tile, lane, L.width, L.height, px, py);
   const uint32_t pixel = py * (uint32_t)L.width + px;
   const uint64_t pixel_key = rt_rng_pixel_key(L.seed, pixel);
   const CameraRegs cam = load_camera(L);
@@ -397,21 +421,12 @@ __device__ __forceinline__ void render_aov(const PtLaunch &L, const PtAovOut &O)
 PT_AOV_FAMILY(PT_AOV_ENTRY)
 #undef PT_AOV_ENTRY
 
-#define PT_AOV_ID(id, ...) id,
 enum PtAovKernelId
 {
-  PT_AOV_FAMILY(PT_AOV_ID) A_COUNT
+  PT_AOV_FAMILY(PT_LIST_ID) A_COUNT
 };
-#undef PT_AOV_ID
 typedef void (*PtAovKernelFn)(const PtLaunch, const PtAovOut);
-struct PtAovKernelInfo
-{
-  const char *name;
-  PtAovKernelFn fn;
-};
-#define PT_AOV_INFO(id, name, ...) {#name, name},
-static const PtAovKernelInfo pt_aov_kernels[A_COUNT] = {PT_AOV_FAMILY(PT_AOV_INFO)};
-#undef PT_AOV_INFO
+static PtKernelList<PtEntryInfo<PtAovKernelFn>, A_COUNT> pt_aov_kernels = {{PT_AOV_FAMILY(PT_LIST_INFO)}};
 
 /* ---- ray-query body: a lane = one ray of the caller's, a wave = 64 consecutive rays ---------------------------------------------
  * rt_hip.h has the contract.  A lane forms its ray (as given, or get_camera_ray of its (u, v) as start_sample forms it; with
@@ -439,7 +454,6 @@ __device__ __forceinline__ void query_rays(const PtLaunch &L, const PtQuery &Q)
   const uint64_t i = (uint64_t)blockIdx.x * PT_BLOCK + threadIdx.x;
   if (i >= Q.n)
     return; /* the last wave's spare lanes, the last workgroup's spare waves (no barrier follows) */
-  constexpr bool BVH = TRIS && !FILT_LDS;
   V3 o, d;
   if (Q.camera_uv)
   { /* get_camera_ray (raytracer.c:375-384), as start_sample forms it from its two draws */
@@ -469,10 +483,7 @@ __device__ __forceinline__ void query_rays(const PtLaunch &L, const PtQuery &Q)
   double min_t = S.t_start, bary_u = 0, bary_v = 0;
   int best = -1;
   if (valid)
-    scan_filtered<TRIS, BVH, FILT_LDS, true, false, false, false, true>(S.geom, S.tri, FILT_LDS ? S.filt_lds : S.filt, S.near_R2, S.n_sph, S.n_sph + S.n_tri,
-                                                    o, d, min_t, best, bary_u, bary_v, nullptr, S.bvh_nodes, S.n_bvh_nodes, S.bvh_tri,
-                                                    S.filt_shift, nullptr, false, S.tri32, nullptr, BigPrune{nullptr, 0u}, nullptr,
-                                                    no_rules);
+    intersect_scene<TRIS, FILT_LDS, true>(S, o, d, min_t, best, bary_u, bary_v, {.big = false, .no_rules = no_rules});
   const bool hit = valid && best >= 0 && min_t < t_max;
   uint32_t object = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
   V3 point = {0, 0, 0}, n = {0, 0, 0};
@@ -542,21 +553,12 @@ __device__ __forceinline__ void query_rays(const PtLaunch &L, const PtQuery &Q)
 PT_QUERY_FAMILY(PT_QUERY_ENTRY)
 #undef PT_QUERY_ENTRY
 
-#define PT_QUERY_ID(id, ...) id,
 enum PtQueryKernelId
 {
-  PT_QUERY_FAMILY(PT_QUERY_ID) Q_COUNT
+  PT_QUERY_FAMILY(PT_LIST_ID) Q_COUNT
 };
-#undef PT_QUERY_ID
 typedef void (*PtQueryKernelFn)(const PtLaunch, const PtQuery);
-struct PtQueryKernelInfo
-{
-  const char *name;
-  PtQueryKernelFn fn;
-};
-#define PT_QUERY_INFO(id, name, ...) {#name, name},
-static const PtQueryKernelInfo pt_query_kernels[Q_COUNT] = {PT_QUERY_FAMILY(PT_QUERY_INFO)};
-#undef PT_QUERY_INFO
+static PtKernelList<PtEntryInfo<PtQueryKernelFn>, Q_COUNT> pt_query_kernels = {{PT_QUERY_FAMILY(PT_LIST_INFO)}};
 
 /* The sample count a resolve divides slot `slot` by: the launch's, or -- an accumulation with frozen tiles (rt_hip_accum_freeze) --
  * the slot's own where it has one (0: the slot is live and holds the launch's count). */
@@ -574,6 +576,7 @@ __device__ __forceinline__ void resolve_finish_pixels(const PtLaunch &L, int32_t
   if (threadIdx.x < PT_TILE_PIXELS * 3)
   {
     const uint32_t t = threadIdx.x / 3u, c = threadIdx.x - 3u * t;
+    /* tile_pixel, written out as in finish_pixels: the call moves pt_resolve_tiles */
     const bool inside = (tile % L.tiles_x) * PT_TILE + (t & 7u) < (uint32_t)L.width &&
                         (tile / L.tiles_x) * PT_TILE + (t >> 3) < (uint32_t)L.height;
     const double inv_s = 1.0 / (double)samples;
@@ -599,6 +602,7 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
     if (threadIdx.x < PT_TILE_PIXELS * 3)
     {
       const uint32_t t = threadIdx.x / 3u, c = threadIdx.x - 3u * t;
+      /* tile_pixel, written out: the call moves pt_resolve_tiles */
       const bool inside = (tile % L.tiles_x) * PT_TILE + (t & 7u) < (uint32_t)L.width && (tile / L.tiles_x) * PT_TILE + (t >> 3) < (uint32_t)L.height;
       unsigned long long w[PT_WIN_N];
 #pragma unroll
@@ -616,11 +620,7 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
     resolve_finish_pixels(L, samples, L.acc_ws + (size_t)slot * (PT_TILE_PIXELS * 3),
                           L.acc_ws + (size_t)L.tile_count * (PT_TILE_PIXELS * 3) + (size_t)slot * 3, tile, out_f, out_b);
   __syncthreads();
-  if (threadIdx.x < PT_TILE_PIXELS * 3)
-    L.tiles_rgb[(size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x] = out_f[threadIdx.x];
-  if (L.tiles_rgb8 && threadIdx.x < PT_TILE_PIXELS * 3 / 4)
-    reinterpret_cast<uint32_t *>(L.tiles_rgb8)[(size_t)slot * (PT_TILE_PIXELS * 3 / 4) + threadIdx.x] =
-        reinterpret_cast<const uint32_t *>(out_b)[threadIdx.x];
+  store_tile_pixels(L, out_f, out_b, slot);
 }
 
 /* Resolve of an accumulation on the static body (rt_hip_accum_resolve): the slice sums its passes left in L.slice_ws -> pixel
@@ -636,9 +636,8 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_slices(const P
   const uint32_t slice = lane & (PT_SLICES - 1);
   const uint32_t slot = blockIdx.x;
   const uint32_t tile = L.tile_first + slot * L.tile_stride;
-  const uint32_t px = (tile % L.tiles_x) * PT_TILE + (pix_in_tile & 7u);
-  const uint32_t py = (tile / L.tiles_x) * PT_TILE + (pix_in_tile >> 3);
-  const bool inside = px < (uint32_t)L.width && py < (uint32_t)L.height;
+  uint32_t px, py;
+  const bool inside = tile_pixel(L.tiles_x, tile, pix_in_tile, L.width, L.height, px, py);
   const double *const sum = L.slice_ws + (size_t)slot * (3u * PT_BLOCK) + threadIdx.x;
   V3 acc = {sum[0], sum[PT_BLOCK], sum[2 * PT_BLOCK]};
   acc.x += __shfl_xor(acc.x, 1);
@@ -658,11 +657,7 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_slices(const P
     out_b[3 * pix_in_tile + 2] = inside ? tonemap(mean.z) : 0;
   }
   __syncthreads();
-  if (threadIdx.x < PT_TILE_PIXELS * 3)
-    L.tiles_rgb[(size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x] = out_f[threadIdx.x];
-  if (L.tiles_rgb8 && threadIdx.x < PT_TILE_PIXELS * 3 / 4)
-    reinterpret_cast<uint32_t *>(L.tiles_rgb8)[(size_t)slot * (PT_TILE_PIXELS * 3 / 4) + threadIdx.x] =
-        reinterpret_cast<const uint32_t *>(out_b)[threadIdx.x];
+  store_tile_pixels(L, out_f, out_b, slot);
 }
 
 /* ---- adaptive sampling (rt_hip.h: rt_hip_tile_error, rt_hip_accum_freeze) ---------------------------------------------------
@@ -680,7 +675,7 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_tile_error(const float
     return;
   const uint32_t tile = tile_first + slot * tile_stride;
   const uint32_t tx0 = (tile % tiles_x) * PT_TILE, ty0 = (tile / tiles_x) * PT_TILE;
-  const bool inside = tx0 + (lane & 7u) < (uint32_t)width && ty0 + (lane >> 3) < (uint32_t)height;
+  const bool inside = tx0 + (lane & 7u) < (uint32_t)width && ty0 + (lane >> 3) < (uint32_t)height; /* tile_pixel, written out: the call moves pt_tile_error */
   const uint32_t valid = min((uint32_t)PT_TILE, (uint32_t)width - tx0) * min((uint32_t)PT_TILE, (uint32_t)height - ty0);
   const size_t at = (size_t)slot * (PT_TILE_PIXELS * 3) + 3u * lane;
   const float c0 = cur[at], c1 = cur[at + 1], c2 = cur[at + 2], p0 = prev[at], p1 = prev[at + 1], p2 = prev[at + 2];
@@ -1107,6 +1102,7 @@ extern "C" __global__ __launch_bounds__(256) void pt_untile(const float *tiles_r
   {
     const uint32_t k = (uint32_t)(idx / PT_TILE_PIXELS), pit = (uint32_t)(idx % PT_TILE_PIXELS);
     const uint32_t tile = tile_first + k * tile_stride;
+    /* tile_pixel, written out: the call moves pt_untile (though not pt_untile_aov below, which has it) */
     const uint32_t x = (tile % tiles_x) * PT_TILE + (pit & 7u);
     const uint32_t y = (tile / tiles_x) * PT_TILE + (pit >> 3);
     if (x >= (uint32_t)width || y >= (uint32_t)height)
@@ -1139,9 +1135,8 @@ extern "C" __global__ __launch_bounds__(256) void pt_untile_aov(const uint32_t *
     const uint32_t c = (uint32_t)(idx - px * channels);
     const uint32_t k = (uint32_t)(px / PT_TILE_PIXELS), pit = (uint32_t)(px % PT_TILE_PIXELS);
     const uint32_t tile = tile_first + k * tile_stride;
-    const uint32_t x = (tile % tiles_x) * PT_TILE + (pit & 7u);
-    const uint32_t y = (tile / tiles_x) * PT_TILE + (pit >> 3);
-    if (x >= (uint32_t)width || y >= (uint32_t)height)
+    uint32_t x, y;
+    if (!tile_pixel(tiles_x, tile, pit, width, height, x, y))
       continue;
     image[((size_t)y * width + x) * channels + c] = tiles[idx];
   }
@@ -1549,12 +1544,9 @@ PtPlan pt_plan_launch(const PtSceneView &scene, const PtPlanAsk &a)
   return p;
 }
 
-const char *pt_kernel_name_of(int which) { return which >= 0 && which < K_COUNT ? pt_kernels[which].name : ""; }
+const char *pt_kernel_name_of(int which) { return pt_kernels.name_of(which); }
 int pt_kernel_count(void) { return K_COUNT; }
-
-/* launches per family member in this process (rt_hip_kernel_launches): what a test run actually exercised */
-static std::atomic<unsigned long long> pt_launch_counts[K_COUNT];
-unsigned long long pt_kernel_launches(int which) { return which >= 0 && which < K_COUNT ? pt_launch_counts[which].load() : 0ull; }
+unsigned long long pt_kernel_launches(int which) { return pt_kernels.launches(which); } /* rt_hip_kernel_launches */
 
 /* slots per XCD a pool must offer so that every resident workgroup of the kernels that take one finds a slot: CUs per XCD x
  * the most workgroups of any such kernel a CU holds (occupancy without dynamic LDS: an upper bound), + 25 %.  Until round 5
@@ -1624,9 +1616,25 @@ hipError_t pt_launch_build_tables(const PtSceneView &scene, double near_R, float
   return hipGetLastError();
 }
 
+/* One launch of a kernel that stages the scene in dynamic LDS (workgroups of PT_BLOCK threads).  Beyond 64 KB the kernel's
+ * limit is raised first.  The attribute belongs to the (kernel, current device) pair: set whenever it is needed -- a
+ * process-wide "already raised" note would skip devices 1..N-1 of the multi-device path (round-2 advisor finding). */
+template <class... Params, class... Args>
+static hipError_t launch_staged(void (*fn)(Params...), uint32_t blocks, size_t lds_bytes, hipStream_t stream, const Args &...args)
+{
+  if (lds_bytes > 64 * 1024)
+  {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess)
+      return e;
+  }
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(PT_BLOCK), lds_bytes, stream, args...);
+  return hipGetLastError();
+}
+
 hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int which)
 {
-  if (which < 0 || which >= K_COUNT)
+  if (!pt_kernels.valid(which))
     return hipErrorInvalidValue;
   size_t extra_lds = 0;
 #ifdef PT_DEV_KERNELS
@@ -1654,14 +1662,6 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
   if (queued) /* the spheres' filter pairs (staged forms), then per-lane traversal stacks (24-bit entries) sized by the tree, after the staged scene */
     lds_bytes += (k.has(STAGES_NONE) ? (size_t)0 : (size_t)pt_filt_pair_slots(launch.scene.n_spheres) * 8u) +
                  (((size_t)max(launch.scene.bvh_depth, 1u) * PT_BLOCK * 3u + 15u) & ~(size_t)15u);
-  if (lds_bytes > 64 * 1024)
-  { /* the attribute belongs to the (kernel, current device) pair: set whenever it is needed -- a process-wide
-     * "already raised" note would skip devices 1..N-1 of the multi-device path (round-2 advisor finding) */
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess)
-      return e;
-  }
   if (launch.acc_keep && (k.has(CHUNKS) ? launch.acc_ws == nullptr || (launch.acc_windows != 0u) != k.has(WINDOWED) : launch.slice_ws == nullptr))
     return hipErrorInvalidValue; /* a pass of an accumulation adds to the sums its caller holds: they are neither cleared nor resolved here */
   if (launch.sample_chunks > 1 && !launch.acc_keep)
@@ -1677,21 +1677,19 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
     return hipErrorInvalidValue;
   /* the parked-walk kernels render a tile per wave, four work units per workgroup */
   const uint32_t n_units = (launch.slot_list ? launch.slot_count : launch.tile_count) * launch.sample_chunks;
-  hipLaunchKernelGGL(kernel, dim3(queued ? (n_units + PT_BLOCK / 64 - 1) / (PT_BLOCK / 64) : n_units), dim3(PT_BLOCK), lds_bytes,
-                     stream, launch);
-  if (launch.sample_chunks > 1 && !launch.acc_keep)
-    hipLaunchKernelGGL(pt_resolve_tiles, dim3(launch.tile_count), dim3(PT_BLOCK), 0, stream, launch, static_cast<const uint32_t *>(nullptr));
-  const hipError_t e = hipGetLastError();
+  hipError_t e = launch_staged(kernel, queued ? (n_units + PT_BLOCK / 64 - 1) / (PT_BLOCK / 64) : n_units, lds_bytes, stream, launch);
+  if (e == hipSuccess && launch.sample_chunks > 1 && !launch.acc_keep)
+    e = launch_staged(pt_resolve_tiles, launch.tile_count, 0, stream, launch, static_cast<const uint32_t *>(nullptr));
   if (e == hipSuccess)
-    pt_launch_counts[which].fetch_add(1ull);
+    pt_kernels.launched(which);
   return e;
 }
 
-bool pt_kernel_takes_chunks(int which) { return which >= 0 && which < K_COUNT && pt_kernels[which].has(CHUNKS); }
+bool pt_kernel_takes_chunks(int which) { return pt_kernels.valid(which) && pt_kernels[which].has(CHUNKS); }
 
 hipError_t pt_launch_resolve(const PtLaunch &launch, const uint32_t *tile_samples, hipStream_t stream, int which)
 {
-  if (which < 0 || which >= K_COUNT || launch.tile_count == 0u || launch.samples < 1)
+  if (!pt_kernels.valid(which) || launch.tile_count == 0u || launch.samples < 1)
     return hipErrorInvalidValue;
   if (pt_kernels[which].has(CHUNKS))
   {
@@ -1744,16 +1742,15 @@ hipError_t pt_launch_selftest_intersect(int kind, const double *rays, const doub
   return hipGetLastError();
 }
 
+/* workgroups of 256 threads for a grid-stride loop over `total` items: one pass, at most 8192 */
+static uint32_t untile_blocks(size_t total) { return (uint32_t)min((total + 255) / 256, (size_t)8192); }
+
 hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,
                             uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *image_rgb,
                             uint8_t *image_rgb8, hipStream_t stream)
 {
   const uint32_t tiles_x = ((uint32_t)width + PT_TILE - 1) / PT_TILE;
-  const size_t total = (size_t)tile_count * PT_TILE_PIXELS;
-  uint32_t blocks = (uint32_t)((total + 255) / 256);
-  if (blocks > 8192)
-    blocks = 8192;
-  hipLaunchKernelGGL(pt_untile, dim3(blocks), dim3(256), 0, stream, tiles_rgb, tiles_rgb8, width, height, tiles_x,
+  hipLaunchKernelGGL(pt_untile, dim3(untile_blocks((size_t)tile_count * PT_TILE_PIXELS)), dim3(256), 0, stream, tiles_rgb, tiles_rgb8, width, height, tiles_x,
                      tile_first, tile_stride, tile_count, image_rgb, image_rgb8);
   return hipGetLastError();
 }
@@ -1770,30 +1767,20 @@ int pt_aov_pick(const PtSceneView &scene)
   return tris ? (chk ? A_TRI_BIG_CHK : A_TRI_BIG) : (chk ? A_BIG_CHK : A_BIG);
 }
 
-const char *pt_aov_kernel_name_of(int which) { return which >= 0 && which < A_COUNT ? pt_aov_kernels[which].name : ""; }
+const char *pt_aov_kernel_name_of(int which) { return pt_aov_kernels.name_of(which); }
 int pt_aov_kernel_count(void) { return A_COUNT; }
-
-static std::atomic<unsigned long long> pt_aov_launch_counts[A_COUNT];
-unsigned long long pt_aov_kernel_launches(int which) { return which >= 0 && which < A_COUNT ? pt_aov_launch_counts[which].load() : 0ull; }
+unsigned long long pt_aov_kernel_launches(int which) { return pt_aov_kernels.launches(which); }
 
 hipError_t pt_launch_aov(const PtLaunch &launch, const PtAovOut &out, hipStream_t stream, int which)
 {
-  if (which < 0 || which >= A_COUNT || launch.tile_count == 0u)
+  if (!pt_aov_kernels.valid(which) || launch.tile_count == 0u)
     return hipErrorInvalidValue;
   /* the staged scene as the beauty kernels stage it (nothing for the in-memory forms) */
   const size_t lds_bytes = which == A_MEM || which == A_MEM_CHK ? 0 : pt_render_lds_bytes(launch.scene);
-  const PtAovKernelFn kernel = pt_aov_kernels[which].fn;
-  if (lds_bytes > 64 * 1024)
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess)
-      return e;
-  }
   const uint32_t waves = PT_BLOCK / 64u; /* a tile per wave */
-  hipLaunchKernelGGL(kernel, dim3((launch.tile_count + waves - 1u) / waves), dim3(PT_BLOCK), lds_bytes, stream, launch, out);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = launch_staged(pt_aov_kernels[which].fn, (launch.tile_count + waves - 1u) / waves, lds_bytes, stream, launch, out);
   if (e == hipSuccess)
-    pt_aov_launch_counts[which].fetch_add(1ull);
+    pt_aov_kernels.launched(which);
   return e;
 }
 
@@ -1808,29 +1795,19 @@ int pt_query_pick(const PtSceneView &scene)
   return tris ? Q_TRI_BIG : Q_BIG;
 }
 
-const char *pt_query_kernel_name_of(int which) { return which >= 0 && which < Q_COUNT ? pt_query_kernels[which].name : ""; }
+const char *pt_query_kernel_name_of(int which) { return pt_query_kernels.name_of(which); }
 int pt_query_kernel_count(void) { return Q_COUNT; }
-
-static std::atomic<unsigned long long> pt_query_launch_counts[Q_COUNT];
-unsigned long long pt_query_kernel_launches(int which) { return which >= 0 && which < Q_COUNT ? pt_query_launch_counts[which].load() : 0ull; }
+unsigned long long pt_query_kernel_launches(int which) { return pt_query_kernels.launches(which); }
 
 hipError_t pt_launch_query(const PtLaunch &launch, const PtQuery &query, hipStream_t stream, int which)
 {
-  if (which < 0 || which >= Q_COUNT || query.n == 0u || query.n > 0xFFFFFFFFull)
+  if (!pt_query_kernels.valid(which) || query.n == 0u || query.n > 0xFFFFFFFFull)
     return hipErrorInvalidValue;
   const size_t lds_bytes = which == Q_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the AOV launch */
-  const PtQueryKernelFn kernel = pt_query_kernels[which].fn;
-  if (lds_bytes > 64 * 1024)
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess)
-      return e;
-  }
   const uint32_t blocks = (uint32_t)((query.n + PT_BLOCK - 1u) / PT_BLOCK); /* at most 2^24 */
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(PT_BLOCK), lds_bytes, stream, launch, query);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = launch_staged(pt_query_kernels[which].fn, blocks, lds_bytes, stream, launch, query);
   if (e == hipSuccess)
-    pt_query_launch_counts[which].fetch_add(1ull);
+    pt_query_kernels.launched(which);
   return e;
 }
 
@@ -1838,11 +1815,7 @@ hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int wi
                                 uint32_t tile_stride, uint32_t tile_count, uint32_t *image, hipStream_t stream)
 {
   const uint32_t tiles_x = ((uint32_t)width + PT_TILE - 1) / PT_TILE;
-  const size_t total = (size_t)tile_count * PT_TILE_PIXELS * channels;
-  uint32_t blocks = (uint32_t)((total + 255) / 256);
-  if (blocks > 8192)
-    blocks = 8192;
-  hipLaunchKernelGGL(pt_untile_aov, dim3(blocks), dim3(256), 0, stream, tiles, width, height, tiles_x, tile_first, tile_stride,
+  hipLaunchKernelGGL(pt_untile_aov, dim3(untile_blocks((size_t)tile_count * PT_TILE_PIXELS * channels)), dim3(256), 0, stream, tiles, width, height, tiles_x, tile_first, tile_stride,
                      tile_count, channels, image);
   return hipGetLastError();
 }

@@ -35,6 +35,32 @@ struct SceneCtx
   BigPrune big;           /* pruning of the leading wall-sized spheres among themselves (sign-test kernels), or off */
 };
 
+/* ---- one intersect() call (raytracer.c:393-464) for the callers that track no TriLast ------------------- */
+
+/* what differs between those callers; the rest of scan_filtered's arguments are the SceneCtx's */
+struct ScanOpts
+{
+  unsigned long long *diag = nullptr; /* PT_DIAG counters */
+  bool big = true;       /* S.big: the walls pruned among themselves where the kernel staged them.  Right for a shadow ray too,
+                          * which asks "any hit?": pruning walls that cannot be the CLOSEST hit never removes the closest one,
+                          * so a hit stays a hit.  false: a caller's ray (BigPrune is the pooled body's) */
+  bool no_rules = false; /* per lane, RULE_SWITCH kernels: no conservative rule may drop anything for this ray */
+};
+
+/* scan_filtered over the staged scene: BVH and the filter table chosen as every site chooses them.  No TriLast, no_prune
+ * off, no pair list, no mesh bound: trace_step, whitted_step's primary ray and render_aov, which pass those, call
+ * scan_filtered themselves -- routed through here, with a TriLast pointer among the options, the listings of
+ * pt_aov_tiles_*_chk, pt_whitted_tiles_tri* and ten members of the family move (docs/HISTORY.md, section L). */
+template <bool TRIS, bool FILT_LDS, bool RULE_SWITCH = false>
+__device__ __forceinline__ void intersect_scene(const SceneCtx &S, const V3 &o, const V3 &d, double &min_t, int &best, double &bary_u,
+                                                double &bary_v, const ScanOpts &opt = {})
+{
+  scan_filtered<TRIS, TRIS && !FILT_LDS, FILT_LDS, true, false, false, false, RULE_SWITCH>(
+      S.geom, S.tri, FILT_LDS ? S.filt_lds : S.filt, S.near_R2, S.n_sph, S.n_sph + S.n_tri, o, d, min_t, best, bary_u, bary_v,
+      opt.diag, S.bvh_nodes, S.n_bvh_nodes, S.bvh_tri, S.filt_shift, nullptr, false, S.tri32, nullptr,
+      opt.big ? S.big : BigPrune{nullptr, 0u}, nullptr, opt.no_rules);
+}
+
 /* GEOM_LDS: sphere geometry and materials are staged in LDS (the pointers are LDS pointers at
  * compile time); otherwise the scene is beyond the staging budget (pt_geom_in_lds) and the
  * kernel reads them from memory.  Kernels pick the instantiation once, at entry. */

@@ -378,11 +378,7 @@ __device__ __forceinline__ bool whitted_step(const SceneCtx &S, Path &P, uint32_
       n_casts++;
       double shadow_t = S.t_start, su = 0, sv = 0;
       int blocker = -1;
-      scan_filtered<TRIS, TRIS && !FILT_LDS, FILT_LDS>(S.geom, S.tri, FILT_LDS ? S.filt_lds : S.filt, S.near_R2, S.n_sph,
-                                                       S.n_sph + S.n_tri, p, ldir, shadow_t, blocker, su, sv, diag_ptr,
-                                                       S.bvh_nodes, S.n_bvh_nodes, S.bvh_tri, S.filt_shift, nullptr, false,
-                                                       S.tri32, nullptr, S.big); /* (a shadow ray asks "any hit?": pruning walls that cannot be the
-                                                                                  * CLOSEST hit never removes the closest one, so a hit stays a hit) */
+      intersect_scene<TRIS, FILT_LDS>(S, p, ldir, shadow_t, blocker, su, sv, {.diag = diag_ptr}); /* ("any hit?": ScanOpts.big) */
       const double lit = blocker >= 0 ? 0.0 : 1.0;
 
       if (flags & PT_FLAG_CHECKER)
@@ -489,6 +485,16 @@ __device__ __forceinline__ uint32_t launch_slot_wave(const PtLaunch &L, uint32_t
   return LIST ? L.slot_list[__builtin_amdgcn_readfirstlane(j)] : j;
 }
 
+/* tile geometry: pixel `pit` (row-major in its 8 x 8 tile) of tile `tile` of a frame tiles_x tiles wide is image pixel (x, y);
+ * returns whether that is inside the image (the last column and row of tiles may hang over its edge).  Written out where the
+ * call would move a kernel's listing: finish_pixels and the resolves' copies of it (pt_resolve_tiles), pt_tile_error, pt_untile. */
+__device__ __forceinline__ bool tile_pixel(uint32_t tiles_x, uint32_t tile, uint32_t pit, int width, int height, uint32_t &x, uint32_t &y)
+{
+  x = (tile % tiles_x) * PT_TILE + (pit & 7u);
+  y = (tile / tiles_x) * PT_TILE + (pit >> 3);
+  return x < (uint32_t)width && y < (uint32_t)height;
+}
+
 __device__ __forceinline__ void finish_pixels(const PtLaunch &L, const unsigned long long *sums,
                                               const unsigned long long *nan_mask, uint32_t tile, float *out_f,
                                               uint8_t *out_b)
@@ -497,6 +503,7 @@ __device__ __forceinline__ void finish_pixels(const PtLaunch &L, const unsigned 
   if (threadIdx.x < PT_TILE_PIXELS * 3)
   {
     const uint32_t t = threadIdx.x / 3u, c = threadIdx.x - 3u * t;
+    /* tile_pixel, written out: the call moves the listings of the pooled members */
     const bool inside = (tile % L.tiles_x) * PT_TILE + (t & 7u) < (uint32_t)L.width &&
                         (tile / L.tiles_x) * PT_TILE + (t >> 3) < (uint32_t)L.height;
     const double inv_s = 1.0 / (double)L.samples;
@@ -508,13 +515,25 @@ __device__ __forceinline__ void finish_pixels(const PtLaunch &L, const unsigned 
   }
 }
 
+/* a finished tile (out_f / out_b in LDS, after a barrier) to slot `slot` of the compact output: 192 floats = 768 contiguous
+ * bytes, and the tonemapped bytes as 48 words.  The resolves' tail; store_tile keeps its own statement of it under with_pixels
+ * (calling this there moves pt_render_tiles_refr_pool* and pt_whitted_tiles). */
+__device__ __forceinline__ void store_tile_pixels(const PtLaunch &L, const float *out_f, const uint8_t *out_b, uint32_t slot)
+{
+  if (threadIdx.x < PT_TILE_PIXELS * 3)
+    L.tiles_rgb[(size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x] = out_f[threadIdx.x];
+  if (L.tiles_rgb8 && threadIdx.x < PT_TILE_PIXELS * 3 / 4)
+    reinterpret_cast<uint32_t *>(L.tiles_rgb8)[(size_t)slot * (PT_TILE_PIXELS * 3 / 4) + threadIdx.x] =
+        reinterpret_cast<const uint32_t *>(out_b)[threadIdx.x];
+}
+
 /* slot = index of the tile in the compact output; with_pixels = false when this workgroup
  * only contributed a sample chunk (pt_resolve_tiles writes the pixels then) */
 __device__ __forceinline__ void store_tile(const PtLaunch &L, const float *out_f, const uint8_t *out_b,
                                            const unsigned long long *wg_stats, uint32_t tile, uint32_t slot,
                                            uint32_t n_prims, bool with_pixels, bool count_samples)
 {
-  /* 192 floats = 768 contiguous bytes per tile */
+  /* store_tile_pixels under with_pixels, written out: the call moves pt_render_tiles_refr_pool* and pt_whitted_tiles */
   if (with_pixels && threadIdx.x < PT_TILE_PIXELS * 3)
     L.tiles_rgb[(size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x] = out_f[threadIdx.x];
   if (with_pixels && L.tiles_rgb8 && threadIdx.x < PT_TILE_PIXELS * 3 / 4)
