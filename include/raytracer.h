@@ -309,6 +309,18 @@ int intersect_rays(const Ray *rays, size_t n, const double *t_max, Object *objec
 int denoise_frame(uint8_t *framebuffer, float *linear_out, const float *linear_in, const RtAovImage *aov, int width, int height,
                   const RtHipDenoiseParams *params);
 
+/* Temporal reprojection of a frame onto the history of the frames before it (include/rt_hip.h, rt_hip_reproject: the contract in
+ * full): linear_in is the frame's linear mean (render_ex's linear_rgb), aov its render_aov buffers (normal, depth, hits and
+ * object_id), camera its camera; hist_linear and hist_len are the previous call's linear_out and len_out, hist_aov and hist_camera
+ * the previous frame's buffers and camera (all four NULL: the first frame).  Writes the accumulated linear image to linear_out
+ * (it may be linear_in) and the history length per pixel to len_out (both required), the tonemapped bytes to framebuffer and the
+ * motion in pixels (2 floats per pixel) to motion_out (either may be NULL).  params NULL: rt_hip_reproject_defaults.  The scene
+ * must not have changed between the two frames.  Runs on one device, the first of the device map.  Returns 0, or a negative
+ * RT_HIP_E* code with the reason on stderr. */
+int reproject_frame(uint8_t *framebuffer, float *linear_out, float *len_out, float *motion_out, const float *linear_in,
+                    const RtAovImage *aov, const Camera *camera, const float *hist_linear, const float *hist_len,
+                    const RtAovImage *hist_aov, const Camera *hist_camera, int width, int height, const RtHipReprojectParams *params);
+
 /* Kernel-only wall time of the last render()/render_ex(), seconds, and the
  * count of scene casts (rays that ran the intersection scan). */
 double rt_last_render_seconds(void);

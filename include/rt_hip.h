@@ -485,6 +485,63 @@ int rt_hip_denoise(const float *d_rgb, const RtHipAov *d_aov, int32_t width, int
 int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
                          int device, float *h_out_rgb, uint8_t *h_out_rgb8);
 
+/* ---- temporal reprojection: a frame's history carried across a camera move --------------------------------------------------
+ * The step between two frames of a static scene: where was each pixel's first-hit point in the previous frame, is it the same
+ * surface there, fetch the accumulated colour there, blend.  Inputs: row-major images of w x h pixels (2 <= w, h <= 2^20,
+ * w*h < 2^32; the lower bound is that of the division by w - 1) on one device -- the frame's colour c (3 floats per pixel) and its
+ * RtHipAov buffers after rt_hip_untile_aov (normal n, depth z, hits, object; albedo is ignored), the frame's camera; and the
+ * HISTORY: the previous call's out_rgb and out_len, the previous frame's RtHipAov buffers and camera (primed names below; H, V,
+ * llc, pos: a camera's horizontal, vertical, lower_left_corner, position).  d_hist_rgb, d_hist_len, d_hist_aov and hist_camera are
+ * NULL together: the first frame.  Cameras are host pointers.
+ * All arithmetic is fp64 +, -, *, /, sqrt, floor in the order written, unfused; values read from float buffers are widened exactly;
+ * every stored value is rounded to float32 (RNE).  dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z;
+ * cross(a,b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x).  Every comparison is false for NaN.  Per pixel p = (x, y):
+ *   1. If any channel of c = rgb(p) is not finite: out = c, len = 0, motion = (qNaN, qNaN) with qNaN = 0x7FC00000.  Done.
+ *   2. If there is no history (NULL), or hits(p) == 0, or !(z_p > 0 && z_p < +inf): out = c, len = 1, motion = qNaN.  Done.  (A
+ *      background pixel needs no history: every sample of it is BACKGROUND.)
+ *   3. The first-hit point, get_camera_ray (raytracer.c:375-384) operation for operation as the RT_HIP_RAYS_CAMERA_UV queries form it:
+ *      u = (x + 0.5) / (w - 1.0), v = (y + 0.5) / (h - 1.0), E = llc + (H*u + V*v), d = vec3_normalize(pos - E) (m = sqrt(dot),
+ *      then * (1.0 / m)), P = pos + d*z_p.
+ *   4. Its place in the previous frame: D = P - pos', R = pos' - llc', N = cross(V', D), det = dot(H', N), us = dot(R, N) / det,
+ *      M = cross(D, H'), vs = dot(R, M) / det, k = dot(R, cross(H', V')).  The point is in front iff (k > 0 && det > 0) ||
+ *      (k < 0 && det < 0).  fx = us*(w - 1.0) - 0.5, fy = vs*(h - 1.0) - 0.5.  ok = in front && fx > -1 && fx < w && fy > -1 &&
+ *      fy < h.  If !ok: out = c, len = 1, motion = qNaN.  Done.  Otherwise motion = (float(fx - x), float(fy - y)).
+ *   5. x0 = floor(fx), a = fx - x0, y0 = floor(fy), b = fy - y0, zexp = sqrt(dot(D, D)), W = A = S = 0.  Taps j = 0, 1 (outer),
+ *      i = 0, 1 (inner): q = (x0 + i, y0 + j) with weight wt = (i ? a : 1.0 - a) * (j ? b : 1.0 - b).  A tap is ACCEPTED iff q is
+ *      inside the image, all three channels of hist_rgb(q) are finite, len'_q >= 1 && len'_q < +inf, hits'_q > 0,
+ *      object'_q == object_p, dot(n_p, n'_q) >= normal_min and |z'_q - zexp| <= depth_tol * zexp.  An accepted tap: W += wt, then
+ *      A += wt * hist_rgb(q) per channel, then S += wt * len'_q.  A rejected tap is SKIPPED, not added as zero.
+ *   6. If !(W > 0): out = c, len = 1.  Otherwise hc = float(A / W) per channel, Nn = S / W + 1.0, if Nn > max_history: Nn =
+ *      max_history, al = 1.0 / Nn, out = float(hc + (c - hc) * al) per channel, len = float(Nn).
+ *   7. out8 = the render epilogue's tonemap of the widened out.
+ * The contract is total: any buffer contents and any camera bytes (a degenerate or NaN camera, depths that are 0, negative or inf,
+ * a zeroed history) have a defined result.  len = 0 marks a pixel the next frame must not use; a zero-filled history (buffers and
+ * camera) behaves like no history.  Out of scope: moving objects (the scene is static between the two frames), demodulated
+ * history, variance estimates.
+ *   - rt_hip_reproject_defaults: flags 0, max_history = 32, depth_tol = 0.05, normal_min = 0.5 (DESIGN, "`pt_reproject`": the sweep).
+ *   - rt_hip_reproject: asynchronous on `stream`, on the device that holds d_rgb.  d_out_rgb and d_out_len are required,
+ *     d_out_rgb8 and d_out_motion (2 floats per pixel) may be NULL; d_out_rgb == d_rgb is allowed (in place).  No output may overlap
+ *     a history buffer, another output, or a buffer of the frame in any other way (RT_HIP_EINVAL).  Arguments are checked before the device is looked for: RT_HIP_EINVAL, then RT_HIP_ENODEV.
+ *     A call takes no pool, workspace or status word.
+ *   - rt_hip_reproject_image: the same from host arrays, synchronous, with its own device buffers, on logical device `device` of
+ *     rt_hip_render_image's device map (the HIP device itself without a map). */
+typedef struct
+{
+  uint32_t flags;     /* must be 0 */
+  double max_history; /* >= 1, finite: cap of the history length N */
+  double depth_tol;   /* >= 0, finite: relative depth tolerance */
+  double normal_min;  /* finite: least n_p . n'_q of an accepted tap */
+} RtHipReprojectParams;
+void rt_hip_reproject_defaults(RtHipReprojectParams *params);
+int rt_hip_reproject(const float *d_rgb, const RtHipAov *d_aov, const RtHipCamera *camera, const float *d_hist_rgb,
+                     const float *d_hist_len, const RtHipAov *d_hist_aov, const RtHipCamera *hist_camera, int32_t width, int32_t height,
+                     const RtHipReprojectParams *params, float *d_out_rgb, uint8_t *d_out_rgb8, float *d_out_len, float *d_out_motion,
+                     void *stream);
+int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
+                           const float *h_hist_len, const RtHipAov *h_hist_aov, const RtHipCamera *hist_camera, int32_t width,
+                           int32_t height, const RtHipReprojectParams *params, int device, float *h_out_rgb, uint8_t *h_out_rgb8,
+                           float *h_out_len, float *h_out_motion);
+
 /* Scatter a compact tile buffer into row-major images (either output may be
  * NULL together with its input). */
 int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t width, int32_t height,

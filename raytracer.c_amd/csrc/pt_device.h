@@ -388,6 +388,23 @@ struct PtDenoise
   double sigma_z;
 };
 
+/* One temporal reprojection (rt_hip.h, rt_hip_reproject; pt_reproject in pt_kernel.hip): row-major w x h images of the frame
+ * (colour, normal, depth, hits, object) and of the history (the same and its length; all null together: the first frame), the two
+ * cameras, and the outputs -- out_rgb and out_len always, the bytes and the motion (2 floats per pixel) where wanted. */
+struct PtReproject
+{
+  const float *rgb, *normal, *depth;
+  const uint32_t *hits, *object;
+  const float *hist_rgb, *hist_len, *hist_normal, *hist_depth; /* hist_rgb null: no history */
+  const uint32_t *hist_hits, *hist_object;
+  float *out_rgb, *out_len;
+  uint8_t *out_rgb8; /* may be null */
+  float *out_motion; /* may be null */
+  int32_t width, height;
+  PtCamera cam, hist_cam;
+  double max_history, depth_tol, normal_min;
+};
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 /* host-side launchers, defined next to the kernels in pt_kernel.hip */
@@ -480,6 +497,8 @@ int pt_query_kernel_count(void);
 unsigned long long pt_query_kernel_launches(int which);
 /* the denoiser: the prepare pass and `iterations` filter passes (the last one remodulates and tonemaps) on `stream` */
 hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma_color, hipStream_t stream);
+/* temporal reprojection: one launch, a 16 x 16 block of pixels per workgroup, on `stream` */
+hipError_t pt_launch_reproject(const PtReproject &args, hipStream_t stream);
 hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,
                             uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *image_rgb,
                             uint8_t *image_rgb8, hipStream_t stream);

@@ -1300,6 +1300,131 @@ extern "C" __global__ __launch_bounds__(256) void pt_denoise_filter_final(const 
   denoise_filter<true>(D, src, step, S2);
 }
 
+/* ---- temporal reprojection (rt_hip_reproject): a frame's history carried across a camera move ------------------------------
+ * rt_hip.h states the arithmetic; this is it, operation for operation, in fp64 (-ffp-contract=off; the library's IEEE division and
+ * correctly rounded sqrt).  A lane is a pixel, a workgroup a 16 x 16 block as pt_denoise_filter's, no LDS.  The pixel's first-hit
+ * point is rebuilt from its depth along the centre ray (get_camera_ray as query_rays forms it, vec3_normalize in its library
+ * form: any camera bytes are allowed here), projected into the history's camera by Cramer's rule, and the history is fetched
+ * with the four bilinear taps that show the same surface.  The taps are unrolled and the same for every lane that reaches them:
+ * an out-of-image tap loads the lane's own pixel under a false predicate and every skip is a predicate on the sums, not an
+ * added zero.  The bytes are written under a wave-uniform branch (out_rgb8 null: no tonemap). */
+__device__ __forceinline__ void reproject_store(const PtReproject &R, size_t p, float ox, float oy, float oz, float len, float mx, float my)
+{
+  R.out_rgb[3 * p + 0] = ox;
+  R.out_rgb[3 * p + 1] = oy;
+  R.out_rgb[3 * p + 2] = oz;
+  R.out_len[p] = len;
+  if (R.out_motion)
+  {
+    R.out_motion[2 * p + 0] = mx;
+    R.out_motion[2 * p + 1] = my;
+  }
+  if (R.out_rgb8)
+  {
+    R.out_rgb8[3 * p + 0] = tonemap((double)ox);
+    R.out_rgb8[3 * p + 1] = tonemap((double)oy);
+    R.out_rgb8[3 * p + 2] = tonemap((double)oz);
+  }
+}
+
+extern "C" __global__ __launch_bounds__(256) void pt_reproject(const PtReproject R)
+{
+  const uint32_t bx = ((uint32_t)R.width + 15u) / 16u;
+  const int32_t x = (int32_t)((blockIdx.x % bx) * 16u + (threadIdx.x & 15u));
+  const int32_t y = (int32_t)((blockIdx.x / bx) * 16u + (threadIdx.x >> 4));
+  if (x >= R.width || y >= R.height)
+    return; /* no barrier follows */
+  const size_t p = (size_t)y * (size_t)R.width + (size_t)x;
+  const float cx = R.rgb[3 * p + 0], cy = R.rgb[3 * p + 1], cz = R.rgb[3 * p + 2];
+  const float qnan = __uint_as_float(0x7FC00000u);
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);
+  /* 1. a colour that is not finite passes through and starts no history */
+  if (!(isfinite(cx) && isfinite(cy) && isfinite(cz)))
+  {
+    reproject_store(R, p, cx, cy, cz, 0.f, qnan, qnan);
+    return;
+  }
+  /* 2. nothing to look up: the first frame, a background pixel, a depth that is no distance */
+  const double zp = (double)R.depth[p];
+  if (!R.hist_rgb || R.hits[p] == 0u || !(zp > 0 && zp < inf))
+  {
+    reproject_store(R, p, cx, cy, cz, 1.f, qnan, qnan);
+    return;
+  }
+  /* 3. the first-hit point: get_camera_ray (raytracer.c:375-384) through the pixel's centre, then point_at */
+  const double w1 = (double)R.width - 1.0, h1 = (double)R.height - 1.0;
+  const double u = ((double)x + 0.5) / w1, v = ((double)y + 0.5) / h1;
+  const V3 pos = ld3(R.cam.pos);
+  const V3 E = v_add(ld3(R.cam.llc), v_add(v_scale(ld3(R.cam.horizontal), u), v_scale(ld3(R.cam.vertical), v)));
+  const V3 d = v_normalize(v_sub(pos, E));
+  const V3 P = v_add(pos, v_scale(d, zp));
+  /* 4. where the history's camera saw it: H' us + V' vs + D / s = R', solved for (us, vs, 1 / s) by Cramer's rule */
+  const V3 Hh = ld3(R.hist_cam.horizontal), Vh = ld3(R.hist_cam.vertical), posh = ld3(R.hist_cam.pos);
+  const V3 D = v_sub(P, posh);
+  const V3 Rr = v_sub(posh, ld3(R.hist_cam.llc));
+  const V3 N = v_cross(Vh, D);
+  const double det = v_dot(Hh, N);
+  const double us = v_dot(Rr, N) / det;
+  const V3 M = v_cross(D, Hh);
+  const double vs = v_dot(Rr, M) / det;
+  const double k = v_dot(Rr, v_cross(Hh, Vh));
+  const bool front = (k > 0 && det > 0) || (k < 0 && det < 0);
+  const double fx = us * w1 - 0.5, fy = vs * h1 - 0.5;
+  const bool ok = front && fx > -1.0 && fx < (double)R.width && fy > -1.0 && fy < (double)R.height;
+  if (!ok)
+  {
+    reproject_store(R, p, cx, cy, cz, 1.f, qnan, qnan);
+    return;
+  }
+  const float mx = (float)(fx - (double)x), my = (float)(fy - (double)y);
+  /* 5. the four taps (ok: floor(fx) is in [-1, w - 1], floor(fy) in [-1, h - 1] -- the conversions are in range) */
+  const double x0d = floor(fx), y0d = floor(fy);
+  const double a = fx - x0d, b = fy - y0d;
+  const int32_t x0 = (int32_t)x0d, y0 = (int32_t)y0d;
+  const double zexp = sqrt(v_dot(D, D));
+  const double ztol = R.depth_tol * zexp;
+  const double npx = R.normal[3 * p + 0], npy = R.normal[3 * p + 1], npz = R.normal[3 * p + 2];
+  const uint32_t op = R.object[p];
+  double W = 0, Ax = 0, Ay = 0, Az = 0, S = 0;
+#pragma unroll
+  for (int j = 0; j < 2; j++)
+  {
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+    {
+      const int32_t qx = x0 + i, qy = y0 + j;
+      const bool inside = qx >= 0 && qx < R.width && qy >= 0 && qy < R.height;
+      const size_t q = inside ? (size_t)qy * (size_t)R.width + (size_t)qx : p;
+      const double wt = (i ? a : 1.0 - a) * (j ? b : 1.0 - b);
+      const float hx = R.hist_rgb[3 * q + 0], hy = R.hist_rgb[3 * q + 1], hz = R.hist_rgb[3 * q + 2];
+      const double lq = (double)R.hist_len[q], zq = (double)R.hist_depth[q];
+      const double g = (npx * (double)R.hist_normal[3 * q + 0] + npy * (double)R.hist_normal[3 * q + 1]) + npz * (double)R.hist_normal[3 * q + 2];
+      const bool take = inside && isfinite(hx) && isfinite(hy) && isfinite(hz) && lq >= 1.0 && lq < inf && R.hist_hits[q] > 0u &&
+                        R.hist_object[q] == op && g >= R.normal_min && __builtin_fabs(zq - zexp) <= ztol;
+      W = take ? W + wt : W;
+      Ax = take ? Ax + wt * (double)hx : Ax;
+      Ay = take ? Ay + wt * (double)hy : Ay;
+      Az = take ? Az + wt * (double)hz : Az;
+      S = take ? S + wt * lq : S;
+    }
+  }
+  /* 6. the blend: a running mean of up to max_history frames */
+  if (!(W > 0))
+  {
+    reproject_store(R, p, cx, cy, cz, 1.f, mx, my);
+    return;
+  }
+  const float hcx = (float)(Ax / W), hcy = (float)(Ay / W), hcz = (float)(Az / W);
+  double Nn = S / W + 1.0;
+  if (Nn > R.max_history)
+    Nn = R.max_history;
+  const double al = 1.0 / Nn;
+  const float ox = (float)((double)hcx + ((double)cx - (double)hcx) * al);
+  const float oy = (float)((double)hcy + ((double)cy - (double)hcy) * al);
+  const float oz = (float)((double)hcz + ((double)cz - (double)hcz) * al);
+  reproject_store(R, p, ox, oy, oz, (float)Nn, mx, my);
+}
+
 /* ---- launch wrappers (host side), declared in pt_device.h ---------------------- */
 
 size_t pt_render_lds_bytes(const PtSceneView &sc)
@@ -1844,4 +1969,12 @@ hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma
     e = hipGetLastError();
   }
   return e;
+}
+
+/* ---- the reprojection's launch (rt_hip_reproject) --------------------------------------------------------------------------- */
+hipError_t pt_launch_reproject(const PtReproject &args, hipStream_t stream)
+{
+  const uint32_t blocks_2d = (((uint32_t)args.width + 15u) / 16u) * (((uint32_t)args.height + 15u) / 16u);
+  hipLaunchKernelGGL(pt_reproject, dim3(blocks_2d), dim3(256), 0, stream, args);
+  return hipGetLastError();
 }

@@ -2233,6 +2233,186 @@ int denoise_image_impl(const float *h_rgb, const RtHipAov *h_aov, int32_t width,
   return RT_HIP_OK;
 }
 
+/* ---- temporal reprojection (rt_hip.h, rt_hip_reproject*) ---------------------------------------------------------------------
+ * One launch of pt_reproject (pt_kernel.hip), no workspace.  The arguments that need no device are checked first. */
+bool reproject_size_ok(int32_t width, int32_t height)
+{
+  return width >= 2 && height >= 2 && width <= (1 << 20) && height <= (1 << 20) && (uint64_t)width * (uint64_t)height <= 0xFFFFFFFFull;
+}
+
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+int check_reproject(const float *rgb, const RtHipAov *aov, const RtHipCamera *camera, const float *hist_rgb, const float *hist_len,
+                    const RtHipAov *hist_aov, const RtHipCamera *hist_camera, int32_t width, int32_t height,
+                    const RtHipReprojectParams *p, const float *out_rgb, const uint8_t *out_rgb8, const float *out_len,
+                    const float *out_motion)
+{
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is NULL");
+  if (!reproject_size_ok(width, height))
+    return fail(RT_HIP_EINVAL, "width and height must be in [2, 2^20] with fewer than 2^32 pixels");
+  if (p->flags != 0u)
+    return fail(RT_HIP_EINVAL, "unknown reproject flags 0x%x", p->flags);
+  if (!(std::isfinite(p->max_history) && p->max_history >= 1.0))
+    return fail(RT_HIP_EINVAL, "max_history must be finite and >= 1");
+  if (!(std::isfinite(p->depth_tol) && p->depth_tol >= 0.0))
+    return fail(RT_HIP_EINVAL, "depth_tol must be finite and >= 0");
+  if (!std::isfinite(p->normal_min))
+    return fail(RT_HIP_EINVAL, "normal_min must be finite");
+  if (!rgb || !camera)
+    return fail(RT_HIP_EINVAL, "the colour image and the camera are required");
+  if (!aov || !aov->normal || !aov->depth || !aov->hits || !aov->object)
+    return fail(RT_HIP_EINVAL, "the normal, depth, hits and object buffers are required");
+  const bool any_hist = hist_rgb || hist_len || hist_aov || hist_camera;
+  if (any_hist && !(hist_rgb && hist_len && hist_aov && hist_camera))
+    return fail(RT_HIP_EINVAL, "the history's colour, length, buffers and camera are given together or not at all");
+  if (any_hist && (!hist_aov->normal || !hist_aov->depth || !hist_aov->hits || !hist_aov->object))
+    return fail(RT_HIP_EINVAL, "the history's normal, depth, hits and object buffers are required");
+  if (!out_rgb || !out_len)
+    return fail(RT_HIP_EINVAL, "out_rgb and out_len are required");
+  /* a lane writes its pixel's outputs while other lanes still read: no output may overlap what the call reads (the history, the
+   * frame's buffers) or another output; only out_rgb == rgb, where a lane reads its own pixel before it writes it, is in place */
+  const size_t n = (size_t)width * (size_t)height;
+  const std::pair<const void *, size_t> outs[4] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_len, 4u * n}, {out_motion, 8u * n}};
+  const std::pair<const void *, size_t> frame[5] = {{rgb, 12u * n}, {aov->normal, 12u * n}, {aov->depth, 4u * n}, {aov->hits, 4u * n},
+                                                    {aov->object, 4u * n}};
+  for (int o = 0; o < 4; o++)
+  {
+    for (int f = 0; f < 5; f++)
+      if (!(o == 0 && f == 0 && out_rgb == rgb) && ranges_overlap(outs[o].first, outs[o].second, frame[f].first, frame[f].second))
+        return fail(RT_HIP_EINVAL, "an output overlaps a buffer of the frame (only out_rgb == rgb is allowed)");
+    for (int q = o + 1; q < 4; q++)
+      if (ranges_overlap(outs[o].first, outs[o].second, outs[q].first, outs[q].second))
+        return fail(RT_HIP_EINVAL, "two outputs overlap");
+  }
+  if (any_hist)
+  {
+    const std::pair<const void *, size_t> hist[6] = {{hist_rgb, 12u * n},        {hist_len, 4u * n},         {hist_aov->normal, 12u * n},
+                                                     {hist_aov->depth, 4u * n}, {hist_aov->hits, 4u * n}, {hist_aov->object, 4u * n}};
+    for (const auto &o : outs)
+      for (const auto &h : hist)
+        if (ranges_overlap(o.first, o.second, h.first, h.second))
+          return fail(RT_HIP_EINVAL, "an output aliases a history buffer");
+  }
+  return RT_HIP_OK;
+}
+
+void camera_of(const RtHipCamera *c, PtCamera &out)
+{
+  for (int k = 0; k < 3; k++)
+  {
+    out.pos[k] = c->position[k];
+    out.horizontal[k] = c->horizontal[k];
+    out.vertical[k] = c->vertical[k];
+    out.llc[k] = c->lower_left_corner[k];
+  }
+}
+
+/* the launch of a checked call, on the current device */
+int reproject_launch(const float *rgb, const RtHipAov *aov, const RtHipCamera *camera, const float *hist_rgb, const float *hist_len,
+                     const RtHipAov *hist_aov, const RtHipCamera *hist_camera, int32_t width, int32_t height,
+                     const RtHipReprojectParams *p, float *out_rgb, uint8_t *out_rgb8, float *out_len, float *out_motion,
+                     hipStream_t stream)
+{
+  PtReproject R = {};
+  R.rgb = rgb;
+  R.normal = aov->normal;
+  R.depth = aov->depth;
+  R.hits = aov->hits;
+  R.object = aov->object;
+  camera_of(camera, R.cam);
+  if (hist_rgb)
+  {
+    R.hist_rgb = hist_rgb;
+    R.hist_len = hist_len;
+    R.hist_normal = hist_aov->normal;
+    R.hist_depth = hist_aov->depth;
+    R.hist_hits = hist_aov->hits;
+    R.hist_object = hist_aov->object;
+    camera_of(hist_camera, R.hist_cam);
+  }
+  R.out_rgb = out_rgb;
+  R.out_rgb8 = out_rgb8;
+  R.out_len = out_len;
+  R.out_motion = out_motion;
+  R.width = width;
+  R.height = height;
+  R.max_history = p->max_history;
+  R.depth_tol = p->depth_tol;
+  R.normal_min = p->normal_min;
+  const hipError_t e = pt_launch_reproject(R, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "pt_reproject launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int reproject_image_impl(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
+                         const float *h_hist_len, const RtHipAov *h_hist_aov, const RtHipCamera *hist_camera, int32_t width,
+                         int32_t height, const RtHipReprojectParams *params, int device, float *h_out_rgb, uint8_t *h_out_rgb8,
+                         float *h_out_len, float *h_out_motion)
+{
+  int rc = check_reproject(h_rgb, h_aov, camera, h_hist_rgb, h_hist_len, h_hist_aov, hist_camera, width, height, params, h_out_rgb,
+                           h_out_rgb8, h_out_len, h_out_motion);
+  if (rc)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", phys, hipGetErrorString(scope.status));
+  const size_t n = (size_t)width * (size_t)height;
+  const bool hist = h_hist_rgb != nullptr;
+  /* one allocation: per image colour (in and out: in place), normal, depth, hits, object; then length, motion, bytes */
+  const size_t b3 = align256(12u * n), b2 = align256(8u * n), b1 = align256(4u * n);
+  const size_t image = 2u * b3 + 3u * b1;
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc((hist ? 2u : 1u) * image + (hist ? 2u : 1u) * b1 + b2 + align256(3u * n)));
+  size_t at = 0;
+  auto part = [&](size_t bytes) { /* the next `bytes` of the allocation */
+    at += bytes;
+    return at - bytes;
+  };
+  float *d_rgb[2] = {nullptr, nullptr}, *d_len[2] = {nullptr, nullptr};
+  RtHipAov d_aov[2] = {};
+  const float *src_rgb[2] = {h_rgb, h_hist_rgb};
+  const RtHipAov *src_aov[2] = {h_aov, h_hist_aov};
+  for (int f = 0; f < (hist ? 2 : 1); f++)
+  {
+    d_rgb[f] = buf.at<float>(part(b3));
+    d_aov[f].normal = buf.at<float>(part(b3));
+    d_aov[f].depth = buf.at<float>(part(b1));
+    d_aov[f].hits = buf.at<uint32_t>(part(b1));
+    d_aov[f].object = buf.at<uint32_t>(part(b1));
+    d_len[f] = buf.at<float>(part(b1));
+    HIP_TRY(hipMemcpy(d_rgb[f], src_rgb[f], 12u * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov[f].normal, src_aov[f]->normal, 12u * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov[f].depth, src_aov[f]->depth, 4u * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov[f].hits, src_aov[f]->hits, 4u * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov[f].object, src_aov[f]->object, 4u * n, hipMemcpyHostToDevice));
+  }
+  if (hist)
+    HIP_TRY(hipMemcpy(d_len[1], h_hist_len, 4u * n, hipMemcpyHostToDevice));
+  float *d_motion = buf.at<float>(part(b2));
+  uint8_t *d_rgb8 = buf.at<uint8_t>(part(align256(3u * n)));
+  rc = reproject_launch(d_rgb[0], &d_aov[0], camera, d_rgb[1], d_len[1], hist ? &d_aov[1] : nullptr, hist_camera, width, height, params,
+                        d_rgb[0], h_out_rgb8 ? d_rgb8 : nullptr, d_len[0], h_out_motion ? d_motion : nullptr, nullptr);
+  if (rc)
+    return rc;
+  HIP_TRY(hipMemcpy(h_out_rgb, d_rgb[0], 12u * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h_out_len, d_len[0], 4u * n, hipMemcpyDeviceToHost));
+  if (h_out_rgb8)
+    HIP_TRY(hipMemcpy(h_out_rgb8, d_rgb8, 3u * n, hipMemcpyDeviceToHost));
+  if (h_out_motion)
+    HIP_TRY(hipMemcpy(h_out_motion, d_motion, 8u * n, hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
 /* ---- ray queries (rt_hip.h, rt_hip_query_*) ---------------------------------------------------------------------------------
  * A query's launch takes the scene- and near_R-dependent fields of launch_prepare with origin_radius in the camera distance's
  * place, and acquire_tables' filter, hierarchy and fp32 triangle table for that near_R -- what intersect() reads -- and nothing
@@ -3370,6 +3550,53 @@ int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t widt
 {
   return guarded("rt_hip_denoise_image",
                  [&] { return denoise_image_impl(h_rgb, h_aov, width, height, params, device, h_out_rgb, h_out_rgb8); });
+}
+
+/* the sweep of tools/reproject_bench.py (DESIGN, "`pt_reproject`") */
+void rt_hip_reproject_defaults(RtHipReprojectParams *params)
+{
+  if (!params)
+    return;
+  *params = RtHipReprojectParams{};
+  params->max_history = 32.0;
+  params->depth_tol = 0.05;
+  params->normal_min = 0.5;
+}
+
+int rt_hip_reproject(const float *d_rgb, const RtHipAov *d_aov, const RtHipCamera *camera, const float *d_hist_rgb,
+                     const float *d_hist_len, const RtHipAov *d_hist_aov, const RtHipCamera *hist_camera, int32_t width, int32_t height,
+                     const RtHipReprojectParams *params, float *d_out_rgb, uint8_t *d_out_rgb8, float *d_out_len, float *d_out_motion,
+                     void *stream)
+{
+  int rc = check_reproject(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, d_out_rgb,
+                           d_out_rgb8, d_out_len, d_out_motion);
+  if (rc)
+    return rc;
+  if (usable_devices() < 1)
+    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
+  /* the device that holds the colour: a host pointer here would fault the kernel, so it is refused */
+  hipPointerAttribute_t attr = {};
+  if (hipPointerGetAttributes(&attr, d_rgb) != hipSuccess || attr.type != hipMemoryTypeDevice)
+  {
+    (void)hipGetLastError();
+    return fail(RT_HIP_EINVAL, "d_rgb is not device memory");
+  }
+  DeviceScope scope(attr.device);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  return reproject_launch(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, d_out_rgb,
+                          d_out_rgb8, d_out_len, d_out_motion, static_cast<hipStream_t>(stream));
+}
+
+int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
+                           const float *h_hist_len, const RtHipAov *h_hist_aov, const RtHipCamera *hist_camera, int32_t width,
+                           int32_t height, const RtHipReprojectParams *params, int device, float *h_out_rgb, uint8_t *h_out_rgb8,
+                           float *h_out_len, float *h_out_motion)
+{
+  return guarded("rt_hip_reproject_image", [&] {
+    return reproject_image_impl(h_rgb, h_aov, camera, h_hist_rgb, h_hist_len, h_hist_aov, hist_camera, width, height, params, device,
+                                h_out_rgb, h_out_rgb8, h_out_len, h_out_motion);
+  });
 }
 
 } // extern "C"

@@ -437,6 +437,32 @@ int denoise_frame(uint8_t *framebuffer, float *linear_out, const float *linear_i
   return rc;
 }
 
+int reproject_frame(uint8_t *framebuffer, float *linear_out, float *len_out, float *motion_out, const float *linear_in,
+                    const RtAovImage *aov, const Camera *camera, const float *hist_linear, const float *hist_len,
+                    const RtAovImage *hist_aov, const Camera *hist_camera, int width, int height, const RtHipReprojectParams *params)
+{
+  RtHipReprojectParams defaults;
+  rt_hip_reproject_defaults(&defaults);
+  if (!aov)
+  {
+    fprintf(stderr, "reproject_frame: the feature buffers are required\n");
+    return RT_HIP_EINVAL;
+  }
+  const RtHipAov h = {aov->albedo, aov->normal, aov->depth, aov->object_id, aov->hits};
+  RtHipAov hh = {NULL, NULL, NULL, NULL, NULL};
+  if (hist_aov)
+  {
+    const RtHipAov given = {hist_aov->albedo, hist_aov->normal, hist_aov->depth, hist_aov->object_id, hist_aov->hits};
+    hh = given;
+  }
+  const int rc = rt_hip_reproject_image(linear_in, &h, (const RtHipCamera *)camera, hist_linear, hist_len, hist_aov ? &hh : NULL,
+                                        (const RtHipCamera *)hist_camera, width, height, params ? params : &defaults, 0, linear_out,
+                                        framebuffer, len_out, motion_out);
+  if (rc)
+    fprintf(stderr, "reproject_frame: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+  return rc;
+}
+
 int intersect_rays(const Ray *rays, size_t n, const double *t_max, Object *objects, size_t n_objects, MeshObject *meshes,
                    size_t n_meshes, Hit *hits, uint8_t *status)
 {

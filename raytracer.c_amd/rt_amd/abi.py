@@ -91,6 +91,10 @@ class RtHipDenoiseParams(C.Structure):  # rt_hip.h: the denoiser's parameters (r
                 ("sigma_color", C.c_double), ("sigma_depth", C.c_double)]
 
 
+class RtHipReprojectParams(C.Structure):  # rt_hip.h: temporal reprojection (rt_hip_reproject_defaults), 32 B
+    _fields_ = [("flags", C.c_uint32), ("max_history", C.c_double), ("depth_tol", C.c_double), ("normal_min", C.c_double)]
+
+
 class RtHipAdaptParams(C.Structure):  # rt_hip.h: adaptive sampling (rt_hip_adapt_defaults)
     _fields_ = [("min_samples", C.c_int32), ("dilate", C.c_uint32), ("threshold", C.c_double)]
 
@@ -212,6 +216,13 @@ SHIM_SYMBOLS = {
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_denoise_image": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_int,
                                        C.c_void_p, C.c_void_p]),
+    "rt_hip_reproject_defaults": (None, [C.POINTER(RtHipReprojectParams)]),
+    "rt_hip_reproject": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(RtHipAov),
+                                   C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(RtHipReprojectParams), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_reproject_image": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(RtHipAov),
+                                         C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(RtHipReprojectParams), C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_render_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t,
                                       C.POINTER(Camera), C.POINTER(RtHipParams), C.c_int, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
@@ -250,6 +261,9 @@ HOST_SYMBOLS = {
                              C.POINTER(Camera), C.POINTER(Options)]),
     "denoise_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.c_int, C.c_int,
                                 C.POINTER(RtHipDenoiseParams)]),
+    "reproject_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.POINTER(Camera),
+                                  C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.POINTER(Camera), C.c_int, C.c_int,
+                                  C.POINTER(RtHipReprojectParams)]),
     "intersect_rays": (C.c_int, [C.POINTER(Ray), C.c_size_t, C.c_void_p, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
                                  C.POINTER(Hit), C.c_void_p]),
     "rt_last_render_cancelled": (C.c_int, []),
@@ -316,6 +330,16 @@ def denoise_params(iterations=None, sigma_color=None, sigma_depth=None, normal_p
     for bit, v in ((DENOISE_DEMODULATE, demodulate), (DENOISE_OBJECT_EDGES, object_edges)):
         if v is not None:
             p.flags = (p.flags | bit) if v else (p.flags & ~bit)
+    return p
+
+
+def reproject_params(max_history=None, depth_tol=None, normal_min=None):
+    """rt_hip_reproject_defaults() with the given fields replaced (None: the default)"""
+    p = RtHipReprojectParams()
+    load_shim().rt_hip_reproject_defaults(C.byref(p))
+    for f, v in (("max_history", max_history), ("depth_tol", depth_tol), ("normal_min", normal_min)):
+        if v is not None:
+            setattr(p, f, v)
     return p
 
 

@@ -254,6 +254,11 @@ class GpuScene:
         torch.cuda.synchronize(image.device)
         return image.cpu().numpy(), rgb.cpu().numpy(), rgb8.cpu().numpy()
 
+    def temporal(self, **params):
+        """A Temporal: frames of this scene under a moving camera, each accumulated onto the reprojected history of the ones
+        before (rt_hip_reproject; params: abi.reproject_params' keywords)"""
+        return Temporal(self, **params)
+
     def render_adaptive(self, seed, samples, max_depth=None, integrator="path", **params):
         """An adaptive frame of at most `samples` per pixel on this GPU (Accumulation.run_adaptive; params: abi.adapt_params'
         keywords) -> (image f32 [H,W,3], image8 u8 [H,W,3], tile sample counts uint32 [tiles_y, tiles_x], stats dict, device
@@ -450,6 +455,162 @@ def denoise(rgb, aov, width, height, out=None, **params):
     _check(shim.rt_hip_denoise(C.c_void_p(rgb.data_ptr()), C.byref(a), width, height, C.byref(p), C.c_void_p(ws.data_ptr()),
                                C.c_void_p(out.data_ptr()), C.c_void_p(out8.data_ptr()), C.c_void_p(stream)), "rt_hip_denoise")
     return out, out8
+
+
+REPROJECT_AOV = ("normal", "depth", "object", "hits")   # what rt_hip_reproject reads of a frame and of the history
+
+
+def _reproject_aov(aov, n, dev, what):
+    a = abi.RtHipAov()
+    for f in REPROJECT_AOV:
+        t = aov[f]
+        if t.device != dev or not t.is_contiguous() or t.element_size() != 4 or t.numel() != n * abi.AOV_CHANNELS[f]:
+            raise ValueError(f"reproject(): {what} {f} must be a contiguous 32-bit tensor of width * height * {abi.AOV_CHANNELS[f]} "
+                             "values on the colour's device")
+        setattr(a, f, t.data_ptr())
+    return a
+
+
+def reproject(rgb, aov, camera, hist=None, out=None, **params):
+    """rt_hip_reproject on torch device tensors, asynchronous on torch's current stream: rgb f32 [H,W,3] (row-major, contiguous),
+    aov a dict of row-major buffers as GpuScene.untile_aov gives them (normal, depth, object, hits), camera the frame's abi.Camera.
+    hist: None (the first frame) or a dict with rgb and len (an earlier call's results), aov and camera (that frame's).  out: a
+    dict of tensors to write into (rgb f32 [H,W,3] -- it may be the input rgb --, len f32 [H,W], motion f32 [H,W,2], rgb8 u8
+    [H,W,3]; what is missing is allocated; motion or rgb8 given as None: not wanted, not computed), none of them a history buffer
+    or another buffer of the call.  params: abi.reproject_params' keywords.
+    -> dict(rgb, len, and motion and rgb8 unless not wanted)"""
+    dev = rgb.device
+    shim = abi.load_shim()
+    p = abi.reproject_params(**params)
+    if rgb.dim() != 3 or rgb.shape[2] != 3 or rgb.dtype != torch.float32 or not rgb.is_contiguous():
+        raise ValueError("reproject(): rgb must be a contiguous float32 [H,W,3] tensor")
+    height, width = int(rgb.shape[0]), int(rgb.shape[1])
+    n = width * height
+    a = _reproject_aov(aov, n, dev, "the frame's")
+    h_rgb = h_len = h_aov = h_cam = None
+    if hist is not None:
+        for f in ("rgb", "len"):
+            t = hist[f]
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n * (3 if f == "rgb" else 1):
+                raise ValueError(f"reproject(): the history's {f} must be a contiguous float32 tensor of the frame's size on its device")
+        h_rgb, h_len = C.c_void_p(hist["rgb"].data_ptr()), C.c_void_p(hist["len"].data_ptr())
+        h_aov, h_cam = C.byref(_reproject_aov(hist["aov"], n, dev, "the history's")), C.byref(hist["camera"])
+    out = dict(out) if out else {}
+    shapes = dict(rgb=((height, width, 3), torch.float32), len=((height, width), torch.float32),
+                  motion=((height, width, 2), torch.float32), rgb8=((height, width, 3), torch.uint8))
+    for f, (shape, dtype) in shapes.items():
+        if f in ("motion", "rgb8") and f in out and out[f] is None:
+            del out[f]
+            continue
+        if f not in out:
+            out[f] = torch.empty(shape, dtype=dtype, device=dev)
+        t = out[f]
+        if t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != shape[0] * shape[1] * (shape[2] if len(shape) > 2 else 1):
+            raise ValueError(f"reproject(): out[{f!r}] must be a contiguous {dtype} tensor of shape {shape} on the colour's device")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_reproject(C.c_void_p(rgb.data_ptr()), C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, width, height,
+                                 C.byref(p), C.c_void_p(out["rgb"].data_ptr()),
+                                 C.c_void_p(out["rgb8"].data_ptr()) if "rgb8" in out else None, C.c_void_p(out["len"].data_ptr()),
+                                 C.c_void_p(out["motion"].data_ptr()) if "motion" in out else None, C.c_void_p(stream)),
+           "rt_hip_reproject")
+    return out
+
+
+class Temporal:
+    """Frames of one scene under a moving camera (GpuScene.temporal): every frame is rendered, its first-hit buffers of the same
+    samples are rendered, and it is accumulated onto the history of the frames before it where the reprojection finds the same
+    surface (rt_hip.h, rt_hip_reproject).  The history -- accumulated colour, length, the first-hit buffers and the camera -- is
+    double-buffered and allocated once; frame() runs on torch's current stream.  The scene must stay open and unchanged."""
+
+    def __init__(self, gs, **params):
+        self.gs = gs
+        self.params = params
+        abi.reproject_params(**params)   # a bad keyword fails here
+        w, h = gs.scene.width, gs.scene.height
+        dev = torch.device("cuda", gs.device)
+        self._total = n_tiles(w, h)
+
+        def slot():
+            aov = dict(normal=torch.zeros((h, w, 3), dtype=torch.float32, device=dev), depth=torch.zeros((h, w), dtype=torch.float32, device=dev),
+                       object=torch.zeros((h, w), dtype=torch.int32, device=dev), hits=torch.zeros((h, w), dtype=torch.int32, device=dev),
+                       albedo=torch.zeros((h, w, 3), dtype=torch.float32, device=dev))
+            return dict(rgb=torch.zeros((h, w, 3), dtype=torch.float32, device=dev), len=torch.zeros((h, w), dtype=torch.float32, device=dev),
+                        aov=aov, camera=abi.Camera())
+        self._slots = [slot(), slot()]
+        self._tiles = torch.empty((self._total, abi.TILE_PIXELS, 3), dtype=torch.float32, device=dev)
+        self._tiles8 = torch.empty((self._total, abi.TILE_PIXELS, 3), dtype=torch.uint8, device=dev)
+        self._motion = torch.zeros((h, w, 2), dtype=torch.float32, device=dev)
+        self._rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+        self._cur = 0          # the slot the next frame is written to
+        self.frames = 0        # frames since the last reset: 0 = the next one has no history
+
+    def _denoised(self, slot, **denoise_params):
+        return denoise(slot["rgb"], slot["aov"], self.gs.scene.width, self.gs.scene.height, **denoise_params)
+
+    def reset(self):
+        """drop the history: the next frame starts from its own samples"""
+        self.frames = 0
+
+    def frame(self, camera, seed, samples, max_depth=None, denoise=False, **denoise_params):
+        """Render `samples` per pixel under `camera` (an abi.Camera), reproject and accumulate -> dict of device tensors, valid
+        until the next frame(): rgb f32 [H,W,3] (the accumulated image), rgb8 u8 [H,W,3], len f32 [H,W], motion f32
+        [H,W,2], aov (the frame's first-hit buffers), and with denoise: denoised / denoised8, rt_hip_denoise of the accumulated
+        image under the frame's buffers (denoise_params: abi.denoise_params' keywords)"""
+        gs, total = self.gs, self._total
+        w, h = gs.scene.width, gs.scene.height
+        cur, prev = self._slots[self._cur], self._slots[self._cur ^ 1]
+        chunks = gs.suggest_chunks(total, samples, max_depth)
+        tiles, _, _ = gs.render_tiles(seed, 0, 1, total, tiles=self._tiles, tiles8=self._tiles8, samples=samples, max_depth=max_depth,
+                                      chunks=chunks, camera=camera)
+        gs.untile(tiles, None, 0, 1, total, image=cur["rgb"])
+        at = gs.render_aov(seed, samples, 0, 1, total, camera=camera, want=DENOISE_AOV)
+        src, dst = abi.RtHipAov(), abi.RtHipAov()
+        for f, t in at.items():
+            setattr(src, f, t.data_ptr())
+            setattr(dst, f, cur["aov"][f].data_ptr())
+        stream = torch.cuda.current_stream(torch.device("cuda", gs.device)).cuda_stream
+        _check(gs.shim.rt_hip_untile_aov(C.byref(src), w, h, 0, 1, total, C.byref(dst), C.c_void_p(stream)), "rt_hip_untile_aov")
+        C.memmove(C.byref(cur["camera"]), C.byref(camera), C.sizeof(abi.Camera))
+        res = reproject(cur["rgb"], cur["aov"], cur["camera"], hist=prev if self.frames else None,
+                        out=dict(rgb=cur["rgb"], len=cur["len"], motion=self._motion, rgb8=self._rgb8), **self.params)
+        res["aov"] = cur["aov"]
+        if denoise:
+            res["denoised"], res["denoised8"] = self._denoised(cur, **denoise_params)
+        self._cur ^= 1
+        self.frames += 1
+        return res
+
+
+def reproject_image_host(rgb, aov, camera, hist=None, device=0, **params):
+    """rt_hip_reproject_image(): the C hosts' entry point (host arrays, its own device buffers on logical device `device`,
+    synchronous).  rgb float32 [H,W,3], aov a dict of numpy arrays as GpuScene.aov_image gives them, hist None or a dict with rgb,
+    len, aov and camera -> dict of numpy arrays: rgb, rgb8, len, motion"""
+    import numpy as np
+    shim = abi.load_shim()
+    p = abi.reproject_params(**params)
+    h, w = rgb.shape[:2]
+    keep = []
+
+    def pack(bufs):
+        a = abi.RtHipAov()
+        for f in REPROJECT_AOV:
+            arr = np.ascontiguousarray(bufs[f], dtype=np.float32 if f in ("normal", "depth") else np.uint32)
+            keep.append(arr)
+            setattr(a, f, arr.ctypes.data)
+        return a
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    a = pack(aov)
+    h_rgb = h_len = h_aov = h_cam = None
+    if hist is not None:
+        hr, hl = np.ascontiguousarray(hist["rgb"], dtype=np.float32), np.ascontiguousarray(hist["len"], dtype=np.float32)
+        keep += [hr, hl]
+        h_rgb, h_len, h_aov, h_cam = hr.ctypes.data, hl.ctypes.data, C.byref(pack(hist["aov"])), C.byref(hist["camera"])
+    out = dict(rgb=np.zeros((h, w, 3), np.float32), rgb8=np.zeros((h, w, 3), np.uint8), len=np.zeros((h, w), np.float32),
+               motion=np.zeros((h, w, 2), np.float32))
+    _check(shim.rt_hip_reproject_image(rgb.ctypes.data, C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, w, h, C.byref(p), device,
+                                       out["rgb"].ctypes.data, out["rgb8"].ctypes.data, out["len"].ctypes.data, out["motion"].ctypes.data),
+           "rt_hip_reproject_image")
+    return out
 
 
 def render_image_host(scene, seed, n_devices=1, samples=None, max_depth=None, integrator="path"):

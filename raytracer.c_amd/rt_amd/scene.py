@@ -62,6 +62,22 @@ def scene_info(config):
     return info
 
 
+def orbit_cameras(config, width, height, frames=8, step_deg=1.0):
+    """`frames` cameras on a circle about the configuration's target, in the horizontal plane through its camera, `step_deg`
+    apart and ending at the configuration's own camera: the camera move the temporal sweep and its tests use"""
+    import math
+    info = scene_info(config)
+    px, py, pz = info.cam_pos
+    tx, ty, tz = info.cam_target
+    dx, dz = px - tx, pz - tz
+    out = []
+    for k in range(frames):
+        a = math.radians(step_deg * (k - (frames - 1)))
+        ca, sa = math.cos(a), math.sin(a)
+        out.append(make_camera(width, height, (tx + ca * dx + sa * dz, py, tz - sa * dx + ca * dz), (tx, ty, tz)))
+    return out
+
+
 def build_scene(config, width=None, height=None, samples=None, max_depth=None):
     """BASELINE.json configs[config-1]; size / spp / depth default to the
     configuration's nominal values and can be scaled down for tests."""
