@@ -300,6 +300,15 @@ int render_aov(RtAovImage *out, Object *objects, size_t n_objects, MeshObject *m
 int intersect_rays(const Ray *rays, size_t n, const double *t_max, Object *objects, size_t n_objects, MeshObject *meshes,
                    size_t n_meshes, Hit *hits, uint8_t *status);
 
+/* What light arrives along the caller's own rays (include/rt_hip.h, rt_hip_trace_rays_host: the contract in full): for each of the n
+ * rays, used as given, radiance[i] = the mean of `samples` trace_path() samples (raytracer.c:482-554) at rt_get_max_depth(), sample s
+ * of ray i on the stream (rt_get_seed(), i, s) after render()'s two jitter draws.  status[i] (may be NULL): 1 traced, 2 invalid ray (a
+ * non-finite component, a direction whose squared length is farther than 2^-13 from 1: radiance 0).  Adds the traced paths and their
+ * primitive tests to ray_count and intersection_test_count, as render does.  Runs on one device, the first of the device map.
+ * Returns 0, or a negative RT_HIP_E* code with the reason on stderr. */
+int trace_rays(const Ray *rays, size_t n, int samples, Object *objects, size_t n_objects, MeshObject *meshes, size_t n_meshes,
+               vec3 *radiance, uint8_t *status);
+
 /* Edge-avoiding a-trous denoise of a frame (include/rt_hip.h, rt_hip_denoise: the contract in full) guided by the first-hit
  * buffers of its own samples: linear_in is the frame's linear mean (render_ex's linear_rgb, width x height x 3 floats), aov its
  * render_aov buffers (normal, depth and hits always; albedo with RT_HIP_DENOISE_DEMODULATE, object_id with _OBJECT_EDGES).

@@ -437,6 +437,82 @@ const char *rt_hip_query_kernel_name(const RtHipScene *scene);
 int rt_hip_query_kernel_count(void);
 const char *rt_hip_query_kernel_launches(int index, uint64_t *launches);
 
+/* ---- radiance queries: trace_path along rays the caller chooses -------------------------------------------------------------
+ * What light arrives along a ray: light probes and lightmap baking (rays that start on surfaces), panoramic, fisheye or orthographic
+ * views, thin-lens depth of field, resampling of chosen pixels, sensor simulation -- trace_path() (raytracer.c:482-554) with a first
+ * ray that no pinhole camera forms.  A call takes n rays (0 <= n < 2^32) and params->samples = S >= 1 samples per ray.
+ * Ray i is formed exactly as rt_hip_query_rays forms it (RT_HIP_RAYS_GIVEN, or RT_HIP_RAYS_CAMERA_UV operation for operation, with
+ * RT_HIP_RAYS_NORMALIZE the direction through vec3_normalize first) and is INVALID under that contract's rule without its t_max
+ * clause: a component of the origin or of the direction is not finite, or | ((dx*dx + dy*dy) + dz*dz) - 1 | > 2^-13.
+ * Sample s of a valid ray: the RNG state is that of the stream (seed, index_first + i, s) of rt_rng.h; its first two draws are taken
+ * and discarded -- they are render()'s jitter (raytracer.c:203-206), so a sample of a pixel and a sample of a ray with that index
+ * see the same draws -- and the sample's value is trace_path(&ray, scene, n, 0) at MAX_DEPTH = params->max_depth with the stream
+ * going on from the third draw.
+ * The mean, in the order of the static render kernels: S_k (k = 0 .. 3) is the ascending vec3_add, from +0.0, of the samples with
+ * s = k (mod 4); total = (S_0 + S_1) + (S_2 + S_3); radiance = total * (1.0 / (double)S).
+ * Outputs are structure-of-arrays (RtHipRadiance; each pointer may be NULL, not all):
+ *   field     per ray              valid ray                                                         invalid ray
+ *   status    uint32               1                                                                 2
+ *   radiance  3 double             the mean above                                                    0
+ *   samples   3 double per sample  the S sample values, ray-major: sample s of ray i at [i*S + s]    0
+ *   paths     uint64               trace_path calls (raytracer.c:484) summed over the ray's samples   0
+ *   casts     uint64               scene scans (intersect calls) summed over the ray's samples       0
+ *   ray       6 double             the ray used, after CAMERA_UV / NORMALIZE                         as computed
+ * d_stats (RT_HIP_NSTATS accumulators, may be NULL) += rays: the sum of paths; casts: the sum of casts; tests: casts x primitives
+ * (derived, as everywhere else); samples: valid rays x S.
+ * Exactness.  Every decision is the reference's -- hit or miss, the closest index, the roulette, the rejection rounds, the
+ * hemisphere flip -- so every draw, and `paths` and `casts` per ray, equal the compiled reference exactly.  The VALUES are those of
+ * the render kernels' iteration (Ls += T (.) e; T = T (.) albedo cos), which is the reference's recursion in another association:
+ * equal to fp64 rounding (a few 2^-53 per bounce), NOT bit for bit.  Bit-exact are:
+ *   (a) radiance is the stated reduction of samples;
+ *   (b) results do not depend on how a batch is split: rays [a, b) traced with index_first = a give the bits the same rays get
+ *       inside a larger call;
+ *   (c) ray equals rt_hip_query_rays' ray for the same input;
+ *   (d) the samples values do not depend on S: a sample is a function of (seed, index, s), the ray and the scene.
+ * The first scan of a ray in the band that is not unit to 2^-40 drops nothing by a conservative rule, as a query's scan; later
+ * bounces keep the rules.  params->origin_radius is rt_hip_query_rays' hint (near_R = 1.5 (origin_radius + reach) + 1, >= 1e15:
+ * RT_HIP_EINVAL) and changes no output bit.  params->max_depth: 0 .. 1000000, and <= 32 for scenes with M_REFRACTION materials
+ * (RT_HIP_ELIMIT), as rt_hip_render_tiles.  params->integrator must be RT_HIP_TRACE_PATH (cast_ray: RT_HIP_EINVAL).
+ *   - rt_hip_trace_defaults: source GIVEN, flags 0, camera NULL, origin_radius 0, samples 1, max_depth 5, seed 0, index_first 0,
+ *     integrator RT_HIP_TRACE_PATH.
+ *   - rt_hip_trace_rays: asynchronous on `stream`, on the scene's device.  d_rays must be 16-byte aligned; index_first + n <= 2^32.
+ *     Arguments are checked before the device is looked for (RT_HIP_EINVAL, then RT_HIP_ENODEV).  n == 0 is RT_HIP_OK and launches
+ *     nothing.  The kernels trace M_REFRACTION's two children through the per-device pending-ray pool and report through the
+ *     device's status word exactly as the render launches of pt_render_tiles_refr and its siblings do: rt_hip_launch_status tells
+ *     of a workgroup that found no slot, and that workgroup's valid rays get NaN radiance and samples (the render's rule).
+ *   - rt_hip_trace_rays_host: the same from host arrays, synchronous, with a scene and buffers of its own, on logical device
+ *     `device` of rt_hip_render_image's device map; h_stats (may be NULL) += the counters.
+ *   - rt_hip_trace_kernel_name names the form a scene's radiance queries take; rt_hip_trace_kernel_count / _launches list the
+ *     forms and how many launches of each this process has made (not members of the family of rt_hip_kernel_count). */
+typedef struct
+{
+  uint32_t source;           /* RT_HIP_RAYS_GIVEN | RT_HIP_RAYS_CAMERA_UV, as rt_hip_query_rays */
+  uint32_t flags;            /* RT_HIP_RAYS_NORMALIZE */
+  const RtHipCamera *camera; /* host pointer; used with RT_HIP_RAYS_CAMERA_UV */
+  double origin_radius;      /* as rt_hip_query_rays: a hint, changes no output bit */
+  int32_t samples;           /* S >= 1 */
+  int32_t max_depth;         /* the reference's MAX_DEPTH */
+  uint64_t seed;
+  uint32_t index_first;      /* stream index of ray 0; index_first + n <= 2^32 */
+  uint32_t integrator;       /* must be RT_HIP_TRACE_PATH */
+} RtHipTraceParams;
+typedef struct
+{
+  uint32_t *status;         /* 1 traced, 2 invalid */
+  double *radiance;         /* 3 per ray: the mean over the S samples */
+  double *samples;          /* 3 per (ray, sample), ray-major: [i*S + s]; optional */
+  uint64_t *paths, *casts;  /* per ray, summed over its samples */
+  double *ray;              /* 6 per ray: the ray used */
+} RtHipRadiance;
+void rt_hip_trace_defaults(RtHipTraceParams *params);
+int rt_hip_trace_rays(const RtHipScene *scene, const double *d_rays, uint64_t n, const RtHipTraceParams *params,
+                      const RtHipRadiance *d_out, uint64_t *d_stats, void *stream);
+int rt_hip_trace_rays_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_rays,
+                           uint64_t n, const RtHipTraceParams *params, int device, const RtHipRadiance *h_out, uint64_t *h_stats);
+const char *rt_hip_trace_kernel_name(const RtHipScene *scene);
+int rt_hip_trace_kernel_count(void);
+const char *rt_hip_trace_kernel_launches(int index, uint64_t *launches);
+
 /* ---- edge-avoiding a-trous denoiser guided by the first-hit buffers ---------------------------------------------------------
  * Inputs: row-major images of w x h pixels (1 <= w, h <= 2^20, w*h < 2^32) on one device -- colour c (3 floats per pixel: the
  * linear mean of rt_hip_render_tiles or rt_hip_accum_resolve after rt_hip_untile) and the RtHipAov buffers of the same frame

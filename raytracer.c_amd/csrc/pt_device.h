@@ -372,6 +372,22 @@ struct PtQuery
   double *point, *normal, *bary, *ray; /* 3, 3, 2, 6 doubles per ray */
 };
 
+/* One radiance query (rt_hip.h, rt_hip_trace_rays; trace_rays in pt_kernel.hip): n rays in as for PtQuery, per ray the mean of
+ * PtLaunch.samples trace_path samples out.  Sample s of ray i runs on the stream (PtLaunch.seed, index_first + i, s) after two
+ * discarded draws; PtLaunch.max_depth is the reference's MAX_DEPTH.  samples: 3 doubles per (ray, sample), [i * S + s].  paths /
+ * casts: per ray, summed over its samples.  Any output may be null (not all: the shim refuses that). */
+struct PtTrace
+{
+  const double *rays;
+  uint64_t n; /* < 2^32, index_first + n <= 2^32 */
+  uint32_t camera_uv, normalize;
+  uint32_t index_first;
+  uint32_t *status;
+  double *radiance, *samples;
+  unsigned long long *paths, *casts;
+  double *ray; /* 6 doubles per ray */
+};
+
 /* One launch of the denoiser (rt_hip.h, rt_hip_denoise; pt_denoise_* in pt_kernel.hip).  The workspace holds, per pixel of the
  * row-major w x h image: two ping-pong float4 colour buffers e[0], e[1] (the filtered signal, .w = 1 valid / 0 invalid), the
  * guidance float4 (normal, depth) and uint2 (hits, object) the prepare pass packs so that a tap is three loads. */
@@ -495,6 +511,14 @@ hipError_t pt_launch_query(const PtLaunch &launch, const PtQuery &query, hipStre
 const char *pt_query_kernel_name_of(int which);
 int pt_query_kernel_count(void);
 unsigned long long pt_query_kernel_launches(int which);
+/* the radiance-query kernels (pt_kernel.hip: trace_rays, PT_TRACE_FAMILY): which form a scene takes (as pt_query_pick), the launch
+ * (64 rays x 4 sample slices per workgroup; launch.samples, max_depth, seed, the pending-ray pool and the status word as a render
+ * launch of the static M_REFRACTION members), names and launch counters */
+int pt_trace_pick(const PtSceneView &scene);
+hipError_t pt_launch_trace(const PtLaunch &launch, const PtTrace &trace, hipStream_t stream, int which);
+const char *pt_trace_kernel_name_of(int which);
+int pt_trace_kernel_count(void);
+unsigned long long pt_trace_kernel_launches(int which);
 /* the denoiser: the prepare pass and `iterations` filter passes (the last one remodulates and tonemaps) on `stream` */
 hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma_color, hipStream_t stream);
 /* temporal reprojection: one launch, a 16 x 16 block of pixels per workgroup, on `stream` */

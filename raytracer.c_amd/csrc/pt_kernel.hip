@@ -64,10 +64,11 @@
  *   pt_body_static.h  render_tiles_static   (pt_render_tiles_v0, *_refr, pt_whitted_tiles*, *_mem)
  * This file keeps the kernel family (PT_FAMILY: the entry points, their ids and properties), the AOV kernels (render_aov,
  * PT_AOV_FAMILY: first-hit feature buffers, not members of the family), the ray-query kernels (query_rays, PT_QUERY_FAMILY: closest
- * hits of the caller's rays, a list of their own too), the table-building and self-test kernels, pt_untile,
+ * hits of the caller's rays, a list of their own too), the radiance-query kernels (trace_rays, PT_TRACE_FAMILY: trace_path along the
+ * caller's rays, a third such list), the table-building and self-test kernels, pt_untile,
  * and the host side declared in pt_device.h: the launch plan (pt_plan_launch, around the pick table pt_pick_kernel) and the
- * launchers (pt_launch_render, pt_launch_aov, pt_launch_query).  The three lists are a PtKernelList each (rows + launch
- * counters) and the three launchers go through launch_staged (dynamic-LDS limit, launch, error).
+ * launchers (pt_launch_render, pt_launch_aov, pt_launch_query, pt_launch_trace).  The four lists are a PtKernelList each (rows + launch
+ * counters) and the four launchers go through launch_staged (dynamic-LDS limit, launch, error).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -219,7 +220,7 @@ PT_FAMILY_DEV(PT_ENTRY)
 #undef PT_ENTRY
 
 /* ---- a kernel list on the host: the rows an X-macro list generates, and how often each was launched in this process
- * (what a test run actually exercised).  The three lists (PT_FAMILY, PT_AOV_FAMILY, PT_QUERY_FAMILY) are one of these each;
+ * (what a test run actually exercised).  The four lists (PT_FAMILY, PT_AOV_FAMILY, PT_QUERY_FAMILY, PT_TRACE_FAMILY) are one of these each;
  * pt_*_name_of / _count / _launches (pt_device.h) ask it.  The lists' ids come from PT_LIST_ID, the rows of the two plain
  * lists from PT_LIST_INFO; the family's rows carry more (PT_INFO), and each list's entry points have their own signature, so
  * the three ENTRY macros stay apart. */
@@ -428,6 +429,43 @@ enum PtAovKernelId
 typedef void (*PtAovKernelFn)(const PtLaunch, const PtAovOut);
 static PtKernelList<PtEntryInfo<PtAovKernelFn>, A_COUNT> pt_aov_kernels = {{PT_AOV_FAMILY(PT_LIST_INFO)}};
 
+/* ---- a ray of the caller's (the ray-query and the radiance-query kernels): ray i of `rays` as given (a 48-byte record) or
+ * get_camera_ray of its (u, v) as start_sample forms it from its two draws; with `normalize` the direction goes through
+ * vec3_normalize first.  t_max: the ray's limit, t_max_of[i], or DBL_MAX without such an array (the radiance queries have none).
+ * Returns whether the ray is valid: every component finite, | |d|^2 - 1 | <= 2^-13 and the limit not NaN (rt_hip.h); no_rules: in
+ * that band but not unit to 2^-40 -- the ray's scan must drop nothing by a conservative rule (query_rays). */
+__device__ __forceinline__ bool caller_ray(const PtLaunch &L, const double *rays, const double *t_max_of, uint64_t i, uint32_t camera_uv,
+                                           uint32_t normalize, V3 &o, V3 &d, double &t_max_out, bool &no_rules_out)
+{
+  if (camera_uv)
+  { /* get_camera_ray (raytracer.c:375-384), as start_sample forms it from its two draws */
+    const double2 uv = reinterpret_cast<const double2 *>(rays)[i];
+    const CameraRegs cam = load_camera(L);
+    const V3 on_plane = v_add(cam.llc, v_add(v_scale(cam.horizontal, uv.x), v_scale(cam.vertical, uv.y)));
+    o = cam.pos;
+    d = v_normalize_fast(v_sub(cam.pos, on_plane));
+  }
+  else
+  { /* a 48-byte record: three 16-byte loads */
+    const double2 *r = reinterpret_cast<const double2 *>(rays) + 3u * i;
+    const double2 a = r[0], b = r[1], c = r[2];
+    o = {a.x, a.y, b.x};
+    d = {b.y, c.x, c.y};
+  }
+  if (normalize)
+    d = v_normalize_fast(d); /* vec3_normalize (vector.h:53-58): zero gives NaN, an overflowing dot gives zero -- both invalid */
+  const double t_max = t_max_of ? t_max_of[i] : L.t_start;
+  const double dd = v_dot(d, d);
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);
+  auto finite = [&](double x) { return __builtin_fabs(x) < inf; }; /* false for NaN */
+  const bool valid = finite(o.x) && finite(o.y) && finite(o.z) && finite(d.x) && finite(d.y) && finite(d.z) &&
+                     __builtin_fabs(dd - 1.0) <= 0x1p-13 && t_max == t_max;
+  const bool no_rules = !(__builtin_fabs(dd - 1.0) <= 0x1p-40);
+  t_max_out = t_max;
+  no_rules_out = no_rules;
+  return valid;
+}
+
 /* ---- ray-query body: a lane = one ray of the caller's, a wave = 64 consecutive rays ---------------------------------------------
  * rt_hip.h has the contract.  A lane forms its ray (as given, or get_camera_ray of its (u, v) as start_sample forms it; with
  * `normalize` the direction goes through vec3_normalize first), decides whether it is valid, runs ONE intersect() -- scan_filtered
@@ -455,30 +493,10 @@ __device__ __forceinline__ void query_rays(const PtLaunch &L, const PtQuery &Q)
   if (i >= Q.n)
     return; /* the last wave's spare lanes, the last workgroup's spare waves (no barrier follows) */
   V3 o, d;
-  if (Q.camera_uv)
-  { /* get_camera_ray (raytracer.c:375-384), as start_sample forms it from its two draws */
-    const double2 uv = reinterpret_cast<const double2 *>(Q.rays)[i];
-    const CameraRegs cam = load_camera(L);
-    const V3 on_plane = v_add(cam.llc, v_add(v_scale(cam.horizontal, uv.x), v_scale(cam.vertical, uv.y)));
-    o = cam.pos;
-    d = v_normalize_fast(v_sub(cam.pos, on_plane));
-  }
-  else
-  { /* a 48-byte record: three 16-byte loads */
-    const double2 *r = reinterpret_cast<const double2 *>(Q.rays) + 3u * i;
-    const double2 a = r[0], b = r[1], c = r[2];
-    o = {a.x, a.y, b.x};
-    d = {b.y, c.x, c.y};
-  }
-  if (Q.normalize)
-    d = v_normalize_fast(d); /* vec3_normalize (vector.h:53-58): zero gives NaN, an overflowing dot gives zero -- both invalid */
-  const double t_max = Q.t_max ? Q.t_max[i] : L.t_start;
-  const double dd = v_dot(d, d);
+  double t_max;
+  bool no_rules;
+  const bool valid = caller_ray(L, Q.rays, Q.t_max, i, Q.camera_uv, Q.normalize, o, d, t_max, no_rules);
   const double inf = __longlong_as_double(0x7FF0000000000000ll);
-  auto finite = [&](double x) { return __builtin_fabs(x) < inf; }; /* false for NaN */
-  const bool valid = finite(o.x) && finite(o.y) && finite(o.z) && finite(d.x) && finite(d.y) && finite(d.z) &&
-                     __builtin_fabs(dd - 1.0) <= 0x1p-13 && t_max == t_max;
-  const bool no_rules = !(__builtin_fabs(dd - 1.0) <= 0x1p-40);
 
   double min_t = S.t_start, bary_u = 0, bary_v = 0;
   int best = -1;
@@ -559,6 +577,208 @@ enum PtQueryKernelId
 };
 typedef void (*PtQueryKernelFn)(const PtLaunch, const PtQuery);
 static PtKernelList<PtEntryInfo<PtQueryKernelFn>, Q_COUNT> pt_query_kernels = {{PT_QUERY_FAMILY(PT_LIST_INFO)}};
+
+/* ---- radiance-query body: a lane = (ray, sample slice), a workgroup = 64 consecutive rays x 4 slices -------------------------------
+ * rt_hip.h has the contract.  render_tiles_static's loop (pt_body_static.h) with three things changed: the lane mapping (ray
+ * blockIdx.x * 64 + (threadIdx.x >> 2), slice threadIdx.x & 3; no tiles, `inside` is i < n), the first ray (caller_ray, as
+ * query_rays forms it, kept in LDS for the lane's later samples; the stream (seed, index_first + i, s) with its first two draws --
+ * render()'s jitter -- taken and discarded, instead of start_sample) and the epilogue (fp64 outputs, per-sample values and per-ray
+ * counters; no float image, no tonemap).  The first scan of a ray in the band that is not unit to 2^-40 runs with no_rules, as
+ * query_rays scans it; later bounces are vec3_normalize results (or mirror images of such) and keep the rules.  BigPrune and the
+ * hull-facet rule are off, as in the static trace_path members (MODE 0 without DEFER_DIR reads no `leaving`).
+ * A lane adds its slice's samples s = slice, slice + 4, ... in ascending order to a sum that starts at +0.0; the four slice sums
+ * are combined as (S0 + S1) + (S2 + S3) by the static body's shuffles and scaled by 1.0 / (double)S. */
+template <bool REFRACT, bool CHECKER, bool TRIS = false, bool FILT_LDS = true, bool GEOM_LDS = true>
+__device__ __forceinline__ void trace_rays(const PtLaunch &L, const PtTrace &Q)
+{
+  static_assert(GEOM_LDS || !FILT_LDS, "a staged filter table comes with staged geometry");
+  constexpr uint32_t RAYS = PT_BLOCK / PT_SLICES; /* rays per workgroup */
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  __shared__ unsigned long long wg_stats[3];
+  __shared__ double ray_lds[6 * RAYS]; /* [component][ray of the workgroup] */
+  SceneCtx S_init = stage_scene<GEOM_LDS, FILT_LDS>(L, lds);
+  __shared__ double atan_tab[CHECKER ? PT_ATAN_TAB : 1];
+  if (CHECKER)
+  {
+    atan_table_to_lds(atan_tab);
+    S_init.atan_tab = atan_tab;
+  }
+  const SceneCtx S = S_init;
+  if (threadIdx.x < 3)
+    wg_stats[threadIdx.x] = 0;
+
+  const uint32_t slice = threadIdx.x & (PT_SLICES - 1), ray_in_wg = threadIdx.x / PT_SLICES;
+  const uint64_t i = (uint64_t)blockIdx.x * RAYS + ray_in_wg;
+  const bool inside = i < Q.n;
+  bool valid = false, band = false;
+  if (inside)
+  {
+    V3 o, d;
+    double no_limit;
+    valid = caller_ray(L, Q.rays, nullptr, i, Q.camera_uv, Q.normalize, o, d, no_limit, band);
+    if (slice == 0)
+    {
+      ray_lds[0 * RAYS + ray_in_wg] = o.x; ray_lds[1 * RAYS + ray_in_wg] = o.y; ray_lds[2 * RAYS + ray_in_wg] = o.z;
+      ray_lds[3 * RAYS + ray_in_wg] = d.x; ray_lds[4 * RAYS + ray_in_wg] = d.y; ray_lds[5 * RAYS + ray_in_wg] = d.z;
+    }
+  }
+  /* the workgroup's slot of the pending-ray pool (PendStack), as the static body takes it */
+  __shared__ uint32_t pend_slot_lds;
+  if (REFRACT && threadIdx.x == 0)
+    pend_slot_lds = pt_pool_acquire(L.pend_flags, L.pend_slots_per_xcd, L.status, PT_FAIL_PEND_SLOT);
+  __syncthreads();
+  const uint32_t pend_slot = REFRACT ? pend_slot_lds : 0u;
+  const bool pend_ok = !REFRACT || pend_slot != 0xFFFFFFFFu;
+  const PendStack stack = {REFRACT && pend_ok ? L.pend_ws + (size_t)pend_slot * L.pend_slot_doubles + threadIdx.x : nullptr,
+                           REFRACT && pend_ok ? (int)L.pend_entries : 0, PT_BLOCK, PT_PEND_FIELDS * PT_BLOCK};
+
+  const uint32_t spp = (uint32_t)L.samples;
+  const uint64_t pixel_key = rt_rng_pixel_key(L.seed, Q.index_first + (uint32_t)i);
+  V3 acc = {0, 0, 0};
+  Path P;
+  P.o = {0, 0, 0};
+  P.d = {0, 0, 1};
+  P.T = {1, 1, 1};
+  P.Ls = {0, 0, 0};
+  P.rng = 1;
+  P.depth = 0;
+  uint32_t n_rays = 0, n_casts = 0;
+  unsigned long long paths = 0, casts = 0; /* of this lane's finished samples */
+  uint32_t s = (valid && pend_ok) ? slice : spp;
+  bool fresh = true;
+  int stack_n = 0;
+  unsigned long long *diag_ptr = L.stats;
+  (void)diag_ptr;
+
+  while (s < spp)
+  {
+    const bool first = fresh;
+    if (fresh)
+    {
+      P.rng = sample_state_from_term(pixel_key, sample_term(s));
+      (void)rnd(P.rng); /* render()'s two jitter draws (raytracer.c:203-206): a sample of a pixel and a sample of a ray */
+      (void)rnd(P.rng); /* with that index see the same draws after them */
+      const uint32_t z = opaque_zero() + ray_in_wg; /* (read here, per sample: hoisted, the ray would hold twelve registers for the whole loop) */
+      P.o = {ray_lds[0 * RAYS + z], ray_lds[1 * RAYS + z], ray_lds[2 * RAYS + z]};
+      P.d = {ray_lds[3 * RAYS + z], ray_lds[4 * RAYS + z], ray_lds[5 * RAYS + z]};
+      P.T = {1, 1, 1};
+      P.Ls = {0, 0, 0};
+      P.depth = 0;
+      fresh = false;
+    }
+    n_rays++;
+    const bool finished = trace_step<1, REFRACT, CHECKER, TRIS, FILT_LDS, 0, false, false, false, PendStack, true>(
+        S, P, n_casts, diag_ptr, stack, stack_n, nullptr, nullptr, first && band);
+    if (finished)
+    {
+      acc = v_add(acc, P.Ls);
+      if (Q.samples)
+      {
+        double *q = Q.samples + 3u * (i * spp + s);
+        q[0] = P.Ls.x; q[1] = P.Ls.y; q[2] = P.Ls.z;
+      }
+      paths += n_rays;
+      casts += n_casts;
+      n_rays = n_casts = 0;
+      s += PT_SLICES;
+      fresh = true;
+    }
+  }
+
+  const double quiet_nan = __longlong_as_double(0x7FF8000000000000ll);
+  if (inside && Q.samples && !(valid && pend_ok)) /* an invalid ray: zeros; a workgroup without its pool slot: NaN (the render's rule) */
+    for (uint32_t k = slice; k < spp; k += PT_SLICES)
+    {
+      double *q = Q.samples + 3u * (i * spp + k);
+      q[0] = q[1] = q[2] = valid ? quiet_nan : 0.0;
+    }
+  /* per-ray mean: the static body's fixed-order reduction over the 4 slice lanes */
+  acc.x += __shfl_xor(acc.x, 1);
+  acc.y += __shfl_xor(acc.y, 1);
+  acc.z += __shfl_xor(acc.z, 1);
+  acc.x += __shfl_xor(acc.x, 2);
+  acc.y += __shfl_xor(acc.y, 2);
+  acc.z += __shfl_xor(acc.z, 2);
+  V3 mean = v_scale(acc, 1.0 / (double)spp);
+  if (valid && !pend_ok)
+    mean.x = mean.y = mean.z = quiet_nan;
+  if (paths)
+  {
+    atomicAdd(&wg_stats[0], paths);
+    atomicAdd(&wg_stats[1], casts);
+  }
+  paths += __shfl_xor(paths, 1);
+  casts += __shfl_xor(casts, 1);
+  paths += __shfl_xor(paths, 2);
+  casts += __shfl_xor(casts, 2);
+  if (inside && slice == 0)
+  {
+    if (valid)
+      atomicAdd(&wg_stats[2], 1ull);
+    if (Q.status)
+      Q.status[i] = valid ? 1u : 2u;
+    if (Q.radiance)
+    {
+      double *q = Q.radiance + 3u * i;
+      q[0] = mean.x; q[1] = mean.y; q[2] = mean.z;
+    }
+    if (Q.paths)
+      Q.paths[i] = paths;
+    if (Q.casts)
+      Q.casts[i] = casts;
+    if (Q.ray)
+    {
+      double2 *q = reinterpret_cast<double2 *>(Q.ray) + 3u * i;
+      q[0] = double2{ray_lds[0 * RAYS + ray_in_wg], ray_lds[1 * RAYS + ray_in_wg]};
+      q[1] = double2{ray_lds[2 * RAYS + ray_in_wg], ray_lds[3 * RAYS + ray_in_wg]};
+      q[2] = double2{ray_lds[4 * RAYS + ray_in_wg], ray_lds[5 * RAYS + ray_in_wg]};
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    if (L.stats)
+    {
+      const unsigned long long c = wg_stats[1];
+      atomicAdd(&L.stats[0], wg_stats[0]);
+      atomicAdd(&L.stats[1], c);
+      atomicAdd(&L.stats[2], c * (unsigned long long)(S.n_sph + S.n_tri));
+      atomicAdd(&L.stats[3], wg_stats[2] * (unsigned long long)spp);
+    }
+    if (REFRACT && pend_ok)
+      atomicExch(&L.pend_flags[pend_slot], 0u); /* every lane is past its last pop (the barrier above) */
+  }
+}
+
+/* ---- the radiance-query kernels (rt_hip_trace_rays): a third list of their own -- no rows of the pick table.  The scene alone picks
+ * the form (pt_trace_pick, as pt_query_pick); the five forms mirror the static trace_path members K_REFR, K_BIG_REFR, K_TRI_REFR,
+ * K_TRI_BIG_REFR and K_MEM, every material's code in each:
+ *   pt_trace_rays          spheres staged, filter staged (sign-test form)
+ *   pt_trace_rays_big      spheres staged, filter by scalar loads
+ *   pt_trace_rays_tri      + triangles through the flat filter and the fp32 pre-test
+ *   pt_trace_rays_tri_big  + triangles through the hierarchy
+ *   pt_trace_rays_mem      geometry from memory, triangles (if any) through the hierarchy
+ * Body: trace_rays<REFRACT, CHECKER, TRIS, FILT_LDS, GEOM_LDS>. */
+#define PT_TRACE_FAMILY(X) \
+  X(T_RAYS,    pt_trace_rays,         (PT_BLOCK, PT_MIN_WAVES_REFR),     trace_rays<true, true>) \
+  X(T_BIG,     pt_trace_rays_big,     (PT_BLOCK, PT_MIN_WAVES_REFR),     trace_rays<true, true, false, false>) \
+  X(T_TRI,     pt_trace_rays_tri,     (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), trace_rays<true, true, true, true>) \
+  X(T_TRI_BIG, pt_trace_rays_tri_big, (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), trace_rays<true, true, true, false>) \
+  X(T_MEM,     pt_trace_rays_mem,     (PT_BLOCK),                        trace_rays<true, true, true, false, false>)
+
+#define PT_TRACE_ENTRY(id, name, bounds, ...) \
+  extern "C" __global__ __launch_bounds__ bounds void name(const PtLaunch L, const PtTrace Q) { __VA_ARGS__(L, Q); }
+PT_TRACE_FAMILY(PT_TRACE_ENTRY)
+#undef PT_TRACE_ENTRY
+
+enum PtTraceKernelId
+{
+  PT_TRACE_FAMILY(PT_LIST_ID) T_COUNT
+};
+typedef void (*PtTraceKernelFn)(const PtLaunch, const PtTrace);
+#define PT_TRACE_INFO(id, name, bounds, ...) {#name, name},
+static PtKernelList<PtEntryInfo<PtTraceKernelFn>, T_COUNT> pt_trace_kernels = {{PT_TRACE_FAMILY(PT_TRACE_INFO)}};
+#undef PT_TRACE_INFO
 
 /* The sample count a resolve divides slot `slot` by: the launch's, or -- an accumulation with frozen tiles (rt_hip_accum_freeze) --
  * the slot's own where it has one (0: the slot is live and holds the launch's count). */
@@ -1933,6 +2153,43 @@ hipError_t pt_launch_query(const PtLaunch &launch, const PtQuery &query, hipStre
   const hipError_t e = launch_staged(pt_query_kernels[which].fn, blocks, lds_bytes, stream, launch, query);
   if (e == hipSuccess)
     pt_query_kernels.launched(which);
+  return e;
+}
+
+/* ---- the radiance-query kernels: which form a scene takes, and the launch ------------------------------------------------- */
+int pt_trace_pick(const PtSceneView &scene)
+{
+  if (!pt_geom_in_lds(scene))
+    return T_MEM;
+  const bool tris = scene.n_triangles != 0u;
+  if (pt_filter_in_lds(scene))
+    return tris ? T_TRI : T_RAYS;
+  return tris ? T_TRI_BIG : T_BIG;
+}
+
+const char *pt_trace_kernel_name_of(int which) { return pt_trace_kernels.name_of(which); }
+int pt_trace_kernel_count(void) { return T_COUNT; }
+unsigned long long pt_trace_kernel_launches(int which) { return pt_trace_kernels.launches(which); }
+
+hipError_t pt_launch_trace(const PtLaunch &launch, const PtTrace &trace, hipStream_t stream, int which)
+{
+#ifdef PT_DIAG
+  return hipErrorNotSupported; /* (the diagnostic build counts into stats[4 ..]: a caller's d_stats has RT_HIP_NSTATS words) */
+#endif
+  if (!pt_trace_kernels.valid(which) || trace.n == 0u || trace.n > 0xFFFFFFFFull || (uint64_t)trace.index_first + trace.n > 0x100000000ull ||
+      launch.samples < 1)
+    return hipErrorInvalidValue;
+  /* every form pushes pending second children: its pool, as pt_launch_render asks of a PEND_POOL member */
+  if (launch.pend_ws == nullptr || launch.pend_slots_per_xcd == 0u || launch.pend_entries == 0u ||
+      launch.pend_entries < pt_pend_entries(launch.scene, 0u, launch.max_depth) ||
+      launch.pend_slot_doubles < (uint64_t)launch.pend_entries * PT_PEND_FIELDS_HOST * PT_BLOCK)
+    return hipErrorInvalidValue;
+  const size_t lds_bytes = which == T_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the query launch */
+  const uint32_t rays_per_wg = PT_BLOCK / PT_SLICES;
+  const uint32_t blocks = (uint32_t)((trace.n + rays_per_wg - 1u) / rays_per_wg); /* at most 2^26 */
+  const hipError_t e = launch_staged(pt_trace_kernels[which].fn, blocks, lds_bytes, stream, launch, trace);
+  if (e == hipSuccess)
+    pt_trace_kernels.launched(which);
   return e;
 }
 

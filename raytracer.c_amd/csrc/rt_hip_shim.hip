@@ -2422,22 +2422,18 @@ bool hits_any(const RtHipHits *h)
   return h && (h->status || h->t || h->object || h->prim || h->point || h->normal || h->bary || h->ray);
 }
 
-/* the arguments of a query that need no device: RT_HIP_EINVAL, or RT_HIP_OK */
-int check_query(const void *rays, bool device_rays, uint64_t n, const RtHipQueryParams *p, const RtHipHits *hits)
+/* the ray front end's arguments (a ray query's and a radiance query's alike) that need no device: RT_HIP_EINVAL, or RT_HIP_OK */
+int check_rays(const void *rays, bool device_rays, uint64_t n, uint32_t source, uint32_t flags, const RtHipCamera *camera, double origin_radius)
 {
-  if (!p)
-    return fail(RT_HIP_EINVAL, "params is required");
-  if (!hits_any(hits))
-    return fail(RT_HIP_EINVAL, "hits: at least one output array is required");
   if (n > 0xFFFFFFFFull)
     return fail(RT_HIP_EINVAL, "n = %llu: a query takes fewer than 2^32 rays", (unsigned long long)n);
-  if (p->source != RT_HIP_RAYS_GIVEN && p->source != RT_HIP_RAYS_CAMERA_UV)
-    return fail(RT_HIP_EINVAL, "source %u is neither RT_HIP_RAYS_GIVEN nor RT_HIP_RAYS_CAMERA_UV", p->source);
-  if (p->flags & ~(uint32_t)RT_HIP_RAYS_NORMALIZE)
-    return fail(RT_HIP_EINVAL, "unknown flags %#x", p->flags);
-  if (!(p->origin_radius >= 0) || !std::isfinite(p->origin_radius))
-    return fail(RT_HIP_EINVAL, "origin_radius %g must be finite and >= 0", p->origin_radius);
-  if (p->source == RT_HIP_RAYS_CAMERA_UV && !p->camera)
+  if (source != RT_HIP_RAYS_GIVEN && source != RT_HIP_RAYS_CAMERA_UV)
+    return fail(RT_HIP_EINVAL, "source %u is neither RT_HIP_RAYS_GIVEN nor RT_HIP_RAYS_CAMERA_UV", source);
+  if (flags & ~(uint32_t)RT_HIP_RAYS_NORMALIZE)
+    return fail(RT_HIP_EINVAL, "unknown flags %#x", flags);
+  if (!(origin_radius >= 0) || !std::isfinite(origin_radius))
+    return fail(RT_HIP_EINVAL, "origin_radius %g must be finite and >= 0", origin_radius);
+  if (source == RT_HIP_RAYS_CAMERA_UV && !camera)
     return fail(RT_HIP_EINVAL, "RT_HIP_RAYS_CAMERA_UV needs params->camera");
   if (n != 0 && !rays)
     return fail(RT_HIP_EINVAL, "rays is required");
@@ -2446,28 +2442,50 @@ int check_query(const void *rays, bool device_rays, uint64_t n, const RtHipQuery
   return RT_HIP_OK;
 }
 
-int query_launch(const RtHipScene *scene, const double *d_rays, const double *d_t_max, uint64_t n, const RtHipQueryParams *p,
-                 const RtHipHits *d_hits, hipStream_t stream)
+/* the arguments of a query that need no device: RT_HIP_EINVAL, or RT_HIP_OK */
+int check_query(const void *rays, bool device_rays, uint64_t n, const RtHipQueryParams *p, const RtHipHits *hits)
 {
-  PtLaunch L;
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is required");
+  if (!hits_any(hits))
+    return fail(RT_HIP_EINVAL, "hits: at least one output array is required");
+  return check_rays(rays, device_rays, n, p->source, p->flags, p->camera, p->origin_radius);
+}
+
+/* The launch of a kernel that scans for rays of the caller's (a ray query, a radiance query): the scene- and near_R-dependent
+ * fields of launch_prepare with origin_radius in the camera distance's place, the camera of RT_HIP_RAYS_CAMERA_UV, and nothing a
+ * rule of the renderer's own rays needs -- the walls are not pruned among themselves (big_pairs stays 0) and no ray leaves a hull
+ * facet (the rule is the parked walks').  L is cleared first. */
+int ray_launch_prepare(const RtHipScene *scene, uint32_t source, const RtHipCamera *camera, double origin_radius, PtLaunch &L)
+{
   memset(&L, 0, sizeof L);
   L.scene = scene->view;
-  if (p->source == RT_HIP_RAYS_CAMERA_UV)
+  if (source == RT_HIP_RAYS_CAMERA_UV)
   {
-    memcpy(L.cam.pos, p->camera->position, sizeof L.cam.pos);
-    memcpy(L.cam.horizontal, p->camera->horizontal, sizeof L.cam.horizontal);
-    memcpy(L.cam.vertical, p->camera->vertical, sizeof L.cam.vertical);
-    memcpy(L.cam.llc, p->camera->lower_left_corner, sizeof L.cam.llc);
+    memcpy(L.cam.pos, camera->position, sizeof L.cam.pos);
+    memcpy(L.cam.horizontal, camera->horizontal, sizeof L.cam.horizontal);
+    memcpy(L.cam.vertical, camera->vertical, sizeof L.cam.vertical);
+    memcpy(L.cam.llc, camera->lower_left_corner, sizeof L.cam.llc);
   }
-  L.near_R = 1.5 * (p->origin_radius + scene->reach) + 1.0;
+  L.near_R = 1.5 * (origin_radius + scene->reach) + 1.0;
   if (!(L.near_R < RT_NEAR_R_LIMIT))
     return fail(RT_HIP_EINVAL, "origin_radius and scene extent give near_R = %g: not a usable finite bound", L.near_R);
   L.near_R2 = L.near_R * L.near_R;
   L.filt_shift = 12.0 * 5.9604644775390625e-08 * (scene->max_center + L.near_R) * (1.0 + 1e-9);
   mesh_bound_for(scene, L.near_R, L.mesh_bound);
-  L.hull_margin = 2.0; /* (no query ray leaves a facet: the rule is trace_step's) */
+  L.hull_margin = 2.0;
   L.background = 10 / 255.0;
   L.t_start = 1.7976931348623157e308; /* DBL_MAX */
+  return RT_HIP_OK;
+}
+
+int query_launch(const RtHipScene *scene, const double *d_rays, const double *d_t_max, uint64_t n, const RtHipQueryParams *p,
+                 const RtHipHits *d_hits, hipStream_t stream)
+{
+  PtLaunch L;
+  int rc = ray_launch_prepare(scene, p->source, p->camera, p->origin_radius, L);
+  if (rc)
+    return rc;
   const PtQuery Q = {.rays = d_rays, .t_max = d_t_max, .n = n, .camera_uv = p->source == RT_HIP_RAYS_CAMERA_UV ? 1u : 0u,
                      .normalize = (p->flags & RT_HIP_RAYS_NORMALIZE) ? 1u : 0u, .status = d_hits->status, .t = d_hits->t,
                      .object = d_hits->object, .prim = d_hits->prim, .point = d_hits->point, .normal = d_hits->normal,
@@ -2476,7 +2494,7 @@ int query_launch(const RtHipScene *scene, const double *d_rays, const double *d_
   DeviceScope scope(scene->device);
   HIP_TRY(scope.status);
   size_t slot = 0;
-  const int rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
+  rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
   if (rc)
     return rc;
   const hipError_t e = pt_launch_query(L, Q, stream, which);
@@ -2539,6 +2557,137 @@ int query_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtH
   for (int k = 0; k < 8; k++)
     if (host[k])
       HIP_TRY(hipMemcpy(host[k], dev[k], bytes_per_ray[k] * n, hipMemcpyDeviceToHost)); /* (null stream: after the kernel) */
+  return RT_HIP_OK;
+}
+
+/* ---- radiance queries (rt_hip.h, rt_hip_trace_*) ------------------------------------------------------------------------------
+ * A radiance query's launch is a query's launch (origin_radius in the camera distance's place, acquire_tables) that traces paths:
+ * it also takes what a render launch of a static M_REFRACTION member takes -- samples, max_depth and seed, the device's status word
+ * (status_word_for) and a slot pool of pending-ray stacks (pend_pool_for under g_pend_mutex, from the lookup until the launch is
+ * enqueued, as rt_hip_render_tiles_chunked holds it).  No plan: the scene alone picks the form, and every form is a PEND_POOL kernel
+ * of PT_PEND_COLUMNS stacks per slot.  BigPrune and the hull-facet rule stay off (big_pairs 0, margin 2), as for a query. */
+bool radiance_any(const RtHipRadiance *o)
+{
+  return o && (o->status || o->radiance || o->samples || o->paths || o->casts || o->ray);
+}
+
+/* the arguments of a radiance query that need no device: RT_HIP_EINVAL, or RT_HIP_OK */
+int check_trace(const void *rays, bool device_rays, uint64_t n, const RtHipTraceParams *p, const RtHipRadiance *out)
+{
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is required");
+  if (!radiance_any(out))
+    return fail(RT_HIP_EINVAL, "radiance: at least one output array is required");
+  if (p->integrator != RT_HIP_TRACE_PATH)
+    return fail(RT_HIP_EINVAL, "integrator %u: a radiance query traces paths (RT_HIP_TRACE_PATH) only", p->integrator);
+  if (p->samples < 1)
+    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", p->samples);
+  if (p->max_depth < 0 || p->max_depth > 1000000)
+    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  if (n > 0xFFFFFFFFull || (uint64_t)p->index_first + n > 0x100000000ull)
+    return fail(RT_HIP_EINVAL, "n = %llu, index_first = %u: a radiance query takes fewer than 2^32 rays with stream indices below 2^32",
+                (unsigned long long)n, p->index_first);
+  return check_rays(rays, device_rays, n, p->source, p->flags, p->camera, p->origin_radius);
+}
+
+int trace_launch(const RtHipScene *scene, const double *d_rays, uint64_t n, const RtHipTraceParams *p, const RtHipRadiance *d_out,
+                 uint64_t *d_stats, hipStream_t stream)
+{
+  if (scene->view.any_refract && p->max_depth > PT_REFRACT_MAX_DEPTH)
+    return fail(RT_HIP_ELIMIT, "scenes with M_REFRACTION materials support max_depth <= %d (two rays per refractive hit, "
+                               "raytracer.c:523-529; the pending-ray stack is fixed)", PT_REFRACT_MAX_DEPTH);
+  PtLaunch L;
+  int rc = ray_launch_prepare(scene, p->source, p->camera, p->origin_radius, L);
+  if (rc)
+    return rc;
+  L.samples = p->samples;
+  L.max_depth = p->max_depth;
+  L.seed = p->seed;
+  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
+  const PtTrace T = {.rays = d_rays, .n = n, .camera_uv = p->source == RT_HIP_RAYS_CAMERA_UV ? 1u : 0u,
+                     .normalize = (p->flags & RT_HIP_RAYS_NORMALIZE) ? 1u : 0u, .index_first = p->index_first, .status = d_out->status,
+                     .radiance = d_out->radiance, .samples = d_out->samples, .paths = reinterpret_cast<unsigned long long *>(d_out->paths),
+                     .casts = reinterpret_cast<unsigned long long *>(d_out->casts), .ray = d_out->ray};
+  const int which = pt_trace_pick(scene->view);
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  rc = status_word_for(scene->device, &L.status);
+  if (rc)
+    return rc;
+  size_t slot = 0;
+  rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
+  if (rc)
+    return rc;
+  hipError_t e = hipSuccess;
+  {
+    std::lock_guard<std::mutex> pend_lock(g_pend_mutex);
+    rc = pend_pool_for(scene->device, pt_pend_entries(scene->view, 0u, p->max_depth), PT_PEND_COLUMNS, L);
+    if (!rc)
+      e = pt_launch_trace(L, T, stream, which);
+  }
+  release_tables(scene, slot, stream);
+  if (rc)
+    return rc;
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_trace_kernel_name_of(which), hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+/* rt_hip_trace_rays_host: a scene of its own on the logical device, one allocation for the rays, the counters and the requested
+ * outputs, the launch on the null stream, the copies.  Everything is owned by this scope. */
+int trace_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_rays,
+                         uint64_t n, const RtHipTraceParams *params, int device, const RtHipRadiance *h_out, uint64_t *h_stats)
+{
+  int rc = check_trace(h_rays, false, n, params, h_out);
+  if (rc || n == 0)
+    return rc; /* (no ray: nothing to do, on any device or none) */
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  struct SceneOwner
+  {
+    RtHipScene *scene = nullptr;
+    ~SceneOwner() { rt_hip_scene_destroy(scene); }
+  } own;
+  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &own.scene);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  const size_t ray_doubles = params->source == RT_HIP_RAYS_CAMERA_UV ? 2u : 6u;
+  void *host[6] = {h_out->status, h_out->radiance, h_out->samples, h_out->paths, h_out->casts, h_out->ray};
+  const size_t bytes_per_ray[6] = {4, 24, 24u * (size_t)params->samples, 8, 8, 48};
+  size_t off[6], total = align256(ray_doubles * 8u * n);
+  const size_t off_stats = total;
+  total += align256(RT_HIP_NSTATS * sizeof(uint64_t));
+  for (int k = 0; k < 6; k++)
+  {
+    off[k] = total;
+    if (host[k])
+      total += align256(bytes_per_ray[k] * n);
+  }
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc(total));
+  HIP_TRY(hipMemcpy(buf.ptr, h_rays, ray_doubles * 8u * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(buf.at<char>(off_stats), 0, RT_HIP_NSTATS * sizeof(uint64_t)));
+  void *dev[6];
+  for (int k = 0; k < 6; k++)
+    dev[k] = host[k] ? buf.at<char>(off[k]) : nullptr;
+  const RtHipRadiance d_out = {(uint32_t *)dev[0], (double *)dev[1], (double *)dev[2], (uint64_t *)dev[3], (uint64_t *)dev[4], (double *)dev[5]};
+  rc = trace_launch(own.scene, buf.at<double>(), n, params, &d_out, buf.at<uint64_t>(off_stats), nullptr);
+  if (rc)
+    return rc;
+  for (int k = 0; k < 6; k++)
+    if (host[k])
+      HIP_TRY(hipMemcpy(host[k], dev[k], bytes_per_ray[k] * n, hipMemcpyDeviceToHost)); /* (null stream: after the kernel) */
+  if (h_stats)
+  {
+    uint64_t st[RT_HIP_NSTATS];
+    HIP_TRY(hipMemcpy(st, buf.at<char>(off_stats), sizeof st, hipMemcpyDeviceToHost));
+    for (int k = 0; k < RT_HIP_NSTATS; k++)
+      h_stats[k] += st[k];
+  }
   return RT_HIP_OK;
 }
 
@@ -3414,6 +3563,51 @@ int rt_hip_query_rays_host(const RtHipSphere *spheres, size_t n_spheres, const R
 {
   return guarded("rt_hip_query_rays_host", [&] {
     return query_rays_host_impl(spheres, n_spheres, meshes, n_meshes, h_rays, h_t_max, n, params, device, h_hits);
+  });
+}
+
+void rt_hip_trace_defaults(RtHipTraceParams *params)
+{
+  if (!params)
+    return;
+  memset(params, 0, sizeof *params);
+  params->source = RT_HIP_RAYS_GIVEN;
+  params->samples = 1;
+  params->max_depth = 5;
+  params->integrator = RT_HIP_TRACE_PATH;
+}
+
+const char *rt_hip_trace_kernel_name(const RtHipScene *scene) { return scene ? pt_trace_kernel_name_of(pt_trace_pick(scene->view)) : ""; }
+
+int rt_hip_trace_kernel_count(void) { return pt_trace_kernel_count(); }
+
+const char *rt_hip_trace_kernel_launches(int index, uint64_t *launches)
+{
+  if (index < 0 || index >= pt_trace_kernel_count())
+    return nullptr;
+  if (launches)
+    *launches = pt_trace_kernel_launches(index);
+  return pt_trace_kernel_name_of(index);
+}
+
+int rt_hip_trace_rays(const RtHipScene *scene, const double *d_rays, uint64_t n, const RtHipTraceParams *params,
+                      const RtHipRadiance *d_out, uint64_t *d_stats, void *stream)
+{
+  const int rc = check_trace(d_rays, true, n, params, d_out);
+  if (rc)
+    return rc;
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "scene is required");
+  if (n == 0)
+    return RT_HIP_OK;
+  return guarded("rt_hip_trace_rays", [&] { return trace_launch(scene, d_rays, n, params, d_out, d_stats, static_cast<hipStream_t>(stream)); });
+}
+
+int rt_hip_trace_rays_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_rays,
+                           uint64_t n, const RtHipTraceParams *params, int device, const RtHipRadiance *h_out, uint64_t *h_stats)
+{
+  return guarded("rt_hip_trace_rays_host", [&] {
+    return trace_rays_host_impl(spheres, n_spheres, meshes, n_meshes, h_rays, n, params, device, h_out, h_stats);
   });
 }
 

@@ -534,3 +534,42 @@ int intersect_rays(const Ray *rays, size_t n, const double *t_max, Object *objec
   free(words);
   return 0;
 }
+
+int trace_rays(const Ray *rays, size_t n, int samples, Object *objects, size_t n_objects, MeshObject *meshes, size_t n_meshes,
+               vec3 *radiance, uint8_t *status)
+{
+  if (!radiance || (n && !rays))
+  {
+    fprintf(stderr, "trace_rays: rays and radiance are required\n");
+    return RT_HIP_EINVAL;
+  }
+  if (n == 0)
+    return 0;
+  uint32_t *st = (uint32_t *)malloc(n * sizeof(uint32_t));
+  if (!st)
+  {
+    fprintf(stderr, "trace_rays: out of memory\n");
+    return RT_HIP_ENOMEM;
+  }
+  RtHipMesh *hm = hip_meshes(meshes, n_meshes);
+  RtHipTraceParams p;
+  rt_hip_trace_defaults(&p);
+  p.samples = samples;
+  p.max_depth = g_max_depth;
+  p.seed = g_seed;
+  const RtHipRadiance out = {st, (double *)radiance, NULL, NULL, NULL, NULL}; /* vec3: three doubles */
+  uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
+  const int rc = rt_hip_trace_rays_host((const RtHipSphere *)objects, n_objects, hm, n_meshes, (const double *)rays, n, &p, 0, &out, stats);
+  free(hm);
+  if (rc)
+    fprintf(stderr, "trace_rays: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+  else
+  {
+    ray_count += (long long)stats[0];
+    intersection_test_count += (long long)stats[2];
+    for (size_t i = 0; status && i < n; i++)
+      status[i] = (uint8_t)st[i];
+  }
+  free(st);
+  return rc;
+}

@@ -115,6 +115,22 @@ HIT_SHAPES = {"status": ("uint32", 1), "t": ("float64", 1), "object": ("uint32",
               "normal": ("float64", 3), "bary": ("float64", 2), "ray": ("float64", 6)}   # dtype, values per ray
 NO_HIT = 0xFFFFFFFF                 # object / prim of a miss
 
+
+class RtHipTraceParams(C.Structure):  # rt_hip.h: a radiance query (rt_hip_trace_defaults), 48 B
+    _fields_ = [("source", C.c_uint32), ("flags", C.c_uint32), ("camera", C.POINTER(Camera)), ("origin_radius", C.c_double),
+                ("samples", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint64), ("index_first", C.c_uint32),
+                ("integrator", C.c_uint32)]
+
+
+class RtHipRadiance(C.Structure):  # rt_hip.h: a radiance query's structure-of-arrays outputs (NULL: not wanted), 48 B
+    _fields_ = [("status", C.c_void_p), ("radiance", C.c_void_p), ("samples", C.c_void_p), ("paths", C.c_void_p),
+                ("casts", C.c_void_p), ("ray", C.c_void_p)]
+
+
+RADIANCE_FIELDS = ("status", "radiance", "samples", "paths", "casts", "ray")   # RtHipRadiance order
+RADIANCE_SHAPES = {"status": ("uint32", 1), "radiance": ("float64", 3), "samples": ("float64", 0), "paths": ("uint64", 1),
+                   "casts": ("uint64", 1), "ray": ("float64", 6)}   # dtype, values per ray (samples: 3 per sample)
+
 ADAPT_CHECKPOINT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_uint32)  # on_checkpoint(user, samples done, live tiles)
 
 DENOISE_DEMODULATE, DENOISE_OBJECT_EDGES = 1, 2   # RT_HIP_DENOISE_*
@@ -210,6 +226,14 @@ SHIM_SYMBOLS = {
     "rt_hip_query_kernel_name": (C.c_char_p, [C.c_void_p]),
     "rt_hip_query_kernel_count": (C.c_int, []),
     "rt_hip_query_kernel_launches": (C.c_char_p, [C.c_int, C.POINTER(C.c_uint64)]),
+    "rt_hip_trace_defaults": (None, [C.POINTER(RtHipTraceParams)]),
+    "rt_hip_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RtHipTraceParams), C.POINTER(RtHipRadiance), C.c_void_p,
+                                    C.c_void_p]),
+    "rt_hip_trace_rays_host": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.c_void_p, C.c_uint64,
+                                         C.POINTER(RtHipTraceParams), C.c_int, C.POINTER(RtHipRadiance), C.c_void_p]),
+    "rt_hip_trace_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "rt_hip_trace_kernel_count": (C.c_int, []),
+    "rt_hip_trace_kernel_launches": (C.c_char_p, [C.c_int, C.POINTER(C.c_uint64)]),
     "rt_hip_denoise_defaults": (None, [C.POINTER(RtHipDenoiseParams)]),
     "rt_hip_denoise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rt_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_void_p,
@@ -266,6 +290,8 @@ HOST_SYMBOLS = {
                                   C.POINTER(RtHipReprojectParams)]),
     "intersect_rays": (C.c_int, [C.POINTER(Ray), C.c_size_t, C.c_void_p, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
                                  C.POINTER(Hit), C.c_void_p]),
+    "trace_rays": (C.c_int, [C.POINTER(Ray), C.c_size_t, C.c_int, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
+                             C.POINTER(Vec3), C.c_void_p]),
     "rt_last_render_cancelled": (C.c_int, []),
     "rt_last_render_seconds": (C.c_double, []),
     "rt_last_ray_bounces": (C.c_longlong, []),
@@ -350,6 +376,23 @@ def query_params(source=RAYS_GIVEN, normalize=False, camera=None, origin_radius=
     load_shim().rt_hip_query_defaults(C.byref(p))
     p.source = source
     p.flags = RAYS_NORMALIZE if normalize else 0
+    if camera is not None:
+        p.camera = C.pointer(camera)
+    if origin_radius is not None:
+        p.origin_radius = origin_radius
+    return p
+
+
+def trace_params(samples, seed, max_depth=None, source=RAYS_GIVEN, normalize=False, camera=None, origin_radius=None, index_first=0):
+    """rt_hip_trace_defaults() with the given fields replaced (max_depth, origin_radius None: the defaults).  The camera is
+    referenced, not copied: keep it alive until the call that takes the params has returned."""
+    p = RtHipTraceParams()
+    load_shim().rt_hip_trace_defaults(C.byref(p))
+    p.source = source
+    p.flags = RAYS_NORMALIZE if normalize else 0
+    p.samples, p.seed, p.index_first = samples, seed, index_first
+    if max_depth is not None:
+        p.max_depth = max_depth
     if camera is not None:
         p.camera = C.pointer(camera)
     if origin_radius is not None:

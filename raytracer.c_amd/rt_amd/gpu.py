@@ -244,6 +244,63 @@ class GpuScene:
         return dict(status=int(res["status"][0]), object=int(res["object"].view("uint32")[0]), prim=int(res["prim"].view("uint32")[0]),
                     t=float(res["t"][0]), point=tuple(res["point"][0].tolist()), normal=tuple(res["normal"][0].tolist()))
 
+    def trace_kernel_name(self):
+        """the radiance-query form this scene's trace_rays / trace_uv launches take"""
+        return self.shim.rt_hip_trace_kernel_name(self.handle).decode()
+
+    def _trace(self, rays, per_ray, params, want, stats):
+        dev = torch.device("cuda", self.device)
+        rays = torch.as_tensor(rays, dtype=torch.float64, device=dev).reshape(-1, per_ray).contiguous()
+        if rays.data_ptr() % 16:
+            rays = rays.clone()   # (a view into a larger tensor: the kernel loads 16 bytes at a time)
+        n, spp = rays.shape[0], params.samples
+        out, rad = {}, abi.RtHipRadiance()
+        for f in want:
+            dtype, k = abi.RADIANCE_SHAPES[f]
+            shape = (n, spp, 3) if f == "samples" else ((n, k) if k > 1 else (n,))
+            out[f] = torch.empty(shape, dtype={"float64": torch.float64, "uint32": torch.int32, "uint64": torch.int64}[dtype], device=dev)
+            setattr(rad, f, out[f].data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "wanted")
+        if stats is None:
+            stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._trace_inputs = rays   # keep alive until the stream has used them
+        _check(self.shim.rt_hip_trace_rays(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.byref(params), C.byref(rad),
+                                           C.c_void_p(stats.data_ptr()), C.c_void_p(stream)), "rt_hip_trace_rays")
+        out["stats"] = stats
+        return out
+
+    def trace_rays(self, rays, samples, seed, max_depth=None, normalize=False, origin_radius=None, index_first=0,
+                   want=("status", "radiance"), stats=None):
+        """What light arrives along the caller's rays (rt_hip.h, rt_hip_trace_rays): rays [n, 6] float64 (origin, direction), the
+        mean of `samples` trace_path samples per ray, sample s of ray i on the stream (seed, index_first + i, s); asynchronous on
+        torch's current stream -> dict of device tensors: status int32 [n] (the uint32 words of the C-ABI), radiance float64
+        [n, 3], samples [n, samples, 3], paths / casts int64 [n], ray [n, 6] (want: which), and stats int64 [4] (rays, casts, tests,
+        samples; += into the tensor given).  max_depth None: the scene's own."""
+        p = abi.trace_params(samples, seed, self.scene.max_depth if max_depth is None else max_depth, abi.RAYS_GIVEN, normalize, None,
+                             origin_radius, index_first)
+        return self._trace(rays, 6, p, want, stats)
+
+    def trace_uv(self, uv, samples, seed, camera=None, max_depth=None, normalize=False, origin_radius=None, index_first=0,
+                 want=("status", "radiance"), stats=None):
+        """... of the camera rays get_camera_ray(camera, u, v) for uv [n, 2] float64 (camera None: the scene's own; origin_radius
+        None: the camera's distance from the world origin)"""
+        cam = camera if camera is not None else self.scene.camera
+        if origin_radius is None:
+            x, y, z = cam.position.tuple()
+            origin_radius = (x * x + y * y + z * z) ** 0.5
+        p = abi.trace_params(samples, seed, self.scene.max_depth if max_depth is None else max_depth, abi.RAYS_CAMERA_UV, normalize, cam,
+                             origin_radius, index_first)
+        return self._trace(uv, 2, p, want, stats)
+
+    def render_panorama(self, width, height, origin, samples, seed, max_depth=None):
+        """An equirectangular view from `origin` (scene.panorama_rays: no Camera expresses it), `samples` paths per pixel, pixel
+        k = y * width + x on the stream (seed, k, s) -> (float64 [height, width, 3] linear radiance on the device, stats)"""
+        from . import scene as S
+        ox, oy, oz = origin
+        out = self.trace_rays(S.panorama_rays(width, height, origin), samples, seed, max_depth,
+                              origin_radius=(ox * ox + oy * oy + oz * oz) ** 0.5, want=("radiance",))
+        return out["radiance"].reshape(height, width, 3), out["stats"]
+
     def denoised_image(self, seed, samples, **params):
         """The whole frame of `samples` per pixel (render_image), its first-hit buffers of the same samples, and the denoise
         (rt_hip_denoise; params: abi.denoise_params' keywords) -> numpy (noisy f32 [H,W,3], denoised f32 [H,W,3], denoised u8 [H,W,3])"""
@@ -698,4 +755,29 @@ def query_rays_host(scene, rays, t_max=None, normalize=False, origin_radius=None
     _check(shim.rt_hip_query_rays_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, rays.ctypes.data,
                                        t_max.ctypes.data if t_max is not None else None, n, C.byref(p), device, C.byref(hits)),
            "rt_hip_query_rays_host")
+    return out
+
+
+def trace_rays_host(scene, rays, samples, seed, max_depth=None, normalize=False, origin_radius=None, camera=None, index_first=0,
+                    device=0, want=("status", "radiance")):
+    """rt_hip_trace_rays_host(): the C hosts' entry point (its own scene and buffers on logical device `device`, synchronous).
+    rays: [n, 6] float64 (origin, direction), or with `camera` (an abi.Camera) [n, 2] (u, v) -> dict of numpy arrays: status uint32
+    [n], radiance float64 [n, 3], samples [n, samples, 3], paths / casts uint64 [n], ray [n, 6], and stats (a dict)"""
+    import numpy as np
+    shim = abi.load_shim()
+    per_ray = 2 if camera is not None else 6
+    rays = np.ascontiguousarray(np.asarray(rays, dtype=np.float64).reshape(-1, per_ray))
+    n = rays.shape[0]
+    p = abi.trace_params(samples, seed, scene.max_depth if max_depth is None else max_depth,
+                         abi.RAYS_CAMERA_UV if camera is not None else abi.RAYS_GIVEN, normalize, camera, origin_radius, index_first)
+    out, rad = {}, abi.RtHipRadiance()
+    for f in want:
+        dtype, k = abi.RADIANCE_SHAPES[f]
+        out[f] = np.zeros((n, samples, 3) if f == "samples" else ((n, k) if k > 1 else (n,)), dtype=dtype)
+        setattr(rad, f, out[f].ctypes.data)
+    stats = (C.c_uint64 * abi.NSTATS)()
+    meshes = scene.hip_meshes()
+    _check(shim.rt_hip_trace_rays_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, rays.ctypes.data, n, C.byref(p), device,
+                                       C.byref(rad), stats), "rt_hip_trace_rays_host")
+    out["stats"] = dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
     return out

@@ -95,6 +95,23 @@ def build_scene(config, width=None, height=None, samples=None, max_depth=None):
                  n_objects=info.n_objects, n_meshes=info.n_meshes, n_triangles=info.n_triangles, camera=cam)
 
 
+def panorama_rays(width, height, origin):
+    """The rays of an equirectangular view from `origin`, row-major [height * width, 6] float64: pixel (x, y) looks along longitude
+    phi = 2 pi (x + 0.5) / width - pi (0 at -z, as the configurations' cameras look) and latitude theta = pi / 2 - pi (y + 0.5) /
+    height (row 0 at the top): d = (cos theta sin phi, sin theta, -cos theta cos phi), then normalised as vec3_normalize would
+    (so | |d|^2 - 1 | is rounding, far inside the radiance queries' band).  No pinhole Camera expresses this view."""
+    import numpy as np
+    phi = 2.0 * np.pi * (np.arange(width) + 0.5) / width - np.pi
+    theta = 0.5 * np.pi - np.pi * (np.arange(height) + 0.5) / height
+    ct, st = np.cos(theta)[:, None], np.sin(theta)[:, None]
+    d = np.stack([ct * np.sin(phi)[None, :], st * np.ones((1, width)), -ct * np.cos(phi)[None, :]], axis=-1).reshape(-1, 3)
+    d = d * (1.0 / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]))[:, None]
+    rays = np.empty((width * height, 6))
+    rays[:, :3] = np.asarray(origin, dtype=np.float64)
+    rays[:, 3:] = d
+    return rays
+
+
 def custom_scene(objects, width, height, samples, max_depth, cam_pos, cam_target, meshes=None):
     """A hand-made scene: objects = list of dicts(flags, radius, center, color, emission)."""
     arr = (abi.Object * max(len(objects), 1))()
