@@ -330,6 +330,16 @@ int reproject_frame(uint8_t *framebuffer, float *linear_out, float *len_out, flo
                     const RtAovImage *aov, const Camera *camera, const float *hist_linear, const float *hist_len,
                     const RtAovImage *hist_aov, const Camera *hist_camera, int width, int height, const RtHipReprojectParams *params);
 
+/* Guided upsampling of a low-resolution frame to full size (include/rt_hip.h, rt_hip_upsample: the contract in full): linear_low is
+ * the low frame's linear mean (render_ex's linear_rgb at low_width x low_height under the FULL frame's camera, denoised or not),
+ * aov_low its render_aov buffers, aov the render_aov buffers of the width x height frame (normal, depth and hits always; albedo with
+ * RT_HIP_UPSAMPLE_DEMODULATE, object_id with _OBJECT_EDGES).  Writes the full-size linear image to linear_out, its tonemapped bytes
+ * to framebuffer and the confidence per pixel (1 .. 0: how much of the bilinear weight found the pixel's surface; 0: plain
+ * bilinear; -1: nothing usable) to conf_out; each may be NULL.  params NULL: rt_hip_upsample_defaults.  Runs on one device, the
+ * first of the device map.  Returns 0, or a negative RT_HIP_E* code with the reason on stderr. */
+int upsample_frame(uint8_t *framebuffer, float *linear_out, float *conf_out, const float *linear_low, const RtAovImage *aov_low,
+                   int low_width, int low_height, const RtAovImage *aov, int width, int height, const RtHipUpsampleParams *params);
+
 /* Kernel-only wall time of the last render()/render_ex(), seconds, and the
  * count of scene casts (rays that ran the intersection scan). */
 double rt_last_render_seconds(void);

@@ -618,6 +618,63 @@ int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHi
                            int32_t height, const RtHipReprojectParams *params, int device, float *h_out_rgb, uint8_t *h_out_rgb8,
                            float *h_out_len, float *h_out_motion);
 
+/* ---- guided upsampling: a full-size frame from a low-resolution render -------------------------------------------------------
+ * Joint bilateral upsampling (Kopf et al. 2007): the colour is rendered (and denoised) at a fraction of the size and brought to
+ * full size under the full-resolution first-hit buffers, which are cheap and exact; with DEMODULATE the texture detail and the
+ * silhouettes come from those guides, not from the colour.  Inputs: row-major images on one device -- the LOW frame of wl x hl
+ * pixels (primed names: colour c', 3 floats per pixel, and its RtHipAov buffers after rt_hip_untile_aov) and the guides, the
+ * RtHipAov buffers of the HIGH frame of w x h pixels; 2 <= w, h, wl, hl <= 2^20 and w*h, wl*hl < 2^32 (the lower bound is that of
+ * the division by w - 1).  Any ratio is allowed, not only integer ones and not only wl < w.  Both frames are of the same scene
+ * under the same camera struct (init_camera depends on the aspect ratio only, and get_camera_ray's (x + r) / (w - 1) ties the two
+ * pixel grids together).  Fields read, at both sizes: normal n, depth z and hits always; albedo with DEMODULATE; object with
+ * OBJECT_EDGES.
+ * All arithmetic is fp64 +, -, *, /, floor in the order written, unfused; values read from float buffers are widened exactly;
+ * every stored value is rounded to float32 (RNE).  eps = 2^-10.  dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  Every comparison is
+ * false for NaN.  Per HIGH pixel p = (x, y):
+ *   1. Its place in the low frame: fx = ((x + 0.5) * (wl - 1.0)) / (w - 1.0) - 0.5, fy likewise with h and hl (with equal sizes
+ *      this is exactly x).  x0 = floor(fx), a = fx - x0, y0 = floor(fy), b = fy - y0.
+ *   2. Taps j = 0, 1 (outer), i = 0, 1 (inner): q = (x0 + i, y0 + j) with weight wt = (i ? a : 1.0 - a) * (j ? b : 1.0 - b).
+ *      e_q = float(c'_q / (albedo'_q + eps)) per channel with DEMODULATE, otherwise e_q = c'_q.  A tap is USABLE iff q is inside
+ *      the low image, wt > 0, and all three channels of e_q are finite.
+ *   3. The guide weight g of a usable tap.  hits_p == 0 and hits'_q == 0: g = 1.  Exactly one of them 0: g = 0.  Otherwise: with
+ *      OBJECT_EDGES and object'_q != object_p, g = 0; otherwise d = dot(n_p, n'_q), d = (d > 0) ? d : 0, wn = d squared k times,
+ *      D = sigma_depth * z_p, Zn = D*D, dz = z'_q - z_p, Zd = Zn + dz*dz, if Zd == 0: Zn = Zd = 1, g = (wn * Zn) / Zd.
+ *      om = wt * g.  The tap is ACCEPTED iff om > 0 && om < +inf (a NaN guide therefore rejects): W += om, then A += om * e_q per
+ *      channel, both from 0.  A tap that is not accepted is SKIPPED, not added as zero.
+ *   4. The blend.  W > 0: e = float(A / W) per channel and conf = float(W / U), where U is the sum of wt over the usable taps,
+ *      added in tap order from 0.  Otherwise the FALLBACK, plain bilinear over the usable taps: e = float(A2 / U) with A2 += wt *
+ *      e_q (tap order, from 0), and conf = 0.  No usable tap: e = 0 per channel and conf = -1.
+ *   5. out = float(e * (albedo_p + eps)) per channel with DEMODULATE, otherwise e.  out8 = the render epilogue's tonemap of the
+ *      widened out.
+ * The contract is total: any buffer contents have a defined result.  conf marks where the low frame held no matching surface
+ * (features and silhouettes finer than a low pixel): 1 where every usable tap matched fully, 0 where none did and the result is
+ * plain bilinear, -1 where the low frame had nothing to give.  A caller can resample exactly those pixels (rt_hip_trace_rays with
+ * RT_HIP_RAYS_CAMERA_UV); that fill is not part of this call.
+ *   - rt_hip_upsample_defaults: DEMODULATE, k = 3 (the denoiser's), sigma_depth = 0.05 (DESIGN, "`pt_upsample`").
+ *   - rt_hip_upsample: asynchronous on `stream`, on the device that holds d_low_rgb.  d_out_rgb is required, d_out_rgb8 and
+ *     d_out_conf (1 float per pixel) may be NULL.  No output may overlap an input or another output (RT_HIP_EINVAL).  Arguments are
+ *     checked before the device is looked for: RT_HIP_EINVAL, then RT_HIP_ENODEV.  A call takes no pool, workspace or status word.
+ *   - rt_hip_upsample_image: the same from host arrays, synchronous, with its own device buffers, on logical device `device` of
+ *     rt_hip_render_image's device map (the HIP device itself without a map). */
+typedef struct
+{
+  uint32_t flags;             /* RT_HIP_UPSAMPLE_* */
+  uint32_t normal_power_log2; /* k, 0 .. 10: the normal weight is max(0, n_p.n'_q)^(2^k) */
+  double sigma_depth;         /* > 0, finite: the depth weight's width, relative to z_p */
+} RtHipUpsampleParams;
+enum
+{
+  RT_HIP_UPSAMPLE_DEMODULATE = 1u,   /* interpolate c' / (albedo' + eps), multiply the full-size albedo back after */
+  RT_HIP_UPSAMPLE_OBJECT_EDGES = 2u, /* never take a tap of another object id */
+};
+void rt_hip_upsample_defaults(RtHipUpsampleParams *params);
+int rt_hip_upsample(const float *d_low_rgb, const RtHipAov *d_low_aov, int32_t low_width, int32_t low_height, const RtHipAov *d_aov,
+                    int32_t width, int32_t height, const RtHipUpsampleParams *params, float *d_out_rgb, uint8_t *d_out_rgb8,
+                    float *d_out_conf, void *stream);
+int rt_hip_upsample_image(const float *h_low_rgb, const RtHipAov *h_low_aov, int32_t low_width, int32_t low_height,
+                          const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipUpsampleParams *params, int device,
+                          float *h_out_rgb, uint8_t *h_out_rgb8, float *h_out_conf);
+
 /* Scatter a compact tile buffer into row-major images (either output may be
  * NULL together with its input). */
 int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t width, int32_t height,

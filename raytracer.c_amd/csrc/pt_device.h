@@ -421,6 +421,23 @@ struct PtReproject
   double max_history, depth_tol, normal_min;
 };
 
+/* One guided upsampling (rt_hip.h, rt_hip_upsample; pt_upsample in pt_kernel.hip): the low frame's row-major wl x hl images
+ * (colour, normal, depth, hits; albedo with demodulate, object with object_edges), the guides of the w x h frame (the same fields
+ * without a colour), and the outputs -- out_rgb always, the bytes and the confidence where wanted. */
+struct PtUpsample
+{
+  const float *low_rgb, *low_albedo, *low_normal, *low_depth;
+  const uint32_t *low_hits, *low_object;
+  const float *albedo, *normal, *depth; /* albedo: read with demodulate only */
+  const uint32_t *hits, *object;        /* object: read with object_edges only */
+  float *out_rgb;
+  uint8_t *out_rgb8; /* may be null */
+  float *out_conf;   /* may be null */
+  int32_t low_width, low_height, width, height;
+  uint32_t demodulate, object_edges, normal_power_log2;
+  double sigma_depth;
+};
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 /* host-side launchers, defined next to the kernels in pt_kernel.hip */
@@ -523,6 +540,8 @@ unsigned long long pt_trace_kernel_launches(int which);
 hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma_color, hipStream_t stream);
 /* temporal reprojection: one launch, a 16 x 16 block of pixels per workgroup, on `stream` */
 hipError_t pt_launch_reproject(const PtReproject &args, hipStream_t stream);
+/* guided upsampling: one launch, a 16 x 16 block of the high frame's pixels per workgroup, on `stream` */
+hipError_t pt_launch_upsample(const PtUpsample &args, hipStream_t stream);
 hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,
                             uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *image_rgb,
                             uint8_t *image_rgb8, hipStream_t stream);

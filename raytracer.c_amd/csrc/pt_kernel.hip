@@ -1645,6 +1645,120 @@ extern "C" __global__ __launch_bounds__(256) void pt_reproject(const PtReproject
   reproject_store(R, p, ox, oy, oz, (float)Nn, mx, my);
 }
 
+/* ---- guided upsampling (rt_hip_upsample): a full-size frame from a low-resolution render -----------------------------------
+ * rt_hip.h states the arithmetic; this is it, operation for operation, in fp64 (-ffp-contract=off; the library's IEEE division).
+ * A lane is a pixel of the HIGH frame, a workgroup a 16 x 16 block as pt_reproject's, no LDS.  The pixel's place in the low frame
+ * follows from get_camera_ray's (x + r) / (w - 1) mapping alone; the four bilinear taps there are weighted by how well their
+ * first-hit buffers match the pixel's own full-resolution ones.  The taps are unrolled and the same for every lane: an
+ * out-of-image tap loads a clamped address under a false predicate, and every skip is a predicate on the sums, not an added zero.
+ * The plain bilinear sums of the fallback ride along (two more fp64 multiply-adds per channel and tap: the kernel is bound by its
+ * loads).  The flags, the bytes and the confidence are wave-uniform branches on kernel arguments. */
+extern "C" __global__ __launch_bounds__(256) void pt_upsample(const PtUpsample U)
+{
+  const uint32_t bx = ((uint32_t)U.width + 15u) / 16u;
+  const int32_t x = (int32_t)((blockIdx.x % bx) * 16u + (threadIdx.x & 15u));
+  const int32_t y = (int32_t)((blockIdx.x / bx) * 16u + (threadIdx.x >> 4));
+  if (x >= U.width || y >= U.height)
+    return; /* no barrier follows */
+  const size_t p = (size_t)y * (size_t)U.width + (size_t)x;
+  constexpr double eps = 1.0 / 1024.0;
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);
+  const bool demod = U.demodulate != 0u, edges = U.object_edges != 0u;
+  /* 1. the place in the low frame: -0.5 < fx < 1.5 wl, so floor(fx) is in [-1, 1.5 * 2^20] -- the conversions are in range */
+  const double fx = (((double)x + 0.5) * ((double)U.low_width - 1.0)) / ((double)U.width - 1.0) - 0.5;
+  const double fy = (((double)y + 0.5) * ((double)U.low_height - 1.0)) / ((double)U.height - 1.0) - 0.5;
+  const double x0d = floor(fx), y0d = floor(fy);
+  const double a = fx - x0d, b = fy - y0d;
+  const int32_t x0 = (int32_t)x0d, y0 = (int32_t)y0d;
+  const double npx = U.normal[3 * p + 0], npy = U.normal[3 * p + 1], npz = U.normal[3 * p + 2];
+  const double zp = (double)U.depth[p];
+  const bool bg_p = U.hits[p] == 0u;
+  const uint32_t op = edges ? U.object[p] : 0u;
+  const double Dp = U.sigma_depth * zp;
+  const double Zn_p = Dp * Dp;
+  double W = 0, Ax = 0, Ay = 0, Az = 0; /* the guided sums */
+  double Us = 0, Bx = 0, By = 0, Bz = 0; /* the plain bilinear sums over the usable taps */
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < 2; j++)
+  {
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+    {
+      /* 2. the tap, its weight and its (demodulated) colour */
+      const int32_t qx = x0 + i, qy = y0 + j;
+      const bool inside = qx >= 0 && qx < U.low_width && qy >= 0 && qy < U.low_height;
+      const int32_t cx = qx < 0 ? 0 : (qx >= U.low_width ? U.low_width - 1 : qx), cy = qy < 0 ? 0 : (qy >= U.low_height ? U.low_height - 1 : qy);
+      const size_t q = (size_t)cy * (size_t)U.low_width + (size_t)cx;
+      const double wt = (i ? a : 1.0 - a) * (j ? b : 1.0 - b);
+      float ex = U.low_rgb[3 * q + 0], ey = U.low_rgb[3 * q + 1], ez = U.low_rgb[3 * q + 2];
+      if (demod)
+      {
+        ex = (float)((double)ex / ((double)U.low_albedo[3 * q + 0] + eps));
+        ey = (float)((double)ey / ((double)U.low_albedo[3 * q + 1] + eps));
+        ez = (float)((double)ez / ((double)U.low_albedo[3 * q + 2] + eps));
+      }
+      const bool usable = inside && wt > 0 && isfinite(ex) && isfinite(ey) && isfinite(ez);
+      /* 3. the guide weight: the surface terms first, then what overrides them */
+      const bool bg_q = U.low_hits[q] == 0u;
+      double d = (npx * (double)U.low_normal[3 * q + 0] + npy * (double)U.low_normal[3 * q + 1]) + npz * (double)U.low_normal[3 * q + 2];
+      d = (d > 0) ? d : 0.0;
+      double wn = d;
+      for (uint32_t k = 0; k < U.normal_power_log2; k++)
+        wn = wn * wn;
+      double Zn = Zn_p;
+      const double dz = (double)U.low_depth[q] - zp;
+      double Zd = Zn + dz * dz;
+      if (Zd == 0)
+        Zn = Zd = 1.0;
+      double g = (wn * Zn) / Zd;
+      if (edges)
+        g = U.low_object[q] != op ? 0.0 : g;
+      g = bg_p != bg_q ? 0.0 : g;
+      g = bg_p && bg_q ? 1.0 : g;
+      const double om = wt * g;
+      const bool take = usable && om > 0 && om < inf;
+      any = any || usable;
+      Us = usable ? Us + wt : Us;
+      Bx = usable ? Bx + wt * (double)ex : Bx;
+      By = usable ? By + wt * (double)ey : By;
+      Bz = usable ? Bz + wt * (double)ez : Bz;
+      W = take ? W + om : W;
+      Ax = take ? Ax + om * (double)ex : Ax;
+      Ay = take ? Ay + om * (double)ey : Ay;
+      Az = take ? Az + om * (double)ez : Az;
+    }
+  }
+  /* 4. the blend: guided where a tap matched, plain bilinear where none did, nothing where the low frame had nothing */
+  const bool guided = W > 0;
+  const double den = guided ? W : Us;
+  float ox = (float)((guided ? Ax : Bx) / den), oy = (float)((guided ? Ay : By) / den), oz = (float)((guided ? Az : Bz) / den);
+  float conf = guided ? (float)(W / Us) : 0.f;
+  if (!guided && !any)
+  {
+    ox = oy = oz = 0.f;
+    conf = -1.f;
+  }
+  /* 5. the full-resolution albedo back, and the bytes */
+  if (demod)
+  {
+    ox = (float)((double)ox * ((double)U.albedo[3 * p + 0] + eps));
+    oy = (float)((double)oy * ((double)U.albedo[3 * p + 1] + eps));
+    oz = (float)((double)oz * ((double)U.albedo[3 * p + 2] + eps));
+  }
+  U.out_rgb[3 * p + 0] = ox;
+  U.out_rgb[3 * p + 1] = oy;
+  U.out_rgb[3 * p + 2] = oz;
+  if (U.out_conf)
+    U.out_conf[p] = conf;
+  if (U.out_rgb8)
+  {
+    U.out_rgb8[3 * p + 0] = tonemap((double)ox);
+    U.out_rgb8[3 * p + 1] = tonemap((double)oy);
+    U.out_rgb8[3 * p + 2] = tonemap((double)oz);
+  }
+}
+
 /* ---- launch wrappers (host side), declared in pt_device.h ---------------------- */
 
 size_t pt_render_lds_bytes(const PtSceneView &sc)
@@ -2233,5 +2347,13 @@ hipError_t pt_launch_reproject(const PtReproject &args, hipStream_t stream)
 {
   const uint32_t blocks_2d = (((uint32_t)args.width + 15u) / 16u) * (((uint32_t)args.height + 15u) / 16u);
   hipLaunchKernelGGL(pt_reproject, dim3(blocks_2d), dim3(256), 0, stream, args);
+  return hipGetLastError();
+}
+
+/* ---- the upsampling's launch (rt_hip_upsample) ------------------------------------------------------------------------------- */
+hipError_t pt_launch_upsample(const PtUpsample &args, hipStream_t stream)
+{
+  const uint32_t blocks_2d = (((uint32_t)args.width + 15u) / 16u) * (((uint32_t)args.height + 15u) / 16u);
+  hipLaunchKernelGGL(pt_upsample, dim3(blocks_2d), dim3(256), 0, stream, args);
   return hipGetLastError();
 }

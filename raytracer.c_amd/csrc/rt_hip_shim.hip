@@ -2413,6 +2413,159 @@ int reproject_image_impl(const float *h_rgb, const RtHipAov *h_aov, const RtHipC
   return RT_HIP_OK;
 }
 
+/* ---- guided upsampling (rt_hip.h, rt_hip_upsample*) ---------------------------------------------------------------------------
+ * One launch of pt_upsample (pt_kernel.hip), no workspace.  The arguments that need no device are checked first. */
+int check_upsample(const float *low_rgb, const RtHipAov *low_aov, int32_t low_width, int32_t low_height, const RtHipAov *aov,
+                   int32_t width, int32_t height, const RtHipUpsampleParams *p, const float *out_rgb, const uint8_t *out_rgb8,
+                   const float *out_conf)
+{
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is NULL");
+  if (!reproject_size_ok(width, height) || !reproject_size_ok(low_width, low_height))
+    return fail(RT_HIP_EINVAL, "the widths and heights must be in [2, 2^20] with fewer than 2^32 pixels per frame");
+  if (p->flags & ~(uint32_t)(RT_HIP_UPSAMPLE_DEMODULATE | RT_HIP_UPSAMPLE_OBJECT_EDGES))
+    return fail(RT_HIP_EINVAL, "unknown upsample flags 0x%x", p->flags);
+  if (p->normal_power_log2 > 10u)
+    return fail(RT_HIP_EINVAL, "normal_power_log2 must be 0 .. 10");
+  if (!(std::isfinite(p->sigma_depth) && p->sigma_depth > 0.0))
+    return fail(RT_HIP_EINVAL, "sigma_depth must be finite and > 0");
+  if (!low_rgb || !low_aov || !aov)
+    return fail(RT_HIP_EINVAL, "the low frame's colour and the buffers of both frames are required");
+  const bool demod = (p->flags & RT_HIP_UPSAMPLE_DEMODULATE) != 0u, edges = (p->flags & RT_HIP_UPSAMPLE_OBJECT_EDGES) != 0u;
+  for (const RtHipAov *a : {low_aov, aov})
+  {
+    if (!a->normal || !a->depth || !a->hits)
+      return fail(RT_HIP_EINVAL, "the normal, depth and hits buffers of both frames are required");
+    if (demod && !a->albedo)
+      return fail(RT_HIP_EINVAL, "RT_HIP_UPSAMPLE_DEMODULATE needs the albedo buffers of both frames");
+    if (edges && !a->object)
+      return fail(RT_HIP_EINVAL, "RT_HIP_UPSAMPLE_OBJECT_EDGES needs the object buffers of both frames");
+  }
+  if (!out_rgb)
+    return fail(RT_HIP_EINVAL, "out_rgb is required");
+  /* a lane writes its pixel while other lanes still read the low frame: no output may overlap what the call reads or another output */
+  const size_t n = (size_t)width * (size_t)height, nl = (size_t)low_width * (size_t)low_height;
+  const std::pair<const void *, size_t> outs[3] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_conf, 4u * n}};
+  const std::pair<const void *, size_t> ins[11] = {{low_rgb, 12u * nl},
+                                                   {demod ? low_aov->albedo : nullptr, 12u * nl},
+                                                   {low_aov->normal, 12u * nl},
+                                                   {low_aov->depth, 4u * nl},
+                                                   {low_aov->hits, 4u * nl},
+                                                   {edges ? low_aov->object : nullptr, 4u * nl},
+                                                   {demod ? aov->albedo : nullptr, 12u * n},
+                                                   {aov->normal, 12u * n},
+                                                   {aov->depth, 4u * n},
+                                                   {aov->hits, 4u * n},
+                                                   {edges ? aov->object : nullptr, 4u * n}};
+  for (int o = 0; o < 3; o++)
+  {
+    for (const auto &in : ins)
+      if (ranges_overlap(outs[o].first, outs[o].second, in.first, in.second))
+        return fail(RT_HIP_EINVAL, "an output overlaps an input");
+    for (int q = o + 1; q < 3; q++)
+      if (ranges_overlap(outs[o].first, outs[o].second, outs[q].first, outs[q].second))
+        return fail(RT_HIP_EINVAL, "two outputs overlap");
+  }
+  return RT_HIP_OK;
+}
+
+/* the launch of a checked call, on the current device */
+int upsample_launch(const float *low_rgb, const RtHipAov *low_aov, int32_t low_width, int32_t low_height, const RtHipAov *aov,
+                    int32_t width, int32_t height, const RtHipUpsampleParams *p, float *out_rgb, uint8_t *out_rgb8, float *out_conf,
+                    hipStream_t stream)
+{
+  PtUpsample U = {};
+  U.demodulate = (p->flags & RT_HIP_UPSAMPLE_DEMODULATE) ? 1u : 0u;
+  U.object_edges = (p->flags & RT_HIP_UPSAMPLE_OBJECT_EDGES) ? 1u : 0u;
+  U.low_rgb = low_rgb;
+  U.low_albedo = U.demodulate ? low_aov->albedo : nullptr;
+  U.low_normal = low_aov->normal;
+  U.low_depth = low_aov->depth;
+  U.low_hits = low_aov->hits;
+  U.low_object = U.object_edges ? low_aov->object : nullptr;
+  U.albedo = U.demodulate ? aov->albedo : nullptr;
+  U.normal = aov->normal;
+  U.depth = aov->depth;
+  U.hits = aov->hits;
+  U.object = U.object_edges ? aov->object : nullptr;
+  U.out_rgb = out_rgb;
+  U.out_rgb8 = out_rgb8;
+  U.out_conf = out_conf;
+  U.low_width = low_width;
+  U.low_height = low_height;
+  U.width = width;
+  U.height = height;
+  U.normal_power_log2 = p->normal_power_log2;
+  U.sigma_depth = p->sigma_depth;
+  const hipError_t e = pt_launch_upsample(U, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "pt_upsample launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int upsample_image_impl(const float *h_low_rgb, const RtHipAov *h_low_aov, int32_t low_width, int32_t low_height, const RtHipAov *h_aov,
+                        int32_t width, int32_t height, const RtHipUpsampleParams *params, int device, float *h_out_rgb,
+                        uint8_t *h_out_rgb8, float *h_out_conf)
+{
+  int rc = check_upsample(h_low_rgb, h_low_aov, low_width, low_height, h_aov, width, height, params, h_out_rgb, h_out_rgb8, h_out_conf);
+  if (rc)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", phys, hipGetErrorString(scope.status));
+  const bool demod = (params->flags & RT_HIP_UPSAMPLE_DEMODULATE) != 0u, edges = (params->flags & RT_HIP_UPSAMPLE_OBJECT_EDGES) != 0u;
+  const size_t count[2] = {(size_t)low_width * (size_t)low_height, (size_t)width * (size_t)height};
+  /* one allocation: per frame albedo, normal, depth, hits, object; then the low colour, the result, the confidence, the bytes */
+  size_t total = 0;
+  for (size_t n : count)
+    total += 2u * align256(12u * n) + 3u * align256(4u * n);
+  total += align256(12u * count[0]) + align256(12u * count[1]) + align256(4u * count[1]) + align256(3u * count[1]);
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc(total));
+  size_t at = 0;
+  auto part = [&](size_t bytes) { /* the next `bytes` of the allocation */
+    at += align256(bytes);
+    return at - align256(bytes);
+  };
+  RtHipAov d_aov[2] = {};
+  const RtHipAov *src[2] = {h_low_aov, h_aov};
+  for (int f = 0; f < 2; f++)
+  {
+    const size_t n = count[f];
+    d_aov[f].albedo = buf.at<float>(part(12u * n));
+    d_aov[f].normal = buf.at<float>(part(12u * n));
+    d_aov[f].depth = buf.at<float>(part(4u * n));
+    d_aov[f].hits = buf.at<uint32_t>(part(4u * n));
+    d_aov[f].object = buf.at<uint32_t>(part(4u * n));
+    if (demod)
+      HIP_TRY(hipMemcpy(d_aov[f].albedo, src[f]->albedo, 12u * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov[f].normal, src[f]->normal, 12u * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov[f].depth, src[f]->depth, 4u * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov[f].hits, src[f]->hits, 4u * n, hipMemcpyHostToDevice));
+    if (edges)
+      HIP_TRY(hipMemcpy(d_aov[f].object, src[f]->object, 4u * n, hipMemcpyHostToDevice));
+  }
+  float *d_low_rgb = buf.at<float>(part(12u * count[0]));
+  float *d_out = buf.at<float>(part(12u * count[1]));
+  float *d_conf = buf.at<float>(part(4u * count[1]));
+  uint8_t *d_rgb8 = buf.at<uint8_t>(part(3u * count[1]));
+  HIP_TRY(hipMemcpy(d_low_rgb, h_low_rgb, 12u * count[0], hipMemcpyHostToDevice));
+  rc = upsample_launch(d_low_rgb, &d_aov[0], low_width, low_height, &d_aov[1], width, height, params, d_out, h_out_rgb8 ? d_rgb8 : nullptr,
+                       h_out_conf ? d_conf : nullptr, nullptr);
+  if (rc)
+    return rc;
+  HIP_TRY(hipMemcpy(h_out_rgb, d_out, 12u * count[1], hipMemcpyDeviceToHost));
+  if (h_out_rgb8)
+    HIP_TRY(hipMemcpy(h_out_rgb8, d_rgb8, 3u * count[1], hipMemcpyDeviceToHost));
+  if (h_out_conf)
+    HIP_TRY(hipMemcpy(h_out_conf, d_conf, 4u * count[1], hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
 /* ---- ray queries (rt_hip.h, rt_hip_query_*) ---------------------------------------------------------------------------------
  * A query's launch takes the scene- and near_R-dependent fields of launch_prepare with origin_radius in the camera distance's
  * place, and acquire_tables' filter, hierarchy and fp32 triangle table for that near_R -- what intersect() reads -- and nothing
@@ -3790,6 +3943,50 @@ int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHi
   return guarded("rt_hip_reproject_image", [&] {
     return reproject_image_impl(h_rgb, h_aov, camera, h_hist_rgb, h_hist_len, h_hist_aov, hist_camera, width, height, params, device,
                                 h_out_rgb, h_out_rgb8, h_out_len, h_out_motion);
+  });
+}
+
+/* k: the denoiser's; sigma_depth: the reprojection's depth tolerance (DESIGN, "`pt_upsample`") */
+void rt_hip_upsample_defaults(RtHipUpsampleParams *params)
+{
+  if (!params)
+    return;
+  *params = RtHipUpsampleParams{};
+  params->flags = RT_HIP_UPSAMPLE_DEMODULATE;
+  params->normal_power_log2 = 3u;
+  params->sigma_depth = 0.05;
+}
+
+int rt_hip_upsample(const float *d_low_rgb, const RtHipAov *d_low_aov, int32_t low_width, int32_t low_height, const RtHipAov *d_aov,
+                    int32_t width, int32_t height, const RtHipUpsampleParams *params, float *d_out_rgb, uint8_t *d_out_rgb8,
+                    float *d_out_conf, void *stream)
+{
+  int rc = check_upsample(d_low_rgb, d_low_aov, low_width, low_height, d_aov, width, height, params, d_out_rgb, d_out_rgb8, d_out_conf);
+  if (rc)
+    return rc;
+  if (usable_devices() < 1)
+    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
+  /* the device that holds the low colour: a host pointer here would fault the kernel, so it is refused */
+  hipPointerAttribute_t attr = {};
+  if (hipPointerGetAttributes(&attr, d_low_rgb) != hipSuccess || attr.type != hipMemoryTypeDevice)
+  {
+    (void)hipGetLastError();
+    return fail(RT_HIP_EINVAL, "d_low_rgb is not device memory");
+  }
+  DeviceScope scope(attr.device);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  return upsample_launch(d_low_rgb, d_low_aov, low_width, low_height, d_aov, width, height, params, d_out_rgb, d_out_rgb8, d_out_conf,
+                         static_cast<hipStream_t>(stream));
+}
+
+int rt_hip_upsample_image(const float *h_low_rgb, const RtHipAov *h_low_aov, int32_t low_width, int32_t low_height,
+                          const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipUpsampleParams *params, int device,
+                          float *h_out_rgb, uint8_t *h_out_rgb8, float *h_out_conf)
+{
+  return guarded("rt_hip_upsample_image", [&] {
+    return upsample_image_impl(h_low_rgb, h_low_aov, low_width, low_height, h_aov, width, height, params, device, h_out_rgb, h_out_rgb8,
+                               h_out_conf);
   });
 }
 

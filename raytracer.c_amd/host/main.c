@@ -22,6 +22,10 @@
  *   -q <x,y>     query instead of rendering: what the ray through the centre of pixel (x, y) of the chosen scene and size hits
  *                (rt_hip_query_rays_host with u = (x + 0.5) / (w - 1), v = (y + 0.5) / (h - 1)): status, object id,
  *                primitive, t, point and normal, one line each.  Nothing is rendered or written.
+ *   -u <f>       preview by guided upsampling, integer f >= 2 (upsample_frame, rt_hip_upsample's defaults, one GPU): the frame is
+ *                rendered at ceil(w / f) x ceil(h / f) under the full size's camera (with -n: and denoised there), the first-hit
+ *                buffers are rendered at both sizes, and the low frame is brought to w x h under the full-size buffers.  The PNG
+ *                goes to -o, the low frame to <name>.low.png.  Not with -g > 1, -e, -q, -p or -a.
  * Timing is wall-clock (the reference's clock()/integer division, main.c:427-433,
  * reports summed CPU time truncated to seconds -- deliberately not reproduced).
  * SIGINT: the reference's handler writes and frees the live framebuffer from
@@ -110,6 +114,7 @@ typedef struct
   int denoise;     /* -n: iterations + 1; 0: not given */
   int adaptive;    /* -e given */
   double threshold; /* -e: the error at or below which a tile stops */
+  int upsample;     /* -u: the factor; 0: not given */
   int query;        /* -q given */
   double qx, qy;    /* -q: the pixel */
   uint64_t seed;
@@ -124,7 +129,8 @@ static void usage(const char *prog)
           "          [-a <prefix of the albedo / normal / depth .pfm files>]\n"
           "          [-n <denoise iterations 0..10: -o denoised, <name>.noisy.png as rendered>]\n"
           "          [-e <adaptive sampling: tiles whose error estimate is <= this stop early; -s is the budget; one GPU>]\n"
-          "          [-q <x,y: print what the ray through the centre of that pixel hits; nothing is rendered>]\n",
+          "          [-q <x,y: print what the ray through the centre of that pixel hits; nothing is rendered>]\n"
+          "          [-u <factor >= 2: render at 1/factor of the size, upsample under full-size first-hit buffers; <name>.low.png>]\n",
           prog);
 }
 
@@ -171,6 +177,11 @@ static int parse_args(int argc, char **argv, Args *a)
       a->query = 1;
       break;
     }
+    case 'u':
+      a->upsample = atoi(val);
+      if (a->upsample < 2 || val[0] < '0' || val[0] > '9')
+        return -1;
+      break;
     case 'p':
       a->pass = atoi(val);
       if (a->pass < 1)
@@ -234,6 +245,90 @@ static int query_pixel(const Args *a, const RtSceneInfo *info, const Object *sce
   return EXIT_SUCCESS;
 }
 
+/* -u: the frame at 1 / f of the size, its first-hit buffers at both sizes, the guided upsampling */
+static int upsample_preview(const Args *a, const RtSceneInfo *info, Object *scene, MeshObject *meshes, Camera *camera)
+{
+  const int w = a->options.width, h = a->options.height, f = a->upsample;
+  const int wl = (w + f - 1) / f, hl = (h + f - 1) / f;
+  if (wl < 2 || hl < 2)
+  {
+    fprintf(stderr, "-u %d: the low frame would be %d x %d; both sides must be at least 2\n", f, wl, hl);
+    return EXIT_FAILURE;
+  }
+  const size_t n = (size_t)w * (size_t)h, nl = (size_t)wl * (size_t)hl;
+  char low_path[4096];
+  const size_t len = strlen(a->options.result);
+  const size_t stem = len >= 4 && strcmp(a->options.result + len - 4, ".png") == 0 ? len - 4 : len;
+  /* one block of floats: per frame albedo, normal (3), depth, hits (1); the low colour twice (as rendered, denoised) */
+  float *block = (float *)malloc((8 * (n + nl) + 6 * nl) * sizeof(float));
+  uint8_t *fb = (uint8_t *)calloc(3 * (n + nl), 1);
+  if (!block || !fb || snprintf(low_path, sizeof low_path, "%.*s.low.png", (int)stem, a->options.result) >= (int)sizeof low_path)
+  {
+    fprintf(stderr, "could not allocate the frames or name the low PNG (-u)\n");
+    free(block);
+    free(fb);
+    return EXIT_FAILURE;
+  }
+  float *at = block;
+  RtAovImage aov[2]; /* low, full */
+  const size_t count[2] = {nl, n};
+  for (int k = 0; k < 2; k++)
+  {
+    aov[k].albedo = at;
+    aov[k].normal = at + 3 * count[k];
+    aov[k].depth = at + 6 * count[k];
+    aov[k].hits = (uint32_t *)(at + 7 * count[k]);
+    aov[k].object_id = NULL;
+    at += 8 * count[k];
+  }
+  float *linear_low = at, *denoised_low = at + 3 * nl;
+  uint8_t *fb_low = fb + 3 * n;
+  Options low = a->options, full = a->options;
+  low.width = wl;
+  low.height = hl;
+  int status = EXIT_SUCCESS;
+  const double tic = now_seconds();
+  render_ex(fb_low, linear_low, scene, info->n_objects, meshes, info->n_meshes, camera, &low);
+  const double kernel_s = rt_last_render_seconds();
+  const float *colour = linear_low;
+  if (rt_last_render_cancelled())
+  {
+    fprintf(stderr, "not upsampled: the low frame is incomplete\n");
+    status = EXIT_FAILURE;
+  }
+  else if (render_aov(&aov[0], scene, info->n_objects, meshes, info->n_meshes, camera, &low) < 0 ||
+           render_aov(&aov[1], scene, info->n_objects, meshes, info->n_meshes, camera, &full) < 0)
+    status = EXIT_FAILURE;
+  if (status == EXIT_SUCCESS && a->denoise)
+  {
+    RtHipDenoiseParams dp;
+    rt_hip_denoise_defaults(&dp);
+    dp.iterations = a->denoise - 1;
+    if (denoise_frame(fb_low, denoised_low, linear_low, &aov[0], wl, hl, &dp) != 0)
+      status = EXIT_FAILURE;
+    colour = denoised_low;
+  }
+  if (status == EXIT_SUCCESS && upsample_frame(fb, NULL, NULL, colour, &aov[0], wl, hl, &aov[1], w, h, NULL) != 0)
+    status = EXIT_FAILURE;
+  if (status == EXIT_SUCCESS)
+  {
+    printf("%d x %d (%d) pixels from %d x %d (-u %d%s)\n", w, h, w * h, wl, hl, f, a->denoise ? ", denoised at the low size" : "");
+    printf("cast %lld rays\n", ray_count);
+    printf("checked %lld possible intersections\n", intersection_test_count);
+    printf("rendering and upsampling took %f seconds (GPU kernels of the low frame %f s)\n", now_seconds() - tic, kernel_s);
+    printf("writing result to '%s' and the low frame to '%s'...\n", a->options.result, low_path);
+    if (stbi_write_png(a->options.result, w, h, 3, fb, w * 3) == 0 || stbi_write_png(low_path, wl, hl, 3, fb_low, wl * 3) == 0)
+      status = EXIT_FAILURE;
+    else
+      printf("done.\n");
+  }
+  else
+    fprintf(stderr, "could not make the preview (-u %d)\n", f);
+  free(block);
+  free(fb);
+  return status;
+}
+
 int main(int argc, char **argv)
 {
   Args a;
@@ -259,6 +354,11 @@ int main(int argc, char **argv)
       (a.pass > 0 && (a.pass > a.options.samples || a.gpus > 1)) || (a.adaptive && (a.pass > 0 || a.gpus > 1)))
   {
     usage(argv[0]);
+    return EXIT_FAILURE;
+  }
+  if (a.upsample && (a.gpus > 1 || a.adaptive || a.query || a.pass > 0 || a.aov))
+  {
+    fprintf(stderr, "-u renders a preview on one GPU: it does not go with -g > 1, -e, -q, -p or -a\n");
     return EXIT_FAILURE;
   }
   printf("seed = %llu\n", (unsigned long long)a.seed);
@@ -288,6 +388,16 @@ int main(int argc, char **argv)
   rt_set_seed(a.seed);
   rt_set_devices(a.gpus);
   rt_set_integrator(a.integrator);
+
+  if (a.upsample)
+  {
+    const int rc = upsample_preview(&a, &info, scene, meshes, &camera);
+    rt_scene_free_meshes(meshes, info.n_meshes);
+    free(meshes);
+    free(scene);
+    free(framebuffer);
+    return rc;
+  }
 
   /* the process's phase clock (bench.py's cli_host entry reads the `phases:` line): the HIP runtime comes up at the first
    * device query; render_ex's own split is the shim's (rt_hip_last_image_phases) */

@@ -463,6 +463,33 @@ int reproject_frame(uint8_t *framebuffer, float *linear_out, float *len_out, flo
   return rc;
 }
 
+int upsample_frame(uint8_t *framebuffer, float *linear_out, float *conf_out, const float *linear_low, const RtAovImage *aov_low,
+                   int low_width, int low_height, const RtAovImage *aov, int width, int height, const RtHipUpsampleParams *params)
+{
+  RtHipUpsampleParams defaults;
+  rt_hip_upsample_defaults(&defaults);
+  if (!aov_low || !aov)
+  {
+    fprintf(stderr, "upsample_frame: the feature buffers of both frames are required\n");
+    return RT_HIP_EINVAL;
+  }
+  const size_t n = width > 0 && height > 0 ? (size_t)width * (size_t)height : 0;
+  float *own = linear_out ? NULL : (float *)malloc((n ? n : 1) * 3 * sizeof(float)); /* the shim's out_rgb is required */
+  if (!linear_out && !own)
+  {
+    fprintf(stderr, "upsample_frame: could not allocate the linear frame\n");
+    return RT_HIP_ENOMEM;
+  }
+  const RtHipAov l = {aov_low->albedo, aov_low->normal, aov_low->depth, aov_low->object_id, aov_low->hits};
+  const RtHipAov h = {aov->albedo, aov->normal, aov->depth, aov->object_id, aov->hits};
+  const int rc = rt_hip_upsample_image(linear_low, &l, low_width, low_height, &h, width, height, params ? params : &defaults, 0,
+                                       linear_out ? linear_out : own, framebuffer, conf_out);
+  free(own);
+  if (rc)
+    fprintf(stderr, "upsample_frame: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+  return rc;
+}
+
 int intersect_rays(const Ray *rays, size_t n, const double *t_max, Object *objects, size_t n_objects, MeshObject *meshes,
                    size_t n_meshes, Hit *hits, uint8_t *status)
 {

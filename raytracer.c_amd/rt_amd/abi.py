@@ -95,6 +95,10 @@ class RtHipReprojectParams(C.Structure):  # rt_hip.h: temporal reprojection (rt_
     _fields_ = [("flags", C.c_uint32), ("max_history", C.c_double), ("depth_tol", C.c_double), ("normal_min", C.c_double)]
 
 
+class RtHipUpsampleParams(C.Structure):  # rt_hip.h: guided upsampling (rt_hip_upsample_defaults), 16 B
+    _fields_ = [("flags", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_depth", C.c_double)]
+
+
 class RtHipAdaptParams(C.Structure):  # rt_hip.h: adaptive sampling (rt_hip_adapt_defaults)
     _fields_ = [("min_samples", C.c_int32), ("dilate", C.c_uint32), ("threshold", C.c_double)]
 
@@ -134,6 +138,7 @@ RADIANCE_SHAPES = {"status": ("uint32", 1), "radiance": ("float64", 3), "samples
 ADAPT_CHECKPOINT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_uint32)  # on_checkpoint(user, samples done, live tiles)
 
 DENOISE_DEMODULATE, DENOISE_OBJECT_EDGES = 1, 2   # RT_HIP_DENOISE_*
+UPSAMPLE_DEMODULATE, UPSAMPLE_OBJECT_EDGES = 1, 2   # RT_HIP_UPSAMPLE_*
 
 AOV_FIELDS = ("albedo", "normal", "depth", "object", "hits")   # RtHipAov order
 AOV_CHANNELS = {"albedo": 3, "normal": 3, "depth": 1, "object": 1, "hits": 1}
@@ -247,6 +252,11 @@ SHIM_SYMBOLS = {
     "rt_hip_reproject_image": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(RtHipAov),
                                          C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(RtHipReprojectParams), C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_upsample_defaults": (None, [C.POINTER(RtHipUpsampleParams)]),
+    "rt_hip_upsample": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipAov), C.c_int32, C.c_int32,
+                                  C.POINTER(RtHipUpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_upsample_image": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipAov), C.c_int32, C.c_int32,
+                                        C.POINTER(RtHipUpsampleParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_render_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t,
                                       C.POINTER(Camera), C.POINTER(RtHipParams), C.c_int, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
@@ -288,6 +298,8 @@ HOST_SYMBOLS = {
     "reproject_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.POINTER(Camera),
                                   C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.POINTER(Camera), C.c_int, C.c_int,
                                   C.POINTER(RtHipReprojectParams)]),
+    "upsample_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtAovImage), C.c_int, C.c_int,
+                                 C.POINTER(RtAovImage), C.c_int, C.c_int, C.POINTER(RtHipUpsampleParams)]),
     "intersect_rays": (C.c_int, [C.POINTER(Ray), C.c_size_t, C.c_void_p, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
                                  C.POINTER(Hit), C.c_void_p]),
     "trace_rays": (C.c_int, [C.POINTER(Ray), C.c_size_t, C.c_int, C.POINTER(Object), C.c_size_t, C.POINTER(MeshObject), C.c_size_t,
@@ -366,6 +378,19 @@ def reproject_params(max_history=None, depth_tol=None, normal_min=None):
     for f, v in (("max_history", max_history), ("depth_tol", depth_tol), ("normal_min", normal_min)):
         if v is not None:
             setattr(p, f, v)
+    return p
+
+
+def upsample_params(sigma_depth=None, normal_power_log2=None, demodulate=None, object_edges=None):
+    """rt_hip_upsample_defaults() with the given fields replaced (None: the default)"""
+    p = RtHipUpsampleParams()
+    load_shim().rt_hip_upsample_defaults(C.byref(p))
+    for f, v in (("sigma_depth", sigma_depth), ("normal_power_log2", normal_power_log2)):
+        if v is not None:
+            setattr(p, f, v)
+    for bit, v in ((UPSAMPLE_DEMODULATE, demodulate), (UPSAMPLE_OBJECT_EDGES, object_edges)):
+        if v is not None:
+            p.flags = (p.flags | bit) if v else (p.flags & ~bit)
     return p
 
 

@@ -316,6 +316,11 @@ class GpuScene:
         before (rt_hip_reproject; params: abi.reproject_params' keywords)"""
         return Temporal(self, **params)
 
+    def preview(self, scale, **params):
+        """A Preview: frames of this scene rendered at ceil(width / scale) x ceil(height / scale) and brought to full size under
+        the full-resolution first-hit buffers (rt_hip_upsample; scale: an integer >= 2; params: abi.upsample_params' keywords)"""
+        return Preview(self, scale, **params)
+
     def render_adaptive(self, seed, samples, max_depth=None, integrator="path", **params):
         """An adaptive frame of at most `samples` per pixel on this GPU (Accumulation.run_adaptive; params: abi.adapt_params'
         keywords) -> (image f32 [H,W,3], image8 u8 [H,W,3], tile sample counts uint32 [tiles_y, tiles_x], stats dict, device
@@ -667,6 +672,127 @@ def reproject_image_host(rgb, aov, camera, hist=None, device=0, **params):
     _check(shim.rt_hip_reproject_image(rgb.ctypes.data, C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, w, h, C.byref(p), device,
                                        out["rgb"].ctypes.data, out["rgb8"].ctypes.data, out["len"].ctypes.data, out["motion"].ctypes.data),
            "rt_hip_reproject_image")
+    return out
+
+
+UPSAMPLE_AOV = ("albedo", "normal", "depth", "object", "hits")   # what rt_hip_upsample may read (albedo, object: by the flags)
+
+
+def _upsample_aov(aov, n, dev, p, what):
+    need = ["normal", "depth", "hits"] + (["albedo"] if p.flags & abi.UPSAMPLE_DEMODULATE else []) + \
+           (["object"] if p.flags & abi.UPSAMPLE_OBJECT_EDGES else [])
+    a = abi.RtHipAov()
+    for f in need:
+        if f not in aov:
+            raise ValueError(f"upsample(): {what} {f} buffer is needed")
+        t = aov[f]
+        if t.device != dev or not t.is_contiguous() or t.element_size() != 4 or t.numel() != n * abi.AOV_CHANNELS[f]:
+            raise ValueError(f"upsample(): {what} {f} must be a contiguous 32-bit tensor of width * height * {abi.AOV_CHANNELS[f]} "
+                             "values on the colour's device")
+        setattr(a, f, t.data_ptr())
+    return a
+
+
+def upsample(low_rgb, low_aov, wl, hl, aov, w, h, out=None, **params):
+    """rt_hip_upsample on torch device tensors, asynchronous on torch's current stream: low_rgb f32 of hl x wl x 3 values (row-major,
+    contiguous), low_aov and aov dicts of row-major buffers as GpuScene.untile_aov gives them at wl x hl and at w x h (normal,
+    depth, hits; albedo with demodulate, object with object_edges).  out: a dict of tensors to write into (rgb f32 [h,w,3], rgb8 u8
+    [h,w,3], conf f32 [h,w]; what is missing is allocated; rgb8 or conf given as None: not wanted, not computed), none of them a
+    buffer the call reads.  params: abi.upsample_params' keywords.  -> dict(rgb, and rgb8 and conf unless not wanted)"""
+    dev = low_rgb.device
+    shim = abi.load_shim()
+    p = abi.upsample_params(**params)
+    if low_rgb.dtype != torch.float32 or not low_rgb.is_contiguous() or low_rgb.numel() != wl * hl * 3:
+        raise ValueError("upsample(): low_rgb must be a contiguous float32 tensor of wl * hl * 3 values")
+    la, a = _upsample_aov(low_aov, wl * hl, dev, p, "the low frame's"), _upsample_aov(aov, w * h, dev, p, "the full frame's")
+    out = dict(out) if out else {}
+    shapes = dict(rgb=((h, w, 3), torch.float32), rgb8=((h, w, 3), torch.uint8), conf=((h, w), torch.float32))
+    for f, (shape, dtype) in shapes.items():
+        if f in ("rgb8", "conf") and f in out and out[f] is None:
+            del out[f]
+            continue
+        if f not in out:
+            out[f] = torch.empty(shape, dtype=dtype, device=dev)
+        t = out[f]
+        if t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != w * h * (shape[2] if len(shape) > 2 else 1):
+            raise ValueError(f"upsample(): out[{f!r}] must be a contiguous {dtype} tensor of shape {shape} on the colour's device")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_upsample(C.c_void_p(low_rgb.data_ptr()), C.byref(la), wl, hl, C.byref(a), w, h, C.byref(p),
+                                C.c_void_p(out["rgb"].data_ptr()), C.c_void_p(out["rgb8"].data_ptr()) if "rgb8" in out else None,
+                                C.c_void_p(out["conf"].data_ptr()) if "conf" in out else None, C.c_void_p(stream)), "rt_hip_upsample")
+    return out
+
+
+class Preview:
+    """Frames of one scene at a fraction of the pixels (GpuScene.preview): the colour is rendered -- and, if wanted, denoised -- at
+    ceil(width / scale) x ceil(height / scale) by a second GpuScene of that size under the FULL frame's camera (get_camera_ray's
+    (x + r) / (w - 1) ties the two pixel grids together), the first-hit buffers are rendered at both sizes, and rt_hip_upsample
+    brings the colour to full size under the full-resolution ones.  frame() runs on torch's current stream.  The scene must stay
+    open and unchanged; close() frees the low scene."""
+
+    def __init__(self, gs, scale, **params):
+        import dataclasses
+        if int(scale) != scale or scale < 2:
+            raise ValueError("preview(): scale must be an integer >= 2")
+        self.gs, self.scale, self.params = gs, int(scale), params
+        abi.upsample_params(**params)   # a bad keyword fails here
+        sc = gs.scene
+        self.low_width, self.low_height = -(-sc.width // self.scale), -(-sc.height // self.scale)
+        if self.low_width < 2 or self.low_height < 2:
+            raise ValueError(f"preview(): the low frame would be {self.low_width} x {self.low_height}; both sides must be at least 2")
+        # the same objects, meshes and camera bytes at another size: nothing is rebuilt (a room's walls follow the FULL aspect)
+        self.low = GpuScene(dataclasses.replace(sc, width=self.low_width, height=self.low_height), device=gs.device)
+
+    def close(self):
+        self.low.close()
+
+    def _denoised(self, rgb, aov, **denoise_params):
+        return denoise(rgb, aov, self.low_width, self.low_height, **denoise_params)
+
+    def frame(self, seed, samples, camera=None, denoise=False, **denoise_params):
+        """Render `samples` per pixel at the low size under `camera` (an abi.Camera; None: the scene's own), the first-hit buffers
+        of `samples` camera samples at both sizes, and upsample -> dict of device tensors: rgb f32 [H,W,3], rgb8 u8 [H,W,3], conf
+        f32 [H,W] (rt_hip.h: 1 .. 0 guided, 0 plain bilinear, -1 nothing usable), aov (the full-size buffers) and low (dict: rgb
+        -- denoised with denoise=True, by rt_hip_denoise under the low buffers with denoise_params, abi.denoise_params' keywords --,
+        noisy: the low frame as rendered, aov)"""
+        gs, lo = self.gs, self.low
+        w, h, wl, hl = gs.scene.width, gs.scene.height, self.low_width, self.low_height
+        total, total_low = n_tiles(w, h), n_tiles(wl, hl)
+        tiles, _, _ = lo.render_tiles(seed, 0, 1, total_low, samples=samples, chunks=lo.suggest_chunks(total_low, samples), camera=camera)
+        noisy, _ = lo.untile(tiles, None, 0, 1, total_low)
+        low_aov = lo.untile_aov(lo.render_aov(seed, samples, 0, 1, total_low, camera=camera, want=UPSAMPLE_AOV), 0, 1, total_low)
+        rgb = noisy
+        if denoise:
+            rgb, _ = self._denoised(noisy, low_aov, **denoise_params)
+        aov = gs.untile_aov(gs.render_aov(seed, samples, 0, 1, total, camera=camera, want=UPSAMPLE_AOV), 0, 1, total)
+        res = upsample(rgb, low_aov, wl, hl, aov, w, h, **self.params)
+        res.update(aov=aov, low=dict(rgb=rgb, noisy=noisy, aov=low_aov))
+        return res
+
+
+def upsample_image_host(low_rgb, low_aov, aov, device=0, **params):
+    """rt_hip_upsample_image(): the C hosts' entry point (host arrays, its own device buffers on logical device `device`,
+    synchronous).  low_rgb float32 [hl,wl,3], low_aov and aov dicts of numpy arrays as GpuScene.aov_image gives them at the two
+    sizes -> dict of numpy arrays: rgb, rgb8, conf"""
+    import numpy as np
+    shim = abi.load_shim()
+    p = abi.upsample_params(**params)
+    keep = []
+
+    def pack(bufs):
+        a = abi.RtHipAov()
+        for f in UPSAMPLE_AOV:
+            if f in bufs and bufs[f] is not None:
+                arr = np.ascontiguousarray(bufs[f], dtype=np.float32 if f in ("albedo", "normal", "depth") else np.uint32)
+                keep.append(arr)
+                setattr(a, f, arr.ctypes.data)
+        return a
+    low_rgb = np.ascontiguousarray(low_rgb, dtype=np.float32)
+    hl, wl = low_rgb.shape[:2]
+    h, w = np.asarray(aov["depth"]).shape
+    out = dict(rgb=np.zeros((h, w, 3), np.float32), rgb8=np.zeros((h, w, 3), np.uint8), conf=np.zeros((h, w), np.float32))
+    _check(shim.rt_hip_upsample_image(low_rgb.ctypes.data, C.byref(pack(low_aov)), wl, hl, C.byref(pack(aov)), w, h, C.byref(p), device,
+                                      out["rgb"].ctypes.data, out["rgb8"].ctypes.data, out["conf"].ctypes.data), "rt_hip_upsample_image")
     return out
 
 
