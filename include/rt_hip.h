@@ -675,6 +675,96 @@ int rt_hip_upsample_image(const float *h_low_rgb, const RtHipAov *h_low_aov, int
                           const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipUpsampleParams *params, int device,
                           float *h_out_rgb, uint8_t *h_out_rgb8, float *h_out_conf);
 
+/* ---- pixel refinement: resample only the pixels a mask selects -----------------------------------------------------------------
+ * The upsampling's conf, the reprojection's len and any other per-pixel map say where a frame is not trustworthy yet.  Three calls
+ * act on such a map on the device: SELECT the pixels, TRACE them with the samples render() itself would give them, BLEND the result
+ * into the frame.  Each has a total contract of its own and they share nothing but the index list.
+ *
+ * rt_hip_select_pixels: the ordered compaction of a map.  d_values: one float per pixel, row-major, w x h with 1 <= w, h <= 2^20 and
+ * n = w*h < 2^32.  Pixel p is SELECTED iff (lo <= v_p && v_p <= hi), negated under RT_HIP_SELECT_INVERT; lo and hi are doubles and
+ * may be +-inf, v_p is widened exactly, a comparison is false for NaN (a NaN value is selected under INVERT only), -0.0 equals 0.0,
+ * lo > hi selects nothing (everything under INVERT).  A NaN bound: RT_HIP_EINVAL.
+ *   d_indices  uint32[capacity]: the selected p = y*w + x in strictly ascending order, the first min(count, capacity) of them;
+ *              entries beyond that are left untouched.  capacity == 0 with d_indices == NULL only counts.
+ *   d_count    one uint32: the full count, also when it exceeds capacity.
+ * d_workspace: rt_hip_select_workspace_bytes(w, h) bytes (0 for a size out of range).  Asynchronous on `stream`, on the device that
+ * holds d_values; no pool, no status word.  Arguments are checked before the device is looked for: RT_HIP_EINVAL, then RT_HIP_ENODEV.
+ * Separate launches on the stream: per-workgroup counts (wave ballot + popcount, 256 pixels per workgroup), their exclusive scan
+ * (1,024 counts per workgroup and level, the levels looped on the host: three levels hold 2^30 counts), a scatter by ballot prefix.
+ * No workgroup waits on another inside a launch, so the result does not depend on scheduling.
+ *
+ * rt_hip_trace_pixels: render()'s own samples for a list of pixels.  The frame is params->width x height (2 <= w, h <= 2^20,
+ * w*h < 2^32: rt_hip_render_tiles' limits) under `camera` (a host pointer); d_pixels is uint32[n], 0 <= n < 2^32, n a host value,
+ * any order, duplicates allowed.  Entry i names pixel p = d_pixels[i], x = p % w, y = p / w, and is INVALID (status 2, zeros, as an
+ * invalid ray) iff p >= w*h.  Sample k (0 <= k < S = params->samples) of a valid entry is THE RENDER'S SAMPLE s = sample_first + k OF
+ * PIXEL p: the stream (seed, p, s) of rt_rng.h, its first two draws r0, r1 the jitter, the ray get_camera_ray(camera, (x + r0) /
+ * (w - 1), (y + r1) / (h - 1)) formed operation for operation as the render kernels form it, the value trace_path(&ray, scene, n, 0)
+ * at MAX_DEPTH = params->max_depth.  sample_first >= 0 and sample_first + S <= 2^31.
+ * The mean has rt_hip_trace_rays' shape with slice = k mod 4: S_j (j = 0 .. 3) is the ascending vec3_add, from +0.0, of the samples
+ * with k = j (mod 4); total = (S_0 + S_1) + (S_2 + S_3); radiance = total * (1.0 / (double)S).
+ * Outputs: RtHipRadiance (status, radiance, samples entry-major [i*S + k], paths, casts: each may be NULL, not all; ray must be
+ * NULL).  d_stats (RT_HIP_NSTATS accumulators, may be NULL) += the render's four counters: rays = the sum of paths, casts, tests =
+ * casts x primitives, samples = valid entries x S.
+ * Exactness, as for radiance queries: every decision is the reference's, so `paths` and `casts` per entry equal the compiled
+ * reference's trace_sample(scene, x, y, sample_first + k, seed) exactly; each sample VALUE is the render kernels' iteration, within
+ * 2^-40 |ref| of it (with M_REFRACTION 2^-40 (|ref| + the entry's largest |ref|)).  Bit-exact are:
+ *   (a) radiance is the stated reduction of samples;
+ *   (b) an entry's outputs are a function of (scene, camera, w, h, seed, p, sample_first, S) alone: not of its position in the list,
+ *       of the other entries, or of how the list is split over calls; a duplicate index gets duplicate bits;
+ *   (c) a sample is a function of (scene, camera, w, h, seed, p, s) alone: S = 8, sample_first = 0 gives in samples 4 .. 7 the bits
+ *       S = 4, sample_first = 4 gives.  Refining a frame of N spp with sample_first = N takes exactly the samples a progressive
+ *       accumulation would take next, and re-draws none the frame already has.
+ * Everything else is rt_hip_trace_rays': the two-child forms through the per-device pending-ray pool, the device's status word
+ * (rt_hip_launch_status), NaN radiance and samples for the valid entries of a workgroup without its slot, max_depth 0 .. 1000000 and
+ * <= 32 with M_REFRACTION (RT_HIP_ELIMIT), integrator RT_HIP_TRACE_PATH only, the error order, n == 0 launching nothing.
+ *   - rt_hip_pixel_defaults: zeros, samples 1, max_depth 5, RT_HIP_TRACE_PATH (width and height are the caller's to set).
+ *   - rt_hip_trace_pixels_host: the same from host arrays, synchronous, with a scene and buffers of its own, on logical device
+ *     `device` of rt_hip_render_image's device map; h_stats (may be NULL) += the counters.
+ *   - rt_hip_pixel_kernel_name / _count / _launches: the five forms (pt_trace_pixels[_big|_tri|_tri_big|_mem], picked as the
+ *     radiance-query forms are; not members of the family of rt_hip_kernel_count) and the launches this process has made of each.
+ *
+ * rt_hip_blend_pixels: the new samples into the frame.  All arithmetic is fp64 + - * / in the order written, floats are widened
+ * exactly, stores are rounded to float32 (RNE).  d_pixels[n] as the select gives them -- DISTINCT (with duplicates which entry wins
+ * a pixel is unspecified; nothing faults); d_status and d_radiance of a trace call over that list; new_weight (finite, > 0,
+ * typically S); prior_scale (>= 0, not NaN); d_prior (one float per pixel; NULL: 1.0 everywhere); the frame d_rgb (3 floats per
+ * pixel of w x h, 1 <= w, h <= 2^20, w*h < 2^32), updated in place.  Per entry with p < w*h and status == 1 and all three channels
+ * of r = radiance finite:
+ *   1. wa = prior_scale * prior_p.
+ *   2. If !(wa > 0), or wa is not finite, or a channel of c = rgb(p) is not finite: out = float(r), W = new_weight.
+ *   3. Otherwise W = wa + new_weight, out = float((c * wa + r * new_weight) / W) per channel.
+ * Any other entry leaves its pixel untouched.  Written at the touched pixels only: d_rgb; d_rgb8 (may be NULL), the render
+ * epilogue's tonemap of the widened out; d_weight (may be NULL; may be d_prior itself), float(W).  The contract is total.  One
+ * launch on `stream`, on the device that holds d_rgb; no pool, no workspace; n == 0 launches nothing.  RT_HIP_EINVAL, then
+ * RT_HIP_ENODEV. */
+enum
+{
+  RT_HIP_SELECT_INVERT = 1u
+};
+typedef struct
+{
+  int32_t width, height;  /* the frame the indices are of */
+  int32_t samples;        /* S >= 1 */
+  int32_t sample_first;   /* s0 >= 0, s0 + S <= 2^31 */
+  int32_t max_depth;      /* the reference's MAX_DEPTH */
+  uint32_t integrator;    /* must be RT_HIP_TRACE_PATH */
+  uint64_t seed;
+} RtHipPixelParams;
+size_t rt_hip_select_workspace_bytes(int32_t width, int32_t height);
+int rt_hip_select_pixels(const float *d_values, int32_t width, int32_t height, double lo, double hi, uint32_t flags, void *d_workspace,
+                         uint32_t *d_indices, uint32_t capacity, uint32_t *d_count, void *stream);
+void rt_hip_pixel_defaults(RtHipPixelParams *params);
+int rt_hip_trace_pixels(const RtHipScene *scene, const RtHipCamera *camera, const uint32_t *d_pixels, uint64_t n,
+                        const RtHipPixelParams *params, const RtHipRadiance *d_out, uint64_t *d_stats, void *stream);
+int rt_hip_trace_pixels_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                             const RtHipCamera *camera, const uint32_t *h_pixels, uint64_t n, const RtHipPixelParams *params, int device,
+                             const RtHipRadiance *h_out, uint64_t *h_stats);
+const char *rt_hip_pixel_kernel_name(const RtHipScene *scene);
+int rt_hip_pixel_kernel_count(void);
+const char *rt_hip_pixel_kernel_launches(int index, uint64_t *launches);
+int rt_hip_blend_pixels(const uint32_t *d_pixels, const uint32_t *d_status, const double *d_radiance, uint64_t n, int32_t width,
+                        int32_t height, double new_weight, double prior_scale, const float *d_prior, float *d_rgb, uint8_t *d_rgb8,
+                        float *d_weight, void *stream);
+
 /* Scatter a compact tile buffer into row-major images (either output may be
  * NULL together with its input). */
 int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t width, int32_t height,

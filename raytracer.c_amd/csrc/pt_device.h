@@ -388,6 +388,47 @@ struct PtTrace
   double *ray; /* 6 doubles per ray */
 };
 
+/* One pixel refinement (rt_hip.h, rt_hip_trace_pixels; trace_pixels in pt_kernel.hip): n pixel indices in, per entry the mean of
+ * PtLaunch.samples samples of the RENDER's own: sample k of entry i is sample sample_first + k of pixel pixels[i] of the launch's
+ * width x height frame (start_sample on the stream (PtLaunch.seed, pixel, sample_first + k)).  n_pixels = width * height: an index
+ * at or beyond it is invalid.  samples: 3 doubles per (entry, sample), [i * S + k].  Any output may be null (not all). */
+struct PtPixels
+{
+  const uint32_t *pixels;
+  uint64_t n; /* < 2^32 */
+  uint32_t n_pixels, sample_first;
+  uint32_t *status;
+  double *radiance, *samples;
+  unsigned long long *paths, *casts;
+};
+
+/* The ordered compaction of a per-pixel map (rt_hip.h, rt_hip_select_pixels; pt_select_* in pt_kernel.hip): pixel p of `values` is
+ * selected iff (lo <= v && v <= hi) != invert.  A workgroup of pt_select_count / pt_select_scatter covers PT_SELECT_BLOCK pixels, a
+ * workgroup of pt_select_scan PT_SELECT_SCAN counts. */
+#define PT_SELECT_BLOCK 256u
+#define PT_SELECT_SCAN 1024u
+struct PtSelect
+{
+  const float *values;
+  uint64_t n; /* pixels, < 2^32 */
+  double lo, hi;
+  uint32_t invert;
+};
+
+/* One blend of traced pixels into a frame (rt_hip.h, rt_hip_blend_pixels; pt_blend_pixels in pt_kernel.hip) */
+struct PtBlend
+{
+  const uint32_t *pixels, *status;
+  const double *radiance;
+  uint64_t n; /* entries, < 2^32 */
+  uint32_t n_pixels;
+  double new_weight, prior_scale;
+  const float *prior; /* may be null: 1.0 */
+  float *rgb;
+  uint8_t *rgb8; /* may be null */
+  float *weight; /* may be null; may be `prior` itself */
+};
+
 /* One launch of the denoiser (rt_hip.h, rt_hip_denoise; pt_denoise_* in pt_kernel.hip).  The workspace holds, per pixel of the
  * row-major w x h image: two ping-pong float4 colour buffers e[0], e[1] (the filtered signal, .w = 1 valid / 0 invalid), the
  * guidance float4 (normal, depth) and uint2 (hits, object) the prepare pass packs so that a tap is three loads. */
@@ -536,6 +577,21 @@ hipError_t pt_launch_trace(const PtLaunch &launch, const PtTrace &trace, hipStre
 const char *pt_trace_kernel_name_of(int which);
 int pt_trace_kernel_count(void);
 unsigned long long pt_trace_kernel_launches(int which);
+/* the pixel-refinement kernels (pt_kernel.hip: trace_pixels, PT_PIXEL_FAMILY): the form a scene takes (pt_trace_pick's choice, the
+ * lists run in parallel), the launch (64 entries x 4 sample slices per workgroup; what a radiance query's launch takes, and the
+ * frame's size and camera), names and launch counters */
+int pt_pixel_pick(const PtSceneView &scene);
+hipError_t pt_launch_pixels(const PtLaunch &launch, const PtPixels &pixels, hipStream_t stream, int which);
+const char *pt_pixel_kernel_name_of(int which);
+int pt_pixel_kernel_count(void);
+unsigned long long pt_pixel_kernel_launches(int which);
+/* the compaction: its workspace (the per-workgroup counts and every level of their scan; 0 for no pixel), and the launches on
+ * `stream` -- the counts, the scan's levels (a loop over levels here on the host, no workgroup waits on another), the scatter
+ * (capacity > 0 only).  *count gets the full count. */
+size_t pt_select_workspace_bytes(uint64_t n);
+hipError_t pt_launch_select(const PtSelect &args, void *workspace, uint32_t *indices, uint32_t capacity, uint32_t *count, hipStream_t stream);
+/* the blend: one launch, an entry per lane */
+hipError_t pt_launch_blend(const PtBlend &args, hipStream_t stream);
 /* the denoiser: the prepare pass and `iterations` filter passes (the last one remodulates and tonemaps) on `stream` */
 hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma_color, hipStream_t stream);
 /* temporal reprojection: one launch, a 16 x 16 block of pixels per workgroup, on `stream` */

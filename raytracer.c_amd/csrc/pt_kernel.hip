@@ -220,7 +220,7 @@ PT_FAMILY_DEV(PT_ENTRY)
 #undef PT_ENTRY
 
 /* ---- a kernel list on the host: the rows an X-macro list generates, and how often each was launched in this process
- * (what a test run actually exercised).  The four lists (PT_FAMILY, PT_AOV_FAMILY, PT_QUERY_FAMILY, PT_TRACE_FAMILY) are one of these each;
+ * (what a test run actually exercised).  The five lists (PT_FAMILY, PT_AOV_FAMILY, PT_QUERY_FAMILY, PT_TRACE_FAMILY, PT_PIXEL_FAMILY) are one of these each;
  * pt_*_name_of / _count / _launches (pt_device.h) ask it.  The lists' ids come from PT_LIST_ID, the rows of the two plain
  * lists from PT_LIST_INFO; the family's rows carry more (PT_INFO), and each list's entry points have their own signature, so
  * the three ENTRY macros stay apart. */
@@ -779,6 +779,186 @@ typedef void (*PtTraceKernelFn)(const PtLaunch, const PtTrace);
 #define PT_TRACE_INFO(id, name, bounds, ...) {#name, name},
 static PtKernelList<PtEntryInfo<PtTraceKernelFn>, T_COUNT> pt_trace_kernels = {{PT_TRACE_FAMILY(PT_TRACE_INFO)}};
 #undef PT_TRACE_INFO
+
+/* ---- pixel-refinement body: a lane = (entry, sample slice), a workgroup = 64 consecutive entries x 4 slices ----------------------
+ * rt_hip.h has the contract (rt_hip_trace_pixels).  A SIBLING of trace_rays, not a template option of it: the entry's front end is
+ * another (a pixel index instead of a ray record: PtPixels has other fields than PtTrace, and a shared argument struct would move
+ * the kernel arguments of the five radiance-query kernels), so sharing would have saved the loop's forty lines at the price of
+ * their listings.  What is the same, statement for statement: the lane mapping, the pool slot, the loop around trace_step, the
+ * per-sample store, the shuffles of the mean, the counters and the epilogue.  What differs:
+ *   - entry i names pixel p = pixels[i] of the launch's frame (x = p % w, y = p / w); p >= w * h is the invalid entry;
+ *   - sample k of the entry is the render's sample s = sample_first + k of that pixel: the fresh branch is start_sample -- the
+ *     stream (seed, p, s), its first two draws the jitter, get_camera_ray of ((x + r0) / (w - 1), (y + r1) / (h - 1)) through
+ *     div_small_int and the unscaled normalize -- exactly what render_tiles_static runs per sample; no ray is stored or re-read;
+ *   - the slice of sample k is k mod 4 (the list's own numbering: sample_first shifts the stream, not the reduction);
+ *   - no first scan runs without the rules: a camera ray is a vec3_normalize result (RULE_SWITCH stays off, as in the render). */
+template <bool REFRACT, bool CHECKER, bool TRIS = false, bool FILT_LDS = true, bool GEOM_LDS = true>
+__device__ __forceinline__ void trace_pixels(const PtLaunch &L, const PtPixels &Q)
+{
+  static_assert(GEOM_LDS || !FILT_LDS, "a staged filter table comes with staged geometry");
+  constexpr uint32_t ENTRIES = PT_BLOCK / PT_SLICES; /* entries per workgroup */
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  __shared__ unsigned long long wg_stats[3];
+  SceneCtx S_init = stage_scene<GEOM_LDS, FILT_LDS>(L, lds);
+  __shared__ double atan_tab[CHECKER ? PT_ATAN_TAB : 1];
+  if (CHECKER)
+  {
+    atan_table_to_lds(atan_tab);
+    S_init.atan_tab = atan_tab;
+  }
+  const SceneCtx S = S_init;
+  if (threadIdx.x < 3)
+    wg_stats[threadIdx.x] = 0;
+
+  const uint32_t slice = threadIdx.x & (PT_SLICES - 1), entry_in_wg = threadIdx.x / PT_SLICES;
+  const uint64_t i = (uint64_t)blockIdx.x * ENTRIES + entry_in_wg;
+  const bool inside = i < Q.n;
+  const uint32_t pixel = inside ? Q.pixels[i] : 0xFFFFFFFFu;
+  const bool valid = inside && pixel < Q.n_pixels;
+  const uint32_t px = pixel % (uint32_t)L.width, py = pixel / (uint32_t)L.width;
+  const CameraRegs cam = load_camera(L);
+  /* the workgroup's slot of the pending-ray pool (PendStack), as the static body takes it */
+  __shared__ uint32_t pend_slot_lds;
+  if (REFRACT && threadIdx.x == 0)
+    pend_slot_lds = pt_pool_acquire(L.pend_flags, L.pend_slots_per_xcd, L.status, PT_FAIL_PEND_SLOT);
+  __syncthreads();
+  const uint32_t pend_slot = REFRACT ? pend_slot_lds : 0u;
+  const bool pend_ok = !REFRACT || pend_slot != 0xFFFFFFFFu;
+  const PendStack stack = {REFRACT && pend_ok ? L.pend_ws + (size_t)pend_slot * L.pend_slot_doubles + threadIdx.x : nullptr,
+                           REFRACT && pend_ok ? (int)L.pend_entries : 0, PT_BLOCK, PT_PEND_FIELDS * PT_BLOCK};
+
+  const uint32_t spp = (uint32_t)L.samples;
+  const uint64_t pixel_key = rt_rng_pixel_key(L.seed, pixel);
+  V3 acc = {0, 0, 0};
+  Path P;
+  P.o = {0, 0, 0};
+  P.d = {0, 0, 1};
+  P.T = {1, 1, 1};
+  P.Ls = {0, 0, 0};
+  P.rng = 1;
+  P.depth = 0;
+  uint32_t n_rays = 0, n_casts = 0;
+  unsigned long long paths = 0, casts = 0; /* of this lane's finished samples */
+  uint32_t k = (valid && pend_ok) ? slice : spp; /* the entry's sample k is the pixel's sample sample_first + k (< 2^31) */
+  bool fresh = true;
+  int stack_n = 0;
+  unsigned long long *diag_ptr = L.stats;
+  (void)diag_ptr;
+
+  while (k < spp)
+  {
+    if (fresh)
+    {
+      start_sample(P, cam, pixel_key, px, py, sample_term(Q.sample_first + k));
+      fresh = false;
+    }
+    n_rays++;
+    const bool finished = trace_step<1, REFRACT, CHECKER, TRIS, FILT_LDS>(S, P, n_casts, diag_ptr, stack, stack_n);
+    if (finished)
+    {
+      acc = v_add(acc, P.Ls);
+      if (Q.samples)
+      {
+        double *q = Q.samples + 3u * (i * spp + k);
+        q[0] = P.Ls.x; q[1] = P.Ls.y; q[2] = P.Ls.z;
+      }
+      paths += n_rays;
+      casts += n_casts;
+      n_rays = n_casts = 0;
+      k += PT_SLICES;
+      fresh = true;
+    }
+  }
+
+  const double quiet_nan = __longlong_as_double(0x7FF8000000000000ll);
+  if (inside && Q.samples && !(valid && pend_ok)) /* an invalid entry: zeros; a workgroup without its pool slot: NaN (the render's rule) */
+    for (uint32_t j = slice; j < spp; j += PT_SLICES)
+    {
+      double *q = Q.samples + 3u * (i * spp + j);
+      q[0] = q[1] = q[2] = valid ? quiet_nan : 0.0;
+    }
+  /* per-entry mean: the static body's fixed-order reduction over the 4 slice lanes */
+  acc.x += __shfl_xor(acc.x, 1);
+  acc.y += __shfl_xor(acc.y, 1);
+  acc.z += __shfl_xor(acc.z, 1);
+  acc.x += __shfl_xor(acc.x, 2);
+  acc.y += __shfl_xor(acc.y, 2);
+  acc.z += __shfl_xor(acc.z, 2);
+  V3 mean = v_scale(acc, 1.0 / (double)spp);
+  if (valid && !pend_ok)
+    mean.x = mean.y = mean.z = quiet_nan;
+  if (paths)
+  {
+    atomicAdd(&wg_stats[0], paths);
+    atomicAdd(&wg_stats[1], casts);
+  }
+  paths += __shfl_xor(paths, 1);
+  casts += __shfl_xor(casts, 1);
+  paths += __shfl_xor(paths, 2);
+  casts += __shfl_xor(casts, 2);
+  if (inside && slice == 0)
+  {
+    if (valid)
+      atomicAdd(&wg_stats[2], 1ull);
+    if (Q.status)
+      Q.status[i] = valid ? 1u : 2u;
+    if (Q.radiance)
+    {
+      double *q = Q.radiance + 3u * i;
+      q[0] = mean.x; q[1] = mean.y; q[2] = mean.z;
+    }
+    if (Q.paths)
+      Q.paths[i] = paths;
+    if (Q.casts)
+      Q.casts[i] = casts;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    if (L.stats)
+    {
+      const unsigned long long c = wg_stats[1];
+      atomicAdd(&L.stats[0], wg_stats[0]);
+      atomicAdd(&L.stats[1], c);
+      atomicAdd(&L.stats[2], c * (unsigned long long)(S.n_sph + S.n_tri));
+      atomicAdd(&L.stats[3], wg_stats[2] * (unsigned long long)spp);
+    }
+    if (REFRACT && pend_ok)
+      atomicExch(&L.pend_flags[pend_slot], 0u); /* every lane is past its last pop (the barrier above) */
+  }
+}
+
+/* ---- the pixel-refinement kernels (rt_hip_trace_pixels): a fourth list of their own -- no rows of the pick table.  The five forms
+ * mirror PT_TRACE_FAMILY row for row and are picked as that list is (pt_pixel_pick = pt_trace_pick: the enums run in parallel):
+ *   pt_trace_pixels          spheres staged, filter staged (sign-test form)
+ *   pt_trace_pixels_big      spheres staged, filter by scalar loads
+ *   pt_trace_pixels_tri      + triangles through the flat filter and the fp32 pre-test
+ *   pt_trace_pixels_tri_big  + triangles through the hierarchy
+ *   pt_trace_pixels_mem      geometry from memory, triangles (if any) through the hierarchy
+ * Body: trace_pixels<REFRACT, CHECKER, TRIS, FILT_LDS, GEOM_LDS>. */
+#define PT_PIXEL_FAMILY(X) \
+  X(P_PIXELS,  pt_trace_pixels,         (PT_BLOCK, PT_MIN_WAVES_REFR),     trace_pixels<true, true>) \
+  X(P_BIG,     pt_trace_pixels_big,     (PT_BLOCK, PT_MIN_WAVES_REFR),     trace_pixels<true, true, false, false>) \
+  X(P_TRI,     pt_trace_pixels_tri,     (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), trace_pixels<true, true, true, true>) \
+  X(P_TRI_BIG, pt_trace_pixels_tri_big, (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), trace_pixels<true, true, true, false>) \
+  X(P_MEM,     pt_trace_pixels_mem,     (PT_BLOCK),                        trace_pixels<true, true, true, false, false>)
+
+#define PT_PIXEL_ENTRY(id, name, bounds, ...) \
+  extern "C" __global__ __launch_bounds__ bounds void name(const PtLaunch L, const PtPixels Q) { __VA_ARGS__(L, Q); }
+PT_PIXEL_FAMILY(PT_PIXEL_ENTRY)
+#undef PT_PIXEL_ENTRY
+
+enum PtPixelKernelId
+{
+  PT_PIXEL_FAMILY(PT_LIST_ID) P_COUNT
+};
+static_assert((int)P_PIXELS == (int)T_RAYS && (int)P_BIG == (int)T_BIG && (int)P_TRI == (int)T_TRI && (int)P_TRI_BIG == (int)T_TRI_BIG &&
+                  (int)P_MEM == (int)T_MEM && (int)P_COUNT == (int)T_COUNT,
+              "the pixel list mirrors the trace list: pt_pixel_pick is pt_trace_pick");
+typedef void (*PtPixelKernelFn)(const PtLaunch, const PtPixels);
+#define PT_PIXEL_INFO(id, name, bounds, ...) {#name, name},
+static PtKernelList<PtEntryInfo<PtPixelKernelFn>, P_COUNT> pt_pixel_kernels = {{PT_PIXEL_FAMILY(PT_PIXEL_INFO)}};
+#undef PT_PIXEL_INFO
 
 /* The sample count a resolve divides slot `slot` by: the launch's, or -- an accumulation with frozen tiles (rt_hip_accum_freeze) --
  * the slot's own where it has one (0: the slot is live and holds the launch's count). */
@@ -1759,6 +1939,146 @@ extern "C" __global__ __launch_bounds__(256) void pt_upsample(const PtUpsample U
   }
 }
 
+/* ---- pixel selection (rt_hip_select_pixels): the ordered compaction of a per-pixel map ---------------------------------------
+ * Three kinds of launch, in stream order; no workgroup reads what another workgroup of the SAME launch writes, so nothing waits and
+ * the result does not depend on scheduling:
+ *   pt_select_count    a workgroup = PT_SELECT_BLOCK consecutive pixels, a lane = a pixel: the wave's ballot of the predicate,
+ *                      its popcount, the four waves' counts through LDS -> counts[workgroup];
+ *   pt_select_scan     a workgroup = PT_SELECT_SCAN consecutive counts (four per lane): their exclusive scan in place, and the
+ *                      workgroup's total -> sums[workgroup].  pt_launch_select runs it level by level -- the sums of one level are
+ *                      the next level's counts -- until one workgroup covers a level (three levels reach 2^30 counts; 2^32 - 1
+ *                      pixels are 2^24), then pt_select_add adds each level's scanned sums back onto the level below.  The top
+ *                      level's one total is the count;
+ *   pt_select_scatter  pt_select_count's predicate and ballot again: pixel p goes to offsets[workgroup] + the counts of the waves
+ *                      before its own + the popcount of the ballot's bits below its lane -- ascending in p by construction.
+ * The predicate is rt_hip.h's, in fp64 on the exactly widened float: (lo <= v && v <= hi), negated under `invert`. */
+__device__ __forceinline__ bool select_predicate(const PtSelect &A, uint64_t p)
+{
+  if (p >= A.n)
+    return false;
+  const double v = (double)A.values[p];
+  const bool in = A.lo <= v && v <= A.hi; /* false for NaN */
+  return A.invert ? !in : in;
+}
+
+extern "C" __global__ __launch_bounds__(PT_SELECT_BLOCK) void pt_select_count(const PtSelect A, uint32_t *__restrict__ counts)
+{
+  __shared__ uint32_t wave_count[PT_SELECT_BLOCK / 64u];
+  const uint64_t p = (uint64_t)blockIdx.x * PT_SELECT_BLOCK + threadIdx.x;
+  const unsigned long long ballot = __ballot(select_predicate(A, p));
+  if ((threadIdx.x & 63u) == 0u)
+    wave_count[threadIdx.x >> 6] = (uint32_t)__popcll(ballot);
+  __syncthreads();
+  if (threadIdx.x == 0)
+    counts[blockIdx.x] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
+}
+
+/* exclusive scan of data[0 .. m) in place, PT_SELECT_SCAN values per workgroup; sums[workgroup] = the workgroup's total */
+extern "C" __global__ __launch_bounds__(256) void pt_select_scan(uint32_t *__restrict__ data, uint32_t m, uint32_t *__restrict__ sums)
+{
+  static_assert(PT_SELECT_SCAN == 4u * 256u, "four values per lane");
+  __shared__ uint32_t lane_total[256];
+  const uint32_t base = blockIdx.x * PT_SELECT_SCAN + 4u * threadIdx.x; /* m <= 2^24: no overflow */
+  uint32_t v[4];
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; j++)
+    v[j] = base + j < m ? data[base + j] : 0u;
+  lane_total[threadIdx.x] = (v[0] + v[1]) + (v[2] + v[3]);
+  __syncthreads();
+  /* Hillis-Steele over the 256 lane totals: inclusive, eight steps, two barriers each (read, then write) */
+  for (uint32_t d = 1u; d < 256u; d <<= 1)
+  {
+    const uint32_t add = threadIdx.x >= d ? lane_total[threadIdx.x - d] : 0u;
+    __syncthreads();
+    lane_total[threadIdx.x] += add;
+    __syncthreads();
+  }
+  uint32_t run = threadIdx.x ? lane_total[threadIdx.x - 1u] : 0u;
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; j++)
+  {
+    if (base + j < m)
+      data[base + j] = run;
+    run += v[j];
+  }
+  if (threadIdx.x == 255u)
+    sums[blockIdx.x] = lane_total[255];
+}
+
+/* data[i] += offsets[i / PT_SELECT_SCAN]: a level's scanned sums back onto the level below */
+extern "C" __global__ __launch_bounds__(256) void pt_select_add(uint32_t *__restrict__ data, uint32_t m, const uint32_t *__restrict__ offsets)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < m)
+    data[i] += offsets[i / PT_SELECT_SCAN];
+}
+
+extern "C" __global__ __launch_bounds__(PT_SELECT_BLOCK) void pt_select_scatter(const PtSelect A, const uint32_t *__restrict__ offsets,
+                                                                                uint32_t *__restrict__ indices, uint32_t capacity)
+{
+  __shared__ uint32_t wave_count[PT_SELECT_BLOCK / 64u];
+  const uint64_t p = (uint64_t)blockIdx.x * PT_SELECT_BLOCK + threadIdx.x;
+  const bool selected = select_predicate(A, p);
+  const unsigned long long ballot = __ballot(selected);
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0u)
+    wave_count[wave] = (uint32_t)__popcll(ballot);
+  __syncthreads();
+  uint32_t at = offsets[blockIdx.x];
+  for (uint32_t w = 0; w < wave; w++)
+    at += wave_count[w];
+  at += __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u)); /* set bits below this lane */
+  if (selected && at < capacity)
+    indices[at] = (uint32_t)p;
+}
+
+/* ---- the blend (rt_hip_blend_pixels): traced pixels into the frame -------------------------------------------------------------
+ * rt_hip.h states the arithmetic; this is it, operation for operation, in fp64.  A lane is an entry of the list; the entries name
+ * distinct pixels (with duplicates the lanes race for the pixel: some entry's complete or partial result, nothing out of bounds).
+ * `weight` may be `prior` itself: a lane reads its pixel's prior before it writes the pixel's weight, and no other lane has that pixel. */
+extern "C" __global__ __launch_bounds__(256) void pt_blend_pixels(const PtBlend B)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= B.n)
+    return; /* no barrier follows */
+  const uint32_t p = B.pixels[i];
+  if (p >= B.n_pixels || B.status[i] != 1u)
+    return;
+  const double rx = B.radiance[3u * i + 0], ry = B.radiance[3u * i + 1], rz = B.radiance[3u * i + 2];
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);
+  auto finite = [&](double x) { return __builtin_fabs(x) < inf; }; /* false for NaN */
+  if (!(finite(rx) && finite(ry) && finite(rz)))
+    return;
+  const size_t q = (size_t)p;
+  const double wa = B.prior_scale * (B.prior ? (double)B.prior[q] : 1.0);
+  const double cx = (double)B.rgb[3 * q + 0], cy = (double)B.rgb[3 * q + 1], cz = (double)B.rgb[3 * q + 2];
+  float ox, oy, oz;
+  double W;
+  if (!(wa > 0) || !finite(wa) || !(finite(cx) && finite(cy) && finite(cz)))
+  {
+    ox = (float)rx; oy = (float)ry; oz = (float)rz;
+    W = B.new_weight;
+  }
+  else
+  {
+    W = wa + B.new_weight;
+    ox = (float)((cx * wa + rx * B.new_weight) / W);
+    oy = (float)((cy * wa + ry * B.new_weight) / W);
+    oz = (float)((cz * wa + rz * B.new_weight) / W);
+  }
+  B.rgb[3 * q + 0] = ox;
+  B.rgb[3 * q + 1] = oy;
+  B.rgb[3 * q + 2] = oz;
+  if (B.rgb8)
+  {
+    B.rgb8[3 * q + 0] = tonemap((double)ox);
+    B.rgb8[3 * q + 1] = tonemap((double)oy);
+    B.rgb8[3 * q + 2] = tonemap((double)oz);
+  }
+  if (B.weight)
+    B.weight[q] = (float)W;
+}
+
 /* ---- launch wrappers (host side), declared in pt_device.h ---------------------- */
 
 size_t pt_render_lds_bytes(const PtSceneView &sc)
@@ -2305,6 +2625,103 @@ hipError_t pt_launch_trace(const PtLaunch &launch, const PtTrace &trace, hipStre
   if (e == hipSuccess)
     pt_trace_kernels.launched(which);
   return e;
+}
+
+/* ---- the pixel-refinement kernels: which form a scene takes, and the launch ------------------------------------------------ */
+int pt_pixel_pick(const PtSceneView &scene) { return pt_trace_pick(scene); } /* (the lists run in parallel: static_assert at PT_PIXEL_FAMILY) */
+
+const char *pt_pixel_kernel_name_of(int which) { return pt_pixel_kernels.name_of(which); }
+int pt_pixel_kernel_count(void) { return P_COUNT; }
+unsigned long long pt_pixel_kernel_launches(int which) { return pt_pixel_kernels.launches(which); }
+
+hipError_t pt_launch_pixels(const PtLaunch &launch, const PtPixels &pixels, hipStream_t stream, int which)
+{
+#ifdef PT_DIAG
+  return hipErrorNotSupported; /* (as pt_launch_trace: the diagnostic build counts into stats[4 ..]) */
+#endif
+  if (!pt_pixel_kernels.valid(which) || pixels.n == 0u || pixels.n > 0xFFFFFFFFull || launch.samples < 1 ||
+      (uint64_t)pixels.sample_first + (uint64_t)launch.samples > 0x80000000ull || launch.width < 2 || launch.height < 2 ||
+      (uint64_t)launch.width * (uint64_t)launch.height != (uint64_t)pixels.n_pixels)
+    return hipErrorInvalidValue;
+  /* every form pushes pending second children: its pool, as pt_launch_trace asks */
+  if (launch.pend_ws == nullptr || launch.pend_slots_per_xcd == 0u || launch.pend_entries == 0u ||
+      launch.pend_entries < pt_pend_entries(launch.scene, 0u, launch.max_depth) ||
+      launch.pend_slot_doubles < (uint64_t)launch.pend_entries * PT_PEND_FIELDS_HOST * PT_BLOCK)
+    return hipErrorInvalidValue;
+  const size_t lds_bytes = which == P_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the trace launch */
+  const uint32_t per_wg = PT_BLOCK / PT_SLICES;
+  const uint32_t blocks = (uint32_t)((pixels.n + per_wg - 1u) / per_wg); /* at most 2^26 */
+  const hipError_t e = launch_staged(pt_pixel_kernels[which].fn, blocks, lds_bytes, stream, launch, pixels);
+  if (e == hipSuccess)
+    pt_pixel_kernels.launched(which);
+  return e;
+}
+
+/* ---- the compaction's launches (rt_hip_select_pixels) ------------------------------------------------------------------------
+ * The workspace: level 0 holds the per-workgroup counts (ceil(n / PT_SELECT_BLOCK) words), level l + 1 the workgroup totals of
+ * level l's scan (ceil(m_l / PT_SELECT_SCAN) words), down to a level of one word; every level starts on a 256-byte boundary. */
+static size_t select_levels(uint64_t n, uint32_t m[8], size_t off[8], int *levels)
+{
+  size_t total = 0;
+  int l = 0;
+  for (uint64_t count = (n + PT_SELECT_BLOCK - 1u) / PT_SELECT_BLOCK; l < 8; count = (count + PT_SELECT_SCAN - 1u) / PT_SELECT_SCAN)
+  {
+    m[l] = (uint32_t)count;
+    off[l] = total;
+    total += ((size_t)count * sizeof(uint32_t) + 255u) & ~(size_t)255u;
+    l++;
+    if (count <= 1u)
+      break;
+  }
+  *levels = l;
+  return total;
+}
+
+size_t pt_select_workspace_bytes(uint64_t n)
+{
+  uint32_t m[8];
+  size_t off[8];
+  int levels;
+  return n == 0u || n > 0xFFFFFFFFull ? 0 : select_levels(n, m, off, &levels);
+}
+
+hipError_t pt_launch_select(const PtSelect &args, void *workspace, uint32_t *indices, uint32_t capacity, uint32_t *count, hipStream_t stream)
+{
+  if (args.n == 0u || args.n > 0xFFFFFFFFull || workspace == nullptr || count == nullptr || (capacity != 0u && indices == nullptr))
+    return hipErrorInvalidValue;
+  uint32_t m[8];
+  size_t off[8];
+  int levels;
+  (void)select_levels(args.n, m, off, &levels);
+  auto level = [&](int l) { return reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + off[l]); };
+  hipLaunchKernelGGL(pt_select_count, dim3(m[0]), dim3(PT_SELECT_BLOCK), 0, stream, args, level(0));
+  /* down: level l scanned in place, its workgroup totals are level l + 1 (m[l + 1] = the scan's workgroups); the last level is one
+   * workgroup, whose one total is the count */
+  for (int l = 0; l < levels; l++)
+  {
+    const uint32_t blocks = (m[l] + PT_SELECT_SCAN - 1u) / PT_SELECT_SCAN;
+    hipLaunchKernelGGL(pt_select_scan, dim3(blocks), dim3(256), 0, stream, level(l), m[l], blocks == 1u ? count : level(l + 1));
+    if (blocks == 1u)
+    {
+      levels = l + 1;
+      break;
+    }
+  }
+  /* up: each level's scanned totals onto the level below */
+  for (int l = levels - 2; l >= 0; l--)
+    hipLaunchKernelGGL(pt_select_add, dim3((m[l] + 255u) / 256u), dim3(256), 0, stream, level(l), m[l], level(l + 1));
+  if (capacity != 0u)
+    hipLaunchKernelGGL(pt_select_scatter, dim3(m[0]), dim3(PT_SELECT_BLOCK), 0, stream, args, level(0), indices, capacity);
+  return hipGetLastError();
+}
+
+/* ---- the blend's launch (rt_hip_blend_pixels) --------------------------------------------------------------------------------- */
+hipError_t pt_launch_blend(const PtBlend &args, hipStream_t stream)
+{
+  if (args.n == 0u || args.n > 0xFFFFFFFFull)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pt_blend_pixels, dim3((uint32_t)((args.n + 255u) / 256u)), dim3(256), 0, stream, args);
+  return hipGetLastError();
 }
 
 hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int width, int height, uint32_t tile_first,

@@ -2844,6 +2844,199 @@ int trace_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtH
   return RT_HIP_OK;
 }
 
+/* ---- pixel refinement (rt_hip.h, rt_hip_select_pixels / _trace_pixels / _blend_pixels) ---------------------------------------
+ * select and blend are image-space calls like the upsampling: arguments checked without a device, then the device that holds the
+ * first buffer.  trace_pixels is a radiance query's launch (trace_launch) whose rays the kernel forms itself: the frame's camera
+ * and size in the launch, the camera's distance in origin_radius' place -- the near_R of a render launch of that camera. */
+bool select_size_ok(int32_t width, int32_t height)
+{
+  return width >= 1 && height >= 1 && width <= (1 << 20) && height <= (1 << 20) && (uint64_t)width * (uint64_t)height <= 0xFFFFFFFFull;
+}
+
+int check_select(const float *values, int32_t width, int32_t height, double lo, double hi, uint32_t flags, const void *workspace,
+                 const uint32_t *indices, uint32_t capacity, const uint32_t *count)
+{
+  if (!select_size_ok(width, height))
+    return fail(RT_HIP_EINVAL, "width and height must be in [1, 2^20] with fewer than 2^32 pixels");
+  if (lo != lo || hi != hi)
+    return fail(RT_HIP_EINVAL, "lo and hi must not be NaN");
+  if (flags & ~(uint32_t)RT_HIP_SELECT_INVERT)
+    return fail(RT_HIP_EINVAL, "unknown select flags 0x%x", flags);
+  if (!values || !workspace || !count)
+    return fail(RT_HIP_EINVAL, "d_values, d_workspace and d_count are required");
+  if (capacity != 0u && !indices)
+    return fail(RT_HIP_EINVAL, "d_indices is required with capacity > 0");
+  return RT_HIP_OK;
+}
+
+/* the device that holds `ptr` made current in `scope`: a host pointer would fault the kernel, so it is refused */
+int device_of(const void *ptr, const char *what, int *device)
+{
+  if (usable_devices() < 1)
+    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
+  hipPointerAttribute_t attr = {};
+  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess || attr.type != hipMemoryTypeDevice)
+  {
+    (void)hipGetLastError();
+    return fail(RT_HIP_EINVAL, "%s is not device memory", what);
+  }
+  *device = attr.device;
+  return RT_HIP_OK;
+}
+
+int check_pixels(const RtHipCamera *camera, const void *pixels, uint64_t n, const RtHipPixelParams *p, const RtHipRadiance *out)
+{
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is required");
+  if (!out || !(out->status || out->radiance || out->samples || out->paths || out->casts))
+    return fail(RT_HIP_EINVAL, "radiance: at least one output array is required");
+  if (out->ray)
+    return fail(RT_HIP_EINVAL, "radiance: ray must be NULL (an entry's samples have a camera ray each)");
+  if (p->integrator != RT_HIP_TRACE_PATH)
+    return fail(RT_HIP_EINVAL, "integrator %u: a pixel refinement traces paths (RT_HIP_TRACE_PATH) only", p->integrator);
+  if (p->samples < 1 || p->sample_first < 0 || (int64_t)p->sample_first + (int64_t)p->samples > ((int64_t)1 << 31))
+    return fail(RT_HIP_EINVAL, "samples = %d, sample_first = %d: samples >= 1, sample_first >= 0, sample_first + samples <= 2^31",
+                p->samples, p->sample_first);
+  if (p->max_depth < 0 || p->max_depth > 1000000)
+    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  if (p->width < 2 || p->height < 2 || p->width > (1 << 20) || p->height > (1 << 20) ||
+      (uint64_t)p->width * (uint64_t)p->height > 0xFFFFFFFFull)
+    return fail(RT_HIP_EINVAL, "width and height must be in [2, 2^20] with fewer than 2^32 pixels");
+  if (n > 0xFFFFFFFFull)
+    return fail(RT_HIP_EINVAL, "n = %llu: a call takes fewer than 2^32 entries", (unsigned long long)n);
+  if (!camera)
+    return fail(RT_HIP_EINVAL, "camera is required");
+  if (n != 0 && !pixels)
+    return fail(RT_HIP_EINVAL, "pixels is required");
+  return RT_HIP_OK;
+}
+
+int pixels_launch(const RtHipScene *scene, const RtHipCamera *camera, const uint32_t *d_pixels, uint64_t n, const RtHipPixelParams *p,
+                  const RtHipRadiance *d_out, uint64_t *d_stats, hipStream_t stream)
+{
+  if (scene->view.any_refract && p->max_depth > PT_REFRACT_MAX_DEPTH)
+    return fail(RT_HIP_ELIMIT, "scenes with M_REFRACTION materials support max_depth <= %d (two rays per refractive hit, "
+                               "raytracer.c:523-529; the pending-ray stack is fixed)", PT_REFRACT_MAX_DEPTH);
+  PtLaunch L;
+  const double *c = camera->position;
+  int rc = ray_launch_prepare(scene, RT_HIP_RAYS_CAMERA_UV, camera, std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), L);
+  if (rc)
+    return rc;
+  L.width = p->width;
+  L.height = p->height;
+  L.w_minus_1 = (double)p->width - 1.0; /* as launch_prepare: start_sample's exact quotient */
+  L.h_minus_1 = (double)p->height - 1.0;
+  L.inv_w_minus_1 = 1.0 / L.w_minus_1;
+  L.inv_h_minus_1 = 1.0 / L.h_minus_1;
+  L.samples = p->samples;
+  L.max_depth = p->max_depth;
+  L.seed = p->seed;
+  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
+  const PtPixels Q = {.pixels = d_pixels, .n = n, .n_pixels = (uint32_t)((uint64_t)p->width * (uint64_t)p->height),
+                      .sample_first = (uint32_t)p->sample_first, .status = d_out->status, .radiance = d_out->radiance,
+                      .samples = d_out->samples, .paths = reinterpret_cast<unsigned long long *>(d_out->paths),
+                      .casts = reinterpret_cast<unsigned long long *>(d_out->casts)};
+  const int which = pt_pixel_pick(scene->view);
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  rc = status_word_for(scene->device, &L.status);
+  if (rc)
+    return rc;
+  size_t slot = 0;
+  rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
+  if (rc)
+    return rc;
+  hipError_t e = hipSuccess;
+  {
+    std::lock_guard<std::mutex> pend_lock(g_pend_mutex);
+    rc = pend_pool_for(scene->device, pt_pend_entries(scene->view, 0u, p->max_depth), PT_PEND_COLUMNS, L);
+    if (!rc)
+      e = pt_launch_pixels(L, Q, stream, which);
+  }
+  release_tables(scene, slot, stream);
+  if (rc)
+    return rc;
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_pixel_kernel_name_of(which), hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+/* rt_hip_trace_pixels_host: a scene of its own on the logical device, one allocation for the list, the counters and the requested
+ * outputs, the launch on the null stream, the copies (as trace_rays_host_impl) */
+int trace_pixels_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
+                           const uint32_t *h_pixels, uint64_t n, const RtHipPixelParams *params, int device, const RtHipRadiance *h_out,
+                           uint64_t *h_stats)
+{
+  int rc = check_pixels(camera, h_pixels, n, params, h_out);
+  if (rc || n == 0)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  struct SceneOwner
+  {
+    RtHipScene *scene = nullptr;
+    ~SceneOwner() { rt_hip_scene_destroy(scene); }
+  } own;
+  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &own.scene);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  void *host[5] = {h_out->status, h_out->radiance, h_out->samples, h_out->paths, h_out->casts};
+  const size_t bytes_per_entry[5] = {4, 24, 24u * (size_t)params->samples, 8, 8};
+  size_t off[5], total = align256(4u * n);
+  const size_t off_stats = total;
+  total += align256(RT_HIP_NSTATS * sizeof(uint64_t));
+  for (int k = 0; k < 5; k++)
+  {
+    off[k] = total;
+    if (host[k])
+      total += align256(bytes_per_entry[k] * n);
+  }
+  DeviceBuffer buf;
+  HIP_TRY(buf.alloc(total));
+  HIP_TRY(hipMemcpy(buf.ptr, h_pixels, 4u * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(buf.at<char>(off_stats), 0, RT_HIP_NSTATS * sizeof(uint64_t)));
+  void *dev[5];
+  for (int k = 0; k < 5; k++)
+    dev[k] = host[k] ? buf.at<char>(off[k]) : nullptr;
+  const RtHipRadiance d_out = {(uint32_t *)dev[0], (double *)dev[1], (double *)dev[2], (uint64_t *)dev[3], (uint64_t *)dev[4], nullptr};
+  rc = pixels_launch(own.scene, camera, buf.at<uint32_t>(), n, params, &d_out, buf.at<uint64_t>(off_stats), nullptr);
+  if (rc)
+    return rc;
+  for (int k = 0; k < 5; k++)
+    if (host[k])
+      HIP_TRY(hipMemcpy(host[k], dev[k], bytes_per_entry[k] * n, hipMemcpyDeviceToHost)); /* (null stream: after the kernel) */
+  if (h_stats)
+  {
+    uint64_t st[RT_HIP_NSTATS];
+    HIP_TRY(hipMemcpy(st, buf.at<char>(off_stats), sizeof st, hipMemcpyDeviceToHost));
+    for (int k = 0; k < RT_HIP_NSTATS; k++)
+      h_stats[k] += st[k];
+  }
+  return RT_HIP_OK;
+}
+
+int check_blend(const uint32_t *pixels, const uint32_t *status, const double *radiance, uint64_t n, int32_t width, int32_t height,
+                double new_weight, double prior_scale, const float *rgb)
+{
+  if (!select_size_ok(width, height))
+    return fail(RT_HIP_EINVAL, "width and height must be in [1, 2^20] with fewer than 2^32 pixels");
+  if (n > 0xFFFFFFFFull)
+    return fail(RT_HIP_EINVAL, "n = %llu: a call takes fewer than 2^32 entries", (unsigned long long)n);
+  if (!(new_weight > 0) || !std::isfinite(new_weight))
+    return fail(RT_HIP_EINVAL, "new_weight %g must be finite and > 0", new_weight);
+  if (!(prior_scale >= 0))
+    return fail(RT_HIP_EINVAL, "prior_scale %g must be >= 0", prior_scale);
+  if (!rgb)
+    return fail(RT_HIP_EINVAL, "d_rgb is required");
+  if (n != 0 && (!pixels || !status || !radiance))
+    return fail(RT_HIP_EINVAL, "d_pixels, d_status and d_radiance are required");
+  return RT_HIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -3988,6 +4181,101 @@ int rt_hip_upsample_image(const float *h_low_rgb, const RtHipAov *h_low_aov, int
     return upsample_image_impl(h_low_rgb, h_low_aov, low_width, low_height, h_aov, width, height, params, device, h_out_rgb, h_out_rgb8,
                                h_out_conf);
   });
+}
+
+size_t rt_hip_select_workspace_bytes(int32_t width, int32_t height)
+{
+  return select_size_ok(width, height) ? pt_select_workspace_bytes((uint64_t)width * (uint64_t)height) : 0;
+}
+
+int rt_hip_select_pixels(const float *d_values, int32_t width, int32_t height, double lo, double hi, uint32_t flags, void *d_workspace,
+                         uint32_t *d_indices, uint32_t capacity, uint32_t *d_count, void *stream)
+{
+  int rc = check_select(d_values, width, height, lo, hi, flags, d_workspace, d_indices, capacity, d_count);
+  if (rc)
+    return rc;
+  int device = -1;
+  rc = device_of(d_values, "d_values", &device);
+  if (rc)
+    return rc;
+  DeviceScope scope(device);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", device, hipGetErrorString(scope.status));
+  const PtSelect A = {.values = d_values, .n = (uint64_t)width * (uint64_t)height, .lo = lo, .hi = hi,
+                      .invert = (flags & RT_HIP_SELECT_INVERT) ? 1u : 0u};
+  const hipError_t e = pt_launch_select(A, d_workspace, d_indices, capacity, d_count, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "pt_select launches: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+void rt_hip_pixel_defaults(RtHipPixelParams *params)
+{
+  if (!params)
+    return;
+  memset(params, 0, sizeof *params);
+  params->samples = 1;
+  params->max_depth = 5;
+  params->integrator = RT_HIP_TRACE_PATH;
+}
+
+const char *rt_hip_pixel_kernel_name(const RtHipScene *scene) { return scene ? pt_pixel_kernel_name_of(pt_pixel_pick(scene->view)) : ""; }
+
+int rt_hip_pixel_kernel_count(void) { return pt_pixel_kernel_count(); }
+
+const char *rt_hip_pixel_kernel_launches(int index, uint64_t *launches)
+{
+  if (index < 0 || index >= pt_pixel_kernel_count())
+    return nullptr;
+  if (launches)
+    *launches = pt_pixel_kernel_launches(index);
+  return pt_pixel_kernel_name_of(index);
+}
+
+int rt_hip_trace_pixels(const RtHipScene *scene, const RtHipCamera *camera, const uint32_t *d_pixels, uint64_t n,
+                        const RtHipPixelParams *params, const RtHipRadiance *d_out, uint64_t *d_stats, void *stream)
+{
+  const int rc = check_pixels(camera, d_pixels, n, params, d_out);
+  if (rc)
+    return rc;
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "scene is required");
+  if (n == 0)
+    return RT_HIP_OK;
+  return guarded("rt_hip_trace_pixels",
+                 [&] { return pixels_launch(scene, camera, d_pixels, n, params, d_out, d_stats, static_cast<hipStream_t>(stream)); });
+}
+
+int rt_hip_trace_pixels_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                             const RtHipCamera *camera, const uint32_t *h_pixels, uint64_t n, const RtHipPixelParams *params, int device,
+                             const RtHipRadiance *h_out, uint64_t *h_stats)
+{
+  return guarded("rt_hip_trace_pixels_host", [&] {
+    return trace_pixels_host_impl(spheres, n_spheres, meshes, n_meshes, camera, h_pixels, n, params, device, h_out, h_stats);
+  });
+}
+
+int rt_hip_blend_pixels(const uint32_t *d_pixels, const uint32_t *d_status, const double *d_radiance, uint64_t n, int32_t width,
+                        int32_t height, double new_weight, double prior_scale, const float *d_prior, float *d_rgb, uint8_t *d_rgb8,
+                        float *d_weight, void *stream)
+{
+  int rc = check_blend(d_pixels, d_status, d_radiance, n, width, height, new_weight, prior_scale, d_rgb);
+  if (rc)
+    return rc;
+  int device = -1;
+  rc = device_of(d_rgb, "d_rgb", &device);
+  if (rc || n == 0)
+    return rc;
+  DeviceScope scope(device);
+  if (scope.status != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", device, hipGetErrorString(scope.status));
+  const PtBlend B = {.pixels = d_pixels, .status = d_status, .radiance = d_radiance, .n = n,
+                     .n_pixels = (uint32_t)((uint64_t)width * (uint64_t)height), .new_weight = new_weight, .prior_scale = prior_scale,
+                     .prior = d_prior, .rgb = d_rgb, .rgb8 = d_rgb8, .weight = d_weight};
+  const hipError_t e = pt_launch_blend(B, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "pt_blend_pixels launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
 }
 
 } // extern "C"

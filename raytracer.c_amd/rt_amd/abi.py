@@ -135,6 +135,14 @@ RADIANCE_FIELDS = ("status", "radiance", "samples", "paths", "casts", "ray")   #
 RADIANCE_SHAPES = {"status": ("uint32", 1), "radiance": ("float64", 3), "samples": ("float64", 0), "paths": ("uint64", 1),
                    "casts": ("uint64", 1), "ray": ("float64", 6)}   # dtype, values per ray (samples: 3 per sample)
 
+class RtHipPixelParams(C.Structure):  # rt_hip.h: a pixel refinement's trace (rt_hip_pixel_defaults), 32 B
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("sample_first", C.c_int32),
+                ("max_depth", C.c_int32), ("integrator", C.c_uint32), ("seed", C.c_uint64)]
+
+
+PIXEL_FIELDS = ("status", "radiance", "samples", "paths", "casts")   # what rt_hip_trace_pixels writes of an RtHipRadiance
+SELECT_INVERT = 1                                                    # RT_HIP_SELECT_INVERT
+
 ADAPT_CHECKPOINT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_uint32)  # on_checkpoint(user, samples done, live tiles)
 
 DENOISE_DEMODULATE, DENOISE_OBJECT_EDGES = 1, 2   # RT_HIP_DENOISE_*
@@ -257,6 +265,19 @@ SHIM_SYMBOLS = {
                                   C.POINTER(RtHipUpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_upsample_image": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipAov), C.c_int32, C.c_int32,
                                         C.POINTER(RtHipUpsampleParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_select_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rt_hip_select_pixels": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_hip_pixel_defaults": (None, [C.POINTER(RtHipPixelParams)]),
+    "rt_hip_trace_pixels": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_uint64, C.POINTER(RtHipPixelParams),
+                                      C.POINTER(RtHipRadiance), C.c_void_p, C.c_void_p]),
+    "rt_hip_trace_pixels_host": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.POINTER(Camera), C.c_void_p,
+                                           C.c_uint64, C.POINTER(RtHipPixelParams), C.c_int, C.POINTER(RtHipRadiance), C.c_void_p]),
+    "rt_hip_pixel_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "rt_hip_pixel_kernel_count": (C.c_int, []),
+    "rt_hip_pixel_kernel_launches": (C.c_char_p, [C.c_int, C.POINTER(C.c_uint64)]),
+    "rt_hip_blend_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_render_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t,
                                       C.POINTER(Camera), C.POINTER(RtHipParams), C.c_int, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
@@ -422,6 +443,16 @@ def trace_params(samples, seed, max_depth=None, source=RAYS_GIVEN, normalize=Fal
         p.camera = C.pointer(camera)
     if origin_radius is not None:
         p.origin_radius = origin_radius
+    return p
+
+
+def pixel_params(width, height, samples, seed, sample_first=0, max_depth=None):
+    """rt_hip_pixel_defaults() with the given fields replaced (max_depth None: the default)"""
+    p = RtHipPixelParams()
+    load_shim().rt_hip_pixel_defaults(C.byref(p))
+    p.width, p.height, p.samples, p.sample_first, p.seed = width, height, samples, sample_first, seed
+    if max_depth is not None:
+        p.max_depth = max_depth
     return p
 
 

@@ -292,6 +292,56 @@ class GpuScene:
                              origin_radius, index_first)
         return self._trace(uv, 2, p, want, stats)
 
+    def pixel_kernel_name(self):
+        """the pixel-refinement form this scene's trace_pixels launches take"""
+        return self.shim.rt_hip_pixel_kernel_name(self.handle).decode()
+
+    def trace_pixels(self, pixels, samples, seed, sample_first=0, camera=None, max_depth=None, n=None, want=("status", "radiance"),
+                     stats=None):
+        """render()'s own samples sample_first .. sample_first + samples - 1 of the listed pixels of the scene's frame (rt_hip.h,
+        rt_hip_trace_pixels): pixels the uint32 indices y * width + x (a 32-bit tensor on the scene's device, as select_pixels
+        returns it, or anything numpy takes), n: how many of them to trace (None: all); asynchronous on torch's current stream ->
+        dict of device tensors: status int32 [n], radiance float64 [n, 3], samples [n, samples, 3], paths / casts int64 [n] (want:
+        which), and stats int64 [4] (+= into the tensor given).  camera None: the scene's own; max_depth None: the scene's own."""
+        dev = torch.device("cuda", self.device)
+        pixels = _pixel_tensor(pixels, dev)
+        n = pixels.numel() if n is None else int(n)
+        if n < 0 or n > pixels.numel():
+            raise ValueError("trace_pixels(): n must be within the list")
+        p = abi.pixel_params(self.scene.width, self.scene.height, samples, seed, sample_first,
+                             self.scene.max_depth if max_depth is None else max_depth)
+        out, rad = {}, abi.RtHipRadiance()
+        for f in want:
+            if f not in abi.PIXEL_FIELDS:
+                raise ValueError(f"trace_pixels(): {f!r} is not an output of a pixel refinement")
+            dtype, k = abi.RADIANCE_SHAPES[f]
+            shape = (n, samples, 3) if f == "samples" else ((n, k) if k > 1 else (n,))
+            out[f] = torch.empty(shape, dtype={"float64": torch.float64, "uint32": torch.int32, "uint64": torch.int64}[dtype], device=dev)
+            setattr(rad, f, out[f].data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "wanted")
+        if stats is None:
+            stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._pixel_inputs = pixels   # keep alive until the stream has used them
+        _check(self.shim.rt_hip_trace_pixels(self.handle, C.byref(camera if camera is not None else self.scene.camera),
+                                             C.c_void_p(pixels.data_ptr() if n else None), n, C.byref(p), C.byref(rad),
+                                             C.c_void_p(stats.data_ptr()), C.c_void_p(stream)), "rt_hip_trace_pixels")
+        out["stats"] = stats
+        return out
+
+    def refine(self, rgb, values, lo, hi, samples, seed, sample_first=0, prior=None, prior_scale=0.0, invert=False, camera=None,
+               max_depth=None, rgb8=None, weight=None, stats=None):
+        """Select, trace, blend, on torch's current stream: the pixels of `values` (f32 [H,W]) within [lo, hi] (select_pixels) get
+        `samples` more samples of the render's own from sample_first on (trace_pixels) and are blended into rgb (f32 [H,W,3], in
+        place) with new_weight = samples against prior_scale * prior (blend_pixels; prior_scale 0: replaced).  rgb8, weight: updated
+        at the touched pixels when given.  -> the number of pixels selected (waits for that one word)."""
+        w, h = self.scene.width, self.scene.height
+        idx, count = select_pixels(values, w, h, lo, hi, invert=invert)
+        if count:
+            out = self.trace_pixels(idx, samples, seed, sample_first, camera, max_depth, n=count, stats=stats)
+            blend_pixels(idx, out["status"], out["radiance"], rgb, w, h, float(samples), prior_scale, prior=prior, rgb8=rgb8, weight=weight,
+                         n=count)
+        return count
+
     def render_panorama(self, width, height, origin, samples, seed, max_depth=None):
         """An equirectangular view from `origin` (scene.panorama_rays: no Camera expresses it), `samples` paths per pixel, pixel
         k = y * width + x on the stream (seed, k, s) -> (float64 [height, width, 3] linear radiance on the device, stats)"""
@@ -519,6 +569,88 @@ def denoise(rgb, aov, width, height, out=None, **params):
     return out, out8
 
 
+def _pixel_tensor(pixels, dev):
+    """a list of pixel indices as a contiguous 32-bit tensor on `dev` (the uint32 words of the C-ABI)"""
+    if isinstance(pixels, torch.Tensor):
+        if pixels.element_size() != 4 or pixels.is_floating_point():
+            raise ValueError("pixel indices must be a 32-bit integer tensor (the uint32 words of the C-ABI)")
+        return pixels.to(dev).contiguous().reshape(-1)
+    import numpy as np
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(pixels, dtype=np.uint32).reshape(-1)).view(np.int32)).to(dev)
+
+
+def select_pixels(values, w, h, lo, hi, invert=False, capacity=None, indices=None):
+    """rt_hip_select_pixels on torch's current stream: values f32 of h x w (row-major, contiguous, on a device) -> (indices: an
+    int32 tensor [capacity] holding the uint32 words p = y * w + x of the selected pixels, ascending, in its first min(count, capacity)
+    entries -- the rest is left as it was --, count: how many pixels are selected; reading it back waits for the stream).
+    capacity None: w * h; 0: count only (indices is None).  indices: a tensor to write into."""
+    dev = values.device
+    shim = abi.load_shim()
+    if values.dtype != torch.float32 or not values.is_contiguous() or values.numel() != w * h:
+        raise ValueError("select_pixels(): values must be a contiguous float32 tensor of w * h values")
+    if capacity is None:
+        capacity = indices.numel() if indices is not None else w * h
+    if capacity and indices is None:
+        indices = torch.empty(capacity, dtype=torch.int32, device=dev)
+    if capacity and (indices.device != dev or indices.element_size() != 4 or not indices.is_contiguous() or indices.numel() < capacity):
+        raise ValueError("select_pixels(): indices must be a contiguous 32-bit tensor of at least `capacity` entries on the map's device")
+    ws = torch.empty(max(shim.rt_hip_select_workspace_bytes(w, h), 1), dtype=torch.uint8, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_select_pixels(C.c_void_p(values.data_ptr()), w, h, lo, hi, abi.SELECT_INVERT if invert else 0,
+                                     C.c_void_p(ws.data_ptr()), C.c_void_p(indices.data_ptr()) if capacity else None, capacity,
+                                     C.c_void_p(count.data_ptr()), C.c_void_p(stream)), "rt_hip_select_pixels")
+    return (indices if capacity else None), int(count.cpu().numpy().view("uint32")[0])
+
+
+def blend_pixels(pixels, status, radiance, rgb, w, h, new_weight, prior_scale=0.0, prior=None, rgb8=None, weight=None, n=None):
+    """rt_hip_blend_pixels on torch's current stream: the first n (None: all) entries of pixels (distinct 32-bit indices, as
+    select_pixels gives them) with the status and radiance trace_pixels gave for them go into rgb (f32 of h x w x 3, in place):
+    replaced where prior_scale * prior is not positive and finite, else blended with weight new_weight against it.  prior: f32 of
+    h x w (None: 1.0); rgb8 (u8 of h x w x 3) and weight (f32 of h x w; it may be prior itself) are written at the touched pixels."""
+    dev = rgb.device
+    pixels = _pixel_tensor(pixels, dev)
+    n = pixels.numel() if n is None else int(n)
+    if n < 0 or n > pixels.numel() or status.numel() < n or radiance.numel() < 3 * n:
+        raise ValueError("blend_pixels(): n must be within the list, its status and its radiance")
+    if status.device != dev or status.element_size() != 4 or not status.is_contiguous() or radiance.device != dev or \
+            radiance.dtype != torch.float64 or not radiance.is_contiguous():
+        raise ValueError("blend_pixels(): status (32-bit) and radiance (float64) must be contiguous tensors on the frame's device")
+    if rgb.dtype != torch.float32 or not rgb.is_contiguous() or rgb.numel() != w * h * 3:
+        raise ValueError("blend_pixels(): rgb must be a contiguous float32 tensor of w * h * 3 values")
+    for t, dtype, k, what in ((prior, torch.float32, 1, "prior"), (weight, torch.float32, 1, "weight"), (rgb8, torch.uint8, 3, "rgb8")):
+        if t is not None and (t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != w * h * k):
+            raise ValueError(f"blend_pixels(): {what} must be a contiguous {dtype} tensor of w * h * {k} values on the frame's device")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _check(abi.load_shim().rt_hip_blend_pixels(ptr(pixels) if n else None, ptr(status) if n else None, ptr(radiance) if n else None, n, w, h,
+                                               new_weight, prior_scale, ptr(prior), ptr(rgb), ptr(rgb8), ptr(weight), C.c_void_p(stream)),
+           "rt_hip_blend_pixels")
+    return rgb
+
+
+def trace_pixels_host(scene, pixels, samples, seed, sample_first=0, camera=None, max_depth=None, device=0, want=("status", "radiance")):
+    """rt_hip_trace_pixels_host(): the C hosts' entry point (its own scene and buffers on logical device `device`, synchronous) ->
+    dict of numpy arrays: status uint32 [n], radiance float64 [n, 3], samples [n, samples, 3], paths / casts uint64 [n], and stats"""
+    import numpy as np
+    shim = abi.load_shim()
+    pixels = np.ascontiguousarray(np.asarray(pixels, dtype=np.uint32).reshape(-1))
+    n = pixels.size
+    p = abi.pixel_params(scene.width, scene.height, samples, seed, sample_first, scene.max_depth if max_depth is None else max_depth)
+    out, rad = {}, abi.RtHipRadiance()
+    for f in want:
+        dtype, k = abi.RADIANCE_SHAPES[f]
+        out[f] = np.zeros((n, samples, 3) if f == "samples" else ((n, k) if k > 1 else (n,)), dtype=dtype)
+        setattr(rad, f, out[f].ctypes.data)
+    stats = (C.c_uint64 * abi.NSTATS)()
+    meshes = scene.hip_meshes()
+    _check(shim.rt_hip_trace_pixels_host(scene.objects, scene.n_objects, meshes, scene.n_meshes,
+                                         C.byref(camera if camera is not None else scene.camera), pixels.ctypes.data, n, C.byref(p), device,
+                                         C.byref(rad), stats), "rt_hip_trace_pixels_host")
+    out["stats"] = dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
+    return out
+
+
 REPROJECT_AOV = ("normal", "depth", "object", "hits")   # what rt_hip_reproject reads of a frame and of the history
 
 
@@ -613,11 +745,16 @@ class Temporal:
         """drop the history: the next frame starts from its own samples"""
         self.frames = 0
 
-    def frame(self, camera, seed, samples, max_depth=None, denoise=False, **denoise_params):
+    def frame(self, camera, seed, samples, max_depth=None, denoise=False, fill=None, **denoise_params):
         """Render `samples` per pixel under `camera` (an abi.Camera), reproject and accumulate -> dict of device tensors, valid
         until the next frame(): rgb f32 [H,W,3] (the accumulated image), rgb8 u8 [H,W,3], len f32 [H,W], motion f32
         [H,W,2], aov (the frame's first-hit buffers), and with denoise: denoised / denoised8, rt_hip_denoise of the accumulated
-        image under the frame's buffers (denoise_params: abi.denoise_params' keywords)"""
+        image under the frame's buffers (denoise_params: abi.denoise_params' keywords).
+        fill (None: nothing, the frame is what it was without the argument; or S >= 1): after the reprojection the pixels with
+        0 <= len <= 1 -- disoccluded, or not to be used -- get S more samples of the render's own, from sample `samples` on
+        (GpuScene.refine with prior = len, prior_scale = samples: a pixel of length 1 blends its `samples` samples with the S new
+        ones, a pixel of length 0 is replaced), and their len becomes (len * samples + S) / samples, rounded as rt_hip_blend_pixels'
+        weight and then divided in float32; res["filled"] is how many (the call then waits for that one word)."""
         gs, total = self.gs, self._total
         w, h = gs.scene.width, gs.scene.height
         cur, prev = self._slots[self._cur], self._slots[self._cur ^ 1]
@@ -636,6 +773,19 @@ class Temporal:
         res = reproject(cur["rgb"], cur["aov"], cur["camera"], hist=prev if self.frames else None,
                         out=dict(rgb=cur["rgb"], len=cur["len"], motion=self._motion, rgb8=self._rgb8), **self.params)
         res["aov"] = cur["aov"]
+        if fill is not None:
+            if int(fill) != fill or fill < 1:
+                raise ValueError("frame(): fill must be an integer >= 1")
+            weight = torch.zeros((h, w), dtype=torch.float32, device=cur["len"].device)
+            idx, count = select_pixels(cur["len"], w, h, 0.0, 1.0)
+            if count:
+                out = gs.trace_pixels(idx, int(fill), seed, sample_first=samples, camera=camera, max_depth=max_depth, n=count)
+                blend_pixels(idx, out["status"], out["radiance"], cur["rgb"], w, h, float(fill), float(samples), prior=cur["len"],
+                             rgb8=self._rgb8, weight=weight, n=count)
+                at = idx[:count].long()   # (plumbing: the weights, in samples, back into the length map, in frames)
+                got, flat = weight.view(-1)[at], cur["len"].view(-1)
+                flat[at] = torch.where(got > 0, got / float(samples), flat[at])   # (weight 0: the blend left the pixel untouched)
+            res["filled"] = count
         if denoise:
             res["denoised"], res["denoised8"] = self._denoised(cur, **denoise_params)
         self._cur ^= 1
@@ -749,12 +899,15 @@ class Preview:
     def _denoised(self, rgb, aov, **denoise_params):
         return denoise(rgb, aov, self.low_width, self.low_height, **denoise_params)
 
-    def frame(self, seed, samples, camera=None, denoise=False, **denoise_params):
+    def frame(self, seed, samples, camera=None, denoise=False, fill=None, **denoise_params):
         """Render `samples` per pixel at the low size under `camera` (an abi.Camera; None: the scene's own), the first-hit buffers
         of `samples` camera samples at both sizes, and upsample -> dict of device tensors: rgb f32 [H,W,3], rgb8 u8 [H,W,3], conf
         f32 [H,W] (rt_hip.h: 1 .. 0 guided, 0 plain bilinear, -1 nothing usable), aov (the full-size buffers) and low (dict: rgb
         -- denoised with denoise=True, by rt_hip_denoise under the low buffers with denoise_params, abi.denoise_params' keywords --,
-        noisy: the low frame as rendered, aov)"""
+        noisy: the low frame as rendered, aov).
+        fill (None: nothing, the frame is what it was without the argument; or S >= 1): after the upsampling the pixels with
+        conf <= 0 -- plain bilinear, or nothing -- are REPLACED by the mean of the full-size render's own samples 0 .. S - 1 of them
+        (GpuScene.refine, prior_scale 0), floats and bytes; res["filled"] is how many (the call then waits for that one word)."""
         gs, lo = self.gs, self.low
         w, h, wl, hl = gs.scene.width, gs.scene.height, self.low_width, self.low_height
         total, total_low = n_tiles(w, h), n_tiles(wl, hl)
@@ -767,6 +920,13 @@ class Preview:
         aov = gs.untile_aov(gs.render_aov(seed, samples, 0, 1, total, camera=camera, want=UPSAMPLE_AOV), 0, 1, total)
         res = upsample(rgb, low_aov, wl, hl, aov, w, h, **self.params)
         res.update(aov=aov, low=dict(rgb=rgb, noisy=noisy, aov=low_aov))
+        if fill is not None:
+            if int(fill) != fill or fill < 1:
+                raise ValueError("frame(): fill must be an integer >= 1")
+            if "conf" not in res:
+                raise ValueError("frame(): fill needs the confidence map")
+            res["filled"] = gs.refine(res["rgb"], res["conf"], float("-inf"), 0.0, int(fill), seed, sample_first=0, camera=camera,
+                                      rgb8=res.get("rgb8"))
         return res
 
 
