@@ -29,15 +29,27 @@
 #ifndef PT_MESH_MAX_WAIT
 #define PT_MESH_MAX_WAIT 16
 #endif
-/* rejection rounds per trip for the directions of diffuse hits (pooled kernels) */
+/* PT_DIR_PARK (SWAP kernels), 1 = a lane whose direction sample is still missing after the trip's rounds PARKS its path on the
+ * wave's retry stack and goes idle; idle lanes take parked paths just before the next trips' rounds (see the loop).  0 = the loop
+ * as it was: such a lane keeps its path and sits the next trip's step out.  An A/B knob (make variant, tools/gpu_ab.py). */
+#ifndef PT_DIR_PARK
+#define PT_DIR_PARK 1
+#endif
+/* rejection rounds per trip for the directions of diffuse hits where stragglers are CARRIED (the !SWAP form, the queued body,
+ * PT_DIR_PARK=0) ... */
 #ifndef PT_DIR_ROUNDS
 #define PT_DIR_ROUNDS 4
 #endif
+/* ... and where they PARK: a parked straggler costs its lane nothing, so the thin late rounds go */
+#ifndef PT_DIR_PARK_ROUNDS
+#define PT_DIR_PARK_ROUNDS 2
+#endif
 /* A/B knob (round 4), default off: stop the rounds early when fewer than PT_DIR_MIN_LANES lanes still want a sample (they
- * carry over like the stragglers of the fourth round).  A round is a wave's 44 instructions whoever still needs it and a
- * carried lane costs one lane's share of a trip, so a lane model put the break-even at ~6 lanes and promised -1 %; measured
+ * carry over like the stragglers of the last round, or park).  A round is a wave's 44 instructions whoever still needs it.
+ * Measured on the carrying loop (before PT_DIR_PARK), where a carried lane idles through a whole step and holds up its
+ * pool's tail, against a lane model that priced it at one lane's share of a trip (break-even ~6 lanes, -1 % promised):
  * with 4 / 6 / 8: headline +1.6 / +1.7 / +2.3 %, config 3 +0.6 / +1.3 / +2.8 %, config 5 +2.6 / +2.7 / +3.0 %, config 2 within
- * noise (profiles/r04_dir_min_lanes_ab.txt): a carried lane also holds up its pool's tail.  1 = every round. */
+ * noise (profiles/r04_dir_min_lanes_ab.txt).  Not measured again on the parking loop.  1 = every round. */
 #ifndef PT_DIR_MIN_LANES
 #define PT_DIR_MIN_LANES 1
 #endif
@@ -212,6 +224,10 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
   uint32_t *const qp = q_pix[wave];
 
   uint32_t n_wait = 0; /* SWAP: paths in this wave's waiting list (wave-uniform) */
+  /* PARK: paths that still lack their direction sample after a trip's rounds wait on the RETRY STACK, which grows from the top
+   * of the same 64 entries (entry 63 downwards) while the steppable paths grow from the bottom: n_wait + n_retry <= 64 */
+  constexpr bool PARK = SWAP && PT_DIR_PARK != 0;
+  uint32_t n_retry = 0; /* (wave-uniform) */
   double *const wf = &w_f[SWAP ? wave : 0][0][0];
   uint32_t *const wu = &w_u[SWAP ? wave : 0][0][0];
   PHASE(11); /* prologue: tile_cull, its barrier, the wave's set-up */
@@ -266,14 +282,18 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
       }
       PHASE(6); /* (of the trip's head: idle lanes take waiting paths from the list) */
       uint32_t batch = 0;
-      if (idle != 0 && next_job < pool)
+      /* PARK: the busy lanes' paths go to the bottom of the list and must not reach the retry stack at its top.  The swap looks
+       * at n_wait alone otherwise -- parked retries never hold a primary trip up -- and where it is put off there are more
+       * retries than idle lanes: every idle lane finds work at the second pick-up point below */
+      const bool may_swap = idle != 0 && (!PARK || n_retry <= (uint32_t)__popcll(idle));
+      if (may_swap && next_job < pool)
       { /* (idle lanes are left only when the list is dry: n_wait == 0 here) take the tile's next batch of 64 jobs */
         if (lane == 0)
           batch = atomicAdd(&wg_next_job, 64u);
         batch = (uint32_t)__builtin_amdgcn_readfirstlane((int)batch);
         next_job = batch < pool ? 0u : pool; /* the pool is dry: never ask again */
       }
-      if (idle != 0 && next_job < pool)
+      if (may_swap && next_job < pool)
       {
         /* the swap */
         const unsigned long long bm = __ballot(busy);
@@ -392,8 +412,9 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
         idle = __ballot(!busy);
       }
     }
-    if (__ballot(busy) == 0)
-      break; /* pool dry and every lane drained (an idle lane would have taken a waiting path): the one exit, reached by all lanes together */
+    if (__ballot(busy) == 0 && (!PARK || n_retry == 0u))
+      break; /* pool dry and every lane drained (an idle lane would have taken a waiting path; parked retries are drained by the
+              * idle lanes at the second pick-up point, trip after trip): the one exit, reached by all lanes together */
     const uint32_t *const prim_pairs = (SWAP && FILT_LDS && primary_trip && cull_ok) ? tile_pairs : nullptr;
     PHASE(0); /* the rest of the trip's head: the camera samples of a swap (start_sample) */
 
@@ -476,20 +497,113 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
         step_done = trace_step<1, false, CHECKER, TRIS, FILT_LDS, 0, true, false, FILT_LDS && !GEOM_LDS>(S, P, n_casts, diag_ptr, no_stack, stack_n, &hit, prim_pairs);
     }
     PHASE(3); /* hit record, roulette, material */
+    /* this trip's radiance terms to the pixel sums; a lane whose path ended falls idle.  (PARK: BEFORE the direction block, so
+     * that the lanes whose path ended in this trip's step are idle at the second pick-up point and a lane that parks its path
+     * has nothing left to add; the two blocks do not read what the other writes) */
+    const auto radiance_to_sums = [&]() {
+      if (busy)
+      {
+        /* This trip's radiance terms (emission of a hit that goes on, or what ends the path) go to the
+         * pixel's fixed-point sum at once: integer adds commute and associate, so the sum depends
+         * neither on which lane finishes first nor on how a sample's terms are grouped -- and no
+         * radiance lives in registers from one trip to the next. */
+        if ((int)(P.Ls.x != 0.0) | (int)(P.Ls.y != 0.0) | (int)(P.Ls.z != 0.0))
+        {
+          if (REFR)
+          { /* no bound on a term here: the windowed sums (win_add); a non-finite or oversized term flags the pixel.  (What they cost:
+             * the same kernel adding plain fixed-point terms instead -- wrong for large terms, a timing experiment -- 19.9 against 20.3 ms) */
+            unsigned long long *const pw = &pix_win[__umul24(pix_slot, 3u * PT_WIN_N)];
+            if (P.Ls.x != 0.0 && !win_add(pw, P.Ls.x)) atomicOr(&pix_nan[0], 1ull << pix_slot);
+            if (P.Ls.y != 0.0 && !win_add(pw + PT_WIN_N, P.Ls.y)) atomicOr(&pix_nan[1], 1ull << pix_slot);
+            if (P.Ls.z != 0.0 && !win_add(pw + 2 * PT_WIN_N, P.Ls.z)) atomicOr(&pix_nan[2], 1ull << pix_slot);
+          }
+          else
+          {
+          /* (3 * pix_slot through v_mul_u32_u24: the compiler's v_mul_lo_u32 issues at a quarter of the rate) */
+          unsigned long long *const px = &pix_sum[__umul24(pix_slot, 3u)];
+          atomicAdd(&px[0], fixed_term(P.Ls.x, L.acc_scale));
+          atomicAdd(&px[1], fixed_term(P.Ls.y, L.acc_scale));
+          atomicAdd(&px[2], fixed_term(P.Ls.z, L.acc_scale));
+          /* a NaN term (a ray through a degenerate normal, say) has no integer: flag the pixel, see finish_pixels */
+          if ((int)(P.Ls.x != P.Ls.x) | (int)(P.Ls.y != P.Ls.y) | (int)(P.Ls.z != P.Ls.z))
+          {
+            if (P.Ls.x != P.Ls.x) atomicOr(&pix_nan[0], 1ull << pix_slot);
+            if (P.Ls.y != P.Ls.y) atomicOr(&pix_nan[1], 1ull << pix_slot);
+            if (P.Ls.z != P.Ls.z) atomicOr(&pix_nan[2], 1ull << pix_slot);
+          }
+          }
+        }
+        if (step_done)
+        {
+          busy = false;
+          if (REFR && pend_id != 0xFFu)
+          { /* the sample is complete (its stack is empty): the id goes back */
+            pend_id_give(pend_free[wave], pend_id);
+            pend_id = 0xFFu;
+          }
+        }
+      }
+    };
+    if (PARK)
+    {
+      radiance_to_sums();
+      PHASE(5); /* radiance to the pixel sums */
+    }
     /* ---- directions of diffuse hits: PT_DIR_ROUNDS rejection rounds per trip ----
      * A lane needs 1.91 rounds on average, but a loop that runs until the wave's last lane has
      * its sample takes ~6.2 (the maximum of ~45 geometric variables) at 20 % lane occupancy.
      * Here every lane that needs a direction -- from this trip's hit or still from an earlier
-     * one -- gets PT_DIR_ROUNDS rounds; the ~5 % left without a sample carry on next trip and
-     * skip that trip's step.  A sample depends on its stream alone, not on the trip it is
-     * drawn in.  (No 100-round cap here: a lane that keeps failing simply keeps its turn; the
+     * one -- gets a fixed number of rounds.  Carrying form (!PARK): PT_DIR_ROUNDS = 4 rounds, the ~5 % left without a
+     * sample carry on next trip and skip that trip's step -- 3.84 rounds a trip at 32 % of the lanes on the headline, the
+     * third and fourth for ~10 and ~5 lanes.  Parking form (PARK): PT_DIR_PARK_ROUNDS = 2 rounds, and what is left without a
+     * sample (~27 %) leaves its lane for the retry stack, to be taken up by lanes that are idle at this point of a later
+     * trip: the rounds run fuller and no lane idles through a step.  A sample depends on its stream alone, not on the
+     * trip or the lane it is drawn in.  (No 100-round cap here: a path that keeps failing simply keeps its turn; the
      * reference aborts at 100, probability 1e-32.) */
+    constexpr int DIR_ROUNDS = PARK ? PT_DIR_PARK_ROUNDS : PT_DIR_ROUNDS;
+    if (PARK && n_retry != 0u)
+    {
+      /* ---- the second pick-up point: idle lanes take parked retries (last in, first out) and run this trip's rounds on them ----
+       * Idle here: the lanes whose path ended in this trip's step, and whatever the trip's head left idle.  A path that gets
+       * its sample is steppable in this lane next trip; one that fails again goes back to the stack below. */
+      const unsigned long long idle = __ballot(!busy);
+      if (idle != 0)
+      {
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+        if (!busy && rank < n_retry)
+        {
+          const uint32_t e = 64u - n_retry + rank; /* the stack's top is its lowest entry */
+          P.o = {wf[0 * 64 + e], wf[1 * 64 + e], wf[2 * 64 + e]};
+          P.d = {wf[3 * 64 + e], wf[4 * 64 + e], wf[5 * 64 + e]};
+          P.T = {wf[6 * 64 + e], wf[7 * 64 + e], wf[8 * 64 + e]};
+          P.rng = (uint64_t)__double_as_longlong(wf[9 * 64 + e]);
+          if (CHECKER)
+            hit.dir_scale = wf[(CHECKER ? 10 : 0) * 64 + e];
+          const uint32_t meta = wu[e];
+          hit.dir_slot = wu[64 + e];
+          pix_slot = meta & 63u;
+          hit.need_dir = true;
+          if (REFR)
+          {
+            P.depth = (int)((meta >> 7) & 63u);
+            stack_n = (int)((meta >> 13) & 63u);
+            pend_id = (meta >> 19) & 0xFFu;
+          }
+          else
+            P.depth = (int)(meta >> 7);
+          busy = true;
+        }
+        n_retry -= min((uint32_t)__popcll(idle), n_retry);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
     if (busy && hit.need_dir)
     {
       V3 q;
       double len2;
       bool again = true;
-      for (int round = 0; round < PT_DIR_ROUNDS && again; round++)
+      for (int round = 0; round < DIR_ROUNDS && again; round++)
       {
         DIAG(10, 1);
         DIAG_LANES(11);
@@ -513,49 +627,47 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
         hit.need_dir = false;
       }
     }
-    PHASE(4); /* direction rounds */
-    if (busy)
+    if (PARK)
     {
-      /* This trip's radiance terms (emission of a hit that goes on, or what ends the path) go to the
-       * pixel's fixed-point sum at once: integer adds commute and associate, so the sum depends
-       * neither on which lane finishes first nor on how a sample's terms are grouped -- and no
-       * radiance lives in registers from one trip to the next. */
-      if ((int)(P.Ls.x != 0.0) | (int)(P.Ls.y != 0.0) | (int)(P.Ls.z != 0.0))
+      /* ---- park: a lane still without its sample writes its whole path to the retry stack and goes idle ----
+       * (the entry of the waiting list, need_dir set.)  Rounds 3 and 4 served ~10 and ~5 lanes at a wave's price, and a lane
+       * that carried its path over sat the next trip's step out; a parked path waits in LDS instead and the lane takes a
+       * steppable path, or fresh samples, at the next trip's head.  Where n_wait + n_retry would pass 64 the lanes that do
+       * not fit keep their path and carry it over as before. */
+      const unsigned long long pm = __ballot(busy && hit.need_dir);
+      if (pm != 0)
       {
-        if (REFR)
-        { /* no bound on a term here: the windowed sums (win_add); a non-finite or oversized term flags the pixel.  (What they cost:
-           * the same kernel adding plain fixed-point terms instead -- wrong for large terms, a timing experiment -- 19.9 against 20.3 ms) */
-          unsigned long long *const pw = &pix_win[__umul24(pix_slot, 3u * PT_WIN_N)];
-          if (P.Ls.x != 0.0 && !win_add(pw, P.Ls.x)) atomicOr(&pix_nan[0], 1ull << pix_slot);
-          if (P.Ls.y != 0.0 && !win_add(pw + PT_WIN_N, P.Ls.y)) atomicOr(&pix_nan[1], 1ull << pix_slot);
-          if (P.Ls.z != 0.0 && !win_add(pw + 2 * PT_WIN_N, P.Ls.z)) atomicOr(&pix_nan[2], 1ull << pix_slot);
+        const uint32_t room = 64u - n_wait - n_retry, want = (uint32_t)__popcll(pm);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+#ifdef PT_DIAG
+        if (L.diag_flags & 2u)
+        { /* (slots past the 44 a caller's buffer is known to hold: counted only where the caller says it has them) */
+          DIAG(44, min(want, room));
+          DIAG(45, want - min(want, room));
         }
-        else
+#endif
+        if (busy && hit.need_dir && rank < room)
         {
-        /* (3 * pix_slot through v_mul_u32_u24: the compiler's v_mul_lo_u32 issues at a quarter of the rate) */
-        unsigned long long *const px = &pix_sum[__umul24(pix_slot, 3u)];
-        atomicAdd(&px[0], fixed_term(P.Ls.x, L.acc_scale));
-        atomicAdd(&px[1], fixed_term(P.Ls.y, L.acc_scale));
-        atomicAdd(&px[2], fixed_term(P.Ls.z, L.acc_scale));
-        /* a NaN term (a ray through a degenerate normal, say) has no integer: flag the pixel, see finish_pixels */
-        if ((int)(P.Ls.x != P.Ls.x) | (int)(P.Ls.y != P.Ls.y) | (int)(P.Ls.z != P.Ls.z))
-        {
-          if (P.Ls.x != P.Ls.x) atomicOr(&pix_nan[0], 1ull << pix_slot);
-          if (P.Ls.y != P.Ls.y) atomicOr(&pix_nan[1], 1ull << pix_slot);
-          if (P.Ls.z != P.Ls.z) atomicOr(&pix_nan[2], 1ull << pix_slot);
+          const uint32_t e = 63u - n_retry - rank;
+          wf[0 * 64 + e] = P.o.x; wf[1 * 64 + e] = P.o.y; wf[2 * 64 + e] = P.o.z;
+          wf[3 * 64 + e] = P.d.x; wf[4 * 64 + e] = P.d.y; wf[5 * 64 + e] = P.d.z;
+          wf[6 * 64 + e] = P.T.x; wf[7 * 64 + e] = P.T.y; wf[8 * 64 + e] = P.T.z;
+          wf[9 * 64 + e] = __longlong_as_double((long long)P.rng);
+          if (CHECKER)
+            wf[(CHECKER ? 10 : 0) * 64 + e] = hit.dir_scale;
+          wu[e] = ((uint32_t)P.depth << 7) | 64u | pix_slot | (REFR ? (((uint32_t)stack_n << 13) | (pend_id << 19)) : 0u);
+          wu[64 + e] = hit.dir_slot;
+          hit.need_dir = false;
+          busy = false;
         }
-        }
-      }
-      if (step_done)
-      {
-        busy = false;
-        if (REFR && pend_id != 0xFFu)
-        { /* the sample is complete (its stack is empty): the id goes back */
-          pend_id_give(pend_free[wave], pend_id);
-          pend_id = 0xFFu;
-        }
+        n_retry += min(want, room);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
       }
     }
+    PHASE(4); /* direction rounds */
+    if (!PARK)
+      radiance_to_sums();
     P.Ls = {0, 0, 0};
     PHASE(5); /* radiance to the pixel sums */
   }
