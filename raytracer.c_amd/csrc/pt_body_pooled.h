@@ -286,6 +286,10 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
        * at n_wait alone otherwise -- parked retries never hold a primary trip up -- and where it is put off there are more
        * retries than idle lanes: every idle lane finds work at the second pick-up point below */
       const bool may_swap = idle != 0 && (!PARK || n_retry <= (uint32_t)__popcll(idle));
+#ifdef PT_DIAG
+      if (PARK && (L.diag_flags & 2u) && idle != 0 && next_job < pool && !may_swap)
+        DIAG(46, 1); /* a swap put off: jobs remain and lanes are idle, but the stack holds more retries than there are idle lanes */
+#endif
       if (may_swap && next_job < pool)
       { /* (idle lanes are left only when the list is dry: n_wait == 0 here) take the tile's next batch of 64 jobs */
         if (lane == 0)
@@ -415,6 +419,10 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
     if (__ballot(busy) == 0 && (!PARK || n_retry == 0u))
       break; /* pool dry and every lane drained (an idle lane would have taken a waiting path; parked retries are drained by the
               * idle lanes at the second pick-up point, trip after trip): the one exit, reached by all lanes together */
+#ifdef PT_DIAG
+    if (PARK && (L.diag_flags & 2u) && __ballot(busy) == 0)
+      DIAG(47, 1); /* a dry drain: no lane is busy, and the trip runs for the stack's retries alone */
+#endif
     const uint32_t *const prim_pairs = (SWAP && FILT_LDS && primary_trip && cull_ok) ? tile_pairs : nullptr;
     PHASE(0); /* the rest of the trip's head: the camera samples of a swap (start_sample) */
 
@@ -644,6 +652,8 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
         { /* (slots past the 44 a caller's buffer is known to hold: counted only where the caller says it has them) */
           DIAG(44, min(want, room));
           DIAG(45, want - min(want, room));
+          if (REFR) /* parked with children: the entry's stack_n and pend_id fields carry something */
+            DIAG(48, __popcll(__ballot(busy && hit.need_dir && rank < room && stack_n > 0)));
         }
 #endif
         if (busy && hit.need_dir && rank < room)

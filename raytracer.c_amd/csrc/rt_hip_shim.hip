@@ -1244,7 +1244,7 @@ int launch_prepare(const RtHipScene *scene, const RtHipCamera *camera, const RtH
     { /* the diagnostic build only: walk the rays the probe or the hull rule would not walk, and count any that find a triangle */
       const char *flag = getenv("RT_HIP_DIAG_WALK_REJECTED");
       L.diag_flags = (flag && flag[0] == '1') ? 1u : 0u;
-      /* RT_HIP_DIAG_PARK_COUNTS=1: the caller's counters hold 64 words, not 48: the retry stack's two go to stats[4 + 44], [4 + 45] */
+      /* RT_HIP_DIAG_PARK_COUNTS=1: the caller's counters hold 64 words, not 48: the retry stack's five go to stats[4 + 44] .. [4 + 48] */
       const char *park = getenv("RT_HIP_DIAG_PARK_COUNTS");
       L.diag_flags |= (park && park[0] == '1') ? 2u : 0u;
     }

@@ -11,7 +11,7 @@ if "--json" in sys.argv:
     k = sys.argv.index("--json")
     json_out = sys.argv[k + 1]
     del sys.argv[k:k + 2]
-os.environ["RT_HIP_DIAG_PARK_COUNTS"] = "1"   # the counters below hold 64 words: the retry stack's two are counted (read at every launch)
+os.environ["RT_HIP_DIAG_PARK_COUNTS"] = "1"   # the counters below hold 64 words: the retry stack's five (slots 44-48) are counted (read at every launch)
 import torch
 from rt_amd import gpu as G, scene as S
 cfg = int(sys.argv[1]) if len(sys.argv) > 1 else 4
@@ -36,7 +36,9 @@ names = ["loop iters (wave)", "loop lanes", "phase2 iters (wave)", "phase2 cands
          "small-mesh fp32 pre-tests (lane)", "small-mesh exact triangle iters (wave)", "wall-sized spheres pruned before the exact tests (lane)",
          "camera rays of tiles that cannot see the mesh (no probe)", "filter evaluations (lane x primitive)", "bvh leaf pre-tests (lane)",
          "exact triangle tests (lane)", "mesh probe evaluations (lane)", "exact sphere tests (lane)",
-         "direction retries parked (lane)", "direction retries that found no room (lane)"]
+         "direction retries parked (lane)", "direction retries that found no room (lane)",
+         "swaps put off for the retry stack (wave)", "trips for the retry stack alone (wave)",
+         "direction retries parked with pending second children (lane)"]
 for n, v in zip(names, d):
     print(f"{n:28s} {v:15d}")
 assert d[12] == 0, 'the conservative filter dropped a sphere the exact test accepts'
@@ -64,7 +66,8 @@ if d[34]:
           f"exact triangle wave iterations per trip {d[36] / it:.2f}, exact sphere {(d[2] - d[36]) / it:.2f}")
 print(f"reject iters per loop iter {d[10] / it:.2f} lanes/64 {d[11] / (64.0 * max(d[10], 1)):.3f}")
 print(f"direction retries parked per loop iter {d[44] / it:.2f}, carried for want of room {d[45] / it:.4f} "
-      f"(of the lanes in the rounds: {(d[44] + d[45]) / max(d[11], 1):.3f})")
+      f"(of the lanes in the rounds: {(d[44] + d[45]) / max(d[11], 1):.3f}); swaps put off for the stack {d[46]}, trips for the "
+      f"stack alone {d[47]}, parked with pending second children {d[48]}")
 
 print(f"per ray-bounce: filter evaluations {d[39] / casts:.2f}, exact sphere tests {d[43] / casts:.3f}, exact triangle tests {d[41] / casts:.4f}, "
       f"node visits {d[15] / casts:.3f}, leaf pre-tests {d[40] / casts:.3f}, probes {d[42] / casts:.3f}, rejection rounds {d[11] / casts:.3f}")
