@@ -2563,16 +2563,29 @@ hipError_t pt_launch_aov(const PtLaunch &launch, const PtAovOut &out, hipStream_
   return e;
 }
 
-/* ---- the ray-query kernels: which form a scene takes, and the launch ------------------------------------------------------- */
-int pt_query_pick(const PtSceneView &scene)
+/* ---- the ray kernels (query, radiance query, pixel refinement): which of a list's five geometric forms a scene takes ----------
+ * One decision for the three lists; each gives its own ids (the query list's order differs from the other two's). */
+static int ray_form_pick(const PtSceneView &scene, int rays, int big, int tri, int tri_big, int mem)
 {
   if (!pt_geom_in_lds(scene))
-    return Q_MEM;
+    return mem;
   const bool tris = scene.n_triangles != 0u;
   if (pt_filter_in_lds(scene))
-    return tris ? Q_TRI : Q_RAYS;
-  return tris ? Q_TRI_BIG : Q_BIG;
+    return tris ? tri : rays;
+  return tris ? tri_big : big;
 }
+
+/* every form of the radiance-query and pixel lists pushes pending second children: its pool, as pt_launch_render asks of a
+ * PEND_POOL member */
+static bool pend_pool_ready(const PtLaunch &launch)
+{
+  return launch.pend_ws != nullptr && launch.pend_slots_per_xcd != 0u && launch.pend_entries != 0u &&
+         launch.pend_entries >= pt_pend_entries(launch.scene, 0u, launch.max_depth) &&
+         launch.pend_slot_doubles >= (uint64_t)launch.pend_entries * PT_PEND_FIELDS_HOST * PT_BLOCK;
+}
+
+/* ---- the ray-query kernels: which form a scene takes, and the launch ------------------------------------------------------- */
+int pt_query_pick(const PtSceneView &scene) { return ray_form_pick(scene, Q_RAYS, Q_BIG, Q_TRI, Q_TRI_BIG, Q_MEM); }
 
 const char *pt_query_kernel_name_of(int which) { return pt_query_kernels.name_of(which); }
 int pt_query_kernel_count(void) { return Q_COUNT; }
@@ -2591,15 +2604,7 @@ hipError_t pt_launch_query(const PtLaunch &launch, const PtQuery &query, hipStre
 }
 
 /* ---- the radiance-query kernels: which form a scene takes, and the launch ------------------------------------------------- */
-int pt_trace_pick(const PtSceneView &scene)
-{
-  if (!pt_geom_in_lds(scene))
-    return T_MEM;
-  const bool tris = scene.n_triangles != 0u;
-  if (pt_filter_in_lds(scene))
-    return tris ? T_TRI : T_RAYS;
-  return tris ? T_TRI_BIG : T_BIG;
-}
+int pt_trace_pick(const PtSceneView &scene) { return ray_form_pick(scene, T_RAYS, T_BIG, T_TRI, T_TRI_BIG, T_MEM); }
 
 const char *pt_trace_kernel_name_of(int which) { return pt_trace_kernels.name_of(which); }
 int pt_trace_kernel_count(void) { return T_COUNT; }
@@ -2613,10 +2618,7 @@ hipError_t pt_launch_trace(const PtLaunch &launch, const PtTrace &trace, hipStre
   if (!pt_trace_kernels.valid(which) || trace.n == 0u || trace.n > 0xFFFFFFFFull || (uint64_t)trace.index_first + trace.n > 0x100000000ull ||
       launch.samples < 1)
     return hipErrorInvalidValue;
-  /* every form pushes pending second children: its pool, as pt_launch_render asks of a PEND_POOL member */
-  if (launch.pend_ws == nullptr || launch.pend_slots_per_xcd == 0u || launch.pend_entries == 0u ||
-      launch.pend_entries < pt_pend_entries(launch.scene, 0u, launch.max_depth) ||
-      launch.pend_slot_doubles < (uint64_t)launch.pend_entries * PT_PEND_FIELDS_HOST * PT_BLOCK)
+  if (!pend_pool_ready(launch))
     return hipErrorInvalidValue;
   const size_t lds_bytes = which == T_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the query launch */
   const uint32_t rays_per_wg = PT_BLOCK / PT_SLICES;
@@ -2643,10 +2645,7 @@ hipError_t pt_launch_pixels(const PtLaunch &launch, const PtPixels &pixels, hipS
       (uint64_t)pixels.sample_first + (uint64_t)launch.samples > 0x80000000ull || launch.width < 2 || launch.height < 2 ||
       (uint64_t)launch.width * (uint64_t)launch.height != (uint64_t)pixels.n_pixels)
     return hipErrorInvalidValue;
-  /* every form pushes pending second children: its pool, as pt_launch_trace asks */
-  if (launch.pend_ws == nullptr || launch.pend_slots_per_xcd == 0u || launch.pend_entries == 0u ||
-      launch.pend_entries < pt_pend_entries(launch.scene, 0u, launch.max_depth) ||
-      launch.pend_slot_doubles < (uint64_t)launch.pend_entries * PT_PEND_FIELDS_HOST * PT_BLOCK)
+  if (!pend_pool_ready(launch))
     return hipErrorInvalidValue;
   const size_t lds_bytes = which == P_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the trace launch */
   const uint32_t per_wg = PT_BLOCK / PT_SLICES;

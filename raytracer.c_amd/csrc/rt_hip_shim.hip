@@ -25,6 +25,7 @@
 #include "pt_device.h"
 #include "rt_hip.h"
 #include "bvh_build.h"
+#include "rt_staging.h"
 
 static_assert(sizeof(RtHipSphere) == 88, "RtHipSphere must match the reference Object");
 static_assert(sizeof(RtHipVertex) == 40, "RtHipVertex must match the reference Vertex");
@@ -125,6 +126,56 @@ struct DeviceBuffer
   T *at(size_t byte_offset = 0) const
   {
     return reinterpret_cast<T *>(static_cast<char *>(ptr) + byte_offset);
+  }
+};
+
+/* The one device allocation of a host-array entry point, laid out by StagePlan (rt_staging.h).  A host form declares its parts,
+ * stage()s them -- the allocation, the cleared parts, the uploads, in declared order --, launches on the null stream with at<T>()'s
+ * pointers (null for a part the call does not want) and download()s: the null stream puts those copies after the kernel. */
+struct StageArena
+{
+  StagePlan plan;
+  DeviceBuffer buf;
+  int part(size_t bytes, const void *src = nullptr, void *dst = nullptr, bool wanted = true) { return plan.add(bytes, src, dst, wanted); }
+  int zeroed(size_t bytes, void *dst) { return plan.add(bytes, nullptr, dst, true, true); }
+  template <class T>
+  T *at(int part) const
+  {
+    const size_t off = plan.offset(part);
+    return off == STAGE_ABSENT ? nullptr : buf.at<T>(off);
+  }
+  int stage()
+  {
+    HIP_TRY(buf.alloc(plan.total));
+    for (const StagePart &p : plan.parts)
+    {
+      if (p.zero)
+        HIP_TRY(hipMemset(buf.at<char>(p.offset), 0, p.bytes));
+      if (p.src)
+        HIP_TRY(hipMemcpy(buf.at<char>(p.offset), p.src, p.bytes, hipMemcpyHostToDevice));
+    }
+    return RT_HIP_OK;
+  }
+  int download() const
+  {
+    for (const StagePart &p : plan.parts)
+      if (p.dst)
+        HIP_TRY(hipMemcpy(p.dst, buf.at<char>(p.offset), p.bytes, hipMemcpyDeviceToHost));
+    return RT_HIP_OK;
+  }
+};
+
+/* a scene of a host form's own on a HIP device: destroyed when the scope ends */
+struct OwnedScene
+{
+  RtHipScene *scene = nullptr;
+  OwnedScene() = default;
+  OwnedScene(const OwnedScene &) = delete;
+  OwnedScene &operator=(const OwnedScene &) = delete;
+  ~OwnedScene() { rt_hip_scene_destroy(scene); }
+  int create(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, int device)
+  {
+    return rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, device, &scene);
   }
 };
 
@@ -2055,40 +2106,29 @@ int physical_device(int device, int *phys)
 int aov_image_of(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *h_image)
 {
   DeviceScope scope(scene->device);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", scene->device, hipGetErrorString(scope.status));
+  HIP_TRY(scope.status);
   RtHipParams p = *params;
   whole_image(p);
   const size_t tile_px = (size_t)p.tile_count * PT_TILE_PIXELS, img_px = (size_t)p.width * p.height;
-  /* one allocation: per requested output its tile buffer and its image, words of 4 bytes */
+  /* per requested output its tile buffer and its image, 32-bit words */
   void *host[5] = {h_image->albedo, h_image->normal, h_image->depth, h_image->object, h_image->hits};
-  size_t off[5] = {0, 0, 0, 0, 0}, words = 0;
+  StageArena A;
+  int tp[5], ip[5];
   for (int k = 0; k < 5; k++)
-    if (host[k])
-    {
-      off[k] = words;
-      words += (k < 2 ? 3u : 1u) * (tile_px + img_px);
-    }
-  DeviceBuffer buf;
-  HIP_TRY(buf.alloc(words * 4u));
-  RtHipAov tiles = {}, image = {};
-  void **tp[5] = {(void **)&tiles.albedo, (void **)&tiles.normal, (void **)&tiles.depth, (void **)&tiles.object, (void **)&tiles.hits};
-  void **ip[5] = {(void **)&image.albedo, (void **)&image.normal, (void **)&image.depth, (void **)&image.object, (void **)&image.hits};
-  for (int k = 0; k < 5; k++)
-    if (host[k])
-    {
-      *tp[k] = buf.at<uint32_t>(4u * off[k]);
-      *ip[k] = buf.at<uint32_t>(4u * (off[k] + (k < 2 ? 3u : 1u) * tile_px));
-    }
-  int rc = rt_hip_render_aov_tiles(scene, camera, &p, &tiles, nullptr);
-  if (!rc)
-    rc = rt_hip_untile_aov(&tiles, p.width, p.height, 0, 1, p.tile_count, &image, nullptr);
+  {
+    const size_t px_bytes = (k < 2 ? 3u : 1u) * sizeof(uint32_t);
+    tp[k] = A.part(px_bytes * tile_px, nullptr, nullptr, host[k] != nullptr);
+    ip[k] = A.part(px_bytes * img_px, nullptr, host[k], host[k] != nullptr);
+  }
+  int rc = A.stage();
   if (rc)
     return rc;
-  for (int k = 0; k < 5; k++)
-    if (host[k])
-      HIP_TRY(hipMemcpy(host[k], *ip[k], (k < 2 ? 3u : 1u) * img_px * 4u, hipMemcpyDeviceToHost));
-  return RT_HIP_OK;
+  const RtHipAov tiles = {A.at<float>(tp[0]), A.at<float>(tp[1]), A.at<float>(tp[2]), A.at<uint32_t>(tp[3]), A.at<uint32_t>(tp[4])};
+  const RtHipAov image = {A.at<float>(ip[0]), A.at<float>(ip[1]), A.at<float>(ip[2]), A.at<uint32_t>(ip[3]), A.at<uint32_t>(ip[4])};
+  rc = rt_hip_render_aov_tiles(scene, camera, &p, &tiles, nullptr);
+  if (!rc)
+    rc = rt_hip_untile_aov(&tiles, p.width, p.height, 0, 1, p.tile_count, &image, nullptr);
+  return rc ? rc : A.download();
 }
 
 /* ... with a scene of its own on the logical device */
@@ -2106,33 +2146,29 @@ int render_aov_image_impl(const RtHipSphere *spheres, size_t n_spheres, const Rt
   rc = physical_device(device, &phys);
   if (rc)
     return rc;
-  RtHipScene *scene = nullptr;
-  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &scene);
-  if (rc)
-    return rc;
-  rc = aov_image_of(scene, camera, params, h_image);
-  rt_hip_scene_destroy(scene);
-  return rc;
+  OwnedScene own;
+  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
+  return rc ? rc : aov_image_of(own.scene, camera, params, h_image);
 }
 
 /* ---- the denoiser (rt_hip.h, rt_hip_denoise_*) ------------------------------------------------------------------------------
  * Workspace layout for n = w*h pixels, each part 256-B aligned: e[0], e[1] and the guidance (16 B per pixel each), then hits +
  * object (8 B per pixel).  The kernels and their arithmetic are pt_denoise_* in pt_kernel.hip. */
-size_t align256(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
-
-bool denoise_size_ok(int32_t width, int32_t height)
+/* a frame of the image-space calls: both sides in [min_side, 2^20], fewer than 2^32 pixels */
+bool frame_size_ok(int32_t width, int32_t height, int32_t min_side)
 {
-  return width >= 1 && height >= 1 && width <= (1 << 20) && height <= (1 << 20) && (uint64_t)width * (uint64_t)height <= 0xFFFFFFFFull;
+  return width >= min_side && height >= min_side && width <= (1 << 20) && height <= (1 << 20) &&
+         (uint64_t)width * (uint64_t)height <= 0xFFFFFFFFull;
 }
 
-size_t denoise_ws_bytes(size_t n) { return 3u * align256(16u * n) + align256(8u * n); }
+size_t denoise_ws_bytes(size_t n) { return 3u * stage_align(16u * n) + stage_align(8u * n); }
 
 int check_denoise(const float *rgb, const RtHipAov *aov, int32_t width, int32_t height, const RtHipDenoiseParams *p, const void *out_rgb,
                   const void *out_rgb8)
 {
   if (!p)
     return fail(RT_HIP_EINVAL, "params is NULL");
-  if (!denoise_size_ok(width, height))
+  if (!frame_size_ok(width, height, 1))
     return fail(RT_HIP_EINVAL, "width and height must be in [1, 2^20] with fewer than 2^32 pixels");
   if (p->iterations < 0 || p->iterations > 10)
     return fail(RT_HIP_EINVAL, "iterations must be in [0, 10]");
@@ -2159,7 +2195,7 @@ int check_denoise(const float *rgb, const RtHipAov *aov, int32_t width, int32_t 
 int denoise_launch(const float *rgb, const RtHipAov *aov, int32_t width, int32_t height, const RtHipDenoiseParams *p, void *ws,
                    float *out_rgb, uint8_t *out_rgb8, hipStream_t stream)
 {
-  const size_t n = (size_t)width * (size_t)height, part = align256(16u * n);
+  const size_t n = (size_t)width * (size_t)height, part = stage_align(16u * n);
   char *w = static_cast<char *>(ws);
   PtDenoise D = {};
   D.rgb = rgb;
@@ -2197,52 +2233,30 @@ int denoise_image_impl(const float *h_rgb, const RtHipAov *h_aov, int32_t width,
   if (rc)
     return rc;
   DeviceScope scope(phys);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", phys, hipGetErrorString(scope.status));
+  HIP_TRY(scope.status);
   const size_t n = (size_t)width * (size_t)height;
   const bool demod = (params->flags & RT_HIP_DENOISE_DEMODULATE) != 0, edges = (params->flags & RT_HIP_DENOISE_OBJECT_EDGES) != 0;
-  /* one allocation: the workspace, then colour (in and out: in place), albedo, normal, depth, hits, object, bytes */
-  const size_t ws = denoise_ws_bytes(n), b3 = align256(12u * n), b1 = align256(4u * n);
-  DeviceBuffer buf;
-  HIP_TRY(buf.alloc(ws + b3 * (demod ? 3u : 2u) + b1 * (edges ? 3u : 2u) + align256(3u * n)));
-  size_t at = ws;
-  auto part = [&](size_t bytes) { /* the next `bytes` of the allocation */
-    at += bytes;
-    return at - bytes;
-  };
-  float *rgb = buf.at<float>(part(b3));
-  RtHipAov d = {};
-  if (demod)
-    d.albedo = buf.at<float>(part(b3));
-  d.normal = buf.at<float>(part(b3));
-  d.depth = buf.at<float>(part(b1));
-  d.hits = buf.at<uint32_t>(part(b1));
-  if (edges)
-    d.object = buf.at<uint32_t>(part(b1));
-  uint8_t *rgb8 = buf.at<uint8_t>(at);
-  const std::pair<void *, const void *> in[6] = {{rgb, h_rgb}, {d.albedo, h_aov->albedo}, {d.normal, h_aov->normal},
-                                                 {d.depth, h_aov->depth}, {d.hits, h_aov->hits}, {d.object, h_aov->object}};
-  const size_t bytes[6] = {12u * n, 12u * n, 12u * n, 4u * n, 4u * n, 4u * n};
-  for (int k = 0; k < 6; k++)
-    if (in[k].first)
-      HIP_TRY(hipMemcpy(in[k].first, in[k].second, bytes[k], hipMemcpyHostToDevice));
-  rc = denoise_launch(rgb, &d, width, height, params, buf.ptr, h_out ? rgb : nullptr, h_out8 ? rgb8 : nullptr, nullptr);
+  /* the workspace, the colour (in and out: the floats are filtered in place), the buffers the flags ask for, the bytes */
+  StageArena A;
+  const int ws = A.part(denoise_ws_bytes(n));
+  const int rgb = A.part(12u * n, h_rgb, h_out);
+  const int albedo = A.part(12u * n, h_aov->albedo, nullptr, demod);
+  const int normal = A.part(12u * n, h_aov->normal);
+  const int depth = A.part(4u * n, h_aov->depth);
+  const int hits = A.part(4u * n, h_aov->hits);
+  const int object = A.part(4u * n, h_aov->object, nullptr, edges);
+  const int rgb8 = A.part(3u * n, nullptr, h_out8, h_out8 != nullptr);
+  rc = A.stage();
   if (rc)
     return rc;
-  if (h_out)
-    HIP_TRY(hipMemcpy(h_out, rgb, 12u * n, hipMemcpyDeviceToHost));
-  if (h_out8)
-    HIP_TRY(hipMemcpy(h_out8, rgb8, 3u * n, hipMemcpyDeviceToHost));
-  return RT_HIP_OK;
+  const RtHipAov d = {A.at<float>(albedo), A.at<float>(normal), A.at<float>(depth), A.at<uint32_t>(object), A.at<uint32_t>(hits)};
+  rc = denoise_launch(A.at<float>(rgb), &d, width, height, params, A.at<char>(ws), h_out ? A.at<float>(rgb) : nullptr, A.at<uint8_t>(rgb8),
+                      nullptr);
+  return rc ? rc : A.download();
 }
 
 /* ---- temporal reprojection (rt_hip.h, rt_hip_reproject*) ---------------------------------------------------------------------
  * One launch of pt_reproject (pt_kernel.hip), no workspace.  The arguments that need no device are checked first. */
-bool reproject_size_ok(int32_t width, int32_t height)
-{
-  return width >= 2 && height >= 2 && width <= (1 << 20) && height <= (1 << 20) && (uint64_t)width * (uint64_t)height <= 0xFFFFFFFFull;
-}
-
 bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
 {
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
@@ -2256,7 +2270,7 @@ int check_reproject(const float *rgb, const RtHipAov *aov, const RtHipCamera *ca
 {
   if (!p)
     return fail(RT_HIP_EINVAL, "params is NULL");
-  if (!reproject_size_ok(width, height))
+  if (!frame_size_ok(width, height, 2))
     return fail(RT_HIP_EINVAL, "width and height must be in [2, 2^20] with fewer than 2^32 pixels");
   if (p->flags != 0u)
     return fail(RT_HIP_EINVAL, "unknown reproject flags 0x%x", p->flags);
@@ -2367,53 +2381,38 @@ int reproject_image_impl(const float *h_rgb, const RtHipAov *h_aov, const RtHipC
   if (rc)
     return rc;
   DeviceScope scope(phys);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", phys, hipGetErrorString(scope.status));
+  HIP_TRY(scope.status);
   const size_t n = (size_t)width * (size_t)height;
   const bool hist = h_hist_rgb != nullptr;
-  /* one allocation: per image colour (in and out: in place), normal, depth, hits, object; then length, motion, bytes */
-  const size_t b3 = align256(12u * n), b2 = align256(8u * n), b1 = align256(4u * n);
-  const size_t image = 2u * b3 + 3u * b1;
-  DeviceBuffer buf;
-  HIP_TRY(buf.alloc((hist ? 2u : 1u) * image + (hist ? 2u : 1u) * b1 + b2 + align256(3u * n)));
-  size_t at = 0;
-  auto part = [&](size_t bytes) { /* the next `bytes` of the allocation */
-    at += bytes;
-    return at - bytes;
-  };
-  float *d_rgb[2] = {nullptr, nullptr}, *d_len[2] = {nullptr, nullptr};
-  RtHipAov d_aov[2] = {};
+  /* per image -- the frame, then the history if there is one -- colour, normal, depth, hits, object and length: the frame's colour
+   * and length are the outputs (the colour in place); then motion and bytes */
+  const RtHipAov none = {};
   const float *src_rgb[2] = {h_rgb, h_hist_rgb};
-  const RtHipAov *src_aov[2] = {h_aov, h_hist_aov};
-  for (int f = 0; f < (hist ? 2 : 1); f++)
+  const RtHipAov *src_aov[2] = {h_aov, hist ? h_hist_aov : &none};
+  StageArena A;
+  int rgb[2], normal[2], depth[2], hits[2], object[2], len[2];
+  for (int f = 0; f < 2; f++)
   {
-    d_rgb[f] = buf.at<float>(part(b3));
-    d_aov[f].normal = buf.at<float>(part(b3));
-    d_aov[f].depth = buf.at<float>(part(b1));
-    d_aov[f].hits = buf.at<uint32_t>(part(b1));
-    d_aov[f].object = buf.at<uint32_t>(part(b1));
-    d_len[f] = buf.at<float>(part(b1));
-    HIP_TRY(hipMemcpy(d_rgb[f], src_rgb[f], 12u * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aov[f].normal, src_aov[f]->normal, 12u * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aov[f].depth, src_aov[f]->depth, 4u * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aov[f].hits, src_aov[f]->hits, 4u * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aov[f].object, src_aov[f]->object, 4u * n, hipMemcpyHostToDevice));
+    const bool have = f == 0 || hist;
+    rgb[f] = A.part(12u * n, src_rgb[f], f == 0 ? h_out_rgb : nullptr, have);
+    normal[f] = A.part(12u * n, src_aov[f]->normal, nullptr, have);
+    depth[f] = A.part(4u * n, src_aov[f]->depth, nullptr, have);
+    hits[f] = A.part(4u * n, src_aov[f]->hits, nullptr, have);
+    object[f] = A.part(4u * n, src_aov[f]->object, nullptr, have);
+    len[f] = A.part(4u * n, f == 0 ? nullptr : h_hist_len, f == 0 ? h_out_len : nullptr, have);
   }
-  if (hist)
-    HIP_TRY(hipMemcpy(d_len[1], h_hist_len, 4u * n, hipMemcpyHostToDevice));
-  float *d_motion = buf.at<float>(part(b2));
-  uint8_t *d_rgb8 = buf.at<uint8_t>(part(align256(3u * n)));
-  rc = reproject_launch(d_rgb[0], &d_aov[0], camera, d_rgb[1], d_len[1], hist ? &d_aov[1] : nullptr, hist_camera, width, height, params,
-                        d_rgb[0], h_out_rgb8 ? d_rgb8 : nullptr, d_len[0], h_out_motion ? d_motion : nullptr, nullptr);
+  const int motion = A.part(8u * n, nullptr, h_out_motion, h_out_motion != nullptr);
+  const int rgb8 = A.part(3u * n, nullptr, h_out_rgb8, h_out_rgb8 != nullptr);
+  rc = A.stage();
   if (rc)
     return rc;
-  HIP_TRY(hipMemcpy(h_out_rgb, d_rgb[0], 12u * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h_out_len, d_len[0], 4u * n, hipMemcpyDeviceToHost));
-  if (h_out_rgb8)
-    HIP_TRY(hipMemcpy(h_out_rgb8, d_rgb8, 3u * n, hipMemcpyDeviceToHost));
-  if (h_out_motion)
-    HIP_TRY(hipMemcpy(h_out_motion, d_motion, 8u * n, hipMemcpyDeviceToHost));
-  return RT_HIP_OK;
+  RtHipAov d_aov[2];
+  for (int f = 0; f < 2; f++)
+    d_aov[f] = {nullptr, A.at<float>(normal[f]), A.at<float>(depth[f]), A.at<uint32_t>(object[f]), A.at<uint32_t>(hits[f])};
+  rc = reproject_launch(A.at<float>(rgb[0]), &d_aov[0], camera, A.at<float>(rgb[1]), A.at<float>(len[1]), hist ? &d_aov[1] : nullptr,
+                        hist_camera, width, height, params, A.at<float>(rgb[0]), A.at<uint8_t>(rgb8), A.at<float>(len[0]),
+                        A.at<float>(motion), nullptr);
+  return rc ? rc : A.download();
 }
 
 /* ---- guided upsampling (rt_hip.h, rt_hip_upsample*) ---------------------------------------------------------------------------
@@ -2424,7 +2423,7 @@ int check_upsample(const float *low_rgb, const RtHipAov *low_aov, int32_t low_wi
 {
   if (!p)
     return fail(RT_HIP_EINVAL, "params is NULL");
-  if (!reproject_size_ok(width, height) || !reproject_size_ok(low_width, low_height))
+  if (!frame_size_ok(width, height, 2) || !frame_size_ok(low_width, low_height, 2))
     return fail(RT_HIP_EINVAL, "the widths and heights must be in [2, 2^20] with fewer than 2^32 pixels per frame");
   if (p->flags & ~(uint32_t)(RT_HIP_UPSAMPLE_DEMODULATE | RT_HIP_UPSAMPLE_OBJECT_EDGES))
     return fail(RT_HIP_EINVAL, "unknown upsample flags 0x%x", p->flags);
@@ -2518,55 +2517,35 @@ int upsample_image_impl(const float *h_low_rgb, const RtHipAov *h_low_aov, int32
   if (rc)
     return rc;
   DeviceScope scope(phys);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", phys, hipGetErrorString(scope.status));
+  HIP_TRY(scope.status);
   const bool demod = (params->flags & RT_HIP_UPSAMPLE_DEMODULATE) != 0u, edges = (params->flags & RT_HIP_UPSAMPLE_OBJECT_EDGES) != 0u;
   const size_t count[2] = {(size_t)low_width * (size_t)low_height, (size_t)width * (size_t)height};
-  /* one allocation: per frame albedo, normal, depth, hits, object; then the low colour, the result, the confidence, the bytes */
-  size_t total = 0;
-  for (size_t n : count)
-    total += 2u * align256(12u * n) + 3u * align256(4u * n);
-  total += align256(12u * count[0]) + align256(12u * count[1]) + align256(4u * count[1]) + align256(3u * count[1]);
-  DeviceBuffer buf;
-  HIP_TRY(buf.alloc(total));
-  size_t at = 0;
-  auto part = [&](size_t bytes) { /* the next `bytes` of the allocation */
-    at += align256(bytes);
-    return at - align256(bytes);
-  };
-  RtHipAov d_aov[2] = {};
+  /* per frame -- low, then full -- the buffers the flags ask for; then the low colour, the result, the confidence, the bytes */
   const RtHipAov *src[2] = {h_low_aov, h_aov};
+  StageArena A;
+  int albedo[2], normal[2], depth[2], hits[2], object[2];
   for (int f = 0; f < 2; f++)
   {
     const size_t n = count[f];
-    d_aov[f].albedo = buf.at<float>(part(12u * n));
-    d_aov[f].normal = buf.at<float>(part(12u * n));
-    d_aov[f].depth = buf.at<float>(part(4u * n));
-    d_aov[f].hits = buf.at<uint32_t>(part(4u * n));
-    d_aov[f].object = buf.at<uint32_t>(part(4u * n));
-    if (demod)
-      HIP_TRY(hipMemcpy(d_aov[f].albedo, src[f]->albedo, 12u * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aov[f].normal, src[f]->normal, 12u * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aov[f].depth, src[f]->depth, 4u * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aov[f].hits, src[f]->hits, 4u * n, hipMemcpyHostToDevice));
-    if (edges)
-      HIP_TRY(hipMemcpy(d_aov[f].object, src[f]->object, 4u * n, hipMemcpyHostToDevice));
+    albedo[f] = A.part(12u * n, src[f]->albedo, nullptr, demod);
+    normal[f] = A.part(12u * n, src[f]->normal);
+    depth[f] = A.part(4u * n, src[f]->depth);
+    hits[f] = A.part(4u * n, src[f]->hits);
+    object[f] = A.part(4u * n, src[f]->object, nullptr, edges);
   }
-  float *d_low_rgb = buf.at<float>(part(12u * count[0]));
-  float *d_out = buf.at<float>(part(12u * count[1]));
-  float *d_conf = buf.at<float>(part(4u * count[1]));
-  uint8_t *d_rgb8 = buf.at<uint8_t>(part(3u * count[1]));
-  HIP_TRY(hipMemcpy(d_low_rgb, h_low_rgb, 12u * count[0], hipMemcpyHostToDevice));
-  rc = upsample_launch(d_low_rgb, &d_aov[0], low_width, low_height, &d_aov[1], width, height, params, d_out, h_out_rgb8 ? d_rgb8 : nullptr,
-                       h_out_conf ? d_conf : nullptr, nullptr);
+  const int low_rgb = A.part(12u * count[0], h_low_rgb);
+  const int out = A.part(12u * count[1], nullptr, h_out_rgb);
+  const int conf = A.part(4u * count[1], nullptr, h_out_conf, h_out_conf != nullptr);
+  const int rgb8 = A.part(3u * count[1], nullptr, h_out_rgb8, h_out_rgb8 != nullptr);
+  rc = A.stage();
   if (rc)
     return rc;
-  HIP_TRY(hipMemcpy(h_out_rgb, d_out, 12u * count[1], hipMemcpyDeviceToHost));
-  if (h_out_rgb8)
-    HIP_TRY(hipMemcpy(h_out_rgb8, d_rgb8, 3u * count[1], hipMemcpyDeviceToHost));
-  if (h_out_conf)
-    HIP_TRY(hipMemcpy(h_out_conf, d_conf, 4u * count[1], hipMemcpyDeviceToHost));
-  return RT_HIP_OK;
+  RtHipAov d_aov[2];
+  for (int f = 0; f < 2; f++)
+    d_aov[f] = {A.at<float>(albedo[f]), A.at<float>(normal[f]), A.at<float>(depth[f]), A.at<uint32_t>(object[f]), A.at<uint32_t>(hits[f])};
+  rc = upsample_launch(A.at<float>(low_rgb), &d_aov[0], low_width, low_height, &d_aov[1], width, height, params, A.at<float>(out),
+                       A.at<uint8_t>(rgb8), A.at<float>(conf), nullptr);
+  return rc ? rc : A.download();
 }
 
 /* ---- ray queries (rt_hip.h, rt_hip_query_*) ---------------------------------------------------------------------------------
@@ -2617,12 +2596,7 @@ int ray_launch_prepare(const RtHipScene *scene, uint32_t source, const RtHipCame
   memset(&L, 0, sizeof L);
   L.scene = scene->view;
   if (source == RT_HIP_RAYS_CAMERA_UV)
-  {
-    memcpy(L.cam.pos, camera->position, sizeof L.cam.pos);
-    memcpy(L.cam.horizontal, camera->horizontal, sizeof L.cam.horizontal);
-    memcpy(L.cam.vertical, camera->vertical, sizeof L.cam.vertical);
-    memcpy(L.cam.llc, camera->lower_left_corner, sizeof L.cam.llc);
-  }
+    camera_of(camera, L.cam);
   L.near_R = 1.5 * (origin_radius + scene->reach) + 1.0;
   if (!(L.near_R < RT_NEAR_R_LIMIT))
     return fail(RT_HIP_EINVAL, "origin_radius and scene extent give near_R = %g: not a usable finite bound", L.near_R);
@@ -2635,11 +2609,30 @@ int ray_launch_prepare(const RtHipScene *scene, uint32_t source, const RtHipCame
   return RT_HIP_OK;
 }
 
+/* One launch of a kernel that reads a scene's camera-dependent tables (an AOV, a query, a radiance query, a pixel refinement): the
+ * scene's device made current, the tables for L.near_R acquired on `stream`, `launch` (-> hipError_t) run, the tables released, a
+ * failure named after the kernel */
+template <class Launch>
+int launch_with_tables(const RtHipScene *scene, PtLaunch &L, hipStream_t stream, const char *kernel, Launch launch)
+{
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  size_t slot = 0;
+  const int rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
+  if (rc)
+    return rc;
+  const hipError_t e = launch();
+  release_tables(scene, slot, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "%s launch: %s", kernel, hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
 int query_launch(const RtHipScene *scene, const double *d_rays, const double *d_t_max, uint64_t n, const RtHipQueryParams *p,
                  const RtHipHits *d_hits, hipStream_t stream)
 {
   PtLaunch L;
-  int rc = ray_launch_prepare(scene, p->source, p->camera, p->origin_radius, L);
+  const int rc = ray_launch_prepare(scene, p->source, p->camera, p->origin_radius, L);
   if (rc)
     return rc;
   const PtQuery Q = {.rays = d_rays, .t_max = d_t_max, .n = n, .camera_uv = p->source == RT_HIP_RAYS_CAMERA_UV ? 1u : 0u,
@@ -2647,17 +2640,7 @@ int query_launch(const RtHipScene *scene, const double *d_rays, const double *d_
                      .object = d_hits->object, .prim = d_hits->prim, .point = d_hits->point, .normal = d_hits->normal,
                      .bary = d_hits->bary, .ray = d_hits->ray};
   const int which = pt_query_pick(scene->view);
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  size_t slot = 0;
-  rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
-  if (rc)
-    return rc;
-  const hipError_t e = pt_launch_query(L, Q, stream, which);
-  release_tables(scene, slot, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_query_kernel_name_of(which), hipGetErrorString(e));
-  return RT_HIP_OK;
+  return launch_with_tables(scene, L, stream, pt_query_kernel_name_of(which), [&] { return pt_launch_query(L, Q, stream, which); });
 }
 
 /* rt_hip_query_rays_host: a scene of its own on the logical device, one allocation for the rays, the limits and the requested
@@ -2674,46 +2657,27 @@ int query_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtH
     return rc;
   if (n == 0)
     return RT_HIP_OK;
-  struct SceneOwner
-  {
-    RtHipScene *scene = nullptr;
-    ~SceneOwner() { rt_hip_scene_destroy(scene); }
-  } own;
-  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &own.scene);
+  OwnedScene own;
+  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
   if (rc)
     return rc;
   DeviceScope scope(phys);
   HIP_TRY(scope.status);
-  const size_t ray_doubles = params->source == RT_HIP_RAYS_CAMERA_UV ? 2u : 6u;
   void *host[8] = {h_hits->status, h_hits->t, h_hits->object, h_hits->prim, h_hits->point, h_hits->normal, h_hits->bary, h_hits->ray};
   const size_t bytes_per_ray[8] = {4, 8, 4, 4, 24, 24, 16, 48};
-  size_t off[8], total = align256(ray_doubles * 8u * n);
-  const size_t off_tmax = total;
-  if (h_t_max)
-    total += align256(8u * n);
+  StageArena A;
+  const int rays = A.part((params->source == RT_HIP_RAYS_CAMERA_UV ? 16u : 48u) * n, h_rays);
+  const int t_max = A.part(8u * n, h_t_max, nullptr, h_t_max != nullptr);
+  int out[8];
   for (int k = 0; k < 8; k++)
-  {
-    off[k] = total;
-    if (host[k])
-      total += align256(bytes_per_ray[k] * n);
-  }
-  DeviceBuffer buf;
-  HIP_TRY(buf.alloc(total));
-  HIP_TRY(hipMemcpy(buf.ptr, h_rays, ray_doubles * 8u * n, hipMemcpyHostToDevice));
-  if (h_t_max)
-    HIP_TRY(hipMemcpy(buf.at<char>(off_tmax), h_t_max, 8u * n, hipMemcpyHostToDevice));
-  void *dev[8];
-  for (int k = 0; k < 8; k++)
-    dev[k] = host[k] ? buf.at<char>(off[k]) : nullptr;
-  const RtHipHits d_hits = {(uint32_t *)dev[0], (double *)dev[1], (uint32_t *)dev[2], (uint32_t *)dev[3],
-                            (double *)dev[4],   (double *)dev[5], (double *)dev[6],   (double *)dev[7]};
-  rc = query_launch(own.scene, buf.at<double>(), h_t_max ? buf.at<double>(off_tmax) : nullptr, n, params, &d_hits, nullptr);
+    out[k] = A.part(bytes_per_ray[k] * n, nullptr, host[k], host[k] != nullptr);
+  rc = A.stage();
   if (rc)
     return rc;
-  for (int k = 0; k < 8; k++)
-    if (host[k])
-      HIP_TRY(hipMemcpy(host[k], dev[k], bytes_per_ray[k] * n, hipMemcpyDeviceToHost)); /* (null stream: after the kernel) */
-  return RT_HIP_OK;
+  const RtHipHits d_hits = {A.at<uint32_t>(out[0]), A.at<double>(out[1]), A.at<uint32_t>(out[2]), A.at<uint32_t>(out[3]),
+                            A.at<double>(out[4]),   A.at<double>(out[5]), A.at<double>(out[6]),   A.at<double>(out[7])};
+  rc = query_launch(own.scene, A.at<double>(rays), A.at<double>(t_max), n, params, &d_hits, nullptr);
+  return rc ? rc : A.download();
 }
 
 /* ---- radiance queries (rt_hip.h, rt_hip_trace_*) ------------------------------------------------------------------------------
@@ -2746,48 +2710,86 @@ int check_trace(const void *rays, bool device_rays, uint64_t n, const RtHipTrace
   return check_rays(rays, device_rays, n, p->source, p->flags, p->camera, p->origin_radius);
 }
 
+/* What a radiance query's and a pixel refinement's launch start from: the depth limit of the fixed pending-ray stack, a query's
+ * launch (ray_launch_prepare), and the path tracer's own fields */
+int pooled_launch_prepare(const RtHipScene *scene, uint32_t source, const RtHipCamera *camera, double origin_radius, int32_t samples,
+                          int32_t max_depth, uint64_t seed, uint64_t *d_stats, PtLaunch &L)
+{
+  if (scene->view.any_refract && max_depth > PT_REFRACT_MAX_DEPTH)
+    return fail(RT_HIP_ELIMIT, "scenes with M_REFRACTION materials support max_depth <= %d (two rays per refractive hit, "
+                               "raytracer.c:523-529; the pending-ray stack is fixed)", PT_REFRACT_MAX_DEPTH);
+  const int rc = ray_launch_prepare(scene, source, camera, origin_radius, L);
+  if (rc)
+    return rc;
+  L.samples = samples;
+  L.max_depth = max_depth;
+  L.seed = seed;
+  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
+  return RT_HIP_OK;
+}
+
+/* ... and how they are launched: launch_with_tables with the device's status word, and its slot pool of pending-ray stacks held
+ * under g_pend_mutex from the lookup until `launch` has enqueued the kernel */
+template <class Launch>
+int pooled_launch(const RtHipScene *scene, PtLaunch &L, hipStream_t stream, const char *kernel, Launch launch)
+{
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  int rc = status_word_for(scene->device, &L.status);
+  if (rc)
+    return rc;
+  int pool_rc = RT_HIP_OK;
+  rc = launch_with_tables(scene, L, stream, kernel, [&] {
+    std::lock_guard<std::mutex> pend_lock(g_pend_mutex);
+    pool_rc = pend_pool_for(scene->device, pt_pend_entries(scene->view, 0u, L.max_depth), PT_PEND_COLUMNS, L);
+    return pool_rc ? hipSuccess : launch();
+  });
+  return pool_rc ? pool_rc : rc;
+}
+
 int trace_launch(const RtHipScene *scene, const double *d_rays, uint64_t n, const RtHipTraceParams *p, const RtHipRadiance *d_out,
                  uint64_t *d_stats, hipStream_t stream)
 {
-  if (scene->view.any_refract && p->max_depth > PT_REFRACT_MAX_DEPTH)
-    return fail(RT_HIP_ELIMIT, "scenes with M_REFRACTION materials support max_depth <= %d (two rays per refractive hit, "
-                               "raytracer.c:523-529; the pending-ray stack is fixed)", PT_REFRACT_MAX_DEPTH);
   PtLaunch L;
-  int rc = ray_launch_prepare(scene, p->source, p->camera, p->origin_radius, L);
+  const int rc = pooled_launch_prepare(scene, p->source, p->camera, p->origin_radius, p->samples, p->max_depth, p->seed, d_stats, L);
   if (rc)
     return rc;
-  L.samples = p->samples;
-  L.max_depth = p->max_depth;
-  L.seed = p->seed;
-  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
   const PtTrace T = {.rays = d_rays, .n = n, .camera_uv = p->source == RT_HIP_RAYS_CAMERA_UV ? 1u : 0u,
                      .normalize = (p->flags & RT_HIP_RAYS_NORMALIZE) ? 1u : 0u, .index_first = p->index_first, .status = d_out->status,
                      .radiance = d_out->radiance, .samples = d_out->samples, .paths = reinterpret_cast<unsigned long long *>(d_out->paths),
                      .casts = reinterpret_cast<unsigned long long *>(d_out->casts), .ray = d_out->ray};
   const int which = pt_trace_pick(scene->view);
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  rc = status_word_for(scene->device, &L.status);
-  if (rc)
-    return rc;
-  size_t slot = 0;
-  rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
-  if (rc)
-    return rc;
-  hipError_t e = hipSuccess;
-  {
-    std::lock_guard<std::mutex> pend_lock(g_pend_mutex);
-    rc = pend_pool_for(scene->device, pt_pend_entries(scene->view, 0u, p->max_depth), PT_PEND_COLUMNS, L);
-    if (!rc)
-      e = pt_launch_trace(L, T, stream, which);
-  }
-  release_tables(scene, slot, stream);
-  if (rc)
-    return rc;
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_trace_kernel_name_of(which), hipGetErrorString(e));
-  return RT_HIP_OK;
+  return pooled_launch(scene, L, stream, pt_trace_kernel_name_of(which), [&] { return pt_launch_trace(L, T, stream, which); });
 }
+
+/* The parts of a radiance query's or a pixel refinement's host form behind its input: the requested outputs, then the counters,
+ * cleared.  The device's RtHipRadiance once the arena is staged, and the counters added to the caller's after the download. */
+struct RadianceStage
+{
+  int out[6], stats;
+  uint64_t st[RT_HIP_NSTATS];
+  uint64_t *h_stats;
+  RadianceStage(const RadianceStage &) = delete; /* (the plan points into st) */
+  RadianceStage(StageArena &A, const RtHipRadiance *h, uint64_t n, int32_t samples, uint64_t *h_stats_) : h_stats(h_stats_)
+  {
+    void *host[6] = {h->status, h->radiance, h->samples, h->paths, h->casts, h->ray};
+    const size_t bytes_per_entry[6] = {4, 24, 24u * (size_t)samples, 8, 8, 48};
+    for (int k = 0; k < 6; k++)
+      out[k] = A.part(bytes_per_entry[k] * n, nullptr, host[k], host[k] != nullptr);
+    stats = A.zeroed(sizeof st, h_stats ? st : nullptr);
+  }
+  RtHipRadiance device(const StageArena &A) const
+  {
+    return {A.at<uint32_t>(out[0]), A.at<double>(out[1]), A.at<double>(out[2]), A.at<uint64_t>(out[3]), A.at<uint64_t>(out[4]), A.at<double>(out[5])};
+  }
+  int download(const StageArena &A) const
+  {
+    const int rc = A.download();
+    for (int k = 0; !rc && h_stats && k < RT_HIP_NSTATS; k++)
+      h_stats[k] += st[k];
+    return rc;
+  }
+};
 
 /* rt_hip_trace_rays_host: a scene of its own on the logical device, one allocation for the rays, the counters and the requested
  * outputs, the launch on the null stream, the copies.  Everything is owned by this scope. */
@@ -2801,65 +2803,31 @@ int trace_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtH
   rc = physical_device(device, &phys);
   if (rc)
     return rc;
-  struct SceneOwner
-  {
-    RtHipScene *scene = nullptr;
-    ~SceneOwner() { rt_hip_scene_destroy(scene); }
-  } own;
-  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &own.scene);
+  OwnedScene own;
+  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
   if (rc)
     return rc;
   DeviceScope scope(phys);
   HIP_TRY(scope.status);
-  const size_t ray_doubles = params->source == RT_HIP_RAYS_CAMERA_UV ? 2u : 6u;
-  void *host[6] = {h_out->status, h_out->radiance, h_out->samples, h_out->paths, h_out->casts, h_out->ray};
-  const size_t bytes_per_ray[6] = {4, 24, 24u * (size_t)params->samples, 8, 8, 48};
-  size_t off[6], total = align256(ray_doubles * 8u * n);
-  const size_t off_stats = total;
-  total += align256(RT_HIP_NSTATS * sizeof(uint64_t));
-  for (int k = 0; k < 6; k++)
-  {
-    off[k] = total;
-    if (host[k])
-      total += align256(bytes_per_ray[k] * n);
-  }
-  DeviceBuffer buf;
-  HIP_TRY(buf.alloc(total));
-  HIP_TRY(hipMemcpy(buf.ptr, h_rays, ray_doubles * 8u * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(buf.at<char>(off_stats), 0, RT_HIP_NSTATS * sizeof(uint64_t)));
-  void *dev[6];
-  for (int k = 0; k < 6; k++)
-    dev[k] = host[k] ? buf.at<char>(off[k]) : nullptr;
-  const RtHipRadiance d_out = {(uint32_t *)dev[0], (double *)dev[1], (double *)dev[2], (uint64_t *)dev[3], (uint64_t *)dev[4], (double *)dev[5]};
-  rc = trace_launch(own.scene, buf.at<double>(), n, params, &d_out, buf.at<uint64_t>(off_stats), nullptr);
+  StageArena A;
+  const int rays = A.part((params->source == RT_HIP_RAYS_CAMERA_UV ? 16u : 48u) * n, h_rays);
+  RadianceStage R(A, h_out, n, params->samples, h_stats);
+  rc = A.stage();
   if (rc)
     return rc;
-  for (int k = 0; k < 6; k++)
-    if (host[k])
-      HIP_TRY(hipMemcpy(host[k], dev[k], bytes_per_ray[k] * n, hipMemcpyDeviceToHost)); /* (null stream: after the kernel) */
-  if (h_stats)
-  {
-    uint64_t st[RT_HIP_NSTATS];
-    HIP_TRY(hipMemcpy(st, buf.at<char>(off_stats), sizeof st, hipMemcpyDeviceToHost));
-    for (int k = 0; k < RT_HIP_NSTATS; k++)
-      h_stats[k] += st[k];
-  }
-  return RT_HIP_OK;
+  const RtHipRadiance d_out = R.device(A);
+  rc = trace_launch(own.scene, A.at<double>(rays), n, params, &d_out, A.at<uint64_t>(R.stats), nullptr);
+  return rc ? rc : R.download(A);
 }
 
 /* ---- pixel refinement (rt_hip.h, rt_hip_select_pixels / _trace_pixels / _blend_pixels) ---------------------------------------
  * select and blend are image-space calls like the upsampling: arguments checked without a device, then the device that holds the
  * first buffer.  trace_pixels is a radiance query's launch (trace_launch) whose rays the kernel forms itself: the frame's camera
  * and size in the launch, the camera's distance in origin_radius' place -- the near_R of a render launch of that camera. */
-bool select_size_ok(int32_t width, int32_t height)
-{
-  return width >= 1 && height >= 1 && width <= (1 << 20) && height <= (1 << 20) && (uint64_t)width * (uint64_t)height <= 0xFFFFFFFFull;
-}
-
 int check_select(const float *values, int32_t width, int32_t height, double lo, double hi, uint32_t flags, const void *workspace,
                  const uint32_t *indices, uint32_t capacity, const uint32_t *count)
 {
-  if (!select_size_ok(width, height))
+  if (!frame_size_ok(width, height, 1))
     return fail(RT_HIP_EINVAL, "width and height must be in [1, 2^20] with fewer than 2^32 pixels");
   if (lo != lo || hi != hi)
     return fail(RT_HIP_EINVAL, "lo and hi must not be NaN");
@@ -2902,8 +2870,7 @@ int check_pixels(const RtHipCamera *camera, const void *pixels, uint64_t n, cons
                 p->samples, p->sample_first);
   if (p->max_depth < 0 || p->max_depth > 1000000)
     return fail(RT_HIP_EINVAL, "max_depth out of range");
-  if (p->width < 2 || p->height < 2 || p->width > (1 << 20) || p->height > (1 << 20) ||
-      (uint64_t)p->width * (uint64_t)p->height > 0xFFFFFFFFull)
+  if (!frame_size_ok(p->width, p->height, 2))
     return fail(RT_HIP_EINVAL, "width and height must be in [2, 2^20] with fewer than 2^32 pixels");
   if (n > 0xFFFFFFFFull)
     return fail(RT_HIP_EINVAL, "n = %llu: a call takes fewer than 2^32 entries", (unsigned long long)n);
@@ -2917,12 +2884,10 @@ int check_pixels(const RtHipCamera *camera, const void *pixels, uint64_t n, cons
 int pixels_launch(const RtHipScene *scene, const RtHipCamera *camera, const uint32_t *d_pixels, uint64_t n, const RtHipPixelParams *p,
                   const RtHipRadiance *d_out, uint64_t *d_stats, hipStream_t stream)
 {
-  if (scene->view.any_refract && p->max_depth > PT_REFRACT_MAX_DEPTH)
-    return fail(RT_HIP_ELIMIT, "scenes with M_REFRACTION materials support max_depth <= %d (two rays per refractive hit, "
-                               "raytracer.c:523-529; the pending-ray stack is fixed)", PT_REFRACT_MAX_DEPTH);
   PtLaunch L;
   const double *c = camera->position;
-  int rc = ray_launch_prepare(scene, RT_HIP_RAYS_CAMERA_UV, camera, std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), L);
+  const int rc = pooled_launch_prepare(scene, RT_HIP_RAYS_CAMERA_UV, camera, std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), p->samples,
+                                       p->max_depth, p->seed, d_stats, L);
   if (rc)
     return rc;
   L.width = p->width;
@@ -2931,37 +2896,12 @@ int pixels_launch(const RtHipScene *scene, const RtHipCamera *camera, const uint
   L.h_minus_1 = (double)p->height - 1.0;
   L.inv_w_minus_1 = 1.0 / L.w_minus_1;
   L.inv_h_minus_1 = 1.0 / L.h_minus_1;
-  L.samples = p->samples;
-  L.max_depth = p->max_depth;
-  L.seed = p->seed;
-  L.stats = reinterpret_cast<unsigned long long *>(d_stats);
   const PtPixels Q = {.pixels = d_pixels, .n = n, .n_pixels = (uint32_t)((uint64_t)p->width * (uint64_t)p->height),
                       .sample_first = (uint32_t)p->sample_first, .status = d_out->status, .radiance = d_out->radiance,
                       .samples = d_out->samples, .paths = reinterpret_cast<unsigned long long *>(d_out->paths),
                       .casts = reinterpret_cast<unsigned long long *>(d_out->casts)};
   const int which = pt_pixel_pick(scene->view);
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  rc = status_word_for(scene->device, &L.status);
-  if (rc)
-    return rc;
-  size_t slot = 0;
-  rc = acquire_tables(scene, L.near_R, stream, &L.scene.filt, &L.scene.bvh_nodes, &slot);
-  if (rc)
-    return rc;
-  hipError_t e = hipSuccess;
-  {
-    std::lock_guard<std::mutex> pend_lock(g_pend_mutex);
-    rc = pend_pool_for(scene->device, pt_pend_entries(scene->view, 0u, p->max_depth), PT_PEND_COLUMNS, L);
-    if (!rc)
-      e = pt_launch_pixels(L, Q, stream, which);
-  }
-  release_tables(scene, slot, stream);
-  if (rc)
-    return rc;
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_pixel_kernel_name_of(which), hipGetErrorString(e));
-  return RT_HIP_OK;
+  return pooled_launch(scene, L, stream, pt_pixel_kernel_name_of(which), [&] { return pt_launch_pixels(L, Q, stream, which); });
 }
 
 /* rt_hip_trace_pixels_host: a scene of its own on the logical device, one allocation for the list, the counters and the requested
@@ -2977,55 +2917,37 @@ int trace_pixels_host_impl(const RtHipSphere *spheres, size_t n_spheres, const R
   rc = physical_device(device, &phys);
   if (rc)
     return rc;
-  struct SceneOwner
-  {
-    RtHipScene *scene = nullptr;
-    ~SceneOwner() { rt_hip_scene_destroy(scene); }
-  } own;
-  rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &own.scene);
+  OwnedScene own;
+  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
   if (rc)
     return rc;
   DeviceScope scope(phys);
   HIP_TRY(scope.status);
-  void *host[5] = {h_out->status, h_out->radiance, h_out->samples, h_out->paths, h_out->casts};
-  const size_t bytes_per_entry[5] = {4, 24, 24u * (size_t)params->samples, 8, 8};
-  size_t off[5], total = align256(4u * n);
-  const size_t off_stats = total;
-  total += align256(RT_HIP_NSTATS * sizeof(uint64_t));
-  for (int k = 0; k < 5; k++)
-  {
-    off[k] = total;
-    if (host[k])
-      total += align256(bytes_per_entry[k] * n);
-  }
-  DeviceBuffer buf;
-  HIP_TRY(buf.alloc(total));
-  HIP_TRY(hipMemcpy(buf.ptr, h_pixels, 4u * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(buf.at<char>(off_stats), 0, RT_HIP_NSTATS * sizeof(uint64_t)));
-  void *dev[5];
-  for (int k = 0; k < 5; k++)
-    dev[k] = host[k] ? buf.at<char>(off[k]) : nullptr;
-  const RtHipRadiance d_out = {(uint32_t *)dev[0], (double *)dev[1], (double *)dev[2], (uint64_t *)dev[3], (uint64_t *)dev[4], nullptr};
-  rc = pixels_launch(own.scene, camera, buf.at<uint32_t>(), n, params, &d_out, buf.at<uint64_t>(off_stats), nullptr);
+  StageArena A;
+  const int pixels = A.part(4u * n, h_pixels);
+  RadianceStage R(A, h_out, n, params->samples, h_stats); /* (check_pixels: h_out->ray is NULL) */
+  rc = A.stage();
   if (rc)
     return rc;
-  for (int k = 0; k < 5; k++)
-    if (host[k])
-      HIP_TRY(hipMemcpy(host[k], dev[k], bytes_per_entry[k] * n, hipMemcpyDeviceToHost)); /* (null stream: after the kernel) */
-  if (h_stats)
-  {
-    uint64_t st[RT_HIP_NSTATS];
-    HIP_TRY(hipMemcpy(st, buf.at<char>(off_stats), sizeof st, hipMemcpyDeviceToHost));
-    for (int k = 0; k < RT_HIP_NSTATS; k++)
-      h_stats[k] += st[k];
-  }
-  return RT_HIP_OK;
+  const RtHipRadiance d_out = R.device(A);
+  rc = pixels_launch(own.scene, camera, A.at<uint32_t>(pixels), n, params, &d_out, A.at<uint64_t>(R.stats), nullptr);
+  return rc ? rc : R.download(A);
+}
+
+/* rt_hip_*_kernel_launches of one of the four kernel lists: entry `index`'s name (null beyond the list) and launch count */
+const char *kernel_launches_of(int index, uint64_t *launches, int count, const char *(*name_of)(int), unsigned long long (*launches_of)(int))
+{
+  if (index < 0 || index >= count)
+    return nullptr;
+  if (launches)
+    *launches = launches_of(index);
+  return name_of(index);
 }
 
 int check_blend(const uint32_t *pixels, const uint32_t *status, const double *radiance, uint64_t n, int32_t width, int32_t height,
                 double new_weight, double prior_scale, const float *rgb)
 {
-  if (!select_size_ok(width, height))
+  if (!frame_size_ok(width, height, 1))
     return fail(RT_HIP_EINVAL, "width and height must be in [1, 2^20] with fewer than 2^32 pixels");
   if (n > 0xFFFFFFFFull)
     return fail(RT_HIP_EINVAL, "n = %llu: a call takes fewer than 2^32 entries", (unsigned long long)n);
@@ -3174,11 +3096,7 @@ int rt_hip_kernel_count(void) { return pt_kernel_count(); }
 
 const char *rt_hip_kernel_launches(int index, uint64_t *launches)
 {
-  if (index < 0 || index >= pt_kernel_count())
-    return nullptr;
-  if (launches)
-    *launches = pt_kernel_launches(index);
-  return pt_kernel_name_of(index);
+  return kernel_launches_of(index, launches, pt_kernel_count(), pt_kernel_name_of, pt_kernel_launches);
 }
 
 const char *rt_hip_kernel_for_class(const RtHipSceneClass *c)
@@ -3597,24 +3515,19 @@ int rt_hip_tile_error(const float *d_cur, const float *d_prev, int32_t width, in
   const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
   if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
     return fail(RT_HIP_EINVAL, "tile range outside the image");
-  if (usable_devices() < 1)
-    return fail(RT_HIP_ENODEV, "no usable HIP device");
-  hipPointerAttribute_t attr = {};
   int on = -1;
   for (const void *ptr : {static_cast<const void *>(d_cur), static_cast<const void *>(d_prev), static_cast<const void *>(d_error)})
   {
-    if (hipPointerGetAttributes(&attr, ptr) != hipSuccess || attr.type != hipMemoryTypeDevice)
-    {
-      (void)hipGetLastError();
-      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be device memory");
-    }
-    if (on >= 0 && attr.device != on)
-      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be on one device (%d, %d)", on, attr.device);
-    on = attr.device;
+    int device = -1;
+    const int rc = device_of(ptr, "one of d_cur, d_prev and d_error", &device);
+    if (rc)
+      return rc;
+    if (on >= 0 && device != on)
+      return fail(RT_HIP_EINVAL, "d_cur, d_prev and d_error must be on one device (%d, %d)", on, device);
+    on = device;
   }
-  DeviceScope scope(attr.device);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  DeviceScope scope(on);
+  HIP_TRY(scope.status);
   const hipError_t e = pt_launch_tile_error(d_cur, d_prev, width, height, tile_first, tile_stride, tile_count, d_error, static_cast<hipStream_t>(stream));
   if (e != hipSuccess)
     return fail(RT_HIP_ERUNTIME, "tile error: %s", hipGetErrorString(e));
@@ -3834,11 +3747,7 @@ int rt_hip_aov_kernel_count(void) { return pt_aov_kernel_count(); }
 
 const char *rt_hip_aov_kernel_launches(int index, uint64_t *launches)
 {
-  if (index < 0 || index >= pt_aov_kernel_count())
-    return nullptr;
-  if (launches)
-    *launches = pt_aov_kernel_launches(index);
-  return pt_aov_kernel_name_of(index);
+  return kernel_launches_of(index, launches, pt_aov_kernel_count(), pt_aov_kernel_name_of, pt_aov_kernel_launches);
 }
 
 int rt_hip_render_aov_tiles(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *d_tiles,
@@ -3859,17 +3768,8 @@ int rt_hip_render_aov_tiles(const RtHipScene *scene, const RtHipCamera *camera, 
       return rc;
     const PtAovOut out = {d_tiles->albedo, d_tiles->normal, d_tiles->depth, d_tiles->object, d_tiles->hits};
     const int which = pt_aov_pick(scene->view);
-    DeviceScope scope(scene->device);
-    HIP_TRY(scope.status);
-    size_t slot = 0;
-    rc = acquire_tables(scene, L.near_R, static_cast<hipStream_t>(stream), &L.scene.filt, &L.scene.bvh_nodes, &slot);
-    if (rc)
-      return rc;
-    const hipError_t e = pt_launch_aov(L, out, static_cast<hipStream_t>(stream), which);
-    release_tables(scene, slot, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_aov_kernel_name_of(which), hipGetErrorString(e));
-    return RT_HIP_OK;
+    return launch_with_tables(scene, L, static_cast<hipStream_t>(stream), pt_aov_kernel_name_of(which),
+                              [&] { return pt_launch_aov(L, out, static_cast<hipStream_t>(stream), which); });
   });
 }
 
@@ -3889,11 +3789,7 @@ int rt_hip_query_kernel_count(void) { return pt_query_kernel_count(); }
 
 const char *rt_hip_query_kernel_launches(int index, uint64_t *launches)
 {
-  if (index < 0 || index >= pt_query_kernel_count())
-    return nullptr;
-  if (launches)
-    *launches = pt_query_kernel_launches(index);
-  return pt_query_kernel_name_of(index);
+  return kernel_launches_of(index, launches, pt_query_kernel_count(), pt_query_kernel_name_of, pt_query_kernel_launches);
 }
 
 int rt_hip_query_rays(const RtHipScene *scene, const double *d_rays, const double *d_t_max, uint64_t n, const RtHipQueryParams *params,
@@ -3932,11 +3828,7 @@ int rt_hip_trace_kernel_count(void) { return pt_trace_kernel_count(); }
 
 const char *rt_hip_trace_kernel_launches(int index, uint64_t *launches)
 {
-  if (index < 0 || index >= pt_trace_kernel_count())
-    return nullptr;
-  if (launches)
-    *launches = pt_trace_kernel_launches(index);
-  return pt_trace_kernel_name_of(index);
+  return kernel_launches_of(index, launches, pt_trace_kernel_count(), pt_trace_kernel_name_of, pt_trace_kernel_launches);
 }
 
 int rt_hip_trace_rays(const RtHipScene *scene, const double *d_rays, uint64_t n, const RtHipTraceParams *params,
@@ -4020,12 +3912,12 @@ int rt_hip_render_adaptive_image(const RtHipSphere *spheres, size_t n_spheres, c
       return rc;
     RtHipParams p = *params;
     whole_image(p);
-    RtHipScene *scene = nullptr;
+    OwnedScene own; /* (outlives the accumulation: destroyed when this scope ends) */
     RtHipAccum *acc = nullptr;
     uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
-    rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys, &scene);
+    rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
     if (!rc)
-      rc = rt_hip_accum_create(scene, camera, &p, &acc);
+      rc = rt_hip_accum_create(own.scene, camera, &p, &acc);
     if (!rc)
       rc = rt_hip_accum_run_adaptive(acc, adapt, stats, kernel_seconds, on_checkpoint, user);
     const bool cancelled = rc == RT_HIP_ECANCELLED; /* the frame of the samples done is still a whole image */
@@ -4043,7 +3935,6 @@ int rt_hip_render_adaptive_image(const RtHipSphere *spheres, size_t n_spheres, c
       for (int k = 0; k < RT_HIP_NSTATS; k++)
         h_stats[k] = stats[k];
     rt_hip_accum_destroy(acc);
-    rt_hip_scene_destroy(scene);
     return rc;
   });
 }
@@ -4062,7 +3953,7 @@ void rt_hip_denoise_defaults(RtHipDenoiseParams *params)
 
 size_t rt_hip_denoise_workspace_bytes(int32_t width, int32_t height)
 {
-  return denoise_size_ok(width, height) ? denoise_ws_bytes((size_t)width * (size_t)height) : 0u;
+  return frame_size_ok(width, height, 1) ? denoise_ws_bytes((size_t)width * (size_t)height) : 0u;
 }
 
 int rt_hip_denoise(const float *d_rgb, const RtHipAov *d_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
@@ -4073,18 +3964,12 @@ int rt_hip_denoise(const float *d_rgb, const RtHipAov *d_aov, int32_t width, int
     return rc;
   if (!d_workspace)
     return fail(RT_HIP_EINVAL, "d_workspace is required (rt_hip_denoise_workspace_bytes)");
-  if (usable_devices() < 1)
-    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
-  /* the device that holds the colour: a host pointer here would fault the kernel, so it is refused */
-  hipPointerAttribute_t attr = {};
-  if (hipPointerGetAttributes(&attr, d_rgb) != hipSuccess || attr.type != hipMemoryTypeDevice)
-  {
-    (void)hipGetLastError();
-    return fail(RT_HIP_EINVAL, "d_rgb is not device memory");
-  }
-  DeviceScope scope(attr.device);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  int device = -1;
+  rc = device_of(d_rgb, "d_rgb", &device);
+  if (rc)
+    return rc;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
   return denoise_launch(d_rgb, d_aov, width, height, params, d_workspace, d_out_rgb, d_out_rgb8, static_cast<hipStream_t>(stream));
 }
 
@@ -4115,18 +4000,12 @@ int rt_hip_reproject(const float *d_rgb, const RtHipAov *d_aov, const RtHipCamer
                            d_out_rgb8, d_out_len, d_out_motion);
   if (rc)
     return rc;
-  if (usable_devices() < 1)
-    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
-  /* the device that holds the colour: a host pointer here would fault the kernel, so it is refused */
-  hipPointerAttribute_t attr = {};
-  if (hipPointerGetAttributes(&attr, d_rgb) != hipSuccess || attr.type != hipMemoryTypeDevice)
-  {
-    (void)hipGetLastError();
-    return fail(RT_HIP_EINVAL, "d_rgb is not device memory");
-  }
-  DeviceScope scope(attr.device);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  int device = -1;
+  rc = device_of(d_rgb, "d_rgb", &device);
+  if (rc)
+    return rc;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
   return reproject_launch(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, d_out_rgb,
                           d_out_rgb8, d_out_len, d_out_motion, static_cast<hipStream_t>(stream));
 }
@@ -4160,18 +4039,12 @@ int rt_hip_upsample(const float *d_low_rgb, const RtHipAov *d_low_aov, int32_t l
   int rc = check_upsample(d_low_rgb, d_low_aov, low_width, low_height, d_aov, width, height, params, d_out_rgb, d_out_rgb8, d_out_conf);
   if (rc)
     return rc;
-  if (usable_devices() < 1)
-    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
-  /* the device that holds the low colour: a host pointer here would fault the kernel, so it is refused */
-  hipPointerAttribute_t attr = {};
-  if (hipPointerGetAttributes(&attr, d_low_rgb) != hipSuccess || attr.type != hipMemoryTypeDevice)
-  {
-    (void)hipGetLastError();
-    return fail(RT_HIP_EINVAL, "d_low_rgb is not device memory");
-  }
-  DeviceScope scope(attr.device);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", attr.device, hipGetErrorString(scope.status));
+  int device = -1;
+  rc = device_of(d_low_rgb, "d_low_rgb", &device);
+  if (rc)
+    return rc;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
   return upsample_launch(d_low_rgb, d_low_aov, low_width, low_height, d_aov, width, height, params, d_out_rgb, d_out_rgb8, d_out_conf,
                          static_cast<hipStream_t>(stream));
 }
@@ -4188,7 +4061,7 @@ int rt_hip_upsample_image(const float *h_low_rgb, const RtHipAov *h_low_aov, int
 
 size_t rt_hip_select_workspace_bytes(int32_t width, int32_t height)
 {
-  return select_size_ok(width, height) ? pt_select_workspace_bytes((uint64_t)width * (uint64_t)height) : 0;
+  return frame_size_ok(width, height, 1) ? pt_select_workspace_bytes((uint64_t)width * (uint64_t)height) : 0;
 }
 
 int rt_hip_select_pixels(const float *d_values, int32_t width, int32_t height, double lo, double hi, uint32_t flags, void *d_workspace,
@@ -4202,8 +4075,7 @@ int rt_hip_select_pixels(const float *d_values, int32_t width, int32_t height, d
   if (rc)
     return rc;
   DeviceScope scope(device);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", device, hipGetErrorString(scope.status));
+  HIP_TRY(scope.status);
   const PtSelect A = {.values = d_values, .n = (uint64_t)width * (uint64_t)height, .lo = lo, .hi = hi,
                       .invert = (flags & RT_HIP_SELECT_INVERT) ? 1u : 0u};
   const hipError_t e = pt_launch_select(A, d_workspace, d_indices, capacity, d_count, static_cast<hipStream_t>(stream));
@@ -4228,11 +4100,7 @@ int rt_hip_pixel_kernel_count(void) { return pt_pixel_kernel_count(); }
 
 const char *rt_hip_pixel_kernel_launches(int index, uint64_t *launches)
 {
-  if (index < 0 || index >= pt_pixel_kernel_count())
-    return nullptr;
-  if (launches)
-    *launches = pt_pixel_kernel_launches(index);
-  return pt_pixel_kernel_name_of(index);
+  return kernel_launches_of(index, launches, pt_pixel_kernel_count(), pt_pixel_kernel_name_of, pt_pixel_kernel_launches);
 }
 
 int rt_hip_trace_pixels(const RtHipScene *scene, const RtHipCamera *camera, const uint32_t *d_pixels, uint64_t n,
@@ -4270,8 +4138,7 @@ int rt_hip_blend_pixels(const uint32_t *d_pixels, const uint32_t *d_status, cons
   if (rc || n == 0)
     return rc;
   DeviceScope scope(device);
-  if (scope.status != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "hipSetDevice(%d): %s", device, hipGetErrorString(scope.status));
+  HIP_TRY(scope.status);
   const PtBlend B = {.pixels = d_pixels, .status = d_status, .radiance = d_radiance, .n = n,
                      .n_pixels = (uint32_t)((uint64_t)width * (uint64_t)height), .new_weight = new_weight, .prior_scale = prior_scale,
                      .prior = d_prior, .rgb = d_rgb, .rgb8 = d_rgb8, .weight = d_weight};

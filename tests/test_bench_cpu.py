@@ -78,7 +78,14 @@ def test_the_source_hash_covers_every_file_of_the_device_code():
             continue            # a system header
         seen.add(name)
         todo += re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M)
-    assert seen <= hashed, sorted(seen - hashed)
+    # rt_staging.h is the one exemption: the layout arithmetic of the shim's host-array forms, pure C++ that a stand-alone
+    # CPU program also includes (tests/test_staging_cpu.py).  It may hold nothing the records depend on -- no device code, no
+    # HIP, no further file of the repository --, which is asserted here; every other file must be hashed.
+    host_only = {"rt_staging.h"}
+    for name in host_only & seen:
+        text = open(os.path.join(csrc, name)).read()
+        assert not re.search(r'__global__|__device__|__shared__|__launch_bounds__|<hip/|hipLaunch|#\s*include\s+"', text), name
+    assert seen - host_only <= hashed, sorted(seen - host_only - hashed)
     assert {f for f in os.listdir(csrc) if re.fullmatch(r"pt_\w+\.h", f)} <= hashed
 
 

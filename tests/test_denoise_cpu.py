@@ -358,9 +358,9 @@ def test_bad_arguments_rejected():
         return shim.rt_hip_denoise(rgb, C.byref(aov if aov is not None else _aov(b)), w, h, C.byref(p) if p is not None else None,
                                    work, out, out8, None)
 
-    def call_image(rgb=ptr(b["rgb"]), aov=None, w=8, h=6, p=good, out=ptr(b["out"]), out8=ptr(b["out8"])):
+    def call_image(rgb=ptr(b["rgb"]), aov=None, w=8, h=6, p=good, out=ptr(b["out"]), out8=ptr(b["out8"]), device=0):
         return shim.rt_hip_denoise_image(rgb, C.byref(aov if aov is not None else _aov(b)), w, h,
-                                         C.byref(p) if p is not None else None, 0, out, out8)
+                                         C.byref(p) if p is not None else None, device, out, out8)
 
     for fn in (call, call_image):
         for w, h in ((0, 6), (8, 0), (-1, 6), ((1 << 20) + 1, 1), (1 << 20, 1 << 12)):
@@ -377,6 +377,9 @@ def test_bad_arguments_rejected():
         assert fn(aov=_aov(b, albedo=False)) == abi.EINVAL                             # DEMODULATE needs the albedo
         assert fn(aov=_aov(b, obj=False)) == abi.EINVAL                                # OBJECT_EDGES needs the object ids
     assert call(work=None) == abi.EINVAL
+    # the image form checks its arguments before it looks its device up (99: there is none such)
+    assert call_image(w=0, device=99) == abi.EINVAL and call_image(out=None, out8=None, device=99) == abi.EINVAL
+    assert call_image(device=99) == abi.ENODEV
     assert shim.rt_hip_denoise(ptr(b["rgb"]), None, 8, 6, C.byref(good), ptr(ws), ptr(b["out"]), None, None) == abi.EINVAL
     assert (b["out"] == 7.0).all() and (b["out8"] == 7).all()
 

@@ -12,7 +12,7 @@ import query_expected as Q
 EINVAL, ENODEV = -2, -1
 
 
-def _host_call(shim, n=1, source=0, flags=0, camera=None, origin_radius=0.0, outputs=True, params=True):
+def _host_call(shim, n=1, source=0, flags=0, camera=None, origin_radius=0.0, outputs=True, params=True, device=0):
     from rt_amd import abi, scene as S
     sc = S.build_scene(1, 16, 16, 1)
     p = abi.RtHipQueryParams()
@@ -26,7 +26,7 @@ def _host_call(shim, n=1, source=0, flags=0, camera=None, origin_radius=0.0, out
     hits = abi.RtHipHits()
     if outputs:
         hits.status = status.ctypes.data
-    rc = shim.rt_hip_query_rays_host(sc.objects, sc.n_objects, None, 0, rays.ctypes.data, None, n, C.byref(p) if params else None, 0,
+    rc = shim.rt_hip_query_rays_host(sc.objects, sc.n_objects, None, 0, rays.ctypes.data, None, n, C.byref(p) if params else None, device,
                                      C.byref(hits))
     sc.free()
     return rc
@@ -58,6 +58,10 @@ def test_arguments_are_checked_before_the_device_is_looked_for():
         assert good == [ENODEV, ENODEV, ENODEV]
     else:
         assert good == [0, 0, 0]
+    # the order of the host form's steps: the arguments, then the device -- for no ray too --, then nothing to do
+    assert _host_call(shim, outputs=False, device=99) == EINVAL
+    assert _host_call(shim, device=99) == ENODEV
+    assert _host_call(shim, n=0, device=99) == ENODEV
 
 
 def test_struct_sizes_and_names():

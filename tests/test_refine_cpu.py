@@ -109,6 +109,23 @@ def test_bad_arguments_are_refused_before_a_device_is_looked_for():
     with_ray.status, with_ray.ray = 16, 16
     assert shim.rt_hip_trace_pixels(one, C.byref(cam), one, 4, C.byref(ok), C.byref(with_ray), None, None) == abi.EINVAL
     assert shim.rt_hip_trace_pixels(one, C.byref(cam), one, 2 ** 32, C.byref(ok), C.byref(rad), None, None) == abi.EINVAL
+    # the order of the host form's steps: the arguments, then nothing to do for no entry, then the device (99: there is none such)
+    sc = R.checkered_room(8, 8, 1)
+    idx = np.zeros(4, np.uint32)
+    status = np.zeros(4, np.uint32)
+    rad.status = status.ctypes.data
+
+    def host_form(n, p, device):
+        return shim.rt_hip_trace_pixels_host(sc.objects, sc.n_objects, None, 0, C.byref(cam), idx.ctypes.data, n, C.byref(p), device,
+                                             C.byref(rad), None)
+    for device in (0, 99):
+        assert host_form(4, bad[0], device) == abi.EINVAL
+        assert host_form(0, bad[0], device) == abi.EINVAL
+        assert host_form(0, ok, device) == 0
+    assert host_form(4, ok, 99) == abi.ENODEV
+    assert host_form(4, ok, 0) == (abi.ENODEV if shim.rt_hip_device_count() == 0 else 0)
+    rad.status = 16
+    sc.free()
     for args in [(one, one, one, 4, 0, 4, 1.0, 0.0, None, one, None, None), (one, one, one, 4, 4, 4, 0.0, 0.0, None, one, None, None),
                  (one, one, one, 4, 4, 4, float("inf"), 0.0, None, one, None, None), (one, one, one, 4, 4, 4, 1.0, -1.0, None, one, None, None),
                  (one, one, one, 4, 4, 4, 1.0, nan, None, one, None, None), (one, one, one, 4, 4, 4, 1.0, 0.0, None, None, None, None),

@@ -200,7 +200,7 @@ class _Args:
         head = (a["rgb"], a["aov"], a["cam"], a["hrgb"], a["hlen"], a["haov"], a["hcam"], a["w"], a["h"], a["p"])
         tail = (a["out"], a["out8"], a["olen"], a["motion"])
         if image:
-            return shim.rt_hip_reproject_image(*head, 0, *tail)
+            return shim.rt_hip_reproject_image(*head, a.get("device", 0), *tail)
         return shim.rt_hip_reproject(*head, *tail, None)
 
 
@@ -239,6 +239,9 @@ def test_bad_arguments_rejected():
         assert A.call(image, out=ptr(k["rgb"]) + 12) == abi.EINVAL           # in place means the same address
         assert A.call(image, olen=ptr(k["out"])) == abi.EINVAL and A.call(image, motion=ptr(k["olen"])) == abi.EINVAL
         assert A.call(image, out8=ptr(k["motion"]) + 4) == abi.EINVAL
+    # the image form checks its arguments before it looks its device up (99: there is none such)
+    assert A.call(True, w=1, device=99) == abi.EINVAL and A.call(True, out=None, device=99) == abi.EINVAL
+    assert A.call(True, device=99) == abi.ENODEV
     assert (k["out"] == 7.0).all() and (k["out8"] == 7).all() and (k["olen"] == 7.0).all() and (k["motion"] == 7.0).all()
     # what is allowed gets past the checks: on a machine without a GPU the answer is "no device", not "bad argument"
     if _no_gpu():

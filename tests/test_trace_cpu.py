@@ -12,7 +12,7 @@ import trace_expected as T
 EINVAL, ENODEV = -2, -1
 
 
-def _host_call(shim, n=1, samples=1, integrator=0, index_first=0, origin_radius=0.0, outputs=True, max_depth=5):
+def _host_call(shim, n=1, samples=1, integrator=0, index_first=0, origin_radius=0.0, outputs=True, max_depth=5, device=0):
     from rt_amd import abi, scene as S
     sc = S.build_scene(1, 16, 16, 1)
     p = abi.RtHipTraceParams()
@@ -24,7 +24,7 @@ def _host_call(shim, n=1, samples=1, integrator=0, index_first=0, origin_radius=
     out = abi.RtHipRadiance()
     if outputs:
         out.status = status.ctypes.data
-    rc = shim.rt_hip_trace_rays_host(sc.objects, sc.n_objects, None, 0, rays.ctypes.data, n, C.byref(p), 0, C.byref(out), None)
+    rc = shim.rt_hip_trace_rays_host(sc.objects, sc.n_objects, None, 0, rays.ctypes.data, n, C.byref(p), device, C.byref(out), None)
     sc.free()
     return rc
 
@@ -76,6 +76,10 @@ def test_arguments_are_checked_before_the_device_is_looked_for():
     assert _host_call(shim, n=0) == 0
     assert _host_call(shim, n=1, index_first=2 ** 32 - 1) == (ENODEV if shim.rt_hip_device_count() == 0 else 0)
     assert _host_call(shim) == (ENODEV if shim.rt_hip_device_count() == 0 else 0)
+    # the order of the host form's steps: the arguments, then nothing to do for no ray, then the device
+    assert _host_call(shim, outputs=False, device=99) == EINVAL
+    assert _host_call(shim, n=0, device=99) == 0
+    assert _host_call(shim, device=99) == ENODEV
 
 
 def test_the_reduction_equals_a_scalar_loop():

@@ -143,7 +143,7 @@ class _Args:
         head = (a["low"], a["laov"], a["wl"], a["hl"], a["aov"], a["w"], a["h"], a["p"])
         tail = (a["out"], a["out8"], a["conf"])
         if image:
-            return shim.rt_hip_upsample_image(*head, 0, *tail)
+            return shim.rt_hip_upsample_image(*head, a.get("device", 0), *tail)
         return shim.rt_hip_upsample(*head, *tail, None)
 
 
@@ -176,6 +176,9 @@ def test_bad_arguments_rejected():
         assert A.call(image, out=ptr(k["low"]) + 12) == abi.EINVAL
         assert A.call(image, out8=ptr(k["out"])) == abi.EINVAL and A.call(image, conf=ptr(k["out"]) + 4) == abi.EINVAL   # ... or another
         assert A.call(image, conf=ptr(k["out8"])) == abi.EINVAL
+    # the image form checks its arguments before it looks its device up (99: there is none such)
+    assert A.call(True, w=1, device=99) == abi.EINVAL and A.call(True, out=None, device=99) == abi.EINVAL
+    assert A.call(True, device=99) == abi.ENODEV
     assert (k["out"] == 7.0).all() and (k["out8"] == 7).all() and (k["conf"] == 7.0).all()
     # what is allowed gets past the checks: on a machine without a GPU the answer is "no device", not "bad argument"
     if _no_gpu():
