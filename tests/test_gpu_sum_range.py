@@ -8,12 +8,13 @@ import numpy as np
 import pytest
 
 from conftest import SEED
+from accum_range_scenes import (_custom, _fixed_point_fits, _parts, colour_scene, hidden_emitter_scene, negative_emission_scene,
+                                visible_emitter_scene)
 from util import assert_parity, class_scene
 
 pytestmark = pytest.mark.gpu
 
 FLOOR = 1e-9  # absolute; NOT fixed_point_floor(): the bar must not grow with the brightest emitter
-SHELL_C = (-12.0, 8.0, -10.0)  # a diffuse shell in the room's upper left, away from the camera (0, 0, 50)
 HIDDEN_E = [1e3, 1e6, 1e9, 1e12, 1e15, 1e30]
 
 
@@ -24,34 +25,6 @@ def gpu():
     assert abi.load_shim().rt_hip_device_count() >= 1, "no HIP device: the GPU tests must run on the GPU box"
     assert torch.cuda.is_available()
     return G
-
-
-def _parts(sc):
-    """the objects and meshes of a scene as custom_scene() takes them"""
-    objs = [dict(flags=int(o.flags), radius=float(o.radius), center=o.center.tuple(), color=o.color.tuple(),
-                 emission=o.emission.tuple()) for o in (sc.objects[i] for i in range(sc.n_objects))]
-    meshes = []
-    for i in range(sc.n_meshes):
-        m = sc.meshes[i]
-        v = m.mesh.vertices
-        tris = [[(v[3 * t + k].pos.x, v[3 * t + k].pos.y, v[3 * t + k].pos.z, v[3 * t + k].tex.x, v[3 * t + k].tex.y)
-                 for k in range(3)] for t in range(m.mesh.num_triangles)]
-        meshes.append(dict(flags=int(m.flags), color=m.color.tuple(), emission=m.emission.tuple(), triangles=tris))
-    return objs, meshes
-
-
-def hidden_emitter_scene(E, width=40, height=24, samples=4, max_depth=5, **cls):
-    """class_scene(**cls) plus an emitter of E sealed inside a closed diffuse shell: no ray can reach it"""
-    objs, meshes = _parts(class_scene(width=width, height=height, samples=samples, depth=max_depth, **cls))
-    from rt_amd import abi
-    objs.append(dict(flags=abi.M_DEFAULT, radius=3.0, center=SHELL_C, color=(0.6, 0.6, 0.6)))
-    objs.append(dict(flags=abi.M_DEFAULT, radius=1.0, center=SHELL_C, color=(1.0, 1.0, 1.0), emission=(E, E, E)))
-    return _custom(objs, meshes, width, height, samples, max_depth)
-
-
-def _custom(objs, meshes, width, height, samples, max_depth):
-    from rt_amd import scene as S
-    return S.custom_scene(objs, width, height, samples, max_depth, (0, 0, 50), (0, 0, 0), meshes=meshes)
 
 
 def _oracle(pt, ref, sc, seed=SEED):
@@ -83,14 +56,6 @@ BODIES = [
     ("tri_queued", dict(tris=600), "pt_render_tiles_tri_queued", "pt_render_tiles_tri_queued_refr"),
     ("tri_queued_sph", dict(tris=600, round_mesh=True), "pt_render_tiles_tri_queued_sph", "pt_render_tiles_tri_queued_refr_sph"),
 ]
-
-
-def _fixed_point_fits(sc, E):
-    """pt_fixed_sums_fit restated: (max_depth + 2) x 2^-s / 2 <= 2^-30 with the launch's scale 2^s (pt_acc_scale_exp)"""
-    import math
-    per = (sc.max_depth + 2) * max(10 / 255, E) * 1.01
-    s = min(math.frexp(2.0 ** 62 / (per * sc.samples))[1], math.frexp(2.0 ** 51 / per)[1]) - 1
-    return (sc.max_depth + 2) * 2.0 ** (-s - 1) <= 2.0 ** -30
 
 
 @pytest.mark.parametrize("E", HIDDEN_E, ids=[f"E={e:g}" for e in HIDDEN_E])
@@ -128,19 +93,8 @@ def test_hidden_emitter_with_glass(gpu, pt, ref, what, cls, E, kernel):
 @pytest.mark.parametrize("E", [1e6, 1e9])
 def test_visible_bright_emitter(gpu, pt, ref, E):
     """a small emitter of E in view beside the dim room: the bar scales with the brightest pixel (hdr), not with E"""
-    from rt_amd import abi
-    objs, meshes = _parts(class_scene(width=40, height=24, samples=4, depth=5))
-    objs.append(dict(flags=abi.M_DEFAULT, radius=1.5, center=(6.0, -4.0, 10.0), color=(1.0, 1.0, 1.0), emission=(E, 0.3 * E, 1.0)))
-    sc = _custom(objs, meshes, 40, 24, 4, 5)
+    sc = visible_emitter_scene(E)
     _render_and_compare(gpu, pt, ref, sc, "pt_render_tiles_refr_pool", f"visible emitter {E:g}", hdr=True)
-
-
-def negative_emission_scene(width=40, height=24, samples=4, max_depth=5, **cls):
-    from rt_amd import abi
-    objs, meshes = _parts(class_scene(width=width, height=height, samples=samples, depth=max_depth, **cls))
-    objs.append(dict(flags=abi.M_DEFAULT, radius=2.5, center=(-5.0, 3.0, 12.0), color=(0.8, 0.9, 0.7), emission=(-2.0, 0.5, -0.1)))
-    objs.append(dict(flags=abi.M_REFLECTION, radius=2.0, center=(5.0, -2.0, 12.0), color=(0.9, 0.9, 0.9), emission=(-0.3, -0.3, 0.2)))
-    return _custom(objs, meshes, width, height, samples, max_depth)
 
 
 NEGATIVE = [
@@ -155,23 +109,6 @@ NEGATIVE = [
 def test_negative_emission(gpu, pt, ref, what, cls, kernel):
     sc = negative_emission_scene(**cls)
     _render_and_compare(gpu, pt, ref, sc, kernel, f"negative emission, {what}")
-
-
-def colour_scene(refr=False, chk=False, tris=0):
-    """colours at the edges: all three channels 0 (prob = 0: the normalised albedo is 0 x inf = NaN, never read -- the
-    roulette ends every path there), one channel 0, and above 1 (normalised by prob = 3); diffuse, M_REFLECTION and
-    M_CHECKERED objects"""
-    from rt_amd import abi
-    objs, meshes = _parts(class_scene(width=40, height=24, samples=4, depth=5, refr=refr, chk=chk, tris=tris))
-    D, R, K = abi.M_DEFAULT, abi.M_REFLECTION, abi.M_CHECKERED
-    objs += [dict(flags=D, radius=2.5, center=(-8.0, -3.0, 10.0), color=(0.0, 0.0, 0.0)),
-             dict(flags=R, radius=2.0, center=(-3.0, 4.0, 12.0), color=(0.0, 0.0, 0.0)),
-             dict(flags=D | K, radius=2.5, center=(2.0, -5.0, 8.0), color=(0.0, 0.0, 0.0)),
-             dict(flags=D, radius=2.0, center=(7.0, 3.0, 10.0), color=(0.7, 0.0, 0.4)),
-             dict(flags=R | K, radius=2.2, center=(-9.0, 6.0, 4.0), color=(3.0, 1.5, 0.2)),
-             dict(flags=D, radius=2.4, center=(9.0, -4.0, 6.0), color=(3.0, 1.5, 0.2)),
-             dict(flags=R, radius=1.8, center=(0.0, 7.0, 14.0), color=(0.0, 2.0, 0.0), emission=(0.5, 0.5, 0.5))]
-    return _custom(objs, meshes, 40, 24, 4, 5)
 
 
 COLOURS = [
