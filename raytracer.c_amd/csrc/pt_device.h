@@ -372,7 +372,7 @@ struct PtQuery
   double *point, *normal, *bary, *ray; /* 3, 3, 2, 6 doubles per ray */
 };
 
-/* One radiance query (rt_hip.h, rt_hip_trace_rays; trace_rays in pt_kernel.hip): n rays in as for PtQuery, per ray the mean of
+/* One radiance query (rt_hip.h, rt_hip_trace_rays; trace_sliced<RayFront> in pt_kernel.hip): n rays in as for PtQuery, per ray the mean of
  * PtLaunch.samples trace_path samples out.  Sample s of ray i runs on the stream (PtLaunch.seed, index_first + i, s) after two
  * discarded draws; PtLaunch.max_depth is the reference's MAX_DEPTH.  samples: 3 doubles per (ray, sample), [i * S + s].  paths /
  * casts: per ray, summed over its samples.  Any output may be null (not all: the shim refuses that). */
@@ -388,7 +388,7 @@ struct PtTrace
   double *ray; /* 6 doubles per ray */
 };
 
-/* One pixel refinement (rt_hip.h, rt_hip_trace_pixels; trace_pixels in pt_kernel.hip): n pixel indices in, per entry the mean of
+/* One pixel refinement (rt_hip.h, rt_hip_trace_pixels; trace_sliced<PixelFront> in pt_kernel.hip): n pixel indices in, per entry the mean of
  * PtLaunch.samples samples of the RENDER's own: sample k of entry i is sample sample_first + k of pixel pixels[i] of the launch's
  * width x height frame (start_sample on the stream (PtLaunch.seed, pixel, sample_first + k)).  n_pixels = width * height: an index
  * at or beyond it is invalid.  samples: 3 doubles per (entry, sample), [i * S + k].  Any output may be null (not all). */
@@ -569,18 +569,17 @@ hipError_t pt_launch_query(const PtLaunch &launch, const PtQuery &query, hipStre
 const char *pt_query_kernel_name_of(int which);
 int pt_query_kernel_count(void);
 unsigned long long pt_query_kernel_launches(int which);
-/* the radiance-query kernels (pt_kernel.hip: trace_rays, PT_TRACE_FAMILY): which form a scene takes (as pt_query_pick), the launch
- * (64 rays x 4 sample slices per workgroup; launch.samples, max_depth, seed, the pending-ray pool and the status word as a render
- * launch of the static M_REFRACTION members), names and launch counters */
+/* the sliced kernels (pt_kernel.hip: PT_SLICED_FAMILY, one table of two lists; body trace_sliced, pt_body_static.h): which of the
+ * five forms a scene takes, in either list (as pt_query_pick), and per list the launch, names and launch counters.
+ * The radiance queries (front end RayFront): 64 rays x 4 sample slices per workgroup; launch.samples, max_depth, seed, the
+ * pending-ray pool and the status word as a render launch of the static M_REFRACTION members */
 int pt_trace_pick(const PtSceneView &scene);
 hipError_t pt_launch_trace(const PtLaunch &launch, const PtTrace &trace, hipStream_t stream, int which);
 const char *pt_trace_kernel_name_of(int which);
 int pt_trace_kernel_count(void);
 unsigned long long pt_trace_kernel_launches(int which);
-/* the pixel-refinement kernels (pt_kernel.hip: trace_pixels, PT_PIXEL_FAMILY): the form a scene takes (pt_trace_pick's choice, the
- * lists run in parallel), the launch (64 entries x 4 sample slices per workgroup; what a radiance query's launch takes, and the
- * frame's size and camera), names and launch counters */
-int pt_pixel_pick(const PtSceneView &scene);
+/* the pixel refinement (front end PixelFront): 64 entries x 4 sample slices per workgroup; what a radiance query's launch takes,
+ * and the frame's size and camera */
 hipError_t pt_launch_pixels(const PtLaunch &launch, const PtPixels &pixels, hipStream_t stream, int which);
 const char *pt_pixel_kernel_name_of(int which);
 int pt_pixel_kernel_count(void);

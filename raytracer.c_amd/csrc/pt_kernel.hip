@@ -62,13 +62,15 @@
  *   pt_body_pooled.h  render_tiles_pooled   (pt_render_tiles[_tri][_big][_chk], _pool_mem*, _refr_pool*)
  *   pt_body_queued.h  render_tiles_queued   (pt_render_tiles_tri_queued*: parked walks, also with M_REFRACTION)
  *   pt_body_static.h  render_tiles_static   (pt_render_tiles_v0, *_refr, pt_whitted_tiles*, *_mem)
+ *                     trace_sliced          (pt_trace_rays*, pt_trace_pixels*), pend_acquire, reduce_slices
  * This file keeps the kernel family (PT_FAMILY: the entry points, their ids and properties), the AOV kernels (render_aov,
  * PT_AOV_FAMILY: first-hit feature buffers, not members of the family), the ray-query kernels (query_rays, PT_QUERY_FAMILY: closest
- * hits of the caller's rays, a list of their own too), the radiance-query kernels (trace_rays, PT_TRACE_FAMILY: trace_path along the
- * caller's rays, a third such list), the table-building and self-test kernels, pt_untile,
+ * hits of the caller's rays, a list of their own too), the sliced kernels (PT_SLICED_FAMILY: trace_sliced behind the front ends
+ * RayFront -- trace_path along the caller's rays -- and PixelFront -- the render's samples of listed pixels --, one table of two
+ * more such lists), the table-building and self-test kernels, pt_untile,
  * and the host side declared in pt_device.h: the launch plan (pt_plan_launch, around the pick table pt_pick_kernel) and the
- * launchers (pt_launch_render, pt_launch_aov, pt_launch_query, pt_launch_trace).  The four lists are a PtKernelList each (rows + launch
- * counters) and the four launchers go through launch_staged (dynamic-LDS limit, launch, error).
+ * launchers (pt_launch_render, pt_launch_aov, pt_launch_query, pt_launch_trace, pt_launch_pixels).  The five lists are a
+ * PtKernelList each (rows + launch counters) and the five launchers go through launch_staged (dynamic-LDS limit, launch, error).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -220,7 +222,7 @@ PT_FAMILY_DEV(PT_ENTRY)
 #undef PT_ENTRY
 
 /* ---- a kernel list on the host: the rows an X-macro list generates, and how often each was launched in this process
- * (what a test run actually exercised).  The five lists (PT_FAMILY, PT_AOV_FAMILY, PT_QUERY_FAMILY, PT_TRACE_FAMILY, PT_PIXEL_FAMILY) are one of these each;
+ * (what a test run actually exercised).  The five lists (PT_FAMILY, PT_AOV_FAMILY, PT_QUERY_FAMILY and the two columns of PT_SLICED_FAMILY) are one of these each;
  * pt_*_name_of / _count / _launches (pt_device.h) ask it.  The lists' ids come from PT_LIST_ID, the rows of the two plain
  * lists from PT_LIST_INFO; the family's rows carry more (PT_INFO), and each list's entry points have their own signature, so
  * the three ENTRY macros stay apart. */
@@ -578,387 +580,138 @@ enum PtQueryKernelId
 typedef void (*PtQueryKernelFn)(const PtLaunch, const PtQuery);
 static PtKernelList<PtEntryInfo<PtQueryKernelFn>, Q_COUNT> pt_query_kernels = {{PT_QUERY_FAMILY(PT_LIST_INFO)}};
 
-/* ---- radiance-query body: a lane = (ray, sample slice), a workgroup = 64 consecutive rays x 4 slices -------------------------------
- * rt_hip.h has the contract.  render_tiles_static's loop (pt_body_static.h) with three things changed: the lane mapping (ray
- * blockIdx.x * 64 + (threadIdx.x >> 2), slice threadIdx.x & 3; no tiles, `inside` is i < n), the first ray (caller_ray, as
- * query_rays forms it, kept in LDS for the lane's later samples; the stream (seed, index_first + i, s) with its first two draws --
- * render()'s jitter -- taken and discarded, instead of start_sample) and the epilogue (fp64 outputs, per-sample values and per-ray
- * counters; no float image, no tonemap).  The first scan of a ray in the band that is not unit to 2^-40 runs with no_rules, as
- * query_rays scans it; later bounces are vec3_normalize results (or mirror images of such) and keep the rules.  BigPrune and the
- * hull-facet rule are off, as in the static trace_path members (MODE 0 without DEFER_DIR reads no `leaving`).
- * A lane adds its slice's samples s = slice, slice + 4, ... in ascending order to a sum that starts at +0.0; the four slice sums
- * are combined as (S0 + S1) + (S2 + S3) by the static body's shuffles and scaled by 1.0 / (double)S. */
-template <bool REFRACT, bool CHECKER, bool TRIS = false, bool FILT_LDS = true, bool GEOM_LDS = true>
-__device__ __forceinline__ void trace_rays(const PtLaunch &L, const PtTrace &Q)
+/* ---- the two front ends of trace_sliced (pt_body_static.h): what an entry of the caller's list is ------------------------------
+ * RayFront (rt_hip_trace_rays): entry i is ray i of the caller's, formed and judged by caller_ray as query_rays does and kept in LDS
+ * for the lane's later samples; its samples run on the stream (seed, index_first + i, k) with the first two draws -- render()'s
+ * jitter -- taken and discarded.  The first scan of a ray in the band that is not unit to 2^-40 runs with no_rules, as query_rays
+ * scans it; later bounces are vec3_normalize results (or mirror images of such) and keep the rules. */
+struct RayFront
 {
-  static_assert(GEOM_LDS || !FILT_LDS, "a staged filter table comes with staged geometry");
-  constexpr uint32_t RAYS = PT_BLOCK / PT_SLICES; /* rays per workgroup */
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  __shared__ unsigned long long wg_stats[3];
-  __shared__ double ray_lds[6 * RAYS]; /* [component][ray of the workgroup] */
-  SceneCtx S_init = stage_scene<GEOM_LDS, FILT_LDS>(L, lds);
-  __shared__ double atan_tab[CHECKER ? PT_ATAN_TAB : 1];
-  if (CHECKER)
+  typedef PtTrace Args;
+  static constexpr bool RULE_SWITCH = true;
+  static constexpr uint32_t RAYS = PT_SLICED_ENTRIES;
+  struct Entry
   {
-    atan_table_to_lds(atan_tab);
-    S_init.atan_tab = atan_tab;
+    bool valid, band;
+  };
+  static __device__ __forceinline__ double *ray_lds() /* [component][ray of the workgroup]: 3 KB, in the ray kernels only */
+  {
+    __shared__ double ray[6 * RAYS];
+    return ray;
   }
-  const SceneCtx S = S_init;
-  if (threadIdx.x < 3)
-    wg_stats[threadIdx.x] = 0;
-
-  const uint32_t slice = threadIdx.x & (PT_SLICES - 1), ray_in_wg = threadIdx.x / PT_SLICES;
-  const uint64_t i = (uint64_t)blockIdx.x * RAYS + ray_in_wg;
-  const bool inside = i < Q.n;
-  bool valid = false, band = false;
-  if (inside)
+  static __device__ __forceinline__ void entry(Entry &E, const PtLaunch &L, const PtTrace &Q, uint64_t i, bool inside, uint32_t slice, uint32_t ray_in_wg)
   {
-    V3 o, d;
-    double no_limit;
-    valid = caller_ray(L, Q.rays, nullptr, i, Q.camera_uv, Q.normalize, o, d, no_limit, band);
-    if (slice == 0)
+    double *const ray = ray_lds();
+    E.valid = false;
+    E.band = false;
+    if (inside)
     {
-      ray_lds[0 * RAYS + ray_in_wg] = o.x; ray_lds[1 * RAYS + ray_in_wg] = o.y; ray_lds[2 * RAYS + ray_in_wg] = o.z;
-      ray_lds[3 * RAYS + ray_in_wg] = d.x; ray_lds[4 * RAYS + ray_in_wg] = d.y; ray_lds[5 * RAYS + ray_in_wg] = d.z;
-    }
-  }
-  /* the workgroup's slot of the pending-ray pool (PendStack), as the static body takes it */
-  __shared__ uint32_t pend_slot_lds;
-  if (REFRACT && threadIdx.x == 0)
-    pend_slot_lds = pt_pool_acquire(L.pend_flags, L.pend_slots_per_xcd, L.status, PT_FAIL_PEND_SLOT);
-  __syncthreads();
-  const uint32_t pend_slot = REFRACT ? pend_slot_lds : 0u;
-  const bool pend_ok = !REFRACT || pend_slot != 0xFFFFFFFFu;
-  const PendStack stack = {REFRACT && pend_ok ? L.pend_ws + (size_t)pend_slot * L.pend_slot_doubles + threadIdx.x : nullptr,
-                           REFRACT && pend_ok ? (int)L.pend_entries : 0, PT_BLOCK, PT_PEND_FIELDS * PT_BLOCK};
-
-  const uint32_t spp = (uint32_t)L.samples;
-  const uint64_t pixel_key = rt_rng_pixel_key(L.seed, Q.index_first + (uint32_t)i);
-  V3 acc = {0, 0, 0};
-  Path P;
-  P.o = {0, 0, 0};
-  P.d = {0, 0, 1};
-  P.T = {1, 1, 1};
-  P.Ls = {0, 0, 0};
-  P.rng = 1;
-  P.depth = 0;
-  uint32_t n_rays = 0, n_casts = 0;
-  unsigned long long paths = 0, casts = 0; /* of this lane's finished samples */
-  uint32_t s = (valid && pend_ok) ? slice : spp;
-  bool fresh = true;
-  int stack_n = 0;
-  unsigned long long *diag_ptr = L.stats;
-  (void)diag_ptr;
-
-  while (s < spp)
-  {
-    const bool first = fresh;
-    if (fresh)
-    {
-      P.rng = sample_state_from_term(pixel_key, sample_term(s));
-      (void)rnd(P.rng); /* render()'s two jitter draws (raytracer.c:203-206): a sample of a pixel and a sample of a ray */
-      (void)rnd(P.rng); /* with that index see the same draws after them */
-      const uint32_t z = opaque_zero() + ray_in_wg; /* (read here, per sample: hoisted, the ray would hold twelve registers for the whole loop) */
-      P.o = {ray_lds[0 * RAYS + z], ray_lds[1 * RAYS + z], ray_lds[2 * RAYS + z]};
-      P.d = {ray_lds[3 * RAYS + z], ray_lds[4 * RAYS + z], ray_lds[5 * RAYS + z]};
-      P.T = {1, 1, 1};
-      P.Ls = {0, 0, 0};
-      P.depth = 0;
-      fresh = false;
-    }
-    n_rays++;
-    const bool finished = trace_step<1, REFRACT, CHECKER, TRIS, FILT_LDS, 0, false, false, false, PendStack, true>(
-        S, P, n_casts, diag_ptr, stack, stack_n, nullptr, nullptr, first && band);
-    if (finished)
-    {
-      acc = v_add(acc, P.Ls);
-      if (Q.samples)
+      V3 o, d;
+      double no_limit;
+      E.valid = caller_ray(L, Q.rays, nullptr, i, Q.camera_uv, Q.normalize, o, d, no_limit, E.band);
+      if (slice == 0)
       {
-        double *q = Q.samples + 3u * (i * spp + s);
-        q[0] = P.Ls.x; q[1] = P.Ls.y; q[2] = P.Ls.z;
+        ray[0 * RAYS + ray_in_wg] = o.x; ray[1 * RAYS + ray_in_wg] = o.y; ray[2 * RAYS + ray_in_wg] = o.z;
+        ray[3 * RAYS + ray_in_wg] = d.x; ray[4 * RAYS + ray_in_wg] = d.y; ray[5 * RAYS + ray_in_wg] = d.z;
       }
-      paths += n_rays;
-      casts += n_casts;
-      n_rays = n_casts = 0;
-      s += PT_SLICES;
-      fresh = true;
     }
   }
-
-  const double quiet_nan = __longlong_as_double(0x7FF8000000000000ll);
-  if (inside && Q.samples && !(valid && pend_ok)) /* an invalid ray: zeros; a workgroup without its pool slot: NaN (the render's rule) */
-    for (uint32_t k = slice; k < spp; k += PT_SLICES)
-    {
-      double *q = Q.samples + 3u * (i * spp + k);
-      q[0] = q[1] = q[2] = valid ? quiet_nan : 0.0;
-    }
-  /* per-ray mean: the static body's fixed-order reduction over the 4 slice lanes */
-  acc.x += __shfl_xor(acc.x, 1);
-  acc.y += __shfl_xor(acc.y, 1);
-  acc.z += __shfl_xor(acc.z, 1);
-  acc.x += __shfl_xor(acc.x, 2);
-  acc.y += __shfl_xor(acc.y, 2);
-  acc.z += __shfl_xor(acc.z, 2);
-  V3 mean = v_scale(acc, 1.0 / (double)spp);
-  if (valid && !pend_ok)
-    mean.x = mean.y = mean.z = quiet_nan;
-  if (paths)
+  static __device__ __forceinline__ uint32_t stream(const PtTrace &Q, const Entry &, uint64_t i) { return Q.index_first + (uint32_t)i; }
+  static __device__ __forceinline__ void fresh(Path &P, const PtTrace &, const Entry &, uint64_t pixel_key, uint32_t k, uint32_t ray_in_wg)
   {
-    atomicAdd(&wg_stats[0], paths);
-    atomicAdd(&wg_stats[1], casts);
+    const double *const ray = ray_lds();
+    P.rng = sample_state_from_term(pixel_key, sample_term(k));
+    (void)rnd(P.rng); /* render()'s two jitter draws (raytracer.c:203-206): a sample of a pixel and a sample of a ray */
+    (void)rnd(P.rng); /* with that index see the same draws after them */
+    const uint32_t z = opaque_zero() + ray_in_wg; /* (read here, per sample: hoisted, the ray would hold twelve registers for the whole loop) */
+    P.o = {ray[0 * RAYS + z], ray[1 * RAYS + z], ray[2 * RAYS + z]};
+    P.d = {ray[3 * RAYS + z], ray[4 * RAYS + z], ray[5 * RAYS + z]};
+    P.T = {1, 1, 1};
+    P.Ls = {0, 0, 0};
+    P.depth = 0;
   }
-  paths += __shfl_xor(paths, 1);
-  casts += __shfl_xor(casts, 1);
-  paths += __shfl_xor(paths, 2);
-  casts += __shfl_xor(casts, 2);
-  if (inside && slice == 0)
+  static __device__ __forceinline__ bool no_rules(const Entry &E, bool first) { return first && E.band; }
+  static __device__ __forceinline__ void store_extra(const PtTrace &Q, uint64_t i, uint32_t ray_in_wg)
   {
-    if (valid)
-      atomicAdd(&wg_stats[2], 1ull);
-    if (Q.status)
-      Q.status[i] = valid ? 1u : 2u;
-    if (Q.radiance)
-    {
-      double *q = Q.radiance + 3u * i;
-      q[0] = mean.x; q[1] = mean.y; q[2] = mean.z;
-    }
-    if (Q.paths)
-      Q.paths[i] = paths;
-    if (Q.casts)
-      Q.casts[i] = casts;
+    const double *const ray = ray_lds();
     if (Q.ray)
     {
       double2 *q = reinterpret_cast<double2 *>(Q.ray) + 3u * i;
-      q[0] = double2{ray_lds[0 * RAYS + ray_in_wg], ray_lds[1 * RAYS + ray_in_wg]};
-      q[1] = double2{ray_lds[2 * RAYS + ray_in_wg], ray_lds[3 * RAYS + ray_in_wg]};
-      q[2] = double2{ray_lds[4 * RAYS + ray_in_wg], ray_lds[5 * RAYS + ray_in_wg]};
+      q[0] = double2{ray[0 * RAYS + ray_in_wg], ray[1 * RAYS + ray_in_wg]};
+      q[1] = double2{ray[2 * RAYS + ray_in_wg], ray[3 * RAYS + ray_in_wg]};
+      q[2] = double2{ray[4 * RAYS + ray_in_wg], ray[5 * RAYS + ray_in_wg]};
     }
   }
-  __syncthreads();
-  if (threadIdx.x == 0)
+};
+
+/* PixelFront (rt_hip_trace_pixels): entry i names pixel p = pixels[i] of the launch's frame (x = p % w, y = p / w); p >= w * h is the
+ * invalid entry.  Sample k of the entry is the render's sample sample_first + k of that pixel: the fresh branch is start_sample --
+ * the stream (seed, p, s), its first two draws the jitter, get_camera_ray through div_small_int and the unscaled normalize --
+ * exactly what render_tiles_static runs per sample; no ray is stored or re-read, so there is no LDS of its own.  The slice of
+ * sample k is k mod 4 (the list's own numbering: sample_first shifts the stream, not the reduction).  No first scan runs without
+ * the rules: a camera ray is a vec3_normalize result (RULE_SWITCH stays off, as in the render). */
+struct PixelFront
+{
+  typedef PtPixels Args;
+  static constexpr bool RULE_SWITCH = false;
+  struct Entry
   {
-    if (L.stats)
-    {
-      const unsigned long long c = wg_stats[1];
-      atomicAdd(&L.stats[0], wg_stats[0]);
-      atomicAdd(&L.stats[1], c);
-      atomicAdd(&L.stats[2], c * (unsigned long long)(S.n_sph + S.n_tri));
-      atomicAdd(&L.stats[3], wg_stats[2] * (unsigned long long)spp);
-    }
-    if (REFRACT && pend_ok)
-      atomicExch(&L.pend_flags[pend_slot], 0u); /* every lane is past its last pop (the barrier above) */
+    bool valid;
+    uint32_t pixel, px, py;
+    CameraRegs cam;
+  };
+  static __device__ __forceinline__ void entry(Entry &E, const PtLaunch &L, const PtPixels &Q, uint64_t i, bool inside, uint32_t, uint32_t)
+  {
+    E.pixel = inside ? Q.pixels[i] : 0xFFFFFFFFu;
+    E.valid = inside && E.pixel < Q.n_pixels;
+    E.px = E.pixel % (uint32_t)L.width;
+    E.py = E.pixel / (uint32_t)L.width;
+    E.cam = load_camera(L);
   }
-}
+  static __device__ __forceinline__ uint32_t stream(const PtPixels &, const Entry &E, uint64_t) { return E.pixel; }
+  static __device__ __forceinline__ void fresh(Path &P, const PtPixels &Q, const Entry &E, uint64_t pixel_key, uint32_t k, uint32_t)
+  { /* the entry's sample k is the pixel's sample sample_first + k (< 2^31) */
+    start_sample(P, E.cam, pixel_key, E.px, E.py, sample_term(Q.sample_first + k));
+  }
+  static __device__ __forceinline__ bool no_rules(const Entry &, bool) { return false; }
+  static __device__ __forceinline__ void store_extra(const PtPixels &, uint64_t, uint32_t) {}
+};
 
-/* ---- the radiance-query kernels (rt_hip_trace_rays): a third list of their own -- no rows of the pick table.  The scene alone picks
- * the form (pt_trace_pick, as pt_query_pick); the five forms mirror the static trace_path members K_REFR, K_BIG_REFR, K_TRI_REFR,
- * K_TRI_BIG_REFR and K_MEM, every material's code in each:
- *   pt_trace_rays          spheres staged, filter staged (sign-test form)
- *   pt_trace_rays_big      spheres staged, filter by scalar loads
- *   pt_trace_rays_tri      + triangles through the flat filter and the fp32 pre-test
- *   pt_trace_rays_tri_big  + triangles through the hierarchy
- *   pt_trace_rays_mem      geometry from memory, triangles (if any) through the hierarchy
- * Body: trace_rays<REFRACT, CHECKER, TRIS, FILT_LDS, GEOM_LDS>. */
-#define PT_TRACE_FAMILY(X) \
-  X(T_RAYS,    pt_trace_rays,         (PT_BLOCK, PT_MIN_WAVES_REFR),     trace_rays<true, true>) \
-  X(T_BIG,     pt_trace_rays_big,     (PT_BLOCK, PT_MIN_WAVES_REFR),     trace_rays<true, true, false, false>) \
-  X(T_TRI,     pt_trace_rays_tri,     (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), trace_rays<true, true, true, true>) \
-  X(T_TRI_BIG, pt_trace_rays_tri_big, (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), trace_rays<true, true, true, false>) \
-  X(T_MEM,     pt_trace_rays_mem,     (PT_BLOCK),                        trace_rays<true, true, true, false, false>)
+/* ---- the ten sliced kernels: the radiance queries (rt_hip_trace_rays) and the pixel refinement (rt_hip_trace_pixels), two lists of
+ * their own -- no rows of the pick table -- generated from ONE table, a row per geometric form.  The scene alone picks the row
+ * (pt_trace_pick, for both lists, as pt_query_pick); the five forms mirror the static trace_path members K_REFR, K_BIG_REFR,
+ * K_TRI_REFR, K_TRI_BIG_REFR and K_MEM, every material's code in each:
+ *   pt_trace_{rays,pixels}          spheres staged, filter staged (sign-test form)
+ *   pt_trace_{rays,pixels}_big      spheres staged, filter by scalar loads
+ *   pt_trace_{rays,pixels}_tri      + triangles through the flat filter and the fp32 pre-test
+ *   pt_trace_{rays,pixels}_tri_big  + triangles through the hierarchy
+ *   pt_trace_{rays,pixels}_mem      geometry from memory, triangles (if any) through the hierarchy
+ * Body: trace_sliced<Front, REFRACT = true, CHECKER = true, TRIS, FILT_LDS, GEOM_LDS>. */
+#define PT_SLICED_FAMILY(X) \
+  X(T_RAYS,    pt_trace_rays,         pt_trace_pixels,         (PT_BLOCK, PT_MIN_WAVES_REFR),     false, true,  true) \
+  X(T_BIG,     pt_trace_rays_big,     pt_trace_pixels_big,     (PT_BLOCK, PT_MIN_WAVES_REFR),     false, false, true) \
+  X(T_TRI,     pt_trace_rays_tri,     pt_trace_pixels_tri,     (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), true,  true,  true) \
+  X(T_TRI_BIG, pt_trace_rays_tri_big, pt_trace_pixels_tri_big, (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), true,  false, true) \
+  X(T_MEM,     pt_trace_rays_mem,     pt_trace_pixels_mem,     (PT_BLOCK),                        true,  false, false)
 
-#define PT_TRACE_ENTRY(id, name, bounds, ...) \
-  extern "C" __global__ __launch_bounds__ bounds void name(const PtLaunch L, const PtTrace Q) { __VA_ARGS__(L, Q); }
-PT_TRACE_FAMILY(PT_TRACE_ENTRY)
-#undef PT_TRACE_ENTRY
+#define PT_SLICED_ENTRY(id, rays, pixels, bounds, ...) \
+  extern "C" __global__ __launch_bounds__ bounds void rays(const PtLaunch L, const PtTrace Q) { trace_sliced<RayFront, true, true, __VA_ARGS__>(L, Q); } \
+  extern "C" __global__ __launch_bounds__ bounds void pixels(const PtLaunch L, const PtPixels Q) { trace_sliced<PixelFront, true, true, __VA_ARGS__>(L, Q); }
+PT_SLICED_FAMILY(PT_SLICED_ENTRY)
+#undef PT_SLICED_ENTRY
 
 enum PtTraceKernelId
 {
-  PT_TRACE_FAMILY(PT_LIST_ID) T_COUNT
+  PT_SLICED_FAMILY(PT_LIST_ID) T_COUNT
 };
 typedef void (*PtTraceKernelFn)(const PtLaunch, const PtTrace);
-#define PT_TRACE_INFO(id, name, bounds, ...) {#name, name},
-static PtKernelList<PtEntryInfo<PtTraceKernelFn>, T_COUNT> pt_trace_kernels = {{PT_TRACE_FAMILY(PT_TRACE_INFO)}};
-#undef PT_TRACE_INFO
-
-/* ---- pixel-refinement body: a lane = (entry, sample slice), a workgroup = 64 consecutive entries x 4 slices ----------------------
- * rt_hip.h has the contract (rt_hip_trace_pixels).  A SIBLING of trace_rays, not a template option of it: the entry's front end is
- * another (a pixel index instead of a ray record: PtPixels has other fields than PtTrace, and a shared argument struct would move
- * the kernel arguments of the five radiance-query kernels), so sharing would have saved the loop's forty lines at the price of
- * their listings.  What is the same, statement for statement: the lane mapping, the pool slot, the loop around trace_step, the
- * per-sample store, the shuffles of the mean, the counters and the epilogue.  What differs:
- *   - entry i names pixel p = pixels[i] of the launch's frame (x = p % w, y = p / w); p >= w * h is the invalid entry;
- *   - sample k of the entry is the render's sample s = sample_first + k of that pixel: the fresh branch is start_sample -- the
- *     stream (seed, p, s), its first two draws the jitter, get_camera_ray of ((x + r0) / (w - 1), (y + r1) / (h - 1)) through
- *     div_small_int and the unscaled normalize -- exactly what render_tiles_static runs per sample; no ray is stored or re-read;
- *   - the slice of sample k is k mod 4 (the list's own numbering: sample_first shifts the stream, not the reduction);
- *   - no first scan runs without the rules: a camera ray is a vec3_normalize result (RULE_SWITCH stays off, as in the render). */
-template <bool REFRACT, bool CHECKER, bool TRIS = false, bool FILT_LDS = true, bool GEOM_LDS = true>
-__device__ __forceinline__ void trace_pixels(const PtLaunch &L, const PtPixels &Q)
-{
-  static_assert(GEOM_LDS || !FILT_LDS, "a staged filter table comes with staged geometry");
-  constexpr uint32_t ENTRIES = PT_BLOCK / PT_SLICES; /* entries per workgroup */
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  __shared__ unsigned long long wg_stats[3];
-  SceneCtx S_init = stage_scene<GEOM_LDS, FILT_LDS>(L, lds);
-  __shared__ double atan_tab[CHECKER ? PT_ATAN_TAB : 1];
-  if (CHECKER)
-  {
-    atan_table_to_lds(atan_tab);
-    S_init.atan_tab = atan_tab;
-  }
-  const SceneCtx S = S_init;
-  if (threadIdx.x < 3)
-    wg_stats[threadIdx.x] = 0;
-
-  const uint32_t slice = threadIdx.x & (PT_SLICES - 1), entry_in_wg = threadIdx.x / PT_SLICES;
-  const uint64_t i = (uint64_t)blockIdx.x * ENTRIES + entry_in_wg;
-  const bool inside = i < Q.n;
-  const uint32_t pixel = inside ? Q.pixels[i] : 0xFFFFFFFFu;
-  const bool valid = inside && pixel < Q.n_pixels;
-  const uint32_t px = pixel % (uint32_t)L.width, py = pixel / (uint32_t)L.width;
-  const CameraRegs cam = load_camera(L);
-  /* the workgroup's slot of the pending-ray pool (PendStack), as the static body takes it */
-  __shared__ uint32_t pend_slot_lds;
-  if (REFRACT && threadIdx.x == 0)
-    pend_slot_lds = pt_pool_acquire(L.pend_flags, L.pend_slots_per_xcd, L.status, PT_FAIL_PEND_SLOT);
-  __syncthreads();
-  const uint32_t pend_slot = REFRACT ? pend_slot_lds : 0u;
-  const bool pend_ok = !REFRACT || pend_slot != 0xFFFFFFFFu;
-  const PendStack stack = {REFRACT && pend_ok ? L.pend_ws + (size_t)pend_slot * L.pend_slot_doubles + threadIdx.x : nullptr,
-                           REFRACT && pend_ok ? (int)L.pend_entries : 0, PT_BLOCK, PT_PEND_FIELDS * PT_BLOCK};
-
-  const uint32_t spp = (uint32_t)L.samples;
-  const uint64_t pixel_key = rt_rng_pixel_key(L.seed, pixel);
-  V3 acc = {0, 0, 0};
-  Path P;
-  P.o = {0, 0, 0};
-  P.d = {0, 0, 1};
-  P.T = {1, 1, 1};
-  P.Ls = {0, 0, 0};
-  P.rng = 1;
-  P.depth = 0;
-  uint32_t n_rays = 0, n_casts = 0;
-  unsigned long long paths = 0, casts = 0; /* of this lane's finished samples */
-  uint32_t k = (valid && pend_ok) ? slice : spp; /* the entry's sample k is the pixel's sample sample_first + k (< 2^31) */
-  bool fresh = true;
-  int stack_n = 0;
-  unsigned long long *diag_ptr = L.stats;
-  (void)diag_ptr;
-
-  while (k < spp)
-  {
-    if (fresh)
-    {
-      start_sample(P, cam, pixel_key, px, py, sample_term(Q.sample_first + k));
-      fresh = false;
-    }
-    n_rays++;
-    const bool finished = trace_step<1, REFRACT, CHECKER, TRIS, FILT_LDS>(S, P, n_casts, diag_ptr, stack, stack_n);
-    if (finished)
-    {
-      acc = v_add(acc, P.Ls);
-      if (Q.samples)
-      {
-        double *q = Q.samples + 3u * (i * spp + k);
-        q[0] = P.Ls.x; q[1] = P.Ls.y; q[2] = P.Ls.z;
-      }
-      paths += n_rays;
-      casts += n_casts;
-      n_rays = n_casts = 0;
-      k += PT_SLICES;
-      fresh = true;
-    }
-  }
-
-  const double quiet_nan = __longlong_as_double(0x7FF8000000000000ll);
-  if (inside && Q.samples && !(valid && pend_ok)) /* an invalid entry: zeros; a workgroup without its pool slot: NaN (the render's rule) */
-    for (uint32_t j = slice; j < spp; j += PT_SLICES)
-    {
-      double *q = Q.samples + 3u * (i * spp + j);
-      q[0] = q[1] = q[2] = valid ? quiet_nan : 0.0;
-    }
-  /* per-entry mean: the static body's fixed-order reduction over the 4 slice lanes */
-  acc.x += __shfl_xor(acc.x, 1);
-  acc.y += __shfl_xor(acc.y, 1);
-  acc.z += __shfl_xor(acc.z, 1);
-  acc.x += __shfl_xor(acc.x, 2);
-  acc.y += __shfl_xor(acc.y, 2);
-  acc.z += __shfl_xor(acc.z, 2);
-  V3 mean = v_scale(acc, 1.0 / (double)spp);
-  if (valid && !pend_ok)
-    mean.x = mean.y = mean.z = quiet_nan;
-  if (paths)
-  {
-    atomicAdd(&wg_stats[0], paths);
-    atomicAdd(&wg_stats[1], casts);
-  }
-  paths += __shfl_xor(paths, 1);
-  casts += __shfl_xor(casts, 1);
-  paths += __shfl_xor(paths, 2);
-  casts += __shfl_xor(casts, 2);
-  if (inside && slice == 0)
-  {
-    if (valid)
-      atomicAdd(&wg_stats[2], 1ull);
-    if (Q.status)
-      Q.status[i] = valid ? 1u : 2u;
-    if (Q.radiance)
-    {
-      double *q = Q.radiance + 3u * i;
-      q[0] = mean.x; q[1] = mean.y; q[2] = mean.z;
-    }
-    if (Q.paths)
-      Q.paths[i] = paths;
-    if (Q.casts)
-      Q.casts[i] = casts;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    if (L.stats)
-    {
-      const unsigned long long c = wg_stats[1];
-      atomicAdd(&L.stats[0], wg_stats[0]);
-      atomicAdd(&L.stats[1], c);
-      atomicAdd(&L.stats[2], c * (unsigned long long)(S.n_sph + S.n_tri));
-      atomicAdd(&L.stats[3], wg_stats[2] * (unsigned long long)spp);
-    }
-    if (REFRACT && pend_ok)
-      atomicExch(&L.pend_flags[pend_slot], 0u); /* every lane is past its last pop (the barrier above) */
-  }
-}
-
-/* ---- the pixel-refinement kernels (rt_hip_trace_pixels): a fourth list of their own -- no rows of the pick table.  The five forms
- * mirror PT_TRACE_FAMILY row for row and are picked as that list is (pt_pixel_pick = pt_trace_pick: the enums run in parallel):
- *   pt_trace_pixels          spheres staged, filter staged (sign-test form)
- *   pt_trace_pixels_big      spheres staged, filter by scalar loads
- *   pt_trace_pixels_tri      + triangles through the flat filter and the fp32 pre-test
- *   pt_trace_pixels_tri_big  + triangles through the hierarchy
- *   pt_trace_pixels_mem      geometry from memory, triangles (if any) through the hierarchy
- * Body: trace_pixels<REFRACT, CHECKER, TRIS, FILT_LDS, GEOM_LDS>. */
-#define PT_PIXEL_FAMILY(X) \
-  X(P_PIXELS,  pt_trace_pixels,         (PT_BLOCK, PT_MIN_WAVES_REFR),     trace_pixels<true, true>) \
-  X(P_BIG,     pt_trace_pixels_big,     (PT_BLOCK, PT_MIN_WAVES_REFR),     trace_pixels<true, true, false, false>) \
-  X(P_TRI,     pt_trace_pixels_tri,     (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), trace_pixels<true, true, true, true>) \
-  X(P_TRI_BIG, pt_trace_pixels_tri_big, (PT_BLOCK, PT_MIN_WAVES_REFR_TRI), trace_pixels<true, true, true, false>) \
-  X(P_MEM,     pt_trace_pixels_mem,     (PT_BLOCK),                        trace_pixels<true, true, true, false, false>)
-
-#define PT_PIXEL_ENTRY(id, name, bounds, ...) \
-  extern "C" __global__ __launch_bounds__ bounds void name(const PtLaunch L, const PtPixels Q) { __VA_ARGS__(L, Q); }
-PT_PIXEL_FAMILY(PT_PIXEL_ENTRY)
-#undef PT_PIXEL_ENTRY
-
-enum PtPixelKernelId
-{
-  PT_PIXEL_FAMILY(PT_LIST_ID) P_COUNT
-};
-static_assert((int)P_PIXELS == (int)T_RAYS && (int)P_BIG == (int)T_BIG && (int)P_TRI == (int)T_TRI && (int)P_TRI_BIG == (int)T_TRI_BIG &&
-                  (int)P_MEM == (int)T_MEM && (int)P_COUNT == (int)T_COUNT,
-              "the pixel list mirrors the trace list: pt_pixel_pick is pt_trace_pick");
 typedef void (*PtPixelKernelFn)(const PtLaunch, const PtPixels);
-#define PT_PIXEL_INFO(id, name, bounds, ...) {#name, name},
-static PtKernelList<PtEntryInfo<PtPixelKernelFn>, P_COUNT> pt_pixel_kernels = {{PT_PIXEL_FAMILY(PT_PIXEL_INFO)}};
-#undef PT_PIXEL_INFO
+#define PT_SLICED_RAYS(id, rays, pixels, ...) {#rays, rays},
+#define PT_SLICED_PIXELS(id, rays, pixels, ...) {#pixels, pixels},
+static PtKernelList<PtEntryInfo<PtTraceKernelFn>, T_COUNT> pt_trace_kernels = {{PT_SLICED_FAMILY(PT_SLICED_RAYS)}};
+static PtKernelList<PtEntryInfo<PtPixelKernelFn>, T_COUNT> pt_pixel_kernels = {{PT_SLICED_FAMILY(PT_SLICED_PIXELS)}};
+#undef PT_SLICED_RAYS
+#undef PT_SLICED_PIXELS
 
 /* The sample count a resolve divides slot `slot` by: the launch's, or -- an accumulation with frozen tiles (rt_hip_accum_freeze) --
  * the slot's own where it has one (0: the slot is live and holds the launch's count). */
@@ -1039,13 +792,7 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_slices(const P
   uint32_t px, py;
   const bool inside = tile_pixel(L.tiles_x, tile, pix_in_tile, L.width, L.height, px, py);
   const double *const sum = L.slice_ws + (size_t)slot * (3u * PT_BLOCK) + threadIdx.x;
-  V3 acc = {sum[0], sum[PT_BLOCK], sum[2 * PT_BLOCK]};
-  acc.x += __shfl_xor(acc.x, 1);
-  acc.y += __shfl_xor(acc.y, 1);
-  acc.z += __shfl_xor(acc.z, 1);
-  acc.x += __shfl_xor(acc.x, 2);
-  acc.y += __shfl_xor(acc.y, 2);
-  acc.z += __shfl_xor(acc.z, 2);
+  const V3 acc = reduce_slices({sum[0], sum[PT_BLOCK], sum[2 * PT_BLOCK]});
   const V3 mean = v_scale(acc, 1.0 / (double)(uint32_t)resolve_samples(L, tile_samples, slot));
   if (slice == 0)
   {
@@ -2564,7 +2311,7 @@ hipError_t pt_launch_aov(const PtLaunch &launch, const PtAovOut &out, hipStream_
 }
 
 /* ---- the ray kernels (query, radiance query, pixel refinement): which of a list's five geometric forms a scene takes ----------
- * One decision for the three lists; each gives its own ids (the query list's order differs from the other two's). */
+ * One decision for the query list and the sliced table; each gives its own ids (their orders differ). */
 static int ray_form_pick(const PtSceneView &scene, int rays, int big, int tri, int tri_big, int mem)
 {
   if (!pt_geom_in_lds(scene))
@@ -2575,7 +2322,7 @@ static int ray_form_pick(const PtSceneView &scene, int rays, int big, int tri, i
   return tris ? tri_big : big;
 }
 
-/* every form of the radiance-query and pixel lists pushes pending second children: its pool, as pt_launch_render asks of a
+/* every form of the sliced kernels pushes pending second children: its pool, as pt_launch_render asks of a
  * PEND_POOL member */
 static bool pend_pool_ready(const PtLaunch &launch)
 {
@@ -2603,8 +2350,26 @@ hipError_t pt_launch_query(const PtLaunch &launch, const PtQuery &query, hipStre
   return e;
 }
 
-/* ---- the radiance-query kernels: which form a scene takes, and the launch ------------------------------------------------- */
+/* ---- the sliced kernels (radiance queries, pixel refinement): which form a scene takes, and the launch ------------------------
+ * One pick for both lists (they are the columns of PT_SLICED_FAMILY), one launch behind both launchers: n entries of `list`'s
+ * form `which`, 64 entries x 4 sample slices per workgroup.  args_ok: the caller's own argument checks. */
 int pt_trace_pick(const PtSceneView &scene) { return ray_form_pick(scene, T_RAYS, T_BIG, T_TRI, T_TRI_BIG, T_MEM); }
+
+template <class List, class Args>
+static hipError_t launch_sliced(List &list, int which, bool args_ok, const PtLaunch &launch, const Args &args, hipStream_t stream)
+{
+#ifdef PT_DIAG
+  return hipErrorNotSupported; /* (the diagnostic build counts into stats[4 ..]: a caller's d_stats has RT_HIP_NSTATS words) */
+#endif
+  if (!list.valid(which) || !args_ok || args.n == 0u || args.n > 0xFFFFFFFFull || launch.samples < 1 || !pend_pool_ready(launch))
+    return hipErrorInvalidValue;
+  const size_t lds_bytes = which == T_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the query launch */
+  const uint32_t blocks = (uint32_t)((args.n + PT_SLICED_ENTRIES - 1u) / PT_SLICED_ENTRIES); /* at most 2^26 */
+  const hipError_t e = launch_staged(list[which].fn, blocks, lds_bytes, stream, launch, args);
+  if (e == hipSuccess)
+    list.launched(which);
+  return e;
+}
 
 const char *pt_trace_kernel_name_of(int which) { return pt_trace_kernels.name_of(which); }
 int pt_trace_kernel_count(void) { return T_COUNT; }
@@ -2612,48 +2377,18 @@ unsigned long long pt_trace_kernel_launches(int which) { return pt_trace_kernels
 
 hipError_t pt_launch_trace(const PtLaunch &launch, const PtTrace &trace, hipStream_t stream, int which)
 {
-#ifdef PT_DIAG
-  return hipErrorNotSupported; /* (the diagnostic build counts into stats[4 ..]: a caller's d_stats has RT_HIP_NSTATS words) */
-#endif
-  if (!pt_trace_kernels.valid(which) || trace.n == 0u || trace.n > 0xFFFFFFFFull || (uint64_t)trace.index_first + trace.n > 0x100000000ull ||
-      launch.samples < 1)
-    return hipErrorInvalidValue;
-  if (!pend_pool_ready(launch))
-    return hipErrorInvalidValue;
-  const size_t lds_bytes = which == T_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the query launch */
-  const uint32_t rays_per_wg = PT_BLOCK / PT_SLICES;
-  const uint32_t blocks = (uint32_t)((trace.n + rays_per_wg - 1u) / rays_per_wg); /* at most 2^26 */
-  const hipError_t e = launch_staged(pt_trace_kernels[which].fn, blocks, lds_bytes, stream, launch, trace);
-  if (e == hipSuccess)
-    pt_trace_kernels.launched(which);
-  return e;
+  return launch_sliced(pt_trace_kernels, which, (uint64_t)trace.index_first + trace.n <= 0x100000000ull, launch, trace, stream);
 }
 
-/* ---- the pixel-refinement kernels: which form a scene takes, and the launch ------------------------------------------------ */
-int pt_pixel_pick(const PtSceneView &scene) { return pt_trace_pick(scene); } /* (the lists run in parallel: static_assert at PT_PIXEL_FAMILY) */
-
 const char *pt_pixel_kernel_name_of(int which) { return pt_pixel_kernels.name_of(which); }
-int pt_pixel_kernel_count(void) { return P_COUNT; }
+int pt_pixel_kernel_count(void) { return T_COUNT; }
 unsigned long long pt_pixel_kernel_launches(int which) { return pt_pixel_kernels.launches(which); }
 
 hipError_t pt_launch_pixels(const PtLaunch &launch, const PtPixels &pixels, hipStream_t stream, int which)
 {
-#ifdef PT_DIAG
-  return hipErrorNotSupported; /* (as pt_launch_trace: the diagnostic build counts into stats[4 ..]) */
-#endif
-  if (!pt_pixel_kernels.valid(which) || pixels.n == 0u || pixels.n > 0xFFFFFFFFull || launch.samples < 1 ||
-      (uint64_t)pixels.sample_first + (uint64_t)launch.samples > 0x80000000ull || launch.width < 2 || launch.height < 2 ||
-      (uint64_t)launch.width * (uint64_t)launch.height != (uint64_t)pixels.n_pixels)
-    return hipErrorInvalidValue;
-  if (!pend_pool_ready(launch))
-    return hipErrorInvalidValue;
-  const size_t lds_bytes = which == P_MEM ? 0 : pt_render_lds_bytes(launch.scene); /* the staged scene, as the trace launch */
-  const uint32_t per_wg = PT_BLOCK / PT_SLICES;
-  const uint32_t blocks = (uint32_t)((pixels.n + per_wg - 1u) / per_wg); /* at most 2^26 */
-  const hipError_t e = launch_staged(pt_pixel_kernels[which].fn, blocks, lds_bytes, stream, launch, pixels);
-  if (e == hipSuccess)
-    pt_pixel_kernels.launched(which);
-  return e;
+  const bool args_ok = (uint64_t)pixels.sample_first + (uint64_t)launch.samples <= 0x80000000ull && launch.width >= 2 && launch.height >= 2 &&
+                       (uint64_t)launch.width * (uint64_t)launch.height == (uint64_t)pixels.n_pixels;
+  return launch_sliced(pt_pixel_kernels, which, args_ok, launch, pixels, stream);
 }
 
 /* ---- the compaction's launches (rt_hip_select_pixels) ------------------------------------------------------------------------

@@ -2900,7 +2900,7 @@ int pixels_launch(const RtHipScene *scene, const RtHipCamera *camera, const uint
                       .sample_first = (uint32_t)p->sample_first, .status = d_out->status, .radiance = d_out->radiance,
                       .samples = d_out->samples, .paths = reinterpret_cast<unsigned long long *>(d_out->paths),
                       .casts = reinterpret_cast<unsigned long long *>(d_out->casts)};
-  const int which = pt_pixel_pick(scene->view);
+  const int which = pt_trace_pick(scene->view);
   return pooled_launch(scene, L, stream, pt_pixel_kernel_name_of(which), [&] { return pt_launch_pixels(L, Q, stream, which); });
 }
 
@@ -4094,7 +4094,7 @@ void rt_hip_pixel_defaults(RtHipPixelParams *params)
   params->integrator = RT_HIP_TRACE_PATH;
 }
 
-const char *rt_hip_pixel_kernel_name(const RtHipScene *scene) { return scene ? pt_pixel_kernel_name_of(pt_pixel_pick(scene->view)) : ""; }
+const char *rt_hip_pixel_kernel_name(const RtHipScene *scene) { return scene ? pt_pixel_kernel_name_of(pt_trace_pick(scene->view)) : ""; }
 
 int rt_hip_pixel_kernel_count(void) { return pt_pixel_kernel_count(); }
 
