@@ -390,7 +390,10 @@ const char *rt_hip_aov_kernel_launches(int index, uint64_t *launches);
  *   normal  3 double   as the AOV contract: spheres vec3_normalize(point - centre), triangles       0
  *                      calculate_surface_normal; never flipped
  *   bary    2 double   triangles: the winner's own barycentric (u, v) as intersect_triangle leaves  0
- *                      them (rt_hip_selftest_intersect's h_tuv[1..2]); spheres: 0
+ *                      them, read off as the texture blend of the corners (0, 0), (1, 0), (0, 1): the value
+ *                      of rt_hip_selftest_intersect's h_tuv[1..2] plus 0.0 -- equal to it but for a zero,
+ *                      which is -0.0 there for some rays through a vertex or along an edge and always
+ *                      +0.0 here, as the blend leaves it; spheres: 0
  *   ray     6 double   the ray the scan used, after CAMERA_UV / NORMALIZE (also for misses; invalid rays: as computed)
  * Everything is fp64 in the reference's order: for every valid ray the outputs equal the compiled reference bit for bit.
  * params->origin_radius (>= 0, finite) is a hint for how far from the world origin the rays start.  It takes the place of the

@@ -522,8 +522,11 @@ __device__ __forceinline__ void query_rays(const PtLaunch &L, const PtQuery &Q)
       n = ld3(S.tri_normal + 3 * (size_t)ti);       /* calculate_surface_normal */
       object = S.tri_object[ti] & ~(PT_HULL_PLUS | PT_HULL_MINUS);
       prim = ti;
-      bu = bary_u;
-      bv = bary_v;
+      /* the reference shows a barycentric only through its texture blend, st0 (1 - u - v) + st1 u + st2 v with the corners (0, 0),
+       * (1, 0), (0, 1): 0 w + 1 u + 0 v is u for every u but -0.0 (f < 0 times a zero dot product: a ray through a vertex or along
+       * an edge), which the sum with +0 turns into +0.0.  The same sum here. */
+      bu = bary_u + 0.0;
+      bv = bary_v + 0.0;
     }
   }
   if (Q.status)

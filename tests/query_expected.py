@@ -3,7 +3,7 @@
 IEEE operations), the validity rule, one intersect() -- the reference's scan with its mesh block revived (intersect_mesh_scene:
 the winner's own t, point, normal and id) -- and the t_max rule.  prim is the lowest global triangle index of the winning mesh
 whose compiled intersect_triangle gives the winner's t, bary that call's u, v (read off as texture coordinates of the corners
-(0, 0), (1, 0), (0, 1): 0 * w + 1 * u + 0 * v is u exactly).  Also the ray sets the GPU tests query, built so that the reference's
+(0, 0), (1, 0), (0, 1): 0 * w + 1 * u + 0 * v is u exactly, but for u = -0.0, which the sum turns into +0.0).  Also the ray sets the GPU tests query, built so that the reference's
 answers are non-trivial (tests/test_query_cpu.py asserts that).
 """
 import numpy as np

@@ -80,6 +80,8 @@ def test_struct_sizes_and_names():
     assert names == ["pt_query_rays", "pt_query_rays_tri", "pt_query_rays_big", "pt_query_rays_tri_big", "pt_query_rays_mem"]
     assert shim.rt_hip_query_kernel_launches(n, None) is None and shim.rt_hip_query_kernel_launches(-1, None) is None
     assert {form for form, _ in Q.SCENES.values() if form} == set(names)   # the GPU module reaches every form
+    import query_edge_rays as E
+    assert {Q.SCENES[name][0] for name in E.FORM_SCENES} == set(names)     # ... and so does tests/test_gpu_query_edges.py
 
 
 def test_host_library_exports_intersect_rays():
