@@ -240,6 +240,14 @@ enum { RT_TRACE_PATH = 0, RT_CAST_RAY = 1 };
 void rt_set_integrator(int integrator);
 int rt_get_integrator(void);
 
+/* Who builds the triangle hierarchy of the scenes render() and its kin upload: RT_BVH_HOST (default) = one host core,
+ * RT_BVH_DEVICE = the GPU (rt_hip.h, RT_HIP_BVH_DEVICE).  Images, bytes and counters are the same under either; the time a
+ * new or changed scene takes to become renderable is what differs.  Other values are ignored.  The reference has no
+ * counterpart: it tests every triangle (raytracer.c:137-150 in a loop). */
+enum { RT_BVH_HOST = 0, RT_BVH_DEVICE = 1 };
+void rt_set_bvh_builder(int builder);
+int rt_get_bvh_builder(void);
+
 /* Cooperative cancellation (what the reference's SIGINT handler, main.c:37-48,422, is for):
  * while a flag is registered, long renders poll it between slabs of tiles; when it becomes
  * non-zero render()/render_ex() return early with the finished part of the image in the

@@ -142,6 +142,42 @@ int rt_hip_device_info(int device, char *name, size_t name_cap, int *compute_uni
 int rt_hip_scene_create(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
                         size_t n_meshes, int device, RtHipScene **out_scene);
 void rt_hip_scene_destroy(RtHipScene *scene);
+
+/* Who builds the triangle hierarchy of a scene.  RT_HIP_BVH_HOST: the recursive binned builder on one host core (BvhBuild,
+ * csrc/bvh_build.h), the default.  RT_HIP_BVH_DEVICE: the capped full-sweep surface-area builder on the device
+ * (csrc/bvh_device.hip): three per-axis sorted lists, every admissible split position of every axis priced, level by level; the
+ * tree is a deterministic function of the triangles (BvhSweep in csrc/bvh_build.h states it in sequential C++, and the device's
+ * nodes and order equal it byte for byte).  A hierarchy only decides WHICH triangles get the exact test: frames, bytes and
+ * counters are the same under either builder; the build time and the walks' cost are what differ.
+ * Both have the same limits: fewer than 2^27 triangles, leaves of at most 15, the least depth such leaves allow.  The device
+ * builder's workspace (about 360 bytes a triangle and the sort's temporaries, freed before the call returns) that cannot be had is RT_HIP_ENOMEM, never a
+ * silent host build. */
+enum
+{
+  RT_HIP_BVH_HOST = 0,
+  RT_HIP_BVH_DEVICE = 1
+};
+typedef struct RtHipSceneOptions
+{
+  uint32_t struct_size; /* sizeof(RtHipSceneOptions), set by rt_hip_scene_options_defaults() */
+  uint32_t bvh_builder; /* RT_HIP_BVH_HOST (default) or RT_HIP_BVH_DEVICE */
+} RtHipSceneOptions;
+void rt_hip_scene_options_defaults(RtHipSceneOptions *opts);
+/* rt_hip_scene_create with options; opts == NULL or the defaults: rt_hip_scene_create itself.  A struct_size below the
+ * struct's or an unknown builder is RT_HIP_EINVAL, reported before any device is looked at. */
+int rt_hip_scene_create_opts(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, int device,
+                             const RtHipSceneOptions *opts, RtHipScene **out_scene);
+/* The hierarchy of a scene (any out pointer may be NULL): the builder that made it, its depth (levels that hold an inner node),
+ * the least depth leaves of 15 allow, its node count, and its expected walk cost -- evaluated on the host from the downloaded
+ * nodes in node order by BvhBuild::tree_cost()'s formula.  A scene without triangles reports 0 nodes and a cost of 0. */
+int rt_hip_scene_bvh_info(const RtHipScene *scene, uint32_t *builder, uint32_t *depth, uint32_t *max_depth, uint32_t *n_nodes,
+                          double *tree_cost);
+/* Downloads the fp64 source nodes (n_nodes x 16 doubles: two child boxes, two refs in the 13th, padding) and the leaf order
+ * (one triangle index per triangle); either may be NULL.  For tests and tools/bvh_sim.py. */
+int rt_hip_scene_bvh_read(const RtHipScene *scene, double *h_nodes, uint32_t *h_order);
+/* seconds the hierarchy build of this scene took: the host builder by the host's clock, the device builder by device events
+ * around its kernels */
+double rt_hip_scene_bvh_build_seconds(const RtHipScene *scene);
 int rt_hip_scene_device(const RtHipScene *scene);
 size_t rt_hip_scene_primitives(const RtHipScene *scene); /* spheres + triangles */
 /* diagnostic: how many triangles the scene marked as HULL FACETS -- every triangle of the scene lies on the inner
@@ -880,6 +916,10 @@ void rt_hip_last_image_phases(double seconds[3]);
  * context at the next frame.  Replaces nothing in the reference (its one parallel construct is the `omp parallel for` of
  * raytracer.c:184-185). */
 int rt_hip_set_device_map(const int *map, int n);
+
+/* The hierarchy builder of the scenes rt_hip_render_image() caches: RT_HIP_BVH_HOST (the default) or RT_HIP_BVH_DEVICE; another
+ * value is RT_HIP_EINVAL.  Part of the cache key: a change rebuilds the cached context at the next frame. */
+int rt_hip_set_bvh_builder(int builder);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,7 @@
 /* bvh_build.h -- the host-side builder of the triangle hierarchy (rt_hip_scene_create, rt_hip_shim.hip).
- * Plain C++ (no HIP): also compiled by g++ into the CPU test of its invariants (tests/bvh_harness.cpp, tests/test_host.py). */
+ * Plain C++ (no HIP): also compiled by g++ into the CPU test of its invariants (tests/bvh_harness.cpp, tests/test_host.py).
+ * Below it BvhSweep, the sequential statement of the tree the device builder makes (tests/bvh_sweep_harness.cpp), and -- for HIP
+ * translation units only -- that builder's interface (bvh_device.hip). */
 #ifndef BVH_BUILD_H
 #define BVH_BUILD_H
 
@@ -284,5 +286,254 @@ struct BvhBuild
     depth = depth_m;
   }
 };
+
+/* ---- the device builder's contract: capped full-sweep SAH over three per-axis sorted lists ----
+ * bvh_device.hip builds this tree with sorts, segmented scans, a segmented arg-min and stable partitions, level by level; BvhSweep
+ * states the same tree in plain sequential C++, and the device's nodes and order are tested against it byte for byte
+ * (tests/bvh_sweep_harness.cpp, tests/test_gpu_bvh_device.py).  The pieces both sides must evaluate alike -- the box of a
+ * triangle, the sort key, the joins of boxes, the area -- are the functions below, compiled into both (-ffp-contract=off).
+ *   per triangle   lo, hi, cen: tri_box's expressions; min / max break the tie of -0.0 and 0.0 (-0.0 is the smaller), so a box
+ *                  does not depend on the order its members were joined in (fmin / fmax leave that to the implementation)
+ *   lists          L0, L1, L2: all triangle indices, La ascending by (cen[a] + 0.0, index)
+ *   levels         level l holds ranges [b, e), each the same set of triangles in all three lists; <= PT_BVH_LEAF: a leaf
+ *   split search   m = e - b, cap = PT_BVH_LEAF << (max_depth - l - 1); for a = 0, 1, 2 and i = 1 .. m-1 ascending with
+ *                  i <= cap && m - i <= cap:  cost = half_area(box La[b, b+i)) * i + half_area(box La[b+i, e)) * (m - i);
+ *                  the winner starts as (axis 0, m / 2) at +infinity and is replaced by a strictly smaller cost only
+ *   partition      the winner list's first i entries go left; all three lists are partitioned stably by side
+ *   nodes          numbered breadth-first (level by level, left to right, root = 0: the walks follow refs only, no kernel
+ *                  relies on the host builder's depth-first numbering); order = the final L0; a one-leaf mesh gets the root
+ *                  with an empty second leaf; depth = the levels that hold an inner node */
+#if defined(__HIPCC__)
+#define BVH_HD __host__ __device__
+#else
+#define BVH_HD
+#endif
+
+BVH_HD inline double bvh_min(double a, double b) { return (a < b || (a == b && std::signbit(a))) ? a : b; }
+BVH_HD inline double bvh_max(double a, double b) { return (a > b || (a == b && std::signbit(b))) ? a : b; }
+BVH_HD inline double bvh_half_area(const double *l, const double *h)
+{
+  const double dx = h[0] - l[0], dy = h[1] - l[1], dz = h[2] - l[2];
+  return dx * dy + dy * dz + dz * dx;
+}
+/* box[0..2] = lo, box[3..5] = hi, cen[0..2] of the triangle g = (v0, e1, e2) */
+BVH_HD inline void bvh_tri_box(const double *g, double *box, double *cen)
+{
+  for (int k = 0; k < 3; k++)
+  {
+    const double a = g[k], b = g[k] + g[3 + k], c = g[k] + g[6 + k];
+    box[k] = bvh_min(a, bvh_min(b, c));
+    box[3 + k] = bvh_max(a, bvh_max(b, c));
+    cen[k] = (a + b + c) / 3.0;
+  }
+}
+/* 64 bits that order as the finite doubles do, -0.0 and 0.0 alike */
+BVH_HD inline uint64_t bvh_sort_key(double c)
+{
+  const double d = c + 0.0;
+  uint64_t u;
+  memcpy(&u, &d, sizeof u);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+BVH_HD inline double bvh_split_cost(double area_left, uint32_t i, double area_right, uint32_t m)
+{
+  return area_left * (double)i + area_right * (double)(m - i);
+}
+
+struct BvhSweep
+{
+  const double *tgeom = nullptr;   /* n_tri x 9: v0, e1, e2 */
+  std::vector<uint32_t> order;     /* the final L0 */
+  std::vector<double> nodes;       /* PT_BVH_SRC_DOUBLES per node, breadth-first */
+  std::vector<double> box, cen;    /* per triangle: lo xyz hi xyz; centroid */
+  std::vector<uint32_t> split_axis, split_left; /* per node: the winner (for the test that re-derives it) */
+  int depth = 0, max_depth = 0;
+
+  static double tree_cost_of(const std::vector<double> &nodes_in_order)
+  {
+    BvhBuild b;
+    b.nodes = nodes_in_order;
+    return b.tree_cost();
+  }
+  double tree_cost() const { return tree_cost_of(nodes); }
+
+  void box_of(const std::vector<uint32_t> &list, uint32_t from, uint32_t to, double *out) const
+  {
+    for (int k = 0; k < 3; k++)
+    {
+      out[k] = HUGE_VAL;
+      out[3 + k] = -HUGE_VAL;
+    }
+    for (uint32_t p = from; p < to; p++)
+      for (int k = 0; k < 3; k++)
+      {
+        out[k] = bvh_min(out[k], box[6 * (size_t)list[p] + k]);
+        out[3 + k] = bvh_max(out[3 + k], box[6 * (size_t)list[p] + 3 + k]);
+      }
+  }
+
+  void build_root(uint32_t n)
+  {
+    max_depth = 0;
+    while (((uint64_t)PT_BVH_LEAF << max_depth) < n)
+      max_depth++;
+    box.resize(6 * (size_t)n);
+    cen.resize(3 * (size_t)n);
+    for (uint32_t t = 0; t < n; t++)
+      bvh_tri_box(tgeom + 9 * (size_t)t, &box[6 * (size_t)t], &cen[3 * (size_t)t]);
+    std::vector<uint32_t> list[3];
+    for (int a = 0; a < 3; a++)
+    {
+      list[a].resize(n);
+      for (uint32_t t = 0; t < n; t++)
+        list[a][t] = t;
+      std::sort(list[a].begin(), list[a].end(), [&](uint32_t x, uint32_t y) {
+        const uint64_t kx = bvh_sort_key(cen[3 * (size_t)x + a]), ky = bvh_sort_key(cen[3 * (size_t)y + a]);
+        return kx != ky ? kx < ky : x < y;
+      });
+    }
+    nodes.clear();
+    split_axis.clear();
+    split_left.clear();
+    depth = 0;
+    if (n <= PT_BVH_LEAF)
+    { /* the root with the one leaf and an empty second one, as BvhBuild::build_tree makes it */
+      nodes.assign(PT_BVH_SRC_DOUBLES, 0.0);
+      box_of(list[0], 0, n, &nodes[0]);
+      memcpy(&nodes[6], &nodes[0], 6 * sizeof(double));
+      const uint32_t refs[2] = {PT_BVH_LEAF_FLAG | n, PT_BVH_LEAF_FLAG};
+      memcpy(&nodes[12], refs, sizeof refs);
+      depth = 1;
+      order = list[0];
+      return;
+    }
+    struct Range { uint32_t b, e; };
+    std::vector<Range> level(1, Range{0, n}), next; /* the inner nodes of a level, left to right */
+    std::vector<uint8_t> side(n, 0);
+    std::vector<uint32_t> tmp(n);
+    std::vector<double> area_l, area_r;
+    uint32_t base = 0;
+    for (int l = 0; !level.empty(); l++)
+    {
+      depth = l + 1;
+      const uint64_t cap = (uint64_t)PT_BVH_LEAF << (max_depth - l - 1);
+      const uint32_t next_base = base + (uint32_t)level.size();
+      nodes.resize((size_t)next_base * PT_BVH_SRC_DOUBLES, 0.0);
+      next.clear();
+      for (size_t s = 0; s < level.size(); s++)
+      {
+        const uint32_t b = level[s].b, e = level[s].e, m = e - b;
+        double best = HUGE_VAL;
+        uint32_t best_axis = 0, best_i = m / 2;
+        area_l.resize(m);
+        area_r.resize(m);
+        for (int a = 0; a < 3; a++)
+        {
+          double run[6] = {HUGE_VAL, HUGE_VAL, HUGE_VAL, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+          for (uint32_t j = 0; j < m; j++) /* area_l[j]: the box of the first j + 1 */
+          {
+            const double *tb = &box[6 * (size_t)list[a][b + j]];
+            for (int k = 0; k < 3; k++)
+            {
+              run[k] = bvh_min(run[k], tb[k]);
+              run[3 + k] = bvh_max(run[3 + k], tb[3 + k]);
+            }
+            area_l[j] = bvh_half_area(run, run + 3);
+          }
+          for (int k = 0; k < 3; k++)
+          {
+            run[k] = HUGE_VAL;
+            run[3 + k] = -HUGE_VAL;
+          }
+          for (uint32_t j = m; j-- > 0;) /* area_r[j]: the box of [j, m) */
+          {
+            const double *tb = &box[6 * (size_t)list[a][b + j]];
+            for (int k = 0; k < 3; k++)
+            {
+              run[k] = bvh_min(run[k], tb[k]);
+              run[3 + k] = bvh_max(run[3 + k], tb[3 + k]);
+            }
+            area_r[j] = bvh_half_area(run, run + 3);
+          }
+          for (uint32_t i = 1; i < m; i++)
+          {
+            if (i > cap || m - i > cap)
+              continue;
+            const double cost = bvh_split_cost(area_l[i - 1], i, area_r[i], m);
+            if (cost < best)
+            {
+              best = cost;
+              best_axis = (uint32_t)a;
+              best_i = i;
+            }
+          }
+        }
+        split_axis.push_back(best_axis);
+        split_left.push_back(best_i);
+        for (uint32_t p = b; p < e; p++)
+          side[list[best_axis][p]] = p >= b + best_i;
+        for (int a = 0; a < 3; a++)
+        {
+          uint32_t zl = b, zr = b + best_i;
+          for (uint32_t p = b; p < e; p++)
+            tmp[side[list[a][p]] ? zr++ : zl++] = list[a][p];
+          std::copy(tmp.begin() + b, tmp.begin() + e, list[a].begin() + b);
+        }
+        double *nd = &nodes[(size_t)(base + s) * PT_BVH_SRC_DOUBLES];
+        uint32_t refs[2];
+        const Range child[2] = {Range{b, b + best_i}, Range{b + best_i, e}};
+        for (int c = 0; c < 2; c++)
+        {
+          box_of(list[0], child[c].b, child[c].e, nd + 6 * c);
+          const uint32_t cm = child[c].e - child[c].b;
+          if (cm <= PT_BVH_LEAF)
+            refs[c] = PT_BVH_LEAF_FLAG | (child[c].b << PT_BVH_COUNT_BITS) | cm;
+          else
+          {
+            refs[c] = next_base + (uint32_t)next.size();
+            next.push_back(child[c]);
+          }
+        }
+        memcpy(nd + 12, refs, sizeof refs);
+      }
+      base = next_base;
+      level.swap(next);
+    }
+    order = list[0];
+  }
+};
+
+/* ---- the device builder (bvh_device.hip), as rt_hip_shim.hip calls it; HIP translation units only ---- */
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+/* A tree built on the current device.  `nodes` and `order` point into the build's one workspace allocation, which lives as
+ * long as this object: the caller copies them to where the scene keeps them.  Not copyable. */
+struct BvhDeviceTree
+{
+  void *workspace = nullptr;
+  const double *nodes = nullptr;   /* n_nodes x PT_BVH_SRC_DOUBLES, breadth-first */
+  const uint32_t *order = nullptr; /* n triangle indices: leaf order */
+  uint32_t n_nodes = 0;
+  int depth = 0, max_depth = 0;
+  float build_ms = 0; /* device events around the build's kernels (the per-level read-back of a count included) */
+  const char *failure = nullptr; /* set where bvh_device_build fails a consistency check of its own rather than a HIP call */
+  BvhDeviceTree() = default;
+  BvhDeviceTree(const BvhDeviceTree &) = delete;
+  BvhDeviceTree &operator=(const BvhDeviceTree &) = delete;
+  ~BvhDeviceTree()
+  {
+    if (workspace)
+      (void)hipFree(workspace);
+  }
+};
+
+/* Builds the tree over tri_geom (device memory, n x 9 doubles: v0, e1, e2; 0 < n < 2^(31 - PT_BVH_COUNT_BITS)) on the null
+ * stream of the current device and waits for it.  hipErrorOutOfMemory when the workspace cannot be had. */
+hipError_t bvh_device_build(const double *tri_geom, uint32_t n, BvhDeviceTree *out);
+
+/* tri_geom_leaf[k] = tri_geom[order[k]] (9 doubles each), on the null stream; all three in device memory */
+hipError_t bvh_device_gather_leaf(const double *tri_geom, const uint32_t *order, uint32_t n, double *tri_geom_leaf);
+#endif /* __HIPCC__ */
 
 #endif /* BVH_BUILD_H */

@@ -277,6 +277,9 @@ struct RtHipScene
   /* bounding sphere of every triangle (bvh_probe): centre, radius, |centre| -- radius < 0: no triangles */
   double mesh_c[3] = {0, 0, 0}, mesh_R = -1, mesh_c_norm = 0;
   bool hull_flags = false; /* tri_object carries PT_HULL_PLUS / PT_HULL_MINUS (pt_build_hull_flags ran) */
+  /* the hierarchy's origin (rt_hip_scene_bvh_info): RT_HIP_BVH_*, the least depth its leaves allow, the build's seconds */
+  uint32_t bvh_builder = RT_HIP_BVH_HOST, bvh_max_depth = 0;
+  double bvh_build_seconds = 0;
 };
 
 /* ---- progressive rendering: one frame accumulated over passes (rt_hip.h, RtHipAccum) ----------------------------------------
@@ -840,7 +843,7 @@ int check_adapt(const RtHipAdaptParams *p)
 }
 
 int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
-                      int device, RtHipScene **out_scene)
+                      int device, uint32_t bvh_builder, RtHipScene **out_scene)
 {
   if (!out_scene)
     return fail(RT_HIP_EINVAL, "out_scene is NULL");
@@ -986,29 +989,58 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
 
   /* ---- hierarchy over the triangles ---- */
   BvhBuild bvh;
+  /* RT_HIP_BVH_DEVICE: the tree stays in the build's workspace, and the triangles it was built from in `dgeom`, until the blob --
+   * sized by the node count the build produces -- has taken both, device to device */
+  BvhDeviceTree dtree;
+  DeviceBuffer dgeom;
+  size_t n_bvh_nodes = 0;
+  int bvh_depth = 0, bvh_max_depth = 0;
+  double bvh_build_seconds = 0;
   /* built for every scene with triangles: the small-scene kernels scan them through the flat
    * filter instead, but the general in-memory kernels (too-large scenes, cast_ray with
    * two-child materials) always walk the hierarchy */
   if (n_tri > 0)
   {
-    bvh.tgeom = tgeom.data();
-    bvh.order.resize(n_tri);
-    bvh.cen.resize(3 * n_tri);
-    bvh.lo.resize(3 * n_tri);
-    bvh.hi.resize(3 * n_tri);
-    for (uint32_t k = 0; k < (uint32_t)n_tri; k++)
-    {
-      bvh.order[k] = k;
-      bvh.tri_box(k);
-    }
     if (n_tri >= (1u << (31 - PT_BVH_COUNT_BITS)))
       return fail(RT_HIP_ELIMIT, "%zu triangles exceed the hierarchy's leaf references (2^%d)", n_tri, 31 - PT_BVH_COUNT_BITS);
-    bvh.build_root((uint32_t)n_tri);
-    if (bvh.depth > PT_BVH_STACK)
-      return fail(RT_HIP_ELIMIT, "triangle hierarchy depth %d exceeds the traversal stack (%d)", bvh.depth, PT_BVH_STACK);
+    if (bvh_builder == RT_HIP_BVH_DEVICE)
+    {
+      DeviceScope build_scope(device);
+      HIP_TRY(build_scope.status);
+      HIP_TRY(dgeom.alloc(tgeom.size() * 8));
+      HIP_TRY(hipMemcpy(dgeom.ptr, tgeom.data(), tgeom.size() * 8, hipMemcpyHostToDevice));
+      const hipError_t be = bvh_device_build(dgeom.at<double>(), (uint32_t)n_tri, &dtree);
+      if (be != hipSuccess && dtree.failure)
+        return fail(RT_HIP_ERUNTIME, "device hierarchy builder: %s", dtree.failure);
+      HIP_TRY(be);
+      n_bvh_nodes = dtree.n_nodes;
+      bvh_depth = dtree.depth;
+      bvh_max_depth = dtree.max_depth;
+      bvh_build_seconds = 1e-3 * dtree.build_ms;
+    }
+    else
+    {
+      const auto t0 = std::chrono::steady_clock::now();
+      bvh.tgeom = tgeom.data();
+      bvh.order.resize(n_tri);
+      bvh.cen.resize(3 * n_tri);
+      bvh.lo.resize(3 * n_tri);
+      bvh.hi.resize(3 * n_tri);
+      for (uint32_t k = 0; k < (uint32_t)n_tri; k++)
+      {
+        bvh.order[k] = k;
+        bvh.tri_box(k);
+      }
+      bvh.build_root((uint32_t)n_tri);
+      n_bvh_nodes = bvh.nodes.size() / PT_BVH_SRC_DOUBLES;
+      bvh_depth = bvh.depth;
+      bvh_max_depth = bvh.max_depth;
+      bvh_build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (bvh_depth > PT_BVH_STACK)
+      return fail(RT_HIP_ELIMIT, "triangle hierarchy depth %d exceeds the traversal stack (%d)", bvh_depth, PT_BVH_STACK);
   }
-  const size_t n_bvh_nodes = bvh.nodes.size() / PT_BVH_SRC_DOUBLES;
-  std::vector<double> tgeom_leaf(9 * bvh.order.size());
+  std::vector<double> tgeom_leaf(9 * bvh.order.size()); /* host builder only: the device builder gathers on the device */
   for (size_t k = 0; k < bvh.order.size(); k++)
     memcpy(&tgeom_leaf[9 * k], &tgeom[9 * (size_t)bvh.order[k]], 9 * sizeof(double));
 
@@ -1026,11 +1058,11 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   /* + 1 pair: the scan's software pipeline reads one pair past the end */
   const size_t filt_bytes = pt_filt_bytes((uint32_t)n_spheres, (uint32_t)n_tri);
   const size_t off_bvh_src = off_filt + pad(filt_bytes);
-  const size_t off_bvh_nodes = off_bvh_src + pad(bvh.nodes.size() * 8);
+  const size_t off_bvh_nodes = off_bvh_src + pad(n_bvh_nodes * PT_BVH_SRC_DOUBLES * 8);
   const size_t bvh_nodes_bytes = n_bvh_nodes * PT_BVH_NODE_WORDS * 4;
   const size_t off_bvh_tri = off_bvh_nodes + pad(bvh_nodes_bytes);
-  const size_t off_tgeom_leaf = off_bvh_tri + pad(bvh.order.size() * 4);
-  const size_t total = off_tgeom_leaf + pad(tgeom_leaf.size() * 8) + 256;
+  const size_t off_tgeom_leaf = off_bvh_tri + pad(n_tri * 4);
+  const size_t total = off_tgeom_leaf + pad(9 * n_tri * 8) + 256;
 
   DeviceScope scope(device);
   HIP_TRY(scope.status);
@@ -1052,13 +1084,23 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   if (e == hipSuccess) e = up(off_mat, mat.data(), mat.size() * 8);
   if (e == hipSuccess) e = up(off_craw, craw.data(), craw.size() * 8);
   if (e == hipSuccess) e = up(off_geom4, geom4.data(), geom4.size() * 8);
-  if (e == hipSuccess) e = up(off_tgeom, tgeom.data(), tgeom.size() * 8);
+  if (e == hipSuccess)
+    e = dgeom ? hipMemcpy(base + off_tgeom, dgeom.ptr, tgeom.size() * 8, hipMemcpyDeviceToDevice) : up(off_tgeom, tgeom.data(), tgeom.size() * 8);
   if (e == hipSuccess) e = up(off_tnorm, tnorm.data(), tnorm.size() * 8);
   if (e == hipSuccess) e = up(off_ttex, ttex.data(), ttex.size() * 8);
   if (e == hipSuccess) e = up(off_tobj, tobj.data(), tobj.size() * 4);
   if (e == hipSuccess) e = up(off_bvh_src, bvh.nodes.data(), bvh.nodes.size() * 8);
   if (e == hipSuccess) e = up(off_bvh_tri, bvh.order.data(), bvh.order.size() * 4);
   if (e == hipSuccess) e = up(off_tgeom_leaf, tgeom_leaf.data(), tgeom_leaf.size() * 8);
+  if (e == hipSuccess && dtree.workspace)
+  { /* the device builder's tree: nodes and order from its workspace, the leaf-ordered geometry gathered in place */
+    e = hipMemcpy(base + off_bvh_src, dtree.nodes, n_bvh_nodes * PT_BVH_SRC_DOUBLES * 8, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(base + off_bvh_tri, dtree.order, n_tri * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess)
+      e = bvh_device_gather_leaf(reinterpret_cast<const double *>(base + off_tgeom), reinterpret_cast<const uint32_t *>(base + off_bvh_tri),
+                                 (uint32_t)n_tri, reinterpret_cast<double *>(base + off_tgeom_leaf));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
   if (e != hipSuccess)
   {
     (void)hipFree(sc->blob);
@@ -1072,7 +1114,10 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   sc->view.bvh_tri = reinterpret_cast<const uint32_t *>(base + off_bvh_tri);
   sc->view.tri_geom_leaf = reinterpret_cast<const double *>(base + off_tgeom_leaf);
   sc->view.n_bvh_nodes = (uint32_t)n_bvh_nodes;
-  sc->view.bvh_depth = (uint32_t)bvh.depth;
+  sc->view.bvh_depth = (uint32_t)bvh_depth;
+  sc->bvh_builder = bvh_builder;
+  sc->bvh_max_depth = (uint32_t)bvh_max_depth;
+  sc->bvh_build_seconds = bvh_build_seconds;
   for (int a = 0; a < 3; a++)
     sc->mesh_c[a] = mesh_c[a];
   sc->mesh_R = mesh_R;
@@ -1568,6 +1613,7 @@ struct ImageCtx
   std::vector<ncclComm_t> comms; /* one per distinct physical device (comm_of) */
   DeviceBuffer all_tiles, all_tiles8, image, image8; /* on the root, phys[0] */
   uint64_t builds = 0; /* how many times a context was (re)built: exposed for tests */
+  int bvh_builder = RT_HIP_BVH_HOST; /* who built the scenes' hierarchies (rt_hip_set_bvh_builder) */
 };
 /* (never destroyed: at process exit the members' destructors would call into a HIP runtime that may be gone already) */
 ImageCtx &g_ctx = *new ImageCtx;
@@ -1578,6 +1624,7 @@ double g_last_phases[3] = {0, 0, 0}; /* rt_hip_last_image_phases */
  * the first frame).  Empty = the identity.  Guarded by g_ctx_mutex. */
 std::vector<int> g_device_map;
 bool g_device_map_env_read = false;
+int g_bvh_builder = RT_HIP_BVH_HOST; /* rt_hip_set_bvh_builder: the builder of the cached scenes.  Guarded by g_ctx_mutex. */
 
 void device_map_from_env()
 {
@@ -1724,7 +1771,7 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
   const bool force_comm = fc && fc[0] == '1';
   ImageCtx &c = g_ctx;
   if (c.G == G && c.W == W && c.H == H && c.force_comm == force_comm && (int)c.dev.size() == G && c.phys == phys &&
-      scene_matches(c.scene_bytes, spheres, n_spheres, meshes, n_meshes))
+      c.bvh_builder == g_bvh_builder && scene_matches(c.scene_bytes, spheres, n_spheres, meshes, n_meshes))
     return RT_HIP_OK;
   ctx_release(c);
   c.builds++;
@@ -1755,7 +1802,10 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
     d.count = (n_tiles > (uint32_t)g) ? (n_tiles - g + G - 1) / G : 0;
     d.first_slot = first_slot;
     first_slot += d.count;
-    const int rc = rt_hip_scene_create(spheres, n_spheres, meshes, n_meshes, phys[g], &d.scene);
+    RtHipSceneOptions opts;
+    rt_hip_scene_options_defaults(&opts);
+    opts.bvh_builder = (uint32_t)g_bvh_builder;
+    const int rc = rt_hip_scene_create_opts(spheres, n_spheres, meshes, n_meshes, phys[g], &opts, &d.scene);
     if (rc)
       return rc;
     HIP_TRY(hipSetDevice(phys[g]));
@@ -1787,6 +1837,7 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
   c.W = W;
   c.H = H;
   c.force_comm = force_comm;
+  c.bvh_builder = g_bvh_builder;
   scene_serialise(c.scene_bytes, spheres, n_spheres, meshes, n_meshes);
   return RT_HIP_OK;
 }
@@ -2071,6 +2122,15 @@ void release_cache_impl()
     ctx_release(g_ctx);
   }
   pend_pools_release();
+}
+
+int set_bvh_builder_impl(int builder)
+{
+  if (builder != RT_HIP_BVH_HOST && builder != RT_HIP_BVH_DEVICE)
+    return fail(RT_HIP_EINVAL, "bvh builder %d: RT_HIP_BVH_HOST (0) or RT_HIP_BVH_DEVICE (1)", builder);
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  g_bvh_builder = builder;
+  return RT_HIP_OK;
 }
 
 uint64_t cache_builds_impl()
@@ -2988,8 +3048,77 @@ int rt_hip_device_info(int device, char *name, size_t name_cap, int *compute_uni
 int rt_hip_scene_create(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
                         size_t n_meshes, int device, RtHipScene **out_scene)
 {
-  return guarded("rt_hip_scene_create", [&] { return scene_create_impl(spheres, n_spheres, meshes, n_meshes, device, out_scene); });
+  return guarded("rt_hip_scene_create",
+                 [&] { return scene_create_impl(spheres, n_spheres, meshes, n_meshes, device, RT_HIP_BVH_HOST, out_scene); });
 }
+
+void rt_hip_scene_options_defaults(RtHipSceneOptions *opts)
+{
+  if (!opts)
+    return;
+  opts->struct_size = (uint32_t)sizeof(RtHipSceneOptions);
+  opts->bvh_builder = RT_HIP_BVH_HOST;
+}
+
+int rt_hip_scene_create_opts(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, int device,
+                             const RtHipSceneOptions *opts, RtHipScene **out_scene)
+{
+  uint32_t builder = RT_HIP_BVH_HOST;
+  if (opts)
+  {
+    if (out_scene)
+      *out_scene = nullptr;
+    if (opts->struct_size < sizeof(RtHipSceneOptions))
+      return fail(RT_HIP_EINVAL, "scene options: struct_size %u, expected %zu (rt_hip_scene_options_defaults)", opts->struct_size,
+                  sizeof(RtHipSceneOptions));
+    if (opts->bvh_builder != RT_HIP_BVH_HOST && opts->bvh_builder != RT_HIP_BVH_DEVICE)
+      return fail(RT_HIP_EINVAL, "scene options: bvh_builder %u is neither RT_HIP_BVH_HOST nor RT_HIP_BVH_DEVICE", opts->bvh_builder);
+    builder = opts->bvh_builder;
+  }
+  return guarded("rt_hip_scene_create_opts",
+                 [&] { return scene_create_impl(spheres, n_spheres, meshes, n_meshes, device, builder, out_scene); });
+}
+
+int rt_hip_scene_bvh_read(const RtHipScene *scene, double *h_nodes, uint32_t *h_order)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_bvh_read: scene is NULL");
+  DeviceScope on(scene->device);
+  HIP_TRY(on.status);
+  if (h_nodes && scene->view.n_bvh_nodes)
+    HIP_TRY(hipMemcpy(h_nodes, scene->view.bvh_src, (size_t)scene->view.n_bvh_nodes * PT_BVH_SRC_DOUBLES * 8, hipMemcpyDeviceToHost));
+  if (h_order && scene->view.n_triangles)
+    HIP_TRY(hipMemcpy(h_order, scene->view.bvh_tri, (size_t)scene->view.n_triangles * 4, hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
+int rt_hip_scene_bvh_info(const RtHipScene *scene, uint32_t *builder, uint32_t *depth, uint32_t *max_depth, uint32_t *n_nodes,
+                          double *tree_cost)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_bvh_info: scene is NULL");
+  if (builder) *builder = scene->bvh_builder;
+  if (depth) *depth = scene->view.bvh_depth;
+  if (max_depth) *max_depth = scene->bvh_max_depth;
+  if (n_nodes) *n_nodes = scene->view.n_bvh_nodes;
+  if (!tree_cost)
+    return RT_HIP_OK;
+  *tree_cost = 0.0;
+  if (scene->view.n_bvh_nodes == 0)
+    return RT_HIP_OK;
+  return guarded("rt_hip_scene_bvh_info", [&]() -> int {
+    std::vector<double> nodes((size_t)scene->view.n_bvh_nodes * PT_BVH_SRC_DOUBLES);
+    const int rc = rt_hip_scene_bvh_read(scene, nodes.data(), nullptr);
+    if (rc)
+      return rc;
+    *tree_cost = BvhSweep::tree_cost_of(nodes);
+    return RT_HIP_OK;
+  });
+}
+
+double rt_hip_scene_bvh_build_seconds(const RtHipScene *scene) { return scene ? scene->bvh_build_seconds : 0.0; }
+
+int rt_hip_set_bvh_builder(int builder) { return set_bvh_builder_impl(builder); }
 
 void rt_hip_release_cache(void) { release_cache_impl(); }
 

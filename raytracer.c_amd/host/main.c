@@ -11,6 +11,8 @@
  *   -r <seed>    RNG seed (default 1666943821)
  *   -i <0|1>     integrator: 0 trace_path (default), 1 cast_ray -- the `#if 1` of
  *                raytracer.c:207-211
+ *   -b <0|1>     who builds the triangle hierarchy: 0 the host (default), 1 the device (rt_set_bvh_builder): the same
+ *                PNG either way, only the scene's build time differs
  *   -p <samples> progressive: add the samples in passes of this many (render_progressive, one GPU), a
  *                line per pass; the PNG is the one-shot image bit for bit
  *   -a <prefix>  after the frame, its first-hit feature buffers (render_aov: the frame's own camera samples, same -s
@@ -109,6 +111,7 @@ typedef struct
 {
   Options options;
   int depth, config, gpus, integrator;
+  int bvh;  /* -b: RT_BVH_HOST or RT_BVH_DEVICE */
   int pass; /* -p: samples per pass; 0: not given (one-shot) */
   const char *aov; /* -a: prefix of the feature-buffer files; NULL: none */
   int denoise;     /* -n: iterations + 1; 0: not given */
@@ -126,6 +129,7 @@ static void usage(const char *prog)
           "Usage: %s -w <width> -h <height> -s <samples per pixel> -o <filename>\n"
           "          [-d <max depth>] [-c <scene config 1..5>] [-g <gpus>] [-r <seed>]\n"
           "          [-i <integrator: 0 trace_path, 1 cast_ray>] [-p <samples per pass, one GPU>]\n"
+          "          [-b <triangle hierarchy built by: 0 the host, 1 the device>]\n"
           "          [-a <prefix of the albedo / normal / depth .pfm files>]\n"
           "          [-n <denoise iterations 0..10: -o denoised, <name>.noisy.png as rendered>]\n"
           "          [-e <adaptive sampling: tiles whose error estimate is <= this stop early; -s is the budget; one GPU>]\n"
@@ -152,6 +156,11 @@ static int parse_args(int argc, char **argv, Args *a)
     case 'g': a->gpus = atoi(val); break;
     case 'r': a->seed = strtoull(val, NULL, 10); break;
     case 'i': a->integrator = atoi(val); break;
+    case 'b':
+      if ((val[0] != '0' && val[0] != '1') || val[1] != '\0')
+        return -1;
+      a->bvh = val[0] - '0';
+      break;
     case 'a': a->aov = val; break;
     case 'n':
       a->denoise = atoi(val) + 1;
@@ -388,6 +397,7 @@ int main(int argc, char **argv)
   rt_set_seed(a.seed);
   rt_set_devices(a.gpus);
   rt_set_integrator(a.integrator);
+  rt_set_bvh_builder(a.bvh);
 
   if (a.upsample)
   {

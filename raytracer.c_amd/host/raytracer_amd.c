@@ -56,6 +56,13 @@ void rt_set_integrator(int integrator)
     g_integrator = integrator;
 }
 int rt_get_integrator(void) { return g_integrator; }
+static int g_bvh_builder = RT_BVH_HOST;
+void rt_set_bvh_builder(int builder)
+{
+  if ((builder == RT_BVH_HOST || builder == RT_BVH_DEVICE) && rt_hip_set_bvh_builder(builder) == RT_HIP_OK)
+    g_bvh_builder = builder;
+}
+int rt_get_bvh_builder(void) { return g_bvh_builder; }
 double rt_last_render_seconds(void) { return g_last_seconds; }
 static long long g_last_samples = 0; /* render_adaptive: pixel samples rendered */
 static const volatile int *g_cancel_flag = NULL; /* render_progressive polls it between passes */

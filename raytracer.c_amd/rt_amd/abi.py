@@ -71,6 +71,15 @@ class RtHipMesh(C.Structure):
                 ("num_triangles", C.c_size_t), ("vertices", C.POINTER(Vertex))]
 
 
+class RtHipSceneOptions(C.Structure):  # rt_hip.h: rt_hip_scene_create_opts' options (rt_hip_scene_options_defaults), 8 B
+    _fields_ = [("struct_size", C.c_uint32), ("bvh_builder", C.c_uint32)]
+
+
+BVH_HOST, BVH_DEVICE = 0, 1  # RtHipSceneOptions.bvh_builder / rt_hip_set_bvh_builder()
+BVH_BUILDERS = {"host": BVH_HOST, "device": BVH_DEVICE}
+BVH_SRC_DOUBLES = 16         # PT_BVH_SRC_DOUBLES: doubles per fp64 source node (rt_hip_scene_bvh_read)
+
+
 class RtHipParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("max_depth", C.c_int32),
                 ("seed", C.c_uint64), ("tile_first", C.c_uint32), ("tile_stride", C.c_uint32),
@@ -171,6 +180,14 @@ SHIM_SYMBOLS = {
     "rt_hip_scene_create": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.c_int,
                                       C.POINTER(C.c_void_p)]),
     "rt_hip_scene_destroy": (None, [C.c_void_p]),
+    "rt_hip_scene_options_defaults": (None, [C.POINTER(RtHipSceneOptions)]),
+    "rt_hip_scene_create_opts": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.c_int,
+                                           C.POINTER(RtHipSceneOptions), C.POINTER(C.c_void_p)]),
+    "rt_hip_scene_bvh_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
+    "rt_hip_scene_bvh_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_scene_bvh_build_seconds": (C.c_double, [C.c_void_p]),
+    "rt_hip_set_bvh_builder": (C.c_int, [C.c_int]),
     "rt_hip_scene_device": (C.c_int, [C.c_void_p]),
     "rt_hip_scene_primitives": (C.c_size_t, [C.c_void_p]),
     "rt_hip_scene_hull_facets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -303,6 +320,8 @@ HOST_SYMBOLS = {
     "rt_set_seed": (None, [C.c_uint64]),
     "rt_set_integrator": (None, [C.c_int]),
     "rt_get_integrator": (C.c_int, []),
+    "rt_set_bvh_builder": (None, [C.c_int]),
+    "rt_get_bvh_builder": (C.c_int, []),
     "rt_set_devices": (None, [C.c_int]),
     "rt_get_max_depth": (C.c_int, []),
     "rt_get_seed": (C.c_uint64, []),

@@ -22,9 +22,12 @@ def _check(rc, what):
 
 
 class GpuScene:
-    """A scene resident in HBM (rt_hip_scene_create)."""
+    """A scene resident in HBM (rt_hip_scene_create_opts).  bvh: who builds the triangle hierarchy, "host" (the default) or
+    "device" -- frames, bytes and counters are the same under either."""
 
-    def __init__(self, scene, device=0):
+    def __init__(self, scene, device=0, bvh="host"):
+        if bvh not in abi.BVH_BUILDERS:
+            raise ValueError(f"bvh must be one of {sorted(abi.BVH_BUILDERS)}, not {bvh!r}")
         self.shim = abi.load_shim()
         if self.shim.rt_hip_device_count() < 1:
             raise ShimError("no HIP device visible; this package has no CPU fallback")
@@ -32,8 +35,11 @@ class GpuScene:
         self.device = device
         self._meshes = scene.hip_meshes()
         handle = C.c_void_p()
-        _check(self.shim.rt_hip_scene_create(scene.objects, scene.n_objects, self._meshes, scene.n_meshes, device,
-                                             C.byref(handle)), "rt_hip_scene_create")
+        opts = abi.RtHipSceneOptions()
+        self.shim.rt_hip_scene_options_defaults(C.byref(opts))
+        opts.bvh_builder = abi.BVH_BUILDERS[bvh]
+        _check(self.shim.rt_hip_scene_create_opts(scene.objects, scene.n_objects, self._meshes, scene.n_meshes, device, C.byref(opts),
+                                                  C.byref(handle)), "rt_hip_scene_create_opts")
         self.handle = handle
         self._accums = []  # handles of the accumulations made here: closed before the scene (rt_hip.h: the scene outlives them)
 
@@ -83,6 +89,27 @@ class GpuScene:
         plus, minus = C.c_uint32(0), C.c_uint32(0)
         _check(self.shim.rt_hip_scene_hull_facets(self.handle, C.byref(plus), C.byref(minus)), "rt_hip_scene_hull_facets")
         return plus.value, minus.value
+
+    def bvh_info(self):
+        """the triangle hierarchy: builder ("host" / "device"), depth, max_depth, n_nodes, tree_cost (the expected instructions
+        of a walk per ray that meets the root's box) and build_seconds"""
+        b, d, md, nn, cost = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_double(0)
+        _check(self.shim.rt_hip_scene_bvh_info(self.handle, C.byref(b), C.byref(d), C.byref(md), C.byref(nn), C.byref(cost)),
+               "rt_hip_scene_bvh_info")
+        names = {v: k for k, v in abi.BVH_BUILDERS.items()}
+        return {"builder": names[b.value], "depth": d.value, "max_depth": md.value, "n_nodes": nn.value, "tree_cost": cost.value,
+                "build_seconds": float(self.shim.rt_hip_scene_bvh_build_seconds(self.handle))}
+
+    def bvh_read(self):
+        """(nodes, order): the fp64 source nodes as an (n_nodes, 16) float64 array -- two child boxes, the two refs in the
+        bytes of column 12 -- and the leaf order as uint32 triangle indices"""
+        import numpy as np
+        info = self.bvh_info()
+        nodes = np.zeros((info["n_nodes"], abi.BVH_SRC_DOUBLES), dtype=np.float64)
+        order = np.zeros(self.scene.n_triangles, dtype=np.uint32)
+        _check(self.shim.rt_hip_scene_bvh_read(self.handle, nodes.ctypes.data if nodes.size else None,
+                                               order.ctypes.data if order.size else None), "rt_hip_scene_bvh_read")
+        return nodes, order
 
     def suggest_chunks(self, count, samples=None, max_depth=None):
         return int(self.shim.rt_hip_suggest_chunks_depth(self.handle, count, samples or self.scene.samples,

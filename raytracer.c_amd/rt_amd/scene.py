@@ -125,8 +125,14 @@ def custom_scene(objects, width, height, samples, max_depth, cam_pos, cam_target
     marr = (abi.MeshObject * max(len(meshes or []), 1))()
     ntri = 0
     for i, m in enumerate(meshes or []):
-        tris = m["triangles"]  # list of 3 x (pos xyz, tex uv) rows, flattened per vertex
-        verts = (abi.Vertex * (3 * len(tris)))()
+        tris = m["triangles"]  # list of 3 x (pos xyz, tex uv) rows, flattened per vertex; or an (n, 3, 3) numpy array of corners
+        n_here = len(tris)
+        verts = (abi.Vertex * (3 * n_here))()
+        if hasattr(tris, "dtype"):   # numpy: the vertex array filled at once (tex 0, 0), not vertex by vertex
+            import numpy as np
+            if len(tris):
+                np.frombuffer(verts, dtype=np.float64).reshape(3 * len(tris), 5)[:, :3] = np.asarray(tris, dtype=np.float64).reshape(-1, 3)
+            tris = ()
         for t, tri in enumerate(tris):
             for k in range(3):
                 p = tri[k]
@@ -136,9 +142,9 @@ def custom_scene(objects, width, height, samples, max_depth, cam_pos, cam_target
         marr[i].flags = m["flags"]
         marr[i].color = abi.Vec3(*m["color"])
         marr[i].emission = abi.Vec3(*m.get("emission", (0, 0, 0)))
-        marr[i].mesh.num_triangles = len(tris)
+        marr[i].mesh.num_triangles = n_here
         marr[i].mesh.vertices = C.cast(verts, C.POINTER(abi.Vertex))
-        ntri += len(tris)
+        ntri += n_here
     cam = make_camera(width, height, cam_pos, cam_target)
     sc = Scene(config=0, width=width, height=height, samples=samples, max_depth=max_depth, objects=arr,
                meshes=marr, n_objects=len(objects), n_meshes=len(meshes or []), n_triangles=ntri, camera=cam,
