@@ -178,6 +178,36 @@ int rt_hip_scene_bvh_read(const RtHipScene *scene, double *h_nodes, uint32_t *h_
 /* seconds the hierarchy build of this scene took: the host builder by the host's clock, the device builder by device events
  * around its kernels */
 double rt_hip_scene_bvh_build_seconds(const RtHipScene *scene);
+
+/* ---- a deforming mesh: new vertex positions for a scene that exists ----
+ * New positions for every triangle of the scene: 9 doubles a triangle (v0, v1, v2), in scene triangle order (mesh by mesh).
+ * d_positions: device memory on the scene's device, not inside the scene (from skinning, a cloth step, a torch tensor);
+ * h_positions: host memory, staged by the call.  Synchronous: returns when the scene is ready, and the next launch of any
+ * kernel sees the new geometry.  Every per-triangle record is recomputed on the device by the operations scene creation uses,
+ * and the existing hierarchy is REFITTED: same topology, same leaf order, new boxes (BvhRefit, csrc/bvh_build.h).  A hierarchy
+ * only decides which triangles get the exact test, so frames, bytes and counters after an update equal those of a scene
+ * freshly created from the same positions; only the walks' cost can drift as the mesh leaves the shape the tree was built for
+ * (rt_hip_scene_bvh_info's tree_cost reports the refitted tree's: recreate the scene when it has drifted too far).  The
+ * parked-walk workspace, the table sets' storage and every handle stay.  Spheres, triangle counts, materials and tex
+ * coordinates do not change; the topology is not rebuilt.
+ * RT_HIP_EINVAL, with the scene unchanged: n_triangles differs from the scene's count; a scene without triangles; a NULL
+ * pointer; d_positions not device memory of the scene's device, or inside the scene; an RtHipAccum on the scene that has not
+ * been destroyed (its plan holds the scene as it was); a launch of the scene being submitted on another thread; a position
+ * that is not finite (|vertex| <= 1e300, rt_hip_scene_create's rule).  RT_HIP_ENOMEM, with the scene unchanged: the workspace
+ * (256 bytes; the host form adds the staged positions; the first update adds 4 bytes a node, kept with the scene).
+ * A HIP runtime failure after writing has begun is RT_HIP_ERUNTIME and leaves the scene UNUSABLE: every later launch or update
+ * on it returns RT_HIP_ERUNTIME, and only rt_hip_scene_destroy is allowed.
+ * The caller must not launch on the scene from another thread during the call; work submitted before it is waited for. */
+int rt_hip_scene_update_vertices(RtHipScene *scene, const double *d_positions, size_t n_triangles);
+int rt_hip_scene_update_vertices_host(RtHipScene *scene, const double *h_positions, size_t n_triangles);
+/* how many updates the scene has taken, and the host-clock seconds of the last one; either may be NULL */
+int rt_hip_scene_update_info(const RtHipScene *scene, uint64_t *updates, double *last_seconds);
+/* for tests: tri_geom (9n), tri_normal (3n), the triangles' entry_src records (6n), tri_object (n, hull bits included); any may be NULL */
+int rt_hip_scene_read_triangles(const RtHipScene *scene, double *geom, double *normal, double *entry, uint32_t *object);
+/* for tests: the triangles' bounding sphere (radius < 0: no triangles), the scene's reach (>= |p| for every point of a primitive
+ * of ordinary size: what near_R is made of) and whether a launch takes the _sph members; any may be NULL */
+int rt_hip_scene_bounds(const RtHipScene *scene, double mesh_center[3], double *mesh_radius, double *reach, uint32_t *mesh_round);
+
 int rt_hip_scene_device(const RtHipScene *scene);
 size_t rt_hip_scene_primitives(const RtHipScene *scene); /* spheres + triangles */
 /* diagnostic: how many triangles the scene marked as HULL FACETS -- every triangle of the scene lies on the inner
@@ -631,7 +661,8 @@ int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t widt
  *   7. out8 = the render epilogue's tonemap of the widened out.
  * The contract is total: any buffer contents and any camera bytes (a degenerate or NaN camera, depths that are 0, negative or inf,
  * a zeroed history) have a defined result.  len = 0 marks a pixel the next frame must not use; a zero-filled history (buffers and
- * camera) behaves like no history.  Out of scope: moving objects (the scene is static between the two frames), demodulated
+ * camera) behaves like no history.  Out of scope: moving objects (the scene is static between the two frames: after
+ * rt_hip_scene_update_vertices the caller starts a new history), demodulated
  * history, variance estimates.
  *   - rt_hip_reproject_defaults: flags 0, max_history = 32, depth_tol = 0.05, normal_min = 0.5 (DESIGN, "`pt_reproject`": the sweep).
  *   - rt_hip_reproject: asynchronous on `stream`, on the device that holds d_rgb.  d_out_rgb and d_out_len are required,
@@ -920,6 +951,13 @@ int rt_hip_set_device_map(const int *map, int n);
 /* The hierarchy builder of the scenes rt_hip_render_image() caches: RT_HIP_BVH_HOST (the default) or RT_HIP_BVH_DEVICE; another
  * value is RT_HIP_EINVAL.  Part of the cache key: a change rebuilds the cached context at the next frame. */
 int rt_hip_set_bvh_builder(int builder);
+
+/* on != 0: when a call's scene differs from the cached one ONLY in vertex positions -- the same counts, spheres, materials, tex
+ * coordinates, builder, devices and size -- every cached scene takes the new positions in place
+ * (rt_hip_scene_update_vertices_host) and rt_hip_cache_updates() counts one, not rt_hip_cache_builds().  The default, 0: such a
+ * scene rebuilds the context as any other change does. */
+void rt_hip_set_scene_updates(int on);
+uint64_t rt_hip_cache_updates(void);
 
 #ifdef __cplusplus
 }

@@ -1,11 +1,13 @@
 /* bvh_build.h -- the host-side builder of the triangle hierarchy (rt_hip_scene_create, rt_hip_shim.hip).
  * Plain C++ (no HIP): also compiled by g++ into the CPU test of its invariants (tests/bvh_harness.cpp, tests/test_host.py).
- * Below it BvhSweep, the sequential statement of the tree the device builder makes (tests/bvh_sweep_harness.cpp), and -- for HIP
- * translation units only -- that builder's interface (bvh_device.hip). */
+ * Below it BvhSweep, the sequential statement of the tree the device builder makes (tests/bvh_sweep_harness.cpp), BvhRefit, the
+ * statement of a refit to moved triangles (tests/bvh_refit_harness.cpp), and -- for HIP translation units only -- the device
+ * builder's interface (bvh_device.hip). */
 #ifndef BVH_BUILD_H
 #define BVH_BUILD_H
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -503,6 +505,121 @@ struct BvhSweep
   }
 };
 
+/* ---- refitting a tree to moved triangles: same topology, same leaf order, new boxes ----
+ * The contract of scene_update.hip's refit (rt_hip_scene_update_vertices), stated in sequential C++ and tested against the
+ * device byte for byte (tests/bvh_refit_harness.cpp, tests/test_gpu_scene_update.py).  Input: a tree as rt_hip_scene_bvh_read
+ * returns it, from either builder, and the new tgeom (n x 9: v0, e1, e2).  Only the box doubles of `nodes` are rewritten; the
+ * refs, the padding and `order` stay.
+ *   child = a leaf [b, b + count)   the join of bvh_tri_box(order[b + j]) over the leaf, started from (+inf, -inf)
+ *   child = an inner node           the join of that node's two child boxes
+ *   child = the empty leaf          (count 0: the second child of a one-leaf mesh's root) its six doubles stay as they are
+ * The join uses bvh_min / bvh_max (-0.0 below 0.0), which are associative and commutative: a box does not depend on the order
+ * its members were joined in, so any schedule -- this loop, the device's level sweep -- gives the same bytes.
+ * Both builders number a child above its parent (BvhBuild: preorder; BvhSweep and the device: breadth-first), so one pass from
+ * the last node to the first meets every node after its children; refit() asserts it, levels() reports a tree that breaks it. */
+struct BvhRefit
+{
+  BVH_HD static uint32_t child_ref(const double *nodes, uint32_t node, int child)
+  {
+    uint32_t refs[2];
+    memcpy(refs, nodes + (size_t)node * PT_BVH_SRC_DOUBLES + 12, sizeof refs);
+    return refs[child];
+  }
+  BVH_HD static bool is_leaf(uint32_t ref) { return (ref & PT_BVH_LEAF_FLAG) != 0; }
+  BVH_HD static uint32_t leaf_count(uint32_t ref) { return ref & ((1u << PT_BVH_COUNT_BITS) - 1u); }
+  BVH_HD static uint32_t leaf_first(uint32_t ref) { return (ref & ~PT_BVH_LEAF_FLAG) >> PT_BVH_COUNT_BITS; }
+
+  BVH_HD static void join(double *box, const double *other)
+  {
+    for (int k = 0; k < 3; k++)
+    {
+      box[k] = bvh_min(box[k], other[k]);
+      box[3 + k] = bvh_max(box[3 + k], other[3 + k]);
+    }
+  }
+  BVH_HD static void empty(double *box)
+  {
+    for (int k = 0; k < 3; k++)
+    {
+      box[k] = HUGE_VAL;
+      box[3 + k] = -HUGE_VAL;
+    }
+  }
+  /* the box of the leaf `ref` (count > 0) over the triangles order[first .. first + count) of tgeom */
+  BVH_HD static void leaf_box(const double *tgeom, const uint32_t *order, uint32_t ref, double *box)
+  {
+    const uint32_t first = leaf_first(ref), count = leaf_count(ref);
+    empty(box);
+    for (uint32_t j = 0; j < count; j++)
+    {
+      double tb[6], cen[3];
+      bvh_tri_box(tgeom + 9 * (size_t)order[first + j], tb, cen);
+      join(box, tb);
+    }
+  }
+  /* the box of the inner node `ref`, whose own child boxes are final */
+  BVH_HD static void inner_box(const double *nodes, uint32_t ref, double *box)
+  {
+    const double *nd = nodes + (size_t)ref * PT_BVH_SRC_DOUBLES;
+    empty(box);
+    join(box, nd);
+    join(box, nd + 6);
+  }
+
+  /* the restatement: nodes (n_nodes x PT_BVH_SRC_DOUBLES) refitted in place; false (and an assertion) where a child is not
+   * numbered above its parent */
+  static bool refit(double *nodes, size_t n_nodes, const uint32_t *order, const double *tgeom)
+  {
+    for (size_t i = n_nodes; i-- > 0;)
+      for (int c = 0; c < 2; c++)
+      {
+        const uint32_t ref = child_ref(nodes, (uint32_t)i, c);
+        double *box = nodes + i * PT_BVH_SRC_DOUBLES + 6 * c;
+        if (is_leaf(ref))
+        {
+          if (leaf_count(ref) != 0)
+            leaf_box(tgeom, order, ref, box);
+          continue;
+        }
+        const bool child_above_parent = ref > i && ref < n_nodes;
+        assert(child_above_parent);
+        if (!child_above_parent)
+          return false;
+        inner_box(nodes, ref, box);
+      }
+    return true;
+  }
+
+  /* The topology's levels, which the device sweeps from the deepest to the root: by_level = the node numbers sorted by depth
+   * (ascending within a level), level_begin[d] .. level_begin[d + 1] = the nodes of depth d.  Depends on the refs alone. */
+  static bool levels(const double *nodes, size_t n_nodes, std::vector<uint32_t> &by_level, std::vector<uint32_t> &level_begin)
+  {
+    std::vector<uint32_t> depth(n_nodes, 0);
+    uint32_t deepest = 0;
+    for (size_t i = 0; i < n_nodes; i++)
+      for (int c = 0; c < 2; c++)
+      {
+        const uint32_t ref = child_ref(nodes, (uint32_t)i, c);
+        if (is_leaf(ref))
+          continue;
+        if (!(ref > i && ref < n_nodes))
+          return false;
+        depth[ref] = depth[i] + 1;
+        deepest = std::max(deepest, depth[ref]);
+      }
+    level_begin.assign(n_nodes ? deepest + 2 : 1, 0);
+    for (size_t i = 0; i < n_nodes; i++)
+      level_begin[depth[i] + 1]++;
+    for (size_t d = 1; d < level_begin.size(); d++)
+      level_begin[d] += level_begin[d - 1];
+    by_level.resize(n_nodes);
+    std::vector<uint32_t> at(level_begin.begin(), level_begin.end());
+    for (size_t i = 0; i < n_nodes; i++)
+      by_level[at[depth[i]]++] = (uint32_t)i;
+    return true;
+  }
+};
+
 /* ---- the device builder (bvh_device.hip), as rt_hip_shim.hip calls it; HIP translation units only ---- */
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -534,6 +651,91 @@ hipError_t bvh_device_build(const double *tri_geom, uint32_t n, BvhDeviceTree *o
 
 /* tri_geom_leaf[k] = tri_geom[order[k]] (9 doubles each), on the null stream; all three in device memory */
 hipError_t bvh_device_gather_leaf(const double *tri_geom, const uint32_t *order, uint32_t n, double *tri_geom_leaf);
+#endif /* __HIPCC__ */
+
+/* ---- a scene's triangles moved in place (scene_update.hip, rt_hip_scene_update_vertices) ----
+ * What a triangle's records are made of, in one text for the host (scene_create_impl, rt_hip_shim.hip) and the device
+ * (k_update_triangles), and -- for HIP translation units only -- the interface of scene_update.hip.  Compiled with
+ * -ffp-contract=off on both sides: the records of an updated scene equal a freshly created scene's bit for bit. */
+
+/* One triangle (p0, p1, p2: xyz each): its tri_geom record g[9] = (v0, e1, e2) and its entry_src record b[PT_ENTRY_SRC_STRIDE],
+ * the phase-1 bound: a sphere around the centroid through the farthest vertex, slightly enlarged; feeds the conservative filter
+ * only, never a result. */
+BVH_HD inline void scene_triangle_entry(const double *p0, const double *p1, const double *p2, double *g, double *b)
+{
+  for (int k = 0; k < 3; k++)
+  {
+    g[k] = p0[k];
+    g[3 + k] = p1[k] - p0[k]; /* raytracer.c:132-133 */
+    g[6 + k] = p2[k] - p0[k];
+  }
+  const double cen[3] = {(p0[0] + p1[0] + p2[0]) / 3.0, (p0[1] + p1[1] + p2[1]) / 3.0, (p0[2] + p1[2] + p2[2]) / 3.0};
+  const double *vs[3] = {p0, p1, p2};
+  double rb2 = 0;
+  for (int j = 0; j < 3; j++)
+  {
+    const double dx = vs[j][0] - cen[0], dy = vs[j][1] - cen[1], dz = vs[j][2] - cen[2];
+    rb2 = std::fmax(rb2, dx * dx + dy * dy + dz * dz);
+  }
+  const double rb = std::sqrt(rb2) * (1.0 + 1e-9) + 1e-300;
+  b[0] = cen[0];
+  b[1] = cen[1];
+  b[2] = cen[2];
+  b[3] = rb * rb;
+  b[4] = std::sqrt(cen[0] * cen[0] + cen[1] * cen[1] + cen[2] * cen[2]) * (1.0 + 1e-12);
+  b[5] = rb;
+}
+
+/* its tri_normal record: calculate_surface_normal :42-45, normalize(cross(v2 - v0, v1 - v0)); NaN for a degenerate triangle */
+BVH_HD inline void scene_triangle_normal(const double *g, double *n)
+{
+  const double *e1 = g + 3, *e2 = g + 6;
+  const double cx = e2[1] * e1[2] - e2[2] * e1[1], cy = e2[2] * e1[0] - e2[0] * e1[2], cz = e2[0] * e1[1] - e2[1] * e1[0];
+  const double s = 1.0 / std::sqrt(cx * cx + cy * cy + cz * cz);
+  n[0] = cx * s;
+  n[1] = cy * s;
+  n[2] = cz * s;
+}
+
+/* corner k (0, 1, 2) of the triangle as the kernels see it: v0, v0 + e1, v0 + e2 */
+BVH_HD inline void scene_triangle_corner(const double *g, int k, double *p)
+{
+  for (int a = 0; a < 3; a++)
+    p[a] = k == 0 ? g[a] : g[a] + g[3 * k + a];
+}
+
+#if defined(__HIPCC__)
+
+/* the arrays of a scene that an update rewrites (device memory) */
+struct SceneUpdateArrays
+{
+  uint32_t n_tri = 0, n_nodes = 0;
+  double *tri_geom = nullptr, *tri_normal = nullptr; /* 9 n, 3 n */
+  double *entry_tri = nullptr;                       /* the triangles' part of entry_src: PT_ENTRY_SRC_STRIDE n */
+  uint32_t *tri_object = nullptr;                    /* n: the hull bits are cleared */
+  double *bvh_src = nullptr;                         /* n_nodes x PT_BVH_SRC_DOUBLES: the boxes are rewritten */
+  const uint32_t *bvh_tri = nullptr;                 /* n: the leaf order */
+  double *tri_geom_leaf = nullptr;                   /* 9 n */
+};
+
+/* what k_check_positions reduces, as the host reads it back */
+struct SceneUpdateCheck
+{
+  double max_len;      /* max |vertex| over the 3 n positions; +infinity where one is not <= 1e300 (NaN included) */
+  double lo[3], hi[3]; /* bounds of the corners as the kernels see them, joined by bvh_min / bvh_max */
+};
+#define SCENE_UPDATE_WORDS 8 /* 64-bit words of device workspace the reductions need: 7 of the check, 1 of r^2 */
+
+/* All on the null stream of the current device; positions = 9 doubles a triangle (v0, v1, v2) in device memory.
+ * scene_update_check reads the positions alone, writes `words` alone and waits for the result. */
+hipError_t scene_update_check(const double *positions, uint32_t n_tri, unsigned long long *words, SceneUpdateCheck *out);
+/* tri_geom, tri_normal, the entry records, tri_object's hull bits; *r2 = the largest squared distance of a corner from mesh_c
+ * (waits for it) */
+hipError_t scene_update_triangles(const SceneUpdateArrays &s, const double *positions, const double mesh_c[3],
+                                  unsigned long long *words, double *r2);
+/* BvhRefit on the device: the leaf children, then the inner ones level by level from the deepest (by_level in device memory,
+ * level_begin on the host: BvhRefit::levels), and tri_geom_leaf.  Enqueues only. */
+hipError_t scene_update_refit(const SceneUpdateArrays &s, const uint32_t *by_level, const uint32_t *level_begin, size_t n_levels);
 #endif /* __HIPCC__ */
 
 #endif /* BVH_BUILD_H */

@@ -13,6 +13,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -280,6 +281,16 @@ struct RtHipScene
   /* the hierarchy's origin (rt_hip_scene_bvh_info): RT_HIP_BVH_*, the least depth its leaves allow, the build's seconds */
   uint32_t bvh_builder = RT_HIP_BVH_HOST, bvh_max_depth = 0;
   double bvh_build_seconds = 0;
+  /* ---- moving the triangles in place (rt_hip_scene_update_vertices) ---- */
+  size_t blob_bytes = 0;     /* new positions must not lie inside the blob */
+  double reach_spheres = 0;  /* the spheres' part of `reach`: joined with the vertices' again by every update */
+  mutable std::atomic<int> live_accums{0}; /* RtHipAccum objects on this scene: their plans hold the view, so no update */
+  bool unusable = false;     /* an update failed after it had begun to write: only rt_hip_scene_destroy is allowed */
+  /* the hierarchy's levels (BvhRefit::levels), made by the first update and kept: they depend on the topology alone */
+  uint32_t *refit_by_level = nullptr; /* device memory, n_bvh_nodes */
+  std::vector<uint32_t> refit_level_begin;
+  uint64_t updates = 0;
+  double last_update_seconds = 0;
 };
 
 /* ---- progressive rendering: one frame accumulated over passes (rt_hip.h, RtHipAccum) ----------------------------------------
@@ -322,17 +333,6 @@ int usable_devices()
 
 bool have_device(int device) { return device >= 0 && device < usable_devices(); }
 
-/* host mirrors of the reference's vector.h operations (order matters) */
-struct H3
-{
-  double x, y, z;
-};
-H3 h_sub(H3 a, H3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-double h_dot(H3 a, H3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-H3 h_cross(H3 a, H3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-H3 h_scale(H3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-H3 h3(const double *p) { return {p[0], p[1], p[2]}; }
-
 double max_abs3(const double *v) { return std::fmax(std::fabs(v[0]), std::fmax(std::fabs(v[1]), std::fabs(v[2]))); }
 
 /* The pooled kernels' fixed-point sums rest on throughput <= 1, i.e. on albedo / MAX(albedo)
@@ -374,32 +374,7 @@ void sphere_entry(const double *center, double radius, double *g)
   g[5] = 0.0; /* a sphere is rejected when its centre is behind the origin at all (raytracer.c:84) */
 }
 
-/* One triangle: tri_geom record (v0, e1, e2) and its entry_src record, the phase-1 bound: a
- * sphere around the centroid through the farthest vertex, slightly enlarged; feeds the
- * conservative filter only, never a result. */
-void triangle_entry(const double *p0, const double *p1, const double *p2, double *g, double *b)
-{
-  H3 v0 = h3(p0), v1 = h3(p1), v2 = h3(p2);
-  H3 e1 = h_sub(v1, v0), e2 = h_sub(v2, v0); /* raytracer.c:132-133 */
-  g[0] = v0.x; g[1] = v0.y; g[2] = v0.z;
-  g[3] = e1.x; g[4] = e1.y; g[5] = e1.z;
-  g[6] = e2.x; g[7] = e2.y; g[8] = e2.z;
-  H3 cen = {(v0.x + v1.x + v2.x) / 3.0, (v0.y + v1.y + v2.y) / 3.0, (v0.z + v1.z + v2.z) / 3.0};
-  double rb2 = 0;
-  const H3 vs[3] = {v0, v1, v2};
-  for (int j = 0; j < 3; j++)
-  {
-    H3 dv = h_sub(vs[j], cen);
-    rb2 = std::fmax(rb2, h_dot(dv, dv));
-  }
-  const double rb = std::sqrt(rb2) * (1.0 + 1e-9) + 1e-300;
-  b[0] = cen.x;
-  b[1] = cen.y;
-  b[2] = cen.z;
-  b[3] = rb * rb;
-  b[4] = std::sqrt(h_dot(cen, cen)) * (1.0 + 1e-12);
-  b[5] = rb;
-}
+/* One triangle's records: scene_triangle_entry / scene_triangle_normal (bvh_build.h), one text with the device's. */
 
 /* ---- bounding-volume hierarchy over triangles: BvhBuild, in bvh_build.h (host C++, shared with the CPU test of its invariants) ---- */
 
@@ -416,6 +391,8 @@ int acquire_tables(const RtHipScene *scene, double near_R, hipStream_t stream, f
 {
   std::lock_guard<std::mutex> lock(scene->table_mutex);
   std::vector<TableSet> &tables = scene->tables;
+  if (scene->unusable)
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an update of its vertices failed half way (rt_hip_scene_update_vertices)");
   for (size_t k = 0; k < tables.size(); k++)
     if (tables[k].near_R == near_R)
     {
@@ -428,7 +405,16 @@ int acquire_tables(const RtHipScene *scene, double near_R, hipStream_t stream, f
       return RT_HIP_OK;
     }
   size_t k = tables.size();
-  if (k < RT_TABLE_SETS)
+  for (size_t j = 0; j < tables.size() && k == tables.size(); j++)
+    if (tables[j].near_R == -1.0 && tables[j].users == 0)
+      k = j; /* a set whose build failed, or that an update of the vertices left stale: rebuilt in place */
+  if (k < tables.size())
+  {
+    HIP_TRY(hipEventSynchronize(tables[k].built));
+    for (auto &r : tables[k].readers)
+      HIP_TRY(hipEventSynchronize(r.second));
+  }
+  else if (k < RT_TABLE_SETS)
   {
     TableSet t;
     if (k == 0)
@@ -882,7 +868,7 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   const size_t n_mat = n_spheres + n_meshes;
 
   /* ---- build the kernel layout on the host (pt_device.h) ---- */
-  double reach = 0, max_emission = 0, max_center = 0;
+  double reach = 0, reach_spheres = 0, max_emission = 0, max_center = 0;
   bool wide_range = false;
   for (size_t i = 0; i < n_spheres; i++)
     max_emission = std::fmax(max_emission, max_abs3(spheres[i].emission));
@@ -907,6 +893,7 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
       reach = std::fmax(reach, g[4] + std::fabs(spheres[i].radius));
     put_material(&mat[PT_MAT_STRIDE * i], spheres[i].flags, spheres[i].color, spheres[i].emission);
   }
+  reach_spheres = reach;
   size_t t = 0;
   for (size_t m = 0; m < n_meshes; m++)
     for (size_t k = 0; k < 3 * meshes[m].num_triangles; k++)
@@ -931,11 +918,8 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     {
       const RtHipVertex *v = meshes[m].vertices + 3 * k;
       double *g = &tgeom[9 * t];
-      triangle_entry(v[0].pos, v[1].pos, v[2].pos, g, &geom[PT_ENTRY_SRC_STRIDE * (n_spheres + t)]);
-      /* calculate_surface_normal :42-45: normalize(cross(v2-v0, v1-v0)) */
-      H3 c = h_cross(h3(g + 6), h3(g + 3));
-      H3 n = h_scale(c, 1.0 / std::sqrt(h_dot(c, c)));
-      tnorm[3 * t + 0] = n.x; tnorm[3 * t + 1] = n.y; tnorm[3 * t + 2] = n.z;
+      scene_triangle_entry(v[0].pos, v[1].pos, v[2].pos, g, &geom[PT_ENTRY_SRC_STRIDE * (n_spheres + t)]);
+      scene_triangle_normal(g, &tnorm[3 * t]);
       for (int j = 0; j < 3; j++)
       {
         ttex[6 * t + 2 * j + 0] = v[j].tex[0];
@@ -1177,6 +1161,8 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     sc->n_big = nb & ~1; /* whole pairs */
   }
   sc->reach = reach;
+  sc->reach_spheres = reach_spheres;
+  sc->blob_bytes = total;
   sc->max_emission = max_emission;
   sc->any_mirror_glass = any_mirror_glass;
   sc->view.any_mirror_glass = any_mirror_glass ? 1u : 0u;
@@ -1436,6 +1422,7 @@ void accum_free(RtHipAccum *a)
     return;
   DeviceScope scope(a->scene->device);
   (void)hipDeviceSynchronize(); /* no pass may still be using what it owns */
+  a->scene->live_accums--;
   delete a;
 }
 
@@ -1613,6 +1600,7 @@ struct ImageCtx
   std::vector<ncclComm_t> comms; /* one per distinct physical device (comm_of) */
   DeviceBuffer all_tiles, all_tiles8, image, image8; /* on the root, phys[0] */
   uint64_t builds = 0; /* how many times a context was (re)built: exposed for tests */
+  uint64_t updates = 0; /* how many times its scenes' vertices were moved in place instead (rt_hip_set_scene_updates) */
   int bvh_builder = RT_HIP_BVH_HOST; /* who built the scenes' hierarchies (rt_hip_set_bvh_builder) */
 };
 /* (never destroyed: at process exit the members' destructors would call into a HIP runtime that may be gone already) */
@@ -1625,6 +1613,7 @@ double g_last_phases[3] = {0, 0, 0}; /* rt_hip_last_image_phases */
 std::vector<int> g_device_map;
 bool g_device_map_env_read = false;
 int g_bvh_builder = RT_HIP_BVH_HOST; /* rt_hip_set_bvh_builder: the builder of the cached scenes.  Guarded by g_ctx_mutex. */
+bool g_scene_updates = false; /* rt_hip_set_scene_updates: moved vertices update the cached scenes in place.  Guarded by g_ctx_mutex. */
 
 void device_map_from_env()
 {
@@ -1652,7 +1641,7 @@ void device_map_from_env()
 }
 
 /* What needs an order: the streams drained, then the communicators, then each device's members with that device current.
- * `builds` survives. */
+ * `builds` and `updates` survive. */
 void ctx_release(ImageCtx &c)
 {
   int prev = 0;
@@ -1685,9 +1674,10 @@ void ctx_release(ImageCtx &c)
   }
   if (!c.phys.empty())
     (void)hipSetDevice(c.phys[0]);
-  const uint64_t builds = c.builds;
+  const uint64_t builds = c.builds, updates = c.updates;
   c = ImageCtx(); /* the root's gathered tiles and images */
   c.builds = builds;
+  c.updates = updates;
   (void)hipSetDevice(prev);
 }
 
@@ -1709,51 +1699,64 @@ struct CtxGuard
 };
 
 /* Everything that defines the scene, field by field (struct padding is not part of the scene), as runs of bytes handed
- * to `f(ptr, n)` in a fixed order.  The cached context keeps the concatenation (ImageCtx::scene_bytes) and is reused only
+ * to `f(ptr, n, vertices)` in a fixed order (vertices: the run is a mesh's RtHipVertex array).  The cached context keeps the concatenation (ImageCtx::scene_bytes) and is reused only
  * while a call's scene equals it byte for byte: scene_matches() compares run by run (memcmp, stopping at the first
  * difference) against the kept copy -- no per-call serialisation, no hashing: a frame of config 5's mesh used to rebuild
  * and hash 1.2 MB on the host inside every rt_hip_render_image() call (round-3 advisor finding). */
 template <class F>
 void scene_walk(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, F &&f)
 {
-  f(&n_spheres, sizeof n_spheres);
-  f(&n_meshes, sizeof n_meshes);
+  f(&n_spheres, sizeof n_spheres, false);
+  f(&n_meshes, sizeof n_meshes, false);
   for (size_t i = 0; i < n_spheres; i++)
   {
-    f(&spheres[i].flags, sizeof spheres[i].flags);
-    f(&spheres[i].radius, sizeof(double) * 10); /* radius, center, color, emission are contiguous doubles */
+    f(&spheres[i].flags, sizeof spheres[i].flags, false);
+    f(&spheres[i].radius, sizeof(double) * 10, false); /* radius, center, color, emission are contiguous doubles */
   }
   for (size_t m = 0; m < n_meshes; m++)
   {
-    f(&meshes[m].flags, sizeof meshes[m].flags);
-    f(meshes[m].color, sizeof(double) * 6); /* color, emission */
-    f(&meshes[m].num_triangles, sizeof meshes[m].num_triangles);
+    f(&meshes[m].flags, sizeof meshes[m].flags, false);
+    f(meshes[m].color, sizeof(double) * 6, false); /* color, emission */
+    f(&meshes[m].num_triangles, sizeof meshes[m].num_triangles, false);
     if (meshes[m].vertices)
-      f(meshes[m].vertices, meshes[m].num_triangles * 3 * sizeof(RtHipVertex));
+      f(meshes[m].vertices, meshes[m].num_triangles * 3 * sizeof(RtHipVertex), true);
   }
 }
 
-bool scene_matches(const std::vector<unsigned char> &kept, const RtHipSphere *spheres, size_t n_spheres,
-                   const RtHipMesh *meshes, size_t n_meshes)
+enum SceneMatch { SCENE_DIFFERS = 0, SCENE_SAME = 1, SCENE_MOVED = 2 /* equal but for vertex positions */ };
+
+SceneMatch scene_matches(const std::vector<unsigned char> &kept, const RtHipSphere *spheres, size_t n_spheres,
+                         const RtHipMesh *meshes, size_t n_meshes)
 {
   size_t at = 0;
-  bool same = true;
-  scene_walk(spheres, n_spheres, meshes, n_meshes, [&](const void *p, size_t n) {
+  bool same = true, moved = false;
+  scene_walk(spheres, n_spheres, meshes, n_meshes, [&](const void *p, size_t n, bool vertices) {
     if (!same)
       return;
-    if (n > kept.size() - at || memcmp(kept.data() + at, p, n) != 0)
+    if (n > kept.size() - at)
       same = false;
-    else
-      at += n;
+    else if (memcmp(kept.data() + at, p, n) != 0)
+    {
+      /* a vertex run may differ in positions; the tex coordinates behind each position must not */
+      const unsigned char *a = kept.data() + at, *b = static_cast<const unsigned char *>(p);
+      const size_t tex = offsetof(RtHipVertex, tex);
+      same = vertices;
+      for (size_t v = 0; same && v < n / sizeof(RtHipVertex); v++)
+        same = memcmp(a + v * sizeof(RtHipVertex) + tex, b + v * sizeof(RtHipVertex) + tex, sizeof(RtHipVertex) - tex) == 0;
+      moved = true;
+    }
+    at += n;
   });
-  return same && at == kept.size();
+  if (!same || at != kept.size())
+    return SCENE_DIFFERS;
+  return moved ? SCENE_MOVED : SCENE_SAME;
 }
 
 void scene_serialise(std::vector<unsigned char> &bytes, const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
                      size_t n_meshes)
 {
   bytes.clear();
-  scene_walk(spheres, n_spheres, meshes, n_meshes, [&](const void *p, size_t n) {
+  scene_walk(spheres, n_spheres, meshes, n_meshes, [&](const void *p, size_t n, bool) {
     const unsigned char *b = static_cast<const unsigned char *>(p);
     bytes.insert(bytes.end(), b, b + n);
   });
@@ -1771,8 +1774,32 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
   const bool force_comm = fc && fc[0] == '1';
   ImageCtx &c = g_ctx;
   if (c.G == G && c.W == W && c.H == H && c.force_comm == force_comm && (int)c.dev.size() == G && c.phys == phys &&
-      c.bvh_builder == g_bvh_builder && scene_matches(c.scene_bytes, spheres, n_spheres, meshes, n_meshes))
-    return RT_HIP_OK;
+      c.bvh_builder == g_bvh_builder)
+  {
+    const SceneMatch match = scene_matches(c.scene_bytes, spheres, n_spheres, meshes, n_meshes);
+    if (match == SCENE_SAME)
+      return RT_HIP_OK;
+    if (match == SCENE_MOVED && g_scene_updates)
+    { /* only vertex positions differ: every device's scene takes them in place; a failure drops the context (CtxGuard) */
+      size_t n_tri = 0;
+      for (size_t m = 0; m < n_meshes; m++)
+        n_tri += meshes[m].num_triangles;
+      std::vector<double> pos(9 * n_tri);
+      size_t at = 0;
+      for (size_t m = 0; m < n_meshes; m++)
+        for (size_t k = 0; k < 3 * meshes[m].num_triangles; k++, at += 3)
+          memcpy(&pos[at], meshes[m].vertices[k].pos, 3 * sizeof(double));
+      for (int g = 0; g < G; g++)
+      {
+        const int rc = rt_hip_scene_update_vertices_host(c.dev[g].scene, pos.data(), n_tri);
+        if (rc)
+          return rc;
+      }
+      scene_serialise(c.scene_bytes, spheres, n_spheres, meshes, n_meshes);
+      c.updates++;
+      return RT_HIP_OK;
+    }
+  }
   ctx_release(c);
   c.builds++;
   c.dev.resize(G);
@@ -2137,6 +2164,18 @@ uint64_t cache_builds_impl()
 {
   std::lock_guard<std::mutex> lock(g_ctx_mutex);
   return g_ctx.builds;
+}
+
+uint64_t cache_updates_impl()
+{
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  return g_ctx.updates;
+}
+
+void set_scene_updates_impl(int on)
+{
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  g_scene_updates = on != 0;
 }
 
 /* logical device `device` of the device map (the HIP device itself without a map) -> the HIP device, or RT_HIP_ENODEV */
@@ -3135,6 +3174,10 @@ int rt_hip_set_device_map(const int *map, int n)
 
 uint64_t rt_hip_cache_builds(void) { return cache_builds_impl(); }
 
+uint64_t rt_hip_cache_updates(void) { return cache_updates_impl(); }
+
+void rt_hip_set_scene_updates(int on) { set_scene_updates_impl(on); }
+
 int rt_hip_render_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
                         size_t n_meshes, const RtHipCamera *camera, const RtHipParams *params,
                         int n_devices, float *h_image_rgb, uint8_t *h_image_rgb8, uint64_t *h_stats,
@@ -3172,6 +3215,8 @@ void rt_hip_scene_destroy(RtHipScene *scene)
       (void)hipDeviceSynchronize();
       park_drop_ws(scene->device);
     }
+    if (scene->refit_by_level)
+      (void)hipFree(scene->refit_by_level);
     (void)hipFree(scene->blob);
   }
   delete scene;
@@ -3204,6 +3249,205 @@ int rt_hip_scene_hull_facets(const RtHipScene *scene, uint32_t *n_plus, uint32_t
     }
     return 0;
   });
+}
+
+/* ---- moving the triangles in place: new records and a refitted hierarchy (scene_update.hip), then the scalars and flags that
+ * scene_create_impl derives from them, by the same formulas.  Nothing of the scene is written before every refusal has been
+ * ruled out; once writing has begun a HIP failure leaves the scene unusable. */
+namespace
+{
+
+int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_triangles, bool on_host)
+{
+  if (!scene || !positions)
+    return fail(RT_HIP_EINVAL, "scene and positions are required");
+  if (scene->unusable)
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update of its vertices failed half way");
+  const size_t n = scene->view.n_triangles;
+  if (n == 0)
+    return fail(RT_HIP_EINVAL, "the scene has no triangles to move");
+  if (n_triangles != n)
+    return fail(RT_HIP_EINVAL, "%zu triangles given, the scene has %zu: an update keeps the count", n_triangles, n);
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  if (!on_host)
+  {
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof attr);
+    if (hipPointerGetAttributes(&attr, positions) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != scene->device)
+    {
+      (void)hipGetLastError();
+      return fail(RT_HIP_EINVAL, "d_positions is not device memory of the scene's device %d", scene->device);
+    }
+    const char *p = reinterpret_cast<const char *>(positions), *blob = static_cast<const char *>(scene->blob);
+    if (p + 72 * n > blob && p < blob + scene->blob_bytes)
+      return fail(RT_HIP_EINVAL, "d_positions lies inside the scene");
+  }
+  std::lock_guard<std::mutex> lock(scene->table_mutex);
+  if (scene->live_accums.load() > 0)
+    return fail(RT_HIP_EINVAL, "%d accumulation(s) on this scene are alive: destroy them before its vertices move", scene->live_accums.load());
+  for (const TableSet &t : scene->tables)
+    if (t.users > 0)
+      return fail(RT_HIP_EINVAL, "a launch of this scene is being submitted");
+  const auto t0 = std::chrono::steady_clock::now();
+
+  /* ---- the one workspace: the reductions' words, then (host form) the staged positions ---- */
+  DeviceBuffer ws;
+  const size_t words_bytes = 256;
+  static_assert(SCENE_UPDATE_WORDS * 8 <= 256, "the reductions' words");
+  if (ws.alloc(words_bytes + (on_host ? 72 * n : 0)) != hipSuccess)
+    return fail(RT_HIP_ENOMEM, "update workspace (%zu KB)", (words_bytes + (on_host ? 72 * n : 0)) >> 10);
+  unsigned long long *words = ws.at<unsigned long long>();
+  const double *d_pos = positions;
+  if (on_host)
+  {
+    HIP_TRY(hipMemcpy(ws.at<char>(words_bytes), positions, 72 * n, hipMemcpyHostToDevice));
+    d_pos = ws.at<double>(words_bytes);
+  }
+  SceneUpdateCheck chk;
+  HIP_TRY(scene_update_check(d_pos, (uint32_t)n, words, &chk));
+  if (!(chk.max_len <= 1e300)) /* scene_create_impl's rule */
+    return fail(RT_HIP_EINVAL, "a new position has a non-finite coordinate");
+
+  /* ---- the topology's levels, at the first update ---- */
+  const uint32_t n_nodes = scene->view.n_bvh_nodes;
+  if (!scene->refit_by_level)
+  {
+    std::vector<double> nodes((size_t)n_nodes * PT_BVH_SRC_DOUBLES);
+    std::vector<uint32_t> by_level, level_begin;
+    HIP_TRY(hipMemcpy(nodes.data(), scene->view.bvh_src, nodes.size() * 8, hipMemcpyDeviceToHost));
+    if (n_nodes == 0 || !BvhRefit::levels(nodes.data(), n_nodes, by_level, level_begin))
+      return fail(RT_HIP_ERUNTIME, "the hierarchy numbers a child below its parent: it cannot be refitted");
+    uint32_t *d_levels = nullptr;
+    if (hipMalloc(&d_levels, by_level.size() * 4) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      return fail(RT_HIP_ENOMEM, "the hierarchy's level array (%zu KB)", (by_level.size() * 4) >> 10);
+    }
+    const hipError_t e = hipMemcpy(d_levels, by_level.data(), by_level.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+      (void)hipFree(d_levels);
+      HIP_TRY(e);
+    }
+    scene->refit_by_level = d_levels;
+    scene->refit_level_begin.swap(level_begin);
+  }
+
+  /* ---- no launch may still read what is about to change: every table set's build and readers, as the recycling path waits ---- */
+  for (TableSet &t : scene->tables)
+  {
+    HIP_TRY(hipEventSynchronize(t.built));
+    for (auto &r : t.readers)
+      HIP_TRY(hipEventSynchronize(r.second));
+  }
+
+  /* ---- writing begins ---- */
+  for (TableSet &t : scene->tables)
+    t.near_R = -1.0; /* filter, fp32 nodes and tri32 records are rebuilt by the next launch (acquire_tables) */
+  auto broke = [&](hipError_t e, const char *what) {
+    (void)hipGetLastError();
+    scene->unusable = true;
+    return fail(RT_HIP_ERUNTIME, "%s: %s; the scene is unusable now (destroy it)", what, hipGetErrorString(e));
+  };
+  SceneUpdateArrays arr;
+  arr.n_tri = (uint32_t)n;
+  arr.n_nodes = n_nodes;
+  arr.tri_geom = const_cast<double *>(scene->view.tri_geom);
+  arr.tri_normal = const_cast<double *>(scene->view.tri_normal);
+  arr.entry_tri = const_cast<double *>(scene->view.entry_src) + PT_ENTRY_SRC_STRIDE * (size_t)scene->view.n_spheres;
+  arr.tri_object = const_cast<uint32_t *>(scene->view.tri_object);
+  arr.bvh_src = const_cast<double *>(scene->view.bvh_src);
+  arr.bvh_tri = scene->view.bvh_tri;
+  arr.tri_geom_leaf = const_cast<double *>(scene->view.tri_geom_leaf);
+  double mesh_c[3], r2 = 0;
+  for (int a = 0; a < 3; a++)
+    mesh_c[a] = 0.5 * chk.lo[a] + 0.5 * chk.hi[a];
+  hipError_t e = scene_update_triangles(arr, d_pos, mesh_c, words, &r2);
+  if (e != hipSuccess)
+    return broke(e, "updating the triangle records");
+  e = scene_update_refit(arr, scene->refit_by_level, scene->refit_level_begin.data(), scene->refit_level_begin.size() - 1);
+  if (e != hipSuccess)
+    return broke(e, "refitting the hierarchy");
+
+  /* ---- the derived scalars, as scene_create_impl has them ---- */
+  double mesh_R = std::sqrt(r2) * (1.0 + 1e-9) + 1e-300;
+  if (!(mesh_R < HUGE_VAL))
+    mesh_R = HUGE_VAL;
+  const double ea = chk.hi[0] - chk.lo[0], eb = chk.hi[1] - chk.lo[1], ec = chk.hi[2] - chk.lo[2];
+  const bool mesh_round = 3.14159265358979 * mesh_R * mesh_R <= 0.5 * (ea * eb + eb * ec + ec * ea);
+  for (int a = 0; a < 3; a++)
+    scene->mesh_c[a] = mesh_c[a];
+  scene->mesh_R = mesh_R;
+  scene->mesh_c_norm = std::sqrt(mesh_c[0] * mesh_c[0] + mesh_c[1] * mesh_c[1] + mesh_c[2] * mesh_c[2]) * (1.0 + 1e-12);
+  scene->view.mesh_round = mesh_round ? 1u : 0u;
+  scene->reach = std::fmax(scene->reach_spheres, chk.max_len);
+  scene->hull_flags = false; /* k_update_triangles cleared the bits */
+  if (n <= PT_HULL_MAX_TRIS && mesh_R >= 0 && mesh_R < 1e150)
+  {
+    const double extent = scene->mesh_c_norm + mesh_R; /* tau as at creation */
+    e = pt_launch_build_hull_flags(scene->view.tri_geom, scene->view.tri_normal, (uint32_t)n, 1.1368683772161603e-13 * extent,
+                                   arr.tri_object, nullptr);
+    if (e != hipSuccess)
+      return broke(e, "hull flags");
+    scene->hull_flags = true;
+  }
+  e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess)
+    return broke(e, "waiting for the update");
+  scene->updates++;
+  scene->last_update_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RT_HIP_OK;
+}
+
+} // namespace
+
+int rt_hip_scene_update_vertices(RtHipScene *scene, const double *d_positions, size_t n_triangles)
+{
+  return guarded("rt_hip_scene_update_vertices", [&] { return scene_update_impl(scene, d_positions, n_triangles, false); });
+}
+
+int rt_hip_scene_update_vertices_host(RtHipScene *scene, const double *h_positions, size_t n_triangles)
+{
+  return guarded("rt_hip_scene_update_vertices_host", [&] { return scene_update_impl(scene, h_positions, n_triangles, true); });
+}
+
+int rt_hip_scene_update_info(const RtHipScene *scene, uint64_t *updates, double *last_seconds)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_update_info: scene is NULL");
+  if (updates) *updates = scene->updates;
+  if (last_seconds) *last_seconds = scene->last_update_seconds;
+  return RT_HIP_OK;
+}
+
+int rt_hip_scene_read_triangles(const RtHipScene *scene, double *geom, double *normal, double *entry, uint32_t *object)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_read_triangles: scene is NULL");
+  const size_t n = scene->view.n_triangles;
+  if (n == 0)
+    return RT_HIP_OK;
+  DeviceScope on(scene->device);
+  HIP_TRY(on.status);
+  if (geom) HIP_TRY(hipMemcpy(geom, scene->view.tri_geom, 72 * n, hipMemcpyDeviceToHost));
+  if (normal) HIP_TRY(hipMemcpy(normal, scene->view.tri_normal, 24 * n, hipMemcpyDeviceToHost));
+  if (entry)
+    HIP_TRY(hipMemcpy(entry, scene->view.entry_src + PT_ENTRY_SRC_STRIDE * (size_t)scene->view.n_spheres, PT_ENTRY_SRC_STRIDE * 8 * n,
+                      hipMemcpyDeviceToHost));
+  if (object) HIP_TRY(hipMemcpy(object, scene->view.tri_object, 4 * n, hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
+int rt_hip_scene_bounds(const RtHipScene *scene, double mesh_center[3], double *mesh_radius, double *reach, uint32_t *mesh_round)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_bounds: scene is NULL");
+  if (mesh_center) memcpy(mesh_center, scene->mesh_c, sizeof scene->mesh_c);
+  if (mesh_radius) *mesh_radius = scene->mesh_R;
+  if (reach) *reach = scene->reach;
+  if (mesh_round) *mesh_round = scene->view.mesh_round;
+  return RT_HIP_OK;
 }
 
 const char *rt_hip_kernel_name(const RtHipScene *scene, uint32_t integrator)
@@ -3449,6 +3693,7 @@ int rt_hip_accum_create(const RtHipScene *scene, const RtHipCamera *camera, cons
     if (!a)
       return fail(RT_HIP_ENOMEM, "accumulation: out of host memory");
     a->scene = scene;
+    scene->live_accums++; /* until accum_free: the plan below holds the scene's view, so its vertices may not move meanwhile */
     /* the plan of a one-shot launch of the whole budget with a chunk workspace and the suggested chunks: the same member, the same
      * sum form, the same fallback rows; the fixed-point scale is the budget's (launch_prepare) */
     const uint32_t chunks = rt_hip_suggest_chunks_depth(scene, params->tile_count, params->samples, params->max_depth);
@@ -3811,7 +4056,7 @@ int rt_hip_selftest_intersect(int kind, const double *h_rays, const double *h_pr
         memcpy(&prims[4 * i], e, 4 * sizeof(double));
       }
       else
-        triangle_entry(h_prims + 9 * i, h_prims + 9 * i + 3, h_prims + 9 * i + 6, &prims[9 * i], e);
+        scene_triangle_entry(h_prims + 9 * i, h_prims + 9 * i + 3, h_prims + 9 * i + 6, &prims[9 * i], e);
       if (!(e[4] <= 1e17))
         return fail(RT_HIP_ELIMIT, "primitive %zu: centre beyond 1e17", i);
       max_center = std::fmax(max_center, e[4]);

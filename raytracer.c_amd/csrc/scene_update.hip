@@ -1,0 +1,245 @@
+/* scene_update.hip -- a scene's triangles moved in place (rt_hip_scene_update_vertices): every per-triangle record the kernels
+ * read is recomputed on the device from new positions, and the existing hierarchy is refitted -- same topology, same leaf order,
+ * new boxes.  The contracts are bvh_build.h's scene_triangle_* inlines (the records: one text with scene_create_impl) and BvhRefit
+ * (bvh_build.h: the boxes); both are met bit for bit, which rests on -ffp-contract=off and on reductions that are maxima and
+ * minima only -- no result depends on the order threads arrive in.
+ *   k_check_positions    max |vertex| and the bounds of the corners: reads the positions, writes seven words, nothing of the scene
+ *   k_update_triangles   tri_geom, tri_normal, the entry_src records, tri_object's hull bits cleared; max r^2 about the new centre
+ *   k_refit_leaves       one thread a child slot: the box of a leaf child from tri_geom through bvh_tri
+ *   k_refit_level        one thread a child slot of one level's nodes: the box of an inner child from that node's two boxes;
+ *                        launched level by level from the deepest, so every launch reads boxes an earlier one finished
+ *   tri_geom_leaf        bvh_device_gather_leaf
+ * 256 threads a workgroup, no scratch, no LDS; no kernel waits for another workgroup: a wave reduces by lane shuffles and hands
+ * its result to one atomic max / min on a 64-bit key. */
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "bvh_build.h"
+
+namespace
+{
+
+constexpr int UPD_BLOCK = 256;
+constexpr uint32_t UPD_CHECK_BLOCKS = 1024; /* k_check_positions strides over the triangles: at most 4096 waves meet the atomics */
+
+/* 64 bits that order as the doubles do, -0.0 below 0.0 (the order of bvh_min / bvh_max) */
+__host__ __device__ inline unsigned long long key_of(double d)
+{
+  unsigned long long u;
+  memcpy(&u, &d, sizeof u);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__host__ __device__ inline double double_of(unsigned long long k)
+{
+  const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+  double d;
+  memcpy(&d, &u, sizeof d);
+  return d;
+}
+
+__device__ inline unsigned long long wave_max(unsigned long long k)
+{
+  for (int d = 32; d >= 1; d >>= 1)
+  {
+    const unsigned long long o = __shfl_xor(k, d);
+    k = o > k ? o : k;
+  }
+  return k;
+}
+__device__ inline unsigned long long wave_min(unsigned long long k)
+{
+  for (int d = 32; d >= 1; d >>= 1)
+  {
+    const unsigned long long o = __shfl_xor(k, d);
+    k = o < k ? o : k;
+  }
+  return k;
+}
+
+/* words[0] = key of max |vertex|, words[1..3] = keys of lo, words[4..6] = keys of hi */
+__global__ void __launch_bounds__(UPD_BLOCK) k_check_positions(const double *__restrict__ positions, uint32_t n,
+                                                              unsigned long long *__restrict__ words)
+{
+  double len = 0.0, lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  for (uint32_t t = blockIdx.x * UPD_BLOCK + threadIdx.x; t < n; t += gridDim.x * UPD_BLOCK)
+  {
+    double p[9], g[9], b[PT_ENTRY_SRC_STRIDE];
+    for (int k = 0; k < 9; k++)
+      p[k] = positions[9 * (size_t)t + k];
+    for (int j = 0; j < 3; j++)
+    {
+      const double *q = p + 3 * j;
+      const double l = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+      len = (l <= 1e300) ? std::fmax(len, l) : HUGE_VAL; /* NaN and what lies beyond the limit alike */
+    }
+    scene_triangle_entry(p, p + 3, p + 6, g, b);
+    for (int j = 0; j < 3; j++)
+    {
+      double c[3];
+      scene_triangle_corner(g, j, c);
+      for (int a = 0; a < 3; a++)
+      {
+        lo[a] = bvh_min(lo[a], c[a]);
+        hi[a] = bvh_max(hi[a], c[a]);
+      }
+    }
+  }
+  const unsigned long long kl = wave_max(key_of(len));
+  unsigned long long klo[3], khi[3];
+  for (int a = 0; a < 3; a++)
+  {
+    klo[a] = wave_min(key_of(lo[a]));
+    khi[a] = wave_max(key_of(hi[a]));
+  }
+  if ((threadIdx.x & 63) == 0)
+  {
+    atomicMax(&words[0], kl);
+    for (int a = 0; a < 3; a++)
+    {
+      atomicMin(&words[1 + a], klo[a]);
+      atomicMax(&words[4 + a], khi[a]);
+    }
+  }
+}
+
+/* word[0] = key of the largest squared distance of a corner from (cx, cy, cz) */
+__global__ void __launch_bounds__(UPD_BLOCK) k_update_triangles(SceneUpdateArrays s, const double *__restrict__ positions, double cx,
+                                                               double cy, double cz, unsigned long long *__restrict__ word)
+{
+  const uint32_t t = blockIdx.x * UPD_BLOCK + threadIdx.x;
+  double r2 = 0.0;
+  if (t < s.n_tri)
+  {
+    double p[9], g[9], b[PT_ENTRY_SRC_STRIDE], nrm[3];
+    for (int k = 0; k < 9; k++)
+      p[k] = positions[9 * (size_t)t + k];
+    scene_triangle_entry(p, p + 3, p + 6, g, b);
+    scene_triangle_normal(g, nrm);
+    for (int k = 0; k < 9; k++)
+      s.tri_geom[9 * (size_t)t + k] = g[k];
+    for (int k = 0; k < 3; k++)
+      s.tri_normal[3 * (size_t)t + k] = nrm[k];
+    for (int k = 0; k < PT_ENTRY_SRC_STRIDE; k++)
+      s.entry_tri[PT_ENTRY_SRC_STRIDE * (size_t)t + k] = b[k];
+    s.tri_object[t] &= ~(PT_HULL_PLUS | PT_HULL_MINUS);
+    for (int j = 0; j < 3; j++)
+    {
+      double c[3];
+      scene_triangle_corner(g, j, c);
+      const double dx = c[0] - cx, dy = c[1] - cy, dz = c[2] - cz;
+      r2 = std::fmax(r2, dx * dx + dy * dy + dz * dz);
+    }
+  }
+  const unsigned long long k = wave_max(key_of(r2));
+  if ((threadIdx.x & 63) == 0)
+    atomicMax(word, k);
+}
+
+__device__ inline void store_box(double *to, const double *box)
+{
+  for (int k = 0; k < 6; k++)
+    to[k] = box[k];
+}
+
+__global__ void __launch_bounds__(UPD_BLOCK) k_refit_leaves(SceneUpdateArrays s)
+{
+  const uint32_t slot = blockIdx.x * UPD_BLOCK + threadIdx.x;
+  if (slot >= 2u * s.n_nodes)
+    return;
+  const uint32_t node = slot >> 1, c = slot & 1u;
+  const uint32_t ref = BvhRefit::child_ref(s.bvh_src, node, (int)c);
+  if (!BvhRefit::is_leaf(ref) || BvhRefit::leaf_count(ref) == 0)
+    return;
+  if (BvhRefit::leaf_first(ref) + BvhRefit::leaf_count(ref) > s.n_tri)
+    return; /* (no tree of either builder has such a leaf: nothing is read past the order) */
+  double box[6];
+  BvhRefit::leaf_box(s.tri_geom, s.bvh_tri, ref, box);
+  store_box(s.bvh_src + (size_t)node * PT_BVH_SRC_DOUBLES + 6 * c, box);
+}
+
+/* the nodes by_level[begin .. end): their inner children's boxes, from nodes one level down */
+__global__ void __launch_bounds__(UPD_BLOCK) k_refit_level(SceneUpdateArrays s, const uint32_t *__restrict__ by_level, uint32_t begin,
+                                                          uint32_t end)
+{
+  const uint32_t slot = blockIdx.x * UPD_BLOCK + threadIdx.x;
+  if (slot >= 2u * (end - begin))
+    return;
+  const uint32_t node = by_level[begin + (slot >> 1)], c = slot & 1u;
+  if (node >= s.n_nodes)
+    return;
+  const uint32_t ref = BvhRefit::child_ref(s.bvh_src, node, (int)c);
+  if (BvhRefit::is_leaf(ref) || ref >= s.n_nodes)
+    return;
+  double box[6];
+  BvhRefit::inner_box(s.bvh_src, ref, box);
+  store_box(s.bvh_src + (size_t)node * PT_BVH_SRC_DOUBLES + 6 * c, box);
+}
+
+#define UPD_TRY(expr)             \
+  do                              \
+  {                               \
+    const hipError_t e_ = (expr); \
+    if (e_ != hipSuccess)         \
+      return e_;                  \
+  } while (0)
+
+} // namespace
+
+hipError_t scene_update_check(const double *positions, uint32_t n_tri, unsigned long long *words, SceneUpdateCheck *out)
+{
+  if (!positions || !words || !out || n_tri == 0)
+    return hipErrorInvalidValue;
+  unsigned long long h[7];
+  h[0] = key_of(0.0);
+  for (int a = 0; a < 3; a++)
+  {
+    h[1 + a] = key_of(HUGE_VAL);
+    h[4 + a] = key_of(-HUGE_VAL);
+  }
+  UPD_TRY(hipMemcpy(words, h, sizeof h, hipMemcpyHostToDevice));
+  const uint32_t blocks = (n_tri + UPD_BLOCK - 1) / UPD_BLOCK;
+  hipLaunchKernelGGL(k_check_positions, dim3(blocks < UPD_CHECK_BLOCKS ? blocks : UPD_CHECK_BLOCKS), dim3(UPD_BLOCK), 0, nullptr,
+                     positions, n_tri, words);
+  UPD_TRY(hipGetLastError());
+  UPD_TRY(hipMemcpy(h, words, sizeof h, hipMemcpyDeviceToHost));
+  out->max_len = double_of(h[0]);
+  for (int a = 0; a < 3; a++)
+  {
+    out->lo[a] = double_of(h[1 + a]);
+    out->hi[a] = double_of(h[4 + a]);
+  }
+  return hipSuccess;
+}
+
+hipError_t scene_update_triangles(const SceneUpdateArrays &s, const double *positions, const double mesh_c[3],
+                                  unsigned long long *words, double *r2)
+{
+  if (!positions || !words || !r2 || s.n_tri == 0)
+    return hipErrorInvalidValue;
+  unsigned long long h = key_of(0.0);
+  UPD_TRY(hipMemcpy(words + 7, &h, sizeof h, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_update_triangles, dim3((s.n_tri + UPD_BLOCK - 1) / UPD_BLOCK), dim3(UPD_BLOCK), 0, nullptr, s, positions,
+                     mesh_c[0], mesh_c[1], mesh_c[2], words + 7);
+  UPD_TRY(hipGetLastError());
+  UPD_TRY(hipMemcpy(&h, words + 7, sizeof h, hipMemcpyDeviceToHost));
+  *r2 = double_of(h);
+  return hipSuccess;
+}
+
+hipError_t scene_update_refit(const SceneUpdateArrays &s, const uint32_t *by_level, const uint32_t *level_begin, size_t n_levels)
+{
+  if (s.n_tri == 0 || s.n_nodes == 0 || !by_level || !level_begin || n_levels == 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_refit_leaves, dim3((2u * s.n_nodes + UPD_BLOCK - 1) / UPD_BLOCK), dim3(UPD_BLOCK), 0, nullptr, s);
+  for (size_t d = n_levels - 1; d-- > 0;) /* (the deepest level's children are leaves all) */
+  {
+    const uint32_t begin = level_begin[d], end = level_begin[d + 1];
+    if (end <= begin || end > s.n_nodes)
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_refit_level, dim3((2u * (end - begin) + UPD_BLOCK - 1) / UPD_BLOCK), dim3(UPD_BLOCK), 0, nullptr, s, by_level,
+                       begin, end);
+  }
+  UPD_TRY(hipGetLastError());
+  return bvh_device_gather_leaf(s.tri_geom, s.bvh_tri, s.n_tri, s.tri_geom_leaf);
+}

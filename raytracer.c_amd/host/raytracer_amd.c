@@ -63,6 +63,13 @@ void rt_set_bvh_builder(int builder)
     g_bvh_builder = builder;
 }
 int rt_get_bvh_builder(void) { return g_bvh_builder; }
+static int g_scene_updates = 0;
+void rt_set_scene_updates(int on)
+{
+  g_scene_updates = on != 0;
+  rt_hip_set_scene_updates(g_scene_updates);
+}
+int rt_get_scene_updates(void) { return g_scene_updates; }
 double rt_last_render_seconds(void) { return g_last_seconds; }
 static long long g_last_samples = 0; /* render_adaptive: pixel samples rendered */
 static const volatile int *g_cancel_flag = NULL; /* render_progressive polls it between passes */

@@ -188,6 +188,14 @@ SHIM_SYMBOLS = {
     "rt_hip_scene_bvh_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_scene_bvh_build_seconds": (C.c_double, [C.c_void_p]),
     "rt_hip_set_bvh_builder": (C.c_int, [C.c_int]),
+    "rt_hip_scene_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rt_hip_scene_update_vertices_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rt_hip_scene_update_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "rt_hip_scene_read_triangles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_scene_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 3), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_uint32)]),
+    "rt_hip_set_scene_updates": (None, [C.c_int]),
+    "rt_hip_cache_updates": (C.c_uint64, []),
     "rt_hip_scene_device": (C.c_int, [C.c_void_p]),
     "rt_hip_scene_primitives": (C.c_size_t, [C.c_void_p]),
     "rt_hip_scene_hull_facets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -322,6 +330,8 @@ HOST_SYMBOLS = {
     "rt_get_integrator": (C.c_int, []),
     "rt_set_bvh_builder": (None, [C.c_int]),
     "rt_get_bvh_builder": (C.c_int, []),
+    "rt_set_scene_updates": (None, [C.c_int]),
+    "rt_get_scene_updates": (C.c_int, []),
     "rt_set_devices": (None, [C.c_int]),
     "rt_get_max_depth": (C.c_int, []),
     "rt_get_seed": (C.c_uint64, []),

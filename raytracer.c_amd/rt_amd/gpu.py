@@ -111,6 +111,53 @@ class GpuScene:
                                                order.ctypes.data if order.size else None), "rt_hip_scene_bvh_read")
         return nodes, order
 
+    def update_vertices(self, positions):
+        """Moves the scene's triangles in place (rt_hip.h, rt_hip_scene_update_vertices): positions of shape (n, 3, 3) -- triangle,
+        corner, xyz, in scene triangle order -- as a float64 torch tensor on the scene's device (taken where it lies, no host
+        copy) or a numpy array (staged by the shim).  Synchronous.  The records are recomputed and the hierarchy REFITTED on the
+        device: frames, bytes and counters equal a freshly created scene's; bvh_info()["tree_cost"] reports the refitted tree's
+        cost, and a caller recreates the scene when that has drifted too far from a fresh tree's.  Temporal and Preview assume a
+        static scene: reset them after an update.  Open accumulations refuse the update (close them first).  self.scene keeps
+        the vertices the scene was created from."""
+        n = self.scene.n_triangles
+        if isinstance(positions, torch.Tensor):
+            if positions.dtype != torch.float64 or tuple(positions.shape) != (n, 3, 3):
+                raise ValueError(f"update_vertices: a float64 tensor of shape ({n}, 3, 3) is expected")
+            t = positions.contiguous()
+            if t.is_cuda:   # what produced the tensor on torch's current stream must be done: the shim works on the null stream
+                torch.cuda.current_stream(t.device).synchronize()
+            # (a host tensor, or one on another device, goes to the device entry all the same: the shim refuses it)
+            _check(self.shim.rt_hip_scene_update_vertices(self.handle, C.c_void_p(t.data_ptr()), n), "rt_hip_scene_update_vertices")
+            return
+        import numpy as np
+        a = np.ascontiguousarray(positions, dtype=np.float64)
+        if a.shape != (n, 3, 3):
+            raise ValueError(f"update_vertices: shape ({n}, 3, 3) is expected, not {a.shape}")
+        _check(self.shim.rt_hip_scene_update_vertices_host(self.handle, a.ctypes.data, n), "rt_hip_scene_update_vertices_host")
+
+    def update_info(self):
+        """{"updates": how many update_vertices() the scene has taken, "last_seconds": the host-clock time of the last}"""
+        k, s = C.c_uint64(0), C.c_double(0)
+        _check(self.shim.rt_hip_scene_update_info(self.handle, C.byref(k), C.byref(s)), "rt_hip_scene_update_info")
+        return {"updates": k.value, "last_seconds": s.value}
+
+    def read_triangles(self):
+        """for tests: dict of numpy arrays as the kernels read them -- geom (n, 9: v0, e1, e2), normal (n, 3), entry (n, 6: the
+        phase-1 bound), object (n, uint32: material slot and hull bits)"""
+        import numpy as np
+        n = self.scene.n_triangles
+        out = dict(geom=np.zeros((n, 9)), normal=np.zeros((n, 3)), entry=np.zeros((n, 6)), object=np.zeros(n, dtype=np.uint32))
+        _check(self.shim.rt_hip_scene_read_triangles(self.handle, *[out[k].ctypes.data if n else None
+                                                                    for k in ("geom", "normal", "entry", "object")]),
+               "rt_hip_scene_read_triangles")
+        return out
+
+    def bounds(self):
+        """for tests: {"mesh_center", "mesh_radius" (< 0: no triangles), "reach", "mesh_round"}"""
+        c, r, reach, rnd = (C.c_double * 3)(), C.c_double(0), C.c_double(0), C.c_uint32(0)
+        _check(self.shim.rt_hip_scene_bounds(self.handle, C.byref(c), C.byref(r), C.byref(reach), C.byref(rnd)), "rt_hip_scene_bounds")
+        return {"mesh_center": tuple(c), "mesh_radius": r.value, "reach": reach.value, "mesh_round": bool(rnd.value)}
+
     def suggest_chunks(self, count, samples=None, max_depth=None):
         return int(self.shim.rt_hip_suggest_chunks_depth(self.handle, count, samples or self.scene.samples,
                                                          self.scene.max_depth if max_depth is None else max_depth))
