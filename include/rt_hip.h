@@ -661,9 +661,9 @@ int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t widt
  *   7. out8 = the render epilogue's tonemap of the widened out.
  * The contract is total: any buffer contents and any camera bytes (a degenerate or NaN camera, depths that are 0, negative or inf,
  * a zeroed history) have a defined result.  len = 0 marks a pixel the next frame must not use; a zero-filled history (buffers and
- * camera) behaves like no history.  Out of scope: moving objects (the scene is static between the two frames: after
- * rt_hip_scene_update_vertices the caller starts a new history), demodulated
- * history, variance estimates.
+ * camera) behaves like no history.  Step 3 assumes a scene that is static between the two frames; after
+ * rt_hip_scene_update_vertices the caller gives the previous points instead (rt_hip_reproject_points, below) and keeps the
+ * history.  Out of scope: moving spheres (the scene cannot move them), topology changes, demodulated history, variance estimates.
  *   - rt_hip_reproject_defaults: flags 0, max_history = 32, depth_tol = 0.05, normal_min = 0.5 (DESIGN, "`pt_reproject`": the sweep).
  *   - rt_hip_reproject: asynchronous on `stream`, on the device that holds d_rgb.  d_out_rgb and d_out_len are required,
  *     d_out_rgb8 and d_out_motion (2 floats per pixel) may be NULL; d_out_rgb == d_rgb is allowed (in place).  No output may overlap
@@ -687,6 +687,49 @@ int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHi
                            const float *h_hist_len, const RtHipAov *h_hist_aov, const RtHipCamera *hist_camera, int32_t width,
                            int32_t height, const RtHipReprojectParams *params, int device, float *h_out_rgb, uint8_t *h_out_rgb8,
                            float *h_out_len, float *h_out_motion);
+
+/* ---- reprojection across vertex updates: previous points per pixel -----------------------------------------------------------
+ * After rt_hip_scene_update_vertices the surface under a pixel was somewhere else one frame ago, and step 3 above, which rebuilds
+ * the first-hit point from today's geometry, looks the history up where the surface was not.  Two calls close the gap: a
+ * RT_HIP_RAYS_CAMERA_UV query through the pixel centres gives each pixel's triangle and barycentrics; rt_hip_prev_points blends
+ * the triangle's PREVIOUS corners with them; rt_hip_reproject_points starts from that point.
+ *
+ * rt_hip_prev_points: d_hits as rt_hip_query_rays fills it (status, prim, bary and point are required, the other fields are not
+ * read), n entries (0 <= n < 2^32); d_positions: 9 doubles per triangle (v0, v1, v2) in scene triangle order -- the layout of
+ * rt_hip_scene_update_vertices, the numbering of the query's prim --, the positions the scene had at the previous frame
+ * (n_triangles may be 0, d_positions then NULL); d_points: 3 doubles per entry.  fp64 +, -, *, unfused, in the order written.  Entry i:
+ *   - status != 1: three quiet NaNs, bits 0x7FF8000000000000;
+ *   - status == 1 and prim == 0xFFFFFFFF (a sphere, which does not move): the three words of point, copied as bits;
+ *   - status == 1 and prim < n_triangles: u = bary[0], v = bary[1], w0 = (1.0 - u) - v, out_k = (a_k*w0 + b_k*u) + c_k*v for
+ *     k = x, y, z with a, b, c the triangle's corners -- the blend intersect_triangle applies to the texture coordinates
+ *     (raytracer.c:158-164), applied to positions;
+ *   - any other prim: three quiet NaNs.
+ * The contract is total: any bits in any input have a defined result (overflow to inf is a result; a NaN that the blend's own
+ * arithmetic makes is a NaN, its sign and payload the machine's).  d_points == d_hits->point is
+ * allowed (a lane reads its own point before it writes); any other overlap of d_points with an input is RT_HIP_EINVAL.
+ * Asynchronous on `stream`, on the device that holds d_points.  Arguments are checked before the device is looked for:
+ * RT_HIP_EINVAL, then RT_HIP_ENODEV.  n == 0 is RT_HIP_OK and launches nothing.  A call takes no pool, workspace or status word.
+ * rt_hip_prev_points_host: the same from host arrays, synchronous, with buffers of its own, on logical device `device` of
+ * rt_hip_render_image's device map.
+ *
+ * rt_hip_reproject_points: rt_hip_reproject's arguments and d_prev_points.  NULL: the call is rt_hip_reproject itself, the same
+ * kernel and the same bits.  Otherwise 3 doubles per pixel, row-major, and the contract is rt_hip_reproject's with step 3 replaced:
+ *   3'. P = prev_points(p).  If a component of P is not finite: out = c, len = 1, motion = qNaN.  Done.  (No surface to look up: a
+ *       disocclusion, a miss, an invalid ray.)  The frame's camera is not read in this form.
+ * Steps 1, 2 and 4-7 are unchanged with D = P - pos': zexp is the previous point's distance from the previous camera, and motion
+ * is the true screen-space motion, the surface's own included.  Parameters, ranges and overlap rules are rt_hip_reproject's;
+ * d_prev_points must not overlap any output (RT_HIP_EINVAL).  rt_hip_reproject_points_image: the same from host arrays. */
+int rt_hip_prev_points(const RtHipHits *d_hits, uint64_t n, const double *d_positions, size_t n_triangles, double *d_points, void *stream);
+int rt_hip_prev_points_host(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles, int device,
+                            double *h_points);
+int rt_hip_reproject_points(const float *d_rgb, const RtHipAov *d_aov, const RtHipCamera *camera, const float *d_hist_rgb,
+                            const float *d_hist_len, const RtHipAov *d_hist_aov, const RtHipCamera *hist_camera, int32_t width,
+                            int32_t height, const RtHipReprojectParams *params, const double *d_prev_points, float *d_out_rgb,
+                            uint8_t *d_out_rgb8, float *d_out_len, float *d_out_motion, void *stream);
+int rt_hip_reproject_points_image(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
+                                  const float *h_hist_len, const RtHipAov *h_hist_aov, const RtHipCamera *hist_camera, int32_t width,
+                                  int32_t height, const RtHipReprojectParams *params, const double *h_prev_points, int device,
+                                  float *h_out_rgb, uint8_t *h_out_rgb8, float *h_out_len, float *h_out_motion);
 
 /* ---- guided upsampling: a full-size frame from a low-resolution render -------------------------------------------------------
  * Joint bilateral upsampling (Kopf et al. 2007): the colour is rendered (and denoised) at a fraction of the size and brought to

@@ -462,6 +462,17 @@ struct PtReproject
   double max_history, depth_tol, normal_min;
 };
 
+/* The previous points of n query hits (rt_hip.h, rt_hip_prev_points; pt_prev_points in pt_kernel.hip): the hits' status, prim,
+ * bary (2 doubles) and point (3 doubles), the previous positions (9 doubles per triangle; may be null with n_triangles 0) and the
+ * output, 3 doubles per entry (it may be `point`). */
+struct PtPrevPoints
+{
+  const uint32_t *status, *prim;
+  const double *bary, *point, *positions;
+  double *out;
+  uint64_t n, n_triangles;
+};
+
 /* One guided upsampling (rt_hip.h, rt_hip_upsample; pt_upsample in pt_kernel.hip): the low frame's row-major wl x hl images
  * (colour, normal, depth, hits; albedo with demodulate, object with object_edges), the guides of the w x h frame (the same fields
  * without a colour), and the outputs -- out_rgb always, the bytes and the confidence where wanted. */
@@ -595,6 +606,10 @@ hipError_t pt_launch_blend(const PtBlend &args, hipStream_t stream);
 hipError_t pt_launch_denoise(const PtDenoise &args, int iterations, double sigma_color, hipStream_t stream);
 /* temporal reprojection: one launch, a 16 x 16 block of pixels per workgroup, on `stream` */
 hipError_t pt_launch_reproject(const PtReproject &args, hipStream_t stream);
+/* the same from the caller's previous points (3 doubles per pixel) in place of step 3: pt_reproject_points */
+hipError_t pt_launch_reproject_points(const PtReproject &args, const double *prev_points, hipStream_t stream);
+/* the previous points of query hits: one launch, an entry per lane, on `stream` (n >= 1) */
+hipError_t pt_launch_prev_points(const PtPrevPoints &args, hipStream_t stream);
 /* guided upsampling: one launch, a 16 x 16 block of the high frame's pixels per workgroup, on `stream` */
 hipError_t pt_launch_upsample(const PtUpsample &args, hipStream_t stream);
 hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,

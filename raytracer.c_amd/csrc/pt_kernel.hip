@@ -1477,102 +1477,160 @@ __device__ __forceinline__ void reproject_store(const PtReproject &R, size_t p, 
   }
 }
 
-extern "C" __global__ __launch_bounds__(256) void pt_reproject(const PtReproject R)
+/* The body of pt_reproject and pt_reproject_points: one text for steps 1, 2 and 4-7, the point source (step 3 or 3') chosen by
+ * POINTS.  It is expanded in the kernels themselves and is not an inlined template like denoise_filter: behind a function
+ * boundary the same text compiles pt_reproject to another listing (1,298 changed lines of 4,190, tools/isa_diff.py), and this
+ * way it keeps the one its measurements were taken on, line for line. */
+#define PT_REPROJECT_BODY(POINTS, prev_points)                                                                                                   \
+{                                                                                                                                                  \
+  const uint32_t bx = ((uint32_t)R.width + 15u) / 16u;                                                                                             \
+  const int32_t x = (int32_t)((blockIdx.x % bx) * 16u + (threadIdx.x & 15u));                                                                      \
+  const int32_t y = (int32_t)((blockIdx.x / bx) * 16u + (threadIdx.x >> 4));                                                                       \
+  if (x >= R.width || y >= R.height)                                                                                                               \
+    return; /* no barrier follows */                                                                                                               \
+  const size_t p = (size_t)y * (size_t)R.width + (size_t)x;                                                                                        \
+  const float cx = R.rgb[3 * p + 0], cy = R.rgb[3 * p + 1], cz = R.rgb[3 * p + 2];                                                                 \
+  const float qnan = __uint_as_float(0x7FC00000u);                                                                                                 \
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);                                                                                   \
+  /* 1. a colour that is not finite passes through and starts no history */                                                                        \
+  if (!(isfinite(cx) && isfinite(cy) && isfinite(cz)))                                                                                             \
+  {                                                                                                                                                \
+    reproject_store(R, p, cx, cy, cz, 0.f, qnan, qnan);                                                                                            \
+    return;                                                                                                                                        \
+  }                                                                                                                                                \
+  /* 2. nothing to look up: the first frame, a background pixel, a depth that is no distance */                                                    \
+  const double zp = (double)R.depth[p];                                                                                                            \
+  if (!R.hist_rgb || R.hits[p] == 0u || !(zp > 0 && zp < inf))                                                                                     \
+  {                                                                                                                                                \
+    reproject_store(R, p, cx, cy, cz, 1.f, qnan, qnan);                                                                                            \
+    return;                                                                                                                                        \
+  }                                                                                                                                                \
+  /* 3. the first-hit point: get_camera_ray (raytracer.c:375-384) through the pixel's centre, then point_at; 3'. (POINTS) the                      \
+   * point the caller gives, where this surface point was in the history's frame -- not finite: nothing to look up */                              \
+  const double w1 = (double)R.width - 1.0, h1 = (double)R.height - 1.0;                                                                            \
+  V3 P;                                                                                                                                            \
+  if constexpr (POINTS)                                                                                                                            \
+  {                                                                                                                                                \
+    P = ld3(prev_points + 3 * p);                                                                                                                  \
+    if (!(isfinite(P.x) && isfinite(P.y) && isfinite(P.z)))                                                                                        \
+    {                                                                                                                                              \
+      reproject_store(R, p, cx, cy, cz, 1.f, qnan, qnan);                                                                                          \
+      return;                                                                                                                                      \
+    }                                                                                                                                              \
+  }                                                                                                                                                \
+  else                                                                                                                                             \
+  {                                                                                                                                                \
+    const double u = ((double)x + 0.5) / w1, v = ((double)y + 0.5) / h1;                                                                           \
+    const V3 pos = ld3(R.cam.pos);                                                                                                                 \
+    const V3 E = v_add(ld3(R.cam.llc), v_add(v_scale(ld3(R.cam.horizontal), u), v_scale(ld3(R.cam.vertical), v)));                                 \
+    const V3 d = v_normalize(v_sub(pos, E));                                                                                                       \
+    P = v_add(pos, v_scale(d, zp));                                                                                                                \
+  }                                                                                                                                                \
+  /* 4. where the history's camera saw it: H' us + V' vs + D / s = R', solved for (us, vs, 1 / s) by Cramer's rule */                              \
+  const V3 Hh = ld3(R.hist_cam.horizontal), Vh = ld3(R.hist_cam.vertical), posh = ld3(R.hist_cam.pos);                                             \
+  const V3 D = v_sub(P, posh);                                                                                                                     \
+  const V3 Rr = v_sub(posh, ld3(R.hist_cam.llc));                                                                                                  \
+  const V3 N = v_cross(Vh, D);                                                                                                                     \
+  const double det = v_dot(Hh, N);                                                                                                                 \
+  const double us = v_dot(Rr, N) / det;                                                                                                            \
+  const V3 M = v_cross(D, Hh);                                                                                                                     \
+  const double vs = v_dot(Rr, M) / det;                                                                                                            \
+  const double k = v_dot(Rr, v_cross(Hh, Vh));                                                                                                     \
+  const bool front = (k > 0 && det > 0) || (k < 0 && det < 0);                                                                                     \
+  const double fx = us * w1 - 0.5, fy = vs * h1 - 0.5;                                                                                             \
+  const bool ok = front && fx > -1.0 && fx < (double)R.width && fy > -1.0 && fy < (double)R.height;                                                \
+  if (!ok)                                                                                                                                         \
+  {                                                                                                                                                \
+    reproject_store(R, p, cx, cy, cz, 1.f, qnan, qnan);                                                                                            \
+    return;                                                                                                                                        \
+  }                                                                                                                                                \
+  const float mx = (float)(fx - (double)x), my = (float)(fy - (double)y);                                                                          \
+  /* 5. the four taps (ok: floor(fx) is in [-1, w - 1], floor(fy) in [-1, h - 1] -- the conversions are in range) */                               \
+  const double x0d = floor(fx), y0d = floor(fy);                                                                                                   \
+  const double a = fx - x0d, b = fy - y0d;                                                                                                         \
+  const int32_t x0 = (int32_t)x0d, y0 = (int32_t)y0d;                                                                                              \
+  const double zexp = sqrt(v_dot(D, D));                                                                                                           \
+  const double ztol = R.depth_tol * zexp;                                                                                                          \
+  const double npx = R.normal[3 * p + 0], npy = R.normal[3 * p + 1], npz = R.normal[3 * p + 2];                                                    \
+  const uint32_t op = R.object[p];                                                                                                                 \
+  double W = 0, Ax = 0, Ay = 0, Az = 0, S = 0;                                                                                                     \
+_Pragma("unroll")                                                                                                                                  \
+  for (int j = 0; j < 2; j++)                                                                                                                      \
+  {                                                                                                                                                \
+_Pragma("unroll")                                                                                                                                  \
+    for (int i = 0; i < 2; i++)                                                                                                                    \
+    {                                                                                                                                              \
+      const int32_t qx = x0 + i, qy = y0 + j;                                                                                                      \
+      const bool inside = qx >= 0 && qx < R.width && qy >= 0 && qy < R.height;                                                                     \
+      const size_t q = inside ? (size_t)qy * (size_t)R.width + (size_t)qx : p;                                                                     \
+      const double wt = (i ? a : 1.0 - a) * (j ? b : 1.0 - b);                                                                                     \
+      const float hx = R.hist_rgb[3 * q + 0], hy = R.hist_rgb[3 * q + 1], hz = R.hist_rgb[3 * q + 2];                                              \
+      const double lq = (double)R.hist_len[q], zq = (double)R.hist_depth[q];                                                                       \
+      const double g = (npx * (double)R.hist_normal[3 * q + 0] + npy * (double)R.hist_normal[3 * q + 1]) + npz * (double)R.hist_normal[3 * q + 2]; \
+      const bool take = inside && isfinite(hx) && isfinite(hy) && isfinite(hz) && lq >= 1.0 && lq < inf && R.hist_hits[q] > 0u &&                  \
+                        R.hist_object[q] == op && g >= R.normal_min && __builtin_fabs(zq - zexp) <= ztol;                                          \
+      W = take ? W + wt : W;                                                                                                                       \
+      Ax = take ? Ax + wt * (double)hx : Ax;                                                                                                       \
+      Ay = take ? Ay + wt * (double)hy : Ay;                                                                                                       \
+      Az = take ? Az + wt * (double)hz : Az;                                                                                                       \
+      S = take ? S + wt * lq : S;                                                                                                                  \
+    }                                                                                                                                              \
+  }                                                                                                                                                \
+  /* 6. the blend: a running mean of up to max_history frames */                                                                                   \
+  if (!(W > 0))                                                                                                                                    \
+  {                                                                                                                                                \
+    reproject_store(R, p, cx, cy, cz, 1.f, mx, my);                                                                                                \
+    return;                                                                                                                                        \
+  }                                                                                                                                                \
+  const float hcx = (float)(Ax / W), hcy = (float)(Ay / W), hcz = (float)(Az / W);                                                                 \
+  double Nn = S / W + 1.0;                                                                                                                         \
+  if (Nn > R.max_history)                                                                                                                          \
+    Nn = R.max_history;                                                                                                                            \
+  const double al = 1.0 / Nn;                                                                                                                      \
+  const float ox = (float)((double)hcx + ((double)cx - (double)hcx) * al);                                                                         \
+  const float oy = (float)((double)hcy + ((double)cy - (double)hcy) * al);                                                                         \
+  const float oz = (float)((double)hcz + ((double)cz - (double)hcz) * al);                                                                         \
+  reproject_store(R, p, ox, oy, oz, (float)Nn, mx, my);                                                                                            \
+}
+
+extern "C" __global__ __launch_bounds__(256) void pt_reproject(const PtReproject R) PT_REPROJECT_BODY(false, (const double *)nullptr)
+/* rt_hip_reproject_points: step 3 replaced by the caller's previous points (3 doubles per pixel); the frame's camera is not read */
+extern "C" __global__ __launch_bounds__(256) void pt_reproject_points(const PtReproject R, const double *prev_points) PT_REPROJECT_BODY(true, prev_points)
+#undef PT_REPROJECT_BODY
+
+/* ---- where each hit point was before a vertex update (rt_hip_prev_points) ----------------------------------------------------
+ * rt_hip.h states the arithmetic; this is it in fp64 (-ffp-contract=off).  A lane is an entry, 256 lanes a workgroup, no LDS.  The
+ * status, prim, bary and point loads are coalesced; the triangle's nine doubles are the one gather.  A lane reads its own point
+ * before it writes, so out may be the hits' point array. */
+extern "C" __global__ __launch_bounds__(256) void pt_prev_points(const PtPrevPoints A)
 {
-  const uint32_t bx = ((uint32_t)R.width + 15u) / 16u;
-  const int32_t x = (int32_t)((blockIdx.x % bx) * 16u + (threadIdx.x & 15u));
-  const int32_t y = (int32_t)((blockIdx.x / bx) * 16u + (threadIdx.x >> 4));
-  if (x >= R.width || y >= R.height)
-    return; /* no barrier follows */
-  const size_t p = (size_t)y * (size_t)R.width + (size_t)x;
-  const float cx = R.rgb[3 * p + 0], cy = R.rgb[3 * p + 1], cz = R.rgb[3 * p + 2];
-  const float qnan = __uint_as_float(0x7FC00000u);
-  const double inf = __longlong_as_double(0x7FF0000000000000ll);
-  /* 1. a colour that is not finite passes through and starts no history */
-  if (!(isfinite(cx) && isfinite(cy) && isfinite(cz)))
-  {
-    reproject_store(R, p, cx, cy, cz, 0.f, qnan, qnan);
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= A.n)
     return;
-  }
-  /* 2. nothing to look up: the first frame, a background pixel, a depth that is no distance */
-  const double zp = (double)R.depth[p];
-  if (!R.hist_rgb || R.hits[p] == 0u || !(zp > 0 && zp < inf))
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+  double ox = qnan, oy = qnan, oz = qnan;
+  if (A.status[i] == 1u)
   {
-    reproject_store(R, p, cx, cy, cz, 1.f, qnan, qnan);
-    return;
-  }
-  /* 3. the first-hit point: get_camera_ray (raytracer.c:375-384) through the pixel's centre, then point_at */
-  const double w1 = (double)R.width - 1.0, h1 = (double)R.height - 1.0;
-  const double u = ((double)x + 0.5) / w1, v = ((double)y + 0.5) / h1;
-  const V3 pos = ld3(R.cam.pos);
-  const V3 E = v_add(ld3(R.cam.llc), v_add(v_scale(ld3(R.cam.horizontal), u), v_scale(ld3(R.cam.vertical), v)));
-  const V3 d = v_normalize(v_sub(pos, E));
-  const V3 P = v_add(pos, v_scale(d, zp));
-  /* 4. where the history's camera saw it: H' us + V' vs + D / s = R', solved for (us, vs, 1 / s) by Cramer's rule */
-  const V3 Hh = ld3(R.hist_cam.horizontal), Vh = ld3(R.hist_cam.vertical), posh = ld3(R.hist_cam.pos);
-  const V3 D = v_sub(P, posh);
-  const V3 Rr = v_sub(posh, ld3(R.hist_cam.llc));
-  const V3 N = v_cross(Vh, D);
-  const double det = v_dot(Hh, N);
-  const double us = v_dot(Rr, N) / det;
-  const V3 M = v_cross(D, Hh);
-  const double vs = v_dot(Rr, M) / det;
-  const double k = v_dot(Rr, v_cross(Hh, Vh));
-  const bool front = (k > 0 && det > 0) || (k < 0 && det < 0);
-  const double fx = us * w1 - 0.5, fy = vs * h1 - 0.5;
-  const bool ok = front && fx > -1.0 && fx < (double)R.width && fy > -1.0 && fy < (double)R.height;
-  if (!ok)
-  {
-    reproject_store(R, p, cx, cy, cz, 1.f, qnan, qnan);
-    return;
-  }
-  const float mx = (float)(fx - (double)x), my = (float)(fy - (double)y);
-  /* 5. the four taps (ok: floor(fx) is in [-1, w - 1], floor(fy) in [-1, h - 1] -- the conversions are in range) */
-  const double x0d = floor(fx), y0d = floor(fy);
-  const double a = fx - x0d, b = fy - y0d;
-  const int32_t x0 = (int32_t)x0d, y0 = (int32_t)y0d;
-  const double zexp = sqrt(v_dot(D, D));
-  const double ztol = R.depth_tol * zexp;
-  const double npx = R.normal[3 * p + 0], npy = R.normal[3 * p + 1], npz = R.normal[3 * p + 2];
-  const uint32_t op = R.object[p];
-  double W = 0, Ax = 0, Ay = 0, Az = 0, S = 0;
-#pragma unroll
-  for (int j = 0; j < 2; j++)
-  {
-#pragma unroll
-    for (int i = 0; i < 2; i++)
+    const uint32_t prim = A.prim[i];
+    if (prim == 0xFFFFFFFFu)
+    { /* a sphere does not move: the point's own words (no arithmetic touches them) */
+      ox = A.point[3 * i + 0];
+      oy = A.point[3 * i + 1];
+      oz = A.point[3 * i + 2];
+    }
+    else if ((uint64_t)prim < A.n_triangles)
     {
-      const int32_t qx = x0 + i, qy = y0 + j;
-      const bool inside = qx >= 0 && qx < R.width && qy >= 0 && qy < R.height;
-      const size_t q = inside ? (size_t)qy * (size_t)R.width + (size_t)qx : p;
-      const double wt = (i ? a : 1.0 - a) * (j ? b : 1.0 - b);
-      const float hx = R.hist_rgb[3 * q + 0], hy = R.hist_rgb[3 * q + 1], hz = R.hist_rgb[3 * q + 2];
-      const double lq = (double)R.hist_len[q], zq = (double)R.hist_depth[q];
-      const double g = (npx * (double)R.hist_normal[3 * q + 0] + npy * (double)R.hist_normal[3 * q + 1]) + npz * (double)R.hist_normal[3 * q + 2];
-      const bool take = inside && isfinite(hx) && isfinite(hy) && isfinite(hz) && lq >= 1.0 && lq < inf && R.hist_hits[q] > 0u &&
-                        R.hist_object[q] == op && g >= R.normal_min && __builtin_fabs(zq - zexp) <= ztol;
-      W = take ? W + wt : W;
-      Ax = take ? Ax + wt * (double)hx : Ax;
-      Ay = take ? Ay + wt * (double)hy : Ay;
-      Az = take ? Az + wt * (double)hz : Az;
-      S = take ? S + wt * lq : S;
+      const double u = A.bary[2 * i + 0], v = A.bary[2 * i + 1];
+      const double w0 = (1.0 - u) - v;
+      const double *t = A.positions + 9 * (size_t)prim;
+      ox = (t[0] * w0 + t[3] * u) + t[6] * v;
+      oy = (t[1] * w0 + t[4] * u) + t[7] * v;
+      oz = (t[2] * w0 + t[5] * u) + t[8] * v;
     }
   }
-  /* 6. the blend: a running mean of up to max_history frames */
-  if (!(W > 0))
-  {
-    reproject_store(R, p, cx, cy, cz, 1.f, mx, my);
-    return;
-  }
-  const float hcx = (float)(Ax / W), hcy = (float)(Ay / W), hcz = (float)(Az / W);
-  double Nn = S / W + 1.0;
-  if (Nn > R.max_history)
-    Nn = R.max_history;
-  const double al = 1.0 / Nn;
-  const float ox = (float)((double)hcx + ((double)cx - (double)hcx) * al);
-  const float oy = (float)((double)hcy + ((double)cy - (double)hcy) * al);
-  const float oz = (float)((double)hcz + ((double)cz - (double)hcz) * al);
-  reproject_store(R, p, ox, oy, oz, (float)Nn, mx, my);
+  A.out[3 * i + 0] = ox;
+  A.out[3 * i + 1] = oy;
+  A.out[3 * i + 2] = oz;
 }
 
 /* ---- guided upsampling (rt_hip_upsample): a full-size frame from a low-resolution render -----------------------------------
@@ -2501,6 +2559,21 @@ hipError_t pt_launch_reproject(const PtReproject &args, hipStream_t stream)
 {
   const uint32_t blocks_2d = (((uint32_t)args.width + 15u) / 16u) * (((uint32_t)args.height + 15u) / 16u);
   hipLaunchKernelGGL(pt_reproject, dim3(blocks_2d), dim3(256), 0, stream, args);
+  return hipGetLastError();
+}
+
+hipError_t pt_launch_reproject_points(const PtReproject &args, const double *prev_points, hipStream_t stream)
+{
+  const uint32_t blocks_2d = (((uint32_t)args.width + 15u) / 16u) * (((uint32_t)args.height + 15u) / 16u);
+  hipLaunchKernelGGL(pt_reproject_points, dim3(blocks_2d), dim3(256), 0, stream, args, prev_points);
+  return hipGetLastError();
+}
+
+/* ---- the previous points' launch (rt_hip_prev_points): n in [1, 2^32) ---------------------------------------------------------- */
+hipError_t pt_launch_prev_points(const PtPrevPoints &args, hipStream_t stream)
+{
+  const uint32_t blocks = (uint32_t)((args.n + 255u) / 256u);
+  hipLaunchKernelGGL(pt_prev_points, dim3(blocks), dim3(256), 0, stream, args);
   return hipGetLastError();
 }
 

@@ -2431,8 +2431,8 @@ void camera_of(const RtHipCamera *c, PtCamera &out)
 /* the launch of a checked call, on the current device */
 int reproject_launch(const float *rgb, const RtHipAov *aov, const RtHipCamera *camera, const float *hist_rgb, const float *hist_len,
                      const RtHipAov *hist_aov, const RtHipCamera *hist_camera, int32_t width, int32_t height,
-                     const RtHipReprojectParams *p, float *out_rgb, uint8_t *out_rgb8, float *out_len, float *out_motion,
-                     hipStream_t stream)
+                     const RtHipReprojectParams *p, const double *prev_points, float *out_rgb, uint8_t *out_rgb8, float *out_len,
+                     float *out_motion, hipStream_t stream)
 {
   PtReproject R = {};
   R.rgb = rgb;
@@ -2460,19 +2460,33 @@ int reproject_launch(const float *rgb, const RtHipAov *aov, const RtHipCamera *c
   R.max_history = p->max_history;
   R.depth_tol = p->depth_tol;
   R.normal_min = p->normal_min;
-  const hipError_t e = pt_launch_reproject(R, stream);
+  const hipError_t e = prev_points ? pt_launch_reproject_points(R, prev_points, stream) : pt_launch_reproject(R, stream);
   if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_reproject launch: %s", hipGetErrorString(e));
+    return fail(RT_HIP_ERUNTIME, "%s launch: %s", prev_points ? "pt_reproject_points" : "pt_reproject", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+/* rt_hip_reproject_points' own rule, after check_reproject's: the previous points (3 doubles per pixel) overlap no output */
+int check_reproject_points(const double *prev_points, int32_t width, int32_t height, const float *out_rgb, const uint8_t *out_rgb8,
+                           const float *out_len, const float *out_motion)
+{
+  const size_t n = (size_t)width * (size_t)height;
+  const std::pair<const void *, size_t> outs[4] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_len, 4u * n}, {out_motion, 8u * n}};
+  for (const auto &o : outs)
+    if (ranges_overlap(o.first, o.second, prev_points, 24u * n))
+      return fail(RT_HIP_EINVAL, "an output overlaps the previous points");
   return RT_HIP_OK;
 }
 
 int reproject_image_impl(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
                          const float *h_hist_len, const RtHipAov *h_hist_aov, const RtHipCamera *hist_camera, int32_t width,
-                         int32_t height, const RtHipReprojectParams *params, int device, float *h_out_rgb, uint8_t *h_out_rgb8,
-                         float *h_out_len, float *h_out_motion)
+                         int32_t height, const RtHipReprojectParams *params, const double *h_prev_points, int device, float *h_out_rgb,
+                         uint8_t *h_out_rgb8, float *h_out_len, float *h_out_motion)
 {
   int rc = check_reproject(h_rgb, h_aov, camera, h_hist_rgb, h_hist_len, h_hist_aov, hist_camera, width, height, params, h_out_rgb,
                            h_out_rgb8, h_out_len, h_out_motion);
+  if (!rc && h_prev_points)
+    rc = check_reproject_points(h_prev_points, width, height, h_out_rgb, h_out_rgb8, h_out_len, h_out_motion);
   if (rc)
     return rc;
   int phys = -1;
@@ -2502,6 +2516,7 @@ int reproject_image_impl(const float *h_rgb, const RtHipAov *h_aov, const RtHipC
   }
   const int motion = A.part(8u * n, nullptr, h_out_motion, h_out_motion != nullptr);
   const int rgb8 = A.part(3u * n, nullptr, h_out_rgb8, h_out_rgb8 != nullptr);
+  const int points = A.part(24u * n, h_prev_points, nullptr, h_prev_points != nullptr);
   rc = A.stage();
   if (rc)
     return rc;
@@ -2509,8 +2524,80 @@ int reproject_image_impl(const float *h_rgb, const RtHipAov *h_aov, const RtHipC
   for (int f = 0; f < 2; f++)
     d_aov[f] = {nullptr, A.at<float>(normal[f]), A.at<float>(depth[f]), A.at<uint32_t>(object[f]), A.at<uint32_t>(hits[f])};
   rc = reproject_launch(A.at<float>(rgb[0]), &d_aov[0], camera, A.at<float>(rgb[1]), A.at<float>(len[1]), hist ? &d_aov[1] : nullptr,
-                        hist_camera, width, height, params, A.at<float>(rgb[0]), A.at<uint8_t>(rgb8), A.at<float>(len[0]),
-                        A.at<float>(motion), nullptr);
+                        hist_camera, width, height, params, A.at<double>(points), A.at<float>(rgb[0]), A.at<uint8_t>(rgb8),
+                        A.at<float>(len[0]), A.at<float>(motion), nullptr);
+  return rc ? rc : A.download();
+}
+
+/* ---- previous points (rt_hip.h, rt_hip_prev_points*) ---------------------------------------------------------------------------
+ * One launch of pt_prev_points (pt_kernel.hip), no workspace.  The arguments that need no device are checked first. */
+int check_prev_points(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, const double *points)
+{
+  if (n >= (1ull << 32))
+    return fail(RT_HIP_EINVAL, "n must be below 2^32");
+  if (n_triangles > SIZE_MAX / 72u)
+    return fail(RT_HIP_EINVAL, "n_triangles is out of range");
+  if (!hits || !hits->status || !hits->prim || !hits->bary || !hits->point)
+    return fail(RT_HIP_EINVAL, "the hits' status, prim, bary and point are required");
+  if (n_triangles && !positions)
+    return fail(RT_HIP_EINVAL, "the previous positions are required (9 doubles per triangle)");
+  if (!points)
+    return fail(RT_HIP_EINVAL, "the output points are required");
+  /* a lane writes its entry while other lanes still read: the output overlaps no input, but for out == point, where a lane reads
+   * its own point before it writes it */
+  const std::pair<const void *, size_t> in[5] = {{hits->status, 4u * n}, {hits->prim, 4u * n}, {hits->bary, 16u * n},
+                                                 {hits->point, 24u * n}, {n_triangles ? positions : nullptr, 72u * n_triangles}};
+  for (int k = 0; k < 5; k++)
+    if (!(k == 3 && points == hits->point) && ranges_overlap(points, 24u * n, in[k].first, in[k].second))
+      return fail(RT_HIP_EINVAL, "the output overlaps an input (only d_points == d_hits->point is allowed)");
+  return RT_HIP_OK;
+}
+
+/* the launch of a checked call, on the current device */
+int prev_points_launch(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, double *points, hipStream_t stream)
+{
+  if (n == 0)
+    return RT_HIP_OK;
+  PtPrevPoints A = {};
+  A.status = hits->status;
+  A.prim = hits->prim;
+  A.bary = hits->bary;
+  A.point = hits->point;
+  A.positions = positions;
+  A.out = points;
+  A.n = n;
+  A.n_triangles = n_triangles;
+  const hipError_t e = pt_launch_prev_points(A, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "pt_prev_points launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int prev_points_host_impl(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles, int device, double *h_points)
+{
+  int rc = check_prev_points(h_hits, n, h_positions, n_triangles, h_points);
+  if (rc)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  if (n == 0)
+    return RT_HIP_OK;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  /* the point part is input and output: the kernel runs in place on it */
+  StageArena A;
+  const int status = A.part(4u * n, h_hits->status);
+  const int prim = A.part(4u * n, h_hits->prim);
+  const int bary = A.part(16u * n, h_hits->bary);
+  const int point = A.part(24u * n, h_hits->point, h_points);
+  const int positions = A.part(72u * n_triangles, h_positions, nullptr, n_triangles != 0);
+  rc = A.stage();
+  if (rc)
+    return rc;
+  const RtHipHits d = {A.at<uint32_t>(status), nullptr, nullptr, A.at<uint32_t>(prim), A.at<double>(point), nullptr, A.at<double>(bary), nullptr};
+  rc = prev_points_launch(&d, n, A.at<double>(positions), n_triangles, A.at<double>(point), nullptr);
   return rc ? rc : A.download();
 }
 
@@ -4370,8 +4457,19 @@ int rt_hip_reproject(const float *d_rgb, const RtHipAov *d_aov, const RtHipCamer
                      const RtHipReprojectParams *params, float *d_out_rgb, uint8_t *d_out_rgb8, float *d_out_len, float *d_out_motion,
                      void *stream)
 {
+  return rt_hip_reproject_points(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, nullptr,
+                                 d_out_rgb, d_out_rgb8, d_out_len, d_out_motion, stream);
+}
+
+int rt_hip_reproject_points(const float *d_rgb, const RtHipAov *d_aov, const RtHipCamera *camera, const float *d_hist_rgb,
+                            const float *d_hist_len, const RtHipAov *d_hist_aov, const RtHipCamera *hist_camera, int32_t width,
+                            int32_t height, const RtHipReprojectParams *params, const double *d_prev_points, float *d_out_rgb,
+                            uint8_t *d_out_rgb8, float *d_out_len, float *d_out_motion, void *stream)
+{
   int rc = check_reproject(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, d_out_rgb,
                            d_out_rgb8, d_out_len, d_out_motion);
+  if (!rc && d_prev_points)
+    rc = check_reproject_points(d_prev_points, width, height, d_out_rgb, d_out_rgb8, d_out_len, d_out_motion);
   if (rc)
     return rc;
   int device = -1;
@@ -4380,8 +4478,8 @@ int rt_hip_reproject(const float *d_rgb, const RtHipAov *d_aov, const RtHipCamer
     return rc;
   DeviceScope scope(device);
   HIP_TRY(scope.status);
-  return reproject_launch(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, d_out_rgb,
-                          d_out_rgb8, d_out_len, d_out_motion, static_cast<hipStream_t>(stream));
+  return reproject_launch(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, d_prev_points,
+                          d_out_rgb, d_out_rgb8, d_out_len, d_out_motion, static_cast<hipStream_t>(stream));
 }
 
 int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
@@ -4390,9 +4488,39 @@ int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHi
                            float *h_out_len, float *h_out_motion)
 {
   return guarded("rt_hip_reproject_image", [&] {
-    return reproject_image_impl(h_rgb, h_aov, camera, h_hist_rgb, h_hist_len, h_hist_aov, hist_camera, width, height, params, device,
-                                h_out_rgb, h_out_rgb8, h_out_len, h_out_motion);
+    return reproject_image_impl(h_rgb, h_aov, camera, h_hist_rgb, h_hist_len, h_hist_aov, hist_camera, width, height, params, nullptr,
+                                device, h_out_rgb, h_out_rgb8, h_out_len, h_out_motion);
   });
+}
+
+int rt_hip_reproject_points_image(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
+                                  const float *h_hist_len, const RtHipAov *h_hist_aov, const RtHipCamera *hist_camera, int32_t width,
+                                  int32_t height, const RtHipReprojectParams *params, const double *h_prev_points, int device,
+                                  float *h_out_rgb, uint8_t *h_out_rgb8, float *h_out_len, float *h_out_motion)
+{
+  return guarded("rt_hip_reproject_points_image", [&] {
+    return reproject_image_impl(h_rgb, h_aov, camera, h_hist_rgb, h_hist_len, h_hist_aov, hist_camera, width, height, params,
+                                h_prev_points, device, h_out_rgb, h_out_rgb8, h_out_len, h_out_motion);
+  });
+}
+
+int rt_hip_prev_points(const RtHipHits *d_hits, uint64_t n, const double *d_positions, size_t n_triangles, double *d_points, void *stream)
+{
+  int rc = check_prev_points(d_hits, n, d_positions, n_triangles, d_points);
+  if (rc || n == 0)
+    return rc;
+  int device = -1;
+  rc = device_of(d_points, "d_points", &device);
+  if (rc)
+    return rc;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  return prev_points_launch(d_hits, n, d_positions, n_triangles, d_points, static_cast<hipStream_t>(stream));
+}
+
+int rt_hip_prev_points_host(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles, int device, double *h_points)
+{
+  return guarded("rt_hip_prev_points_host", [&] { return prev_points_host_impl(h_hits, n, h_positions, n_triangles, device, h_points); });
 }
 
 /* k: the denoiser's; sigma_depth: the reprojection's depth tolerance (DESIGN, "`pt_upsample`") */

@@ -285,6 +285,16 @@ SHIM_SYMBOLS = {
     "rt_hip_reproject_image": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(RtHipAov),
                                          C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(RtHipReprojectParams), C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_prev_points": (C.c_int, [C.POINTER(RtHipHits), C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rt_hip_prev_points_host": (C.c_int, [C.POINTER(RtHipHits), C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    # rt_hip_reproject's arguments with the previous points after params
+    "rt_hip_reproject_points": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(RtHipAov),
+                                          C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(RtHipReprojectParams), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_reproject_points_image": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.POINTER(Camera), C.c_void_p, C.c_void_p,
+                                                C.POINTER(RtHipAov), C.POINTER(Camera), C.c_int32, C.c_int32,
+                                                C.POINTER(RtHipReprojectParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
     "rt_hip_upsample_defaults": (None, [C.POINTER(RtHipUpsampleParams)]),
     "rt_hip_upsample": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipAov), C.c_int32, C.c_int32,
                                   C.POINTER(RtHipUpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

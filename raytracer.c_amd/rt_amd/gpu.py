@@ -116,9 +116,10 @@ class GpuScene:
         corner, xyz, in scene triangle order -- as a float64 torch tensor on the scene's device (taken where it lies, no host
         copy) or a numpy array (staged by the shim).  Synchronous.  The records are recomputed and the hierarchy REFITTED on the
         device: frames, bytes and counters equal a freshly created scene's; bvh_info()["tree_cost"] reports the refitted tree's
-        cost, and a caller recreates the scene when that has drifted too far from a fresh tree's.  Temporal and Preview assume a
-        static scene: reset them after an update.  Open accumulations refuse the update (close them first).  self.scene keeps
-        the vertices the scene was created from."""
+        cost, and a caller recreates the scene when that has drifted too far from a fresh tree's.  A Temporal keeps its history
+        across an update when its next frame() is given the positions from before it (prev_positions); without them, and for a
+        Preview, which assumes a static scene, reset after an update.  Open accumulations refuse the update (close them first).
+        self.scene keeps the vertices the scene was created from."""
         n = self.scene.n_triangles
         if isinstance(positions, torch.Tensor):
             if positions.dtype != torch.float64 or tuple(positions.shape) != (n, 3, 3):
@@ -269,7 +270,7 @@ class GpuScene:
         """the ray-query form this scene's query_rays / query_uv launches take"""
         return self.shim.rt_hip_query_kernel_name(self.handle).decode()
 
-    def _query(self, rays, per_ray, t_max, params, want):
+    def _query(self, rays, per_ray, t_max, params, want, into=None):
         dev = torch.device("cuda", self.device)
         rays = torch.as_tensor(rays, dtype=torch.float64, device=dev).reshape(-1, per_ray).contiguous()
         if rays.data_ptr() % 16:
@@ -282,7 +283,13 @@ class GpuScene:
         out, hits = {}, abi.RtHipHits()
         for f in want:
             dtype, k = abi.HIT_SHAPES[f]
-            out[f] = torch.empty((n, k) if k > 1 else (n,), dtype=torch.float64 if dtype == "float64" else torch.int32, device=dev)
+            shape, tdtype = (n, k) if k > 1 else (n,), torch.float64 if dtype == "float64" else torch.int32
+            if into is not None and f in into:
+                out[f] = into[f]
+                if out[f].device != dev or out[f].dtype != tdtype or tuple(out[f].shape) != shape or not out[f].is_contiguous():
+                    raise ValueError(f"query: out[{f!r}] must be a contiguous {tdtype} tensor of shape {shape} on the scene's device")
+            else:
+                out[f] = torch.empty(shape, dtype=tdtype, device=dev)
             setattr(hits, f, out[f].data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "wanted")
         stream = torch.cuda.current_stream(dev).cuda_stream
         self._query_inputs = (rays, t_max)   # keep alive until the stream has used them
@@ -299,14 +306,15 @@ class GpuScene:
         origin the rays start (a speed hint that changes no output bit; None: the default)."""
         return self._query(rays, 6, t_max, abi.query_params(abi.RAYS_GIVEN, normalize, None, origin_radius), want)
 
-    def query_uv(self, uv, camera=None, t_max=None, normalize=False, origin_radius=None, want=abi.HIT_FIELDS):
+    def query_uv(self, uv, camera=None, t_max=None, normalize=False, origin_radius=None, want=abi.HIT_FIELDS, out=None):
         """... of the camera rays get_camera_ray(camera, u, v) for uv [n, 2] float64 (camera None: the scene's own; origin_radius
-        None: the camera's distance from the world origin)"""
+        None: the camera's distance from the world origin; out: a dict of tensors to write wanted fields into, what is missing
+        is allocated)"""
         cam = camera if camera is not None else self.scene.camera
         if origin_radius is None:
             x, y, z = cam.position.tuple()
             origin_radius = (x * x + y * y + z * z) ** 0.5
-        return self._query(uv, 2, t_max, abi.query_params(abi.RAYS_CAMERA_UV, normalize, cam, origin_radius), want)
+        return self._query(uv, 2, t_max, abi.query_params(abi.RAYS_CAMERA_UV, normalize, cam, origin_radius), want, out)
 
     def pick(self, x, y):
         """What is under the centre of pixel (x, y) of the scene's own camera and size: u = (x + 0.5) / (w - 1), v = (y + 0.5) /
@@ -437,7 +445,7 @@ class GpuScene:
 
     def temporal(self, **params):
         """A Temporal: frames of this scene under a moving camera, each accumulated onto the reprojected history of the ones
-        before (rt_hip_reproject; params: abi.reproject_params' keywords)"""
+        before (rt_hip_reproject, and rt_hip_reproject_points across update_vertices; params: abi.reproject_params' keywords)"""
         return Temporal(self, **params)
 
     def preview(self, scale, **params):
@@ -739,13 +747,69 @@ def _reproject_aov(aov, n, dev, what):
     return a
 
 
-def reproject(rgb, aov, camera, hist=None, out=None, **params):
+def prev_points(hits, positions, out=None):
+    """rt_hip_prev_points on torch device tensors, asynchronous on torch's current stream: where each hit point of a query was
+    before an update_vertices.  hits: a dict as GpuScene.query_rays / query_uv return it, with status, prim, bary and point;
+    positions: float64 (n_triangles, 3, 3), the positions the scene had at the previous frame, in update_vertices' layout (None:
+    no triangles); out: float64 [n, 3] to write into (it may be hits["point"]; None: allocated) -> float64 [n, 3], NaN where there
+    is no surface to follow (a miss, an invalid ray, a prim outside the positions)"""
+    st = hits["status"]
+    dev, n = st.device, int(st.numel())
+    h = abi.RtHipHits()
+    for f in ("status", "prim", "bary", "point"):
+        dtype, k = abi.HIT_SHAPES[f]
+        t = hits[f]
+        if t.device != dev or not t.is_contiguous() or t.numel() != n * k or t.dtype != (torch.float64 if dtype == "float64" else torch.int32):
+            raise ValueError(f"prev_points(): hits[{f!r}] must be a contiguous tensor of {n} x {k} values as a query returns it")
+        setattr(h, f, t.data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "given")
+    n_tri, pos = 0, None
+    if positions is not None:
+        if positions.dtype != torch.float64 or positions.dim() != 3 or tuple(positions.shape[1:]) != (3, 3) or positions.device != dev:
+            raise ValueError("prev_points(): positions must be a float64 tensor of shape (n_triangles, 3, 3) on the hits' device")
+        pos = positions.contiguous()
+        n_tri = int(pos.shape[0])
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    elif out.device != dev or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 3 * n:
+        raise ValueError(f"prev_points(): out must be a contiguous float64 tensor of {n} x 3 values on the hits' device")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(abi.load_shim().rt_hip_prev_points(C.byref(h), n, C.c_void_p(pos.data_ptr()) if n_tri else None, n_tri,
+                                              C.c_void_p(out.data_ptr() if n else 1), C.c_void_p(stream)), "rt_hip_prev_points")
+    return out
+
+
+def prev_points_host(hits, positions, device=0):
+    """rt_hip_prev_points_host(): host arrays, its own device buffers on logical device `device`, synchronous.  hits: a dict of
+    numpy arrays with status, prim (uint32 [n]), bary (float64 [n, 2]) and point (float64 [n, 3]); positions: float64
+    (n_triangles, 3, 3) or None -> float64 [n, 3]"""
+    import numpy as np
+    arrs = {f: np.ascontiguousarray(hits[f], dtype=np.float64 if abi.HIT_SHAPES[f][0] == "float64" else np.uint32)
+            for f in ("status", "prim", "bary", "point")}
+    n = arrs["status"].size
+    h = abi.RtHipHits()
+    for f, a in arrs.items():
+        if a.size != n * abi.HIT_SHAPES[f][1]:
+            raise ValueError(f"prev_points_host(): hits[{f!r}] must hold {n} x {abi.HIT_SHAPES[f][1]} values")
+        setattr(h, f, a.ctypes.data if n else 1)
+    pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3, 3)
+    n_tri = 0 if pos is None else pos.shape[0]
+    out = np.zeros((n, 3), np.float64)
+    _check(abi.load_shim().rt_hip_prev_points_host(C.byref(h), n, pos.ctypes.data if n_tri else None, n_tri, device,
+                                                   out.ctypes.data if n else 1), "rt_hip_prev_points_host")
+    return out
+
+
+def reproject(rgb, aov, camera, hist=None, out=None, prev_points=None, **params):
     """rt_hip_reproject on torch device tensors, asynchronous on torch's current stream: rgb f32 [H,W,3] (row-major, contiguous),
     aov a dict of row-major buffers as GpuScene.untile_aov gives them (normal, depth, object, hits), camera the frame's abi.Camera.
     hist: None (the first frame) or a dict with rgb and len (an earlier call's results), aov and camera (that frame's).  out: a
     dict of tensors to write into (rgb f32 [H,W,3] -- it may be the input rgb --, len f32 [H,W], motion f32 [H,W,2], rgb8 u8
     [H,W,3]; what is missing is allocated; motion or rgb8 given as None: not wanted, not computed), none of them a history buffer
     or another buffer of the call.  params: abi.reproject_params' keywords.
+    prev_points (None: the scene is static between the two frames, rt_hip_reproject): float64 [H,W,3], where each pixel's
+    surface point was in the history's frame, as prev_points() gives it for the pixel-centre query -- the reprojection starts
+    from it instead of the depth along the frame's ray (rt_hip_reproject_points), and a pixel whose point is not finite starts
+    a new history.
     -> dict(rgb, len, and motion and rgb8 unless not wanted)"""
     dev = rgb.device
     shim = abi.load_shim()
@@ -776,11 +840,16 @@ def reproject(rgb, aov, camera, hist=None, out=None, **params):
         if t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != shape[0] * shape[1] * (shape[2] if len(shape) > 2 else 1):
             raise ValueError(f"reproject(): out[{f!r}] must be a contiguous {dtype} tensor of shape {shape} on the colour's device")
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(shim.rt_hip_reproject(C.c_void_p(rgb.data_ptr()), C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, width, height,
-                                 C.byref(p), C.c_void_p(out["rgb"].data_ptr()),
-                                 C.c_void_p(out["rgb8"].data_ptr()) if "rgb8" in out else None, C.c_void_p(out["len"].data_ptr()),
-                                 C.c_void_p(out["motion"].data_ptr()) if "motion" in out else None, C.c_void_p(stream)),
-           "rt_hip_reproject")
+    outs = (C.c_void_p(out["rgb"].data_ptr()), C.c_void_p(out["rgb8"].data_ptr()) if "rgb8" in out else None,
+            C.c_void_p(out["len"].data_ptr()), C.c_void_p(out["motion"].data_ptr()) if "motion" in out else None, C.c_void_p(stream))
+    if prev_points is None:
+        _check(shim.rt_hip_reproject(C.c_void_p(rgb.data_ptr()), C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, width, height,
+                                     C.byref(p), *outs), "rt_hip_reproject")
+        return out
+    if prev_points.device != dev or prev_points.dtype != torch.float64 or not prev_points.is_contiguous() or prev_points.numel() != 3 * n:
+        raise ValueError("reproject(): prev_points must be a contiguous float64 tensor of width * height * 3 values on the colour's device")
+    _check(shim.rt_hip_reproject_points(C.c_void_p(rgb.data_ptr()), C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, width, height,
+                                        C.byref(p), C.c_void_p(prev_points.data_ptr()), *outs), "rt_hip_reproject_points")
     return out
 
 
@@ -788,7 +857,8 @@ class Temporal:
     """Frames of one scene under a moving camera (GpuScene.temporal): every frame is rendered, its first-hit buffers of the same
     samples are rendered, and it is accumulated onto the history of the frames before it where the reprojection finds the same
     surface (rt_hip.h, rt_hip_reproject).  The history -- accumulated colour, length, the first-hit buffers and the camera -- is
-    double-buffered and allocated once; frame() runs on torch's current stream.  The scene must stay open and unchanged."""
+    double-buffered and allocated once; frame() runs on torch's current stream.  The scene must stay open; its triangles may
+    move between frames (GpuScene.update_vertices) when frame() is given the positions they had at the previous frame."""
 
     def __init__(self, gs, **params):
         self.gs = gs
@@ -809,6 +879,13 @@ class Temporal:
         self._tiles8 = torch.empty((self._total, abi.TILE_PIXELS, 3), dtype=torch.uint8, device=dev)
         self._motion = torch.zeros((h, w, 2), dtype=torch.float32, device=dev)
         self._rgb8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+        # frames across update_vertices (prev_positions): the pixel-centre grid of rt_hip_reproject's step 3, the query's hit
+        # buffers and the previous points
+        ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
+        self._uv = torch.stack([(xs + 0.5) / (float(w) - 1.0), (ys + 0.5) / (float(h) - 1.0)], dim=-1).reshape(-1, 2).contiguous().to(dev)
+        self._hits = dict(status=torch.zeros(w * h, dtype=torch.int32, device=dev), prim=torch.zeros(w * h, dtype=torch.int32, device=dev),
+                          bary=torch.zeros((w * h, 2), dtype=torch.float64, device=dev), point=torch.zeros((w * h, 3), dtype=torch.float64, device=dev))
+        self._points = torch.zeros((w * h, 3), dtype=torch.float64, device=dev)
         self._cur = 0          # the slot the next frame is written to
         self.frames = 0        # frames since the last reset: 0 = the next one has no history
 
@@ -819,7 +896,7 @@ class Temporal:
         """drop the history: the next frame starts from its own samples"""
         self.frames = 0
 
-    def frame(self, camera, seed, samples, max_depth=None, denoise=False, fill=None, **denoise_params):
+    def frame(self, camera, seed, samples, max_depth=None, denoise=False, fill=None, prev_positions=None, **denoise_params):
         """Render `samples` per pixel under `camera` (an abi.Camera), reproject and accumulate -> dict of device tensors, valid
         until the next frame(): rgb f32 [H,W,3] (the accumulated image), rgb8 u8 [H,W,3], len f32 [H,W], motion f32
         [H,W,2], aov (the frame's first-hit buffers), and with denoise: denoised / denoised8, rt_hip_denoise of the accumulated
@@ -828,7 +905,11 @@ class Temporal:
         0 <= len <= 1 -- disoccluded, or not to be used -- get S more samples of the render's own, from sample `samples` on
         (GpuScene.refine with prior = len, prior_scale = samples: a pixel of length 1 blends its `samples` samples with the S new
         ones, a pixel of length 0 is replaced), and their len becomes (len * samples + S) / samples, rounded as rt_hip_blend_pixels'
-        weight and then divided in float32; res["filled"] is how many (the call then waits for that one word)."""
+        weight and then divided in float32; res["filled"] is how many (the call then waits for that one word).
+        prev_positions (None: the scene has not moved since the previous frame()): the float64 (n_triangles, 3, 3) device tensor
+        of the positions the scene had at the previous frame(), after an update_vertices.  With a history, the pixel centres are
+        queried under `camera` (query_uv), each hit is taken back to those positions (prev_points) and the reprojection starts
+        from there (reproject(prev_points=...)): the history follows the moving surface."""
         gs, total = self.gs, self._total
         w, h = gs.scene.width, gs.scene.height
         cur, prev = self._slots[self._cur], self._slots[self._cur ^ 1]
@@ -844,8 +925,12 @@ class Temporal:
         stream = torch.cuda.current_stream(torch.device("cuda", gs.device)).cuda_stream
         _check(gs.shim.rt_hip_untile_aov(C.byref(src), w, h, 0, 1, total, C.byref(dst), C.c_void_p(stream)), "rt_hip_untile_aov")
         C.memmove(C.byref(cur["camera"]), C.byref(camera), C.sizeof(abi.Camera))
+        points = None
+        if prev_positions is not None and self.frames:
+            hits = gs.query_uv(self._uv, camera=camera, want=("status", "prim", "bary", "point"), out=self._hits)
+            points = prev_points(hits, prev_positions, out=self._points)
         res = reproject(cur["rgb"], cur["aov"], cur["camera"], hist=prev if self.frames else None,
-                        out=dict(rgb=cur["rgb"], len=cur["len"], motion=self._motion, rgb8=self._rgb8), **self.params)
+                        out=dict(rgb=cur["rgb"], len=cur["len"], motion=self._motion, rgb8=self._rgb8), prev_points=points, **self.params)
         res["aov"] = cur["aov"]
         if fill is not None:
             if int(fill) != fill or fill < 1:
@@ -867,10 +952,11 @@ class Temporal:
         return res
 
 
-def reproject_image_host(rgb, aov, camera, hist=None, device=0, **params):
+def reproject_image_host(rgb, aov, camera, hist=None, device=0, prev_points=None, **params):
     """rt_hip_reproject_image(): the C hosts' entry point (host arrays, its own device buffers on logical device `device`,
     synchronous).  rgb float32 [H,W,3], aov a dict of numpy arrays as GpuScene.aov_image gives them, hist None or a dict with rgb,
-    len, aov and camera -> dict of numpy arrays: rgb, rgb8, len, motion"""
+    len, aov and camera; prev_points: None, or float64 [H,W,3] (rt_hip_reproject_points_image) -> dict of numpy arrays: rgb,
+    rgb8, len, motion"""
     import numpy as np
     shim = abi.load_shim()
     p = abi.reproject_params(**params)
@@ -893,9 +979,16 @@ def reproject_image_host(rgb, aov, camera, hist=None, device=0, **params):
         h_rgb, h_len, h_aov, h_cam = hr.ctypes.data, hl.ctypes.data, C.byref(pack(hist["aov"])), C.byref(hist["camera"])
     out = dict(rgb=np.zeros((h, w, 3), np.float32), rgb8=np.zeros((h, w, 3), np.uint8), len=np.zeros((h, w), np.float32),
                motion=np.zeros((h, w, 2), np.float32))
-    _check(shim.rt_hip_reproject_image(rgb.ctypes.data, C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, w, h, C.byref(p), device,
-                                       out["rgb"].ctypes.data, out["rgb8"].ctypes.data, out["len"].ctypes.data, out["motion"].ctypes.data),
-           "rt_hip_reproject_image")
+    outs = (out["rgb"].ctypes.data, out["rgb8"].ctypes.data, out["len"].ctypes.data, out["motion"].ctypes.data)
+    if prev_points is None:
+        _check(shim.rt_hip_reproject_image(rgb.ctypes.data, C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, w, h, C.byref(p), device,
+                                           *outs), "rt_hip_reproject_image")
+        return out
+    pts = np.ascontiguousarray(prev_points, dtype=np.float64)
+    if pts.size != 3 * w * h:
+        raise ValueError("reproject_image_host(): prev_points must hold width * height * 3 values")
+    _check(shim.rt_hip_reproject_points_image(rgb.ctypes.data, C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, w, h, C.byref(p),
+                                              pts.ctypes.data, device, *outs), "rt_hip_reproject_points_image")
     return out
 
 
