@@ -1,7 +1,7 @@
 # Top-level build.  Everything is built IN-TREE so the binaries travel to the GPU box
 # with the source snapshot (they are git-ignored, not gpurun-ignored).
 #
-#   make            shim + its PT_DIAG twin + its development build + its PT_DIR_PARK=0 twin + host library + CLI + oracle checkers
+#   make            shim + its PT_DIAG twin + its development build + its PT_DIR_PARK=0 and PT_MFMA16=0 twins (the latter also as PT_DIAG) + host library + CLI + oracle checkers
 #   make shim       raytracer.c_amd/csrc/librt_hip.so        (hipcc, gfx950 only)
 #   make host       raytracer.c_amd/host/libraytracer_amd.so + raytracer (gcc, C99)
 #   make oracle     oracle/libpt_oracle.so (+ oracle/_ref/*.so when /root/reference exists)
@@ -29,7 +29,7 @@ CLI     := $(HOST)/raytracer
 HOST_SRC := $(HOST)/raytracer_amd.c $(HOST)/scenes.c $(HOST)/obj_load.c $(HOST)/png_out.c
 HOST_HDR := $(INC)/raytracer.h $(INC)/vector.h $(INC)/rt_hip.h $(INC)/rt_rng.h $(HOST)/scenes.h
 
-all: shim shim-diag shim-dev shim-park0 host oracle
+all: shim shim-diag shim-dev shim-park0 shim-mfma0 shim-diag-mfma0 host oracle
 
 # oracle/_ref/ref_main_dropin links against the host library: build that first
 oracle: host
@@ -63,6 +63,21 @@ $(CSRC)/variants/librt_hip_park0.so: $(KERNEL_SRC)
 	@mkdir -p $(CSRC)/variants
 	$(HIPCC) $(HIPFLAGS) -DPT_DIR_PARK=0 -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
 
+# the other arm of the matrix-pipe filter's A/B (-DPT_MFMA16=0: phase 1 of every sphere in the packed-fp32 loop).  Not the product:
+# tests/test_gpu_mfma16.py renders with it in a child process and asks for the shipped build's frames and counters bit for bit, and
+# tools/gpu_ab.py times it.  Built by `make all` so that it travels with the snapshot.
+shim-mfma0: $(CSRC)/variants/librt_hip_mfma0.so
+$(CSRC)/variants/librt_hip_mfma0.so: $(KERNEL_SRC)
+	@mkdir -p $(CSRC)/variants
+	$(HIPCC) $(HIPFLAGS) -DPT_MFMA16=0 -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+
+# the diagnostic build of that arm: tests/test_gpu_mfma16.py compares the two diagnostic builds' candidate counts (what the matrix
+# pipe keeps and the packed loop drops, per filter evaluation)
+shim-diag-mfma0: $(CSRC)/variants/librt_hip_diag_mfma0.so
+$(CSRC)/variants/librt_hip_diag_mfma0.so: $(KERNEL_SRC)
+	@mkdir -p $(CSRC)/variants
+	$(HIPCC) $(HIPFLAGS) -DPT_DIAG -DPT_MFMA16=0 -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+
 host: $(HOSTLIB) $(CLI)
 $(HOSTLIB): $(HOST_SRC) $(HOST_HDR) $(SHIM)
 	$(CC) $(CFLAGS) -shared -o $@ $(HOST_SRC) -L$(CSRC) -lrt_hip -Wl,-rpath,'$$ORIGIN/../csrc' -lz -lm
@@ -74,10 +89,10 @@ oracle:
 	$(MAKE) -C $(ROOT)oracle all
 
 clean:
-	rm -f $(SHIM) $(CSRC)/librt_hip_diag.so $(CSRC)/librt_hip_dev.so $(CSRC)/variants/librt_hip_park0.so $(HOSTLIB) $(CLI)
+	rm -f $(SHIM) $(CSRC)/librt_hip_diag.so $(CSRC)/librt_hip_dev.so $(CSRC)/variants/librt_hip_park0.so $(CSRC)/variants/librt_hip_mfma0.so $(CSRC)/variants/librt_hip_diag_mfma0.so $(HOSTLIB) $(CLI)
 	$(MAKE) -C $(ROOT)oracle clean
 
-.PHONY: all shim shim-diag shim-dev shim-park0 host oracle clean
+.PHONY: all shim shim-diag shim-dev shim-park0 shim-mfma0 shim-diag-mfma0 host oracle clean
 
 # development: alternative builds of the shim for A/B runs (tools/gpu_ab.py), e.g.
 #   make variant NAME=tri4 DEFS="-DPT_MIN_WAVES_TRI=4"   ->  raytracer.c_amd/csrc/variants/librt_hip_tri4.so

@@ -908,7 +908,13 @@ int rt_hip_selftest_math(int op, const double *h_a, const double *h_b, double *h
  * filter in small scenes; f = 1: compares from LDS; f = 2: compares by scalar loads) for ray i
  * against the 64 primitives of its block [64 (i/64), +64): bit j set = primitive 64 (i/64) + j
  * is kept.  The filter is built for ray origins within near_R (rays beyond keep everything),
- * as rt_hip_render_tiles builds it for a camera.  |centre|, |radius| <= 1e17. */
+ * as rt_hip_render_tiles builds it for a camera.  |centre|, |radius| <= 1e17.
+ * kind 2 (spheres as kind 0, n a multiple of 64; a build with -DPT_MFMA16=0 refuses it): the keep words of phase 1 on the fp16
+ * matrix pipe.  In each block of 64 cases the first 32 spheres are the matrix rows and the other 32 follow in the packed loop, as
+ * in a scene of more than 32 small spheres.  h_keep[3i + 0] = the packed sign-test form alone, h_keep[3i + 1] = the matrix pipe
+ * merged with it as the render kernels merge them, h_keep[3i + 2] = the device's exact test of ray i against the block's 64
+ * spheres (bit j = a hit).  h_hit[i] = 1 when the block's 32 rows fit the matrix form (0: it ran the packed loop instead).
+ * h_tuv[3i], h_tuv[3i + 1] = the matrix pipe's raw tca16 and ll16 of ray 64 (i/64) + i % 32 and sphere 64 (i/64) + 16 ((i % 64) / 32). */
 int rt_hip_selftest_intersect(int kind, const double *h_rays, const double *h_prims, size_t n, double near_R,
                               uint8_t *h_hit, double *h_tuv, uint64_t *h_keep, int device);
 

@@ -119,6 +119,15 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
     S_init.big = BigPrune{big_tab, L.big_pairs};
   }
   const SceneCtx S = S_init;
+  /* PT_MFMA16 builds: phase 1 of the 32 spheres behind the wall pairs on the fp16 matrix pipe (pt_filter.h, filter_mfma16), for
+   * one-chunk sphere scenes that have them, in every trip but the primary ones (whose filter looks at a few pairs only) */
+  constexpr bool MFMA_FILT = PT_MFMA16 && SWAP && FILT_LDS && GEOM_LDS && !TRIS && !REFR;
+  __shared__ u32x4_t mf_a[MFMA_FILT ? 64 : 1];
+  __shared__ uint32_t mf_bad;
+  const uint32_t mf_first = 2u * L.big_pairs;
+  const bool mf_sized = MFMA_FILT && S.n_sph <= 64u && S.n_sph >= mf_first + PT_MFMA16_ROWS && L.near_R <= PT_MFMA16_NEAR_R_MAX;
+  if (MFMA_FILT && threadIdx.x == 3)
+    mf_bad = 0u;
   if (threadIdx.x < 2)
     wg_stats[threadIdx.x] = 0;
   if (threadIdx.x == 2)
@@ -154,11 +163,25 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
   const uint32_t slot = launch_slot(L, blockIdx.x % launch_slots(L, LIST), LIST), chunk = blockIdx.x / launch_slots(L, LIST);
   const uint32_t tile = L.tile_first + slot * L.tile_stride;
   const bool cull_ok = S.n_sph + S.n_tri <= 64u * CULL_WORDS;
+  if (mf_sized && threadIdx.x < PT_MFMA16_ROWS)
+  { /* thread = sphere mf_first + threadIdx.x: its row of the A operand (pt_device.h), or the note that one does not fit */
+    uint16_t row[16];
+    if (!pt_mfma16_row(L.scene.entry_src + PT_ENTRY_SRC_STRIDE * (size_t)(mf_first + threadIdx.x), L.near_R, S.filt_shift, row))
+      atomicOr(&mf_bad, 1u);
+    const uint32_t m = mfma16_row_of(threadIdx.x);
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+      mf_a[32 * h + m] = u32x4_t{row[8 * h + 0] | ((uint32_t)row[8 * h + 1] << 16), row[8 * h + 2] | ((uint32_t)row[8 * h + 3] << 16),
+                                 row[8 * h + 4] | ((uint32_t)row[8 * h + 5] << 16), row[8 * h + 6] | ((uint32_t)row[8 * h + 7] << 16)};
+  }
   if (SWAP && FILT_LDS && cull_ok)
   { /* the primitives a camera ray of this tile can reach at all: what the filter of a PRIMARY trip looks at */
     tile_cull(cam_lds, L.scene.entry_src, S.n_sph, S.n_sph + S.n_tri, (tile % L.tiles_x) * PT_TILE, (tile / L.tiles_x) * PT_TILE, tile_pairs);
     __syncthreads();
   }
+  else if (MFMA_FILT)
+    __syncthreads();
+  const Mfma16 MF = {mf_a, mf_first, mf_sized && __builtin_amdgcn_readfirstlane((int)mf_bad) == 0};
   /* SWAP kernels: the four waves draw their 64-job batches from ONE pool, the tile's 64 pixels x samples (an LDS
    * counter): whichever wave is free takes the next batch, so the waves finish together whatever the rows of the
    * tile cost (a batch = one sample index of every pixel of the tile: its rays span exactly the tile's cone).  The
@@ -425,6 +448,16 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
 #endif
     const uint32_t *const prim_pairs = (SWAP && FILT_LDS && primary_trip && cull_ok) ? tile_pairs : nullptr;
     PHASE(0); /* the rest of the trip's head: the camera samples of a swap (start_sample) */
+    /* phase 1 on the matrix pipe: here, where all 64 lanes are active (the MFMA and the lane swaps act on the whole wave), for
+     * every lane's current ray; a lane that does not step this trip ignores its word */
+    PreCand pre_cand = {0u, 0u, false};
+    if (MFMA_FILT && MF.on && !primary_trip)
+    {
+      pre_cand.drop = filter_mfma16(MF, filter_ray<true, true>(P.o, P.d, S.filt_shift, S.near_R2));
+      pre_cand.first = MF.first;
+      pre_cand.on = true;
+      DIAG(4, 1); /* trips whose small spheres went through the matrix pipe (wave): how a test sees that the path ran */
+    }
 
     bool step_done = false;
     /* lanes still sampling a direction from an earlier trip sit this trip's step out */
@@ -502,7 +535,7 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
         step_done = trace_step<1, true, CHECKER, TRIS, FILT_LDS, 0, true, false, FILT_LDS && !GEOM_LDS, PoolStack>(S, P, n_casts, diag_ptr, mine, stack_n, &hit, prim_pairs);
       }
       else
-        step_done = trace_step<1, false, CHECKER, TRIS, FILT_LDS, 0, true, false, FILT_LDS && !GEOM_LDS>(S, P, n_casts, diag_ptr, no_stack, stack_n, &hit, prim_pairs);
+        step_done = trace_step<1, false, CHECKER, TRIS, FILT_LDS, 0, true, false, FILT_LDS && !GEOM_LDS>(S, P, n_casts, diag_ptr, no_stack, stack_n, &hit, prim_pairs, false, pre_cand);
     }
     PHASE(3); /* hit record, roulette, material */
     /* this trip's radiance terms to the pixel sums; a lane whose path ended falls idle.  (PARK: BEFORE the direction block, so

@@ -262,6 +262,110 @@ __host__ __device__
 #endif
 static inline double pt_sign_widen_total(double A, double g) { return pt_sign_widen_r2(A, g) + pt_sign_widen_kq(g); }
 
+/* Phase 1 of the small spheres on the fp16 matrix pipe (pt_filter.h, filter_mfma16; -DPT_MFMA16=1 builds only): a sphere's
+ * row of the A operand of v_mfma_f32_32x32x16_f16, 16 halves
+ *     k:  0    1    2    3    4    5    6    7  |  8    9  10  11   12   13   14 15
+ *         cxh  cyh  czh  cxh  cyh  czh  cxl  cyl | czl   1   1   1   kqh  kql   0  0
+ * against the ray's  xh yh zh xl yl zl xh yh | zh p1 p2 p3 s s 0 0  with (x, p, s) = (d, -o'.d in three parts, 0) for tca' and
+ * (-2 o', |o'|^2 in three parts, 1) for ll: every product but lo x lo, accumulated in fp32.  c = hi + lo is the fp64 centre
+ * rounded to 22 bits (hi = RN16(c), lo = RN16(c - hi)); kq = kqh + kql EXACTLY, and at most |c|^2 - (r^2 + W16).
+ *   The bound behind W16, derived as the one above pt_build_filter (pt_kernel.hip): u = 2^-11, e = 2^-24, A = |c| + near_R + tol (tol = the launch's
+ *   filt_shift, the pull-back of the ray's origin: pt_mfma16_row takes it and adds it),
+ *   |d| <= 1.0001, the ray's values split by the device with |x - xh - xl| <= 4 u^2 |x| (round to nearest or towards zero) and
+ *   |xl| <= 2 u |x|, halves below 2^-14 quantised to 2^-24 (phi = 2^-24 covers a product's two such floors), and the matrix
+ *   pipe's sum of K = 16 exact products taken to lose at most one fp32 ulp of the sum of magnitudes per addition,
+ *   16 x 2^-23 = 2^-19 in all, whatever the order:
+ *     a product:  |ch xh + ch xl + cl xh - c x| <= (u^2 + 4 u^2 + e + 2.01 u^2) |c x| + phi (|c| + |x|) <= 2^-19 |c x| + phi (|c| + |x|);
+ *     tca16:  |tca16 - tca'| <= 2^-19 1.0001 |c| + 2^-19 1.02 A + 5.1 e A (o'.d, as for the fp32 form) + 2^-29 A + floors
+ *             <= ET = 3 x 2^-19 A + 2^-20;
+ *     ll16:   |ll16 - (|c - o'|^2 - r2_hi16)| <= 10 e A^2 + 5 e |kq| (the fp32 values the two forms share) + 2^-19 A^2 / 2 (products,
+ *             2 |c||o'| <= A^2 / 2) + 2^-29 A^2 + 2^-19 (|kq| + A^2) + 6 phi A  <= EL = 1.82 x 2^-19 A^2 + 1.16 x 2^-19 |kq| + 6 phi A;
+ *     q''16 = fma(tca16, |tca16|, -ll16):  |tca'| <= 1.0001 A, so
+ *             |q''16 - (r2_hi16 - d2)| <= ET (2.0002 A + ET) + EL + 2 e (A^2 + |kq|) <= E16 = 8 x 2^-19 A^2 + 1.5 x 2^-19 |kq| + 2^-18 A.
+ *   A lane whose tca16 comes out negative although tca' > 0 has tca' <= ET and sees -tca16^2 - ll16 >= W16 - 2 ET^2 - EL: inside
+ *   the same bound, so the fp32 form's pull-back of the origin needs no widening.  W16 = 2^-16 A^2 + 2^-18 g + 2^-17 A with
+ *   g = | |c|^2 - r^2 | (|kq| <= g + W16): about six times the fp32 form's 40 e A^2, against radii of order 1.
+ * A sphere FITS the form (return 1) when everything is finite, its radius is below the wall threshold, |c_i| <= 4096 and
+ * |kq| <= 60000 (fp16's range), and near_R <= PT_MFMA16_NEAR_R_MAX so that |o'|^2 < 65504 for every ray that is filtered at all. */
+#define PT_MFMA16_NEAR_R_MAX 250.0
+#define PT_MFMA16_ROWS 32u
+#define PT_WALL_RADIUS 1000.0
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint16_t pt_f16_rn(double x) /* round to nearest even; |x| < 65520 and finite */
+{
+  const uint16_t s = x < 0.0 ? 0x8000u : 0u;
+  const double a = fabs(x);
+  if (a == 0.0)
+    return s;
+  int ex;
+  (void)frexp(a, &ex); /* a = m 2^ex, m in [0.5, 1) */
+  const int q = ((ex - 1 < -14) ? -14 : ex - 1) - 10;
+  const double v = ldexp(rint(ldexp(a, -q)), q);
+  if (v == 0.0)
+    return s;
+  (void)frexp(v, &ex);
+  const int E = ex - 1;
+  if (E < -14)
+    return (uint16_t)(s | (uint16_t)ldexp(v, 24));
+  return (uint16_t)(s | (uint16_t)(((E + 15) << 10) + ((int)ldexp(v, 10 - E) - 1024)));
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline double pt_f16_value(uint16_t h)
+{
+  const int E = (h >> 10) & 31, m = h & 1023;
+  const double v = E == 0 ? ldexp((double)m, -24) : ldexp((double)(m + 1024), E - 25);
+  return (h & 0x8000u) ? -v : v;
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline double pt_mfma16_widen(double A, double g)
+{
+  return (A * A / 65536.0 + g / 262144.0 + A / 131072.0) * (1.0 + 1e-6);
+}
+/* src = cx cy cz r^2 |c| . (an entry_src record); tol = the launch's filt_shift, by which the ray's origin is pulled back (part of A);
+ * row[16] as laid out above */
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline int pt_mfma16_row(const double *src, double near_R, double tol, uint16_t row[16])
+{
+  for (int k = 0; k < 16; k++)
+    row[k] = 0;
+  const double cn = src[4], r2 = src[3];
+  if (!(near_R <= PT_MFMA16_NEAR_R_MAX) || !(tol >= 0.0) || !(tol <= 1.0) || !(cn <= 8192.0) || !(r2 >= 0.0) || !(r2 < PT_WALL_RADIUS * PT_WALL_RADIUS))
+    return 0;
+  uint16_t hi[3], lo[3];
+  for (int a = 0; a < 3; a++)
+  {
+    if (!(fabs(src[a]) <= 4096.0))
+      return 0;
+    hi[a] = pt_f16_rn(src[a]);
+    lo[a] = pt_f16_rn(src[a] - pt_f16_value(hi[a]));
+  }
+  const double A = (cn + near_R + tol) * (1.0 + 1e-6), cc = cn * cn, g = fabs(cc - r2);
+  double kq = cc - (r2 + pt_mfma16_widen(A, g));
+  kq -= fabs(kq) / 2097152.0 + 1.0 / 8388608.0; /* the split's own residual (<= 2^-22 |kq| + 2^-25), taken off beforehand */
+  if (!(fabs(kq) <= 60000.0))
+    return 0;
+  const uint16_t kh = pt_f16_rn(kq), kl = pt_f16_rn(kq - pt_f16_value(kh));
+  const uint16_t one = 0x3C00u;
+  row[0] = row[3] = hi[0];
+  row[1] = row[4] = hi[1];
+  row[2] = row[5] = hi[2];
+  row[6] = lo[0];
+  row[7] = lo[1];
+  row[8] = lo[2];
+  row[9] = row[10] = row[11] = one;
+  row[12] = kh;
+  row[13] = kl;
+  return 1;
+}
+
 /* The filter buffer of a small scene (pt_filter_in_lds) holds two tables: the pair table of
  * phase 1 (PT_FILT_STRIDE f32x2 per primitive pair, + the look-ahead pair), then, 16-byte aligned,
  * the fp32 triangle table of the per-lane pre-test (PT_TRI32_STRIDE floats per triangle). */

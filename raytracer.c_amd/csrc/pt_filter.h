@@ -162,12 +162,110 @@ struct BigPrune
   uint32_t n_pairs; /* 0: off (wave-uniform) */
 };
 
+/* ---- phase 1 of the small spheres on the fp16 matrix pipe (PT_MFMA16, on by default; -DPT_MFMA16=0 is the A/B's other arm,
+ * `make shim-mfma0`: every sphere through the packed-fp32 loop, as before) ----
+ * The sign-test form is a dense contraction, 64 rays x 32 spheres x (4 components in three fp16 products each); the wall-sized
+ * leading pairs stay in the packed-fp32 loop (BigPrune needs their tca32' and q32 there, and no 11-bit split bounds a radius of
+ * 1e4).  v_mfma_f32_32x32x16_f16: lane l gives row l % 32 of A and column l % 32 of B, eight halves each, k = 8 (l / 32) + j;
+ * register v of the result is row 8 (v / 4) + 4 (l / 32) + (v % 4) of column l % 32 -- and whatever k means to the hardware,
+ * A's and B's halves meet pairwise, which is all the contraction needs.  Rays are the columns: tile 0 = rays 0..31, tile 1 = rays
+ * 32..63, so every lane forms its own ray's sixteen halves and one v_permlane32_swap per register hands the partner lane
+ * (+-32) the half it contributes.  Rows are laid out (pooled body, prologue) so that lane half h, register v is sphere
+ * first + 16 h + v: sixteen sign bits shifted in per tile, one more swap, and each lane holds its own ray's 32 drop bits. */
+#ifndef PT_MFMA16
+#define PT_MFMA16 1
+#endif
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+struct Mfma16
+{
+  const u32x4_t *a; /* LDS: [2][32] A rows, half h of row m at a[32 h + m]: lane l reads a[l] */
+  uint32_t first;   /* the 32 spheres first .. first + 31 (even; = 2 x the wall pairs) */
+  bool on;          /* wave-uniform */
+};
+/* the lane's drop bits of spheres first .. first + 31 (a set bit means DROP), or nothing */
+struct PreCand
+{
+  uint32_t drop;
+  uint32_t first;
+  bool on; /* wave-uniform */
+};
+/* which row of the A operand holds sphere first + s (s < 32) */
+__device__ __forceinline__ uint32_t mfma16_row_of(uint32_t s) { return 8u * ((s & 15u) >> 2) + 4u * (s >> 4) + (s & 3u); }
+/* ALL 64 lanes must be active.  PROBE (the self-test only, pt_selftest_mfma16): the lane's raw accumulators of tile 0, register 0
+ * -- tca16 and ll16 of ray lane % 32 and sphere first + 16 (lane / 32) -- go to probe[0..1].  (A template switch: as a run-time
+ * null test the dead stores cost pt_render_tiles two registers and three spills.) */
+template <bool PROBE = false>
+__device__ __forceinline__ uint32_t filter_mfma16(const Mfma16 &M, const FiltRay &fr, float *probe = nullptr)
+{
+  auto pk = [](float a, float b) -> uint32_t { return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b)); };
+  auto lo_f = [](uint32_t p) -> float { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p & 0xFFFFu)); };
+  auto hi_f = [](uint32_t p) -> float { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p >> 16)); };
+  /* x y z -> (xh yh) (zh xl) (yl zl), and w in three parts behind zh: (zh w1) (w2 w3) */
+  auto split = [&](float x, float y, float z, float w, uint32_t P[4], uint32_t Q[4], uint32_t ones) {
+    P[0] = pk(x, y);
+    const float xl = x - lo_f(P[0]), yl = y - hi_f(P[0]);
+    P[1] = pk(z, xl);
+    const float zl = z - lo_f(P[1]);
+    P[2] = pk(yl, zl);
+    P[3] = P[0];
+    Q[0] = pk(z, w);
+    const float w2 = w - hi_f(Q[0]);
+    const uint32_t t = pk(w2, 0.f);
+    const float w3 = w2 - lo_f(t);
+    Q[1] = pk(w2, w3);
+    Q[2] = ones;
+    Q[3] = 0u;
+  };
+  const uint32_t lane = threadIdx.x & 63u;
+  const f16x8 A = __builtin_bit_cast(f16x8, M.a[lane]);
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  uint32_t PT_[4], QT[4], PL[4], QL[4];
+  split(fr.dx.x, fr.dy.x, fr.dz.x, -fr.od, PT_, QT, 0u);
+  split(fr.m2ox, fr.m2oy, fr.m2oz, fr.oo, PL, QL, 0x3C003C00u);
+  /* lanes 32..63 of P <-> lanes 0..31 of Q: P becomes tile 0's B operand, Q tile 1's */
+#pragma unroll
+  for (int r = 0; r < 4; r++)
+  {
+    u32x2_t t = __builtin_amdgcn_permlane32_swap(PT_[r], QT[r], false, false);
+    PT_[r] = t.x;
+    QT[r] = t.y;
+    t = __builtin_amdgcn_permlane32_swap(PL[r], QL[r], false, false);
+    PL[r] = t.x;
+    QL[r] = t.y;
+  }
+  uint32_t w[2];
+#pragma unroll
+  for (int tile = 0; tile < 2; tile++)
+  {
+    const u32x4_t bt = tile ? u32x4_t{QT[0], QT[1], QT[2], QT[3]} : u32x4_t{PT_[0], PT_[1], PT_[2], PT_[3]};
+    const u32x4_t bl = tile ? u32x4_t{QL[0], QL[1], QL[2], QL[3]} : u32x4_t{PL[0], PL[1], PL[2], PL[3]};
+    const f32x16 tca = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, __builtin_bit_cast(f16x8, bt), zero, 0, 0, 0);
+    const f32x16 ll = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, __builtin_bit_cast(f16x8, bl), zero, 0, 0, 0);
+    if (PROBE && tile == 0)
+    {
+      probe[0] = tca[0];
+      probe[1] = ll[0];
+    }
+    uint32_t word = 0u;
+#pragma unroll
+    for (int v = 15; v >= 0; v--) /* descending: bit v = register v */
+      word = __builtin_amdgcn_alignbit(word, __float_as_uint(__builtin_fmaf(tca[v], __builtin_fabsf(tca[v]), -ll[v])), 31);
+    w[tile] = word;
+  }
+  /* own ray: spheres first + 0..15 in w[0] (lane half 0 computed them), first + 16..31 in w[1] */
+  const u32x2_t t = __builtin_amdgcn_permlane32_swap(w[0], w[1], false, false);
+  return (t.x & 0xFFFFu) | (t.y << 16);
+}
+
 /* TABLE_MEM: the FILT_LDS form of the filter with its table in memory (pt_render_tiles_pool_mem_s); the other form's table
  * always is */
 template <bool TRIS, bool FILT_LDS, bool TABLE_MEM = false>
 __device__ __forceinline__ void filter_chunk(const f32x2 *__restrict__ filt, uint32_t base, uint32_t chunk, const FiltRay &fr,
                                              uint32_t &cand_lo, uint32_t &cand_hi, BigPrune big = BigPrune{nullptr, 0u},
-                                             uint32_t *pruned_out = nullptr)
+                                             uint32_t *pruned_out = nullptr, PreCand pre = PreCand{0u, 0u, false})
 {
   constexpr bool SHIFT = FILT_LDS && !TRIS;
   constexpr bool MEM = TABLE_MEM || !FILT_LDS;
@@ -256,7 +354,13 @@ __device__ __forceinline__ void filter_chunk(const f32x2 *__restrict__ filt, uin
     };
     /* the leading wall pairs come last (descending order) and by a loop of their own, which also estimates their hit distances */
     const uint32_t nb = (SHIFT && base == 0u) ? min(big.n_pairs, pairs_lo) : 0u;
-    run_desc(pairs_lo - 1u, pairs_lo - nb, cand_lo);
+    /* the matrix pipe has the 16 pairs behind the walls already (filter_mfma16; pre.first = 2 nb, chunk >= pre.first + 32):
+     * their drop bits stand in the word the walls' are shifted into */
+    const bool pre_on = PT_MFMA16 && SHIFT && pre.on;
+    if (pre_on)
+      cand_lo = pre.drop;
+    else
+      run_desc(pairs_lo - 1u, pairs_lo - nb, cand_lo);
     uint32_t pruned = 0u;
     if (SHIFT && nb != 0u)
     {
@@ -303,7 +407,14 @@ __device__ __forceinline__ void filter_chunk(const f32x2 *__restrict__ filt, uin
     }
     if (pruned_out)
       *pruned_out = pruned;
-    run_desc(n_pairs - 1u, n_pairs - pairs_lo, cand_hi);
+    if (pre_on)
+    { /* the pairs past the matrix pipe's 16, then its own spheres of index 32 and up below them */
+      const uint32_t done = (pre.first >> 1) + 16u; /* <= n_pairs */
+      run_desc(n_pairs - 1u, n_pairs - done, cand_hi);
+      cand_hi = (cand_hi << pre.first) | (uint32_t)(((unsigned long long)pre.drop << pre.first) >> 32);
+    }
+    else
+      run_desc(n_pairs - 1u, n_pairs - pairs_lo, cand_hi);
     if (SHIFT)
     { /* drop bits -> keep bits */
       cand_lo = ~cand_lo;
@@ -583,8 +694,9 @@ __device__ __forceinline__ void scan_filtered(const double *geom, const double *
                                               double filt_shift = 0.0, TriLast *last = nullptr, bool no_prune = false,
                                               const float4 *tri32 = nullptr, const uint32_t *prim_pairs = nullptr,
                                               BigPrune big = BigPrune{nullptr, 0u}, const MeshBound *mesh_bound = nullptr,
-                                              bool no_rules = false)
+                                              bool no_rules = false, PreCand pre = PreCand{0u, 0u, false})
 {
+  /* pre (PT_MFMA16 builds, one-chunk sphere scenes): the matrix pipe's drop bits of this lane's ray, formed before the divergent part of the trip */
   /* no_rules (per lane, read with RULE_SWITCH only; the ray-query kernels, whose rays are the caller's): this ray is outside what the skipping rules are
    * proven for, so none may drop anything for it -- the filter keeps every primitive, the fp32 pre-tests and the wall pruning
    * are bypassed, the hierarchy walk enters every box and pre-tests no leaf.  The exact tests alone decide, in scan order.  It
@@ -628,7 +740,7 @@ __device__ __forceinline__ void scan_filtered(const double *geom, const double *
     else if (FILT_LDS && prim_pairs != nullptr)
       filter_chunk_listed<SHIFT, FILT_MEM>(filt, base, chunk, prim_pairs[base >> 6], fr, cand_lo, cand_hi);
     else
-      filter_chunk<TRIS, FILT_LDS, FILT_MEM>(filt, base, chunk, fr, cand_lo, cand_hi, big, &pruned);
+      filter_chunk<TRIS, FILT_LDS, FILT_MEM>(filt, base, chunk, fr, cand_lo, cand_hi, big, &pruned, pre);
     /* triangle candidates of this chunk: bits from entry n_sph on */
     uint32_t tri_lo = 0, tri_hi = 0;
     if (TRIS && !BVH)

@@ -1042,6 +1042,75 @@ extern "C" __global__ __launch_bounds__(64) void pt_selftest_intersect(int kind,
   }
 }
 
+/* Self-test hook (rt_hip_selftest_intersect, kind 2): the keep words of phase 1 on the fp16 matrix pipe (filter_mfma16), on
+ * caller data.  prims = n x 4 (cx cy cz r*r) as for kind 0, n a multiple of 64.  One wavefront per block of 64 rays and 64
+ * spheres; the block's first 32 spheres are the matrix rows (pt_mfma16_row, built here as the pooled body's prologue builds
+ * them, first = 0), its other 32 go through the packed loop behind them, as in a scene of more than 32 small spheres.
+ * Every lane runs its own ray against the block's 64 spheres:
+ *   keep[3i + 0]  packed sign-test form alone (what -DPT_MFMA16=0 computes)
+ *   keep[3i + 1]  matrix pipe for spheres 0..31, merged by filter_chunk as in the render kernels
+ *   keep[3i + 2]  the kernel's exact test (exact_sphere), bit j = ray i hits sphere 64 b + j
+ * hit[i] = 1 when all 32 rows fit the form (else the block ran the packed loop twice); tuv[3i], tuv[3i + 1] = the matrix pipe's
+ * tca16 and ll16 of ray 64 b + (i % 32) and sphere 64 b + 16 ((i % 64) / 32): values a test can set against fp64 and the bounds ET, EL
+ * of pt_mfma16_row. */
+extern "C" __global__ __launch_bounds__(64) void pt_selftest_mfma16(const double *rays, const double *prims, const double *entry_src,
+                                                                   const f32x2 *filt, uint32_t n, double near_R, double near_R2,
+                                                                   double filt_shift, uint8_t *hit, double *tuv, unsigned long long *keep)
+{
+  __shared__ f32x2 filt_lds[PT_FILT_STRIDE * 33];
+  __shared__ u32x4_t mf_a[64];
+  __shared__ uint32_t mf_bad;
+  const uint32_t base = blockIdx.x * 64u; /* base + 64 <= n */
+  if (threadIdx.x == 0)
+    mf_bad = 0u;
+  for (uint32_t k = threadIdx.x; k < PT_FILT_STRIDE * 33; k += 64)
+    filt_lds[k] = filt[PT_FILT_STRIDE * (size_t)(base >> 1) + k];
+  __syncthreads();
+  if (threadIdx.x < PT_MFMA16_ROWS)
+  {
+    uint16_t row[16];
+    if (!pt_mfma16_row(entry_src + PT_ENTRY_SRC_STRIDE * (size_t)(base + threadIdx.x), near_R, filt_shift, row))
+      atomicOr(&mf_bad, 1u);
+    const uint32_t m = mfma16_row_of(threadIdx.x);
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+      mf_a[32 * h + m] = u32x4_t{row[8 * h + 0] | ((uint32_t)row[8 * h + 1] << 16), row[8 * h + 2] | ((uint32_t)row[8 * h + 3] << 16),
+                                 row[8 * h + 4] | ((uint32_t)row[8 * h + 5] << 16), row[8 * h + 6] | ((uint32_t)row[8 * h + 7] << 16)};
+  }
+  __syncthreads();
+  const Mfma16 MF = {mf_a, 0u, __builtin_amdgcn_readfirstlane((int)mf_bad) == 0};
+  const uint32_t i = base + threadIdx.x;
+  const V3 o = ld3(rays + 6 * (size_t)i), d = ld3(rays + 6 * (size_t)i + 3);
+  const FiltRay fr = filter_ray<true, true>(o, d, filt_shift, near_R2);
+  uint32_t lo, hi;
+  filter_chunk<false, true>(filt_lds, 0u, 64u, fr, lo, hi);
+  const unsigned long long m0 = ((unsigned long long)hi << 32) | lo;
+  PreCand pre = {0u, 0u, false};
+  float probe[2] = {0.f, 0.f};
+  if (MF.on)
+  {
+    pre.drop = filter_mfma16<true>(MF, fr, probe);
+    pre.on = true;
+  }
+  filter_chunk<false, true>(filt_lds, 0u, 64u, fr, lo, hi, BigPrune{nullptr, 0u}, nullptr, pre);
+  const unsigned long long m1 = ((unsigned long long)hi << 32) | lo;
+  unsigned long long m2 = 0ull;
+  for (uint32_t j = 0; j < 64u; j++)
+  {
+    double t = 1.7976931348623157e308;
+    int best = -1;
+    exact_sphere(prims + 4 * (size_t)(base + j), 0u, o, d, t, best);
+    m2 |= best >= 0 ? (1ull << j) : 0ull;
+  }
+  hit[i] = MF.on ? 1 : 0;
+  tuv[3 * (size_t)i + 0] = (double)probe[0];
+  tuv[3 * (size_t)i + 1] = (double)probe[1];
+  tuv[3 * (size_t)i + 2] = 0.0;
+  keep[3 * (size_t)i + 0] = m0; /* (filter_chunk has given far-origin lanes every bit) */
+  keep[3 * (size_t)i + 1] = m1;
+  keep[3 * (size_t)i + 2] = m2;
+}
+
 /* Self-test hook (rt_hip_selftest_xcc): which XCD each workgroup of a launch ran on, as the parked-walk kernels read it
  * (pt_park_acquire): counts[x] = workgroups that saw HW_REG_XCC_ID == x. */
 extern "C" __global__ __launch_bounds__(64) void pt_selftest_xcc(unsigned int *counts)
@@ -2320,7 +2389,15 @@ hipError_t pt_launch_selftest_intersect(int kind, const double *rays, const doub
 {
   if (n == 0)
     return hipSuccess;
+  if (kind == 2 && (!PT_MFMA16 || n % 64u != 0u))
+    return hipErrorNotSupported; /* a build without the matrix-pipe filter has nothing to test */
   hipLaunchKernelGGL(pt_build_filter, dim3(min(1024u, (n + 255u) / 256u)), dim3(256), 0, stream, entry_src, n, near_R, filt);
+  if (kind == 2)
+  {
+    hipLaunchKernelGGL(pt_selftest_mfma16, dim3(n / 64u), dim3(64), 0, stream, rays, prims, entry_src, reinterpret_cast<const f32x2 *>(filt), n,
+                       near_R, near_R * near_R, filt_shift, hit, tuv, keep);
+    return hipGetLastError();
+  }
   if (kind == 1)
     hipLaunchKernelGGL(pt_build_tri32, dim3((n + 255u) / 256u), dim3(256), 0, stream, prims, n, near_R, tri32);
   hipLaunchKernelGGL(pt_selftest_intersect, dim3((n + 63u) / 64u), dim3(64), 0, stream, kind, rays, prims,

@@ -75,7 +75,8 @@ template <int VARIANT, bool REFRACT, bool CHECKER, bool TRIS, bool FILT_LDS, int
           bool SPH_LDS = false, bool FILT_MEM = false, class STK = PendStack, bool RULE_SWITCH = false>
 __device__ __forceinline__ bool trace_step(const SceneCtx &S, Path &P, uint32_t &n_casts,
                                            unsigned long long *diag_ptr, const STK &stack, int &stack_n,
-                                           HitRec *rec = nullptr, const uint32_t *prim_pairs = nullptr, bool no_rules = false)
+                                           HitRec *rec = nullptr, const uint32_t *prim_pairs = nullptr, bool no_rules = false,
+                                           PreCand pre = PreCand{0u, 0u, false})
 {
   V3 add = {S.bg, S.bg, S.bg}; /* what this call contributes if the path ends here */
   bool path_ends = true;
@@ -117,7 +118,7 @@ __device__ __forceinline__ bool trace_step(const SceneCtx &S, Path &P, uint32_t 
         scan_filtered<TRIS, TRIS && !FILT_LDS, FILT_LDS, MODE == 0, CHECKER && TRIS, SPH_LDS, FILT_MEM, RULE_SWITCH>(
             S.geom, S.tri, (FILT_LDS || SPH_LDS) ? S.filt_lds : S.filt, S.near_R2, S.n_sph, S.n_sph + S.n_tri, o, d, H.min_t, H.best,
             H.bary_u, H.bary_v, diag_ptr, S.bvh_nodes, S.n_bvh_nodes, S.bvh_tri, S.filt_shift, &H.last, S.stale_uv, S.tri32, prim_pairs, S.big,
-            (TRIS && FILT_LDS && !(CHECKER && TRIS)) ? &S.mesh_bound : nullptr, no_rules); /* (not where hit.u / hit.v follow EVERY passing triangle: same thing,
+            (TRIS && FILT_LDS && !(CHECKER && TRIS)) ? &S.mesh_bound : nullptr, no_rules, pre); /* (not where hit.u / hit.v follow EVERY passing triangle: same thing,
                                                                                * a triangle the ray passes lies inside the ball -- but keep that path as it was) */
     }
     if (MODE == 1)

@@ -4118,23 +4118,25 @@ int rt_hip_selftest_xcc(uint32_t n_workgroups, uint32_t h_counts[16], int device
 int rt_hip_selftest_intersect(int kind, const double *h_rays, const double *h_prims, size_t n, double near_R,
                               uint8_t *h_hit, double *h_tuv, uint64_t *h_keep, int device)
 {
-  if ((kind != 0 && kind != 1) || !h_rays || !h_prims || !h_hit || !h_tuv || !h_keep)
+  if ((kind != 0 && kind != 1 && kind != 2) || !h_rays || !h_prims || !h_hit || !h_tuv || !h_keep)
     return fail(RT_HIP_EINVAL, "bad self-test arguments");
   if (!(near_R > 0) || !(near_R < 1e15) || n > 0x7FFFFFFFu)
     return fail(RT_HIP_EINVAL, "near_R must be a positive finite bound, n < 2^31");
   if (!have_device(device))
     return fail(RT_HIP_ENODEV, "no HIP device %d", device);
+  if (kind == 2 && n % 64 != 0)
+    return fail(RT_HIP_EINVAL, "the matrix-filter self-test takes whole blocks of 64 cases");
   if (n == 0)
     return RT_HIP_OK;
   return guarded("rt_hip_selftest_intersect", [&]() -> int {
     /* the records exactly as rt_hip_scene_create lays them out (same helpers) */
-    const size_t rec = kind == 0 ? 4 : 9;
+    const size_t rec = kind == 1 ? 9 : 4;
     std::vector<double> prims(rec * n), entry(PT_ENTRY_SRC_STRIDE * n);
     double max_center = 0;
     for (size_t i = 0; i < n; i++)
     {
       double *e = &entry[PT_ENTRY_SRC_STRIDE * i];
-      if (kind == 0)
+      if (kind != 1)
       {
         const double *p = h_prims + 4 * i;
         if (!(std::fabs(p[3]) >= 1e-100) || !(std::fabs(p[3]) <= 1e17))

@@ -25,7 +25,7 @@ torch.cuda.synchronize()
 st = stats.cpu().tolist()
 rays, casts = st[0], st[1]
 d = st[4:]
-names = ["loop iters (wave)", "loop lanes", "phase2 iters (wave)", "phase2 cands (lane)", "sqrt blocks (wave)", "sqrt lanes",
+names = ["loop iters (wave)", "loop lanes", "phase2 iters (wave)", "phase2 cands (lane)", "trips with the small spheres on the matrix pipe (wave)", "(unused)",
          "fresh blocks (wave)", "fresh lanes", "hit blocks (wave)", "hit lanes", "reject-loop iters (wave)", "reject-loop lanes", "FILTER VIOLATIONS (must be 0)", "bvh node visits (wave)", "bvh leaf triangle tests (wave)", "bvh node-visit lanes", "bvh leaf pre-tests (wave)", "parked rays", "walked rays returning a triangle",
          "walks of 1 node visit", "walks of 2-3", "walks of 4-6", "walks of 7+",
          "parked rays inside the triangles' bounding sphere",
