@@ -248,10 +248,11 @@ enum { RT_BVH_HOST = 0, RT_BVH_DEVICE = 1 };
 void rt_set_bvh_builder(int builder);
 int rt_get_bvh_builder(void);
 
-/* A deforming mesh.  on != 0: when the scene of a render() call differs from the previous call's only in vertex positions -- the
- * same objects, materials, triangle counts and tex coordinates, the same size and devices -- the scene kept on the GPU takes the
- * new positions in place (rt_hip.h, rt_hip_scene_update_vertices_host: the triangles' records recomputed and the hierarchy
- * refitted on the device) instead of being rebuilt, so render() in a loop over an animated MeshObject[] re-creates nothing.
+/* A deforming mesh, moving spheres.  on != 0: when the scene of a render() call differs from the previous call's only in vertex
+ * positions, sphere centres and sphere radii -- the same counts, flags, colours, emissions and tex coordinates, the same size and
+ * devices -- the scene kept on the GPU takes them in place (rt_hip.h, rt_hip_scene_update_vertices_host: the triangles' records
+ * recomputed and the hierarchy refitted on the device; rt_hip_scene_update_spheres_host: the spheres' records and what the scene
+ * derives from them) instead of being rebuilt, so render() in a loop over an animated MeshObject[] or Object[] re-creates nothing.
  * The frame is the one a rebuilt scene gives, bit for bit.  The default, 0: every changed scene is rebuilt.  The CLI renders one
  * frame per process and has no use for it. */
 void rt_set_scene_updates(int on);

@@ -200,13 +200,42 @@ double rt_hip_scene_bvh_build_seconds(const RtHipScene *scene);
  * The caller must not launch on the scene from another thread during the call; work submitted before it is waited for. */
 int rt_hip_scene_update_vertices(RtHipScene *scene, const double *d_positions, size_t n_triangles);
 int rt_hip_scene_update_vertices_host(RtHipScene *scene, const double *h_positions, size_t n_triangles);
-/* how many updates the scene has taken, and the host-clock seconds of the last one; either may be NULL */
+/* how many updates the scene has taken -- of either kind, vertices or spheres -- and the host-clock seconds of the last one; either
+ * may be NULL */
 int rt_hip_scene_update_info(const RtHipScene *scene, uint64_t *updates, double *last_seconds);
 /* for tests: tri_geom (9n), tri_normal (3n), the triangles' entry_src records (6n), tri_object (n, hull bits included); any may be NULL */
 int rt_hip_scene_read_triangles(const RtHipScene *scene, double *geom, double *normal, double *entry, uint32_t *object);
 /* for tests: the triangles' bounding sphere (radius < 0: no triangles), the scene's reach (>= |p| for every point of a primitive
  * of ordinary size: what near_R is made of) and whether a launch takes the _sph members; any may be NULL */
 int rt_hip_scene_bounds(const RtHipScene *scene, double mesh_center[3], double *mesh_radius, double *reach, uint32_t *mesh_round);
+
+/* ---- moving spheres: new centres and radii for a scene that exists ----
+ * d_spheres / h_spheres: 4 doubles a sphere (cx, cy, cz, radius) for EVERY sphere of the scene, in object order -- the layout of
+ * rt_hip_selftest_intersect kind 0.  d_spheres: device memory on the scene's device, not inside the scene (a particle system, a
+ * physics step that keeps its state in a torch tensor); h_spheres: host memory, staged by the call.  Synchronous, as the vertex
+ * update is.  One streaming kernel (k_update_spheres, csrc/scene_update.hip), a thread a sphere, rewrites the spheres' entry_src
+ * records and their geom4 copy and reduces what a scene derives from its spheres -- the spheres' part of the reach, the largest
+ * |centre|, the wide-range flag -- by maxima alone; the leading wall-sized spheres (whole pairs, at most 8) come from the first 8
+ * records.  scene_sphere_bounds (csrc/scene_spheres.h; the text stands in csrc/bvh_build.h) is the one text of all of it, shared with rt_hip_scene_create.  Then every table set is stale and
+ * rebuilt in place by the next launch.  Materials, flags, counts, meshes, object ids and every handle stay.
+ * CONTRACT: after an update the records, the scalars (rt_hip_scene_sphere_bounds, rt_hip_scene_bounds), rt_hip_kernel_name and the
+ * frames, bytes and counters of every launch equal, bit for bit, those of a scene freshly created from the same spheres.  A move may
+ * change the wide-range flag or the number of leading walls, and with them the kernel a launch picks: that is intended, and why a
+ * live RtHipAccum refuses the update.
+ * Acceptance is rt_hip_scene_create's: |radius| outside [1e-100, 1e100] (or NaN) is RT_HIP_ELIMIT; any centre is taken.
+ * RT_HIP_EINVAL: a NULL pointer; n_spheres differs from the scene's count; a scene without spheres; d_spheres not device memory of
+ * the scene's device, or inside the scene; an RtHipAccum on the scene that has not been destroyed; a launch of the scene being
+ * submitted on another thread.  RT_HIP_ENOMEM: the workspace (256 bytes; the host form adds the staged spheres).  After each of these
+ * the scene is unchanged: the kernel's first run writes nothing of the scene.  A scene that an earlier update left unusable:
+ * RT_HIP_ERUNTIME.  A HIP runtime failure after writing has begun is RT_HIP_ERUNTIME and leaves the scene UNUSABLE, as above. */
+int rt_hip_scene_update_spheres(RtHipScene *scene, const double *d_spheres, size_t n_spheres);
+int rt_hip_scene_update_spheres_host(RtHipScene *scene, const double *h_spheres, size_t n_spheres);
+/* for tests: entry_src's sphere records (6n doubles), geom4 (4n); either may be NULL */
+int rt_hip_scene_read_spheres(const RtHipScene *scene, double *entry, double *geom4);
+/* for tests: what the scene derives from its spheres -- the spheres' part of the reach, max |centre|, the wide-range flag a launch
+ * reads, the leading walls (n_big of them, whole pairs; big_r / big_c are 0 from n_big on); any may be NULL */
+int rt_hip_scene_sphere_bounds(const RtHipScene *scene, double *reach_spheres, double *max_center, uint32_t *wide_range, uint32_t *n_big,
+                               double big_r[8], double big_c[8]);
 
 int rt_hip_scene_device(const RtHipScene *scene);
 size_t rt_hip_scene_primitives(const RtHipScene *scene); /* spheres + triangles */
@@ -663,7 +692,7 @@ int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t widt
  * a zeroed history) have a defined result.  len = 0 marks a pixel the next frame must not use; a zero-filled history (buffers and
  * camera) behaves like no history.  Step 3 assumes a scene that is static between the two frames; after
  * rt_hip_scene_update_vertices the caller gives the previous points instead (rt_hip_reproject_points, below) and keeps the
- * history.  Out of scope: moving spheres (the scene cannot move them), topology changes, demodulated history, variance estimates.
+ * history.  Moved spheres (rt_hip_scene_update_spheres) likewise: rt_hip_prev_points_moved.  Out of scope: topology changes, demodulated history, variance estimates.
  *   - rt_hip_reproject_defaults: flags 0, max_history = 32, depth_tol = 0.05, normal_min = 0.5 (DESIGN, "`pt_reproject`": the sweep).
  *   - rt_hip_reproject: asynchronous on `stream`, on the device that holds d_rgb.  d_out_rgb and d_out_len are required,
  *     d_out_rgb8 and d_out_motion (2 floats per pixel) may be NULL; d_out_rgb == d_rgb is allowed (in place).  No output may overlap
@@ -699,7 +728,7 @@ int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHi
  * rt_hip_scene_update_vertices, the numbering of the query's prim --, the positions the scene had at the previous frame
  * (n_triangles may be 0, d_positions then NULL); d_points: 3 doubles per entry.  fp64 +, -, *, unfused, in the order written.  Entry i:
  *   - status != 1: three quiet NaNs, bits 0x7FF8000000000000;
- *   - status == 1 and prim == 0xFFFFFFFF (a sphere, which does not move): the three words of point, copied as bits;
+ *   - status == 1 and prim == 0xFFFFFFFF (a sphere; one that moved: rt_hip_prev_points_moved): the three words of point, copied as bits;
  *   - status == 1 and prim < n_triangles: u = bary[0], v = bary[1], w0 = (1.0 - u) - v, out_k = (a_k*w0 + b_k*u) + c_k*v for
  *     k = x, y, z with a, b, c the triangle's corners -- the blend intersect_triangle applies to the texture coordinates
  *     (raytracer.c:158-164), applied to positions;
@@ -718,10 +747,26 @@ int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHi
  *       disocclusion, a miss, an invalid ray.)  The frame's camera is not read in this form.
  * Steps 1, 2 and 4-7 are unchanged with D = P - pos': zexp is the previous point's distance from the previous camera, and motion
  * is the true screen-space motion, the surface's own included.  Parameters, ranges and overlap rules are rt_hip_reproject's;
- * d_prev_points must not overlap any output (RT_HIP_EINVAL).  rt_hip_reproject_points_image: the same from host arrays. */
+ * d_prev_points must not overlap any output (RT_HIP_EINVAL).  rt_hip_reproject_points_image: the same from host arrays.
+ *
+ * rt_hip_prev_points_moved: rt_hip_prev_points after rt_hip_scene_update_spheres.  d_hits->object is required as well; d_spheres_prev
+ * and d_spheres_cur: 4 doubles per sphere (cx, cy, cz, radius) in object order, the spheres at the previous frame and now.  The
+ * contract above holds word for word for triangles, for status != 1 and for out-of-range prims.  A sphere hit, status == 1 and prim
+ * == 0xFFFFFFFF:
+ *   - object < n_spheres: with (c', r') the previous sphere and (c, r) the current one, s = r' / r, then
+ *     out_k = c'_k + (point_k - c_k) * s for k = x, y, z -- fp64, unfused, in that order: the surface point rides the sphere's
+ *     translation and uniform scale (a sphere has no orientation in this scene model);
+ *   - object >= n_spheres: three quiet NaNs;
+ *   - d_spheres_prev == NULL and n_spheres == 0: the three words of point, copied as bits -- the call is rt_hip_prev_points itself.
+ * With n_spheres != 0 both arrays are required (RT_HIP_EINVAL); they and object must not overlap d_points.  Totality, the overlap
+ * rule, the error order and n == 0 are rt_hip_prev_points'.  rt_hip_reproject_points is fed unchanged. */
 int rt_hip_prev_points(const RtHipHits *d_hits, uint64_t n, const double *d_positions, size_t n_triangles, double *d_points, void *stream);
 int rt_hip_prev_points_host(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles, int device,
                             double *h_points);
+int rt_hip_prev_points_moved(const RtHipHits *d_hits, uint64_t n, const double *d_positions, size_t n_triangles,
+                             const double *d_spheres_prev, const double *d_spheres_cur, size_t n_spheres, double *d_points, void *stream);
+int rt_hip_prev_points_moved_host(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles,
+                                  const double *h_spheres_prev, const double *h_spheres_cur, size_t n_spheres, int device, double *h_points);
 int rt_hip_reproject_points(const float *d_rgb, const RtHipAov *d_aov, const RtHipCamera *camera, const float *d_hist_rgb,
                             const float *d_hist_len, const RtHipAov *d_hist_aov, const RtHipCamera *hist_camera, int32_t width,
                             int32_t height, const RtHipReprojectParams *params, const double *d_prev_points, float *d_out_rgb,
@@ -1001,9 +1046,10 @@ int rt_hip_set_device_map(const int *map, int n);
  * value is RT_HIP_EINVAL.  Part of the cache key: a change rebuilds the cached context at the next frame. */
 int rt_hip_set_bvh_builder(int builder);
 
-/* on != 0: when a call's scene differs from the cached one ONLY in vertex positions -- the same counts, spheres, materials, tex
- * coordinates, builder, devices and size -- every cached scene takes the new positions in place
- * (rt_hip_scene_update_vertices_host) and rt_hip_cache_updates() counts one, not rt_hip_cache_builds().  The default, 0: such a
+/* on != 0: when a call's scene differs from the cached one ONLY in vertex positions, sphere centres and sphere radii -- the same
+ * counts, flags, colours, emissions, tex coordinates, builder, devices and size -- every cached scene takes them in place
+ * (rt_hip_scene_update_vertices_host, rt_hip_scene_update_spheres_host, both where both differ) and rt_hip_cache_updates() counts
+ * one per frame, not rt_hip_cache_builds().  The default, 0: such a
  * scene rebuilds the context as any other change does. */
 void rt_hip_set_scene_updates(int on);
 uint64_t rt_hip_cache_updates(void);

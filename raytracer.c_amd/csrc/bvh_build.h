@@ -704,6 +704,102 @@ BVH_HD inline void scene_triangle_corner(const double *g, int k, double *p)
     p[a] = k == 0 ? g[a] : g[a] + g[3 * k + a];
 }
 
+/* ---- a scene's spheres moved in place (scene_update.hip, rt_hip_scene_update_spheres) ----
+ * What a scene derives from its spheres, in one text for the host (scene_create_impl, rt_hip_shim.hip), the device
+ * (k_update_spheres, scene_update.hip) and the CPU test of both (tests/sphere_update_harness.cpp, through scene_spheres.h).  Input
+ * everywhere: 4 doubles a sphere, cx cy cz radius, in object order (the layout of rt_hip_scene_update_spheres and of
+ * rt_hip_selftest_intersect kind 0).  Compiled with -ffp-contract=off on every side: the records and scalars of an updated scene
+ * equal a freshly created scene's bit for bit.  Every scalar is a maximum (or an OR, the maximum of 0 and 1) over the spheres, or a
+ * function of the leading eight records alone, so the device's reduction does not depend on the order its waves arrive in. */
+#define SCENE_SPHERE_IN 4   /* doubles a sphere of the input: cx cy cz radius */
+#define SCENE_SPHERE_WALLS 8 /* leading wall-sized spheres looked at: 2 PT_BIG_PAIRS */
+
+/* One sphere's record of entry_src (pt_device.h): cx cy cz, r*r, |c| rounded up, 0 -- and, where asked for, its geom4 copy (the
+ * first PT_GEOM_STRIDE doubles: what the exact test and the normal read). */
+BVH_HD inline void scene_sphere_entry(const double *center, double radius, double *g, double *g4)
+{
+  g[0] = center[0];
+  g[1] = center[1];
+  g[2] = center[2];
+  g[3] = radius * radius; /* raytracer.c:87 */
+  /* |c|, rounded up: feeds the conservative phase-1 thresholds only, never a result */
+  g[4] = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) * (1.0 + 1e-12);
+  g[5] = 0.0; /* a sphere is rejected when its centre is behind the origin at all (raytracer.c:84) */
+  if (g4)
+    for (int k = 0; k < PT_GEOM_STRIDE; k++)
+      g4[k] = g[k];
+}
+
+/* rt_hip_scene_create's rule for a radius (RT_HIP_ELIMIT otherwise); false for NaN */
+BVH_HD inline bool scene_sphere_radius_ok(double radius) { return std::fabs(radius) >= 1e-100 && std::fabs(radius) <= 1e100; }
+
+/* The sphere's part of each scalar; the scene's value is the maximum over the spheres, from 0.
+ * reach_spheres: |c| + |r| of a sphere of ordinary size (wall-sized spheres would only loosen the filter).  fmax(0, x) is x for
+ * every x a sphere can give (x >= 0, or +inf) and drops a NaN, as the host's running fmax(reach, x) does. */
+BVH_HD inline double scene_sphere_reach_part(const double *g, double radius)
+{
+  return std::fabs(radius) < 1000.0 ? std::fmax(0.0, g[4] + std::fabs(radius)) : 0.0;
+}
+BVH_HD inline double scene_sphere_center_part(const double *g) { return std::fmax(0.0, g[4]); }
+/* a centre or radius beyond 1e17 (or not a number): the scene takes the scalar-table _big kernels */
+BVH_HD inline uint32_t scene_sphere_wide_part(const double *g, double radius)
+{
+  return (!(g[4] <= 1e17) || !(std::fabs(radius) <= 1e17)) ? 1u : 0u;
+}
+/* a wall-sized sphere that BigPrune (pt_filter.h) may use */
+BVH_HD inline bool scene_sphere_is_wall(double radius) { return std::fabs(radius) >= 1000.0 && std::fabs(radius) <= 1e17; }
+
+struct SceneSphereBounds
+{
+  double reach_spheres = 0; /* the spheres' part of the scene's reach */
+  double max_center = 0;    /* max |centre| (rounded up) */
+  uint32_t wide_range = 0;
+  /* the LEADING wall-sized spheres, whole pairs of them, at most SCENE_SPHERE_WALLS: radius and |centre|; 0 from n_big on */
+  uint32_t n_big = 0;
+  double big_r[SCENE_SPHERE_WALLS] = {0}, big_c[SCENE_SPHERE_WALLS] = {0};
+};
+
+/* n_big, big_r, big_c from the leading records (spheres: 4 doubles each, n of them; only the first SCENE_SPHERE_WALLS are read) */
+inline void scene_sphere_leading_walls(const double *spheres, size_t n, SceneSphereBounds *b)
+{
+  uint32_t nb = 0;
+  double r[SCENE_SPHERE_WALLS], c[SCENE_SPHERE_WALLS];
+  while (nb < SCENE_SPHERE_WALLS && (size_t)nb < n && scene_sphere_is_wall(spheres[SCENE_SPHERE_IN * (size_t)nb + 3]))
+  {
+    double g[PT_ENTRY_SRC_STRIDE];
+    scene_sphere_entry(spheres + SCENE_SPHERE_IN * (size_t)nb, spheres[SCENE_SPHERE_IN * (size_t)nb + 3], g, nullptr);
+    r[nb] = std::fabs(spheres[SCENE_SPHERE_IN * (size_t)nb + 3]);
+    c[nb] = g[4];
+    nb++;
+  }
+  b->n_big = nb & ~1u; /* whole pairs */
+  for (uint32_t k = 0; k < SCENE_SPHERE_WALLS; k++)
+  {
+    b->big_r[k] = k < b->n_big ? r[k] : 0.0;
+    b->big_c[k] = k < b->n_big ? c[k] : 0.0;
+  }
+}
+
+/* The sequential statement of everything above: the records (entry: PT_ENTRY_SRC_STRIDE n doubles, geom4: PT_GEOM_STRIDE n; either
+ * may be null) and the scalars of n spheres.  What scene_create_impl calls, and what the device's update is tested against. */
+inline void scene_sphere_bounds(const double *spheres, size_t n, double *entry, double *geom4, SceneSphereBounds *b)
+{
+  *b = SceneSphereBounds();
+  for (size_t i = 0; i < n; i++)
+  {
+    const double *s = spheres + SCENE_SPHERE_IN * i;
+    double g[PT_ENTRY_SRC_STRIDE];
+    scene_sphere_entry(s, s[3], g, geom4 ? geom4 + PT_GEOM_STRIDE * i : nullptr);
+    if (entry)
+      for (int k = 0; k < PT_ENTRY_SRC_STRIDE; k++)
+        entry[PT_ENTRY_SRC_STRIDE * i + k] = g[k];
+    b->reach_spheres = std::fmax(b->reach_spheres, scene_sphere_reach_part(g, s[3]));
+    b->max_center = std::fmax(b->max_center, scene_sphere_center_part(g));
+    b->wide_range |= scene_sphere_wide_part(g, s[3]);
+  }
+  scene_sphere_leading_walls(spheres, n, b);
+}
+
 #if defined(__HIPCC__)
 
 /* the arrays of a scene that an update rewrites (device memory) */
@@ -736,6 +832,17 @@ hipError_t scene_update_triangles(const SceneUpdateArrays &s, const double *posi
 /* BvhRefit on the device: the leaf children, then the inner ones level by level from the deepest (by_level in device memory,
  * level_begin on the host: BvhRefit::levels), and tri_geom_leaf.  Enqueues only. */
 hipError_t scene_update_refit(const SceneUpdateArrays &s, const uint32_t *by_level, const uint32_t *level_begin, size_t n_levels);
+
+/* ---- the interface of scene_update.hip's sphere half (rt_hip_scene_update_spheres) ----
+ * Both on the null stream of the current device; spheres = 4 doubles a sphere in device memory; words: SCENE_SPHERE_WORDS 64-bit
+ * words of device workspace. */
+#define SCENE_SPHERE_WORDS 4
+/* reads the spheres alone, writes `words` alone and waits: the scalars that are maxima (n_big, big_r, big_c are not set) and
+ * whether every radius is acceptable */
+hipError_t scene_update_spheres_check(const double *spheres, uint32_t n, unsigned long long *words, SceneSphereBounds *out, bool *radii_ok);
+/* writes the n records of entry (PT_ENTRY_SRC_STRIDE n) and geom4 (PT_GEOM_STRIDE n): the same kernel with its outputs given and
+ * no words -- it reduces nothing.  Enqueues only. */
+hipError_t scene_update_spheres_write(const double *spheres, uint32_t n, double *entry, double *geom4);
 #endif /* __HIPCC__ */
 
 #endif /* BVH_BUILD_H */

@@ -577,6 +577,18 @@ struct PtPrevPoints
   uint64_t n, n_triangles;
 };
 
+/* The same with moved spheres (rt_hip.h, rt_hip_prev_points_moved; pt_prev_points_moved in pt_kernel.hip): the hits' object as
+ * well, and the previous and current spheres, 4 doubles each (cx cy cz radius; may be null with n_spheres 0).  spheres_static:
+ * the call gave no previous spheres and n_spheres 0 -- a sphere hit copies its point, as pt_prev_points does. */
+struct PtPrevPointsMoved
+{
+  const uint32_t *status, *prim, *object;
+  const double *bary, *point, *positions, *spheres_prev, *spheres_cur;
+  double *out;
+  uint64_t n, n_triangles, n_spheres;
+  uint32_t spheres_static;
+};
+
 /* One guided upsampling (rt_hip.h, rt_hip_upsample; pt_upsample in pt_kernel.hip): the low frame's row-major wl x hl images
  * (colour, normal, depth, hits; albedo with demodulate, object with object_edges), the guides of the w x h frame (the same fields
  * without a colour), and the outputs -- out_rgb always, the bytes and the confidence where wanted. */
@@ -714,6 +726,7 @@ hipError_t pt_launch_reproject(const PtReproject &args, hipStream_t stream);
 hipError_t pt_launch_reproject_points(const PtReproject &args, const double *prev_points, hipStream_t stream);
 /* the previous points of query hits: one launch, an entry per lane, on `stream` (n >= 1) */
 hipError_t pt_launch_prev_points(const PtPrevPoints &args, hipStream_t stream);
+hipError_t pt_launch_prev_points_moved(const PtPrevPointsMoved &args, hipStream_t stream);
 /* guided upsampling: one launch, a 16 x 16 block of the high frame's pixels per workgroup, on `stream` */
 hipError_t pt_launch_upsample(const PtUpsample &args, hipStream_t stream);
 hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,

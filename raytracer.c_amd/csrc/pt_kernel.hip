@@ -1702,6 +1702,54 @@ extern "C" __global__ __launch_bounds__(256) void pt_prev_points(const PtPrevPoi
   A.out[3 * i + 2] = oz;
 }
 
+/* ---- the same after the spheres moved too (rt_hip_prev_points_moved) --------------------------------------------------------------
+ * pt_prev_points with one more clause: a hit on sphere `object` rides that sphere's translation and uniform scale, from the
+ * current sphere (c, r) to the previous one (c', r'): s = r' / r, out_k = c'_k + (point_k - c_k) * s, fp64, unfused, in that
+ * order.  The two sphere records (4 doubles each) are the gather of such a lane.  A kernel of its own, so that pt_prev_points'
+ * listing stays what it was. */
+extern "C" __global__ __launch_bounds__(256) void pt_prev_points_moved(const PtPrevPointsMoved A)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= A.n)
+    return;
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+  double ox = qnan, oy = qnan, oz = qnan;
+  if (A.status[i] == 1u)
+  {
+    const uint32_t prim = A.prim[i];
+    if (prim == 0xFFFFFFFFu)
+    {
+      const uint32_t obj = A.object[i];
+      if (A.spheres_static != 0u)
+      { /* no spheres given: none moved, the point's own words (no arithmetic touches them) */
+        ox = A.point[3 * i + 0];
+        oy = A.point[3 * i + 1];
+        oz = A.point[3 * i + 2];
+      }
+      else if ((uint64_t)obj < A.n_spheres)
+      {
+        const double *was = A.spheres_prev + 4 * (size_t)obj, *now = A.spheres_cur + 4 * (size_t)obj;
+        const double s = was[3] / now[3];
+        ox = was[0] + (A.point[3 * i + 0] - now[0]) * s;
+        oy = was[1] + (A.point[3 * i + 1] - now[1]) * s;
+        oz = was[2] + (A.point[3 * i + 2] - now[2]) * s;
+      }
+    }
+    else if ((uint64_t)prim < A.n_triangles)
+    {
+      const double u = A.bary[2 * i + 0], v = A.bary[2 * i + 1];
+      const double w0 = (1.0 - u) - v;
+      const double *t = A.positions + 9 * (size_t)prim;
+      ox = (t[0] * w0 + t[3] * u) + t[6] * v;
+      oy = (t[1] * w0 + t[4] * u) + t[7] * v;
+      oz = (t[2] * w0 + t[5] * u) + t[8] * v;
+    }
+  }
+  A.out[3 * i + 0] = ox;
+  A.out[3 * i + 1] = oy;
+  A.out[3 * i + 2] = oz;
+}
+
 /* ---- guided upsampling (rt_hip_upsample): a full-size frame from a low-resolution render -----------------------------------
  * rt_hip.h states the arithmetic; this is it, operation for operation, in fp64 (-ffp-contract=off; the library's IEEE division).
  * A lane is a pixel of the HIGH frame, a workgroup a 16 x 16 block as pt_reproject's, no LDS.  The pixel's place in the low frame
@@ -2651,6 +2699,13 @@ hipError_t pt_launch_prev_points(const PtPrevPoints &args, hipStream_t stream)
 {
   const uint32_t blocks = (uint32_t)((args.n + 255u) / 256u);
   hipLaunchKernelGGL(pt_prev_points, dim3(blocks), dim3(256), 0, stream, args);
+  return hipGetLastError();
+}
+
+hipError_t pt_launch_prev_points_moved(const PtPrevPointsMoved &args, hipStream_t stream)
+{
+  const uint32_t blocks = (uint32_t)((args.n + 255u) / 256u);
+  hipLaunchKernelGGL(pt_prev_points_moved, dim3(blocks), dim3(256), 0, stream, args);
   return hipGetLastError();
 }
 

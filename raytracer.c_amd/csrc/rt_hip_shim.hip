@@ -284,6 +284,8 @@ struct RtHipScene
   /* ---- moving the triangles in place (rt_hip_scene_update_vertices) ---- */
   size_t blob_bytes = 0;     /* new positions must not lie inside the blob */
   double reach_spheres = 0;  /* the spheres' part of `reach`: joined with the vertices' again by every update */
+  double reach_triangles = 0; /* the vertices' part (max |vertex|; 0 without triangles): joined with the spheres' by rt_hip_scene_update_spheres */
+  bool force_wide = false;   /* PT_DEV_KERNELS, RT_HIP_FORCE_BIG=1: an OR on top of the wide_range the spheres give */
   mutable std::atomic<int> live_accums{0}; /* RtHipAccum objects on this scene: their plans hold the view, so no update */
   bool unusable = false;     /* an update failed after it had begun to write: only rt_hip_scene_destroy is allowed */
   /* the hierarchy's levels (BvhRefit::levels), made by the first update and kept: they depend on the topology alone */
@@ -362,17 +364,8 @@ void put_material(double *m, uint32_t flags, const double *color, const double *
   memcpy(&m[7], &bits, sizeof bits);
 }
 
-/* One sphere's record of entry_src (pt_device.h): cx cy cz, r*r, |c| rounded up, 0. */
-void sphere_entry(const double *center, double radius, double *g)
-{
-  g[0] = center[0];
-  g[1] = center[1];
-  g[2] = center[2];
-  g[3] = radius * radius; /* raytracer.c:87 */
-  /* |c|, rounded up: feeds the conservative phase-1 thresholds only, never a result */
-  g[4] = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) * (1.0 + 1e-12);
-  g[5] = 0.0; /* a sphere is rejected when its centre is behind the origin at all (raytracer.c:84) */
-}
+/* One sphere's record of entry_src (pt_device.h), its geom4 copy and every scalar a scene derives from its spheres:
+ * scene_sphere_* (bvh_build.h), one text with the device's (rt_hip_scene_update_spheres). */
 
 /* One triangle's records: scene_triangle_entry / scene_triangle_normal (bvh_build.h), one text with the device's. */
 
@@ -392,7 +385,7 @@ int acquire_tables(const RtHipScene *scene, double near_R, hipStream_t stream, f
   std::lock_guard<std::mutex> lock(scene->table_mutex);
   std::vector<TableSet> &tables = scene->tables;
   if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an update of its vertices failed half way (rt_hip_scene_update_vertices)");
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an update of its vertices or spheres failed half way (rt_hip_scene_update_*)");
   for (size_t k = 0; k < tables.size(); k++)
     if (tables[k].near_R == near_R)
     {
@@ -828,6 +821,20 @@ int check_adapt(const RtHipAdaptParams *p)
   return RT_HIP_OK;
 }
 
+/* the scalars of bvh_build.h into the scene -- at creation, and after every update of the spheres (`reach` is the caller's) */
+void take_sphere_bounds(RtHipScene *sc, const SceneSphereBounds &sb)
+{
+  sc->view.wide_range = (sb.wide_range || sc->force_wide) ? 1u : 0u;
+  sc->max_center = sb.max_center;
+  sc->n_big = (int)sb.n_big;
+  for (int k = 0; k < SCENE_SPHERE_WALLS; k++)
+  {
+    sc->big_r[k] = sb.big_r[k];
+    sc->big_c[k] = sb.big_c[k];
+  }
+  sc->reach_spheres = sb.reach_spheres;
+}
+
 int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
                       int device, uint32_t bvh_builder, RtHipScene **out_scene)
 {
@@ -849,7 +856,7 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     any_checker |= (spheres[i].flags & PT_FLAG_CHECKER) != 0;
     if (!material_ok(spheres[i].color, spheres[i].emission))
       return fail(RT_HIP_EINVAL, "sphere %zu: colour must be finite and >= 0, emission finite", i);
-    if (!(std::fabs(spheres[i].radius) >= 1e-100) || !(std::fabs(spheres[i].radius) <= 1e100))
+    if (!scene_sphere_radius_ok(spheres[i].radius))
       return fail(RT_HIP_ELIMIT, "sphere %zu: |radius| %g outside [1e-100, 1e100]", i, spheres[i].radius);
   }
   for (size_t m = 0; m < n_meshes; m++)
@@ -868,8 +875,7 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   const size_t n_mat = n_spheres + n_meshes;
 
   /* ---- build the kernel layout on the host (pt_device.h) ---- */
-  double reach = 0, reach_spheres = 0, max_emission = 0, max_center = 0;
-  bool wide_range = false;
+  double reach = 0, reach_triangles = 0, max_emission = 0;
   for (size_t i = 0; i < n_spheres; i++)
     max_emission = std::fmax(max_emission, max_abs3(spheres[i].emission));
   for (size_t m = 0; m < n_meshes; m++)
@@ -882,18 +888,19 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     memcpy(&craw[3 * i], spheres[i].color, 3 * sizeof(double));
   for (size_t m = 0; m < n_meshes; m++)
     memcpy(&craw[3 * (n_spheres + m)], meshes[m].color, 3 * sizeof(double));
-  for (size_t i = 0; i < n_spheres; i++)
+  /* the spheres' records and what the scene derives from them: bvh_build.h, as an update of the spheres derives it again */
+  SceneSphereBounds sb;
   {
-    double *g = &geom[PT_ENTRY_SRC_STRIDE * i];
-    sphere_entry(spheres[i].center, spheres[i].radius, g);
-    memcpy(&geom4[PT_GEOM_STRIDE * i], g, PT_GEOM_STRIDE * sizeof(double));
-    max_center = std::fmax(max_center, g[4]);
-    wide_range |= !(g[4] <= 1e17) || !(std::fabs(spheres[i].radius) <= 1e17);
-    if (std::fabs(spheres[i].radius) < 1000.0) /* wall-sized spheres would only loosen the filter */
-      reach = std::fmax(reach, g[4] + std::fabs(spheres[i].radius));
-    put_material(&mat[PT_MAT_STRIDE * i], spheres[i].flags, spheres[i].color, spheres[i].emission);
+    std::vector<double> in(SCENE_SPHERE_IN * n_spheres);
+    for (size_t i = 0; i < n_spheres; i++)
+    {
+      memcpy(&in[SCENE_SPHERE_IN * i], spheres[i].center, 3 * sizeof(double));
+      in[SCENE_SPHERE_IN * i + 3] = spheres[i].radius;
+      put_material(&mat[PT_MAT_STRIDE * i], spheres[i].flags, spheres[i].color, spheres[i].emission);
+    }
+    scene_sphere_bounds(in.data(), n_spheres, geom.data(), geom4.data(), &sb);
   }
-  reach_spheres = reach;
+  reach = sb.reach_spheres;
   size_t t = 0;
   for (size_t m = 0; m < n_meshes; m++)
     for (size_t k = 0; k < 3 * meshes[m].num_triangles; k++)
@@ -910,6 +917,7 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
        * near_R = 1.5 (|camera| + reach) + 1 >= 1e15 as "not a usable finite bound" -- so every vertex a kernel ever sees
        * lies within 6.7e14 of the origin, which is what exact_triangle's UNSCALED division rests on, see below) */
       reach = std::fmax(reach, len);
+      reach_triangles = std::fmax(reach_triangles, len);
     }
   for (size_t m = 0; m < n_meshes; m++)
   {
@@ -1144,24 +1152,12 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     /* development knob (tools/many_spheres.py): RT_HIP_FORCE_BIG=1 sends a small scene to the scalar-table _big kernels,
      * which it otherwise reaches only through a centre or radius beyond 1e17 */
     const char *fb = getenv("RT_HIP_FORCE_BIG");
-    if (fb && fb[0] == '1')
-      wide_range = true;
+    sc->force_wide = fb && fb[0] == '1';
   }
 #endif
-  sc->view.wide_range = wide_range ? 1u : 0u;
-  sc->max_center = max_center;
-  {
-    int nb = 0;
-    while (nb < 8 && (size_t)nb < n_spheres && std::fabs(spheres[nb].radius) >= 1000.0 && std::fabs(spheres[nb].radius) <= 1e17)
-    {
-      sc->big_r[nb] = std::fabs(spheres[nb].radius);
-      sc->big_c[nb] = geom[PT_ENTRY_SRC_STRIDE * (size_t)nb + 4];
-      nb++;
-    }
-    sc->n_big = nb & ~1; /* whole pairs */
-  }
+  take_sphere_bounds(sc, sb);
   sc->reach = reach;
-  sc->reach_spheres = reach_spheres;
+  sc->reach_triangles = reach_triangles;
   sc->blob_bytes = total;
   sc->max_emission = max_emission;
   sc->any_mirror_glass = any_mirror_glass;
@@ -1699,38 +1695,42 @@ struct CtxGuard
 };
 
 /* Everything that defines the scene, field by field (struct padding is not part of the scene), as runs of bytes handed
- * to `f(ptr, n, vertices)` in a fixed order (vertices: the run is a mesh's RtHipVertex array).  The cached context keeps the concatenation (ImageCtx::scene_bytes) and is reused only
+ * to `f(ptr, n, kind)` in a fixed order (kind: RUN_VERTICES, the run is a mesh's RtHipVertex array; RUN_SPHERE, a sphere's ten doubles, radius and centre first; RUN_OTHER).  The cached context keeps the concatenation (ImageCtx::scene_bytes) and is reused only
  * while a call's scene equals it byte for byte: scene_matches() compares run by run (memcmp, stopping at the first
  * difference) against the kept copy -- no per-call serialisation, no hashing: a frame of config 5's mesh used to rebuild
  * and hash 1.2 MB on the host inside every rt_hip_render_image() call (round-3 advisor finding). */
+enum { RUN_OTHER = 0, RUN_VERTICES = 1, RUN_SPHERE = 2 };
 template <class F>
 void scene_walk(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, F &&f)
 {
-  f(&n_spheres, sizeof n_spheres, false);
-  f(&n_meshes, sizeof n_meshes, false);
+  f(&n_spheres, sizeof n_spheres, RUN_OTHER);
+  f(&n_meshes, sizeof n_meshes, RUN_OTHER);
   for (size_t i = 0; i < n_spheres; i++)
   {
-    f(&spheres[i].flags, sizeof spheres[i].flags, false);
-    f(&spheres[i].radius, sizeof(double) * 10, false); /* radius, center, color, emission are contiguous doubles */
+    f(&spheres[i].flags, sizeof spheres[i].flags, RUN_OTHER);
+    f(&spheres[i].radius, sizeof(double) * 10, RUN_SPHERE); /* radius, center, color, emission are contiguous doubles */
   }
   for (size_t m = 0; m < n_meshes; m++)
   {
-    f(&meshes[m].flags, sizeof meshes[m].flags, false);
-    f(meshes[m].color, sizeof(double) * 6, false); /* color, emission */
-    f(&meshes[m].num_triangles, sizeof meshes[m].num_triangles, false);
+    f(&meshes[m].flags, sizeof meshes[m].flags, RUN_OTHER);
+    f(meshes[m].color, sizeof(double) * 6, RUN_OTHER); /* color, emission */
+    f(&meshes[m].num_triangles, sizeof meshes[m].num_triangles, RUN_OTHER);
     if (meshes[m].vertices)
-      f(meshes[m].vertices, meshes[m].num_triangles * 3 * sizeof(RtHipVertex), true);
+      f(meshes[m].vertices, meshes[m].num_triangles * 3 * sizeof(RtHipVertex), RUN_VERTICES);
   }
 }
 
-enum SceneMatch { SCENE_DIFFERS = 0, SCENE_SAME = 1, SCENE_MOVED = 2 /* equal but for vertex positions */ };
+/* SCENE_MOVED: equal but for vertex positions (MOVED_VERTICES) and sphere centres and radii (MOVED_SPHERES), as *moved says */
+enum SceneMatch { SCENE_DIFFERS = 0, SCENE_SAME = 1, SCENE_MOVED = 2 };
+enum { MOVED_VERTICES = 1, MOVED_SPHERES = 2 };
 
 SceneMatch scene_matches(const std::vector<unsigned char> &kept, const RtHipSphere *spheres, size_t n_spheres,
-                         const RtHipMesh *meshes, size_t n_meshes)
+                         const RtHipMesh *meshes, size_t n_meshes, int *moved_what)
 {
   size_t at = 0;
-  bool same = true, moved = false;
-  scene_walk(spheres, n_spheres, meshes, n_meshes, [&](const void *p, size_t n, bool vertices) {
+  bool same = true;
+  int moved = 0;
+  scene_walk(spheres, n_spheres, meshes, n_meshes, [&](const void *p, size_t n, int kind) {
     if (!same)
       return;
     if (n > kept.size() - at)
@@ -1740,15 +1740,19 @@ SceneMatch scene_matches(const std::vector<unsigned char> &kept, const RtHipSphe
       /* a vertex run may differ in positions; the tex coordinates behind each position must not */
       const unsigned char *a = kept.data() + at, *b = static_cast<const unsigned char *>(p);
       const size_t tex = offsetof(RtHipVertex, tex);
-      same = vertices;
-      for (size_t v = 0; same && v < n / sizeof(RtHipVertex); v++)
-        same = memcmp(a + v * sizeof(RtHipVertex) + tex, b + v * sizeof(RtHipVertex) + tex, sizeof(RtHipVertex) - tex) == 0;
-      moved = true;
+      same = kind != RUN_OTHER;
+      if (kind == RUN_VERTICES)
+        for (size_t v = 0; same && v < n / sizeof(RtHipVertex); v++)
+          same = memcmp(a + v * sizeof(RtHipVertex) + tex, b + v * sizeof(RtHipVertex) + tex, sizeof(RtHipVertex) - tex) == 0;
+      else if (kind == RUN_SPHERE) /* the radius and the centre may differ; the colour and the emission behind them must not */
+        same = memcmp(a + 4 * sizeof(double), b + 4 * sizeof(double), n - 4 * sizeof(double)) == 0;
+      moved |= kind == RUN_VERTICES ? MOVED_VERTICES : MOVED_SPHERES;
     }
     at += n;
   });
   if (!same || at != kept.size())
     return SCENE_DIFFERS;
+  *moved_what = moved;
   return moved ? SCENE_MOVED : SCENE_SAME;
 }
 
@@ -1756,7 +1760,7 @@ void scene_serialise(std::vector<unsigned char> &bytes, const RtHipSphere *spher
                      size_t n_meshes)
 {
   bytes.clear();
-  scene_walk(spheres, n_spheres, meshes, n_meshes, [&](const void *p, size_t n, bool) {
+  scene_walk(spheres, n_spheres, meshes, n_meshes, [&](const void *p, size_t n, int) {
     const unsigned char *b = static_cast<const unsigned char *>(p);
     bytes.insert(bytes.end(), b, b + n);
   });
@@ -1776,24 +1780,44 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
   if (c.G == G && c.W == W && c.H == H && c.force_comm == force_comm && (int)c.dev.size() == G && c.phys == phys &&
       c.bvh_builder == g_bvh_builder)
   {
-    const SceneMatch match = scene_matches(c.scene_bytes, spheres, n_spheres, meshes, n_meshes);
+    int moved = 0;
+    const SceneMatch match = scene_matches(c.scene_bytes, spheres, n_spheres, meshes, n_meshes, &moved);
     if (match == SCENE_SAME)
       return RT_HIP_OK;
     if (match == SCENE_MOVED && g_scene_updates)
-    { /* only vertex positions differ: every device's scene takes them in place; a failure drops the context (CtxGuard) */
-      size_t n_tri = 0;
-      for (size_t m = 0; m < n_meshes; m++)
-        n_tri += meshes[m].num_triangles;
-      std::vector<double> pos(9 * n_tri);
-      size_t at = 0;
-      for (size_t m = 0; m < n_meshes; m++)
-        for (size_t k = 0; k < 3 * meshes[m].num_triangles; k++, at += 3)
-          memcpy(&pos[at], meshes[m].vertices[k].pos, 3 * sizeof(double));
-      for (int g = 0; g < G; g++)
+    { /* only vertex positions, sphere centres and radii differ: every device's scene takes them in place, by the update of each
+       * kind that differs; a failure drops the context (CtxGuard) */
+      if (moved & MOVED_VERTICES)
       {
-        const int rc = rt_hip_scene_update_vertices_host(c.dev[g].scene, pos.data(), n_tri);
-        if (rc)
-          return rc;
+        size_t n_tri = 0;
+        for (size_t m = 0; m < n_meshes; m++)
+          n_tri += meshes[m].num_triangles;
+        std::vector<double> pos(9 * n_tri);
+        size_t at = 0;
+        for (size_t m = 0; m < n_meshes; m++)
+          for (size_t k = 0; k < 3 * meshes[m].num_triangles; k++, at += 3)
+            memcpy(&pos[at], meshes[m].vertices[k].pos, 3 * sizeof(double));
+        for (int g = 0; g < G; g++)
+        {
+          const int rc = rt_hip_scene_update_vertices_host(c.dev[g].scene, pos.data(), n_tri);
+          if (rc)
+            return rc;
+        }
+      }
+      if (moved & MOVED_SPHERES)
+      {
+        std::vector<double> sph(SCENE_SPHERE_IN * n_spheres);
+        for (size_t i = 0; i < n_spheres; i++)
+        {
+          memcpy(&sph[SCENE_SPHERE_IN * i], spheres[i].center, 3 * sizeof(double));
+          sph[SCENE_SPHERE_IN * i + 3] = spheres[i].radius;
+        }
+        for (int g = 0; g < G; g++)
+        {
+          const int rc = rt_hip_scene_update_spheres_host(c.dev[g].scene, sph.data(), n_spheres);
+          if (rc)
+            return rc;
+        }
       }
       scene_serialise(c.scene_bytes, spheres, n_spheres, meshes, n_meshes);
       c.updates++;
@@ -2598,6 +2622,86 @@ int prev_points_host_impl(const RtHipHits *h_hits, uint64_t n, const double *h_p
     return rc;
   const RtHipHits d = {A.at<uint32_t>(status), nullptr, nullptr, A.at<uint32_t>(prim), A.at<double>(point), nullptr, A.at<double>(bary), nullptr};
   rc = prev_points_launch(&d, n, A.at<double>(positions), n_triangles, A.at<double>(point), nullptr);
+  return rc ? rc : A.download();
+}
+
+/* ---- previous points with moved spheres (rt_hip.h, rt_hip_prev_points_moved*) ------------------------------------------------
+ * rt_hip_prev_points' checks, then the spheres': object is required, and both sphere arrays with a non-zero count.  One launch of
+ * pt_prev_points_moved (pt_kernel.hip), no workspace. */
+int check_prev_points_moved(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, const double *spheres_prev,
+                            const double *spheres_cur, size_t n_spheres, const double *points)
+{
+  const int rc = check_prev_points(hits, n, positions, n_triangles, points);
+  if (rc)
+    return rc;
+  if (!hits->object)
+    return fail(RT_HIP_EINVAL, "the hits' object is required");
+  if (n_spheres > SIZE_MAX / 32u)
+    return fail(RT_HIP_EINVAL, "n_spheres is out of range");
+  if (n_spheres && (!spheres_prev || !spheres_cur))
+    return fail(RT_HIP_EINVAL, "the previous and the current spheres are required (4 doubles per sphere)");
+  const std::pair<const void *, size_t> in[3] = {{hits->object, 4u * n}, {n_spheres ? spheres_prev : nullptr, 32u * n_spheres},
+                                                 {n_spheres ? spheres_cur : nullptr, 32u * n_spheres}};
+  for (int k = 0; k < 3; k++)
+    if (ranges_overlap(points, 24u * n, in[k].first, in[k].second))
+      return fail(RT_HIP_EINVAL, "the output overlaps an input (only d_points == d_hits->point is allowed)");
+  return RT_HIP_OK;
+}
+
+int prev_points_moved_launch(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, const double *spheres_prev,
+                             const double *spheres_cur, size_t n_spheres, bool spheres_static, double *points, hipStream_t stream)
+{
+  if (n == 0)
+    return RT_HIP_OK;
+  PtPrevPointsMoved A = {};
+  A.status = hits->status;
+  A.prim = hits->prim;
+  A.object = hits->object;
+  A.bary = hits->bary;
+  A.point = hits->point;
+  A.positions = positions;
+  A.spheres_prev = spheres_prev;
+  A.spheres_cur = spheres_cur;
+  A.out = points;
+  A.n = n;
+  A.n_triangles = n_triangles;
+  A.n_spheres = n_spheres;
+  A.spheres_static = spheres_static ? 1u : 0u; /* d_spheres_prev == NULL with n_spheres == 0: rt_hip_prev_points itself */
+  const hipError_t e = pt_launch_prev_points_moved(A, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "pt_prev_points_moved launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int prev_points_moved_host_impl(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles,
+                                const double *h_spheres_prev, const double *h_spheres_cur, size_t n_spheres, int device, double *h_points)
+{
+  int rc = check_prev_points_moved(h_hits, n, h_positions, n_triangles, h_spheres_prev, h_spheres_cur, n_spheres, h_points);
+  if (rc)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  if (n == 0)
+    return RT_HIP_OK;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  StageArena A;
+  const int status = A.part(4u * n, h_hits->status);
+  const int prim = A.part(4u * n, h_hits->prim);
+  const int object = A.part(4u * n, h_hits->object);
+  const int bary = A.part(16u * n, h_hits->bary);
+  const int point = A.part(24u * n, h_hits->point, h_points);
+  const int positions = A.part(72u * n_triangles, h_positions, nullptr, n_triangles != 0);
+  const int sprev = A.part(32u * n_spheres, h_spheres_prev, nullptr, n_spheres != 0);
+  const int scur = A.part(32u * n_spheres, h_spheres_cur, nullptr, n_spheres != 0);
+  rc = A.stage();
+  if (rc)
+    return rc;
+  const RtHipHits d = {A.at<uint32_t>(status), nullptr, A.at<uint32_t>(object), A.at<uint32_t>(prim), A.at<double>(point), nullptr, A.at<double>(bary), nullptr};
+  rc = prev_points_moved_launch(&d, n, A.at<double>(positions), n_triangles, A.at<double>(sprev), A.at<double>(scur), n_spheres,
+                                !h_spheres_prev && n_spheres == 0, A.at<double>(point), nullptr);
   return rc ? rc : A.download();
 }
 
@@ -3468,7 +3572,8 @@ int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_trian
   scene->mesh_R = mesh_R;
   scene->mesh_c_norm = std::sqrt(mesh_c[0] * mesh_c[0] + mesh_c[1] * mesh_c[1] + mesh_c[2] * mesh_c[2]) * (1.0 + 1e-12);
   scene->view.mesh_round = mesh_round ? 1u : 0u;
-  scene->reach = std::fmax(scene->reach_spheres, chk.max_len);
+  scene->reach_triangles = chk.max_len; /* kept: a later update of the spheres joins it with their part again */
+  scene->reach = std::fmax(scene->reach_spheres, scene->reach_triangles);
   scene->hull_flags = false; /* k_update_triangles cleared the bits */
   if (n <= PT_HULL_MAX_TRIS && mesh_R >= 0 && mesh_R < 1e150)
   {
@@ -3487,7 +3592,143 @@ int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_trian
   return RT_HIP_OK;
 }
 
+/* ---- moving the spheres in place: the sphere records of entry_src and geom4 rewritten by k_update_spheres (scene_update.hip), then
+ * the scalars scene_create_impl derives from the spheres, by bvh_build.h's one text.  The same discipline as above: the
+ * kernel's first run writes nothing of the scene (the maxima, and whether every radius is acceptable); only when no refusal is
+ * left does its second run write.  The table sets go stale as after a vertex update: the filter is made of these records. */
+int scene_update_spheres_impl(RtHipScene *scene, const double *spheres, size_t n_spheres, bool on_host)
+{
+  if (!scene || !spheres)
+    return fail(RT_HIP_EINVAL, "scene and spheres are required");
+  if (scene->unusable)
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  const size_t n = scene->view.n_spheres;
+  if (n == 0)
+    return fail(RT_HIP_EINVAL, "the scene has no spheres to move");
+  if (n_spheres != n)
+    return fail(RT_HIP_EINVAL, "%zu spheres given, the scene has %zu: an update keeps the count", n_spheres, n);
+  const size_t in_bytes = SCENE_SPHERE_IN * 8 * n;
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  if (!on_host)
+  {
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof attr);
+    if (hipPointerGetAttributes(&attr, spheres) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != scene->device)
+    {
+      (void)hipGetLastError();
+      return fail(RT_HIP_EINVAL, "d_spheres is not device memory of the scene's device %d", scene->device);
+    }
+    const char *p = reinterpret_cast<const char *>(spheres), *blob = static_cast<const char *>(scene->blob);
+    if (p + in_bytes > blob && p < blob + scene->blob_bytes)
+      return fail(RT_HIP_EINVAL, "d_spheres lies inside the scene");
+  }
+  std::lock_guard<std::mutex> lock(scene->table_mutex);
+  if (scene->live_accums.load() > 0)
+    return fail(RT_HIP_EINVAL, "%d accumulation(s) on this scene are alive: destroy them before its spheres move", scene->live_accums.load());
+  for (const TableSet &t : scene->tables)
+    if (t.users > 0)
+      return fail(RT_HIP_EINVAL, "a launch of this scene is being submitted");
+  const auto t0 = std::chrono::steady_clock::now();
+
+  /* ---- the one workspace: the reductions' words, then (host form) the staged spheres ---- */
+  DeviceBuffer ws;
+  const size_t words_bytes = 256;
+  static_assert(SCENE_SPHERE_WORDS * 8 <= 256, "the reductions' words");
+  if (ws.alloc(words_bytes + (on_host ? in_bytes : 0)) != hipSuccess)
+    return fail(RT_HIP_ENOMEM, "update workspace (%zu KB)", (words_bytes + (on_host ? in_bytes : 0)) >> 10);
+  unsigned long long *words = ws.at<unsigned long long>();
+  const double *d_in = spheres;
+  if (on_host)
+  {
+    HIP_TRY(hipMemcpy(ws.at<char>(words_bytes), spheres, in_bytes, hipMemcpyHostToDevice));
+    d_in = ws.at<double>(words_bytes);
+  }
+  SceneSphereBounds sb;
+  bool radii_ok = false;
+  HIP_TRY(scene_update_spheres_check(d_in, (uint32_t)n, words, &sb, &radii_ok));
+  if (!radii_ok) /* scene_create_impl's rule */
+    return fail(RT_HIP_ELIMIT, "a sphere's |radius| is outside [1e-100, 1e100]");
+  /* the leading walls: the first records read back, and bvh_build.h's text on the host */
+  {
+    double lead[SCENE_SPHERE_IN * SCENE_SPHERE_WALLS];
+    const size_t n_lead = n < SCENE_SPHERE_WALLS ? n : (size_t)SCENE_SPHERE_WALLS;
+    if (on_host)
+      memcpy(lead, spheres, SCENE_SPHERE_IN * 8 * n_lead);
+    else
+      HIP_TRY(hipMemcpy(lead, d_in, SCENE_SPHERE_IN * 8 * n_lead, hipMemcpyDeviceToHost));
+    scene_sphere_leading_walls(lead, n_lead, &sb);
+  }
+
+  /* ---- no launch may still read what is about to change ---- */
+  for (TableSet &t : scene->tables)
+  {
+    HIP_TRY(hipEventSynchronize(t.built));
+    for (auto &r : t.readers)
+      HIP_TRY(hipEventSynchronize(r.second));
+  }
+
+  /* ---- writing begins ---- */
+  for (TableSet &t : scene->tables)
+    t.near_R = -1.0; /* the filter is rebuilt by the next launch (acquire_tables) */
+  auto broke = [&](hipError_t e, const char *what) {
+    (void)hipGetLastError();
+    scene->unusable = true;
+    return fail(RT_HIP_ERUNTIME, "%s: %s; the scene is unusable now (destroy it)", what, hipGetErrorString(e));
+  };
+  hipError_t e = scene_update_spheres_write(d_in, (uint32_t)n, const_cast<double *>(scene->view.entry_src),
+                                            const_cast<double *>(scene->view.geom4));
+  if (e != hipSuccess)
+    return broke(e, "updating the sphere records");
+  e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess)
+    return broke(e, "waiting for the update");
+  take_sphere_bounds(scene, sb);
+  scene->reach = std::fmax(scene->reach_spheres, scene->reach_triangles);
+  scene->updates++;
+  scene->last_update_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RT_HIP_OK;
+}
+
 } // namespace
+
+int rt_hip_scene_update_spheres(RtHipScene *scene, const double *d_spheres, size_t n_spheres)
+{
+  return guarded("rt_hip_scene_update_spheres", [&] { return scene_update_spheres_impl(scene, d_spheres, n_spheres, false); });
+}
+
+int rt_hip_scene_update_spheres_host(RtHipScene *scene, const double *h_spheres, size_t n_spheres)
+{
+  return guarded("rt_hip_scene_update_spheres_host", [&] { return scene_update_spheres_impl(scene, h_spheres, n_spheres, true); });
+}
+
+int rt_hip_scene_read_spheres(const RtHipScene *scene, double *entry, double *geom4)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_read_spheres: scene is NULL");
+  const size_t n = scene->view.n_spheres;
+  if (n == 0)
+    return RT_HIP_OK;
+  DeviceScope on(scene->device);
+  HIP_TRY(on.status);
+  if (entry) HIP_TRY(hipMemcpy(entry, scene->view.entry_src, PT_ENTRY_SRC_STRIDE * 8 * n, hipMemcpyDeviceToHost));
+  if (geom4) HIP_TRY(hipMemcpy(geom4, scene->view.geom4, PT_GEOM_STRIDE * 8 * n, hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
+int rt_hip_scene_sphere_bounds(const RtHipScene *scene, double *reach_spheres, double *max_center, uint32_t *wide_range, uint32_t *n_big,
+                               double big_r[8], double big_c[8])
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_sphere_bounds: scene is NULL");
+  if (reach_spheres) *reach_spheres = scene->reach_spheres;
+  if (max_center) *max_center = scene->max_center;
+  if (wide_range) *wide_range = scene->view.wide_range;
+  if (n_big) *n_big = (uint32_t)scene->n_big;
+  if (big_r) memcpy(big_r, scene->big_r, sizeof scene->big_r);
+  if (big_c) memcpy(big_c, scene->big_c, sizeof scene->big_c);
+  return RT_HIP_OK;
+}
 
 int rt_hip_scene_update_vertices(RtHipScene *scene, const double *d_positions, size_t n_triangles)
 {
@@ -4141,7 +4382,7 @@ int rt_hip_selftest_intersect(int kind, const double *h_rays, const double *h_pr
         const double *p = h_prims + 4 * i;
         if (!(std::fabs(p[3]) >= 1e-100) || !(std::fabs(p[3]) <= 1e17))
           return fail(RT_HIP_ELIMIT, "sphere %zu: |radius| %g outside [1e-100, 1e17]", i, p[3]);
-        sphere_entry(p, p[3], e);
+        scene_sphere_entry(p, p[3], e, nullptr);
         memcpy(&prims[4 * i], e, 4 * sizeof(double));
       }
       else
@@ -4523,6 +4764,30 @@ int rt_hip_prev_points(const RtHipHits *d_hits, uint64_t n, const double *d_posi
 int rt_hip_prev_points_host(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles, int device, double *h_points)
 {
   return guarded("rt_hip_prev_points_host", [&] { return prev_points_host_impl(h_hits, n, h_positions, n_triangles, device, h_points); });
+}
+
+int rt_hip_prev_points_moved(const RtHipHits *d_hits, uint64_t n, const double *d_positions, size_t n_triangles, const double *d_spheres_prev,
+                             const double *d_spheres_cur, size_t n_spheres, double *d_points, void *stream)
+{
+  int rc = check_prev_points_moved(d_hits, n, d_positions, n_triangles, d_spheres_prev, d_spheres_cur, n_spheres, d_points);
+  if (rc || n == 0)
+    return rc;
+  int device = -1;
+  rc = device_of(d_points, "d_points", &device);
+  if (rc)
+    return rc;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  return prev_points_moved_launch(d_hits, n, d_positions, n_triangles, d_spheres_prev, d_spheres_cur, n_spheres,
+                                  !d_spheres_prev && n_spheres == 0, d_points, static_cast<hipStream_t>(stream));
+}
+
+int rt_hip_prev_points_moved_host(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles,
+                                  const double *h_spheres_prev, const double *h_spheres_cur, size_t n_spheres, int device, double *h_points)
+{
+  return guarded("rt_hip_prev_points_moved_host", [&] {
+    return prev_points_moved_host_impl(h_hits, n, h_positions, n_triangles, h_spheres_prev, h_spheres_cur, n_spheres, device, h_points);
+  });
 }
 
 /* k: the denoiser's; sigma_depth: the reprojection's depth tolerance (DESIGN, "`pt_upsample`") */

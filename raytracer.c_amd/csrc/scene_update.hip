@@ -9,6 +9,9 @@
  *   k_refit_level        one thread a child slot of one level's nodes: the box of an inner child from that node's two boxes;
  *                        launched level by level from the deepest, so every launch reads boxes an earlier one finished
  *   tri_geom_leaf        bvh_device_gather_leaf
+ * and a scene's spheres moved in place (rt_hip_scene_update_spheres; the contract is scene_spheres.h's scene_sphere_bounds):
+ *   k_update_spheres     one thread a sphere: the entry_src record and its geom4 copy (where an output is given), and the maxima
+ *                        the scene keeps of its spheres -- reach, max |centre|, wide range -- with "a radius is out of range"
  * 256 threads a workgroup, no scratch, no LDS; no kernel waits for another workgroup: a wave reduces by lane shuffles and hands
  * its result to one atomic max / min on a 64-bit key. */
 #include <hip/hip_runtime.h>
@@ -16,6 +19,7 @@
 #include <cstring>
 
 #include "bvh_build.h"
+#include "scene_spheres.h"
 
 namespace
 {
@@ -176,6 +180,45 @@ __global__ void __launch_bounds__(UPD_BLOCK) k_refit_level(SceneUpdateArrays s, 
   store_box(s.bvh_src + (size_t)node * PT_BVH_SRC_DOUBLES + 6 * c, box);
 }
 
+/* words[0] = key of reach_spheres, words[1] = key of max_center, words[2] = wide_range, words[3] = a radius is out of range.
+ * entry == nullptr: nothing but the words is written (the check before anything of the scene changes); words == nullptr: nothing
+ * is reduced (the write after it). */
+__global__ void __launch_bounds__(UPD_BLOCK) k_update_spheres(const double *__restrict__ spheres, uint32_t n, double *__restrict__ entry,
+                                                             double *__restrict__ geom4, unsigned long long *__restrict__ words)
+{
+  const uint32_t i = blockIdx.x * UPD_BLOCK + threadIdx.x;
+  double reach = 0.0, center = 0.0;
+  unsigned long long wide = 0, bad = 0;
+  if (i < n)
+  {
+    double s[SCENE_SPHERE_IN], g[PT_ENTRY_SRC_STRIDE], g4[PT_GEOM_STRIDE];
+    for (int k = 0; k < SCENE_SPHERE_IN; k++)
+      s[k] = spheres[SCENE_SPHERE_IN * (size_t)i + k];
+    scene_sphere_entry(s, s[3], g, g4);
+    if (entry)
+    {
+      for (int k = 0; k < PT_ENTRY_SRC_STRIDE; k++)
+        entry[PT_ENTRY_SRC_STRIDE * (size_t)i + k] = g[k];
+      for (int k = 0; k < PT_GEOM_STRIDE; k++)
+        geom4[PT_GEOM_STRIDE * (size_t)i + k] = g4[k];
+    }
+    reach = scene_sphere_reach_part(g, s[3]);
+    center = scene_sphere_center_part(g);
+    wide = scene_sphere_wide_part(g, s[3]);
+    bad = scene_sphere_radius_ok(s[3]) ? 0u : 1u;
+  }
+  if (!words)
+    return; /* the write run: the check run has reduced already (a kernel argument: the whole grid takes this way) */
+  const unsigned long long kr = wave_max(key_of(reach)), kc = wave_max(key_of(center)), kw = wave_max(wide), kb = wave_max(bad);
+  if ((threadIdx.x & 63) == 0)
+  {
+    atomicMax(&words[0], kr);
+    atomicMax(&words[1], kc);
+    atomicMax(&words[2], kw);
+    atomicMax(&words[3], kb);
+  }
+}
+
 #define UPD_TRY(expr)             \
   do                              \
   {                               \
@@ -242,4 +285,41 @@ hipError_t scene_update_refit(const SceneUpdateArrays &s, const uint32_t *by_lev
   }
   UPD_TRY(hipGetLastError());
   return bvh_device_gather_leaf(s.tri_geom, s.bvh_tri, s.n_tri, s.tri_geom_leaf);
+}
+
+/* ---- the sphere half ---- */
+namespace
+{
+hipError_t launch_update_spheres(const double *spheres, uint32_t n, double *entry, double *geom4, unsigned long long *words)
+{
+  if (words)
+  {
+    const unsigned long long h[SCENE_SPHERE_WORDS] = {key_of(0.0), key_of(0.0), 0, 0};
+    UPD_TRY(hipMemcpy(words, h, sizeof h, hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL(k_update_spheres, dim3((n + UPD_BLOCK - 1) / UPD_BLOCK), dim3(UPD_BLOCK), 0, nullptr, spheres, n, entry, geom4, words);
+  return hipGetLastError();
+}
+} // namespace
+
+hipError_t scene_update_spheres_check(const double *spheres, uint32_t n, unsigned long long *words, SceneSphereBounds *out, bool *radii_ok)
+{
+  if (!spheres || !words || !out || !radii_ok || n == 0)
+    return hipErrorInvalidValue;
+  UPD_TRY(launch_update_spheres(spheres, n, nullptr, nullptr, words));
+  unsigned long long h[SCENE_SPHERE_WORDS];
+  UPD_TRY(hipMemcpy(h, words, sizeof h, hipMemcpyDeviceToHost));
+  *out = SceneSphereBounds();
+  out->reach_spheres = double_of(h[0]);
+  out->max_center = double_of(h[1]);
+  out->wide_range = h[2] ? 1u : 0u;
+  *radii_ok = h[3] == 0;
+  return hipSuccess;
+}
+
+hipError_t scene_update_spheres_write(const double *spheres, uint32_t n, double *entry, double *geom4)
+{
+  if (!spheres || !entry || !geom4 || n == 0)
+    return hipErrorInvalidValue;
+  return launch_update_spheres(spheres, n, entry, geom4, nullptr);
 }

@@ -194,6 +194,11 @@ SHIM_SYMBOLS = {
     "rt_hip_scene_read_triangles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_scene_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 3), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_uint32)]),
+    "rt_hip_scene_update_spheres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rt_hip_scene_update_spheres_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rt_hip_scene_read_spheres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_scene_sphere_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint32), C.POINTER(C.c_double * 8), C.POINTER(C.c_double * 8)]),
     "rt_hip_set_scene_updates": (None, [C.c_int]),
     "rt_hip_cache_updates": (C.c_uint64, []),
     "rt_hip_scene_device": (C.c_int, [C.c_void_p]),
@@ -287,6 +292,10 @@ SHIM_SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_prev_points": (C.c_int, [C.POINTER(RtHipHits), C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rt_hip_prev_points_host": (C.c_int, [C.POINTER(RtHipHits), C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "rt_hip_prev_points_moved": (C.c_int, [C.POINTER(RtHipHits), C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p]),
+    "rt_hip_prev_points_moved_host": (C.c_int, [C.POINTER(RtHipHits), C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                C.c_size_t, C.c_int, C.c_void_p]),
     # rt_hip_reproject's arguments with the previous points after params
     "rt_hip_reproject_points": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(RtHipAov),
                                           C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(RtHipReprojectParams), C.c_void_p,

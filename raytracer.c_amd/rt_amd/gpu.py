@@ -136,8 +136,65 @@ class GpuScene:
             raise ValueError(f"update_vertices: shape ({n}, 3, 3) is expected, not {a.shape}")
         _check(self.shim.rt_hip_scene_update_vertices_host(self.handle, a.ctypes.data, n), "rt_hip_scene_update_vertices_host")
 
+    def spheres(self):
+        """the scene's spheres as they are now: a float64 (n_objects, 4) device tensor, cx cy cz radius in object order -- what the
+        scene was created from, or the last update_spheres() made THROUGH THIS OBJECT (a clone of its input: the scene itself keeps
+        r * r, not the radius, so they cannot be read back).  A caller that updates through the C ABI directly keeps its own copy:
+        this one does not see that update.  What Temporal.frame(prev_spheres=...) takes as "now".  Not to be written."""
+        if getattr(self, "_spheres", None) is None:
+            import numpy as np
+            a = np.array([[o.center.x, o.center.y, o.center.z, o.radius] for o in self.scene.objects[:self.scene.n_objects]],
+                         dtype=np.float64).reshape(-1, 4)
+            self._spheres = torch.from_numpy(a).to(torch.device("cuda", self.device))
+        return self._spheres
+
+    def update_spheres(self, spheres):
+        """Moves the scene's spheres in place (rt_hip.h, rt_hip_scene_update_spheres): centre and radius of EVERY sphere, shape
+        (n_objects, 4) -- cx cy cz radius, in object order -- as a float64 torch tensor on the scene's device (taken where it lies)
+        or a numpy array (staged by the shim).  Synchronous.  Records, derived scalars, kernel_name(), frames, bytes and counters
+        equal a freshly created scene's.  A Temporal keeps its history across the move when its next frame() is given the spheres
+        from before it (prev_spheres).  Open accumulations refuse the update.  self.scene keeps the spheres the scene was created
+        from; spheres() has the current ones."""
+        n = self.scene.n_objects
+        dev = torch.device("cuda", self.device)
+        if isinstance(spheres, torch.Tensor):
+            if spheres.dtype != torch.float64 or tuple(spheres.shape) != (n, 4):
+                raise ValueError(f"update_spheres: a float64 tensor of shape ({n}, 4) is expected")
+            t = spheres.contiguous()
+            if t.is_cuda:   # what produced the tensor on torch's current stream must be done: the shim works on the null stream
+                torch.cuda.current_stream(t.device).synchronize()
+            _check(self.shim.rt_hip_scene_update_spheres(self.handle, C.c_void_p(t.data_ptr()), n), "rt_hip_scene_update_spheres")
+            self._spheres = t.detach().clone()
+            return
+        import numpy as np
+        a = np.ascontiguousarray(spheres, dtype=np.float64)
+        if a.shape != (n, 4):
+            raise ValueError(f"update_spheres: shape ({n}, 4) is expected, not {a.shape}")
+        _check(self.shim.rt_hip_scene_update_spheres_host(self.handle, a.ctypes.data, n), "rt_hip_scene_update_spheres_host")
+        self._spheres = torch.from_numpy(a.copy()).to(dev)
+
+    def read_spheres(self):
+        """for tests: dict of numpy arrays as the kernels read them -- entry (n, 6: cx cy cz r^2 |c| 0), geom4 (n, 4)"""
+        import numpy as np
+        n = self.scene.n_objects
+        out = dict(entry=np.zeros((n, 6)), geom4=np.zeros((n, 4)))
+        _check(self.shim.rt_hip_scene_read_spheres(self.handle, *[out[k].ctypes.data if n else None for k in ("entry", "geom4")]),
+               "rt_hip_scene_read_spheres")
+        return out
+
+    def sphere_bounds(self):
+        """for tests: what the scene derives from its spheres -- {"reach_spheres", "max_center", "wide_range", "n_big", "big_r",
+        "big_c"} (the last two: tuples of 8, zero from n_big on)"""
+        reach, mc, wide, nb = C.c_double(0), C.c_double(0), C.c_uint32(0), C.c_uint32(0)
+        br, bc = (C.c_double * 8)(), (C.c_double * 8)()
+        _check(self.shim.rt_hip_scene_sphere_bounds(self.handle, C.byref(reach), C.byref(mc), C.byref(wide), C.byref(nb), C.byref(br),
+                                                    C.byref(bc)), "rt_hip_scene_sphere_bounds")
+        return {"reach_spheres": reach.value, "max_center": mc.value, "wide_range": bool(wide.value), "n_big": nb.value,
+                "big_r": tuple(br), "big_c": tuple(bc)}
+
     def update_info(self):
-        """{"updates": how many update_vertices() the scene has taken, "last_seconds": the host-clock time of the last}"""
+        """{"updates": how many update_vertices() and update_spheres() the scene has taken, "last_seconds": the host-clock time of
+        the last}"""
         k, s = C.c_uint64(0), C.c_double(0)
         _check(self.shim.rt_hip_scene_update_info(self.handle, C.byref(k), C.byref(s)), "rt_hip_scene_update_info")
         return {"updates": k.value, "last_seconds": s.value}
@@ -778,6 +835,83 @@ def prev_points(hits, positions, out=None):
     return out
 
 
+def _sphere_pair(name, spheres_prev, spheres_cur, check):
+    """(n_spheres, prev, cur) of the two sphere arrays of prev_points_moved*(): both None, or both float64 (n, 4)"""
+    if spheres_prev is None and spheres_cur is None:
+        return 0, None, None
+    if spheres_prev is None or spheres_cur is None:
+        raise ValueError(f"{name}(): spheres_prev and spheres_cur go together")
+    prev, cur = check(spheres_prev), check(spheres_cur)
+    if prev.shape != cur.shape:
+        raise ValueError(f"{name}(): spheres_prev and spheres_cur must have the same shape")
+    return int(prev.shape[0]), prev, cur
+
+
+def prev_points_moved(hits, positions, spheres_prev, spheres_cur, out=None):
+    """rt_hip_prev_points_moved on torch device tensors, asynchronous on torch's current stream: prev_points() across an
+    update_spheres as well.  hits needs object too; spheres_prev / spheres_cur: float64 (n_spheres, 4), cx cy cz radius in object
+    order, the spheres at the previous frame and now (both None: no sphere moved, prev_points() itself).  A hit on a sphere rides
+    its translation and uniform scale; a sphere hit whose object is outside the arrays gives NaN."""
+    st = hits["status"]
+    dev, n = st.device, int(st.numel())
+    h = abi.RtHipHits()
+    for f in ("status", "prim", "object", "bary", "point"):
+        dtype, k = abi.HIT_SHAPES[f]
+        t = hits[f]
+        if t.device != dev or not t.is_contiguous() or t.numel() != n * k or t.dtype != (torch.float64 if dtype == "float64" else torch.int32):
+            raise ValueError(f"prev_points_moved(): hits[{f!r}] must be a contiguous tensor of {n} x {k} values as a query returns it")
+        setattr(h, f, t.data_ptr() if n else 1)
+    n_tri, pos = 0, None
+    if positions is not None:
+        if positions.dtype != torch.float64 or positions.dim() != 3 or tuple(positions.shape[1:]) != (3, 3) or positions.device != dev:
+            raise ValueError("prev_points_moved(): positions must be a float64 tensor of shape (n_triangles, 3, 3) on the hits' device")
+        pos = positions.contiguous()
+        n_tri = int(pos.shape[0])
+
+    def check(t):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 4 or t.device != dev:
+            raise ValueError("prev_points_moved(): the spheres must be float64 tensors of shape (n_spheres, 4) on the hits' device")
+        return t.contiguous()
+    n_sph, sprev, scur = _sphere_pair("prev_points_moved", spheres_prev, spheres_cur, check)
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    elif out.device != dev or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 3 * n:
+        raise ValueError(f"prev_points_moved(): out must be a contiguous float64 tensor of {n} x 3 values on the hits' device")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    given = sprev is not None   # (an empty pair is still "given": a sphere hit then has no sphere to ride, NaN)
+    _check(abi.load_shim().rt_hip_prev_points_moved(C.byref(h), n, C.c_void_p(pos.data_ptr()) if n_tri else None, n_tri,
+                                                    C.c_void_p(sprev.data_ptr() if n_sph else 1) if given else None,
+                                                    C.c_void_p(scur.data_ptr() if n_sph else 1) if given else None, n_sph,
+                                                    C.c_void_p(out.data_ptr() if n else 1), C.c_void_p(stream)), "rt_hip_prev_points_moved")
+    return out
+
+
+def prev_points_moved_host(hits, positions, spheres_prev, spheres_cur, device=0):
+    """rt_hip_prev_points_moved_host(): host arrays, its own device buffers on logical device `device`, synchronous.  hits: numpy
+    arrays with status, prim, object (uint32 [n]), bary (float64 [n, 2]) and point (float64 [n, 3]); positions: float64
+    (n_triangles, 3, 3) or None; spheres_prev / spheres_cur: float64 (n_spheres, 4) or both None -> float64 [n, 3]"""
+    import numpy as np
+    arrs = {f: np.ascontiguousarray(hits[f], dtype=np.float64 if abi.HIT_SHAPES[f][0] == "float64" else np.uint32)
+            for f in ("status", "prim", "object", "bary", "point")}
+    n = arrs["status"].size
+    h = abi.RtHipHits()
+    for f, a in arrs.items():
+        if a.size != n * abi.HIT_SHAPES[f][1]:
+            raise ValueError(f"prev_points_moved_host(): hits[{f!r}] must hold {n} x {abi.HIT_SHAPES[f][1]} values")
+        setattr(h, f, a.ctypes.data if n else 1)
+    pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3, 3)
+    n_tri = 0 if pos is None else pos.shape[0]
+    n_sph, sprev, scur = _sphere_pair("prev_points_moved_host", spheres_prev, spheres_cur,
+                                      lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 4))
+    out = np.zeros((n, 3), np.float64)
+    given = sprev is not None
+    _check(abi.load_shim().rt_hip_prev_points_moved_host(C.byref(h), n, pos.ctypes.data if n_tri else None, n_tri,
+                                                         (sprev.ctypes.data if n_sph else 1) if given else None,
+                                                         (scur.ctypes.data if n_sph else 1) if given else None, n_sph, device,
+                                                         out.ctypes.data if n else 1), "rt_hip_prev_points_moved_host")
+    return out
+
+
 def prev_points_host(hits, positions, device=0):
     """rt_hip_prev_points_host(): host arrays, its own device buffers on logical device `device`, synchronous.  hits: a dict of
     numpy arrays with status, prim (uint32 [n]), bary (float64 [n, 2]) and point (float64 [n, 3]); positions: float64
@@ -884,7 +1018,8 @@ class Temporal:
         ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
         self._uv = torch.stack([(xs + 0.5) / (float(w) - 1.0), (ys + 0.5) / (float(h) - 1.0)], dim=-1).reshape(-1, 2).contiguous().to(dev)
         self._hits = dict(status=torch.zeros(w * h, dtype=torch.int32, device=dev), prim=torch.zeros(w * h, dtype=torch.int32, device=dev),
-                          bary=torch.zeros((w * h, 2), dtype=torch.float64, device=dev), point=torch.zeros((w * h, 3), dtype=torch.float64, device=dev))
+                          bary=torch.zeros((w * h, 2), dtype=torch.float64, device=dev), point=torch.zeros((w * h, 3), dtype=torch.float64, device=dev),
+                          object=torch.zeros(w * h, dtype=torch.int32, device=dev))
         self._points = torch.zeros((w * h, 3), dtype=torch.float64, device=dev)
         self._cur = 0          # the slot the next frame is written to
         self.frames = 0        # frames since the last reset: 0 = the next one has no history
@@ -896,7 +1031,8 @@ class Temporal:
         """drop the history: the next frame starts from its own samples"""
         self.frames = 0
 
-    def frame(self, camera, seed, samples, max_depth=None, denoise=False, fill=None, prev_positions=None, **denoise_params):
+    def frame(self, camera, seed, samples, max_depth=None, denoise=False, fill=None, prev_positions=None, prev_spheres=None,
+              **denoise_params):
         """Render `samples` per pixel under `camera` (an abi.Camera), reproject and accumulate -> dict of device tensors, valid
         until the next frame(): rgb f32 [H,W,3] (the accumulated image), rgb8 u8 [H,W,3], len f32 [H,W], motion f32
         [H,W,2], aov (the frame's first-hit buffers), and with denoise: denoised / denoised8, rt_hip_denoise of the accumulated
@@ -909,7 +1045,10 @@ class Temporal:
         prev_positions (None: the scene has not moved since the previous frame()): the float64 (n_triangles, 3, 3) device tensor
         of the positions the scene had at the previous frame(), after an update_vertices.  With a history, the pixel centres are
         queried under `camera` (query_uv), each hit is taken back to those positions (prev_points) and the reprojection starts
-        from there (reproject(prev_points=...)): the history follows the moving surface."""
+        from there (reproject(prev_points=...)): the history follows the moving surface.
+        prev_spheres (None: no sphere has moved since the previous frame()): the float64 (n_objects, 4) device tensor of the
+        spheres the scene had at the previous frame(), after an update_spheres -- the sphere twin of prev_positions.  With either,
+        the same query feeds prev_points_moved with the scene's current spheres (GpuScene.spheres())."""
         gs, total = self.gs, self._total
         w, h = gs.scene.width, gs.scene.height
         cur, prev = self._slots[self._cur], self._slots[self._cur ^ 1]
@@ -926,9 +1065,10 @@ class Temporal:
         _check(gs.shim.rt_hip_untile_aov(C.byref(src), w, h, 0, 1, total, C.byref(dst), C.c_void_p(stream)), "rt_hip_untile_aov")
         C.memmove(C.byref(cur["camera"]), C.byref(camera), C.sizeof(abi.Camera))
         points = None
-        if prev_positions is not None and self.frames:
-            hits = gs.query_uv(self._uv, camera=camera, want=("status", "prim", "bary", "point"), out=self._hits)
-            points = prev_points(hits, prev_positions, out=self._points)
+        if (prev_positions is not None or prev_spheres is not None) and self.frames:
+            hits = gs.query_uv(self._uv, camera=camera, want=("status", "prim", "object", "bary", "point"), out=self._hits)
+            # (without prev_spheres this is prev_points' own arithmetic: a sphere hit keeps its point, bit for bit)
+            points = prev_points_moved(hits, prev_positions, prev_spheres, None if prev_spheres is None else gs.spheres(), out=self._points)
         res = reproject(cur["rgb"], cur["aov"], cur["camera"], hist=prev if self.frames else None,
                         out=dict(rgb=cur["rgb"], len=cur["len"], motion=self._motion, rgb8=self._rgb8), prev_points=points, **self.params)
         res["aov"] = cur["aov"]
