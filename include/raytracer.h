@@ -258,6 +258,15 @@ int rt_get_bvh_builder(void);
 void rt_set_scene_updates(int on);
 int rt_get_scene_updates(void);
 
+/* Under rt_set_scene_updates(1) a refit keeps the hierarchy's topology, and the walks get dearer as the mesh leaves the shape the
+ * tree was built for.  A ratio r >= 1 (finite) makes every frame that is taken as an in-place vertex update end with
+ * rt_hip_scene_maintain_bvh(scene, r) on every cached scene: the refitted tree is priced on the device, and rebuilt in place when
+ * it costs more than r times what it cost as built (rt_hip.h; DESIGN.md has the measured relation between a ratio and frame
+ * time -- there is no recommended value).  0, the default: never.  Another value (NaN, infinite, negative, between 0 and 1) is
+ * ignored and the setting stays, as rt_set_bvh_builder ignores an unknown builder.  The frame is the same either way, bit for bit. */
+void rt_set_bvh_rebuild_ratio(double max_ratio);
+double rt_get_bvh_rebuild_ratio(void);
+
 /* Cooperative cancellation (what the reference's SIGINT handler, main.c:37-48,422, is for):
  * while a flag is registered, long renders poll it between slabs of tiles; when it becomes
  * non-zero render()/render_ex() return early with the finished part of the image in the

@@ -179,6 +179,72 @@ int rt_hip_scene_bvh_read(const RtHipScene *scene, double *h_nodes, uint32_t *h_
  * around its kernels */
 double rt_hip_scene_bvh_build_seconds(const RtHipScene *scene);
 
+/* ---- a tree priced on the device ----
+ * rt_hip_scene_bvh_info's tree_cost downloads every node (128 bytes each); this evaluates the same formula where the nodes lie
+ * (k_tree_cost, csrc/scene_update.hip; the terms are csrc/bvh_build.h's bvh_cost_*) and reads back 8 bytes.  Synchronous, on the
+ * null stream of the scene's device.
+ * CONTRACT: the cost is a pure function of the bytes of the fp64 source nodes (n_nodes x 16 doubles, rt_hip_scene_bvh_read's
+ * layout; n0 = node 0), all arithmetic fp64, unfused, in the order written:
+ *   root      lo[k] = fmin(n0[k], n0[6 + k]), hi[k] = fmax(n0[3 + k], n0[9 + k]) for k = 0, 1, 2; a_root = half_area(lo, hi) with
+ *             half_area = dx * dy + dy * dz + dz * dx, d = hi - lo.  n_nodes == 0, or !(a_root > 0) || !(a_root < 1e300): the cost
+ *             is 0.0.
+ *   terms     node i: (c0 + c1); c_k = +0.0 where child k is an empty leaf (leaf flag set, count 0), otherwise
+ *             (half_area(child k's box) / a_root) * (leaf ? 45.0 * count : 60.0), count = the ref's low 4 bits.
+ *   sum       in blocks of 256 terms, missing terms +0.0: for m = 128, 64, ..., 1: v[i] = v[i] + v[i + m] for i < m (the shape
+ *             rt_hip_tile_error states); v[0] is the block's sum.  The block sums are the next level's terms, reduced by the same
+ *             rule, level after level, until one value `total` is left.  cost = 60.0 + total.
+ * No atomic takes part and no workgroup waits for another (the levels are launched one after another), so the same bytes give the
+ * same cost on every run.  It differs from rt_hip_scene_bvh_info's node-order sum by rounding alone: at most
+ * n_nodes * 2^-52 * cost, both being sums of 2 n_nodes non-negative terms.
+ * TOTAL: any node bytes have a defined result -- NaN boxes, inverted boxes, refs that point nowhere (a ref is only read for its
+ * flag and count; no child is followed).  A NaN in one of the root's two boxes gives way to the other box's component (fmin /
+ * fmax); a root area that is NaN, zero, negative or >= 1e300 prices the tree at 0.0; otherwise a NaN or infinite term makes the
+ * cost NaN or infinite by IEEE addition in the order above (a NaN result's sign and payload are not specified).
+ * rt_hip_scene_bvh_cost: the scene's current tree (refitted, if it was); a scene without triangles: 0.0.  RT_HIP_EINVAL: a NULL
+ * argument.  RT_HIP_ERUNTIME: an unusable scene.  RT_HIP_ENOMEM: the workspace (8 bytes per 256 nodes; made at the
+ * first call and kept with the scene, so a per-frame question allocates nothing).
+ * rt_hip_bvh_cost_nodes_host: the same for n_nodes nodes in host memory, staged on `device` (logical, as in rt_hip_scene_create)
+ * -- for tools, and for tests of the reduction's edges.  Arguments are checked before a device is looked for: a NULL cost, NULL
+ * nodes with n_nodes > 0 or n_nodes >= 2^27 is RT_HIP_EINVAL, then a missing device RT_HIP_ENODEV.  n_nodes == 0 needs no
+ * device: 0.0. */
+int rt_hip_scene_bvh_cost(const RtHipScene *scene, double *cost);
+int rt_hip_bvh_cost_nodes_host(const double *h_nodes, size_t n_nodes, int device, double *cost);
+
+/* ---- the topology rebuilt in place ----
+ * rt_hip_scene_rebuild_bvh runs the device builder (RT_HIP_BVH_DEVICE above) over the scene's current triangles -- they are on the
+ * device already, and after any number of vertex updates equal a fresh scene's bit for bit -- and installs the new tree in the
+ * scene the handle names.  Synchronous.
+ * CONTRACT: after the call the nodes and order of rt_hip_scene_bvh_read, the leaf-ordered geometry, rt_hip_scene_bvh_info (the
+ * builder becomes RT_HIP_BVH_DEVICE, whoever built the scene), rt_hip_kernel_name, the frames, bytes and counters of every launch
+ * and the ray queries equal, byte for byte, those of a scene freshly created with RT_HIP_BVH_DEVICE from the same positions.
+ * Spheres, materials, triangle records, hull bits, bounds, the parked-walk workspace and every handle stay.
+ * The new tree's node count may differ from the old one's.  A scene keeps a node capacity (the count it was created with, or the
+ * largest a rebuild has needed since): a tree that fits is written in place; one that does not gets a side allocation for the
+ * source nodes and the first table set's fp32 nodes (192 bytes a node), kept until the scene is destroyed or a later rebuild
+ * needs a larger one.  Table sets beyond the first are freed (the next launch that needs one allocates it at the new size);
+ * every table set is stale and rebuilt by the next launch, as after an update; the level array of the refit is dropped and made
+ * again by the next vertex update.
+ * Refusals, every one before the first write into the scene (the build writes its own workspace alone), so the scene is
+ * unchanged: RT_HIP_EINVAL -- a NULL scene; a scene without triangles; an RtHipAccum on the scene that has not been destroyed; a
+ * launch of the scene being submitted on another thread.  RT_HIP_ERUNTIME -- an unusable scene; an inconsistency the builder
+ * found in its own result.  RT_HIP_ENOMEM -- the builder's workspace (about 360 bytes a triangle) or the side allocation.
+ * RT_HIP_ELIMIT -- a depth above the traversal stack (24; it cannot occur at an unchanged triangle count).  A HIP runtime failure
+ * after installing has begun is RT_HIP_ERUNTIME and leaves the scene UNUSABLE, as a failed update does.
+ * rt_hip_scene_rebuild_info (any out pointer may be NULL): how many rebuilds the scene has taken (rt_hip_scene_update_info keeps
+ * counting updates alone), the host-clock seconds of the last one, and built_cost -- rt_hip_scene_bvh_cost of the tree as it was
+ * last BUILT: taken at every rebuild, and for a created scene at the first request (this call, rt_hip_scene_maintain_bvh) or
+ * before its first vertex update refits the tree, whichever comes first; 0.0 without triangles. */
+int rt_hip_scene_rebuild_bvh(RtHipScene *scene);
+int rt_hip_scene_rebuild_info(const RtHipScene *scene, uint64_t *rebuilds, double *last_seconds, double *built_cost);
+
+/* The decision: prices the current (refitted) tree on the device, reports *cost_ratio = cost / built_cost (1.0 where built_cost
+ * is 0: nothing to compare), and rebuilds iff cost_ratio > max_ratio (*rebuilt = 1; else 0).  After a rebuild the next call
+ * reports 1.0.  There is no default ratio: what a ratio costs in frame time depends on the scene and the view ("Keeping
+ * a deforming mesh's tree good", has a measured table to choose from).  RT_HIP_EINVAL: max_ratio NaN, infinite or below 1 (checked
+ * first); a NULL scene; a scene without triangles.  Otherwise rt_hip_scene_bvh_cost's and rt_hip_scene_rebuild_bvh's errors; a
+ * refusal of the rebuild leaves the scene as it was, and *cost_ratio is set even then.  Either out pointer may be NULL. */
+int rt_hip_scene_maintain_bvh(RtHipScene *scene, double max_ratio, double *cost_ratio, int *rebuilt);
+
 /* ---- a deforming mesh: new vertex positions for a scene that exists ----
  * New positions for every triangle of the scene: 9 doubles a triangle (v0, v1, v2), in scene triangle order (mesh by mesh).
  * d_positions: device memory on the scene's device, not inside the scene (from skinning, a cloth step, a torch tensor);
@@ -187,7 +253,8 @@ double rt_hip_scene_bvh_build_seconds(const RtHipScene *scene);
  * and the existing hierarchy is REFITTED: same topology, same leaf order, new boxes (BvhRefit, csrc/bvh_build.h).  A hierarchy
  * only decides which triangles get the exact test, so frames, bytes and counters after an update equal those of a scene
  * freshly created from the same positions; only the walks' cost can drift as the mesh leaves the shape the tree was built for
- * (rt_hip_scene_bvh_info's tree_cost reports the refitted tree's: recreate the scene when it has drifted too far).  The
+ * (rt_hip_scene_bvh_cost prices the refitted tree on the device; rt_hip_scene_maintain_bvh compares it with the tree as built and
+ * rt_hip_scene_rebuild_bvh gives the scene a new topology in place when it has drifted too far: all above).  The
  * parked-walk workspace, the table sets' storage and every handle stay.  Spheres, triangle counts, materials and tex
  * coordinates do not change; the topology is not rebuilt.
  * RT_HIP_EINVAL, with the scene unchanged: n_triangles differs from the scene's count; a scene without triangles; a NULL
@@ -1053,6 +1120,13 @@ int rt_hip_set_bvh_builder(int builder);
  * scene rebuilds the context as any other change does. */
 void rt_hip_set_scene_updates(int on);
 uint64_t rt_hip_cache_updates(void);
+
+/* The cached context's rebuild ratio: 0 (the default) never rebuilds; a finite ratio >= 1 makes every frame that
+ * rt_hip_set_scene_updates(1) takes as an in-place VERTEX update end with rt_hip_scene_maintain_bvh(scene, ratio) on every cached
+ * scene, and rt_hip_cache_rebuilds() counts the frames in which at least one of them rebuilt.  Another value (NaN, infinite,
+ * negative, between 0 and 1) is RT_HIP_EINVAL and leaves the setting.  Not part of the cache key. */
+int rt_hip_set_bvh_rebuild_ratio(double max_ratio);
+uint64_t rt_hip_cache_rebuilds(void);
 
 #ifdef __cplusplus
 }

@@ -800,6 +800,38 @@ inline void scene_sphere_bounds(const double *spheres, size_t n, double *entry, 
   scene_sphere_leading_walls(spheres, n, b);
 }
 
+/* ---- a tree priced on the device (scene_update.hip: k_tree_cost; rt_hip_scene_bvh_cost, rt_hip.h states the contract) ----
+ * BvhBuild::tree_cost()'s formula, term by term, in one text for the kernel and for whoever restates it on the host: the terms
+ * are the same doubles; only the order of the additions differs (a fixed tree here, node order there).  fp64, unfused
+ * (-ffp-contract=off), in the order written. */
+#define BVH_COST_BLOCK 256 /* terms a block of the reduction tree takes */
+/* the half area of the root's box, from node 0: NaN components of one child's box give way to the other's (fmin / fmax) */
+BVH_HD inline double bvh_cost_root_area(const double *n0)
+{
+  double lo[3], hi[3];
+  for (int k = 0; k < 3; k++)
+  {
+    lo[k] = std::fmin(n0[k], n0[6 + k]);
+    hi[k] = std::fmax(n0[3 + k], n0[9 + k]);
+  }
+  return bvh_half_area(lo, hi);
+}
+BVH_HD inline bool bvh_cost_root_ok(double a_root) { return a_root > 0 && a_root < 1e300; }
+/* node n's term (c0 + c1): an empty leaf child is +0.0, another child (half_area / a_root) * (leaf ? 45 count : 60) */
+BVH_HD inline double bvh_cost_term(const double *n, double a_root)
+{
+  uint32_t refs[2];
+  memcpy(refs, n + 12, sizeof refs);
+  double c[2];
+  for (int k = 0; k < 2; k++)
+  {
+    const bool leaf = (refs[k] & PT_BVH_LEAF_FLAG) != 0;
+    const uint32_t count = refs[k] & ((1u << PT_BVH_COUNT_BITS) - 1u);
+    c[k] = (leaf && count == 0) ? 0.0 : (bvh_half_area(n + 6 * k, n + 6 * k + 3) / a_root) * (leaf ? 45.0 * (double)count : 60.0);
+  }
+  return c[0] + c[1];
+}
+
 #if defined(__HIPCC__)
 
 /* the arrays of a scene that an update rewrites (device memory) */
@@ -832,6 +864,18 @@ hipError_t scene_update_triangles(const SceneUpdateArrays &s, const double *posi
 /* BvhRefit on the device: the leaf children, then the inner ones level by level from the deepest (by_level in device memory,
  * level_begin on the host: BvhRefit::levels), and tri_geom_leaf.  Enqueues only. */
 hipError_t scene_update_refit(const SceneUpdateArrays &s, const uint32_t *by_level, const uint32_t *level_begin, size_t n_levels);
+
+/* doubles of device workspace the cost of n_nodes nodes needs: a sum per block of nodes, and a sum per block of those */
+inline size_t scene_tree_cost_ws_doubles(uint32_t n_nodes)
+{
+  const size_t b1 = ((size_t)n_nodes + BVH_COST_BLOCK - 1) / BVH_COST_BLOCK;
+  return b1 + (b1 + BVH_COST_BLOCK - 1) / BVH_COST_BLOCK;
+}
+/* The cost of a tree by the contract above (k_tree_cost, scene_update.hip): nodes = n_nodes x PT_BVH_SRC_DOUBLES in device memory
+ * of the current device.  Null stream; ws = scene_tree_cost_ws_doubles(n_nodes) doubles of device memory the caller keeps (a
+ * scene keeps one: no allocation in a per-frame question), or nullptr: the call allocates and frees them (hipErrorOutOfMemory
+ * where they cannot be had).  Waits, and reads back the 8 bytes of the result.  n_nodes == 0: 0.0, nothing launched. */
+hipError_t scene_tree_cost(const double *nodes, uint32_t n_nodes, double *ws, double *cost);
 
 /* ---- the interface of scene_update.hip's sphere half (rt_hip_scene_update_spheres) ----
  * Both on the null stream of the current device; spheres = 4 doubles a sphere in device memory; words: SCENE_SPHERE_WORDS 64-bit

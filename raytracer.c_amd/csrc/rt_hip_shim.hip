@@ -293,6 +293,19 @@ struct RtHipScene
   std::vector<uint32_t> refit_level_begin;
   uint64_t updates = 0;
   double last_update_seconds = 0;
+  /* ---- the topology rebuilt in place (rt_hip_scene_rebuild_bvh) ---- */
+  uint32_t bvh_node_capacity = 0; /* nodes that view.bvh_src and view.bvh_nodes have room for */
+  void *bvh_side = nullptr;       /* a tree of more nodes than the blob's regions hold: source nodes, then table set 0's fp32 nodes */
+  size_t bvh_side_bytes = 0;
+  uint64_t rebuilds = 0;
+  double last_rebuild_seconds = 0;
+  /* the device cost of the tree as it was last built (scene_built_cost; guarded by table_mutex) */
+  mutable double built_cost = 0;
+  mutable bool built_cost_known = false;
+  /* the cost kernel's workspace (scene_tree_cost), kept so that a per-frame question allocates nothing: made at the first cost,
+   * replaced when a tree of more nodes is priced; guarded by table_mutex */
+  mutable double *cost_ws = nullptr;
+  mutable uint32_t cost_ws_nodes = 0;
 };
 
 /* ---- progressive rendering: one frame accumulated over passes (rt_hip.h, RtHipAccum) ----------------------------------------
@@ -1116,6 +1129,7 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   sc->mesh_c_norm = std::sqrt(mesh_c[0] * mesh_c[0] + mesh_c[1] * mesh_c[1] + mesh_c[2] * mesh_c[2]) * (1.0 + 1e-12);
   sc->filt_bytes = filt_bytes;
   sc->bvh_nodes_bytes = bvh_nodes_bytes;
+  sc->bvh_node_capacity = (uint32_t)n_bvh_nodes;
   sc->view.material = reinterpret_cast<const double *>(base + off_mat);
   sc->view.color_raw = reinterpret_cast<const double *>(base + off_craw);
   sc->view.geom4 = reinterpret_cast<const double *>(base + off_geom4);
@@ -1597,6 +1611,7 @@ struct ImageCtx
   DeviceBuffer all_tiles, all_tiles8, image, image8; /* on the root, phys[0] */
   uint64_t builds = 0; /* how many times a context was (re)built: exposed for tests */
   uint64_t updates = 0; /* how many times its scenes' vertices were moved in place instead (rt_hip_set_scene_updates) */
+  uint64_t rebuilds = 0; /* in how many of those frames a scene's hierarchy was rebuilt in place (rt_hip_set_bvh_rebuild_ratio) */
   int bvh_builder = RT_HIP_BVH_HOST; /* who built the scenes' hierarchies (rt_hip_set_bvh_builder) */
 };
 /* (never destroyed: at process exit the members' destructors would call into a HIP runtime that may be gone already) */
@@ -1610,6 +1625,7 @@ std::vector<int> g_device_map;
 bool g_device_map_env_read = false;
 int g_bvh_builder = RT_HIP_BVH_HOST; /* rt_hip_set_bvh_builder: the builder of the cached scenes.  Guarded by g_ctx_mutex. */
 bool g_scene_updates = false; /* rt_hip_set_scene_updates: moved vertices update the cached scenes in place.  Guarded by g_ctx_mutex. */
+double g_bvh_rebuild_ratio = 0; /* rt_hip_set_bvh_rebuild_ratio: 0 = never; else rt_hip_scene_maintain_bvh's max_ratio after such an update.  Guarded by g_ctx_mutex. */
 
 void device_map_from_env()
 {
@@ -1637,7 +1653,7 @@ void device_map_from_env()
 }
 
 /* What needs an order: the streams drained, then the communicators, then each device's members with that device current.
- * `builds` and `updates` survive. */
+ * `builds`, `updates` and `rebuilds` survive. */
 void ctx_release(ImageCtx &c)
 {
   int prev = 0;
@@ -1670,10 +1686,11 @@ void ctx_release(ImageCtx &c)
   }
   if (!c.phys.empty())
     (void)hipSetDevice(c.phys[0]);
-  const uint64_t builds = c.builds, updates = c.updates;
+  const uint64_t builds = c.builds, updates = c.updates, rebuilds = c.rebuilds;
   c = ImageCtx(); /* the root's gathered tiles and images */
   c.builds = builds;
   c.updates = updates;
+  c.rebuilds = rebuilds;
   (void)hipSetDevice(prev);
 }
 
@@ -1802,6 +1819,20 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
           const int rc = rt_hip_scene_update_vertices_host(c.dev[g].scene, pos.data(), n_tri);
           if (rc)
             return rc;
+        }
+        if (g_bvh_rebuild_ratio != 0)
+        { /* the refitted trees priced against the trees as built; rebuilt in place where the ratio is above the setting */
+          bool any = false;
+          for (int g = 0; g < G; g++)
+          {
+            int rebuilt = 0;
+            const int rc = rt_hip_scene_maintain_bvh(c.dev[g].scene, g_bvh_rebuild_ratio, nullptr, &rebuilt);
+            if (rc)
+              return rc;
+            any = any || rebuilt != 0;
+          }
+          if (any)
+            c.rebuilds++;
         }
       }
       if (moved & MOVED_SPHERES)
@@ -2200,6 +2231,21 @@ void set_scene_updates_impl(int on)
 {
   std::lock_guard<std::mutex> lock(g_ctx_mutex);
   g_scene_updates = on != 0;
+}
+
+int set_bvh_rebuild_ratio_impl(double max_ratio)
+{
+  if (!(max_ratio == 0.0 || (max_ratio >= 1.0 && max_ratio < HUGE_VAL)))
+    return fail(RT_HIP_EINVAL, "bvh rebuild ratio: 0 (never rebuild) or a finite ratio >= 1");
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  g_bvh_rebuild_ratio = max_ratio == 0.0 ? 0.0 : max_ratio;
+  return RT_HIP_OK;
+}
+
+uint64_t cache_rebuilds_impl()
+{
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  return g_ctx.rebuilds;
 }
 
 /* logical device `device` of the device map (the HIP device itself without a map) -> the HIP device, or RT_HIP_ENODEV */
@@ -3369,6 +3415,10 @@ uint64_t rt_hip_cache_updates(void) { return cache_updates_impl(); }
 
 void rt_hip_set_scene_updates(int on) { set_scene_updates_impl(on); }
 
+int rt_hip_set_bvh_rebuild_ratio(double max_ratio) { return set_bvh_rebuild_ratio_impl(max_ratio); }
+
+uint64_t rt_hip_cache_rebuilds(void) { return cache_rebuilds_impl(); }
+
 int rt_hip_render_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes,
                         size_t n_meshes, const RtHipCamera *camera, const RtHipParams *params,
                         int n_devices, float *h_image_rgb, uint8_t *h_image_rgb8, uint64_t *h_stats,
@@ -3408,6 +3458,10 @@ void rt_hip_scene_destroy(RtHipScene *scene)
     }
     if (scene->refit_by_level)
       (void)hipFree(scene->refit_by_level);
+    if (scene->bvh_side)
+      (void)hipFree(scene->bvh_side);
+    if (scene->cost_ws)
+      (void)hipFree(scene->cost_ws);
     (void)hipFree(scene->blob);
   }
   delete scene;
@@ -3448,6 +3502,61 @@ int rt_hip_scene_hull_facets(const RtHipScene *scene, uint32_t *n_plus, uint32_t
 namespace
 {
 
+/* [p, p + bytes) meets memory the scene owns: the blob, or the side allocation a rebuild made for a larger tree */
+bool lies_inside_scene(const RtHipScene *scene, const void *ptr, size_t bytes)
+{
+  const char *p = static_cast<const char *>(ptr);
+  auto meets = [&](const void *base, size_t size) {
+    const char *b = static_cast<const char *>(base);
+    return b && p + bytes > b && p < b + size;
+  };
+  return meets(scene->blob, scene->blob_bytes) || meets(scene->bvh_side, scene->bvh_side_bytes);
+}
+
+/* The device cost of the tree as it was last built: a rebuild sets it; for a created scene it is taken here, at the first
+ * request -- and an update asks before its first refit, so it is never a refitted tree's.  Caller holds table_mutex and has the
+ * scene's device current. */
+/* The cost of `nodes` (the scene's own, or a tree still in its builder's workspace) through the workspace the scene keeps.  Every
+ * cost call waits for its result, so a workspace that is too small is free to be replaced.  Caller holds table_mutex and has the
+ * scene's device current. */
+int scene_cost_of(const RtHipScene *scene, const double *nodes, uint32_t n_nodes, double *cost)
+{
+  if (n_nodes > scene->cost_ws_nodes)
+  {
+    double *ws = nullptr;
+    const size_t bytes = scene_tree_cost_ws_doubles(n_nodes) * sizeof(double);
+    if (hipMalloc(&ws, bytes) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      return fail(RT_HIP_ENOMEM, "the cost kernel's workspace (%zu bytes)", bytes);
+    }
+    if (scene->cost_ws)
+      (void)hipFree(scene->cost_ws);
+    scene->cost_ws = ws;
+    scene->cost_ws_nodes = n_nodes;
+  }
+  HIP_TRY(scene_tree_cost(nodes, n_nodes, scene->cost_ws, cost));
+  return RT_HIP_OK;
+}
+
+int scene_built_cost(const RtHipScene *scene, double *cost)
+{
+  if (!scene->built_cost_known)
+  {
+    double c = 0.0;
+    {
+      const int rc = scene_cost_of(scene, scene->view.bvh_src, scene->view.n_bvh_nodes, &c);
+      if (rc)
+        return rc;
+    }
+    scene->built_cost = c;
+    scene->built_cost_known = true;
+  }
+  if (cost)
+    *cost = scene->built_cost;
+  return RT_HIP_OK;
+}
+
 int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_triangles, bool on_host)
 {
   if (!scene || !positions)
@@ -3470,8 +3579,7 @@ int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_trian
       (void)hipGetLastError();
       return fail(RT_HIP_EINVAL, "d_positions is not device memory of the scene's device %d", scene->device);
     }
-    const char *p = reinterpret_cast<const char *>(positions), *blob = static_cast<const char *>(scene->blob);
-    if (p + 72 * n > blob && p < blob + scene->blob_bytes)
+    if (lies_inside_scene(scene, positions, 72 * n))
       return fail(RT_HIP_EINVAL, "d_positions lies inside the scene");
   }
   std::lock_guard<std::mutex> lock(scene->table_mutex);
@@ -3500,7 +3608,12 @@ int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_trian
   if (!(chk.max_len <= 1e300)) /* scene_create_impl's rule */
     return fail(RT_HIP_EINVAL, "a new position has a non-finite coordinate");
 
-  /* ---- the topology's levels, at the first update ---- */
+  /* ---- the cost of the tree as built, while it still is that tree; the topology's levels, at the first update ---- */
+  {
+    const int rc = scene_built_cost(scene, nullptr);
+    if (rc)
+      return rc;
+  }
   const uint32_t n_nodes = scene->view.n_bvh_nodes;
   if (!scene->refit_by_level)
   {
@@ -3619,8 +3732,7 @@ int scene_update_spheres_impl(RtHipScene *scene, const double *spheres, size_t n
       (void)hipGetLastError();
       return fail(RT_HIP_EINVAL, "d_spheres is not device memory of the scene's device %d", scene->device);
     }
-    const char *p = reinterpret_cast<const char *>(spheres), *blob = static_cast<const char *>(scene->blob);
-    if (p + in_bytes > blob && p < blob + scene->blob_bytes)
+    if (lies_inside_scene(scene, spheres, in_bytes))
       return fail(RT_HIP_EINVAL, "d_spheres lies inside the scene");
   }
   std::lock_guard<std::mutex> lock(scene->table_mutex);
@@ -3690,7 +3802,246 @@ int scene_update_spheres_impl(RtHipScene *scene, const double *spheres, size_t n
   return RT_HIP_OK;
 }
 
+/* ---- the tree priced on the device, and the topology rebuilt in place (rt_hip.h states both contracts) ---- */
+int scene_cost_impl(const RtHipScene *scene, double *cost)
+{
+  if (!scene || !cost)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_bvh_cost: scene and cost are required");
+  *cost = 0.0;
+  if (scene->unusable)
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  std::lock_guard<std::mutex> lock(scene->table_mutex);
+  return scene_cost_of(scene, scene->view.bvh_src, scene->view.n_bvh_nodes, cost);
+}
+
+int cost_nodes_host_impl(const double *h_nodes, size_t n_nodes, int device, double *cost)
+{
+  if (!cost || (!h_nodes && n_nodes > 0) || n_nodes >= ((size_t)1 << (31 - PT_BVH_COUNT_BITS)))
+    return fail(RT_HIP_EINVAL, "rt_hip_bvh_cost_nodes_host: cost is required, nodes where n_nodes > 0, and n_nodes < 2^%d",
+                31 - PT_BVH_COUNT_BITS);
+  *cost = 0.0;
+  if (n_nodes == 0)
+    return RT_HIP_OK;
+  int phys = 0;
+  {
+    const int rc = physical_device(device, &phys);
+    if (rc)
+      return rc;
+  }
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  DeviceBuffer staged;
+  const size_t bytes = n_nodes * PT_BVH_SRC_DOUBLES * 8;
+  if (staged.alloc(bytes) != hipSuccess)
+    return fail(RT_HIP_ENOMEM, "the staged nodes (%zu KB)", bytes >> 10);
+  HIP_TRY(hipMemcpy(staged.ptr, h_nodes, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(scene_tree_cost(staged.at<double>(), (uint32_t)n_nodes, nullptr, cost));
+  return RT_HIP_OK;
+}
+
+/* caller holds table_mutex, has the scene's device current and has ruled out a NULL, unusable or triangle-less scene */
+int scene_rebuild_locked(RtHipScene *scene)
+{
+  if (scene->live_accums.load() > 0)
+    return fail(RT_HIP_EINVAL, "%d accumulation(s) on this scene are alive: destroy them before its hierarchy is rebuilt",
+                scene->live_accums.load());
+  for (const TableSet &t : scene->tables)
+    if (t.users > 0)
+      return fail(RT_HIP_EINVAL, "a launch of this scene is being submitted");
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t n = scene->view.n_triangles;
+
+  /* ---- the build, in its own workspace; the new tree priced where it lies ---- */
+  BvhDeviceTree dtree;
+  const hipError_t be = bvh_device_build(scene->view.tri_geom, (uint32_t)n, &dtree);
+  if (be != hipSuccess && dtree.failure)
+    return fail(RT_HIP_ERUNTIME, "device hierarchy builder: %s", dtree.failure);
+  HIP_TRY(be);
+  if (dtree.depth > PT_BVH_STACK)
+    return fail(RT_HIP_ELIMIT, "triangle hierarchy depth %d exceeds the traversal stack (%d)", dtree.depth, PT_BVH_STACK);
+  if (dtree.n_nodes == 0)
+    return fail(RT_HIP_ERUNTIME, "device hierarchy builder: a tree without nodes");
+  double cost = 0.0;
+  {
+    const int rc = scene_cost_of(scene, dtree.nodes, dtree.n_nodes, &cost);
+    if (rc)
+      return rc;
+  }
+
+  /* ---- room for it: in place while the count fits the capacity, else a side allocation ---- */
+  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t src_bytes = (size_t)dtree.n_nodes * PT_BVH_SRC_DOUBLES * 8, f32_bytes = (size_t)dtree.n_nodes * PT_BVH_NODE_WORDS * 4;
+  DeviceBuffer side;
+  const size_t side_bytes = pad(src_bytes) + pad(f32_bytes);
+  if (dtree.n_nodes > scene->bvh_node_capacity && side.alloc(side_bytes) != hipSuccess)
+    return fail(RT_HIP_ENOMEM, "the side allocation of a larger hierarchy (%zu KB)", side_bytes >> 10);
+
+  /* ---- no launch may still read what is about to change: every table set's build and readers, as the updates wait ---- */
+  for (TableSet &t : scene->tables)
+  {
+    HIP_TRY(hipEventSynchronize(t.built));
+    for (auto &r : t.readers)
+      HIP_TRY(hipEventSynchronize(r.second));
+  }
+
+  /* ---- installing begins ---- */
+  auto broke = [&](hipError_t e, const char *what) {
+    (void)hipGetLastError();
+    scene->unusable = true;
+    return fail(RT_HIP_ERUNTIME, "%s: %s; the scene is unusable now (destroy it)", what, hipGetErrorString(e));
+  };
+  if (scene->refit_by_level) /* the old topology's levels: the next vertex update makes the new one's */
+    (void)hipFree(scene->refit_by_level);
+  scene->refit_by_level = nullptr;
+  scene->refit_level_begin.clear();
+  while (scene->tables.size() > 1) /* the owned sets hold fp32 nodes of the old count: the next launch that needs one allocates it anew */
+  {
+    TableSet &t = scene->tables.back();
+    for (auto &r : t.readers)
+      (void)hipEventDestroy(r.second);
+    if (t.built) (void)hipEventDestroy(t.built);
+    if (t.owned)
+    {
+      (void)hipFree(t.filt);
+      (void)hipFree(t.bvh_nodes);
+    }
+    scene->tables.pop_back();
+  }
+  if (side)
+  {
+    if (scene->bvh_side)
+      (void)hipFree(scene->bvh_side);
+    scene->bvh_side = side.ptr;
+    scene->bvh_side_bytes = side_bytes;
+    side.ptr = nullptr; /* the scene's now */
+    scene->view.bvh_src = reinterpret_cast<const double *>(scene->bvh_side);
+    scene->view.bvh_nodes = reinterpret_cast<float *>(static_cast<char *>(scene->bvh_side) + pad(src_bytes));
+    scene->bvh_node_capacity = dtree.n_nodes;
+  }
+  for (TableSet &t : scene->tables)
+  {
+    t.bvh_nodes = scene->view.bvh_nodes; /* (set 0 alone is left: its nodes are the view's) */
+    t.near_R = -1.0; /* rebuilt by the next launch (acquire_tables) */
+  }
+  hipError_t e = hipMemcpy(const_cast<double *>(scene->view.bvh_src), dtree.nodes, src_bytes, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(const_cast<uint32_t *>(scene->view.bvh_tri), dtree.order, n * 4, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess)
+    e = bvh_device_gather_leaf(scene->view.tri_geom, scene->view.bvh_tri, (uint32_t)n, const_cast<double *>(scene->view.tri_geom_leaf));
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess)
+    return broke(e, "installing the rebuilt hierarchy");
+  scene->view.n_bvh_nodes = dtree.n_nodes;
+  scene->view.bvh_depth = (uint32_t)dtree.depth;
+  scene->bvh_builder = RT_HIP_BVH_DEVICE;
+  scene->bvh_max_depth = (uint32_t)dtree.max_depth;
+  scene->bvh_build_seconds = 1e-3 * dtree.build_ms;
+  scene->bvh_nodes_bytes = f32_bytes;
+  scene->built_cost = cost;
+  scene->built_cost_known = true;
+  scene->rebuilds++;
+  scene->last_rebuild_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RT_HIP_OK;
+}
+
+int scene_rebuild_impl(RtHipScene *scene)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_rebuild_bvh: scene is NULL");
+  if (scene->unusable)
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  if (scene->view.n_triangles == 0)
+    return fail(RT_HIP_EINVAL, "the scene has no triangles: there is no hierarchy to rebuild");
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  std::lock_guard<std::mutex> lock(scene->table_mutex);
+  return scene_rebuild_locked(scene);
+}
+
+/* max_ratio as rt_hip_scene_maintain_bvh takes it: finite and >= 1 */
+bool rebuild_ratio_ok(double r) { return r >= 1.0 && r < HUGE_VAL; }
+
+int scene_maintain_impl(RtHipScene *scene, double max_ratio, double *cost_ratio, int *rebuilt)
+{
+  if (cost_ratio) *cost_ratio = 0.0;
+  if (rebuilt) *rebuilt = 0;
+  if (!rebuild_ratio_ok(max_ratio))
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_maintain_bvh: max_ratio must be finite and >= 1");
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_maintain_bvh: scene is NULL");
+  if (scene->unusable)
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  if (scene->view.n_triangles == 0)
+    return fail(RT_HIP_EINVAL, "the scene has no triangles: there is no hierarchy to maintain");
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  std::lock_guard<std::mutex> lock(scene->table_mutex);
+  double built = 0.0, cost = 0.0;
+  {
+    const int rc = scene_built_cost(scene, &built);
+    if (rc)
+      return rc;
+  }
+  {
+    const int rc = scene_cost_of(scene, scene->view.bvh_src, scene->view.n_bvh_nodes, &cost);
+    if (rc)
+      return rc;
+  }
+  const double ratio = built == 0.0 ? 1.0 : cost / built;
+  if (cost_ratio) *cost_ratio = ratio;
+  if (!(ratio > max_ratio))
+    return RT_HIP_OK;
+  const int rc = scene_rebuild_locked(scene);
+  if (rc == RT_HIP_OK && rebuilt)
+    *rebuilt = 1;
+  return rc;
+}
+
 } // namespace
+
+int rt_hip_scene_bvh_cost(const RtHipScene *scene, double *cost)
+{
+  return guarded("rt_hip_scene_bvh_cost", [&] { return scene_cost_impl(scene, cost); });
+}
+
+int rt_hip_bvh_cost_nodes_host(const double *h_nodes, size_t n_nodes, int device, double *cost)
+{
+  return guarded("rt_hip_bvh_cost_nodes_host", [&] { return cost_nodes_host_impl(h_nodes, n_nodes, device, cost); });
+}
+
+int rt_hip_scene_rebuild_bvh(RtHipScene *scene)
+{
+  return guarded("rt_hip_scene_rebuild_bvh", [&] { return scene_rebuild_impl(scene); });
+}
+
+int rt_hip_scene_rebuild_info(const RtHipScene *scene, uint64_t *rebuilds, double *last_seconds, double *built_cost)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_rebuild_info: scene is NULL");
+  if (rebuilds) *rebuilds = scene->rebuilds;
+  if (last_seconds) *last_seconds = scene->last_rebuild_seconds;
+  if (!built_cost)
+    return RT_HIP_OK;
+  *built_cost = 0.0;
+  if (scene->view.n_bvh_nodes == 0)
+    return RT_HIP_OK;
+  if (scene->unusable)
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  return guarded("rt_hip_scene_rebuild_info", [&]() -> int {
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    std::lock_guard<std::mutex> lock(scene->table_mutex);
+    return scene_built_cost(scene, built_cost);
+  });
+}
+
+int rt_hip_scene_maintain_bvh(RtHipScene *scene, double max_ratio, double *cost_ratio, int *rebuilt)
+{
+  return guarded("rt_hip_scene_maintain_bvh", [&] { return scene_maintain_impl(scene, max_ratio, cost_ratio, rebuilt); });
+}
 
 int rt_hip_scene_update_spheres(RtHipScene *scene, const double *d_spheres, size_t n_spheres)
 {

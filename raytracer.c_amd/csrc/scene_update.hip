@@ -12,8 +12,11 @@
  * and a scene's spheres moved in place (rt_hip_scene_update_spheres; the contract is scene_spheres.h's scene_sphere_bounds):
  *   k_update_spheres     one thread a sphere: the entry_src record and its geom4 copy (where an output is given), and the maxima
  *                        the scene keeps of its spheres -- reach, max |centre|, wide range -- with "a radius is out of range"
- * 256 threads a workgroup, no scratch, no LDS; no kernel waits for another workgroup: a wave reduces by lane shuffles and hands
- * its result to one atomic max / min on a 64-bit key. */
+ * and a tree priced where it lies (rt_hip_scene_bvh_cost; the contract is bvh_build.h's bvh_cost_* and rt_hip.h):
+ *   k_tree_cost          one level of a fixed reduction tree over the nodes' cost terms, launched level by level from the host
+ * 256 threads a workgroup, no scratch, no LDS (k_tree_cost: 2 KB, for its two widest halvings); no kernel waits for another
+ * workgroup: a wave reduces by lane shuffles and hands its result to one atomic max / min on a 64-bit key (k_tree_cost: to its
+ * block's own slot -- a sum has no atomics here). */
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -219,6 +222,59 @@ __global__ void __launch_bounds__(UPD_BLOCK) k_update_spheres(const double *__re
   }
 }
 
+/* One level of the cost's reduction tree (bvh_build.h: bvh_cost_*; rt_hip.h states the contract).  in == nullptr: the first level,
+ * term i is node i's, one node a thread, read once as two 64-byte halves; otherwise term i = in[i].  Terms from n on are +0.0.
+ * out[block] = the block's sum by halving: v[i] = v[i] + v[i + m] for i < m, m = 128 and 64 through LDS, 32 .. 1 by lane shuffles
+ * in the first wave.  The launch of one workgroup is the last level: it writes the cost, 60 + total, or 0.0 where the root's
+ * area is not in (0, 1e300).  Every thread derives the root's area from node 0 (a uniform read); nothing depends on the order
+ * workgroups or waves run in. */
+typedef double cost_d2 __attribute__((ext_vector_type(2)));
+
+__global__ void __launch_bounds__(BVH_COST_BLOCK) k_tree_cost(const double *__restrict__ nodes, uint32_t n_nodes,
+                                                             const double *__restrict__ in, uint32_t n, double *__restrict__ out)
+{
+  static_assert(BVH_COST_BLOCK == 256 && PT_BVH_SRC_DOUBLES == 16, "four waves a block, 128 bytes a node");
+  __shared__ double s_v[BVH_COST_BLOCK];
+  const uint32_t t = threadIdx.x, i = blockIdx.x * BVH_COST_BLOCK + t;
+  double n0[12];
+  for (int k = 0; k < 12; k++)
+    n0[k] = nodes[k];
+  const double a_root = bvh_cost_root_area(n0);
+  double v = 0.0;
+  if (i < n)
+  {
+    if (in)
+      v = in[i];
+    else if (i < n_nodes)
+    {
+      const cost_d2 *p = reinterpret_cast<const cost_d2 *>(nodes + (size_t)i * PT_BVH_SRC_DOUBLES);
+      double nd[PT_BVH_SRC_DOUBLES];
+      for (int h = 0; h < 2; h++) /* the two halves */
+        for (int k = 0; k < 4; k++)
+        {
+          const cost_d2 q = __builtin_nontemporal_load(p + 4 * h + k);
+          nd[8 * h + 2 * k] = q.x;
+          nd[8 * h + 2 * k + 1] = q.y;
+        }
+      v = bvh_cost_term(nd, a_root);
+    }
+  }
+  s_v[t] = v;
+  __syncthreads();
+  if (t < 128)
+    v = v + s_v[t + 128];
+  if (t >= 64 && t < 128)
+    s_v[t] = v; /* (no thread reads below 128 in the step above) */
+  __syncthreads();
+  if (t >= 64)
+    return;
+  v = v + s_v[t + 64];
+  for (int m = 32; m >= 1; m >>= 1)
+    v = v + __shfl_down(v, m); /* lane i < m is the tree's v[i]; the lanes from m on hold values nobody reads */
+  if (t == 0)
+    out[blockIdx.x] = gridDim.x != 1 ? v : bvh_cost_root_ok(a_root) ? 60.0 + v : 0.0;
+}
+
 #define UPD_TRY(expr)             \
   do                              \
   {                               \
@@ -285,6 +341,51 @@ hipError_t scene_update_refit(const SceneUpdateArrays &s, const uint32_t *by_lev
   }
   UPD_TRY(hipGetLastError());
   return bvh_device_gather_leaf(s.tri_geom, s.bvh_tri, s.n_tri, s.tri_geom_leaf);
+}
+
+hipError_t scene_tree_cost(const double *nodes, uint32_t n_nodes, double *ws, double *cost)
+{
+  if (!cost)
+    return hipErrorInvalidValue;
+  *cost = 0.0;
+  if (n_nodes == 0)
+    return hipSuccess;
+  if (!nodes)
+    return hipErrorInvalidValue;
+  /* level l's sums go to buf[l & 1]: the first holds a sum per block of nodes, the second a sum per block of those; every later
+   * level is shorter than the one two before it */
+  const uint32_t b1 = (n_nodes + BVH_COST_BLOCK - 1) / BVH_COST_BLOCK;
+  hipError_t e = hipSuccess;
+  double *own = nullptr;
+  if (!ws)
+  {
+    e = hipMalloc(&own, scene_tree_cost_ws_doubles(n_nodes) * sizeof(double));
+    if (e != hipSuccess)
+    {
+      (void)hipGetLastError();
+      return e;
+    }
+    ws = own;
+  }
+  double *buf[2] = {ws, ws + b1};
+  const double *in = nullptr;
+  uint32_t n = n_nodes;
+  int k = 0;
+  for (;; k ^= 1)
+  {
+    const uint32_t blocks = (n + BVH_COST_BLOCK - 1) / BVH_COST_BLOCK;
+    hipLaunchKernelGGL(k_tree_cost, dim3(blocks), dim3(BVH_COST_BLOCK), 0, nullptr, nodes, n_nodes, in, n, buf[k]);
+    if (blocks == 1)
+      break;
+    in = buf[k];
+    n = blocks;
+  }
+  e = hipGetLastError();
+  if (e == hipSuccess)
+    e = hipMemcpy(cost, buf[k], sizeof(double), hipMemcpyDeviceToHost);
+  if (own)
+    (void)hipFree(own);
+  return e;
 }
 
 /* ---- the sphere half ---- */

@@ -70,6 +70,13 @@ void rt_set_scene_updates(int on)
   rt_hip_set_scene_updates(g_scene_updates);
 }
 int rt_get_scene_updates(void) { return g_scene_updates; }
+static double g_bvh_rebuild_ratio = 0;
+void rt_set_bvh_rebuild_ratio(double max_ratio)
+{
+  if (rt_hip_set_bvh_rebuild_ratio(max_ratio) == RT_HIP_OK)
+    g_bvh_rebuild_ratio = max_ratio == 0 ? 0 : max_ratio;
+}
+double rt_get_bvh_rebuild_ratio(void) { return g_bvh_rebuild_ratio; }
 double rt_last_render_seconds(void) { return g_last_seconds; }
 static long long g_last_samples = 0; /* render_adaptive: pixel samples rendered */
 static const volatile int *g_cancel_flag = NULL; /* render_progressive polls it between passes */

@@ -201,6 +201,13 @@ SHIM_SYMBOLS = {
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_double * 8), C.POINTER(C.c_double * 8)]),
     "rt_hip_set_scene_updates": (None, [C.c_int]),
     "rt_hip_cache_updates": (C.c_uint64, []),
+    "rt_hip_scene_bvh_cost": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rt_hip_bvh_cost_nodes_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
+    "rt_hip_scene_rebuild_bvh": (C.c_int, [C.c_void_p]),
+    "rt_hip_scene_rebuild_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rt_hip_scene_maintain_bvh": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "rt_hip_set_bvh_rebuild_ratio": (C.c_int, [C.c_double]),
+    "rt_hip_cache_rebuilds": (C.c_uint64, []),
     "rt_hip_scene_device": (C.c_int, [C.c_void_p]),
     "rt_hip_scene_primitives": (C.c_size_t, [C.c_void_p]),
     "rt_hip_scene_hull_facets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -351,6 +358,8 @@ HOST_SYMBOLS = {
     "rt_get_bvh_builder": (C.c_int, []),
     "rt_set_scene_updates": (None, [C.c_int]),
     "rt_get_scene_updates": (C.c_int, []),
+    "rt_set_bvh_rebuild_ratio": (None, [C.c_double]),
+    "rt_get_bvh_rebuild_ratio": (C.c_double, []),
     "rt_set_devices": (None, [C.c_int]),
     "rt_get_max_depth": (C.c_int, []),
     "rt_get_seed": (C.c_uint64, []),

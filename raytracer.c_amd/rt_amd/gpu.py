@@ -111,12 +111,13 @@ class GpuScene:
                                                order.ctypes.data if order.size else None), "rt_hip_scene_bvh_read")
         return nodes, order
 
-    def update_vertices(self, positions):
+    def update_vertices(self, positions, rebuild_above=None):
         """Moves the scene's triangles in place (rt_hip.h, rt_hip_scene_update_vertices): positions of shape (n, 3, 3) -- triangle,
         corner, xyz, in scene triangle order -- as a float64 torch tensor on the scene's device (taken where it lies, no host
         copy) or a numpy array (staged by the shim).  Synchronous.  The records are recomputed and the hierarchy REFITTED on the
-        device: frames, bytes and counters equal a freshly created scene's; bvh_info()["tree_cost"] reports the refitted tree's
-        cost, and a caller recreates the scene when that has drifted too far from a fresh tree's.  A Temporal keeps its history
+        device: frames, bytes and counters equal a freshly created scene's.  rebuild_above: None leaves the refitted tree as it
+        is; a ratio >= 1 ends the update with maintain_bvh(rebuild_above), whose result is returned (None otherwise): the tree
+        is rebuilt in place when the refit has made it that much dearer than it was built.  A Temporal keeps its history
         across an update when its next frame() is given the positions from before it (prev_positions); without them, and for a
         Preview, which assumes a static scene, reset after an update.  Open accumulations refuse the update (close them first).
         self.scene keeps the vertices the scene was created from."""
@@ -129,12 +130,40 @@ class GpuScene:
                 torch.cuda.current_stream(t.device).synchronize()
             # (a host tensor, or one on another device, goes to the device entry all the same: the shim refuses it)
             _check(self.shim.rt_hip_scene_update_vertices(self.handle, C.c_void_p(t.data_ptr()), n), "rt_hip_scene_update_vertices")
-            return
-        import numpy as np
-        a = np.ascontiguousarray(positions, dtype=np.float64)
-        if a.shape != (n, 3, 3):
-            raise ValueError(f"update_vertices: shape ({n}, 3, 3) is expected, not {a.shape}")
-        _check(self.shim.rt_hip_scene_update_vertices_host(self.handle, a.ctypes.data, n), "rt_hip_scene_update_vertices_host")
+        else:
+            import numpy as np
+            a = np.ascontiguousarray(positions, dtype=np.float64)
+            if a.shape != (n, 3, 3):
+                raise ValueError(f"update_vertices: shape ({n}, 3, 3) is expected, not {a.shape}")
+            _check(self.shim.rt_hip_scene_update_vertices_host(self.handle, a.ctypes.data, n), "rt_hip_scene_update_vertices_host")
+        return None if rebuild_above is None else self.maintain_bvh(rebuild_above)
+
+    def bvh_cost(self):
+        """the expected walk cost of the scene's current tree (refitted, if it was), evaluated on the device by the fixed
+        reduction tree rt_hip.h states (rt_hip_scene_bvh_cost): 8 bytes come back, not the nodes"""
+        cost = C.c_double(0)
+        _check(self.shim.rt_hip_scene_bvh_cost(self.handle, C.byref(cost)), "rt_hip_scene_bvh_cost")
+        return cost.value
+
+    def rebuild_bvh(self):
+        """Rebuilds the triangle hierarchy in place with the device builder, over the triangles as they are now
+        (rt_hip_scene_rebuild_bvh): afterwards tree, kernel_name(), frames, bytes, counters and queries equal those of
+        GpuScene(..., bvh="device") created from the same positions.  Handles stay; open accumulations refuse it."""
+        _check(self.shim.rt_hip_scene_rebuild_bvh(self.handle), "rt_hip_scene_rebuild_bvh")
+
+    def rebuild_info(self):
+        """{"rebuilds", "last_seconds", "built_cost": bvh_cost() of the tree as it was last built}"""
+        k, s, c = C.c_uint64(0), C.c_double(0), C.c_double(0)
+        _check(self.shim.rt_hip_scene_rebuild_info(self.handle, C.byref(k), C.byref(s), C.byref(c)), "rt_hip_scene_rebuild_info")
+        return {"rebuilds": k.value, "last_seconds": s.value, "built_cost": c.value}
+
+    def maintain_bvh(self, max_ratio):
+        """Prices the current tree on the device and rebuilds it in place iff bvh_cost() / built_cost > max_ratio (finite, >= 1)
+        -> {"cost_ratio", "rebuilt"} (rt_hip_scene_maintain_bvh)"""
+        ratio, rebuilt = C.c_double(0), C.c_int(0)
+        _check(self.shim.rt_hip_scene_maintain_bvh(self.handle, float(max_ratio), C.byref(ratio), C.byref(rebuilt)),
+               "rt_hip_scene_maintain_bvh")
+        return {"cost_ratio": ratio.value, "rebuilt": bool(rebuilt.value)}
 
     def spheres(self):
         """the scene's spheres as they are now: a float64 (n_objects, 4) device tensor, cx cy cz radius in object order -- what the
