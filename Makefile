@@ -22,7 +22,9 @@ CFLAGS  := -std=c99 -D_DEFAULT_SOURCE -O2 -ffp-contract=off -fPIC -Wall -Wno-unu
 
 SHIM    := $(CSRC)/librt_hip.so
 # the device code is ONE translation unit, pt_kernel.hip, split by topic into the pt_*.h headers it includes
-KERNEL_SRC := $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip $(wildcard $(CSRC)/pt_*.h) $(CSRC)/bvh_build.h $(CSRC)/scene_spheres.h $(CSRC)/rt_staging.h $(INC)/rt_hip.h $(INC)/rt_rng.h
+# the four sources every build of the shim compiles, in this order
+SHIM_SRC := $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip
+KERNEL_SRC := $(SHIM_SRC) $(wildcard $(CSRC)/pt_*.h) $(CSRC)/bvh_build.h $(CSRC)/scene_spheres.h $(CSRC)/rt_staging.h $(INC)/rt_hip.h $(INC)/rt_rng.h
 HOSTLIB := $(HOST)/libraytracer_amd.so
 CLI     := $(HOST)/raytracer
 
@@ -36,7 +38,7 @@ oracle: host
 
 shim: $(SHIM)
 $(SHIM): $(KERNEL_SRC)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SHIM_SRC) -lrccl
 
 # diagnostic build: wave-level event counters in stats[4..] and the exhaustive re-checks of every conservative rule
 # (filter, fp32 pre-tests, bounding-sphere probe, hull facets).  Not the product: only tests/test_gpu_diag.py
@@ -44,7 +46,7 @@ $(SHIM): $(KERNEL_SRC)
 # the GPU box with the snapshot like the other binaries (git-ignored, not gpurun-ignored).
 shim-diag: $(CSRC)/librt_hip_diag.so
 $(CSRC)/librt_hip_diag.so: $(KERNEL_SRC)
-	$(HIPCC) $(HIPFLAGS) -DPT_DIAG -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+	$(HIPCC) $(HIPFLAGS) -DPT_DIAG -shared -o $@ $(SHIM_SRC) -lrccl
 
 # development build (-DPT_DEV_KERNELS): the product plus what only A/B runs and tests of the fallbacks need -- pt_render_tiles_v0
 # (the literal single-phase scan), RT_HIP_KERNEL_VARIANT (other arms of the pick table), RT_HIP_FORCE_BIG, RT_HIP_NO_BIG_PRUNE,
@@ -53,7 +55,7 @@ $(CSRC)/librt_hip_diag.so: $(KERNEL_SRC)
 # child processes of the tests and by tools/; built by `make all` so that it travels to the GPU box with the snapshot.
 shim-dev: $(CSRC)/librt_hip_dev.so
 $(CSRC)/librt_hip_dev.so: $(KERNEL_SRC)
-	$(HIPCC) $(HIPFLAGS) -DPT_DEV_KERNELS -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+	$(HIPCC) $(HIPFLAGS) -DPT_DEV_KERNELS -shared -o $@ $(SHIM_SRC) -lrccl
 
 # the A/B knob's other arm (-DPT_DIR_PARK=0: direction retries carried in their lane, four rounds a trip, as before the retry
 # stack).  Not the product: tests/test_gpu_dir_park.py renders one case with it in a child process and asks for the shipped
@@ -61,7 +63,7 @@ $(CSRC)/librt_hip_dev.so: $(KERNEL_SRC)
 shim-park0: $(CSRC)/variants/librt_hip_park0.so
 $(CSRC)/variants/librt_hip_park0.so: $(KERNEL_SRC)
 	@mkdir -p $(CSRC)/variants
-	$(HIPCC) $(HIPFLAGS) -DPT_DIR_PARK=0 -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+	$(HIPCC) $(HIPFLAGS) -DPT_DIR_PARK=0 -shared -o $@ $(SHIM_SRC) -lrccl
 
 # the other arm of the matrix-pipe filter's A/B (-DPT_MFMA16=0: phase 1 of every sphere in the packed-fp32 loop).  Not the product:
 # tests/test_gpu_mfma16.py renders with it in a child process and asks for the shipped build's frames and counters bit for bit, and
@@ -69,14 +71,14 @@ $(CSRC)/variants/librt_hip_park0.so: $(KERNEL_SRC)
 shim-mfma0: $(CSRC)/variants/librt_hip_mfma0.so
 $(CSRC)/variants/librt_hip_mfma0.so: $(KERNEL_SRC)
 	@mkdir -p $(CSRC)/variants
-	$(HIPCC) $(HIPFLAGS) -DPT_MFMA16=0 -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+	$(HIPCC) $(HIPFLAGS) -DPT_MFMA16=0 -shared -o $@ $(SHIM_SRC) -lrccl
 
 # the diagnostic build of that arm: tests/test_gpu_mfma16.py compares the two diagnostic builds' candidate counts (what the matrix
 # pipe keeps and the packed loop drops, per filter evaluation)
 shim-diag-mfma0: $(CSRC)/variants/librt_hip_diag_mfma0.so
 $(CSRC)/variants/librt_hip_diag_mfma0.so: $(KERNEL_SRC)
 	@mkdir -p $(CSRC)/variants
-	$(HIPCC) $(HIPFLAGS) -DPT_DIAG -DPT_MFMA16=0 -shared -o $@ $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+	$(HIPCC) $(HIPFLAGS) -DPT_DIAG -DPT_MFMA16=0 -shared -o $@ $(SHIM_SRC) -lrccl
 
 host: $(HOSTLIB) $(CLI)
 $(HOSTLIB): $(HOST_SRC) $(HOST_HDR) $(SHIM)
@@ -98,5 +100,5 @@ clean:
 #   make variant NAME=tri4 DEFS="-DPT_MIN_WAVES_TRI=4"   ->  raytracer.c_amd/csrc/variants/librt_hip_tri4.so
 variant:
 	@mkdir -p $(CSRC)/variants
-	$(HIPCC) $(HIPFLAGS) $(DEFS) -shared -o $(CSRC)/variants/librt_hip_$(NAME).so $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip -lrccl
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -shared -o $(CSRC)/variants/librt_hip_$(NAME).so $(SHIM_SRC) -lrccl
 .PHONY: variant

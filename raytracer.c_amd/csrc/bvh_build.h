@@ -704,6 +704,41 @@ BVH_HD inline void scene_triangle_corner(const double *g, int k, double *p)
     p[a] = k == 0 ? g[a] : g[a] + g[3 * k + a];
 }
 
+/* What a scene derives from the bounds of its triangles' corners, in one text for rt_hip_scene_create and
+ * rt_hip_scene_update_vertices (host code on both sides; tests/mesh_bounds_harness.cpp is its CPU test).  The two reductions --
+ * lo, hi over the corners, then r2 = the largest squared distance of a corner from scene_mesh_centre(lo, hi) -- are the
+ * caller's: a host loop at creation, scene_update_check and scene_update_triangles on the device. */
+struct SceneMeshBounds
+{
+  double c[3] = {0, 0, 0}; /* bounding sphere of every triangle (bvh_probe): the middle of the corners' bounds */
+  double R = -1;           /* its radius; < 0: no triangles */
+  double c_norm = 0;       /* |c|, rounded up */
+  bool round = false;      /* the sphere's silhouette is no larger than the mean silhouette of the triangles' box */
+  double tau = -1;         /* the margin of pt_build_hull_flags; < 0: no hull flags */
+};
+
+inline void scene_mesh_centre(const double lo[3], const double hi[3], double c[3])
+{
+  for (int a = 0; a < 3; a++)
+    c[a] = 0.5 * lo[a] + 0.5 * hi[a];
+}
+
+/* The radius is the farthest corner's distance with slack for the roundings of e1, e2 and of the exact test's own barycentric
+ * limits; non-finite input gives a bound that keeps every ray (and `round` is whatever the comparison says: false for NaN).
+ * tau = 2^-43 x the triangles' extent -- 64 u sigma_max extent with u = 2^-53 and the shape limit sigma_max = 16, well above the
+ * residual of a facet's own corners and of coplanar neighbours (~u sigma extent) -- unless the extent is too large for it. */
+inline void scene_mesh_bounds(const double lo[3], const double hi[3], double r2, SceneMeshBounds *b)
+{
+  scene_mesh_centre(lo, hi, b->c);
+  b->R = std::sqrt(r2) * (1.0 + 1e-9) + 1e-300;
+  if (!(b->R < HUGE_VAL))
+    b->R = HUGE_VAL;
+  b->c_norm = std::sqrt(b->c[0] * b->c[0] + b->c[1] * b->c[1] + b->c[2] * b->c[2]) * (1.0 + 1e-12);
+  const double ea = hi[0] - lo[0], eb = hi[1] - lo[1], ec = hi[2] - lo[2], extent = b->c_norm + b->R;
+  b->round = 3.14159265358979 * b->R * b->R <= 0.5 * (ea * eb + eb * ec + ec * ea);
+  b->tau = b->R < 1e150 ? 1.1368683772161603e-13 * extent : -1.0;
+}
+
 /* ---- a scene's spheres moved in place (scene_update.hip, rt_hip_scene_update_spheres) ----
  * What a scene derives from its spheres, in one text for the host (scene_create_impl, rt_hip_shim.hip), the device
  * (k_update_spheres, scene_update.hip) and the CPU test of both (tests/sphere_update_harness.cpp, through scene_spheres.h).  Input

@@ -391,14 +391,92 @@ std::atomic<uint32_t> g_fail_alloc{0};
 /* the kernel the calling thread's last rt_hip_render_tiles* launched (rt_hip_last_launch_kernel) */
 thread_local int g_last_kernel = -1;
 
+size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+/* every launch that reads the set is done: its build, and the last read of every stream that ever read it */
+hipError_t table_set_wait(const TableSet &t)
+{
+  hipError_t first = t.built ? hipEventSynchronize(t.built) : hipSuccess;
+  for (auto &r : t.readers) /* all of them, whatever one of them says */
+    if (const hipError_t e = hipEventSynchronize(r.second); first == hipSuccess)
+      first = e;
+  return first;
+}
+
+/* the set's events and, where it owns them, its tables; the caller has waited */
+void table_set_free(TableSet &t)
+{
+  for (auto &r : t.readers)
+    (void)hipEventDestroy(r.second);
+  if (t.built)
+    (void)hipEventDestroy(t.built);
+  if (t.owned)
+  {
+    (void)hipFree(t.filt);
+    (void)hipFree(t.bvh_nodes);
+  }
+}
+
+/* the one refusal of no scene, and of a scene that a mutation left half written */
+int scene_usable(const RtHipScene *scene, const char *who)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "%s: scene is NULL (a scene is required)", who);
+  if (scene->unusable)
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an update of its vertices or spheres failed half way (rt_hip_scene_update_*)");
+  return RT_HIP_OK;
+}
+
+/* A scene about to be written -- its vertices, its spheres or its hierarchy -- after scene_usable() and the mutation's own
+ * refusals.  The constructor makes the scene's device current (scope.status says how that went); then, in this order:
+ *   lock.lock()      table_mutex, held until the scope ends
+ *   idle()           refuses while accumulations are alive or a launch is being submitted; `change` is what they must not see
+ *   drain()          no launch may still read what is about to change: every table set's build and readers
+ *   stale()          writing begins: filter, fp32 nodes and tri32 records are rebuilt by the next launch (acquire_tables)
+ *   broke(e, what)   the one exit of a HIP failure after that: only rt_hip_scene_destroy is allowed from here on */
+struct SceneWrite
+{
+  RtHipScene *scene;
+  const char *change;
+  DeviceScope scope;
+  std::unique_lock<std::mutex> lock;
+  SceneWrite(RtHipScene *s, const char *change_) : scene(s), change(change_), scope(s->device), lock(s->table_mutex, std::defer_lock) {}
+  int idle() const
+  {
+    if (scene->live_accums.load() > 0)
+      return fail(RT_HIP_EINVAL, "%d accumulation(s) on this scene are alive: destroy them before %s", scene->live_accums.load(), change);
+    for (const TableSet &t : scene->tables)
+      if (t.users > 0)
+        return fail(RT_HIP_EINVAL, "a launch of this scene is being submitted");
+    return RT_HIP_OK;
+  }
+  int drain() const
+  {
+    for (const TableSet &t : scene->tables)
+      HIP_TRY(table_set_wait(t));
+    return RT_HIP_OK;
+  }
+  void stale() const
+  {
+    for (TableSet &t : scene->tables)
+      t.near_R = -1.0;
+  }
+  int broke(hipError_t e, const char *what) const
+  {
+    (void)hipGetLastError();
+    scene->unusable = true;
+    return fail(RT_HIP_ERUNTIME, "%s: %s; the scene is unusable now (destroy it)", what, hipGetErrorString(e));
+  }
+};
+
 /* The table set of `scene` for `near_R`, ready to be read by work submitted to `stream` after this
  * call (see TableSet).  *slot identifies it for release_tables(). */
 int acquire_tables(const RtHipScene *scene, double near_R, hipStream_t stream, float **filt, float **bvh_nodes, size_t *slot)
 {
   std::lock_guard<std::mutex> lock(scene->table_mutex);
   std::vector<TableSet> &tables = scene->tables;
-  if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an update of its vertices or spheres failed half way (rt_hip_scene_update_*)");
+  if (const int rc = scene_usable(scene, "a launch"))
+    return rc;
   for (size_t k = 0; k < tables.size(); k++)
     if (tables[k].near_R == near_R)
     {
@@ -415,11 +493,7 @@ int acquire_tables(const RtHipScene *scene, double near_R, hipStream_t stream, f
     if (tables[j].near_R == -1.0 && tables[j].users == 0)
       k = j; /* a set whose build failed, or that an update of the vertices left stale: rebuilt in place */
   if (k < tables.size())
-  {
-    HIP_TRY(hipEventSynchronize(tables[k].built));
-    for (auto &r : tables[k].readers)
-      HIP_TRY(hipEventSynchronize(r.second));
-  }
+    HIP_TRY(table_set_wait(tables[k]));
   else if (k < RT_TABLE_SETS)
   {
     TableSet t;
@@ -442,11 +516,7 @@ int acquire_tables(const RtHipScene *scene, double near_R, hipStream_t stream, f
     hipError_t e = hipEventCreateWithFlags(&t.built, hipEventDisableTiming);
     if (e != hipSuccess)
     {
-      if (t.owned)
-      {
-        (void)hipFree(t.filt);
-        (void)hipFree(t.bvh_nodes);
-      }
+      table_set_free(t);
       return fail(RT_HIP_ERUNTIME, "hipEventCreate: %s", hipGetErrorString(e));
     }
     tables.push_back(t);
@@ -461,9 +531,7 @@ int acquire_tables(const RtHipScene *scene, double near_R, hipStream_t stream, f
     if (k == tables.size())
       return fail(RT_HIP_ELIMIT, "more than %d launches of one scene with different camera distances are being submitted at once",
                   RT_TABLE_SETS);
-    HIP_TRY(hipEventSynchronize(tables[k].built));
-    for (auto &r : tables[k].readers) /* every stream that ever read this set, not only the last one to release it */
-      HIP_TRY(hipEventSynchronize(r.second));
+    HIP_TRY(table_set_wait(tables[k]));
   }
   TableSet &t = tables[k];
   t.near_R = near_R;
@@ -848,6 +916,68 @@ void take_sphere_bounds(RtHipScene *sc, const SceneSphereBounds &sb)
   sc->reach_spheres = sb.reach_spheres;
 }
 
+/* its twin for the triangles -- at creation, and after every update of the vertices */
+void take_mesh_bounds(RtHipScene *sc, const SceneMeshBounds &mb)
+{
+  for (int a = 0; a < 3; a++)
+    sc->mesh_c[a] = mb.c[a];
+  sc->mesh_R = mb.R;
+  sc->mesh_c_norm = mb.c_norm;
+  sc->view.mesh_round = mb.round ? 1u : 0u;
+}
+
+/* hull facets (pt_build_hull_flags) with the margin scene_mesh_bounds gave, where there is one and the triangles are few enough;
+ * tri_object's bits are clear before.  Enqueues on the null stream: the caller waits. */
+hipError_t scene_hull_flags(RtHipScene *sc, double tau)
+{
+  const uint32_t n = sc->view.n_triangles;
+  sc->hull_flags = false;
+  if (n == 0 || n > PT_HULL_MAX_TRIS || tau < 0)
+    return hipSuccess;
+  const hipError_t e =
+      pt_launch_build_hull_flags(sc->view.tri_geom, sc->view.tri_normal, n, tau, const_cast<uint32_t *>(sc->view.tri_object), nullptr);
+  sc->hull_flags = e == hipSuccess;
+  return e;
+}
+
+/* the device builder over tri_geom (device memory, n x 9) with the refusals that creation and rebuild share */
+int build_device_tree(const double *tri_geom, size_t n, BvhDeviceTree *tree)
+{
+  const hipError_t be = bvh_device_build(tri_geom, (uint32_t)n, tree);
+  if (be != hipSuccess && tree->failure)
+    return fail(RT_HIP_ERUNTIME, "device hierarchy builder: %s", tree->failure);
+  HIP_TRY(be);
+  if (tree->depth > PT_BVH_STACK)
+    return fail(RT_HIP_ELIMIT, "triangle hierarchy depth %d exceeds the traversal stack (%d)", tree->depth, PT_BVH_STACK);
+  if (tree->n_nodes == 0)
+    return fail(RT_HIP_ERUNTIME, "device hierarchy builder: a tree without nodes");
+  return RT_HIP_OK;
+}
+
+/* A device-built tree into the scene: nodes and order out of the builder's workspace to where view.bvh_src and view.bvh_tri point
+ * (room for tree.n_nodes is the caller's business), the leaf-ordered geometry gathered from view.tri_geom, a wait for the null
+ * stream, then the scalars that describe the tree. */
+hipError_t install_device_tree(RtHipScene *sc, const BvhDeviceTree &tree)
+{
+  const uint32_t n = sc->view.n_triangles;
+  hipError_t e = hipMemcpy(const_cast<double *>(sc->view.bvh_src), tree.nodes, (size_t)tree.n_nodes * PT_BVH_SRC_DOUBLES * 8, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(const_cast<uint32_t *>(sc->view.bvh_tri), tree.order, (size_t)n * 4, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess)
+    e = bvh_device_gather_leaf(sc->view.tri_geom, sc->view.bvh_tri, n, const_cast<double *>(sc->view.tri_geom_leaf));
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess)
+    return e;
+  sc->view.n_bvh_nodes = tree.n_nodes;
+  sc->view.bvh_depth = (uint32_t)tree.depth;
+  sc->bvh_builder = RT_HIP_BVH_DEVICE;
+  sc->bvh_max_depth = (uint32_t)tree.max_depth;
+  sc->bvh_build_seconds = 1e-3 * tree.build_ms;
+  sc->bvh_nodes_bytes = (size_t)tree.n_nodes * PT_BVH_NODE_WORDS * 4;
+  return hipSuccess;
+}
+
 int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
                       int device, uint32_t bvh_builder, RtHipScene **out_scene)
 {
@@ -950,46 +1080,29 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     }
   }
 
-  /* ---- bounding sphere of all triangles, as the kernels see them (v0, v0 + e1, v0 + e2): centre = middle of
-   * their bounds, radius = the farthest corner, with slack for the roundings of e1, e2 and of the exact test's
-   * own barycentric limits ---- */
-  double mesh_c[3] = {0, 0, 0}, mesh_R = -1;
-  bool mesh_round = false; /* the sphere's silhouette is no larger than the mean silhouette of the triangles' box */
+  /* ---- bounding sphere of all triangles, as the kernels see them (v0, v0 + e1, v0 + e2): the two reductions here, what follows
+   * them in bvh_build.h's one text, as an update of the vertices derives it again ---- */
+  SceneMeshBounds mb;
   if (n_tri != 0)
   {
-    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    auto corner = [&](size_t tri, int k, double *p) {
-      const double *g = &tgeom[9 * tri];
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL}, c[3], p[3], r2 = 0;
+    for (size_t i = 0; i < 3 * n_tri; i++)
+    {
+      scene_triangle_corner(&tgeom[9 * (i / 3)], (int)(i % 3), p);
       for (int a = 0; a < 3; a++)
-        p[a] = k == 0 ? g[a] : g[a] + g[3 * k + a];
-    };
-    for (size_t i = 0; i < n_tri; i++)
-      for (int k = 0; k < 3; k++)
       {
-        double p[3];
-        corner(i, k, p);
-        for (int a = 0; a < 3; a++)
-        {
-          lo[a] = std::fmin(lo[a], p[a]);
-          hi[a] = std::fmax(hi[a], p[a]);
-        }
+        lo[a] = std::fmin(lo[a], p[a]);
+        hi[a] = std::fmax(hi[a], p[a]);
       }
-    for (int a = 0; a < 3; a++)
-      mesh_c[a] = 0.5 * lo[a] + 0.5 * hi[a];
-    double r2 = 0;
-    for (size_t i = 0; i < n_tri; i++)
-      for (int k = 0; k < 3; k++)
-      {
-        double p[3];
-        corner(i, k, p);
-        const double dx = p[0] - mesh_c[0], dy = p[1] - mesh_c[1], dz = p[2] - mesh_c[2];
-        r2 = std::fmax(r2, dx * dx + dy * dy + dz * dz);
-      }
-    mesh_R = std::sqrt(r2) * (1.0 + 1e-9) + 1e-300;
-    if (!(mesh_R < HUGE_VAL)) /* non-finite input: a bound that keeps every ray */
-      mesh_R = HUGE_VAL;
-    const double a = hi[0] - lo[0], b = hi[1] - lo[1], c = hi[2] - lo[2];
-    mesh_round = 3.14159265358979 * mesh_R * mesh_R <= 0.5 * (a * b + b * c + c * a); /* false for NaN / inf */
+    }
+    scene_mesh_centre(lo, hi, c);
+    for (size_t i = 0; i < 3 * n_tri; i++)
+    {
+      scene_triangle_corner(&tgeom[9 * (i / 3)], (int)(i % 3), p);
+      const double dx = p[0] - c[0], dy = p[1] - c[1], dz = p[2] - c[2];
+      r2 = std::fmax(r2, dx * dx + dy * dy + dz * dz);
+    }
+    scene_mesh_bounds(lo, hi, r2, &mb);
   }
 
   /* ---- hierarchy over the triangles ---- */
@@ -1014,14 +1127,10 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
       HIP_TRY(build_scope.status);
       HIP_TRY(dgeom.alloc(tgeom.size() * 8));
       HIP_TRY(hipMemcpy(dgeom.ptr, tgeom.data(), tgeom.size() * 8, hipMemcpyHostToDevice));
-      const hipError_t be = bvh_device_build(dgeom.at<double>(), (uint32_t)n_tri, &dtree);
-      if (be != hipSuccess && dtree.failure)
-        return fail(RT_HIP_ERUNTIME, "device hierarchy builder: %s", dtree.failure);
-      HIP_TRY(be);
-      n_bvh_nodes = dtree.n_nodes;
-      bvh_depth = dtree.depth;
-      bvh_max_depth = dtree.max_depth;
-      bvh_build_seconds = 1e-3 * dtree.build_ms;
+      const int rc = build_device_tree(dgeom.at<double>(), n_tri, &dtree);
+      if (rc)
+        return rc;
+      n_bvh_nodes = dtree.n_nodes; /* the blob is sized by it; install_device_tree gives the scene the rest */
     }
     else
     {
@@ -1041,33 +1150,32 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
       bvh_depth = bvh.depth;
       bvh_max_depth = bvh.max_depth;
       bvh_build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (bvh_depth > PT_BVH_STACK)
+        return fail(RT_HIP_ELIMIT, "triangle hierarchy depth %d exceeds the traversal stack (%d)", bvh_depth, PT_BVH_STACK);
     }
-    if (bvh_depth > PT_BVH_STACK)
-      return fail(RT_HIP_ELIMIT, "triangle hierarchy depth %d exceeds the traversal stack (%d)", bvh_depth, PT_BVH_STACK);
   }
   std::vector<double> tgeom_leaf(9 * bvh.order.size()); /* host builder only: the device builder gathers on the device */
   for (size_t k = 0; k < bvh.order.size(); k++)
     memcpy(&tgeom_leaf[9 * k], &tgeom[9 * (size_t)bvh.order[k]], 9 * sizeof(double));
 
   /* ---- one device blob ---- */
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t off_geom = 0;
-  const size_t off_mat = off_geom + pad(geom.size() * 8);
-  const size_t off_craw = off_mat + pad(mat.size() * 8);
-  const size_t off_geom4 = off_craw + pad(craw.size() * 8);
-  const size_t off_tgeom = off_geom4 + pad(geom4.size() * 8);
-  const size_t off_tnorm = off_tgeom + pad(tgeom.size() * 8);
-  const size_t off_ttex = off_tnorm + pad(tnorm.size() * 8);
-  const size_t off_tobj = off_ttex + pad(ttex.size() * 8);
-  const size_t off_filt = off_tobj + pad(tobj.size() * 4);
+  const size_t off_mat = off_geom + pad256(geom.size() * 8);
+  const size_t off_craw = off_mat + pad256(mat.size() * 8);
+  const size_t off_geom4 = off_craw + pad256(craw.size() * 8);
+  const size_t off_tgeom = off_geom4 + pad256(geom4.size() * 8);
+  const size_t off_tnorm = off_tgeom + pad256(tgeom.size() * 8);
+  const size_t off_ttex = off_tnorm + pad256(tnorm.size() * 8);
+  const size_t off_tobj = off_ttex + pad256(ttex.size() * 8);
+  const size_t off_filt = off_tobj + pad256(tobj.size() * 4);
   /* + 1 pair: the scan's software pipeline reads one pair past the end */
   const size_t filt_bytes = pt_filt_bytes((uint32_t)n_spheres, (uint32_t)n_tri);
-  const size_t off_bvh_src = off_filt + pad(filt_bytes);
-  const size_t off_bvh_nodes = off_bvh_src + pad(n_bvh_nodes * PT_BVH_SRC_DOUBLES * 8);
+  const size_t off_bvh_src = off_filt + pad256(filt_bytes);
+  const size_t off_bvh_nodes = off_bvh_src + pad256(n_bvh_nodes * PT_BVH_SRC_DOUBLES * 8);
   const size_t bvh_nodes_bytes = n_bvh_nodes * PT_BVH_NODE_WORDS * 4;
-  const size_t off_bvh_tri = off_bvh_nodes + pad(bvh_nodes_bytes);
-  const size_t off_tgeom_leaf = off_bvh_tri + pad(n_tri * 4);
-  const size_t total = off_tgeom_leaf + pad(9 * n_tri * 8) + 256;
+  const size_t off_bvh_tri = off_bvh_nodes + pad256(bvh_nodes_bytes);
+  const size_t off_tgeom_leaf = off_bvh_tri + pad256(n_tri * 4);
+  const size_t total = off_tgeom_leaf + pad256(9 * n_tri * 8) + 256;
 
   DeviceScope scope(device);
   HIP_TRY(scope.status);
@@ -1082,6 +1190,11 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     return fail(RT_HIP_ENOMEM, "hipMalloc(%zu): %s", total, hipGetErrorString(e));
   }
   char *base = static_cast<char *>(sc->blob);
+  sc->view.bvh_src = reinterpret_cast<const double *>(base + off_bvh_src);
+  sc->view.bvh_tri = reinterpret_cast<const uint32_t *>(base + off_bvh_tri);
+  sc->view.tri_geom_leaf = reinterpret_cast<const double *>(base + off_tgeom_leaf);
+  sc->view.tri_geom = reinterpret_cast<const double *>(base + off_tgeom);
+  sc->view.n_triangles = (uint32_t)n_tri;
   auto up = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
     return bytes ? hipMemcpy(base + off, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
   };
@@ -1097,15 +1210,13 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   if (e == hipSuccess) e = up(off_bvh_src, bvh.nodes.data(), bvh.nodes.size() * 8);
   if (e == hipSuccess) e = up(off_bvh_tri, bvh.order.data(), bvh.order.size() * 4);
   if (e == hipSuccess) e = up(off_tgeom_leaf, tgeom_leaf.data(), tgeom_leaf.size() * 8);
+  sc->view.n_bvh_nodes = (uint32_t)n_bvh_nodes;
+  sc->view.bvh_depth = (uint32_t)bvh_depth;
+  sc->bvh_builder = bvh_builder;
+  sc->bvh_max_depth = (uint32_t)bvh_max_depth;
+  sc->bvh_build_seconds = bvh_build_seconds;
   if (e == hipSuccess && dtree.workspace)
-  { /* the device builder's tree: nodes and order from its workspace, the leaf-ordered geometry gathered in place */
-    e = hipMemcpy(base + off_bvh_src, dtree.nodes, n_bvh_nodes * PT_BVH_SRC_DOUBLES * 8, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(base + off_bvh_tri, dtree.order, n_tri * 4, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess)
-      e = bvh_device_gather_leaf(reinterpret_cast<const double *>(base + off_tgeom), reinterpret_cast<const uint32_t *>(base + off_bvh_tri),
-                                 (uint32_t)n_tri, reinterpret_cast<double *>(base + off_tgeom_leaf));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-  }
+    e = install_device_tree(sc, dtree);
   if (e != hipSuccess)
   {
     (void)hipFree(sc->blob);
@@ -1114,38 +1225,20 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   }
   sc->view.entry_src = reinterpret_cast<const double *>(base + off_geom);
   sc->view.filt = reinterpret_cast<float *>(base + off_filt);
-  sc->view.bvh_src = reinterpret_cast<const double *>(base + off_bvh_src);
   sc->view.bvh_nodes = reinterpret_cast<float *>(base + off_bvh_nodes);
-  sc->view.bvh_tri = reinterpret_cast<const uint32_t *>(base + off_bvh_tri);
-  sc->view.tri_geom_leaf = reinterpret_cast<const double *>(base + off_tgeom_leaf);
-  sc->view.n_bvh_nodes = (uint32_t)n_bvh_nodes;
-  sc->view.bvh_depth = (uint32_t)bvh_depth;
-  sc->bvh_builder = bvh_builder;
-  sc->bvh_max_depth = (uint32_t)bvh_max_depth;
-  sc->bvh_build_seconds = bvh_build_seconds;
-  for (int a = 0; a < 3; a++)
-    sc->mesh_c[a] = mesh_c[a];
-  sc->mesh_R = mesh_R;
-  sc->mesh_c_norm = std::sqrt(mesh_c[0] * mesh_c[0] + mesh_c[1] * mesh_c[1] + mesh_c[2] * mesh_c[2]) * (1.0 + 1e-12);
+  take_mesh_bounds(sc, mb);
   sc->filt_bytes = filt_bytes;
   sc->bvh_nodes_bytes = bvh_nodes_bytes;
   sc->bvh_node_capacity = (uint32_t)n_bvh_nodes;
   sc->view.material = reinterpret_cast<const double *>(base + off_mat);
   sc->view.color_raw = reinterpret_cast<const double *>(base + off_craw);
   sc->view.geom4 = reinterpret_cast<const double *>(base + off_geom4);
-  sc->view.tri_geom = reinterpret_cast<const double *>(base + off_tgeom);
   sc->view.tri_normal = reinterpret_cast<const double *>(base + off_tnorm);
   sc->view.tri_tex = reinterpret_cast<const double *>(base + off_ttex);
   sc->view.tri_object = reinterpret_cast<const uint32_t *>(base + off_tobj);
-  if (n_tri != 0 && n_tri <= PT_HULL_MAX_TRIS && mesh_R >= 0 && mesh_R < 1e150)
   {
-    /* hull facets (pt_build_hull_flags): tau = 2^-43 x the triangles' extent -- 64 u sigma_max extent with u = 2^-53
-     * and the shape limit sigma_max = 16, well above the residual of a facet's own corners and of coplanar
-     * neighbours (~u sigma extent) */
-    const double extent = sc->mesh_c_norm + mesh_R;
-    hipError_t he = pt_launch_build_hull_flags(sc->view.tri_geom, sc->view.tri_normal, (uint32_t)n_tri,
-                                               1.1368683772161603e-13 * extent, reinterpret_cast<uint32_t *>(base + off_tobj), nullptr);
-    if (he == hipSuccess)
+    hipError_t he = scene_hull_flags(sc, mb.tau);
+    if (he == hipSuccess && sc->hull_flags)
       he = hipDeviceSynchronize();
     if (he != hipSuccess)
     {
@@ -1153,13 +1246,10 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
       delete sc;
       return fail(RT_HIP_ERUNTIME, "hull flags: %s", hipGetErrorString(he));
     }
-    sc->hull_flags = true;
   }
   sc->view.n_spheres = (uint32_t)n_spheres;
   sc->view.n_meshes = (uint32_t)n_meshes;
-  sc->view.n_triangles = (uint32_t)n_tri;
   sc->view.any_checker = any_checker ? 1u : 0u;
-  sc->view.mesh_round = mesh_round ? 1u : 0u;
   sc->view.any_refract = any_refract ? 1u : 0u;
 #ifdef PT_DEV_KERNELS
   {
@@ -3438,18 +3528,8 @@ void rt_hip_scene_destroy(RtHipScene *scene)
     DeviceScope scope(scene->device);
     for (TableSet &t : scene->tables)
     {
-      if (t.built) (void)hipEventSynchronize(t.built);
-      for (auto &r : t.readers)
-      {
-        (void)hipEventSynchronize(r.second);
-        (void)hipEventDestroy(r.second);
-      }
-      if (t.built) (void)hipEventDestroy(t.built);
-      if (t.owned)
-      {
-        (void)hipFree(t.filt);
-        (void)hipFree(t.bvh_nodes);
-      }
+      (void)table_set_wait(t);
+      table_set_free(t);
     }
     if (scene->park_ws)
     { /* every launch of this scene must be past its last ring access before the pool can go */
@@ -3497,7 +3577,7 @@ int rt_hip_scene_hull_facets(const RtHipScene *scene, uint32_t *n_plus, uint32_t
 }
 
 /* ---- moving the triangles in place: new records and a refitted hierarchy (scene_update.hip), then the scalars and flags that
- * scene_create_impl derives from them, by the same formulas.  Nothing of the scene is written before every refusal has been
+ * scene_create_impl derives from them, by bvh_build.h's one text (scene_mesh_bounds).  Nothing of the scene is written before every refusal has been
  * ruled out; once writing has begun a HIP failure leaves the scene unusable. */
 namespace
 {
@@ -3523,17 +3603,15 @@ int scene_cost_of(const RtHipScene *scene, const double *nodes, uint32_t n_nodes
 {
   if (n_nodes > scene->cost_ws_nodes)
   {
-    double *ws = nullptr;
+    DeviceBuffer ws;
     const size_t bytes = scene_tree_cost_ws_doubles(n_nodes) * sizeof(double);
-    if (hipMalloc(&ws, bytes) != hipSuccess)
-    {
-      (void)hipGetLastError();
+    if (ws.alloc(bytes) != hipSuccess)
       return fail(RT_HIP_ENOMEM, "the cost kernel's workspace (%zu bytes)", bytes);
-    }
     if (scene->cost_ws)
       (void)hipFree(scene->cost_ws);
-    scene->cost_ws = ws;
+    scene->cost_ws = ws.at<double>();
     scene->cost_ws_nodes = n_nodes;
+    ws.ptr = nullptr; /* the scene's now */
   }
   HIP_TRY(scene_tree_cost(nodes, n_nodes, scene->cost_ws, cost));
   return RT_HIP_OK;
@@ -3544,11 +3622,8 @@ int scene_built_cost(const RtHipScene *scene, double *cost)
   if (!scene->built_cost_known)
   {
     double c = 0.0;
-    {
-      const int rc = scene_cost_of(scene, scene->view.bvh_src, scene->view.n_bvh_nodes, &c);
-      if (rc)
-        return rc;
-    }
+    if (const int rc = scene_cost_of(scene, scene->view.bvh_src, scene->view.n_bvh_nodes, &c))
+      return rc;
     scene->built_cost = c;
     scene->built_cost_known = true;
   }
@@ -3557,63 +3632,65 @@ int scene_built_cost(const RtHipScene *scene, double *cost)
   return RT_HIP_OK;
 }
 
+/* A caller's device array that an update reads (`bytes` of it): device memory of the scene's device, outside what the scene owns */
+int check_update_input(const RtHipScene *scene, const void *ptr, size_t bytes, const char *name)
+{
+  int device = -1;
+  if (device_of(ptr, name, &device) != RT_HIP_OK || device != scene->device)
+    return fail(RT_HIP_EINVAL, "%s is not device memory of the scene's device %d", name, scene->device);
+  if (lies_inside_scene(scene, ptr, bytes))
+    return fail(RT_HIP_EINVAL, "%s lies inside the scene", name);
+  return RT_HIP_OK;
+}
+
+/* The updates' one workspace: 256 bytes for the reductions' words, then (host form) the caller's array staged behind them.
+ * *d_in is the array on the device either way. */
+int stage_update_input(const double *in, size_t bytes, bool on_host, DeviceBuffer &ws, unsigned long long **words, const double **d_in)
+{
+  const size_t words_bytes = 256, total = words_bytes + (on_host ? bytes : 0);
+  static_assert(SCENE_UPDATE_WORDS * 8 <= 256 && SCENE_SPHERE_WORDS * 8 <= 256, "the reductions' words");
+  if (ws.alloc(total) != hipSuccess)
+    return fail(RT_HIP_ENOMEM, "update workspace (%zu KB)", total >> 10);
+  *words = ws.at<unsigned long long>();
+  *d_in = on_host ? ws.at<double>(words_bytes) : in;
+  if (on_host)
+    HIP_TRY(hipMemcpy(ws.at<char>(words_bytes), in, bytes, hipMemcpyHostToDevice));
+  return RT_HIP_OK;
+}
+
 int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_triangles, bool on_host)
 {
-  if (!scene || !positions)
-    return fail(RT_HIP_EINVAL, "scene and positions are required");
-  if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update of its vertices failed half way");
+  if (!positions)
+    return fail(RT_HIP_EINVAL, "positions are required");
+  if (const int rc = scene_usable(scene, "rt_hip_scene_update_vertices"))
+    return rc;
   const size_t n = scene->view.n_triangles;
   if (n == 0)
     return fail(RT_HIP_EINVAL, "the scene has no triangles to move");
   if (n_triangles != n)
     return fail(RT_HIP_EINVAL, "%zu triangles given, the scene has %zu: an update keeps the count", n_triangles, n);
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
+  SceneWrite w(scene, "its vertices move");
+  HIP_TRY(w.scope.status);
   if (!on_host)
-  {
-    hipPointerAttribute_t attr;
-    memset(&attr, 0, sizeof attr);
-    if (hipPointerGetAttributes(&attr, positions) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != scene->device)
-    {
-      (void)hipGetLastError();
-      return fail(RT_HIP_EINVAL, "d_positions is not device memory of the scene's device %d", scene->device);
-    }
-    if (lies_inside_scene(scene, positions, 72 * n))
-      return fail(RT_HIP_EINVAL, "d_positions lies inside the scene");
-  }
-  std::lock_guard<std::mutex> lock(scene->table_mutex);
-  if (scene->live_accums.load() > 0)
-    return fail(RT_HIP_EINVAL, "%d accumulation(s) on this scene are alive: destroy them before its vertices move", scene->live_accums.load());
-  for (const TableSet &t : scene->tables)
-    if (t.users > 0)
-      return fail(RT_HIP_EINVAL, "a launch of this scene is being submitted");
+    if (const int rc = check_update_input(scene, positions, 72 * n, "d_positions"))
+      return rc;
+  w.lock.lock();
+  if (const int rc = w.idle())
+    return rc;
   const auto t0 = std::chrono::steady_clock::now();
-
-  /* ---- the one workspace: the reductions' words, then (host form) the staged positions ---- */
   DeviceBuffer ws;
-  const size_t words_bytes = 256;
-  static_assert(SCENE_UPDATE_WORDS * 8 <= 256, "the reductions' words");
-  if (ws.alloc(words_bytes + (on_host ? 72 * n : 0)) != hipSuccess)
-    return fail(RT_HIP_ENOMEM, "update workspace (%zu KB)", (words_bytes + (on_host ? 72 * n : 0)) >> 10);
-  unsigned long long *words = ws.at<unsigned long long>();
-  const double *d_pos = positions;
-  if (on_host)
-  {
-    HIP_TRY(hipMemcpy(ws.at<char>(words_bytes), positions, 72 * n, hipMemcpyHostToDevice));
-    d_pos = ws.at<double>(words_bytes);
-  }
+  unsigned long long *words = nullptr;
+  const double *d_pos = nullptr;
+  if (const int rc = stage_update_input(positions, 72 * n, on_host, ws, &words, &d_pos))
+    return rc;
   SceneUpdateCheck chk;
   HIP_TRY(scene_update_check(d_pos, (uint32_t)n, words, &chk));
   if (!(chk.max_len <= 1e300)) /* scene_create_impl's rule */
     return fail(RT_HIP_EINVAL, "a new position has a non-finite coordinate");
 
   /* ---- the cost of the tree as built, while it still is that tree; the topology's levels, at the first update ---- */
-  {
-    const int rc = scene_built_cost(scene, nullptr);
-    if (rc)
-      return rc;
-  }
+  if (const int rc = scene_built_cost(scene, nullptr))
+    return rc;
   const uint32_t n_nodes = scene->view.n_bvh_nodes;
   if (!scene->refit_by_level)
   {
@@ -3622,38 +3699,20 @@ int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_trian
     HIP_TRY(hipMemcpy(nodes.data(), scene->view.bvh_src, nodes.size() * 8, hipMemcpyDeviceToHost));
     if (n_nodes == 0 || !BvhRefit::levels(nodes.data(), n_nodes, by_level, level_begin))
       return fail(RT_HIP_ERUNTIME, "the hierarchy numbers a child below its parent: it cannot be refitted");
-    uint32_t *d_levels = nullptr;
-    if (hipMalloc(&d_levels, by_level.size() * 4) != hipSuccess)
-    {
-      (void)hipGetLastError();
+    DeviceBuffer d_levels;
+    if (d_levels.alloc(by_level.size() * 4) != hipSuccess)
       return fail(RT_HIP_ENOMEM, "the hierarchy's level array (%zu KB)", (by_level.size() * 4) >> 10);
-    }
-    const hipError_t e = hipMemcpy(d_levels, by_level.data(), by_level.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-      (void)hipFree(d_levels);
-      HIP_TRY(e);
-    }
-    scene->refit_by_level = d_levels;
+    HIP_TRY(hipMemcpy(d_levels.ptr, by_level.data(), by_level.size() * 4, hipMemcpyHostToDevice));
+    scene->refit_by_level = d_levels.at<uint32_t>();
+    d_levels.ptr = nullptr; /* the scene's now */
     scene->refit_level_begin.swap(level_begin);
   }
 
-  /* ---- no launch may still read what is about to change: every table set's build and readers, as the recycling path waits ---- */
-  for (TableSet &t : scene->tables)
-  {
-    HIP_TRY(hipEventSynchronize(t.built));
-    for (auto &r : t.readers)
-      HIP_TRY(hipEventSynchronize(r.second));
-  }
+  if (const int rc = w.drain())
+    return rc;
 
   /* ---- writing begins ---- */
-  for (TableSet &t : scene->tables)
-    t.near_R = -1.0; /* filter, fp32 nodes and tri32 records are rebuilt by the next launch (acquire_tables) */
-  auto broke = [&](hipError_t e, const char *what) {
-    (void)hipGetLastError();
-    scene->unusable = true;
-    return fail(RT_HIP_ERUNTIME, "%s: %s; the scene is unusable now (destroy it)", what, hipGetErrorString(e));
-  };
+  w.stale();
   SceneUpdateArrays arr;
   arr.n_tri = (uint32_t)n;
   arr.n_nodes = n_nodes;
@@ -3665,41 +3724,26 @@ int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_trian
   arr.bvh_tri = scene->view.bvh_tri;
   arr.tri_geom_leaf = const_cast<double *>(scene->view.tri_geom_leaf);
   double mesh_c[3], r2 = 0;
-  for (int a = 0; a < 3; a++)
-    mesh_c[a] = 0.5 * chk.lo[a] + 0.5 * chk.hi[a];
+  scene_mesh_centre(chk.lo, chk.hi, mesh_c);
   hipError_t e = scene_update_triangles(arr, d_pos, mesh_c, words, &r2);
   if (e != hipSuccess)
-    return broke(e, "updating the triangle records");
+    return w.broke(e, "updating the triangle records");
   e = scene_update_refit(arr, scene->refit_by_level, scene->refit_level_begin.data(), scene->refit_level_begin.size() - 1);
   if (e != hipSuccess)
-    return broke(e, "refitting the hierarchy");
+    return w.broke(e, "refitting the hierarchy");
 
-  /* ---- the derived scalars, as scene_create_impl has them ---- */
-  double mesh_R = std::sqrt(r2) * (1.0 + 1e-9) + 1e-300;
-  if (!(mesh_R < HUGE_VAL))
-    mesh_R = HUGE_VAL;
-  const double ea = chk.hi[0] - chk.lo[0], eb = chk.hi[1] - chk.lo[1], ec = chk.hi[2] - chk.lo[2];
-  const bool mesh_round = 3.14159265358979 * mesh_R * mesh_R <= 0.5 * (ea * eb + eb * ec + ec * ea);
-  for (int a = 0; a < 3; a++)
-    scene->mesh_c[a] = mesh_c[a];
-  scene->mesh_R = mesh_R;
-  scene->mesh_c_norm = std::sqrt(mesh_c[0] * mesh_c[0] + mesh_c[1] * mesh_c[1] + mesh_c[2] * mesh_c[2]) * (1.0 + 1e-12);
-  scene->view.mesh_round = mesh_round ? 1u : 0u;
+  /* ---- the derived scalars and the hull flags (k_update_triangles cleared the bits), by creation's text ---- */
+  SceneMeshBounds mb;
+  scene_mesh_bounds(chk.lo, chk.hi, r2, &mb);
+  take_mesh_bounds(scene, mb);
   scene->reach_triangles = chk.max_len; /* kept: a later update of the spheres joins it with their part again */
   scene->reach = std::fmax(scene->reach_spheres, scene->reach_triangles);
-  scene->hull_flags = false; /* k_update_triangles cleared the bits */
-  if (n <= PT_HULL_MAX_TRIS && mesh_R >= 0 && mesh_R < 1e150)
-  {
-    const double extent = scene->mesh_c_norm + mesh_R; /* tau as at creation */
-    e = pt_launch_build_hull_flags(scene->view.tri_geom, scene->view.tri_normal, (uint32_t)n, 1.1368683772161603e-13 * extent,
-                                   arr.tri_object, nullptr);
-    if (e != hipSuccess)
-      return broke(e, "hull flags");
-    scene->hull_flags = true;
-  }
+  e = scene_hull_flags(scene, mb.tau);
+  if (e != hipSuccess)
+    return w.broke(e, "hull flags");
   e = hipStreamSynchronize(nullptr);
   if (e != hipSuccess)
-    return broke(e, "waiting for the update");
+    return w.broke(e, "waiting for the update");
   scene->updates++;
   scene->last_update_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return RT_HIP_OK;
@@ -3711,51 +3755,30 @@ int scene_update_impl(RtHipScene *scene, const double *positions, size_t n_trian
  * left does its second run write.  The table sets go stale as after a vertex update: the filter is made of these records. */
 int scene_update_spheres_impl(RtHipScene *scene, const double *spheres, size_t n_spheres, bool on_host)
 {
-  if (!scene || !spheres)
-    return fail(RT_HIP_EINVAL, "scene and spheres are required");
-  if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  if (!spheres)
+    return fail(RT_HIP_EINVAL, "spheres are required");
+  if (const int rc = scene_usable(scene, "rt_hip_scene_update_spheres"))
+    return rc;
   const size_t n = scene->view.n_spheres;
   if (n == 0)
     return fail(RT_HIP_EINVAL, "the scene has no spheres to move");
   if (n_spheres != n)
     return fail(RT_HIP_EINVAL, "%zu spheres given, the scene has %zu: an update keeps the count", n_spheres, n);
   const size_t in_bytes = SCENE_SPHERE_IN * 8 * n;
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
+  SceneWrite w(scene, "its spheres move");
+  HIP_TRY(w.scope.status);
   if (!on_host)
-  {
-    hipPointerAttribute_t attr;
-    memset(&attr, 0, sizeof attr);
-    if (hipPointerGetAttributes(&attr, spheres) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != scene->device)
-    {
-      (void)hipGetLastError();
-      return fail(RT_HIP_EINVAL, "d_spheres is not device memory of the scene's device %d", scene->device);
-    }
-    if (lies_inside_scene(scene, spheres, in_bytes))
-      return fail(RT_HIP_EINVAL, "d_spheres lies inside the scene");
-  }
-  std::lock_guard<std::mutex> lock(scene->table_mutex);
-  if (scene->live_accums.load() > 0)
-    return fail(RT_HIP_EINVAL, "%d accumulation(s) on this scene are alive: destroy them before its spheres move", scene->live_accums.load());
-  for (const TableSet &t : scene->tables)
-    if (t.users > 0)
-      return fail(RT_HIP_EINVAL, "a launch of this scene is being submitted");
+    if (const int rc = check_update_input(scene, spheres, in_bytes, "d_spheres"))
+      return rc;
+  w.lock.lock();
+  if (const int rc = w.idle())
+    return rc;
   const auto t0 = std::chrono::steady_clock::now();
-
-  /* ---- the one workspace: the reductions' words, then (host form) the staged spheres ---- */
   DeviceBuffer ws;
-  const size_t words_bytes = 256;
-  static_assert(SCENE_SPHERE_WORDS * 8 <= 256, "the reductions' words");
-  if (ws.alloc(words_bytes + (on_host ? in_bytes : 0)) != hipSuccess)
-    return fail(RT_HIP_ENOMEM, "update workspace (%zu KB)", (words_bytes + (on_host ? in_bytes : 0)) >> 10);
-  unsigned long long *words = ws.at<unsigned long long>();
-  const double *d_in = spheres;
-  if (on_host)
-  {
-    HIP_TRY(hipMemcpy(ws.at<char>(words_bytes), spheres, in_bytes, hipMemcpyHostToDevice));
-    d_in = ws.at<double>(words_bytes);
-  }
+  unsigned long long *words = nullptr;
+  const double *d_in = nullptr;
+  if (const int rc = stage_update_input(spheres, in_bytes, on_host, ws, &words, &d_in))
+    return rc;
   SceneSphereBounds sb;
   bool radii_ok = false;
   HIP_TRY(scene_update_spheres_check(d_in, (uint32_t)n, words, &sb, &radii_ok));
@@ -3772,29 +3795,18 @@ int scene_update_spheres_impl(RtHipScene *scene, const double *spheres, size_t n
     scene_sphere_leading_walls(lead, n_lead, &sb);
   }
 
-  /* ---- no launch may still read what is about to change ---- */
-  for (TableSet &t : scene->tables)
-  {
-    HIP_TRY(hipEventSynchronize(t.built));
-    for (auto &r : t.readers)
-      HIP_TRY(hipEventSynchronize(r.second));
-  }
+  if (const int rc = w.drain())
+    return rc;
 
   /* ---- writing begins ---- */
-  for (TableSet &t : scene->tables)
-    t.near_R = -1.0; /* the filter is rebuilt by the next launch (acquire_tables) */
-  auto broke = [&](hipError_t e, const char *what) {
-    (void)hipGetLastError();
-    scene->unusable = true;
-    return fail(RT_HIP_ERUNTIME, "%s: %s; the scene is unusable now (destroy it)", what, hipGetErrorString(e));
-  };
+  w.stale();
   hipError_t e = scene_update_spheres_write(d_in, (uint32_t)n, const_cast<double *>(scene->view.entry_src),
                                             const_cast<double *>(scene->view.geom4));
   if (e != hipSuccess)
-    return broke(e, "updating the sphere records");
+    return w.broke(e, "updating the sphere records");
   e = hipStreamSynchronize(nullptr);
   if (e != hipSuccess)
-    return broke(e, "waiting for the update");
+    return w.broke(e, "waiting for the update");
   take_sphere_bounds(scene, sb);
   scene->reach = std::fmax(scene->reach_spheres, scene->reach_triangles);
   scene->updates++;
@@ -3808,8 +3820,8 @@ int scene_cost_impl(const RtHipScene *scene, double *cost)
   if (!scene || !cost)
     return fail(RT_HIP_EINVAL, "rt_hip_scene_bvh_cost: scene and cost are required");
   *cost = 0.0;
-  if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  if (const int rc = scene_usable(scene, "rt_hip_scene_bvh_cost"))
+    return rc;
   DeviceScope scope(scene->device);
   HIP_TRY(scope.status);
   std::lock_guard<std::mutex> lock(scene->table_mutex);
@@ -3841,72 +3853,39 @@ int cost_nodes_host_impl(const double *h_nodes, size_t n_nodes, int device, doub
   return RT_HIP_OK;
 }
 
-/* caller holds table_mutex, has the scene's device current and has ruled out a NULL, unusable or triangle-less scene */
-int scene_rebuild_locked(RtHipScene *scene)
+/* `w` holds table_mutex and has the scene's device current; a NULL, unusable or triangle-less scene is ruled out */
+int scene_rebuild_locked(SceneWrite &w)
 {
-  if (scene->live_accums.load() > 0)
-    return fail(RT_HIP_EINVAL, "%d accumulation(s) on this scene are alive: destroy them before its hierarchy is rebuilt",
-                scene->live_accums.load());
-  for (const TableSet &t : scene->tables)
-    if (t.users > 0)
-      return fail(RT_HIP_EINVAL, "a launch of this scene is being submitted");
+  RtHipScene *scene = w.scene;
+  if (const int rc = w.idle())
+    return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  const size_t n = scene->view.n_triangles;
 
   /* ---- the build, in its own workspace; the new tree priced where it lies ---- */
   BvhDeviceTree dtree;
-  const hipError_t be = bvh_device_build(scene->view.tri_geom, (uint32_t)n, &dtree);
-  if (be != hipSuccess && dtree.failure)
-    return fail(RT_HIP_ERUNTIME, "device hierarchy builder: %s", dtree.failure);
-  HIP_TRY(be);
-  if (dtree.depth > PT_BVH_STACK)
-    return fail(RT_HIP_ELIMIT, "triangle hierarchy depth %d exceeds the traversal stack (%d)", dtree.depth, PT_BVH_STACK);
-  if (dtree.n_nodes == 0)
-    return fail(RT_HIP_ERUNTIME, "device hierarchy builder: a tree without nodes");
+  if (const int rc = build_device_tree(scene->view.tri_geom, scene->view.n_triangles, &dtree))
+    return rc;
   double cost = 0.0;
-  {
-    const int rc = scene_cost_of(scene, dtree.nodes, dtree.n_nodes, &cost);
-    if (rc)
-      return rc;
-  }
+  if (const int rc = scene_cost_of(scene, dtree.nodes, dtree.n_nodes, &cost))
+    return rc;
 
   /* ---- room for it: in place while the count fits the capacity, else a side allocation ---- */
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t src_bytes = (size_t)dtree.n_nodes * PT_BVH_SRC_DOUBLES * 8, f32_bytes = (size_t)dtree.n_nodes * PT_BVH_NODE_WORDS * 4;
   DeviceBuffer side;
-  const size_t side_bytes = pad(src_bytes) + pad(f32_bytes);
+  const size_t side_bytes = pad256(src_bytes) + pad256(f32_bytes);
   if (dtree.n_nodes > scene->bvh_node_capacity && side.alloc(side_bytes) != hipSuccess)
     return fail(RT_HIP_ENOMEM, "the side allocation of a larger hierarchy (%zu KB)", side_bytes >> 10);
-
-  /* ---- no launch may still read what is about to change: every table set's build and readers, as the updates wait ---- */
-  for (TableSet &t : scene->tables)
-  {
-    HIP_TRY(hipEventSynchronize(t.built));
-    for (auto &r : t.readers)
-      HIP_TRY(hipEventSynchronize(r.second));
-  }
+  if (const int rc = w.drain())
+    return rc;
 
   /* ---- installing begins ---- */
-  auto broke = [&](hipError_t e, const char *what) {
-    (void)hipGetLastError();
-    scene->unusable = true;
-    return fail(RT_HIP_ERUNTIME, "%s: %s; the scene is unusable now (destroy it)", what, hipGetErrorString(e));
-  };
   if (scene->refit_by_level) /* the old topology's levels: the next vertex update makes the new one's */
     (void)hipFree(scene->refit_by_level);
   scene->refit_by_level = nullptr;
   scene->refit_level_begin.clear();
   while (scene->tables.size() > 1) /* the owned sets hold fp32 nodes of the old count: the next launch that needs one allocates it anew */
   {
-    TableSet &t = scene->tables.back();
-    for (auto &r : t.readers)
-      (void)hipEventDestroy(r.second);
-    if (t.built) (void)hipEventDestroy(t.built);
-    if (t.owned)
-    {
-      (void)hipFree(t.filt);
-      (void)hipFree(t.bvh_nodes);
-    }
+    table_set_free(scene->tables.back());
     scene->tables.pop_back();
   }
   if (side)
@@ -3917,29 +3896,15 @@ int scene_rebuild_locked(RtHipScene *scene)
     scene->bvh_side_bytes = side_bytes;
     side.ptr = nullptr; /* the scene's now */
     scene->view.bvh_src = reinterpret_cast<const double *>(scene->bvh_side);
-    scene->view.bvh_nodes = reinterpret_cast<float *>(static_cast<char *>(scene->bvh_side) + pad(src_bytes));
+    scene->view.bvh_nodes = reinterpret_cast<float *>(static_cast<char *>(scene->bvh_side) + pad256(src_bytes));
     scene->bvh_node_capacity = dtree.n_nodes;
   }
   for (TableSet &t : scene->tables)
-  {
     t.bvh_nodes = scene->view.bvh_nodes; /* (set 0 alone is left: its nodes are the view's) */
-    t.near_R = -1.0; /* rebuilt by the next launch (acquire_tables) */
-  }
-  hipError_t e = hipMemcpy(const_cast<double *>(scene->view.bvh_src), dtree.nodes, src_bytes, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(const_cast<uint32_t *>(scene->view.bvh_tri), dtree.order, n * 4, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess)
-    e = bvh_device_gather_leaf(scene->view.tri_geom, scene->view.bvh_tri, (uint32_t)n, const_cast<double *>(scene->view.tri_geom_leaf));
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(nullptr);
+  w.stale();
+  const hipError_t e = install_device_tree(scene, dtree);
   if (e != hipSuccess)
-    return broke(e, "installing the rebuilt hierarchy");
-  scene->view.n_bvh_nodes = dtree.n_nodes;
-  scene->view.bvh_depth = (uint32_t)dtree.depth;
-  scene->bvh_builder = RT_HIP_BVH_DEVICE;
-  scene->bvh_max_depth = (uint32_t)dtree.max_depth;
-  scene->bvh_build_seconds = 1e-3 * dtree.build_ms;
-  scene->bvh_nodes_bytes = f32_bytes;
+    return w.broke(e, "installing the rebuilt hierarchy");
   scene->built_cost = cost;
   scene->built_cost_known = true;
   scene->rebuilds++;
@@ -3949,16 +3914,14 @@ int scene_rebuild_locked(RtHipScene *scene)
 
 int scene_rebuild_impl(RtHipScene *scene)
 {
-  if (!scene)
-    return fail(RT_HIP_EINVAL, "rt_hip_scene_rebuild_bvh: scene is NULL");
-  if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  if (const int rc = scene_usable(scene, "rt_hip_scene_rebuild_bvh"))
+    return rc;
   if (scene->view.n_triangles == 0)
     return fail(RT_HIP_EINVAL, "the scene has no triangles: there is no hierarchy to rebuild");
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  std::lock_guard<std::mutex> lock(scene->table_mutex);
-  return scene_rebuild_locked(scene);
+  SceneWrite w(scene, "its hierarchy is rebuilt");
+  HIP_TRY(w.scope.status);
+  w.lock.lock();
+  return scene_rebuild_locked(w);
 }
 
 /* max_ratio as rt_hip_scene_maintain_bvh takes it: finite and >= 1 */
@@ -3970,31 +3933,23 @@ int scene_maintain_impl(RtHipScene *scene, double max_ratio, double *cost_ratio,
   if (rebuilt) *rebuilt = 0;
   if (!rebuild_ratio_ok(max_ratio))
     return fail(RT_HIP_EINVAL, "rt_hip_scene_maintain_bvh: max_ratio must be finite and >= 1");
-  if (!scene)
-    return fail(RT_HIP_EINVAL, "rt_hip_scene_maintain_bvh: scene is NULL");
-  if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  if (const int rc = scene_usable(scene, "rt_hip_scene_maintain_bvh"))
+    return rc;
   if (scene->view.n_triangles == 0)
     return fail(RT_HIP_EINVAL, "the scene has no triangles: there is no hierarchy to maintain");
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  std::lock_guard<std::mutex> lock(scene->table_mutex);
+  SceneWrite w(scene, "its hierarchy is rebuilt");
+  HIP_TRY(w.scope.status);
+  w.lock.lock(); /* held across pricing and rebuild */
   double built = 0.0, cost = 0.0;
-  {
-    const int rc = scene_built_cost(scene, &built);
-    if (rc)
-      return rc;
-  }
-  {
-    const int rc = scene_cost_of(scene, scene->view.bvh_src, scene->view.n_bvh_nodes, &cost);
-    if (rc)
-      return rc;
-  }
+  if (const int rc = scene_built_cost(scene, &built))
+    return rc;
+  if (const int rc = scene_cost_of(scene, scene->view.bvh_src, scene->view.n_bvh_nodes, &cost))
+    return rc;
   const double ratio = built == 0.0 ? 1.0 : cost / built;
   if (cost_ratio) *cost_ratio = ratio;
   if (!(ratio > max_ratio))
     return RT_HIP_OK;
-  const int rc = scene_rebuild_locked(scene);
+  const int rc = scene_rebuild_locked(w);
   if (rc == RT_HIP_OK && rebuilt)
     *rebuilt = 1;
   return rc;
@@ -4028,8 +3983,8 @@ int rt_hip_scene_rebuild_info(const RtHipScene *scene, uint64_t *rebuilds, doubl
   *built_cost = 0.0;
   if (scene->view.n_bvh_nodes == 0)
     return RT_HIP_OK;
-  if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an earlier update failed half way");
+  if (const int rc = scene_usable(scene, "rt_hip_scene_rebuild_info"))
+    return rc;
   return guarded("rt_hip_scene_rebuild_info", [&]() -> int {
     DeviceScope scope(scene->device);
     HIP_TRY(scope.status);
