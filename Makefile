@@ -22,8 +22,8 @@ CFLAGS  := -std=c99 -D_DEFAULT_SOURCE -O2 -ffp-contract=off -fPIC -Wall -Wno-unu
 
 SHIM    := $(CSRC)/librt_hip.so
 # the device code is ONE translation unit, pt_kernel.hip, split by topic into the pt_*.h headers it includes
-# the four sources every build of the shim compiles, in this order
-SHIM_SRC := $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip
+# the five sources every build of the shim compiles, in this order
+SHIM_SRC := $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip $(CSRC)/lens.hip
 KERNEL_SRC := $(SHIM_SRC) $(wildcard $(CSRC)/pt_*.h) $(CSRC)/bvh_build.h $(CSRC)/scene_spheres.h $(CSRC)/rt_staging.h $(INC)/rt_hip.h $(INC)/rt_rng.h
 HOSTLIB := $(HOST)/libraytracer_amd.so
 CLI     := $(HOST)/raytracer

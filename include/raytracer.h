@@ -240,6 +240,18 @@ enum { RT_TRACE_PATH = 0, RT_CAST_RAY = 1 };
 void rt_set_integrator(int integrator);
 int rt_get_integrator(void);
 
+/* A thin lens for render() / render_ex(): depth of field.  aperture_radius 0 (the default) leaves them on the pinhole path they
+ * take without this call, whatever focus_distance is.  With an aperture above 0 the frame is the lens frame of rt_hip.h
+ * (rt_hip_render_lens_image: lens rays of radius aperture_radius about the camera position, sharp on the plane focus_distance in
+ * front of the camera, traced as radiance queries) on one device, with the path tracer.  The setter only stores the values and
+ * refuses nothing: what the shim refuses (a focus_distance that is not positive and finite, RT_CAST_RAY) makes render() fail as
+ * it fails for any other refusal.  The defaults are 0 and 1.  Either pointer of the getter may be NULL.
+ * The lens frame runs on ONE device whatever rt_set_devices() or RT_DEVICES say, and takes no part in cancellation: the flag of
+ * rt_set_cancel_flag() is not polled, the frame is always whole, and rt_last_render_cancelled() reads 0 after it.
+ * rt_last_render_seconds() is the whole call by the host's clock, not kernel time. */
+void rt_set_lens(double aperture_radius, double focus_distance);
+void rt_get_lens(double *aperture_radius, double *focus_distance);
+
 /* Who builds the triangle hierarchy of the scenes render() and its kin upload: RT_BVH_HOST (default) = one host core,
  * RT_BVH_DEVICE = the GPU (rt_hip.h, RT_HIP_BVH_DEVICE).  Images, bytes and counters are the same under either; the time a
  * new or changed scene takes to become renderable is what differs.  Other values are ignored.  The reference has no

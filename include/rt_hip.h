@@ -678,6 +678,88 @@ const char *rt_hip_trace_kernel_name(const RtHipScene *scene);
 int rt_hip_trace_kernel_count(void);
 const char *rt_hip_trace_kernel_launches(int index, uint64_t *launches);
 
+/* ---- thin-lens camera: depth of field from generated lens rays ------------------------------------------------------------------
+ * A frame with depth of field is made of three pieces: a kernel that writes the LENS RAYS of one sample pass, the radiance query
+ * above (rt_hip_trace_rays, called as it stands: no render, accumulation or pixel-list kernel knows of a lens), and a kernel that
+ * folds the pass into a per-pixel sum, with a resolve.  What is new is a pure function of its arguments and is stated here operation
+ * for operation; everything about paths is rt_hip_trace_rays' contract.
+ *
+ * THE LENS RAY of pixel p = y*width + x and sample s, NP = width*height, under a camera, a seed and an RtHipLens.  fp64 + - * / sqrt,
+ * unfused, in the order written; vec3_* are vector.h's (vec3_normalize(a) = a * (1.0 / sqrt((a.x*a.x + a.y*a.y) + a.z*a.z))):
+ *   stream index   k = s*NP + p.  The frame lives in the ray-index space of rt_hip_trace_rays, one sample per ray: (s + 1)*NP <= 2^32.
+ *   jitter         r0, r1 = the first two draws of the stream (seed, k, 0) of rt_rng.h; u = ((double)x + r0) / ((double)width - 1.0),
+ *                  v = ((double)y + r1) / ((double)height - 1.0) (raytracer.c:203-204).  These are the two draws rt_hip_trace_rays
+ *                  discards before the path starts: jitter and path share one stream without overlap.
+ *   direction      d = position - (lower_left_corner + (horizontal*u + vertical*v)), get_camera_ray's order (raytracer.c:377-381),
+ *                  NOT normalised.  For a camera made by init_camera d = forward + (0.5 - u) horizontal + (0.5 - v) vertical: its
+ *                  forward component is 1, so position + d*f lies on the plane at distance f in front of the camera.
+ *   focus point    F = position + d*focus_distance.
+ *   lens axes      ax = vec3_normalize(horizontal), ay = vec3_normalize(vertical), made once on the host.
+ *   lens point     from a second stream, so that the path's draws do not move: state rt_rng_seed(rt_mix64(seed ^ 0x6C656E73), k, 0).
+ *                  A round draws r1 then r2, a = 2.0*r1 - 1.0, b = 2.0*r2 - 1.0, and is accepted iff a*a + b*b < 1.0; the first
+ *                  accepted round of at most 32 gives (a, b); if none accepts, a = b = 0.0 (the centre of the lens).
+ *                  L = position + (ax*(a*R) + ay*(b*R)) with R = aperture_radius.
+ *   ray            origin L, direction vec3_normalize(F - L).
+ * Where the origins lie: a*a + b*b < 1, so with horizontal and vertical orthogonal |L - position| <= R to rounding (the offset
+ * ax*(a*R) + ay*(b*R) itself is within R (1 + 2^-50)); a sheared camera's lens is the parallelogram's ellipse, within
+ * R sqrt(1 + |ax . ay|) of the position.
+ * aperture_radius == 0 runs the same formula -- L = position + (ax*0 + ay*0), the direction through F -- and is NOT promised to
+ * equal the pinhole ray of get_camera_ray bit for bit (F - L is d*focus_distance after two more roundings).
+ * A camera whose horizontal, vertical or lower_left_corner is not finite (or overflows on the way), horizontal or vertical of
+ * length 0, or F == L give a ray that rt_hip_trace_rays calls INVALID (status 2); rt_hip_lens_rays writes it as computed.
+ *
+ * THE FRAME (rt_hip_render_lens): of params, width, height, samples = S, max_depth and seed are used; integrator must be
+ * RT_HIP_TRACE_PATH; the tile fields must describe the whole frame (tile_first 0, tile_stride 0 or 1, tile_count 0 or all tiles).
+ * sum is zeroed to +0.0; for s = 0 .. S-1 and each slice of at most slice_pixels pixels in ascending order: the slice's lens rays;
+ * rt_hip_trace_rays' own launch with samples = 1, index_first = s*NP + the slice's first pixel, RT_HIP_RAYS_GIVEN and origin_radius
+ * = |position| + aperture_radius (a hint: it changes no bit); sum[p] = vec3_add(sum[p], radiance[p]) -- so in ascending s --, and a ray
+ * of status 2 makes its pixel's sum a quiet NaN in all three channels.  Then mean = sum * (1.0 / (double)S), rgb = (float)mean and rgb8 =
+ * the render epilogue's gamma-5 tonemap of mean (the device function rt_hip_accum_resolve's kernels call), row-major, not tiled.
+ * Everything goes on `stream` with no host wait between passes; d_stats (may be NULL) accumulates rt_hip_trace_rays' counters.
+ * CONTRACT:
+ *   (a) the rays equal the statement above bit for bit;
+ *   (b) sample s of pixel p is what rt_hip_trace_rays returns for that ray at index_first + i = s*NP + p, samples = 1: `paths` and
+ *       `casts` equal the compiled reference's per ray, and the values are inside that contract's bar;
+ *   (c) sum, rgb and rgb8 are the stated reductions of those samples, bit for bit;
+ *   (d) no output bit depends on slice_pixels;
+ *   (e) scenes with M_REFRACTION report through the device's status word exactly as rt_hip_trace_rays says.
+ *   - rt_hip_lens_defaults: aperture_radius 0, focus_distance 1, flags 0.
+ *   - rt_hip_lens_rays: the generator alone: rays of pixels [pixel_first, pixel_first + n) of sample `sample` into d_rays (n x 6
+ *     doubles, 16-byte aligned, as rt_hip_trace_rays takes them); pixel_first + n <= NP; asynchronous on `stream`, on the device
+ *     that holds d_rays.  n == 0 is RT_HIP_OK and launches nothing.
+ *   - rt_hip_lens_workspace_bytes: the d_workspace of rt_hip_render_lens (a slice's rays, status words and radiance, and the frame's
+ *     sums, 24 bytes a pixel, whether or not d_sum is given); 0 for a size out of range or slice_pixels == 0.
+ *   - rt_hip_render_lens: d_sum (3 doubles a pixel) may be NULL: the sums then live in the workspace; d_rgb (3 floats a pixel) and
+ *     d_rgb8 (3 bytes) may each be NULL, but one of the three outputs is required.  slice_pixels above NP means NP.
+ *   - rt_hip_lens_resolve: the resolve alone, for a caller that keeps d_sum: mean = sum * (1.0 / (double)samples) of width x height
+ *     pixels into d_rgb and d_rgb8 (either may be NULL, not both) by the rule above; total: any bits in sum have a result (a NaN or
+ *     negative mean reads byte 255 or 0 as the tonemap has it).  Asynchronous on `stream`, on the device that holds d_sum.
+ *   - rt_hip_render_lens_image: the host form, synchronous, with a scene and buffers of its own on logical device `device` of
+ *     rt_hip_render_image's device map; h_rgb, h_rgb8: either may be NULL, not both; h_stats (may be NULL) is overwritten; it checks
+ *     the device's status word (rt_hip_launch_status) and returns its error.
+ * Refusals, each before the first launch and with the outputs untouched, arguments before the device is looked for.  RT_HIP_EINVAL:
+ * aperture_radius negative, NaN or infinite; focus_distance not finite or <= 0; lens flags or reserved not 0; width or height < 2 (or
+ * above 2^20); samples < 1; samples * NP > 2^32; slice_pixels == 0; RT_HIP_CAST_RAY; tile fields of a part of the frame; max_depth
+ * outside 0 .. 1000000; a NULL required pointer; a d_workspace or d_rays that is not 16-byte aligned, a d_sum that is not 8-byte
+ * aligned; a camera position that is not finite; near_R >= 1e15 (rt_hip_trace_rays' rule).  RT_HIP_ELIMIT: max_depth above 32 with an
+ * M_REFRACTION material, as rt_hip_trace_rays. */
+typedef struct
+{
+  double aperture_radius; /* R >= 0, finite; 0: every ray starts at the camera position */
+  double focus_distance;  /* f > 0, finite: the plane at this distance in front of the camera is sharp */
+  uint32_t flags;         /* must be 0 */
+  uint32_t reserved;      /* must be 0 */
+} RtHipLens;
+void rt_hip_lens_defaults(RtHipLens *lens);
+int rt_hip_lens_rays(const RtHipCamera *camera, const RtHipLens *lens, int32_t width, int32_t height, uint64_t seed, uint32_t sample,
+                     uint32_t pixel_first, uint32_t n, double *d_rays, void *stream);
+size_t rt_hip_lens_workspace_bytes(int32_t width, int32_t height, uint32_t slice_pixels);
+int rt_hip_render_lens(const RtHipScene *scene, const RtHipCamera *camera, const RtHipLens *lens, const RtHipParams *params,
+                       uint32_t slice_pixels, void *d_workspace, double *d_sum, float *d_rgb, uint8_t *d_rgb8, uint64_t *d_stats, void *stream);
+int rt_hip_lens_resolve(const double *d_sum, int32_t width, int32_t height, int32_t samples, float *d_rgb, uint8_t *d_rgb8, void *stream);
+int rt_hip_render_lens_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
+                             const RtHipLens *lens, const RtHipParams *params, int device, float *h_rgb, uint8_t *h_rgb8, uint64_t *h_stats);
+
 /* ---- edge-avoiding a-trous denoiser guided by the first-hit buffers ---------------------------------------------------------
  * Inputs: row-major images of w x h pixels (1 <= w, h <= 2^20, w*h < 2^32) on one device -- colour c (3 floats per pixel: the
  * linear mean of rt_hip_render_tiles or rt_hip_accum_resolve after rt_hip_untile) and the RtHipAov buffers of the same frame

@@ -734,4 +734,33 @@ hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, i
                             uint8_t *image_rgb8, hipStream_t stream);
 #endif
 
+/* ---- the thin-lens camera (rt_hip.h, "thin-lens camera"; the kernels are lens.hip's, a translation unit of its own) ---- */
+/* One sample pass's lens rays for the pixels [pixel_first, pixel_first + n) of a width-wide frame.  The camera as RtHipCamera
+ * holds it; ax, ay: vec3_normalize of its horizontal and vertical, made on the host; w_minus_1 = (double)width - 1.0 and
+ * h_minus_1 likewise (raytracer.c:203-204); lens_seed = rt_mix64(seed ^ 0x6C656E73); index_first = sample * NP + pixel_first,
+ * the stream index of the first ray. */
+struct PtLensRays
+{
+  double position[3], horizontal[3], vertical[3], lower_left_corner[3];
+  double ax[3], ay[3];
+  double w_minus_1, h_minus_1;
+  double aperture_radius, focus_distance;
+  uint64_t seed, lens_seed;
+  uint32_t width, pixel_first, n, index_first;
+  double *rays; /* n x 6 doubles, 16-byte aligned */
+};
+
+#define PT_LENS_ROUNDS 32 /* rejection rounds of the lens point before the centre is taken */
+
+#if defined(__HIPCC__)
+/* n >= 1 */
+hipError_t lens_launch_rays(const PtLensRays &args, hipStream_t stream);
+/* sum[3 * pixel_first + t] += radiance[t] for t < 3 n; a ray of status 2 makes its pixel's three sums NaN */
+hipError_t lens_launch_accumulate(const uint32_t *status, const double *radiance, uint32_t pixel_first, uint32_t n, double *sum,
+                                  hipStream_t stream);
+/* mean = sum * (1.0 / samples) -> float and tonemapped byte, row-major; either output may be null */
+hipError_t lens_launch_resolve(const double *sum, uint64_t n_pixels, int32_t samples, float *rgb, uint8_t *rgb8, hipStream_t stream);
+#endif
+
+
 #endif /* PT_DEVICE_H */

@@ -25,6 +25,7 @@
 
 #include "pt_device.h"
 #include "rt_hip.h"
+#include "rt_rng.h"
 #include "bvh_build.h"
 #include "rt_staging.h"
 
@@ -3246,6 +3247,203 @@ int trace_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtH
   return rc ? rc : R.download(A);
 }
 
+/* ---- thin-lens camera (rt_hip.h, rt_hip_lens_* / rt_hip_render_lens*) ---------------------------------------------------------
+ * A lens frame is lens rays (lens.hip), the radiance query as it stands (trace_launch) and a per-pixel sum (lens.hip).  The checks
+ * need no device; the frame refuses everything it can before its first launch. */
+int check_lens(const RtHipCamera *camera, const RtHipLens *lens, int32_t width, int32_t height)
+{
+  if (!camera || !lens)
+    return fail(RT_HIP_EINVAL, "camera and lens are required");
+  if (!(lens->aperture_radius >= 0) || !std::isfinite(lens->aperture_radius))
+    return fail(RT_HIP_EINVAL, "aperture_radius %g must be finite and >= 0", lens->aperture_radius);
+  if (!(lens->focus_distance > 0) || !std::isfinite(lens->focus_distance))
+    return fail(RT_HIP_EINVAL, "focus_distance %g must be finite and > 0", lens->focus_distance);
+  if (lens->flags != 0u || lens->reserved != 0u)
+    return fail(RT_HIP_EINVAL, "lens flags and reserved must be 0");
+  if (!frame_size_ok(width, height, 2))
+    return fail(RT_HIP_EINVAL, "width and height must be in [2, 2^20] with fewer than 2^32 pixels");
+  return RT_HIP_OK;
+}
+
+/* vec3_normalize (vector.h:53-58) on the host: v * (1.0 / sqrt((x*x + y*y) + z*z)) */
+void lens_axis(const double v[3], double out[3])
+{
+  const double inv = 1.0 / std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+  for (int k = 0; k < 3; k++)
+    out[k] = v[k] * inv;
+}
+
+/* the generator's arguments but for the range (pixel_first, n, index_first) and the output */
+PtLensRays lens_args(const RtHipCamera *camera, const RtHipLens *lens, int32_t width, int32_t height, uint64_t seed)
+{
+  PtLensRays A;
+  memset(&A, 0, sizeof A);
+  memcpy(A.position, camera->position, sizeof A.position);
+  memcpy(A.horizontal, camera->horizontal, sizeof A.horizontal);
+  memcpy(A.vertical, camera->vertical, sizeof A.vertical);
+  memcpy(A.lower_left_corner, camera->lower_left_corner, sizeof A.lower_left_corner);
+  lens_axis(camera->horizontal, A.ax);
+  lens_axis(camera->vertical, A.ay);
+  A.w_minus_1 = (double)width - 1.0;
+  A.h_minus_1 = (double)height - 1.0;
+  A.aperture_radius = lens->aperture_radius;
+  A.focus_distance = lens->focus_distance;
+  A.seed = seed;
+  A.lens_seed = rt_mix64(seed ^ 0x6C656E73ull);
+  A.width = (uint32_t)width;
+  return A;
+}
+
+/* the parts of a lens frame's workspace: a slice's rays, status words and radiance, then the frame's sums */
+struct LensWorkspace
+{
+  size_t rays, status, radiance, sum, total;
+  LensWorkspace(uint64_t n_pixels, uint64_t slice)
+  {
+    rays = 0;
+    status = rays + stage_align(48u * slice);
+    radiance = status + stage_align(4u * slice);
+    sum = radiance + stage_align(24u * slice);
+    total = sum + stage_align(24u * n_pixels);
+  }
+};
+
+/* what rt_hip_render_lens refuses without a device: RT_HIP_EINVAL, or RT_HIP_OK */
+int check_render_lens(const RtHipCamera *camera, const RtHipLens *lens, const RtHipParams *p, uint32_t slice_pixels, bool any_output)
+{
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is required");
+  const int rc = check_lens(camera, lens, p->width, p->height);
+  if (rc)
+    return rc;
+  if (!any_output)
+    return fail(RT_HIP_EINVAL, "at least one of sum, rgb and rgb8 is required");
+  if (p->integrator != RT_HIP_TRACE_PATH)
+    return fail(RT_HIP_EINVAL, "integrator %u: a lens frame traces paths (RT_HIP_TRACE_PATH) only", p->integrator);
+  if (p->samples < 1)
+    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", p->samples);
+  if (p->max_depth < 0 || p->max_depth > 1000000)
+    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  const uint64_t n_pixels = (uint64_t)p->width * (uint64_t)p->height;
+  if ((uint64_t)p->samples * n_pixels > 0x100000000ull)
+    return fail(RT_HIP_EINVAL, "samples x pixels = %d x %llu exceeds 2^32: a lens sample is a ray index of rt_hip_trace_rays", p->samples,
+                (unsigned long long)n_pixels);
+  if (slice_pixels == 0u)
+    return fail(RT_HIP_EINVAL, "slice_pixels must be >= 1");
+  const uint64_t n_tiles = (uint64_t)tiles_x_of(p->width) * tiles_y_of(p->height);
+  if (p->tile_first != 0u || p->tile_stride > 1u || (p->tile_count != 0u && p->tile_count != n_tiles))
+    return fail(RT_HIP_EINVAL, "a lens frame is the whole frame: the tile fields must describe it or be 0");
+  return RT_HIP_OK;
+}
+
+int lens_rays_launch(const PtLensRays &A, hipStream_t stream)
+{
+  const hipError_t e = lens_launch_rays(A, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "k_lens_rays launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+/* The frame: for every sample pass and slice the generator, the radiance query's own launch (trace_launch) and the sum; then the
+ * resolve.  All on `stream`, no host wait.  The depth limit and near_R are trace_launch's refusals: asked for once, up front. */
+int render_lens_launch(const RtHipScene *scene, const RtHipCamera *camera, const RtHipLens *lens, const RtHipParams *p, uint32_t slice_pixels,
+                       void *d_workspace, double *d_sum, float *d_rgb, uint8_t *d_rgb8, uint64_t *d_stats, hipStream_t stream)
+{
+  const uint64_t n_pixels = (uint64_t)p->width * (uint64_t)p->height;
+  const uint32_t slice = (uint32_t)std::min<uint64_t>(slice_pixels, n_pixels);
+  RtHipTraceParams T;
+  rt_hip_trace_defaults(&T);
+  T.origin_radius = std::sqrt((camera->position[0] * camera->position[0] + camera->position[1] * camera->position[1]) +
+                              camera->position[2] * camera->position[2]) + lens->aperture_radius;
+  if (!std::isfinite(T.origin_radius))
+    return fail(RT_HIP_EINVAL, "the camera position is not finite");
+  T.samples = 1;
+  T.max_depth = p->max_depth;
+  T.seed = p->seed;
+  {
+    PtLaunch dry;
+    const int rc = pooled_launch_prepare(scene, T.source, nullptr, T.origin_radius, 1, T.max_depth, T.seed, nullptr, dry);
+    if (rc)
+      return rc;
+  }
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  const LensWorkspace W(n_pixels, slice);
+  char *const ws = static_cast<char *>(d_workspace);
+  double *const rays = reinterpret_cast<double *>(ws + W.rays);
+  uint32_t *const status = reinterpret_cast<uint32_t *>(ws + W.status);
+  double *const radiance = reinterpret_cast<double *>(ws + W.radiance);
+  double *const sum = d_sum ? d_sum : reinterpret_cast<double *>(ws + W.sum);
+  HIP_TRY(hipMemsetAsync(sum, 0, 24u * n_pixels, stream));
+  PtLensRays A = lens_args(camera, lens, p->width, p->height, p->seed);
+  A.rays = rays;
+  const RtHipRadiance out = {status, radiance, nullptr, nullptr, nullptr, nullptr};
+  for (int32_t s = 0; s < p->samples; s++)
+    for (uint64_t first = 0; first < n_pixels; first += slice)
+    {
+      A.pixel_first = (uint32_t)first;
+      A.n = (uint32_t)std::min<uint64_t>(slice, n_pixels - first);
+      A.index_first = (uint32_t)((uint64_t)s * n_pixels + first);
+      int rc = lens_rays_launch(A, stream);
+      if (rc)
+        return rc;
+      T.index_first = A.index_first;
+      rc = trace_launch(scene, rays, A.n, &T, &out, d_stats, stream);
+      if (rc)
+        return rc;
+      const hipError_t e = lens_launch_accumulate(status, radiance, A.pixel_first, A.n, sum, stream);
+      if (e != hipSuccess)
+        return fail(RT_HIP_ERUNTIME, "k_lens_accumulate launch: %s", hipGetErrorString(e));
+    }
+  if (d_rgb || d_rgb8)
+  {
+    const hipError_t e = lens_launch_resolve(sum, n_pixels, p->samples, d_rgb, d_rgb8, stream);
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "k_lens_resolve launch: %s", hipGetErrorString(e));
+  }
+  return RT_HIP_OK;
+}
+
+/* rt_hip_render_lens_image: a scene of its own on the logical device, one allocation for the workspace, the frame and the counters,
+ * the frame on the null stream, the copies, the device's status word.  Everything is owned by this scope. */
+int render_lens_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
+                           const RtHipLens *lens, const RtHipParams *params, int device, float *h_rgb, uint8_t *h_rgb8, uint64_t *h_stats)
+{
+  constexpr uint32_t HOST_SLICE = 1u << 21; /* pixels a launch: 160 MB of rays, status words and radiance at most */
+  int rc = check_render_lens(camera, lens, params, HOST_SLICE, h_rgb || h_rgb8);
+  if (rc)
+    return rc;
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  OwnedScene own;
+  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  const uint64_t n_pixels = (uint64_t)params->width * (uint64_t)params->height;
+  StageArena A;
+  const int ws = A.part(LensWorkspace(n_pixels, std::min<uint64_t>(HOST_SLICE, n_pixels)).total);
+  const int rgb = A.part(12u * n_pixels, nullptr, h_rgb, h_rgb != nullptr);
+  const int rgb8 = A.part(3u * n_pixels, nullptr, h_rgb8, h_rgb8 != nullptr);
+  const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
+  rc = A.stage();
+  if (rc)
+    return rc;
+  rc = render_lens_launch(own.scene, camera, lens, params, HOST_SLICE, A.at<char>(ws), nullptr, A.at<float>(rgb), A.at<uint8_t>(rgb8),
+                          A.at<uint64_t>(stats), nullptr);
+  if (rc)
+    return rc;
+  rc = A.download();
+  if (rc)
+    return rc;
+  uint32_t flags = 0;
+  rc = status_take(phys, &flags);
+  return rc ? rc : status_to_error(flags);
+}
+
 /* ---- pixel refinement (rt_hip.h, rt_hip_select_pixels / _trace_pixels / _blend_pixels) ---------------------------------------
  * select and blend are image-space calls like the upsampling: arguments checked without a device, then the device that holds the
  * first buffer.  trace_pixels is a radiance query's launch (trace_launch) whose rays the kernel forms itself: the frame's camera
@@ -4859,6 +5057,97 @@ int rt_hip_trace_rays_host(const RtHipSphere *spheres, size_t n_spheres, const R
 {
   return guarded("rt_hip_trace_rays_host", [&] {
     return trace_rays_host_impl(spheres, n_spheres, meshes, n_meshes, h_rays, n, params, device, h_out, h_stats);
+  });
+}
+
+void rt_hip_lens_defaults(RtHipLens *lens)
+{
+  if (!lens)
+    return;
+  memset(lens, 0, sizeof *lens);
+  lens->focus_distance = 1.0;
+}
+
+int rt_hip_lens_rays(const RtHipCamera *camera, const RtHipLens *lens, int32_t width, int32_t height, uint64_t seed, uint32_t sample,
+                     uint32_t pixel_first, uint32_t n, double *d_rays, void *stream)
+{
+  int rc = check_lens(camera, lens, width, height);
+  if (rc)
+    return rc;
+  const uint64_t n_pixels = (uint64_t)width * (uint64_t)height;
+  if (((uint64_t)sample + 1u) * n_pixels > 0x100000000ull)
+    return fail(RT_HIP_EINVAL, "sample %u of %llu pixels: the stream index sample x pixels + pixel must stay below 2^32", sample,
+                (unsigned long long)n_pixels);
+  if ((uint64_t)pixel_first + n > n_pixels)
+    return fail(RT_HIP_EINVAL, "pixels [%u, +%u) exceed the frame's %llu", pixel_first, n, (unsigned long long)n_pixels);
+  if (n == 0)
+    return RT_HIP_OK;
+  if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u))
+    return fail(RT_HIP_EINVAL, "d_rays is required and must be 16-byte aligned");
+  int device = -1;
+  rc = device_of(d_rays, "d_rays", &device);
+  if (rc)
+    return rc;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  PtLensRays A = lens_args(camera, lens, width, height, seed);
+  A.pixel_first = pixel_first;
+  A.n = n;
+  A.index_first = (uint32_t)((uint64_t)sample * n_pixels + pixel_first);
+  A.rays = d_rays;
+  return lens_rays_launch(A, static_cast<hipStream_t>(stream));
+}
+
+size_t rt_hip_lens_workspace_bytes(int32_t width, int32_t height, uint32_t slice_pixels)
+{
+  if (!frame_size_ok(width, height, 2) || slice_pixels == 0u)
+    return 0;
+  const uint64_t n_pixels = (uint64_t)width * (uint64_t)height;
+  return LensWorkspace(n_pixels, std::min<uint64_t>(slice_pixels, n_pixels)).total;
+}
+
+int rt_hip_lens_resolve(const double *d_sum, int32_t width, int32_t height, int32_t samples, float *d_rgb, uint8_t *d_rgb8, void *stream)
+{
+  if (!frame_size_ok(width, height, 2))
+    return fail(RT_HIP_EINVAL, "width and height must be in [2, 2^20] with fewer than 2^32 pixels");
+  if (samples < 1)
+    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", samples);
+  if (!d_sum || (!d_rgb && !d_rgb8))
+    return fail(RT_HIP_EINVAL, "d_sum and an output are required");
+  int device = -1;
+  const int rc = device_of(d_sum, "d_sum", &device);
+  if (rc)
+    return rc;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  const hipError_t e = lens_launch_resolve(d_sum, (uint64_t)width * (uint64_t)height, samples, d_rgb, d_rgb8, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "k_lens_resolve launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int rt_hip_render_lens(const RtHipScene *scene, const RtHipCamera *camera, const RtHipLens *lens, const RtHipParams *params,
+                       uint32_t slice_pixels, void *d_workspace, double *d_sum, float *d_rgb, uint8_t *d_rgb8, uint64_t *d_stats, void *stream)
+{
+  const int rc = check_render_lens(camera, lens, params, slice_pixels, d_sum || d_rgb || d_rgb8);
+  if (rc)
+    return rc;
+  if (!scene || !d_workspace)
+    return fail(RT_HIP_EINVAL, "scene and d_workspace are required");
+  if (reinterpret_cast<uintptr_t>(d_workspace) & 15u) /* (the slice's rays lie at its start: rt_hip_trace_rays' own rule) */
+    return fail(RT_HIP_EINVAL, "d_workspace must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_sum) & 7u)
+    return fail(RT_HIP_EINVAL, "d_sum must be 8-byte aligned");
+  return guarded("rt_hip_render_lens", [&] {
+    return render_lens_launch(scene, camera, lens, params, slice_pixels, d_workspace, d_sum, d_rgb, d_rgb8, d_stats, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_hip_render_lens_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
+                             const RtHipLens *lens, const RtHipParams *params, int device, float *h_rgb, uint8_t *h_rgb8, uint64_t *h_stats)
+{
+  return guarded("rt_hip_render_lens_image", [&] {
+    return render_lens_image_impl(spheres, n_spheres, meshes, n_meshes, camera, lens, params, device, h_rgb, h_rgb8, h_stats);
   });
 }
 

@@ -120,6 +120,8 @@ typedef struct
   int upsample;     /* -u: the factor; 0: not given */
   int query;        /* -q given */
   double qx, qy;    /* -q: the pixel */
+  int lens;         /* -l given */
+  double lens_aperture, lens_focus; /* -l: the thin lens' aperture radius and focus distance */
   uint64_t seed;
 } Args;
 
@@ -134,7 +136,9 @@ static void usage(const char *prog)
           "          [-n <denoise iterations 0..10: -o denoised, <name>.noisy.png as rendered>]\n"
           "          [-e <adaptive sampling: tiles whose error estimate is <= this stop early; -s is the budget; one GPU>]\n"
           "          [-q <x,y: print what the ray through the centre of that pixel hits; nothing is rendered>]\n"
-          "          [-u <factor >= 2: render at 1/factor of the size, upsample under full-size first-hit buffers; <name>.low.png>]\n",
+          "          [-u <factor >= 2: render at 1/factor of the size, upsample under full-size first-hit buffers; <name>.low.png>]\n"
+          "          [-l <aperture,focus: depth of field from a thin lens of that radius, sharp at that distance; one GPU, trace_path,\n"
+          "               not with -p, -e or -u; aperture 0 is the pinhole frame>]\n",
           prog);
 }
 
@@ -184,6 +188,19 @@ static int parse_args(int argc, char **argv, Args *a)
       if (end == second || *end != '\0' || !(a->qx >= 0) || !(a->qy >= 0) || a->qx != floor(a->qx) || a->qy != floor(a->qy))
         return -1;
       a->query = 1;
+      break;
+    }
+    case 'l':
+    {
+      char *end = NULL;
+      a->lens_aperture = strtod(val, &end);
+      if (end == val || *end != ',')
+        return -1;
+      const char *second = end + 1;
+      a->lens_focus = strtod(second, &end);
+      if (end == second || *end != '\0' || !(a->lens_aperture >= 0) || !(a->lens_focus > 0))
+        return -1;
+      a->lens = 1;
       break;
     }
     case 'u':
@@ -360,7 +377,8 @@ int main(int argc, char **argv)
   RtSceneInfo info;
   if (rt_scene_info(a.config, &info) != 0 || a.options.width < 2 || a.options.height < 2 || a.options.samples < 1 ||
       (a.integrator != RT_TRACE_PATH && a.integrator != RT_CAST_RAY) ||
-      (a.pass > 0 && (a.pass > a.options.samples || a.gpus > 1)) || (a.adaptive && (a.pass > 0 || a.gpus > 1)))
+      (a.pass > 0 && (a.pass > a.options.samples || a.gpus > 1)) || (a.adaptive && (a.pass > 0 || a.gpus > 1)) ||
+      (a.lens && a.lens_aperture > 0 && (a.pass > 0 || a.adaptive || a.upsample || a.gpus > 1 || a.integrator != RT_TRACE_PATH)))
   {
     usage(argv[0]);
     return EXIT_FAILURE;
@@ -398,6 +416,8 @@ int main(int argc, char **argv)
   rt_set_devices(a.gpus);
   rt_set_integrator(a.integrator);
   rt_set_bvh_builder(a.bvh);
+  if (a.lens)
+    rt_set_lens(a.lens_aperture, a.lens_focus);
 
   if (a.upsample)
   {

@@ -56,6 +56,21 @@ void rt_set_integrator(int integrator)
     g_integrator = integrator;
 }
 int rt_get_integrator(void) { return g_integrator; }
+
+/* the thin lens of render() / render_ex(): stored as given, judged by the shim when a frame is rendered */
+static double g_lens_aperture = 0.0, g_lens_focus = 1.0;
+void rt_set_lens(double aperture_radius, double focus_distance)
+{
+  g_lens_aperture = aperture_radius;
+  g_lens_focus = focus_distance;
+}
+void rt_get_lens(double *aperture_radius, double *focus_distance)
+{
+  if (aperture_radius)
+    *aperture_radius = g_lens_aperture;
+  if (focus_distance)
+    *focus_distance = g_lens_focus;
+}
 static int g_bvh_builder = RT_BVH_HOST;
 void rt_set_bvh_builder(int builder)
 {
@@ -278,8 +293,23 @@ void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t 
 
   uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
   double seconds = 0;
-  int rc = rt_hip_render_image((const RtHipSphere *)objects, n_objects, hm, n_meshes, (const RtHipCamera *)camera,
-                               &p, devices_to_use(), linear_rgb, framebuffer, stats, &seconds);
+  int rc;
+  if (g_lens_aperture > 0)
+  { /* depth of field: the lens frame, on one device; the seconds are the call's, by the host's clock */
+    RtHipLens lens;
+    rt_hip_lens_defaults(&lens);
+    lens.aperture_radius = g_lens_aperture;
+    lens.focus_distance = g_lens_focus;
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    rc = rt_hip_render_lens_image((const RtHipSphere *)objects, n_objects, hm, n_meshes, (const RtHipCamera *)camera, &lens, &p, 0,
+                                  linear_rgb, framebuffer, stats);
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    seconds = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+  }
+  else
+    rc = rt_hip_render_image((const RtHipSphere *)objects, n_objects, hm, n_meshes, (const RtHipCamera *)camera,
+                             &p, devices_to_use(), linear_rgb, framebuffer, stats, &seconds);
   free(hm);
   g_last_cancelled = rc == RT_HIP_ECANCELLED;
   if (rc != RT_HIP_OK && rc != RT_HIP_ECANCELLED)

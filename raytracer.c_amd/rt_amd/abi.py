@@ -144,6 +144,10 @@ RADIANCE_FIELDS = ("status", "radiance", "samples", "paths", "casts", "ray")   #
 RADIANCE_SHAPES = {"status": ("uint32", 1), "radiance": ("float64", 3), "samples": ("float64", 0), "paths": ("uint64", 1),
                    "casts": ("uint64", 1), "ray": ("float64", 6)}   # dtype, values per ray (samples: 3 per sample)
 
+class RtHipLens(C.Structure):  # rt_hip.h: a thin lens (rt_hip_lens_defaults), 24 B
+    _fields_ = [("aperture_radius", C.c_double), ("focus_distance", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class RtHipPixelParams(C.Structure):  # rt_hip.h: a pixel refinement's trace (rt_hip_pixel_defaults), 32 B
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("sample_first", C.c_int32),
                 ("max_depth", C.c_int32), ("integrator", C.c_uint32), ("seed", C.c_uint64)]
@@ -284,6 +288,15 @@ SHIM_SYMBOLS = {
     "rt_hip_trace_kernel_name": (C.c_char_p, [C.c_void_p]),
     "rt_hip_trace_kernel_count": (C.c_int, []),
     "rt_hip_trace_kernel_launches": (C.c_char_p, [C.c_int, C.POINTER(C.c_uint64)]),
+    "rt_hip_lens_defaults": (None, [C.POINTER(RtHipLens)]),
+    "rt_hip_lens_rays": (C.c_int, [C.POINTER(Camera), C.POINTER(RtHipLens), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_hip_lens_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_uint32]),
+    "rt_hip_render_lens": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipLens), C.POINTER(RtHipParams), C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_lens_resolve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_render_lens_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.POINTER(Camera),
+                                           C.POINTER(RtHipLens), C.POINTER(RtHipParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_denoise_defaults": (None, [C.POINTER(RtHipDenoiseParams)]),
     "rt_hip_denoise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rt_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_void_p,
@@ -352,6 +365,8 @@ HOST_SYMBOLS = {
                          C.POINTER(Camera), C.POINTER(Options)]),
     "rt_set_max_depth": (None, [C.c_int]),
     "rt_set_seed": (None, [C.c_uint64]),
+    "rt_set_lens": (None, [C.c_double, C.c_double]),
+    "rt_get_lens": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_set_integrator": (None, [C.c_int]),
     "rt_get_integrator": (C.c_int, []),
     "rt_set_bvh_builder": (None, [C.c_int]),
@@ -447,6 +462,14 @@ def denoise_params(iterations=None, sigma_color=None, sigma_depth=None, normal_p
         if v is not None:
             p.flags = (p.flags | bit) if v else (p.flags & ~bit)
     return p
+
+
+def lens_params(aperture, focus):
+    """an RtHipLens of the given aperture radius and focus distance"""
+    lens = RtHipLens()
+    load_shim().rt_hip_lens_defaults(C.byref(lens))
+    lens.aperture_radius, lens.focus_distance = aperture, focus
+    return lens
 
 
 def reproject_params(max_history=None, depth_tol=None, normal_min=None):

@@ -510,6 +510,44 @@ class GpuScene:
                          n=count)
         return count
 
+    def render_lens(self, aperture, focus, samples, seed, camera=None, max_depth=None, slice_pixels=None, stats=None):
+        """A frame with depth of field (rt_hip.h, rt_hip_render_lens): a thin lens of radius `aperture` focused at distance `focus`
+        in front of the camera (None: the scene's own), `samples` lens rays per pixel traced by the radiance query; asynchronous on
+        torch's current stream -> (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3], sum float64 [H, W, 3], stats int64 [4]; += into the
+        tensor given).  slice_pixels: pixels per launch (None: the whole frame); no output bit depends on it."""
+        dev = torch.device("cuda", self.device)
+        cam = camera if camera is not None else self.scene.camera
+        w, h = self.scene.width, self.scene.height
+        p = self.params(seed, 0, 0, 0, samples=samples, max_depth=max_depth)
+        lens = abi.lens_params(aperture, focus)
+        slice_pixels = w * h if slice_pixels is None else slice_pixels
+        ws = torch.empty(max(self.shim.rt_hip_lens_workspace_bytes(w, h, slice_pixels), 256), dtype=torch.uint8, device=dev)
+        rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        total = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+        if stats is None:
+            stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._lens_workspace = ws   # keep alive until the stream has used it
+        _check(self.shim.rt_hip_render_lens(self.handle, C.byref(cam), C.byref(lens), C.byref(p), slice_pixels, C.c_void_p(ws.data_ptr()),
+                                            C.c_void_p(total.data_ptr()), C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()),
+                                            C.c_void_p(stats.data_ptr()), C.c_void_p(stream)), "rt_hip_render_lens")
+        return rgb, rgb8, total, stats
+
+    def focus_at(self, x, y, camera=None):
+        """Autofocus: the focus_distance that puts what is under the centre of pixel (x, y) in focus, or None where the ray misses.
+        One ray query through the pixel centre (as pick()); the hit's t over |d|, d the lens contract's direction, not normalised:
+        d = position - (lower_left_corner + (horizontal*u + vertical*v)) (synchronises)"""
+        cam = camera if camera is not None else self.scene.camera
+        u, v = (x + 0.5) / (self.scene.width - 1.0), (y + 0.5) / (self.scene.height - 1.0)
+        out = self.query_uv([[u, v]], camera=cam, want=("status", "t"))
+        torch.cuda.synchronize(torch.device("cuda", self.device))
+        if int(out["status"].cpu()[0]) != 1:
+            return None
+        pos, llc, hor, ver = (c.tuple() for c in (cam.position, cam.lower_left_corner, cam.horizontal, cam.vertical))
+        d = [pos[k] - (llc[k] + (hor[k] * u + ver[k] * v)) for k in range(3)]
+        return float(out["t"].cpu()[0]) / ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) ** 0.5
+
     def render_panorama(self, width, height, origin, samples, seed, max_depth=None):
         """An equirectangular view from `origin` (scene.panorama_rays: no Camera expresses it), `samples` paths per pixel, pixel
         k = y * width + x on the stream (seed, k, s) -> (float64 [height, width, 3] linear radiance on the device, stats)"""
@@ -1403,3 +1441,52 @@ def trace_rays_host(scene, rays, samples, seed, max_depth=None, normalize=False,
                                        C.byref(rad), stats), "rt_hip_trace_rays_host")
     out["stats"] = dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
     return out
+
+
+def lens_rays(camera, width, height, aperture, focus, seed, sample, pixel_first=0, n=None, device=0):
+    """The lens rays of one sample pass (rt_hip.h, rt_hip_lens_rays): pixels [pixel_first, pixel_first + n) (n None: to the frame's
+    end) of sample `sample` -> a device tensor [n, 6] float64 (origin, direction), asynchronous on torch's current stream"""
+    shim = abi.load_shim()
+    dev = torch.device("cuda", device)
+    n = width * height - pixel_first if n is None else n
+    rays = torch.empty((max(n, 0), 6), dtype=torch.float64, device=dev)
+    lens = abi.lens_params(aperture, focus)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_lens_rays(C.byref(camera), C.byref(lens), width, height, seed, sample, pixel_first, n,
+                                 C.c_void_p(rays.data_ptr() if n > 0 else None), C.c_void_p(stream)), "rt_hip_lens_rays")
+    return rays
+
+
+def lens_resolve(total, samples):
+    """The lens frame's resolve alone (rt_hip.h, rt_hip_lens_resolve): total float64 [H, W, 3] on a device -> (rgb float32 [H, W, 3],
+    rgb8 uint8 [H, W, 3]), the mean over `samples` and its tonemapped bytes; asynchronous on torch's current stream"""
+    shim = abi.load_shim()
+    total = total.contiguous()
+    h, w, _ = total.shape
+    rgb = torch.empty((h, w, 3), dtype=torch.float32, device=total.device)
+    rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=total.device)
+    stream = torch.cuda.current_stream(total.device).cuda_stream
+    _check(shim.rt_hip_lens_resolve(C.c_void_p(total.data_ptr()), w, h, samples, C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()),
+                                    C.c_void_p(stream)), "rt_hip_lens_resolve")
+    return rgb, rgb8
+
+
+def render_lens_host(scene, aperture, focus, samples, seed, camera=None, max_depth=None, device=0):
+    """rt_hip_render_lens_image(): the C hosts' entry point (its own scene on logical device `device`, synchronous) ->
+    (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3], stats dict)"""
+    import numpy as np
+    shim = abi.load_shim()
+    p = abi.RtHipParams()
+    p.width, p.height = scene.width, scene.height
+    p.samples = samples
+    p.max_depth = scene.max_depth if max_depth is None else max_depth
+    p.seed = seed
+    lens = abi.lens_params(aperture, focus)
+    cam = camera if camera is not None else scene.camera
+    img = np.zeros((scene.height, scene.width, 3), dtype=np.float32)
+    img8 = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
+    stats = (C.c_uint64 * abi.NSTATS)()
+    meshes = scene.hip_meshes()
+    _check(shim.rt_hip_render_lens_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(cam), C.byref(lens), C.byref(p),
+                                         device, img.ctypes.data, img8.ctypes.data, stats), "rt_hip_render_lens_image")
+    return img, img8, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
