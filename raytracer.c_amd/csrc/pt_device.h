@@ -506,7 +506,7 @@ struct PtPixels
   unsigned long long *paths, *casts;
 };
 
-/* The ordered compaction of a per-pixel map (rt_hip.h, rt_hip_select_pixels; pt_select_* in pt_kernel.hip): pixel p of `values` is
+/* The ordered compaction of a per-pixel map (rt_hip.h, rt_hip_select_pixels; pt_select_* in image_ops.hip): pixel p of `values` is
  * selected iff (lo <= v && v <= hi) != invert.  A workgroup of pt_select_count / pt_select_scatter covers PT_SELECT_BLOCK pixels, a
  * workgroup of pt_select_scan PT_SELECT_SCAN counts. */
 #define PT_SELECT_BLOCK 256u
@@ -519,7 +519,7 @@ struct PtSelect
   uint32_t invert;
 };
 
-/* One blend of traced pixels into a frame (rt_hip.h, rt_hip_blend_pixels; pt_blend_pixels in pt_kernel.hip) */
+/* One blend of traced pixels into a frame (rt_hip.h, rt_hip_blend_pixels; pt_blend_pixels in image_ops.hip) */
 struct PtBlend
 {
   const uint32_t *pixels, *status;
@@ -533,7 +533,7 @@ struct PtBlend
   float *weight; /* may be null; may be `prior` itself */
 };
 
-/* One launch of the denoiser (rt_hip.h, rt_hip_denoise; pt_denoise_* in pt_kernel.hip).  The workspace holds, per pixel of the
+/* One launch of the denoiser (rt_hip.h, rt_hip_denoise; pt_denoise_* in image_ops.hip).  The workspace holds, per pixel of the
  * row-major w x h image: two ping-pong float4 colour buffers e[0], e[1] (the filtered signal, .w = 1 valid / 0 invalid), the
  * guidance float4 (normal, depth) and uint2 (hits, object) the prepare pass packs so that a tap is three loads. */
 struct PtDenoise
@@ -549,7 +549,7 @@ struct PtDenoise
   double sigma_z;
 };
 
-/* One temporal reprojection (rt_hip.h, rt_hip_reproject; pt_reproject in pt_kernel.hip): row-major w x h images of the frame
+/* One temporal reprojection (rt_hip.h, rt_hip_reproject; pt_reproject in image_ops.hip): row-major w x h images of the frame
  * (colour, normal, depth, hits, object) and of the history (the same and its length; all null together: the first frame), the two
  * cameras, and the outputs -- out_rgb and out_len always, the bytes and the motion (2 floats per pixel) where wanted. */
 struct PtReproject
@@ -566,7 +566,7 @@ struct PtReproject
   double max_history, depth_tol, normal_min;
 };
 
-/* The previous points of n query hits (rt_hip.h, rt_hip_prev_points; pt_prev_points in pt_kernel.hip): the hits' status, prim,
+/* The previous points of n query hits (rt_hip.h, rt_hip_prev_points; pt_prev_points in image_ops.hip): the hits' status, prim,
  * bary (2 doubles) and point (3 doubles), the previous positions (9 doubles per triangle; may be null with n_triangles 0) and the
  * output, 3 doubles per entry (it may be `point`). */
 struct PtPrevPoints
@@ -577,7 +577,7 @@ struct PtPrevPoints
   uint64_t n, n_triangles;
 };
 
-/* The same with moved spheres (rt_hip.h, rt_hip_prev_points_moved; pt_prev_points_moved in pt_kernel.hip): the hits' object as
+/* The same with moved spheres (rt_hip.h, rt_hip_prev_points_moved; pt_prev_points_moved in image_ops.hip): the hits' object as
  * well, and the previous and current spheres, 4 doubles each (cx cy cz radius; may be null with n_spheres 0).  spheres_static:
  * the call gave no previous spheres and n_spheres 0 -- a sphere hit copies its point, as pt_prev_points does. */
 struct PtPrevPointsMoved
@@ -589,7 +589,7 @@ struct PtPrevPointsMoved
   uint32_t spheres_static;
 };
 
-/* One guided upsampling (rt_hip.h, rt_hip_upsample; pt_upsample in pt_kernel.hip): the low frame's row-major wl x hl images
+/* One guided upsampling (rt_hip.h, rt_hip_upsample; pt_upsample in image_ops.hip): the low frame's row-major wl x hl images
  * (colour, normal, depth, hits; albedo with demodulate, object with object_edges), the guides of the w x h frame (the same fields
  * without a colour), and the outputs -- out_rgb always, the bytes and the confidence where wanted. */
 struct PtUpsample
@@ -608,7 +608,7 @@ struct PtUpsample
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-/* host-side launchers, defined next to the kernels in pt_kernel.hip */
+/* host-side launchers, defined next to the kernels in pt_kernel.hip (and, under their own heading below, in image_ops.hip) */
 size_t pt_render_lds_bytes(const PtSceneView &scene);
 /* the chunks a trace_path launch of a scene with M_REFRACTION takes at least when it has a chunk workspace (pt_plan_launch;
  * rt_hip_suggest_chunks_depth suggests as many): pt_refr_pool_chunks_needed where that is a usable chunk count -- at most one
@@ -681,14 +681,12 @@ hipError_t pt_launch_selftest_intersect(int kind, const double *rays, const doub
                                         float *filt, float *tri32, uint32_t n, double near_R, double filt_shift,
                                         uint8_t *hit, double *tuv, unsigned long long *keep, hipStream_t stream);
 /* the AOV kernels (pt_kernel.hip: render_aov, PT_AOV_FAMILY): which form a scene takes, the launch (a tile per wave; the outputs: PtAovOut),
- * names and launch counters; and the scatter of their compact 1- or 3-channel 32-bit buffers to row-major images */
+ * names and launch counters (the scatter of their compact buffers to row-major images: pt_launch_untile_aov below) */
 int pt_aov_pick(const PtSceneView &scene);
 hipError_t pt_launch_aov(const PtLaunch &launch, const PtAovOut &out, hipStream_t stream, int which);
 const char *pt_aov_kernel_name_of(int which);
 int pt_aov_kernel_count(void);
 unsigned long long pt_aov_kernel_launches(int which);
-hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int width, int height, uint32_t tile_first,
-                                uint32_t tile_stride, uint32_t tile_count, uint32_t *image, hipStream_t stream);
 /* the ray-query kernels (pt_kernel.hip: query_rays, PT_QUERY_FAMILY): which form a scene takes, the launch (a ray per lane), names and
  * launch counters */
 int pt_query_pick(const PtSceneView &scene);
@@ -711,6 +709,15 @@ hipError_t pt_launch_pixels(const PtLaunch &launch, const PtPixels &pixels, hipS
 const char *pt_pixel_kernel_name_of(int which);
 int pt_pixel_kernel_count(void);
 unsigned long long pt_pixel_kernel_launches(int which);
+/* ---- the image-space passes (image_ops.hip, a translation unit of its own): launchers of kernels that see buffers of pixels or
+ * of list entries and never a scene, a ray or a PtLaunch ---- */
+/* the scatter of compact tile-major buffers to row-major images: the colour (floats and bytes, either may be null), and the AOV
+ * kernels' 1- or 3-channel 32-bit buffers */
+hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,
+                            uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *image_rgb,
+                            uint8_t *image_rgb8, hipStream_t stream);
+hipError_t pt_launch_untile_aov(const uint32_t *tiles, uint32_t channels, int width, int height, uint32_t tile_first,
+                                uint32_t tile_stride, uint32_t tile_count, uint32_t *image, hipStream_t stream);
 /* the compaction: its workspace (the per-workgroup counts and every level of their scan; 0 for no pixel), and the launches on
  * `stream` -- the counts, the scan's levels (a loop over levels here on the host, no workgroup waits on another), the scatter
  * (capacity > 0 only).  *count gets the full count. */
@@ -729,9 +736,6 @@ hipError_t pt_launch_prev_points(const PtPrevPoints &args, hipStream_t stream);
 hipError_t pt_launch_prev_points_moved(const PtPrevPointsMoved &args, hipStream_t stream);
 /* guided upsampling: one launch, a 16 x 16 block of the high frame's pixels per workgroup, on `stream` */
 hipError_t pt_launch_upsample(const PtUpsample &args, hipStream_t stream);
-hipError_t pt_launch_untile(const float *tiles_rgb, const uint8_t *tiles_rgb8, int width, int height,
-                            uint32_t tile_first, uint32_t tile_stride, uint32_t tile_count, float *image_rgb,
-                            uint8_t *image_rgb8, hipStream_t stream);
 #endif
 
 /* ---- the thin-lens camera (rt_hip.h, "thin-lens camera"; the kernels are lens.hip's, a translation unit of its own) ---- */

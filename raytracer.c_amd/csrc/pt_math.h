@@ -1,7 +1,8 @@
-/* pt_math.h -- vectors, the RNG draws, fixed-point terms, the tonemap, the material code's math without library calls
- * (atan2_tab, cube, pow10, frac1), and the PT_DIAG / PT_PHASE instrumentation macros.
- * Part of the one translation unit pt_kernel.hip (included there, in this order: pt_math.h, pt_intersect.h, pt_filter.h,
- * pt_scene_ctx.h, pt_trace.h, pt_body_pooled.h, pt_body_queued.h, pt_body_static.h); device code for gfx950 only. */
+/* pt_math.h -- vectors, the RNG draws, fixed-point terms, the tonemap, the tile geometry, the material code's math without library
+ * calls (atan2_tab, cube, pow10, frac1), and the PT_DIAG / PT_PHASE instrumentation macros.
+ * Part of the translation unit pt_kernel.hip (included there, in this order: pt_math.h, pt_intersect.h, pt_filter.h,
+ * pt_scene_ctx.h, pt_trace.h, pt_body_pooled.h, pt_body_queued.h, pt_body_static.h), and the one of these headers that stands
+ * alone after pt_device.h and rt_rng.h: lens.hip and image_ops.hip include it too.  Device code for gfx950 only. */
 #ifndef PT_MATH_H
 #define PT_MATH_H
 
@@ -71,6 +72,17 @@ __device__ __forceinline__ uint8_t tonemap(double x)
   double lo = (g < 1) ? g : 1.0; /* MIN(x, 1): NaN -> 1 */
   double cl = (0 > lo) ? 0.0 : lo; /* MAX(0, .) */
   return (uint8_t)(255.0 * cl);
+}
+
+/* tile geometry: pixel `pit` (row-major in its 8 x 8 tile) of tile `tile` of a frame tiles_x tiles wide is image pixel (x, y);
+ * returns whether that is inside the image (the last column and row of tiles may hang over its edge).  Written out where the
+ * call would move a kernel's listing: finish_pixels and the resolves' copies of it (pt_resolve_tiles), pt_tile_error, pt_untile.
+ * Here and not in pt_trace.h: image_ops.hip (pt_untile_aov) needs it, and takes this header alone. */
+__device__ __forceinline__ bool tile_pixel(uint32_t tiles_x, uint32_t tile, uint32_t pit, int width, int height, uint32_t &x, uint32_t &y)
+{
+  x = (tile % tiles_x) * PT_TILE + (pit & 7u);
+  y = (tile / tiles_x) * PT_TILE + (pit >> 3);
+  return x < (uint32_t)width && y < (uint32_t)height;
 }
 
 /* ---- math of the material code without library calls inside the trip loops -------------------------------------

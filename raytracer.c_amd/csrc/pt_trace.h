@@ -488,16 +488,6 @@ __device__ __forceinline__ uint32_t launch_slot_wave(const PtLaunch &L, uint32_t
   return LIST ? L.slot_list[__builtin_amdgcn_readfirstlane(j)] : j;
 }
 
-/* tile geometry: pixel `pit` (row-major in its 8 x 8 tile) of tile `tile` of a frame tiles_x tiles wide is image pixel (x, y);
- * returns whether that is inside the image (the last column and row of tiles may hang over its edge).  Written out where the
- * call would move a kernel's listing: finish_pixels and the resolves' copies of it (pt_resolve_tiles), pt_tile_error, pt_untile. */
-__device__ __forceinline__ bool tile_pixel(uint32_t tiles_x, uint32_t tile, uint32_t pit, int width, int height, uint32_t &x, uint32_t &y)
-{
-  x = (tile % tiles_x) * PT_TILE + (pit & 7u);
-  y = (tile / tiles_x) * PT_TILE + (pit >> 3);
-  return x < (uint32_t)width && y < (uint32_t)height;
-}
-
 __device__ __forceinline__ void finish_pixels(const PtLaunch &L, const unsigned long long *sums,
                                               const unsigned long long *nan_mask, uint32_t tile, float *out_f,
                                               uint8_t *out_b)

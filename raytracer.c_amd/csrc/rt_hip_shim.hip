@@ -1,5 +1,5 @@
 /* rt_hip_shim.hip -- the C-ABI of include/rt_hip.h over the kernels of
- * pt_kernel.hip.  Thin by design: argument checks, the one-time conversion of
+ * pt_kernel.hip and its sibling units.  Thin by design: argument checks, the one-time conversion of
  * the reference's scene structs (Object raytracer.h:104-111, Vertex :61) into
  * the kernel's HBM layout (pt_device.h), launches, and the single-process
  * multi-GPU gather.  No CPU rendering path exists here: every failure is
@@ -164,6 +164,53 @@ struct StageArena
       if (p.dst)
         HIP_TRY(hipMemcpy(p.dst, buf.at<char>(p.offset), p.bytes, hipMemcpyDeviceToHost));
     return RT_HIP_OK;
+  }
+};
+
+/* The parts of a radiance query's or a pixel refinement's host form behind its input: the requested outputs, then the counters,
+ * cleared.  The device's RtHipRadiance once the arena is staged, and the counters added to the caller's after the download. */
+struct RadianceStage
+{
+  int out[6], stats;
+  uint64_t st[RT_HIP_NSTATS];
+  uint64_t *h_stats;
+  RadianceStage(const RadianceStage &) = delete; /* (the plan points into st) */
+  RadianceStage(StageArena &A, const RtHipRadiance *h, uint64_t n, int32_t samples, uint64_t *h_stats_) : h_stats(h_stats_)
+  {
+    void *host[6] = {h->status, h->radiance, h->samples, h->paths, h->casts, h->ray};
+    const size_t bytes_per_entry[6] = {4, 24, 24u * (size_t)samples, 8, 8, 48};
+    for (int k = 0; k < 6; k++)
+      out[k] = A.part(bytes_per_entry[k] * n, nullptr, host[k], host[k] != nullptr);
+    stats = A.zeroed(sizeof st, h_stats ? st : nullptr);
+  }
+  RtHipRadiance device(const StageArena &A) const
+  {
+    return {A.at<uint32_t>(out[0]), A.at<double>(out[1]), A.at<double>(out[2]), A.at<uint64_t>(out[3]), A.at<uint64_t>(out[4]), A.at<double>(out[5])};
+  }
+  int download(const StageArena &A) const
+  {
+    const int rc = A.download();
+    for (int k = 0; !rc && h_stats && k < RT_HIP_NSTATS; k++)
+      h_stats[k] += st[k];
+    return rc;
+  }
+};
+
+/* The first-hit buffers an image-space host form reads: the channels of an n-pixel RtHipAov as uploaded parts, declared in the
+ * order albedo, normal, depth, hits, object -- albedo and object where the call's flags want them, nothing at all without `have`
+ * (a history that is not given).  The device's RtHipAov once the arena is staged: null for a channel that has no part. */
+struct AovStage
+{
+  int albedo, normal, depth, hits, object; /* (initialised in this order) */
+  AovStage(StageArena &A, const RtHipAov *h, size_t n, bool want_albedo, bool want_object, bool have = true)
+      : albedo(A.part(12u * n, h->albedo, nullptr, have && want_albedo)), normal(A.part(12u * n, h->normal, nullptr, have)),
+        depth(A.part(4u * n, h->depth, nullptr, have)), hits(A.part(4u * n, h->hits, nullptr, have)),
+        object(A.part(4u * n, h->object, nullptr, have && want_object))
+  {
+  }
+  RtHipAov device(const StageArena &A) const
+  {
+    return {A.at<float>(albedo), A.at<float>(normal), A.at<float>(depth), A.at<uint32_t>(object), A.at<uint32_t>(hits)};
   }
 };
 
@@ -2361,6 +2408,46 @@ int physical_device(int device, int *phys)
   return RT_HIP_OK;
 }
 
+/* the device that holds `ptr`: a host pointer would fault the kernel, so it is refused */
+int device_of(const void *ptr, const char *what, int *device)
+{
+  if (usable_devices() < 1)
+    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
+  hipPointerAttribute_t attr = {};
+  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess || attr.type != hipMemoryTypeDevice)
+  {
+    (void)hipGetLastError();
+    return fail(RT_HIP_EINVAL, "%s is not device memory", what);
+  }
+  *device = attr.device;
+  return RT_HIP_OK;
+}
+
+/* The two prologues of the calls that have no scene: `body` runs with a device current -- the one that holds `ptr` (a
+ * device-pointer form), or logical device `device` of the device map (a host-array form; body(phys) gets the HIP device) -- and
+ * the previous device comes back when it returns.  A lookup that fails is the call's answer and `body` does not run. */
+template <class F>
+int on_device_of(const void *ptr, const char *what, F &&body)
+{
+  int device = -1;
+  if (const int rc = device_of(ptr, what, &device))
+    return rc;
+  DeviceScope scope(device);
+  HIP_TRY(scope.status);
+  return body();
+}
+
+template <class F>
+int on_logical_device(int device, F &&body)
+{
+  int phys = -1;
+  if (const int rc = physical_device(device, &phys))
+    return rc;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  return body(phys);
+}
+
 /* rt_hip_render_aov_image on its scene: compact buffers for the requested outputs, one launch over every tile, the scatter, the
  * copies.  Synchronous on the null stream. */
 int aov_image_of(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *h_image)
@@ -2413,7 +2500,7 @@ int render_aov_image_impl(const RtHipSphere *spheres, size_t n_spheres, const Rt
 
 /* ---- the denoiser (rt_hip.h, rt_hip_denoise_*) ------------------------------------------------------------------------------
  * Workspace layout for n = w*h pixels, each part 256-B aligned: e[0], e[1] and the guidance (16 B per pixel each), then hits +
- * object (8 B per pixel).  The kernels and their arithmetic are pt_denoise_* in pt_kernel.hip. */
+ * object (8 B per pixel).  The kernels and their arithmetic are pt_denoise_* in image_ops.hip. */
 /* a frame of the image-space calls: both sides in [min_side, 2^20], fewer than 2^32 pixels */
 bool frame_size_ok(int32_t width, int32_t height, int32_t min_side)
 {
@@ -2485,42 +2572,59 @@ int denoise_launch(const float *rgb, const RtHipAov *aov, int32_t width, int32_t
 int denoise_image_impl(const float *h_rgb, const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
                        int device, float *h_out, uint8_t *h_out8)
 {
-  int rc = check_denoise(h_rgb, h_aov, width, height, params, h_out, h_out8);
-  if (rc)
+  if (const int rc = check_denoise(h_rgb, h_aov, width, height, params, h_out, h_out8))
     return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  const size_t n = (size_t)width * (size_t)height;
-  const bool demod = (params->flags & RT_HIP_DENOISE_DEMODULATE) != 0, edges = (params->flags & RT_HIP_DENOISE_OBJECT_EDGES) != 0;
-  /* the workspace, the colour (in and out: the floats are filtered in place), the buffers the flags ask for, the bytes */
-  StageArena A;
-  const int ws = A.part(denoise_ws_bytes(n));
-  const int rgb = A.part(12u * n, h_rgb, h_out);
-  const int albedo = A.part(12u * n, h_aov->albedo, nullptr, demod);
-  const int normal = A.part(12u * n, h_aov->normal);
-  const int depth = A.part(4u * n, h_aov->depth);
-  const int hits = A.part(4u * n, h_aov->hits);
-  const int object = A.part(4u * n, h_aov->object, nullptr, edges);
-  const int rgb8 = A.part(3u * n, nullptr, h_out8, h_out8 != nullptr);
-  rc = A.stage();
-  if (rc)
-    return rc;
-  const RtHipAov d = {A.at<float>(albedo), A.at<float>(normal), A.at<float>(depth), A.at<uint32_t>(object), A.at<uint32_t>(hits)};
-  rc = denoise_launch(A.at<float>(rgb), &d, width, height, params, A.at<char>(ws), h_out ? A.at<float>(rgb) : nullptr, A.at<uint8_t>(rgb8),
-                      nullptr);
-  return rc ? rc : A.download();
+  return on_logical_device(device, [&](int) {
+    const size_t n = (size_t)width * (size_t)height;
+    const bool demod = (params->flags & RT_HIP_DENOISE_DEMODULATE) != 0, edges = (params->flags & RT_HIP_DENOISE_OBJECT_EDGES) != 0;
+    /* the workspace, the colour (in and out: the floats are filtered in place), the buffers the flags ask for, the bytes */
+    StageArena A;
+    const int ws = A.part(denoise_ws_bytes(n));
+    const int rgb = A.part(12u * n, h_rgb, h_out);
+    const AovStage aov(A, h_aov, n, demod, edges);
+    const int rgb8 = A.part(3u * n, nullptr, h_out8, h_out8 != nullptr);
+    int rc = A.stage();
+    if (rc)
+      return rc;
+    const RtHipAov d = aov.device(A);
+    rc = denoise_launch(A.at<float>(rgb), &d, width, height, params, A.at<char>(ws), h_out ? A.at<float>(rgb) : nullptr,
+                        A.at<uint8_t>(rgb8), nullptr);
+    return rc ? rc : A.download();
+  });
 }
 
 /* ---- temporal reprojection (rt_hip.h, rt_hip_reproject*) ---------------------------------------------------------------------
- * One launch of pt_reproject (pt_kernel.hip), no workspace.  The arguments that need no device are checked first. */
+ * One launch of pt_reproject (image_ops.hip), no workspace.  The arguments that need no device are checked first. */
 bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
 {
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
   return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+/* The overlap rule of the image-space calls, whose lanes write their outputs while other lanes still read: output by output, in
+ * the order given, first against every input (`in_text`), then against the outputs after it (`out_text`; null: they are not
+ * compared).  One pair may be in place -- outs[place_out] and ins[place_in] at the SAME address, where a lane reads its own
+ * element before it writes it; -1: none.  A null span is absent and overlaps nothing. */
+struct Span
+{
+  const void *ptr;
+  size_t bytes;
+};
+
+template <size_t N_OUT, size_t N_IN>
+int check_overlap(const Span (&outs)[N_OUT], const Span (&ins)[N_IN], int place_out, int place_in, const char *in_text, const char *out_text)
+{
+  for (size_t o = 0; o < N_OUT; o++)
+  {
+    for (size_t i = 0; i < N_IN; i++)
+      if (!((int)o == place_out && (int)i == place_in && outs[o].ptr == ins[i].ptr) &&
+          ranges_overlap(outs[o].ptr, outs[o].bytes, ins[i].ptr, ins[i].bytes))
+        return fail(RT_HIP_EINVAL, "%s", in_text);
+    for (size_t q = o + 1; out_text && q < N_OUT; q++)
+      if (ranges_overlap(outs[o].ptr, outs[o].bytes, outs[q].ptr, outs[q].bytes))
+        return fail(RT_HIP_EINVAL, "%s", out_text);
+  }
+  return RT_HIP_OK;
 }
 
 int check_reproject(const float *rgb, const RtHipAov *aov, const RtHipCamera *camera, const float *hist_rgb, const float *hist_len,
@@ -2554,28 +2658,16 @@ int check_reproject(const float *rgb, const RtHipAov *aov, const RtHipCamera *ca
   /* a lane writes its pixel's outputs while other lanes still read: no output may overlap what the call reads (the history, the
    * frame's buffers) or another output; only out_rgb == rgb, where a lane reads its own pixel before it writes it, is in place */
   const size_t n = (size_t)width * (size_t)height;
-  const std::pair<const void *, size_t> outs[4] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_len, 4u * n}, {out_motion, 8u * n}};
-  const std::pair<const void *, size_t> frame[5] = {{rgb, 12u * n}, {aov->normal, 12u * n}, {aov->depth, 4u * n}, {aov->hits, 4u * n},
-                                                    {aov->object, 4u * n}};
-  for (int o = 0; o < 4; o++)
-  {
-    for (int f = 0; f < 5; f++)
-      if (!(o == 0 && f == 0 && out_rgb == rgb) && ranges_overlap(outs[o].first, outs[o].second, frame[f].first, frame[f].second))
-        return fail(RT_HIP_EINVAL, "an output overlaps a buffer of the frame (only out_rgb == rgb is allowed)");
-    for (int q = o + 1; q < 4; q++)
-      if (ranges_overlap(outs[o].first, outs[o].second, outs[q].first, outs[q].second))
-        return fail(RT_HIP_EINVAL, "two outputs overlap");
-  }
-  if (any_hist)
-  {
-    const std::pair<const void *, size_t> hist[6] = {{hist_rgb, 12u * n},        {hist_len, 4u * n},         {hist_aov->normal, 12u * n},
-                                                     {hist_aov->depth, 4u * n}, {hist_aov->hits, 4u * n}, {hist_aov->object, 4u * n}};
-    for (const auto &o : outs)
-      for (const auto &h : hist)
-        if (ranges_overlap(o.first, o.second, h.first, h.second))
-          return fail(RT_HIP_EINVAL, "an output aliases a history buffer");
-  }
-  return RT_HIP_OK;
+  const Span outs[4] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_len, 4u * n}, {out_motion, 8u * n}};
+  const Span frame[5] = {{rgb, 12u * n}, {aov->normal, 12u * n}, {aov->depth, 4u * n}, {aov->hits, 4u * n}, {aov->object, 4u * n}};
+  if (const int rc = check_overlap(outs, frame, 0, 0, "an output overlaps a buffer of the frame (only out_rgb == rgb is allowed)",
+                                   "two outputs overlap"))
+    return rc;
+  if (!any_hist)
+    return RT_HIP_OK;
+  const Span hist[6] = {{hist_rgb, 12u * n},        {hist_len, 4u * n},       {hist_aov->normal, 12u * n},
+                        {hist_aov->depth, 4u * n}, {hist_aov->hits, 4u * n}, {hist_aov->object, 4u * n}};
+  return check_overlap(outs, hist, -1, -1, "an output aliases a history buffer", nullptr);
 }
 
 void camera_of(const RtHipCamera *c, PtCamera &out)
@@ -2632,11 +2724,9 @@ int check_reproject_points(const double *prev_points, int32_t width, int32_t hei
                            const float *out_len, const float *out_motion)
 {
   const size_t n = (size_t)width * (size_t)height;
-  const std::pair<const void *, size_t> outs[4] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_len, 4u * n}, {out_motion, 8u * n}};
-  for (const auto &o : outs)
-    if (ranges_overlap(o.first, o.second, prev_points, 24u * n))
-      return fail(RT_HIP_EINVAL, "an output overlaps the previous points");
-  return RT_HIP_OK;
+  const Span outs[4] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_len, 4u * n}, {out_motion, 8u * n}};
+  const Span points[1] = {{prev_points, 24u * n}};
+  return check_overlap(outs, points, -1, -1, "an output overlaps the previous points", nullptr);
 }
 
 int reproject_image_impl(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
@@ -2650,49 +2740,49 @@ int reproject_image_impl(const float *h_rgb, const RtHipAov *h_aov, const RtHipC
     rc = check_reproject_points(h_prev_points, width, height, h_out_rgb, h_out_rgb8, h_out_len, h_out_motion);
   if (rc)
     return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  const size_t n = (size_t)width * (size_t)height;
-  const bool hist = h_hist_rgb != nullptr;
-  /* per image -- the frame, then the history if there is one -- colour, normal, depth, hits, object and length: the frame's colour
-   * and length are the outputs (the colour in place); then motion and bytes */
-  const RtHipAov none = {};
-  const float *src_rgb[2] = {h_rgb, h_hist_rgb};
-  const RtHipAov *src_aov[2] = {h_aov, hist ? h_hist_aov : &none};
-  StageArena A;
-  int rgb[2], normal[2], depth[2], hits[2], object[2], len[2];
-  for (int f = 0; f < 2; f++)
-  {
-    const bool have = f == 0 || hist;
-    rgb[f] = A.part(12u * n, src_rgb[f], f == 0 ? h_out_rgb : nullptr, have);
-    normal[f] = A.part(12u * n, src_aov[f]->normal, nullptr, have);
-    depth[f] = A.part(4u * n, src_aov[f]->depth, nullptr, have);
-    hits[f] = A.part(4u * n, src_aov[f]->hits, nullptr, have);
-    object[f] = A.part(4u * n, src_aov[f]->object, nullptr, have);
-    len[f] = A.part(4u * n, f == 0 ? nullptr : h_hist_len, f == 0 ? h_out_len : nullptr, have);
-  }
-  const int motion = A.part(8u * n, nullptr, h_out_motion, h_out_motion != nullptr);
-  const int rgb8 = A.part(3u * n, nullptr, h_out_rgb8, h_out_rgb8 != nullptr);
-  const int points = A.part(24u * n, h_prev_points, nullptr, h_prev_points != nullptr);
-  rc = A.stage();
-  if (rc)
-    return rc;
-  RtHipAov d_aov[2];
-  for (int f = 0; f < 2; f++)
-    d_aov[f] = {nullptr, A.at<float>(normal[f]), A.at<float>(depth[f]), A.at<uint32_t>(object[f]), A.at<uint32_t>(hits[f])};
-  rc = reproject_launch(A.at<float>(rgb[0]), &d_aov[0], camera, A.at<float>(rgb[1]), A.at<float>(len[1]), hist ? &d_aov[1] : nullptr,
-                        hist_camera, width, height, params, A.at<double>(points), A.at<float>(rgb[0]), A.at<uint8_t>(rgb8),
-                        A.at<float>(len[0]), A.at<float>(motion), nullptr);
-  return rc ? rc : A.download();
+  return on_logical_device(device, [&](int) {
+    const size_t n = (size_t)width * (size_t)height;
+    const bool hist = h_hist_rgb != nullptr;
+    /* per image -- the frame, then the history if there is one -- colour, normal, depth, hits, object and length: the frame's
+     * colour and length are the outputs (the colour in place); then motion and bytes */
+    const RtHipAov none = {};
+    StageArena A;
+    const int rgb = A.part(12u * n, h_rgb, h_out_rgb);
+    const AovStage aov(A, h_aov, n, false, true);
+    const int len = A.part(4u * n, nullptr, h_out_len);
+    const int hist_rgb = A.part(12u * n, h_hist_rgb, nullptr, hist);
+    const AovStage hist_aov(A, hist ? h_hist_aov : &none, n, false, true, hist);
+    const int hist_len = A.part(4u * n, h_hist_len, nullptr, hist);
+    const int motion = A.part(8u * n, nullptr, h_out_motion, h_out_motion != nullptr);
+    const int rgb8 = A.part(3u * n, nullptr, h_out_rgb8, h_out_rgb8 != nullptr);
+    const int points = A.part(24u * n, h_prev_points, nullptr, h_prev_points != nullptr);
+    int rc = A.stage();
+    if (rc)
+      return rc;
+    const RtHipAov d_aov = aov.device(A), d_hist_aov = hist_aov.device(A);
+    rc = reproject_launch(A.at<float>(rgb), &d_aov, camera, A.at<float>(hist_rgb), A.at<float>(hist_len), hist ? &d_hist_aov : nullptr,
+                          hist_camera, width, height, params, A.at<double>(points), A.at<float>(rgb), A.at<uint8_t>(rgb8),
+                          A.at<float>(len), A.at<float>(motion), nullptr);
+    return rc ? rc : A.download();
+  });
 }
 
-/* ---- previous points (rt_hip.h, rt_hip_prev_points*) ---------------------------------------------------------------------------
- * One launch of pt_prev_points (pt_kernel.hip), no workspace.  The arguments that need no device are checked first. */
-int check_prev_points(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, const double *points)
+/* ---- previous points (rt_hip.h, rt_hip_prev_points*, rt_hip_prev_points_moved*) ------------------------------------------------
+ * One launch of pt_prev_points, or of pt_prev_points_moved for a call that takes spheres (image_ops.hip), no workspace.  One path
+ * for both: `spheres` is null for rt_hip_prev_points and the call's sphere arguments for rt_hip_prev_points_moved.  The arguments
+ * that need no device are checked first: the common ones, then the spheres' -- object is required, and both sphere arrays with a
+ * non-zero count. */
+struct MovedSpheres
+{
+  const double *prev, *cur; /* 4 doubles per sphere; null with n == 0 */
+  size_t n;
+  bool none_given; /* no previous spheres and n == 0: no sphere moved (PtPrevPointsMoved.spheres_static) -- by the CALL's pointers */
+};
+
+MovedSpheres moved_spheres(const double *prev, const double *cur, size_t n) { return {prev, cur, n, !prev && n == 0}; }
+
+int check_prev_points(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, const MovedSpheres *spheres,
+                      const double *points)
 {
   if (n >= (1ull << 32))
     return fail(RT_HIP_EINVAL, "n must be below 2^32");
@@ -2706,144 +2796,94 @@ int check_prev_points(const RtHipHits *hits, uint64_t n, const double *positions
     return fail(RT_HIP_EINVAL, "the output points are required");
   /* a lane writes its entry while other lanes still read: the output overlaps no input, but for out == point, where a lane reads
    * its own point before it writes it */
-  const std::pair<const void *, size_t> in[5] = {{hits->status, 4u * n}, {hits->prim, 4u * n}, {hits->bary, 16u * n},
-                                                 {hits->point, 24u * n}, {n_triangles ? positions : nullptr, 72u * n_triangles}};
-  for (int k = 0; k < 5; k++)
-    if (!(k == 3 && points == hits->point) && ranges_overlap(points, 24u * n, in[k].first, in[k].second))
-      return fail(RT_HIP_EINVAL, "the output overlaps an input (only d_points == d_hits->point is allowed)");
-  return RT_HIP_OK;
+  const char *text = "the output overlaps an input (only d_points == d_hits->point is allowed)";
+  const Span out[1] = {{points, 24u * n}};
+  const Span in[5] = {{hits->status, 4u * n}, {hits->prim, 4u * n}, {hits->bary, 16u * n}, {hits->point, 24u * n},
+                      {n_triangles ? positions : nullptr, 72u * n_triangles}};
+  if (const int rc = check_overlap(out, in, 0, 3, text, nullptr))
+    return rc;
+  if (!spheres)
+    return RT_HIP_OK;
+  if (!hits->object)
+    return fail(RT_HIP_EINVAL, "the hits' object is required");
+  if (spheres->n > SIZE_MAX / 32u)
+    return fail(RT_HIP_EINVAL, "n_spheres is out of range");
+  if (spheres->n && (!spheres->prev || !spheres->cur))
+    return fail(RT_HIP_EINVAL, "the previous and the current spheres are required (4 doubles per sphere)");
+  const Span moved[3] = {{hits->object, 4u * n}, {spheres->n ? spheres->prev : nullptr, 32u * spheres->n},
+                         {spheres->n ? spheres->cur : nullptr, 32u * spheres->n}};
+  return check_overlap(out, moved, -1, -1, text, nullptr);
 }
 
 /* the launch of a checked call, on the current device */
-int prev_points_launch(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, double *points, hipStream_t stream)
+int prev_points_launch(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, const MovedSpheres *spheres,
+                       double *points, hipStream_t stream)
 {
   if (n == 0)
     return RT_HIP_OK;
-  PtPrevPoints A = {};
-  A.status = hits->status;
-  A.prim = hits->prim;
-  A.bary = hits->bary;
-  A.point = hits->point;
-  A.positions = positions;
-  A.out = points;
-  A.n = n;
-  A.n_triangles = n_triangles;
-  const hipError_t e = pt_launch_prev_points(A, stream);
+  hipError_t e;
+  if (spheres)
+  {
+    const PtPrevPointsMoved A = {.status = hits->status, .prim = hits->prim, .object = hits->object, .bary = hits->bary, .point = hits->point,
+                                 .positions = positions, .spheres_prev = spheres->prev, .spheres_cur = spheres->cur, .out = points, .n = n,
+                                 .n_triangles = n_triangles, .n_spheres = spheres->n, .spheres_static = spheres->none_given ? 1u : 0u};
+    e = pt_launch_prev_points_moved(A, stream);
+  }
+  else
+  {
+    const PtPrevPoints A = {.status = hits->status, .prim = hits->prim, .bary = hits->bary, .point = hits->point, .positions = positions,
+                            .out = points, .n = n, .n_triangles = n_triangles};
+    e = pt_launch_prev_points(A, stream);
+  }
   if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_prev_points launch: %s", hipGetErrorString(e));
+    return fail(RT_HIP_ERUNTIME, "%s launch: %s", spheres ? "pt_prev_points_moved" : "pt_prev_points", hipGetErrorString(e));
   return RT_HIP_OK;
 }
 
-int prev_points_host_impl(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles, int device, double *h_points)
+/* the device-pointer form: no entry returns before a device is looked for */
+int prev_points_device(const RtHipHits *d_hits, uint64_t n, const double *d_positions, size_t n_triangles, const MovedSpheres *spheres,
+                       double *d_points, void *stream)
 {
-  int rc = check_prev_points(h_hits, n, h_positions, n_triangles, h_points);
-  if (rc)
+  const int rc = check_prev_points(d_hits, n, d_positions, n_triangles, spheres, d_points);
+  if (rc || n == 0)
     return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  if (n == 0)
-    return RT_HIP_OK;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  /* the point part is input and output: the kernel runs in place on it */
-  StageArena A;
-  const int status = A.part(4u * n, h_hits->status);
-  const int prim = A.part(4u * n, h_hits->prim);
-  const int bary = A.part(16u * n, h_hits->bary);
-  const int point = A.part(24u * n, h_hits->point, h_points);
-  const int positions = A.part(72u * n_triangles, h_positions, nullptr, n_triangles != 0);
-  rc = A.stage();
-  if (rc)
-    return rc;
-  const RtHipHits d = {A.at<uint32_t>(status), nullptr, nullptr, A.at<uint32_t>(prim), A.at<double>(point), nullptr, A.at<double>(bary), nullptr};
-  rc = prev_points_launch(&d, n, A.at<double>(positions), n_triangles, A.at<double>(point), nullptr);
-  return rc ? rc : A.download();
+  return on_device_of(d_points, "d_points", [&] {
+    return prev_points_launch(d_hits, n, d_positions, n_triangles, spheres, d_points, static_cast<hipStream_t>(stream));
+  });
 }
 
-/* ---- previous points with moved spheres (rt_hip.h, rt_hip_prev_points_moved*) ------------------------------------------------
- * rt_hip_prev_points' checks, then the spheres': object is required, and both sphere arrays with a non-zero count.  One launch of
- * pt_prev_points_moved (pt_kernel.hip), no workspace. */
-int check_prev_points_moved(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, const double *spheres_prev,
-                            const double *spheres_cur, size_t n_spheres, const double *points)
+/* the host-array form: the logical device is looked up before no entry returns */
+int prev_points_host_impl(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles, const MovedSpheres *spheres,
+                          int device, double *h_points)
 {
-  const int rc = check_prev_points(hits, n, positions, n_triangles, points);
-  if (rc)
+  if (const int rc = check_prev_points(h_hits, n, h_positions, n_triangles, spheres, h_points))
     return rc;
-  if (!hits->object)
-    return fail(RT_HIP_EINVAL, "the hits' object is required");
-  if (n_spheres > SIZE_MAX / 32u)
-    return fail(RT_HIP_EINVAL, "n_spheres is out of range");
-  if (n_spheres && (!spheres_prev || !spheres_cur))
-    return fail(RT_HIP_EINVAL, "the previous and the current spheres are required (4 doubles per sphere)");
-  const std::pair<const void *, size_t> in[3] = {{hits->object, 4u * n}, {n_spheres ? spheres_prev : nullptr, 32u * n_spheres},
-                                                 {n_spheres ? spheres_cur : nullptr, 32u * n_spheres}};
-  for (int k = 0; k < 3; k++)
-    if (ranges_overlap(points, 24u * n, in[k].first, in[k].second))
-      return fail(RT_HIP_EINVAL, "the output overlaps an input (only d_points == d_hits->point is allowed)");
-  return RT_HIP_OK;
-}
-
-int prev_points_moved_launch(const RtHipHits *hits, uint64_t n, const double *positions, size_t n_triangles, const double *spheres_prev,
-                             const double *spheres_cur, size_t n_spheres, bool spheres_static, double *points, hipStream_t stream)
-{
-  if (n == 0)
-    return RT_HIP_OK;
-  PtPrevPointsMoved A = {};
-  A.status = hits->status;
-  A.prim = hits->prim;
-  A.object = hits->object;
-  A.bary = hits->bary;
-  A.point = hits->point;
-  A.positions = positions;
-  A.spheres_prev = spheres_prev;
-  A.spheres_cur = spheres_cur;
-  A.out = points;
-  A.n = n;
-  A.n_triangles = n_triangles;
-  A.n_spheres = n_spheres;
-  A.spheres_static = spheres_static ? 1u : 0u; /* d_spheres_prev == NULL with n_spheres == 0: rt_hip_prev_points itself */
-  const hipError_t e = pt_launch_prev_points_moved(A, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_prev_points_moved launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
-}
-
-int prev_points_moved_host_impl(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles,
-                                const double *h_spheres_prev, const double *h_spheres_cur, size_t n_spheres, int device, double *h_points)
-{
-  int rc = check_prev_points_moved(h_hits, n, h_positions, n_triangles, h_spheres_prev, h_spheres_cur, n_spheres, h_points);
-  if (rc)
-    return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  if (n == 0)
-    return RT_HIP_OK;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  StageArena A;
-  const int status = A.part(4u * n, h_hits->status);
-  const int prim = A.part(4u * n, h_hits->prim);
-  const int object = A.part(4u * n, h_hits->object);
-  const int bary = A.part(16u * n, h_hits->bary);
-  const int point = A.part(24u * n, h_hits->point, h_points);
-  const int positions = A.part(72u * n_triangles, h_positions, nullptr, n_triangles != 0);
-  const int sprev = A.part(32u * n_spheres, h_spheres_prev, nullptr, n_spheres != 0);
-  const int scur = A.part(32u * n_spheres, h_spheres_cur, nullptr, n_spheres != 0);
-  rc = A.stage();
-  if (rc)
-    return rc;
-  const RtHipHits d = {A.at<uint32_t>(status), nullptr, A.at<uint32_t>(object), A.at<uint32_t>(prim), A.at<double>(point), nullptr, A.at<double>(bary), nullptr};
-  rc = prev_points_moved_launch(&d, n, A.at<double>(positions), n_triangles, A.at<double>(sprev), A.at<double>(scur), n_spheres,
-                                !h_spheres_prev && n_spheres == 0, A.at<double>(point), nullptr);
-  return rc ? rc : A.download();
+  return on_logical_device(device, [&](int) -> int {
+    if (n == 0)
+      return RT_HIP_OK;
+    /* the point part is input and output: the kernel runs in place on it */
+    const size_t n_spheres = spheres ? spheres->n : 0;
+    StageArena A;
+    const int status = A.part(4u * n, h_hits->status);
+    const int prim = A.part(4u * n, h_hits->prim);
+    const int object = A.part(4u * n, h_hits->object, nullptr, spheres != nullptr);
+    const int bary = A.part(16u * n, h_hits->bary);
+    const int point = A.part(24u * n, h_hits->point, h_points);
+    const int positions = A.part(72u * n_triangles, h_positions, nullptr, n_triangles != 0);
+    const int sprev = A.part(32u * n_spheres, spheres ? spheres->prev : nullptr, nullptr, n_spheres != 0);
+    const int scur = A.part(32u * n_spheres, spheres ? spheres->cur : nullptr, nullptr, n_spheres != 0);
+    int rc = A.stage();
+    if (rc)
+      return rc;
+    const RtHipHits d = {A.at<uint32_t>(status), nullptr, A.at<uint32_t>(object), A.at<uint32_t>(prim), A.at<double>(point), nullptr, A.at<double>(bary), nullptr};
+    const MovedSpheres d_spheres = {A.at<double>(sprev), A.at<double>(scur), n_spheres, spheres && spheres->none_given};
+    rc = prev_points_launch(&d, n, A.at<double>(positions), n_triangles, spheres ? &d_spheres : nullptr, A.at<double>(point), nullptr);
+    return rc ? rc : A.download();
+  });
 }
 
 /* ---- guided upsampling (rt_hip.h, rt_hip_upsample*) ---------------------------------------------------------------------------
- * One launch of pt_upsample (pt_kernel.hip), no workspace.  The arguments that need no device are checked first. */
+ * One launch of pt_upsample (image_ops.hip), no workspace.  The arguments that need no device are checked first. */
 int check_upsample(const float *low_rgb, const RtHipAov *low_aov, int32_t low_width, int32_t low_height, const RtHipAov *aov,
                    int32_t width, int32_t height, const RtHipUpsampleParams *p, const float *out_rgb, const uint8_t *out_rgb8,
                    const float *out_conf)
@@ -2874,28 +2914,19 @@ int check_upsample(const float *low_rgb, const RtHipAov *low_aov, int32_t low_wi
     return fail(RT_HIP_EINVAL, "out_rgb is required");
   /* a lane writes its pixel while other lanes still read the low frame: no output may overlap what the call reads or another output */
   const size_t n = (size_t)width * (size_t)height, nl = (size_t)low_width * (size_t)low_height;
-  const std::pair<const void *, size_t> outs[3] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_conf, 4u * n}};
-  const std::pair<const void *, size_t> ins[11] = {{low_rgb, 12u * nl},
-                                                   {demod ? low_aov->albedo : nullptr, 12u * nl},
-                                                   {low_aov->normal, 12u * nl},
-                                                   {low_aov->depth, 4u * nl},
-                                                   {low_aov->hits, 4u * nl},
-                                                   {edges ? low_aov->object : nullptr, 4u * nl},
-                                                   {demod ? aov->albedo : nullptr, 12u * n},
-                                                   {aov->normal, 12u * n},
-                                                   {aov->depth, 4u * n},
-                                                   {aov->hits, 4u * n},
-                                                   {edges ? aov->object : nullptr, 4u * n}};
-  for (int o = 0; o < 3; o++)
-  {
-    for (const auto &in : ins)
-      if (ranges_overlap(outs[o].first, outs[o].second, in.first, in.second))
-        return fail(RT_HIP_EINVAL, "an output overlaps an input");
-    for (int q = o + 1; q < 3; q++)
-      if (ranges_overlap(outs[o].first, outs[o].second, outs[q].first, outs[q].second))
-        return fail(RT_HIP_EINVAL, "two outputs overlap");
-  }
-  return RT_HIP_OK;
+  const Span outs[3] = {{out_rgb, 12u * n}, {out_rgb8, 3u * n}, {out_conf, 4u * n}};
+  const Span ins[11] = {{low_rgb, 12u * nl},
+                        {demod ? low_aov->albedo : nullptr, 12u * nl},
+                        {low_aov->normal, 12u * nl},
+                        {low_aov->depth, 4u * nl},
+                        {low_aov->hits, 4u * nl},
+                        {edges ? low_aov->object : nullptr, 4u * nl},
+                        {demod ? aov->albedo : nullptr, 12u * n},
+                        {aov->normal, 12u * n},
+                        {aov->depth, 4u * n},
+                        {aov->hits, 4u * n},
+                        {edges ? aov->object : nullptr, 4u * n}};
+  return check_overlap(outs, ins, -1, -1, "an output overlaps an input", "two outputs overlap");
 }
 
 /* the launch of a checked call, on the current device */
@@ -2936,43 +2967,26 @@ int upsample_image_impl(const float *h_low_rgb, const RtHipAov *h_low_aov, int32
                         int32_t width, int32_t height, const RtHipUpsampleParams *params, int device, float *h_out_rgb,
                         uint8_t *h_out_rgb8, float *h_out_conf)
 {
-  int rc = check_upsample(h_low_rgb, h_low_aov, low_width, low_height, h_aov, width, height, params, h_out_rgb, h_out_rgb8, h_out_conf);
-  if (rc)
+  if (const int rc = check_upsample(h_low_rgb, h_low_aov, low_width, low_height, h_aov, width, height, params, h_out_rgb, h_out_rgb8, h_out_conf))
     return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  const bool demod = (params->flags & RT_HIP_UPSAMPLE_DEMODULATE) != 0u, edges = (params->flags & RT_HIP_UPSAMPLE_OBJECT_EDGES) != 0u;
-  const size_t count[2] = {(size_t)low_width * (size_t)low_height, (size_t)width * (size_t)height};
-  /* per frame -- low, then full -- the buffers the flags ask for; then the low colour, the result, the confidence, the bytes */
-  const RtHipAov *src[2] = {h_low_aov, h_aov};
-  StageArena A;
-  int albedo[2], normal[2], depth[2], hits[2], object[2];
-  for (int f = 0; f < 2; f++)
-  {
-    const size_t n = count[f];
-    albedo[f] = A.part(12u * n, src[f]->albedo, nullptr, demod);
-    normal[f] = A.part(12u * n, src[f]->normal);
-    depth[f] = A.part(4u * n, src[f]->depth);
-    hits[f] = A.part(4u * n, src[f]->hits);
-    object[f] = A.part(4u * n, src[f]->object, nullptr, edges);
-  }
-  const int low_rgb = A.part(12u * count[0], h_low_rgb);
-  const int out = A.part(12u * count[1], nullptr, h_out_rgb);
-  const int conf = A.part(4u * count[1], nullptr, h_out_conf, h_out_conf != nullptr);
-  const int rgb8 = A.part(3u * count[1], nullptr, h_out_rgb8, h_out_rgb8 != nullptr);
-  rc = A.stage();
-  if (rc)
-    return rc;
-  RtHipAov d_aov[2];
-  for (int f = 0; f < 2; f++)
-    d_aov[f] = {A.at<float>(albedo[f]), A.at<float>(normal[f]), A.at<float>(depth[f]), A.at<uint32_t>(object[f]), A.at<uint32_t>(hits[f])};
-  rc = upsample_launch(A.at<float>(low_rgb), &d_aov[0], low_width, low_height, &d_aov[1], width, height, params, A.at<float>(out),
-                       A.at<uint8_t>(rgb8), A.at<float>(conf), nullptr);
-  return rc ? rc : A.download();
+  return on_logical_device(device, [&](int) {
+    const bool demod = (params->flags & RT_HIP_UPSAMPLE_DEMODULATE) != 0u, edges = (params->flags & RT_HIP_UPSAMPLE_OBJECT_EDGES) != 0u;
+    const size_t nl = (size_t)low_width * (size_t)low_height, n = (size_t)width * (size_t)height;
+    /* per frame -- low, then full -- the buffers the flags ask for; then the low colour, the result, the confidence, the bytes */
+    StageArena A;
+    const AovStage low_aov(A, h_low_aov, nl, demod, edges), aov(A, h_aov, n, demod, edges);
+    const int low_rgb = A.part(12u * nl, h_low_rgb);
+    const int out = A.part(12u * n, nullptr, h_out_rgb);
+    const int conf = A.part(4u * n, nullptr, h_out_conf, h_out_conf != nullptr);
+    const int rgb8 = A.part(3u * n, nullptr, h_out_rgb8, h_out_rgb8 != nullptr);
+    int rc = A.stage();
+    if (rc)
+      return rc;
+    const RtHipAov d_low_aov = low_aov.device(A), d_aov = aov.device(A);
+    rc = upsample_launch(A.at<float>(low_rgb), &d_low_aov, low_width, low_height, &d_aov, width, height, params, A.at<float>(out),
+                         A.at<uint8_t>(rgb8), A.at<float>(conf), nullptr);
+    return rc ? rc : A.download();
+  });
 }
 
 /* ---- ray queries (rt_hip.h, rt_hip_query_*) ---------------------------------------------------------------------------------
@@ -3188,35 +3202,6 @@ int trace_launch(const RtHipScene *scene, const double *d_rays, uint64_t n, cons
   const int which = pt_trace_pick(scene->view);
   return pooled_launch(scene, L, stream, pt_trace_kernel_name_of(which), [&] { return pt_launch_trace(L, T, stream, which); });
 }
-
-/* The parts of a radiance query's or a pixel refinement's host form behind its input: the requested outputs, then the counters,
- * cleared.  The device's RtHipRadiance once the arena is staged, and the counters added to the caller's after the download. */
-struct RadianceStage
-{
-  int out[6], stats;
-  uint64_t st[RT_HIP_NSTATS];
-  uint64_t *h_stats;
-  RadianceStage(const RadianceStage &) = delete; /* (the plan points into st) */
-  RadianceStage(StageArena &A, const RtHipRadiance *h, uint64_t n, int32_t samples, uint64_t *h_stats_) : h_stats(h_stats_)
-  {
-    void *host[6] = {h->status, h->radiance, h->samples, h->paths, h->casts, h->ray};
-    const size_t bytes_per_entry[6] = {4, 24, 24u * (size_t)samples, 8, 8, 48};
-    for (int k = 0; k < 6; k++)
-      out[k] = A.part(bytes_per_entry[k] * n, nullptr, host[k], host[k] != nullptr);
-    stats = A.zeroed(sizeof st, h_stats ? st : nullptr);
-  }
-  RtHipRadiance device(const StageArena &A) const
-  {
-    return {A.at<uint32_t>(out[0]), A.at<double>(out[1]), A.at<double>(out[2]), A.at<uint64_t>(out[3]), A.at<uint64_t>(out[4]), A.at<double>(out[5])};
-  }
-  int download(const StageArena &A) const
-  {
-    const int rc = A.download();
-    for (int k = 0; !rc && h_stats && k < RT_HIP_NSTATS; k++)
-      h_stats[k] += st[k];
-    return rc;
-  }
-};
 
 /* rt_hip_trace_rays_host: a scene of its own on the logical device, one allocation for the rays, the counters and the requested
  * outputs, the launch on the null stream, the copies.  Everything is owned by this scope. */
@@ -3461,21 +3446,6 @@ int check_select(const float *values, int32_t width, int32_t height, double lo, 
     return fail(RT_HIP_EINVAL, "d_values, d_workspace and d_count are required");
   if (capacity != 0u && !indices)
     return fail(RT_HIP_EINVAL, "d_indices is required with capacity > 0");
-  return RT_HIP_OK;
-}
-
-/* the device that holds `ptr` made current in `scope`: a host pointer would fault the kernel, so it is refused */
-int device_of(const void *ptr, const char *what, int *device)
-{
-  if (usable_devices() < 1)
-    return fail(RT_HIP_ENODEV, "no HIP device is available (this library has no CPU path)");
-  hipPointerAttribute_t attr = {};
-  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess || attr.type != hipMemoryTypeDevice)
-  {
-    (void)hipGetLastError();
-    return fail(RT_HIP_EINVAL, "%s is not device memory", what);
-  }
-  *device = attr.device;
   return RT_HIP_OK;
 }
 
@@ -4034,21 +4004,15 @@ int cost_nodes_host_impl(const double *h_nodes, size_t n_nodes, int device, doub
   *cost = 0.0;
   if (n_nodes == 0)
     return RT_HIP_OK;
-  int phys = 0;
-  {
-    const int rc = physical_device(device, &phys);
-    if (rc)
-      return rc;
-  }
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  DeviceBuffer staged;
-  const size_t bytes = n_nodes * PT_BVH_SRC_DOUBLES * 8;
-  if (staged.alloc(bytes) != hipSuccess)
-    return fail(RT_HIP_ENOMEM, "the staged nodes (%zu KB)", bytes >> 10);
-  HIP_TRY(hipMemcpy(staged.ptr, h_nodes, bytes, hipMemcpyHostToDevice));
-  HIP_TRY(scene_tree_cost(staged.at<double>(), (uint32_t)n_nodes, nullptr, cost));
-  return RT_HIP_OK;
+  return on_logical_device(device, [&](int) -> int {
+    DeviceBuffer staged;
+    const size_t bytes = n_nodes * PT_BVH_SRC_DOUBLES * 8;
+    if (staged.alloc(bytes) != hipSuccess)
+      return fail(RT_HIP_ENOMEM, "the staged nodes (%zu KB)", bytes >> 10);
+    HIP_TRY(hipMemcpy(staged.ptr, h_nodes, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(scene_tree_cost(staged.at<double>(), (uint32_t)n_nodes, nullptr, cost));
+    return RT_HIP_OK;
+  });
 }
 
 /* `w` holds table_mutex and has the scene's device current; a NULL, unusable or triangle-less scene is ruled out */
@@ -5084,18 +5048,14 @@ int rt_hip_lens_rays(const RtHipCamera *camera, const RtHipLens *lens, int32_t w
     return RT_HIP_OK;
   if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u))
     return fail(RT_HIP_EINVAL, "d_rays is required and must be 16-byte aligned");
-  int device = -1;
-  rc = device_of(d_rays, "d_rays", &device);
-  if (rc)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  PtLensRays A = lens_args(camera, lens, width, height, seed);
-  A.pixel_first = pixel_first;
-  A.n = n;
-  A.index_first = (uint32_t)((uint64_t)sample * n_pixels + pixel_first);
-  A.rays = d_rays;
-  return lens_rays_launch(A, static_cast<hipStream_t>(stream));
+  return on_device_of(d_rays, "d_rays", [&] {
+    PtLensRays A = lens_args(camera, lens, width, height, seed);
+    A.pixel_first = pixel_first;
+    A.n = n;
+    A.index_first = (uint32_t)((uint64_t)sample * n_pixels + pixel_first);
+    A.rays = d_rays;
+    return lens_rays_launch(A, static_cast<hipStream_t>(stream));
+  });
 }
 
 size_t rt_hip_lens_workspace_bytes(int32_t width, int32_t height, uint32_t slice_pixels)
@@ -5114,16 +5074,12 @@ int rt_hip_lens_resolve(const double *d_sum, int32_t width, int32_t height, int3
     return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", samples);
   if (!d_sum || (!d_rgb && !d_rgb8))
     return fail(RT_HIP_EINVAL, "d_sum and an output are required");
-  int device = -1;
-  const int rc = device_of(d_sum, "d_sum", &device);
-  if (rc)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  const hipError_t e = lens_launch_resolve(d_sum, (uint64_t)width * (uint64_t)height, samples, d_rgb, d_rgb8, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "k_lens_resolve launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return on_device_of(d_sum, "d_sum", [&]() -> int {
+    const hipError_t e = lens_launch_resolve(d_sum, (uint64_t)width * (uint64_t)height, samples, d_rgb, d_rgb8, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "k_lens_resolve launch: %s", hipGetErrorString(e));
+    return RT_HIP_OK;
+  });
 }
 
 int rt_hip_render_lens(const RtHipScene *scene, const RtHipCamera *camera, const RtHipLens *lens, const RtHipParams *params,
@@ -5258,18 +5214,13 @@ size_t rt_hip_denoise_workspace_bytes(int32_t width, int32_t height)
 int rt_hip_denoise(const float *d_rgb, const RtHipAov *d_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
                    void *d_workspace, float *d_out_rgb, uint8_t *d_out_rgb8, void *stream)
 {
-  int rc = check_denoise(d_rgb, d_aov, width, height, params, d_out_rgb, d_out_rgb8);
-  if (rc)
+  if (const int rc = check_denoise(d_rgb, d_aov, width, height, params, d_out_rgb, d_out_rgb8))
     return rc;
   if (!d_workspace)
     return fail(RT_HIP_EINVAL, "d_workspace is required (rt_hip_denoise_workspace_bytes)");
-  int device = -1;
-  rc = device_of(d_rgb, "d_rgb", &device);
-  if (rc)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  return denoise_launch(d_rgb, d_aov, width, height, params, d_workspace, d_out_rgb, d_out_rgb8, static_cast<hipStream_t>(stream));
+  return on_device_of(d_rgb, "d_rgb", [&] {
+    return denoise_launch(d_rgb, d_aov, width, height, params, d_workspace, d_out_rgb, d_out_rgb8, static_cast<hipStream_t>(stream));
+  });
 }
 
 int rt_hip_denoise_image(const float *h_rgb, const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
@@ -5310,14 +5261,10 @@ int rt_hip_reproject_points(const float *d_rgb, const RtHipAov *d_aov, const RtH
     rc = check_reproject_points(d_prev_points, width, height, d_out_rgb, d_out_rgb8, d_out_len, d_out_motion);
   if (rc)
     return rc;
-  int device = -1;
-  rc = device_of(d_rgb, "d_rgb", &device);
-  if (rc)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  return reproject_launch(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, d_prev_points,
-                          d_out_rgb, d_out_rgb8, d_out_len, d_out_motion, static_cast<hipStream_t>(stream));
+  return on_device_of(d_rgb, "d_rgb", [&] {
+    return reproject_launch(d_rgb, d_aov, camera, d_hist_rgb, d_hist_len, d_hist_aov, hist_camera, width, height, params, d_prev_points,
+                            d_out_rgb, d_out_rgb8, d_out_len, d_out_motion, static_cast<hipStream_t>(stream));
+  });
 }
 
 int rt_hip_reproject_image(const float *h_rgb, const RtHipAov *h_aov, const RtHipCamera *camera, const float *h_hist_rgb,
@@ -5344,45 +5291,28 @@ int rt_hip_reproject_points_image(const float *h_rgb, const RtHipAov *h_aov, con
 
 int rt_hip_prev_points(const RtHipHits *d_hits, uint64_t n, const double *d_positions, size_t n_triangles, double *d_points, void *stream)
 {
-  int rc = check_prev_points(d_hits, n, d_positions, n_triangles, d_points);
-  if (rc || n == 0)
-    return rc;
-  int device = -1;
-  rc = device_of(d_points, "d_points", &device);
-  if (rc)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  return prev_points_launch(d_hits, n, d_positions, n_triangles, d_points, static_cast<hipStream_t>(stream));
+  return prev_points_device(d_hits, n, d_positions, n_triangles, nullptr, d_points, stream);
 }
 
 int rt_hip_prev_points_host(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles, int device, double *h_points)
 {
-  return guarded("rt_hip_prev_points_host", [&] { return prev_points_host_impl(h_hits, n, h_positions, n_triangles, device, h_points); });
+  return guarded("rt_hip_prev_points_host",
+                 [&] { return prev_points_host_impl(h_hits, n, h_positions, n_triangles, nullptr, device, h_points); });
 }
 
 int rt_hip_prev_points_moved(const RtHipHits *d_hits, uint64_t n, const double *d_positions, size_t n_triangles, const double *d_spheres_prev,
                              const double *d_spheres_cur, size_t n_spheres, double *d_points, void *stream)
 {
-  int rc = check_prev_points_moved(d_hits, n, d_positions, n_triangles, d_spheres_prev, d_spheres_cur, n_spheres, d_points);
-  if (rc || n == 0)
-    return rc;
-  int device = -1;
-  rc = device_of(d_points, "d_points", &device);
-  if (rc)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  return prev_points_moved_launch(d_hits, n, d_positions, n_triangles, d_spheres_prev, d_spheres_cur, n_spheres,
-                                  !d_spheres_prev && n_spheres == 0, d_points, static_cast<hipStream_t>(stream));
+  const MovedSpheres spheres = moved_spheres(d_spheres_prev, d_spheres_cur, n_spheres);
+  return prev_points_device(d_hits, n, d_positions, n_triangles, &spheres, d_points, stream);
 }
 
 int rt_hip_prev_points_moved_host(const RtHipHits *h_hits, uint64_t n, const double *h_positions, size_t n_triangles,
                                   const double *h_spheres_prev, const double *h_spheres_cur, size_t n_spheres, int device, double *h_points)
 {
-  return guarded("rt_hip_prev_points_moved_host", [&] {
-    return prev_points_moved_host_impl(h_hits, n, h_positions, n_triangles, h_spheres_prev, h_spheres_cur, n_spheres, device, h_points);
-  });
+  const MovedSpheres spheres = moved_spheres(h_spheres_prev, h_spheres_cur, n_spheres);
+  return guarded("rt_hip_prev_points_moved_host",
+                 [&] { return prev_points_host_impl(h_hits, n, h_positions, n_triangles, &spheres, device, h_points); });
 }
 
 /* k: the denoiser's; sigma_depth: the reprojection's depth tolerance (DESIGN, "`pt_upsample`") */
@@ -5400,17 +5330,12 @@ int rt_hip_upsample(const float *d_low_rgb, const RtHipAov *d_low_aov, int32_t l
                     int32_t width, int32_t height, const RtHipUpsampleParams *params, float *d_out_rgb, uint8_t *d_out_rgb8,
                     float *d_out_conf, void *stream)
 {
-  int rc = check_upsample(d_low_rgb, d_low_aov, low_width, low_height, d_aov, width, height, params, d_out_rgb, d_out_rgb8, d_out_conf);
-  if (rc)
+  if (const int rc = check_upsample(d_low_rgb, d_low_aov, low_width, low_height, d_aov, width, height, params, d_out_rgb, d_out_rgb8, d_out_conf))
     return rc;
-  int device = -1;
-  rc = device_of(d_low_rgb, "d_low_rgb", &device);
-  if (rc)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  return upsample_launch(d_low_rgb, d_low_aov, low_width, low_height, d_aov, width, height, params, d_out_rgb, d_out_rgb8, d_out_conf,
-                         static_cast<hipStream_t>(stream));
+  return on_device_of(d_low_rgb, "d_low_rgb", [&] {
+    return upsample_launch(d_low_rgb, d_low_aov, low_width, low_height, d_aov, width, height, params, d_out_rgb, d_out_rgb8, d_out_conf,
+                           static_cast<hipStream_t>(stream));
+  });
 }
 
 int rt_hip_upsample_image(const float *h_low_rgb, const RtHipAov *h_low_aov, int32_t low_width, int32_t low_height,
@@ -5431,21 +5356,16 @@ size_t rt_hip_select_workspace_bytes(int32_t width, int32_t height)
 int rt_hip_select_pixels(const float *d_values, int32_t width, int32_t height, double lo, double hi, uint32_t flags, void *d_workspace,
                          uint32_t *d_indices, uint32_t capacity, uint32_t *d_count, void *stream)
 {
-  int rc = check_select(d_values, width, height, lo, hi, flags, d_workspace, d_indices, capacity, d_count);
-  if (rc)
+  if (const int rc = check_select(d_values, width, height, lo, hi, flags, d_workspace, d_indices, capacity, d_count))
     return rc;
-  int device = -1;
-  rc = device_of(d_values, "d_values", &device);
-  if (rc)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  const PtSelect A = {.values = d_values, .n = (uint64_t)width * (uint64_t)height, .lo = lo, .hi = hi,
-                      .invert = (flags & RT_HIP_SELECT_INVERT) ? 1u : 0u};
-  const hipError_t e = pt_launch_select(A, d_workspace, d_indices, capacity, d_count, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_select launches: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return on_device_of(d_values, "d_values", [&]() -> int {
+    const PtSelect A = {.values = d_values, .n = (uint64_t)width * (uint64_t)height, .lo = lo, .hi = hi,
+                        .invert = (flags & RT_HIP_SELECT_INVERT) ? 1u : 0u};
+    const hipError_t e = pt_launch_select(A, d_workspace, d_indices, capacity, d_count, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "pt_select launches: %s", hipGetErrorString(e));
+    return RT_HIP_OK;
+  });
 }
 
 void rt_hip_pixel_defaults(RtHipPixelParams *params)
@@ -5494,22 +5414,19 @@ int rt_hip_blend_pixels(const uint32_t *d_pixels, const uint32_t *d_status, cons
                         int32_t height, double new_weight, double prior_scale, const float *d_prior, float *d_rgb, uint8_t *d_rgb8,
                         float *d_weight, void *stream)
 {
-  int rc = check_blend(d_pixels, d_status, d_radiance, n, width, height, new_weight, prior_scale, d_rgb);
-  if (rc)
+  if (const int rc = check_blend(d_pixels, d_status, d_radiance, n, width, height, new_weight, prior_scale, d_rgb))
     return rc;
-  int device = -1;
-  rc = device_of(d_rgb, "d_rgb", &device);
-  if (rc || n == 0)
-    return rc;
-  DeviceScope scope(device);
-  HIP_TRY(scope.status);
-  const PtBlend B = {.pixels = d_pixels, .status = d_status, .radiance = d_radiance, .n = n,
-                     .n_pixels = (uint32_t)((uint64_t)width * (uint64_t)height), .new_weight = new_weight, .prior_scale = prior_scale,
-                     .prior = d_prior, .rgb = d_rgb, .rgb8 = d_rgb8, .weight = d_weight};
-  const hipError_t e = pt_launch_blend(B, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_blend_pixels launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return on_device_of(d_rgb, "d_rgb", [&]() -> int { /* (the device is looked up before an empty list returns) */
+    if (n == 0)
+      return RT_HIP_OK;
+    const PtBlend B = {.pixels = d_pixels, .status = d_status, .radiance = d_radiance, .n = n,
+                       .n_pixels = (uint32_t)((uint64_t)width * (uint64_t)height), .new_weight = new_weight, .prior_scale = prior_scale,
+                       .prior = d_prior, .rgb = d_rgb, .rgb8 = d_rgb8, .weight = d_weight};
+    const hipError_t e = pt_launch_blend(B, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "pt_blend_pixels launch: %s", hipGetErrorString(e));
+    return RT_HIP_OK;
+  });
 }
 
 } // extern "C"

@@ -1,4 +1,4 @@
-"""Reprojection across sphere updates on the GPU: rt_hip_prev_points_moved (pt_prev_points_moved, pt_kernel.hip) equals the numpy
+"""Reprojection across sphere updates on the GPU: rt_hip_prev_points_moved (pt_prev_points_moved, image_ops.hip) equals the numpy
 restatement of its contract (tests/prev_points_moved_expected.py) BIT FOR BIT -- on real hits of a 12-sphere + cube scene before
 and after a move, in the NULL / 0 form, which must be rt_hip_prev_points itself, and on planted entries no query returns --, in the
 device and the host form; and Temporal.frame(prev_spheres=...) does what it is for: the accumulated frame of a ball moving through

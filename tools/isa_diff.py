@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Which kernels of two device-code listings differ (tools/isa_stats.sh writes such a listing: ISA_OUT=a.s tools/isa_stats.sh).
+"""Which kernels of two device-code listings differ (tools/isa_stats.sh writes two such listings, one per
+translation unit: ISA_OUT=dir tools/isa_stats.sh -> dir/pt_kernel.s, dir/image_ops.s; compare them one at a time).
 Kernel bodies are compared line by line with block labels renumbered and comments dropped; the .amdhsa metadata is not part of a
 body.  Used to show that a change left the members of the family as they were (adaptive sampling).
 usage: python tools/isa_diff.py before.s after.s   -> one line per kernel that differs or exists on one side only; exit 1 if any
