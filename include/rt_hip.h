@@ -1119,9 +1119,18 @@ int rt_hip_selftest_intersect(int kind, const double *h_rays, const double *h_pr
 enum
 {
   RT_HIP_FAIL_ALLOC_PARK_WS = 1,
-  RT_HIP_FAIL_ALLOC_WIDE_PEND = 2
+  RT_HIP_FAIL_ALLOC_WIDE_PEND = 2,
+  RT_HIP_FAIL_ALLOC_TAIL_WS = 4 /* the mixed grid's workspace (rt_hip_mixed_grid_launches): the launch stays uniform */
 };
 void rt_hip_selftest_fail_alloc(uint32_t mask);
+
+/* How many launches of this process took the MIXED GRID: rt_hip_render_tiles (one chunk, no workspace) of many rounds of workgroups
+ * on pt_render_tiles runs the frame's last tiles as sample chunks behind the whole ones, in the same launch, so that the device
+ * stays full to the frame's end; the frame, the bytes and the counters are the uniform launch's bit for bit.  The chunked tiles'
+ * sums live in a small per-device workspace of the shim's (2 MB on an MI355X; rt_hip_release_cache() frees it).
+ * RT_HIP_GRID_UNIFORM=1 in the environment keeps every launch uniform; RT_HIP_GRID_SPLIT=<whole tiles>,<chunks> sets the split
+ * of every launch whose form takes one (tests, sweeps). */
+uint64_t rt_hip_mixed_grid_launches(void);
 
 /* How many slots per XCD the two per-device pools get on `device` (the parked-walk workspace, the pending-ray pool): CUs per
  * XCD x the most workgroups of any slot-taking kernel a CU can hold, + 25 %, rounded up to a multiple of 32. */
@@ -1172,7 +1181,8 @@ uint64_t rt_hip_cache_builds(void);
 /* What the shim holds on `device` besides scenes and frames, bytes (0: not allocated): the parked-walk workspace (scenes with a
  * mesh hierarchy; freed with the last such scene) and the pending-ray pool (two-child materials; grows to the deepest and widest
  * launch, is rebuilt to fit after 16 launches in a row needed at most a quarter of a pool above 1 GB, freed by
- * rt_hip_release_cache()).  INTEGRATION.md has the sizes. */
+ * rt_hip_release_cache()).  INTEGRATION.md has the sizes.  Two small per-device allocations are NOT reported here: the 256 B status
+ * word and the mixed grid's chunk records (rt_hip_mixed_grid_launches: one round of workgroups x 1.5 KB, 2 MB on an MI355X). */
 int rt_hip_pool_bytes(int device, size_t *park_ws_bytes, size_t *pend_pool_bytes);
 
 /* Where the host time of the last rt_hip_render_image() went, seconds: [0] context (scene compare; on a rebuild: upload,

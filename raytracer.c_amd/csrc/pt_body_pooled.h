@@ -61,9 +61,30 @@
  * body: pixel sums need a bound on a term (here: win_add, order-free without one), and the second child of a refractive hit
  * waits on a per-lane stack while paths of this body move between lanes (here: the stack is addressed by a path ID that
  * travels with the path -- PendStack, pend_id_take). */
-template <bool CHECKER, bool TRIS, bool FILT_LDS, bool GEOM_LDS, bool REFR = false>
+/* The unit of a workgroup of a MIXED member: entry j of the launch's slots, chunk `chunk` of `chunks`.  The first n_whole workgroups
+ * are whole slots; the grid's rest is the other slots x sample_chunks, chunk-major.  n_whole = 0 (every launch over a list, too) is
+ * the uniform grid by the same arithmetic.  Wave-uniform: blockIdx and launch words only. */
+struct MixedUnit
+{
+  uint32_t j, chunk, chunks;
+};
+__device__ __forceinline__ MixedUnit mixed_unit(const PtLaunch &L, const bool LIST)
+{
+  const uint32_t n_whole = LIST ? 0u : L.n_whole;
+  if (blockIdx.x < n_whole)
+    return {blockIdx.x, 0u, 1u};
+  const uint32_t r = blockIdx.x - n_whole, n_chunked = launch_slots(L, LIST) - n_whole;
+  return {n_whole + r % n_chunked, r / n_chunked, L.sample_chunks};
+}
+
+/* MIXED (pt_render_tiles): the member takes a MIXED GRID (PtLaunch.n_whole > 0) -- whole tiles first, one workgroup each, then the
+ * launch's last tiles as sample chunks, so that the workgroups the frame ends with are short ones and the device stays full to the
+ * end.  Which of the two a workgroup is follows from blockIdx alone: wave-uniform, decided in the prologue
+ * and once more at the epilogue; the trip loop does not know.  Every other member reads no new field and keeps its code. */
+template <bool CHECKER, bool TRIS, bool FILT_LDS, bool GEOM_LDS, bool REFR = false, bool MIXED = false>
 __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const bool LIST)
 {
+  static_assert(!MIXED || !REFR, "the mixed grid: fixed-point sums only");
   static_assert(!REFR || (CHECKER && FILT_LDS && (GEOM_LDS || !TRIS)), "the pooled refraction kernels: sphere scenes (staged, or streamed from memory) and small staged mesh scenes, every material");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ float out_f[PT_TILE_PIXELS * 3];
@@ -102,6 +123,9 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
       pt_phase_acc[threadIdx.x >> 6][k] = 0;
     pt_phase_last[threadIdx.x >> 6] = __builtin_amdgcn_s_memtime();
   }
+  /* RT_HIP_PHASE_WG_TIMES=1 (tools/grid_tail.py): the caller's counters hold 80 + 2 x workgroups words, and every workgroup notes
+   * when it began and ended on the device's constant 100 MHz clock */
+  const unsigned long long wg_began = wall_clock64();
 #endif
   SceneCtx S_init = stage_scene<GEOM_LDS, FILT_LDS>(L, lds);
   __shared__ double atan_tab[CHECKER ? PT_ATAN_TAB : 1];
@@ -147,7 +171,7 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
   }
   if (threadIdx.x < PT_TILE_PIXELS)
   {
-    const uint32_t t0 = L.tile_first + launch_slot(L, blockIdx.x % launch_slots(L, LIST), LIST) * L.tile_stride;
+    const uint32_t t0 = L.tile_first + launch_slot(L, MIXED ? mixed_unit(L, LIST).j : blockIdx.x % launch_slots(L, LIST), LIST) * L.tile_stride;
     const uint32_t kx = (t0 % L.tiles_x) * PT_TILE + (threadIdx.x & 7u), ky = (t0 / L.tiles_x) * PT_TILE + (threadIdx.x >> 3);
     pix_key[threadIdx.x] = rt_rng_pixel_key(L.seed, ky * (uint32_t)L.width + kx);
   }
@@ -159,8 +183,14 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
   /* ---- this wave's pixels and job pool ---- */
   const uint32_t wave = threadIdx.x >> 6;
   /* grid = tile_count x sample_chunks, chunk-major: consecutive workgroups are different
-   * tiles, so the chunks of an expensive tile are spread over the launch */
-  const uint32_t slot = launch_slot(L, blockIdx.x % launch_slots(L, LIST), LIST), chunk = blockIdx.x / launch_slots(L, LIST);
+   * tiles, so the chunks of an expensive tile are spread over the launch (MIXED: mixed_unit) */
+  /* (mixed_unit is asked at each of its five uses, inside the MIXED ternaries, on purpose.  Held once in a `const MixedUnit U` ahead
+   * of the pixel keys -- the non-MIXED members' blockIdx % and / in the same value -- it is the same arithmetic, but the compiler then
+   * keeps the quotients across the barrier and allocates the whole body anew: tools/isa_diff.py showed 34 of the 108 kernels
+   * differing, 1,600 .. 3,500 changed lines each, the trip loop among them.  As written, the other members keep the listing they
+   * had before the mixed grid and pt_render_tiles keeps its trip loop's instructions: do not fold it without that comparison.) */
+  const uint32_t slot = launch_slot(L, MIXED ? mixed_unit(L, LIST).j : blockIdx.x % launch_slots(L, LIST), LIST);
+  const uint32_t chunk = MIXED ? mixed_unit(L, LIST).chunk : blockIdx.x / launch_slots(L, LIST);
   const uint32_t tile = L.tile_first + slot * L.tile_stride;
   const bool cull_ok = S.n_sph + S.n_tri <= 64u * CULL_WORDS;
   if (mf_sized && threadIdx.x < PT_MFMA16_ROWS)
@@ -194,8 +224,8 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
   const uint32_t spp = (uint32_t)L.samples;
   /* this workgroup's share of the samples: [s_begin, s_end) of every pixel (absolute indices: a pass of an accumulation starts at
    * sample_first, 0 otherwise) */
-  const uint32_t s_begin = L.sample_first + (uint32_t)(((uint64_t)chunk * spp) / L.sample_chunks);
-  const uint32_t s_end = L.sample_first + (uint32_t)(((uint64_t)(chunk + 1u) * spp) / L.sample_chunks);
+  const uint32_t s_begin = L.sample_first + (uint32_t)(((uint64_t)chunk * spp) / (MIXED ? mixed_unit(L, LIST).chunks : L.sample_chunks));
+  const uint32_t s_end = L.sample_first + (uint32_t)(((uint64_t)(chunk + 1u) * spp) / (MIXED ? mixed_unit(L, LIST).chunks : L.sample_chunks));
   const uint32_t pool_jobs = n_valid * (s_end - s_begin); /* jobs: j -> pixel j % n_valid, sample s_begin + j / n_valid */
 
   Path P;
@@ -766,8 +796,8 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
     if (pend_ok && threadIdx.x == 0)
       atomicExch(&L.pend_flags[pend_slot], 0u); /* every lane is past its last pop (the barriers above) */
   }
-  else if (L.sample_chunks == 1 && !L.acc_keep)
-  {
+  else if (MIXED ? ((!LIST && blockIdx.x < L.n_whole) || L.sample_chunks == 1) && !L.acc_keep : L.sample_chunks == 1 && !L.acc_keep)
+  { /* (MIXED: a whole slot of a mixed grid finishes here too -- asked of blockIdx again, so that nothing lives through the loop for it) */
     finish_pixels(L, pix_sum, pix_nan, tile, out_f, out_b);
     __syncthreads();
     store_tile(L, out_f, out_b, wg_stats, tile, slot, S.n_sph + S.n_tri, true, true);
@@ -784,13 +814,22 @@ __device__ __forceinline__ void render_tiles_pooled(const PtLaunch &L, const boo
   {
     /* one of several sample chunks of this tile (or a pass of an accumulation): add the partial sums to the tile's record in
      * HBM (integer atomics: exact, order-independent); pt_resolve_tiles finishes the pixels */
+    /* (MIXED: the workspace holds the chunked slots' records alone, PtLaunch.n_whole) */
+    const uint32_t n_whole = MIXED && !LIST ? L.n_whole : 0u;
     if (threadIdx.x < PT_TILE_PIXELS * 3 && pix_sum[threadIdx.x] != 0)
-      atomicAdd(&L.acc_ws[(size_t)slot * (PT_TILE_PIXELS * 3) + threadIdx.x], pix_sum[threadIdx.x]);
+      atomicAdd(&L.acc_ws[(size_t)(slot - n_whole) * (PT_TILE_PIXELS * 3) + threadIdx.x], pix_sum[threadIdx.x]);
     /* the NaN flags follow the sums of all tiles in the workspace */
     if (threadIdx.x < 3 && pix_nan[threadIdx.x] != 0)
-      atomicOr(&L.acc_ws[(size_t)L.tile_count * (PT_TILE_PIXELS * 3) + (size_t)slot * 3 + threadIdx.x], pix_nan[threadIdx.x]);
+      atomicOr(&L.acc_ws[(size_t)(L.tile_count - n_whole) * (PT_TILE_PIXELS * 3) + (size_t)(slot - n_whole) * 3 + threadIdx.x], pix_nan[threadIdx.x]);
     store_tile(L, out_f, out_b, wg_stats, tile, slot, S.n_sph + S.n_tri, false, chunk == 0);
   }
+#ifdef PT_PHASE
+  if (threadIdx.x == 0 && L.stats && (L.diag_flags & 4u))
+  {
+    L.stats[80 + 2 * (size_t)blockIdx.x] = wg_began;
+    L.stats[81 + 2 * (size_t)blockIdx.x] = wall_clock64();
+  }
+#endif
 }
 
 #endif /* PT_BODY_POOLED_H */

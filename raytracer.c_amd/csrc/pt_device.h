@@ -402,7 +402,7 @@ struct PtLaunch
   double near_R2, w_minus_1, h_minus_1;
   double filt_shift; /* 12 e (max |c| + near_R): how far behind the origin the sign-test filter starts its ray */
   double hull_margin; /* a ray leaves a hull facet for good if (outward normal) . d exceeds this (rt_hip_shim.hip) */
-  uint32_t diag_flags; /* PT_DIAG builds only: bit 0 = walk the rays the probe's bounding sphere rejects, to check them; bit 1 = the counters have 64 words (retry-stack counts, slots 44..48) */
+  uint32_t diag_flags; /* PT_DIAG builds: bit 0 = walk the rays the probe's bounding sphere rejects, to check them; bit 1 = the counters have 64 words (retry-stack counts, slots 44..48).  PT_PHASE builds: bit 2 = the counters hold 80 + 2 x workgroups words and every workgroup of the pooled kernels notes when it began and ended (tools/grid_tail.py) */
   float mesh_bound[5]; /* bvh_probe: the triangles' bounding sphere for this near_R: cx cy cz r2_hi neg_tol (pt_intersect.h, MeshBound) */
   /* two constants passed in so that they live in SGPRs (as literals the compiler parks each in a
    * VGPR pair for the whole loop, and spilled them): BACKGROUND's component 10/255
@@ -451,6 +451,12 @@ struct PtLaunch
    * every launch without frozen tiles; a list needs acc_keep (pt_launch_render) */
   const uint32_t *slot_list;
   uint32_t slot_count;
+  /* the mixed grid (the MIXED members, one launch): slots below n_whole run as ONE workgroup each and finish their pixels in the
+   * kernel, whatever sample_chunks says; the slots from n_whole on run as sample_chunks workgroups each, dispatched after every whole
+   * one, and acc_ws holds records for THOSE slots alone (record slot - n_whole; the NaN masks behind tile_count - n_whole records),
+   * which pt_resolve_tiles finishes.  0 in every other launch: the uniform forms, as before.  Needs sample_chunks > 1 and neither
+   * acc_keep nor a slot list (pt_launch_render) */
+  uint32_t n_whole;
 };
 
 /* The compact tile-major outputs of an AOV launch (rt_hip.h, RtHipAov; render_aov in pt_kernel.hip): tile slot k owns albedo / normal
@@ -638,6 +644,7 @@ struct PtPlan
 {
   int kernel;                          /* index into the family */
   uint32_t sample_chunks;              /* what the kernel runs */
+  bool mixed;                          /* the kernel takes a mixed grid (PtLaunch.n_whole > 0) */
   bool windowed;                       /* pixel sums are windowed (win_add): the chunk workspace has PT_ACC_WS_WORDS_WIN words per tile */
   bool queued;                         /* parked walks: a tile per wave */
   uint32_t pend_entries, pend_columns; /* the pending-ray pool it needs (pend_pool_for); 0 entries: none */
@@ -648,6 +655,9 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
  * body), and the resolve of the sums its passes left: pt_resolve_tiles or pt_resolve_slices over launch.samples samples
  * (tile_samples: null, or a count per slot that replaces it where nonzero) */
 bool pt_kernel_takes_chunks(int which);
+/* workgroups of member `which` the current device holds at once for a launch of `scene` (CUs x workgroups a CU takes with the
+ * launch's dynamic LDS); 0: not known */
+uint32_t pt_resident_workgroups(int which, const PtSceneView &scene);
 hipError_t pt_launch_resolve(const PtLaunch &launch, const uint32_t *tile_samples, hipStream_t stream, int which);
 /* adaptive sampling: the per-tile error estimate of two resolves (pt_tile_error), and the freeze -- the keep mask from the errors
  * (error == nullptr: `keep` holds the caller's mask), then the live slots frozen or compacted into slot_list (pt_tile_compact).

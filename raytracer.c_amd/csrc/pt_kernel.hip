@@ -137,10 +137,11 @@
  *   STAGES_NONE  geometry and tables from memory: no staged scene in LDS, whatever the scene's size
  *   WIDE_PEND    4 x 512 stacks per pool slot (path ids that travel through the ring)
  *   CHUNKS       takes sample_chunks > 1 (integer partial sums merged by pt_resolve_tiles)
- *   WINDOWED     ... as windowed sums (win_add): PT_ACC_WS_WORDS_WIN words per tile of the chunk workspace */
+ *   WINDOWED     ... as windowed sums (win_add): PT_ACC_WS_WORDS_WIN words per tile of the chunk workspace
+ *   MIXED        takes a mixed grid (PtLaunch.n_whole > 0): whole tiles, then the last tiles as sample chunks, in one launch */
 enum PtKernelProps : uint32_t
 {
-  PEND_POOL = 1u, QUEUED = 2u, STAGES_NONE = 4u, WIDE_PEND = 8u, CHUNKS = 16u, WINDOWED = 32u
+  PEND_POOL = 1u, QUEUED = 2u, STAGES_NONE = 4u, WIDE_PEND = 8u, CHUNKS = 16u, WINDOWED = 32u, MIXED = 64u
 };
 
 /* launch bounds (waves per SIMD; PT_MIN_WAVES, _TRI, _CHK: pt_body_pooled.h).  `make variant DEFS=-DPT_MIN_WAVES_...` and
@@ -176,7 +177,7 @@ enum PtKernelProps : uint32_t
 /* bodies: render_tiles_pooled<CHECKER, TRIS, FILT_LDS, GEOM_LDS[, REFR]>, render_tiles_queued<CHECKER[, SPHERE_PROBE, REFR,
  * GEOM_LDS]>, render_tiles_static<VARIANT, REFRACT, CHECKER, TRIS, FILT_LDS, WHITTED, GEOM_LDS> */
 #define PT_FAMILY(X) \
-  X(K_TILES,               pt_render_tiles,                     (PT_BLOCK, PT_MIN_WAVES),             CHUNKS,                                             render_tiles_pooled<false, false, true, true>) \
+  X(K_TILES,               pt_render_tiles,                     (PT_BLOCK, PT_MIN_WAVES),             CHUNKS | MIXED,                                     render_tiles_pooled<false, false, true, true, false, true>) \
   X(K_BIG,                 pt_render_tiles_big,                 (PT_BLOCK, PT_MIN_WAVES),             CHUNKS,                                             render_tiles_pooled<false, false, false, true>) \
   X(K_TRI,                 pt_render_tiles_tri,                 (PT_BLOCK, PT_MIN_WAVES_TRI),         CHUNKS,                                             render_tiles_pooled<false, true, true, true>) \
   X(K_TRI_BIG,             pt_render_tiles_tri_big,             (PT_BLOCK, 4),                        CHUNKS,                                             render_tiles_pooled<false, true, false, true>) \
@@ -754,7 +755,8 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
 {
   __shared__ float out_f[PT_TILE_PIXELS * 3];
   __shared__ uint8_t out_b[PT_TILE_PIXELS * 3 + 64];
-  const uint32_t slot = blockIdx.x;
+  /* (a mixed grid, PtLaunch.n_whole > 0: the grid is the chunked slots, and the workspace holds their records alone) */
+  const uint32_t slot = L.n_whole + blockIdx.x;
   const int32_t samples = resolve_samples(L, tile_samples, slot);
   const uint32_t tile = L.tile_first + slot * L.tile_stride;
   if (L.acc_windows)
@@ -777,8 +779,8 @@ extern "C" __global__ __launch_bounds__(PT_BLOCK) void pt_resolve_tiles(const Pt
     }
   }
   else
-    resolve_finish_pixels(L, samples, L.acc_ws + (size_t)slot * (PT_TILE_PIXELS * 3),
-                          L.acc_ws + (size_t)L.tile_count * (PT_TILE_PIXELS * 3) + (size_t)slot * 3, tile, out_f, out_b);
+    resolve_finish_pixels(L, samples, L.acc_ws + (size_t)blockIdx.x * (PT_TILE_PIXELS * 3),
+                          L.acc_ws + (size_t)(L.tile_count - L.n_whole) * (PT_TILE_PIXELS * 3) + (size_t)blockIdx.x * 3, tile, out_f, out_b);
   __syncthreads();
   store_tile_pixels(L, out_f, out_b, slot);
 }
@@ -1546,6 +1548,7 @@ PtPlan pt_plan_launch(const PtSceneView &scene, const PtPlanAsk &a)
   const PtKernelInfo &k = pt_kernels[p.kernel];
   p.sample_chunks = k.has(CHUNKS) ? chunks : 1u;
   p.windowed = k.has(WINDOWED);
+  p.mixed = k.has(MIXED);
   p.queued = k.has(QUEUED);
   if (k.has(PEND_POOL))
   {
@@ -1675,11 +1678,15 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
                  (((size_t)max(launch.scene.bvh_depth, 1u) * PT_BLOCK * 3u + 15u) & ~(size_t)15u);
   if (launch.acc_keep && (k.has(CHUNKS) ? launch.acc_ws == nullptr || (launch.acc_windows != 0u) != k.has(WINDOWED) : launch.slice_ws == nullptr))
     return hipErrorInvalidValue; /* a pass of an accumulation adds to the sums its caller holds: they are neither cleared nor resolved here */
+  /* a mixed grid: a member that takes one, whole slots and chunked slots both, chunks to split into, one-shot, no list */
+  if (launch.n_whole != 0u && (!k.has(MIXED) || launch.n_whole >= launch.tile_count || launch.sample_chunks < 2u || launch.acc_keep || launch.slot_list))
+    return hipErrorInvalidValue;
+  const uint32_t n_chunked = launch.tile_count - launch.n_whole; /* slots that run as sample chunks, if any does: they own the workspace */
   if (launch.sample_chunks > 1 && !launch.acc_keep)
   {
     if ((launch.acc_windows != 0u) != k.has(WINDOWED) || launch.acc_ws == nullptr)
       return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(launch.acc_ws, 0, (size_t)launch.tile_count * (k.has(WINDOWED) ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long), stream);
+    hipError_t e = hipMemsetAsync(launch.acc_ws, 0, (size_t)n_chunked * (k.has(WINDOWED) ? PT_ACC_WS_WORDS_WIN : PT_ACC_WS_WORDS) * sizeof(unsigned long long), stream);
     if (e != hipSuccess)
       return e;
   }
@@ -1687,16 +1694,32 @@ hipError_t pt_launch_render(const PtLaunch &launch, hipStream_t stream, int whic
   if ((launch.slot_list != nullptr) != (launch.slot_count != 0u) || (launch.slot_list && !launch.acc_keep) || launch.slot_count > launch.tile_count)
     return hipErrorInvalidValue;
   /* the parked-walk kernels render a tile per wave, four work units per workgroup */
-  const uint32_t n_units = (launch.slot_list ? launch.slot_count : launch.tile_count) * launch.sample_chunks;
+  const uint32_t n_units = launch.n_whole + (launch.slot_list ? launch.slot_count : n_chunked) * launch.sample_chunks;
   hipError_t e = launch_staged(kernel, queued ? (n_units + PT_BLOCK / 64 - 1) / (PT_BLOCK / 64) : n_units, lds_bytes, stream, launch);
   if (e == hipSuccess && launch.sample_chunks > 1 && !launch.acc_keep)
-    e = launch_staged(pt_resolve_tiles, launch.tile_count, 0, stream, launch, static_cast<const uint32_t *>(nullptr));
+    e = launch_staged(pt_resolve_tiles, n_chunked, 0, stream, launch, static_cast<const uint32_t *>(nullptr));
   if (e == hipSuccess)
     pt_kernels.launched(which);
   return e;
 }
 
 bool pt_kernel_takes_chunks(int which) { return pt_kernels.valid(which) && pt_kernels[which].has(CHUNKS); }
+
+uint32_t pt_resident_workgroups(int which, const PtSceneView &scene)
+{
+  if (!pt_kernels.valid(which))
+    return 0u;
+  const PtKernelInfo &k = pt_kernels[which];
+  int dev = 0, cus = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(k.fn), PT_BLOCK,
+                                                   k.has(STAGES_NONE) ? (size_t)0 : pt_render_lds_bytes(scene)) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return 0u;
+  }
+  return cus > 0 && n > 0 ? (uint32_t)cus * (uint32_t)n : 0u;
+}
 
 hipError_t pt_launch_resolve(const PtLaunch &launch, const uint32_t *tile_samples, hipStream_t stream, int which)
 {

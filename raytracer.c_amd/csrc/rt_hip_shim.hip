@@ -913,6 +913,160 @@ void pend_pools_release()
   (void)hipSetDevice(prev);
 }
 
+/* ---- the mixed grid (PtLaunch.n_whole): a one-chunk launch of many rounds of workgroups ends with the device
+ * partly empty -- the dispatcher runs dry while every CU still holds workgroups at random points of their lives, and the frame ends
+ * with the last of them.  So the launch's LAST tiles run as sample chunks, short workgroups, behind the whole ones: one launch, the
+ * same sums bit for bit (integer partial sums, pt_resolve_tiles), and only those tiles pay the chunks' prologues and the resolve.
+ * The shim chooses it by itself where the caller asked for one chunk and gave no workspace; the chunked slots' records live in a
+ * per-device workspace the shim owns (GridTailWs), as the parked-walk workspace is owned. */
+struct GridTailWs
+{
+  unsigned long long *ws = nullptr; /* a raw pointer, as the other per-device pools hold theirs: freed by grid_tail_release() alone, never at exit */
+  size_t bytes = 0;
+  hipEvent_t done = nullptr;   /* recorded behind the last launch that used the workspace ... */
+  hipStream_t stream = nullptr; /* ... on this stream: a launch on another stream waits for it first */
+  bool used = false;
+  /* what pt_resident_workgroups said last on this device, and for which member and dynamic LDS: asked again only when those change */
+  uint32_t resident = 0;
+  int resident_kernel = -1;
+  size_t resident_lds = 0;
+};
+std::mutex g_tail_mutex; /* held from the lookup until the launch that uses the workspace is enqueued */
+GridTailWs g_tail[64];
+std::atomic<uint64_t> g_mixed_launches{0};
+
+/* The rule.  It reads launch facts only: the slots, the samples, the workgroups the device holds at once (pt_resident_workgroups:
+ * 1,280 of pt_render_tiles on an MI355X).  A launch of fewer than GRID_TAIL_MIN_ROUNDS rounds of workgroups stays as it is -- there
+ * the chunks' prologues weigh more and the tail is a larger share of a frame that suggest_chunks already covers --, and a chunk keeps
+ * at least GRID_TAIL_MIN_SAMPLES samples (rt_hip_suggest_chunks' floor).  The last GRID_TAIL_ROUNDS rounds' worth of slots are
+ * chunked, GRID_TAIL_CHUNKS workgroups each: swept on the headline, profiles/r20_grid_tail_sweep.txt.  GRID_TAIL_MIN_ROUNDS is NOT
+ * measured: the headline's 25 rounds are the only launch length timed, and 8 is a guess that keeps a third of that.
+ * Two switches for A/B runs and tests, read at every launch: RT_HIP_GRID_UNIFORM=1 keeps every launch uniform;
+ * RT_HIP_GRID_SPLIT=<n_whole>,<chunks> sets the split of every launch whose FORM takes one (one chunk asked, no workspace given, a
+ * MIXED member, a plain one-shot launch) whatever its size: n_whole >= the slots is the uniform one-chunk launch, 0 the uniform
+ * chunked one. */
+constexpr uint32_t GRID_TAIL_MIN_ROUNDS = 8, GRID_TAIL_ROUNDS = 1, GRID_TAIL_CHUNKS = 4, GRID_TAIL_MIN_SAMPLES = 128;
+
+/* -> true with *n_whole, *chunks set: the launch takes them (n_whole < tile_count, chunks >= 2); false: it stays uniform */
+bool grid_split_for(const PtLaunch &L, const PtPlan &plan, int device, uint32_t *n_whole, uint32_t *chunks)
+{
+  if (!plan.mixed || plan.sample_chunks != 1u || L.acc_keep || L.slot_list || L.tile_count < 2u || L.samples < 2)
+    return false;
+  const char *uni = getenv("RT_HIP_GRID_UNIFORM");
+  if (uni && uni[0] == '1')
+    return false;
+  if (const char *e = getenv("RT_HIP_GRID_SPLIT"))
+  {
+    char *end = nullptr;
+    const unsigned long w = strtoul(e, &end, 10);
+    const unsigned long c = (end && *end == ',') ? strtoul(end + 1, nullptr, 10) : 0ul;
+    if (w >= L.tile_count || c < 2ul || c > (unsigned long)L.samples || (uint64_t)(L.tile_count - w) * c + w > 0x7FFFFFFFull)
+      return false;
+    *n_whole = (uint32_t)w;
+    *chunks = (uint32_t)c;
+    return true;
+  }
+  /* the free tests first: a launch of few samples or few tiles asks the runtime nothing and takes no lock */
+  if ((uint32_t)L.samples < GRID_TAIL_CHUNKS * GRID_TAIL_MIN_SAMPLES || L.tile_count < GRID_TAIL_MIN_ROUNDS || device < 0 || device >= 64)
+    return false;
+  uint32_t resident = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_tail_mutex);
+    GridTailWs &t = g_tail[device];
+    const size_t lds = pt_render_lds_bytes(L.scene);
+    if (t.resident_kernel != plan.kernel || t.resident_lds != lds)
+    {
+      t.resident = pt_resident_workgroups(plan.kernel, L.scene);
+      t.resident_kernel = plan.kernel;
+      t.resident_lds = lds;
+    }
+    resident = t.resident;
+  }
+  if (resident == 0u || (uint64_t)L.tile_count < (uint64_t)GRID_TAIL_MIN_ROUNDS * resident)
+    return false;
+  *n_whole = L.tile_count - GRID_TAIL_ROUNDS * resident;
+  *chunks = GRID_TAIL_CHUNKS;
+  return true;
+}
+
+/* The device's workspace for n_chunked slots, grown when a launch needs more (after the device has drained), and `stream` made to
+ * wait for the launch that used it last where that ran elsewhere.  nullptr: it cannot be had (or RT_HIP_FAIL_ALLOC_TAIL_WS says
+ * so), and the launch stays uniform.  The caller holds g_tail_mutex, the current device is `device`; grid_tail_used() follows the launch. */
+unsigned long long *grid_tail_ws(int device, uint32_t n_chunked, hipStream_t stream)
+{
+  if (device < 0 || device >= 64 || (g_fail_alloc.load() & RT_HIP_FAIL_ALLOC_TAIL_WS))
+    return nullptr;
+  GridTailWs &t = g_tail[device];
+  const size_t need = (size_t)n_chunked * PT_ACC_WS_WORDS * sizeof(unsigned long long);
+  if (t.bytes < need)
+  {
+    if (t.ws)
+    {
+      if (hipDeviceSynchronize() != hipSuccess)
+      {
+        (void)hipGetLastError();
+        return nullptr;
+      }
+      (void)hipFree(t.ws);
+      t.ws = nullptr;
+    }
+    t.bytes = 0;
+    t.used = false;
+    if (hipMalloc(&t.ws, need) != hipSuccess)
+    {
+      (void)hipGetLastError(); /* the launch goes on uniform: nothing sticky behind the failure */
+      t.ws = nullptr;
+      return nullptr;
+    }
+    t.bytes = need;
+  }
+  if (!t.done && hipEventCreateWithFlags(&t.done, hipEventDisableTiming) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    t.done = nullptr;
+    return nullptr;
+  }
+  if (t.used && t.stream != stream && hipStreamWaitEvent(stream, t.done, 0) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return t.ws;
+}
+
+void grid_tail_used(int device, hipStream_t stream)
+{
+  GridTailWs &t = g_tail[device];
+  if (hipEventRecord(t.done, stream) != hipSuccess)
+  { /* nothing to order the next user by: let this one finish */
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(stream);
+    t.used = false;
+    return;
+  }
+  t.stream = stream;
+  t.used = true;
+}
+
+void grid_tail_release()
+{
+  std::lock_guard<std::mutex> lock(g_tail_mutex);
+  int prev = 0;
+  (void)hipGetDevice(&prev);
+  for (int d = 0; d < 64; d++)
+    if (g_tail[d].ws || g_tail[d].done)
+    {
+      (void)hipSetDevice(d);
+      (void)hipDeviceSynchronize();
+      if (g_tail[d].done)
+        (void)hipEventDestroy(g_tail[d].done);
+      if (g_tail[d].ws)
+        (void)hipFree(g_tail[d].ws);
+      g_tail[d] = GridTailWs();
+    }
+  (void)hipSetDevice(prev);
+}
+
 uint32_t tiles_x_of(int width) { return ((uint32_t)width + PT_TILE - 1) / PT_TILE; }
 uint32_t tiles_y_of(int height) { return ((uint32_t)height + PT_TILE - 1) / PT_TILE; }
 
@@ -1477,6 +1631,12 @@ int launch_prepare(const RtHipScene *scene, const RtHipCamera *camera, const RtH
       /* RT_HIP_DIAG_PARK_COUNTS=1: the caller's counters hold 64 words, not 48: the retry stack's five go to stats[4 + 44] .. [4 + 48] */
       const char *park = getenv("RT_HIP_DIAG_PARK_COUNTS");
       L.diag_flags |= (park && park[0] == '1') ? 2u : 0u;
+    }
+#endif
+#ifdef PT_PHASE
+    { /* the phase build only (tools/grid_tail.py): RT_HIP_PHASE_WG_TIMES=1: the caller's counters hold 80 + 2 x workgroups words */
+      const char *times = getenv("RT_HIP_PHASE_WG_TIMES");
+      L.diag_flags |= (times && times[0] == '1') ? 4u : 0u;
     }
 #endif
     L.background = 10 / 255.0;
@@ -2342,6 +2502,7 @@ void release_cache_impl()
     ctx_release(g_ctx);
   }
   pend_pools_release();
+  grid_tail_release();
 }
 
 int set_bvh_builder_impl(int builder)
@@ -4291,6 +4452,8 @@ const char *rt_hip_kernel_for_class(const RtHipSceneClass *c)
 
 void rt_hip_selftest_fail_alloc(uint32_t mask) { g_fail_alloc.store(mask); }
 
+uint64_t rt_hip_mixed_grid_launches(void) { return g_mixed_launches.load(); }
+
 int rt_hip_selftest_pool_slots(int device, uint32_t *park_slots_per_xcd, uint32_t *pend_slots_per_xcd)
 {
   if (!have_device(device))
@@ -4449,7 +4612,29 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
                      &plan);
     if (!rc && (uint64_t)L.tile_count * L.sample_chunks > 0x7FFFFFFFull)
       rc = fail(RT_HIP_EINVAL, "tile_count x sample_chunks exceeds the grid limit");
+    /* one chunk asked and no workspace given: the mixed grid, where the rule takes it and its workspace can be had */
+    std::unique_lock<std::mutex> tail_lock(g_tail_mutex, std::defer_lock);
+    uint32_t n_whole = 0, tail_chunks = 0;
+    if (!rc && sample_chunks == 1 && !d_workspace && grid_split_for(L, plan, scene->device, &n_whole, &tail_chunks))
+    {
+      tail_lock.lock();
+      if (unsigned long long *ws = grid_tail_ws(scene->device, L.tile_count - n_whole, st))
+      {
+        L.acc_ws = ws;
+        L.n_whole = n_whole;
+        L.sample_chunks = tail_chunks;
+      }
+      else
+        tail_lock.unlock();
+    }
     const hipError_t e = rc ? hipSuccess : pt_launch_render(L, st, plan.kernel);
+    if (tail_lock.owns_lock())
+    {
+      grid_tail_used(scene->device, st);
+      if (e == hipSuccess && L.n_whole != 0u)
+        g_mixed_launches.fetch_add(1);
+      tail_lock.unlock();
+    }
     if (pend_lock.owns_lock())
       pend_lock.unlock();
     release_tables(scene, slot, st);

@@ -13,7 +13,7 @@ HOST_PATH = os.path.join(PKG_DIR, "host", "libraytracer_amd.so")
 M_DEFAULT, M_REFLECTION, M_REFRACTION, M_CHECKERED = 2, 4, 8, 16
 TILE, TILE_PIXELS, TILE_FLOATS = 8, 64, 192
 STAT_RAYS, STAT_CASTS, STAT_TESTS, STAT_SAMPLES, NSTATS = 0, 1, 2, 3, 4
-FAIL_ALLOC_PARK_WS, FAIL_ALLOC_WIDE_PEND = 1, 2   # rt_hip_selftest_fail_alloc
+FAIL_ALLOC_PARK_WS, FAIL_ALLOC_WIDE_PEND, FAIL_ALLOC_TAIL_WS = 1, 2, 4   # rt_hip_selftest_fail_alloc
 FAIL_PEND_SLOT, FAIL_PARK_SLOT = 1, 2             # rt_hip_launch_status
 EINVAL = -2                                       # RT_HIP_EINVAL
 # render_progressive's per-pass callback: (samples done, budget, kernel seconds of the pass, user)
@@ -263,6 +263,7 @@ SHIM_SYMBOLS = {
     "rt_hip_kernel_for_class": (C.c_char_p, [C.c_void_p]),
     "rt_hip_launch_status": (C.c_int, [C.c_int, C.POINTER(C.c_uint32)]),
     "rt_hip_selftest_fail_alloc": (None, [C.c_uint32]),
+    "rt_hip_mixed_grid_launches": (C.c_uint64, []),
     "rt_hip_selftest_pool_slots": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_hip_render_aov_tiles": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipParams), C.POINTER(RtHipAov), C.c_void_p]),
     "rt_hip_untile_aov": (C.c_int, [C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
