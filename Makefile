@@ -22,11 +22,11 @@ CFLAGS  := -std=c99 -D_DEFAULT_SOURCE -O2 -ffp-contract=off -fPIC -Wall -Wno-unu
 
 SHIM    := $(CSRC)/librt_hip.so
 # the path tracer's device code is one translation unit, pt_kernel.hip, split by topic into the pt_*.h headers it includes; the
-# hierarchy build, the scene updates, the lens and the image-space passes are a translation unit each
-# the six sources every build of the shim compiles, in this order
+# hierarchy build, the scene updates, the lens, the image-space passes and the light probes are a translation unit each
+# the seven sources every build of the shim compiles, in this order
 SHIM_SRC := $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip $(CSRC)/lens.hip \
-            $(CSRC)/image_ops.hip
-KERNEL_SRC := $(SHIM_SRC) $(wildcard $(CSRC)/pt_*.h) $(CSRC)/bvh_build.h $(CSRC)/scene_spheres.h $(CSRC)/rt_staging.h $(INC)/rt_hip.h $(INC)/rt_rng.h
+            $(CSRC)/image_ops.hip $(CSRC)/probe.hip
+KERNEL_SRC := $(SHIM_SRC) $(wildcard $(CSRC)/pt_*.h) $(CSRC)/bvh_build.h $(CSRC)/scene_spheres.h $(CSRC)/ray_store.h $(CSRC)/rt_staging.h $(INC)/rt_hip.h $(INC)/rt_rng.h
 HOSTLIB := $(HOST)/libraytracer_amd.so
 CLI     := $(HOST)/raytracer
 

@@ -760,6 +760,105 @@ int rt_hip_lens_resolve(const double *d_sum, int32_t width, int32_t height, int3
 int rt_hip_render_lens_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
                              const RtHipLens *lens, const RtHipParams *params, int device, float *h_rgb, uint8_t *h_rgb8, uint64_t *h_stats);
 
+/* ---- light probes: SH9 radiance and irradiance baked from generated probe rays -----------------------------------------------------
+ * A bake is made of three pieces, as a lens frame is: a kernel that writes the PROBE RAYS of a slice of ray indices, the radiance
+ * query above (rt_hip_trace_rays, called as it stands) and a kernel that folds the slice's samples into per-probe sums, with a
+ * resolve.  What is new is a pure function of its arguments and is stated here operation for operation; everything about paths is
+ * rt_hip_trace_rays' contract.  The reference has no probe code: its random_on_unit_sphere and random_on_hemisphere are restated.
+ *
+ * RAY INDEX SPACE.  N probes, S = params->samples samples a probe; the ray of (probe i, sample s) has index k = i*S + s (probe-major: a
+ * slice of consecutive k keeps the device full even for few probes); N*S <= 2^32.
+ *
+ * THE PROBE RAY of index k under a seed.  fp64 + - * / sqrt, unfused, in the order written:
+ *   stream         state rt_rng_seed(rt_mix64(seed ^ 0x70726F62), k, 0) of rt_rng.h: a stream of its own, as the lens has one.  The
+ *                  path's stream (seed, k, 0) is untouched, and the two draws rt_hip_trace_rays discards stay unused.
+ *   a round        random_on_unit_sphere's (raytracer.c:231-243): draws r1, r2, r3; x = r1*2.0 + -1.0, y and z likewise;
+ *                  q = (x*x + y*y) + z*z; accepted iff q <= 1.0 && q >= 2^-20.  The first accepted round of at most 32 gives
+ *                  d = (x, y, z) * (1.0 / sqrt(q)); if none accepts, d = (0, 0, 1) (probability about 5e-11 a ray).
+ *   RT_HIP_PROBE_SPHERE      origin = the probe's position (3 doubles), direction d.
+ *   RT_HIP_PROBE_HEMISPHERE  needs normals (3 doubles a probe, used as given: not normalised) and bias >= 0:
+ *                  c = (d.x*n.x + d.y*n.y) + d.z*n.z; if c < 0 then d = d * -1.0 (random_on_hemisphere, :245-253); origin =
+ *                  position + n*bias.
+ * A position or normal that is not finite gives a ray that rt_hip_trace_rays calls INVALID (status 2); it is written as computed.
+ *
+ * THE FOLD.  With the ray's stored direction (x, y, z) and its sample `radiance` (3 doubles), for every basis j and channel c, over
+ * the probe's rays in ascending k from +0.0: sum = sum + (radiance[c] * w_j), the product rounded before the add.  A ray of status 2
+ * makes all of its probe's sums NaN (isnan; sign and payload unspecified).
+ *   SPHERE, 9 bases (real spherical harmonics to l = 2):  w0 = Y0, w1 = Y1*y, w2 = Y1*z, w3 = Y1*x, w4 = Y2A*(x*y), w5 = Y2A*(y*z),
+ *     w6 = Y2B*(3.0*(z*z) - 1.0), w7 = Y2A*(x*z), w8 = Y2C*(x*x - y*y), with Y0 = 0.28209479177387814, Y1 = 0.4886025119029199,
+ *     Y2A = 1.0925484305920792, Y2B = 0.31539156525252005, Y2C = 0.5462742152960396.
+ *   HEMISPHERE, 1 basis:  c = (x*n.x + y*n.y) + z*n.z; w0 = c > 0 ? c : 0.0.
+ * THE RESOLVE.  coeff = (sum * (1.0 / (double)S)) * K; K = 12.566370614359172 (4 pi) for SPHERE: the SH9 radiance coefficients,
+ * N x 9 x 3 doubles [probe][basis][channel]; K = 6.283185307179586 (2 pi) for HEMISPHERE: the irradiance E, N x 1 x 3.  The float
+ * copy is (float)coeff.
+ * IRRADIANCE FROM SH9 (rt_hip_probe_irradiance): m entries of a probe index (uint32) and a normal n (3 doubles, used as given);
+ * E_c = the ascending sum from +0.0 over j = 0 .. 8 of (A_j * coeff[i][j][c]) * w_j(n), w_j as above, A_0 = 3.141592653589793,
+ * A_1..3 = 2.0943951023931953, A_4..8 = 0.7853981633974483 (the cosine lobe's band factors).  A probe index >= N gives a quiet NaN:
+ * the function is total.
+ *
+ * THE BAKE (rt_hip_bake_probes): the sums are zeroed to +0.0 and the probes' status to 1; the ray indices are walked in ascending
+ * slices of at most slice_rays rays (above N*S means N*S): the slice's rays; rt_hip_trace_rays' own launch with samples = 1,
+ * index_first = the slice's first k, RT_HIP_RAYS_GIVEN and origin_radius = params->origin_radius (the caller's hint: every origin
+ * lies within it of the world's origin; it changes no bit); the fold.  Then the resolve.  Everything goes on `stream` with no host
+ * wait between slices; d_stats (may be NULL) accumulates rt_hip_trace_rays' counters.
+ * CONTRACT:
+ *   (a) the rays equal the statement above bit for bit;
+ *   (b) sample s of probe i is what rt_hip_trace_rays returns for that ray at index_first + j = i*S + s, samples = 1: `paths` and
+ *       `casts` equal the compiled reference's per ray, and the values are inside that contract's bar;
+ *   (c) sums, coefficients and their float copy are the stated reductions of those samples, bit for bit;
+ *   (d) one thread adds a sum in ascending k across slices: no output bit depends on slice_rays;
+ *   (e) scenes with M_REFRACTION report through the device's status word exactly as rt_hip_trace_rays says.
+ *   - rt_hip_probe_defaults: mode SPHERE, flags 0, samples 64, max_depth 5, seed 0, bias 0, origin_radius 0, reserved 0.
+ *   - rt_hip_probe_rays: the generator alone: rays [k_first, k_first + n) into d_rays (n x 6 doubles, 16-byte aligned, as
+ *     rt_hip_trace_rays takes them); k_first + n <= N*S; max_depth and origin_radius are not used; asynchronous on `stream`, on the
+ *     device that holds d_rays.  n == 0 is RT_HIP_OK and launches nothing.
+ *   - rt_hip_probe_workspace_bytes: the d_workspace of rt_hip_bake_probes for slices of slice_rays rays (a slice's rays, status
+ *     words and radiance, 76 bytes a ray, and the sums, 24 bytes a basis and probe, whether or not d_sum is given).  A caller whose
+ *     slice_rays exceeds N*S may size it with N*S.  0 for an unknown mode or slice_rays == 0.
+ *   - rt_hip_bake_probes: d_positions (and d_normals for HEMISPHERE) hold 3 doubles a probe.  d_sum (N x bases x 3 doubles) may be
+ *     NULL: the sums then live in the workspace; d_coeff (the same shape) is required; d_coeff_f (floats) and d_status (a uint32 a
+ *     probe: 1, or 2 if any of its rays was invalid) may be NULL.
+ *   - rt_hip_probe_resolve: the resolve alone, for a caller that keeps d_sum; d_coeff_f may be NULL.  Asynchronous on `stream`, on
+ *     the device that holds d_sum.
+ *   - rt_hip_probe_irradiance: d_coeff holds n_probes x 9 x 3 doubles; d_irradiance gets 3 doubles an entry.  m == 0 is RT_HIP_OK.
+ *   - rt_hip_bake_probes_host: the host form, synchronous, with a scene and buffers of its own on logical device `device` of
+ *     rt_hip_render_image's device map; h_coeff is required, h_coeff_f and h_status may be NULL; h_stats (may be NULL) is
+ *     overwritten; it checks the device's status word (rt_hip_launch_status) and returns its error.
+ * Refusals, each before the first launch and with the outputs untouched, arguments before the device is looked for.  RT_HIP_EINVAL:
+ * an unknown mode; flags or reserved not 0; samples < 1; n_probes * samples > 2^32; slice_rays == 0; bias or origin_radius negative
+ * or not finite; HEMISPHERE without normals; max_depth outside 0 .. 1000000; a d_workspace or d_rays that is not 16-byte aligned; a
+ * NULL required pointer; near_R >= 1e15 (rt_hip_trace_rays' rule).  RT_HIP_ELIMIT: max_depth above 32 with an M_REFRACTION material,
+ * as rt_hip_trace_rays.  n_probes == 0 with good params is RT_HIP_OK and launches nothing. */
+enum
+{
+  RT_HIP_PROBE_SPHERE = 0,
+  RT_HIP_PROBE_HEMISPHERE = 1
+};
+typedef struct
+{
+  uint32_t mode;        /* RT_HIP_PROBE_SPHERE | RT_HIP_PROBE_HEMISPHERE */
+  uint32_t flags;       /* must be 0 */
+  int32_t samples;      /* S >= 1 rays a probe */
+  int32_t max_depth;    /* the reference's MAX_DEPTH */
+  uint64_t seed;
+  double bias;          /* >= 0, finite: a hemisphere probe's rays start at position + normal*bias */
+  double origin_radius; /* as rt_hip_trace_rays: a hint, changes no output bit */
+  uint64_t reserved;    /* must be 0 */
+} RtHipProbeParams;
+void rt_hip_probe_defaults(RtHipProbeParams *params);
+int rt_hip_probe_rays(const double *d_positions, const double *d_normals, uint64_t n_probes, const RtHipProbeParams *params, uint64_t k_first,
+                      uint64_t n, double *d_rays, void *stream);
+size_t rt_hip_probe_workspace_bytes(uint64_t n_probes, uint32_t mode, uint32_t slice_rays);
+int rt_hip_bake_probes(const RtHipScene *scene, const double *d_positions, const double *d_normals, uint64_t n_probes,
+                       const RtHipProbeParams *params, uint32_t slice_rays, void *d_workspace, double *d_sum, double *d_coeff, float *d_coeff_f,
+                       uint32_t *d_status, uint64_t *d_stats, void *stream);
+int rt_hip_probe_resolve(const double *d_sum, uint64_t n_probes, uint32_t mode, int32_t samples, double *d_coeff, float *d_coeff_f, void *stream);
+int rt_hip_probe_irradiance(const double *d_coeff, uint64_t n_probes, const uint32_t *d_index, const double *d_normals, uint64_t m,
+                            double *d_irradiance, void *stream);
+int rt_hip_bake_probes_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_positions,
+                            const double *h_normals, uint64_t n_probes, const RtHipProbeParams *params, int device, double *h_coeff,
+                            float *h_coeff_f, uint32_t *h_status, uint64_t *h_stats);
+
 /* ---- edge-avoiding a-trous denoiser guided by the first-hit buffers ---------------------------------------------------------
  * Inputs: row-major images of w x h pixels (1 <= w, h <= 2^20, w*h < 2^32) on one device -- colour c (3 floats per pixel: the
  * linear mean of rt_hip_render_tiles or rt_hip_accum_resolve after rt_hip_untile) and the RtHipAov buffers of the same frame

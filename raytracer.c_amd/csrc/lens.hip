@@ -3,8 +3,8 @@
  *   k_lens_rays        one thread a (pixel of a slice, fixed sample): the ray of rt_hip.h's contract, operation for operation --
  *                      jitter from the first two draws of the stream (seed, k, 0), the pinhole direction not normalised, the focus
  *                      point, the lens point by rejection from the stream (lens_seed, k, 0), at most PT_LENS_ROUNDS rounds (the loop
- *                      diverges per lane and is left to); 6 doubles a ray.  A wave's 64 rays are 192 pieces of 16 bytes: they change
- *                      lanes (ds_bpermute, no LDS allocated) so that each of the wave's three stores writes 1 KB in a row.
+ *                      diverges per lane and is left to); 6 doubles a ray, written by ray_store.h's
+ *                      wave-transposed stores (shared with probe.hip).
  *   k_lens_accumulate  one thread a (pixel, channel): sum += radiance; status 2 makes the pixel's sums NaN.  No atomics.
  *   k_lens_resolve     one thread a (pixel, channel): sum * (1.0 / S) -> float, and the byte by pt_math.h's tonemap, the device
  *                      function every resolve of pt_kernel.hip calls.  Row-major.
@@ -15,24 +15,12 @@
 #include "pt_device.h"
 #include "rt_rng.h"
 #include "pt_math.h"
+#include "ray_store.h"
 
 namespace
 {
 
 constexpr int LENS_BLOCK = 256;
-
-/* 16 bytes of a ray as the stores move them: two doubles' bits */
-struct Piece
-{
-  unsigned long long a, b;
-};
-
-__device__ __forceinline__ Piece piece_of(double a, double b) { return {(unsigned long long)__double_as_longlong(a), (unsigned long long)__double_as_longlong(b)}; }
-/* the piece lane `from` holds, under `keep` (all ones or zero); wave-uniform control flow: every lane takes part */
-__device__ __forceinline__ Piece piece_from(Piece v, uint32_t from, unsigned long long keep)
-{
-  return {__shfl(v.a, (int)from) & keep, __shfl(v.b, (int)from) & keep};
-}
 
 __global__ void __launch_bounds__(LENS_BLOCK) k_lens_rays(const PtLensRays A)
 {
@@ -73,20 +61,7 @@ __global__ void __launch_bounds__(LENS_BLOCK) k_lens_rays(const PtLensRays A)
   const V3 L = v_add(pos, v_add(v_scale(ld3(A.ax), a * R), v_scale(ld3(A.ay), b * R)));
   const V3 dir = v_normalize(v_sub(F, L));
 
-  /* ray r of the wave is pieces 3r .. 3r + 2; store j writes pieces [64 j, 64 j + 64), lane l the piece 64 j + l */
-  const Piece m0 = piece_of(L.x, L.y), m1 = piece_of(L.z, dir.x), m2 = piece_of(dir.y, dir.z);
-  Piece *const out = reinterpret_cast<Piece *>(A.rays) + 3u * (size_t)wave_first;
-#pragma unroll
-  for (uint32_t j = 0; j < 3u; j++)
-  {
-    const uint32_t piece = 64u * j + lane, from = piece / 3u, part = piece - 3u * from;
-    /* (masks, not a three-way select: the compiler turns that into an indexed array in scratch) */
-    const Piece q0 = piece_from(m0, from, part == 0u ? ~0ull : 0ull), q1 = piece_from(m1, from, part == 1u ? ~0ull : 0ull),
-                q2 = piece_from(m2, from, part == 2u ? ~0ull : 0ull);
-    const Piece q = {q0.a | q1.a | q2.a, q0.b | q1.b | q2.b};
-    if (piece < 3u * in_wave)
-      out[piece] = q;
-  }
+  store_wave_rays(A.rays, wave_first, lane, in_wave, L, dir);
 }
 
 __global__ void __launch_bounds__(LENS_BLOCK) k_lens_accumulate(const uint32_t *__restrict__ status, const double *__restrict__ radiance,

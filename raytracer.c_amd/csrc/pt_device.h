@@ -776,5 +776,59 @@ hipError_t lens_launch_accumulate(const uint32_t *status, const double *radiance
 hipError_t lens_launch_resolve(const double *sum, uint64_t n_pixels, int32_t samples, float *rgb, uint8_t *rgb8, hipStream_t stream);
 #endif
 
+/* ---- light probes (rt_hip.h, "light probes"; the kernels are probe.hip's, a translation unit of its own) ---- */
+/* The contract's constants, here and nowhere else: the kernels and the shim read these. */
+#define PT_PROBE_KEY 0x70726F62ull        /* the direction stream is (rt_mix64(seed ^ PT_PROBE_KEY), k, 0) */
+#define PT_PROBE_ROUNDS 32                /* rejection rounds of a direction before (0, 0, 1) is taken */
+#define PT_PROBE_Q_MIN 9.5367431640625e-07 /* 2^-20: a round whose squared length is below this is rejected */
+#define PT_PROBE_Y0 0.28209479177387814
+#define PT_PROBE_Y1 0.4886025119029199
+#define PT_PROBE_Y2A 1.0925484305920792
+#define PT_PROBE_Y2B 0.31539156525252005
+#define PT_PROBE_Y2C 0.5462742152960396
+#define PT_PROBE_K_SPHERE 12.566370614359172
+#define PT_PROBE_K_HEMISPHERE 6.283185307179586
+#define PT_PROBE_A0 3.141592653589793
+#define PT_PROBE_A1 2.0943951023931953
+#define PT_PROBE_A2 0.7853981633974483
+#define PT_PROBE_SH 9 /* bases of a sphere probe; a hemisphere probe has one */
+
+/* The probe rays of indices [k_first, k_first + n): ray k belongs to probe k / samples.  positions and normals hold 3 doubles a probe
+ * (normals: hemisphere only); probe_seed = rt_mix64(seed ^ PT_PROBE_KEY); rays[0 .. 6) is ray k_first. */
+struct PtProbeRays
+{
+  const double *positions, *normals;
+  double *rays; /* n x 6 doubles, 16-byte aligned */
+  uint64_t k_first, probe_seed;
+  double bias;
+  uint32_t n, samples, hemisphere;
+};
+
+/* One slice's fold: the slice holds the rays [k_first, k_first + n) -- their 6 doubles, status words and radiance --, and touches the
+ * probes probe_first .. probe_first + n_probes - 1; sum holds bases x 3 doubles a probe (bases = hemisphere ? 1 : PT_PROBE_SH). */
+struct PtProbeFold
+{
+  const double *rays, *radiance, *normals;
+  const uint32_t *status;
+  double *sum;
+  uint32_t *probe_status; /* may be null */
+  uint64_t k_first, probe_first, n_probes;
+  uint32_t n, samples, hemisphere;
+};
+
+#if defined(__HIPCC__)
+/* n >= 1 */
+hipError_t probe_launch_rays(const PtProbeRays &args, hipStream_t stream);
+/* n >= 1: sum = sum + (radiance * w) over the slice's rays of each probe in ascending k, a thread a (probe, basis, channel); a ray
+ * of status 2 makes its probe's sums NaN and its probe_status 2 */
+hipError_t probe_launch_fold(const PtProbeFold &args, hipStream_t stream);
+/* coeff = (sum * (1.0 / samples)) * k for n_values values; coeff_f (may be null) = (float)coeff */
+hipError_t probe_launch_resolve(const double *sum, uint64_t n_values, int32_t samples, double k, double *coeff, float *coeff_f,
+                                hipStream_t stream);
+/* m >= 1 entries (probe index, normal): the irradiance of rt_hip.h from n_probes x PT_PROBE_SH x 3 coefficients, 3 doubles an entry */
+hipError_t probe_launch_irradiance(const double *coeff, uint64_t n_probes, const uint32_t *index, const double *normals, uint64_t m,
+                                   double *irradiance, hipStream_t stream);
+#endif
+
 
 #endif /* PT_DEVICE_H */

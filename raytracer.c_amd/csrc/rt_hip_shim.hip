@@ -3590,6 +3590,197 @@ int render_lens_image_impl(const RtHipSphere *spheres, size_t n_spheres, const R
   return rc ? rc : status_to_error(flags);
 }
 
+/* ---- light probes (rt_hip.h, rt_hip_probe_* / rt_hip_bake_probes*) -------------------------------------------------------------
+ * A bake is probe rays (probe.hip), the radiance query as it stands (trace_launch) and a per-probe fold (probe.hip).  The checks need
+ * no device; the bake refuses everything it can before its first launch. */
+uint32_t probe_bases(uint32_t mode) { return mode == RT_HIP_PROBE_HEMISPHERE ? 1u : (uint32_t)PT_PROBE_SH; }
+
+/* what every probe call refuses in its params without a device: RT_HIP_EINVAL, or RT_HIP_OK */
+int check_probe(const RtHipProbeParams *p, uint64_t n_probes, bool have_normals)
+{
+  if (!p)
+    return fail(RT_HIP_EINVAL, "params is required");
+  if (p->mode != RT_HIP_PROBE_SPHERE && p->mode != RT_HIP_PROBE_HEMISPHERE)
+    return fail(RT_HIP_EINVAL, "mode %u is neither RT_HIP_PROBE_SPHERE nor RT_HIP_PROBE_HEMISPHERE", p->mode);
+  if (p->flags != 0u || p->reserved != 0u)
+    return fail(RT_HIP_EINVAL, "probe flags and reserved must be 0");
+  if (p->samples < 1)
+    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", p->samples);
+  if (n_probes > 0x100000000ull || n_probes * (uint64_t)p->samples > 0x100000000ull)
+    return fail(RT_HIP_EINVAL, "probes x samples = %llu x %d exceeds 2^32: a probe sample is a ray index of rt_hip_trace_rays",
+                (unsigned long long)n_probes, p->samples);
+  if (!(p->bias >= 0) || !std::isfinite(p->bias))
+    return fail(RT_HIP_EINVAL, "bias %g must be finite and >= 0", p->bias);
+  if (!(p->origin_radius >= 0) || !std::isfinite(p->origin_radius))
+    return fail(RT_HIP_EINVAL, "origin_radius %g must be finite and >= 0", p->origin_radius);
+  if (p->max_depth < 0 || p->max_depth > 1000000)
+    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  if (p->mode == RT_HIP_PROBE_HEMISPHERE && !have_normals && n_probes != 0)
+    return fail(RT_HIP_EINVAL, "RT_HIP_PROBE_HEMISPHERE needs normals");
+  return RT_HIP_OK;
+}
+
+/* the generator's arguments but for the range (k_first, n) and the output */
+PtProbeRays probe_args(const double *d_positions, const double *d_normals, const RtHipProbeParams *p)
+{
+  PtProbeRays A;
+  memset(&A, 0, sizeof A);
+  A.positions = d_positions;
+  A.normals = d_normals;
+  A.probe_seed = rt_mix64(p->seed ^ PT_PROBE_KEY);
+  A.bias = p->bias;
+  A.samples = (uint32_t)p->samples;
+  A.hemisphere = p->mode == RT_HIP_PROBE_HEMISPHERE ? 1u : 0u;
+  return A;
+}
+
+/* the parts of a bake's workspace: a slice's rays, status words and radiance, then the probes' sums */
+struct ProbeWorkspace
+{
+  size_t rays, status, radiance, sum, total;
+  ProbeWorkspace(uint64_t n_probes, uint32_t bases, uint64_t slice)
+  {
+    rays = 0;
+    status = rays + stage_align(48u * slice);
+    radiance = status + stage_align(4u * slice);
+    sum = radiance + stage_align(24u * slice);
+    total = sum + stage_align(24u * bases * n_probes);
+  }
+};
+
+int probe_rays_launch(const PtProbeRays &A, hipStream_t stream)
+{
+  const hipError_t e = probe_launch_rays(A, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "k_probe_rays launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+int probe_resolve_launch(const double *d_sum, uint64_t n_probes, uint32_t mode, int32_t samples, double *d_coeff, float *d_coeff_f,
+                         hipStream_t stream)
+{
+  const double k = mode == RT_HIP_PROBE_HEMISPHERE ? PT_PROBE_K_HEMISPHERE : PT_PROBE_K_SPHERE;
+  const hipError_t e = probe_launch_resolve(d_sum, 3u * probe_bases(mode) * n_probes, samples, k, d_coeff, d_coeff_f, stream);
+  if (e != hipSuccess)
+    return fail(RT_HIP_ERUNTIME, "k_probe_resolve launch: %s", hipGetErrorString(e));
+  return RT_HIP_OK;
+}
+
+/* The bake: for every slice the generator, the radiance query's own launch (trace_launch) and the fold; then the resolve.  All on
+ * `stream`, no host wait.  The depth limit and near_R are trace_launch's refusals: asked for once, up front.  n_probes >= 1. */
+int bake_probes_launch(const RtHipScene *scene, const double *d_positions, const double *d_normals, uint64_t n_probes,
+                       const RtHipProbeParams *p, uint32_t slice_rays, void *d_workspace, double *d_sum, double *d_coeff, float *d_coeff_f,
+                       uint32_t *d_status, uint64_t *d_stats, hipStream_t stream)
+{
+  const uint64_t total = n_probes * (uint64_t)p->samples, S = (uint64_t)p->samples;
+  const uint64_t slice = std::min<uint64_t>(slice_rays, total);
+  const uint32_t bases = probe_bases(p->mode);
+  RtHipTraceParams T;
+  rt_hip_trace_defaults(&T);
+  T.origin_radius = p->origin_radius;
+  T.samples = 1;
+  T.max_depth = p->max_depth;
+  T.seed = p->seed;
+  {
+    PtLaunch dry;
+    const int rc = pooled_launch_prepare(scene, T.source, nullptr, T.origin_radius, 1, T.max_depth, T.seed, nullptr, dry);
+    if (rc)
+      return rc;
+  }
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  const ProbeWorkspace W(n_probes, bases, slice);
+  char *const ws = static_cast<char *>(d_workspace);
+  double *const rays = reinterpret_cast<double *>(ws + W.rays);
+  uint32_t *const status = reinterpret_cast<uint32_t *>(ws + W.status);
+  double *const radiance = reinterpret_cast<double *>(ws + W.radiance);
+  double *const sum = d_sum ? d_sum : reinterpret_cast<double *>(ws + W.sum);
+  HIP_TRY(hipMemsetAsync(sum, 0, 24u * bases * n_probes, stream));
+  if (d_status)
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status), 1, n_probes, stream));
+  PtProbeRays A = probe_args(d_positions, d_normals, p);
+  A.rays = rays;
+  PtProbeFold F;
+  memset(&F, 0, sizeof F);
+  F.rays = rays;
+  F.radiance = radiance;
+  F.normals = d_normals;
+  F.status = status;
+  F.sum = sum;
+  F.probe_status = d_status;
+  F.samples = A.samples;
+  F.hemisphere = A.hemisphere;
+  const RtHipRadiance out = {status, radiance, nullptr, nullptr, nullptr, nullptr};
+  for (uint64_t first = 0; first < total; first += slice)
+  {
+    A.k_first = first;
+    A.n = (uint32_t)std::min<uint64_t>(slice, total - first);
+    int rc = probe_rays_launch(A, stream);
+    if (rc)
+      return rc;
+    T.index_first = (uint32_t)first;
+    rc = trace_launch(scene, rays, A.n, &T, &out, d_stats, stream);
+    if (rc)
+      return rc;
+    F.k_first = first;
+    F.n = A.n;
+    F.probe_first = first / S;
+    F.n_probes = (first + A.n - 1u) / S - F.probe_first + 1u;
+    const hipError_t e = probe_launch_fold(F, stream);
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "k_probe_fold launch: %s", hipGetErrorString(e));
+  }
+  return probe_resolve_launch(sum, n_probes, p->mode, p->samples, d_coeff, d_coeff_f, stream);
+}
+
+/* rt_hip_bake_probes_host: a scene of its own on the logical device, one allocation for the probes, the workspace, the outputs and
+ * the counters, the bake on the null stream, the copies, the device's status word.  Everything is owned by this scope. */
+int bake_probes_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_positions,
+                          const double *h_normals, uint64_t n_probes, const RtHipProbeParams *params, int device, double *h_coeff,
+                          float *h_coeff_f, uint32_t *h_status, uint64_t *h_stats)
+{
+  constexpr uint32_t HOST_SLICE = 1u << 21; /* rays a launch: 160 MB of rays, status words and radiance at most */
+  int rc = check_probe(params, n_probes, h_normals != nullptr);
+  if (rc || n_probes == 0)
+    return rc; /* (no probe: nothing to do, on any device or none) */
+  if (!h_positions || !h_coeff)
+    return fail(RT_HIP_EINVAL, "h_positions and h_coeff are required");
+  int phys = -1;
+  rc = physical_device(device, &phys);
+  if (rc)
+    return rc;
+  OwnedScene own;
+  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
+  if (rc)
+    return rc;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  const bool hemisphere = params->mode == RT_HIP_PROBE_HEMISPHERE;
+  const uint32_t bases = probe_bases(params->mode);
+  const uint64_t total = n_probes * (uint64_t)params->samples;
+  StageArena A;
+  const int ws = A.part(ProbeWorkspace(n_probes, bases, std::min<uint64_t>(HOST_SLICE, total)).total);
+  const int positions = A.part(24u * n_probes, h_positions);
+  const int normals = A.part(24u * n_probes, h_normals, nullptr, hemisphere);
+  const int coeff = A.part(24u * bases * n_probes, nullptr, h_coeff);
+  const int coeff_f = A.part(12u * bases * n_probes, nullptr, h_coeff_f, h_coeff_f != nullptr);
+  const int status = A.part(4u * n_probes, nullptr, h_status, h_status != nullptr);
+  const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
+  rc = A.stage();
+  if (rc)
+    return rc;
+  rc = bake_probes_launch(own.scene, A.at<double>(positions), A.at<double>(normals), n_probes, params, HOST_SLICE, A.at<char>(ws), nullptr,
+                          A.at<double>(coeff), A.at<float>(coeff_f), A.at<uint32_t>(status), A.at<uint64_t>(stats), nullptr);
+  if (rc)
+    return rc;
+  rc = A.download();
+  if (rc)
+    return rc;
+  uint32_t flags = 0;
+  rc = status_take(phys, &flags);
+  return rc ? rc : status_to_error(flags);
+}
+
 /* ---- pixel refinement (rt_hip.h, rt_hip_select_pixels / _trace_pixels / _blend_pixels) ---------------------------------------
  * select and blend are image-space calls like the upsampling: arguments checked without a device, then the device that holds the
  * first buffer.  trace_pixels is a radiance query's launch (trace_launch) whose rays the kernel forms itself: the frame's camera
@@ -5289,6 +5480,117 @@ int rt_hip_render_lens_image(const RtHipSphere *spheres, size_t n_spheres, const
 {
   return guarded("rt_hip_render_lens_image", [&] {
     return render_lens_image_impl(spheres, n_spheres, meshes, n_meshes, camera, lens, params, device, h_rgb, h_rgb8, h_stats);
+  });
+}
+
+void rt_hip_probe_defaults(RtHipProbeParams *params)
+{
+  if (!params)
+    return;
+  memset(params, 0, sizeof *params);
+  params->mode = RT_HIP_PROBE_SPHERE;
+  params->samples = 64;
+  params->max_depth = 5;
+}
+
+int rt_hip_probe_rays(const double *d_positions, const double *d_normals, uint64_t n_probes, const RtHipProbeParams *params, uint64_t k_first,
+                      uint64_t n, double *d_rays, void *stream)
+{
+  int rc = check_probe(params, n_probes, d_normals != nullptr);
+  if (rc)
+    return rc;
+  const uint64_t total = n_probes * (uint64_t)params->samples;
+  if (k_first > total || n > total - k_first)
+    return fail(RT_HIP_EINVAL, "rays [%llu, +%llu) exceed the %llu of %llu probes x %d samples", (unsigned long long)k_first,
+                (unsigned long long)n, (unsigned long long)total, (unsigned long long)n_probes, params->samples);
+  if (n > 0xFFFFFFFFull)
+    return fail(RT_HIP_EINVAL, "n = %llu: a call writes fewer than 2^32 rays", (unsigned long long)n);
+  if (n == 0)
+    return RT_HIP_OK;
+  if (!d_positions)
+    return fail(RT_HIP_EINVAL, "d_positions is required");
+  if (!d_rays || (reinterpret_cast<uintptr_t>(d_rays) & 15u))
+    return fail(RT_HIP_EINVAL, "d_rays is required and must be 16-byte aligned");
+  return on_device_of(d_rays, "d_rays", [&] {
+    PtProbeRays A = probe_args(d_positions, d_normals, params);
+    A.k_first = k_first;
+    A.n = (uint32_t)n;
+    A.rays = d_rays;
+    return probe_rays_launch(A, static_cast<hipStream_t>(stream));
+  });
+}
+
+size_t rt_hip_probe_workspace_bytes(uint64_t n_probes, uint32_t mode, uint32_t slice_rays)
+{
+  if ((mode != RT_HIP_PROBE_SPHERE && mode != RT_HIP_PROBE_HEMISPHERE) || slice_rays == 0u || n_probes > 0x100000000ull)
+    return 0;
+  return ProbeWorkspace(n_probes, probe_bases(mode), slice_rays).total;
+}
+
+int rt_hip_bake_probes(const RtHipScene *scene, const double *d_positions, const double *d_normals, uint64_t n_probes,
+                       const RtHipProbeParams *params, uint32_t slice_rays, void *d_workspace, double *d_sum, double *d_coeff, float *d_coeff_f,
+                       uint32_t *d_status, uint64_t *d_stats, void *stream)
+{
+  const int rc = check_probe(params, n_probes, d_normals != nullptr);
+  if (rc)
+    return rc;
+  if (slice_rays == 0u)
+    return fail(RT_HIP_EINVAL, "slice_rays must be >= 1");
+  if (reinterpret_cast<uintptr_t>(d_workspace) & 15u) /* (the slice's rays lie at its start: rt_hip_trace_rays' own rule) */
+    return fail(RT_HIP_EINVAL, "d_workspace must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_sum) & 7u)
+    return fail(RT_HIP_EINVAL, "d_sum must be 8-byte aligned");
+  if (n_probes == 0)
+    return RT_HIP_OK;
+  if (!scene || !d_positions || !d_workspace || !d_coeff)
+    return fail(RT_HIP_EINVAL, "scene, d_positions, d_workspace and d_coeff are required");
+  return guarded("rt_hip_bake_probes", [&] {
+    return bake_probes_launch(scene, d_positions, d_normals, n_probes, params, slice_rays, d_workspace, d_sum, d_coeff, d_coeff_f, d_status,
+                              d_stats, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_hip_probe_resolve(const double *d_sum, uint64_t n_probes, uint32_t mode, int32_t samples, double *d_coeff, float *d_coeff_f, void *stream)
+{
+  if (mode != RT_HIP_PROBE_SPHERE && mode != RT_HIP_PROBE_HEMISPHERE)
+    return fail(RT_HIP_EINVAL, "mode %u is neither RT_HIP_PROBE_SPHERE nor RT_HIP_PROBE_HEMISPHERE", mode);
+  if (samples < 1)
+    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", samples);
+  if (n_probes > 0x100000000ull)
+    return fail(RT_HIP_EINVAL, "n_probes = %llu exceeds 2^32", (unsigned long long)n_probes);
+  if (n_probes == 0)
+    return RT_HIP_OK;
+  if (!d_sum || !d_coeff)
+    return fail(RT_HIP_EINVAL, "d_sum and d_coeff are required");
+  return on_device_of(d_sum, "d_sum",
+                      [&] { return probe_resolve_launch(d_sum, n_probes, mode, samples, d_coeff, d_coeff_f, static_cast<hipStream_t>(stream)); });
+}
+
+int rt_hip_probe_irradiance(const double *d_coeff, uint64_t n_probes, const uint32_t *d_index, const double *d_normals, uint64_t m,
+                            double *d_irradiance, void *stream)
+{
+  if (n_probes > 0x100000000ull || m > 0xFFFFFFFFull)
+    return fail(RT_HIP_EINVAL, "n_probes = %llu, m = %llu: at most 2^32 probes and fewer than 2^32 entries", (unsigned long long)n_probes,
+                (unsigned long long)m);
+  if (m == 0)
+    return RT_HIP_OK;
+  if ((!d_coeff && n_probes != 0) || !d_index || !d_normals || !d_irradiance)
+    return fail(RT_HIP_EINVAL, "d_coeff, d_index, d_normals and d_irradiance are required");
+  return on_device_of(d_irradiance, "d_irradiance", [&] {
+    const hipError_t e = probe_launch_irradiance(d_coeff, n_probes, d_index, d_normals, m, d_irradiance, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess)
+      return fail(RT_HIP_ERUNTIME, "k_probe_irradiance launch: %s", hipGetErrorString(e));
+    return (int)RT_HIP_OK;
+  });
+}
+
+int rt_hip_bake_probes_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const double *h_positions,
+                            const double *h_normals, uint64_t n_probes, const RtHipProbeParams *params, int device, double *h_coeff,
+                            float *h_coeff_f, uint32_t *h_status, uint64_t *h_stats)
+{
+  return guarded("rt_hip_bake_probes_host", [&] {
+    return bake_probes_host_impl(spheres, n_spheres, meshes, n_meshes, h_positions, h_normals, n_probes, params, device, h_coeff, h_coeff_f,
+                                 h_status, h_stats);
   });
 }
 

@@ -24,6 +24,9 @@
  *   -q <x,y>     query instead of rendering: what the ray through the centre of pixel (x, y) of the chosen scene and size hits
  *                (rt_hip_query_rays_host with u = (x + 0.5) / (w - 1), v = (y + 0.5) / (h - 1)): status, object id,
  *                primitive, t, point and normal, one line each.  Nothing is rendered or written.
+ *   -k <x,y,z>   a light probe instead of rendering: the 27 SH9 radiance coefficients of the chosen scene at that point
+ *                (rt_hip_bake_probes_host, RT_HIP_PROBE_SPHERE, -s rays, -d and -r as given): status and nine lines of three
+ *                channels.  Nothing is rendered or written.
  *   -u <f>       preview by guided upsampling, integer f >= 2 (upsample_frame, rt_hip_upsample's defaults, one GPU): the frame is
  *                rendered at ceil(w / f) x ceil(h / f) under the full size's camera (with -n: and denoised there), the first-hit
  *                buffers are rendered at both sizes, and the low frame is brought to w x h under the full-size buffers.  The PNG
@@ -122,6 +125,8 @@ typedef struct
   double qx, qy;    /* -q: the pixel */
   int lens;         /* -l given */
   double lens_aperture, lens_focus; /* -l: the thin lens' aperture radius and focus distance */
+  int probe;        /* -k given */
+  double probe_at[3]; /* -k: the light probe's position */
   uint64_t seed;
 } Args;
 
@@ -138,7 +143,8 @@ static void usage(const char *prog)
           "          [-q <x,y: print what the ray through the centre of that pixel hits; nothing is rendered>]\n"
           "          [-u <factor >= 2: render at 1/factor of the size, upsample under full-size first-hit buffers; <name>.low.png>]\n"
           "          [-l <aperture,focus: depth of field from a thin lens of that radius, sharp at that distance; one GPU, trace_path,\n"
-          "               not with -p, -e or -u; aperture 0 is the pinhole frame>]\n",
+          "               not with -p, -e or -u; aperture 0 is the pinhole frame>]\n"
+          "          [-k <x,y,z: print the 27 SH9 coefficients of a light probe there, -s rays, -d and -r as given; nothing is rendered>]\n",
           prog);
 }
 
@@ -203,6 +209,20 @@ static int parse_args(int argc, char **argv, Args *a)
       a->lens = 1;
       break;
     }
+    case 'k':
+    {
+      const char *at = val;
+      for (int c = 0; c < 3; c++)
+      {
+        char *end = NULL;
+        a->probe_at[c] = strtod(at, &end);
+        if (end == at || *end != (c < 2 ? ',' : '\0') || !isfinite(a->probe_at[c]))
+          return -1;
+        at = end + 1;
+      }
+      a->probe = 1;
+      break;
+    }
     case 'u':
       a->upsample = atoi(val);
       if (a->upsample < 2 || val[0] < '0' || val[0] > '9')
@@ -219,6 +239,21 @@ static int parse_args(int argc, char **argv, Args *a)
   return 0;
 }
 
+/* the scene's meshes as the shim takes them; the caller frees */
+static RtHipMesh *hip_meshes_of(const RtSceneInfo *info, const MeshObject *meshes)
+{
+  RtHipMesh *hm = (RtHipMesh *)calloc(info->n_meshes ? info->n_meshes : 1, sizeof *hm);
+  for (size_t m = 0; hm && m < info->n_meshes; m++)
+  {
+    hm[m].flags = meshes[m].flags;
+    memcpy(hm[m].color, &meshes[m].color, sizeof hm[m].color);
+    memcpy(hm[m].emission, &meshes[m].emission, sizeof hm[m].emission);
+    hm[m].num_triangles = meshes[m].mesh.num_triangles;
+    hm[m].vertices = (const RtHipVertex *)meshes[m].mesh.vertices;
+  }
+  return hm;
+}
+
 /* -q: one camera ray through the shim's query entry point for C hosts */
 static int query_pixel(const Args *a, const RtSceneInfo *info, const Object *scene, const MeshObject *meshes, const Camera *camera)
 {
@@ -227,17 +262,9 @@ static int query_pixel(const Args *a, const RtSceneInfo *info, const Object *sce
     fprintf(stderr, "-q %g,%g: outside the %d x %d image\n", a->qx, a->qy, a->options.width, a->options.height);
     return EXIT_FAILURE;
   }
-  RtHipMesh *hm = (RtHipMesh *)calloc(info->n_meshes ? info->n_meshes : 1, sizeof *hm);
+  RtHipMesh *hm = hip_meshes_of(info, meshes);
   if (!hm)
     return EXIT_FAILURE;
-  for (size_t m = 0; m < info->n_meshes; m++)
-  {
-    hm[m].flags = meshes[m].flags;
-    memcpy(hm[m].color, &meshes[m].color, sizeof hm[m].color);
-    memcpy(hm[m].emission, &meshes[m].emission, sizeof hm[m].emission);
-    hm[m].num_triangles = meshes[m].mesh.num_triangles;
-    hm[m].vertices = (const RtHipVertex *)meshes[m].mesh.vertices;
-  }
   const double uv[2] = {(a->qx + 0.5) / ((double)a->options.width - 1.0), (a->qy + 0.5) / ((double)a->options.height - 1.0)};
   const double *c = &camera->position.x;
   RtHipQueryParams p;
@@ -268,6 +295,36 @@ static int query_pixel(const Args *a, const RtSceneInfo *info, const Object *sce
     printf("point = %.17g %.17g %.17g\n", point[0], point[1], point[2]);
     printf("normal = %.17g %.17g %.17g\n", normal[0], normal[1], normal[2]);
   }
+  return EXIT_SUCCESS;
+}
+
+/* -k: one light probe through the shim's bake entry point for C hosts */
+static int probe_point(const Args *a, const RtSceneInfo *info, const Object *scene, const MeshObject *meshes)
+{
+  RtHipMesh *hm = hip_meshes_of(info, meshes);
+  if (!hm)
+    return EXIT_FAILURE;
+  const double *c = a->probe_at;
+  RtHipProbeParams p;
+  rt_hip_probe_defaults(&p);
+  p.samples = a->options.samples;
+  p.max_depth = a->depth;
+  p.seed = a->seed;
+  p.origin_radius = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+  double coeff[27];
+  uint32_t status = 0;
+  const int rc = rt_hip_bake_probes_host((const RtHipSphere *)scene, info->n_objects, hm, info->n_meshes, c, NULL, 1, &p, 0, coeff, NULL, &status, NULL);
+  free(hm);
+  if (rc)
+  {
+    fprintf(stderr, "probe: GPU path failed (%d): %s\n", rc, rt_hip_last_error());
+    return EXIT_FAILURE;
+  }
+  printf("probe = %.17g,%.17g,%.17g\n", c[0], c[1], c[2]);
+  printf("samples = %d\n", p.samples);
+  printf("status = %u\n", status);
+  for (int j = 0; j < 9; j++)
+    printf("sh[%d] = %.17g %.17g %.17g\n", j, coeff[3 * j], coeff[3 * j + 1], coeff[3 * j + 2]);
   return EXIT_SUCCESS;
 }
 
@@ -410,6 +467,8 @@ int main(int argc, char **argv)
 
   if (a.query)
     return query_pixel(&a, &info, scene, meshes, &camera);
+  if (a.probe)
+    return probe_point(&a, &info, scene, meshes);
 
   rt_set_max_depth(a.depth);
   rt_set_seed(a.seed);

@@ -148,6 +148,15 @@ class RtHipLens(C.Structure):  # rt_hip.h: a thin lens (rt_hip_lens_defaults), 2
     _fields_ = [("aperture_radius", C.c_double), ("focus_distance", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+PROBE_SPHERE, PROBE_HEMISPHERE = 0, 1   # RtHipProbeParams.mode
+PROBE_BASES = {PROBE_SPHERE: 9, PROBE_HEMISPHERE: 1}
+
+
+class RtHipProbeParams(C.Structure):  # rt_hip.h: a light-probe bake (rt_hip_probe_defaults), 48 B
+    _fields_ = [("mode", C.c_uint32), ("flags", C.c_uint32), ("samples", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint64),
+                ("bias", C.c_double), ("origin_radius", C.c_double), ("reserved", C.c_uint64)]
+
+
 class RtHipPixelParams(C.Structure):  # rt_hip.h: a pixel refinement's trace (rt_hip_pixel_defaults), 32 B
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("sample_first", C.c_int32),
                 ("max_depth", C.c_int32), ("integrator", C.c_uint32), ("seed", C.c_uint64)]
@@ -298,6 +307,16 @@ SHIM_SYMBOLS = {
     "rt_hip_lens_resolve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_render_lens_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.POINTER(Camera),
                                            C.POINTER(RtHipLens), C.POINTER(RtHipParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_defaults": (None, [C.POINTER(RtHipProbeParams)]),
+    "rt_hip_probe_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RtHipProbeParams), C.c_uint64, C.c_uint64, C.c_void_p,
+                                    C.c_void_p]),
+    "rt_hip_probe_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "rt_hip_bake_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RtHipProbeParams), C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_resolve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_irradiance": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rt_hip_bake_probes_host": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
+                                          C.POINTER(RtHipProbeParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_denoise_defaults": (None, [C.POINTER(RtHipDenoiseParams)]),
     "rt_hip_denoise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rt_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_void_p,
@@ -471,6 +490,16 @@ def lens_params(aperture, focus):
     load_shim().rt_hip_lens_defaults(C.byref(lens))
     lens.aperture_radius, lens.focus_distance = aperture, focus
     return lens
+
+
+def probe_params(mode, samples, seed, max_depth=None, bias=0.0, origin_radius=0.0):
+    """rt_hip_probe_defaults() with the given fields replaced (max_depth None: the default)"""
+    p = RtHipProbeParams()
+    load_shim().rt_hip_probe_defaults(C.byref(p))
+    p.mode, p.samples, p.seed, p.bias, p.origin_radius = mode, samples, seed, bias, origin_radius
+    if max_depth is not None:
+        p.max_depth = max_depth
+    return p
 
 
 def reproject_params(max_history=None, depth_tol=None, normal_min=None):

@@ -548,6 +548,50 @@ class GpuScene:
         d = [pos[k] - (llc[k] + (hor[k] * u + ver[k] * v)) for k in range(3)]
         return float(out["t"].cpu()[0]) / ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) ** 0.5
 
+    def _bake(self, mode, positions, normals, samples, seed, bias, max_depth, origin_radius, slice_rays, stats):
+        """rt_hip_bake_probes on torch's current stream -> dict(coeff float64 [N, bases, 3], coeff_f float32, sum float64, status int32
+        [N], stats int64 [4])"""
+        dev = torch.device("cuda", self.device)
+        pos = torch.as_tensor(positions, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+        nrm = None if normals is None else torch.as_tensor(normals, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+        n, bases = pos.shape[0], abi.PROBE_BASES[mode]
+        if nrm is not None and nrm.shape[0] != n:
+            raise ValueError(f"{nrm.shape[0]} normals for {n} probes")
+        if origin_radius is None:
+            origin_radius = _origin_radius(pos, nrm, bias)
+        p = abi.probe_params(mode, samples, seed, self.scene.max_depth if max_depth is None else max_depth, bias, origin_radius)
+        total = max(n * samples, 1)
+        slice_rays = total if slice_rays is None else slice_rays
+        ws = torch.empty(max(self.shim.rt_hip_probe_workspace_bytes(n, mode, max(min(slice_rays, total), 1)), 256), dtype=torch.uint8, device=dev)
+        out = dict(coeff=torch.empty((n, bases, 3), dtype=torch.float64, device=dev),
+                   coeff_f=torch.empty((n, bases, 3), dtype=torch.float32, device=dev),
+                   sum=torch.empty((n, bases, 3), dtype=torch.float64, device=dev), status=torch.empty(n, dtype=torch.int32, device=dev),
+                   stats=torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev) if stats is None else stats)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._probe_buffers = (ws, pos, nrm)   # keep alive until the stream has used them
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+        _check(self.shim.rt_hip_bake_probes(self.handle, ptr(pos), ptr(nrm), n, C.byref(p), slice_rays, C.c_void_p(ws.data_ptr()), ptr(out["sum"]),
+                                            ptr(out["coeff"]), ptr(out["coeff_f"]), ptr(out["status"]), C.c_void_p(out["stats"].data_ptr()),
+                                            C.c_void_p(stream)), "rt_hip_bake_probes")
+        return out
+
+    def bake_probes(self, positions, samples, seed, max_depth=None, origin_radius=None, slice_rays=None, stats=None, details=False):
+        """Light probes (rt_hip.h, rt_hip_bake_probes, RT_HIP_PROBE_SPHERE): the SH9 coefficients of the radiance arriving at
+        positions [N, 3] from `samples` uniform directions a probe, traced by the radiance query; asynchronous on torch's current
+        stream -> float64 [N, 9, 3] on the device (details: the dict of coeff, coeff_f float32, sum, status int32 [N] -- 2 where a
+        ray of the probe was invalid --, stats).  origin_radius None: the largest finite |position| (synchronises); slice_rays: rays
+        per launch (None: all); no output bit depends on either."""
+        out = self._bake(abi.PROBE_SPHERE, positions, None, samples, seed, 0.0, max_depth, origin_radius, slice_rays, stats)
+        return out if details else out["coeff"]
+
+    def bake_irradiance(self, positions, normals, samples, seed, bias=0.0, max_depth=None, origin_radius=None, slice_rays=None, stats=None,
+                        details=False):
+        """Irradiance at surface points (rt_hip.h, rt_hip_bake_probes, RT_HIP_PROBE_HEMISPHERE): E = 2 pi x the mean of radiance x
+        cosine over `samples` uniform directions of the hemisphere about normals [N, 3] (used as given), rays starting at position +
+        normal * bias -> float64 [N, 3] on the device (details: as bake_probes, the arrays [N, 1, 3])"""
+        out = self._bake(abi.PROBE_HEMISPHERE, positions, normals, samples, seed, bias, max_depth, origin_radius, slice_rays, stats)
+        return out if details else out["coeff"].reshape(-1, 3)
+
     def render_panorama(self, width, height, origin, samples, seed, max_depth=None):
         """An equirectangular view from `origin` (scene.panorama_rays: no Camera expresses it), `samples` paths per pixel, pixel
         k = y * width + x on the stream (seed, k, s) -> (float64 [height, width, 3] linear radiance on the device, stats)"""
@@ -1490,3 +1534,95 @@ def render_lens_host(scene, aperture, focus, samples, seed, camera=None, max_dep
     _check(shim.rt_hip_render_lens_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(cam), C.byref(lens), C.byref(p),
                                          device, img.ctypes.data, img8.ctypes.data, stats), "rt_hip_render_lens_image")
     return img, img8, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
+
+
+def _origin_radius(pos, nrm, bias):
+    """an origin_radius for probes at pos (+ nrm * bias): the largest finite distance from the world's origin (synchronises)"""
+    r = torch.linalg.vector_norm(pos, dim=1)
+    r = r[torch.isfinite(r)]
+    out = float(r.max()) if r.numel() else 0.0
+    if nrm is not None and bias:
+        m = torch.linalg.vector_norm(nrm, dim=1)
+        m = m[torch.isfinite(m)]
+        out += bias * (float(m.max()) if m.numel() else 0.0)
+    return out * (1.0 + 2.0 ** -40)
+
+
+def probe_rays(positions, samples, seed, normals=None, bias=0.0, k_first=0, n=None, device=0):
+    """The probe rays of indices [k_first, k_first + n) (rt_hip.h, rt_hip_probe_rays; n None: to the end), ray k = probe * samples
+    + sample; normals [N, 3]: hemisphere probes, rays flipped to the normal's side and started at position + normal * bias ->
+    a device tensor [n, 6] float64 (origin, direction), asynchronous on torch's current stream"""
+    shim = abi.load_shim()
+    dev = torch.device("cuda", device)
+    pos = torch.as_tensor(positions, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+    nrm = None if normals is None else torch.as_tensor(normals, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+    n = pos.shape[0] * samples - k_first if n is None else n
+    rays = torch.empty((max(n, 0), 6), dtype=torch.float64, device=dev)
+    p = abi.probe_params(abi.PROBE_SPHERE if nrm is None else abi.PROBE_HEMISPHERE, samples, seed, bias=bias)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_probe_rays(C.c_void_p(pos.data_ptr() if pos.numel() else None), C.c_void_p(nrm.data_ptr() if nrm is not None else None),
+                                  pos.shape[0], C.byref(p), k_first, n, C.c_void_p(rays.data_ptr() if n > 0 else None), C.c_void_p(stream)),
+           "rt_hip_probe_rays")
+    return rays
+
+
+def probe_resolve(total, samples):
+    """A bake's resolve alone (rt_hip.h, rt_hip_probe_resolve): total float64 [N, 9, 3] (sphere probes) or [N, 1, 3] (hemisphere) on
+    a device -> (coeff float64, coeff_f float32) of that shape; asynchronous on torch's current stream"""
+    shim = abi.load_shim()
+    total = total.contiguous()
+    n, bases, _ = total.shape
+    mode = {9: abi.PROBE_SPHERE, 1: abi.PROBE_HEMISPHERE}[bases]
+    coeff, coeff_f = torch.empty_like(total), torch.empty(total.shape, dtype=torch.float32, device=total.device)
+    stream = torch.cuda.current_stream(total.device).cuda_stream
+    _check(shim.rt_hip_probe_resolve(C.c_void_p(total.data_ptr()), n, mode, samples, C.c_void_p(coeff.data_ptr()), C.c_void_p(coeff_f.data_ptr()),
+                                     C.c_void_p(stream)), "rt_hip_probe_resolve")
+    return coeff, coeff_f
+
+
+def probe_irradiance(sh, index, normals):
+    """Irradiance from SH9 probes (rt_hip.h, rt_hip_probe_irradiance): sh float64 [N, 9, 3] on a device, index [m] (which probe),
+    normals [m, 3] (used as given) -> float64 [m, 3]; an index >= N gives NaN; asynchronous on torch's current stream"""
+    shim = abi.load_shim()
+    sh = sh.contiguous()
+    dev = sh.device
+    idx = (torch.as_tensor(index, device=dev).to(torch.int64) & 0xFFFFFFFF).to(torch.uint32).reshape(-1).contiguous()
+    nrm = torch.as_tensor(normals, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+    m = nrm.shape[0]
+    if idx.numel() != m:
+        raise ValueError(f"{idx.numel()} indices for {m} normals")
+    out = torch.empty((m, 3), dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_probe_irradiance(C.c_void_p(sh.data_ptr() if sh.numel() else None), sh.shape[0], C.c_void_p(idx.data_ptr() if m else None),
+                                        C.c_void_p(nrm.data_ptr() if m else None), m, C.c_void_p(out.data_ptr() if m else None),
+                                        C.c_void_p(stream)), "rt_hip_probe_irradiance")
+    return out
+
+
+def bake_probes_host(scene, positions, samples, seed, normals=None, bias=0.0, max_depth=None, origin_radius=None, device=0):
+    """rt_hip_bake_probes_host(): the C hosts' entry point (its own scene on logical device `device`, synchronous); normals None:
+    sphere probes -> (coeff float64 [N, 9, 3], coeff_f float32, status uint32 [N], stats dict); with normals: hemisphere probes,
+    the arrays [N, 1, 3]"""
+    import numpy as np
+    shim = abi.load_shim()
+    pos = np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1, 3))
+    nrm = None if normals is None else np.ascontiguousarray(np.asarray(normals, dtype=np.float64).reshape(-1, 3))
+    mode = abi.PROBE_SPHERE if nrm is None else abi.PROBE_HEMISPHERE
+    if origin_radius is None:
+        r = np.sqrt((pos * pos).sum(axis=1))
+        origin_radius = float(r[np.isfinite(r)].max(initial=0.0))
+        if nrm is not None:
+            m = np.sqrt((nrm * nrm).sum(axis=1))
+            origin_radius += bias * float(m[np.isfinite(m)].max(initial=0.0))
+        origin_radius *= 1.0 + 2.0 ** -40
+    p = abi.probe_params(mode, samples, seed, scene.max_depth if max_depth is None else max_depth, bias, origin_radius)
+    n, bases = pos.shape[0], abi.PROBE_BASES[mode]
+    coeff = np.zeros((n, bases, 3), dtype=np.float64)
+    coeff_f = np.zeros((n, bases, 3), dtype=np.float32)
+    status = np.zeros(n, dtype=np.uint32)
+    stats = (C.c_uint64 * abi.NSTATS)()
+    meshes = scene.hip_meshes()
+    _check(shim.rt_hip_bake_probes_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, pos.ctypes.data, nrm.ctypes.data if nrm is not None else None,
+                                        n, C.byref(p), device, coeff.ctypes.data, coeff_f.ctypes.data, status.ctypes.data, stats),
+           "rt_hip_bake_probes_host")
+    return coeff, coeff_f, status, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
