@@ -54,6 +54,12 @@ int fail(int code, const char *fmt, ...)
   return code;
 }
 
+/* what a kernel launch gave as the call's answer: RT_HIP_OK, or RT_HIP_ERUNTIME naming the kernel */
+int launched(hipError_t e, const char *kernel)
+{
+  return e == hipSuccess ? (int)RT_HIP_OK : fail(RT_HIP_ERUNTIME, "%s launch: %s", kernel, hipGetErrorString(e));
+}
+
 #define HIP_TRY(expr)                                                                               \
   do                                                                                                \
   {                                                                                                 \
@@ -2584,9 +2590,10 @@ int device_of(const void *ptr, const char *what, int *device)
   return RT_HIP_OK;
 }
 
-/* The two prologues of the calls that have no scene: `body` runs with a device current -- the one that holds `ptr` (a
- * device-pointer form), or logical device `device` of the device map (a host-array form; body(phys) gets the HIP device) -- and
- * the previous device comes back when it returns.  A lookup that fails is the call's answer and `body` does not run. */
+/* The prologues of the calls that are given no scene: `body` runs with a device current -- the one that holds `ptr` (a
+ * device-pointer form), or logical device `device` of the device map (a host-array form; body(phys) gets the HIP device; a host
+ * form that is given a scene's primitives gets body(scene, phys): a scene of the call's own on that device, destroyed on return) --
+ * and the previous device comes back when it returns.  A lookup or a scene that fails is the call's answer and `body` does not run. */
 template <class F>
 int on_device_of(const void *ptr, const char *what, F &&body)
 {
@@ -2609,12 +2616,24 @@ int on_logical_device(int device, F &&body)
   return body(phys);
 }
 
-/* rt_hip_render_aov_image on its scene: compact buffers for the requested outputs, one launch over every tile, the scatter, the
- * copies.  Synchronous on the null stream. */
+template <class F>
+int with_owned_scene(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, int device, F &&body)
+{
+  int phys = -1;
+  if (const int rc = physical_device(device, &phys))
+    return rc;
+  OwnedScene own;
+  if (const int rc = own.create(spheres, n_spheres, meshes, n_meshes, phys))
+    return rc;
+  DeviceScope scope(phys);
+  HIP_TRY(scope.status);
+  return body(own.scene, phys);
+}
+
+/* rt_hip_render_aov_image on its scene, the scene's device current: compact buffers for the requested outputs, one launch over
+ * every tile, the scatter, the copies.  Synchronous on the null stream. */
 int aov_image_of(const RtHipScene *scene, const RtHipCamera *camera, const RtHipParams *params, const RtHipAov *h_image)
 {
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
   RtHipParams p = *params;
   whole_image(p);
   const size_t tile_px = (size_t)p.tile_count * PT_TILE_PIXELS, img_px = (size_t)p.width * p.height;
@@ -2647,16 +2666,10 @@ int render_aov_image_impl(const RtHipSphere *spheres, size_t n_spheres, const Rt
     return fail(RT_HIP_EINVAL, "camera and params are required");
   if (!aov_any(h_image))
     return fail(RT_HIP_EINVAL, "h_image: at least one output array is required");
-  int rc = check_params(params);
-  if (rc)
+  if (const int rc = check_params(params))
     return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  OwnedScene own;
-  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
-  return rc ? rc : aov_image_of(own.scene, camera, params, h_image);
+  return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device,
+                          [&](const RtHipScene *scene, int) { return aov_image_of(scene, camera, params, h_image); });
 }
 
 /* ---- the denoiser (rt_hip.h, rt_hip_denoise_*) ------------------------------------------------------------------------------
@@ -2724,10 +2737,7 @@ int denoise_launch(const float *rgb, const RtHipAov *aov, int32_t width, int32_t
   D.object_edges = (p->flags & RT_HIP_DENOISE_OBJECT_EDGES) ? 1u : 0u;
   D.k = p->normal_power_log2;
   D.sigma_z = p->sigma_depth;
-  const hipError_t e = pt_launch_denoise(D, p->iterations, p->sigma_color, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_denoise launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return launched(pt_launch_denoise(D, p->iterations, p->sigma_color, stream), "pt_denoise");
 }
 
 int denoise_image_impl(const float *h_rgb, const RtHipAov *h_aov, int32_t width, int32_t height, const RtHipDenoiseParams *params,
@@ -2874,10 +2884,8 @@ int reproject_launch(const float *rgb, const RtHipAov *aov, const RtHipCamera *c
   R.max_history = p->max_history;
   R.depth_tol = p->depth_tol;
   R.normal_min = p->normal_min;
-  const hipError_t e = prev_points ? pt_launch_reproject_points(R, prev_points, stream) : pt_launch_reproject(R, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", prev_points ? "pt_reproject_points" : "pt_reproject", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return prev_points ? launched(pt_launch_reproject_points(R, prev_points, stream), "pt_reproject_points")
+                     : launched(pt_launch_reproject(R, stream), "pt_reproject");
 }
 
 /* rt_hip_reproject_points' own rule, after check_reproject's: the previous points (3 doubles per pixel) overlap no output */
@@ -2982,23 +2990,16 @@ int prev_points_launch(const RtHipHits *hits, uint64_t n, const double *position
 {
   if (n == 0)
     return RT_HIP_OK;
-  hipError_t e;
   if (spheres)
   {
     const PtPrevPointsMoved A = {.status = hits->status, .prim = hits->prim, .object = hits->object, .bary = hits->bary, .point = hits->point,
                                  .positions = positions, .spheres_prev = spheres->prev, .spheres_cur = spheres->cur, .out = points, .n = n,
                                  .n_triangles = n_triangles, .n_spheres = spheres->n, .spheres_static = spheres->none_given ? 1u : 0u};
-    e = pt_launch_prev_points_moved(A, stream);
+    return launched(pt_launch_prev_points_moved(A, stream), "pt_prev_points_moved");
   }
-  else
-  {
-    const PtPrevPoints A = {.status = hits->status, .prim = hits->prim, .bary = hits->bary, .point = hits->point, .positions = positions,
-                            .out = points, .n = n, .n_triangles = n_triangles};
-    e = pt_launch_prev_points(A, stream);
-  }
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", spheres ? "pt_prev_points_moved" : "pt_prev_points", hipGetErrorString(e));
-  return RT_HIP_OK;
+  const PtPrevPoints A = {.status = hits->status, .prim = hits->prim, .bary = hits->bary, .point = hits->point, .positions = positions,
+                          .out = points, .n = n, .n_triangles = n_triangles};
+  return launched(pt_launch_prev_points(A, stream), "pt_prev_points");
 }
 
 /* the device-pointer form: no entry returns before a device is looked for */
@@ -3118,10 +3119,7 @@ int upsample_launch(const float *low_rgb, const RtHipAov *low_aov, int32_t low_w
   U.height = height;
   U.normal_power_log2 = p->normal_power_log2;
   U.sigma_depth = p->sigma_depth;
-  const hipError_t e = pt_launch_upsample(U, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_upsample launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return launched(pt_launch_upsample(U, stream), "pt_upsample");
 }
 
 int upsample_image_impl(const float *h_low_rgb, const RtHipAov *h_low_aov, int32_t low_width, int32_t low_height, const RtHipAov *h_aov,
@@ -3225,9 +3223,7 @@ int launch_with_tables(const RtHipScene *scene, PtLaunch &L, hipStream_t stream,
     return rc;
   const hipError_t e = launch();
   release_tables(scene, slot, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "%s launch: %s", kernel, hipGetErrorString(e));
-  return RT_HIP_OK;
+  return launched(e, kernel);
 }
 
 int query_launch(const RtHipScene *scene, const double *d_rays, const double *d_t_max, uint64_t n, const RtHipQueryParams *p,
@@ -3253,33 +3249,28 @@ int query_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtH
   int rc = check_query(h_rays, false, n, params, h_hits);
   if (rc)
     return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
   if (n == 0)
-    return RT_HIP_OK;
-  OwnedScene own;
-  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
-  if (rc)
-    return rc;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  void *host[8] = {h_hits->status, h_hits->t, h_hits->object, h_hits->prim, h_hits->point, h_hits->normal, h_hits->bary, h_hits->ray};
-  const size_t bytes_per_ray[8] = {4, 8, 4, 4, 24, 24, 16, 48};
-  StageArena A;
-  const int rays = A.part((params->source == RT_HIP_RAYS_CAMERA_UV ? 16u : 48u) * n, h_rays);
-  const int t_max = A.part(8u * n, h_t_max, nullptr, h_t_max != nullptr);
-  int out[8];
-  for (int k = 0; k < 8; k++)
-    out[k] = A.part(bytes_per_ray[k] * n, nullptr, host[k], host[k] != nullptr);
-  rc = A.stage();
-  if (rc)
-    return rc;
-  const RtHipHits d_hits = {A.at<uint32_t>(out[0]), A.at<double>(out[1]), A.at<uint32_t>(out[2]), A.at<uint32_t>(out[3]),
-                            A.at<double>(out[4]),   A.at<double>(out[5]), A.at<double>(out[6]),   A.at<double>(out[7])};
-  rc = query_launch(own.scene, A.at<double>(rays), A.at<double>(t_max), n, params, &d_hits, nullptr);
-  return rc ? rc : A.download();
+  { /* (the device is looked up before an empty query returns) */
+    int phys = -1;
+    return physical_device(device, &phys);
+  }
+  return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device, [&](const RtHipScene *scene, int) {
+    void *host[8] = {h_hits->status, h_hits->t, h_hits->object, h_hits->prim, h_hits->point, h_hits->normal, h_hits->bary, h_hits->ray};
+    const size_t bytes_per_ray[8] = {4, 8, 4, 4, 24, 24, 16, 48};
+    StageArena A;
+    const int rays = A.part((params->source == RT_HIP_RAYS_CAMERA_UV ? 16u : 48u) * n, h_rays);
+    const int t_max = A.part(8u * n, h_t_max, nullptr, h_t_max != nullptr);
+    int out[8];
+    for (int k = 0; k < 8; k++)
+      out[k] = A.part(bytes_per_ray[k] * n, nullptr, host[k], host[k] != nullptr);
+    rc = A.stage();
+    if (rc)
+      return rc;
+    const RtHipHits d_hits = {A.at<uint32_t>(out[0]), A.at<double>(out[1]), A.at<uint32_t>(out[2]), A.at<uint32_t>(out[3]),
+                              A.at<double>(out[4]),   A.at<double>(out[5]), A.at<double>(out[6]),   A.at<double>(out[7])};
+    rc = query_launch(scene, A.at<double>(rays), A.at<double>(t_max), n, params, &d_hits, nullptr);
+    return rc ? rc : A.download();
+  });
 }
 
 /* ---- radiance queries (rt_hip.h, rt_hip_trace_*) ------------------------------------------------------------------------------
@@ -3293,6 +3284,31 @@ bool radiance_any(const RtHipRadiance *o)
   return o && (o->status || o->radiance || o->samples || o->paths || o->casts || o->ray);
 }
 
+/* What every form that traces paths refuses in its integrator, samples and max_depth, in that order; `what` names the form.  A
+ * form that checks something else between them (a pixel refinement, a bake) calls the parts. */
+int check_integrator(uint32_t integrator, const char *what)
+{
+  if (integrator != RT_HIP_TRACE_PATH)
+    return fail(RT_HIP_EINVAL, "integrator %u: %s traces paths (RT_HIP_TRACE_PATH) only", integrator, what);
+  return RT_HIP_OK;
+}
+
+int check_max_depth(int32_t max_depth)
+{
+  if (max_depth < 0 || max_depth > 1000000)
+    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  return RT_HIP_OK;
+}
+
+int check_path_fields(uint32_t integrator, int32_t samples, int32_t max_depth, const char *what)
+{
+  if (const int rc = check_integrator(integrator, what))
+    return rc;
+  if (samples < 1)
+    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", samples);
+  return check_max_depth(max_depth);
+}
+
 /* the arguments of a radiance query that need no device: RT_HIP_EINVAL, or RT_HIP_OK */
 int check_trace(const void *rays, bool device_rays, uint64_t n, const RtHipTraceParams *p, const RtHipRadiance *out)
 {
@@ -3300,12 +3316,8 @@ int check_trace(const void *rays, bool device_rays, uint64_t n, const RtHipTrace
     return fail(RT_HIP_EINVAL, "params is required");
   if (!radiance_any(out))
     return fail(RT_HIP_EINVAL, "radiance: at least one output array is required");
-  if (p->integrator != RT_HIP_TRACE_PATH)
-    return fail(RT_HIP_EINVAL, "integrator %u: a radiance query traces paths (RT_HIP_TRACE_PATH) only", p->integrator);
-  if (p->samples < 1)
-    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", p->samples);
-  if (p->max_depth < 0 || p->max_depth > 1000000)
-    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  if (const int rc = check_path_fields(p->integrator, p->samples, p->max_depth, "a radiance query"))
+    return rc;
   if (n > 0xFFFFFFFFull || (uint64_t)p->index_first + n > 0x100000000ull)
     return fail(RT_HIP_EINVAL, "n = %llu, index_first = %u: a radiance query takes fewer than 2^32 rays with stream indices below 2^32",
                 (unsigned long long)n, p->index_first);
@@ -3372,30 +3384,126 @@ int trace_rays_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtH
   int rc = check_trace(h_rays, false, n, params, h_out);
   if (rc || n == 0)
     return rc; /* (no ray: nothing to do, on any device or none) */
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  OwnedScene own;
-  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
-  if (rc)
-    return rc;
-  DeviceScope scope(phys);
+  return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device, [&](const RtHipScene *scene, int) {
+    StageArena A;
+    const int rays = A.part((params->source == RT_HIP_RAYS_CAMERA_UV ? 16u : 48u) * n, h_rays);
+    RadianceStage R(A, h_out, n, params->samples, h_stats);
+    rc = A.stage();
+    if (rc)
+      return rc;
+    const RtHipRadiance d_out = R.device(A);
+    rc = trace_launch(scene, A.at<double>(rays), n, params, &d_out, A.at<uint64_t>(R.stats), nullptr);
+    return rc ? rc : R.download(A);
+  });
+}
+
+/* ---- generated-ray jobs: what a lens frame and a probe bake share ---------------------------------------------------------------
+ * A job is `total` ray indices cut into slices of at most `slice`, a slice ending at every multiple of `period` as well.  Per slice,
+ * on one stream and with no host wait: the caller's generator writes the rays of indices [first, first + n), the radiance query as it
+ * stands (trace_launch, one sample a ray, index_first = first) traces them, the caller's fold adds them into the job's sums; after the
+ * last slice the caller's resolve.  The workspace: a slice's rays, status words and radiance, then sum_bytes of sums. */
+struct SliceWorkspace
+{
+  size_t rays, status, radiance, sum, total;
+  SliceWorkspace(uint64_t slice, size_t sum_bytes)
+  {
+    rays = 0;
+    status = rays + stage_align(48u * slice);
+    radiance = status + stage_align(4u * slice);
+    sum = radiance + stage_align(24u * slice);
+    total = sum + stage_align(sum_bytes);
+  }
+};
+
+/* ... as pointers: the sums are the caller's d_sum where it gives one */
+struct SliceBuffers
+{
+  double *rays;
+  uint32_t *status;
+  double *radiance, *sum;
+};
+
+struct SlicedJob
+{
+  double origin_radius; /* trace_launch's, with max_depth and seed */
+  int32_t max_depth;
+  uint64_t seed;
+  uint64_t total, slice, period;
+  size_t sum_bytes;
+  void *d_workspace;
+  double *d_sum;
+  uint64_t *d_stats;
+};
+
+/* The job on `stream`: trace_launch's own refusals (the depth limit, near_R) asked for once, up front; then, with the scene's device
+ * current, the sums cleared, write(B, first, n) and fold(B, first, n) around every slice's trace_launch, and resolve(B).  Each
+ * callable -> RT_HIP_*. */
+template <class Write, class Fold, class Resolve>
+int sliced_trace(const RtHipScene *scene, const SlicedJob &J, hipStream_t stream, Write write, Fold fold, Resolve resolve)
+{
+  RtHipTraceParams T;
+  rt_hip_trace_defaults(&T);
+  T.origin_radius = J.origin_radius;
+  T.samples = 1;
+  T.max_depth = J.max_depth;
+  T.seed = J.seed;
+  {
+    PtLaunch dry;
+    const int rc = pooled_launch_prepare(scene, T.source, nullptr, T.origin_radius, 1, T.max_depth, T.seed, nullptr, dry);
+    if (rc)
+      return rc;
+  }
+  DeviceScope scope(scene->device);
   HIP_TRY(scope.status);
-  StageArena A;
-  const int rays = A.part((params->source == RT_HIP_RAYS_CAMERA_UV ? 16u : 48u) * n, h_rays);
-  RadianceStage R(A, h_out, n, params->samples, h_stats);
-  rc = A.stage();
-  if (rc)
+  const SliceWorkspace W(J.slice, J.sum_bytes);
+  char *const ws = static_cast<char *>(J.d_workspace);
+  const SliceBuffers B = {reinterpret_cast<double *>(ws + W.rays), reinterpret_cast<uint32_t *>(ws + W.status),
+                          reinterpret_cast<double *>(ws + W.radiance), J.d_sum ? J.d_sum : reinterpret_cast<double *>(ws + W.sum)};
+  HIP_TRY(hipMemsetAsync(B.sum, 0, J.sum_bytes, stream));
+  const RtHipRadiance out = {B.status, B.radiance, nullptr, nullptr, nullptr, nullptr};
+  for (uint64_t first = 0, n; first < J.total; first += n)
+  {
+    n = std::min<uint64_t>(J.slice, J.period - first % J.period);
+    int rc = write(B, first, (uint32_t)n);
+    if (rc)
+      return rc;
+    T.index_first = (uint32_t)first;
+    rc = trace_launch(scene, B.rays, n, &T, &out, J.d_stats, stream);
+    if (rc)
+      return rc;
+    rc = fold(B, first, (uint32_t)n);
+    if (rc)
+      return rc;
+  }
+  return resolve(B);
+}
+
+/* rt_hip_render_lens' and rt_hip_bake_probes' rule for the job's buffers (null pointers pass: each call has its own text for them) */
+int check_slice_buffers(const void *d_workspace, const double *d_sum)
+{
+  if (reinterpret_cast<uintptr_t>(d_workspace) & 15u) /* (the slice's rays lie at its start: rt_hip_trace_rays' own rule) */
+    return fail(RT_HIP_EINVAL, "d_workspace must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_sum) & 7u)
+    return fail(RT_HIP_EINVAL, "d_sum must be 8-byte aligned");
+  return RT_HIP_OK;
+}
+
+/* the slice of the host forms, in rays a launch: 160 MB of rays, status words and radiance at most */
+constexpr uint32_t HOST_SLICE = 1u << 21;
+
+/* ... and their end: the copies, then the device's status word as the call's answer */
+int download_then_status(const StageArena &A, int phys)
+{
+  if (const int rc = A.download())
     return rc;
-  const RtHipRadiance d_out = R.device(A);
-  rc = trace_launch(own.scene, A.at<double>(rays), n, params, &d_out, A.at<uint64_t>(R.stats), nullptr);
-  return rc ? rc : R.download(A);
+  uint32_t flags = 0;
+  const int rc = status_take(phys, &flags);
+  return rc ? rc : status_to_error(flags);
 }
 
 /* ---- thin-lens camera (rt_hip.h, rt_hip_lens_* / rt_hip_render_lens*) ---------------------------------------------------------
- * A lens frame is lens rays (lens.hip), the radiance query as it stands (trace_launch) and a per-pixel sum (lens.hip).  The checks
- * need no device; the frame refuses everything it can before its first launch. */
+ * A lens frame is a generated-ray job (above): lens rays (lens.hip), a per-pixel sum (lens.hip), one sample pass of the frame a
+ * period.  The checks need no device; the frame refuses everything it can before its first launch. */
 int check_lens(const RtHipCamera *camera, const RtHipLens *lens, int32_t width, int32_t height)
 {
   if (!camera || !lens)
@@ -3440,36 +3548,23 @@ PtLensRays lens_args(const RtHipCamera *camera, const RtHipLens *lens, int32_t w
   return A;
 }
 
-/* the parts of a lens frame's workspace: a slice's rays, status words and radiance, then the frame's sums */
-struct LensWorkspace
+/* a lens frame's workspace: slices never exceed the frame, the sums are three doubles a pixel */
+SliceWorkspace lens_workspace(uint64_t n_pixels, uint64_t slice_pixels)
 {
-  size_t rays, status, radiance, sum, total;
-  LensWorkspace(uint64_t n_pixels, uint64_t slice)
-  {
-    rays = 0;
-    status = rays + stage_align(48u * slice);
-    radiance = status + stage_align(4u * slice);
-    sum = radiance + stage_align(24u * slice);
-    total = sum + stage_align(24u * n_pixels);
-  }
-};
+  return SliceWorkspace(std::min<uint64_t>(slice_pixels, n_pixels), 24u * n_pixels);
+}
 
 /* what rt_hip_render_lens refuses without a device: RT_HIP_EINVAL, or RT_HIP_OK */
 int check_render_lens(const RtHipCamera *camera, const RtHipLens *lens, const RtHipParams *p, uint32_t slice_pixels, bool any_output)
 {
   if (!p)
     return fail(RT_HIP_EINVAL, "params is required");
-  const int rc = check_lens(camera, lens, p->width, p->height);
-  if (rc)
+  if (const int rc = check_lens(camera, lens, p->width, p->height))
     return rc;
   if (!any_output)
     return fail(RT_HIP_EINVAL, "at least one of sum, rgb and rgb8 is required");
-  if (p->integrator != RT_HIP_TRACE_PATH)
-    return fail(RT_HIP_EINVAL, "integrator %u: a lens frame traces paths (RT_HIP_TRACE_PATH) only", p->integrator);
-  if (p->samples < 1)
-    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", p->samples);
-  if (p->max_depth < 0 || p->max_depth > 1000000)
-    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  if (const int rc = check_path_fields(p->integrator, p->samples, p->max_depth, "a lens frame"))
+    return rc;
   const uint64_t n_pixels = (uint64_t)p->width * (uint64_t)p->height;
   if ((uint64_t)p->samples * n_pixels > 0x100000000ull)
     return fail(RT_HIP_EINVAL, "samples x pixels = %d x %llu exceeds 2^32: a lens sample is a ray index of rt_hip_trace_rays", p->samples,
@@ -3482,72 +3577,35 @@ int check_render_lens(const RtHipCamera *camera, const RtHipLens *lens, const Rt
   return RT_HIP_OK;
 }
 
-int lens_rays_launch(const PtLensRays &A, hipStream_t stream)
-{
-  const hipError_t e = lens_launch_rays(A, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "k_lens_rays launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
-}
-
-/* The frame: for every sample pass and slice the generator, the radiance query's own launch (trace_launch) and the sum; then the
- * resolve.  All on `stream`, no host wait.  The depth limit and near_R are trace_launch's refusals: asked for once, up front. */
+/* The frame: a job of samples x pixels ray indices, a sample pass a period -- so pixel_first = first % pixels and no slice spans two
+ * passes --, then the resolve.  All on `stream`, no host wait. */
 int render_lens_launch(const RtHipScene *scene, const RtHipCamera *camera, const RtHipLens *lens, const RtHipParams *p, uint32_t slice_pixels,
                        void *d_workspace, double *d_sum, float *d_rgb, uint8_t *d_rgb8, uint64_t *d_stats, hipStream_t stream)
 {
   const uint64_t n_pixels = (uint64_t)p->width * (uint64_t)p->height;
-  const uint32_t slice = (uint32_t)std::min<uint64_t>(slice_pixels, n_pixels);
-  RtHipTraceParams T;
-  rt_hip_trace_defaults(&T);
-  T.origin_radius = std::sqrt((camera->position[0] * camera->position[0] + camera->position[1] * camera->position[1]) +
-                              camera->position[2] * camera->position[2]) + lens->aperture_radius;
-  if (!std::isfinite(T.origin_radius))
+  const double origin_radius = std::sqrt((camera->position[0] * camera->position[0] + camera->position[1] * camera->position[1]) +
+                                         camera->position[2] * camera->position[2]) + lens->aperture_radius;
+  if (!std::isfinite(origin_radius))
     return fail(RT_HIP_EINVAL, "the camera position is not finite");
-  T.samples = 1;
-  T.max_depth = p->max_depth;
-  T.seed = p->seed;
-  {
-    PtLaunch dry;
-    const int rc = pooled_launch_prepare(scene, T.source, nullptr, T.origin_radius, 1, T.max_depth, T.seed, nullptr, dry);
-    if (rc)
-      return rc;
-  }
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  const LensWorkspace W(n_pixels, slice);
-  char *const ws = static_cast<char *>(d_workspace);
-  double *const rays = reinterpret_cast<double *>(ws + W.rays);
-  uint32_t *const status = reinterpret_cast<uint32_t *>(ws + W.status);
-  double *const radiance = reinterpret_cast<double *>(ws + W.radiance);
-  double *const sum = d_sum ? d_sum : reinterpret_cast<double *>(ws + W.sum);
-  HIP_TRY(hipMemsetAsync(sum, 0, 24u * n_pixels, stream));
+  const SlicedJob J = {.origin_radius = origin_radius, .max_depth = p->max_depth, .seed = p->seed, .total = (uint64_t)p->samples * n_pixels,
+                       .slice = std::min<uint64_t>(slice_pixels, n_pixels), .period = n_pixels, .sum_bytes = 24u * n_pixels,
+                       .d_workspace = d_workspace, .d_sum = d_sum, .d_stats = d_stats};
   PtLensRays A = lens_args(camera, lens, p->width, p->height, p->seed);
-  A.rays = rays;
-  const RtHipRadiance out = {status, radiance, nullptr, nullptr, nullptr, nullptr};
-  for (int32_t s = 0; s < p->samples; s++)
-    for (uint64_t first = 0; first < n_pixels; first += slice)
-    {
-      A.pixel_first = (uint32_t)first;
-      A.n = (uint32_t)std::min<uint64_t>(slice, n_pixels - first);
-      A.index_first = (uint32_t)((uint64_t)s * n_pixels + first);
-      int rc = lens_rays_launch(A, stream);
-      if (rc)
-        return rc;
-      T.index_first = A.index_first;
-      rc = trace_launch(scene, rays, A.n, &T, &out, d_stats, stream);
-      if (rc)
-        return rc;
-      const hipError_t e = lens_launch_accumulate(status, radiance, A.pixel_first, A.n, sum, stream);
-      if (e != hipSuccess)
-        return fail(RT_HIP_ERUNTIME, "k_lens_accumulate launch: %s", hipGetErrorString(e));
-    }
-  if (d_rgb || d_rgb8)
-  {
-    const hipError_t e = lens_launch_resolve(sum, n_pixels, p->samples, d_rgb, d_rgb8, stream);
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "k_lens_resolve launch: %s", hipGetErrorString(e));
-  }
-  return RT_HIP_OK;
+  return sliced_trace(
+      scene, J, stream,
+      [&](const SliceBuffers &B, uint64_t first, uint32_t n) {
+        A.rays = B.rays;
+        A.pixel_first = (uint32_t)(first % n_pixels);
+        A.n = n;
+        A.index_first = (uint32_t)first;
+        return launched(lens_launch_rays(A, stream), "k_lens_rays");
+      },
+      [&](const SliceBuffers &B, uint64_t first, uint32_t n) {
+        return launched(lens_launch_accumulate(B.status, B.radiance, (uint32_t)(first % n_pixels), n, B.sum, stream), "k_lens_accumulate");
+      },
+      [&](const SliceBuffers &B) {
+        return d_rgb || d_rgb8 ? launched(lens_launch_resolve(B.sum, n_pixels, p->samples, d_rgb, d_rgb8, stream), "k_lens_resolve") : (int)RT_HIP_OK;
+      });
 }
 
 /* rt_hip_render_lens_image: a scene of its own on the logical device, one allocation for the workspace, the frame and the counters,
@@ -3555,44 +3613,27 @@ int render_lens_launch(const RtHipScene *scene, const RtHipCamera *camera, const
 int render_lens_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
                            const RtHipLens *lens, const RtHipParams *params, int device, float *h_rgb, uint8_t *h_rgb8, uint64_t *h_stats)
 {
-  constexpr uint32_t HOST_SLICE = 1u << 21; /* pixels a launch: 160 MB of rays, status words and radiance at most */
-  int rc = check_render_lens(camera, lens, params, HOST_SLICE, h_rgb || h_rgb8);
-  if (rc)
+  if (const int rc = check_render_lens(camera, lens, params, HOST_SLICE, h_rgb || h_rgb8))
     return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  OwnedScene own;
-  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
-  if (rc)
-    return rc;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  const uint64_t n_pixels = (uint64_t)params->width * (uint64_t)params->height;
-  StageArena A;
-  const int ws = A.part(LensWorkspace(n_pixels, std::min<uint64_t>(HOST_SLICE, n_pixels)).total);
-  const int rgb = A.part(12u * n_pixels, nullptr, h_rgb, h_rgb != nullptr);
-  const int rgb8 = A.part(3u * n_pixels, nullptr, h_rgb8, h_rgb8 != nullptr);
-  const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
-  rc = A.stage();
-  if (rc)
-    return rc;
-  rc = render_lens_launch(own.scene, camera, lens, params, HOST_SLICE, A.at<char>(ws), nullptr, A.at<float>(rgb), A.at<uint8_t>(rgb8),
-                          A.at<uint64_t>(stats), nullptr);
-  if (rc)
-    return rc;
-  rc = A.download();
-  if (rc)
-    return rc;
-  uint32_t flags = 0;
-  rc = status_take(phys, &flags);
-  return rc ? rc : status_to_error(flags);
+  return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device, [&](const RtHipScene *scene, int phys) {
+    const uint64_t n_pixels = (uint64_t)params->width * (uint64_t)params->height;
+    StageArena A;
+    const int ws = A.part(lens_workspace(n_pixels, HOST_SLICE).total);
+    const int rgb = A.part(12u * n_pixels, nullptr, h_rgb, h_rgb != nullptr);
+    const int rgb8 = A.part(3u * n_pixels, nullptr, h_rgb8, h_rgb8 != nullptr);
+    const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
+    int rc = A.stage();
+    if (rc)
+      return rc;
+    rc = render_lens_launch(scene, camera, lens, params, HOST_SLICE, A.at<char>(ws), nullptr, A.at<float>(rgb), A.at<uint8_t>(rgb8),
+                            A.at<uint64_t>(stats), nullptr);
+    return rc ? rc : download_then_status(A, phys);
+  });
 }
 
 /* ---- light probes (rt_hip.h, rt_hip_probe_* / rt_hip_bake_probes*) -------------------------------------------------------------
- * A bake is probe rays (probe.hip), the radiance query as it stands (trace_launch) and a per-probe fold (probe.hip).  The checks need
- * no device; the bake refuses everything it can before its first launch. */
+ * A bake is a generated-ray job (above): probe rays (probe.hip), a per-probe fold (probe.hip), the whole bake one period.  The checks
+ * need no device; the bake refuses everything it can before its first launch. */
 uint32_t probe_bases(uint32_t mode) { return mode == RT_HIP_PROBE_HEMISPHERE ? 1u : (uint32_t)PT_PROBE_SH; }
 
 /* what every probe call refuses in its params without a device: RT_HIP_EINVAL, or RT_HIP_OK */
@@ -3613,8 +3654,8 @@ int check_probe(const RtHipProbeParams *p, uint64_t n_probes, bool have_normals)
     return fail(RT_HIP_EINVAL, "bias %g must be finite and >= 0", p->bias);
   if (!(p->origin_radius >= 0) || !std::isfinite(p->origin_radius))
     return fail(RT_HIP_EINVAL, "origin_radius %g must be finite and >= 0", p->origin_radius);
-  if (p->max_depth < 0 || p->max_depth > 1000000)
-    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  if (const int rc = check_max_depth(p->max_depth))
+    return rc;
   if (p->mode == RT_HIP_PROBE_HEMISPHERE && !have_normals && n_probes != 0)
     return fail(RT_HIP_EINVAL, "RT_HIP_PROBE_HEMISPHERE needs normals");
   return RT_HIP_OK;
@@ -3634,103 +3675,58 @@ PtProbeRays probe_args(const double *d_positions, const double *d_normals, const
   return A;
 }
 
-/* the parts of a bake's workspace: a slice's rays, status words and radiance, then the probes' sums */
-struct ProbeWorkspace
+/* a bake's workspace: the sums are three doubles a basis and probe */
+SliceWorkspace probe_workspace(uint64_t n_probes, uint32_t mode, uint64_t slice_rays)
 {
-  size_t rays, status, radiance, sum, total;
-  ProbeWorkspace(uint64_t n_probes, uint32_t bases, uint64_t slice)
-  {
-    rays = 0;
-    status = rays + stage_align(48u * slice);
-    radiance = status + stage_align(4u * slice);
-    sum = radiance + stage_align(24u * slice);
-    total = sum + stage_align(24u * bases * n_probes);
-  }
-};
-
-int probe_rays_launch(const PtProbeRays &A, hipStream_t stream)
-{
-  const hipError_t e = probe_launch_rays(A, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "k_probe_rays launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return SliceWorkspace(slice_rays, 24u * probe_bases(mode) * n_probes);
 }
 
 int probe_resolve_launch(const double *d_sum, uint64_t n_probes, uint32_t mode, int32_t samples, double *d_coeff, float *d_coeff_f,
                          hipStream_t stream)
 {
   const double k = mode == RT_HIP_PROBE_HEMISPHERE ? PT_PROBE_K_HEMISPHERE : PT_PROBE_K_SPHERE;
-  const hipError_t e = probe_launch_resolve(d_sum, 3u * probe_bases(mode) * n_probes, samples, k, d_coeff, d_coeff_f, stream);
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "k_probe_resolve launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return launched(probe_launch_resolve(d_sum, 3u * probe_bases(mode) * n_probes, samples, k, d_coeff, d_coeff_f, stream), "k_probe_resolve");
 }
 
-/* The bake: for every slice the generator, the radiance query's own launch (trace_launch) and the fold; then the resolve.  All on
- * `stream`, no host wait.  The depth limit and near_R are trace_launch's refusals: asked for once, up front.  n_probes >= 1. */
+/* The bake: a job of probes x samples ray indices in one period, the probes' status words marked before the first slice's rays are
+ * written, then the resolve.  All on `stream`, no host wait.  n_probes >= 1. */
 int bake_probes_launch(const RtHipScene *scene, const double *d_positions, const double *d_normals, uint64_t n_probes,
                        const RtHipProbeParams *p, uint32_t slice_rays, void *d_workspace, double *d_sum, double *d_coeff, float *d_coeff_f,
                        uint32_t *d_status, uint64_t *d_stats, hipStream_t stream)
 {
   const uint64_t total = n_probes * (uint64_t)p->samples, S = (uint64_t)p->samples;
-  const uint64_t slice = std::min<uint64_t>(slice_rays, total);
-  const uint32_t bases = probe_bases(p->mode);
-  RtHipTraceParams T;
-  rt_hip_trace_defaults(&T);
-  T.origin_radius = p->origin_radius;
-  T.samples = 1;
-  T.max_depth = p->max_depth;
-  T.seed = p->seed;
-  {
-    PtLaunch dry;
-    const int rc = pooled_launch_prepare(scene, T.source, nullptr, T.origin_radius, 1, T.max_depth, T.seed, nullptr, dry);
-    if (rc)
-      return rc;
-  }
-  DeviceScope scope(scene->device);
-  HIP_TRY(scope.status);
-  const ProbeWorkspace W(n_probes, bases, slice);
-  char *const ws = static_cast<char *>(d_workspace);
-  double *const rays = reinterpret_cast<double *>(ws + W.rays);
-  uint32_t *const status = reinterpret_cast<uint32_t *>(ws + W.status);
-  double *const radiance = reinterpret_cast<double *>(ws + W.radiance);
-  double *const sum = d_sum ? d_sum : reinterpret_cast<double *>(ws + W.sum);
-  HIP_TRY(hipMemsetAsync(sum, 0, 24u * bases * n_probes, stream));
-  if (d_status)
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status), 1, n_probes, stream));
+  const SlicedJob J = {.origin_radius = p->origin_radius, .max_depth = p->max_depth, .seed = p->seed, .total = total,
+                       .slice = std::min<uint64_t>(slice_rays, total), .period = total, .sum_bytes = 24u * probe_bases(p->mode) * n_probes,
+                       .d_workspace = d_workspace, .d_sum = d_sum, .d_stats = d_stats};
   PtProbeRays A = probe_args(d_positions, d_normals, p);
-  A.rays = rays;
   PtProbeFold F;
   memset(&F, 0, sizeof F);
-  F.rays = rays;
-  F.radiance = radiance;
   F.normals = d_normals;
-  F.status = status;
-  F.sum = sum;
   F.probe_status = d_status;
   F.samples = A.samples;
   F.hemisphere = A.hemisphere;
-  const RtHipRadiance out = {status, radiance, nullptr, nullptr, nullptr, nullptr};
-  for (uint64_t first = 0; first < total; first += slice)
-  {
-    A.k_first = first;
-    A.n = (uint32_t)std::min<uint64_t>(slice, total - first);
-    int rc = probe_rays_launch(A, stream);
-    if (rc)
-      return rc;
-    T.index_first = (uint32_t)first;
-    rc = trace_launch(scene, rays, A.n, &T, &out, d_stats, stream);
-    if (rc)
-      return rc;
-    F.k_first = first;
-    F.n = A.n;
-    F.probe_first = first / S;
-    F.n_probes = (first + A.n - 1u) / S - F.probe_first + 1u;
-    const hipError_t e = probe_launch_fold(F, stream);
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "k_probe_fold launch: %s", hipGetErrorString(e));
-  }
-  return probe_resolve_launch(sum, n_probes, p->mode, p->samples, d_coeff, d_coeff_f, stream);
+  return sliced_trace(
+      scene, J, stream,
+      [&](const SliceBuffers &B, uint64_t first, uint32_t n) {
+        if (first == 0 && d_status)
+          HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status), 1, n_probes, stream));
+        A.rays = B.rays;
+        A.k_first = first;
+        A.n = n;
+        return launched(probe_launch_rays(A, stream), "k_probe_rays");
+      },
+      [&](const SliceBuffers &B, uint64_t first, uint32_t n) {
+        F.rays = B.rays;
+        F.radiance = B.radiance;
+        F.status = B.status;
+        F.sum = B.sum;
+        F.k_first = first;
+        F.n = n;
+        F.probe_first = first / S;
+        F.n_probes = (first + n - 1u) / S - F.probe_first + 1u;
+        return launched(probe_launch_fold(F, stream), "k_probe_fold");
+      },
+      [&](const SliceBuffers &B) { return probe_resolve_launch(B.sum, n_probes, p->mode, p->samples, d_coeff, d_coeff_f, stream); });
 }
 
 /* rt_hip_bake_probes_host: a scene of its own on the logical device, one allocation for the probes, the workspace, the outputs and
@@ -3739,46 +3735,30 @@ int bake_probes_host_impl(const RtHipSphere *spheres, size_t n_spheres, const Rt
                           const double *h_normals, uint64_t n_probes, const RtHipProbeParams *params, int device, double *h_coeff,
                           float *h_coeff_f, uint32_t *h_status, uint64_t *h_stats)
 {
-  constexpr uint32_t HOST_SLICE = 1u << 21; /* rays a launch: 160 MB of rays, status words and radiance at most */
   int rc = check_probe(params, n_probes, h_normals != nullptr);
   if (rc || n_probes == 0)
     return rc; /* (no probe: nothing to do, on any device or none) */
   if (!h_positions || !h_coeff)
     return fail(RT_HIP_EINVAL, "h_positions and h_coeff are required");
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  OwnedScene own;
-  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
-  if (rc)
-    return rc;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  const bool hemisphere = params->mode == RT_HIP_PROBE_HEMISPHERE;
-  const uint32_t bases = probe_bases(params->mode);
-  const uint64_t total = n_probes * (uint64_t)params->samples;
-  StageArena A;
-  const int ws = A.part(ProbeWorkspace(n_probes, bases, std::min<uint64_t>(HOST_SLICE, total)).total);
-  const int positions = A.part(24u * n_probes, h_positions);
-  const int normals = A.part(24u * n_probes, h_normals, nullptr, hemisphere);
-  const int coeff = A.part(24u * bases * n_probes, nullptr, h_coeff);
-  const int coeff_f = A.part(12u * bases * n_probes, nullptr, h_coeff_f, h_coeff_f != nullptr);
-  const int status = A.part(4u * n_probes, nullptr, h_status, h_status != nullptr);
-  const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
-  rc = A.stage();
-  if (rc)
-    return rc;
-  rc = bake_probes_launch(own.scene, A.at<double>(positions), A.at<double>(normals), n_probes, params, HOST_SLICE, A.at<char>(ws), nullptr,
-                          A.at<double>(coeff), A.at<float>(coeff_f), A.at<uint32_t>(status), A.at<uint64_t>(stats), nullptr);
-  if (rc)
-    return rc;
-  rc = A.download();
-  if (rc)
-    return rc;
-  uint32_t flags = 0;
-  rc = status_take(phys, &flags);
-  return rc ? rc : status_to_error(flags);
+  return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device, [&](const RtHipScene *scene, int phys) {
+    const bool hemisphere = params->mode == RT_HIP_PROBE_HEMISPHERE;
+    const uint32_t bases = probe_bases(params->mode);
+    const uint64_t total = n_probes * (uint64_t)params->samples;
+    StageArena A;
+    const int ws = A.part(probe_workspace(n_probes, params->mode, std::min<uint64_t>(HOST_SLICE, total)).total);
+    const int positions = A.part(24u * n_probes, h_positions);
+    const int normals = A.part(24u * n_probes, h_normals, nullptr, hemisphere);
+    const int coeff = A.part(24u * bases * n_probes, nullptr, h_coeff);
+    const int coeff_f = A.part(12u * bases * n_probes, nullptr, h_coeff_f, h_coeff_f != nullptr);
+    const int status = A.part(4u * n_probes, nullptr, h_status, h_status != nullptr);
+    const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
+    rc = A.stage();
+    if (rc)
+      return rc;
+    rc = bake_probes_launch(scene, A.at<double>(positions), A.at<double>(normals), n_probes, params, HOST_SLICE, A.at<char>(ws), nullptr,
+                            A.at<double>(coeff), A.at<float>(coeff_f), A.at<uint32_t>(status), A.at<uint64_t>(stats), nullptr);
+    return rc ? rc : download_then_status(A, phys);
+  });
 }
 
 /* ---- pixel refinement (rt_hip.h, rt_hip_select_pixels / _trace_pixels / _blend_pixels) ---------------------------------------
@@ -3809,13 +3789,13 @@ int check_pixels(const RtHipCamera *camera, const void *pixels, uint64_t n, cons
     return fail(RT_HIP_EINVAL, "radiance: at least one output array is required");
   if (out->ray)
     return fail(RT_HIP_EINVAL, "radiance: ray must be NULL (an entry's samples have a camera ray each)");
-  if (p->integrator != RT_HIP_TRACE_PATH)
-    return fail(RT_HIP_EINVAL, "integrator %u: a pixel refinement traces paths (RT_HIP_TRACE_PATH) only", p->integrator);
+  if (const int rc = check_integrator(p->integrator, "a pixel refinement"))
+    return rc;
   if (p->samples < 1 || p->sample_first < 0 || (int64_t)p->sample_first + (int64_t)p->samples > ((int64_t)1 << 31))
     return fail(RT_HIP_EINVAL, "samples = %d, sample_first = %d: samples >= 1, sample_first >= 0, sample_first + samples <= 2^31",
                 p->samples, p->sample_first);
-  if (p->max_depth < 0 || p->max_depth > 1000000)
-    return fail(RT_HIP_EINVAL, "max_depth out of range");
+  if (const int rc = check_max_depth(p->max_depth))
+    return rc;
   if (!frame_size_ok(p->width, p->height, 2))
     return fail(RT_HIP_EINVAL, "width and height must be in [2, 2^20] with fewer than 2^32 pixels");
   if (n > 0xFFFFFFFFull)
@@ -3859,25 +3839,17 @@ int trace_pixels_host_impl(const RtHipSphere *spheres, size_t n_spheres, const R
   int rc = check_pixels(camera, h_pixels, n, params, h_out);
   if (rc || n == 0)
     return rc;
-  int phys = -1;
-  rc = physical_device(device, &phys);
-  if (rc)
-    return rc;
-  OwnedScene own;
-  rc = own.create(spheres, n_spheres, meshes, n_meshes, phys);
-  if (rc)
-    return rc;
-  DeviceScope scope(phys);
-  HIP_TRY(scope.status);
-  StageArena A;
-  const int pixels = A.part(4u * n, h_pixels);
-  RadianceStage R(A, h_out, n, params->samples, h_stats); /* (check_pixels: h_out->ray is NULL) */
-  rc = A.stage();
-  if (rc)
-    return rc;
-  const RtHipRadiance d_out = R.device(A);
-  rc = pixels_launch(own.scene, camera, A.at<uint32_t>(pixels), n, params, &d_out, A.at<uint64_t>(R.stats), nullptr);
-  return rc ? rc : R.download(A);
+  return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device, [&](const RtHipScene *scene, int) {
+    StageArena A;
+    const int pixels = A.part(4u * n, h_pixels);
+    RadianceStage R(A, h_out, n, params->samples, h_stats); /* (check_pixels: h_out->ray is NULL) */
+    rc = A.stage();
+    if (rc)
+      return rc;
+    const RtHipRadiance d_out = R.device(A);
+    rc = pixels_launch(scene, camera, A.at<uint32_t>(pixels), n, params, &d_out, A.at<uint64_t>(R.stats), nullptr);
+    return rc ? rc : R.download(A);
+  });
 }
 
 /* rt_hip_*_kernel_launches of one of the four kernel lists: entry `index`'s name (null beyond the list) and launch count */
@@ -4829,12 +4801,11 @@ int rt_hip_render_tiles_chunked(const RtHipScene *scene, const RtHipCamera *came
     if (pend_lock.owns_lock())
       pend_lock.unlock();
     release_tables(scene, slot, st);
-    if (rc)
-      return rc;
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "%s launch: %s", pt_kernel_name_of(plan.kernel), hipGetErrorString(e));
-    g_last_kernel = plan.kernel;
-    return RT_HIP_OK;
+    if (!rc)
+      rc = launched(e, pt_kernel_name_of(plan.kernel));
+    if (!rc)
+      g_last_kernel = plan.kernel;
+    return rc;
   });
 }
 
@@ -5277,11 +5248,8 @@ int rt_hip_untile(const float *d_tiles_rgb, const uint8_t *d_tiles_rgb8, int32_t
   const uint64_t n_tiles = (uint64_t)tiles_x_of(width) * tiles_y_of(height);
   if ((uint64_t)tile_first + (uint64_t)(tile_count - 1) * tile_stride >= n_tiles)
     return fail(RT_HIP_EINVAL, "tile range exceeds the image");
-  hipError_t e = pt_launch_untile(d_tiles_rgb, d_tiles_rgb8, width, height, tile_first, tile_stride, tile_count,
-                                  d_image_rgb, d_image_rgb8, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(RT_HIP_ERUNTIME, "pt_untile launch: %s", hipGetErrorString(e));
-  return RT_HIP_OK;
+  return launched(pt_launch_untile(d_tiles_rgb, d_tiles_rgb8, width, height, tile_first, tile_stride, tile_count,
+                                  d_image_rgb, d_image_rgb8, static_cast<hipStream_t>(stream)), "pt_untile");
 }
 
 /* ---- first-hit feature buffers (rt_hip.h, RtHipAov) ----------------------------------------------------------------------
@@ -5430,7 +5398,7 @@ int rt_hip_lens_rays(const RtHipCamera *camera, const RtHipLens *lens, int32_t w
     A.n = n;
     A.index_first = (uint32_t)((uint64_t)sample * n_pixels + pixel_first);
     A.rays = d_rays;
-    return lens_rays_launch(A, static_cast<hipStream_t>(stream));
+    return launched(lens_launch_rays(A, static_cast<hipStream_t>(stream)), "k_lens_rays");
   });
 }
 
@@ -5438,8 +5406,7 @@ size_t rt_hip_lens_workspace_bytes(int32_t width, int32_t height, uint32_t slice
 {
   if (!frame_size_ok(width, height, 2) || slice_pixels == 0u)
     return 0;
-  const uint64_t n_pixels = (uint64_t)width * (uint64_t)height;
-  return LensWorkspace(n_pixels, std::min<uint64_t>(slice_pixels, n_pixels)).total;
+  return lens_workspace((uint64_t)width * (uint64_t)height, slice_pixels).total;
 }
 
 int rt_hip_lens_resolve(const double *d_sum, int32_t width, int32_t height, int32_t samples, float *d_rgb, uint8_t *d_rgb8, void *stream)
@@ -5451,25 +5418,19 @@ int rt_hip_lens_resolve(const double *d_sum, int32_t width, int32_t height, int3
   if (!d_sum || (!d_rgb && !d_rgb8))
     return fail(RT_HIP_EINVAL, "d_sum and an output are required");
   return on_device_of(d_sum, "d_sum", [&]() -> int {
-    const hipError_t e = lens_launch_resolve(d_sum, (uint64_t)width * (uint64_t)height, samples, d_rgb, d_rgb8, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "k_lens_resolve launch: %s", hipGetErrorString(e));
-    return RT_HIP_OK;
+    return launched(lens_launch_resolve(d_sum, (uint64_t)width * (uint64_t)height, samples, d_rgb, d_rgb8, static_cast<hipStream_t>(stream)), "k_lens_resolve");
   });
 }
 
 int rt_hip_render_lens(const RtHipScene *scene, const RtHipCamera *camera, const RtHipLens *lens, const RtHipParams *params,
                        uint32_t slice_pixels, void *d_workspace, double *d_sum, float *d_rgb, uint8_t *d_rgb8, uint64_t *d_stats, void *stream)
 {
-  const int rc = check_render_lens(camera, lens, params, slice_pixels, d_sum || d_rgb || d_rgb8);
-  if (rc)
+  if (const int rc = check_render_lens(camera, lens, params, slice_pixels, d_sum || d_rgb || d_rgb8))
     return rc;
   if (!scene || !d_workspace)
     return fail(RT_HIP_EINVAL, "scene and d_workspace are required");
-  if (reinterpret_cast<uintptr_t>(d_workspace) & 15u) /* (the slice's rays lie at its start: rt_hip_trace_rays' own rule) */
-    return fail(RT_HIP_EINVAL, "d_workspace must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_sum) & 7u)
-    return fail(RT_HIP_EINVAL, "d_sum must be 8-byte aligned");
+  if (const int rc = check_slice_buffers(d_workspace, d_sum))
+    return rc;
   return guarded("rt_hip_render_lens", [&] {
     return render_lens_launch(scene, camera, lens, params, slice_pixels, d_workspace, d_sum, d_rgb, d_rgb8, d_stats, static_cast<hipStream_t>(stream));
   });
@@ -5516,7 +5477,7 @@ int rt_hip_probe_rays(const double *d_positions, const double *d_normals, uint64
     A.k_first = k_first;
     A.n = (uint32_t)n;
     A.rays = d_rays;
-    return probe_rays_launch(A, static_cast<hipStream_t>(stream));
+    return launched(probe_launch_rays(A, static_cast<hipStream_t>(stream)), "k_probe_rays");
   });
 }
 
@@ -5524,22 +5485,19 @@ size_t rt_hip_probe_workspace_bytes(uint64_t n_probes, uint32_t mode, uint32_t s
 {
   if ((mode != RT_HIP_PROBE_SPHERE && mode != RT_HIP_PROBE_HEMISPHERE) || slice_rays == 0u || n_probes > 0x100000000ull)
     return 0;
-  return ProbeWorkspace(n_probes, probe_bases(mode), slice_rays).total;
+  return probe_workspace(n_probes, mode, slice_rays).total;
 }
 
 int rt_hip_bake_probes(const RtHipScene *scene, const double *d_positions, const double *d_normals, uint64_t n_probes,
                        const RtHipProbeParams *params, uint32_t slice_rays, void *d_workspace, double *d_sum, double *d_coeff, float *d_coeff_f,
                        uint32_t *d_status, uint64_t *d_stats, void *stream)
 {
-  const int rc = check_probe(params, n_probes, d_normals != nullptr);
-  if (rc)
+  if (const int rc = check_probe(params, n_probes, d_normals != nullptr))
     return rc;
   if (slice_rays == 0u)
     return fail(RT_HIP_EINVAL, "slice_rays must be >= 1");
-  if (reinterpret_cast<uintptr_t>(d_workspace) & 15u) /* (the slice's rays lie at its start: rt_hip_trace_rays' own rule) */
-    return fail(RT_HIP_EINVAL, "d_workspace must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_sum) & 7u)
-    return fail(RT_HIP_EINVAL, "d_sum must be 8-byte aligned");
+  if (const int rc = check_slice_buffers(d_workspace, d_sum)) /* (before the empty bake returns and before the null checks) */
+    return rc;
   if (n_probes == 0)
     return RT_HIP_OK;
   if (!scene || !d_positions || !d_workspace || !d_coeff)
@@ -5577,10 +5535,7 @@ int rt_hip_probe_irradiance(const double *d_coeff, uint64_t n_probes, const uint
   if ((!d_coeff && n_probes != 0) || !d_index || !d_normals || !d_irradiance)
     return fail(RT_HIP_EINVAL, "d_coeff, d_index, d_normals and d_irradiance are required");
   return on_device_of(d_irradiance, "d_irradiance", [&] {
-    const hipError_t e = probe_launch_irradiance(d_coeff, n_probes, d_index, d_normals, m, d_irradiance, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "k_probe_irradiance launch: %s", hipGetErrorString(e));
-    return (int)RT_HIP_OK;
+    return launched(probe_launch_irradiance(d_coeff, n_probes, d_index, d_normals, m, d_irradiance, static_cast<hipStream_t>(stream)), "k_probe_irradiance");
   });
 }
 
@@ -5614,8 +5569,8 @@ int rt_hip_untile_aov(const RtHipAov *d_tiles, int32_t width, int32_t height, ui
       continue;
     const hipError_t e = pt_launch_untile_aov(static_cast<const uint32_t *>(src[k]), k < 2 ? 3u : 1u, width, height, tile_first,
                                               tile_stride, tile_count, static_cast<uint32_t *>(dst[k]), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "pt_untile_aov launch: %s", hipGetErrorString(e));
+    if (const int rc = launched(e, "pt_untile_aov"))
+      return rc;
   }
   return RT_HIP_OK;
 }
@@ -5909,10 +5864,7 @@ int rt_hip_blend_pixels(const uint32_t *d_pixels, const uint32_t *d_status, cons
     const PtBlend B = {.pixels = d_pixels, .status = d_status, .radiance = d_radiance, .n = n,
                        .n_pixels = (uint32_t)((uint64_t)width * (uint64_t)height), .new_weight = new_weight, .prior_scale = prior_scale,
                        .prior = d_prior, .rgb = d_rgb, .rgb8 = d_rgb8, .weight = d_weight};
-    const hipError_t e = pt_launch_blend(B, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess)
-      return fail(RT_HIP_ERUNTIME, "pt_blend_pixels launch: %s", hipGetErrorString(e));
-    return RT_HIP_OK;
+    return launched(pt_launch_blend(B, static_cast<hipStream_t>(stream)), "pt_blend_pixels");
   });
 }
 

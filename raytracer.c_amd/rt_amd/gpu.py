@@ -21,6 +21,43 @@ def _check(rc, what):
         raise ShimError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
 
+def _stats_dict(stats):
+    """the four counters of a call (RT_HIP_NSTATS words, abi.STAT_* order) by name"""
+    return dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
+
+
+def _distance(xyz):
+    """|xyz|: how far a camera or a ray origin is from the world's origin, the default origin_radius of its rays"""
+    x, y, z = xyz
+    return (x * x + y * y + z * z) ** 0.5
+
+
+def _device_rays(rays, per_ray, dev):
+    """rays or uv pairs as a contiguous float64 tensor [n, per_ray] on `dev` that starts on a 16-byte boundary"""
+    rays = torch.as_tensor(rays, dtype=torch.float64, device=dev).reshape(-1, per_ray).contiguous()
+    return rays.clone() if rays.data_ptr() % 16 else rays   # (a view into a larger tensor: the kernel loads 16 bytes at a time)
+
+
+def _wanted(record, shapes, want, n, dev, samples=0, into=None):
+    """The outputs `want` of an RtHipHits or an RtHipRadiance (`record`; shapes: abi.HIT_SHAPES or abi.RADIANCE_SHAPES) for n entries
+    -> (dict, record): tensors on `dev` (the C-ABI's uint32 / uint64 words as int32 / int64; a field of `into` is used where given), or
+    numpy arrays with dev None.  Each one's address goes into the record's field (n == 0 launches nothing: it only says "wanted")."""
+    import numpy as np
+    kinds = {"float64": torch.float64, "uint32": torch.int32, "uint64": torch.int64}
+    out = {}
+    for f in want:
+        dtype, k = shapes[f]
+        shape = (n, samples, 3) if f == "samples" else ((n, k) if k > 1 else (n,))
+        if into is not None and f in into:
+            out[f] = t = into[f]
+            if t.device != dev or t.dtype != kinds[dtype] or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"query: out[{f!r}] must be a contiguous {kinds[dtype]} tensor of shape {shape} on the scene's device")
+        else:
+            out[f] = np.zeros(shape, dtype=dtype) if dev is None else torch.empty(shape, dtype=kinds[dtype], device=dev)
+        setattr(record, f, (out[f].ctypes.data if dev is None else out[f].data_ptr()) if n else 1)
+    return out, record
+
+
 class GpuScene:
     """A scene resident in HBM (rt_hip_scene_create_opts).  bvh: who builds the triangle hierarchy, "host" (the default) or
     "device" -- frames, bytes and counters are the same under either."""
@@ -358,25 +395,13 @@ class GpuScene:
 
     def _query(self, rays, per_ray, t_max, params, want, into=None):
         dev = torch.device("cuda", self.device)
-        rays = torch.as_tensor(rays, dtype=torch.float64, device=dev).reshape(-1, per_ray).contiguous()
-        if rays.data_ptr() % 16:
-            rays = rays.clone()   # (a view into a larger tensor: the kernel loads 16 bytes at a time)
+        rays = _device_rays(rays, per_ray, dev)
         n = rays.shape[0]
         if t_max is not None:
             t_max = torch.as_tensor(t_max, dtype=torch.float64, device=dev).reshape(-1).contiguous()
             if t_max.numel() != n:
                 raise ValueError("query: t_max must hold one value per ray")
-        out, hits = {}, abi.RtHipHits()
-        for f in want:
-            dtype, k = abi.HIT_SHAPES[f]
-            shape, tdtype = (n, k) if k > 1 else (n,), torch.float64 if dtype == "float64" else torch.int32
-            if into is not None and f in into:
-                out[f] = into[f]
-                if out[f].device != dev or out[f].dtype != tdtype or tuple(out[f].shape) != shape or not out[f].is_contiguous():
-                    raise ValueError(f"query: out[{f!r}] must be a contiguous {tdtype} tensor of shape {shape} on the scene's device")
-            else:
-                out[f] = torch.empty(shape, dtype=tdtype, device=dev)
-            setattr(hits, f, out[f].data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "wanted")
+        out, hits = _wanted(abi.RtHipHits(), abi.HIT_SHAPES, want, n, dev, into=into)
         stream = torch.cuda.current_stream(dev).cuda_stream
         self._query_inputs = (rays, t_max)   # keep alive until the stream has used them
         _check(self.shim.rt_hip_query_rays(self.handle, C.c_void_p(rays.data_ptr() if n else None),
@@ -398,8 +423,7 @@ class GpuScene:
         is allocated)"""
         cam = camera if camera is not None else self.scene.camera
         if origin_radius is None:
-            x, y, z = cam.position.tuple()
-            origin_radius = (x * x + y * y + z * z) ** 0.5
+            origin_radius = _distance(cam.position.tuple())
         return self._query(uv, 2, t_max, abi.query_params(abi.RAYS_CAMERA_UV, normalize, cam, origin_radius), want, out)
 
     def pick(self, x, y):
@@ -418,16 +442,9 @@ class GpuScene:
 
     def _trace(self, rays, per_ray, params, want, stats):
         dev = torch.device("cuda", self.device)
-        rays = torch.as_tensor(rays, dtype=torch.float64, device=dev).reshape(-1, per_ray).contiguous()
-        if rays.data_ptr() % 16:
-            rays = rays.clone()   # (a view into a larger tensor: the kernel loads 16 bytes at a time)
-        n, spp = rays.shape[0], params.samples
-        out, rad = {}, abi.RtHipRadiance()
-        for f in want:
-            dtype, k = abi.RADIANCE_SHAPES[f]
-            shape = (n, spp, 3) if f == "samples" else ((n, k) if k > 1 else (n,))
-            out[f] = torch.empty(shape, dtype={"float64": torch.float64, "uint32": torch.int32, "uint64": torch.int64}[dtype], device=dev)
-            setattr(rad, f, out[f].data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "wanted")
+        rays = _device_rays(rays, per_ray, dev)
+        n = rays.shape[0]
+        out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, dev, params.samples)
         if stats is None:
             stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -454,8 +471,7 @@ class GpuScene:
         None: the camera's distance from the world origin)"""
         cam = camera if camera is not None else self.scene.camera
         if origin_radius is None:
-            x, y, z = cam.position.tuple()
-            origin_radius = (x * x + y * y + z * z) ** 0.5
+            origin_radius = _distance(cam.position.tuple())
         p = abi.trace_params(samples, seed, self.scene.max_depth if max_depth is None else max_depth, abi.RAYS_CAMERA_UV, normalize, cam,
                              origin_radius, index_first)
         return self._trace(uv, 2, p, want, stats)
@@ -478,14 +494,10 @@ class GpuScene:
             raise ValueError("trace_pixels(): n must be within the list")
         p = abi.pixel_params(self.scene.width, self.scene.height, samples, seed, sample_first,
                              self.scene.max_depth if max_depth is None else max_depth)
-        out, rad = {}, abi.RtHipRadiance()
         for f in want:
             if f not in abi.PIXEL_FIELDS:
                 raise ValueError(f"trace_pixels(): {f!r} is not an output of a pixel refinement")
-            dtype, k = abi.RADIANCE_SHAPES[f]
-            shape = (n, samples, 3) if f == "samples" else ((n, k) if k > 1 else (n,))
-            out[f] = torch.empty(shape, dtype={"float64": torch.float64, "uint32": torch.int32, "uint64": torch.int64}[dtype], device=dev)
-            setattr(rad, f, out[f].data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "wanted")
+        out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, dev, samples)
         if stats is None:
             stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -558,7 +570,8 @@ class GpuScene:
         if nrm is not None and nrm.shape[0] != n:
             raise ValueError(f"{nrm.shape[0]} normals for {n} probes")
         if origin_radius is None:
-            origin_radius = _origin_radius(pos, nrm, bias)
+            norms = lambda t: None if t is None else torch.linalg.vector_norm(t, dim=1)
+            origin_radius = _origin_radius(norms(pos), norms(nrm), bias)   # (synchronises)
         p = abi.probe_params(mode, samples, seed, self.scene.max_depth if max_depth is None else max_depth, bias, origin_radius)
         total = max(n * samples, 1)
         slice_rays = total if slice_rays is None else slice_rays
@@ -596,9 +609,8 @@ class GpuScene:
         """An equirectangular view from `origin` (scene.panorama_rays: no Camera expresses it), `samples` paths per pixel, pixel
         k = y * width + x on the stream (seed, k, s) -> (float64 [height, width, 3] linear radiance on the device, stats)"""
         from . import scene as S
-        ox, oy, oz = origin
-        out = self.trace_rays(S.panorama_rays(width, height, origin), samples, seed, max_depth,
-                              origin_radius=(ox * ox + oy * oy + oz * oz) ** 0.5, want=("radiance",))
+        out = self.trace_rays(S.panorama_rays(width, height, origin), samples, seed, max_depth, origin_radius=_distance(origin),
+                              want=("radiance",))
         return out["radiance"].reshape(height, width, 3), out["stats"]
 
     def denoised_image(self, seed, samples, **params):
@@ -649,8 +661,7 @@ class GpuScene:
         torch.cuda.synchronize(tiles.device)
         self.launch_status()   # a workgroup without its pool slot fails the frame here, not as NaN pixels
         st = stats.cpu().tolist()
-        return image, image8, dict(rays=st[abi.STAT_RAYS], casts=st[abi.STAT_CASTS], tests=st[abi.STAT_TESTS],
-                                   samples=st[abi.STAT_SAMPLES])
+        return image, image8, _stats_dict(st)
 
 
 class Accumulation:
@@ -753,7 +764,7 @@ class Accumulation:
         cb = abi.ADAPT_CHECKPOINT(lambda user, done, live: 1 if on_checkpoint(done, live) else 0) if on_checkpoint else None
         _check(self.shim.rt_hip_accum_run_adaptive(self.handle, C.byref(p), stats, C.byref(secs),
                                                    C.cast(cb, C.c_void_p) if cb else None, None), "rt_hip_accum_run_adaptive")
-        return dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3]), secs.value
+        return _stats_dict(stats), secs.value
 
     def close(self):
         if self.handle:
@@ -887,17 +898,13 @@ def trace_pixels_host(scene, pixels, samples, seed, sample_first=0, camera=None,
     pixels = np.ascontiguousarray(np.asarray(pixels, dtype=np.uint32).reshape(-1))
     n = pixels.size
     p = abi.pixel_params(scene.width, scene.height, samples, seed, sample_first, scene.max_depth if max_depth is None else max_depth)
-    out, rad = {}, abi.RtHipRadiance()
-    for f in want:
-        dtype, k = abi.RADIANCE_SHAPES[f]
-        out[f] = np.zeros((n, samples, 3) if f == "samples" else ((n, k) if k > 1 else (n,)), dtype=dtype)
-        setattr(rad, f, out[f].ctypes.data)
+    out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, None, samples)
     stats = (C.c_uint64 * abi.NSTATS)()
     meshes = scene.hip_meshes()
     _check(shim.rt_hip_trace_pixels_host(scene.objects, scene.n_objects, meshes, scene.n_meshes,
                                          C.byref(camera if camera is not None else scene.camera), pixels.ctypes.data, n, C.byref(p), device,
                                          C.byref(rad), stats), "rt_hip_trace_pixels_host")
-    out["stats"] = dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
+    out["stats"] = _stats_dict(stats)
     return out
 
 
@@ -1392,7 +1399,7 @@ def render_image_host(scene, seed, n_devices=1, samples=None, max_depth=None, in
     _check(shim.rt_hip_render_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera),
                                     C.byref(p), n_devices, img.ctypes.data, img8.ctypes.data, stats, C.byref(secs)),
            "rt_hip_render_image")
-    return img, img8, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3]), secs.value
+    return img, img8, _stats_dict(stats), secs.value
 
 
 def aov_image_host(scene, seed, samples, device=0):
@@ -1433,7 +1440,7 @@ def adaptive_image_host(scene, seed, samples, device=0, max_depth=None, integrat
     _check(shim.rt_hip_render_adaptive_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera), C.byref(p),
                                              C.byref(ap), device, img.ctypes.data, img8.ctypes.data, counts.ctypes.data, stats,
                                              C.byref(secs), None, None), "rt_hip_render_adaptive_image")
-    return img, img8, counts, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3]), secs.value
+    return img, img8, counts, _stats_dict(stats), secs.value
 
 
 def query_rays_host(scene, rays, t_max=None, normalize=False, origin_radius=None, camera=None, device=0, want=abi.HIT_FIELDS):
@@ -1450,11 +1457,7 @@ def query_rays_host(scene, rays, t_max=None, normalize=False, origin_radius=None
         if t_max.size != n:
             raise ValueError("query_rays_host: t_max must hold one value per ray")
     p = abi.query_params(abi.RAYS_CAMERA_UV if camera is not None else abi.RAYS_GIVEN, normalize, camera, origin_radius)
-    out, hits = {}, abi.RtHipHits()
-    for f in want:
-        dtype, k = abi.HIT_SHAPES[f]
-        out[f] = np.zeros((n, k) if k > 1 else (n,), dtype=dtype)
-        setattr(hits, f, out[f].ctypes.data)
+    out, hits = _wanted(abi.RtHipHits(), abi.HIT_SHAPES, want, n, None)
     meshes = scene.hip_meshes()
     _check(shim.rt_hip_query_rays_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, rays.ctypes.data,
                                        t_max.ctypes.data if t_max is not None else None, n, C.byref(p), device, C.byref(hits)),
@@ -1474,16 +1477,12 @@ def trace_rays_host(scene, rays, samples, seed, max_depth=None, normalize=False,
     n = rays.shape[0]
     p = abi.trace_params(samples, seed, scene.max_depth if max_depth is None else max_depth,
                          abi.RAYS_CAMERA_UV if camera is not None else abi.RAYS_GIVEN, normalize, camera, origin_radius, index_first)
-    out, rad = {}, abi.RtHipRadiance()
-    for f in want:
-        dtype, k = abi.RADIANCE_SHAPES[f]
-        out[f] = np.zeros((n, samples, 3) if f == "samples" else ((n, k) if k > 1 else (n,)), dtype=dtype)
-        setattr(rad, f, out[f].ctypes.data)
+    out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, None, samples)
     stats = (C.c_uint64 * abi.NSTATS)()
     meshes = scene.hip_meshes()
     _check(shim.rt_hip_trace_rays_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, rays.ctypes.data, n, C.byref(p), device,
                                        C.byref(rad), stats), "rt_hip_trace_rays_host")
-    out["stats"] = dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
+    out["stats"] = _stats_dict(stats)
     return out
 
 
@@ -1533,18 +1532,18 @@ def render_lens_host(scene, aperture, focus, samples, seed, camera=None, max_dep
     meshes = scene.hip_meshes()
     _check(shim.rt_hip_render_lens_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(cam), C.byref(lens), C.byref(p),
                                          device, img.ctypes.data, img8.ctypes.data, stats), "rt_hip_render_lens_image")
-    return img, img8, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
+    return img, img8, _stats_dict(stats)
 
 
-def _origin_radius(pos, nrm, bias):
-    """an origin_radius for probes at pos (+ nrm * bias): the largest finite distance from the world's origin (synchronises)"""
-    r = torch.linalg.vector_norm(pos, dim=1)
-    r = r[torch.isfinite(r)]
-    out = float(r.max()) if r.numel() else 0.0
-    if nrm is not None and bias:
-        m = torch.linalg.vector_norm(nrm, dim=1)
-        m = m[torch.isfinite(m)]
-        out += bias * (float(m.max()) if m.numel() else 0.0)
+def _origin_radius(r, m, bias):
+    """An origin_radius for probes at positions of lengths r (+ normals of lengths m, or None, times bias): the largest finite
+    distance from the world's origin, a shade more.  r, m: tensors or numpy arrays [N]."""
+    def largest(x):
+        x = x[abs(x) < float("inf")]
+        return float(x.max()) if len(x) else 0.0
+    out = largest(r)
+    if m is not None and bias:
+        out += bias * largest(m)
     return out * (1.0 + 2.0 ** -40)
 
 
@@ -1609,12 +1608,8 @@ def bake_probes_host(scene, positions, samples, seed, normals=None, bias=0.0, ma
     nrm = None if normals is None else np.ascontiguousarray(np.asarray(normals, dtype=np.float64).reshape(-1, 3))
     mode = abi.PROBE_SPHERE if nrm is None else abi.PROBE_HEMISPHERE
     if origin_radius is None:
-        r = np.sqrt((pos * pos).sum(axis=1))
-        origin_radius = float(r[np.isfinite(r)].max(initial=0.0))
-        if nrm is not None:
-            m = np.sqrt((nrm * nrm).sum(axis=1))
-            origin_radius += bias * float(m[np.isfinite(m)].max(initial=0.0))
-        origin_radius *= 1.0 + 2.0 ** -40
+        norms = lambda a: None if a is None else np.sqrt((a * a).sum(axis=1))
+        origin_radius = _origin_radius(norms(pos), norms(nrm), bias)
     p = abi.probe_params(mode, samples, seed, scene.max_depth if max_depth is None else max_depth, bias, origin_radius)
     n, bases = pos.shape[0], abi.PROBE_BASES[mode]
     coeff = np.zeros((n, bases, 3), dtype=np.float64)
@@ -1625,4 +1620,4 @@ def bake_probes_host(scene, positions, samples, seed, normals=None, bias=0.0, ma
     _check(shim.rt_hip_bake_probes_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, pos.ctypes.data, nrm.ctypes.data if nrm is not None else None,
                                         n, C.byref(p), device, coeff.ctypes.data, coeff_f.ctypes.data, status.ctypes.data, stats),
            "rt_hip_bake_probes_host")
-    return coeff, coeff_f, status, dict(rays=stats[0], casts=stats[1], tests=stats[2], samples=stats[3])
+    return coeff, coeff_f, status, _stats_dict(stats)

@@ -172,6 +172,31 @@ def test_frame_is_the_stated_composition(gpu, name):
     assert (_bits(m_rgb) == _bits(rgb)).all() and (m_rgb8 == rgb8).all() and m_st == st
 
 
+def test_slices_end_at_every_sample_pass(gpu):
+    """5 x 3 pixels, 3 samples: a slice that does not divide the pass (4), one short of it (14), the pass (15) and slices larger than
+    it (16, 2^31) give the whole-frame call's outputs and counters bit for bit, and that frame is the composition over the passes'
+    own rays -- lens_rays(sample = s), traced at index_first = s * 15 -- which a slice running on into the next pass would break"""
+    w, h, s_count = 5, 3, 3
+    sc = util.class_scene(width=w, height=h, depth=DEPTH, samples=s_count, n_packed=4)
+    gs = gpu.GpuScene(sc)
+    radiance, status = [], []
+    for s in range(s_count):
+        rays = L.lens_rays(L.camera_tuple(sc.camera), w, h, APERTURE, FOCUS, L.SEED, s)
+        assert (_bits(_host(gpu.lens_rays(sc.camera, w, h, APERTURE, FOCUS, L.SEED, s))) == _bits(rays)).all(), s
+        out = gs.trace_rays(rays, 1, L.SEED, index_first=s * w * h)
+        radiance.append(_host(out["radiance"]))
+        status.append(_host(out["status"]).view(np.uint32))
+    whole = [_host(t) for t in gs.render_lens(APERTURE, FOCUS, s_count, L.SEED)]
+    assert (_bits(whole[2].reshape(-1, 3)) == _bits(L.accumulate(radiance, status))).all()
+    for slice_pixels in (1, 4, 14, 15, 16, 2 ** 31):
+        got = [_host(t) for t in gs.render_lens(APERTURE, FOCUS, s_count, L.SEED, slice_pixels=slice_pixels)]
+        assert gs.launch_status() == 0
+        for a, b in zip(got, whole):   # rgb, rgb8, sum, counters
+            assert (_bits(a) == _bits(b)).all(), f"slice_pixels = {slice_pixels} changes the frame"
+    gs.close()
+    sc.free()
+
+
 # ---- 3. the compiled reference ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(SCENES))
 def test_paths_casts_and_values_equal_the_reference(gpu, ref_mesh, pt, name):

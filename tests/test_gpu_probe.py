@@ -208,6 +208,31 @@ def test_bake_is_the_stated_composition_for_every_slice(gpu, name, mode):
     assert gs.launch_status() == 0
 
 
+@pytest.mark.parametrize("mode", ["sphere", "hemisphere"])
+def test_small_bake_for_slices_about_a_probe(gpu, mode):
+    """3 probes x 5 samples: slices of 4 and 6 straddle a probe, 5 is a probe, 14, 15 and 16 are one short of the bake, the bake and
+    more than it -- each gives the whole bake's sums, coefficients, status words and counters bit for bit, and that bake is the stated
+    composition over rays 0 .. 14"""
+    sc, gs = _scene(gpu, "room")
+    n, s = 3, 5
+    pos = P.positions(n, 3.0)
+    nrm, bias = (P.normals(n), 2.0 ** -10) if mode == "hemisphere" else (None, 0.0)
+    rays, call, total = _composition(gs, pos, nrm, s, bias, 4.0)
+    assert (_bits(_host(gpu.probe_rays(pos, s, P.SEED, normals=nrm, bias=bias))) == _bits(rays)).all()
+
+    def bake(slice_rays):
+        if mode == "hemisphere":
+            return _details(gs.bake_irradiance(pos, nrm, s, P.SEED, bias=bias, max_depth=DEPTH, origin_radius=4.0, slice_rays=slice_rays, details=True))
+        return _details(gs.bake_probes(pos, s, P.SEED, max_depth=DEPTH, origin_radius=4.0, slice_rays=slice_rays, details=True))
+    whole = bake(None)
+    assert (_bits(whole["sum"]) == _bits(total)).all() and (whole["stats"] == call["stats"]).all()
+    for slice_rays in (1, 4, 5, 6, 14, 15, 16):
+        other = bake(slice_rays)
+        for k in ("sum", "coeff", "coeff_f", "status", "stats"):
+            assert (_bits(other[k]) == _bits(whole[k])).all(), (mode, slice_rays, k)
+    assert gs.launch_status() == 0
+
+
 # ---- 5. invalid probes ---------------------------------------------------------------------------------------------------------------------
 def test_invalid_probes_are_nan_and_their_neighbours_untouched(gpu):
     """Probe k's rays have the indices [k S, (k + 1) S) whatever the other probes are: the neighbours of an invalid probe must hold
