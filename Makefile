@@ -93,7 +93,7 @@ oracle:
 	$(MAKE) -C $(ROOT)oracle all
 
 clean:
-	rm -f $(SHIM) $(CSRC)/librt_hip_diag.so $(CSRC)/librt_hip_dev.so $(CSRC)/variants/librt_hip_park0.so $(CSRC)/variants/librt_hip_mfma0.so $(CSRC)/variants/librt_hip_diag_mfma0.so $(HOSTLIB) $(CLI)
+	rm -f $(SHIM) $(CSRC)/librt_hip_diag.so $(CSRC)/librt_hip_dev.so $(CSRC)/variants/librt_hip_park0.so $(CSRC)/variants/librt_hip_mfma0.so $(CSRC)/variants/librt_hip_diag_mfma0.so $(CSRC)/variants/librt_hip_gather.so $(HOSTLIB) $(CLI)
 	$(MAKE) -C $(ROOT)oracle clean
 
 .PHONY: all shim shim-diag shim-dev shim-park0 shim-mfma0 shim-diag-mfma0 host oracle clean

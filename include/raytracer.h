@@ -252,6 +252,17 @@ int rt_get_integrator(void);
 void rt_set_lens(double aperture_radius, double focus_distance);
 void rt_get_lens(double *aperture_radius, double *focus_distance);
 
+/* The probe-lit preview in render()'s and render_ex()'s place (rt_hip.h, "probe grids"): with nx, ny, nz >= 1 set, they bake a grid
+ * of nx x ny x nz light probes over the scene -- on each axis [-reach, reach] about the world's origin, reach = rt_hip_scene_bounds',
+ * origin = -reach, step = (2.0 * reach) / (double)(n - 1); an axis of one probe has it at 0 --, options->samples rays a probe at
+ * rt_set_max_depth()'s depth under rt_set_seed()'s seed, and write rt_hip_probe_preview_image's frame (one first-hit sample a pixel
+ * for the albedo, the default miss colour, no facing weight; made on the one scene whose bounds placed the grid, through
+ * rt_hip_probe_preview_scene_image): noise-free and globally lit.  Any count below 1 turns it
+ * off (the default).  It goes before rt_set_lens, runs on ONE device and takes no part in cancellation, as the lens frame;
+ * ray_count and intersection_test_count grow by the bake's rays.  The reference has no counterpart. */
+void rt_set_probe_grid(int nx, int ny, int nz);
+void rt_get_probe_grid(int *nx, int *ny, int *nz);
+
 /* Who builds the triangle hierarchy of the scenes render() and its kin upload: RT_BVH_HOST (default) = one host core,
  * RT_BVH_DEVICE = the GPU (rt_hip.h, RT_HIP_BVH_DEVICE).  Images, bytes and counters are the same under either; the time a
  * new or changed scene takes to become renderable is what differs.  Other values are ignored.  The reference has no

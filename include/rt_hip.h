@@ -859,6 +859,104 @@ int rt_hip_bake_probes_host(const RtHipSphere *spheres, size_t n_spheres, const 
                             const double *h_normals, uint64_t n_probes, const RtHipProbeParams *params, int device, double *h_coeff,
                             float *h_coeff_f, uint32_t *h_status, uint64_t *h_stats);
 
+/* ---- probe grids: shade entries from a regular grid of baked SH9 probes ------------------------------------------------------------
+ * What light reaches a surface point, given the probes around it: a regular GRID of sphere probes, a kernel that SHADES entries (a
+ * point and a normal each: the first hits of a frame's pixels, lightmap texels, a moving object's vertices) from the grid's baked
+ * coefficients, and the PROBE-LIT PREVIEW of a frame made of a ray query, the albedo of the first-hit buffers and that kernel.  The
+ * ray, radiance and first-hit queries are called as they stand; what is new is a pure function of its arguments, stated here.
+ *
+ * THE GRID (RtHipProbeGrid).  count[0] x count[1] x count[2] = n probes; probe (ix, iy, iz) has index i = (iz*count[1] + iy)*count[0]
+ * + ix and on axis a the position origin[a] + (double)i_a * step[a], the product rounded before the add (fp64, unfused).
+ *   - rt_hip_probe_grid_defaults: struct_size = sizeof(RtHipProbeGrid), flags 0, origin 0, step 1, count 1, miss_color
+ *     (float)(10.0/255.0) in each channel (the reference's background), reserved 0.
+ *   - rt_hip_probe_grid_positions: d_positions gets n x 3 doubles, one thread a probe; they feed rt_hip_bake_probes in
+ *     RT_HIP_PROBE_SPHERE mode unchanged.  Asynchronous on `stream`, on the device that holds d_positions.
+ *   - rt_hip_bake_probe_grid: rt_hip_probe_grid_positions into the workspace, then rt_hip_bake_probes at them, and nothing else:
+ *     params->mode must be RT_HIP_PROBE_SPHERE; d_coeff (n x 9 x 3 doubles) is required, d_coeff_f, d_status and d_stats may be NULL;
+ *     the sums live in the workspace.  rt_hip_probe_grid_workspace_bytes = rt_hip_probe_workspace_bytes(n, SPHERE, slice_rays) plus
+ *     the positions (24 bytes a probe, after the bake's part); 0 for a grid any call would refuse or slice_rays == 0.
+ *
+ * THE SHADE (rt_hip_probe_shade): m entries, m < 2^32.  d_points and d_normals hold 3 doubles an entry (the layout of RtHipHits.point
+ * and .normal: a ray query's output feeds it directly); d_status (may be NULL) the query's status words; d_albedo (may be NULL) 3
+ * floats an entry, a row-major AOV albedo image as it stands; d_add (may be NULL) 3 floats an entry, e.g. the emission of what was
+ * hit; d_irradiance (3 doubles an entry) and d_color (3 floats an entry) may each be NULL, not both.  Asynchronous on `stream`, on
+ * the device that holds d_points.
+ * CONTRACT.  All arithmetic is fp64 + - * / sqrt, unfused, in the order written; A_j, w_j(n) and the quiet NaN are those of
+ * rt_hip_probe_irradiance above.
+ *   1. Class of an entry.  MISS: d_status is given and the word is not 1.  INVALID: not a miss, and any component of its point or
+ *      normal is not finite.  Otherwise VALID.
+ *   2. Cell.  For each axis a with N = count[a]: g = (p_a - origin[a]) / step[a]; g = g > 0.0 ? g : 0.0; top = (double)(N - 1);
+ *      g = g < top ? g : top; i0 = (uint32_t)g (truncates); if N >= 2 && i0 > N - 2 then i0 = N - 2; f = g - (double)i0;
+ *      i1 = N >= 2 ? i0 + 1 : 0; w_a[0] = 1.0 - f, w_a[1] = f.  (N == 1: f = 0, w = (1, 0).)
+ *   3. Corners.  For c = 0 .. 7 with bx = c & 1, by = (c >> 1) & 1, bz = c >> 2: the probe is (i_x[bx], i_y[by], i_z[bz]);
+ *      tri = (w_x[bx] * w_y[by]) * w_z[bz].  Without RT_HIP_GRID_FACING w_c = tri.  With it: v = the corner's position (the grid's
+ *      formula) - p; q = (v.x*v.x + v.y*v.y) + v.z*v.z; cs = q > 0.0 ? ((v.x*n.x + v.y*n.y) + v.z*n.z) * (1.0 / sqrt(q)) : 1.0;
+ *      s = (cs + 1.0) * 0.5; face = s*s + 0.2; w_c = tri * face.  The normal is used as given, not normalised.
+ *   4. Blend.  Over c ascending, from +0.0; a corner with w_c == 0.0 (either sign) is skipped and its coefficients do not enter: a
+ *      NaN probe outside the support cannot poison an entry; a NaN weight does not skip.  B[j][ch] = B[j][ch] + (w_c *
+ *      coeff[i_c][j][ch]); W = W + w_c.
+ *   5. Evaluate.  E_ch = the ascending sum from +0.0 over j = 0 .. 8 of (A_j * B[j][ch]) * w_j(n); E_ch = E_ch / W;
+ *      E_ch = E_ch < 0.0 ? 0.0 : E_ch (clamps SH ringing; a NaN stays NaN).
+ *   6. A VALID entry: irradiance = E; color_ch = (float)((((double)albedo_ch * E_ch) * 0.3183098861837907) + (double)add_ch); an absent
+ *      albedo counts as 1.0f, an absent add as +0.0 (the term is added all the same).
+ *   7. MISS: irradiance +0.0, color_ch = (float)((double)miss_color[ch] + (double)add_ch).  INVALID: a quiet NaN in every output, sign
+ *      and payload unspecified.
+ * The function is TOTAL: any bytes in d_coeff, any finite point and any normal give a defined result, and no index leaves [0, n).
+ * The kernel reads a wave's coefficients through wave-uniform loads where the wave's valid entries share a cell and per lane where
+ * they do not: the same operations in the same order, the same bits.
+ *
+ * THE PREVIEW (rt_hip_probe_preview), width, height >= 2, all on `stream` with no host wait: the pixel centres u = ((double)x + 0.5)
+ * / ((double)width - 1.0), v = ((double)y + 0.5) / ((double)height - 1.0), pixel p = y*width + x; rt_hip_query_rays' launch with
+ * RT_HIP_RAYS_CAMERA_UV at them for status, point, normal and object; rt_hip_render_aov_tiles and rt_hip_untile_aov for the albedo
+ * at aov_samples samples under `seed` (the whole frame); add = (float)emission[object], read from the scene's own material records
+ * on the device (spheres, then meshes: rt_hip_scene_create's numbering; nothing is uploaded; +0.0f for a miss); the shade; rgb8 = the render epilogue's gamma-5 tonemap of
+ * (double)rgb (the device function rt_hip_accum_resolve's kernels call).  d_rgb (3 floats a pixel, row-major) is required, d_rgb8
+ * may be NULL.  Bit for bit the composition of those calls; no output bit depends on anything else.
+ *   - rt_hip_probe_preview_workspace_bytes: the d_workspace (16-byte aligned) of a width x height preview of `scene`; 0 for a size
+ *     out of range.
+ *   - rt_hip_probe_preview_image: the host form, synchronous, with a scene and buffers of its own on logical device `device` of
+ *     rt_hip_render_image's device map: it bakes the grid (rt_hip_bake_probe_grid under probe_params), runs the preview with
+ *     seed = probe_params->seed and reads back h_rgb, h_rgb8 (either may be NULL, not both) and h_coeff (may be NULL); h_stats (may
+ *     be NULL) is overwritten with the bake's counters; it checks the device's status word and returns its error.
+ *   - rt_hip_probe_preview_scene_image: the same from a scene the caller holds, on that scene's device: for a host that has asked
+ *     the scene something first (its bounds, to place the grid) and would otherwise set the scene up twice.
+ * Refusals, each before any launch, arguments before a device is looked for.  RT_HIP_EINVAL: a struct_size below the struct's;
+ * unknown flags or a non-zero reserved; a step that is not finite or not positive; an origin that is not finite; a count of 0 or a
+ * product above 2^24; a miss_color that is not finite; a NULL required pointer, or both outputs NULL; m >= 2^32; for the bake and
+ * the preview what rt_hip_bake_probes, rt_hip_query_rays and rt_hip_render_aov_tiles refuse.  m == 0 is RT_HIP_OK and launches
+ * nothing. */
+enum
+{
+  RT_HIP_GRID_FACING = 1u
+};
+typedef struct
+{
+  uint32_t struct_size; /* set by rt_hip_probe_grid_defaults */
+  uint32_t flags;       /* RT_HIP_GRID_FACING or 0 */
+  double origin[3];     /* position of probe (0,0,0) */
+  double step[3];       /* finite, > 0 */
+  uint32_t count[3];    /* each >= 1; count[0]*count[1]*count[2] <= 2^24 */
+  float miss_color[3];  /* colour of an entry that is a miss; default (float)(10.0/255.0) x 3 */
+  uint32_t reserved;    /* 0 */
+} RtHipProbeGrid;
+void rt_hip_probe_grid_defaults(RtHipProbeGrid *grid);
+int rt_hip_probe_grid_positions(const RtHipProbeGrid *grid, double *d_positions, void *stream);
+size_t rt_hip_probe_grid_workspace_bytes(const RtHipProbeGrid *grid, uint32_t slice_rays);
+int rt_hip_bake_probe_grid(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeParams *params, uint32_t slice_rays,
+                           void *d_workspace, double *d_coeff, float *d_coeff_f, uint32_t *d_status, uint64_t *d_stats, void *stream);
+int rt_hip_probe_shade(const RtHipProbeGrid *grid, const double *d_coeff, const double *d_points, const double *d_normals,
+                       const uint32_t *d_status, const float *d_albedo, const float *d_add, uint64_t m, double *d_irradiance, float *d_color,
+                       void *stream);
+size_t rt_hip_probe_preview_workspace_bytes(const RtHipScene *scene, int32_t width, int32_t height);
+int rt_hip_probe_preview(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid, const double *d_coeff, int32_t width,
+                         int32_t height, int32_t aov_samples, uint64_t seed, void *d_workspace, float *d_rgb, uint8_t *d_rgb8, void *stream);
+int rt_hip_probe_preview_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
+                               const RtHipProbeGrid *grid, const RtHipProbeParams *probe_params, int32_t width, int32_t height,
+                               int32_t aov_samples, int device, float *h_rgb, uint8_t *h_rgb8, double *h_coeff, uint64_t *h_stats);
+int rt_hip_probe_preview_scene_image(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid,
+                                     const RtHipProbeParams *probe_params, int32_t width, int32_t height, int32_t aov_samples, float *h_rgb,
+                                     uint8_t *h_rgb8, double *h_coeff, uint64_t *h_stats);
+
 /* ---- edge-avoiding a-trous denoiser guided by the first-hit buffers ---------------------------------------------------------
  * Inputs: row-major images of w x h pixels (1 <= w, h <= 2^20, w*h < 2^32) on one device -- colour c (3 floats per pixel: the
  * linear mean of rt_hip_render_tiles or rt_hip_accum_resolve after rt_hip_untile) and the RtHipAov buffers of the same frame

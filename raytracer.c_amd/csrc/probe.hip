@@ -8,6 +8,11 @@
  *                       slice, in ascending k; status 2 makes the probe's sums NaN.  No atomics: a sum has one writer.
  *   k_probe_resolve     one thread a value: (sum * (1.0 / S)) * K -> double and float.
  *   k_probe_irradiance  one thread an (entry, channel): the nine terms (A_j * coeff) * w_j(n) added in ascending j.
+ *   k_probe_grid_positions  one thread a probe of a regular grid: origin + (double)i * step per axis.
+ *   k_probe_shade       one thread an entry (a point and a normal): the cell, the eight corners' weights, the blend of their 27
+ *                       coefficients in registers, the irradiance and the colour (rt_hip.h, "probe grids", operation for operation).
+ *                       A wave whose valid lanes share a cell reads the coefficients through wave-uniform loads.
+ *   k_probe_pixel_centres, k_probe_emission, k_probe_tonemap  what rt_hip_probe_preview puts around the shade.
  * The constants are pt_device.h's.  fp64, unfused (-ffp-contract=off, as every source of the shim), IEEE division and sqrt.  256
  * threads a workgroup, no scratch, no LDS; no kernel waits for another workgroup. */
 #include <hip/hip_runtime.h>
@@ -156,6 +161,181 @@ __global__ void __launch_bounds__(PROBE_BLOCK) k_probe_irradiance(const double *
   irradiance[t] = E;
 }
 
+/* ---- probe grids (rt_hip.h, "probe grids") ---- */
+
+/* the position of probe index i on axis a: the product rounded before the add */
+__device__ __forceinline__ double grid_at(const PtGrid &G, int a, uint32_t i) { return G.origin[a] + (double)i * G.step[a]; }
+
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_grid_positions(const PtGrid G, double *__restrict__ positions)
+{
+  const uint32_t i = blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (i >= G.count[0] * G.count[1] * G.count[2])
+    return;
+  const uint32_t ix = i % G.count[0], r = i / G.count[0], iy = r % G.count[1], iz = r / G.count[1];
+  positions[3u * (size_t)i + 0u] = grid_at(G, 0, ix);
+  positions[3u * (size_t)i + 1u] = grid_at(G, 1, iy);
+  positions[3u * (size_t)i + 2u] = grid_at(G, 2, iz);
+}
+
+/* step 2 of the contract on one axis: the lower probe index and the fraction; a NaN coordinate reads cell 0 (the function is total) */
+__device__ __forceinline__ uint32_t grid_cell(const PtGrid &G, int a, double p, double &f)
+{
+  const uint32_t N = G.count[a];
+  double g = (p - G.origin[a]) / G.step[a];
+  g = g > 0.0 ? g : 0.0;
+  const double top = (double)(N - 1u);
+  g = g < top ? g : top;
+  uint32_t i0 = (uint32_t)g;
+  if (N >= 2u && i0 > N - 2u)
+    i0 = N - 2u;
+  f = g - (double)i0;
+  return i0;
+}
+
+#ifndef PT_SHADE_UNIFORM
+#define PT_SHADE_UNIFORM 1 /* 0: the per-lane gather alone (tools/probe_shade_bench.py's other arm) */
+#endif
+
+/* Steps 3 and 4: the eight corners of the cell whose lower probe is (x0, y0, z0), in ascending c.  The caller gives the cell either as
+ * each lane's own registers or as the wave's one cell in scalar registers -- then the addresses are wave-uniform and the coefficients
+ * come through scalar loads; the operations on B and W, and their order, are the same text. */
+__device__ __forceinline__ void shade_blend(const PtProbeShade &A, uint32_t x0, uint32_t y0, uint32_t z0, const double (&wx)[2],
+                                            const double (&wy)[2], const double (&wz)[2], V3 p, V3 n, bool valid, double (&B)[27], double &W)
+{
+  const PtGrid &G = A.grid;
+  const uint32_t x1 = G.count[0] >= 2u ? x0 + 1u : 0u, y1 = G.count[1] >= 2u ? y0 + 1u : 0u, z1 = G.count[2] >= 2u ? z0 + 1u : 0u;
+#pragma unroll
+  for (uint32_t c = 0; c < 8u; c++)
+  {
+    const uint32_t bx = c & 1u, by = (c >> 1) & 1u, bz = c >> 2;
+    const uint32_t ix = bx ? x1 : x0, iy = by ? y1 : y0, iz = bz ? z1 : z0;
+    double w = (wx[bx] * wy[by]) * wz[bz];
+    if (G.flags & PT_GRID_FACING)
+    {
+      const V3 v = {grid_at(G, 0, ix) - p.x, grid_at(G, 1, iy) - p.y, grid_at(G, 2, iz) - p.z};
+      const double q = (v.x * v.x + v.y * v.y) + v.z * v.z;
+      const double cs = q > 0.0 ? ((v.x * n.x + v.y * n.y) + v.z * n.z) * (1.0 / sqrt(q)) : 1.0;
+      const double s = (cs + 1.0) * 0.5;
+      w = w * (s * s + PT_GRID_FACE_FLOOR);
+    }
+    if (valid && w != 0.0) /* (a NaN weight does not skip) */
+    {
+      const double *__restrict__ const a = A.coeff + (size_t)((iz * G.count[1] + iy) * G.count[0] + ix) * (3u * PT_PROBE_SH);
+#pragma unroll
+      for (uint32_t k = 0; k < 27u; k++)
+        B[k] = B[k] + (w * a[k]);
+      W = W + w;
+    }
+  }
+}
+
+/* One thread an entry.  A lane beyond m shades entry m - 1 again and stores nothing, so that every lane of a wave reaches the
+ * wave-wide test: if the VALID lanes of the wave share one cell, its index goes to scalar registers (the first valid lane's, read
+ * across, and a vote that all agree) and shade_blend's loads become wave-uniform; a wave that straddles cells gathers per lane. */
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_shade(const PtProbeShade A)
+{
+  const uint32_t t = blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  const bool stores = t < A.m;
+  const size_t e = stores ? t : A.m - 1u;
+  const V3 p = ld3(A.points + 3u * e), n = ld3(A.normals + 3u * e);
+  const bool miss = A.status && A.status[e] != 1u;
+  /* x - x is +-0.0 for a finite x and NaN for any other */
+  const bool finite = ((p.x - p.x) + (p.y - p.y)) + (p.z - p.z) == 0.0 && ((n.x - n.x) + (n.y - n.y)) + (n.z - n.z) == 0.0;
+  const bool valid = !miss && finite;
+
+  double fx, fy, fz;
+  const uint32_t x0 = grid_cell(A.grid, 0, p.x, fx), y0 = grid_cell(A.grid, 1, p.y, fy), z0 = grid_cell(A.grid, 2, p.z, fz);
+  const double wx[2] = {1.0 - fx, fx}, wy[2] = {1.0 - fy, fy}, wz[2] = {1.0 - fz, fz};
+
+  double B[27], W = 0.0;
+#pragma unroll
+  for (uint32_t k = 0; k < 27u; k++)
+    B[k] = 0.0;
+#if PT_SHADE_UNIFORM
+  const unsigned long long voters = __ballot(valid);
+  if (voters != 0ull)
+  {
+    const int first = __builtin_ctzll(voters);
+    const uint32_t ux = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane((int)x0, first)),
+                   uy = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane((int)y0, first)),
+                   uz = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane((int)z0, first));
+    if (__all(!valid || (x0 == ux && y0 == uy && z0 == uz)))
+      shade_blend(A, ux, uy, uz, wx, wy, wz, p, n, valid, B, W);
+    else
+      shade_blend(A, x0, y0, z0, wx, wy, wz, p, n, valid, B, W);
+  }
+#else
+  shade_blend(A, x0, y0, z0, wx, wy, wz, p, n, valid, B, W);
+#endif
+
+  /* step 5 */
+  double E[3];
+#pragma unroll
+  for (uint32_t ch = 0; ch < 3u; ch++)
+  {
+    double s = 0.0;
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)PT_PROBE_SH; j++)
+    {
+      const double band = j == 0u ? PT_PROBE_A0 : (j < 4u ? PT_PROBE_A1 : PT_PROBE_A2);
+      s = s + (band * B[3u * j + ch]) * sh_basis(j, n.x, n.y, n.z);
+    }
+    s = s / W;
+    E[ch] = s < 0.0 ? 0.0 : s;
+  }
+  if (!stores)
+    return;
+  /* steps 6 and 7 */
+  if (A.irradiance)
+  {
+#pragma unroll
+    for (uint32_t ch = 0; ch < 3u; ch++)
+      A.irradiance[3u * e + ch] = miss ? 0.0 : (valid ? E[ch] : quiet_nan());
+  }
+  if (A.color)
+  {
+#pragma unroll
+    for (uint32_t ch = 0; ch < 3u; ch++)
+    {
+      const double add = A.add ? (double)A.add[3u * e + ch] : 0.0;
+      const double albedo = (double)(A.albedo ? A.albedo[3u * e + ch] : 1.0f);
+      const double lit = ((albedo * E[ch]) * PT_GRID_INV_PI) + add;
+      A.color[3u * e + ch] = miss ? (float)((double)A.grid.miss_color[ch] + add) : (valid ? (float)lit : (float)quiet_nan());
+    }
+  }
+}
+
+/* what rt_hip_probe_preview puts around the shade: the pixel centres, the emission of what a pixel's ray hit, the bytes */
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_pixel_centres(uint32_t width, uint32_t n, double w_minus_1, double h_minus_1,
+                                                                      double *__restrict__ uv)
+{
+  const uint32_t p = blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (p >= n)
+    return;
+  const uint32_t y = p / width, x = p - y * width;
+  uv[2u * (size_t)p + 0u] = ((double)x + 0.5) / w_minus_1;
+  uv[2u * (size_t)p + 1u] = ((double)y + 0.5) / h_minus_1;
+}
+
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_emission(const uint32_t *__restrict__ object, uint64_t n_values,
+                                                                 const double *__restrict__ emission, uint32_t stride, uint32_t n_objects,
+                                                                 float *__restrict__ add)
+{
+  const uint64_t t = (uint64_t)blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (t >= n_values)
+    return;
+  const uint64_t i = t / 3u;
+  const uint32_t c = (uint32_t)(t - 3u * i), o = object[i];
+  add[t] = o < n_objects ? (float)emission[(size_t)stride * o + c] : 0.0f;
+}
+
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_tonemap(const float *__restrict__ rgb, uint64_t n_values, uint8_t *__restrict__ rgb8)
+{
+  const uint64_t t = (uint64_t)blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (t < n_values)
+    rgb8[t] = tonemap((double)rgb[t]);
+}
+
 uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + PROBE_BLOCK - 1u) / PROBE_BLOCK); }
 
 } // namespace
@@ -185,5 +365,39 @@ hipError_t probe_launch_irradiance(const double *coeff, uint64_t n_probes, const
                                    double *irradiance, hipStream_t stream)
 {
   hipLaunchKernelGGL(k_probe_irradiance, dim3(blocks_for(3u * m)), dim3(PROBE_BLOCK), 0, stream, coeff, n_probes, index, normals, m, irradiance);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_grid_positions(const PtGrid &grid, double *positions, hipStream_t stream)
+{
+  const uint64_t n = (uint64_t)grid.count[0] * grid.count[1] * grid.count[2];
+  hipLaunchKernelGGL(k_probe_grid_positions, dim3(blocks_for(n)), dim3(PROBE_BLOCK), 0, stream, grid, positions);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_shade(const PtProbeShade &args, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_probe_shade, dim3(blocks_for(args.m)), dim3(PROBE_BLOCK), 0, stream, args);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_emission(const uint32_t *object, uint64_t n, const double *emission, uint32_t stride, uint32_t n_objects, float *add,
+                                 hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_probe_emission, dim3(blocks_for(3u * n)), dim3(PROBE_BLOCK), 0, stream, object, 3u * n, emission, stride, n_objects, add);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_tonemap(const float *rgb, uint64_t n_values, uint8_t *rgb8, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_probe_tonemap, dim3(blocks_for(n_values)), dim3(PROBE_BLOCK), 0, stream, rgb, n_values, rgb8);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_pixel_centres(uint32_t width, uint32_t height, double *uv, hipStream_t stream)
+{
+  const uint64_t n = (uint64_t)width * height;
+  hipLaunchKernelGGL(k_probe_pixel_centres, dim3(blocks_for(n)), dim3(PROBE_BLOCK), 0, stream, width, (uint32_t)n, (double)width - 1.0,
+                     (double)height - 1.0, uv);
   return hipGetLastError();
 }

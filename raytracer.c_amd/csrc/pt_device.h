@@ -57,6 +57,7 @@
 #define PT_SLICES 4         /* sample slices per pixel inside one wavefront */
 #define PT_BLOCK 256        /* 4 wavefronts: 64 pixels x 4 slices */
 #define PT_MAT_STRIDE 8     /* doubles per material record */
+#define PT_MAT_EMISSION 4   /* ... of which doubles 4 .. 6 are the emission (x, y, z) */
 #define PT_FILT_LDS_MAX 256  /* primitives up to which the filter table is also staged in LDS */
 #ifndef PT_BVH_LEAF
 #define PT_BVH_LEAF 15        /* max triangles per BVH leaf (< 2^PT_BVH_COUNT_BITS); config 5 at 4K x 256 spp: 2: 435 ms,
@@ -828,6 +829,47 @@ hipError_t probe_launch_resolve(const double *sum, uint64_t n_values, int32_t sa
 /* m >= 1 entries (probe index, normal): the irradiance of rt_hip.h from n_probes x PT_PROBE_SH x 3 coefficients, 3 doubles an entry */
 hipError_t probe_launch_irradiance(const double *coeff, uint64_t n_probes, const uint32_t *index, const double *normals, uint64_t m,
                                    double *irradiance, hipStream_t stream);
+#endif
+
+/* ---- probe grids (rt_hip.h, "probe grids"; the kernels are probe.hip's) ---- */
+#define PT_GRID_FACING 1u              /* RT_HIP_GRID_FACING */
+#define PT_GRID_FACE_FLOOR 0.2         /* face = s*s + PT_GRID_FACE_FLOOR */
+#define PT_GRID_INV_PI 0.3183098861837907 /* a Lambertian surface's radiance is albedo * E * (1 / pi) */
+
+/* A checked RtHipProbeGrid as the kernels take it */
+struct PtGrid
+{
+  double origin[3], step[3];
+  uint32_t count[3], flags;
+  float miss_color[3];
+};
+
+/* m entries shaded from the grid's n x PT_PROBE_SH x 3 coefficients; status, albedo and add may be null, irradiance or color too
+ * (not both) */
+struct PtProbeShade
+{
+  PtGrid grid;
+  const double *coeff, *points, *normals;
+  const uint32_t *status;
+  const float *albedo, *add;
+  double *irradiance;
+  float *color;
+  uint32_t m;
+};
+
+#if defined(__HIPCC__)
+/* the grid's n x 3 positions, a thread a probe */
+hipError_t probe_launch_grid_positions(const PtGrid &grid, double *positions, hipStream_t stream);
+/* m >= 1: rt_hip.h's probe shade, a thread an entry */
+hipError_t probe_launch_shade(const PtProbeShade &args, hipStream_t stream);
+/* add[3 i + c] = (float)emission[stride * object[i] + c] for object[i] < n_objects, else +0.0f: n entries, emission a table of
+ * n_objects records of `stride` doubles */
+hipError_t probe_launch_emission(const uint32_t *object, uint64_t n, const double *emission, uint32_t stride, uint32_t n_objects, float *add,
+                                 hipStream_t stream);
+/* rgb8 = pt_math.h's tonemap of (double)rgb, n_values values */
+hipError_t probe_launch_tonemap(const float *rgb, uint64_t n_values, uint8_t *rgb8, hipStream_t stream);
+/* uv[2 p] = ((double)x + 0.5) / ((double)width - 1.0), uv[2 p + 1] = ((double)y + 0.5) / ((double)height - 1.0), p = y * width + x */
+hipError_t probe_launch_pixel_centres(uint32_t width, uint32_t height, double *uv, hipStream_t stream);
 #endif
 
 

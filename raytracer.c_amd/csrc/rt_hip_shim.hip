@@ -3761,6 +3761,265 @@ int bake_probes_host_impl(const RtHipSphere *spheres, size_t n_spheres, const Rt
   });
 }
 
+/* ---- probe grids (rt_hip.h, rt_hip_probe_grid_* / rt_hip_probe_shade / rt_hip_probe_preview*) ------------------------------------
+ * The grid's checks need no device.  The bake is the positions and rt_hip_bake_probes' launch; the preview is a ray query, the
+ * first-hit albedo, the emission of what was hit, the shade and the bytes, each the call that exists. */
+uint64_t grid_probes(const RtHipProbeGrid *g) { return (uint64_t)g->count[0] * g->count[1] * g->count[2]; }
+
+/* what every grid call refuses in its grid without a device: RT_HIP_EINVAL, or RT_HIP_OK */
+int check_grid(const RtHipProbeGrid *g)
+{
+  if (!g)
+    return fail(RT_HIP_EINVAL, "grid is required");
+  if (g->struct_size < sizeof(RtHipProbeGrid))
+    return fail(RT_HIP_EINVAL, "grid->struct_size = %u is below the %zu of RtHipProbeGrid: start from rt_hip_probe_grid_defaults", g->struct_size,
+                sizeof(RtHipProbeGrid));
+  if ((g->flags & ~(uint32_t)RT_HIP_GRID_FACING) || g->reserved != 0u)
+    return fail(RT_HIP_EINVAL, "unknown grid flags 0x%x or reserved not 0", g->flags);
+  uint64_t n = 1;
+  for (int a = 0; a < 3; a++)
+  {
+    if (!(g->step[a] > 0) || !std::isfinite(g->step[a]) || !std::isfinite(g->origin[a]))
+      return fail(RT_HIP_EINVAL, "grid axis %d: the step %g must be finite and > 0, the origin %g finite", a, g->step[a], g->origin[a]);
+    if (!std::isfinite(g->miss_color[a]))
+      return fail(RT_HIP_EINVAL, "miss_color must be finite");
+    if (g->count[a] == 0u)
+      return fail(RT_HIP_EINVAL, "grid axis %d has no probe", a);
+    n *= g->count[a]; /* (at most 2^56 before the test below: below 2^24 after two factors, or refused at the third) */
+    if (n > (1u << 24))
+      return fail(RT_HIP_EINVAL, "the grid has more than 2^24 probes");
+  }
+  return RT_HIP_OK;
+}
+
+PtGrid grid_args(const RtHipProbeGrid *g)
+{
+  PtGrid G;
+  memset(&G, 0, sizeof G);
+  for (int a = 0; a < 3; a++)
+  {
+    G.origin[a] = g->origin[a];
+    G.step[a] = g->step[a];
+    G.count[a] = g->count[a];
+    G.miss_color[a] = g->miss_color[a];
+  }
+  G.flags = g->flags;
+  return G;
+}
+
+/* a grid bake's workspace: rt_hip_bake_probes' own, then the positions */
+size_t grid_bake_positions_at(uint64_t n_probes, uint64_t slice_rays) { return probe_workspace(n_probes, RT_HIP_PROBE_SPHERE, slice_rays).total; }
+
+int check_grid_bake(const RtHipProbeGrid *grid, const RtHipProbeParams *params)
+{
+  if (const int rc = check_grid(grid))
+    return rc;
+  if (const int rc = check_probe(params, grid_probes(grid), false))
+    return rc;
+  if (params->mode != RT_HIP_PROBE_SPHERE)
+    return fail(RT_HIP_EINVAL, "a grid is baked in RT_HIP_PROBE_SPHERE mode: its shade evaluates SH9 coefficients");
+  return RT_HIP_OK;
+}
+
+/* the two calls in sequence, on the scene's device */
+int bake_probe_grid_launch(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeParams *p, uint32_t slice_rays, void *d_workspace,
+                           double *d_coeff, float *d_coeff_f, uint32_t *d_status, uint64_t *d_stats, hipStream_t stream)
+{
+  const uint64_t n = grid_probes(grid), total = n * (uint64_t)p->samples;
+  double *const positions = reinterpret_cast<double *>(static_cast<char *>(d_workspace) + grid_bake_positions_at(n, std::min<uint64_t>(slice_rays, total)));
+  {
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    if (const int rc = launched(probe_launch_grid_positions(grid_args(grid), positions, stream), "k_probe_grid_positions"))
+      return rc;
+  }
+  return bake_probes_launch(scene, positions, nullptr, n, p, slice_rays, d_workspace, nullptr, d_coeff, d_coeff_f, d_status, d_stats, stream);
+}
+
+/* what rt_hip_probe_shade refuses without a device */
+int check_shade(const RtHipProbeGrid *grid, const double *coeff, const double *points, const double *normals, uint64_t m, const void *irradiance,
+                const void *color)
+{
+  if (const int rc = check_grid(grid))
+    return rc;
+  if (m > 0xFFFFFFFFull)
+    return fail(RT_HIP_EINVAL, "m = %llu: a call shades fewer than 2^32 entries", (unsigned long long)m);
+  if (!coeff || !points || !normals)
+    return fail(RT_HIP_EINVAL, "d_coeff, d_points and d_normals are required");
+  if (!irradiance && !color)
+    return fail(RT_HIP_EINVAL, "one of d_irradiance and d_color is required");
+  return RT_HIP_OK;
+}
+
+int shade_launch(const RtHipProbeGrid *grid, const double *d_coeff, const double *d_points, const double *d_normals, const uint32_t *d_status,
+                 const float *d_albedo, const float *d_add, uint64_t m, double *d_irradiance, float *d_color, hipStream_t stream)
+{
+  PtProbeShade A;
+  memset(&A, 0, sizeof A);
+  A.grid = grid_args(grid);
+  A.coeff = d_coeff;
+  A.points = d_points;
+  A.normals = d_normals;
+  A.status = d_status;
+  A.albedo = d_albedo;
+  A.add = d_add;
+  A.irradiance = d_irradiance;
+  A.color = d_color;
+  A.m = (uint32_t)m;
+  return launched(probe_launch_shade(A, stream), "k_probe_shade");
+}
+
+/* a preview's workspace for n pixels in tile_px tile pixels: the centres, the query's outputs, the albedo as tiles and as an image,
+ * the emission */
+struct PreviewWorkspace
+{
+  size_t uv, status, object, point, normal, albedo_tiles, albedo, add, total;
+  PreviewWorkspace(uint64_t n, uint64_t tile_px)
+  {
+    uv = 0;
+    status = uv + stage_align(16u * n);
+    object = status + stage_align(4u * n);
+    point = object + stage_align(4u * n);
+    normal = point + stage_align(24u * n);
+    albedo_tiles = normal + stage_align(24u * n);
+    albedo = albedo_tiles + stage_align(12u * tile_px);
+    add = albedo + stage_align(12u * n);
+    total = add + stage_align(12u * n);
+  }
+};
+
+uint64_t frame_tile_pixels(int32_t width, int32_t height) { return (uint64_t)tiles_x_of(width) * tiles_y_of(height) * PT_TILE_PIXELS; }
+
+/* what rt_hip_probe_preview refuses without a device */
+int check_preview(const RtHipCamera *camera, const RtHipProbeGrid *grid, int32_t width, int32_t height, int32_t aov_samples)
+{
+  if (const int rc = check_grid(grid))
+    return rc;
+  if (!camera)
+    return fail(RT_HIP_EINVAL, "camera is required");
+  if (!frame_size_ok(width, height, 2))
+    return fail(RT_HIP_EINVAL, "width and height must be in [2, 2^20] with fewer than 2^32 pixels");
+  if (aov_samples < 1 || aov_samples > (1 << 26))
+    return fail(RT_HIP_EINVAL, "aov_samples = %d must be in [1, 2^26]", aov_samples);
+  return RT_HIP_OK;
+}
+
+/* The preview on `stream`, no host wait: each step is the call the header names. */
+int probe_preview_launch(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid, const double *d_coeff, int32_t width,
+                         int32_t height, int32_t aov_samples, uint64_t seed, void *d_workspace, float *d_rgb, uint8_t *d_rgb8, hipStream_t stream)
+{
+  const uint64_t n = (uint64_t)width * (uint64_t)height;
+  const PreviewWorkspace W(n, frame_tile_pixels(width, height));
+  char *const ws = static_cast<char *>(d_workspace);
+  double *const uv = reinterpret_cast<double *>(ws + W.uv);
+  const RtHipHits hits = {reinterpret_cast<uint32_t *>(ws + W.status), nullptr, reinterpret_cast<uint32_t *>(ws + W.object), nullptr,
+                          reinterpret_cast<double *>(ws + W.point), reinterpret_cast<double *>(ws + W.normal), nullptr, nullptr};
+  float *const add = reinterpret_cast<float *>(ws + W.add);
+  RtHipQueryParams Q;
+  rt_hip_query_defaults(&Q);
+  Q.source = RT_HIP_RAYS_CAMERA_UV;
+  Q.camera = camera;
+  /* (the camera's distance: a hint, as a render launch of that camera has it; it changes no bit) */
+  Q.origin_radius = std::sqrt((camera->position[0] * camera->position[0] + camera->position[1] * camera->position[1]) +
+                              camera->position[2] * camera->position[2]);
+  if (const int rc = check_query(uv, true, n, &Q, &hits))
+    return rc;
+  {
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    if (const int rc = launched(probe_launch_pixel_centres((uint32_t)width, (uint32_t)height, uv, stream), "k_probe_pixel_centres"))
+      return rc;
+  }
+  if (const int rc = query_launch(scene, uv, nullptr, n, &Q, &hits, stream))
+    return rc;
+  RtHipParams P;
+  memset(&P, 0, sizeof P);
+  P.width = width;
+  P.height = height;
+  P.samples = aov_samples;
+  P.seed = seed;
+  whole_image(P);
+  const RtHipAov tiles = {reinterpret_cast<float *>(ws + W.albedo_tiles), nullptr, nullptr, nullptr, nullptr};
+  const RtHipAov image = {reinterpret_cast<float *>(ws + W.albedo), nullptr, nullptr, nullptr, nullptr};
+  if (const int rc = rt_hip_render_aov_tiles(scene, camera, &P, &tiles, stream))
+    return rc;
+  if (const int rc = rt_hip_untile_aov(&tiles, width, height, 0, 1, P.tile_count, &image, stream))
+    return rc;
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  /* the scene's material records hold the emission, spheres then meshes: rt_hip_scene_create's numbering */
+  if (const int rc = launched(probe_launch_emission(hits.object, n, scene->view.material + PT_MAT_EMISSION, PT_MAT_STRIDE, scene->view.n_spheres + scene->view.n_meshes,
+                                                    add, stream), "k_probe_emission"))
+    return rc;
+  if (const int rc = shade_launch(grid, d_coeff, hits.point, hits.normal, hits.status, image.albedo, add, n, nullptr, d_rgb, stream))
+    return rc;
+  return d_rgb8 ? launched(probe_launch_tonemap(d_rgb, 3u * n, d_rgb8, stream), "k_probe_tonemap") : (int)RT_HIP_OK;
+}
+
+/* what the preview's host forms refuse without a device */
+int check_preview_image(const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeParams *params, int32_t width, int32_t height,
+                        int32_t aov_samples, const void *h_rgb, const void *h_rgb8)
+{
+  if (const int rc = check_grid_bake(grid, params))
+    return rc;
+  if (const int rc = check_preview(camera, grid, width, height, aov_samples))
+    return rc;
+  if (!h_rgb && !h_rgb8)
+    return fail(RT_HIP_EINVAL, "one of h_rgb and h_rgb8 is required");
+  return RT_HIP_OK;
+}
+
+/* The preview's host forms on a scene, its device (`phys`) current: one allocation for both workspaces, the coefficients, the frame
+ * and the counters; the bake and the preview on the null stream, the copies, the device's status word. */
+int preview_image_of(const RtHipScene *scene, int phys, const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeParams *params,
+                     int32_t width, int32_t height, int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8, double *h_coeff, uint64_t *h_stats)
+{
+  const uint64_t n_probes = grid_probes(grid), total = n_probes * (uint64_t)params->samples, n = (uint64_t)width * (uint64_t)height;
+  const uint64_t slice = std::min<uint64_t>(HOST_SLICE, total);
+  StageArena A;
+  const int bake_ws = A.part(grid_bake_positions_at(n_probes, slice) + stage_align(24u * n_probes));
+  const int ws = A.part(PreviewWorkspace(n, frame_tile_pixels(width, height)).total);
+  const int coeff = A.part(24u * PT_PROBE_SH * n_probes, nullptr, h_coeff);
+  const int rgb = A.part(12u * n, nullptr, h_rgb);
+  const int rgb8 = A.part(3u * n, nullptr, h_rgb8, h_rgb8 != nullptr);
+  const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
+  int rc = A.stage();
+  if (rc)
+    return rc;
+  rc = bake_probe_grid_launch(scene, grid, params, HOST_SLICE, A.at<char>(bake_ws), A.at<double>(coeff), nullptr, nullptr, A.at<uint64_t>(stats),
+                              nullptr);
+  if (!rc)
+    rc = probe_preview_launch(scene, camera, grid, A.at<double>(coeff), width, height, aov_samples, params->seed, A.at<char>(ws),
+                              A.at<float>(rgb), A.at<uint8_t>(rgb8), nullptr);
+  return rc ? rc : download_then_status(A, phys);
+}
+
+/* rt_hip_probe_preview_image: ... with a scene of its own on the logical device */
+int probe_preview_image_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
+                             const RtHipProbeGrid *grid, const RtHipProbeParams *params, int32_t width, int32_t height, int32_t aov_samples,
+                             int device, float *h_rgb, uint8_t *h_rgb8, double *h_coeff, uint64_t *h_stats)
+{
+  if (const int rc = check_preview_image(camera, grid, params, width, height, aov_samples, h_rgb, h_rgb8))
+    return rc;
+  return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device, [&](const RtHipScene *scene, int phys) {
+    return preview_image_of(scene, phys, camera, grid, params, width, height, aov_samples, h_rgb, h_rgb8, h_coeff, h_stats);
+  });
+}
+
+/* rt_hip_probe_preview_scene_image: ... on a scene the caller holds, on that scene's device */
+int probe_preview_scene_image_impl(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeParams *params,
+                                   int32_t width, int32_t height, int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8, double *h_coeff,
+                                   uint64_t *h_stats)
+{
+  if (const int rc = check_preview_image(camera, grid, params, width, height, aov_samples, h_rgb, h_rgb8))
+    return rc;
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "scene is required");
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  return preview_image_of(scene, scene->device, camera, grid, params, width, height, aov_samples, h_rgb, h_rgb8, h_coeff, h_stats);
+}
+
 /* ---- pixel refinement (rt_hip.h, rt_hip_select_pixels / _trace_pixels / _blend_pixels) ---------------------------------------
  * select and blend are image-space calls like the upsampling: arguments checked without a device, then the device that holds the
  * first buffer.  trace_pixels is a radiance query's launch (trace_launch) whose rays the kernel forms itself: the frame's camera
@@ -5546,6 +5805,110 @@ int rt_hip_bake_probes_host(const RtHipSphere *spheres, size_t n_spheres, const 
   return guarded("rt_hip_bake_probes_host", [&] {
     return bake_probes_host_impl(spheres, n_spheres, meshes, n_meshes, h_positions, h_normals, n_probes, params, device, h_coeff, h_coeff_f,
                                  h_status, h_stats);
+  });
+}
+
+void rt_hip_probe_grid_defaults(RtHipProbeGrid *grid)
+{
+  if (!grid)
+    return;
+  memset(grid, 0, sizeof *grid);
+  grid->struct_size = (uint32_t)sizeof *grid;
+  for (int a = 0; a < 3; a++)
+  {
+    grid->step[a] = 1.0;
+    grid->count[a] = 1u;
+    grid->miss_color[a] = (float)(10.0 / 255.0);
+  }
+}
+
+int rt_hip_probe_grid_positions(const RtHipProbeGrid *grid, double *d_positions, void *stream)
+{
+  if (const int rc = check_grid(grid))
+    return rc;
+  if (!d_positions)
+    return fail(RT_HIP_EINVAL, "d_positions is required");
+  return on_device_of(d_positions, "d_positions", [&] {
+    return launched(probe_launch_grid_positions(grid_args(grid), d_positions, static_cast<hipStream_t>(stream)), "k_probe_grid_positions");
+  });
+}
+
+size_t rt_hip_probe_grid_workspace_bytes(const RtHipProbeGrid *grid, uint32_t slice_rays)
+{
+  if (slice_rays == 0u || check_grid(grid))
+    return 0;
+  const uint64_t n = grid_probes(grid);
+  return grid_bake_positions_at(n, slice_rays) + stage_align(24u * n);
+}
+
+int rt_hip_bake_probe_grid(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeParams *params, uint32_t slice_rays,
+                           void *d_workspace, double *d_coeff, float *d_coeff_f, uint32_t *d_status, uint64_t *d_stats, void *stream)
+{
+  if (const int rc = check_grid_bake(grid, params))
+    return rc;
+  if (slice_rays == 0u)
+    return fail(RT_HIP_EINVAL, "slice_rays must be >= 1");
+  if (const int rc = check_slice_buffers(d_workspace, nullptr))
+    return rc;
+  if (!scene || !d_workspace || !d_coeff)
+    return fail(RT_HIP_EINVAL, "scene, d_workspace and d_coeff are required");
+  return guarded("rt_hip_bake_probe_grid", [&] {
+    return bake_probe_grid_launch(scene, grid, params, slice_rays, d_workspace, d_coeff, d_coeff_f, d_status, d_stats, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_hip_probe_shade(const RtHipProbeGrid *grid, const double *d_coeff, const double *d_points, const double *d_normals,
+                       const uint32_t *d_status, const float *d_albedo, const float *d_add, uint64_t m, double *d_irradiance, float *d_color,
+                       void *stream)
+{
+  if (const int rc = check_shade(grid, d_coeff, d_points, d_normals, m, d_irradiance, d_color))
+    return rc;
+  if (m == 0)
+    return RT_HIP_OK;
+  return on_device_of(d_points, "d_points", [&] {
+    return shade_launch(grid, d_coeff, d_points, d_normals, d_status, d_albedo, d_add, m, d_irradiance, d_color, static_cast<hipStream_t>(stream));
+  });
+}
+
+size_t rt_hip_probe_preview_workspace_bytes(const RtHipScene *scene, int32_t width, int32_t height)
+{
+  (void)scene; /* (the size does not depend on the scene today) */
+  if (!frame_size_ok(width, height, 2))
+    return 0;
+  return PreviewWorkspace((uint64_t)width * (uint64_t)height, frame_tile_pixels(width, height)).total;
+}
+
+int rt_hip_probe_preview(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid, const double *d_coeff, int32_t width,
+                         int32_t height, int32_t aov_samples, uint64_t seed, void *d_workspace, float *d_rgb, uint8_t *d_rgb8, void *stream)
+{
+  if (const int rc = check_preview(camera, grid, width, height, aov_samples))
+    return rc;
+  if (!scene || !d_coeff || !d_workspace || !d_rgb)
+    return fail(RT_HIP_EINVAL, "scene, d_coeff, d_workspace and d_rgb are required");
+  if (reinterpret_cast<uintptr_t>(d_workspace) & 15u)
+    return fail(RT_HIP_EINVAL, "d_workspace must be 16-byte aligned");
+  return guarded("rt_hip_probe_preview", [&] {
+    return probe_preview_launch(scene, camera, grid, d_coeff, width, height, aov_samples, seed, d_workspace, d_rgb, d_rgb8,
+                                static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_hip_probe_preview_scene_image(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid,
+                                     const RtHipProbeParams *probe_params, int32_t width, int32_t height, int32_t aov_samples, float *h_rgb,
+                                     uint8_t *h_rgb8, double *h_coeff, uint64_t *h_stats)
+{
+  return guarded("rt_hip_probe_preview_scene_image", [&] {
+    return probe_preview_scene_image_impl(scene, camera, grid, probe_params, width, height, aov_samples, h_rgb, h_rgb8, h_coeff, h_stats);
+  });
+}
+
+int rt_hip_probe_preview_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipCamera *camera,
+                               const RtHipProbeGrid *grid, const RtHipProbeParams *probe_params, int32_t width, int32_t height,
+                               int32_t aov_samples, int device, float *h_rgb, uint8_t *h_rgb8, double *h_coeff, uint64_t *h_stats)
+{
+  return guarded("rt_hip_probe_preview_image", [&] {
+    return probe_preview_image_impl(spheres, n_spheres, meshes, n_meshes, camera, grid, probe_params, width, height, aov_samples, device, h_rgb,
+                                    h_rgb8, h_coeff, h_stats);
   });
 }
 

@@ -27,6 +27,8 @@
  *   -k <x,y,z>   a light probe instead of rendering: the 27 SH9 radiance coefficients of the chosen scene at that point
  *                (rt_hip_bake_probes_host, RT_HIP_PROBE_SPHERE, -s rays, -d and -r as given): status and nine lines of three
  *                channels.  Nothing is rendered or written.
+ *   -m <nx,ny,nz> the probe-lit preview in the frame's place (rt_set_probe_grid): a grid of nx x ny x nz light probes over the scene's
+ *                bounds, -s rays a probe, -d and -r as given; the PNG is rt_hip_probe_preview_image's frame.  One GPU.
  *   -u <f>       preview by guided upsampling, integer f >= 2 (upsample_frame, rt_hip_upsample's defaults, one GPU): the frame is
  *                rendered at ceil(w / f) x ceil(h / f) under the full size's camera (with -n: and denoised there), the first-hit
  *                buffers are rendered at both sizes, and the low frame is brought to w x h under the full-size buffers.  The PNG
@@ -127,6 +129,7 @@ typedef struct
   double lens_aperture, lens_focus; /* -l: the thin lens' aperture radius and focus distance */
   int probe;        /* -k given */
   double probe_at[3]; /* -k: the light probe's position */
+  int grid[3];      /* -m: probes an axis of the probe-lit preview; 0: not given */
   uint64_t seed;
 } Args;
 
@@ -144,7 +147,9 @@ static void usage(const char *prog)
           "          [-u <factor >= 2: render at 1/factor of the size, upsample under full-size first-hit buffers; <name>.low.png>]\n"
           "          [-l <aperture,focus: depth of field from a thin lens of that radius, sharp at that distance; one GPU, trace_path,\n"
           "               not with -p, -e or -u; aperture 0 is the pinhole frame>]\n"
-          "          [-k <x,y,z: print the 27 SH9 coefficients of a light probe there, -s rays, -d and -r as given; nothing is rendered>]\n",
+          "          [-k <x,y,z: print the 27 SH9 coefficients of a light probe there, -s rays, -d and -r as given; nothing is rendered>]\n"
+          "          [-m <nx,ny,nz: the probe-lit preview in the frame's place: a grid of that many light probes over the scene, -s rays a\n"
+          "               probe; one GPU, not with -p, -e, -u, -l or -i 1>]\n",
           prog);
 }
 
@@ -221,6 +226,20 @@ static int parse_args(int argc, char **argv, Args *a)
         at = end + 1;
       }
       a->probe = 1;
+      break;
+    }
+    case 'm':
+    {
+      const char *at = val;
+      for (int c = 0; c < 3; c++)
+      {
+        char *end = NULL;
+        const long n = strtol(at, &end, 10);
+        if (end == at || *end != (c < 2 ? ',' : '\0') || n < 1 || n > (1 << 24))
+          return -1;
+        a->grid[c] = (int)n;
+        at = end + 1;
+      }
       break;
     }
     case 'u':
@@ -435,7 +454,9 @@ int main(int argc, char **argv)
   if (rt_scene_info(a.config, &info) != 0 || a.options.width < 2 || a.options.height < 2 || a.options.samples < 1 ||
       (a.integrator != RT_TRACE_PATH && a.integrator != RT_CAST_RAY) ||
       (a.pass > 0 && (a.pass > a.options.samples || a.gpus > 1)) || (a.adaptive && (a.pass > 0 || a.gpus > 1)) ||
-      (a.lens && a.lens_aperture > 0 && (a.pass > 0 || a.adaptive || a.upsample || a.gpus > 1 || a.integrator != RT_TRACE_PATH)))
+      (a.lens && a.lens_aperture > 0 && (a.pass > 0 || a.adaptive || a.upsample || a.gpus > 1 || a.integrator != RT_TRACE_PATH)) ||
+      (a.grid[0] && (a.pass > 0 || a.adaptive || a.upsample || a.gpus > 1 || a.integrator != RT_TRACE_PATH || (a.lens && a.lens_aperture > 0) ||
+                     (long long)a.grid[0] * a.grid[1] * a.grid[2] > (1 << 24))))
   {
     usage(argv[0]);
     return EXIT_FAILURE;
@@ -477,6 +498,8 @@ int main(int argc, char **argv)
   rt_set_bvh_builder(a.bvh);
   if (a.lens)
     rt_set_lens(a.lens_aperture, a.lens_focus);
+  if (a.grid[0])
+    rt_set_probe_grid(a.grid[0], a.grid[1], a.grid[2]);
 
   if (a.upsample)
   {

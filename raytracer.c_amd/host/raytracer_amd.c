@@ -71,6 +71,24 @@ void rt_get_lens(double *aperture_radius, double *focus_distance)
   if (focus_distance)
     *focus_distance = g_lens_focus;
 }
+/* the probe grid of render() / render_ex(): probes an axis; all 0: off */
+static int g_probe_grid[3] = {0, 0, 0};
+void rt_set_probe_grid(int nx, int ny, int nz)
+{
+  const int on = nx >= 1 && ny >= 1 && nz >= 1;
+  g_probe_grid[0] = on ? nx : 0;
+  g_probe_grid[1] = on ? ny : 0;
+  g_probe_grid[2] = on ? nz : 0;
+}
+void rt_get_probe_grid(int *nx, int *ny, int *nz)
+{
+  if (nx)
+    *nx = g_probe_grid[0];
+  if (ny)
+    *ny = g_probe_grid[1];
+  if (nz)
+    *nz = g_probe_grid[2];
+}
 static int g_bvh_builder = RT_BVH_HOST;
 void rt_set_bvh_builder(int builder)
 {
@@ -285,6 +303,31 @@ static RtHipParams image_params(const Options *options)
   return p;
 }
 
+/* rt_set_probe_grid's grid for a scene: g_probe_grid probes an axis spanning [-reach, reach] about the world's origin, `reach` the
+ * scene's own bound (rt_hip_scene_bounds: >= |p| for every point of a primitive of ordinary size; 1 where the scene has none); an axis
+ * of one probe has it at 0.  origin = -reach, step = (2.0 * reach) / (double)(n - 1).  The bake's origin_radius is the cube's
+ * corner, sqrt(3.0) * reach, a shade more. */
+static int probe_grid_over(const RtHipScene *scene, RtHipProbeGrid *grid, RtHipProbeParams *pp)
+{
+  double reach = 0;
+  const int rc = rt_hip_scene_bounds(scene, NULL, NULL, &reach, NULL);
+  if (rc)
+    return rc;
+  if (!(reach > 0))
+    reach = 1.0;
+  rt_hip_probe_grid_defaults(grid);
+  for (int a = 0; a < 3; a++)
+  {
+    const int n = g_probe_grid[a];
+    grid->count[a] = (uint32_t)n;
+    grid->origin[a] = n >= 2 ? -reach : 0.0;
+    grid->step[a] = n >= 2 ? (2.0 * reach) / (double)(n - 1) : 1.0;
+  }
+  rt_hip_probe_defaults(pp);
+  pp->origin_radius = sqrt(3.0) * reach * 1.0000001;
+  return RT_HIP_OK;
+}
+
 void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects,
                MeshObject *meshes, size_t n_meshes, Camera *camera, Options *options)
 {
@@ -294,7 +337,30 @@ void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t 
   uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
   double seconds = 0;
   int rc;
-  if (g_lens_aperture > 0)
+  if (g_probe_grid[0] > 0)
+  { /* the probe-lit preview on ONE scene: a grid over its bounds, options->samples rays a probe, one first-hit sample a pixel */
+    RtHipScene *scene = NULL;
+    RtHipProbeGrid grid;
+    RtHipProbeParams pp;
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    rc = rt_hip_scene_create((const RtHipSphere *)objects, n_objects, hm, n_meshes, 0, &scene);
+    if (!rc)
+      rc = probe_grid_over(scene, &grid, &pp);
+    if (!rc)
+    {
+      pp.samples = p.samples;
+      pp.max_depth = p.max_depth;
+      pp.seed = p.seed;
+      rc = rt_hip_probe_preview_scene_image(scene, (const RtHipCamera *)camera, &grid, &pp, p.width, p.height, 1, linear_rgb, framebuffer, NULL,
+                                            stats);
+    }
+    if (scene)
+      rt_hip_scene_destroy(scene);
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    seconds = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+  }
+  else if (g_lens_aperture > 0)
   { /* depth of field: the lens frame, on one device; the seconds are the call's, by the host's clock */
     RtHipLens lens;
     rt_hip_lens_defaults(&lens);

@@ -157,6 +157,14 @@ class RtHipProbeParams(C.Structure):  # rt_hip.h: a light-probe bake (rt_hip_pro
                 ("bias", C.c_double), ("origin_radius", C.c_double), ("reserved", C.c_uint64)]
 
 
+GRID_FACING = 1   # RT_HIP_GRID_FACING
+
+
+class RtHipProbeGrid(C.Structure):  # rt_hip.h: a regular grid of probes (rt_hip_probe_grid_defaults), 88 B
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("origin", C.c_double * 3), ("step", C.c_double * 3),
+                ("count", C.c_uint32 * 3), ("miss_color", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
 class RtHipPixelParams(C.Structure):  # rt_hip.h: a pixel refinement's trace (rt_hip_pixel_defaults), 32 B
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("sample_first", C.c_int32),
                 ("max_depth", C.c_int32), ("integrator", C.c_uint32), ("seed", C.c_uint64)]
@@ -317,6 +325,21 @@ SHIM_SYMBOLS = {
     "rt_hip_probe_irradiance": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rt_hip_bake_probes_host": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64,
                                           C.POINTER(RtHipProbeParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_grid_defaults": (None, [C.POINTER(RtHipProbeGrid)]),
+    "rt_hip_probe_grid_positions": (C.c_int, [C.POINTER(RtHipProbeGrid), C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_grid_workspace_bytes": (C.c_size_t, [C.POINTER(RtHipProbeGrid), C.c_uint32]),
+    "rt_hip_bake_probe_grid": (C.c_int, [C.c_void_p, C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeParams), C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_shade": (C.c_int, [C.POINTER(RtHipProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_preview_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+    "rt_hip_probe_preview": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipProbeGrid), C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_preview_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.POINTER(Camera),
+                                             C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeParams), C.c_int32, C.c_int32, C.c_int32, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_preview_scene_image": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeParams), C.c_int32,
+                                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_denoise_defaults": (None, [C.POINTER(RtHipDenoiseParams)]),
     "rt_hip_denoise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rt_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_void_p,
@@ -387,6 +410,8 @@ HOST_SYMBOLS = {
     "rt_set_seed": (None, [C.c_uint64]),
     "rt_set_lens": (None, [C.c_double, C.c_double]),
     "rt_get_lens": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rt_set_probe_grid": (None, [C.c_int, C.c_int, C.c_int]),
+    "rt_get_probe_grid": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_set_integrator": (None, [C.c_int]),
     "rt_get_integrator": (C.c_int, []),
     "rt_set_bvh_builder": (None, [C.c_int]),
@@ -500,6 +525,19 @@ def probe_params(mode, samples, seed, max_depth=None, bias=0.0, origin_radius=0.
     if max_depth is not None:
         p.max_depth = max_depth
     return p
+
+
+def probe_grid(origin, step, count, facing=False, miss_color=None):
+    """rt_hip_probe_grid_defaults() with the given origin, step and count (three each) replaced; facing: RT_HIP_GRID_FACING;
+    miss_color None: the default"""
+    g = RtHipProbeGrid()
+    load_shim().rt_hip_probe_grid_defaults(C.byref(g))
+    for a in range(3):
+        g.origin[a], g.step[a], g.count[a] = origin[a], step[a], count[a]
+        if miss_color is not None:
+            g.miss_color[a] = miss_color[a]
+    g.flags = GRID_FACING if facing else 0
+    return g
 
 
 def reproject_params(max_history=None, depth_tol=None, normal_min=None):

@@ -605,6 +605,50 @@ class GpuScene:
         out = self._bake(abi.PROBE_HEMISPHERE, positions, normals, samples, seed, bias, max_depth, origin_radius, slice_rays, stats)
         return out if details else out["coeff"].reshape(-1, 3)
 
+    def bake_probe_grid(self, grid, samples, seed, max_depth=None, origin_radius=None, slice_rays=None, stats=None, details=False):
+        """A grid of sphere probes baked in one call (rt_hip.h, rt_hip_bake_probe_grid: the grid's positions, then rt_hip_bake_probes
+        at them); grid: abi.probe_grid(...) -> float64 [N, 9, 3] on the device, N = the grid's probes in index order (details: the dict
+        of coeff, coeff_f, status, stats).  origin_radius None: the farthest corner of the grid from the world's origin."""
+        dev = torch.device("cuda", self.device)
+        n = grid.count[0] * grid.count[1] * grid.count[2]
+        if origin_radius is None:
+            far = [max(abs(grid.origin[a]), abs(grid.origin[a] + (grid.count[a] - 1) * grid.step[a])) for a in range(3)]
+            origin_radius = _distance(far) * (1.0 + 2.0 ** -40)
+        p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, self.scene.max_depth if max_depth is None else max_depth, 0.0, origin_radius)
+        total = max(n * samples, 1)
+        slice_rays = total if slice_rays is None else slice_rays
+        ws = torch.empty(max(self.shim.rt_hip_probe_grid_workspace_bytes(C.byref(grid), max(min(slice_rays, total), 1)), 256), dtype=torch.uint8,
+                         device=dev)
+        out = dict(coeff=torch.empty((n, 9, 3), dtype=torch.float64, device=dev), coeff_f=torch.empty((n, 9, 3), dtype=torch.float32, device=dev),
+                   status=torch.empty(n, dtype=torch.int32, device=dev),
+                   stats=torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev) if stats is None else stats)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._probe_buffers = (ws,)   # keep alive until the stream has used them
+        _check(self.shim.rt_hip_bake_probe_grid(self.handle, C.byref(grid), C.byref(p), slice_rays, C.c_void_p(ws.data_ptr()),
+                                                C.c_void_p(out["coeff"].data_ptr()), C.c_void_p(out["coeff_f"].data_ptr()),
+                                                C.c_void_p(out["status"].data_ptr()), C.c_void_p(out["stats"].data_ptr()), C.c_void_p(stream)),
+               "rt_hip_bake_probe_grid")
+        return out if details else out["coeff"]
+
+    def probe_preview(self, grid, coeff, camera=None, aov_samples=1, seed=0):
+        """The probe-lit preview of the scene's frame (rt_hip.h, rt_hip_probe_preview): first hits at the pixel centres, their albedo
+        and emission, lit by the grid's baked coefficients coeff [N, 9, 3]; asynchronous on torch's current stream ->
+        (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3]) on the device"""
+        dev = torch.device("cuda", self.device)
+        w, h = self.scene.width, self.scene.height
+        coeff = torch.as_tensor(coeff, dtype=torch.float64, device=dev).contiguous()
+        if coeff.numel() != grid.count[0] * grid.count[1] * grid.count[2] * 27:
+            raise ValueError("probe_preview: coeff must hold 9 x 3 values per probe of the grid")
+        ws = torch.empty(max(self.shim.rt_hip_probe_preview_workspace_bytes(self.handle, w, h), 256), dtype=torch.uint8, device=dev)
+        rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._preview_buffers = (ws, coeff)   # keep alive until the stream has used them
+        _check(self.shim.rt_hip_probe_preview(self.handle, C.byref(camera if camera is not None else self.scene.camera), C.byref(grid),
+                                              C.c_void_p(coeff.data_ptr()), w, h, aov_samples, seed, C.c_void_p(ws.data_ptr()),
+                                              C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()), C.c_void_p(stream)), "rt_hip_probe_preview")
+        return rgb, rgb8
+
     def render_panorama(self, width, height, origin, samples, seed, max_depth=None):
         """An equirectangular view from `origin` (scene.panorama_rays: no Camera expresses it), `samples` paths per pixel, pixel
         k = y * width + x on the stream (seed, k, s) -> (float64 [height, width, 3] linear radiance on the device, stats)"""
@@ -1596,6 +1640,73 @@ def probe_irradiance(sh, index, normals):
                                         C.c_void_p(nrm.data_ptr() if m else None), m, C.c_void_p(out.data_ptr() if m else None),
                                         C.c_void_p(stream)), "rt_hip_probe_irradiance")
     return out
+
+
+def probe_grid_positions(grid, device=0):
+    """The positions of a grid's probes in index order (rt_hip.h, rt_hip_probe_grid_positions); grid: abi.probe_grid(...) ->
+    float64 [N, 3] on the device, asynchronous on torch's current stream"""
+    shim = abi.load_shim()
+    dev = torch.device("cuda", device)
+    out = torch.empty((grid.count[0] * grid.count[1] * grid.count[2], 3), dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_probe_grid_positions(C.byref(grid), C.c_void_p(out.data_ptr() if out.numel() else None), C.c_void_p(stream)),
+           "rt_hip_probe_grid_positions")
+    return out
+
+
+def probe_shade(grid, coeff, points, normals, status=None, albedo=None, add=None, want=("irradiance", "color"), out=None, m=None):
+    """Entries shaded from a grid of SH9 probes (rt_hip.h, rt_hip_probe_shade): coeff float64 [N, 9, 3] on a device, points and
+    normals [m, 3] float64 (a ray query's point and normal as they stand), status [m] (the query's words) or None, albedo and add
+    [m, 3] float32 or None -> dict of irradiance float64 [m, 3] and color float32 [m, 3] (want: which; out: a dict of tensors to write
+    into; m: shade the first m entries only); asynchronous on torch's current stream"""
+    shim = abi.load_shim()
+    coeff = coeff.contiguous()
+    dev = coeff.device
+    pts = torch.as_tensor(points, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+    nrm = torch.as_tensor(normals, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+    n = pts.shape[0]
+    if nrm.shape[0] != n:
+        raise ValueError(f"{nrm.shape[0]} normals for {n} points")
+    st = None if status is None else torch.as_tensor(status, device=dev).reshape(-1).contiguous()
+    if st is not None and st.dtype not in (torch.int32, torch.uint32):
+        st = st.to(torch.int32)
+    alb = None if albedo is None else torch.as_tensor(albedo, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
+    ad = None if add is None else torch.as_tensor(add, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
+    for name, t, per in (("status", st, 1), ("albedo", alb, 3), ("add", ad, 3)):
+        if t is not None and t.numel() != per * n:
+            raise ValueError(f"probe_shade: {name} must hold {per} value(s) per entry")
+    res = dict(out) if out is not None else {}
+    for f, dt in (("irradiance", torch.float64), ("color", torch.float32)):
+        if f in want and f not in res:
+            res[f] = torch.empty((n, 3), dtype=dt, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(shim.rt_hip_probe_shade(C.byref(grid), ptr(coeff), ptr(pts), ptr(nrm), ptr(st), ptr(alb), ptr(ad), n if m is None else m,
+                                   ptr(res.get("irradiance") if "irradiance" in want else None), ptr(res.get("color") if "color" in want else None),
+                                   C.c_void_p(stream)), "rt_hip_probe_shade")
+    return {f: res[f] for f in want}
+
+
+def probe_preview_host(scene, grid, samples, seed, camera=None, aov_samples=1, max_depth=None, origin_radius=None, device=0):
+    """rt_hip_probe_preview_image(): the C hosts' entry point (its own scene on logical device `device`, synchronous): the grid baked
+    with `samples` rays a probe under `seed`, then the preview of the scene's frame -> (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3],
+    coeff float64 [N, 9, 3], stats dict)"""
+    import numpy as np
+    shim = abi.load_shim()
+    n = grid.count[0] * grid.count[1] * grid.count[2]
+    if origin_radius is None:
+        far = [max(abs(grid.origin[a]), abs(grid.origin[a] + (grid.count[a] - 1) * grid.step[a])) for a in range(3)]
+        origin_radius = _distance(far) * (1.0 + 2.0 ** -40)
+    p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, scene.max_depth if max_depth is None else max_depth, 0.0, origin_radius)
+    img = np.zeros((scene.height, scene.width, 3), dtype=np.float32)
+    img8 = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
+    coeff = np.zeros((n, 9, 3), dtype=np.float64)
+    stats = (C.c_uint64 * abi.NSTATS)()
+    cam = camera if camera is not None else scene.camera
+    _check(shim.rt_hip_probe_preview_image(scene.objects, scene.n_objects, scene.hip_meshes(), scene.n_meshes, C.byref(cam), C.byref(grid),
+                                           C.byref(p), scene.width, scene.height, aov_samples, device, img.ctypes.data, img8.ctypes.data,
+                                           coeff.ctypes.data, stats), "rt_hip_probe_preview_image")
+    return img, img8, coeff, _stats_dict(stats)
 
 
 def bake_probes_host(scene, positions, samples, seed, normals=None, bias=0.0, max_depth=None, origin_radius=None, device=0):
