@@ -180,6 +180,7 @@ UPSAMPLE_DEMODULATE, UPSAMPLE_OBJECT_EDGES = 1, 2   # RT_HIP_UPSAMPLE_*
 
 AOV_FIELDS = ("albedo", "normal", "depth", "object", "hits")   # RtHipAov order
 AOV_CHANNELS = {"albedo": 3, "normal": 3, "depth": 1, "object": 1, "hits": 1}
+AOV_DTYPES = {"albedo": "float32", "normal": "float32", "depth": "float32", "object": "uint32", "hits": "uint32"}   # numpy's names
 ENODEV = -1                                                     # RT_HIP_ENODEV
 
 

@@ -4,7 +4,9 @@ pixel is computed by librt_hip.so.  There is no CPU / eager fallback: if the shi
 missing or no GPU is visible, calls raise.
 """
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 
 from . import abi
@@ -38,24 +40,66 @@ def _device_rays(rays, per_ray, dev):
     return rays.clone() if rays.data_ptr() % 16 else rays   # (a view into a larger tensor: the kernel loads 16 bytes at a time)
 
 
+_TORCH = {"float32": torch.float32, "float64": torch.float64, "uint32": torch.int32, "uint64": torch.int64}   # (the C-ABI's words, as torch holds them)
+
+
+def _stream(dev):
+    """torch's current stream on `dev`, as the shim takes it"""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _ptr(t):
+    """a tensor's address as the shim takes it (None: a null pointer)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _is(t, dev=None, n=None, dtype=None, size=None):
+    """The one tensor requirement: t is contiguous and -- of what is asked -- on `dev`, of n values, of this dtype, of this element
+    size.  The caller says what it asks and keeps its own refusal."""
+    return (dev is None or t.device == dev) and t.is_contiguous() and (n is None or t.numel() == n) and \
+        (dtype is None or t.dtype == dtype) and (size is None or t.element_size() == size)
+
+
 def _wanted(record, shapes, want, n, dev, samples=0, into=None):
     """The outputs `want` of an RtHipHits or an RtHipRadiance (`record`; shapes: abi.HIT_SHAPES or abi.RADIANCE_SHAPES) for n entries
     -> (dict, record): tensors on `dev` (the C-ABI's uint32 / uint64 words as int32 / int64; a field of `into` is used where given), or
     numpy arrays with dev None.  Each one's address goes into the record's field (n == 0 launches nothing: it only says "wanted")."""
-    import numpy as np
-    kinds = {"float64": torch.float64, "uint32": torch.int32, "uint64": torch.int64}
     out = {}
     for f in want:
         dtype, k = shapes[f]
         shape = (n, samples, 3) if f == "samples" else ((n, k) if k > 1 else (n,))
         if into is not None and f in into:
             out[f] = t = into[f]
-            if t.device != dev or t.dtype != kinds[dtype] or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"query: out[{f!r}] must be a contiguous {kinds[dtype]} tensor of shape {shape} on the scene's device")
+            if not _is(t, dev, dtype=_TORCH[dtype]) or tuple(t.shape) != shape:
+                raise ValueError(f"query: out[{f!r}] must be a contiguous {_TORCH[dtype]} tensor of shape {shape} on the scene's device")
         else:
-            out[f] = np.zeros(shape, dtype=dtype) if dev is None else torch.empty(shape, dtype=kinds[dtype], device=dev)
+            out[f] = np.zeros(shape, dtype=dtype) if dev is None else torch.empty(shape, dtype=_TORCH[dtype], device=dev)
         setattr(record, f, (out[f].ctypes.data if dev is None else out[f].data_ptr()) if n else 1)
     return out, record
+
+
+def _aov_record(bufs, fields, check=None, optional=False, host=False):
+    """The one RtHipAov builder: the addresses of bufs[f] for f in `fields`, device tensors or -- host -- arrays, which are converted to
+    the field's type (abi.AOV_DTYPES) and stay alive with the record.  optional: a field that is missing or None stays null.
+    check(f, buffer): the caller's requirement of a field; it raises the caller's refusal."""
+    a = abi.RtHipAov()
+    a.kept = []
+    for f in fields:
+        t = bufs.get(f) if optional else bufs[f]
+        if check is not None:
+            check(f, t)
+        if t is None:
+            continue
+        if host:
+            t = np.ascontiguousarray(t, dtype=abi.AOV_DTYPES[f])
+            a.kept.append(t)
+        setattr(a, f, t.ctypes.data if host else t.data_ptr())
+    return a
+
+
+def _aov_shape(f, *lead):
+    """the shape of field f's buffer of lead pixels: a trailing 3 where the field has three channels"""
+    return lead + ((3,) if abi.AOV_CHANNELS[f] == 3 else ())
 
 
 class GpuScene:
@@ -140,7 +184,6 @@ class GpuScene:
     def bvh_read(self):
         """(nodes, order): the fp64 source nodes as an (n_nodes, 16) float64 array -- two child boxes, the two refs in the
         bytes of column 12 -- and the leaf order as uint32 triangle indices"""
-        import numpy as np
         info = self.bvh_info()
         nodes = np.zeros((info["n_nodes"], abi.BVH_SRC_DOUBLES), dtype=np.float64)
         order = np.zeros(self.scene.n_triangles, dtype=np.uint32)
@@ -168,7 +211,6 @@ class GpuScene:
             # (a host tensor, or one on another device, goes to the device entry all the same: the shim refuses it)
             _check(self.shim.rt_hip_scene_update_vertices(self.handle, C.c_void_p(t.data_ptr()), n), "rt_hip_scene_update_vertices")
         else:
-            import numpy as np
             a = np.ascontiguousarray(positions, dtype=np.float64)
             if a.shape != (n, 3, 3):
                 raise ValueError(f"update_vertices: shape ({n}, 3, 3) is expected, not {a.shape}")
@@ -208,7 +250,6 @@ class GpuScene:
         r * r, not the radius, so they cannot be read back).  A caller that updates through the C ABI directly keeps its own copy:
         this one does not see that update.  What Temporal.frame(prev_spheres=...) takes as "now".  Not to be written."""
         if getattr(self, "_spheres", None) is None:
-            import numpy as np
             a = np.array([[o.center.x, o.center.y, o.center.z, o.radius] for o in self.scene.objects[:self.scene.n_objects]],
                          dtype=np.float64).reshape(-1, 4)
             self._spheres = torch.from_numpy(a).to(torch.device("cuda", self.device))
@@ -232,7 +273,6 @@ class GpuScene:
             _check(self.shim.rt_hip_scene_update_spheres(self.handle, C.c_void_p(t.data_ptr()), n), "rt_hip_scene_update_spheres")
             self._spheres = t.detach().clone()
             return
-        import numpy as np
         a = np.ascontiguousarray(spheres, dtype=np.float64)
         if a.shape != (n, 4):
             raise ValueError(f"update_spheres: shape ({n}, 4) is expected, not {a.shape}")
@@ -241,7 +281,6 @@ class GpuScene:
 
     def read_spheres(self):
         """for tests: dict of numpy arrays as the kernels read them -- entry (n, 6: cx cy cz r^2 |c| 0), geom4 (n, 4)"""
-        import numpy as np
         n = self.scene.n_objects
         out = dict(entry=np.zeros((n, 6)), geom4=np.zeros((n, 4)))
         _check(self.shim.rt_hip_scene_read_spheres(self.handle, *[out[k].ctypes.data if n else None for k in ("entry", "geom4")]),
@@ -268,7 +307,6 @@ class GpuScene:
     def read_triangles(self):
         """for tests: dict of numpy arrays as the kernels read them -- geom (n, 9: v0, e1, e2), normal (n, 3), entry (n, 6: the
         phase-1 bound), object (n, uint32: material slot and hull bits)"""
-        import numpy as np
         n = self.scene.n_triangles
         out = dict(geom=np.zeros((n, 9)), normal=np.zeros((n, 3)), entry=np.zeros((n, 6)), object=np.zeros(n, dtype=np.uint32))
         _check(self.shim.rt_hip_scene_read_triangles(self.handle, *[out[k].ctypes.data if n else None
@@ -301,7 +339,6 @@ class GpuScene:
         if stats is None:
             stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
         p = self.params(seed, first, stride, count, samples, max_depth, integrator)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         if chunks > 1 and workspace is None:
             workspace = torch.empty(self.shim.rt_hip_scene_chunk_workspace_bytes(self.handle, max(count, 1)), dtype=torch.uint8, device=dev)
         self._workspace = workspace  # keep alive until the stream has used it
@@ -309,7 +346,7 @@ class GpuScene:
                                                      C.byref(p), chunks,
                                                      workspace.data_ptr() if workspace is not None else None,
                                                      tiles.data_ptr(), tiles8.data_ptr(), stats.data_ptr(),
-                                                     C.c_void_p(stream)),
+                                                     _stream(dev)),
                "rt_hip_render_tiles_chunked")
         return tiles, tiles8, stats
 
@@ -334,10 +371,9 @@ class GpuScene:
             image = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
         if image8 is None and tiles8 is not None:
             image8 = torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _check(self.shim.rt_hip_untile(tiles.data_ptr(), tiles8.data_ptr() if tiles8 is not None else None, w, h,
                                        first, stride, count, image.data_ptr(),
-                                       image8.data_ptr() if image8 is not None else None, C.c_void_p(stream)),
+                                       image8.data_ptr() if image8 is not None else None, _stream(dev)),
                "rt_hip_untile")
         return image, image8
 
@@ -353,29 +389,23 @@ class GpuScene:
         if count is None:
             count = n_tiles(self.scene.width, self.scene.height)
         dev = torch.device("cuda", self.device)
-        out, aov = {}, abi.RtHipAov()
-        for f in want:
-            shape = (max(count, 1), abi.TILE_PIXELS) + ((3,) if abi.AOV_CHANNELS[f] == 3 else ())
-            out[f] = torch.empty(shape, dtype=torch.float32 if f in ("albedo", "normal", "depth") else torch.int32, device=dev)
-            setattr(aov, f, out[f].data_ptr())
+        out = {f: torch.empty(_aov_shape(f, max(count, 1), abi.TILE_PIXELS), dtype=_TORCH[abi.AOV_DTYPES[f]], device=dev) for f in want}
         p = self.params(seed, first, stride, count, samples)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _check(self.shim.rt_hip_render_aov_tiles(self.handle, C.byref(camera if camera is not None else self.scene.camera),
-                                                 C.byref(p), C.byref(aov), C.c_void_p(stream)), "rt_hip_render_aov_tiles")
+                                                 C.byref(p), C.byref(_aov_record(out, want)), _stream(dev)), "rt_hip_render_aov_tiles")
         return out
 
     def untile_aov(self, tiles, first, stride, count):
         """Scatter render_aov's compact buffers into row-major tensors ([H,W,3] / [H,W], zeros where no tile of the set lies)
         on torch's current stream"""
         w, h = self.scene.width, self.scene.height
-        src, dst, out = abi.RtHipAov(), abi.RtHipAov(), {}
-        for f, t in tiles.items():
-            out[f] = torch.zeros((h, w) + ((3,) if abi.AOV_CHANNELS[f] == 3 else ()), dtype=t.dtype, device=t.device)
-            setattr(src, f, t.data_ptr())
-            setattr(dst, f, out[f].data_ptr())
-        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-        _check(self.shim.rt_hip_untile_aov(C.byref(src), w, h, first, stride, count, C.byref(dst), C.c_void_p(stream)),
-               "rt_hip_untile_aov")
+        out = {f: torch.zeros(_aov_shape(f, h, w), dtype=t.dtype, device=t.device) for f, t in tiles.items()}
+        return self._untile_aov(tiles, first, stride, count, out)
+
+    def _untile_aov(self, tiles, first, stride, count, out):
+        """... into the row-major tensors `out` holds for the tiles' fields"""
+        _check(self.shim.rt_hip_untile_aov(C.byref(_aov_record(tiles, tiles)), self.scene.width, self.scene.height, first, stride, count,
+                                           C.byref(_aov_record(out, tiles)), _stream(torch.device("cuda", self.device))), "rt_hip_untile_aov")
         return out
 
     def aov_image(self, seed, samples):
@@ -384,10 +414,7 @@ class GpuScene:
         total = n_tiles(self.scene.width, self.scene.height)
         img = self.untile_aov(self.render_aov(seed, samples, 0, 1, total), 0, 1, total)
         torch.cuda.synchronize(torch.device("cuda", self.device))
-        out = {f: t.cpu().numpy() for f, t in img.items()}
-        for f in ("object", "hits"):
-            out[f] = out[f].view("uint32")
-        return out
+        return {f: t.cpu().numpy().view(abi.AOV_DTYPES[f]) for f, t in img.items()}
 
     def query_kernel_name(self):
         """the ray-query form this scene's query_rays / query_uv launches take"""
@@ -402,11 +429,10 @@ class GpuScene:
             if t_max.numel() != n:
                 raise ValueError("query: t_max must hold one value per ray")
         out, hits = _wanted(abi.RtHipHits(), abi.HIT_SHAPES, want, n, dev, into=into)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         self._query_inputs = (rays, t_max)   # keep alive until the stream has used them
         _check(self.shim.rt_hip_query_rays(self.handle, C.c_void_p(rays.data_ptr() if n else None),
                                            C.c_void_p(t_max.data_ptr()) if t_max is not None and n else None, n, C.byref(params),
-                                           C.byref(hits), C.c_void_p(stream)), "rt_hip_query_rays")
+                                           C.byref(hits), _stream(dev)), "rt_hip_query_rays")
         return out
 
     def query_rays(self, rays, t_max=None, normalize=False, origin_radius=None, want=abi.HIT_FIELDS):
@@ -447,10 +473,9 @@ class GpuScene:
         out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, dev, params.samples)
         if stats is None:
             stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         self._trace_inputs = rays   # keep alive until the stream has used them
         _check(self.shim.rt_hip_trace_rays(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.byref(params), C.byref(rad),
-                                           C.c_void_p(stats.data_ptr()), C.c_void_p(stream)), "rt_hip_trace_rays")
+                                           C.c_void_p(stats.data_ptr()), _stream(dev)), "rt_hip_trace_rays")
         out["stats"] = stats
         return out
 
@@ -500,11 +525,10 @@ class GpuScene:
         out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, dev, samples)
         if stats is None:
             stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         self._pixel_inputs = pixels   # keep alive until the stream has used them
         _check(self.shim.rt_hip_trace_pixels(self.handle, C.byref(camera if camera is not None else self.scene.camera),
                                              C.c_void_p(pixels.data_ptr() if n else None), n, C.byref(p), C.byref(rad),
-                                             C.c_void_p(stats.data_ptr()), C.c_void_p(stream)), "rt_hip_trace_pixels")
+                                             C.c_void_p(stats.data_ptr()), _stream(dev)), "rt_hip_trace_pixels")
         out["stats"] = stats
         return out
 
@@ -539,11 +563,10 @@ class GpuScene:
         total = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
         if stats is None:
             stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         self._lens_workspace = ws   # keep alive until the stream has used it
         _check(self.shim.rt_hip_render_lens(self.handle, C.byref(cam), C.byref(lens), C.byref(p), slice_pixels, C.c_void_p(ws.data_ptr()),
                                             C.c_void_p(total.data_ptr()), C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()),
-                                            C.c_void_p(stats.data_ptr()), C.c_void_p(stream)), "rt_hip_render_lens")
+                                            C.c_void_p(stats.data_ptr()), _stream(dev)), "rt_hip_render_lens")
         return rgb, rgb8, total, stats
 
     def focus_at(self, x, y, camera=None):
@@ -580,12 +603,11 @@ class GpuScene:
                    coeff_f=torch.empty((n, bases, 3), dtype=torch.float32, device=dev),
                    sum=torch.empty((n, bases, 3), dtype=torch.float64, device=dev), status=torch.empty(n, dtype=torch.int32, device=dev),
                    stats=torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev) if stats is None else stats)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         self._probe_buffers = (ws, pos, nrm)   # keep alive until the stream has used them
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
         _check(self.shim.rt_hip_bake_probes(self.handle, ptr(pos), ptr(nrm), n, C.byref(p), slice_rays, C.c_void_p(ws.data_ptr()), ptr(out["sum"]),
                                             ptr(out["coeff"]), ptr(out["coeff_f"]), ptr(out["status"]), C.c_void_p(out["stats"].data_ptr()),
-                                            C.c_void_p(stream)), "rt_hip_bake_probes")
+                                            _stream(dev)), "rt_hip_bake_probes")
         return out
 
     def bake_probes(self, positions, samples, seed, max_depth=None, origin_radius=None, slice_rays=None, stats=None, details=False):
@@ -622,11 +644,10 @@ class GpuScene:
         out = dict(coeff=torch.empty((n, 9, 3), dtype=torch.float64, device=dev), coeff_f=torch.empty((n, 9, 3), dtype=torch.float32, device=dev),
                    status=torch.empty(n, dtype=torch.int32, device=dev),
                    stats=torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev) if stats is None else stats)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         self._probe_buffers = (ws,)   # keep alive until the stream has used them
         _check(self.shim.rt_hip_bake_probe_grid(self.handle, C.byref(grid), C.byref(p), slice_rays, C.c_void_p(ws.data_ptr()),
                                                 C.c_void_p(out["coeff"].data_ptr()), C.c_void_p(out["coeff_f"].data_ptr()),
-                                                C.c_void_p(out["status"].data_ptr()), C.c_void_p(out["stats"].data_ptr()), C.c_void_p(stream)),
+                                                C.c_void_p(out["status"].data_ptr()), C.c_void_p(out["stats"].data_ptr()), _stream(dev)),
                "rt_hip_bake_probe_grid")
         return out if details else out["coeff"]
 
@@ -642,11 +663,10 @@ class GpuScene:
         ws = torch.empty(max(self.shim.rt_hip_probe_preview_workspace_bytes(self.handle, w, h), 256), dtype=torch.uint8, device=dev)
         rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
         rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         self._preview_buffers = (ws, coeff)   # keep alive until the stream has used them
         _check(self.shim.rt_hip_probe_preview(self.handle, C.byref(camera if camera is not None else self.scene.camera), C.byref(grid),
                                               C.c_void_p(coeff.data_ptr()), w, h, aov_samples, seed, C.c_void_p(ws.data_ptr()),
-                                              C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()), C.c_void_p(stream)), "rt_hip_probe_preview")
+                                              C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()), _stream(dev)), "rt_hip_probe_preview")
         return rgb, rgb8
 
     def render_panorama(self, width, height, origin, samples, seed, max_depth=None):
@@ -729,8 +749,7 @@ class Accumulation:
     def add(self, n, stats=None):
         """render the next n samples of every pixel; stats: an i64 [4] device tensor the pass's counters are added to"""
         dev = torch.device("cuda", self.gs.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(self.shim.rt_hip_accum_add(self.handle, n, stats.data_ptr() if stats is not None else None, C.c_void_p(stream)),
+        _check(self.shim.rt_hip_accum_add(self.handle, n, stats.data_ptr() if stats is not None else None, _stream(dev)),
                "rt_hip_accum_add")
         return stats
 
@@ -741,8 +760,7 @@ class Accumulation:
             tiles = torch.empty((self.count, abi.TILE_PIXELS, 3), dtype=torch.float32, device=dev)
         if tiles8 is None:
             tiles8 = torch.empty((self.count, abi.TILE_PIXELS, 3), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(self.shim.rt_hip_accum_resolve(self.handle, tiles.data_ptr(), tiles8.data_ptr(), C.c_void_p(stream)),
+        _check(self.shim.rt_hip_accum_resolve(self.handle, tiles.data_ptr(), tiles8.data_ptr(), _stream(dev)),
                "rt_hip_accum_resolve")
         return tiles, tiles8
 
@@ -774,26 +792,23 @@ class Accumulation:
         if (error is None) == (mask is None):
             raise ValueError("freeze(): give the tile errors or a mask")
         dev = torch.device("cuda", self.gs.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         live = C.c_uint32(0)
         if error is not None:
             p = abi.adapt_params(threshold=threshold, dilate=dilate)
-            if error.device != dev or error.dtype != torch.float32 or error.numel() != self.count or not error.is_contiguous():
+            if not _is(error, dev, self.count, torch.float32):
                 raise ValueError("freeze(): error must be a contiguous float32 tensor of one value per slot on the scene's device")
-            _check(self.shim.rt_hip_accum_freeze(self.handle, C.c_void_p(error.data_ptr()), p.threshold, p.dilate, C.byref(live),
-                                                 C.c_void_p(stream)), "rt_hip_accum_freeze")
+            _check(self.shim.rt_hip_accum_freeze(self.handle, _ptr(error), p.threshold, p.dilate, C.byref(live),
+                                                 _stream(dev)), "rt_hip_accum_freeze")
         else:
-            import numpy as np
             m = np.ascontiguousarray((mask.cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)) != 0, dtype=np.uint8)
             if m.size != self.count:
                 raise ValueError("freeze(): mask must hold one value per slot")
-            _check(self.shim.rt_hip_accum_freeze_mask(self.handle, C.c_void_p(m.ctypes.data), C.byref(live), C.c_void_p(stream)),
+            _check(self.shim.rt_hip_accum_freeze_mask(self.handle, C.c_void_p(m.ctypes.data), C.byref(live), _stream(dev)),
                    "rt_hip_accum_freeze_mask")
         return int(live.value)
 
     def tile_samples(self):
         """the sample-count map: numpy uint32 [count], how many samples each slot holds (synchronises)"""
-        import numpy as np
         out = np.zeros(self.count, dtype=np.uint32)
         _check(self.shim.rt_hip_accum_tile_samples(self.handle, C.c_void_p(out.ctypes.data)), "rt_hip_accum_tile_samples")
         return out
@@ -829,14 +844,12 @@ def tile_error(cur, prev, width, height, first=0, stride=1, count=None, out=None
     dev = cur.device
     if count is None:
         count = n_tiles(width, height)
-    for t in (cur, prev):
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != count * abi.TILE_PIXELS * 3:
-            raise ValueError("tile_error(): cur and prev must be contiguous float32 tile buffers of count x 64 x 3 on one device")
+    if not all(_is(t, dev, count * abi.TILE_PIXELS * 3, torch.float32) for t in (cur, prev)):
+        raise ValueError("tile_error(): cur and prev must be contiguous float32 tile buffers of count x 64 x 3 on one device")
     if out is None:
         out = torch.empty(count, dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(abi.load_shim().rt_hip_tile_error(C.c_void_p(cur.data_ptr()), C.c_void_p(prev.data_ptr()), width, height, first, stride,
-                                             count, C.c_void_p(out.data_ptr()), C.c_void_p(stream)), "rt_hip_tile_error")
+    _check(abi.load_shim().rt_hip_tile_error(_ptr(cur), _ptr(prev), width, height, first, stride, count, _ptr(out), _stream(dev)),
+           "rt_hip_tile_error")
     return out
 
 
@@ -851,26 +864,23 @@ def denoise(rgb, aov, width, height, out=None, **params):
     dev = rgb.device
     shim = abi.load_shim()
     p = abi.denoise_params(**params)
-    for t in [rgb] + list(aov.values()):
-        if t.device != dev or not t.is_contiguous():
-            raise ValueError("denoise(): every buffer must be a contiguous tensor on the colour's device")
+    if not all(_is(t, dev) for t in [rgb] + list(aov.values())):
+        raise ValueError("denoise(): every buffer must be a contiguous tensor on the colour's device")
     if rgb.dtype != torch.float32 or rgb.numel() != width * height * 3:
         raise ValueError("denoise(): rgb must be float32 of width * height * 3 values")
-    a = abi.RtHipAov()
-    for f, t in aov.items():
-        if f in abi.AOV_FIELDS:
-            if t.numel() != width * height * abi.AOV_CHANNELS[f]:
-                raise ValueError(f"denoise(): {f} must hold width * height * {abi.AOV_CHANNELS[f]} values")
-            setattr(a, f, t.data_ptr())
+
+    def check(f, t):   # (of a feature buffer the count alone is asked, not the type)
+        if t.numel() != width * height * abi.AOV_CHANNELS[f]:
+            raise ValueError(f"denoise(): {f} must hold width * height * {abi.AOV_CHANNELS[f]} values")
+    a = _aov_record(aov, [f for f in aov if f in abi.AOV_FIELDS], check)
     if out is None:
         out = torch.empty((height, width, 3), dtype=torch.float32, device=dev)
-    elif out.device != dev or out.dtype != torch.float32 or out.numel() != width * height * 3 or not out.is_contiguous():
+    elif not _is(out, dev, width * height * 3, torch.float32):
         raise ValueError("denoise(): out must be a contiguous float32 tensor of width * height * 3 values on the colour's device")
     out8 = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
     ws = torch.empty(max(shim.rt_hip_denoise_workspace_bytes(width, height), 1), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(shim.rt_hip_denoise(C.c_void_p(rgb.data_ptr()), C.byref(a), width, height, C.byref(p), C.c_void_p(ws.data_ptr()),
-                               C.c_void_p(out.data_ptr()), C.c_void_p(out8.data_ptr()), C.c_void_p(stream)), "rt_hip_denoise")
+    _check(shim.rt_hip_denoise(_ptr(rgb), C.byref(a), width, height, C.byref(p), _ptr(ws), _ptr(out), _ptr(out8), _stream(dev)),
+           "rt_hip_denoise")
     return out, out8
 
 
@@ -880,7 +890,6 @@ def _pixel_tensor(pixels, dev):
         if pixels.element_size() != 4 or pixels.is_floating_point():
             raise ValueError("pixel indices must be a 32-bit integer tensor (the uint32 words of the C-ABI)")
         return pixels.to(dev).contiguous().reshape(-1)
-    import numpy as np
     return torch.from_numpy(np.ascontiguousarray(np.asarray(pixels, dtype=np.uint32).reshape(-1)).view(np.int32)).to(dev)
 
 
@@ -891,20 +900,18 @@ def select_pixels(values, w, h, lo, hi, invert=False, capacity=None, indices=Non
     capacity None: w * h; 0: count only (indices is None).  indices: a tensor to write into."""
     dev = values.device
     shim = abi.load_shim()
-    if values.dtype != torch.float32 or not values.is_contiguous() or values.numel() != w * h:
+    if not _is(values, n=w * h, dtype=torch.float32):
         raise ValueError("select_pixels(): values must be a contiguous float32 tensor of w * h values")
     if capacity is None:
         capacity = indices.numel() if indices is not None else w * h
     if capacity and indices is None:
         indices = torch.empty(capacity, dtype=torch.int32, device=dev)
-    if capacity and (indices.device != dev or indices.element_size() != 4 or not indices.is_contiguous() or indices.numel() < capacity):
+    if capacity and (not _is(indices, dev, size=4) or indices.numel() < capacity):
         raise ValueError("select_pixels(): indices must be a contiguous 32-bit tensor of at least `capacity` entries on the map's device")
     ws = torch.empty(max(shim.rt_hip_select_workspace_bytes(w, h), 1), dtype=torch.uint8, device=dev)
     count = torch.zeros(1, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(shim.rt_hip_select_pixels(C.c_void_p(values.data_ptr()), w, h, lo, hi, abi.SELECT_INVERT if invert else 0,
-                                     C.c_void_p(ws.data_ptr()), C.c_void_p(indices.data_ptr()) if capacity else None, capacity,
-                                     C.c_void_p(count.data_ptr()), C.c_void_p(stream)), "rt_hip_select_pixels")
+    _check(shim.rt_hip_select_pixels(_ptr(values), w, h, lo, hi, abi.SELECT_INVERT if invert else 0, _ptr(ws),
+                                     _ptr(indices) if capacity else None, capacity, _ptr(count), _stream(dev)), "rt_hip_select_pixels")
     return (indices if capacity else None), int(count.cpu().numpy().view("uint32")[0])
 
 
@@ -918,26 +925,22 @@ def blend_pixels(pixels, status, radiance, rgb, w, h, new_weight, prior_scale=0.
     n = pixels.numel() if n is None else int(n)
     if n < 0 or n > pixels.numel() or status.numel() < n or radiance.numel() < 3 * n:
         raise ValueError("blend_pixels(): n must be within the list, its status and its radiance")
-    if status.device != dev or status.element_size() != 4 or not status.is_contiguous() or radiance.device != dev or \
-            radiance.dtype != torch.float64 or not radiance.is_contiguous():
+    if not _is(status, dev, size=4) or not _is(radiance, dev, dtype=torch.float64):
         raise ValueError("blend_pixels(): status (32-bit) and radiance (float64) must be contiguous tensors on the frame's device")
-    if rgb.dtype != torch.float32 or not rgb.is_contiguous() or rgb.numel() != w * h * 3:
+    if not _is(rgb, n=w * h * 3, dtype=torch.float32):
         raise ValueError("blend_pixels(): rgb must be a contiguous float32 tensor of w * h * 3 values")
     for t, dtype, k, what in ((prior, torch.float32, 1, "prior"), (weight, torch.float32, 1, "weight"), (rgb8, torch.uint8, 3, "rgb8")):
-        if t is not None and (t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != w * h * k):
+        if t is not None and not _is(t, dev, w * h * k, dtype):
             raise ValueError(f"blend_pixels(): {what} must be a contiguous {dtype} tensor of w * h * {k} values on the frame's device")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    _check(abi.load_shim().rt_hip_blend_pixels(ptr(pixels) if n else None, ptr(status) if n else None, ptr(radiance) if n else None, n, w, h,
-                                               new_weight, prior_scale, ptr(prior), ptr(rgb), ptr(rgb8), ptr(weight), C.c_void_p(stream)),
-           "rt_hip_blend_pixels")
+    lists = [_ptr(t) if n else None for t in (pixels, status, radiance)]   # (no entry: no list)
+    _check(abi.load_shim().rt_hip_blend_pixels(*lists, n, w, h, new_weight, prior_scale, _ptr(prior), _ptr(rgb), _ptr(rgb8), _ptr(weight),
+                                               _stream(dev)), "rt_hip_blend_pixels")
     return rgb
 
 
 def trace_pixels_host(scene, pixels, samples, seed, sample_first=0, camera=None, max_depth=None, device=0, want=("status", "radiance")):
     """rt_hip_trace_pixels_host(): the C hosts' entry point (its own scene and buffers on logical device `device`, synchronous) ->
     dict of numpy arrays: status uint32 [n], radiance float64 [n, 3], samples [n, samples, 3], paths / casts uint64 [n], and stats"""
-    import numpy as np
     shim = abi.load_shim()
     pixels = np.ascontiguousarray(np.asarray(pixels, dtype=np.uint32).reshape(-1))
     n = pixels.size
@@ -955,45 +958,40 @@ def trace_pixels_host(scene, pixels, samples, seed, sample_first=0, camera=None,
 REPROJECT_AOV = ("normal", "depth", "object", "hits")   # what rt_hip_reproject reads of a frame and of the history
 
 
-def _reproject_aov(aov, n, dev, what):
-    a = abi.RtHipAov()
-    for f in REPROJECT_AOV:
-        t = aov[f]
-        if t.device != dev or not t.is_contiguous() or t.element_size() != 4 or t.numel() != n * abi.AOV_CHANNELS[f]:
-            raise ValueError(f"reproject(): {what} {f} must be a contiguous 32-bit tensor of width * height * {abi.AOV_CHANNELS[f]} "
+def _frame_aov(name, aov, fields, n, dev, what, needed=False):
+    """The RtHipAov of a frame's row-major device buffers for reproject() / upsample(): each of `fields` a contiguous tensor of 4-byte
+    elements and n pixels on dev.  needed: a missing field is refused by name (else it is a KeyError)."""
+    def check(f, t):
+        if needed and f not in aov:
+            raise ValueError(f"{name}(): {what} {f} buffer is needed")
+        if not _is(t, dev, n * abi.AOV_CHANNELS[f], size=4):
+            raise ValueError(f"{name}(): {what} {f} must be a contiguous 32-bit tensor of width * height * {abi.AOV_CHANNELS[f]} "
                              "values on the colour's device")
-        setattr(a, f, t.data_ptr())
-    return a
+    return _aov_record(aov, fields, check, optional=needed)
 
 
-def prev_points(hits, positions, out=None):
-    """rt_hip_prev_points on torch device tensors, asynchronous on torch's current stream: where each hit point of a query was
-    before an update_vertices.  hits: a dict as GpuScene.query_rays / query_uv return it, with status, prim, bary and point;
-    positions: float64 (n_triangles, 3, 3), the positions the scene had at the previous frame, in update_vertices' layout (None:
-    no triangles); out: float64 [n, 3] to write into (it may be hits["point"]; None: allocated) -> float64 [n, 3], NaN where there
-    is no surface to follow (a miss, an invalid ray, a prim outside the positions)"""
-    st = hits["status"]
-    dev, n = st.device, int(st.numel())
-    h = abi.RtHipHits()
-    for f in ("status", "prim", "bary", "point"):
-        dtype, k = abi.HIT_SHAPES[f]
-        t = hits[f]
-        if t.device != dev or not t.is_contiguous() or t.numel() != n * k or t.dtype != (torch.float64 if dtype == "float64" else torch.int32):
-            raise ValueError(f"prev_points(): hits[{f!r}] must be a contiguous tensor of {n} x {k} values as a query returns it")
-        setattr(h, f, t.data_ptr() if n else 1)   # (n == 0 launches nothing; the pointer only says "given")
-    n_tri, pos = 0, None
-    if positions is not None:
-        if positions.dtype != torch.float64 or positions.dim() != 3 or tuple(positions.shape[1:]) != (3, 3) or positions.device != dev:
-            raise ValueError("prev_points(): positions must be a float64 tensor of shape (n_triangles, 3, 3) on the hits' device")
-        pos = positions.contiguous()
-        n_tri = int(pos.shape[0])
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    elif out.device != dev or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 3 * n:
-        raise ValueError(f"prev_points(): out must be a contiguous float64 tensor of {n} x 3 values on the hits' device")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(abi.load_shim().rt_hip_prev_points(C.byref(h), n, C.c_void_p(pos.data_ptr()) if n_tri else None, n_tri,
-                                              C.c_void_p(out.data_ptr() if n else 1), C.c_void_p(stream)), "rt_hip_prev_points")
+def _reproject_aov(aov, n, dev, what):
+    return _frame_aov("reproject", aov, REPROJECT_AOV, n, dev, what)
+
+
+def _upsample_aov(aov, n, dev, p, what):
+    need = ["normal", "depth", "hits"] + (["albedo"] if p.flags & abi.UPSAMPLE_DEMODULATE else []) + \
+           (["object"] if p.flags & abi.UPSAMPLE_OBJECT_EDGES else [])
+    return _frame_aov("upsample", aov, need, n, dev, what, needed=True)
+
+
+def _out_dict(name, out, shapes, dev):
+    """The one rule of an `out` dict, shapes: {field: (shape, dtype, optional)} -> the filled dict: what is missing is allocated, an
+    optional field given as None is not wanted and leaves the dict, what is given is checked."""
+    out = dict(out) if out else {}
+    for f, (shape, dtype, optional) in shapes.items():
+        if optional and f in out and out[f] is None:
+            del out[f]
+            continue
+        if f not in out:
+            out[f] = torch.empty(shape, dtype=dtype, device=dev)
+        if not _is(out[f], dev, math.prod(shape), dtype):
+            raise ValueError(f"{name}(): out[{f!r}] must be a contiguous {dtype} tensor of shape {shape} on the colour's device")
     return out
 
 
@@ -1009,90 +1007,86 @@ def _sphere_pair(name, spheres_prev, spheres_cur, check):
     return int(prev.shape[0]), prev, cur
 
 
+def _prev_points(name, hits, positions, spheres=None, out=None, device=None):
+    """The one body of prev_points(), prev_points_moved() and their host forms.  spheres: None (rt_hip_prev_points*) or the pair
+    (spheres_prev, spheres_cur) (rt_hip_prev_points_moved*, which reads hits["object"] too).  device None: torch tensors on the hits'
+    device, on torch's current stream; else numpy arrays and the host form on that logical device.  An array of no entries goes down
+    as the address 1: nothing reads it, it only says "given"."""
+    host = device is not None
+    address = (lambda a, some=True: a.ctypes.data if some else 1) if host else (lambda t, some=True: C.c_void_p(t.data_ptr() if some else 1))
+    h, dev, n = abi.RtHipHits(), None, None
+    h.kept = []   # (what a host form converted stays alive with the record)
+    for f in ("status", "prim", "bary", "point") if spheres is None else ("status", "prim", "object", "bary", "point"):
+        dtype, k = abi.HIT_SHAPES[f]
+        t = np.ascontiguousarray(hits[f], dtype=dtype) if host else hits[f]
+        if n is None:   # (status: it says how many)
+            dev, n = (None, t.size) if host else (t.device, int(t.numel()))
+        if host and t.size != n * k:
+            raise ValueError(f"{name}(): hits[{f!r}] must hold {n} x {k} values")
+        if not host and not _is(t, dev, n * k, _TORCH[dtype]):
+            raise ValueError(f"{name}(): hits[{f!r}] must be a contiguous tensor of {n} x {k} values as a query returns it")
+        h.kept.append(t)
+        setattr(h, f, (t.ctypes.data if host else t.data_ptr()) if n else 1)
+    pos = None
+    if positions is not None and host:
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3, 3)
+    elif positions is not None:
+        if positions.dtype != torch.float64 or positions.dim() != 3 or tuple(positions.shape[1:]) != (3, 3) or positions.device != dev:
+            raise ValueError(f"{name}(): positions must be a float64 tensor of shape (n_triangles, 3, 3) on the hits' device")
+        pos = positions.contiguous()
+    n_tri = 0 if pos is None else int(pos.shape[0])
+    moved = ()
+    if spheres is not None:
+        def check(t):
+            if host:
+                return np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 4)
+            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 4 or t.device != dev:
+                raise ValueError(f"{name}(): the spheres must be float64 tensors of shape (n_spheres, 4) on the hits' device")
+            return t.contiguous()
+        n_sph, sprev, scur = _sphere_pair(name, *spheres, check)
+        # (an empty pair is still "given": a sphere hit then has no sphere to ride, NaN)
+        moved = tuple(None if a is None else address(a, n_sph) for a in (sprev, scur)) + (n_sph,)
+    if host:
+        out = np.zeros((n, 3), np.float64)
+    elif out is None:
+        out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    elif not _is(out, dev, 3 * n, torch.float64):
+        raise ValueError(f"{name}(): out must be a contiguous float64 tensor of {n} x 3 values on the hits' device")
+    symbol = "rt_hip_" + name
+    _check(getattr(abi.load_shim(), symbol)(C.byref(h), n, address(pos) if n_tri else None, n_tri, *moved,
+                                            *((device, address(out, n)) if host else (address(out, n), _stream(dev)))), symbol)
+    return out
+
+
+def prev_points(hits, positions, out=None):
+    """rt_hip_prev_points on torch device tensors, asynchronous on torch's current stream: where each hit point of a query was
+    before an update_vertices.  hits: a dict as GpuScene.query_rays / query_uv return it, with status, prim, bary and point;
+    positions: float64 (n_triangles, 3, 3), the positions the scene had at the previous frame, in update_vertices' layout (None:
+    no triangles); out: float64 [n, 3] to write into (it may be hits["point"]; None: allocated) -> float64 [n, 3], NaN where there
+    is no surface to follow (a miss, an invalid ray, a prim outside the positions)"""
+    return _prev_points("prev_points", hits, positions, out=out)
+
+
 def prev_points_moved(hits, positions, spheres_prev, spheres_cur, out=None):
     """rt_hip_prev_points_moved on torch device tensors, asynchronous on torch's current stream: prev_points() across an
     update_spheres as well.  hits needs object too; spheres_prev / spheres_cur: float64 (n_spheres, 4), cx cy cz radius in object
     order, the spheres at the previous frame and now (both None: no sphere moved, prev_points() itself).  A hit on a sphere rides
     its translation and uniform scale; a sphere hit whose object is outside the arrays gives NaN."""
-    st = hits["status"]
-    dev, n = st.device, int(st.numel())
-    h = abi.RtHipHits()
-    for f in ("status", "prim", "object", "bary", "point"):
-        dtype, k = abi.HIT_SHAPES[f]
-        t = hits[f]
-        if t.device != dev or not t.is_contiguous() or t.numel() != n * k or t.dtype != (torch.float64 if dtype == "float64" else torch.int32):
-            raise ValueError(f"prev_points_moved(): hits[{f!r}] must be a contiguous tensor of {n} x {k} values as a query returns it")
-        setattr(h, f, t.data_ptr() if n else 1)
-    n_tri, pos = 0, None
-    if positions is not None:
-        if positions.dtype != torch.float64 or positions.dim() != 3 or tuple(positions.shape[1:]) != (3, 3) or positions.device != dev:
-            raise ValueError("prev_points_moved(): positions must be a float64 tensor of shape (n_triangles, 3, 3) on the hits' device")
-        pos = positions.contiguous()
-        n_tri = int(pos.shape[0])
-
-    def check(t):
-        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 4 or t.device != dev:
-            raise ValueError("prev_points_moved(): the spheres must be float64 tensors of shape (n_spheres, 4) on the hits' device")
-        return t.contiguous()
-    n_sph, sprev, scur = _sphere_pair("prev_points_moved", spheres_prev, spheres_cur, check)
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    elif out.device != dev or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 3 * n:
-        raise ValueError(f"prev_points_moved(): out must be a contiguous float64 tensor of {n} x 3 values on the hits' device")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    given = sprev is not None   # (an empty pair is still "given": a sphere hit then has no sphere to ride, NaN)
-    _check(abi.load_shim().rt_hip_prev_points_moved(C.byref(h), n, C.c_void_p(pos.data_ptr()) if n_tri else None, n_tri,
-                                                    C.c_void_p(sprev.data_ptr() if n_sph else 1) if given else None,
-                                                    C.c_void_p(scur.data_ptr() if n_sph else 1) if given else None, n_sph,
-                                                    C.c_void_p(out.data_ptr() if n else 1), C.c_void_p(stream)), "rt_hip_prev_points_moved")
-    return out
+    return _prev_points("prev_points_moved", hits, positions, (spheres_prev, spheres_cur), out)
 
 
 def prev_points_moved_host(hits, positions, spheres_prev, spheres_cur, device=0):
     """rt_hip_prev_points_moved_host(): host arrays, its own device buffers on logical device `device`, synchronous.  hits: numpy
     arrays with status, prim, object (uint32 [n]), bary (float64 [n, 2]) and point (float64 [n, 3]); positions: float64
     (n_triangles, 3, 3) or None; spheres_prev / spheres_cur: float64 (n_spheres, 4) or both None -> float64 [n, 3]"""
-    import numpy as np
-    arrs = {f: np.ascontiguousarray(hits[f], dtype=np.float64 if abi.HIT_SHAPES[f][0] == "float64" else np.uint32)
-            for f in ("status", "prim", "object", "bary", "point")}
-    n = arrs["status"].size
-    h = abi.RtHipHits()
-    for f, a in arrs.items():
-        if a.size != n * abi.HIT_SHAPES[f][1]:
-            raise ValueError(f"prev_points_moved_host(): hits[{f!r}] must hold {n} x {abi.HIT_SHAPES[f][1]} values")
-        setattr(h, f, a.ctypes.data if n else 1)
-    pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3, 3)
-    n_tri = 0 if pos is None else pos.shape[0]
-    n_sph, sprev, scur = _sphere_pair("prev_points_moved_host", spheres_prev, spheres_cur,
-                                      lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 4))
-    out = np.zeros((n, 3), np.float64)
-    given = sprev is not None
-    _check(abi.load_shim().rt_hip_prev_points_moved_host(C.byref(h), n, pos.ctypes.data if n_tri else None, n_tri,
-                                                         (sprev.ctypes.data if n_sph else 1) if given else None,
-                                                         (scur.ctypes.data if n_sph else 1) if given else None, n_sph, device,
-                                                         out.ctypes.data if n else 1), "rt_hip_prev_points_moved_host")
-    return out
+    return _prev_points("prev_points_moved_host", hits, positions, (spheres_prev, spheres_cur), device=device)
 
 
 def prev_points_host(hits, positions, device=0):
     """rt_hip_prev_points_host(): host arrays, its own device buffers on logical device `device`, synchronous.  hits: a dict of
     numpy arrays with status, prim (uint32 [n]), bary (float64 [n, 2]) and point (float64 [n, 3]); positions: float64
     (n_triangles, 3, 3) or None -> float64 [n, 3]"""
-    import numpy as np
-    arrs = {f: np.ascontiguousarray(hits[f], dtype=np.float64 if abi.HIT_SHAPES[f][0] == "float64" else np.uint32)
-            for f in ("status", "prim", "bary", "point")}
-    n = arrs["status"].size
-    h = abi.RtHipHits()
-    for f, a in arrs.items():
-        if a.size != n * abi.HIT_SHAPES[f][1]:
-            raise ValueError(f"prev_points_host(): hits[{f!r}] must hold {n} x {abi.HIT_SHAPES[f][1]} values")
-        setattr(h, f, a.ctypes.data if n else 1)
-    pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3, 3)
-    n_tri = 0 if pos is None else pos.shape[0]
-    out = np.zeros((n, 3), np.float64)
-    _check(abi.load_shim().rt_hip_prev_points_host(C.byref(h), n, pos.ctypes.data if n_tri else None, n_tri, device,
-                                                   out.ctypes.data if n else 1), "rt_hip_prev_points_host")
-    return out
+    return _prev_points("prev_points_host", hits, positions, device=device)
 
 
 def reproject(rgb, aov, camera, hist=None, out=None, prev_points=None, **params):
@@ -1118,34 +1112,20 @@ def reproject(rgb, aov, camera, hist=None, out=None, prev_points=None, **params)
     h_rgb = h_len = h_aov = h_cam = None
     if hist is not None:
         for f in ("rgb", "len"):
-            t = hist[f]
-            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n * (3 if f == "rgb" else 1):
+            if not _is(hist[f], dev, n * (3 if f == "rgb" else 1), torch.float32):
                 raise ValueError(f"reproject(): the history's {f} must be a contiguous float32 tensor of the frame's size on its device")
-        h_rgb, h_len = C.c_void_p(hist["rgb"].data_ptr()), C.c_void_p(hist["len"].data_ptr())
+        h_rgb, h_len = _ptr(hist["rgb"]), _ptr(hist["len"])
         h_aov, h_cam = C.byref(_reproject_aov(hist["aov"], n, dev, "the history's")), C.byref(hist["camera"])
-    out = dict(out) if out else {}
-    shapes = dict(rgb=((height, width, 3), torch.float32), len=((height, width), torch.float32),
-                  motion=((height, width, 2), torch.float32), rgb8=((height, width, 3), torch.uint8))
-    for f, (shape, dtype) in shapes.items():
-        if f in ("motion", "rgb8") and f in out and out[f] is None:
-            del out[f]
-            continue
-        if f not in out:
-            out[f] = torch.empty(shape, dtype=dtype, device=dev)
-        t = out[f]
-        if t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != shape[0] * shape[1] * (shape[2] if len(shape) > 2 else 1):
-            raise ValueError(f"reproject(): out[{f!r}] must be a contiguous {dtype} tensor of shape {shape} on the colour's device")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    outs = (C.c_void_p(out["rgb"].data_ptr()), C.c_void_p(out["rgb8"].data_ptr()) if "rgb8" in out else None,
-            C.c_void_p(out["len"].data_ptr()), C.c_void_p(out["motion"].data_ptr()) if "motion" in out else None, C.c_void_p(stream))
+    out = _out_dict("reproject", out, dict(rgb=((height, width, 3), torch.float32, False), len=((height, width), torch.float32, False),
+                                           motion=((height, width, 2), torch.float32, True), rgb8=((height, width, 3), torch.uint8, True)), dev)
+    frames = (_ptr(rgb), C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, width, height, C.byref(p))
+    outs = (_ptr(out["rgb"]), _ptr(out.get("rgb8")), _ptr(out["len"]), _ptr(out.get("motion")), _stream(dev))
     if prev_points is None:
-        _check(shim.rt_hip_reproject(C.c_void_p(rgb.data_ptr()), C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, width, height,
-                                     C.byref(p), *outs), "rt_hip_reproject")
+        _check(shim.rt_hip_reproject(*frames, *outs), "rt_hip_reproject")
         return out
-    if prev_points.device != dev or prev_points.dtype != torch.float64 or not prev_points.is_contiguous() or prev_points.numel() != 3 * n:
+    if not _is(prev_points, dev, 3 * n, torch.float64):
         raise ValueError("reproject(): prev_points must be a contiguous float64 tensor of width * height * 3 values on the colour's device")
-    _check(shim.rt_hip_reproject_points(C.c_void_p(rgb.data_ptr()), C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, width, height,
-                                        C.byref(p), C.c_void_p(prev_points.data_ptr()), *outs), "rt_hip_reproject_points")
+    _check(shim.rt_hip_reproject_points(*frames, _ptr(prev_points), *outs), "rt_hip_reproject_points")
     return out
 
 
@@ -1219,12 +1199,7 @@ class Temporal:
                                       chunks=chunks, camera=camera)
         gs.untile(tiles, None, 0, 1, total, image=cur["rgb"])
         at = gs.render_aov(seed, samples, 0, 1, total, camera=camera, want=DENOISE_AOV)
-        src, dst = abi.RtHipAov(), abi.RtHipAov()
-        for f, t in at.items():
-            setattr(src, f, t.data_ptr())
-            setattr(dst, f, cur["aov"][f].data_ptr())
-        stream = torch.cuda.current_stream(torch.device("cuda", gs.device)).cuda_stream
-        _check(gs.shim.rt_hip_untile_aov(C.byref(src), w, h, 0, 1, total, C.byref(dst), C.c_void_p(stream)), "rt_hip_untile_aov")
+        gs._untile_aov(at, 0, 1, total, cur["aov"])
         C.memmove(C.byref(cur["camera"]), C.byref(camera), C.sizeof(abi.Camera))
         points = None
         if (prev_positions is not None or prev_spheres is not None) and self.frames:
@@ -1259,57 +1234,31 @@ def reproject_image_host(rgb, aov, camera, hist=None, device=0, prev_points=None
     synchronous).  rgb float32 [H,W,3], aov a dict of numpy arrays as GpuScene.aov_image gives them, hist None or a dict with rgb,
     len, aov and camera; prev_points: None, or float64 [H,W,3] (rt_hip_reproject_points_image) -> dict of numpy arrays: rgb,
     rgb8, len, motion"""
-    import numpy as np
     shim = abi.load_shim()
     p = abi.reproject_params(**params)
     h, w = rgb.shape[:2]
-    keep = []
-
-    def pack(bufs):
-        a = abi.RtHipAov()
-        for f in REPROJECT_AOV:
-            arr = np.ascontiguousarray(bufs[f], dtype=np.float32 if f in ("normal", "depth") else np.uint32)
-            keep.append(arr)
-            setattr(a, f, arr.ctypes.data)
-        return a
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    a = pack(aov)
+    a = _aov_record(aov, REPROJECT_AOV, host=True)
     h_rgb = h_len = h_aov = h_cam = None
     if hist is not None:
         hr, hl = np.ascontiguousarray(hist["rgb"], dtype=np.float32), np.ascontiguousarray(hist["len"], dtype=np.float32)
-        keep += [hr, hl]
-        h_rgb, h_len, h_aov, h_cam = hr.ctypes.data, hl.ctypes.data, C.byref(pack(hist["aov"])), C.byref(hist["camera"])
+        h_rgb, h_len = hr.ctypes.data, hl.ctypes.data
+        h_aov, h_cam = C.byref(_aov_record(hist["aov"], REPROJECT_AOV, host=True)), C.byref(hist["camera"])
     out = dict(rgb=np.zeros((h, w, 3), np.float32), rgb8=np.zeros((h, w, 3), np.uint8), len=np.zeros((h, w), np.float32),
                motion=np.zeros((h, w, 2), np.float32))
+    frames = (rgb.ctypes.data, C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, w, h, C.byref(p))
     outs = (out["rgb"].ctypes.data, out["rgb8"].ctypes.data, out["len"].ctypes.data, out["motion"].ctypes.data)
     if prev_points is None:
-        _check(shim.rt_hip_reproject_image(rgb.ctypes.data, C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, w, h, C.byref(p), device,
-                                           *outs), "rt_hip_reproject_image")
+        _check(shim.rt_hip_reproject_image(*frames, device, *outs), "rt_hip_reproject_image")
         return out
     pts = np.ascontiguousarray(prev_points, dtype=np.float64)
     if pts.size != 3 * w * h:
         raise ValueError("reproject_image_host(): prev_points must hold width * height * 3 values")
-    _check(shim.rt_hip_reproject_points_image(rgb.ctypes.data, C.byref(a), C.byref(camera), h_rgb, h_len, h_aov, h_cam, w, h, C.byref(p),
-                                              pts.ctypes.data, device, *outs), "rt_hip_reproject_points_image")
+    _check(shim.rt_hip_reproject_points_image(*frames, pts.ctypes.data, device, *outs), "rt_hip_reproject_points_image")
     return out
 
 
 UPSAMPLE_AOV = ("albedo", "normal", "depth", "object", "hits")   # what rt_hip_upsample may read (albedo, object: by the flags)
-
-
-def _upsample_aov(aov, n, dev, p, what):
-    need = ["normal", "depth", "hits"] + (["albedo"] if p.flags & abi.UPSAMPLE_DEMODULATE else []) + \
-           (["object"] if p.flags & abi.UPSAMPLE_OBJECT_EDGES else [])
-    a = abi.RtHipAov()
-    for f in need:
-        if f not in aov:
-            raise ValueError(f"upsample(): {what} {f} buffer is needed")
-        t = aov[f]
-        if t.device != dev or not t.is_contiguous() or t.element_size() != 4 or t.numel() != n * abi.AOV_CHANNELS[f]:
-            raise ValueError(f"upsample(): {what} {f} must be a contiguous 32-bit tensor of width * height * {abi.AOV_CHANNELS[f]} "
-                             "values on the colour's device")
-        setattr(a, f, t.data_ptr())
-    return a
 
 
 def upsample(low_rgb, low_aov, wl, hl, aov, w, h, out=None, **params):
@@ -1321,24 +1270,13 @@ def upsample(low_rgb, low_aov, wl, hl, aov, w, h, out=None, **params):
     dev = low_rgb.device
     shim = abi.load_shim()
     p = abi.upsample_params(**params)
-    if low_rgb.dtype != torch.float32 or not low_rgb.is_contiguous() or low_rgb.numel() != wl * hl * 3:
+    if not _is(low_rgb, n=wl * hl * 3, dtype=torch.float32):
         raise ValueError("upsample(): low_rgb must be a contiguous float32 tensor of wl * hl * 3 values")
     la, a = _upsample_aov(low_aov, wl * hl, dev, p, "the low frame's"), _upsample_aov(aov, w * h, dev, p, "the full frame's")
-    out = dict(out) if out else {}
-    shapes = dict(rgb=((h, w, 3), torch.float32), rgb8=((h, w, 3), torch.uint8), conf=((h, w), torch.float32))
-    for f, (shape, dtype) in shapes.items():
-        if f in ("rgb8", "conf") and f in out and out[f] is None:
-            del out[f]
-            continue
-        if f not in out:
-            out[f] = torch.empty(shape, dtype=dtype, device=dev)
-        t = out[f]
-        if t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != w * h * (shape[2] if len(shape) > 2 else 1):
-            raise ValueError(f"upsample(): out[{f!r}] must be a contiguous {dtype} tensor of shape {shape} on the colour's device")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(shim.rt_hip_upsample(C.c_void_p(low_rgb.data_ptr()), C.byref(la), wl, hl, C.byref(a), w, h, C.byref(p),
-                                C.c_void_p(out["rgb"].data_ptr()), C.c_void_p(out["rgb8"].data_ptr()) if "rgb8" in out else None,
-                                C.c_void_p(out["conf"].data_ptr()) if "conf" in out else None, C.c_void_p(stream)), "rt_hip_upsample")
+    out = _out_dict("upsample", out, dict(rgb=((h, w, 3), torch.float32, False), rgb8=((h, w, 3), torch.uint8, True),
+                                          conf=((h, w), torch.float32, True)), dev)
+    _check(shim.rt_hip_upsample(_ptr(low_rgb), C.byref(la), wl, hl, C.byref(a), w, h, C.byref(p), _ptr(out["rgb"]), _ptr(out.get("rgb8")),
+                                _ptr(out.get("conf")), _stream(dev)), "rt_hip_upsample")
     return out
 
 
@@ -1403,31 +1341,20 @@ def upsample_image_host(low_rgb, low_aov, aov, device=0, **params):
     """rt_hip_upsample_image(): the C hosts' entry point (host arrays, its own device buffers on logical device `device`,
     synchronous).  low_rgb float32 [hl,wl,3], low_aov and aov dicts of numpy arrays as GpuScene.aov_image gives them at the two
     sizes -> dict of numpy arrays: rgb, rgb8, conf"""
-    import numpy as np
     shim = abi.load_shim()
     p = abi.upsample_params(**params)
-    keep = []
-
-    def pack(bufs):
-        a = abi.RtHipAov()
-        for f in UPSAMPLE_AOV:
-            if f in bufs and bufs[f] is not None:
-                arr = np.ascontiguousarray(bufs[f], dtype=np.float32 if f in ("albedo", "normal", "depth") else np.uint32)
-                keep.append(arr)
-                setattr(a, f, arr.ctypes.data)
-        return a
+    la, a = (_aov_record(bufs, UPSAMPLE_AOV, optional=True, host=True) for bufs in (low_aov, aov))
     low_rgb = np.ascontiguousarray(low_rgb, dtype=np.float32)
     hl, wl = low_rgb.shape[:2]
     h, w = np.asarray(aov["depth"]).shape
     out = dict(rgb=np.zeros((h, w, 3), np.float32), rgb8=np.zeros((h, w, 3), np.uint8), conf=np.zeros((h, w), np.float32))
-    _check(shim.rt_hip_upsample_image(low_rgb.ctypes.data, C.byref(pack(low_aov)), wl, hl, C.byref(pack(aov)), w, h, C.byref(p), device,
+    _check(shim.rt_hip_upsample_image(low_rgb.ctypes.data, C.byref(la), wl, hl, C.byref(a), w, h, C.byref(p), device,
                                       out["rgb"].ctypes.data, out["rgb8"].ctypes.data, out["conf"].ctypes.data), "rt_hip_upsample_image")
     return out
 
 
 def render_image_host(scene, seed, n_devices=1, samples=None, max_depth=None, integrator="path"):
     """rt_hip_render_image(): the C hosts' entry point (host buffers, synchronous)."""
-    import numpy as np
     shim = abi.load_shim()
     p = abi.RtHipParams()
     p.width, p.height = scene.width, scene.height
@@ -1449,18 +1376,14 @@ def render_image_host(scene, seed, n_devices=1, samples=None, max_depth=None, in
 def aov_image_host(scene, seed, samples, device=0):
     """rt_hip_render_aov_image(): the C hosts' entry point (its own scene on logical device `device`, synchronous) -> dict of
     row-major numpy arrays as GpuScene.aov_image"""
-    import numpy as np
     shim = abi.load_shim()
     p = abi.RtHipParams()
     p.width, p.height, p.samples, p.seed = scene.width, scene.height, samples, seed
     h, w = scene.height, scene.width
-    out, aov = {}, abi.RtHipAov()
-    for f in abi.AOV_FIELDS:
-        out[f] = np.zeros((h, w, 3) if abi.AOV_CHANNELS[f] == 3 else (h, w), dtype=np.float32 if f in ("albedo", "normal", "depth") else np.uint32)
-        setattr(aov, f, out[f].ctypes.data)
+    out = {f: np.zeros(_aov_shape(f, h, w), dtype=abi.AOV_DTYPES[f]) for f in abi.AOV_FIELDS}
     meshes = scene.hip_meshes()
     _check(shim.rt_hip_render_aov_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera), C.byref(p),
-                                        device, C.byref(aov)), "rt_hip_render_aov_image")
+                                        device, C.byref(_aov_record(out, abi.AOV_FIELDS, host=True))), "rt_hip_render_aov_image")
     return out
 
 
@@ -1468,7 +1391,6 @@ def adaptive_image_host(scene, seed, samples, device=0, max_depth=None, integrat
     """rt_hip_render_adaptive_image(): the C hosts' entry point (its own scene and accumulation on logical device `device`,
     synchronous; params: abi.adapt_params' keywords) -> (image f32 [H,W,3], image8 u8 [H,W,3], tile sample counts uint32
     [tiles_y, tiles_x], stats dict, device seconds)"""
-    import numpy as np
     shim = abi.load_shim()
     p = abi.RtHipParams()
     p.width, p.height, p.samples, p.seed = scene.width, scene.height, samples, seed
@@ -1491,7 +1413,6 @@ def query_rays_host(scene, rays, t_max=None, normalize=False, origin_radius=None
     """rt_hip_query_rays_host(): the C hosts' entry point (its own scene and buffers on logical device `device`, synchronous).
     rays: [n, 6] float64 (origin, direction), or with `camera` (an abi.Camera) [n, 2] (u, v) -> dict of numpy arrays: status /
     object / prim uint32 [n], t float64 [n], point / normal [n, 3], bary [n, 2], ray [n, 6]"""
-    import numpy as np
     shim = abi.load_shim()
     per_ray = 2 if camera is not None else 6
     rays = np.ascontiguousarray(np.asarray(rays, dtype=np.float64).reshape(-1, per_ray))
@@ -1514,7 +1435,6 @@ def trace_rays_host(scene, rays, samples, seed, max_depth=None, normalize=False,
     """rt_hip_trace_rays_host(): the C hosts' entry point (its own scene and buffers on logical device `device`, synchronous).
     rays: [n, 6] float64 (origin, direction), or with `camera` (an abi.Camera) [n, 2] (u, v) -> dict of numpy arrays: status uint32
     [n], radiance float64 [n, 3], samples [n, samples, 3], paths / casts uint64 [n], ray [n, 6], and stats (a dict)"""
-    import numpy as np
     shim = abi.load_shim()
     per_ray = 2 if camera is not None else 6
     rays = np.ascontiguousarray(np.asarray(rays, dtype=np.float64).reshape(-1, per_ray))
@@ -1538,9 +1458,8 @@ def lens_rays(camera, width, height, aperture, focus, seed, sample, pixel_first=
     n = width * height - pixel_first if n is None else n
     rays = torch.empty((max(n, 0), 6), dtype=torch.float64, device=dev)
     lens = abi.lens_params(aperture, focus)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     _check(shim.rt_hip_lens_rays(C.byref(camera), C.byref(lens), width, height, seed, sample, pixel_first, n,
-                                 C.c_void_p(rays.data_ptr() if n > 0 else None), C.c_void_p(stream)), "rt_hip_lens_rays")
+                                 C.c_void_p(rays.data_ptr() if n > 0 else None), _stream(dev)), "rt_hip_lens_rays")
     return rays
 
 
@@ -1552,16 +1471,14 @@ def lens_resolve(total, samples):
     h, w, _ = total.shape
     rgb = torch.empty((h, w, 3), dtype=torch.float32, device=total.device)
     rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=total.device)
-    stream = torch.cuda.current_stream(total.device).cuda_stream
     _check(shim.rt_hip_lens_resolve(C.c_void_p(total.data_ptr()), w, h, samples, C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()),
-                                    C.c_void_p(stream)), "rt_hip_lens_resolve")
+                                    _stream(total.device)), "rt_hip_lens_resolve")
     return rgb, rgb8
 
 
 def render_lens_host(scene, aperture, focus, samples, seed, camera=None, max_depth=None, device=0):
     """rt_hip_render_lens_image(): the C hosts' entry point (its own scene on logical device `device`, synchronous) ->
     (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3], stats dict)"""
-    import numpy as np
     shim = abi.load_shim()
     p = abi.RtHipParams()
     p.width, p.height = scene.width, scene.height
@@ -1602,9 +1519,8 @@ def probe_rays(positions, samples, seed, normals=None, bias=0.0, k_first=0, n=No
     n = pos.shape[0] * samples - k_first if n is None else n
     rays = torch.empty((max(n, 0), 6), dtype=torch.float64, device=dev)
     p = abi.probe_params(abi.PROBE_SPHERE if nrm is None else abi.PROBE_HEMISPHERE, samples, seed, bias=bias)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     _check(shim.rt_hip_probe_rays(C.c_void_p(pos.data_ptr() if pos.numel() else None), C.c_void_p(nrm.data_ptr() if nrm is not None else None),
-                                  pos.shape[0], C.byref(p), k_first, n, C.c_void_p(rays.data_ptr() if n > 0 else None), C.c_void_p(stream)),
+                                  pos.shape[0], C.byref(p), k_first, n, C.c_void_p(rays.data_ptr() if n > 0 else None), _stream(dev)),
            "rt_hip_probe_rays")
     return rays
 
@@ -1617,9 +1533,8 @@ def probe_resolve(total, samples):
     n, bases, _ = total.shape
     mode = {9: abi.PROBE_SPHERE, 1: abi.PROBE_HEMISPHERE}[bases]
     coeff, coeff_f = torch.empty_like(total), torch.empty(total.shape, dtype=torch.float32, device=total.device)
-    stream = torch.cuda.current_stream(total.device).cuda_stream
     _check(shim.rt_hip_probe_resolve(C.c_void_p(total.data_ptr()), n, mode, samples, C.c_void_p(coeff.data_ptr()), C.c_void_p(coeff_f.data_ptr()),
-                                     C.c_void_p(stream)), "rt_hip_probe_resolve")
+                                     _stream(total.device)), "rt_hip_probe_resolve")
     return coeff, coeff_f
 
 
@@ -1635,10 +1550,9 @@ def probe_irradiance(sh, index, normals):
     if idx.numel() != m:
         raise ValueError(f"{idx.numel()} indices for {m} normals")
     out = torch.empty((m, 3), dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     _check(shim.rt_hip_probe_irradiance(C.c_void_p(sh.data_ptr() if sh.numel() else None), sh.shape[0], C.c_void_p(idx.data_ptr() if m else None),
                                         C.c_void_p(nrm.data_ptr() if m else None), m, C.c_void_p(out.data_ptr() if m else None),
-                                        C.c_void_p(stream)), "rt_hip_probe_irradiance")
+                                        _stream(dev)), "rt_hip_probe_irradiance")
     return out
 
 
@@ -1648,8 +1562,7 @@ def probe_grid_positions(grid, device=0):
     shim = abi.load_shim()
     dev = torch.device("cuda", device)
     out = torch.empty((grid.count[0] * grid.count[1] * grid.count[2], 3), dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(shim.rt_hip_probe_grid_positions(C.byref(grid), C.c_void_p(out.data_ptr() if out.numel() else None), C.c_void_p(stream)),
+    _check(shim.rt_hip_probe_grid_positions(C.byref(grid), C.c_void_p(out.data_ptr() if out.numel() else None), _stream(dev)),
            "rt_hip_probe_grid_positions")
     return out
 
@@ -1680,10 +1593,9 @@ def probe_shade(grid, coeff, points, normals, status=None, albedo=None, add=None
         if f in want and f not in res:
             res[f] = torch.empty((n, 3), dtype=dt, device=dev)
     ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     _check(shim.rt_hip_probe_shade(C.byref(grid), ptr(coeff), ptr(pts), ptr(nrm), ptr(st), ptr(alb), ptr(ad), n if m is None else m,
                                    ptr(res.get("irradiance") if "irradiance" in want else None), ptr(res.get("color") if "color" in want else None),
-                                   C.c_void_p(stream)), "rt_hip_probe_shade")
+                                   _stream(dev)), "rt_hip_probe_shade")
     return {f: res[f] for f in want}
 
 
@@ -1691,7 +1603,6 @@ def probe_preview_host(scene, grid, samples, seed, camera=None, aov_samples=1, m
     """rt_hip_probe_preview_image(): the C hosts' entry point (its own scene on logical device `device`, synchronous): the grid baked
     with `samples` rays a probe under `seed`, then the preview of the scene's frame -> (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3],
     coeff float64 [N, 9, 3], stats dict)"""
-    import numpy as np
     shim = abi.load_shim()
     n = grid.count[0] * grid.count[1] * grid.count[2]
     if origin_radius is None:
@@ -1713,7 +1624,6 @@ def bake_probes_host(scene, positions, samples, seed, normals=None, bias=0.0, ma
     """rt_hip_bake_probes_host(): the C hosts' entry point (its own scene on logical device `device`, synchronous); normals None:
     sphere probes -> (coeff float64 [N, 9, 3], coeff_f float32, status uint32 [N], stats dict); with normals: hemisphere probes,
     the arrays [N, 1, 3]"""
-    import numpy as np
     shim = abi.load_shim()
     pos = np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1, 3))
     nrm = None if normals is None else np.ascontiguousarray(np.asarray(normals, dtype=np.float64).reshape(-1, 3))
