@@ -53,6 +53,79 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _some(t, some=True):
+    """... of a tensor that may be missing or empty, or of which nothing is to be read (some false): a null c_void_p then"""
+    return C.c_void_p(t.data_ptr() if t is not None and some and t.numel() else None)
+
+
+def _camera(scene, camera):
+    """the camera of a call: the one given, or the scene's own"""
+    return camera if camera is not None else scene.camera
+
+
+def _depth(scene, max_depth):
+    """the max_depth of a call: the one given (0 is one), or the scene's own"""
+    return scene.max_depth if max_depth is None else max_depth
+
+
+def _params(scene, seed, samples, max_depth, integrator="path", tiles=(0, 0, 0)):
+    """the one RtHipParams builder: the scene's size, and (first, stride, count) of the tiles where a call has them"""
+    p = abi.RtHipParams()
+    p.integrator = abi.INTEGRATORS[integrator]
+    p.width, p.height, p.samples, p.max_depth, p.seed = scene.width, scene.height, samples, max_depth, seed
+    p.tile_first, p.tile_stride, p.tile_count = tiles
+    return p
+
+
+def _counters(dev, stats=None):
+    """the counters of a device call (int64 [RT_HIP_NSTATS]): the tensor given, which the call adds to, or zeros"""
+    return torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev) if stats is None else stats
+
+
+def _host_counters():
+    """... of a host form"""
+    return (C.c_uint64 * abi.NSTATS)()
+
+
+def _host_scene(scene):
+    """the four leading arguments of a scene-owning host form (hip_meshes()' result lives in the call's arguments)"""
+    return scene.objects, scene.n_objects, scene.hip_meshes(), scene.n_meshes
+
+
+def _points3(x, dev, dtype=torch.float64):
+    """positions, normals or colours as a contiguous [N, 3] tensor on `dev`"""
+    return torch.as_tensor(x, dtype=dtype, device=dev).reshape(-1, 3).contiguous()
+
+
+def _frame_pair(h, w, dev):
+    """(rgb float32 [h, w, 3], rgb8 uint8 [h, w, 3]) for a call to fill: on `dev`, or numpy arrays with dev None"""
+    if dev is None:
+        return np.zeros((h, w, 3), dtype=np.float32), np.zeros((h, w, 3), dtype=np.uint8)
+    return torch.empty((h, w, 3), dtype=torch.float32, device=dev), torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+
+
+def _workspace(nbytes, dev):
+    """a byte workspace of a generated-ray job: at least 256 bytes"""
+    return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+
+
+def _grid_count(grid):
+    return grid.count[0] * grid.count[1] * grid.count[2]
+
+
+def _grid_radius(grid):
+    """the default origin_radius of a grid's probes: its farthest corner from the world's origin, a shade more"""
+    far = [max(abs(grid.origin[a]), abs(grid.origin[a] + (grid.count[a] - 1) * grid.step[a])) for a in range(3)]
+    return _distance(far) * (1.0 + 2.0 ** -40)
+
+
+def _slices(n, samples, slice_rays):
+    """(slice_rays, rays a launch) of a sliced bake of n probes: None is everything at once, and a launch has 1 .. total rays"""
+    total = max(n * samples, 1)
+    slice_rays = total if slice_rays is None else slice_rays
+    return slice_rays, max(min(slice_rays, total), 1)
+
+
 def _is(t, dev=None, n=None, dtype=None, size=None):
     """The one tensor requirement: t is contiguous and -- of what is asked -- on `dev`, of n values, of this dtype, of this element
     size.  The caller says what it asks and keeps its own refusal."""
@@ -114,15 +187,20 @@ class GpuScene:
             raise ShimError("no HIP device visible; this package has no CPU fallback")
         self.scene = scene
         self.device = device
-        self._meshes = scene.hip_meshes()
         handle = C.c_void_p()
         opts = abi.RtHipSceneOptions()
         self.shim.rt_hip_scene_options_defaults(C.byref(opts))
         opts.bvh_builder = abi.BVH_BUILDERS[bvh]
-        _check(self.shim.rt_hip_scene_create_opts(scene.objects, scene.n_objects, self._meshes, scene.n_meshes, device, C.byref(opts),
-                                                  C.byref(handle)), "rt_hip_scene_create_opts")
+        objects, n_objects, self._meshes, n_meshes = _host_scene(scene)
+        _check(self.shim.rt_hip_scene_create_opts(objects, n_objects, self._meshes, n_meshes, device, C.byref(opts), C.byref(handle)),
+               "rt_hip_scene_create_opts")
         self.handle = handle
         self._accums = []  # handles of the accumulations made here: closed before the scene (rt_hip.h: the scene outlives them)
+
+    @property
+    def dev(self):
+        """the scene's device, as torch names it"""
+        return torch.device("cuda", self.device)
 
     def close(self):
         if self.handle:
@@ -143,14 +221,7 @@ class GpuScene:
             pass
 
     def params(self, seed, first, stride, count, samples=None, max_depth=None, integrator="path"):
-        p = abi.RtHipParams()
-        p.integrator = abi.INTEGRATORS[integrator]
-        p.width, p.height = self.scene.width, self.scene.height
-        p.samples = samples or self.scene.samples
-        p.max_depth = self.scene.max_depth if max_depth is None else max_depth
-        p.seed = seed
-        p.tile_first, p.tile_stride, p.tile_count = first, stride, count
-        return p
+        return _params(self.scene, seed, samples or self.scene.samples, _depth(self.scene, max_depth), integrator, (first, stride, count))
 
     def kernel_name(self, integrator="path"):
         return self.shim.rt_hip_kernel_name(self.handle, abi.INTEGRATORS[integrator]).decode()
@@ -201,21 +272,27 @@ class GpuScene:
         across an update when its next frame() is given the positions from before it (prev_positions); without them, and for a
         Preview, which assumes a static scene, reset after an update.  Open accumulations refuse the update (close them first).
         self.scene keeps the vertices the scene was created from."""
-        n = self.scene.n_triangles
-        if isinstance(positions, torch.Tensor):
-            if positions.dtype != torch.float64 or tuple(positions.shape) != (n, 3, 3):
-                raise ValueError(f"update_vertices: a float64 tensor of shape ({n}, 3, 3) is expected")
-            t = positions.contiguous()
+        self._update("update_vertices", positions, (self.scene.n_triangles, 3, 3))
+        return None if rebuild_above is None else self.maintain_bvh(rebuild_above)
+
+    def _update(self, name, x, shape):
+        """The one body of update_vertices / update_spheres (rt_hip_scene_<name>, or its _host form for what is no tensor) -> what
+        went down: the contiguous tensor, or the float64 array"""
+        symbol = "rt_hip_scene_" + name
+        if isinstance(x, torch.Tensor):
+            if x.dtype != torch.float64 or tuple(x.shape) != shape:
+                raise ValueError(f"{name}: a float64 tensor of shape {shape} is expected")
+            t = x.contiguous()
             if t.is_cuda:   # what produced the tensor on torch's current stream must be done: the shim works on the null stream
                 torch.cuda.current_stream(t.device).synchronize()
             # (a host tensor, or one on another device, goes to the device entry all the same: the shim refuses it)
-            _check(self.shim.rt_hip_scene_update_vertices(self.handle, C.c_void_p(t.data_ptr()), n), "rt_hip_scene_update_vertices")
-        else:
-            a = np.ascontiguousarray(positions, dtype=np.float64)
-            if a.shape != (n, 3, 3):
-                raise ValueError(f"update_vertices: shape ({n}, 3, 3) is expected, not {a.shape}")
-            _check(self.shim.rt_hip_scene_update_vertices_host(self.handle, a.ctypes.data, n), "rt_hip_scene_update_vertices_host")
-        return None if rebuild_above is None else self.maintain_bvh(rebuild_above)
+            _check(getattr(self.shim, symbol)(self.handle, _ptr(t), shape[0]), symbol)
+            return t
+        a = np.ascontiguousarray(x, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"{name}: shape {shape} is expected, not {a.shape}")
+        _check(getattr(self.shim, symbol + "_host")(self.handle, a.ctypes.data, shape[0]), symbol + "_host")
+        return a
 
     def bvh_cost(self):
         """the expected walk cost of the scene's current tree (refitted, if it was), evaluated on the device by the fixed
@@ -252,7 +329,7 @@ class GpuScene:
         if getattr(self, "_spheres", None) is None:
             a = np.array([[o.center.x, o.center.y, o.center.z, o.radius] for o in self.scene.objects[:self.scene.n_objects]],
                          dtype=np.float64).reshape(-1, 4)
-            self._spheres = torch.from_numpy(a).to(torch.device("cuda", self.device))
+            self._spheres = torch.from_numpy(a).to(self.dev)
         return self._spheres
 
     def update_spheres(self, spheres):
@@ -262,22 +339,8 @@ class GpuScene:
         equal a freshly created scene's.  A Temporal keeps its history across the move when its next frame() is given the spheres
         from before it (prev_spheres).  Open accumulations refuse the update.  self.scene keeps the spheres the scene was created
         from; spheres() has the current ones."""
-        n = self.scene.n_objects
-        dev = torch.device("cuda", self.device)
-        if isinstance(spheres, torch.Tensor):
-            if spheres.dtype != torch.float64 or tuple(spheres.shape) != (n, 4):
-                raise ValueError(f"update_spheres: a float64 tensor of shape ({n}, 4) is expected")
-            t = spheres.contiguous()
-            if t.is_cuda:   # what produced the tensor on torch's current stream must be done: the shim works on the null stream
-                torch.cuda.current_stream(t.device).synchronize()
-            _check(self.shim.rt_hip_scene_update_spheres(self.handle, C.c_void_p(t.data_ptr()), n), "rt_hip_scene_update_spheres")
-            self._spheres = t.detach().clone()
-            return
-        a = np.ascontiguousarray(spheres, dtype=np.float64)
-        if a.shape != (n, 4):
-            raise ValueError(f"update_spheres: shape ({n}, 4) is expected, not {a.shape}")
-        _check(self.shim.rt_hip_scene_update_spheres_host(self.handle, a.ctypes.data, n), "rt_hip_scene_update_spheres_host")
-        self._spheres = torch.from_numpy(a.copy()).to(dev)
+        x = self._update("update_spheres", spheres, (self.scene.n_objects, 4))
+        self._spheres = x.detach().clone() if isinstance(x, torch.Tensor) else torch.from_numpy(x.copy()).to(self.dev)
 
     def read_spheres(self):
         """for tests: dict of numpy arrays as the kernels read them -- entry (n, 6: cx cy cz r^2 |c| 0), geom4 (n, 4)"""
@@ -322,7 +385,7 @@ class GpuScene:
 
     def suggest_chunks(self, count, samples=None, max_depth=None):
         return int(self.shim.rt_hip_suggest_chunks_depth(self.handle, count, samples or self.scene.samples,
-                                                         self.scene.max_depth if max_depth is None else max_depth))
+                                                         _depth(self.scene, max_depth)))
 
     def render_tiles(self, seed, first, stride, count, tiles=None, tiles8=None, stats=None, samples=None,
                      max_depth=None, chunks=1, workspace=None, integrator="path", camera=None):
@@ -331,19 +394,17 @@ class GpuScene:
         every tile's samples over that many workgroups (same image, bit for bit).
         integrator: "path" = trace_path (what the reference ships), "whitted" = cast_ray.
         camera: an abi.Camera to render with instead of the scene's own."""
-        dev = torch.device("cuda", self.device)
+        dev = self.dev
         if tiles is None:
             tiles = torch.empty((max(count, 1), abi.TILE_PIXELS, 3), dtype=torch.float32, device=dev)
         if tiles8 is None:
             tiles8 = torch.empty((max(count, 1), abi.TILE_PIXELS, 3), dtype=torch.uint8, device=dev)
-        if stats is None:
-            stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
+        stats = _counters(dev, stats)
         p = self.params(seed, first, stride, count, samples, max_depth, integrator)
         if chunks > 1 and workspace is None:
             workspace = torch.empty(self.shim.rt_hip_scene_chunk_workspace_bytes(self.handle, max(count, 1)), dtype=torch.uint8, device=dev)
         self._workspace = workspace  # keep alive until the stream has used it
-        _check(self.shim.rt_hip_render_tiles_chunked(self.handle, C.byref(camera if camera is not None else self.scene.camera),
-                                                     C.byref(p), chunks,
+        _check(self.shim.rt_hip_render_tiles_chunked(self.handle, C.byref(_camera(self.scene, camera)), C.byref(p), chunks,
                                                      workspace.data_ptr() if workspace is not None else None,
                                                      tiles.data_ptr(), tiles8.data_ptr(), stats.data_ptr(),
                                                      _stream(dev)),
@@ -358,8 +419,8 @@ class GpuScene:
             count = n_tiles(self.scene.width, self.scene.height)
         p = self.params(seed, first, stride, count, samples, max_depth, integrator)
         handle = C.c_void_p()
-        _check(self.shim.rt_hip_accum_create(self.handle, C.byref(camera if camera is not None else self.scene.camera),
-                                             C.byref(p), C.byref(handle)), "rt_hip_accum_create")
+        _check(self.shim.rt_hip_accum_create(self.handle, C.byref(_camera(self.scene, camera)), C.byref(p), C.byref(handle)),
+               "rt_hip_accum_create")
         self._accums = [h for h in self._accums if h] + [handle]
         return Accumulation(self, handle, count, seed, first, stride, camera)
 
@@ -388,11 +449,11 @@ class GpuScene:
         words of the C-ABI, bit for bit: .view(torch.uint32) or numpy's .view(np.uint32) reads them as such).  want: which."""
         if count is None:
             count = n_tiles(self.scene.width, self.scene.height)
-        dev = torch.device("cuda", self.device)
+        dev = self.dev
         out = {f: torch.empty(_aov_shape(f, max(count, 1), abi.TILE_PIXELS), dtype=_TORCH[abi.AOV_DTYPES[f]], device=dev) for f in want}
         p = self.params(seed, first, stride, count, samples)
-        _check(self.shim.rt_hip_render_aov_tiles(self.handle, C.byref(camera if camera is not None else self.scene.camera),
-                                                 C.byref(p), C.byref(_aov_record(out, want)), _stream(dev)), "rt_hip_render_aov_tiles")
+        _check(self.shim.rt_hip_render_aov_tiles(self.handle, C.byref(_camera(self.scene, camera)), C.byref(p),
+                                                 C.byref(_aov_record(out, want)), _stream(dev)), "rt_hip_render_aov_tiles")
         return out
 
     def untile_aov(self, tiles, first, stride, count):
@@ -405,7 +466,7 @@ class GpuScene:
     def _untile_aov(self, tiles, first, stride, count, out):
         """... into the row-major tensors `out` holds for the tiles' fields"""
         _check(self.shim.rt_hip_untile_aov(C.byref(_aov_record(tiles, tiles)), self.scene.width, self.scene.height, first, stride, count,
-                                           C.byref(_aov_record(out, tiles)), _stream(torch.device("cuda", self.device))), "rt_hip_untile_aov")
+                                           C.byref(_aov_record(out, tiles)), _stream(self.dev)), "rt_hip_untile_aov")
         return out
 
     def aov_image(self, seed, samples):
@@ -413,7 +474,7 @@ class GpuScene:
         float32 [H,W,3], depth float32 [H,W], object / hits uint32 [H,W]"""
         total = n_tiles(self.scene.width, self.scene.height)
         img = self.untile_aov(self.render_aov(seed, samples, 0, 1, total), 0, 1, total)
-        torch.cuda.synchronize(torch.device("cuda", self.device))
+        torch.cuda.synchronize(self.dev)
         return {f: t.cpu().numpy().view(abi.AOV_DTYPES[f]) for f, t in img.items()}
 
     def query_kernel_name(self):
@@ -421,7 +482,7 @@ class GpuScene:
         return self.shim.rt_hip_query_kernel_name(self.handle).decode()
 
     def _query(self, rays, per_ray, t_max, params, want, into=None):
-        dev = torch.device("cuda", self.device)
+        dev = self.dev
         rays = _device_rays(rays, per_ray, dev)
         n = rays.shape[0]
         if t_max is not None:
@@ -430,8 +491,7 @@ class GpuScene:
                 raise ValueError("query: t_max must hold one value per ray")
         out, hits = _wanted(abi.RtHipHits(), abi.HIT_SHAPES, want, n, dev, into=into)
         self._query_inputs = (rays, t_max)   # keep alive until the stream has used them
-        _check(self.shim.rt_hip_query_rays(self.handle, C.c_void_p(rays.data_ptr() if n else None),
-                                           C.c_void_p(t_max.data_ptr()) if t_max is not None and n else None, n, C.byref(params),
+        _check(self.shim.rt_hip_query_rays(self.handle, _some(rays), _ptr(t_max) if n else None, n, C.byref(params),
                                            C.byref(hits), _stream(dev)), "rt_hip_query_rays")
         return out
 
@@ -447,17 +507,20 @@ class GpuScene:
         """... of the camera rays get_camera_ray(camera, u, v) for uv [n, 2] float64 (camera None: the scene's own; origin_radius
         None: the camera's distance from the world origin; out: a dict of tensors to write wanted fields into, what is missing
         is allocated)"""
-        cam = camera if camera is not None else self.scene.camera
-        if origin_radius is None:
-            origin_radius = _distance(cam.position.tuple())
+        cam, origin_radius = self._uv_source(camera, origin_radius)
         return self._query(uv, 2, t_max, abi.query_params(abi.RAYS_CAMERA_UV, normalize, cam, origin_radius), want, out)
+
+    def _uv_source(self, camera, origin_radius):
+        """(camera, origin_radius) of a query of camera rays: the scene's own camera, and its distance from the world's origin"""
+        cam = _camera(self.scene, camera)
+        return cam, _distance(cam.position.tuple()) if origin_radius is None else origin_radius
 
     def pick(self, x, y):
         """What is under the centre of pixel (x, y) of the scene's own camera and size: u = (x + 0.5) / (w - 1), v = (y + 0.5) /
         (h - 1) -> dict of Python values: status, object, prim, t, point, normal (synchronises)"""
         uv = [[(x + 0.5) / (self.scene.width - 1), (y + 0.5) / (self.scene.height - 1)]]
         out = self.query_uv(uv, want=("status", "object", "prim", "t", "point", "normal"))
-        torch.cuda.synchronize(torch.device("cuda", self.device))
+        torch.cuda.synchronize(self.dev)
         res = {f: t.cpu().numpy() for f, t in out.items()}
         return dict(status=int(res["status"][0]), object=int(res["object"].view("uint32")[0]), prim=int(res["prim"].view("uint32")[0]),
                     t=float(res["t"][0]), point=tuple(res["point"][0].tolist()), normal=tuple(res["normal"][0].tolist()))
@@ -467,17 +530,20 @@ class GpuScene:
         return self.shim.rt_hip_trace_kernel_name(self.handle).decode()
 
     def _trace(self, rays, per_ray, params, want, stats):
-        dev = torch.device("cuda", self.device)
+        dev = self.dev
         rays = _device_rays(rays, per_ray, dev)
         n = rays.shape[0]
-        out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, dev, params.samples)
-        if stats is None:
-            stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
+        out, rad = self._radiance(want, n, params.samples, stats)
         self._trace_inputs = rays   # keep alive until the stream has used them
-        _check(self.shim.rt_hip_trace_rays(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.byref(params), C.byref(rad),
-                                           C.c_void_p(stats.data_ptr()), _stream(dev)), "rt_hip_trace_rays")
-        out["stats"] = stats
+        _check(self.shim.rt_hip_trace_rays(self.handle, _some(rays), n, C.byref(params), C.byref(rad), _ptr(out["stats"]), _stream(dev)),
+               "rt_hip_trace_rays")
         return out
+
+    def _radiance(self, want, n, samples, stats):
+        """(dict, RtHipRadiance) of a radiance query's outputs `want` for n entries, the counters -- given or zeros -- as out["stats"]"""
+        out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, self.dev, samples)
+        out["stats"] = _counters(self.dev, stats)
+        return out, rad
 
     def trace_rays(self, rays, samples, seed, max_depth=None, normalize=False, origin_radius=None, index_first=0,
                    want=("status", "radiance"), stats=None):
@@ -486,19 +552,15 @@ class GpuScene:
         torch's current stream -> dict of device tensors: status int32 [n] (the uint32 words of the C-ABI), radiance float64
         [n, 3], samples [n, samples, 3], paths / casts int64 [n], ray [n, 6] (want: which), and stats int64 [4] (rays, casts, tests,
         samples; += into the tensor given).  max_depth None: the scene's own."""
-        p = abi.trace_params(samples, seed, self.scene.max_depth if max_depth is None else max_depth, abi.RAYS_GIVEN, normalize, None,
-                             origin_radius, index_first)
+        p = abi.trace_params(samples, seed, _depth(self.scene, max_depth), abi.RAYS_GIVEN, normalize, None, origin_radius, index_first)
         return self._trace(rays, 6, p, want, stats)
 
     def trace_uv(self, uv, samples, seed, camera=None, max_depth=None, normalize=False, origin_radius=None, index_first=0,
                  want=("status", "radiance"), stats=None):
         """... of the camera rays get_camera_ray(camera, u, v) for uv [n, 2] float64 (camera None: the scene's own; origin_radius
         None: the camera's distance from the world origin)"""
-        cam = camera if camera is not None else self.scene.camera
-        if origin_radius is None:
-            origin_radius = _distance(cam.position.tuple())
-        p = abi.trace_params(samples, seed, self.scene.max_depth if max_depth is None else max_depth, abi.RAYS_CAMERA_UV, normalize, cam,
-                             origin_radius, index_first)
+        cam, origin_radius = self._uv_source(camera, origin_radius)
+        p = abi.trace_params(samples, seed, _depth(self.scene, max_depth), abi.RAYS_CAMERA_UV, normalize, cam, origin_radius, index_first)
         return self._trace(uv, 2, p, want, stats)
 
     def pixel_kernel_name(self):
@@ -512,24 +574,19 @@ class GpuScene:
         returns it, or anything numpy takes), n: how many of them to trace (None: all); asynchronous on torch's current stream ->
         dict of device tensors: status int32 [n], radiance float64 [n, 3], samples [n, samples, 3], paths / casts int64 [n] (want:
         which), and stats int64 [4] (+= into the tensor given).  camera None: the scene's own; max_depth None: the scene's own."""
-        dev = torch.device("cuda", self.device)
+        dev = self.dev
         pixels = _pixel_tensor(pixels, dev)
         n = pixels.numel() if n is None else int(n)
         if n < 0 or n > pixels.numel():
             raise ValueError("trace_pixels(): n must be within the list")
-        p = abi.pixel_params(self.scene.width, self.scene.height, samples, seed, sample_first,
-                             self.scene.max_depth if max_depth is None else max_depth)
+        p = abi.pixel_params(self.scene.width, self.scene.height, samples, seed, sample_first, _depth(self.scene, max_depth))
         for f in want:
             if f not in abi.PIXEL_FIELDS:
                 raise ValueError(f"trace_pixels(): {f!r} is not an output of a pixel refinement")
-        out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, dev, samples)
-        if stats is None:
-            stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
+        out, rad = self._radiance(want, n, samples, stats)
         self._pixel_inputs = pixels   # keep alive until the stream has used them
-        _check(self.shim.rt_hip_trace_pixels(self.handle, C.byref(camera if camera is not None else self.scene.camera),
-                                             C.c_void_p(pixels.data_ptr() if n else None), n, C.byref(p), C.byref(rad),
-                                             C.c_void_p(stats.data_ptr()), _stream(dev)), "rt_hip_trace_pixels")
-        out["stats"] = stats
+        _check(self.shim.rt_hip_trace_pixels(self.handle, C.byref(_camera(self.scene, camera)), _some(pixels, n), n, C.byref(p), C.byref(rad),
+                                             _ptr(out["stats"]), _stream(dev)), "rt_hip_trace_pixels")
         return out
 
     def refine(self, rgb, values, lo, hi, samples, seed, sample_first=0, prior=None, prior_scale=0.0, invert=False, camera=None,
@@ -551,32 +608,28 @@ class GpuScene:
         in front of the camera (None: the scene's own), `samples` lens rays per pixel traced by the radiance query; asynchronous on
         torch's current stream -> (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3], sum float64 [H, W, 3], stats int64 [4]; += into the
         tensor given).  slice_pixels: pixels per launch (None: the whole frame); no output bit depends on it."""
-        dev = torch.device("cuda", self.device)
-        cam = camera if camera is not None else self.scene.camera
+        dev = self.dev
         w, h = self.scene.width, self.scene.height
         p = self.params(seed, 0, 0, 0, samples=samples, max_depth=max_depth)
         lens = abi.lens_params(aperture, focus)
         slice_pixels = w * h if slice_pixels is None else slice_pixels
-        ws = torch.empty(max(self.shim.rt_hip_lens_workspace_bytes(w, h, slice_pixels), 256), dtype=torch.uint8, device=dev)
-        rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        ws = _workspace(self.shim.rt_hip_lens_workspace_bytes(w, h, slice_pixels), dev)
+        rgb, rgb8 = _frame_pair(h, w, dev)
         total = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
-        if stats is None:
-            stats = torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev)
+        stats = _counters(dev, stats)
         self._lens_workspace = ws   # keep alive until the stream has used it
-        _check(self.shim.rt_hip_render_lens(self.handle, C.byref(cam), C.byref(lens), C.byref(p), slice_pixels, C.c_void_p(ws.data_ptr()),
-                                            C.c_void_p(total.data_ptr()), C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()),
-                                            C.c_void_p(stats.data_ptr()), _stream(dev)), "rt_hip_render_lens")
+        _check(self.shim.rt_hip_render_lens(self.handle, C.byref(_camera(self.scene, camera)), C.byref(lens), C.byref(p), slice_pixels, _ptr(ws),
+                                            _ptr(total), _ptr(rgb), _ptr(rgb8), _ptr(stats), _stream(dev)), "rt_hip_render_lens")
         return rgb, rgb8, total, stats
 
     def focus_at(self, x, y, camera=None):
         """Autofocus: the focus_distance that puts what is under the centre of pixel (x, y) in focus, or None where the ray misses.
         One ray query through the pixel centre (as pick()); the hit's t over |d|, d the lens contract's direction, not normalised:
         d = position - (lower_left_corner + (horizontal*u + vertical*v)) (synchronises)"""
-        cam = camera if camera is not None else self.scene.camera
+        cam = _camera(self.scene, camera)
         u, v = (x + 0.5) / (self.scene.width - 1.0), (y + 0.5) / (self.scene.height - 1.0)
         out = self.query_uv([[u, v]], camera=cam, want=("status", "t"))
-        torch.cuda.synchronize(torch.device("cuda", self.device))
+        torch.cuda.synchronize(self.dev)
         if int(out["status"].cpu()[0]) != 1:
             return None
         pos, llc, hor, ver = (c.tuple() for c in (cam.position, cam.lower_left_corner, cam.horizontal, cam.vertical))
@@ -586,28 +639,25 @@ class GpuScene:
     def _bake(self, mode, positions, normals, samples, seed, bias, max_depth, origin_radius, slice_rays, stats):
         """rt_hip_bake_probes on torch's current stream -> dict(coeff float64 [N, bases, 3], coeff_f float32, sum float64, status int32
         [N], stats int64 [4])"""
-        dev = torch.device("cuda", self.device)
-        pos = torch.as_tensor(positions, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
-        nrm = None if normals is None else torch.as_tensor(normals, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+        dev = self.dev
+        pos, nrm = _points3(positions, dev), None if normals is None else _points3(normals, dev)
         n, bases = pos.shape[0], abi.PROBE_BASES[mode]
         if nrm is not None and nrm.shape[0] != n:
             raise ValueError(f"{nrm.shape[0]} normals for {n} probes")
         if origin_radius is None:
             norms = lambda t: None if t is None else torch.linalg.vector_norm(t, dim=1)
             origin_radius = _origin_radius(norms(pos), norms(nrm), bias)   # (synchronises)
-        p = abi.probe_params(mode, samples, seed, self.scene.max_depth if max_depth is None else max_depth, bias, origin_radius)
-        total = max(n * samples, 1)
-        slice_rays = total if slice_rays is None else slice_rays
-        ws = torch.empty(max(self.shim.rt_hip_probe_workspace_bytes(n, mode, max(min(slice_rays, total), 1)), 256), dtype=torch.uint8, device=dev)
+        p = abi.probe_params(mode, samples, seed, _depth(self.scene, max_depth), bias, origin_radius)
+        slice_rays, launch = _slices(n, samples, slice_rays)
+        ws = _workspace(self.shim.rt_hip_probe_workspace_bytes(n, mode, launch), dev)
         out = dict(coeff=torch.empty((n, bases, 3), dtype=torch.float64, device=dev),
                    coeff_f=torch.empty((n, bases, 3), dtype=torch.float32, device=dev),
                    sum=torch.empty((n, bases, 3), dtype=torch.float64, device=dev), status=torch.empty(n, dtype=torch.int32, device=dev),
-                   stats=torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev) if stats is None else stats)
+                   stats=_counters(dev, stats))
         self._probe_buffers = (ws, pos, nrm)   # keep alive until the stream has used them
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-        _check(self.shim.rt_hip_bake_probes(self.handle, ptr(pos), ptr(nrm), n, C.byref(p), slice_rays, C.c_void_p(ws.data_ptr()), ptr(out["sum"]),
-                                            ptr(out["coeff"]), ptr(out["coeff_f"]), ptr(out["status"]), C.c_void_p(out["stats"].data_ptr()),
-                                            _stream(dev)), "rt_hip_bake_probes")
+        _check(self.shim.rt_hip_bake_probes(self.handle, _some(pos), _some(nrm), n, C.byref(p), slice_rays, _ptr(ws), _some(out["sum"]),
+                                            _some(out["coeff"]), _some(out["coeff_f"]), _some(out["status"]), _ptr(out["stats"]), _stream(dev)),
+               "rt_hip_bake_probes")
         return out
 
     def bake_probes(self, positions, samples, seed, max_depth=None, origin_radius=None, slice_rays=None, stats=None, details=False):
@@ -631,42 +681,32 @@ class GpuScene:
         """A grid of sphere probes baked in one call (rt_hip.h, rt_hip_bake_probe_grid: the grid's positions, then rt_hip_bake_probes
         at them); grid: abi.probe_grid(...) -> float64 [N, 9, 3] on the device, N = the grid's probes in index order (details: the dict
         of coeff, coeff_f, status, stats).  origin_radius None: the farthest corner of the grid from the world's origin."""
-        dev = torch.device("cuda", self.device)
-        n = grid.count[0] * grid.count[1] * grid.count[2]
-        if origin_radius is None:
-            far = [max(abs(grid.origin[a]), abs(grid.origin[a] + (grid.count[a] - 1) * grid.step[a])) for a in range(3)]
-            origin_radius = _distance(far) * (1.0 + 2.0 ** -40)
-        p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, self.scene.max_depth if max_depth is None else max_depth, 0.0, origin_radius)
-        total = max(n * samples, 1)
-        slice_rays = total if slice_rays is None else slice_rays
-        ws = torch.empty(max(self.shim.rt_hip_probe_grid_workspace_bytes(C.byref(grid), max(min(slice_rays, total), 1)), 256), dtype=torch.uint8,
-                         device=dev)
+        dev, n = self.dev, _grid_count(grid)
+        p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, _depth(self.scene, max_depth), 0.0,
+                             _grid_radius(grid) if origin_radius is None else origin_radius)
+        slice_rays, launch = _slices(n, samples, slice_rays)
+        ws = _workspace(self.shim.rt_hip_probe_grid_workspace_bytes(C.byref(grid), launch), dev)
         out = dict(coeff=torch.empty((n, 9, 3), dtype=torch.float64, device=dev), coeff_f=torch.empty((n, 9, 3), dtype=torch.float32, device=dev),
-                   status=torch.empty(n, dtype=torch.int32, device=dev),
-                   stats=torch.zeros(abi.NSTATS, dtype=torch.int64, device=dev) if stats is None else stats)
+                   status=torch.empty(n, dtype=torch.int32, device=dev), stats=_counters(dev, stats))
         self._probe_buffers = (ws,)   # keep alive until the stream has used them
-        _check(self.shim.rt_hip_bake_probe_grid(self.handle, C.byref(grid), C.byref(p), slice_rays, C.c_void_p(ws.data_ptr()),
-                                                C.c_void_p(out["coeff"].data_ptr()), C.c_void_p(out["coeff_f"].data_ptr()),
-                                                C.c_void_p(out["status"].data_ptr()), C.c_void_p(out["stats"].data_ptr()), _stream(dev)),
-               "rt_hip_bake_probe_grid")
+        _check(self.shim.rt_hip_bake_probe_grid(self.handle, C.byref(grid), C.byref(p), slice_rays, _ptr(ws), _ptr(out["coeff"]), _ptr(out["coeff_f"]),
+                                                _ptr(out["status"]), _ptr(out["stats"]), _stream(dev)), "rt_hip_bake_probe_grid")
         return out if details else out["coeff"]
 
     def probe_preview(self, grid, coeff, camera=None, aov_samples=1, seed=0):
         """The probe-lit preview of the scene's frame (rt_hip.h, rt_hip_probe_preview): first hits at the pixel centres, their albedo
         and emission, lit by the grid's baked coefficients coeff [N, 9, 3]; asynchronous on torch's current stream ->
         (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3]) on the device"""
-        dev = torch.device("cuda", self.device)
+        dev = self.dev
         w, h = self.scene.width, self.scene.height
         coeff = torch.as_tensor(coeff, dtype=torch.float64, device=dev).contiguous()
-        if coeff.numel() != grid.count[0] * grid.count[1] * grid.count[2] * 27:
+        if coeff.numel() != _grid_count(grid) * 27:
             raise ValueError("probe_preview: coeff must hold 9 x 3 values per probe of the grid")
-        ws = torch.empty(max(self.shim.rt_hip_probe_preview_workspace_bytes(self.handle, w, h), 256), dtype=torch.uint8, device=dev)
-        rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        ws = _workspace(self.shim.rt_hip_probe_preview_workspace_bytes(self.handle, w, h), dev)
+        rgb, rgb8 = _frame_pair(h, w, dev)
         self._preview_buffers = (ws, coeff)   # keep alive until the stream has used them
-        _check(self.shim.rt_hip_probe_preview(self.handle, C.byref(camera if camera is not None else self.scene.camera), C.byref(grid),
-                                              C.c_void_p(coeff.data_ptr()), w, h, aov_samples, seed, C.c_void_p(ws.data_ptr()),
-                                              C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()), _stream(dev)), "rt_hip_probe_preview")
+        _check(self.shim.rt_hip_probe_preview(self.handle, C.byref(_camera(self.scene, camera)), C.byref(grid), _ptr(coeff), w, h, aov_samples,
+                                              seed, _ptr(ws), _ptr(rgb), _ptr(rgb8), _stream(dev)), "rt_hip_probe_preview")
         return rgb, rgb8
 
     def render_panorama(self, width, height, origin, samples, seed, max_depth=None):
@@ -748,14 +788,14 @@ class Accumulation:
 
     def add(self, n, stats=None):
         """render the next n samples of every pixel; stats: an i64 [4] device tensor the pass's counters are added to"""
-        dev = torch.device("cuda", self.gs.device)
+        dev = self.gs.dev
         _check(self.shim.rt_hip_accum_add(self.handle, n, stats.data_ptr() if stats is not None else None, _stream(dev)),
                "rt_hip_accum_add")
         return stats
 
     def resolve(self, tiles=None, tiles8=None):
         """the mean of the samples done -> (tiles f32 [count,64,3], tiles8 u8 [count,64,3]); pass buffers to reuse them"""
-        dev = torch.device("cuda", self.gs.device)
+        dev = self.gs.dev
         if tiles is None:
             tiles = torch.empty((self.count, abi.TILE_PIXELS, 3), dtype=torch.float32, device=dev)
         if tiles8 is None:
@@ -791,7 +831,7 @@ class Accumulation:
         freeze) the slots the caller names.  Runs on torch's current stream and waits for the count -> live slots left."""
         if (error is None) == (mask is None):
             raise ValueError("freeze(): give the tile errors or a mask")
-        dev = torch.device("cuda", self.gs.device)
+        dev = self.gs.dev
         live = C.c_uint32(0)
         if error is not None:
             p = abi.adapt_params(threshold=threshold, dilate=dilate)
@@ -818,7 +858,7 @@ class Accumulation:
         from an empty accumulation.  on_checkpoint(samples_done, live_tiles) -> truthy to cancel.
         -> (stats dict of what was rendered, device seconds)"""
         p = abi.adapt_params(**params)
-        stats = (C.c_uint64 * abi.NSTATS)()
+        stats = _host_counters()
         secs = C.c_double(0)
         cb = abi.ADAPT_CHECKPOINT(lambda user, done, live: 1 if on_checkpoint(done, live) else 0) if on_checkpoint else None
         _check(self.shim.rt_hip_accum_run_adaptive(self.handle, C.byref(p), stats, C.byref(secs),
@@ -944,12 +984,10 @@ def trace_pixels_host(scene, pixels, samples, seed, sample_first=0, camera=None,
     shim = abi.load_shim()
     pixels = np.ascontiguousarray(np.asarray(pixels, dtype=np.uint32).reshape(-1))
     n = pixels.size
-    p = abi.pixel_params(scene.width, scene.height, samples, seed, sample_first, scene.max_depth if max_depth is None else max_depth)
+    p = abi.pixel_params(scene.width, scene.height, samples, seed, sample_first, _depth(scene, max_depth))
     out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, None, samples)
-    stats = (C.c_uint64 * abi.NSTATS)()
-    meshes = scene.hip_meshes()
-    _check(shim.rt_hip_trace_pixels_host(scene.objects, scene.n_objects, meshes, scene.n_meshes,
-                                         C.byref(camera if camera is not None else scene.camera), pixels.ctypes.data, n, C.byref(p), device,
+    stats = _host_counters()
+    _check(shim.rt_hip_trace_pixels_host(*_host_scene(scene), C.byref(_camera(scene, camera)), pixels.ctypes.data, n, C.byref(p), device,
                                          C.byref(rad), stats), "rt_hip_trace_pixels_host")
     out["stats"] = _stats_dict(stats)
     return out
@@ -1141,7 +1179,7 @@ class Temporal:
         self.params = params
         abi.reproject_params(**params)   # a bad keyword fails here
         w, h = gs.scene.width, gs.scene.height
-        dev = torch.device("cuda", gs.device)
+        dev = gs.dev
         self._total = n_tiles(w, h)
 
         def slot():
@@ -1356,20 +1394,12 @@ def upsample_image_host(low_rgb, low_aov, aov, device=0, **params):
 def render_image_host(scene, seed, n_devices=1, samples=None, max_depth=None, integrator="path"):
     """rt_hip_render_image(): the C hosts' entry point (host buffers, synchronous)."""
     shim = abi.load_shim()
-    p = abi.RtHipParams()
-    p.width, p.height = scene.width, scene.height
-    p.samples = samples or scene.samples
-    p.max_depth = scene.max_depth if max_depth is None else max_depth
-    p.seed = seed
-    p.integrator = abi.INTEGRATORS[integrator]
-    img = np.zeros((scene.height, scene.width, 3), dtype=np.float32)
-    img8 = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
-    stats = (C.c_uint64 * abi.NSTATS)()
+    p = _params(scene, seed, samples or scene.samples, _depth(scene, max_depth), integrator)
+    img, img8 = _frame_pair(scene.height, scene.width, None)
+    stats = _host_counters()
     secs = C.c_double(0)
-    meshes = scene.hip_meshes()
-    _check(shim.rt_hip_render_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera),
-                                    C.byref(p), n_devices, img.ctypes.data, img8.ctypes.data, stats, C.byref(secs)),
-           "rt_hip_render_image")
+    _check(shim.rt_hip_render_image(*_host_scene(scene), C.byref(scene.camera), C.byref(p), n_devices, img.ctypes.data, img8.ctypes.data, stats,
+                                    C.byref(secs)), "rt_hip_render_image")
     return img, img8, _stats_dict(stats), secs.value
 
 
@@ -1377,13 +1407,10 @@ def aov_image_host(scene, seed, samples, device=0):
     """rt_hip_render_aov_image(): the C hosts' entry point (its own scene on logical device `device`, synchronous) -> dict of
     row-major numpy arrays as GpuScene.aov_image"""
     shim = abi.load_shim()
-    p = abi.RtHipParams()
-    p.width, p.height, p.samples, p.seed = scene.width, scene.height, samples, seed
+    p = _params(scene, seed, samples, 0)   # (first hits: no depth to give)
     h, w = scene.height, scene.width
     out = {f: np.zeros(_aov_shape(f, h, w), dtype=abi.AOV_DTYPES[f]) for f in abi.AOV_FIELDS}
-    meshes = scene.hip_meshes()
-    _check(shim.rt_hip_render_aov_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera), C.byref(p),
-                                        device, C.byref(_aov_record(out, abi.AOV_FIELDS, host=True))), "rt_hip_render_aov_image")
+    _check(shim.rt_hip_render_aov_image(*_host_scene(scene), C.byref(scene.camera), C.byref(p), device, C.byref(_aov_record(out, abi.AOV_FIELDS, host=True))), "rt_hip_render_aov_image")
     return out
 
 
@@ -1392,21 +1419,23 @@ def adaptive_image_host(scene, seed, samples, device=0, max_depth=None, integrat
     synchronous; params: abi.adapt_params' keywords) -> (image f32 [H,W,3], image8 u8 [H,W,3], tile sample counts uint32
     [tiles_y, tiles_x], stats dict, device seconds)"""
     shim = abi.load_shim()
-    p = abi.RtHipParams()
-    p.width, p.height, p.samples, p.seed = scene.width, scene.height, samples, seed
-    p.max_depth = scene.max_depth if max_depth is None else max_depth
-    p.integrator = abi.INTEGRATORS[integrator]
+    p = _params(scene, seed, samples, _depth(scene, max_depth), integrator)
     ap = abi.adapt_params(**params)
     h, w = scene.height, scene.width
-    img, img8 = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.uint8)
+    img, img8 = _frame_pair(h, w, None)
     counts = np.zeros(((h + abi.TILE - 1) // abi.TILE, (w + abi.TILE - 1) // abi.TILE), np.uint32)
-    stats = (C.c_uint64 * abi.NSTATS)()
+    stats = _host_counters()
     secs = C.c_double(0)
-    meshes = scene.hip_meshes()
-    _check(shim.rt_hip_render_adaptive_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(scene.camera), C.byref(p),
-                                             C.byref(ap), device, img.ctypes.data, img8.ctypes.data, counts.ctypes.data, stats,
-                                             C.byref(secs), None, None), "rt_hip_render_adaptive_image")
+    _check(shim.rt_hip_render_adaptive_image(*_host_scene(scene), C.byref(scene.camera), C.byref(p), C.byref(ap), device, img.ctypes.data,
+                                             img8.ctypes.data, counts.ctypes.data, stats, C.byref(secs), None, None),
+           "rt_hip_render_adaptive_image")
     return img, img8, counts, _stats_dict(stats), secs.value
+
+
+def _host_rays(rays, camera):
+    """(rays, n, source) of a host query: float64 [n, 6] given rays, or with a camera [n, 2] (u, v)"""
+    rays = np.ascontiguousarray(np.asarray(rays, dtype=np.float64).reshape(-1, 2 if camera is not None else 6))
+    return rays, rays.shape[0], abi.RAYS_CAMERA_UV if camera is not None else abi.RAYS_GIVEN
 
 
 def query_rays_host(scene, rays, t_max=None, normalize=False, origin_radius=None, camera=None, device=0, want=abi.HIT_FIELDS):
@@ -1414,17 +1443,14 @@ def query_rays_host(scene, rays, t_max=None, normalize=False, origin_radius=None
     rays: [n, 6] float64 (origin, direction), or with `camera` (an abi.Camera) [n, 2] (u, v) -> dict of numpy arrays: status /
     object / prim uint32 [n], t float64 [n], point / normal [n, 3], bary [n, 2], ray [n, 6]"""
     shim = abi.load_shim()
-    per_ray = 2 if camera is not None else 6
-    rays = np.ascontiguousarray(np.asarray(rays, dtype=np.float64).reshape(-1, per_ray))
-    n = rays.shape[0]
+    rays, n, source = _host_rays(rays, camera)
     if t_max is not None:
         t_max = np.ascontiguousarray(np.asarray(t_max, dtype=np.float64).reshape(-1))
         if t_max.size != n:
             raise ValueError("query_rays_host: t_max must hold one value per ray")
-    p = abi.query_params(abi.RAYS_CAMERA_UV if camera is not None else abi.RAYS_GIVEN, normalize, camera, origin_radius)
+    p = abi.query_params(source, normalize, camera, origin_radius)
     out, hits = _wanted(abi.RtHipHits(), abi.HIT_SHAPES, want, n, None)
-    meshes = scene.hip_meshes()
-    _check(shim.rt_hip_query_rays_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, rays.ctypes.data,
+    _check(shim.rt_hip_query_rays_host(*_host_scene(scene), rays.ctypes.data,
                                        t_max.ctypes.data if t_max is not None else None, n, C.byref(p), device, C.byref(hits)),
            "rt_hip_query_rays_host")
     return out
@@ -1436,16 +1462,12 @@ def trace_rays_host(scene, rays, samples, seed, max_depth=None, normalize=False,
     rays: [n, 6] float64 (origin, direction), or with `camera` (an abi.Camera) [n, 2] (u, v) -> dict of numpy arrays: status uint32
     [n], radiance float64 [n, 3], samples [n, samples, 3], paths / casts uint64 [n], ray [n, 6], and stats (a dict)"""
     shim = abi.load_shim()
-    per_ray = 2 if camera is not None else 6
-    rays = np.ascontiguousarray(np.asarray(rays, dtype=np.float64).reshape(-1, per_ray))
-    n = rays.shape[0]
-    p = abi.trace_params(samples, seed, scene.max_depth if max_depth is None else max_depth,
-                         abi.RAYS_CAMERA_UV if camera is not None else abi.RAYS_GIVEN, normalize, camera, origin_radius, index_first)
+    rays, n, source = _host_rays(rays, camera)
+    p = abi.trace_params(samples, seed, _depth(scene, max_depth), source, normalize, camera, origin_radius, index_first)
     out, rad = _wanted(abi.RtHipRadiance(), abi.RADIANCE_SHAPES, want, n, None, samples)
-    stats = (C.c_uint64 * abi.NSTATS)()
-    meshes = scene.hip_meshes()
-    _check(shim.rt_hip_trace_rays_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, rays.ctypes.data, n, C.byref(p), device,
-                                       C.byref(rad), stats), "rt_hip_trace_rays_host")
+    stats = _host_counters()
+    _check(shim.rt_hip_trace_rays_host(*_host_scene(scene), rays.ctypes.data, n, C.byref(p), device, C.byref(rad), stats),
+           "rt_hip_trace_rays_host")
     out["stats"] = _stats_dict(stats)
     return out
 
@@ -1459,7 +1481,7 @@ def lens_rays(camera, width, height, aperture, focus, seed, sample, pixel_first=
     rays = torch.empty((max(n, 0), 6), dtype=torch.float64, device=dev)
     lens = abi.lens_params(aperture, focus)
     _check(shim.rt_hip_lens_rays(C.byref(camera), C.byref(lens), width, height, seed, sample, pixel_first, n,
-                                 C.c_void_p(rays.data_ptr() if n > 0 else None), _stream(dev)), "rt_hip_lens_rays")
+                                 _some(rays), _stream(dev)), "rt_hip_lens_rays")
     return rays
 
 
@@ -1469,10 +1491,8 @@ def lens_resolve(total, samples):
     shim = abi.load_shim()
     total = total.contiguous()
     h, w, _ = total.shape
-    rgb = torch.empty((h, w, 3), dtype=torch.float32, device=total.device)
-    rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=total.device)
-    _check(shim.rt_hip_lens_resolve(C.c_void_p(total.data_ptr()), w, h, samples, C.c_void_p(rgb.data_ptr()), C.c_void_p(rgb8.data_ptr()),
-                                    _stream(total.device)), "rt_hip_lens_resolve")
+    rgb, rgb8 = _frame_pair(h, w, total.device)
+    _check(shim.rt_hip_lens_resolve(_ptr(total), w, h, samples, _ptr(rgb), _ptr(rgb8), _stream(total.device)), "rt_hip_lens_resolve")
     return rgb, rgb8
 
 
@@ -1480,19 +1500,12 @@ def render_lens_host(scene, aperture, focus, samples, seed, camera=None, max_dep
     """rt_hip_render_lens_image(): the C hosts' entry point (its own scene on logical device `device`, synchronous) ->
     (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3], stats dict)"""
     shim = abi.load_shim()
-    p = abi.RtHipParams()
-    p.width, p.height = scene.width, scene.height
-    p.samples = samples
-    p.max_depth = scene.max_depth if max_depth is None else max_depth
-    p.seed = seed
+    p = _params(scene, seed, samples, _depth(scene, max_depth))
     lens = abi.lens_params(aperture, focus)
-    cam = camera if camera is not None else scene.camera
-    img = np.zeros((scene.height, scene.width, 3), dtype=np.float32)
-    img8 = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
-    stats = (C.c_uint64 * abi.NSTATS)()
-    meshes = scene.hip_meshes()
-    _check(shim.rt_hip_render_lens_image(scene.objects, scene.n_objects, meshes, scene.n_meshes, C.byref(cam), C.byref(lens), C.byref(p),
-                                         device, img.ctypes.data, img8.ctypes.data, stats), "rt_hip_render_lens_image")
+    img, img8 = _frame_pair(scene.height, scene.width, None)
+    stats = _host_counters()
+    _check(shim.rt_hip_render_lens_image(*_host_scene(scene), C.byref(_camera(scene, camera)), C.byref(lens), C.byref(p), device, img.ctypes.data,
+                                         img8.ctypes.data, stats), "rt_hip_render_lens_image")
     return img, img8, _stats_dict(stats)
 
 
@@ -1514,14 +1527,11 @@ def probe_rays(positions, samples, seed, normals=None, bias=0.0, k_first=0, n=No
     a device tensor [n, 6] float64 (origin, direction), asynchronous on torch's current stream"""
     shim = abi.load_shim()
     dev = torch.device("cuda", device)
-    pos = torch.as_tensor(positions, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
-    nrm = None if normals is None else torch.as_tensor(normals, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+    pos, nrm = _points3(positions, dev), None if normals is None else _points3(normals, dev)
     n = pos.shape[0] * samples - k_first if n is None else n
     rays = torch.empty((max(n, 0), 6), dtype=torch.float64, device=dev)
     p = abi.probe_params(abi.PROBE_SPHERE if nrm is None else abi.PROBE_HEMISPHERE, samples, seed, bias=bias)
-    _check(shim.rt_hip_probe_rays(C.c_void_p(pos.data_ptr() if pos.numel() else None), C.c_void_p(nrm.data_ptr() if nrm is not None else None),
-                                  pos.shape[0], C.byref(p), k_first, n, C.c_void_p(rays.data_ptr() if n > 0 else None), _stream(dev)),
-           "rt_hip_probe_rays")
+    _check(shim.rt_hip_probe_rays(_some(pos), _some(nrm), pos.shape[0], C.byref(p), k_first, n, _some(rays), _stream(dev)), "rt_hip_probe_rays")
     return rays
 
 
@@ -1533,8 +1543,7 @@ def probe_resolve(total, samples):
     n, bases, _ = total.shape
     mode = {9: abi.PROBE_SPHERE, 1: abi.PROBE_HEMISPHERE}[bases]
     coeff, coeff_f = torch.empty_like(total), torch.empty(total.shape, dtype=torch.float32, device=total.device)
-    _check(shim.rt_hip_probe_resolve(C.c_void_p(total.data_ptr()), n, mode, samples, C.c_void_p(coeff.data_ptr()), C.c_void_p(coeff_f.data_ptr()),
-                                     _stream(total.device)), "rt_hip_probe_resolve")
+    _check(shim.rt_hip_probe_resolve(_ptr(total), n, mode, samples, _ptr(coeff), _ptr(coeff_f), _stream(total.device)), "rt_hip_probe_resolve")
     return coeff, coeff_f
 
 
@@ -1545,14 +1554,12 @@ def probe_irradiance(sh, index, normals):
     sh = sh.contiguous()
     dev = sh.device
     idx = (torch.as_tensor(index, device=dev).to(torch.int64) & 0xFFFFFFFF).to(torch.uint32).reshape(-1).contiguous()
-    nrm = torch.as_tensor(normals, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+    nrm = _points3(normals, dev)
     m = nrm.shape[0]
     if idx.numel() != m:
         raise ValueError(f"{idx.numel()} indices for {m} normals")
     out = torch.empty((m, 3), dtype=torch.float64, device=dev)
-    _check(shim.rt_hip_probe_irradiance(C.c_void_p(sh.data_ptr() if sh.numel() else None), sh.shape[0], C.c_void_p(idx.data_ptr() if m else None),
-                                        C.c_void_p(nrm.data_ptr() if m else None), m, C.c_void_p(out.data_ptr() if m else None),
-                                        _stream(dev)), "rt_hip_probe_irradiance")
+    _check(shim.rt_hip_probe_irradiance(_some(sh), sh.shape[0], _some(idx), _some(nrm), m, _some(out), _stream(dev)), "rt_hip_probe_irradiance")
     return out
 
 
@@ -1561,9 +1568,8 @@ def probe_grid_positions(grid, device=0):
     float64 [N, 3] on the device, asynchronous on torch's current stream"""
     shim = abi.load_shim()
     dev = torch.device("cuda", device)
-    out = torch.empty((grid.count[0] * grid.count[1] * grid.count[2], 3), dtype=torch.float64, device=dev)
-    _check(shim.rt_hip_probe_grid_positions(C.byref(grid), C.c_void_p(out.data_ptr() if out.numel() else None), _stream(dev)),
-           "rt_hip_probe_grid_positions")
+    out = torch.empty((_grid_count(grid), 3), dtype=torch.float64, device=dev)
+    _check(shim.rt_hip_probe_grid_positions(C.byref(grid), _some(out), _stream(dev)), "rt_hip_probe_grid_positions")
     return out
 
 
@@ -1575,16 +1581,14 @@ def probe_shade(grid, coeff, points, normals, status=None, albedo=None, add=None
     shim = abi.load_shim()
     coeff = coeff.contiguous()
     dev = coeff.device
-    pts = torch.as_tensor(points, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
-    nrm = torch.as_tensor(normals, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+    pts, nrm = _points3(points, dev), _points3(normals, dev)
     n = pts.shape[0]
     if nrm.shape[0] != n:
         raise ValueError(f"{nrm.shape[0]} normals for {n} points")
     st = None if status is None else torch.as_tensor(status, device=dev).reshape(-1).contiguous()
     if st is not None and st.dtype not in (torch.int32, torch.uint32):
         st = st.to(torch.int32)
-    alb = None if albedo is None else torch.as_tensor(albedo, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
-    ad = None if add is None else torch.as_tensor(add, dtype=torch.float32, device=dev).reshape(-1, 3).contiguous()
+    alb, ad = (None if t is None else _points3(t, dev, torch.float32) for t in (albedo, add))
     for name, t, per in (("status", st, 1), ("albedo", alb, 3), ("add", ad, 3)):
         if t is not None and t.numel() != per * n:
             raise ValueError(f"probe_shade: {name} must hold {per} value(s) per entry")
@@ -1592,10 +1596,9 @@ def probe_shade(grid, coeff, points, normals, status=None, albedo=None, add=None
     for f, dt in (("irradiance", torch.float64), ("color", torch.float32)):
         if f in want and f not in res:
             res[f] = torch.empty((n, 3), dtype=dt, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-    _check(shim.rt_hip_probe_shade(C.byref(grid), ptr(coeff), ptr(pts), ptr(nrm), ptr(st), ptr(alb), ptr(ad), n if m is None else m,
-                                   ptr(res.get("irradiance") if "irradiance" in want else None), ptr(res.get("color") if "color" in want else None),
-                                   _stream(dev)), "rt_hip_probe_shade")
+    _check(shim.rt_hip_probe_shade(C.byref(grid), _some(coeff), _some(pts), _some(nrm), _some(st), _some(alb), _some(ad), n if m is None else m,
+                                   _some(res.get("irradiance"), "irradiance" in want), _some(res.get("color"), "color" in want), _stream(dev)),
+           "rt_hip_probe_shade")
     return {f: res[f] for f in want}
 
 
@@ -1604,19 +1607,14 @@ def probe_preview_host(scene, grid, samples, seed, camera=None, aov_samples=1, m
     with `samples` rays a probe under `seed`, then the preview of the scene's frame -> (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3],
     coeff float64 [N, 9, 3], stats dict)"""
     shim = abi.load_shim()
-    n = grid.count[0] * grid.count[1] * grid.count[2]
-    if origin_radius is None:
-        far = [max(abs(grid.origin[a]), abs(grid.origin[a] + (grid.count[a] - 1) * grid.step[a])) for a in range(3)]
-        origin_radius = _distance(far) * (1.0 + 2.0 ** -40)
-    p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, scene.max_depth if max_depth is None else max_depth, 0.0, origin_radius)
-    img = np.zeros((scene.height, scene.width, 3), dtype=np.float32)
-    img8 = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
-    coeff = np.zeros((n, 9, 3), dtype=np.float64)
-    stats = (C.c_uint64 * abi.NSTATS)()
-    cam = camera if camera is not None else scene.camera
-    _check(shim.rt_hip_probe_preview_image(scene.objects, scene.n_objects, scene.hip_meshes(), scene.n_meshes, C.byref(cam), C.byref(grid),
-                                           C.byref(p), scene.width, scene.height, aov_samples, device, img.ctypes.data, img8.ctypes.data,
-                                           coeff.ctypes.data, stats), "rt_hip_probe_preview_image")
+    p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, _depth(scene, max_depth), 0.0,
+                         _grid_radius(grid) if origin_radius is None else origin_radius)
+    img, img8 = _frame_pair(scene.height, scene.width, None)
+    coeff = np.zeros((_grid_count(grid), 9, 3), dtype=np.float64)
+    stats = _host_counters()
+    _check(shim.rt_hip_probe_preview_image(*_host_scene(scene), C.byref(_camera(scene, camera)), C.byref(grid), C.byref(p), scene.width,
+                                           scene.height, aov_samples, device, img.ctypes.data, img8.ctypes.data, coeff.ctypes.data, stats),
+           "rt_hip_probe_preview_image")
     return img, img8, coeff, _stats_dict(stats)
 
 
@@ -1631,14 +1629,12 @@ def bake_probes_host(scene, positions, samples, seed, normals=None, bias=0.0, ma
     if origin_radius is None:
         norms = lambda a: None if a is None else np.sqrt((a * a).sum(axis=1))
         origin_radius = _origin_radius(norms(pos), norms(nrm), bias)
-    p = abi.probe_params(mode, samples, seed, scene.max_depth if max_depth is None else max_depth, bias, origin_radius)
+    p = abi.probe_params(mode, samples, seed, _depth(scene, max_depth), bias, origin_radius)
     n, bases = pos.shape[0], abi.PROBE_BASES[mode]
     coeff = np.zeros((n, bases, 3), dtype=np.float64)
     coeff_f = np.zeros((n, bases, 3), dtype=np.float32)
     status = np.zeros(n, dtype=np.uint32)
-    stats = (C.c_uint64 * abi.NSTATS)()
-    meshes = scene.hip_meshes()
-    _check(shim.rt_hip_bake_probes_host(scene.objects, scene.n_objects, meshes, scene.n_meshes, pos.ctypes.data, nrm.ctypes.data if nrm is not None else None,
-                                        n, C.byref(p), device, coeff.ctypes.data, coeff_f.ctypes.data, status.ctypes.data, stats),
-           "rt_hip_bake_probes_host")
+    stats = _host_counters()
+    _check(shim.rt_hip_bake_probes_host(*_host_scene(scene), pos.ctypes.data, nrm.ctypes.data if nrm is not None else None, n, C.byref(p), device,
+                                        coeff.ctypes.data, coeff_f.ctypes.data, status.ctypes.data, stats), "rt_hip_bake_probes_host")
     return coeff, coeff_f, status, _stats_dict(stats)
