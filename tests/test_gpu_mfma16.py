@@ -12,13 +12,30 @@ the kernel, so this is how the tests know which form they compared.  And its twi
 counts the packed loop's candidates on the same rays: what the matrix form keeps beyond them stays below 2 % of config 4's filter
 evaluations (more, and phase 2 eats what phase 1 saves).
 
+The EDGE scenes of tests/mfma16_child.py (edge_scenes: 64 x 64, 8 spp for frames, 4 spp under PT_DIAG, depth 16) take the same three
+statements to where the prologue's selection rule changes its answer and away from config 4's operating point.  The matrix pipe must
+run (0 < matrix_trips < trips) with no violation, and shipped must equal packed, on: the room scaled by 1/8 about the origin (near_R
+16.5; 1/8 is the smallest power of two that leaves the walls wall-sized), the camera placed for near_R in [247.5, 250], the origin near
+a corner of the room, no walls with 32 and with 64 small spheres (mf_first = 0), floor and ceiling only (n_big 2), two walls listed
+behind the rows (n_big 4, the walls at mf_first + 32 and + 33), 64 spheres with six walls, rows on the axes, at the origin, concentric
+and identical -- and on the family's other member whose body has the filter, pt_render_tiles_chk (one checkered sphere; the family
+table gives MFMA_FILT to pt_render_tiles and pt_render_tiles_chk alone).  It must NOT run (matrix_trips == 0), with the same frames and
+no violation, on: near_R in (250, 252.5], five leading walls (n_big 4: the fifth is row 0), a wall-sized sphere amid the rows, 65
+spheres, no walls and 31 small spheres.  Four of them -- scaled 1/8, near_R under 250, no walls 32, five walls -- also meet the CPU oracle
+through util.assert_parity, so these operating points are compared with the reference and not only with a sibling build.
+
 Each build renders the whole list in ONE child process (RT_HIP_SHIM_PATH); the lists are rendered once per module."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+import mfma16_child as CH
+from conftest import SEED
+from util import assert_parity, fixed_point_floor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "raytracer.c_amd", "csrc")
@@ -95,3 +112,51 @@ def test_matrix_filter_keeps_few_candidates_the_packed_filter_drops():
     share = (a["candidates"] - b["candidates"]) / a["filter_evals"]
     print("config 4: candidates %d (matrix) vs %d (packed) of %d filter evaluations: %.4f %%" % (a["candidates"], b["candidates"], a["filter_evals"], 100 * share))
     assert share < 0.02
+
+
+EDGES = CH.edge_scenes()
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    from rt_amd import abi, gpu as G
+    assert abi.load_shim().rt_hip_device_count() >= 1, "no HIP device: the GPU tests must run on the GPU box"
+    assert torch.cuda.is_available()
+    return G
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene", list(EDGES))
+def test_matrix_filter_on_the_edges_of_its_selection_rule(scene):
+    e = EDGES[scene]
+    a, b, d, dp = _run("shipped", "frames")[scene], _run("packed", "frames")[scene], _run("diag", "diag")[scene], _run("diag_packed", "diag")[scene]
+    print(scene, d)
+    assert a["kernel"] == b["kernel"] == d["kernel"] and (e["kernel"] is None or a["kernel"] == e["kernel"])
+    assert a["n"] == len(e["objs"]) and a["n_big"] == e["n_big"]
+    assert (a["counters"], a["tiles"], a["tiles8"]) == (b["counters"], b["tiles"], b["tiles8"]), f"{scene}: shipped and packed frames differ"
+    assert a["counters"][0] > 0
+    assert d["violations"] == dp["violations"] == 0
+    assert d["filter_evals"] > 10000 and 0 < d["candidates"] < d["filter_evals"], "the check was vacuous"
+    assert (d["counters"], d["tiles"], d["trips"], d["filter_evals"]) == (dp["counters"], dp["tiles"], dp["trips"], dp["filter_evals"])
+    assert dp["matrix_trips"] == 0
+    if e["on"]:
+        assert 0 < d["matrix_trips"] < d["trips"], "the matrix pipe did not run: the scene fell back to the packed loop"
+        print("%s (%s, near_R %.2f): candidates %d (matrix) vs %d (packed) of %d filter evaluations: %.4f %%"
+              % (scene, d["kernel"], d["near_R"], d["candidates"], dp["candidates"], d["filter_evals"], 100.0 * (d["candidates"] - dp["candidates"]) / d["filter_evals"]))
+    else:
+        assert d["matrix_trips"] == 0, "the matrix pipe ran on a scene it must leave to the packed loop"
+        assert d["candidates"] == dp["candidates"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene", ["scaled 1/8", "near_R under 250", "no walls 32", "five walls"])
+def test_edge_scenes_meet_the_oracle(gpu, pt, scene):
+    sc, e = CH.edge_scene(scene, 8)
+    mean, rgb8, ost = pt.render_pixels(sc, SEED)
+    gs = gpu.GpuScene(sc)
+    CH.check_edge(gs, e)
+    img, img8, st = gs.render_image(SEED)
+    assert gs.last_launch_kernel() == "pt_render_tiles" and gs.launch_status() == 0
+    assert_parity(img.cpu().numpy(), img8.cpu().numpy(), st, mean, rgb8, ost, what=scene, hdr=True, abs_floor=fixed_point_floor(sc))
+    gs.close()

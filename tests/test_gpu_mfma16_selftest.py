@@ -17,7 +17,22 @@ What is asserted, and where the figures come from (the derivation above pt_mfma1
   - the pipe's raw tca16 and ll16 (spheres 0 and 16 against 32 rays of each block) are within ET and EL of fp64: the sum of
     sixteen exact products on the matrix pipe loses what the bound allows for and no more;
   - NaN directions hit nothing in the exact test; which bits such a ray keeps is not specified (a NaN's sign is arbitrary).
-The share of exact misses that the matrix form keeps and the packed form drops is printed."""
+The share of exact misses that the matrix form keeps and the packed form drops is printed.
+
+That layout sits at one operating point (near_R = 160, radii of order 1, centres 20 to 60 out).  The SHARED SETS of
+tests/mfma16_vectors.py take the same statements to the edges of the fit rule and of the bound, one self-test call per set:
+near_R = 250 and the next double after it (no row may fit), the layout scaled down to near_R = 2^-6 (centre halves below 2^-14: fp16
+subnormals, where the phi floors of the derivation carry the bound), signed zeros and components of 2^-15 and 2^-20, concentric and
+identical spheres, a radius of 1e-100, |kq| near 60000 beside the twins that just do not fit, and a call whose middle block alone
+has an unfitting row.  Per set:
+  - h_hit per block as the set states; where it is 0 the matrix words ARE the packed words;
+  - no pair the device's exact test accepts is dropped by either form (no tolerance), and that test equals the oracle's;
+  - hits, grazes and axis rays keep their sphere, rays inside one keep it, rays beyond near_R and in the far-origin shell
+    (|o| = near_R (1 - 2^-20): filter_ray turns away |o'|^2 > 0.9999 near_R^2) keep everything, surface origins lose nothing exact;
+  - the aimed misses are dropped.  They stand at r^2 + 2.5 W16 where E16 < 1.5 W16 - (the split's residual) holds for every row of
+    the set -- asserted from the formulas first -- and else (near_R = 2^-6: the constant 2^-22 of the residual outweighs W16 / 2
+    there) at r^2 + W16 + residual + 1.25 E16, from E16's formula; never from what the device returns;
+  - raw tca16 and ll16 within ET and EL on every fitting block (spheres 0 and 16 of the block against its lanes 0..31)."""
 import ctypes as C
 import os
 import sys
@@ -27,6 +42,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "raytracer.c_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import mfma16_vectors as V   # noqa: E402
 
 NEAR_R = 160.0
 E = 2.0 ** -24
@@ -44,16 +62,10 @@ def _spheres():
 
 
 def _bounds(cen, rad):
-    """A, W16, ET, EL per sphere, as pt_mfma16_row computes them (filt_shift as the self-test's launch sets it)"""
-    cn = np.linalg.norm(cen, axis=1) * (1.0 + 1e-12)
-    tol = 12.0 * E * (cn.max() + NEAR_R) * (1.0 + 1e-9)
-    A = (cn + NEAR_R + tol) * (1.0 + 1e-6)
-    g = np.abs(cn * cn - rad * rad)
-    W16 = (A * A / 65536.0 + g / 262144.0 + A / 131072.0) * (1.0 + 1e-6)
-    kq = np.abs(cn * cn - rad * rad - W16)
-    ET = 3 * 2.0 ** -19 * A + 2.0 ** -20
-    EL = 1.82 * 2.0 ** -19 * A * A + 1.16 * 2.0 ** -19 * kq + 6 * E * A
-    return tol, A, W16, ET, EL
+    """A, W16, ET, EL per sphere (tests/mfma16_vectors.py restates pt_mfma16_row's figures; filt_shift as the self-test's launch sets it)"""
+    tol = V.filt_shift(float(V.center_norm(cen).max()), NEAR_R)
+    B = V.bounds(cen, rad, NEAR_R, tol)
+    return tol, B["A"], B["W16"], B["ET"], B["EL"]
 
 
 def _frame(k):
@@ -165,3 +177,104 @@ def test_accumulators_of_the_matrix_pipe_are_within_the_bound(run):
         assert -R["EL"][s] - (kq * 2.0 ** -20 + 2.0 ** -22) - 1e-9 * (1 + kq) <= err <= R["EL"][s] + 1e-9 * (1 + kq), (i, R["tuv"][i, 1], target)
         worst_t, worst_l = max(worst_t, abs(R["tuv"][i, 0] - tca) / R["ET"][s]), max(worst_l, abs(err) / R["EL"][s])
     print("largest |tca16 - tca'| / ET = %.3f, |ll16 - ll| / EL = %.3f" % (worst_t, worst_l))
+
+
+# ---- the shared sets ------------------------------------------------------------------------------------------------------------
+_CALLS = {}
+
+
+def _call(name):
+    """one rt_hip_selftest_intersect call per set, shared by the tests of that set"""
+    if name not in _CALLS:
+        from rt_amd import abi
+        shim = abi.load_shim()
+        S = V.SETS[name]
+        rays, prims = V.arrays(S)
+        n = len(rays)
+        hit, tuv, keep = np.zeros(n, dtype=np.uint8), np.zeros((n, 3)), np.zeros((n, 3), dtype=np.uint64)
+        rc = shim.rt_hip_selftest_intersect(2, rays.ctypes.data, prims.ctypes.data, n, C.c_double(S["near_R"]), hit.ctypes.data, tuv.ctypes.data,
+                                            keep.ctypes.data, 0)
+        assert rc == 0, shim.rt_hip_last_error()
+        bits = lambda col: ((keep[:, col][:, None] >> np.arange(64, dtype=np.uint64)[None]) & np.uint64(1)).astype(bool)   # noqa: E731
+        _CALLS[name] = dict(hit=hit, tuv=tuv, packed=bits(0), matrix=bits(1), exact=bits(2))
+    return _CALLS[name]
+
+
+def test_must_drop_inequality_of_every_set():
+    """E16 < 1.5 W16 - residual, row by row, from the formulas: it holds everywhere but at near_R = 2^-6, whose misses stand at
+    r^2 + W16 + residual + 1.25 E16 instead (docs/HISTORY.md: the comment's "E16 <= W16" is not general)"""
+    for name, S in V.SETS.items():
+        for b in S["blocks"]:
+            B = {k: v[:32] for k, v in b["bounds"].items()}
+            holds = bool(V.must_drop_holds(B).all())
+            assert holds == b["drop_plain"] == (name != "small-2^-6"), name
+            d2 = b["rad"][:32] ** 2 + (2.5 * B["W16"] if holds else B["W16"] + B["resid"] + 1.25 * B["E16"])
+            assert (d2 > b["rad"][:32] ** 2 + B["W16"] + B["resid"] + B["E16"]).all(), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(V.SETS))
+def test_keep_words_on_the_shared_sets(name, pt):
+    S, R = V.SETS[name], _call(name)
+    kept_extra = evals = 0
+    for n, b in enumerate(S["blocks"]):
+        at = slice(64 * n, 64 * n + 64)
+        hit, packed, matrix, exact = R["hit"][at], R["packed"][at], R["matrix"][at], R["exact"][at]
+        rays, kind, cen, rad = b["rays"], b["kind"], b["cen"], b["rad"]
+        assert (hit == (1 if b["fits"] else 0)).all(), (name, n, "the block's rows fit" if hit.any() else "a row did not fit")
+        if not b["fits"]:
+            assert np.array_equal(matrix, packed), (name, n, "a block that fell back does not give the packed words")
+        finite = np.isfinite(rays).all(axis=1)
+        oracle = np.array([[bool(pt.intersect_sphere(rays[i], cen[j], rad[j])[0]) for j in range(64)] for i in range(64)])
+        assert np.array_equal(oracle[finite], exact[finite]), (name, n, "the device's exact test and the oracle's disagree")
+        assert not exact[~finite].any()
+        assert not (exact & ~matrix).any(), (name, n, "the matrix form drops a pair the exact test accepts", np.argwhere(exact & ~matrix)[:4])
+        assert not (exact & ~packed).any(), (name, n, "the packed form drops a pair the exact test accepts")
+        own = lambda m: m[np.arange(64), b["target"]]   # noqa: E731
+        for what in ("hit", "graze", "axis"):
+            assert own(exact)[kind == what].all() and own(matrix)[kind == what].all() and own(packed)[kind == what].all(), (name, n, what)
+        for what in ("miss", "margin", "nan", "away"):
+            assert not own(exact)[kind == what].any(), (name, n, what)
+        assert own(matrix)[kind == "inside"].all(), (name, n)
+        for what in ("far", "edge"):
+            assert matrix[kind == what].all() and packed[kind == what].all(), (name, n, what)
+        for what in ("surf_in", "surf_out", "rim"):
+            assert not (own(exact) & ~own(matrix))[kind == what].any(), (name, n, what)
+        assert np.array_equal(matrix[:, 32:], packed[:, 32:]), (name, n, "the packed loop behind the matrix rows changed its words")
+        if b["fits"]:
+            assert not own(matrix)[kind == "miss"].any(), (name, n, "an aimed miss beyond W16 + E16 is kept: a row of the A operand is misplaced, or the bound does not hold")
+            near = ~np.isin(kind, ("far", "edge", "nan"))
+            extra = matrix[near, :32] & ~packed[near, :32] & ~exact[near, :32]
+            kept_extra, evals = kept_extra + int(extra.sum()), evals + extra.size
+            print("%s block %d: margin rays kept %d of %d" % (name, n, own(matrix)[kind == "margin"].sum(), (kind == "margin").sum()))
+    print("%s: exact misses the matrix form keeps and the packed form drops: %d of %d evaluations (%.3f %%)"
+          % (name, kept_extra, evals, 100.0 * kept_extra / max(evals, 1)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [n for n, S in V.SETS.items() if any(b["fits"] for b in S["blocks"])])
+def test_accumulators_on_the_shared_sets(name):
+    S, R = V.SETS[name], _call(name)
+    worst_t = worst_l = 0.0
+    checked = 0
+    for n, b in enumerate(S["blocks"]):
+        if not b["fits"]:
+            continue
+        B = b["bounds"]
+        for i in range(64):
+            ray, s = i % 32, 16 * (i // 32)
+            if b["kind"][ray] in ("nan", "far"):
+                continue
+            o, d = b["rays"][ray, :3] - S["tol"] * b["rays"][ray, 3:], b["rays"][ray, 3:]
+            L = b["cen"][s] - o
+            tca = float(L @ d)
+            tca16, ll16 = R["tuv"][64 * n + i, 0], R["tuv"][64 * n + i, 1]
+            assert abs(tca16 - tca) <= B["ET"][s], (name, n, i, tca16, tca)
+            target = float(L @ L) - b["rad"][s] ** 2 - B["W16"][s]
+            kq = B["kq"][s]
+            err = ll16 - target
+            assert -B["EL"][s] - B["resid"][s] - 1e-9 * (1 + kq) <= err <= B["EL"][s] + 1e-9 * (1 + kq), (name, n, i, ll16, target)
+            worst_t, worst_l = max(worst_t, abs(tca16 - tca) / B["ET"][s]), max(worst_l, abs(err) / B["EL"][s])
+            checked += 1
+    assert checked >= 64
+    print("%s: largest |tca16 - tca'| / ET = %.3f, |ll16 - ll| / EL = %.3f over %d probes" % (name, worst_t, worst_l, checked))

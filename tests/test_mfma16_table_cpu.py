@@ -9,7 +9,12 @@ tests/mfma16_row_harness.cpp, and a numpy emulation of the device's side of the 
   - spheres out of range are not flagged: a wall-sized radius, a far centre, kq beyond 60000, near_R beyond the form's limit, NaN;
   - the emulation on config 4's scene: every (ray, sphere) pair with tca >= 0 and d2 <= r^2 -- a superset of what the exact test
     accepts -- is kept, and the pairs the matrix form keeps although the packed-fp32 form's widening would drop them are fewer
-    than 2 % of the evaluations (beyond that phase 2 would eat what phase 1 saves)."""
+    than 2 % of the evaluations (beyond that phase 2 would eat what phase 1 saves);
+  - the shared sets of tests/mfma16_vectors.py (near_R at 250 and just past it, down to 2^-6, signed zeros and tiny components, |kq| near
+    60000 and the just-unfitting twins, a block with one unfitting row): every row fits or not as the set states and as the fit rule
+    restated there says, a fitting row passes the layout checks, an unfitting one is all zeros, and the emulation keeps every pair
+    with tca >= 0 and d2 <= r^2 on every fitting block.  The emulation is not the device -- the device's split rounds differently --:
+    this checks the vectors and the bound's arithmetic, the GPU self-test checks the kernel on the same sets."""
 import os
 import subprocess
 import sys
@@ -19,6 +24,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "raytracer.c_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import mfma16_vectors as V   # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -85,7 +93,8 @@ def test_spheres_out_of_range_are_not_flagged(harness):
 
 def _rtz16(x):
     """fp32 array -> fp16 rounded towards zero (v_cvt_pkrtz_f16_f32), as float64"""
-    h = x.astype(np.float16)
+    with np.errstate(over="ignore"):   # (a ray from beyond near_R: |o'|^2 past fp16's range, as on the device; such a ray keeps everything)
+        h = x.astype(np.float16)
     over = np.abs(h.astype(np.float64)) > np.abs(x.astype(np.float64))
     h = np.where(over, np.nextafter(h, np.float16(0)), h)
     return h.astype(np.float64)
@@ -98,6 +107,30 @@ def _split(x, parts):
         out.append(p)
         rest = (rest.astype(np.float64) - p).astype(np.float32)   # exact in fp32
     return out
+
+
+def _emulate(H, o, d, tol, near_R):
+    """the device's side of the contraction against the rows H [32, 16]: -> keep bits [n, 32] and the rays the filter looks at at all
+    (the others start beyond near_R by filter_ray's fp32 rule and keep everything)"""
+    # the device's ray (filter_ray, SHIFT): fp32, pulled back
+    o32 = (o - tol * d).astype(np.float32)
+    d32 = d.astype(np.float32)
+    od = (o32.astype(np.float64) * d32).sum(-1).astype(np.float32)
+    oo = (o32.astype(np.float64) ** 2).sum(-1).astype(np.float32)
+
+    def contract(x, w, s):
+        xs = [_split(x[:, a], 2) for a in range(3)]
+        ws = _split(w, 3)
+        B = np.stack([xs[0][0], xs[1][0], xs[2][0], xs[0][1], xs[1][1], xs[2][1], xs[0][0], xs[1][0], xs[2][0], ws[0], ws[1], ws[2],
+                      np.full(len(w), s), np.full(len(w), s), np.zeros(len(w)), np.zeros(len(w))], axis=1)   # n x 16
+        acc = np.zeros((len(w), 32), dtype=np.float32)
+        for kk in range(16):                                # fp32 accumulation, one rounding per term
+            acc = (acc.astype(np.float64) + B[:, kk][:, None] * H[None, :, kk]).astype(np.float32)
+        return acc
+    t16 = contract(d32, -od, 0.0)
+    l16 = contract(-2.0 * o32, oo, 1.0)
+    q16 = (t16.astype(np.float64) * np.abs(t16) - l16).astype(np.float32)
+    return ~(np.signbit(q16)), oo <= np.float32(near_R * near_R * 0.9999)
 
 
 def test_emulated_matrix_filter_is_conservative_and_tight_on_config4(harness):
@@ -132,25 +165,7 @@ def test_emulated_matrix_filter_is_conservative_and_tight_on_config4(harness):
     tca = (L * d[:, None]).sum(-1)
     d2 = (L * L).sum(-1) - tca * tca
     may_hit = (tca >= 0) & (d2 <= rad[None] ** 2)
-    # the device's ray (filter_ray, SHIFT): fp32, pulled back
-    o32 = (o - tol * d).astype(np.float32)
-    d32 = d.astype(np.float32)
-    od = (o32.astype(np.float64) * d32).sum(-1).astype(np.float32)
-    oo = (o32.astype(np.float64) ** 2).sum(-1).astype(np.float32)
-
-    def contract(x, w, s):
-        xs = [_split(x[:, a], 2) for a in range(3)]
-        ws = _split(w, 3)
-        B = np.stack([xs[0][0], xs[1][0], xs[2][0], xs[0][1], xs[1][1], xs[2][1], xs[0][0], xs[1][0], xs[2][0], ws[0], ws[1], ws[2],
-                      np.full(len(w), s), np.full(len(w), s), np.zeros(len(w)), np.zeros(len(w))], axis=1)   # n x 16
-        acc = np.zeros((len(w), 32), dtype=np.float32)
-        for kk in range(16):                                # fp32 accumulation, one rounding per term
-            acc = (acc.astype(np.float64) + B[:, kk][:, None] * H[None, :, kk]).astype(np.float32)
-        return acc
-    t16 = contract(d32, -od, 0.0)
-    l16 = contract(-2.0 * o32, oo, 1.0)
-    q16 = (t16.astype(np.float64) * np.abs(t16) - l16).astype(np.float32)
-    keep16 = ~(np.signbit(q16))
+    keep16, _ = _emulate(H, o, d, tol, near_R)
     assert not (may_hit & ~keep16).any(), "the emulated matrix form drops a pair with tca >= 0 and d2 <= r^2"
     # the packed-fp32 form's decision, by its widening (40 e A^2 + 12 e g) in exact arithmetic
     A = cn + near_R
@@ -162,3 +177,60 @@ def test_emulated_matrix_filter_is_conservative_and_tight_on_config4(harness):
     print("false keeps of the matrix form beyond the packed form's: %.4f %% of %d evaluations" % (100 * share, keep16.size))
     assert share < 0.02
     assert (~keep16).mean() > 0.8, "the filter should reject most pairs"
+
+
+@pytest.mark.parametrize("name", list(V.SETS))
+def test_rows_of_the_shared_sets_fit_as_stated(harness, name):
+    S = V.SETS[name]
+    for n, b in enumerate(S["blocks"]):
+        spheres = [(*b["cen"][k], b["rad"][k]) for k in range(32)]
+        rows = harness(spheres, S["near_R"], S["tol"])
+        said = V.fits(b["cen"][:32], b["rad"][:32], S["near_R"], S["tol"])
+        assert [r[0] for r in rows] == [int(f) for f in said], (name, n)
+        assert all(r[0] == 1 for r in rows) == b["fits"], (name, n)
+        for k, (s, row) in enumerate(zip(spheres, rows)):
+            if row[0]:
+                _check_row(s, row, S["near_R"])
+                B = b["bounds"]
+                assert row[2] == pytest.approx(B["W16"][k], rel=1e-12) and row[3] == pytest.approx(B["A"][k], rel=1e-12)
+            else:
+                assert (row[1] == 0.0).all() and not np.signbit(row[1]).any(), (name, n, k)
+    if name == "over":
+        assert not any(r[0] for r in rows)
+
+
+@pytest.mark.parametrize("near_R", [160.0, 1.0])
+def test_rows_of_radius_zero(harness, near_R):
+    """a radius of exactly 0 fits the form (the shim's entry points ask |radius| >= 1e-100, so only the row builder ever sees it)"""
+    spheres = [(x * near_R / 160.0, y, z, r) for x, y, z, r in V.ZERO_RADIUS_SPHERES]
+    tol = V.filt_shift(16.0 * near_R / 160.0, near_R)
+    for s, row in zip(spheres, harness(spheres, near_R, tol)):
+        _check_row(s, row, near_R)
+
+
+@pytest.mark.parametrize("name", list(V.SETS))
+def test_emulated_matrix_filter_is_conservative_on_the_shared_sets(harness, name):
+    S = V.SETS[name]
+    looked_at = 0
+    for n, b in enumerate(S["blocks"]):
+        rows = harness([(*b["cen"][k], b["rad"][k]) for k in range(32)], S["near_R"], S["tol"])
+        if not b["fits"]:
+            assert not all(r[0] for r in rows)
+            continue
+        H = np.array([r[1] for r in rows])
+        ok = np.isfinite(b["rays"]).all(axis=1)
+        rays = b["rays"][ok]
+        keep16, near = _emulate(H, rays[:, :3], rays[:, 3:], S["tol"], S["near_R"])
+        tca, d2, hit = V.exact_tables(rays, b["cen"][:32], b["rad"][:32])
+        may_hit = (tca >= 0) & (d2 <= (b["rad"][:32] ** 2)[None])
+        assert not (hit & ~may_hit).any()
+        lost = may_hit & ~keep16 & near[:, None]
+        assert not lost.any(), (name, n, "the emulated matrix form drops a pair with tca >= 0 and d2 <= r^2", np.argwhere(lost)[:4])
+        assert not near[b["kind"][ok] == "far"].any() and not near[b["kind"][ok] == "edge"].any()
+        assert near[np.isin(b["kind"][ok], ("hit", "miss", "graze", "margin", "rim"))].all(), (name, n)
+        looked_at += int(near.sum())
+        aimed = np.nonzero(near & (b["kind"][ok] == "miss"))[0]
+        kept = keep16[aimed, b["target"][ok][aimed]]
+        print("%s block %d: the emulation keeps %d of %d aimed must-drop misses, drops %.1f %% of all pairs"
+              % (name, n, kept.sum(), len(aimed), 100.0 * (~keep16[near]).mean()))
+    assert (looked_at > 0) == any(b["fits"] for b in S["blocks"])
