@@ -263,6 +263,13 @@ void rt_get_lens(double *aperture_radius, double *focus_distance);
 void rt_set_probe_grid(int nx, int ny, int nz);
 void rt_get_probe_grid(int *nx, int *ny, int *nz);
 
+/* The probe grid's visibility weight (rt_hip.h, "probe visibility"): with res in 2 .. 32 the preview above also bakes every probe's
+ * depth moments in a res x res octahedral map from the same rays and shades through rt_hip_probe_preview_vis_scene_image, the other
+ * fields rt_hip_probe_vis_defaults' for the grid: light no longer leaks through walls thinner than a cell.  0, or any other value,
+ * turns it off (the default): the frame is then the plain preview's, bit for bit.  Without a probe grid it does nothing. */
+void rt_set_probe_visibility(int res);
+int rt_get_probe_visibility(void);
+
 /* Who builds the triangle hierarchy of the scenes render() and its kin upload: RT_BVH_HOST (default) = one host core,
  * RT_BVH_DEVICE = the GPU (rt_hip.h, RT_HIP_BVH_DEVICE).  Images, bytes and counters are the same under either; the time a
  * new or changed scene takes to become renderable is what differs.  Other values are ignored.  The reference has no

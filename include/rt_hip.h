@@ -957,6 +957,113 @@ int rt_hip_probe_preview_scene_image(const RtHipScene *scene, const RtHipCamera 
                                      const RtHipProbeParams *probe_params, int32_t width, int32_t height, int32_t aov_samples, float *h_rgb,
                                      uint8_t *h_rgb8, double *h_coeff, uint64_t *h_stats);
 
+/* ---- probe visibility: baked depth moments keep a probe behind a wall from lighting the wall's other side ---------------------------
+ * RT_HIP_GRID_FACING is a weight, not a visibility test.  This is the usual remedy of irradiance volumes: every probe keeps the mean
+ * and the mean square of the distance to the nearest surface in an R x R octahedral MAP of directions, baked from the very rays of
+ * its radiance bake by the ray query that exists (query_launch, untouched), and the shade weighs every corner by the Chebyshev bound
+ * of the chance that the probe sees the shaded point.  What is new is a pure function of its arguments, stated here.  All arithmetic
+ * is fp64 + - * / sqrt, unfused, in the order written; |x| clears the sign bit; sgn(v) = v >= 0.0 ? 1.0 : -1.0.
+ *
+ * THE PARAMETERS (RtHipProbeVis): res = R (2 .. 32), sharp (0 .. 8), d_max (finite, > 0), bias (finite, >= 0), floor (finite, in
+ * (0, 1]); flags and reserved 0.
+ *   - rt_hip_probe_vis_defaults(vis, grid): struct_size = sizeof(RtHipProbeVis), flags 0, res 8, sharp 5, with the grid's step
+ *     (sx, sy, sz): d_max = 1.5 * sqrt((sx*sx + sy*sy) + sz*sz), bias = 0.125 * min(sx, sy, sz), floor = 2^-6, reserved 0.  A NULL
+ *     grid counts as step (1, 1, 1).
+ *
+ * THE MAP.  Texel (tx, ty), 0 <= tx, ty < R, has index tx + R*ty.  Its CENTRE DIRECTION e: a = (((double)tx + 0.5) / (double)R) * 2.0
+ * - 1.0, b likewise from ty; z = (1.0 - |a|) - |b|; if z < 0.0 then (x, y) = ((1.0 - |b|) * sgn(a), (1.0 - |a|) * sgn(b)), else
+ * (x, y) = (a, b); e = (x, y, z) * (1.0 / sqrt((x*x + y*y) + z*z)).
+ * THE LOOKUP of a probe's map at a direction v (not normalised, not zero):
+ *   1. s = (|v.x| + |v.y|) + |v.z|; a = v.x / s; b = v.y / s; if v.z < 0.0 then (a, b) = ((1.0 - |b|) * sgn(a), (1.0 - |a|) * sgn(b)),
+ *      both from the unfolded a and b.
+ *   2. Per axis, with a (tx) and b (ty): u = (a*0.5 + 0.5) * (double)R - 0.5; u = u >= -0.5 ? u : -0.5 (a NaN reads from -0.5: the
+ *      function is total); top = (double)R - 0.5; u = u <= top ? u : top; i0 = floor(u), in -1 .. R-1; f = u - (double)i0; i1 = i0 + 1.
+ *   3. A texel (i, j) outside the map is continued across its edge, in this order: if i is out of 0 .. R-1 then i is clamped into it
+ *      and j = R-1-j; then if j is out of range then j is clamped and i = R-1-i.  So (-1, j) reads (0, R-1-j), (-1, -1) reads
+ *      (R-1, R-1).  Each of the four texels is continued on its own.
+ *   4. gx = 1.0 - fx, gy = 1.0 - fy; w00 = gx*gy, w10 = fx*gy, w01 = gx*fy, w11 = fx*fy; with m_ab the value of texel (i_a, j_b):
+ *      value = ((w00*m00 + w10*m10) + w01*m01) + w11*m11, for mean and for mean2 alike.
+ *
+ * THE DEPTH FOLD.  Sums W, M1, M2 per (probe, texel), over the probe's rays in ascending k (the ray index space and the rays of
+ * "light probes" above) from +0.0.  For a ray of stored direction d, status word st and distance t from the ray query, and the texel's
+ * e: c = (d.x*e.x + d.y*e.y) + d.z*e.z; c = c > 0.0 ? c : 0.0; w = c, then w = w*w `sharp` times (the lobe c^(2^sharp));
+ * dist = st == 1 ? (t < d_max ? t : d_max) : d_max; W = W + w; M1 = M1 + w*dist; M2 = M2 + w*(dist*dist).  A ray of status 2 makes
+ * all sums of its probe NaN and the probe's status word 2.  One thread owns a (probe, texel) and carries its sums across slices:
+ * no bit depends on slice_rays.
+ * THE DEPTH RESOLVE.  mean = W > 0.0 ? M1 / W : d_max; mean2 = W > 0.0 ? M2 / W : d_max*d_max; a NaN W (an invalid probe) gives NaN
+ * for both.  d_moments: N x R*R x 2 doubles [probe][texel][mean, mean2].
+ *
+ * THE BAKE (rt_hip_bake_probe_depth), params->mode RT_HIP_PROBE_SPHERE: the sums are zeroed and the probes' status set to 1; the
+ * ray indices are walked in ascending slices of at most slice_rays: the slice's probe rays (rt_hip_probe_rays' kernel as it stands:
+ * under the same RtHipProbeParams the rays of rt_hip_bake_probes, bit for bit), rt_hip_query_rays' own launch for status and t
+ * (RT_HIP_RAYS_GIVEN, no t_max, origin_radius = params->origin_radius), the fold; then the resolve.  All on `stream`, no host wait.
+ * params->max_depth is checked as rt_hip_bake_probes checks it and not used.
+ *   - rt_hip_probe_depth_workspace_bytes: the d_workspace for slices of slice_rays rays (60 bytes a ray, and the sums, 24 bytes a
+ *     texel and probe); 0 for res out of range, slice_rays == 0 or n_probes * res * res > 2^28.
+ *   - rt_hip_bake_probe_depth: d_positions 3 doubles a probe; d_moments required; d_status (a uint32 a probe) may be NULL.
+ *   - rt_hip_bake_probe_grid_depth: rt_hip_probe_grid_positions into the workspace, then rt_hip_bake_probe_depth at them;
+ *     rt_hip_probe_grid_depth_workspace_bytes = the bake's own plus the positions (24 bytes a probe, after the bake's part).
+ *
+ * THE SHADE (rt_hip_probe_shade_vis): rt_hip_probe_shade's arguments, classes and steps 1 .. 7, with step 3 extended.  A corner whose
+ * weight so far -- tri, times face with RT_HIP_GRID_FACING -- is == 0.0 is skipped as before, and its moments are not read either.
+ * Otherwise, with C the corner's position (the grid's formula):
+ *   p' = p + n*bias per component (the product rounded before the add); v = p' - C; q = (v.x*v.x + v.y*v.y) + v.z*v.z; r = sqrt(q).
+ *   q > 0.0: (mean, mean2) = the lookup of probe i_c's map at v.  If r > mean: var = |mean*mean - mean2|; d = r - mean;
+ *     ch = var / (var + d*d); ch = (ch*ch)*ch; vis_w = ch > floor ? ch : floor (a NaN ch, from 0/0, gives floor).  Otherwise
+ *     vis_w = 1.0.  Then, if mean or mean2 is NaN, vis_w = a quiet NaN: an invalid probe poisons exactly the entries it would light.
+ *   q == 0.0 (or NaN): vis_w = 1.0, and the moments are not read.
+ *   w_c = w_c * vis_w.
+ * Steps 4 to 7 follow with that w_c.  The function stays TOTAL: any bytes in d_moments give a defined result and no index leaves the
+ * maps; for moments that are not NaN vis_w lies in [floor, 1], so that the weight sum of a VALID entry is never 0 where it was not
+ * before.  With every mean >= every r it is rt_hip_probe_shade bit for bit (w_c * 1.0 = w_c).  The kernel reads the coefficients
+ * through wave-uniform loads where a wave's valid entries share a cell, as k_probe_shade does, and the moments per lane: the same
+ * operations in the same order in both arms, the same bits.
+ *
+ * THE PREVIEW.  rt_hip_probe_preview_vis is rt_hip_probe_preview with rt_hip_probe_shade_vis in the shade's place (the same
+ * workspace: rt_hip_probe_preview_workspace_bytes); rt_hip_probe_preview_vis_image and _vis_scene_image are the host forms: they bake
+ * the grid's coefficients (rt_hip_bake_probe_grid) and its moments (rt_hip_bake_probe_grid_depth) under probe_params, run the preview
+ * and read back; h_moments (may be NULL) gets the moments.  Each is bit for bit the composition of the public calls.
+ * Refusals, each before the first launch and with the outputs untouched, arguments before a device is looked for.  RT_HIP_EINVAL: a
+ * NULL vis or a struct_size below the struct's; flags or reserved not 0; res outside 2 .. 32; sharp above 8; d_max not finite or not
+ * > 0; bias not finite or negative; floor not finite or outside (0, 1]; n_probes * res * res > 2^28; a mode that is not
+ * RT_HIP_PROBE_SPHERE; slice_rays == 0; a d_workspace that is not 16-byte aligned; a NULL required pointer; what rt_hip_bake_probes,
+ * rt_hip_query_rays, rt_hip_probe_shade and rt_hip_probe_preview refuse.  n_probes == 0 or m == 0 with good arguments is RT_HIP_OK
+ * and launches nothing. */
+typedef struct
+{
+  uint32_t struct_size; /* set by rt_hip_probe_vis_defaults */
+  uint32_t flags;       /* must be 0 */
+  uint32_t res;         /* R: the map has R x R texels, 2 .. 32 */
+  uint32_t sharp;       /* 0 .. 8: a ray weighs c^(2^sharp) in a texel */
+  double d_max;         /* finite, > 0: distances are clamped to it, a miss counts as it */
+  double bias;          /* finite, >= 0: the shaded point is moved along its normal by it */
+  double floor;         /* finite, in (0, 1]: the least visibility weight */
+  uint64_t reserved;    /* must be 0 */
+} RtHipProbeVis;
+void rt_hip_probe_vis_defaults(RtHipProbeVis *vis, const RtHipProbeGrid *grid);
+size_t rt_hip_probe_depth_workspace_bytes(uint64_t n_probes, uint32_t res, uint32_t slice_rays);
+int rt_hip_bake_probe_depth(const RtHipScene *scene, const double *d_positions, uint64_t n_probes, const RtHipProbeVis *vis,
+                            const RtHipProbeParams *probe_params, uint32_t slice_rays, void *d_workspace, double *d_moments,
+                            uint32_t *d_status, void *stream);
+size_t rt_hip_probe_grid_depth_workspace_bytes(const RtHipProbeGrid *grid, uint32_t res, uint32_t slice_rays);
+int rt_hip_bake_probe_grid_depth(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                                 const RtHipProbeParams *probe_params, uint32_t slice_rays, void *d_workspace, double *d_moments,
+                                 uint32_t *d_status, void *stream);
+int rt_hip_probe_shade_vis(const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const double *d_coeff, const double *d_moments,
+                           const double *d_points, const double *d_normals, const uint32_t *d_status, const float *d_albedo,
+                           const float *d_add, uint64_t m, double *d_irradiance, float *d_color, void *stream);
+int rt_hip_probe_preview_vis(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                             const double *d_coeff, const double *d_moments, int32_t width, int32_t height, int32_t aov_samples,
+                             uint64_t seed, void *d_workspace, float *d_rgb, uint8_t *d_rgb8, void *stream);
+int rt_hip_probe_preview_vis_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                                   const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                                   const RtHipProbeParams *probe_params, int32_t width, int32_t height, int32_t aov_samples, int device,
+                                   float *h_rgb, uint8_t *h_rgb8, double *h_coeff, double *h_moments, uint64_t *h_stats);
+int rt_hip_probe_preview_vis_scene_image(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid,
+                                         const RtHipProbeVis *vis, const RtHipProbeParams *probe_params, int32_t width, int32_t height,
+                                         int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8, double *h_coeff, double *h_moments,
+                                         uint64_t *h_stats);
+
 /* ---- edge-avoiding a-trous denoiser guided by the first-hit buffers ---------------------------------------------------------
  * Inputs: row-major images of w x h pixels (1 <= w, h <= 2^20, w*h < 2^32) on one device -- colour c (3 floats per pixel: the
  * linear mean of rt_hip_render_tiles or rt_hip_accum_resolve after rt_hip_untile) and the RtHipAov buffers of the same frame

@@ -13,6 +13,10 @@
  *                       coefficients in registers, the irradiance and the colour (rt_hip.h, "probe grids", operation for operation).
  *                       A wave whose valid lanes share a cell reads the coefficients through wave-uniform loads.
  *   k_probe_pixel_centres, k_probe_emission, k_probe_tonemap  what rt_hip_probe_preview puts around the shade.
+ *   k_probe_depth_fold  one thread a (probe of the slice, texel of its octahedral map): the weight and the two depth moments of the
+ *                       probe's rays in the slice, in ascending k, from a ray query's status words and t (rt_hip.h, "probe visibility").
+ *   k_probe_depth_resolve  one thread a (probe, texel): the mean depth and the mean squared depth.
+ *   k_probe_shade_vis   k_probe_shade with a Chebyshev visibility weight a corner, looked up per lane in the probe's map.
  * The constants are pt_device.h's.  fp64, unfused (-ffp-contract=off, as every source of the shim), IEEE division and sqrt.  256
  * threads a workgroup, no scratch, no LDS; no kernel waits for another workgroup. */
 #include <hip/hip_runtime.h>
@@ -336,6 +340,254 @@ __global__ void __launch_bounds__(PROBE_BLOCK) k_probe_tonemap(const float *__re
     rgb8[t] = tonemap((double)rgb[t]);
 }
 
+/* ---- probe visibility (rt_hip.h, "probe visibility") ---- */
+
+__device__ __forceinline__ double oct_sgn(double v) { return v >= 0.0 ? 1.0 : -1.0; }
+
+/* the centre direction of texel (tx, ty) of an R x R octahedral map */
+__device__ __forceinline__ V3 oct_texel_dir(uint32_t R, uint32_t tx, uint32_t ty)
+{
+  const double a = (((double)tx + 0.5) / (double)R) * 2.0 - 1.0, b = (((double)ty + 0.5) / (double)R) * 2.0 - 1.0;
+  const double z = (1.0 - fabs(a)) - fabs(b);
+  double x = a, y = b;
+  if (z < 0.0)
+  {
+    x = (1.0 - fabs(b)) * oct_sgn(a);
+    y = (1.0 - fabs(a)) * oct_sgn(b);
+  }
+  const V3 v = {x, y, z};
+  return v_scale(v, 1.0 / sqrt((x * x + y * y) + z * z));
+}
+
+/* One thread a (probe of the slice, texel): W, M1 and M2 over the probe's rays in the slice, in ascending k.  A sum has one writer,
+ * which loads it and stores it: the slices leave no trace in its bits. */
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_depth_fold(const PtProbeDepthFold A)
+{
+  const uint32_t R = A.vis.res, texels = R * R;
+  const uint64_t t = (uint64_t)blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (t >= A.n_probes * texels)
+    return;
+  const uint64_t probe = A.probe_first + t / texels;
+  const uint32_t texel = (uint32_t)(t % texels), ty = texel / R, tx = texel - R * ty;
+  const V3 e = oct_texel_dir(R, tx, ty);
+  const uint64_t lo = max(A.k_first, probe * A.samples), hi = min(A.k_first + A.n, (probe + 1u) * A.samples);
+  double *const s = A.sum + (probe * texels + texel) * 3u;
+  double W = s[0], M1 = s[1], M2 = s[2];
+  bool invalid = false;
+  for (uint64_t i = lo - A.k_first; i < hi - A.k_first; i++)
+  {
+    const double x = A.rays[6u * i + 3u], y = A.rays[6u * i + 4u], z = A.rays[6u * i + 5u];
+    double c = (x * e.x + y * e.y) + z * e.z;
+    c = c > 0.0 ? c : 0.0;
+    double w = c;
+    for (uint32_t k = 0; k < A.vis.sharp; k++)
+      w = w * w;
+    const uint32_t st = A.status[i];
+    const double hit = A.t[i];
+    const double dist = st == 1u ? (hit < A.vis.d_max ? hit : A.vis.d_max) : A.vis.d_max;
+    W = W + w;
+    M1 = M1 + w * dist;
+    M2 = M2 + w * (dist * dist);
+    invalid |= st == 2u;
+  }
+  if (invalid)
+  {
+    W = M1 = M2 = quiet_nan();
+    if (A.probe_status && texel == 0u)
+      A.probe_status[probe] = 2u;
+  }
+  s[0] = W;
+  s[1] = M1;
+  s[2] = M2;
+}
+
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_depth_resolve(const double *__restrict__ sum, uint64_t n_texels, double d_max,
+                                                                      double *__restrict__ moments)
+{
+  const uint64_t t = (uint64_t)blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (t >= n_texels)
+    return;
+  const double W = sum[3u * t], M1 = sum[3u * t + 1u], M2 = sum[3u * t + 2u];
+  /* (a NaN W is the probe's invalid mark: it must reach the moments, and NaN > 0 would hide it) */
+  const bool nan = W != W;
+  moments[2u * t] = nan ? W : (W > 0.0 ? M1 / W : d_max);
+  moments[2u * t + 1u] = nan ? W : (W > 0.0 ? M2 / W : d_max * d_max);
+}
+
+/* a texel index pair continued across the map's edge: first i, then j */
+__device__ __forceinline__ uint32_t oct_texel(int R, int i, int j)
+{
+  if (i < 0 || i > R - 1)
+  {
+    i = i < 0 ? 0 : R - 1;
+    j = R - 1 - j;
+  }
+  if (j < 0 || j > R - 1)
+  {
+    j = j < 0 ? 0 : R - 1;
+    i = R - 1 - i;
+  }
+  return (uint32_t)(i + R * j);
+}
+
+/* one axis of the sample position: the lower texel (-1 .. R - 1) and the fraction; a NaN reads from -0.5 (the function is total) */
+__device__ __forceinline__ int oct_axis(int R, double a, double &f)
+{
+  double u = (a * 0.5 + 0.5) * (double)R - 0.5;
+  u = u >= -0.5 ? u : -0.5;
+  const double top = (double)R - 0.5;
+  u = u <= top ? u : top;
+  const double fl = floor(u);
+  f = u - fl;
+  return (int)fl;
+}
+
+/* the bilinear lookup of a probe's (mean, mean2) at the direction v, |v| > 0 */
+__device__ __forceinline__ void oct_lookup(const double *__restrict__ map, uint32_t res, V3 v, double &mean, double &mean2)
+{
+  const int R = (int)res;
+  const double s = (fabs(v.x) + fabs(v.y)) + fabs(v.z);
+  double a = v.x / s, b = v.y / s;
+  if (v.z < 0.0)
+  {
+    const double fa = (1.0 - fabs(b)) * oct_sgn(a), fb = (1.0 - fabs(a)) * oct_sgn(b);
+    a = fa;
+    b = fb;
+  }
+  double fx, fy;
+  const int i0 = oct_axis(R, a, fx), j0 = oct_axis(R, b, fy);
+  const double gx = 1.0 - fx, gy = 1.0 - fy;
+  const double w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
+  const double *const m00 = map + 2u * oct_texel(R, i0, j0), *const m10 = map + 2u * oct_texel(R, i0 + 1, j0),
+                     *const m01 = map + 2u * oct_texel(R, i0, j0 + 1), *const m11 = map + 2u * oct_texel(R, i0 + 1, j0 + 1);
+  mean = ((w00 * m00[0] + w10 * m10[0]) + w01 * m01[0]) + w11 * m11[0];
+  mean2 = ((w00 * m00[1] + w10 * m10[1]) + w01 * m01[1]) + w11 * m11[1];
+}
+
+/* shade_blend's text with the visibility weight in step 3: a copy, so that k_probe_shade's code does not move.  The cell comes as
+ * lanes' registers or as the wave's scalars (the coefficient loads are then wave-uniform); the moment lookups are per lane in both. */
+__device__ __forceinline__ void shade_blend_vis(const PtProbeShadeVis &A, uint32_t x0, uint32_t y0, uint32_t z0, const double (&wx)[2],
+                                                const double (&wy)[2], const double (&wz)[2], V3 p, V3 n, bool valid, double (&B)[27],
+                                                double &W)
+{
+  const PtGrid &G = A.shade.grid;
+  const PtProbeVis &S = A.vis;
+  const uint32_t x1 = G.count[0] >= 2u ? x0 + 1u : 0u, y1 = G.count[1] >= 2u ? y0 + 1u : 0u, z1 = G.count[2] >= 2u ? z0 + 1u : 0u;
+  const V3 pb = {p.x + n.x * S.bias, p.y + n.y * S.bias, p.z + n.z * S.bias};
+#pragma unroll
+  for (uint32_t c = 0; c < 8u; c++)
+  {
+    const uint32_t bx = c & 1u, by = (c >> 1) & 1u, bz = c >> 2;
+    const uint32_t ix = bx ? x1 : x0, iy = by ? y1 : y0, iz = bz ? z1 : z0;
+    const V3 corner = {grid_at(G, 0, ix), grid_at(G, 1, iy), grid_at(G, 2, iz)};
+    double w = (wx[bx] * wy[by]) * wz[bz];
+    if (G.flags & PT_GRID_FACING)
+    {
+      const V3 v = {corner.x - p.x, corner.y - p.y, corner.z - p.z};
+      const double q = (v.x * v.x + v.y * v.y) + v.z * v.z;
+      const double cs = q > 0.0 ? ((v.x * n.x + v.y * n.y) + v.z * n.z) * (1.0 / sqrt(q)) : 1.0;
+      const double s = (cs + 1.0) * 0.5;
+      w = w * (s * s + PT_GRID_FACE_FLOOR);
+    }
+    if (valid && w != 0.0) /* (a NaN weight does not skip) */
+    {
+      const size_t probe = (size_t)((iz * G.count[1] + iy) * G.count[0] + ix);
+      const V3 v = {pb.x - corner.x, pb.y - corner.y, pb.z - corner.z};
+      const double q = (v.x * v.x + v.y * v.y) + v.z * v.z;
+      const double r = sqrt(q);
+      double vis_w = 1.0;
+      if (q > 0.0)
+      {
+        double mean, mean2;
+        oct_lookup(A.moments + probe * (2u * S.res * S.res), S.res, v, mean, mean2);
+        if (r > mean)
+        {
+          const double var = fabs(mean * mean - mean2), d = r - mean;
+          double ch = var / (var + d * d);
+          ch = (ch * ch) * ch;
+          vis_w = ch > S.floor ? ch : S.floor;
+        }
+        if (mean != mean || mean2 != mean2)
+          vis_w = quiet_nan();
+      }
+      w = w * vis_w;
+      const double *__restrict__ const a = A.shade.coeff + probe * (3u * PT_PROBE_SH);
+#pragma unroll
+      for (uint32_t k = 0; k < 27u; k++)
+        B[k] = B[k] + (w * a[k]);
+      W = W + w;
+    }
+  }
+}
+
+/* k_probe_shade's text around shade_blend_vis */
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_shade_vis(const PtProbeShadeVis V)
+{
+  const PtProbeShade &A = V.shade;
+  const uint32_t t = blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  const bool stores = t < A.m;
+  const size_t e = stores ? t : A.m - 1u;
+  const V3 p = ld3(A.points + 3u * e), n = ld3(A.normals + 3u * e);
+  const bool miss = A.status && A.status[e] != 1u;
+  const bool finite = ((p.x - p.x) + (p.y - p.y)) + (p.z - p.z) == 0.0 && ((n.x - n.x) + (n.y - n.y)) + (n.z - n.z) == 0.0;
+  const bool valid = !miss && finite;
+
+  double fx, fy, fz;
+  const uint32_t x0 = grid_cell(A.grid, 0, p.x, fx), y0 = grid_cell(A.grid, 1, p.y, fy), z0 = grid_cell(A.grid, 2, p.z, fz);
+  const double wx[2] = {1.0 - fx, fx}, wy[2] = {1.0 - fy, fy}, wz[2] = {1.0 - fz, fz};
+
+  double B[27], W = 0.0;
+#pragma unroll
+  for (uint32_t k = 0; k < 27u; k++)
+    B[k] = 0.0;
+  const unsigned long long voters = __ballot(valid);
+  if (voters != 0ull)
+  {
+    const int first = __builtin_ctzll(voters);
+    const uint32_t ux = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane((int)x0, first)),
+                   uy = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane((int)y0, first)),
+                   uz = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane((int)z0, first));
+    if (__all(!valid || (x0 == ux && y0 == uy && z0 == uz)))
+      shade_blend_vis(V, ux, uy, uz, wx, wy, wz, p, n, valid, B, W);
+    else
+      shade_blend_vis(V, x0, y0, z0, wx, wy, wz, p, n, valid, B, W);
+  }
+
+  double E[3];
+#pragma unroll
+  for (uint32_t ch = 0; ch < 3u; ch++)
+  {
+    double s = 0.0;
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)PT_PROBE_SH; j++)
+    {
+      const double band = j == 0u ? PT_PROBE_A0 : (j < 4u ? PT_PROBE_A1 : PT_PROBE_A2);
+      s = s + (band * B[3u * j + ch]) * sh_basis(j, n.x, n.y, n.z);
+    }
+    s = s / W;
+    E[ch] = s < 0.0 ? 0.0 : s;
+  }
+  if (!stores)
+    return;
+  if (A.irradiance)
+  {
+#pragma unroll
+    for (uint32_t ch = 0; ch < 3u; ch++)
+      A.irradiance[3u * e + ch] = miss ? 0.0 : (valid ? E[ch] : quiet_nan());
+  }
+  if (A.color)
+  {
+#pragma unroll
+    for (uint32_t ch = 0; ch < 3u; ch++)
+    {
+      const double add = A.add ? (double)A.add[3u * e + ch] : 0.0;
+      const double albedo = (double)(A.albedo ? A.albedo[3u * e + ch] : 1.0f);
+      const double lit = ((albedo * E[ch]) * PT_GRID_INV_PI) + add;
+      A.color[3u * e + ch] = miss ? (float)((double)A.grid.miss_color[ch] + add) : (valid ? (float)lit : (float)quiet_nan());
+    }
+  }
+}
+
 uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + PROBE_BLOCK - 1u) / PROBE_BLOCK); }
 
 } // namespace
@@ -378,6 +630,25 @@ hipError_t probe_launch_grid_positions(const PtGrid &grid, double *positions, hi
 hipError_t probe_launch_shade(const PtProbeShade &args, hipStream_t stream)
 {
   hipLaunchKernelGGL(k_probe_shade, dim3(blocks_for(args.m)), dim3(PROBE_BLOCK), 0, stream, args);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_depth_fold(const PtProbeDepthFold &args, hipStream_t stream)
+{
+  const uint64_t threads = args.n_probes * args.vis.res * args.vis.res;
+  hipLaunchKernelGGL(k_probe_depth_fold, dim3(blocks_for(threads)), dim3(PROBE_BLOCK), 0, stream, args);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_depth_resolve(const double *sum, uint64_t n_texels, double d_max, double *moments, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_probe_depth_resolve, dim3(blocks_for(n_texels)), dim3(PROBE_BLOCK), 0, stream, sum, n_texels, d_max, moments);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_shade_vis(const PtProbeShadeVis &args, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_probe_shade_vis, dim3(blocks_for(args.shade.m)), dim3(PROBE_BLOCK), 0, stream, args);
   return hipGetLastError();
 }
 

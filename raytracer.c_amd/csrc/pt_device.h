@@ -872,5 +872,48 @@ hipError_t probe_launch_tonemap(const float *rgb, uint64_t n_values, uint8_t *rg
 hipError_t probe_launch_pixel_centres(uint32_t width, uint32_t height, double *uv, hipStream_t stream);
 #endif
 
+/* ---- probe visibility (rt_hip.h, "probe visibility"; the kernels are probe.hip's) ---- */
+#define PT_VIS_RES_MIN 2u
+#define PT_VIS_RES_MAX 32u
+#define PT_VIS_SHARP_MAX 8u
+
+/* A checked RtHipProbeVis as the kernels take it */
+struct PtProbeVis
+{
+  double d_max, bias, floor;
+  uint32_t res, sharp;
+};
+
+/* One slice's depth fold: the slice holds the rays [k_first, k_first + n) -- their 6 doubles, the query's status words and t --, and
+ * touches the probes probe_first .. probe_first + n_probes - 1; sum holds res x res x 3 doubles a probe: (W, M1, M2) a texel. */
+struct PtProbeDepthFold
+{
+  const double *rays, *t;
+  const uint32_t *status;
+  double *sum;
+  uint32_t *probe_status; /* may be null */
+  uint64_t k_first, probe_first, n_probes;
+  uint32_t n, samples;
+  PtProbeVis vis;
+};
+
+/* the shade's arguments and the moments: n x res x res x 2 doubles (mean, mean2) */
+struct PtProbeShadeVis
+{
+  PtProbeShade shade;
+  PtProbeVis vis;
+  const double *moments;
+};
+
+#if defined(__HIPCC__)
+/* n >= 1: (W, M1, M2) of each (probe, texel) over the slice's rays of the probe in ascending k, a thread a (probe, texel); a ray of
+ * status 2 makes its probe's sums NaN and its probe_status 2 */
+hipError_t probe_launch_depth_fold(const PtProbeDepthFold &args, hipStream_t stream);
+/* moments[2 i] = W > 0 ? M1 / W : d_max, moments[2 i + 1] = W > 0 ? M2 / W : d_max * d_max for n_texels (probe, texel) pairs */
+hipError_t probe_launch_depth_resolve(const double *sum, uint64_t n_texels, double d_max, double *moments, hipStream_t stream);
+/* m >= 1: rt_hip.h's probe shade with the visibility weight, a thread an entry */
+hipError_t probe_launch_shade_vis(const PtProbeShadeVis &args, hipStream_t stream);
+#endif
+
 
 #endif /* PT_DEVICE_H */

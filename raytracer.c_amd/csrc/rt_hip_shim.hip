@@ -3905,8 +3905,14 @@ int check_preview(const RtHipCamera *camera, const RtHipProbeGrid *grid, int32_t
 }
 
 /* The preview on `stream`, no host wait: each step is the call the header names. */
+int shade_vis_launch(const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const double *d_coeff, const double *d_moments, const double *d_points,
+                     const double *d_normals, const uint32_t *d_status, const float *d_albedo, const float *d_add, uint64_t m, double *d_irradiance,
+                     float *d_color, hipStream_t stream);
+
+/* (vis: rt_hip_probe_preview_vis' shade, with d_moments; null: rt_hip_probe_preview's) */
 int probe_preview_launch(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid, const double *d_coeff, int32_t width,
-                         int32_t height, int32_t aov_samples, uint64_t seed, void *d_workspace, float *d_rgb, uint8_t *d_rgb8, hipStream_t stream)
+                         int32_t height, int32_t aov_samples, uint64_t seed, void *d_workspace, float *d_rgb, uint8_t *d_rgb8, hipStream_t stream,
+                         const RtHipProbeVis *vis = nullptr, const double *d_moments = nullptr)
 {
   const uint64_t n = (uint64_t)width * (uint64_t)height;
   const PreviewWorkspace W(n, frame_tile_pixels(width, height));
@@ -3951,7 +3957,9 @@ int probe_preview_launch(const RtHipScene *scene, const RtHipCamera *camera, con
   if (const int rc = launched(probe_launch_emission(hits.object, n, scene->view.material + PT_MAT_EMISSION, PT_MAT_STRIDE, scene->view.n_spheres + scene->view.n_meshes,
                                                     add, stream), "k_probe_emission"))
     return rc;
-  if (const int rc = shade_launch(grid, d_coeff, hits.point, hits.normal, hits.status, image.albedo, add, n, nullptr, d_rgb, stream))
+  if (const int rc = vis ? shade_vis_launch(grid, vis, d_coeff, d_moments, hits.point, hits.normal, hits.status, image.albedo, add, n, nullptr,
+                                            d_rgb, stream)
+                         : shade_launch(grid, d_coeff, hits.point, hits.normal, hits.status, image.albedo, add, n, nullptr, d_rgb, stream))
     return rc;
   return d_rgb8 ? launched(probe_launch_tonemap(d_rgb, 3u * n, d_rgb8, stream), "k_probe_tonemap") : (int)RT_HIP_OK;
 }
@@ -4018,6 +4026,228 @@ int probe_preview_scene_image_impl(const RtHipScene *scene, const RtHipCamera *c
   DeviceScope scope(scene->device);
   HIP_TRY(scope.status);
   return preview_image_of(scene, scene->device, camera, grid, params, width, height, aov_samples, h_rgb, h_rgb8, h_coeff, h_stats);
+}
+
+/* ---- probe visibility (rt_hip.h, rt_hip_probe_vis_* / rt_hip_bake_probe_depth / rt_hip_probe_shade_vis / _preview_vis*) -----------
+ * The depth bake is a generated-ray job whose middle is the ray query's launch instead of the radiance query's: a sibling of
+ * sliced_trace with a workspace of its own, so that the lens and the radiance bake keep theirs.  The checks need no device. */
+constexpr uint64_t VIS_TEXELS_MAX = 1ull << 28;
+
+/* what every visibility call refuses in its vis without a device; n_probes: the probes whose maps the call holds */
+int check_vis(const RtHipProbeVis *v, uint64_t n_probes)
+{
+  if (!v)
+    return fail(RT_HIP_EINVAL, "vis is required");
+  if (v->struct_size < sizeof(RtHipProbeVis))
+    return fail(RT_HIP_EINVAL, "vis->struct_size = %u is below the %zu of RtHipProbeVis: start from rt_hip_probe_vis_defaults", v->struct_size,
+                sizeof(RtHipProbeVis));
+  if (v->flags != 0u || v->reserved != 0u)
+    return fail(RT_HIP_EINVAL, "vis flags and reserved must be 0");
+  if (v->res < PT_VIS_RES_MIN || v->res > PT_VIS_RES_MAX)
+    return fail(RT_HIP_EINVAL, "vis->res = %u must be in [%u, %u]", v->res, PT_VIS_RES_MIN, PT_VIS_RES_MAX);
+  if (v->sharp > PT_VIS_SHARP_MAX)
+    return fail(RT_HIP_EINVAL, "vis->sharp = %u must be at most %u", v->sharp, PT_VIS_SHARP_MAX);
+  if (!(v->d_max > 0) || !std::isfinite(v->d_max))
+    return fail(RT_HIP_EINVAL, "vis->d_max %g must be finite and > 0", v->d_max);
+  if (!(v->bias >= 0) || !std::isfinite(v->bias))
+    return fail(RT_HIP_EINVAL, "vis->bias %g must be finite and >= 0", v->bias);
+  if (!(v->floor > 0) || !(v->floor <= 1))
+    return fail(RT_HIP_EINVAL, "vis->floor %g must be in (0, 1]", v->floor);
+  if (n_probes > VIS_TEXELS_MAX || n_probes * v->res * v->res > VIS_TEXELS_MAX)
+    return fail(RT_HIP_EINVAL, "%llu probes x %u x %u texels exceed 2^28", (unsigned long long)n_probes, v->res, v->res);
+  return RT_HIP_OK;
+}
+
+PtProbeVis vis_args(const RtHipProbeVis *v)
+{
+  PtProbeVis V;
+  memset(&V, 0, sizeof V);
+  V.d_max = v->d_max;
+  V.bias = v->bias;
+  V.floor = v->floor;
+  V.res = v->res;
+  V.sharp = v->sharp;
+  return V;
+}
+
+/* a depth bake's workspace: a slice's rays, status words and distances, then the sums, three doubles a texel and probe */
+struct DepthWorkspace
+{
+  size_t rays, status, t, sum, total;
+  DepthWorkspace(uint64_t slice, uint64_t n_probes, uint32_t res)
+  {
+    rays = 0;
+    status = rays + stage_align(48u * slice);
+    t = status + stage_align(4u * slice);
+    sum = t + stage_align(8u * slice);
+    total = sum + stage_align(24u * n_probes * res * res);
+  }
+};
+
+/* what rt_hip_bake_probe_depth refuses without a device, but for its pointers */
+int check_depth_bake(const RtHipProbeVis *vis, const RtHipProbeParams *params, uint64_t n_probes, uint32_t slice_rays, const void *d_workspace)
+{
+  if (const int rc = check_probe(params, n_probes, false))
+    return rc;
+  if (params->mode != RT_HIP_PROBE_SPHERE)
+    return fail(RT_HIP_EINVAL, "depth moments are baked in RT_HIP_PROBE_SPHERE mode: a map covers every direction");
+  if (const int rc = check_vis(vis, n_probes))
+    return rc;
+  if (slice_rays == 0u)
+    return fail(RT_HIP_EINVAL, "slice_rays must be >= 1");
+  return check_slice_buffers(d_workspace, nullptr);
+}
+
+/* The depth bake on `stream`, no host wait: the query's own refusal (near_R) asked for once, up front; then the sums cleared, the
+ * status words marked, and per slice the probe rays, query_launch for status and t, the fold; then the resolve.  n_probes >= 1. */
+int bake_probe_depth_launch(const RtHipScene *scene, const double *d_positions, uint64_t n_probes, const RtHipProbeVis *vis,
+                            const RtHipProbeParams *p, uint32_t slice_rays, void *d_workspace, double *d_moments, uint32_t *d_status,
+                            hipStream_t stream)
+{
+  const uint64_t S = (uint64_t)p->samples, total = n_probes * S, slice = std::min<uint64_t>(slice_rays, total);
+  const uint64_t texels = n_probes * vis->res * vis->res;
+  RtHipQueryParams Q;
+  rt_hip_query_defaults(&Q);
+  Q.origin_radius = p->origin_radius;
+  {
+    PtLaunch dry;
+    if (const int rc = ray_launch_prepare(scene, Q.source, nullptr, Q.origin_radius, dry))
+      return rc;
+  }
+  const DepthWorkspace W(slice, n_probes, vis->res);
+  char *const ws = static_cast<char *>(d_workspace);
+  double *const rays = reinterpret_cast<double *>(ws + W.rays), *const sum = reinterpret_cast<double *>(ws + W.sum);
+  const RtHipHits hits = {reinterpret_cast<uint32_t *>(ws + W.status), reinterpret_cast<double *>(ws + W.t), nullptr, nullptr, nullptr, nullptr,
+                          nullptr, nullptr};
+  PtProbeRays A = probe_args(d_positions, nullptr, p);
+  A.rays = rays;
+  PtProbeDepthFold F;
+  memset(&F, 0, sizeof F);
+  F.rays = rays;
+  F.t = hits.t;
+  F.status = hits.status;
+  F.sum = sum;
+  F.probe_status = d_status;
+  F.samples = A.samples;
+  F.vis = vis_args(vis);
+  {
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    HIP_TRY(hipMemsetAsync(sum, 0, 24u * texels, stream));
+    if (d_status)
+      HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status), 1, n_probes, stream));
+  }
+  for (uint64_t first = 0, n; first < total; first += n)
+  {
+    n = std::min<uint64_t>(slice, total - first);
+    {
+      DeviceScope scope(scene->device);
+      HIP_TRY(scope.status);
+      A.k_first = first;
+      A.n = (uint32_t)n;
+      if (const int rc = launched(probe_launch_rays(A, stream), "k_probe_rays"))
+        return rc;
+    }
+    if (const int rc = query_launch(scene, rays, nullptr, n, &Q, &hits, stream))
+      return rc;
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    F.k_first = first;
+    F.n = (uint32_t)n;
+    F.probe_first = first / S;
+    F.n_probes = (first + n - 1u) / S - F.probe_first + 1u;
+    if (const int rc = launched(probe_launch_depth_fold(F, stream), "k_probe_depth_fold"))
+      return rc;
+  }
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  return launched(probe_launch_depth_resolve(sum, texels, vis->d_max, d_moments, stream), "k_probe_depth_resolve");
+}
+
+/* a grid depth bake's workspace: the bake's own, then the positions */
+size_t grid_depth_positions_at(uint64_t n_probes, uint32_t res, uint64_t slice_rays) { return DepthWorkspace(slice_rays, n_probes, res).total; }
+
+int check_grid_depth_bake(const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeParams *params, uint32_t slice_rays,
+                          const void *d_workspace)
+{
+  if (const int rc = check_grid(grid))
+    return rc;
+  return check_depth_bake(vis, params, grid_probes(grid), slice_rays, d_workspace);
+}
+
+/* the two calls in sequence, on the scene's device */
+int bake_probe_grid_depth_launch(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeParams *p,
+                                 uint32_t slice_rays, void *d_workspace, double *d_moments, uint32_t *d_status, hipStream_t stream)
+{
+  const uint64_t n = grid_probes(grid), total = n * (uint64_t)p->samples;
+  double *const positions =
+      reinterpret_cast<double *>(static_cast<char *>(d_workspace) + grid_depth_positions_at(n, vis->res, std::min<uint64_t>(slice_rays, total)));
+  {
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    if (const int rc = launched(probe_launch_grid_positions(grid_args(grid), positions, stream), "k_probe_grid_positions"))
+      return rc;
+  }
+  return bake_probe_depth_launch(scene, positions, n, vis, p, slice_rays, d_workspace, d_moments, d_status, stream);
+}
+
+int shade_vis_launch(const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const double *d_coeff, const double *d_moments, const double *d_points,
+                     const double *d_normals, const uint32_t *d_status, const float *d_albedo, const float *d_add, uint64_t m, double *d_irradiance,
+                     float *d_color, hipStream_t stream)
+{
+  PtProbeShadeVis A;
+  memset(&A, 0, sizeof A);
+  A.shade.grid = grid_args(grid);
+  A.shade.coeff = d_coeff;
+  A.shade.points = d_points;
+  A.shade.normals = d_normals;
+  A.shade.status = d_status;
+  A.shade.albedo = d_albedo;
+  A.shade.add = d_add;
+  A.shade.irradiance = d_irradiance;
+  A.shade.color = d_color;
+  A.shade.m = (uint32_t)m;
+  A.vis = vis_args(vis);
+  A.moments = d_moments;
+  return launched(probe_launch_shade_vis(A, stream), "k_probe_shade_vis");
+}
+
+/* what the _vis preview's host forms refuse without a device */
+int check_preview_vis_image(const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeParams *params,
+                            int32_t width, int32_t height, int32_t aov_samples, const void *h_rgb, const void *h_rgb8)
+{
+  if (const int rc = check_preview_image(camera, grid, params, width, height, aov_samples, h_rgb, h_rgb8))
+    return rc;
+  return check_vis(vis, grid_probes(grid));
+}
+
+/* preview_image_of with the moments baked after the coefficients and the _vis preview */
+int preview_vis_image_of(const RtHipScene *scene, int phys, const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                         const RtHipProbeParams *params, int32_t width, int32_t height, int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8,
+                         double *h_coeff, double *h_moments, uint64_t *h_stats)
+{
+  const uint64_t n_probes = grid_probes(grid), total = n_probes * (uint64_t)params->samples, n = (uint64_t)width * (uint64_t)height;
+  const uint64_t slice = std::min<uint64_t>(HOST_SLICE, total);
+  StageArena A;
+  const int bake_ws = A.part(grid_bake_positions_at(n_probes, slice) + stage_align(24u * n_probes));
+  const int depth_ws = A.part(grid_depth_positions_at(n_probes, vis->res, slice) + stage_align(24u * n_probes));
+  const int ws = A.part(PreviewWorkspace(n, frame_tile_pixels(width, height)).total);
+  const int coeff = A.part(24u * PT_PROBE_SH * n_probes, nullptr, h_coeff);
+  const int moments = A.part(16u * n_probes * vis->res * vis->res, nullptr, h_moments);
+  const int rgb = A.part(12u * n, nullptr, h_rgb);
+  const int rgb8 = A.part(3u * n, nullptr, h_rgb8, h_rgb8 != nullptr);
+  const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
+  int rc = A.stage();
+  if (rc)
+    return rc;
+  rc = bake_probe_grid_launch(scene, grid, params, HOST_SLICE, A.at<char>(bake_ws), A.at<double>(coeff), nullptr, nullptr, A.at<uint64_t>(stats),
+                              nullptr);
+  if (!rc)
+    rc = bake_probe_grid_depth_launch(scene, grid, vis, params, HOST_SLICE, A.at<char>(depth_ws), A.at<double>(moments), nullptr, nullptr);
+  if (!rc)
+    rc = probe_preview_launch(scene, camera, grid, A.at<double>(coeff), width, height, aov_samples, params->seed, A.at<char>(ws),
+                              A.at<float>(rgb), A.at<uint8_t>(rgb8), nullptr, vis, A.at<double>(moments));
+  return rc ? rc : download_then_status(A, phys);
 }
 
 /* ---- pixel refinement (rt_hip.h, rt_hip_select_pixels / _trace_pixels / _blend_pixels) ---------------------------------------
@@ -5909,6 +6139,134 @@ int rt_hip_probe_preview_image(const RtHipSphere *spheres, size_t n_spheres, con
   return guarded("rt_hip_probe_preview_image", [&] {
     return probe_preview_image_impl(spheres, n_spheres, meshes, n_meshes, camera, grid, probe_params, width, height, aov_samples, device, h_rgb,
                                     h_rgb8, h_coeff, h_stats);
+  });
+}
+
+void rt_hip_probe_vis_defaults(RtHipProbeVis *vis, const RtHipProbeGrid *grid)
+{
+  if (!vis)
+    return;
+  memset(vis, 0, sizeof *vis);
+  vis->struct_size = (uint32_t)sizeof *vis;
+  vis->res = 8u;
+  vis->sharp = 5u;
+  const double sx = grid ? grid->step[0] : 1.0, sy = grid ? grid->step[1] : 1.0, sz = grid ? grid->step[2] : 1.0;
+  vis->d_max = 1.5 * std::sqrt((sx * sx + sy * sy) + sz * sz);
+  vis->bias = 0.125 * std::min(sx, std::min(sy, sz));
+  vis->floor = 0.015625; /* 2^-6 */
+}
+
+size_t rt_hip_probe_depth_workspace_bytes(uint64_t n_probes, uint32_t res, uint32_t slice_rays)
+{
+  if (res < PT_VIS_RES_MIN || res > PT_VIS_RES_MAX || slice_rays == 0u || n_probes > VIS_TEXELS_MAX || n_probes * res * res > VIS_TEXELS_MAX)
+    return 0;
+  return DepthWorkspace(slice_rays, n_probes, res).total;
+}
+
+int rt_hip_bake_probe_depth(const RtHipScene *scene, const double *d_positions, uint64_t n_probes, const RtHipProbeVis *vis,
+                            const RtHipProbeParams *probe_params, uint32_t slice_rays, void *d_workspace, double *d_moments,
+                            uint32_t *d_status, void *stream)
+{
+  if (const int rc = check_depth_bake(vis, probe_params, n_probes, slice_rays, d_workspace))
+    return rc;
+  if (n_probes == 0)
+    return RT_HIP_OK;
+  if (!scene || !d_positions || !d_workspace || !d_moments)
+    return fail(RT_HIP_EINVAL, "scene, d_positions, d_workspace and d_moments are required");
+  return guarded("rt_hip_bake_probe_depth", [&] {
+    return bake_probe_depth_launch(scene, d_positions, n_probes, vis, probe_params, slice_rays, d_workspace, d_moments, d_status,
+                                   static_cast<hipStream_t>(stream));
+  });
+}
+
+size_t rt_hip_probe_grid_depth_workspace_bytes(const RtHipProbeGrid *grid, uint32_t res, uint32_t slice_rays)
+{
+  if (check_grid(grid))
+    return 0;
+  const uint64_t n = grid_probes(grid);
+  const size_t bake = rt_hip_probe_depth_workspace_bytes(n, res, slice_rays);
+  return bake ? bake + stage_align(24u * n) : 0;
+}
+
+int rt_hip_bake_probe_grid_depth(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                                 const RtHipProbeParams *probe_params, uint32_t slice_rays, void *d_workspace, double *d_moments,
+                                 uint32_t *d_status, void *stream)
+{
+  if (const int rc = check_grid_depth_bake(grid, vis, probe_params, slice_rays, d_workspace))
+    return rc;
+  if (!scene || !d_workspace || !d_moments)
+    return fail(RT_HIP_EINVAL, "scene, d_workspace and d_moments are required");
+  return guarded("rt_hip_bake_probe_grid_depth", [&] {
+    return bake_probe_grid_depth_launch(scene, grid, vis, probe_params, slice_rays, d_workspace, d_moments, d_status,
+                                        static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_hip_probe_shade_vis(const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const double *d_coeff, const double *d_moments,
+                           const double *d_points, const double *d_normals, const uint32_t *d_status, const float *d_albedo,
+                           const float *d_add, uint64_t m, double *d_irradiance, float *d_color, void *stream)
+{
+  if (const int rc = check_shade(grid, d_coeff, d_points, d_normals, m, d_irradiance, d_color))
+    return rc;
+  if (const int rc = check_vis(vis, grid_probes(grid)))
+    return rc;
+  if (!d_moments)
+    return fail(RT_HIP_EINVAL, "d_moments is required");
+  if (m == 0)
+    return RT_HIP_OK;
+  return on_device_of(d_points, "d_points", [&] {
+    return shade_vis_launch(grid, vis, d_coeff, d_moments, d_points, d_normals, d_status, d_albedo, d_add, m, d_irradiance, d_color,
+                            static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_hip_probe_preview_vis(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                             const double *d_coeff, const double *d_moments, int32_t width, int32_t height, int32_t aov_samples,
+                             uint64_t seed, void *d_workspace, float *d_rgb, uint8_t *d_rgb8, void *stream)
+{
+  if (const int rc = check_preview(camera, grid, width, height, aov_samples))
+    return rc;
+  if (const int rc = check_vis(vis, grid_probes(grid)))
+    return rc;
+  if (!scene || !d_coeff || !d_moments || !d_workspace || !d_rgb)
+    return fail(RT_HIP_EINVAL, "scene, d_coeff, d_moments, d_workspace and d_rgb are required");
+  if (reinterpret_cast<uintptr_t>(d_workspace) & 15u)
+    return fail(RT_HIP_EINVAL, "d_workspace must be 16-byte aligned");
+  return guarded("rt_hip_probe_preview_vis", [&] {
+    return probe_preview_launch(scene, camera, grid, d_coeff, width, height, aov_samples, seed, d_workspace, d_rgb, d_rgb8,
+                                static_cast<hipStream_t>(stream), vis, d_moments);
+  });
+}
+
+int rt_hip_probe_preview_vis_scene_image(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid,
+                                         const RtHipProbeVis *vis, const RtHipProbeParams *probe_params, int32_t width, int32_t height,
+                                         int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8, double *h_coeff, double *h_moments,
+                                         uint64_t *h_stats)
+{
+  return guarded("rt_hip_probe_preview_vis_scene_image", [&]() -> int {
+    if (const int rc = check_preview_vis_image(camera, grid, vis, probe_params, width, height, aov_samples, h_rgb, h_rgb8))
+      return rc;
+    if (!scene)
+      return fail(RT_HIP_EINVAL, "scene is required");
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    return preview_vis_image_of(scene, scene->device, camera, grid, vis, probe_params, width, height, aov_samples, h_rgb, h_rgb8, h_coeff,
+                                h_moments, h_stats);
+  });
+}
+
+int rt_hip_probe_preview_vis_image(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                                   const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                                   const RtHipProbeParams *probe_params, int32_t width, int32_t height, int32_t aov_samples, int device,
+                                   float *h_rgb, uint8_t *h_rgb8, double *h_coeff, double *h_moments, uint64_t *h_stats)
+{
+  return guarded("rt_hip_probe_preview_vis_image", [&]() -> int {
+    if (const int rc = check_preview_vis_image(camera, grid, vis, probe_params, width, height, aov_samples, h_rgb, h_rgb8))
+      return rc;
+    return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device, [&](const RtHipScene *scene, int phys) {
+      return preview_vis_image_of(scene, phys, camera, grid, vis, probe_params, width, height, aov_samples, h_rgb, h_rgb8, h_coeff, h_moments,
+                                  h_stats);
+    });
   });
 }
 

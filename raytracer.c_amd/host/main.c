@@ -27,8 +27,9 @@
  *   -k <x,y,z>   a light probe instead of rendering: the 27 SH9 radiance coefficients of the chosen scene at that point
  *                (rt_hip_bake_probes_host, RT_HIP_PROBE_SPHERE, -s rays, -d and -r as given): status and nine lines of three
  *                channels.  Nothing is rendered or written.
- *   -m <nx,ny,nz> the probe-lit preview in the frame's place (rt_set_probe_grid): a grid of nx x ny x nz light probes over the scene's
- *                bounds, -s rays a probe, -d and -r as given; the PNG is rt_hip_probe_preview_image's frame.  One GPU.
+ *   -m <nx,ny,nz[,res]> the probe-lit preview in the frame's place (rt_set_probe_grid): a grid of nx x ny x nz light probes over the
+ *                scene's bounds, -s rays a probe, -d and -r as given; the PNG is rt_hip_probe_preview_image's frame.  One GPU.  A fourth
+ *                number, 2 .. 32, weighs every probe by its baked visibility (rt_set_probe_visibility): depth moments in res x res maps.
  *   -u <f>       preview by guided upsampling, integer f >= 2 (upsample_frame, rt_hip_upsample's defaults, one GPU): the frame is
  *                rendered at ceil(w / f) x ceil(h / f) under the full size's camera (with -n: and denoised there), the first-hit
  *                buffers are rendered at both sizes, and the low frame is brought to w x h under the full-size buffers.  The PNG
@@ -130,6 +131,7 @@ typedef struct
   int probe;        /* -k given */
   double probe_at[3]; /* -k: the light probe's position */
   int grid[3];      /* -m: probes an axis of the probe-lit preview; 0: not given */
+  int grid_vis;     /* -m's fourth number: the resolution of the probes' visibility maps; 0: not given */
   uint64_t seed;
 } Args;
 
@@ -148,8 +150,9 @@ static void usage(const char *prog)
           "          [-l <aperture,focus: depth of field from a thin lens of that radius, sharp at that distance; one GPU, trace_path,\n"
           "               not with -p, -e or -u; aperture 0 is the pinhole frame>]\n"
           "          [-k <x,y,z: print the 27 SH9 coefficients of a light probe there, -s rays, -d and -r as given; nothing is rendered>]\n"
-          "          [-m <nx,ny,nz: the probe-lit preview in the frame's place: a grid of that many light probes over the scene, -s rays a\n"
-          "               probe; one GPU, not with -p, -e, -u, -l or -i 1>]\n",
+          "          [-m <nx,ny,nz[,res]: the probe-lit preview in the frame's place: a grid of that many light probes over the scene, -s rays a\n"
+          "               probe; res in 2 .. 32: probes weighed by baked visibility maps of res x res texels; one GPU, not with -p, -e, -u, -l or\n"
+          "               -i 1>]\n",
           prog);
 }
 
@@ -235,10 +238,19 @@ static int parse_args(int argc, char **argv, Args *a)
       {
         char *end = NULL;
         const long n = strtol(at, &end, 10);
-        if (end == at || *end != (c < 2 ? ',' : '\0') || n < 1 || n > (1 << 24))
+        if (end == at || (c < 2 ? *end != ',' : (*end != ',' && *end != '\0')) || n < 1 || n > (1 << 24))
           return -1;
         a->grid[c] = (int)n;
-        at = end + 1;
+        at = end + (*end ? 1 : 0);
+      }
+      a->grid_vis = 0;
+      if (*at || at[-1] == ',')
+      { /* the optional fourth number: the visibility maps' resolution */
+        char *end = NULL;
+        const long res = strtol(at, &end, 10);
+        if (end == at || *end != '\0' || res < 2 || res > 32)
+          return -1;
+        a->grid_vis = (int)res;
       }
       break;
     }
@@ -500,6 +512,7 @@ int main(int argc, char **argv)
     rt_set_lens(a.lens_aperture, a.lens_focus);
   if (a.grid[0])
     rt_set_probe_grid(a.grid[0], a.grid[1], a.grid[2]);
+  rt_set_probe_visibility(a.grid[0] ? a.grid_vis : 0);
 
   if (a.upsample)
   {

@@ -89,6 +89,10 @@ void rt_get_probe_grid(int *nx, int *ny, int *nz)
   if (nz)
     *nz = g_probe_grid[2];
 }
+/* the octahedral map's resolution of the probe grid's visibility weight; 0: off */
+static int g_probe_vis_res = 0;
+void rt_set_probe_visibility(int res) { g_probe_vis_res = res >= 2 && res <= 32 ? res : 0; }
+int rt_get_probe_visibility(void) { return g_probe_vis_res; }
 static int g_bvh_builder = RT_BVH_HOST;
 void rt_set_bvh_builder(int builder)
 {
@@ -352,8 +356,17 @@ void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t 
       pp.samples = p.samples;
       pp.max_depth = p.max_depth;
       pp.seed = p.seed;
-      rc = rt_hip_probe_preview_scene_image(scene, (const RtHipCamera *)camera, &grid, &pp, p.width, p.height, 1, linear_rgb, framebuffer, NULL,
-                                            stats);
+      if (g_probe_vis_res > 0)
+      { /* ... with every corner weighed by its baked visibility: the defaults for this grid at the chosen resolution */
+        RtHipProbeVis vis;
+        rt_hip_probe_vis_defaults(&vis, &grid);
+        vis.res = (uint32_t)g_probe_vis_res;
+        rc = rt_hip_probe_preview_vis_scene_image(scene, (const RtHipCamera *)camera, &grid, &vis, &pp, p.width, p.height, 1, linear_rgb,
+                                                  framebuffer, NULL, NULL, stats);
+      }
+      else
+        rc = rt_hip_probe_preview_scene_image(scene, (const RtHipCamera *)camera, &grid, &pp, p.width, p.height, 1, linear_rgb, framebuffer,
+                                              NULL, stats);
     }
     if (scene)
       rt_hip_scene_destroy(scene);

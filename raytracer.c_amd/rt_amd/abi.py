@@ -165,6 +165,11 @@ class RtHipProbeGrid(C.Structure):  # rt_hip.h: a regular grid of probes (rt_hip
                 ("count", C.c_uint32 * 3), ("miss_color", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
+class RtHipProbeVis(C.Structure):  # rt_hip.h: a grid's depth-moment visibility (rt_hip_probe_vis_defaults), 48 B
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("res", C.c_uint32), ("sharp", C.c_uint32), ("d_max", C.c_double),
+                ("bias", C.c_double), ("floor", C.c_double), ("reserved", C.c_uint64)]
+
+
 class RtHipPixelParams(C.Structure):  # rt_hip.h: a pixel refinement's trace (rt_hip_pixel_defaults), 32 B
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("sample_first", C.c_int32),
                 ("max_depth", C.c_int32), ("integrator", C.c_uint32), ("seed", C.c_uint64)]
@@ -341,6 +346,24 @@ SHIM_SYMBOLS = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_probe_preview_scene_image": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeParams), C.c_int32,
                                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_vis_defaults": (None, [C.POINTER(RtHipProbeVis), C.POINTER(RtHipProbeGrid)]),
+    "rt_hip_probe_depth_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "rt_hip_bake_probe_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RtHipProbeVis), C.POINTER(RtHipProbeParams), C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_grid_depth_workspace_bytes": (C.c_size_t, [C.POINTER(RtHipProbeGrid), C.c_uint32, C.c_uint32]),
+    "rt_hip_bake_probe_grid_depth": (C.c_int, [C.c_void_p, C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis), C.POINTER(RtHipProbeParams),
+                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_shade_vis": (C.c_int, [C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_preview_vis": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis), C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "rt_hip_probe_preview_vis_image": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.POINTER(Camera),
+                                                 C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis), C.POINTER(RtHipProbeParams), C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_preview_vis_scene_image": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis),
+                                                       C.POINTER(RtHipProbeParams), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_denoise_defaults": (None, [C.POINTER(RtHipDenoiseParams)]),
     "rt_hip_denoise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rt_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_void_p,
@@ -413,6 +436,8 @@ HOST_SYMBOLS = {
     "rt_get_lens": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_set_probe_grid": (None, [C.c_int, C.c_int, C.c_int]),
     "rt_get_probe_grid": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rt_set_probe_visibility": (None, [C.c_int]),
+    "rt_get_probe_visibility": (C.c_int, []),
     "rt_set_integrator": (None, [C.c_int]),
     "rt_get_integrator": (C.c_int, []),
     "rt_set_bvh_builder": (None, [C.c_int]),
@@ -539,6 +564,16 @@ def probe_grid(origin, step, count, facing=False, miss_color=None):
             g.miss_color[a] = miss_color[a]
     g.flags = GRID_FACING if facing else 0
     return g
+
+
+def probe_vis(grid, res=None, sharp=None, d_max=None, bias=None, floor=None):
+    """rt_hip_probe_vis_defaults() for `grid` (abi.probe_grid(...), or None) with the given fields replaced (None: the default)"""
+    v = RtHipProbeVis()
+    load_shim().rt_hip_probe_vis_defaults(C.byref(v), None if grid is None else C.byref(grid))
+    for f, x in (("res", res), ("sharp", sharp), ("d_max", d_max), ("bias", bias), ("floor", floor)):
+        if x is not None:
+            setattr(v, f, x)
+    return v
 
 
 def reproject_params(max_history=None, depth_tol=None, normal_min=None):

@@ -119,6 +119,14 @@ def _grid_radius(grid):
     return _distance(far) * (1.0 + 2.0 ** -40)
 
 
+def _moments(moments, grid, vis, dev, who):
+    """a grid's depth moments as a contiguous float64 tensor on `dev`: R*R x 2 values a probe"""
+    t = torch.as_tensor(moments, dtype=torch.float64, device=dev).contiguous()
+    if t.numel() != _grid_count(grid) * vis.res * vis.res * 2:
+        raise ValueError(f"{who}: moments must hold {vis.res} x {vis.res} x 2 values per probe of the grid")
+    return t
+
+
 def _slices(n, samples, slice_rays):
     """(slice_rays, rays a launch) of a sliced bake of n probes: None is everything at once, and a launch has 1 .. total rays"""
     total = max(n * samples, 1)
@@ -677,10 +685,12 @@ class GpuScene:
         out = self._bake(abi.PROBE_HEMISPHERE, positions, normals, samples, seed, bias, max_depth, origin_radius, slice_rays, stats)
         return out if details else out["coeff"].reshape(-1, 3)
 
-    def bake_probe_grid(self, grid, samples, seed, max_depth=None, origin_radius=None, slice_rays=None, stats=None, details=False):
+    def bake_probe_grid(self, grid, samples, seed, max_depth=None, origin_radius=None, slice_rays=None, stats=None, details=False, vis=None):
         """A grid of sphere probes baked in one call (rt_hip.h, rt_hip_bake_probe_grid: the grid's positions, then rt_hip_bake_probes
         at them); grid: abi.probe_grid(...) -> float64 [N, 9, 3] on the device, N = the grid's probes in index order (details: the dict
-        of coeff, coeff_f, status, stats).  origin_radius None: the farthest corner of the grid from the world's origin."""
+        of coeff, coeff_f, status, stats).  origin_radius None: the farthest corner of the grid from the world's origin.  vis
+        (abi.probe_vis(...)): the depth moments of the same rays as well (rt_hip_bake_probe_grid_depth) -> (coeff, moments float64
+        [N, R*R, 2]); details: the dict gains moments and depth_status."""
         dev, n = self.dev, _grid_count(grid)
         p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, _depth(self.scene, max_depth), 0.0,
                              _grid_radius(grid) if origin_radius is None else origin_radius)
@@ -691,12 +701,55 @@ class GpuScene:
         self._probe_buffers = (ws,)   # keep alive until the stream has used them
         _check(self.shim.rt_hip_bake_probe_grid(self.handle, C.byref(grid), C.byref(p), slice_rays, _ptr(ws), _ptr(out["coeff"]), _ptr(out["coeff_f"]),
                                                 _ptr(out["status"]), _ptr(out["stats"]), _stream(dev)), "rt_hip_bake_probe_grid")
+        if vis is not None:
+            out["moments"], out["depth_status"] = self._grid_depth(grid, vis, p, slice_rays, launch)
+            return out if details else (out["coeff"], out["moments"])
         return out if details else out["coeff"]
 
-    def probe_preview(self, grid, coeff, camera=None, aov_samples=1, seed=0):
+    def _grid_depth(self, grid, vis, p, slice_rays, launch):
+        """rt_hip_bake_probe_grid_depth under the probe params p -> (moments float64 [N, R*R, 2], status int32 [N])"""
+        dev, n = self.dev, _grid_count(grid)
+        ws = _workspace(self.shim.rt_hip_probe_grid_depth_workspace_bytes(C.byref(grid), vis.res, launch), dev)
+        moments = torch.empty((n, vis.res * vis.res, 2), dtype=torch.float64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        self._depth_buffers = (ws,)   # keep alive until the stream has used them
+        _check(self.shim.rt_hip_bake_probe_grid_depth(self.handle, C.byref(grid), C.byref(vis), C.byref(p), slice_rays, _ptr(ws), _ptr(moments),
+                                                      _ptr(status), _stream(dev)), "rt_hip_bake_probe_grid_depth")
+        return moments, status
+
+    def probe_depth_moments(self, positions, vis, samples, seed, origin_radius=None, slice_rays=None, details=False):
+        """The depth moments of sphere probes at positions [N, 3] (rt_hip.h, rt_hip_bake_probe_depth): per probe an R x R octahedral
+        map of the mean and the mean square of the distance to the nearest surface, folded from the closest hits of the very rays
+        bake_probes traces under the same samples and seed; vis: abi.probe_vis(...); asynchronous on torch's current stream ->
+        float64 [N, R*R, 2] on the device (details: the dict of moments and status int32 [N], 2 where a ray of the probe was
+        invalid).  positions may be an abi.probe_grid(...): the grid's probes (rt_hip_bake_probe_grid_depth).  No output bit depends
+        on origin_radius or slice_rays."""
+        dev = self.dev
+        if isinstance(positions, abi.RtHipProbeGrid):
+            grid = positions
+            p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, None, 0.0, _grid_radius(grid) if origin_radius is None else origin_radius)
+            slice_rays, launch = _slices(_grid_count(grid), samples, slice_rays)
+            moments, status = self._grid_depth(grid, vis, p, slice_rays, launch)
+            return dict(moments=moments, status=status) if details else moments
+        pos = _points3(positions, dev)
+        n = pos.shape[0]
+        if origin_radius is None:
+            origin_radius = _origin_radius(torch.linalg.vector_norm(pos, dim=1), None, 0.0)   # (synchronises)
+        p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, None, 0.0, origin_radius)
+        slice_rays, launch = _slices(n, samples, slice_rays)
+        ws = _workspace(self.shim.rt_hip_probe_depth_workspace_bytes(n, vis.res, launch), dev)
+        moments = torch.empty((n, vis.res * vis.res, 2), dtype=torch.float64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        self._depth_buffers = (ws, pos)   # keep alive until the stream has used them
+        _check(self.shim.rt_hip_bake_probe_depth(self.handle, _some(pos), n, C.byref(vis), C.byref(p), slice_rays, _ptr(ws), _some(moments),
+                                                 _some(status), _stream(dev)), "rt_hip_bake_probe_depth")
+        return dict(moments=moments, status=status) if details else moments
+
+    def probe_preview(self, grid, coeff, camera=None, aov_samples=1, seed=0, vis=None, moments=None):
         """The probe-lit preview of the scene's frame (rt_hip.h, rt_hip_probe_preview): first hits at the pixel centres, their albedo
         and emission, lit by the grid's baked coefficients coeff [N, 9, 3]; asynchronous on torch's current stream ->
-        (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3]) on the device"""
+        (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3]) on the device.  vis (abi.probe_vis(...)) and moments [N, R*R, 2]: both or
+        neither; with them the shade weighs every corner by its visibility (rt_hip_probe_preview_vis)."""
         dev = self.dev
         w, h = self.scene.width, self.scene.height
         coeff = torch.as_tensor(coeff, dtype=torch.float64, device=dev).contiguous()
@@ -704,6 +757,15 @@ class GpuScene:
             raise ValueError("probe_preview: coeff must hold 9 x 3 values per probe of the grid")
         ws = _workspace(self.shim.rt_hip_probe_preview_workspace_bytes(self.handle, w, h), dev)
         rgb, rgb8 = _frame_pair(h, w, dev)
+        if (vis is None) != (moments is None):
+            raise ValueError("probe_preview: vis and moments go together")
+        if vis is not None:
+            moments = _moments(moments, grid, vis, dev, "probe_preview")
+            self._preview_buffers = (ws, coeff, moments)   # keep alive until the stream has used them
+            _check(self.shim.rt_hip_probe_preview_vis(self.handle, C.byref(_camera(self.scene, camera)), C.byref(grid), C.byref(vis), _ptr(coeff),
+                                                      _ptr(moments), w, h, aov_samples, seed, _ptr(ws), _ptr(rgb), _ptr(rgb8), _stream(dev)),
+                   "rt_hip_probe_preview_vis")
+            return rgb, rgb8
         self._preview_buffers = (ws, coeff)   # keep alive until the stream has used them
         _check(self.shim.rt_hip_probe_preview(self.handle, C.byref(_camera(self.scene, camera)), C.byref(grid), _ptr(coeff), w, h, aov_samples,
                                               seed, _ptr(ws), _ptr(rgb), _ptr(rgb8), _stream(dev)), "rt_hip_probe_preview")
@@ -1573,12 +1635,16 @@ def probe_grid_positions(grid, device=0):
     return out
 
 
-def probe_shade(grid, coeff, points, normals, status=None, albedo=None, add=None, want=("irradiance", "color"), out=None, m=None):
+def probe_shade(grid, coeff, points, normals, status=None, albedo=None, add=None, want=("irradiance", "color"), out=None, m=None, vis=None,
+                moments=None):
     """Entries shaded from a grid of SH9 probes (rt_hip.h, rt_hip_probe_shade): coeff float64 [N, 9, 3] on a device, points and
     normals [m, 3] float64 (a ray query's point and normal as they stand), status [m] (the query's words) or None, albedo and add
     [m, 3] float32 or None -> dict of irradiance float64 [m, 3] and color float32 [m, 3] (want: which; out: a dict of tensors to write
-    into; m: shade the first m entries only); asynchronous on torch's current stream"""
+    into; m: shade the first m entries only); asynchronous on torch's current stream.  vis (abi.probe_vis(...)) and moments
+    [N, R*R, 2]: both or neither; with them every corner is weighed by its visibility (rt_hip_probe_shade_vis)."""
     shim = abi.load_shim()
+    if (vis is None) != (moments is None):
+        raise ValueError("probe_shade: vis and moments go together")
     coeff = coeff.contiguous()
     dev = coeff.device
     pts, nrm = _points3(points, dev), _points3(normals, dev)
@@ -1596,9 +1662,14 @@ def probe_shade(grid, coeff, points, normals, status=None, albedo=None, add=None
     for f, dt in (("irradiance", torch.float64), ("color", torch.float32)):
         if f in want and f not in res:
             res[f] = torch.empty((n, 3), dtype=dt, device=dev)
+    outs = (_some(res.get("irradiance"), "irradiance" in want), _some(res.get("color"), "color" in want), _stream(dev))
+    if vis is not None:
+        mom = _moments(moments, grid, vis, dev, "probe_shade")
+        _check(shim.rt_hip_probe_shade_vis(C.byref(grid), C.byref(vis), _some(coeff), _some(mom), _some(pts), _some(nrm), _some(st), _some(alb),
+                                           _some(ad), n if m is None else m, *outs), "rt_hip_probe_shade_vis")
+        return {f: res[f] for f in want}
     _check(shim.rt_hip_probe_shade(C.byref(grid), _some(coeff), _some(pts), _some(nrm), _some(st), _some(alb), _some(ad), n if m is None else m,
-                                   _some(res.get("irradiance"), "irradiance" in want), _some(res.get("color"), "color" in want), _stream(dev)),
-           "rt_hip_probe_shade")
+                                   *outs), "rt_hip_probe_shade")
     return {f: res[f] for f in want}
 
 
@@ -1616,6 +1687,22 @@ def probe_preview_host(scene, grid, samples, seed, camera=None, aov_samples=1, m
                                            scene.height, aov_samples, device, img.ctypes.data, img8.ctypes.data, coeff.ctypes.data, stats),
            "rt_hip_probe_preview_image")
     return img, img8, coeff, _stats_dict(stats)
+
+
+def probe_preview_vis_host(scene, grid, vis, samples, seed, camera=None, aov_samples=1, max_depth=None, origin_radius=None, device=0):
+    """rt_hip_probe_preview_vis_image(): probe_preview_host with the grid's depth moments baked as well and the visibility-weighted
+    shade -> (rgb float32 [H, W, 3], rgb8 uint8 [H, W, 3], coeff float64 [N, 9, 3], moments float64 [N, R*R, 2], stats dict)"""
+    shim = abi.load_shim()
+    p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, _depth(scene, max_depth), 0.0,
+                         _grid_radius(grid) if origin_radius is None else origin_radius)
+    img, img8 = _frame_pair(scene.height, scene.width, None)
+    coeff = np.zeros((_grid_count(grid), 9, 3), dtype=np.float64)
+    moments = np.zeros((_grid_count(grid), vis.res * vis.res, 2), dtype=np.float64)
+    stats = _host_counters()
+    _check(shim.rt_hip_probe_preview_vis_image(*_host_scene(scene), C.byref(_camera(scene, camera)), C.byref(grid), C.byref(vis), C.byref(p),
+                                               scene.width, scene.height, aov_samples, device, img.ctypes.data, img8.ctypes.data,
+                                               coeff.ctypes.data, moments.ctypes.data, stats), "rt_hip_probe_preview_vis_image")
+    return img, img8, coeff, moments, _stats_dict(stats)
 
 
 def bake_probes_host(scene, positions, samples, seed, normals=None, bias=0.0, max_depth=None, origin_radius=None, device=0):
