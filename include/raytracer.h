@@ -270,6 +270,18 @@ void rt_get_probe_grid(int *nx, int *ny, int *nz);
 void rt_set_probe_visibility(int res);
 int rt_get_probe_visibility(void);
 
+/* A probe grid that follows a moving scene (rt_hip.h, "probe updates").  With rt_set_probe_grid on, rt_set_scene_updates(1) and
+ * rays >= 1, render() and render_ex() keep their scene and the grid's state (coefficients, depth moments, ages) between calls.  A call
+ * whose scene equals the previous call's but for sphere centres and radii and vertex positions takes those in place; if the grid it
+ * derives is the previous call's as well -- the same counts, the same reach, the same visibility resolution -- the frame is one
+ * update round of `rays` rays a probe (stride 1, the hysteresis given, round 1, 2, ... counting up from the bake) and the preview lit
+ * by the state (rt_hip_probe_update_preview_scene_image), instead of the full bake.  Anything else starts over with the full bake of
+ * options->samples rays a probe, which leaves every age at 1: a first call, another scene, a changed reach or resolution.
+ * rays <= 0 (the default) turns it off: render() is then bit for bit what it is without this call, and keeps nothing.  A hysteresis
+ * outside [0, 1) leaves the setting as it was. */
+void rt_set_probe_update(int rays, double hysteresis);
+void rt_get_probe_update(int *rays, double *hysteresis);
+
 /* Who builds the triangle hierarchy of the scenes render() and its kin upload: RT_BVH_HOST (default) = one host core,
  * RT_BVH_DEVICE = the GPU (rt_hip.h, RT_HIP_BVH_DEVICE).  Images, bytes and counters are the same under either; the time a
  * new or changed scene takes to become renderable is what differs.  Other values are ignored.  The reference has no

@@ -1064,6 +1064,101 @@ int rt_hip_probe_preview_vis_scene_image(const RtHipScene *scene, const RtHipCam
                                          int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8, double *h_coeff, double *h_moments,
                                          uint64_t *h_stats);
 
+/* ---- probe updates: a grid that follows a moving scene, round by round, with hysteresis --------------------------------------------
+ * A baked grid is a snapshot.  After rt_hip_scene_update_spheres or _vertices an UPDATE ROUND traces a few fresh rays for some of the
+ * probes and blends them into the grid's STATE: its coefficients, its depth moments and an AGE a probe (a uint32: how many rounds have
+ * updated the probe since it started over; 0 = it holds nothing yet).  The generator, the radiance and the ray query and the two folds
+ * are called as they stand; what is new is a pure function of its arguments, stated here.  All arithmetic is fp64 + - * /, unfused,
+ * in the order written.
+ *
+ * THE ROUND'S PROBES (RtHipProbeUpdate: stride >= 1, phase < stride).  With n the grid's probe count, the round updates the probes
+ * i_j = phase + j*stride for j = 0 .. M-1, M = phase < n ? (n - 1 - phase) / stride + 1 : 0 (rt_hip_probe_update_count).  No list is
+ * taken: no two writers can collide, and the function is total.
+ * THE ROUND'S RAYS are those of rt_hip_bake_probes in RT_HIP_PROBE_SPHERE mode at the M positions of i_0 .. i_{M-1} (the grid's
+ * formula), in that order, under probe_params with one change: seed_u = rt_mix64(seed + (uint64_t)round), a wrapping add and
+ * rt_rng.h's rt_mix64.  So ray k = j*S + s, and the fresh sums are that call's d_sum bit for bit; with a vis the fresh W, M1, M2 are
+ * the depth fold's sums ("probe visibility") of the very same rays.
+ *
+ * ALPHA of probe i.  a = age[i]; warm = 1.0 / ((double)a + 1.0); base = 1.0 - h; alpha = warm > base ? warm : base.  An age of 0 gives
+ * alpha == 1.0: the probe STARTS OVER.  (h == 0.0 gives alpha == 1.0 at any age, and a probe of age >= 1 blends all the same.)
+ * THE COEFFICIENT BLEND of an updated probe.  fresh[b][ch] = (sum[j][b][ch] * (1.0 / (double)S)) * K, S and K the resolve's own.
+ *   age 0:         out = fresh; old is not read, so that uninitialised memory and a NaN state both recover; change_out = 1.0.
+ *   otherwise:     c = 0.0, m = 0.0, and over ch = 0, 1, 2 of band 0: d = |fresh[0][ch] - old[0][ch]|; c = d > c ? d : c;
+ *                  g = |fresh[0][ch]| > |old[0][ch]| ? |fresh[0][ch]| : |old[0][ch]|; m = g > m ? g : m (a NaN is passed over).
+ *                  change_out = m > 0.0 ? c / m : 0.0.  The fast rule: if change > 0.0 && c > change * m then
+ *                  alpha = alpha > (1.0 - fast) ? alpha : (1.0 - fast).  keep = 1.0 - alpha;
+ *                  out[b][ch] = (old[b][ch] * keep) + (fresh[b][ch] * alpha).
+ *   A NaN fresh sum (an invalid ray) makes the probe's coefficients NaN.  d_coeff_f, where given, gets (float)out; d_change, where
+ *   given, change_out.
+ * THE MOMENT BLEND of an updated probe, per texel, with the alpha by age alone (the fast rule does not apply); keep = 1.0 - alpha:
+ *   W is NaN:    both moments become W.
+ *   W > 0.0:     f = M1 / W, f2 = M2 / W; at age 0 out = (f, f2) and old is not read, else out = (old * keep) + (f * alpha), each
+ *                moment.
+ *   otherwise    (W == 0.0: the round says nothing about this texel) old stays bit for bit; at age 0 the texel gets
+ *                (d_max, d_max*d_max), as the depth resolve gives.
+ * THE AGE STEP, after both blends: age[i] = age[i] == 0xFFFFFFFF ? age[i] : age[i] + 1, for the round's probes only.
+ * A probe that is not in the round keeps every bit of coeff, coeff_f, moments, age, change and status.  The status word of an updated
+ * probe becomes the word rt_hip_bake_probes gives it in the round's bake.  That is 1: a round refuses a grid whose farthest position
+ * origin[a] + (double)(count[a] - 1) * step[a] is not finite on some axis, so every position is finite, every generated direction is
+ * a unit vector, and no ray of a round is invalid.  NaN sums reach the blends only through rt_hip_probe_blend_*, from a caller.
+ *
+ *   - rt_hip_probe_update_defaults: struct_size = sizeof(RtHipProbeUpdate), stride 1, phase 0, round 0, hysteresis 0.9, change 0,
+ *     fast 0, flags and reserved 0.
+ *   - rt_hip_probe_update_count: M; 0 for arguments any call would refuse.
+ *   - rt_hip_probe_update_workspace_bytes: the d_workspace (16-byte aligned) of a round in slices of slice_rays rays: the bake's
+ *     part for M probes, with a vis the depth bake's, the M positions and M status words; 0 for arguments any call would refuse.
+ *   - rt_hip_probe_grid_update: the round on `stream` with no host wait; no output bit depends on slice_rays.  d_coeff (n x 9 x 3
+ *     doubles) and d_age (n uint32) are required; d_moments (n x R*R x 2) is given iff vis is; d_coeff_f, d_change (a double a
+ *     probe), d_status (a uint32 a probe) and d_stats (rt_hip_trace_rays' counters, added to) may be NULL.
+ *   - rt_hip_probe_blend_coeff, _blend_moments, _age_step: the blends and the step alone, on sums the caller supplies by j (M x 9 x 3
+ *     doubles; M x R*R x 3 doubles: W, M1, M2), asynchronous on `stream`, on the device that holds d_age.  M == 0 launches nothing.
+ *   - rt_hip_probe_grid_update_host: the host form, synchronous, with a scene of its own on logical device `device`; h_coeff,
+ *     h_moments (iff vis) and h_age are read and written, h_coeff_f, h_change and h_status (each may be NULL) written for the round's
+ *     probes and otherwise as given; h_stats (may be NULL) is overwritten; it checks the device's status word (rt_hip_launch_status).
+ *   - rt_hip_probe_update_preview_scene_image: for a host that holds a scene and a state across frames: the round
+ *     (rt_hip_probe_grid_update) on the state in h_coeff, h_moments (iff vis) and h_age, read and written, then rt_hip_probe_preview
+ *     (with a vis: rt_hip_probe_preview_vis) lit by the state the round leaves, seed = probe_params->seed, read back into h_rgb and
+ *     h_rgb8 (either may be NULL, not both); synchronous, on the scene's device; h_stats (may be NULL) is overwritten with the
+ *     round's counters; it checks the device's status word.  Bit for bit the composition of the two calls; it refuses what they do.
+ * Refusals, each before any launch and with the outputs untouched, arguments before the device is looked for.  RT_HIP_EINVAL: a NULL
+ * upd or a struct_size below the struct's; flags or reserved not 0; stride 0; phase >= stride; hysteresis or fast outside [0, 1) or
+ * not finite; change negative or not finite; d_moments and vis not both given or both absent; a NULL d_age or d_coeff; a d_moments
+ * that is not 16-byte aligned; a grid whose last position on an axis is not finite; samples < 1 for the blend; everything
+ * rt_hip_bake_probe_grid and rt_hip_bake_probe_grid_depth refuse.  M == 0 is RT_HIP_OK and launches nothing. */
+typedef struct
+{
+  uint32_t struct_size; /* set by rt_hip_probe_update_defaults */
+  uint32_t flags;       /* must be 0 */
+  uint32_t stride;      /* >= 1: a round updates the probes i with i % stride == phase */
+  uint32_t phase;       /* < stride */
+  uint32_t round;       /* u: picks the round's rays */
+  uint32_t reserved;    /* 0 */
+  double hysteresis;    /* h in [0, 1): share of the old state a warm probe keeps */
+  double change;        /* finite, >= 0; 0 = off: relative change of the L0 band above which `fast` applies */
+  double fast;          /* in [0, 1): the hysteresis of a probe whose change exceeds `change` */
+} RtHipProbeUpdate;
+void rt_hip_probe_update_defaults(RtHipProbeUpdate *upd);
+uint64_t rt_hip_probe_update_count(const RtHipProbeGrid *grid, const RtHipProbeUpdate *upd);
+size_t rt_hip_probe_update_workspace_bytes(const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeUpdate *upd,
+                                           uint32_t slice_rays);
+int rt_hip_probe_grid_update(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                             const RtHipProbeParams *probe_params, const RtHipProbeUpdate *upd, uint32_t slice_rays, void *d_workspace,
+                             double *d_coeff, float *d_coeff_f, double *d_moments, uint32_t *d_age, double *d_change, uint32_t *d_status,
+                             uint64_t *d_stats, void *stream);
+int rt_hip_probe_blend_coeff(const double *d_sum, int32_t samples, const RtHipProbeGrid *grid, const RtHipProbeUpdate *upd,
+                             const uint32_t *d_age, double *d_coeff, float *d_coeff_f, double *d_change, void *stream);
+int rt_hip_probe_blend_moments(const double *d_sums, const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeUpdate *upd,
+                               const uint32_t *d_age, double *d_moments, void *stream);
+int rt_hip_probe_age_step(const RtHipProbeGrid *grid, const RtHipProbeUpdate *upd, uint32_t *d_age, void *stream);
+int rt_hip_probe_grid_update_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                                  const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeParams *probe_params,
+                                  const RtHipProbeUpdate *upd, int device, double *h_coeff, float *h_coeff_f, double *h_moments,
+                                  uint32_t *h_age, double *h_change, uint32_t *h_status, uint64_t *h_stats);
+int rt_hip_probe_update_preview_scene_image(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid,
+                                            const RtHipProbeVis *vis, const RtHipProbeParams *probe_params, const RtHipProbeUpdate *upd,
+                                            int32_t width, int32_t height, int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8, double *h_coeff,
+                                            double *h_moments, uint32_t *h_age, uint64_t *h_stats);
+
 /* ---- edge-avoiding a-trous denoiser guided by the first-hit buffers ---------------------------------------------------------
  * Inputs: row-major images of w x h pixels (1 <= w, h <= 2^20, w*h < 2^32) on one device -- colour c (3 floats per pixel: the
  * linear mean of rt_hip_render_tiles or rt_hip_accum_resolve after rt_hip_untile) and the RtHipAov buffers of the same frame

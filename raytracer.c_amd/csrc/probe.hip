@@ -17,6 +17,9 @@
  *                       probe's rays in the slice, in ascending k, from a ray query's status words and t (rt_hip.h, "probe visibility").
  *   k_probe_depth_resolve  one thread a (probe, texel): the mean depth and the mean squared depth.
  *   k_probe_shade_vis   k_probe_shade with a Chebyshev visibility weight a corner, looked up per lane in the probe's map.
+ *   k_probe_grid_positions_strided, k_probe_coeff_blend, k_probe_moment_blend, k_probe_age_step  an update round (rt_hip.h, "probe
+ *                       updates"): the positions of the round's probes, a round's fresh sums blended into the grid's coefficients and
+ *                       moments by each probe's age, the ages stepped.
  * The constants are pt_device.h's.  fp64, unfused (-ffp-contract=off, as every source of the shim), IEEE division and sqrt.  256
  * threads a workgroup, no scratch, no LDS; no kernel waits for another workgroup. */
 #include <hip/hip_runtime.h>
@@ -588,9 +591,167 @@ __global__ void __launch_bounds__(PROBE_BLOCK) k_probe_shade_vis(const PtProbeSh
   }
 }
 
+/* ---- probe updates (rt_hip.h, "probe updates") ---- */
+
+/* the grid index of the round's j-th probe */
+__device__ __forceinline__ size_t round_probe(const PtProbeRound &R, uint64_t j) { return (size_t)(R.phase + j * R.stride); }
+
+/* alpha of a probe by its age: the larger of 1 / (age + 1) and 1 - h */
+__device__ __forceinline__ double age_alpha(uint32_t age, double h)
+{
+  const double warm = 1.0 / ((double)age + 1.0), base = 1.0 - h;
+  return warm > base ? warm : base;
+}
+
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_grid_positions_strided(const PtGrid G, const PtProbeRound R, double *__restrict__ positions)
+{
+  const uint32_t j = blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (j >= R.m)
+    return;
+  const uint32_t i = (uint32_t)round_probe(R, j);
+  const uint32_t ix = i % G.count[0], r = i / G.count[0], iy = r % G.count[1], iz = r / G.count[1];
+  positions[3u * (size_t)j + 0u] = grid_at(G, 0, ix);
+  positions[3u * (size_t)j + 1u] = grid_at(G, 1, iy);
+  positions[3u * (size_t)j + 2u] = grid_at(G, 2, iz);
+}
+
+/* One thread a (probe of the round, basis, channel).  Every thread of a probe works the change rule out again from the probe's three
+ * L0 values -- 27 contiguous doubles a probe on both sides, so that a wave's loads stay on whole lines --: a value has one writer.
+ * The blend is in place, and the L0 values are read by threads that do not write them: a workgroup holds PROBE_BLEND_PROBES whole
+ * probes (243 of its 256 threads), and all of its reads come before its barrier, all of its writes after. */
+constexpr uint32_t PROBE_BLEND_PROBES = PROBE_BLOCK / (3u * PT_PROBE_SH);
+static_assert(PROBE_BLEND_PROBES >= 1u, "a workgroup of k_probe_coeff_blend holds at least one whole probe");
+
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_coeff_blend(const PtProbeCoeffBlend A)
+{
+  constexpr uint32_t V = 3u * PT_PROBE_SH;
+  const uint32_t slot = threadIdx.x / V, r = threadIdx.x - slot * V;
+  const uint64_t j_any = (uint64_t)blockIdx.x * PROBE_BLEND_PROBES + slot;
+  const bool live = slot < PROBE_BLEND_PROBES && j_any < A.round.m;
+  const uint64_t j = live ? j_any : 0u; /* (a thread without a value reads nothing and writes nothing) */
+  const size_t i = round_probe(A.round, j);
+  const double *__restrict__ const s = A.sum + j * V;
+  double *const old = A.coeff + i * V;
+  const uint32_t age = live ? A.age[i] : 0u;
+  double alpha = age_alpha(age, A.hysteresis);
+  const double fresh = live ? (s[r] * A.inv_samples) * A.k : 0.0;
+  double out = fresh, change_out = 1.0;
+  const bool blends = age != 0u; /* (a probe that starts over does not read its old state) */
+  const double old_r = blends ? old[r] : 0.0, o0 = blends ? old[0] : 0.0, o1 = blends ? old[1] : 0.0, o2 = blends ? old[2] : 0.0;
+  __syncthreads();
+  if (!live)
+    return;
+  if (blends)
+  {
+    const double o3[3] = {o0, o1, o2};
+    double c = 0.0, m = 0.0;
+#pragma unroll
+    for (uint32_t ch = 0; ch < 3u; ch++)
+    {
+      const double f = (s[ch] * A.inv_samples) * A.k, o = o3[ch];
+      const double d = fabs(f - o), af = fabs(f), ao = fabs(o), big = af > ao ? af : ao;
+      c = d > c ? d : c;
+      m = big > m ? big : m;
+    }
+    change_out = m > 0.0 ? c / m : 0.0;
+    if (A.change > 0.0 && c > A.change * m)
+    {
+      const double quick = 1.0 - A.fast;
+      alpha = alpha > quick ? alpha : quick;
+    }
+    const double keep = 1.0 - alpha;
+    out = (old_r * keep) + (fresh * alpha);
+  }
+  old[r] = out;
+  if (A.coeff_f)
+    A.coeff_f[i * V + r] = (float)out;
+  if (A.change_out && r == 0u)
+    A.change_out[i] = change_out;
+}
+
+/* One thread a (probe of the round, texel): the moment pair is loaded and stored as 16 bytes.  A texel the round says nothing about
+ * (W == 0) is not stored at all unless the probe starts over. */
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_moment_blend(const PtProbeMomentBlend A)
+{
+  const uint32_t texels = A.res * A.res;
+  const uint64_t t = (uint64_t)blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (t >= (uint64_t)A.round.m * texels)
+    return;
+  const uint64_t j = t / texels;
+  const uint32_t texel = (uint32_t)(t - j * texels);
+  const size_t i = round_probe(A.round, j);
+  const double *__restrict__ const s = A.sums + (j * texels + texel) * 3u;
+  double2 *const at = reinterpret_cast<double2 *>(A.moments) + (i * texels + texel);
+  const uint32_t age = A.age[i];
+  const double alpha = age_alpha(age, A.hysteresis);
+  const double W = s[0], M1 = s[1], M2 = s[2];
+  double2 out;
+  if (W != W)
+    out.x = out.y = W;
+  else if (W > 0.0)
+  {
+    out.x = M1 / W;
+    out.y = M2 / W;
+    if (age != 0u)
+    {
+      const double2 old = *at;
+      const double keep = 1.0 - alpha;
+      out.x = (old.x * keep) + (out.x * alpha);
+      out.y = (old.y * keep) + (out.y * alpha);
+    }
+  }
+  else if (age == 0u)
+  {
+    out.x = A.d_max;
+    out.y = A.d_max * A.d_max;
+  }
+  else
+    return;
+  *at = out;
+}
+
+__global__ void __launch_bounds__(PROBE_BLOCK) k_probe_age_step(const PtProbeRound R, uint32_t *__restrict__ age,
+                                                                 const uint32_t *__restrict__ round_status, uint32_t *__restrict__ status)
+{
+  const uint32_t j = blockIdx.x * PROBE_BLOCK + threadIdx.x;
+  if (j >= R.m)
+    return;
+  const size_t i = round_probe(R, j);
+  const uint32_t a = age[i];
+  age[i] = a == 0xFFFFFFFFu ? a : a + 1u;
+  if (round_status && status)
+    status[i] = round_status[j];
+}
+
 uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + PROBE_BLOCK - 1u) / PROBE_BLOCK); }
 
 } // namespace
+
+hipError_t probe_launch_grid_positions_strided(const PtGrid &grid, const PtProbeRound &round, double *positions, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_probe_grid_positions_strided, dim3(blocks_for(round.m)), dim3(PROBE_BLOCK), 0, stream, grid, round, positions);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_coeff_blend(const PtProbeCoeffBlend &args, hipStream_t stream)
+{
+  const uint32_t blocks = (args.round.m + PROBE_BLEND_PROBES - 1u) / PROBE_BLEND_PROBES;
+  hipLaunchKernelGGL(k_probe_coeff_blend, dim3(blocks), dim3(PROBE_BLOCK), 0, stream, args);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_moment_blend(const PtProbeMomentBlend &args, hipStream_t stream)
+{
+  const uint64_t threads = (uint64_t)args.round.m * args.res * args.res;
+  hipLaunchKernelGGL(k_probe_moment_blend, dim3(blocks_for(threads)), dim3(PROBE_BLOCK), 0, stream, args);
+  return hipGetLastError();
+}
+
+hipError_t probe_launch_age_step(const PtProbeRound &round, uint32_t *age, const uint32_t *round_status, uint32_t *status, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_probe_age_step, dim3(blocks_for(round.m)), dim3(PROBE_BLOCK), 0, stream, round, age, round_status, status);
+  return hipGetLastError();
+}
 
 hipError_t probe_launch_rays(const PtProbeRays &args, hipStream_t stream)
 {

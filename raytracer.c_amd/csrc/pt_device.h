@@ -915,5 +915,48 @@ hipError_t probe_launch_depth_resolve(const double *sum, uint64_t n_texels, doub
 hipError_t probe_launch_shade_vis(const PtProbeShadeVis &args, hipStream_t stream);
 #endif
 
+/* ---- probe updates (rt_hip.h, "probe updates"; the kernels are probe.hip's) ---- */
+
+/* A round's probes: i_j = phase + j * stride for j = 0 .. m - 1, every one below the grid's count */
+struct PtProbeRound
+{
+  uint32_t stride, phase, m;
+};
+
+/* the coefficient blend of a round: sum holds m x PT_PROBE_SH x 3 doubles by j; coeff, coeff_f, change and age are the grid's, by i;
+ * coeff_f and change_out may be null */
+struct PtProbeCoeffBlend
+{
+  PtProbeRound round;
+  const double *sum;
+  const uint32_t *age;
+  double *coeff;
+  float *coeff_f;
+  double *change_out;
+  double inv_samples, k, hysteresis, change, fast;
+};
+
+/* the moment blend of a round: sums holds m x res x res x 3 doubles (W, M1, M2) by j; moments the grid's res x res x 2 a probe, by i */
+struct PtProbeMomentBlend
+{
+  PtProbeRound round;
+  const double *sums;
+  const uint32_t *age;
+  double *moments;
+  double hysteresis, d_max;
+  uint32_t res;
+};
+
+#if defined(__HIPCC__)
+/* m >= 1: positions[3 j ..] = the grid's position of probe i_j, a thread an updated probe */
+hipError_t probe_launch_grid_positions_strided(const PtGrid &grid, const PtProbeRound &round, double *positions, hipStream_t stream);
+/* m >= 1: rt_hip.h's coefficient blend, a thread an (updated probe, basis, channel) */
+hipError_t probe_launch_coeff_blend(const PtProbeCoeffBlend &args, hipStream_t stream);
+/* m >= 1: rt_hip.h's moment blend, a thread an (updated probe, texel) */
+hipError_t probe_launch_moment_blend(const PtProbeMomentBlend &args, hipStream_t stream);
+/* m >= 1: age[i_j] steps up to 0xFFFFFFFF and stays; where both are given, status[i_j] = round_status[j] */
+hipError_t probe_launch_age_step(const PtProbeRound &round, uint32_t *age, const uint32_t *round_status, uint32_t *status, hipStream_t stream);
+#endif
+
 
 #endif /* PT_DEVICE_H */

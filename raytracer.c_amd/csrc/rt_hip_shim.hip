@@ -3726,7 +3726,9 @@ int bake_probes_launch(const RtHipScene *scene, const double *d_positions, const
         F.n_probes = (first + n - 1u) / S - F.probe_first + 1u;
         return launched(probe_launch_fold(F, stream), "k_probe_fold");
       },
-      [&](const SliceBuffers &B) { return probe_resolve_launch(B.sum, n_probes, p->mode, p->samples, d_coeff, d_coeff_f, stream); });
+      [&](const SliceBuffers &B) { /* (no d_coeff: an update round's job, which stops at its sums) */
+        return d_coeff ? probe_resolve_launch(B.sum, n_probes, p->mode, p->samples, d_coeff, d_coeff_f, stream) : (int)RT_HIP_OK;
+      });
 }
 
 /* rt_hip_bake_probes_host: a scene of its own on the logical device, one allocation for the probes, the workspace, the outputs and
@@ -4159,6 +4161,8 @@ int bake_probe_depth_launch(const RtHipScene *scene, const double *d_positions, 
     if (const int rc = launched(probe_launch_depth_fold(F, stream), "k_probe_depth_fold"))
       return rc;
   }
+  if (!d_moments) /* (an update round's job, which stops at its sums) */
+    return RT_HIP_OK;
   DeviceScope scope(scene->device);
   HIP_TRY(scope.status);
   return launched(probe_launch_depth_resolve(sum, texels, vis->d_max, d_moments, stream), "k_probe_depth_resolve");
@@ -4248,6 +4252,212 @@ int preview_vis_image_of(const RtHipScene *scene, int phys, const RtHipCamera *c
     rc = probe_preview_launch(scene, camera, grid, A.at<double>(coeff), width, height, aov_samples, params->seed, A.at<char>(ws),
                               A.at<float>(rgb), A.at<uint8_t>(rgb8), nullptr, vis, A.at<double>(moments));
   return rc ? rc : download_then_status(A, phys);
+}
+
+/* ---- probe updates (rt_hip.h, rt_hip_probe_update_* / rt_hip_probe_grid_update* / rt_hip_probe_blend_*) -----------------------------
+ * A round is the radiance bake's job and the depth bake's job at the positions of the round's probes, each stopped before its resolve,
+ * then the blends of their sums into the grid's state and the age step.  The checks need no device. */
+int check_update(const RtHipProbeUpdate *u)
+{
+  if (!u)
+    return fail(RT_HIP_EINVAL, "upd is required");
+  if (u->struct_size < sizeof(RtHipProbeUpdate))
+    return fail(RT_HIP_EINVAL, "upd->struct_size = %u is below the %zu of RtHipProbeUpdate: start from rt_hip_probe_update_defaults",
+                u->struct_size, sizeof(RtHipProbeUpdate));
+  if (u->flags != 0u || u->reserved != 0u)
+    return fail(RT_HIP_EINVAL, "update flags and reserved must be 0");
+  if (u->stride == 0u || u->phase >= u->stride)
+    return fail(RT_HIP_EINVAL, "stride = %u must be >= 1 and phase = %u below it", u->stride, u->phase);
+  if (!(u->hysteresis >= 0) || !(u->hysteresis < 1))
+    return fail(RT_HIP_EINVAL, "hysteresis %g must be in [0, 1)", u->hysteresis);
+  if (!(u->fast >= 0) || !(u->fast < 1))
+    return fail(RT_HIP_EINVAL, "fast %g must be in [0, 1)", u->fast);
+  if (!(u->change >= 0) || !std::isfinite(u->change))
+    return fail(RT_HIP_EINVAL, "change %g must be finite and >= 0", u->change);
+  return RT_HIP_OK;
+}
+
+/* the round's probes of a checked update on a checked grid */
+PtProbeRound round_args(const RtHipProbeGrid *grid, const RtHipProbeUpdate *u)
+{
+  const uint64_t n = grid_probes(grid);
+  return {u->stride, u->phase, u->phase < n ? (uint32_t)((n - 1u - u->phase) / u->stride + 1u) : 0u};
+}
+
+/* a round's workspace: the bake's own for m probes, the depth bake's own (res 0: none), the m positions, the m status words */
+struct UpdateWorkspace
+{
+  size_t bake, depth, positions, status, total;
+  UpdateWorkspace(uint64_t m, uint64_t slice, uint32_t res)
+  {
+    bake = 0;
+    depth = bake + probe_workspace(m, RT_HIP_PROBE_SPHERE, slice).total;
+    positions = depth + (res ? DepthWorkspace(slice, m, res).total : 0u);
+    status = positions + stage_align(24u * m);
+    total = status + stage_align(4u * m);
+  }
+};
+
+/* the one layout of a round's workspace, for the size the caller asks and for the launch: slices never exceed the round's m x S rays
+ * (S unknown: the size is asked for slice_rays as given, which every part grows with) */
+UpdateWorkspace update_workspace(uint64_t m, uint64_t slice_rays, uint64_t samples, uint32_t res)
+{
+  return UpdateWorkspace(m, samples ? std::min<uint64_t>(slice_rays, m * samples) : slice_rays, res);
+}
+
+/* what rt_hip_probe_grid_update refuses without a device, but for its pointers */
+int check_grid_update(const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeParams *params, const RtHipProbeUpdate *upd,
+                      uint32_t slice_rays, const void *d_workspace)
+{
+  if (const int rc = check_update(upd))
+    return rc;
+  if (const int rc = check_grid_bake(grid, params))
+    return rc;
+  if (vis)
+    if (const int rc = check_vis(vis, grid_probes(grid)))
+      return rc;
+  for (int a = 0; a < 3; a++) /* (the positions grow along an axis: the last one finite, every one finite -- no ray of a round is invalid) */
+    if (!std::isfinite(grid->origin[a] + (double)(grid->count[a] - 1u) * grid->step[a]))
+      return fail(RT_HIP_EINVAL, "grid axis %d: the position of its last probe is not finite", a);
+  if (slice_rays == 0u)
+    return fail(RT_HIP_EINVAL, "slice_rays must be >= 1");
+  return check_slice_buffers(d_workspace, nullptr);
+}
+
+int coeff_blend_launch(const double *d_sum, int32_t samples, const PtProbeRound &R, const RtHipProbeUpdate *upd, const uint32_t *d_age,
+                       double *d_coeff, float *d_coeff_f, double *d_change, hipStream_t stream)
+{
+  const PtProbeCoeffBlend A = {R, d_sum, d_age, d_coeff, d_coeff_f, d_change, 1.0 / (double)samples, PT_PROBE_K_SPHERE, upd->hysteresis,
+                               upd->change, upd->fast};
+  return launched(probe_launch_coeff_blend(A, stream), "k_probe_coeff_blend");
+}
+
+int moment_blend_launch(const double *d_sums, const RtHipProbeVis *vis, const PtProbeRound &R, const RtHipProbeUpdate *upd,
+                        const uint32_t *d_age, double *d_moments, hipStream_t stream)
+{
+  const PtProbeMomentBlend A = {R, d_sums, d_age, d_moments, upd->hysteresis, vis->d_max, vis->res};
+  return launched(probe_launch_moment_blend(A, stream), "k_probe_moment_blend");
+}
+
+/* The round on `stream`, no host wait; R.m >= 1.  The two jobs run under a copy of the params with the round's seed and write their
+ * sums into their own parts of the workspace; the radiance job marks the round's status words (the depth job sees the same rays). */
+int grid_update_launch(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeParams *params,
+                       const RtHipProbeUpdate *upd, uint32_t slice_rays, void *d_workspace, double *d_coeff, float *d_coeff_f,
+                       double *d_moments, uint32_t *d_age, double *d_change, uint32_t *d_status, uint64_t *d_stats, hipStream_t stream)
+{
+  const PtProbeRound R = round_args(grid, upd);
+  RtHipProbeParams q = *params;
+  q.seed = rt_mix64(params->seed + (uint64_t)upd->round);
+  const uint64_t m = R.m, slice = std::min<uint64_t>(slice_rays, m * (uint64_t)q.samples);
+  const UpdateWorkspace W = update_workspace(m, slice_rays, (uint64_t)q.samples, vis ? vis->res : 0u);
+  char *const ws = static_cast<char *>(d_workspace);
+  double *const positions = reinterpret_cast<double *>(ws + W.positions);
+  uint32_t *const round_status = reinterpret_cast<uint32_t *>(ws + W.status);
+  double *const sum = reinterpret_cast<double *>(ws + W.bake + probe_workspace(m, RT_HIP_PROBE_SPHERE, slice).sum);
+  {
+    DeviceScope scope(scene->device);
+    HIP_TRY(scope.status);
+    if (const int rc = launched(probe_launch_grid_positions_strided(grid_args(grid), R, positions, stream), "k_probe_grid_positions_strided"))
+      return rc;
+  }
+  if (const int rc = bake_probes_launch(scene, positions, nullptr, m, &q, slice_rays, ws + W.bake, nullptr, nullptr, nullptr, round_status, d_stats,
+                                        stream))
+    return rc;
+  if (vis)
+    if (const int rc = bake_probe_depth_launch(scene, positions, m, vis, &q, slice_rays, ws + W.depth, nullptr, nullptr, stream))
+      return rc;
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  if (const int rc = coeff_blend_launch(sum, q.samples, R, upd, d_age, d_coeff, d_coeff_f, d_change, stream))
+    return rc;
+  if (vis)
+  {
+    const double *const sums = reinterpret_cast<const double *>(ws + W.depth + DepthWorkspace(slice, m, vis->res).sum);
+    if (const int rc = moment_blend_launch(sums, vis, R, upd, d_age, d_moments, stream))
+      return rc;
+  }
+  return launched(probe_launch_age_step(R, d_age, round_status, d_status, stream), "k_probe_age_step");
+}
+
+/* rt_hip_probe_grid_update_host: a scene of its own on the logical device, one allocation for the workspace, the state and the
+ * counters, the round on the null stream, the copies, the device's status word */
+int grid_update_host_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, const RtHipProbeGrid *grid,
+                          const RtHipProbeVis *vis, const RtHipProbeParams *params, const RtHipProbeUpdate *upd, int device, double *h_coeff,
+                          float *h_coeff_f, double *h_moments, uint32_t *h_age, double *h_change, uint32_t *h_status, uint64_t *h_stats)
+{
+  if (const int rc = check_grid_update(grid, vis, params, upd, HOST_SLICE, nullptr))
+    return rc;
+  if (!h_coeff || !h_age)
+    return fail(RT_HIP_EINVAL, "h_coeff and h_age are required");
+  if ((vis != nullptr) != (h_moments != nullptr))
+    return fail(RT_HIP_EINVAL, "vis and h_moments go together");
+  const PtProbeRound R = round_args(grid, upd);
+  if (R.m == 0u)
+    return RT_HIP_OK; /* (no probe in the round: nothing to do, on any device or none) */
+  return with_owned_scene(spheres, n_spheres, meshes, n_meshes, device, [&](const RtHipScene *scene, int phys) {
+    const uint64_t n = grid_probes(grid);
+    const uint32_t res = vis ? vis->res : 0u;
+    StageArena A;
+    const int ws = A.part(update_workspace(R.m, HOST_SLICE, (uint64_t)params->samples, res).total);
+    const int coeff = A.part(24u * PT_PROBE_SH * n, h_coeff, h_coeff);
+    const int coeff_f = A.part(12u * PT_PROBE_SH * n, h_coeff_f, h_coeff_f, h_coeff_f != nullptr);
+    const int moments = A.part(16u * n * res * res, h_moments, h_moments, vis != nullptr);
+    const int age = A.part(4u * n, h_age, h_age);
+    const int change = A.part(8u * n, h_change, h_change, h_change != nullptr);
+    const int status = A.part(4u * n, h_status, h_status, h_status != nullptr);
+    const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
+    int rc = A.stage();
+    if (rc)
+      return rc;
+    rc = grid_update_launch(scene, grid, vis, params, upd, HOST_SLICE, A.at<char>(ws), A.at<double>(coeff), A.at<float>(coeff_f),
+                            A.at<double>(moments), A.at<uint32_t>(age), A.at<double>(change), A.at<uint32_t>(status), A.at<uint64_t>(stats),
+                            nullptr);
+    return rc ? rc : download_then_status(A, phys);
+  });
+}
+
+/* rt_hip_probe_update_preview_scene_image: on a scene the caller holds, on that scene's device: one allocation for both workspaces,
+ * the state, the frame and the counters; the round and the preview lit by the state it leaves on the null stream, the copies, the
+ * device's status word */
+int update_preview_scene_image_impl(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                                    const RtHipProbeParams *params, const RtHipProbeUpdate *upd, int32_t width, int32_t height,
+                                    int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8, double *h_coeff, double *h_moments, uint32_t *h_age,
+                                    uint64_t *h_stats)
+{
+  if (const int rc = check_grid_update(grid, vis, params, upd, HOST_SLICE, nullptr))
+    return rc;
+  if (const int rc = check_preview(camera, grid, width, height, aov_samples))
+    return rc;
+  if (!h_rgb && !h_rgb8)
+    return fail(RT_HIP_EINVAL, "one of h_rgb and h_rgb8 is required");
+  if (!scene || !h_coeff || !h_age)
+    return fail(RT_HIP_EINVAL, "scene, h_coeff and h_age are required");
+  if ((vis != nullptr) != (h_moments != nullptr))
+    return fail(RT_HIP_EINVAL, "vis and h_moments go together");
+  DeviceScope scope(scene->device);
+  HIP_TRY(scope.status);
+  const PtProbeRound R = round_args(grid, upd);
+  const uint64_t n_probes = grid_probes(grid), n = (uint64_t)width * (uint64_t)height;
+  const uint32_t res = vis ? vis->res : 0u;
+  StageArena A;
+  const int update_ws = A.part(update_workspace(R.m, HOST_SLICE, (uint64_t)params->samples, res).total);
+  const int ws = A.part(PreviewWorkspace(n, frame_tile_pixels(width, height)).total);
+  const int coeff = A.part(24u * PT_PROBE_SH * n_probes, h_coeff, h_coeff);
+  const int moments = A.part(16u * n_probes * res * res, h_moments, h_moments, vis != nullptr);
+  const int age = A.part(4u * n_probes, h_age, h_age);
+  const int rgb = A.part(12u * n, nullptr, h_rgb);
+  const int rgb8 = A.part(3u * n, nullptr, h_rgb8, h_rgb8 != nullptr);
+  const int stats = A.zeroed(RT_HIP_NSTATS * sizeof(uint64_t), h_stats);
+  int rc = A.stage();
+  if (rc)
+    return rc;
+  if (R.m != 0u)
+    rc = grid_update_launch(scene, grid, vis, params, upd, HOST_SLICE, A.at<char>(update_ws), A.at<double>(coeff), nullptr, A.at<double>(moments),
+                            A.at<uint32_t>(age), nullptr, nullptr, A.at<uint64_t>(stats), nullptr);
+  if (!rc)
+    rc = probe_preview_launch(scene, camera, grid, A.at<double>(coeff), width, height, aov_samples, params->seed, A.at<char>(ws), A.at<float>(rgb),
+                              A.at<uint8_t>(rgb8), nullptr, vis, A.at<double>(moments));
+  return rc ? rc : download_then_status(A, scene->device);
 }
 
 /* ---- pixel refinement (rt_hip.h, rt_hip_select_pixels / _trace_pixels / _blend_pixels) ---------------------------------------
@@ -6267,6 +6477,132 @@ int rt_hip_probe_preview_vis_image(const RtHipSphere *spheres, size_t n_spheres,
       return preview_vis_image_of(scene, phys, camera, grid, vis, probe_params, width, height, aov_samples, h_rgb, h_rgb8, h_coeff, h_moments,
                                   h_stats);
     });
+  });
+}
+
+void rt_hip_probe_update_defaults(RtHipProbeUpdate *upd)
+{
+  if (!upd)
+    return;
+  memset(upd, 0, sizeof *upd);
+  upd->struct_size = (uint32_t)sizeof *upd;
+  upd->stride = 1u;
+  upd->hysteresis = 0.9;
+}
+
+uint64_t rt_hip_probe_update_count(const RtHipProbeGrid *grid, const RtHipProbeUpdate *upd)
+{
+  if (check_grid(grid) || check_update(upd))
+    return 0;
+  return round_args(grid, upd).m;
+}
+
+size_t rt_hip_probe_update_workspace_bytes(const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeUpdate *upd,
+                                           uint32_t slice_rays)
+{
+  if (slice_rays == 0u || check_grid(grid) || check_update(upd) || (vis && check_vis(vis, grid_probes(grid))))
+    return 0;
+  return update_workspace(round_args(grid, upd).m, slice_rays, 0u, vis ? vis->res : 0u).total;
+}
+
+int rt_hip_probe_grid_update(const RtHipScene *scene, const RtHipProbeGrid *grid, const RtHipProbeVis *vis,
+                             const RtHipProbeParams *probe_params, const RtHipProbeUpdate *upd, uint32_t slice_rays, void *d_workspace,
+                             double *d_coeff, float *d_coeff_f, double *d_moments, uint32_t *d_age, double *d_change, uint32_t *d_status,
+                             uint64_t *d_stats, void *stream)
+{
+  if (const int rc = check_grid_update(grid, vis, probe_params, upd, slice_rays, d_workspace))
+    return rc;
+  if ((vis != nullptr) != (d_moments != nullptr))
+    return fail(RT_HIP_EINVAL, "vis and d_moments go together");
+  if (!scene || !d_workspace || !d_coeff || !d_age)
+    return fail(RT_HIP_EINVAL, "scene, d_workspace, d_coeff and d_age are required");
+  if (reinterpret_cast<uintptr_t>(d_moments) & 15u) /* (the moment blend moves a pair as 16 bytes) */
+    return fail(RT_HIP_EINVAL, "d_moments must be 16-byte aligned");
+  if (round_args(grid, upd).m == 0u)
+    return RT_HIP_OK;
+  return guarded("rt_hip_probe_grid_update", [&] {
+    return grid_update_launch(scene, grid, vis, probe_params, upd, slice_rays, d_workspace, d_coeff, d_coeff_f, d_moments, d_age, d_change,
+                              d_status, d_stats, static_cast<hipStream_t>(stream));
+  });
+}
+
+int rt_hip_probe_blend_coeff(const double *d_sum, int32_t samples, const RtHipProbeGrid *grid, const RtHipProbeUpdate *upd,
+                             const uint32_t *d_age, double *d_coeff, float *d_coeff_f, double *d_change, void *stream)
+{
+  if (const int rc = check_grid(grid))
+    return rc;
+  if (const int rc = check_update(upd))
+    return rc;
+  if (samples < 1)
+    return fail(RT_HIP_EINVAL, "samples = %d must be >= 1", samples);
+  if (!d_age || !d_coeff)
+    return fail(RT_HIP_EINVAL, "d_age and d_coeff are required");
+  const PtProbeRound R = round_args(grid, upd);
+  if (R.m == 0u)
+    return RT_HIP_OK;
+  if (!d_sum)
+    return fail(RT_HIP_EINVAL, "d_sum is required");
+  return on_device_of(d_age, "d_age",
+                      [&] { return coeff_blend_launch(d_sum, samples, R, upd, d_age, d_coeff, d_coeff_f, d_change, static_cast<hipStream_t>(stream)); });
+}
+
+int rt_hip_probe_blend_moments(const double *d_sums, const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeUpdate *upd,
+                               const uint32_t *d_age, double *d_moments, void *stream)
+{
+  if (const int rc = check_grid(grid))
+    return rc;
+  if (const int rc = check_update(upd))
+    return rc;
+  if (const int rc = check_vis(vis, grid_probes(grid)))
+    return rc;
+  if (!d_age || !d_moments)
+    return fail(RT_HIP_EINVAL, "d_age and d_moments are required");
+  if (reinterpret_cast<uintptr_t>(d_moments) & 15u)
+    return fail(RT_HIP_EINVAL, "d_moments must be 16-byte aligned");
+  const PtProbeRound R = round_args(grid, upd);
+  if (R.m == 0u)
+    return RT_HIP_OK;
+  if (!d_sums)
+    return fail(RT_HIP_EINVAL, "d_sums is required");
+  return on_device_of(d_age, "d_age",
+                      [&] { return moment_blend_launch(d_sums, vis, R, upd, d_age, d_moments, static_cast<hipStream_t>(stream)); });
+}
+
+int rt_hip_probe_age_step(const RtHipProbeGrid *grid, const RtHipProbeUpdate *upd, uint32_t *d_age, void *stream)
+{
+  if (const int rc = check_grid(grid))
+    return rc;
+  if (const int rc = check_update(upd))
+    return rc;
+  if (!d_age)
+    return fail(RT_HIP_EINVAL, "d_age is required");
+  const PtProbeRound R = round_args(grid, upd);
+  if (R.m == 0u)
+    return RT_HIP_OK;
+  return on_device_of(d_age, "d_age", [&] {
+    return launched(probe_launch_age_step(R, d_age, nullptr, nullptr, static_cast<hipStream_t>(stream)), "k_probe_age_step");
+  });
+}
+
+int rt_hip_probe_grid_update_host(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes,
+                                  const RtHipProbeGrid *grid, const RtHipProbeVis *vis, const RtHipProbeParams *probe_params,
+                                  const RtHipProbeUpdate *upd, int device, double *h_coeff, float *h_coeff_f, double *h_moments,
+                                  uint32_t *h_age, double *h_change, uint32_t *h_status, uint64_t *h_stats)
+{
+  return guarded("rt_hip_probe_grid_update_host", [&] {
+    return grid_update_host_impl(spheres, n_spheres, meshes, n_meshes, grid, vis, probe_params, upd, device, h_coeff, h_coeff_f, h_moments,
+                                 h_age, h_change, h_status, h_stats);
+  });
+}
+
+int rt_hip_probe_update_preview_scene_image(const RtHipScene *scene, const RtHipCamera *camera, const RtHipProbeGrid *grid,
+                                            const RtHipProbeVis *vis, const RtHipProbeParams *probe_params, const RtHipProbeUpdate *upd,
+                                            int32_t width, int32_t height, int32_t aov_samples, float *h_rgb, uint8_t *h_rgb8, double *h_coeff,
+                                            double *h_moments, uint32_t *h_age, uint64_t *h_stats)
+{
+  return guarded("rt_hip_probe_update_preview_scene_image", [&] {
+    return update_preview_scene_image_impl(scene, camera, grid, vis, probe_params, upd, width, height, aov_samples, h_rgb, h_rgb8, h_coeff,
+                                           h_moments, h_age, h_stats);
   });
 }
 

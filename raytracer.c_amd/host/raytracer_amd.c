@@ -332,6 +332,218 @@ static int probe_grid_over(const RtHipScene *scene, RtHipProbeGrid *grid, RtHipP
   return RT_HIP_OK;
 }
 
+/* ---- rt_set_probe_update: the scene and the grid's state that render_ex() keeps between calls -------------------------------------- */
+static int g_probe_update_rays = 0;
+static double g_probe_update_hysteresis = 0.9;
+void rt_set_probe_update(int rays, double hysteresis)
+{
+  if (hysteresis >= 0 && hysteresis < 1)
+    g_probe_update_hysteresis = hysteresis;
+  g_probe_update_rays = rays > 0 ? rays : 0;
+}
+void rt_get_probe_update(int *rays, double *hysteresis)
+{
+  if (rays)
+    *rays = g_probe_update_rays;
+  if (hysteresis)
+    *hysteresis = g_probe_update_hysteresis;
+}
+
+/* the scene of the previous call with deep copies of what it was made from, and the state of the grid derived from it */
+static struct
+{
+  RtHipScene *scene;
+  Object *objects;
+  MeshObject *meshes; /* (each mesh.vertices is a copy of its own) */
+  size_t n_objects, n_meshes;
+  RtHipProbeGrid grid;
+  int res, have_state;
+  uint32_t round;
+  double *coeff, *moments;
+  uint32_t *age;
+} g_kept;
+
+static void kept_drop_state(void)
+{
+  free(g_kept.coeff);
+  free(g_kept.moments);
+  free(g_kept.age);
+  g_kept.coeff = g_kept.moments = NULL;
+  g_kept.age = NULL;
+  g_kept.have_state = 0;
+}
+
+static void kept_drop(void)
+{
+  kept_drop_state();
+  if (g_kept.scene)
+    rt_hip_scene_destroy(g_kept.scene);
+  for (size_t m = 0; m < g_kept.n_meshes; m++)
+    free(g_kept.meshes[m].mesh.vertices);
+  free(g_kept.meshes);
+  free(g_kept.objects);
+  memset(&g_kept, 0, sizeof g_kept);
+}
+
+/* does the call's scene equal the kept one but for sphere centres and radii and vertex positions? */
+static int kept_matches(const Object *objects, size_t n_objects, const MeshObject *meshes, size_t n_meshes)
+{
+  if (!g_kept.scene || n_objects != g_kept.n_objects || n_meshes != g_kept.n_meshes)
+    return 0;
+  for (size_t i = 0; i < n_objects; i++)
+    if (objects[i].flags != g_kept.objects[i].flags || memcmp(&objects[i].color, &g_kept.objects[i].color, sizeof(vec3)) != 0 ||
+        memcmp(&objects[i].emission, &g_kept.objects[i].emission, sizeof(vec3)) != 0)
+      return 0;
+  for (size_t m = 0; m < n_meshes; m++)
+  {
+    const MeshObject *a = &meshes[m], *b = &g_kept.meshes[m];
+    if (a->flags != b->flags || memcmp(&a->color, &b->color, sizeof(vec3)) != 0 || memcmp(&a->emission, &b->emission, sizeof(vec3)) != 0 ||
+        a->mesh.num_triangles != b->mesh.num_triangles)
+      return 0;
+    for (size_t k = 0; k < 3 * (size_t)a->mesh.num_triangles; k++)
+      if (memcmp(&a->mesh.vertices[k].tex, &b->mesh.vertices[k].tex, sizeof(vec2)) != 0)
+        return 0;
+  }
+  return 1;
+}
+
+/* deep copies of the call's scene into g_kept (the scene handle apart); 0 when out of memory */
+static int kept_copy(const Object *objects, size_t n_objects, const MeshObject *meshes, size_t n_meshes)
+{
+  g_kept.objects = (Object *)malloc(sizeof(Object) * (n_objects ? n_objects : 1));
+  g_kept.meshes = (MeshObject *)calloc(n_meshes ? n_meshes : 1, sizeof(MeshObject));
+  if (!g_kept.objects || !g_kept.meshes)
+    return 0;
+  memcpy(g_kept.objects, objects, sizeof(Object) * n_objects);
+  g_kept.n_objects = n_objects;
+  for (size_t m = 0; m < n_meshes; m++)
+  {
+    const size_t bytes = sizeof(Vertex) * 3 * (size_t)meshes[m].mesh.num_triangles;
+    g_kept.meshes[m] = meshes[m];
+    g_kept.meshes[m].mesh.vertices = (Vertex *)malloc(bytes ? bytes : 1);
+    g_kept.n_meshes = m + 1;
+    if (!g_kept.meshes[m].mesh.vertices)
+      return 0;
+    memcpy(g_kept.meshes[m].mesh.vertices, meshes[m].mesh.vertices, bytes);
+  }
+  return 1;
+}
+
+/* the kept scene takes the call's centres, radii and positions in place (rt_hip_scene_update_*_host), and so do the copies */
+static int kept_take(const Object *objects, size_t n_objects, const MeshObject *meshes, size_t n_meshes)
+{
+  int rc = RT_HIP_OK;
+  size_t n_tri = 0;
+  for (size_t m = 0; m < n_meshes; m++)
+    n_tri += (size_t)meshes[m].mesh.num_triangles;
+  double *buf = (double *)malloc(sizeof(double) * (4 * n_objects + 9 * n_tri + 1));
+  if (!buf)
+    return RT_HIP_ENOMEM;
+  if (n_objects)
+  {
+    for (size_t i = 0; i < n_objects; i++)
+    {
+      memcpy(buf + 4 * i, &objects[i].center, sizeof(vec3));
+      buf[4 * i + 3] = objects[i].radius;
+    }
+    rc = rt_hip_scene_update_spheres_host(g_kept.scene, buf, n_objects);
+  }
+  if (!rc && n_tri)
+  {
+    double *pos = buf + 4 * n_objects;
+    size_t at = 0;
+    for (size_t m = 0; m < n_meshes; m++)
+      for (size_t k = 0; k < 3 * (size_t)meshes[m].mesh.num_triangles; k++, at += 3)
+        memcpy(pos + at, &meshes[m].mesh.vertices[k].pos, sizeof(vec3));
+    rc = rt_hip_scene_update_vertices_host(g_kept.scene, pos, n_tri);
+  }
+  free(buf);
+  if (!rc)
+  {
+    memcpy(g_kept.objects, objects, sizeof(Object) * n_objects);
+    for (size_t m = 0; m < n_meshes; m++)
+      memcpy(g_kept.meshes[m].mesh.vertices, meshes[m].mesh.vertices, sizeof(Vertex) * 3 * (size_t)meshes[m].mesh.num_triangles);
+  }
+  return rc;
+}
+
+/* render_ex()'s probe-lit frame under rt_set_probe_update: the kept scene where the call's scene matches it, else a new one that is
+ * kept; one round and the preview where the derived grid is the previous call's too, else the full bake, whose state is kept */
+static int render_probe_following(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects, MeshObject *meshes,
+                                  size_t n_meshes, const RtHipMesh *hm, Camera *camera, const RtHipParams *p, uint64_t *stats)
+{
+  int rc, same_scene = kept_matches(objects, n_objects, meshes, n_meshes);
+  if (same_scene && kept_take(objects, n_objects, meshes, n_meshes) != RT_HIP_OK)
+    same_scene = 0; /* (an update the scene refuses: start over) */
+  if (!same_scene)
+  {
+    kept_drop();
+    rc = rt_hip_scene_create((const RtHipSphere *)objects, n_objects, hm, n_meshes, 0, &g_kept.scene);
+    if (rc)
+      return rc;
+    if (!kept_copy(objects, n_objects, meshes, n_meshes))
+    {
+      kept_drop();
+      return RT_HIP_ENOMEM;
+    }
+  }
+  RtHipProbeGrid grid;
+  RtHipProbeParams pp;
+  RtHipProbeVis vis;
+  rc = probe_grid_over(g_kept.scene, &grid, &pp);
+  if (rc)
+    return rc;
+  pp.max_depth = p->max_depth;
+  pp.seed = p->seed;
+  rt_hip_probe_vis_defaults(&vis, &grid);
+  vis.res = (uint32_t)(g_probe_vis_res > 0 ? g_probe_vis_res : 2);
+  const RtHipProbeVis *v = g_probe_vis_res > 0 ? &vis : NULL;
+  if (same_scene && g_kept.have_state && g_kept.res == g_probe_vis_res &&
+      memcmp(grid.count, g_kept.grid.count, sizeof grid.count) == 0 && memcmp(grid.origin, g_kept.grid.origin, sizeof grid.origin) == 0 &&
+      memcmp(grid.step, g_kept.grid.step, sizeof grid.step) == 0) /* (the same counts and the same reach) */
+  {
+    RtHipProbeUpdate upd;
+    rt_hip_probe_update_defaults(&upd);
+    upd.hysteresis = g_probe_update_hysteresis;
+    upd.round = ++g_kept.round;
+    pp.samples = g_probe_update_rays;
+    rc = rt_hip_probe_update_preview_scene_image(g_kept.scene, (const RtHipCamera *)camera, &grid, v, &pp, &upd, p->width, p->height, 1,
+                                                 linear_rgb, framebuffer, g_kept.coeff, v ? g_kept.moments : NULL, g_kept.age, stats);
+    if (rc)
+      kept_drop();
+    return rc;
+  }
+  kept_drop_state();
+  const size_t n = (size_t)grid.count[0] * grid.count[1] * grid.count[2], texels = (size_t)vis.res * vis.res;
+  g_kept.coeff = (double *)malloc(sizeof(double) * 27 * n);
+  g_kept.moments = (double *)malloc(sizeof(double) * 2 * texels * n);
+  g_kept.age = (uint32_t *)malloc(sizeof(uint32_t) * n);
+  if (!g_kept.coeff || !g_kept.moments || !g_kept.age)
+  {
+    kept_drop();
+    return RT_HIP_ENOMEM;
+  }
+  pp.samples = p->samples;
+  if (v)
+    rc = rt_hip_probe_preview_vis_scene_image(g_kept.scene, (const RtHipCamera *)camera, &grid, v, &pp, p->width, p->height, 1, linear_rgb,
+                                              framebuffer, g_kept.coeff, g_kept.moments, stats);
+  else
+    rc = rt_hip_probe_preview_scene_image(g_kept.scene, (const RtHipCamera *)camera, &grid, &pp, p->width, p->height, 1, linear_rgb, framebuffer,
+                                          g_kept.coeff, stats);
+  if (rc)
+  {
+    kept_drop();
+    return rc;
+  }
+  for (size_t i = 0; i < n; i++)
+    g_kept.age[i] = 1u; /* the bake stands for one round */
+  g_kept.grid = grid;
+  g_kept.res = g_probe_vis_res;
+  g_kept.round = 0;
+  g_kept.have_state = 1;
+  return RT_HIP_OK;
+}
+
 void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects,
                MeshObject *meshes, size_t n_meshes, Camera *camera, Options *options)
 {
@@ -341,7 +553,18 @@ void render_ex(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t 
   uint64_t stats[RT_HIP_NSTATS] = {0, 0, 0, 0};
   double seconds = 0;
   int rc;
-  if (g_probe_grid[0] > 0)
+  const int following = g_probe_grid[0] > 0 && g_probe_update_rays > 0 && g_scene_updates;
+  if (!following)
+    kept_drop(); /* (a frame of any other kind keeps nothing) */
+  if (following)
+  { /* the probe-lit preview with the scene and the grid's state kept between calls (rt_set_probe_update) */
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    rc = render_probe_following(framebuffer, linear_rgb, objects, n_objects, meshes, n_meshes, hm, camera, &p, stats);
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    seconds = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+  }
+  else if (g_probe_grid[0] > 0)
   { /* the probe-lit preview on ONE scene: a grid over its bounds, options->samples rays a probe, one first-hit sample a pixel */
     RtHipScene *scene = NULL;
     RtHipProbeGrid grid;

@@ -170,6 +170,11 @@ class RtHipProbeVis(C.Structure):  # rt_hip.h: a grid's depth-moment visibility 
                 ("bias", C.c_double), ("floor", C.c_double), ("reserved", C.c_uint64)]
 
 
+class RtHipProbeUpdate(C.Structure):  # rt_hip.h: an update round of a grid's state (rt_hip_probe_update_defaults), 48 B
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("stride", C.c_uint32), ("phase", C.c_uint32), ("round", C.c_uint32),
+                ("reserved", C.c_uint32), ("hysteresis", C.c_double), ("change", C.c_double), ("fast", C.c_double)]
+
+
 class RtHipPixelParams(C.Structure):  # rt_hip.h: a pixel refinement's trace (rt_hip_pixel_defaults), 32 B
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("sample_first", C.c_int32),
                 ("max_depth", C.c_int32), ("integrator", C.c_uint32), ("seed", C.c_uint64)]
@@ -364,6 +369,24 @@ SHIM_SYMBOLS = {
     "rt_hip_probe_preview_vis_scene_image": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis),
                                                        C.POINTER(RtHipProbeParams), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_update_defaults": (None, [C.POINTER(RtHipProbeUpdate)]),
+    "rt_hip_probe_update_count": (C.c_uint64, [C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeUpdate)]),
+    "rt_hip_probe_update_workspace_bytes": (C.c_size_t, [C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis), C.POINTER(RtHipProbeUpdate),
+                                                         C.c_uint32]),
+    "rt_hip_probe_grid_update": (C.c_int, [C.c_void_p, C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis), C.POINTER(RtHipProbeParams),
+                                           C.POINTER(RtHipProbeUpdate), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_blend_coeff": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeUpdate), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_blend_moments": (C.c_int, [C.c_void_p, C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis), C.POINTER(RtHipProbeUpdate),
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_age_step": (C.c_int, [C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeUpdate), C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_grid_update_host": (C.c_int, [C.POINTER(Object), C.c_size_t, C.POINTER(RtHipMesh), C.c_size_t, C.POINTER(RtHipProbeGrid),
+                                                C.POINTER(RtHipProbeVis), C.POINTER(RtHipProbeParams), C.POINTER(RtHipProbeUpdate), C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_probe_update_preview_scene_image": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RtHipProbeGrid), C.POINTER(RtHipProbeVis),
+                                                          C.POINTER(RtHipProbeParams), C.POINTER(RtHipProbeUpdate), C.c_int32, C.c_int32,
+                                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_denoise_defaults": (None, [C.POINTER(RtHipDenoiseParams)]),
     "rt_hip_denoise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rt_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtHipAov), C.c_int32, C.c_int32, C.POINTER(RtHipDenoiseParams), C.c_void_p,
@@ -436,6 +459,8 @@ HOST_SYMBOLS = {
     "rt_get_lens": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_set_probe_grid": (None, [C.c_int, C.c_int, C.c_int]),
     "rt_get_probe_grid": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rt_set_probe_update": (None, [C.c_int, C.c_double]),
+    "rt_get_probe_update": (None, [C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "rt_set_probe_visibility": (None, [C.c_int]),
     "rt_get_probe_visibility": (C.c_int, []),
     "rt_set_integrator": (None, [C.c_int]),
@@ -574,6 +599,16 @@ def probe_vis(grid, res=None, sharp=None, d_max=None, bias=None, floor=None):
         if x is not None:
             setattr(v, f, x)
     return v
+
+
+def probe_update(stride=None, phase=None, round=None, hysteresis=None, change=None, fast=None):
+    """rt_hip_probe_update_defaults() with the given fields replaced (None: the default)"""
+    u = RtHipProbeUpdate()
+    load_shim().rt_hip_probe_update_defaults(C.byref(u))
+    for f, x in (("stride", stride), ("phase", phase), ("round", round), ("hysteresis", hysteresis), ("change", change), ("fast", fast)):
+        if x is not None:
+            setattr(u, f, x)
+    return u
 
 
 def reproject_params(max_history=None, depth_tol=None, normal_min=None):

@@ -771,6 +771,40 @@ class GpuScene:
                                               seed, _ptr(ws), _ptr(rgb), _ptr(rgb8), _stream(dev)), "rt_hip_probe_preview")
         return rgb, rgb8
 
+    def probe_grid_update(self, grid, upd, samples, seed, coeff, age, vis=None, moments=None, coeff_f=None, change=None, status=None,
+                          max_depth=None, origin_radius=None, slice_rays=None, stats=None):
+        """One update round of a grid's state in place (rt_hip.h, rt_hip_probe_grid_update): `samples` fresh rays for each of the
+        round's probes (upd: abi.probe_update(...)), blended into coeff float64 [N, 9, 3] and -- with vis -- moments float64
+        [N, R*R, 2] by each probe's age int32 [N], which steps; coeff_f float32, change float64 [N] and status int32 [N] are written
+        where given.  Device tensors, asynchronous on torch's current stream -> the counters int64 [4].  No output bit depends on
+        origin_radius or slice_rays."""
+        dev, n = self.dev, _grid_count(grid)
+        if (vis is None) != (moments is None):
+            raise ValueError("probe_grid_update: vis and moments go together")
+        for name, t, dt, k in (("coeff", coeff, torch.float64, 27 * n), ("age", age, torch.int32, n), ("coeff_f", coeff_f, torch.float32, 27 * n),
+                               ("moments", moments, torch.float64, 0 if vis is None else 2 * n * vis.res * vis.res),
+                               ("change", change, torch.float64, n), ("status", status, torch.int32, n)):
+            if t is not None and not _is(t, dev, k, dt):
+                raise ValueError(f"probe_grid_update: {name} must be a contiguous {dt} tensor of {k} values on the scene's device")
+        p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, _depth(self.scene, max_depth), 0.0,
+                             _grid_radius(grid) if origin_radius is None else origin_radius)
+        m = self.shim.rt_hip_probe_update_count(C.byref(grid), C.byref(upd))
+        slice_rays, launch = _slices(m, samples, slice_rays)
+        v = None if vis is None else C.byref(vis)
+        ws = _workspace(self.shim.rt_hip_probe_update_workspace_bytes(C.byref(grid), v, C.byref(upd), launch), dev)
+        stats = _counters(dev, stats)
+        self._update_buffers = (ws,)   # keep alive until the stream has used them
+        _check(self.shim.rt_hip_probe_grid_update(self.handle, C.byref(grid), v, C.byref(p), C.byref(upd), slice_rays, _ptr(ws), _ptr(coeff),
+                                                  _ptr(coeff_f), _ptr(moments), _ptr(age), _ptr(change), _ptr(status), _ptr(stats), _stream(dev)),
+               "rt_hip_probe_grid_update")
+        return stats
+
+    def probe_grid_state(self, grid, samples, seed, vis=None, hysteresis=0.9, stride=1, change=0.0, fast=0.0):
+        """A grid's state that follows the scene (ProbeGridState): every age 0, nothing traced yet; .update() runs rounds of
+        `samples` rays a probe under `seed`.  The state lives beside the scene, not in it: it survives update_spheres,
+        update_vertices and rebuild_bvh."""
+        return ProbeGridState(self, grid, samples, seed, vis, hysteresis, stride, change, fast)
+
     def render_panorama(self, width, height, origin, samples, seed, max_depth=None):
         """An equirectangular view from `origin` (scene.panorama_rays: no Camera expresses it), `samples` paths per pixel, pixel
         k = y * width + x on the stream (seed, k, s) -> (float64 [height, width, 3] linear radiance on the device, stats)"""
@@ -828,6 +862,44 @@ class GpuScene:
         self.launch_status()   # a workgroup without its pool slot fails the frame here, not as NaN pixels
         st = stats.cpu().tolist()
         return image, image8, _stats_dict(st)
+
+
+class ProbeGridState:
+    """The coefficients (coeff float64 [N, 9, 3], coeff_f float32), depth moments (moments float64 [N, R*R, 2], with a vis), ages
+    (age int32 [N]), last relative changes (change float64 [N]) and status words (status int32 [N]) of a grid on the scene's device,
+    and the number of rounds run (round).  GpuScene.probe_grid_state() makes one."""
+
+    def __init__(self, gs, grid, samples, seed, vis, hysteresis, stride, change, fast):
+        dev, n = gs.dev, _grid_count(grid)
+        self.gs, self.grid, self.vis, self.samples, self.seed = gs, grid, vis, samples, seed
+        self.hysteresis, self.stride, self.change_limit, self.fast = hysteresis, stride, change, fast
+        self.round = 0
+        self.coeff = torch.zeros((n, 9, 3), dtype=torch.float64, device=dev)
+        self.coeff_f = torch.zeros((n, 9, 3), dtype=torch.float32, device=dev)
+        self.moments = None if vis is None else torch.zeros((n, vis.res * vis.res, 2), dtype=torch.float64, device=dev)
+        self.age = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.change = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.status = torch.ones(n, dtype=torch.int32, device=dev)
+        self.stats = _counters(dev)
+
+    def update(self, rounds=1, slice_rays=None):
+        """`rounds` update rounds: round u updates the probes of phase u % stride under the seed of round u; asynchronous"""
+        for _ in range(rounds):
+            upd = abi.probe_update(self.stride, self.round % self.stride, self.round & 0xFFFFFFFF, self.hysteresis, self.change_limit,
+                                   self.fast)
+            self.gs.probe_grid_update(self.grid, upd, self.samples, self.seed, self.coeff, self.age, self.vis, self.moments, self.coeff_f,
+                                      self.change, self.status, slice_rays=slice_rays, stats=self.stats)
+            self.round += 1
+        return self
+
+    def reset(self):
+        """every probe starts over with its next round: the ages become 0 (the rest of the state is not read again)"""
+        self.age.zero_()
+        return self
+
+    def preview(self, camera=None, aov_samples=1):
+        """GpuScene.probe_preview lit by the state as it stands"""
+        return self.gs.probe_preview(self.grid, self.coeff, camera, aov_samples, self.seed, self.vis, self.moments)
 
 
 class Accumulation:
@@ -1671,6 +1743,54 @@ def probe_shade(grid, coeff, points, normals, status=None, albedo=None, add=None
     _check(shim.rt_hip_probe_shade(C.byref(grid), _some(coeff), _some(pts), _some(nrm), _some(st), _some(alb), _some(ad), n if m is None else m,
                                    *outs), "rt_hip_probe_shade")
     return {f: res[f] for f in want}
+
+
+def _round_count(grid, upd):
+    return abi.load_shim().rt_hip_probe_update_count(C.byref(grid), C.byref(upd))
+
+
+def probe_blend_coeff(total, samples, grid, upd, age, coeff, coeff_f=None, change=None):
+    """The coefficient blend of an update round alone (rt_hip.h, rt_hip_probe_blend_coeff): total float64 [M, 9, 3], the fresh sums
+    of the round's M probes in their order, blended in place into coeff float64 [N, 9, 3] (coeff_f float32 and change float64 [N]
+    where given) by age int32 [N]; device tensors, asynchronous on torch's current stream"""
+    dev = age.device
+    total = torch.as_tensor(total, dtype=torch.float64, device=dev).contiguous()
+    if total.numel() != 27 * _round_count(grid, upd):
+        raise ValueError("probe_blend_coeff: total must hold 9 x 3 values per probe of the round")
+    _check(abi.load_shim().rt_hip_probe_blend_coeff(_some(total), samples, C.byref(grid), C.byref(upd), _ptr(age), _ptr(coeff), _ptr(coeff_f),
+                                                    _ptr(change), _stream(dev)), "rt_hip_probe_blend_coeff")
+
+
+def probe_blend_moments(sums, grid, vis, upd, age, moments):
+    """The moment blend of an update round alone (rt_hip.h, rt_hip_probe_blend_moments): sums float64 [M, R*R, 3] (W, M1, M2 a texel)
+    of the round's M probes, blended in place into moments float64 [N, R*R, 2] by age int32 [N]; device tensors, asynchronous"""
+    dev = age.device
+    sums = torch.as_tensor(sums, dtype=torch.float64, device=dev).contiguous()
+    if sums.numel() != 3 * vis.res * vis.res * _round_count(grid, upd):
+        raise ValueError("probe_blend_moments: sums must hold R x R x 3 values per probe of the round")
+    _check(abi.load_shim().rt_hip_probe_blend_moments(_some(sums), C.byref(grid), C.byref(vis), C.byref(upd), _ptr(age), _ptr(moments),
+                                                      _stream(dev)), "rt_hip_probe_blend_moments")
+
+
+def probe_age_step(grid, upd, age):
+    """The age step of an update round alone (rt_hip.h, rt_hip_probe_age_step) on age int32 [N], in place; asynchronous"""
+    _check(abi.load_shim().rt_hip_probe_age_step(C.byref(grid), C.byref(upd), _ptr(age), _stream(age.device)), "rt_hip_probe_age_step")
+
+
+def probe_update_host(scene, grid, upd, samples, seed, coeff, age, vis=None, moments=None, coeff_f=None, change=None, status=None,
+                      max_depth=None, origin_radius=None, device=0):
+    """rt_hip_probe_grid_update_host(): the C hosts' entry point (its own scene on logical device `device`, synchronous): one update
+    round on a state held in numpy arrays, in place -- coeff float64 [N, 9, 3], age uint32 [N], with vis moments float64 [N, R*R, 2];
+    coeff_f float32, change float64 [N] and status uint32 [N] where given -> stats dict"""
+    shim = abi.load_shim()
+    p = abi.probe_params(abi.PROBE_SPHERE, samples, seed, _depth(scene, max_depth), 0.0,
+                         _grid_radius(grid) if origin_radius is None else origin_radius)
+    stats = _host_counters()
+    at = lambda a: None if a is None else a.ctypes.data
+    _check(shim.rt_hip_probe_grid_update_host(*_host_scene(scene), C.byref(grid), None if vis is None else C.byref(vis), C.byref(p),
+                                              C.byref(upd), device, at(coeff), at(coeff_f), at(moments), at(age), at(change), at(status), stats),
+           "rt_hip_probe_grid_update_host")
+    return _stats_dict(stats)
 
 
 def probe_preview_host(scene, grid, samples, seed, camera=None, aov_samples=1, max_depth=None, origin_radius=None, device=0):
