@@ -26,7 +26,7 @@ SHIM    := $(CSRC)/librt_hip.so
 # the seven sources every build of the shim compiles, in this order
 SHIM_SRC := $(CSRC)/pt_kernel.hip $(CSRC)/rt_hip_shim.hip $(CSRC)/bvh_device.hip $(CSRC)/scene_update.hip $(CSRC)/lens.hip \
             $(CSRC)/image_ops.hip $(CSRC)/probe.hip
-KERNEL_SRC := $(SHIM_SRC) $(wildcard $(CSRC)/pt_*.h) $(CSRC)/bvh_build.h $(CSRC)/scene_spheres.h $(CSRC)/ray_store.h $(CSRC)/rt_staging.h $(INC)/rt_hip.h $(INC)/rt_rng.h
+KERNEL_SRC := $(SHIM_SRC) $(wildcard $(CSRC)/pt_*.h) $(CSRC)/bvh_build.h $(CSRC)/scene_spheres.h $(CSRC)/scene_materials.h $(CSRC)/ray_store.h $(CSRC)/rt_staging.h $(INC)/rt_hip.h $(INC)/rt_rng.h
 HOSTLIB := $(HOST)/libraytracer_amd.so
 CLI     := $(HOST)/raytracer
 

@@ -276,7 +276,8 @@ int rt_get_probe_visibility(void);
  * derives is the previous call's as well -- the same counts, the same reach, the same visibility resolution -- the frame is one
  * update round of `rays` rays a probe (stride 1, the hysteresis given, round 1, 2, ... counting up from the bake) and the preview lit
  * by the state (rt_hip_probe_update_preview_scene_image), instead of the full bake.  Anything else starts over with the full bake of
- * options->samples rays a probe, which leaves every age at 1: a first call, another scene, a changed reach or resolution.
+ * options->samples rays a probe, which leaves every age at 1: a first call, another scene (changed flags, colours or emission
+ * included, unless rt_set_material_updates(1) lets the kept scene take them in place), a changed reach or resolution.
  * rays <= 0 (the default) turns it off: render() is then bit for bit what it is without this call, and keeps nothing.  A hysteresis
  * outside [0, 1) leaves the setting as it was. */
 void rt_set_probe_update(int rays, double hysteresis);
@@ -299,6 +300,16 @@ int rt_get_bvh_builder(void);
  * frame per process and has no use for it. */
 void rt_set_scene_updates(int on);
 int rt_get_scene_updates(void);
+
+/* A lamp dimmed, a wall recoloured, a ball turned to glass.  on != 0: the scene of a render() call may also differ from the
+ * previous call's in flags, colours and emission (of objects and meshes): the scene kept on the GPU takes them in place (rt_hip.h,
+ * rt_hip_scene_update_materials_host: the material records and what the scene derives from them) instead of being rebuilt.
+ * Independent of rt_set_scene_updates: a call that changes materials and positions updates in place only where both are on.  Under
+ * rt_set_probe_update such a call runs one update round on the kept grid state (the state follows the new light by its hysteresis)
+ * instead of the full bake.  The frame of a plain render() is the one a rebuilt scene gives, bit for bit.  The default, 0: a changed
+ * material rebuilds the scene, and under rt_set_probe_update starts over with the full bake. */
+void rt_set_material_updates(int on);
+int rt_get_material_updates(void);
 
 /* Under rt_set_scene_updates(1) a refit keeps the hierarchy's topology, and the walks get dearer as the mesh leaves the shape the
  * tree was built for.  A ratio r >= 1 (finite) makes every frame that is taken as an in-place vertex update end with

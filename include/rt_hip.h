@@ -267,8 +267,8 @@ int rt_hip_scene_maintain_bvh(RtHipScene *scene, double max_ratio, double *cost_
  * The caller must not launch on the scene from another thread during the call; work submitted before it is waited for. */
 int rt_hip_scene_update_vertices(RtHipScene *scene, const double *d_positions, size_t n_triangles);
 int rt_hip_scene_update_vertices_host(RtHipScene *scene, const double *h_positions, size_t n_triangles);
-/* how many updates the scene has taken -- of either kind, vertices or spheres -- and the host-clock seconds of the last one; either
- * may be NULL */
+/* how many updates the scene has taken -- of any kind: vertices, spheres or materials -- and the host-clock seconds of the last
+ * one; either may be NULL */
 int rt_hip_scene_update_info(const RtHipScene *scene, uint64_t *updates, double *last_seconds);
 /* for tests: tri_geom (9n), tri_normal (3n), the triangles' entry_src records (6n), tri_object (n, hull bits included); any may be NULL */
 int rt_hip_scene_read_triangles(const RtHipScene *scene, double *geom, double *normal, double *entry, uint32_t *object);
@@ -284,7 +284,8 @@ int rt_hip_scene_bounds(const RtHipScene *scene, double mesh_center[3], double *
  * records and their geom4 copy and reduces what a scene derives from its spheres -- the spheres' part of the reach, the largest
  * |centre|, the wide-range flag -- by maxima alone; the leading wall-sized spheres (whole pairs, at most 8) come from the first 8
  * records.  scene_sphere_bounds (csrc/scene_spheres.h; the text stands in csrc/bvh_build.h) is the one text of all of it, shared with rt_hip_scene_create.  Then every table set is stale and
- * rebuilt in place by the next launch.  Materials, flags, counts, meshes, object ids and every handle stay.
+ * rebuilt in place by the next launch.  Materials, flags, counts, meshes, object ids and every handle stay (materials and flags
+ * have an update of their own, rt_hip_scene_update_materials).
  * CONTRACT: after an update the records, the scalars (rt_hip_scene_sphere_bounds, rt_hip_scene_bounds), rt_hip_kernel_name and the
  * frames, bytes and counters of every launch equal, bit for bit, those of a scene freshly created from the same spheres.  A move may
  * change the wide-range flag or the number of leading walls, and with them the kernel a launch picks: that is intended, and why a
@@ -303,6 +304,45 @@ int rt_hip_scene_read_spheres(const RtHipScene *scene, double *entry, double *ge
  * reads, the leading walls (n_big of them, whole pairs; big_r / big_c are 0 from n_big on); any may be NULL */
 int rt_hip_scene_sphere_bounds(const RtHipScene *scene, double *reach_spheres, double *max_center, uint32_t *wide_range, uint32_t *n_big,
                                double big_r[8], double big_c[8]);
+
+/* ---- changing materials: new colours, emission and (optionally) flags for a scene that exists ----
+ * d_materials / h_materials: 6 doubles an object (colour r g b, emission r g b) for EVERY object of the scene in
+ * rt_hip_scene_create's numbering -- the spheres in their order, then mesh m at n_spheres + m.  d_flags / h_flags: one uint32 an
+ * object (M_DEFAULT 2 | M_REFLECTION 4 | M_REFRACTION 8, | M_CHECKERED 16), or NULL: every object keeps the flags it has.
+ * d_*: device memory on the scene's device, not inside the scene; h_*: host memory, staged by the call.  Synchronous, as the other
+ * updates are.  One streaming kernel (k_update_materials, csrc/scene_update.hip), a thread an object, rewrites the `material`
+ * records (prob, albedo / prob, emission, flags) and the color_raw triples and reduces what a scene derives from its materials:
+ * the largest |emission component| (a maximum) and three flag classes (ORs) -- an M_REFRACTION material, an M_CHECKERED one, one
+ * with M_REFLECTION and M_REFRACTION.  scene_material_bounds (csrc/scene_materials.h; the text stands in csrc/bvh_build.h) is the
+ * one text of all of it, shared with rt_hip_scene_create.  The table sets hold filter records, fp32 nodes and tri32 records, made
+ * of positions alone: they STAY VALID, and the next launch builds nothing.  Geometry, counts, meshes, object ids and every handle
+ * stay.
+ * CONTRACT: after an update the records and scalars (rt_hip_scene_read_materials, rt_hip_scene_material_bounds), rt_hip_kernel_name
+ * for every integrator, the query, trace and AOV kernel names, and the frames, bytes and counters of every launch equal, bit for
+ * bit, those of a scene freshly created from the same data -- where "bit for bit" takes a NaN of a record as equal to a NaN: a
+ * black colour gives prob = 0 and 0 * (1 / 0) = NaN in doubles 1..3 of its record, whose sign bit is the machine's default (the
+ * host's at creation, the device's after an update); no kernel reads the three (the reference's `random_double() < prob` never
+ * holds for prob = 0), so no output can differ.  An update may change a flag class or the largest emission, and with them the
+ * kernel a launch picks and the scale of its fixed-point sums: that is intended, and why a live RtHipAccum refuses the update.
+ * Histories (temporal reprojection, previews) hold radiance of the old materials: reset them after an update.
+ * Acceptance is rt_hip_scene_create's: a colour component that is negative, above 1e100 or NaN, or an |emission component| above
+ * 1e100 or NaN, is RT_HIP_EINVAL (-0.0 is accepted).  Also RT_HIP_EINVAL: a NULL d_materials; n_objects differs from n_spheres +
+ * n_meshes; a scene without objects; d_materials or d_flags not device memory of the scene's device, or inside the scene; an
+ * RtHipAccum on the scene that has not been destroyed; a launch of the scene being submitted on another thread.  RT_HIP_ENOMEM: the
+ * workspace (256 bytes; the host form adds the staged input).  After each of these the scene is unchanged: the kernel's first run
+ * writes nothing of the scene.  A scene that an earlier update left unusable: RT_HIP_ERUNTIME.  A HIP runtime failure after writing
+ * has begun is RT_HIP_ERUNTIME and leaves the scene UNUSABLE, as above. */
+int rt_hip_scene_update_materials(RtHipScene *scene, const double *d_materials, const uint32_t *d_flags, size_t n_objects);
+int rt_hip_scene_update_materials_host(RtHipScene *scene, const double *h_materials, const uint32_t *h_flags, size_t n_objects);
+/* for tests: the `material` records (8n doubles: prob, albedo / prob, emission, the flags as the uint64 bit pattern of double 7)
+ * and color_raw (3n), n = n_spheres + n_meshes; either may be NULL */
+int rt_hip_scene_read_materials(const RtHipScene *scene, double *material, double *color_raw);
+/* for tests: what the scene derives from its materials -- the largest |emission component| and the three flag classes a launch
+ * reads; any may be NULL */
+int rt_hip_scene_material_bounds(const RtHipScene *scene, double *max_emission, uint32_t *any_refract, uint32_t *any_checker,
+                                 uint32_t *any_mirror_glass);
+/* for tests: the scene's one device allocation (what "inside the scene" means to the updates' refusals); either may be NULL */
+int rt_hip_scene_memory(const RtHipScene *scene, const void **base, size_t *bytes);
 
 int rt_hip_scene_device(const RtHipScene *scene);
 size_t rt_hip_scene_primitives(const RtHipScene *scene); /* spheres + triangles */
@@ -1611,6 +1651,14 @@ int rt_hip_set_bvh_builder(int builder);
  * scene rebuilds the context as any other change does. */
 void rt_hip_set_scene_updates(int on);
 uint64_t rt_hip_cache_updates(void);
+
+/* on != 0: a call's scene may also differ from the cached one in flags, colours and emission (of spheres and meshes): every cached
+ * scene takes them in place (rt_hip_scene_update_materials_host) and rt_hip_cache_updates() counts one per frame.  Independent of
+ * rt_hip_set_scene_updates: a scene that differs both in materials and in positions is updated in place only if both switches
+ * allow their part (still one count a frame); otherwise the context is rebuilt.  A device's chunk workspace, which is sized by the
+ * scene's flag class, is freed by such an update and made again by the next chunked launch.  The default, 0: a changed material rebuilds the
+ * context, whatever rt_hip_set_scene_updates says. */
+void rt_hip_set_material_updates(int on);
 
 /* The cached context's rebuild ratio: 0 (the default) never rebuilds; a finite ratio >= 1 makes every frame that
  * rt_hip_set_scene_updates(1) takes as an in-place VERTEX update end with rt_hip_scene_maintain_bvh(scene, ratio) on every cached

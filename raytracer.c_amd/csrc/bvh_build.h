@@ -835,6 +835,97 @@ inline void scene_sphere_bounds(const double *spheres, size_t n, double *entry, 
   scene_sphere_leading_walls(spheres, n, b);
 }
 
+/* ---- a scene's materials changed in place (scene_update.hip, rt_hip_scene_update_materials) ----
+ * What a scene derives from its materials, in one text for the host (scene_create_impl, rt_hip_shim.hip), the device
+ * (k_update_materials, scene_update.hip) and the CPU test of both (tests/material_harness.cpp, through scene_materials.h): the
+ * `material` record of PT_MAT_STRIDE doubles an object, its `color_raw` triple, and the object's part of four scalars --
+ * max_emission (a maximum) and the three flag classes any_refract, any_checker, any_mirror_glass (ORs).  Input everywhere: 6
+ * doubles an object, colour then emission, and the object's flags; objects in rt_hip_scene_create's numbering, spheres first,
+ * mesh m at n_spheres + m.  Compiled with -ffp-contract=off on every side: records and scalars of an updated scene equal a
+ * freshly created scene's bit for bit -- with ONE exception that no kernel can see: a black colour gives prob = 0, inv = +inf and
+ * 0 * inf = NaN in doubles 1..3, and the sign bit of that default NaN is the machine's (host and device may differ).  The
+ * reference never reads the three (`random_double() < 0` is false, raytracer.c:497-500), so a comparison of records takes a NaN
+ * as equal to a NaN and every other word by its bits. */
+#define SCENE_MATERIAL_IN 6 /* doubles an object of the input: colour rgb, emission rgb */
+
+/* rt_hip_scene_create's rule (RT_HIP_EINVAL otherwise): the pooled kernels' fixed-point sums rest on throughput <= 1, i.e. on
+ * albedo / MAX(albedo) in [0, 1] -- colours finite and non-negative (-0.0 is), at most 1e100; |emission| at most 1e100.  False
+ * for a NaN anywhere. */
+BVH_HD inline bool scene_material_ok(const double *color, const double *emission)
+{
+  for (int k = 0; k < 3; k++)
+    if (!(color[k] >= 0.0) || !(color[k] <= 1e100) || !(std::fabs(emission[k]) <= 1e100))
+      return false;
+  return true;
+}
+
+/* One object's record (pt_device.h): prob, albedo / prob, emission, the flags as the uint64 bit pattern of double 7 */
+BVH_HD inline void scene_material_record(uint32_t flags, const double *color, const double *emission, double *m)
+{
+  /* raytracer.c:497: prob = MAX(albedo.x, MAX(albedo.y, albedo.z)) */
+  const double yz = color[1] > color[2] ? color[1] : color[2];
+  const double prob = color[0] > yz ? color[0] : yz;
+  const double inv = 1 / prob; /* :500 vec3_scalar_mult(albedo, 1 / prob) */
+  m[0] = prob;
+  m[1] = color[0] * inv;
+  m[2] = color[1] * inv;
+  m[3] = color[2] * inv;
+  m[4] = emission[0];
+  m[5] = emission[1];
+  m[6] = emission[2];
+  const uint64_t bits = flags;
+  memcpy(&m[7], &bits, sizeof bits);
+}
+/* the flags a record holds (an update without flags keeps them) */
+BVH_HD inline uint32_t scene_material_flags(const double *m)
+{
+  uint64_t bits;
+  memcpy(&bits, &m[7], sizeof bits);
+  return (uint32_t)bits;
+}
+
+/* The object's part of each scalar.  max_emission: the scene's value is the maximum over the objects, from 0 (material_ok has
+ * ruled out a NaN). */
+BVH_HD inline double scene_material_emission_part(const double *emission)
+{
+  return std::fmax(std::fabs(emission[0]), std::fmax(std::fabs(emission[1]), std::fabs(emission[2])));
+}
+/* the flag classes, one bit each; the scene's value is the OR over the objects */
+#define SCENE_MATERIAL_REFRACT 1u      /* view.any_refract: an M_REFRACTION material */
+#define SCENE_MATERIAL_CHECKER 2u      /* view.any_checker: an M_CHECKERED material */
+#define SCENE_MATERIAL_MIRROR_GLASS 4u /* any_mirror_glass: M_REFLECTION and M_REFRACTION on one object */
+BVH_HD inline uint32_t scene_material_class_part(uint32_t flags)
+{
+  const uint32_t both = PT_FLAG_MIRROR | PT_FLAG_REFRACT;
+  return ((flags & PT_FLAG_REFRACT) ? SCENE_MATERIAL_REFRACT : 0u) | ((flags & PT_FLAG_CHECKER) ? SCENE_MATERIAL_CHECKER : 0u) |
+         ((flags & both) == both ? SCENE_MATERIAL_MIRROR_GLASS : 0u);
+}
+
+struct SceneMaterialBounds
+{
+  double max_emission = 0; /* max |emission component| over the objects */
+  uint32_t classes = 0;    /* SCENE_MATERIAL_* of any object */
+};
+
+/* The sequential statement of everything above for n objects that material_ok accepts: the records (material: PT_MAT_STRIDE n
+ * doubles), the colours as given (color_raw: 3 n; either may be null) and the scalars.  in: SCENE_MATERIAL_IN doubles an object.
+ * What scene_create_impl calls, and what the device's update is tested against. */
+inline void scene_material_bounds(const double *in, const uint32_t *flags, size_t n, double *material, double *color_raw, SceneMaterialBounds *b)
+{
+  *b = SceneMaterialBounds();
+  for (size_t i = 0; i < n; i++)
+  {
+    const double *c = in + SCENE_MATERIAL_IN * i, *e = c + 3;
+    if (material)
+      scene_material_record(flags[i], c, e, material + PT_MAT_STRIDE * i);
+    if (color_raw)
+      for (int k = 0; k < 3; k++)
+        color_raw[3 * i + k] = c[k];
+    b->max_emission = std::fmax(b->max_emission, scene_material_emission_part(e));
+    b->classes |= scene_material_class_part(flags[i]);
+  }
+}
+
 /* ---- a tree priced on the device (scene_update.hip: k_tree_cost; rt_hip_scene_bvh_cost, rt_hip.h states the contract) ----
  * BvhBuild::tree_cost()'s formula, term by term, in one text for the kernel and for whoever restates it on the host: the terms
  * are the same doubles; only the order of the additions differs (a fixed tree here, node order there).  fp64, unfused
@@ -922,6 +1013,18 @@ hipError_t scene_update_spheres_check(const double *spheres, uint32_t n, unsigne
 /* writes the n records of entry (PT_ENTRY_SRC_STRIDE n) and geom4 (PT_GEOM_STRIDE n): the same kernel with its outputs given and
  * no words -- it reduces nothing.  Enqueues only. */
 hipError_t scene_update_spheres_write(const double *spheres, uint32_t n, double *entry, double *geom4);
+
+/* ---- the interface of scene_update.hip's material half (rt_hip_scene_update_materials) ----
+ * Both on the null stream of the current device; in = SCENE_MATERIAL_IN doubles an object, flags = a word an object or nullptr
+ * (every object keeps the flags of its record), both in device memory; words: SCENE_MATERIAL_WORDS 64-bit words of workspace. */
+#define SCENE_MATERIAL_WORDS 5
+/* reads the input and, without flags, double 7 of the n records at `present`; writes `words` alone and waits: the scalars, and
+ * whether scene_material_ok accepts every object (max_emission then leaves the refused ones out) */
+hipError_t scene_update_materials_check(const double *in, const uint32_t *flags, uint32_t n, const double *present,
+                                        unsigned long long *words, SceneMaterialBounds *out, bool *materials_ok);
+/* writes the n records of material (PT_MAT_STRIDE n; without flags each keeps its own) and color_raw (3 n): the same kernel with
+ * its outputs given and no words -- it reduces nothing.  Enqueues only. */
+hipError_t scene_update_materials_write(const double *in, const uint32_t *flags, uint32_t n, double *material, double *color_raw);
 #endif /* __HIPCC__ */
 
 #endif /* BVH_BUILD_H */

@@ -402,34 +402,8 @@ int usable_devices()
 
 bool have_device(int device) { return device >= 0 && device < usable_devices(); }
 
-double max_abs3(const double *v) { return std::fmax(std::fabs(v[0]), std::fmax(std::fabs(v[1]), std::fabs(v[2]))); }
-
-/* The pooled kernels' fixed-point sums rest on throughput <= 1, i.e. on albedo / MAX(albedo)
- * in [0, 1]: colours must be finite and non-negative; emission finite. */
-bool material_ok(const double *color, const double *emission)
-{
-  for (int k = 0; k < 3; k++)
-    if (!(color[k] >= 0.0) || !(color[k] <= 1e100) || !(std::fabs(emission[k]) <= 1e100))
-      return false;
-  return true;
-}
-
-void put_material(double *m, uint32_t flags, const double *color, const double *emission)
-{
-  /* raytracer.c:497: prob = MAX(albedo.x, MAX(albedo.y, albedo.z)) */
-  double yz = color[1] > color[2] ? color[1] : color[2];
-  double prob = color[0] > yz ? color[0] : yz;
-  double inv = 1 / prob; /* :500 vec3_scalar_mult(albedo, 1 / prob) */
-  m[0] = prob;
-  m[1] = color[0] * inv;
-  m[2] = color[1] * inv;
-  m[3] = color[2] * inv;
-  m[4] = emission[0];
-  m[5] = emission[1];
-  m[6] = emission[2];
-  uint64_t bits = flags;
-  memcpy(&m[7], &bits, sizeof bits);
-}
+/* One object's `material` record, its color_raw triple, the acceptance rule and every scalar a scene derives from its materials:
+ * scene_material_* (bvh_build.h), one text with the device's (rt_hip_scene_update_materials). */
 
 /* One sphere's record of entry_src (pt_device.h), its geom4 copy and every scalar a scene derives from its spheres:
  * scene_sphere_* (bvh_build.h), one text with the device's (rt_hip_scene_update_spheres). */
@@ -477,7 +451,7 @@ int scene_usable(const RtHipScene *scene, const char *who)
   if (!scene)
     return fail(RT_HIP_EINVAL, "%s: scene is NULL (a scene is required)", who);
   if (scene->unusable)
-    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an update of its vertices or spheres failed half way (rt_hip_scene_update_*)");
+    return fail(RT_HIP_ERUNTIME, "the scene is unusable: an update of its vertices, spheres or materials failed half way (rt_hip_scene_update_*)");
   return RT_HIP_OK;
 }
 
@@ -1134,6 +1108,16 @@ void take_mesh_bounds(RtHipScene *sc, const SceneMeshBounds &mb)
   sc->view.mesh_round = mb.round ? 1u : 0u;
 }
 
+/* ... and for the materials -- at creation, and after every update of the materials */
+void take_material_bounds(RtHipScene *sc, const SceneMaterialBounds &b)
+{
+  sc->max_emission = b.max_emission;
+  sc->view.any_refract = (b.classes & SCENE_MATERIAL_REFRACT) ? 1u : 0u;
+  sc->view.any_checker = (b.classes & SCENE_MATERIAL_CHECKER) ? 1u : 0u;
+  sc->any_mirror_glass = (b.classes & SCENE_MATERIAL_MIRROR_GLASS) != 0;
+  sc->view.any_mirror_glass = sc->any_mirror_glass ? 1u : 0u;
+}
+
 /* hull facets (pt_build_hull_flags) with the margin scene_mesh_bounds gave, where there is one and the triangles are few enough;
  * tri_object's bits are clear before.  Enqueues on the null stream: the caller waits. */
 hipError_t scene_hull_flags(RtHipScene *sc, double tau)
@@ -1198,27 +1182,19 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     return fail(RT_HIP_ENODEV, "no HIP device %d (found %d)", device, usable_devices());
 
   size_t n_tri = 0;
-  bool any_checker = false, any_refract = false, any_mirror_glass = false;
-  const uint32_t both = PT_FLAG_MIRROR | PT_FLAG_REFRACT;
   for (size_t i = 0; i < n_spheres; i++)
   {
-    any_refract |= (spheres[i].flags & PT_FLAG_REFRACT) != 0;
-    any_mirror_glass |= (spheres[i].flags & both) == both;
-    any_checker |= (spheres[i].flags & PT_FLAG_CHECKER) != 0;
-    if (!material_ok(spheres[i].color, spheres[i].emission))
+    if (!scene_material_ok(spheres[i].color, spheres[i].emission))
       return fail(RT_HIP_EINVAL, "sphere %zu: colour must be finite and >= 0, emission finite", i);
     if (!scene_sphere_radius_ok(spheres[i].radius))
       return fail(RT_HIP_ELIMIT, "sphere %zu: |radius| %g outside [1e-100, 1e100]", i, spheres[i].radius);
   }
   for (size_t m = 0; m < n_meshes; m++)
   {
-    any_refract |= (meshes[m].flags & PT_FLAG_REFRACT) != 0;
-    any_mirror_glass |= (meshes[m].flags & both) == both;
-    if (!material_ok(meshes[m].color, meshes[m].emission))
+    if (!scene_material_ok(meshes[m].color, meshes[m].emission))
       return fail(RT_HIP_EINVAL, "mesh %zu: colour must be finite and >= 0, emission finite", m);
     if (meshes[m].num_triangles && !meshes[m].vertices)
       return fail(RT_HIP_EINVAL, "mesh %zu has triangles but no vertices", m);
-    any_checker |= (meshes[m].flags & PT_FLAG_CHECKER) != 0;
     n_tri += meshes[m].num_triangles;
   }
   if (n_spheres + n_meshes > 0xFFFFFFu || n_tri > 0x7FFFFFFFu - n_spheres)
@@ -1226,19 +1202,25 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   const size_t n_mat = n_spheres + n_meshes;
 
   /* ---- build the kernel layout on the host (pt_device.h) ---- */
-  double reach = 0, reach_triangles = 0, max_emission = 0;
-  for (size_t i = 0; i < n_spheres; i++)
-    max_emission = std::fmax(max_emission, max_abs3(spheres[i].emission));
-  for (size_t m = 0; m < n_meshes; m++)
-    max_emission = std::fmax(max_emission, max_abs3(meshes[m].emission));
+  double reach = 0, reach_triangles = 0;
   std::vector<double> geom(PT_ENTRY_SRC_STRIDE * (n_spheres + n_tri)), mat(PT_MAT_STRIDE * n_mat), tgeom(9 * n_tri), tnorm(3 * n_tri),
       ttex(6 * n_tri);
   std::vector<uint32_t> tobj(n_tri);
   std::vector<double> craw(3 * n_mat), geom4(PT_GEOM_STRIDE * n_spheres);
-  for (size_t i = 0; i < n_spheres; i++)
-    memcpy(&craw[3 * i], spheres[i].color, 3 * sizeof(double));
-  for (size_t m = 0; m < n_meshes; m++)
-    memcpy(&craw[3 * (n_spheres + m)], meshes[m].color, 3 * sizeof(double));
+  /* the materials' records and what the scene derives from them: bvh_build.h, as an update of the materials derives it again */
+  SceneMaterialBounds matb;
+  {
+    std::vector<double> in(SCENE_MATERIAL_IN * n_mat);
+    std::vector<uint32_t> flags(n_mat);
+    for (size_t i = 0; i < n_mat; i++)
+    {
+      const bool sph = i < n_spheres;
+      memcpy(&in[SCENE_MATERIAL_IN * i], sph ? spheres[i].color : meshes[i - n_spheres].color, 3 * sizeof(double));
+      memcpy(&in[SCENE_MATERIAL_IN * i + 3], sph ? spheres[i].emission : meshes[i - n_spheres].emission, 3 * sizeof(double));
+      flags[i] = sph ? spheres[i].flags : meshes[i - n_spheres].flags;
+    }
+    scene_material_bounds(in.data(), flags.data(), n_mat, mat.data(), craw.data(), &matb);
+  }
   /* the spheres' records and what the scene derives from them: bvh_build.h, as an update of the spheres derives it again */
   SceneSphereBounds sb;
   {
@@ -1247,7 +1229,6 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     {
       memcpy(&in[SCENE_SPHERE_IN * i], spheres[i].center, 3 * sizeof(double));
       in[SCENE_SPHERE_IN * i + 3] = spheres[i].radius;
-      put_material(&mat[PT_MAT_STRIDE * i], spheres[i].flags, spheres[i].color, spheres[i].emission);
     }
     scene_sphere_bounds(in.data(), n_spheres, geom.data(), geom4.data(), &sb);
   }
@@ -1272,7 +1253,6 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
     }
   for (size_t m = 0; m < n_meshes; m++)
   {
-    put_material(&mat[PT_MAT_STRIDE * (n_spheres + m)], meshes[m].flags, meshes[m].color, meshes[m].emission);
     for (size_t k = 0; k < meshes[m].num_triangles; k++, t++)
     {
       const RtHipVertex *v = meshes[m].vertices + 3 * k;
@@ -1457,8 +1437,6 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   }
   sc->view.n_spheres = (uint32_t)n_spheres;
   sc->view.n_meshes = (uint32_t)n_meshes;
-  sc->view.any_checker = any_checker ? 1u : 0u;
-  sc->view.any_refract = any_refract ? 1u : 0u;
 #ifdef PT_DEV_KERNELS
   {
     /* development knob (tools/many_spheres.py): RT_HIP_FORCE_BIG=1 sends a small scene to the scalar-table _big kernels,
@@ -1471,9 +1449,7 @@ int scene_create_impl(const RtHipSphere *spheres, size_t n_spheres, const RtHipM
   sc->reach = reach;
   sc->reach_triangles = reach_triangles;
   sc->blob_bytes = total;
-  sc->max_emission = max_emission;
-  sc->any_mirror_glass = any_mirror_glass;
-  sc->view.any_mirror_glass = any_mirror_glass ? 1u : 0u;
+  take_material_bounds(sc, matb);
   *out_scene = sc;
   return RT_HIP_OK;
 }
@@ -1929,6 +1905,7 @@ std::vector<int> g_device_map;
 bool g_device_map_env_read = false;
 int g_bvh_builder = RT_HIP_BVH_HOST; /* rt_hip_set_bvh_builder: the builder of the cached scenes.  Guarded by g_ctx_mutex. */
 bool g_scene_updates = false; /* rt_hip_set_scene_updates: moved vertices update the cached scenes in place.  Guarded by g_ctx_mutex. */
+bool g_material_updates = false; /* rt_hip_set_material_updates: changed flags, colours and emission update the cached scenes in place.  Guarded by g_ctx_mutex. */
 double g_bvh_rebuild_ratio = 0; /* rt_hip_set_bvh_rebuild_ratio: 0 = never; else rt_hip_scene_maintain_bvh's max_ratio after such an update.  Guarded by g_ctx_mutex. */
 
 void device_map_from_env()
@@ -2016,11 +1993,11 @@ struct CtxGuard
 };
 
 /* Everything that defines the scene, field by field (struct padding is not part of the scene), as runs of bytes handed
- * to `f(ptr, n, kind)` in a fixed order (kind: RUN_VERTICES, the run is a mesh's RtHipVertex array; RUN_SPHERE, a sphere's ten doubles, radius and centre first; RUN_OTHER).  The cached context keeps the concatenation (ImageCtx::scene_bytes) and is reused only
+ * to `f(ptr, n, kind)` in a fixed order (kind: RUN_VERTICES, the run is a mesh's RtHipVertex array; RUN_SPHERE, a sphere's ten doubles, radius and centre first, colour and emission behind them; RUN_FLAGS, an object's flags; RUN_MATERIAL, a mesh's colour and emission; RUN_OTHER).  The cached context keeps the concatenation (ImageCtx::scene_bytes) and is reused only
  * while a call's scene equals it byte for byte: scene_matches() compares run by run (memcmp, stopping at the first
  * difference) against the kept copy -- no per-call serialisation, no hashing: a frame of config 5's mesh used to rebuild
  * and hash 1.2 MB on the host inside every rt_hip_render_image() call (round-3 advisor finding). */
-enum { RUN_OTHER = 0, RUN_VERTICES = 1, RUN_SPHERE = 2 };
+enum { RUN_OTHER = 0, RUN_VERTICES = 1, RUN_SPHERE = 2, RUN_FLAGS = 3, RUN_MATERIAL = 4 };
 template <class F>
 void scene_walk(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *meshes, size_t n_meshes, F &&f)
 {
@@ -2028,22 +2005,23 @@ void scene_walk(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
   f(&n_meshes, sizeof n_meshes, RUN_OTHER);
   for (size_t i = 0; i < n_spheres; i++)
   {
-    f(&spheres[i].flags, sizeof spheres[i].flags, RUN_OTHER);
+    f(&spheres[i].flags, sizeof spheres[i].flags, RUN_FLAGS);
     f(&spheres[i].radius, sizeof(double) * 10, RUN_SPHERE); /* radius, center, color, emission are contiguous doubles */
   }
   for (size_t m = 0; m < n_meshes; m++)
   {
-    f(&meshes[m].flags, sizeof meshes[m].flags, RUN_OTHER);
-    f(meshes[m].color, sizeof(double) * 6, RUN_OTHER); /* color, emission */
+    f(&meshes[m].flags, sizeof meshes[m].flags, RUN_FLAGS);
+    f(meshes[m].color, sizeof(double) * 6, RUN_MATERIAL); /* color, emission */
     f(&meshes[m].num_triangles, sizeof meshes[m].num_triangles, RUN_OTHER);
     if (meshes[m].vertices)
       f(meshes[m].vertices, meshes[m].num_triangles * 3 * sizeof(RtHipVertex), RUN_VERTICES);
   }
 }
 
-/* SCENE_MOVED: equal but for vertex positions (MOVED_VERTICES) and sphere centres and radii (MOVED_SPHERES), as *moved says */
+/* SCENE_MOVED: equal but for vertex positions (MOVED_VERTICES), sphere centres and radii (MOVED_SPHERES) and flags, colours and
+ * emission (MOVED_MATERIALS), as *moved says: what an update in place can take, each kind where its switch allows it */
 enum SceneMatch { SCENE_DIFFERS = 0, SCENE_SAME = 1, SCENE_MOVED = 2 };
-enum { MOVED_VERTICES = 1, MOVED_SPHERES = 2 };
+enum { MOVED_VERTICES = 1, MOVED_SPHERES = 2, MOVED_MATERIALS = 4 };
 
 SceneMatch scene_matches(const std::vector<unsigned char> &kept, const RtHipSphere *spheres, size_t n_spheres,
                          const RtHipMesh *meshes, size_t n_meshes, int *moved_what)
@@ -2063,11 +2041,20 @@ SceneMatch scene_matches(const std::vector<unsigned char> &kept, const RtHipSphe
       const size_t tex = offsetof(RtHipVertex, tex);
       same = kind != RUN_OTHER;
       if (kind == RUN_VERTICES)
+      {
         for (size_t v = 0; same && v < n / sizeof(RtHipVertex); v++)
           same = memcmp(a + v * sizeof(RtHipVertex) + tex, b + v * sizeof(RtHipVertex) + tex, sizeof(RtHipVertex) - tex) == 0;
-      else if (kind == RUN_SPHERE) /* the radius and the centre may differ; the colour and the emission behind them must not */
-        same = memcmp(a + 4 * sizeof(double), b + 4 * sizeof(double), n - 4 * sizeof(double)) == 0;
-      moved |= kind == RUN_VERTICES ? MOVED_VERTICES : MOVED_SPHERES;
+        moved |= MOVED_VERTICES;
+      }
+      else if (kind == RUN_SPHERE)
+      { /* the radius and the centre are the sphere's place; the colour and the emission behind them its material */
+        if (memcmp(a, b, 4 * sizeof(double)) != 0)
+          moved |= MOVED_SPHERES;
+        if (memcmp(a + 4 * sizeof(double), b + 4 * sizeof(double), n - 4 * sizeof(double)) != 0)
+          moved |= MOVED_MATERIALS;
+      }
+      else
+        moved |= MOVED_MATERIALS;
     }
     at += n;
   });
@@ -2105,9 +2092,12 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
     const SceneMatch match = scene_matches(c.scene_bytes, spheres, n_spheres, meshes, n_meshes, &moved);
     if (match == SCENE_SAME)
       return RT_HIP_OK;
-    if (match == SCENE_MOVED && g_scene_updates)
-    { /* only vertex positions, sphere centres and radii differ: every device's scene takes them in place, by the update of each
-       * kind that differs; a failure drops the context (CtxGuard) */
+    const bool may_move = !(moved & (MOVED_VERTICES | MOVED_SPHERES)) || g_scene_updates;
+    const bool may_recolour = !(moved & MOVED_MATERIALS) || g_material_updates;
+    if (match == SCENE_MOVED && may_move && may_recolour)
+    { /* only vertex positions, sphere centres and radii differ (rt_hip_set_scene_updates), or flags, colours and emission
+       * (rt_hip_set_material_updates): every device's scene takes them in place, by the update of each kind that differs; a
+       * failure drops the context (CtxGuard) */
       if (moved & MOVED_VERTICES)
       {
         size_t n_tri = 0;
@@ -2152,6 +2142,30 @@ int ctx_prepare(const RtHipSphere *spheres, size_t n_spheres, const RtHipMesh *m
           const int rc = rt_hip_scene_update_spheres_host(c.dev[g].scene, sph.data(), n_spheres);
           if (rc)
             return rc;
+        }
+      }
+      if (moved & MOVED_MATERIALS)
+      {
+        const size_t n_mat = n_spheres + n_meshes;
+        std::vector<double> mat(SCENE_MATERIAL_IN * n_mat);
+        std::vector<uint32_t> flags(n_mat);
+        for (size_t i = 0; i < n_mat; i++)
+        {
+          const bool sph = i < n_spheres;
+          memcpy(&mat[SCENE_MATERIAL_IN * i], sph ? spheres[i].color : meshes[i - n_spheres].color, 3 * sizeof(double));
+          memcpy(&mat[SCENE_MATERIAL_IN * i + 3], sph ? spheres[i].emission : meshes[i - n_spheres].emission, 3 * sizeof(double));
+          flags[i] = sph ? spheres[i].flags : meshes[i - n_spheres].flags;
+        }
+        for (int g = 0; g < G; g++)
+        {
+          const int rc = rt_hip_scene_update_materials_host(c.dev[g].scene, mat.data(), flags.data(), n_mat);
+          if (rc)
+            return rc;
+          /* the chunk workspace was sized for the scene's flag class as it was (rt_hip_scene_chunk_workspace_bytes: the windowed
+           * sums of the M_REFRACTION forms are six times the plain record): the next chunked launch sizes it anew, as a rebuilt
+           * context would.  The frames are synchronous and the update has drained the scene: nothing reads it any more. */
+          HIP_TRY(hipSetDevice(c.phys[g]));
+          c.dev[g].ws.release();
         }
       }
       scene_serialise(c.scene_bytes, spheres, n_spheres, meshes, n_meshes);
@@ -2536,6 +2550,12 @@ void set_scene_updates_impl(int on)
 {
   std::lock_guard<std::mutex> lock(g_ctx_mutex);
   g_scene_updates = on != 0;
+}
+
+void set_material_updates_impl(int on)
+{
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  g_material_updates = on != 0;
 }
 
 int set_bvh_rebuild_ratio_impl(double max_ratio)
@@ -4696,6 +4716,8 @@ uint64_t rt_hip_cache_updates(void) { return cache_updates_impl(); }
 
 void rt_hip_set_scene_updates(int on) { set_scene_updates_impl(on); }
 
+void rt_hip_set_material_updates(int on) { set_material_updates_impl(on); }
+
 int rt_hip_set_bvh_rebuild_ratio(double max_ratio) { return set_bvh_rebuild_ratio_impl(max_ratio); }
 
 uint64_t rt_hip_cache_rebuilds(void) { return cache_rebuilds_impl(); }
@@ -4839,7 +4861,7 @@ int check_update_input(const RtHipScene *scene, const void *ptr, size_t bytes, c
 int stage_update_input(const double *in, size_t bytes, bool on_host, DeviceBuffer &ws, unsigned long long **words, const double **d_in)
 {
   const size_t words_bytes = 256, total = words_bytes + (on_host ? bytes : 0);
-  static_assert(SCENE_UPDATE_WORDS * 8 <= 256 && SCENE_SPHERE_WORDS * 8 <= 256, "the reductions' words");
+  static_assert(SCENE_UPDATE_WORDS * 8 <= 256 && SCENE_SPHERE_WORDS * 8 <= 256 && SCENE_MATERIAL_WORDS * 8 <= 256, "the reductions' words");
   if (ws.alloc(total) != hipSuccess)
     return fail(RT_HIP_ENOMEM, "update workspace (%zu KB)", total >> 10);
   *words = ws.at<unsigned long long>();
@@ -5000,6 +5022,76 @@ int scene_update_spheres_impl(RtHipScene *scene, const double *spheres, size_t n
     return w.broke(e, "waiting for the update");
   take_sphere_bounds(scene, sb);
   scene->reach = std::fmax(scene->reach_spheres, scene->reach_triangles);
+  scene->updates++;
+  scene->last_update_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RT_HIP_OK;
+}
+
+/* ---- changing the materials in place: the `material` records and color_raw rewritten by k_update_materials (scene_update.hip),
+ * then the scalars scene_create_impl derives from the materials, by bvh_build.h's one text.  The same discipline as above: the
+ * kernel's first run writes nothing of the scene (the scalars, and whether every material is acceptable); only when no refusal is
+ * left does its second run write.  The table sets STAY VALID (no stale()): pt_launch_build_tables reads entry_src, bvh_src and
+ * tri_geom / tri_geom_leaf alone -- filter records, fp32 nodes and tri32 records hold nothing a material decides.  The host form
+ * stages the materials and, where given, the flags behind them in the one workspace. */
+int scene_update_materials_impl(RtHipScene *scene, const double *materials, const uint32_t *flags, size_t n_objects, bool on_host)
+{
+  if (const int rc = scene_usable(scene, "rt_hip_scene_update_materials"))
+    return rc;
+  if (!materials)
+    return fail(RT_HIP_EINVAL, "materials are required");
+  const size_t n = (size_t)scene->view.n_spheres + scene->view.n_meshes;
+  if (n == 0)
+    return fail(RT_HIP_EINVAL, "the scene has no objects whose materials could change");
+  if (n_objects != n)
+    return fail(RT_HIP_EINVAL, "%zu objects given, the scene has %zu: an update keeps the count", n_objects, n);
+  const size_t mat_bytes = SCENE_MATERIAL_IN * 8 * n, flag_bytes = flags ? 4 * n : 0;
+  SceneWrite w(scene, "its materials change");
+  HIP_TRY(w.scope.status);
+  if (!on_host)
+  {
+    if (const int rc = check_update_input(scene, materials, mat_bytes, "d_materials"))
+      return rc;
+    if (flags)
+      if (const int rc = check_update_input(scene, flags, flag_bytes, "d_flags"))
+        return rc;
+  }
+  w.lock.lock();
+  if (const int rc = w.idle())
+    return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  DeviceBuffer ws;
+  unsigned long long *words = nullptr;
+  const double *d_in = nullptr;
+  const uint32_t *d_flags = flags;
+  if (on_host && flags)
+  { /* one staged array: the doubles, then the words */
+    std::vector<double> both(SCENE_MATERIAL_IN * n + (n + 1) / 2);
+    memcpy(both.data(), materials, mat_bytes);
+    memcpy(both.data() + SCENE_MATERIAL_IN * n, flags, flag_bytes);
+    if (const int rc = stage_update_input(both.data(), both.size() * 8, true, ws, &words, &d_in))
+      return rc;
+    d_flags = reinterpret_cast<const uint32_t *>(d_in + SCENE_MATERIAL_IN * n);
+  }
+  else if (const int rc = stage_update_input(materials, mat_bytes, on_host, ws, &words, &d_in))
+    return rc;
+  SceneMaterialBounds mb;
+  bool materials_ok = false;
+  HIP_TRY(scene_update_materials_check(d_in, d_flags, (uint32_t)n, scene->view.material, words, &mb, &materials_ok));
+  if (!materials_ok) /* scene_create_impl's rule */
+    return fail(RT_HIP_EINVAL, "a material is refused: colour must be finite and >= 0, emission finite (both at most 1e100)");
+
+  if (const int rc = w.drain())
+    return rc;
+
+  /* ---- writing begins ---- */
+  hipError_t e = scene_update_materials_write(d_in, d_flags, (uint32_t)n, const_cast<double *>(scene->view.material),
+                                              const_cast<double *>(scene->view.color_raw));
+  if (e != hipSuccess)
+    return w.broke(e, "updating the material records");
+  e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess)
+    return w.broke(e, "waiting for the update");
+  take_material_bounds(scene, mb);
   scene->updates++;
   scene->last_update_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return RT_HIP_OK;
@@ -5191,6 +5283,51 @@ int rt_hip_scene_update_spheres(RtHipScene *scene, const double *d_spheres, size
 int rt_hip_scene_update_spheres_host(RtHipScene *scene, const double *h_spheres, size_t n_spheres)
 {
   return guarded("rt_hip_scene_update_spheres_host", [&] { return scene_update_spheres_impl(scene, h_spheres, n_spheres, true); });
+}
+
+int rt_hip_scene_update_materials(RtHipScene *scene, const double *d_materials, const uint32_t *d_flags, size_t n_objects)
+{
+  return guarded("rt_hip_scene_update_materials", [&] { return scene_update_materials_impl(scene, d_materials, d_flags, n_objects, false); });
+}
+
+int rt_hip_scene_update_materials_host(RtHipScene *scene, const double *h_materials, const uint32_t *h_flags, size_t n_objects)
+{
+  return guarded("rt_hip_scene_update_materials_host", [&] { return scene_update_materials_impl(scene, h_materials, h_flags, n_objects, true); });
+}
+
+int rt_hip_scene_read_materials(const RtHipScene *scene, double *material, double *color_raw)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_read_materials: scene is NULL");
+  const size_t n = (size_t)scene->view.n_spheres + scene->view.n_meshes;
+  if (n == 0)
+    return RT_HIP_OK;
+  DeviceScope on(scene->device);
+  HIP_TRY(on.status);
+  if (material) HIP_TRY(hipMemcpy(material, scene->view.material, PT_MAT_STRIDE * 8 * n, hipMemcpyDeviceToHost));
+  if (color_raw) HIP_TRY(hipMemcpy(color_raw, scene->view.color_raw, 3 * 8 * n, hipMemcpyDeviceToHost));
+  return RT_HIP_OK;
+}
+
+int rt_hip_scene_material_bounds(const RtHipScene *scene, double *max_emission, uint32_t *any_refract, uint32_t *any_checker,
+                                 uint32_t *any_mirror_glass)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_material_bounds: scene is NULL");
+  if (max_emission) *max_emission = scene->max_emission;
+  if (any_refract) *any_refract = scene->view.any_refract;
+  if (any_checker) *any_checker = scene->view.any_checker;
+  if (any_mirror_glass) *any_mirror_glass = scene->view.any_mirror_glass;
+  return RT_HIP_OK;
+}
+
+int rt_hip_scene_memory(const RtHipScene *scene, const void **base, size_t *bytes)
+{
+  if (!scene)
+    return fail(RT_HIP_EINVAL, "rt_hip_scene_memory: scene is NULL");
+  if (base) *base = scene->blob;
+  if (bytes) *bytes = scene->blob_bytes;
+  return RT_HIP_OK;
 }
 
 int rt_hip_scene_read_spheres(const RtHipScene *scene, double *entry, double *geom4)

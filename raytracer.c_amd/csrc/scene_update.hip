@@ -12,6 +12,10 @@
  * and a scene's spheres moved in place (rt_hip_scene_update_spheres; the contract is scene_spheres.h's scene_sphere_bounds):
  *   k_update_spheres     one thread a sphere: the entry_src record and its geom4 copy (where an output is given), and the maxima
  *                        the scene keeps of its spheres -- reach, max |centre|, wide range -- with "a radius is out of range"
+ * and a scene's materials changed in place (rt_hip_scene_update_materials; the contract is scene_materials.h's scene_material_bounds):
+ *   k_update_materials   one thread an object: the `material` record and the color_raw triple (where an output is given), and what
+ *                        the scene keeps of its materials -- max |emission|, the three flag classes -- with "a material is not
+ *                        acceptable"
  * and a tree priced where it lies (rt_hip_scene_bvh_cost; the contract is bvh_build.h's bvh_cost_* and rt_hip.h):
  *   k_tree_cost          one level of a fixed reduction tree over the nodes' cost terms, launched level by level from the host
  * 256 threads a workgroup, no scratch, no LDS (k_tree_cost: 2 KB, for its two widest halvings); no kernel waits for another
@@ -22,6 +26,7 @@
 #include <cstring>
 
 #include "bvh_build.h"
+#include "scene_materials.h"
 #include "scene_spheres.h"
 
 namespace
@@ -219,6 +224,52 @@ __global__ void __launch_bounds__(UPD_BLOCK) k_update_spheres(const double *__re
     atomicMax(&words[1], kc);
     atomicMax(&words[2], kw);
     atomicMax(&words[3], kb);
+  }
+}
+
+/* words[0] = key of max_emission, words[1..3] = an object is of the class (M_REFRACTION; M_CHECKERED; M_REFLECTION and
+ * M_REFRACTION), words[4] = a material is not acceptable.  in: SCENE_MATERIAL_IN doubles an object; flags: a word an object, or
+ * nullptr: every object keeps the flags of its present record (double 7 of `present`, the scene's records).  material == nullptr:
+ * nothing but the words is written (the check before anything of the scene changes); words == nullptr: nothing is reduced (the
+ * write after it).  The write run's `material` is `present`: a thread reads its own record's flags before it stores the record. */
+__global__ void __launch_bounds__(UPD_BLOCK) k_update_materials(const double *__restrict__ in, const uint32_t *__restrict__ flags, uint32_t n,
+                                                               const double *present, double *material, double *__restrict__ color_raw,
+                                                               unsigned long long *__restrict__ words)
+{
+  const uint32_t i = blockIdx.x * UPD_BLOCK + threadIdx.x;
+  double emit = 0.0;
+  unsigned long long refr = 0, chk = 0, glass2 = 0, bad = 0;
+  if (i < n)
+  {
+    double c[SCENE_MATERIAL_IN], m[PT_MAT_STRIDE];
+    for (int k = 0; k < SCENE_MATERIAL_IN; k++)
+      c[k] = in[SCENE_MATERIAL_IN * (size_t)i + k];
+    const uint32_t f = flags ? flags[i] : scene_material_flags(present + PT_MAT_STRIDE * (size_t)i);
+    if (material)
+    {
+      scene_material_record(f, c, c + 3, m);
+      for (int k = 0; k < PT_MAT_STRIDE; k++)
+        material[PT_MAT_STRIDE * (size_t)i + k] = m[k];
+      for (int k = 0; k < 3; k++)
+        color_raw[3 * (size_t)i + k] = c[k];
+    }
+    bad = scene_material_ok(c, c + 3) ? 0u : 1u;
+    emit = bad ? 0.0 : scene_material_emission_part(c + 3); /* (a refused update takes no scalar; a NaN has no key) */
+    const uint32_t cls = scene_material_class_part(f);
+    refr = (cls & SCENE_MATERIAL_REFRACT) ? 1u : 0u;
+    chk = (cls & SCENE_MATERIAL_CHECKER) ? 1u : 0u;
+    glass2 = (cls & SCENE_MATERIAL_MIRROR_GLASS) ? 1u : 0u;
+  }
+  if (!words)
+    return; /* the write run: the check run has reduced already (a kernel argument: the whole grid takes this way) */
+  const unsigned long long ke = wave_max(key_of(emit)), kr = wave_max(refr), kc = wave_max(chk), kg = wave_max(glass2), kb = wave_max(bad);
+  if ((threadIdx.x & 63) == 0)
+  {
+    atomicMax(&words[0], ke);
+    atomicMax(&words[1], kr);
+    atomicMax(&words[2], kc);
+    atomicMax(&words[3], kg);
+    atomicMax(&words[4], kb);
   }
 }
 
@@ -423,4 +474,43 @@ hipError_t scene_update_spheres_write(const double *spheres, uint32_t n, double 
   if (!spheres || !entry || !geom4 || n == 0)
     return hipErrorInvalidValue;
   return launch_update_spheres(spheres, n, entry, geom4, nullptr);
+}
+
+/* ---- the material half ---- */
+namespace
+{
+hipError_t launch_update_materials(const double *in, const uint32_t *flags, uint32_t n, const double *present, double *material,
+                                   double *color_raw, unsigned long long *words)
+{
+  if (words)
+  {
+    const unsigned long long h[SCENE_MATERIAL_WORDS] = {key_of(0.0), 0, 0, 0, 0};
+    UPD_TRY(hipMemcpy(words, h, sizeof h, hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL(k_update_materials, dim3((n + UPD_BLOCK - 1) / UPD_BLOCK), dim3(UPD_BLOCK), 0, nullptr, in, flags, n, present,
+                     material, color_raw, words);
+  return hipGetLastError();
+}
+} // namespace
+
+hipError_t scene_update_materials_check(const double *in, const uint32_t *flags, uint32_t n, const double *present,
+                                        unsigned long long *words, SceneMaterialBounds *out, bool *materials_ok)
+{
+  if (!in || !present || !words || !out || !materials_ok || n == 0)
+    return hipErrorInvalidValue;
+  UPD_TRY(launch_update_materials(in, flags, n, present, nullptr, nullptr, words));
+  unsigned long long h[SCENE_MATERIAL_WORDS];
+  UPD_TRY(hipMemcpy(h, words, sizeof h, hipMemcpyDeviceToHost));
+  *out = SceneMaterialBounds();
+  out->max_emission = double_of(h[0]);
+  out->classes = (h[1] ? SCENE_MATERIAL_REFRACT : 0u) | (h[2] ? SCENE_MATERIAL_CHECKER : 0u) | (h[3] ? SCENE_MATERIAL_MIRROR_GLASS : 0u);
+  *materials_ok = h[4] == 0;
+  return hipSuccess;
+}
+
+hipError_t scene_update_materials_write(const double *in, const uint32_t *flags, uint32_t n, double *material, double *color_raw)
+{
+  if (!in || !material || !color_raw || n == 0)
+    return hipErrorInvalidValue;
+  return launch_update_materials(in, flags, n, material, material, color_raw, nullptr);
 }

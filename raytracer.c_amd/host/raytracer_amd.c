@@ -107,6 +107,13 @@ void rt_set_scene_updates(int on)
   rt_hip_set_scene_updates(g_scene_updates);
 }
 int rt_get_scene_updates(void) { return g_scene_updates; }
+static int g_material_updates = 0;
+void rt_set_material_updates(int on)
+{
+  g_material_updates = on != 0;
+  rt_hip_set_material_updates(g_material_updates);
+}
+int rt_get_material_updates(void) { return g_material_updates; }
 static double g_bvh_rebuild_ratio = 0;
 void rt_set_bvh_rebuild_ratio(double max_ratio)
 {
@@ -385,26 +392,29 @@ static void kept_drop(void)
   memset(&g_kept, 0, sizeof g_kept);
 }
 
-/* does the call's scene equal the kept one but for sphere centres and radii and vertex positions? */
-static int kept_matches(const Object *objects, size_t n_objects, const MeshObject *meshes, size_t n_meshes)
+/* does the call's scene equal the kept one but for sphere centres and radii and vertex positions -- and, under
+ * rt_set_material_updates(1), flags, colours and emission (*recoloured says whether those differ)? */
+static int kept_matches(const Object *objects, size_t n_objects, const MeshObject *meshes, size_t n_meshes, int *recoloured)
 {
+  *recoloured = 0;
   if (!g_kept.scene || n_objects != g_kept.n_objects || n_meshes != g_kept.n_meshes)
     return 0;
   for (size_t i = 0; i < n_objects; i++)
     if (objects[i].flags != g_kept.objects[i].flags || memcmp(&objects[i].color, &g_kept.objects[i].color, sizeof(vec3)) != 0 ||
         memcmp(&objects[i].emission, &g_kept.objects[i].emission, sizeof(vec3)) != 0)
-      return 0;
+      *recoloured = 1;
   for (size_t m = 0; m < n_meshes; m++)
   {
     const MeshObject *a = &meshes[m], *b = &g_kept.meshes[m];
-    if (a->flags != b->flags || memcmp(&a->color, &b->color, sizeof(vec3)) != 0 || memcmp(&a->emission, &b->emission, sizeof(vec3)) != 0 ||
-        a->mesh.num_triangles != b->mesh.num_triangles)
+    if (a->flags != b->flags || memcmp(&a->color, &b->color, sizeof(vec3)) != 0 || memcmp(&a->emission, &b->emission, sizeof(vec3)) != 0)
+      *recoloured = 1;
+    if ((*recoloured && !g_material_updates) || a->mesh.num_triangles != b->mesh.num_triangles)
       return 0;
     for (size_t k = 0; k < 3 * (size_t)a->mesh.num_triangles; k++)
       if (memcmp(&a->mesh.vertices[k].tex, &b->mesh.vertices[k].tex, sizeof(vec2)) != 0)
         return 0;
   }
-  return 1;
+  return !*recoloured || g_material_updates;
 }
 
 /* deep copies of the call's scene into g_kept (the scene handle apart); 0 when out of memory */
@@ -429,8 +439,9 @@ static int kept_copy(const Object *objects, size_t n_objects, const MeshObject *
   return 1;
 }
 
-/* the kept scene takes the call's centres, radii and positions in place (rt_hip_scene_update_*_host), and so do the copies */
-static int kept_take(const Object *objects, size_t n_objects, const MeshObject *meshes, size_t n_meshes)
+/* the kept scene takes the call's centres, radii and positions in place (rt_hip_scene_update_*_host) -- where they differ
+ * (recoloured), its flags, colours and emission too (rt_hip_scene_update_materials_host) --, and so do the copies */
+static int kept_take(const Object *objects, size_t n_objects, const MeshObject *meshes, size_t n_meshes, int recoloured)
 {
   int rc = RT_HIP_OK;
   size_t n_tri = 0;
@@ -458,9 +469,32 @@ static int kept_take(const Object *objects, size_t n_objects, const MeshObject *
     rc = rt_hip_scene_update_vertices_host(g_kept.scene, pos, n_tri);
   }
   free(buf);
+  if (!rc && recoloured)
+  {
+    const size_t n = n_objects + n_meshes;
+    double *mat = (double *)malloc(sizeof(double) * 6 * n);
+    uint32_t *flags = (uint32_t *)malloc(sizeof(uint32_t) * n);
+    rc = mat && flags ? RT_HIP_OK : RT_HIP_ENOMEM;
+    for (size_t i = 0; !rc && i < n; i++)
+    {
+      memcpy(mat + 6 * i, i < n_objects ? &objects[i].color : &meshes[i - n_objects].color, sizeof(vec3));
+      memcpy(mat + 6 * i + 3, i < n_objects ? &objects[i].emission : &meshes[i - n_objects].emission, sizeof(vec3));
+      flags[i] = i < n_objects ? objects[i].flags : meshes[i - n_objects].flags;
+    }
+    if (!rc)
+      rc = rt_hip_scene_update_materials_host(g_kept.scene, mat, flags, n);
+    free(mat);
+    free(flags);
+  }
   if (!rc)
   {
     memcpy(g_kept.objects, objects, sizeof(Object) * n_objects);
+    for (size_t m = 0; m < n_meshes; m++)
+    {
+      g_kept.meshes[m].flags = meshes[m].flags;
+      g_kept.meshes[m].color = meshes[m].color;
+      g_kept.meshes[m].emission = meshes[m].emission;
+    }
     for (size_t m = 0; m < n_meshes; m++)
       memcpy(g_kept.meshes[m].mesh.vertices, meshes[m].mesh.vertices, sizeof(Vertex) * 3 * (size_t)meshes[m].mesh.num_triangles);
   }
@@ -472,8 +506,9 @@ static int kept_take(const Object *objects, size_t n_objects, const MeshObject *
 static int render_probe_following(uint8_t *framebuffer, float *linear_rgb, Object *objects, size_t n_objects, MeshObject *meshes,
                                   size_t n_meshes, const RtHipMesh *hm, Camera *camera, const RtHipParams *p, uint64_t *stats)
 {
-  int rc, same_scene = kept_matches(objects, n_objects, meshes, n_meshes);
-  if (same_scene && kept_take(objects, n_objects, meshes, n_meshes) != RT_HIP_OK)
+  int recoloured = 0;
+  int rc, same_scene = kept_matches(objects, n_objects, meshes, n_meshes, &recoloured);
+  if (same_scene && kept_take(objects, n_objects, meshes, n_meshes, recoloured) != RT_HIP_OK)
     same_scene = 0; /* (an update the scene refuses: start over) */
   if (!same_scene)
   {

@@ -231,6 +231,13 @@ SHIM_SYMBOLS = {
     "rt_hip_scene_read_spheres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_hip_scene_sphere_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_double * 8), C.POINTER(C.c_double * 8)]),
+    "rt_hip_scene_update_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rt_hip_scene_update_materials_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rt_hip_scene_read_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_hip_scene_material_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint32)]),
+    "rt_hip_scene_memory": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "rt_hip_set_material_updates": (None, [C.c_int]),
     "rt_hip_set_scene_updates": (None, [C.c_int]),
     "rt_hip_cache_updates": (C.c_uint64, []),
     "rt_hip_scene_bvh_cost": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
@@ -469,6 +476,8 @@ HOST_SYMBOLS = {
     "rt_get_bvh_builder": (C.c_int, []),
     "rt_set_scene_updates": (None, [C.c_int]),
     "rt_get_scene_updates": (C.c_int, []),
+    "rt_set_material_updates": (None, [C.c_int]),
+    "rt_get_material_updates": (C.c_int, []),
     "rt_set_bvh_rebuild_ratio": (None, [C.c_double]),
     "rt_get_bvh_rebuild_ratio": (C.c_double, []),
     "rt_set_devices": (None, [C.c_int]),

@@ -368,9 +368,78 @@ class GpuScene:
         return {"reach_spheres": reach.value, "max_center": mc.value, "wide_range": bool(wide.value), "n_big": nb.value,
                 "big_r": tuple(br), "big_c": tuple(bc)}
 
+    def materials(self):
+        """the scene's materials as they are now: (colors float64 (n, 3), emission float64 (n, 3), flags int32 (n,)) device
+        tensors, n = n_objects + n_meshes in the shim's numbering (spheres, then mesh m at n_objects + m) -- what the scene was
+        created from, or the last update_materials() made THROUGH THIS OBJECT.  Not to be written."""
+        if getattr(self, "_materials", None) is None:
+            sc = self.scene
+            things = [sc.objects[i] for i in range(sc.n_objects)] + [sc.meshes[m] for m in range(sc.n_meshes)]
+            a = np.array([o.color.tuple() + o.emission.tuple() for o in things], dtype=np.float64).reshape(-1, 6)
+            f = np.array([o.flags for o in things], dtype=np.int32).reshape(-1)
+            a, f = torch.from_numpy(a).to(self.dev), torch.from_numpy(f).to(self.dev)
+            self._materials = (a[:, :3].contiguous(), a[:, 3:].contiguous(), f)
+        return self._materials
+
+    def update_materials(self, colors=None, emission=None, flags=None):
+        """Changes the scene's materials in place (rt_hip.h, rt_hip_scene_update_materials): colors and emission of shape (n, 3),
+        n = n_objects + n_meshes -- spheres in object order, then mesh m at n_objects + m -- as float64 torch tensors on the
+        scene's device or numpy arrays; flags of shape (n,), int32 / uint32 (abi.M_*).  An omitted part keeps its current values
+        (flags: the scene's own records keep theirs).  With every part given as a tensor the device entry reads them where they
+        lie; otherwise the host entry stages them.  Synchronous.  Records, derived scalars, kernel names, frames, bytes and
+        counters equal a freshly created scene's; geometry, tables and every handle stay.  A Temporal or a Preview holds radiance
+        of the old materials: reset it after an update.  Open accumulations refuse the update.  self.scene keeps the materials the
+        scene was created from; materials() has the current ones.  (_update's body takes one array and one pointer; here up to three
+        parts, each given or kept, decide together which entry is taken, so the dispatch is this method's own.)"""
+        n = self.scene.n_objects + self.scene.n_meshes
+        col0, emi0, flg0 = self.materials()
+        parts = [col0 if colors is None else colors, emi0 if emission is None else emission]
+        for name, x in zip(("colors", "emission"), parts):
+            if isinstance(x, torch.Tensor) and x.dtype != torch.float64 or tuple(x.shape) != (n, 3):
+                raise ValueError(f"update_materials: {name} of shape {(n, 3)} (float64 where a tensor) are expected")
+        if flags is not None:
+            if (flags.dtype not in ((torch.int32, torch.uint32) if isinstance(flags, torch.Tensor) else (np.dtype(np.int32), np.dtype(np.uint32)))
+                    or tuple(flags.shape) != (n,)):
+                raise ValueError(f"update_materials: flags of shape {(n,)}, int32 or uint32, are expected")
+        if all(isinstance(x, torch.Tensor) for x in parts) and isinstance(flags, (torch.Tensor, type(None))):
+            # the device entry: one (n, 6) tensor of the two parts (a host tensor goes down all the same: the shim refuses it)
+            t = torch.cat([x.to(torch.float64) for x in parts], dim=1).contiguous()
+            f = None if flags is None else flags.contiguous()
+            for x in (t, f):
+                if x is not None and x.is_cuda:   # what produced it on torch's current stream must be done: the shim works on the null stream
+                    torch.cuda.current_stream(x.device).synchronize()
+            _check(self.shim.rt_hip_scene_update_materials(self.handle, _ptr(t), _ptr(f), n), "rt_hip_scene_update_materials")
+            new_f = flg0 if f is None else f.detach().view(torch.int32).clone().to(self.dev)
+        else:
+            host = [x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x for x in parts]
+            a = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64) for x in host], axis=1))
+            f = None if flags is None else np.ascontiguousarray(flags.detach().cpu().numpy() if isinstance(flags, torch.Tensor) else flags)
+            _check(self.shim.rt_hip_scene_update_materials_host(self.handle, a.ctypes.data, None if f is None else f.ctypes.data, n),
+                   "rt_hip_scene_update_materials_host")
+            t = torch.from_numpy(a).to(self.dev)
+            new_f = flg0 if f is None else torch.from_numpy(f.astype(np.int32)).to(self.dev)
+        self._materials = (t[:, :3].contiguous(), t[:, 3:].contiguous(), new_f)
+
+    def read_materials(self):
+        """for tests: dict of numpy arrays as the kernels read them -- material (n, 8: prob, albedo / prob, emission, the flags as
+        the bit pattern of column 7), color_raw (n, 3)"""
+        n = self.scene.n_objects + self.scene.n_meshes
+        out = dict(material=np.zeros((n, 8)), color_raw=np.zeros((n, 3)))
+        _check(self.shim.rt_hip_scene_read_materials(self.handle, *[out[k].ctypes.data if n else None for k in ("material", "color_raw")]),
+               "rt_hip_scene_read_materials")
+        return out
+
+    def material_bounds(self):
+        """for tests: what the scene derives from its materials -- {"max_emission", "any_refract", "any_checker",
+        "any_mirror_glass"}"""
+        e, r, c, g = C.c_double(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(self.shim.rt_hip_scene_material_bounds(self.handle, C.byref(e), C.byref(r), C.byref(c), C.byref(g)),
+               "rt_hip_scene_material_bounds")
+        return {"max_emission": e.value, "any_refract": bool(r.value), "any_checker": bool(c.value), "any_mirror_glass": bool(g.value)}
+
     def update_info(self):
-        """{"updates": how many update_vertices() and update_spheres() the scene has taken, "last_seconds": the host-clock time of
-        the last}"""
+        """{"updates": how many update_vertices(), update_spheres() and update_materials() the scene has taken, "last_seconds": the
+        host-clock time of the last}"""
         k, s = C.c_uint64(0), C.c_double(0)
         _check(self.shim.rt_hip_scene_update_info(self.handle, C.byref(k), C.byref(s)), "rt_hip_scene_update_info")
         return {"updates": k.value, "last_seconds": s.value}
